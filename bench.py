@@ -1,20 +1,25 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X ICP inner loop.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N
           --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...)
 
 N = 1 (BASELINE.json configs[1]): one synthetic 640x480 Kinect frame pair, 30 % valid pixels
 (~92k points per cloud), 20 fixed ICP iterations.  One "step" = one icpk_align call = 21 NN
 sweeps + 20 reduce / solve / transform iterations, clouds resident in HBM.  value = ICP
-iterations/s of that single pair; NN Mpoints/s and Gpairs/s are reported alongside.  The same
-line carries
-  roofline            the NN kernel that was timed against what can physically bind it: HBM bytes
+iterations/s of that single pair over exactly K timed steps; ms_per_step = their wall time / K;
+NN Mpoints/s and Gpairs/s are reported alongside.
+
+A plain run does only that: set-up, W warm-up steps, K timed steps, the outputs (--dump-outputs)
+and the line.  --full adds everything else, each figure from runs of its own after the timed
+steps:
+  roofline            the NN kernel against what can physically bind it: HBM bytes
                       per launch from the PMC counters (profiles/hbm_traffic.json, written by
                       tools/collect_counters.py from separate rocprofv3 --pmc passes) over the
-                      launch duration measured live with HIP events on the kernel's stream,
-                      vs 8 TB/s; plus the VALU-issue fraction from SQ_INSTS_VALU;
+                      launch duration measured live with HIP events on the kernel's stream
+                      (a profiled run of K more steps), vs 8 TB/s; plus the VALU-issue fraction
+                      from SQ_INSTS_VALU;
   roofline_algorithmic the brute-force scan's operand bytes (Nq*Nt*12 + Nq*20)
                       over the same duration -- a YARDSTICK, not traffic (the grid kernel
                       returns the brute-force result without touching those bytes);
@@ -24,13 +29,25 @@ line carries
                       100..163) through icpk_align_batch_device -- the number the N > 1 lines
                       scale against;
   extra               the dense 307 200-point pair (the metric string's "307k-pt") and config 5
-                      (10^6 x 10^6 points, 50 iterations).
+                      (10^6 x 10^6 points, 50 iterations);
+  stage_ms_per_step, roofline_bruteforce, pcie_inclusive_iter_s  per-stage device times, the
+                      brute-force kernel on the same sweep, the rate with host buffers.
 
 N > 1 (BASELINE.json configs[3], frame-batch mode): the SAME 64 pairs,
 block-partitioned 64/N per rank, one process per GPU, every rank aligns its block in lock-step
 groups on its GPU, no per-iteration collective; one RCCL all-gather of the results per step
 (icpk_comm_gather_results, RCCL behind the C ABI).  One step = the whole 64-pair batch; value =
-aggregate iterations/s; total work is fixed, so "scaling" is "strong".
+aggregate iterations/s; total work is fixed, so "scaling" is "strong".  --full adds the per-rank
+step times, the cross-rank consistency check, the roofline, the key-frame broadcast and the same
+batch on one GPU.
+
+--dump-outputs DIR: after the timed steps, what the timed path handed its caller in the last
+step, as DIR/<name>.npy (float32 / float64; integers as float64).  N = 1: transform (4, 4),
+stats (1, 4) = [iterations, status, pairs, mse], return_code (1,), and what the caller can read
+back from the context: aligned_source (3, Nq), nn_index / nn_distance (Nq,) of the last sweep.
+N > 1 (rank 0): the gathered transforms (n, 4, 4) and stats (n, 4); --shard queries: transform and
+stats of the one pair.  The inputs are fixed seeds: the same arguments give the same inputs in
+every run.
 """
 import argparse
 import gc
@@ -63,7 +80,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--blocks", type=int, default=5, help="N = 1: timed regions of --steps steps each; the median one is reported")
+    ap.add_argument("--blocks", type=int, default=1,
+                    help="N = 1: timed regions of --steps steps each; the median one is reported (default 1: exactly --steps "
+                         "timed steps)")
     ap.add_argument("--iters", type=int, default=20, help="fixed ICP iterations per alignment (config 2: 20)")
     ap.add_argument("--workload", default="kinect640x480_30pct",
                     choices=["kinect640x480_30pct", "kinect640x480_dense", "kinect_v2_512x424", "dense1m", "frustum10k"])
@@ -79,8 +98,15 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the frame_batch / dense / config-5 blocks at N = 1")
     ap.add_argument("--batch-pairs", type=int, default=BATCH_PAIRS)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (CPU baseline, roofline, frame batch, extra workloads, "
+                         "frame path; N > 1: per-rank times, consistency check, single-GPU reference, broadcast)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.blocks < 1:
+        ap.error("--steps and --blocks must be >= 1, --warmup >= 0")
+    return args
 
 
 def make_workload(name, seed):
@@ -340,18 +366,20 @@ def set_clouds_device(ctx, src_d, tgt_d):
     ctx.set_source_device(src_d.data_ptr(), src_d.data_ptr() + nq * es, src_d.data_ptr() + 2 * nq * es, nq)
 
 
-def timed_alignments(torch, ctx, params, steps, warmup, sync_all, blocks=1):
+def timed_alignments(torch, ctx, params, steps, warmup, sync_all, blocks=1, profile=True):
     """W untimed, then `blocks` timed regions of exactly K steps each, every region bracketed by sync_all(); a step =
     icpk_reset_source (the pair back at its initial pose: three stream-ordered device copies, inside the timed region) +
-    icpk_align.  One NN launch per alignment (the position rotating over its sweeps) is bracketed by two HIP events on
-    the context's stream.  Returns the MEDIAN block's (elapsed, iterations, launches) -- one scheduler hiccup cannot
-    move the number -- plus the event totals over all blocks and every block's elapsed time."""
+    icpk_align.  profile: one NN launch per alignment (the position rotating over its sweeps) is bracketed by two HIP
+    events on the context's stream.  Returns the MEDIAN block's (elapsed, iterations, launches) -- one scheduler hiccup
+    cannot move the number -- plus the event totals over all blocks and every block's elapsed time.  The last step's
+    (T, stats, rc) is left in timed_alignments.last_result."""
     params.profile = 0
     for _ in range(warmup):
         ctx.reset_source()
         ctx.align(params)
-    params.profile = 1
-    params.profile_stride = params.max_iterations + 1
+    if profile:
+        params.profile = 1
+        params.profile_stride = params.max_iterations + 1
     gc.collect()
     gc.disable()  # a generation-2 collection of the interpreter (tens of ms) must not land in a timed region
     nn_ms = 0.0
@@ -371,9 +399,24 @@ def timed_alignments(torch, ctx, params, steps, warmup, sync_all, blocks=1):
         sync_all()
         per_block.append((time.perf_counter() - t0, iters_done, nn_launches))
     gc.enable()
+    params.profile = 0
     elapsed, iters_done, nn_launches = sorted(per_block)[len(per_block) // 2]
     timed_alignments.last_blocks = [round(b[0] * 1e3, 4) for b in per_block]
+    timed_alignments.last_result = (T, st, rc)
     return elapsed, iters_done, nn_launches, nn_timed, nn_ms
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 kept, everything else as float64 (exact for the
+    int32 indices and counts), 64 MB at most in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+        total += a.nbytes
+        assert total <= 64 << 20, f"--dump-outputs: more than 64 MB ({name})"
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def batch_pairs_on_device(torch, dev, indices):
@@ -414,19 +457,17 @@ def bench_single(args, torch, dev, gpu_index):
     def sync_all():
         torch.cuda.synchronize()
 
-    elapsed, iters_done, nn_launches, nn_timed, nn_ms = timed_alignments(torch, ctx, params, args.steps, args.warmup, sync_all,
-                                                                         blocks=args.blocks)
+    # the headline: the K timed steps carry no profiling events (the roofline below takes a run of its own)
+    elapsed, iters_done, nn_launches, _, _ = timed_alignments(torch, ctx, params, args.steps, args.warmup, sync_all,
+                                                              blocks=args.blocks, profile=False)
     block_ms = list(timed_alignments.last_blocks)
-    avg_nn_s = nn_ms / max(nn_timed, 1) / 1e3
-    timing = (f"two HIP events on the kernel's own stream around one K1 launch per alignment of the timed regions, the "
-              f"position rotating over the {args.iters + 1} sweeps ({nn_timed} of {nn_launches * args.blocks} launches; includes ~4 us of "
-              "event/dispatch latency; the rocprofv3 --kernel-trace average of the same command is in profiles/)")
-    phys, yard = roofline_blocks(args.workload, args.nn_mode, nq, nt, avg_nn_s, timing, KERNEL_NAMES[args.nn_mode])
-    # per-stage device times from one extra, untimed alignment (events around every stage)
-    params.profile = 2
-    _, st2, _ = ctx.align(params)
-    stage_ms = {"nn": st2.nn_ms_total, "reduce": st2.reduce_ms_total, "transform": st2.transform_ms_total, "total": st2.total_ms}
-    params.profile = 0
+    if args.dump_outputs:  # before anything else runs on the context: the state the last timed step left
+        from icp_slam_prototype_amd import batch
+
+        T, st, rc = timed_alignments.last_result
+        idx, dist = ctx.get_associations()
+        dump_outputs(args.dump_outputs, {"transform": T, "stats": batch.stats_rows([st]), "return_code": [rc],
+                                         "aligned_source": ctx.get_source(), "nn_index": idx, "nn_distance": dist})
     out = {
         "metric": METRIC, "value": iters_done / elapsed, "unit": "iter/s", "n_gpus": 1, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
@@ -435,12 +476,29 @@ def bench_single(args, torch, dev, gpu_index):
                          "reported": "the median block: value = its iterations / its wall time, ms_per_step = its wall time / K"},
         "config": {"workload": f"{args.workload}: ONE frame pair, {nq} source x {nt} target points, {args.iters} fixed ICP "
                                f"iterations per step from the pair's initial pose, solve={args.solve}, nn={args.nn_mode} (BASELINE configs[1]); the "
-                               f"N > 1 lines run configs[3] (64 such pairs) and scale against frame_batch below",
+                               f"N > 1 lines run configs[3] (64 such pairs) and scale against frame_batch (--full)",
                    "frame_pairs_per_step": 1, "parallelism": "1 GPU"},
         "nn_mpoints_per_s": nn_launches * nq / elapsed / 1e6,
         "nn_gpairs_per_s_wall": float(nn_launches) * nq * nt / elapsed / 1e9,
-        "roofline": phys, "roofline_algorithmic": yard, "stage_ms_per_step": stage_ms,
     }
+    if not args.full:
+        ctx.close()
+        print(json.dumps(out))
+        return
+    # the NN kernel's launch time for the roofline: K more steps, one NN launch per alignment bracketed by events
+    _, _, p_launches, nn_timed, nn_ms = timed_alignments(torch, ctx, params, args.steps, 0, sync_all, profile=True)
+    avg_nn_s = nn_ms / max(nn_timed, 1) / 1e3
+    timing = (f"two HIP events on the kernel's own stream around one K1 launch per alignment of a profiled run of {args.steps} "
+              f"steps after the timed ones, the position rotating over the {args.iters + 1} sweeps ({nn_timed} of {p_launches} "
+              "launches; includes ~4 us of event/dispatch latency; the rocprofv3 --kernel-trace average of the same command is "
+              "in profiles/)")
+    phys, yard = roofline_blocks(args.workload, args.nn_mode, nq, nt, avg_nn_s, timing, KERNEL_NAMES[args.nn_mode])
+    # per-stage device times from one extra, untimed alignment (events around every stage)
+    params.profile = 2
+    _, st2, _ = ctx.align(params)
+    stage_ms = {"nn": st2.nn_ms_total, "reduce": st2.reduce_ms_total, "transform": st2.transform_ms_total, "total": st2.total_ms}
+    params.profile = 0
+    out.update({"roofline": phys, "roofline_algorithmic": yard, "stage_ms_per_step": stage_ms})
     if args.nn_mode in ("pruned", "grid"):
         # the same sweep by the brute-force (un-pruned) filtered kernel north_star names: every one
         # of the Nq*Nt pairs is evaluated; HIP events on the context's stream around each launch
@@ -753,68 +811,70 @@ def bench_frame_batch(args, torch, dist, rank, world, dev, cdev, gpu_index, rehe
     tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     elapsed = float(tt.item())
-    # per-rank step times (mean over the timed steps), so that the spread between ranks is readable from the one line
-    mine = torch.tensor([statistics.mean(t_align) * 1e3, statistics.mean(t_gather) * 1e3], dtype=torch.float64, device=cdev)
-    per_rank = [torch.zeros_like(mine) for _ in range(world)]
-    dist.all_gather(per_rank, mine)
-    per_rank = [[round(float(v), 4) for v in t.cpu()] for t in per_rank]
-    # every rank holds the same gathered result, every pair ran its 20 iterations
-    chk = torch.tensor(np.concatenate([Tg.reshape(-1), Sg.reshape(-1)]).astype(np.float64), device=cdev)
-    lo, hi = chk.clone(), chk.clone()
-    dist.all_reduce(lo, op=dist.ReduceOp.MIN)
-    dist.all_reduce(hi, op=dist.ReduceOp.MAX)
-    consistent = bool(torch.equal(lo, hi)) and rc == 0 and bool((Sg[:, 0] == args.iters).all()) and bool((Sg[:, 1] == 0).all())
-    roof = None
-    try:  # (auxiliary: never let it cost the line) one more call with a bracketed NN launch per group
-        params.profile = 1
-        prof = [ctx.align_batch_device(pargs, params)[1] for _ in range(6)]
-        params.profile = 0
-        roof = batch_roofline(prof, int(os.environ.get("ICPK_BATCH_GROUP", "16")))
-    except Exception as e:  # noqa: BLE001
-        roof = {"error": repr(e)}
-    # key-frame broadcast (north_star: RCCL broadcast of the target cloud over xGMI), untimed
-    # part of the run: rank 0's first target becomes every rank's target; median of 5
-    bcast_ms = bcast_err = None
-    nt0 = 0
-    if isinstance(comm, batch.RcclComm):
-        try:  # auxiliary: never let it cost the line
-            t_h = keep[0][1].cpu().numpy() if count else np.zeros((3, 1), np.float32)
-            if rank == 0:
-                ctx.set_target(t_h)
-            ts = []
-            for _ in range(5):
-                sync_all()
-                tb = time.perf_counter()
-                comm.broadcast_target(0)
-                ts.append((time.perf_counter() - tb) * 1e3)
-            bcast_ms = statistics.median(ts)
-            nt0 = ctx.target_size
+    if args.dump_outputs and rank == 0:  # every rank holds the same gathered results
+        dump_outputs(args.dump_outputs, {"transforms": Tg, "stats": Sg})
+    if args.full:
+        # per-rank step times (mean over the timed steps), so that the spread between ranks is readable from the one line
+        mine = torch.tensor([statistics.mean(t_align) * 1e3, statistics.mean(t_gather) * 1e3], dtype=torch.float64, device=cdev)
+        per_rank = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(per_rank, mine)
+        per_rank = [[round(float(v), 4) for v in t.cpu()] for t in per_rank]
+        # every rank holds the same gathered result, every pair ran its 20 iterations
+        chk = torch.tensor(np.concatenate([Tg.reshape(-1), Sg.reshape(-1)]).astype(np.float64), device=cdev)
+        lo, hi = chk.clone(), chk.clone()
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+        dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+        consistent = bool(torch.equal(lo, hi)) and rc == 0 and bool((Sg[:, 0] == args.iters).all()) and bool((Sg[:, 1] == 0).all())
+        roof = None
+        try:  # (auxiliary: never let it cost the line) one more call with a bracketed NN launch per group
+            params.profile = 1
+            prof = [ctx.align_batch_device(pargs, params)[1] for _ in range(6)]
+            params.profile = 0
+            roof = batch_roofline(prof, int(os.environ.get("ICPK_BATCH_GROUP", "16")))
         except Exception as e:  # noqa: BLE001
-            bcast_err = repr(e)
-    # the SAME batch on ONE GPU (rank 0's), outside the timed region: the reference the N-GPU value scales against
-    single = None
-    try:
-        if rank == 0:
-            keep1, pargs1 = batch_pairs_on_device(torch, dev, range(n_pairs))
-            for _ in range(2):
-                ctx.align_batch_device(pargs1, params)
-            each = []
-            for _ in range(5):
-                torch.cuda.synchronize()
-                tb = time.perf_counter()
-                _, st1, _ = ctx.align_batch_device(pargs1, params)
-                torch.cuda.synchronize()
-                each.append(time.perf_counter() - tb)
-            d1 = statistics.median(each)
-            single = {"ms_per_batch": d1 * 1e3, "value": sum(x.iterations for x in st1) / d1, "unit": "iter/s",
-                      "timing": "median of 5 calls of icpk_align_batch_device on rank 0's GPU, the other ranks idle"}
-            del keep1
-    except Exception as e:  # noqa: BLE001 -- auxiliary: never let it cost the line
-        single = {"error": repr(e)}
+            roof = {"error": repr(e)}
+        # key-frame broadcast (north_star: RCCL broadcast of the target cloud over xGMI), untimed
+        # part of the run: rank 0's first target becomes every rank's target; median of 5
+        bcast_ms = bcast_err = None
+        nt0 = 0
+        if isinstance(comm, batch.RcclComm):
+            try:  # auxiliary: never let it cost the line
+                t_h = keep[0][1].cpu().numpy() if count else np.zeros((3, 1), np.float32)
+                if rank == 0:
+                    ctx.set_target(t_h)
+                ts = []
+                for _ in range(5):
+                    sync_all()
+                    tb = time.perf_counter()
+                    comm.broadcast_target(0)
+                    ts.append((time.perf_counter() - tb) * 1e3)
+                bcast_ms = statistics.median(ts)
+                nt0 = ctx.target_size
+            except Exception as e:  # noqa: BLE001
+                bcast_err = repr(e)
+        # the SAME batch on ONE GPU (rank 0's), outside the timed region: the reference the N-GPU value scales against
+        single = None
+        try:
+            if rank == 0:
+                keep1, pargs1 = batch_pairs_on_device(torch, dev, range(n_pairs))
+                for _ in range(2):
+                    ctx.align_batch_device(pargs1, params)
+                each = []
+                for _ in range(5):
+                    torch.cuda.synchronize()
+                    tb = time.perf_counter()
+                    _, st1, _ = ctx.align_batch_device(pargs1, params)
+                    torch.cuda.synchronize()
+                    each.append(time.perf_counter() - tb)
+                d1 = statistics.median(each)
+                single = {"ms_per_batch": d1 * 1e3, "value": sum(x.iterations for x in st1) / d1, "unit": "iter/s",
+                          "timing": "median of 5 calls of icpk_align_batch_device on rank 0's GPU, the other ranks idle"}
+                del keep1
+        except Exception as e:  # noqa: BLE001 -- auxiliary: never let it cost the line
+            single = {"error": repr(e)}
     dist.barrier()
     if rank == 0:
         total_iters = float(Sg[:, 0].sum()) * args.steps
-        al = [r[0] for r in per_rank]
         out = {
             "metric": METRIC, "value": total_iters / elapsed, "unit": "iter/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
@@ -825,18 +885,22 @@ def bench_frame_batch(args, torch, dist, rank, world, dev, cdev, gpu_index, rehe
                        "frame_pairs_per_step": n_pairs, "pairs_per_gpu": count,
                        "parallelism": f"frame-batch x{world}: block partition, no per-iteration collective, one all-gather "
                                       f"of the results per step"},
-            "roofline": roof,
-            "per_rank_ms_per_step": {"align_batch_device": al, "gather_results_incl_wait": [r[1] for r in per_rank],
-                                     "align_min": min(al), "align_max": max(al)},
-            "single_gpu_reference": single,
-            "speedup_vs_single_gpu": (total_iters / elapsed / single["value"]) if single and "value" in single else None,
             "collectives": comm.kind, "collectives_fallback_reason": comm_err,
-            "results_consistent_on_all_ranks": consistent,
-            "keyframe_broadcast_ms": bcast_ms, "keyframe_broadcast_error": bcast_err,
-            "keyframe_broadcast_bytes": (3 * 4 * nt0) if bcast_ms is not None else None,
             "note": "N = 1 of this bench reports the single-pair configs[1] rate as `value` and this same 64-pair batch on "
-                    "one GPU as `frame_batch.value`: scale the N > 1 lines against the latter",
+                    "one GPU as `frame_batch.value` (--full): scale the N > 1 lines against the latter",
         }
+        if args.full:
+            al = [r[0] for r in per_rank]
+            out.update({
+                "roofline": roof,
+                "per_rank_ms_per_step": {"align_batch_device": al, "gather_results_incl_wait": [r[1] for r in per_rank],
+                                         "align_min": min(al), "align_max": max(al)},
+                "single_gpu_reference": single,
+                "speedup_vs_single_gpu": (total_iters / elapsed / single["value"]) if single and "value" in single else None,
+                "results_consistent_on_all_ranks": consistent,
+                "keyframe_broadcast_ms": bcast_ms, "keyframe_broadcast_error": bcast_err,
+                "keyframe_broadcast_bytes": (3 * 4 * nt0) if bcast_ms is not None else None,
+            })
         print(json.dumps(out))
     if isinstance(comm, batch.RcclComm):
         comm.close()
@@ -908,13 +972,17 @@ def bench_query_sharded(args, torch, dist, rank, world, dev, cdev, gpu_index, re
     t0 = time.perf_counter()
     iters = 0
     for _ in range(args.steps):
-        iters += one_step()[1]
+        last = one_step()
+        iters += last[1]
     torch.cuda.synchronize()
     dist.barrier()
     torch.cuda.synchronize()
     tt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=cdev)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:  # (T, iterations, pairs, mse, status), identical on every rank
+        T, it, pairs, mse, status = last
+        dump_outputs(args.dump_outputs, {"transform": T, "stats": np.array([[it, status, pairs, mse]], np.float64)})
     if rank == 0:
         print(json.dumps({
             "metric": METRIC, "value": iters / elapsed, "unit": "iter/s", "n_gpus": world, "steps": args.steps,
@@ -945,7 +1013,8 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: N > 1 must be launched with one process per GPU "
                          f"(python -m torch.distributed.run --nnodes=1 --nproc-per-node {args.gpus} ... bench.py --gpus {args.gpus})")
 
-    if world == 1 and not args.no_extras and args.workload == "kinect640x480_30pct" and args.solve == "reference" and args.nn_mode == "grid":
+    if (world == 1 and args.full and not args.no_extras and args.workload == "kinect640x480_30pct" and args.solve == "reference"
+            and args.nn_mode == "grid"):
         # the frame path from a C++ caller, measured while nothing else holds the GPU (see tracker_path)
         global _NATIVE_TRACKER
         try:

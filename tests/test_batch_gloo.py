@@ -56,7 +56,8 @@ def _worker(rank, world, port, n_frames, q):
 
 @pytest.mark.parametrize("n_frames", [5, 4])
 def test_frame_batch_two_ranks_matches_serial(n_frames, oracle):
-    import torch.multiprocessing as mp
+    import multiprocessing as mp  # not torch.multiprocessing: importing torch here would load its own HIP runtime into
+    # the pytest process beside the one libicpk.so bound, and later GPU tests would see two runtimes (no device)
 
     from icp_slam_prototype_amd import synth
 
@@ -119,7 +120,8 @@ def _pair_worker(rank, world, port, n_pairs, q):
 
 @pytest.mark.parametrize("n_pairs", [6, 5, 1])
 def test_pair_batch_two_ranks_matches_serial(n_pairs, oracle):
-    import torch.multiprocessing as mp
+    import multiprocessing as mp  # not torch.multiprocessing: importing torch here would load its own HIP runtime into
+    # the pytest process beside the one libicpk.so bound, and later GPU tests would see two runtimes (no device)
 
     from icp_slam_prototype_amd import synth
 
@@ -216,7 +218,8 @@ def test_query_sharded_too_few_pairs_fallback(oracle):
 def test_query_sharded_alignment_two_ranks(solve, oracle):
     """One pair, queries split over 2 ranks, one all-reduce of the 19 sums per iteration:
     same transform as the single-process loop up to the summation order across ranks."""
-    import torch.multiprocessing as mp
+    import multiprocessing as mp  # not torch.multiprocessing: importing torch here would load its own HIP runtime into
+    # the pytest process beside the one libicpk.so bound, and later GPU tests would see two runtimes (no device)
 
     from icp_slam_prototype_amd import synth
 

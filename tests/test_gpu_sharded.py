@@ -35,7 +35,8 @@ def _worker(rank, world, port, solve, q):
 
 @pytest.mark.parametrize("solve", [0, 1])
 def test_query_sharded_matches_single_context(solve):
-    import torch.multiprocessing as mp
+    import multiprocessing as mp  # not torch.multiprocessing: importing torch here would load its own HIP runtime into
+    # the pytest process beside the one libicpk.so bound, and later GPU tests would see two runtimes (no device)
 
     from icp_slam_prototype_amd import binding, synth
 
