@@ -40,7 +40,19 @@ SYMBOLS = [
     "icpk_comm_unique_id", "icpk_comm_init_rccl", "icpk_comm_destroy", "icpk_comm_rank", "icpk_comm_world",
     "icpk_comm_partition", "icpk_comm_broadcast_target", "icpk_comm_gather_results", "icpk_comm_allreduce_sums",
     "icpk_comm_barrier", "icpk_align_query_sharded",
+    "icpk_map_reset", "icpk_map_release", "icpk_map_update", "icpk_map_update_points", "icpk_map_set_points",
+    "icpk_map_size", "icpk_map_get_list", "icpk_map_get_certainty", "icpk_map_query", "icpk_map_list_to_target",
+    "icpk_map_voxel", "icpk_align_to_map",
 ]
+
+# voxel certainty map (map.hpp:9-13)
+MAP_HEIGHT = 300
+MAP_CELLS = MAP_HEIGHT ** 3
+MAP_MAX_CONFIDENCE = 180
+MAP_DELTA_CONFIDENCE = 25
+MAP_KEYPOINTS, MAP_POINTS = 0, 1
+MAP_FROM_SOURCE, MAP_FROM_TARGET = 0, 1
+MAP_ADD_CLOUD, MAP_ADD_ASSOCIATED, MAP_ADD_UNASSOCIATED = 0, 1, 2
 
 
 class Params(C.Structure):
@@ -184,6 +196,20 @@ def load():
     lib.icpk_comm_allreduce_sums.argtypes = [C.c_void_p, dp, C.c_int32, C.POINTER(C.c_int64)]
     lib.icpk_comm_barrier.argtypes = [C.c_void_p]
     lib.icpk_align_query_sharded.argtypes = [C.c_void_p, C.POINTER(Params), fp, C.POINTER(Stats)]
+    u8 = C.POINTER(C.c_uint8)
+    lib.icpk_map_reset.argtypes = [C.c_void_p]
+    lib.icpk_map_release.argtypes = [C.c_void_p]
+    lib.icpk_map_update.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32]
+    lib.icpk_map_update_points.argtypes = [C.c_void_p, C.c_int32, fp, fp, fp, C.c_int32, C.c_int32]
+    lib.icpk_map_set_points.argtypes = [C.c_void_p, C.c_int32]
+    lib.icpk_map_size.argtypes = [C.c_void_p, C.c_int32]
+    lib.icpk_map_get_list.argtypes = [C.c_void_p, C.c_int32, fp, fp, fp]
+    lib.icpk_map_get_certainty.argtypes = [C.c_void_p, u8]
+    lib.icpk_map_query.argtypes = [C.c_void_p, fp, fp, fp, C.c_int32, u8, u8, ip, ip]
+    lib.icpk_map_list_to_target.argtypes = [C.c_void_p, C.c_int32]
+    lib.icpk_map_voxel.argtypes = [fp, ip]
+    lib.icpk_map_voxel.restype = None
+    lib.icpk_align_to_map.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, fp, C.POINTER(Stats)]
     _lib = lib
     return lib
 
@@ -235,6 +261,14 @@ def backproject_keypoints(depth, kp_xy, fx=468.60, cx=318.27):
     if m < 0:
         raise IcpkError(m, "icpk_backproject_keypoints")
     return np.ascontiguousarray(out[:m].T), kept[:m].copy()
+
+
+def map_voxel(p):
+    """map.cpp:55-85 getVoxelCoordinates on the host: (3,) point -> (3,) int32 voxel."""
+    p = _f(p).reshape(3)
+    v = np.zeros(3, np.int32)
+    load().icpk_map_voxel(_fp(p), v.ctypes.data_as(C.POINTER(C.c_int32)))
+    return v
 
 
 def make_rotation_matrix(x, y, z):
@@ -541,6 +575,69 @@ class Context:
         T = np.zeros(16, np.float32)
         st = Stats()
         rc = self._chk(self._lib.icpk_align(self._h, C.byref(p), _fp(T), C.byref(st)))
+        return T.reshape(4, 4), st, rc
+
+    # -- voxel certainty map (map.hpp / map.cpp) --------------------------------
+    def map_reset(self):
+        self._chk(self._lib.icpk_map_reset(self._h))
+
+    def map_release(self):
+        self._chk(self._lib.icpk_map_release(self._h))
+
+    def map_update(self, rule, delta, from_=MAP_FROM_SOURCE, indices=None):
+        """rule ICPK_MAP_ADD_* over the context's source / target (indices: list applied in order, None: all)."""
+        if indices is None:
+            return self._chk(self._lib.icpk_map_update(self._h, rule, from_, None, 0, delta))
+        idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        return self._chk(self._lib.icpk_map_update(self._h, rule, from_, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   idx.size, delta))
+
+    def map_update_points(self, rule, pts, delta):
+        x, y, z = (_f(pts[k]) for k in range(3))
+        return self._chk(self._lib.icpk_map_update_points(self._h, rule, _fp(x), _fp(y), _fp(z), x.size, delta))
+
+    def map_set_points(self, from_=MAP_FROM_TARGET):
+        self._chk(self._lib.icpk_map_set_points(self._h, from_))
+
+    def map_size(self, lst):
+        return self._chk(self._lib.icpk_map_size(self._h, lst))
+
+    def map_get_list(self, lst):
+        n = self.map_size(lst)
+        out = np.empty((3, n), np.float32)
+        self._chk(self._lib.icpk_map_get_list(self._h, lst, _fp(out[0]), _fp(out[1]), _fp(out[2])))
+        return out
+
+    def map_get_certainty(self):
+        """the whole grid, (300, 300, 300) uint8 indexed [x, y, z]"""
+        out = np.empty(MAP_CELLS, np.uint8)
+        self._chk(self._lib.icpk_map_get_certainty(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out.reshape(MAP_HEIGHT, MAP_HEIGHT, MAP_HEIGHT)
+
+    def map_query(self, pts):
+        """per point: (certainty uint8, occupied uint8, slot list int32, slot index int32); -1, -1 = empty slot"""
+        x, y, z = (_f(pts[k]) for k in range(3))
+        n = x.size
+        cert = np.zeros(n, np.uint8)
+        occ = np.zeros(n, np.uint8)
+        sl = np.zeros(n, np.int32)
+        si = np.zeros(n, np.int32)
+        u8 = C.POINTER(C.c_uint8)
+        ip = C.POINTER(C.c_int32)
+        self._chk(self._lib.icpk_map_query(self._h, _fp(x), _fp(y), _fp(z), n, cert.ctypes.data_as(u8),
+                                           occ.ctypes.data_as(u8), sl.ctypes.data_as(ip), si.ctypes.data_as(ip)))
+        return cert, occ, sl, si
+
+    def map_list_to_target(self, lst):
+        self._chk(self._lib.icpk_map_list_to_target(self._h, lst))
+
+    def align_to_map(self, params=None, delta=MAP_DELTA_CONFIDENCE, **kw):
+        """icp.cpp:98-271 against the map: the context's source vs the map's key points (the context's target is
+        replaced), then the rejected key points of every sweep through ADD_UNASSOCIATED.  Returns (T, stats, rc)."""
+        p = params if params is not None else default_params(**kw)
+        T = np.zeros(16, np.float32)
+        st = Stats()
+        rc = self._chk(self._lib.icpk_align_to_map(self._h, C.byref(p), delta, _fp(T), C.byref(st)))
         return T.reshape(4, 4), st, rc
 
     def align_query_sharded(self, params=None, **kw):

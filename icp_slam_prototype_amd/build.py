@@ -11,7 +11,8 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libicpk.so")
 
 SOURCES = ["icpk_api.cpp", "icpk_comm.cpp", "kernels_nn.hip", "kernels_reduce.hip", "kernels_transform.hip",
-           "kernels_backproject.hip", "kernels_sort.hip", "kernels_nn_pruned.hip", "kernels_loop.hip", "kernels_grid.hip", "kernels_frontend.hip"]
+           "kernels_backproject.hip", "kernels_sort.hip", "kernels_nn_pruned.hip", "kernels_loop.hip", "kernels_grid.hip", "kernels_frontend.hip",
+           "icpk_map.cpp", "kernels_map.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -79,6 +80,23 @@ def build_tracker_bench(force=False):
     return TRACKER_BENCH
 
 
+MAP_TEST = os.path.join(LIBDIR, "test_map_tracker")
+
+
+def build_map_test(force=False):
+    """Host-only C++ program over icp_align.hpp's icp::Map / icp::MapTracker (g++, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_map_tracker.cpp")
+    hdrs = [os.path.join(HERE, "include", h) for h in ("icp_align.hpp", "icp_map.hpp")]
+    build()
+    newest = max(os.path.getmtime(p) for p in [src, LIB] + hdrs)
+    if not force and os.path.exists(MAP_TEST) and os.path.getmtime(MAP_TEST) >= newest:
+        return MAP_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", MAP_TEST])
+    return MAP_TEST
+
+
 FAKE_RCCL = os.path.join(LIBDIR, "libfake_rccl.so")
 
 
@@ -99,3 +117,4 @@ if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_cpp_test(force="--force" in sys.argv))
     print(build_tracker_bench(force="--force" in sys.argv))
+    print(build_map_test(force="--force" in sys.argv))

@@ -743,6 +743,7 @@ float mse_from(const double* sums, int64_t n) {
 }  // namespace
 
 int icpk_host_fail(icpk_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg); }
+int icpk_host_ensure_unpacked(icpk_ctx* ctx) { return ensure_unpacked(ctx); }
 int icpk_host_ensure_cloud(icpk_ctx* ctx, icpk::Cloud& c, int n) { return ensure_cloud(ctx, c, n); }
 int icpk_host_target_replaced(icpk_ctx* ctx) {
   Cloud& c = ctx->tgt;
@@ -959,6 +960,7 @@ void icpk_destroy(icpk_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   icpk_comm_release(ctx);
+  icpk_map_free(ctx);
   for (icpk_ctx* sl : ctx->slots) icpk_destroy(sl);
   ctx->slots.clear();
   for (hipStream_t st : {ctx->setup_stream[0], ctx->setup_stream[1]})

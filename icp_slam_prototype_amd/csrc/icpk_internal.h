@@ -431,4 +431,42 @@ void launch_grid_tscatter_batch(const SetupBatchOf<TscatterArgs>& b, int count, 
 void launch_grid_qscatter_batch(const SetupBatchOf<QscatterArgs>& b, int count, hipStream_t s);
 void launch_grid_tqscatter(const TscatterArgs& t, const QscatterArgs& q, hipStream_t s);
 
+// kernels_map.hip -- the voxel certainty map (map.hpp, map.cpp)
+constexpr int MAP_DIM = 300;                              // map.hpp:9 MAP_HEIGHT
+constexpr int MAP_CELLS = MAP_DIM * MAP_DIM * MAP_DIM;    // keys < 2^25
+constexpr int MAP_TILE = 1024;                            // items per workgroup of the sort / compaction kernels
+constexpr int MAP_RADIX_BITS = 9;
+constexpr int MAP_RADIX = 1 << MAP_RADIX_BITS;
+constexpr int MAP_PASSES = 3;                             // 27 bits >= 25
+static_assert((1 << (MAP_RADIX_BITS * MAP_PASSES)) >= MAP_CELLS, "radix passes must cover every voxel key");
+struct MapPoints {  // batch element i = point idx[i] of the planes (idx == nullptr: point i)
+  const float* x;
+  const float* y;
+  const float* z;
+  const int* idx;
+  int n;
+};
+struct MapBuffers {  // batch-sized scratch of an update (n entries each unless noted)
+  int* key;          // voxel keys in input order
+  int* ka;
+  int* kb;
+  int* va;
+  int* vb;
+  int* hist;         // MAP_RADIX x tiles
+  int* flag;
+  int* tcount;       // tiles + 1
+  int* total;        // 1: entries appended by the update / rejected positions found
+};
+void launch_map_update(const MapPoints& p, int rule, int delta, int old_len, int list, float* lx, float* ly, float* lz,
+                       uint8_t* cert, int* slot, const MapBuffers& b, hipStream_t s);
+// out[i] = certainty, out[n + i] = slot of point i's voxel
+void launch_map_query(const float* x, const float* y, const float* z, int n, const uint8_t* cert, const int* slot,
+                      int* out, hipStream_t s);
+// the rejected positions of nsw association sweeps of ns source points (motion[s]: the transform after sweep s) against
+// nt map key points, compacted into ox / oy / oz in (sweep, query) order; *b.total = their number.  px / py / pz:
+// ns x nsw scratch; b sized for ns x nsw entries.
+void launch_map_rejected(const float* x, const float* y, const float* z, int ns, const Rt* motion, int nsw, float* px,
+                         float* py, float* pz, const float* tx, const float* ty, const float* tz, int nt,
+                         float max_dist, float* ox, float* oy, float* oz, const MapBuffers& b, hipStream_t s);
+
 }  // namespace icpk

@@ -1,0 +1,439 @@
+// icpk_map.cpp -- host side of the voxel certainty map (map.hpp, map.cpp; icpk_map_* in include/icpk.h).
+//
+// The grid (uint8 certainty), the slots (int32: (list index << 1) | list, -1 = empty) and the two point lists live in
+// HBM next to the context's clouds.  An update is 12 launches (kernels_map.hip) and ONE host wait, for the number of
+// points it appended; the lists grow on the device with capacity doubling.  The host keeps the list lengths.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "icpk.h"
+#include "icpk_ctx.h"
+#include "icpk_internal.h"
+#include "solve_impl.h"
+
+using namespace icpk;
+
+struct icpk_map_state {
+  uint8_t* cert = nullptr;  // MAP_CELLS, world[x][y][z]
+  int* slot = nullptr;      // MAP_CELLS
+  float* list[2] = {nullptr, nullptr};  // three planes of list_cap[k] floats each
+  int list_n[2] = {0, 0};
+  int list_cap[2] = {0, 0};
+  int* scratch = nullptr;  // MapBuffers of up to scratch_cap batch elements
+  int scratch_cap = 0;
+  MapBuffers b{};
+  int* idx = nullptr;  // uploaded index list
+  int idx_cap = 0;
+  float* batch = nullptr;  // three planes: uploaded points / query points / rejected positions
+  int batch_cap = 0;
+  float* pos = nullptr;  // three planes: the positions of every association sweep (icpk_align_to_map)
+  int pos_cap = 0;
+  Rt* motion = nullptr;
+  int motion_cap = 0;
+  int* qout = nullptr;  // icpk_map_query: certainty and slot per point
+  int qout_cap = 0;
+  int* total_host = nullptr;  // pinned
+};
+
+namespace {
+
+float* plane(float* base, int cap, int k) { return base + (size_t)k * cap; }
+
+int grow_int(icpk_ctx* ctx, int*& p, int& cap, int need) {
+  if (need <= cap) return ICPK_OK;
+  if (p) ICPK_HIP(ctx, hipFree(p));
+  p = nullptr;
+  cap = 0;
+  ICPK_HIP(ctx, hipMalloc((void**)&p, (size_t)need * sizeof(int)));
+  cap = need;
+  return ICPK_OK;
+}
+
+int grow_planes(icpk_ctx* ctx, float*& p, int& cap, int need) {
+  if (need <= cap) return ICPK_OK;
+  if (p) ICPK_HIP(ctx, hipFree(p));
+  p = nullptr;
+  cap = 0;
+  ICPK_HIP(ctx, hipMalloc((void**)&p, (size_t)3 * need * sizeof(float)));
+  cap = need;
+  return ICPK_OK;
+}
+
+int ensure_map(icpk_ctx* ctx) {
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  if (ctx->map) return ICPK_OK;
+  icpk_map_state* m = new icpk_map_state();
+  ctx->map = m;
+  hipError_t e = hipMalloc((void**)&m->cert, (size_t)MAP_CELLS);
+  if (e == hipSuccess) e = hipMalloc((void**)&m->slot, (size_t)MAP_CELLS * sizeof(int));
+  if (e == hipSuccess) e = hipHostMalloc((void**)&m->total_host, sizeof(int), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMemsetAsync(m->cert, 0, (size_t)MAP_CELLS, ctx->stream);  // map.cpp:26
+  if (e == hipSuccess) e = hipMemsetAsync(m->slot, 0xff, (size_t)MAP_CELLS * sizeof(int), ctx->stream);  // map.cpp:27
+  if (e != hipSuccess) {
+    icpk_map_free(ctx);  // (no half-built map is left behind)
+    ctx->err = std::string("map allocation: ") + hipGetErrorString(e);
+    return ICPK_E_HIP;
+  }
+  return ICPK_OK;
+}
+
+// room for `need` entries in a list, its first list_n entries kept (capacity doubling)
+int ensure_list(icpk_ctx* ctx, int list, int need) {
+  icpk_map_state* m = ctx->map;
+  if (need <= m->list_cap[list]) return ICPK_OK;
+  int cap = m->list_cap[list] * 2;
+  if (cap < need) cap = need;
+  if (cap < 1024) cap = 1024;
+  float* p = nullptr;
+  ICPK_HIP(ctx, hipMalloc((void**)&p, (size_t)3 * cap * sizeof(float)));
+  const int n = m->list_n[list];
+  if (n > 0)
+    for (int k = 0; k < 3; ++k)
+      ICPK_HIP(ctx, hipMemcpyAsync(plane(p, cap, k), plane(m->list[list], m->list_cap[list], k), (size_t)n * sizeof(float),
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+  if (m->list[list]) {
+    ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ICPK_HIP(ctx, hipFree(m->list[list]));
+  }
+  m->list[list] = p;
+  m->list_cap[list] = cap;
+  return ICPK_OK;
+}
+
+int ensure_scratch(icpk_ctx* ctx, int n) {
+  icpk_map_state* m = ctx->map;
+  if (n <= m->scratch_cap) return ICPK_OK;
+  int cap = m->scratch_cap * 2;
+  if (cap < n) cap = n;
+  const size_t tiles = (size_t)(cap + MAP_TILE - 1) / MAP_TILE;
+  const size_t ints = (size_t)6 * cap + (size_t)MAP_RADIX * tiles + (tiles + 1) + 1;
+  if (m->scratch) ICPK_HIP(ctx, hipFree(m->scratch));
+  m->scratch = nullptr;
+  m->scratch_cap = 0;
+  ICPK_HIP(ctx, hipMalloc((void**)&m->scratch, ints * sizeof(int)));
+  int* p = m->scratch;
+  m->b.key = p;
+  m->b.ka = p + (size_t)cap;
+  m->b.kb = p + (size_t)2 * cap;
+  m->b.va = p + (size_t)3 * cap;
+  m->b.vb = p + (size_t)4 * cap;
+  m->b.flag = p + (size_t)5 * cap;
+  m->b.hist = p + (size_t)6 * cap;
+  m->b.tcount = m->b.hist + (size_t)MAP_RADIX * tiles;
+  m->b.total = m->b.tcount + tiles + 1;
+  m->scratch_cap = cap;
+  return ICPK_OK;
+}
+
+int list_of_rule(int rule) { return rule == ICPK_MAP_ADD_ASSOCIATED ? ICPK_MAP_POINTS : ICPK_MAP_KEYPOINTS; }
+
+// the batch through `rule`; one host wait for the number of appended points
+int run_update(icpk_ctx* ctx, int rule, const MapPoints& p, int delta) {
+  icpk_map_state* m = ctx->map;
+  if (p.n <= 0) return ICPK_OK;
+  const int list = list_of_rule(rule);
+  const int old = m->list_n[list];
+  if ((long long)old + p.n > (1ll << 30)) return icpk_host_fail(ctx, ICPK_E_ARG, "map list would exceed 2^30 entries");
+  int rc = ensure_list(ctx, list, old + p.n);
+  if (rc) return rc;
+  rc = ensure_scratch(ctx, p.n);
+  if (rc) return rc;
+  const int cap = m->list_cap[list];
+  float* L = m->list[list];
+  launch_map_update(p, rule, delta, old, list, plane(L, cap, 0), plane(L, cap, 1), plane(L, cap, 2), m->cert, m->slot, m->b,
+                    ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ICPK_HIP(ctx, hipMemcpyAsync(m->total_host, m->b.total, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  m->list_n[list] = old + *m->total_host;
+  return ICPK_OK;
+}
+
+// the context's source (working copy) or target as update input
+int cloud_of(icpk_ctx* ctx, int from, const Cloud** c) {
+  if (from == ICPK_MAP_FROM_SOURCE) {
+    if (!ctx->have_src) return icpk_host_fail(ctx, ICPK_E_NOT_SET, "source cloud not set");
+    if (int rc = icpk_host_ensure_unpacked(ctx)) return rc;
+    *c = &ctx->src;
+    return ICPK_OK;
+  }
+  if (from == ICPK_MAP_FROM_TARGET) {
+    if (!ctx->have_tgt) return icpk_host_fail(ctx, ICPK_E_NOT_SET, "target cloud not set");
+    *c = &ctx->tgt;
+    return ICPK_OK;
+  }
+  return icpk_host_fail(ctx, ICPK_E_ARG, "bad map source (ICPK_MAP_FROM_*)");
+}
+
+bool bad_rule(int rule, int delta) {
+  return rule < ICPK_MAP_ADD_CLOUD || rule > ICPK_MAP_ADD_UNASSOCIATED || delta < 1 || delta > 255;
+}
+
+int upload_points(icpk_ctx* ctx, const float* x, const float* y, const float* z, int n) {
+  icpk_map_state* m = ctx->map;
+  int rc = grow_planes(ctx, m->batch, m->batch_cap, n);
+  if (rc) return rc;
+  const float* src[3] = {x, y, z};
+  for (int k = 0; k < 3; ++k)
+    ICPK_HIP(ctx, hipMemcpyAsync(plane(m->batch, m->batch_cap, k), src[k], (size_t)n * sizeof(float), hipMemcpyHostToDevice,
+                                 ctx->stream));
+  return ICPK_OK;
+}
+
+}  // namespace
+
+void icpk_map_free(icpk_ctx* ctx) {
+  icpk_map_state* m = ctx ? ctx->map : nullptr;
+  if (!m) return;
+  (void)hipSetDevice(ctx->device);
+  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  void* dev[] = {m->cert, m->slot, m->list[0], m->list[1], m->scratch, m->idx, m->batch, m->pos, m->motion, m->qout};
+  for (void* p : dev)
+    if (p) (void)hipFree(p);
+  if (m->total_host) (void)hipHostFree(m->total_host);
+  delete m;
+  ctx->map = nullptr;
+}
+
+extern "C" {
+
+int icpk_map_reset(icpk_ctx* ctx) {
+  if (!ctx) return ICPK_E_ARG;
+  const bool fresh = ctx->map == nullptr;
+  int rc = ensure_map(ctx);
+  if (rc) return rc;
+  icpk_map_state* m = ctx->map;
+  if (!fresh) {
+    ICPK_HIP(ctx, hipMemsetAsync(m->cert, 0, (size_t)MAP_CELLS, ctx->stream));
+    ICPK_HIP(ctx, hipMemsetAsync(m->slot, 0xff, (size_t)MAP_CELLS * sizeof(int), ctx->stream));
+  }
+  m->list_n[0] = m->list_n[1] = 0;
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_map_release(icpk_ctx* ctx) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_map_free(ctx);
+  return ICPK_OK;
+}
+
+int icpk_map_update(icpk_ctx* ctx, int32_t rule, int32_t from, const int32_t* indices, int32_t n, int32_t delta) {
+  if (!ctx) return ICPK_E_ARG;
+  if (bad_rule(rule, delta)) return icpk_host_fail(ctx, ICPK_E_ARG, "bad map rule or delta (1 <= d <= 255)");
+  if (indices && n < 0) return icpk_host_fail(ctx, ICPK_E_ARG, "negative index count");
+  int rc = ensure_map(ctx);
+  if (rc) return rc;
+  const Cloud* c = nullptr;
+  rc = cloud_of(ctx, from, &c);
+  if (rc) return rc;
+  MapPoints p{c->x(), c->y(), c->z(), nullptr, c->n};
+  if (indices) {
+    for (int32_t k = 0; k < n; ++k)
+      if (indices[k] < 0 || indices[k] >= c->n) return icpk_host_fail(ctx, ICPK_E_ARG, "map index outside the cloud");
+    icpk_map_state* m = ctx->map;
+    rc = grow_int(ctx, m->idx, m->idx_cap, n);
+    if (rc) return rc;
+    if (n > 0)
+      ICPK_HIP(ctx, hipMemcpyAsync(m->idx, indices, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    p.idx = m->idx;
+    p.n = n;
+  }
+  return run_update(ctx, rule, p, delta);
+}
+
+int icpk_map_update_points(icpk_ctx* ctx, int32_t rule, const float* x, const float* y, const float* z, int32_t n,
+                           int32_t delta) {
+  if (!ctx) return ICPK_E_ARG;
+  if (bad_rule(rule, delta)) return icpk_host_fail(ctx, ICPK_E_ARG, "bad map rule or delta (1 <= d <= 255)");
+  if (n < 0 || (n > 0 && (!x || !y || !z))) return icpk_host_fail(ctx, ICPK_E_ARG, "bad point arrays");
+  int rc = ensure_map(ctx);
+  if (rc) return rc;
+  if (n == 0) return ICPK_OK;
+  rc = upload_points(ctx, x, y, z, n);
+  if (rc) return rc;
+  icpk_map_state* m = ctx->map;
+  MapPoints p{plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1), plane(m->batch, m->batch_cap, 2), nullptr,
+              n};
+  return run_update(ctx, rule, p, delta);
+}
+
+int icpk_map_set_points(icpk_ctx* ctx, int32_t from) {
+  if (!ctx) return ICPK_E_ARG;
+  int rc = ensure_map(ctx);
+  if (rc) return rc;
+  const Cloud* c = nullptr;
+  rc = cloud_of(ctx, from, &c);
+  if (rc) return rc;
+  icpk_map_state* m = ctx->map;
+  m->list_n[ICPK_MAP_POINTS] = 0;  // (nothing of the old list survives the assignment)
+  rc = ensure_list(ctx, ICPK_MAP_POINTS, c->n);
+  if (rc) return rc;
+  const int cap = m->list_cap[ICPK_MAP_POINTS];
+  const float* src[3] = {c->x(), c->y(), c->z()};
+  if (c->n > 0)
+    for (int k = 0; k < 3; ++k)
+      ICPK_HIP(ctx, hipMemcpyAsync(plane(m->list[ICPK_MAP_POINTS], cap, k), src[k], (size_t)c->n * sizeof(float),
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  m->list_n[ICPK_MAP_POINTS] = c->n;
+  return ICPK_OK;
+}
+
+int32_t icpk_map_size(icpk_ctx* ctx, int32_t list) {
+  if (!ctx || (list != ICPK_MAP_KEYPOINTS && list != ICPK_MAP_POINTS)) return ICPK_E_ARG;
+  return ctx->map ? ctx->map->list_n[list] : 0;
+}
+
+int icpk_map_get_list(icpk_ctx* ctx, int32_t list, float* x, float* y, float* z) {
+  if (!ctx || (list != ICPK_MAP_KEYPOINTS && list != ICPK_MAP_POINTS)) return ICPK_E_ARG;
+  if (!ctx->map || ctx->map->list_n[list] == 0) return ICPK_OK;
+  if (!x || !y || !z) return ICPK_E_ARG;
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  icpk_map_state* m = ctx->map;
+  float* dst[3] = {x, y, z};
+  for (int k = 0; k < 3; ++k)
+    ICPK_HIP(ctx, hipMemcpyAsync(dst[k], plane(m->list[list], m->list_cap[list], k), (size_t)m->list_n[list] * sizeof(float),
+                                 hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_map_get_certainty(icpk_ctx* ctx, uint8_t* out) {
+  if (!ctx || !out) return ICPK_E_ARG;
+  int rc = ensure_map(ctx);
+  if (rc) return rc;
+  ICPK_HIP(ctx, hipMemcpyAsync(out, ctx->map->cert, (size_t)MAP_CELLS, hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_map_query(icpk_ctx* ctx, const float* x, const float* y, const float* z, int32_t n, uint8_t* cert_out,
+                   uint8_t* occupied_out, int32_t* slot_list_out, int32_t* slot_index_out) {
+  if (!ctx || n < 0 || (n > 0 && (!x || !y || !z))) return ICPK_E_ARG;
+  int rc = ensure_map(ctx);
+  if (rc || n == 0) return rc;
+  rc = upload_points(ctx, x, y, z, n);
+  if (rc) return rc;
+  icpk_map_state* m = ctx->map;
+  rc = grow_int(ctx, m->qout, m->qout_cap, 2 * n);
+  if (rc) return rc;
+  launch_map_query(plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1), plane(m->batch, m->batch_cap, 2), n,
+                   m->cert, m->slot, m->qout, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  std::vector<int> out((size_t)2 * n);
+  ICPK_HIP(ctx, hipMemcpyAsync(out.data(), m->qout, out.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int32_t i = 0; i < n; ++i) {
+    const int c = out[(size_t)i], s = out[(size_t)n + i];
+    if (cert_out) cert_out[i] = (uint8_t)c;
+    if (occupied_out) occupied_out[i] = c >= ICPK_MAP_MAX_CONFIDENCE ? 1 : 0;  // map.cpp:443
+    if (slot_list_out) slot_list_out[i] = s < 0 ? -1 : (s & 1);
+    if (slot_index_out) slot_index_out[i] = s < 0 ? -1 : (s >> 1);
+  }
+  return ICPK_OK;
+}
+
+int icpk_map_list_to_target(icpk_ctx* ctx, int32_t list) {
+  if (!ctx || (list != ICPK_MAP_KEYPOINTS && list != ICPK_MAP_POINTS)) return ICPK_E_ARG;
+  int rc = ensure_map(ctx);
+  if (rc) return rc;
+  icpk_map_state* m = ctx->map;
+  const int cap = m->list_cap[list];
+  float* L = m->list[list];
+  return icpk_set_target_device(ctx, L ? plane(L, cap, 0) : nullptr, L ? plane(L, cap, 1) : nullptr,
+                                L ? plane(L, cap, 2) : nullptr, m->list_n[list]);
+}
+
+void icpk_map_voxel(const float p[3], int32_t v[3]) {
+  const float c = 10.0f / (float)MAP_DIM;  // map.cpp:58
+  for (int k = 0; k < 3; ++k) {
+    const float q = p[k] / c;
+    // int(q) as the reference's x86 build converts (cvttss2si: truncation, INT_MIN for NaN, +-inf, |q| >= 2^31), then
+    // the clamp of map.cpp:65-82: whatever is negative, NaN or out of range lands in 0 (as kernels_map.hip's map_axis)
+    const int i = (q >= 0.f && q < 2147483648.f) ? (int)q : 0;
+    v[k] = i >= MAP_DIM ? MAP_DIM - 1 : i;
+  }
+}
+
+int icpk_align_to_map(icpk_ctx* ctx, const icpk_params* p, int32_t delta, float T_out[16], icpk_stats* stats) {
+  if (T_out)
+    for (int k = 0; k < 16; ++k) T_out[k] = (k % 5 == 0) ? 1.f : 0.f;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!ctx || !p || !T_out) return ICPK_E_ARG;
+  if (delta < 1 || delta > 255) return icpk_host_fail(ctx, ICPK_E_ARG, "bad delta (1 <= d <= 255)");
+  if (p->solve != ICPK_SOLVE_REFERENCE && p->solve != ICPK_SOLVE_KABSCH)
+    return icpk_host_fail(ctx, ICPK_E_ARG, "icpk_align_to_map: reference or Kabsch flavour (the map has no normals)");
+  if (!ctx->have_src) return icpk_host_fail(ctx, ICPK_E_NOT_SET, "source cloud not set");
+  int rc = ensure_map(ctx);
+  if (rc) return rc;
+  icpk_map_state* m = ctx->map;
+  if (m->list_n[ICPK_MAP_KEYPOINTS] == 0) {  // icp.cpp:490-491, :622-638, map.cpp:124-126
+    rc = icpk_reset_source(ctx);
+    if (rc) return rc;
+    ctx->trace_R.clear();
+    ctx->trace_t.clear();
+    ctx->trace_mse.clear();
+    ctx->trace_pairs.clear();
+    if (stats) stats->status = ICPK_W_EMPTY_MAP;
+    return ICPK_W_EMPTY_MAP;
+  }
+  rc = icpk_map_list_to_target(ctx, ICPK_MAP_KEYPOINTS);
+  if (rc) return rc;
+  icpk_stats st;
+  const int status = icpk_align(ctx, p, T_out, &st);
+  if (stats) *stats = st;
+  if (status < 0) return status;
+  const int ns = ctx->src0.n;
+  if (st.final_pairs <= 0 || ns <= 0) return status;  // map.cpp:124-126: no associations, no update
+
+  // the motion the loop applied after each completed iteration (icpk_align: reference flavour R^-1 and -offset,
+  // icp.cpp:235-245; Kabsch the step itself); the sweeps ran at P_0 .. P_niter
+  const int niter = (int)(ctx->trace_R.size() / 9);
+  const int nsw = niter + 1;
+  std::vector<Rt> mo((size_t)(niter > 0 ? niter : 1));
+  for (int s = 0; s < niter; ++s) {
+    const float* R = ctx->trace_R.data() + 9 * (size_t)s;
+    const float* t = ctx->trace_t.data() + 3 * (size_t)s;
+    if (p->solve == ICPK_SOLVE_REFERENCE) {
+      invert3f(R, mo[(size_t)s].R);
+      for (int k = 0; k < 3; ++k) mo[(size_t)s].t[k] = -t[k];
+    } else {
+      std::memcpy(mo[(size_t)s].R, R, sizeof(mo[(size_t)s].R));
+      std::memcpy(mo[(size_t)s].t, t, sizeof(mo[(size_t)s].t));
+    }
+  }
+  if (niter > m->motion_cap) {
+    if (m->motion) ICPK_HIP(ctx, hipFree(m->motion));
+    m->motion = nullptr;
+    m->motion_cap = 0;
+    ICPK_HIP(ctx, hipMalloc((void**)&m->motion, (size_t)niter * sizeof(Rt)));
+    m->motion_cap = niter;
+  }
+  if (niter > 0)
+    ICPK_HIP(ctx, hipMemcpyAsync(m->motion, mo.data(), (size_t)niter * sizeof(Rt), hipMemcpyHostToDevice, ctx->stream));
+  const long long total_pos = (long long)ns * nsw;
+  if (total_pos > (1ll << 30)) return icpk_host_fail(ctx, ICPK_E_ARG, "too many sweep positions");
+  const int mpos = (int)total_pos;
+  rc = ensure_scratch(ctx, mpos);
+  if (!rc) rc = grow_planes(ctx, m->pos, m->pos_cap, mpos);
+  if (!rc) rc = grow_planes(ctx, m->batch, m->batch_cap, mpos);
+  if (rc) return rc;
+  launch_map_rejected(ctx->src0.x(), ctx->src0.y(), ctx->src0.z(), ns, m->motion, nsw, plane(m->pos, m->pos_cap, 0),
+                      plane(m->pos, m->pos_cap, 1), plane(m->pos, m->pos_cap, 2), ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(),
+                      ctx->tgt.n, p->max_nn_dist, plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1),
+                      plane(m->batch, m->batch_cap, 2), m->b, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ICPK_HIP(ctx, hipMemcpyAsync(m->total_host, m->b.total, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int nrej = *m->total_host;
+  MapPoints rej{plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1), plane(m->batch, m->batch_cap, 2), nullptr,
+                nrej};
+  rc = run_update(ctx, ICPK_MAP_ADD_UNASSOCIATED, rej, delta);  // icp.cpp:271
+  return rc ? rc : status;
+}
+
+}  // extern "C"

@@ -354,6 +354,83 @@ int icpk_backproject_pair(icpk_ctx *ctx, const uint16_t *depth_source, const uin
                           int32_t morph, int32_t anchor_x, int32_t anchor_y, int32_t *n_source,
                           int32_t *n_target);
 
+/* ---- voxel certainty map: map::Map (map.hpp, map.cpp) on the device ------- */
+/* One map per context, allocated on first use: a 300^3 uint8 certainty grid (`world`, map.hpp:25; 27 MB) and an int32
+ * slot per voxel (`pointLookupTable`, map.hpp:24; 108 MB) that holds (list index << 1) | list of the point that filled
+ * it, -1 while empty.  Two point lists grow on the device: the key points (mapCloud.keypoints) and the points
+ * (mapCloud.points).  Storage order of the grid is world[x][y][z]: offset (x * 300 + y) * 300 + z.
+ * Empty slot: the reference compares the slot with a default color_point_t (zero point, black) and this library drops
+ * colour, so a slot here is empty until a point fills it.  The two differ only for a point at exactly (0, 0, 0), which
+ * the reference would treat as never filling its slot: PARITY UNPINNED there.  Slots persist across updates and are
+ * shared by both lists; they keep their (list, index) when icpk_map_set_points replaces the point list. */
+#define ICPK_MAP_HEIGHT 300          /* map.hpp:9  MAP_HEIGHT                                   */
+#define ICPK_MAP_PHYSICAL_HEIGHT 10.0f /* map.hpp:10 PHYSICAL_HEIGHT (cell c = float(10 / 300)) */
+#define ICPK_MAP_MAX_CONFIDENCE 180  /* map.hpp:13                                               */
+#define ICPK_MAP_DELTA_CONFIDENCE 25 /* map.hpp:11                                               */
+#define ICPK_MAP_CELLS (ICPK_MAP_HEIGHT * ICPK_MAP_HEIGHT * ICPK_MAP_HEIGHT)
+/* lists */
+#define ICPK_MAP_KEYPOINTS 0 /* mapCloud.keypoints */
+#define ICPK_MAP_POINTS 1    /* mapCloud.points    */
+/* the cloud of the context an update reads */
+#define ICPK_MAP_FROM_SOURCE 0 /* the working source, as icpk_get_source returns it */
+#define ICPK_MAP_FROM_TARGET 1 /* the target, as icpk_get_target returns it         */
+/* update rules; per point, in input order (d = delta, 1 <= d <= 255; cert = the voxel's certainty):
+ *   ADD_CLOUD         map.cpp:220-269 (icp.cpp:62):  cert = min(255, cert + d); then if the slot is empty and
+ *                     cert >= 180, fill it and append the point to the KEY-POINT list
+ *   ADD_ASSOCIATED    map.cpp:88-119:  if cert > 255 - d: cert = 255 and, if the slot is empty, fill it and append
+ *                     the point to the POINT list; else cert += d
+ *   ADD_UNASSOCIATED  map.cpp:122-206 (icp.cpp:271):  if cert >= 180 - d: cert = 255 and, if the slot is empty, fill
+ *                     it and append the point to the KEY-POINT list; else cert += d
+ * A batch leaves grid, slots and lists exactly as applying its points one by one in index order would, however many
+ * of them share a voxel. */
+#define ICPK_MAP_ADD_CLOUD 0
+#define ICPK_MAP_ADD_ASSOCIATED 1
+#define ICPK_MAP_ADD_UNASSOCIATED 2
+
+/* map.cpp:17-31 Map::Map(): certainty 0, every slot empty, both lists empty (allocates the map on first use) */
+int icpk_map_reset(icpk_ctx *ctx);
+/* frees the map's device memory (the next map call starts from an empty map) */
+int icpk_map_release(icpk_ctx *ctx);
+/* the points of the context's source or target (ICPK_MAP_FROM_*) through `rule` with delta d, read where they lie.
+ * indices: host list of n point indices (repeats allowed, applied in order); NULL: the whole cloud in order (n is then
+ * ignored).  ICPK_E_ARG for a bad rule, d outside [1, 255] or an index outside the cloud. */
+int icpk_map_update(icpk_ctx *ctx, int32_t rule, int32_t from, const int32_t *indices, int32_t n, int32_t delta);
+/* same for n points in host arrays */
+int icpk_map_update_points(icpk_ctx *ctx, int32_t rule, const float *x, const float *y, const float *z, int32_t n,
+                           int32_t delta);
+/* icp.cpp:63 map.mapCloud.points = previousCloud.points: the point list becomes a copy of the context's source or
+ * target (device-to-device).  Grid and slots are not touched. */
+int icpk_map_set_points(icpk_ctx *ctx, int32_t from);
+/* length of a list (ICPK_MAP_KEYPOINTS / ICPK_MAP_POINTS); 0 before the map exists, negative on a bad argument */
+int32_t icpk_map_size(icpk_ctx *ctx, int32_t list);
+/* a list to host arrays of icpk_map_size(list) entries, in list order */
+int icpk_map_get_list(icpk_ctx *ctx, int32_t list, float *x, float *y, float *z);
+/* the whole certainty grid (ICPK_MAP_CELLS bytes, world[x][y][z] order) to host memory */
+int icpk_map_get_certainty(icpk_ctx *ctx, uint8_t *out);
+/* per point of n host points: the certainty of its voxel, isOccupied (map.cpp:441-444: cert >= 180), and the slot's
+ * list and index (-1, -1: empty).  Any output may be NULL. */
+int icpk_map_query(icpk_ctx *ctx, const float *x, const float *y, const float *z, int32_t n, uint8_t *cert_out,
+                   uint8_t *occupied_out, int32_t *slot_list_out, int32_t *slot_index_out);
+/* a list becomes the context's target (device-to-device), ready for icpk_nn, icpk_associate_keypoints and icpk_align */
+int icpk_map_list_to_target(icpk_ctx *ctx, int32_t list);
+/* map.cpp:55-85 getVoxelCoordinates on the host: per axis q = p / c (float), i = int(q) with the x86 conversion
+ * (NaN, +-inf and |q| >= 2^31 give INT_MIN), clamped to [0, 299] */
+void icpk_map_voxel(const float p[3], int32_t v[3]);
+/* The live body of icp::getTransformation (icp.cpp:98-271) against the map:
+ *   source = the context's source (the frame's posed key points); target = the map's key-point list, copied
+ *   device-to-device: THE CONTEXT'S TARGET IS REPLACED.  The loop is icpk_align's with p->max_nn_dist as the
+ *   acceptance (the reference's MAX_NN_KEYPOINT_DISTANCE, 0.1): T_out, stats, icpk_get_trace and the aligned source are
+ *   those of icpk_align on the same two clouds, bit for bit.  Every association sweep the loop ran (the initial one,
+ *   :98, and one per completed iteration, :255; none after the min_pairs fallback, :163-182) contributes its rejected
+ *   source points, at their positions in that sweep, to one list (`nonAssociations`, never cleared within the call,
+ *   :507-509); then, if the last sweep accepted at least one pair (map.cpp:124-126), that list goes through
+ *   ICPK_MAP_ADD_UNASSOCIATED with `delta` (:271).
+ * Empty key-point list: returns ICPK_W_EMPTY_MAP with identity T_out, no iteration, the working source reset to the
+ * uploaded one and the map untouched -- what the reference gives: findGlobalKeyPointAssociations returns at
+ * :490-491, meanSquareError of no errors is 0 (:622-638) so the loop does not run, and map.update returns on no
+ * associations.  Reference and Kabsch flavours (ICPK_E_ARG for point-to-plane: the map has no normals). */
+int icpk_align_to_map(icpk_ctx *ctx, const icpk_params *p, int32_t delta, float T_out[16], icpk_stats *stats);
+
 /* ---- point-to-plane extension (BASELINE config 3; not in the reference) ---- */
 #define ICPK_NORMALS_CROSS 0     /* normalised cross product of back-projected central differences */
 #define ICPK_NORMALS_REFERENCE 1 /* SLAM.cpp:421-425 getNormalMap formula, interior pixels          */

@@ -1,0 +1,326 @@
+"""The voxel certainty map on the device (icpk_map_*, icpk_align_to_map, icp::MapTracker) against the sequential
+model of tests/map_model.py: after every update the whole 27 MB grid, both lists in order and the slots must be bit
+equal; the live path (icp.cpp:27-271) against a restatement composed from the model and oracle primitives."""
+import os
+import struct
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import map_model as mm
+from icp_slam_prototype_amd import binding, build, synth
+
+pytestmark = pytest.mark.gpu
+
+I3 = np.eye(3, dtype=np.float32)
+P5 = np.full(3, 5, np.float32)
+
+
+def check_state(ctx, model, probe=None, rng=None):
+    g = ctx.map_get_certainty()
+    want = model.grid()
+    if not np.array_equal(g, want):
+        d = np.argwhere(g != want)
+        raise AssertionError(f"grid differs in {len(d)} voxels, first {tuple(d[0])}: {g[tuple(d[0])]} vs {want[tuple(d[0])]}")
+    for lst in (mm.KEYPOINTS, mm.POINTS):
+        got = ctx.map_get_list(lst)
+        exp = model.list_array(lst)
+        assert got.shape == exp.shape, (lst, got.shape, exp.shape)
+        assert np.array_equal(got.view(np.uint32), exp.view(np.uint32)), lst
+    pts = [model.list_array(mm.KEYPOINTS), model.list_array(mm.POINTS)]
+    if probe is not None:
+        pts.append(np.asarray(probe, np.float32))
+    if rng is not None:
+        pts.append(rng.uniform(-0.5, 10.5, (3, 2000)).astype(np.float32))
+    q = np.concatenate(pts, axis=1)
+    if q.shape[1] == 0:
+        return
+    cert, occ, sl, si = ctx.map_query(q)
+    for i in range(q.shape[1]):
+        v = mm.voxel(q[:, i])
+        assert cert[i] == model.certainty(v)
+        assert bool(occ[i]) == model.is_occupied(q[:, i])
+        assert (int(sl[i]), int(si[i])) == model.query_slot(q[:, i]), (i, q[:, i])
+
+
+def test_batches_match_the_sequential_model():
+    rng = np.random.default_rng(11)
+    kin = synth.kinect_pair(rows=480, cols=640, valid=0.3, seed=4)["source"]  # posed around (5, 5, 5)
+    model = mm.Map()
+    with binding.Context(0) as ctx:
+        ctx.map_reset()
+        check_state(ctx, model)
+        # 1: the first frame (icp.cpp:62): ADD_CLOUD, d = 180, over a 640 x 480 Kinect cloud, from the source
+        ctx.set_source(kin)
+        ctx.map_update(binding.MAP_ADD_CLOUD, 180, binding.MAP_FROM_SOURCE)
+        model.update(mm.ADD_CLOUD, kin, 180)
+        check_state(ctx, model, rng=rng)
+        # 2: 10 000 points in one voxel, ADD_ASSOCIATED d = 25 (fills on the 11th hit of an empty voxel)
+        one = (np.float32(3.0) + rng.uniform(0, 0.02, (3, 10000))).astype(np.float32)
+        v0 = mm.voxel(one[:, 0])
+        one = one[:, [mm.voxel(one[:, i]) == v0 for i in range(one.shape[1])]]
+        ctx.map_update_points(binding.MAP_ADD_ASSOCIATED, one, 25)
+        model.update(mm.ADD_ASSOCIATED, one, 25)
+        check_state(ctx, model, probe=one[:, :5], rng=rng)
+        # 3: a cloud clamped onto the faces of the room (far outside [0, 10)), ADD_UNASSOCIATED d = 25
+        far = (rng.uniform(-60, 60, (3, 30000))).astype(np.float32)
+        far[1] = np.float32(-3.0)  # every point on the y = 0 face
+        ctx.map_update_points(binding.MAP_ADD_UNASSOCIATED, far, 25)
+        model.update(mm.ADD_UNASSOCIATED, far, 25)
+        check_state(ctx, model, probe=far[:, :50], rng=rng)
+        # 4: non-finite and huge coordinates (all land in voxel 0 of their axis), ADD_CLOUD d = 100
+        bad = np.array([[np.nan, np.inf, -np.inf, 1e10, -1e10, 0.0, 2.0 ** 40, 7.0] * 40,
+                        [1.0, np.nan, 2.0, np.inf, 3.0, -0.0, 4.0, 1e10] * 40,
+                        [np.inf, 1.0, np.nan, 5.0, -np.inf, 9.99, -1e10, 7.0] * 40], np.float32)
+        ctx.map_update_points(binding.MAP_ADD_CLOUD, bad, 100)
+        model.update(mm.ADD_CLOUD, bad, 100)
+        check_state(ctx, model, probe=bad, rng=rng)
+        # 5: an index list with repeats over the target, ADD_UNASSOCIATED d = 60
+        tgt = synth.kinect_pair(rows=120, cols=160, valid=0.8, seed=9)["target"]
+        ctx.set_target(tgt)
+        idx = rng.integers(0, tgt.shape[1], 20000).astype(np.int32)
+        idx[1000:1100] = idx[0]
+        ctx.map_update(binding.MAP_ADD_UNASSOCIATED, 60, binding.MAP_FROM_TARGET, idx)
+        model.update(mm.ADD_UNASSOCIATED, tgt, 60, indices=idx)
+        check_state(ctx, model, probe=tgt[:, idx[:200]], rng=rng)
+        # 6: extreme deltas: ADD_ASSOCIATED d = 255 over the Kinect cloud again, then ADD_CLOUD d = 1 in reverse order
+        ctx.map_update(binding.MAP_ADD_ASSOCIATED, 255, binding.MAP_FROM_SOURCE)
+        model.update(mm.ADD_ASSOCIATED, kin, 255)
+        check_state(ctx, model, rng=rng)
+        rev = np.arange(tgt.shape[1] - 1, -1, -1, dtype=np.int32)
+        ctx.map_update(binding.MAP_ADD_CLOUD, 1, binding.MAP_FROM_TARGET, rev)
+        model.update(mm.ADD_CLOUD, tgt, 1, indices=rev)
+        check_state(ctx, model, rng=rng)
+        # 7: the point list replaced (icp.cpp:63); grid and slots unchanged
+        ctx.map_set_points(binding.MAP_FROM_TARGET)
+        model.set_points(tgt)
+        check_state(ctx, model, rng=rng)
+        # bad arguments are refused and change nothing
+        for rule, d in ((3, 25), (0, 0), (1, 256)):
+            with pytest.raises(binding.IcpkError):
+                ctx.map_update_points(rule, one[:, :3], d)
+        with pytest.raises(binding.IcpkError):
+            ctx.map_update(binding.MAP_ADD_CLOUD, 25, binding.MAP_FROM_TARGET, [0, tgt.shape[1]])
+        check_state(ctx, model)
+        # reset == Map::Map()
+        ctx.map_reset()
+        check_state(ctx, mm.Map())
+
+
+def test_list_to_target_feeds_the_keypoint_association():
+    rng = np.random.default_rng(5)
+    pair = synth.kinect_pair(rows=120, cols=160, valid=0.5, seed=21)
+    with binding.Context(0) as ctx:
+        ctx.map_reset()
+        ctx.map_update_points(binding.MAP_ADD_CLOUD, pair["target"], 180)
+        kp = ctx.map_get_list(binding.MAP_KEYPOINTS)
+        assert kp.shape[1] > 100
+        ctx.map_list_to_target(binding.MAP_KEYPOINTS)
+        assert np.array_equal(ctx.get_target().view(np.uint32), kp.view(np.uint32))
+        q = pair["source"][:, rng.choice(pair["source"].shape[1], 1500, replace=False)]
+        ctx.set_source(q)
+        a = ctx.associate_keypoints(0.1)
+        ctx.set_target(kp)
+        b = ctx.associate_keypoints(0.1)
+        assert a[0] == b[0] == binding.OK
+        for x, y in zip(a[1:], b[1:]):
+            assert np.array_equal(np.asarray(x).view(np.uint32), np.asarray(y).view(np.uint32))
+
+
+# ---- the live path ---------------------------------------------------------------------------------------------
+ROWS, COLS, NFRAMES, MAX_ITER, THR = 240, 320, 10, 10, 1e-5
+
+
+def live_frames():
+    rng = np.random.default_rng(3)
+    frames = []
+    for k in range(NFRAMES):  # camera turning by 0.4 degree and moving 1 cm per frame
+        Rm = synth.rot_xyz_deg(0, 0.4 * k, 0)
+        d = synth.render_room_depth(ROWS, COLS, Rm, np.array([0.01 * k, 0.0, 0.005 * k]), noise_sigma=0.001, rng=rng)
+        frames.append(d.astype(np.uint16))
+    kp = np.stack([rng.uniform(4, COLS - 5, 1200), rng.uniform(4, ROWS - 5, 1200)], 1).astype(np.float32)
+    return frames, kp
+
+
+FALLBACK_FRAME = 5  # this frame runs with min_pairs above any pair count: the loop falls back at once
+
+
+def mul3f(A, B):
+    A = A.astype(np.float64)
+    B = B.astype(np.float64)
+    return ((A[:, 0:1] * B[0:1, :] + A[:, 1:2] * B[1:2, :]) + A[:, 2:3] * B[2:3, :]).astype(np.float32)
+
+
+def inv3_pose(m):
+    """icp::Tracker / icp::MapTracker's pose inverse (icp_align.hpp, icp_map.hpp: invert3), same double operations"""
+    a, b, c, d, e, f, g, h, i = (float(v) for v in np.asarray(m, np.float32).reshape(9))
+    det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g)
+    s = 1.0 / det if det != 0.0 else 0.0
+    t = [(e * i - f * h) * s, (c * h - b * i) * s, (b * f - c * e) * s,
+         (f * g - d * i) * s, (a * i - c * g) * s, (c * d - a * f) * s,
+         (d * h - e * g) * s, (b * g - a * h) * s, (a * e - b * d) * s]
+    return np.array(t, np.float64).astype(np.float32).reshape(3, 3)
+
+
+class Restatement:
+    """icp.cpp:27-271 composed from the model and oracle primitives; the loop's solves come from icpk_align on a
+    context of its own (T and trace), its sweeps from the oracle's key-point association."""
+
+    def __init__(self, oracle, ref_ctx):
+        self.o = oracle
+        self.ref = ref_ctx
+        self.model = mm.Map()
+        self.reset_pose()
+
+    def reset_pose(self):
+        self.Rcam, self.pcam = I3.copy(), P5.copy()
+        self.lastR, self.lastT = I3.copy(), np.zeros(3, np.float32)
+
+    def frame(self, data, previous, kp, params):
+        o, model = self.o, self.model
+        if len(model.lists[mm.POINTS]) == 0:  # icp.cpp:47-68
+            self.reset_pose()
+            kprev = o.transform_points(o.backproject_keypoints(previous, kp)[0], I3, P5)
+            model.update(mm.ADD_CLOUD, kprev, 180)
+            model.set_points(o.transform_points(o.backproject(previous), I3, P5))
+        src = o.transform_points(o.backproject_keypoints(data, kp)[0], self.Rcam, self.pcam)
+        tgt = model.list_array(mm.KEYPOINTS)
+        if tgt.shape[1] == 0:
+            return binding.W_EMPTY_MAP, np.eye(4, dtype=np.float32), None, [], src
+        p = params
+        p.last_rotation[:] = [float(v) for v in self.lastR.reshape(9)]
+        p.last_translation[:] = [float(v) for v in self.lastT]
+        self.ref.set_target(tgt)
+        self.ref.set_source(src)
+        T, st, rc = self.ref.align(p)
+        trace = self.ref.get_trace(max(p.max_iterations, 1))
+        aligned = self.ref.get_source()
+        # the oracle's loop on the same clouds agrees to rounding of the solve (polar vs Jacobi SVD)
+        ol = o.align(src, tgt, max_iterations=p.max_iterations, threshold=p.threshold, max_nn_dist=p.max_nn_dist,
+                     min_pairs=p.min_pairs, solve=0, sum_order=1, threads=4, last_rotation=self.lastR,
+                     last_translation=self.lastT)
+        assert ol["status"] == rc and ol["iterations"] == st.iterations
+        assert np.abs(ol["T"].astype(np.float64) - T.astype(np.float64)).max() < 1e-5
+        # every sweep the loop ran, at its positions (icp.cpp:98, :255)
+        P, rejected, last = src, [], None
+        for s in range(len(trace) + 1):
+            last = o.keypoint_associations(P, tgt, p.max_nn_dist)
+            rejected.append(P[:, last[3]])
+            if s < len(trace):
+                P = o.transform_points(P, o.inv3(trace[s]["R"]), -trace[s]["t"])
+        assert len(last[0]) == st.final_pairs
+        if rc != binding.W_TOO_FEW_PAIRS:
+            assert np.array_equal(P.view(np.uint32), aligned.view(np.uint32))  # the replayed sweeps are the loop's
+        if st.final_pairs > 0:  # map.cpp:124-126, icp.cpp:271
+            model.update(mm.ADD_UNASSOCIATED, np.concatenate(rejected, axis=1), 25)
+        for it in trace:  # icp.cpp:235-246
+            self.Rcam = mul3f(self.Rcam, inv3_pose(it["R"]))
+            self.pcam = (self.pcam - it["t"]).astype(np.float32)
+        self.lastT = (-T[:3, 3]).astype(np.float32)
+        if rc != binding.W_TOO_FEW_PAIRS:
+            self.lastR = I3.copy()
+        return rc, T, st, trace, aligned
+
+
+@pytest.mark.parametrize("host_loop", [0, 1])
+def test_align_to_map_live_sequence(oracle, host_loop):
+    frames, kp = live_frames()
+    with binding.Context(0) as ctx, binding.Context(0) as ref:
+        ctx.map_reset()
+        rs = Restatement(oracle, ref)
+        # an empty map: identity, W_EMPTY_MAP, nothing touched (icp.cpp:490-491, :622-638; map.cpp:124-126)
+        kp0 = oracle.transform_points(oracle.backproject_keypoints(frames[0], kp)[0], I3, P5)
+        ctx.set_source(kp0)
+        T, st, rc = ctx.align_to_map(binding.default_params(max_nn_dist=0.1, host_loop=host_loop))
+        assert rc == binding.W_EMPTY_MAP and np.array_equal(T, np.eye(4, dtype=np.float32)) and st.iterations == 0
+        assert np.array_equal(ctx.get_source().view(np.uint32), kp0.view(np.uint32))
+        check_state(ctx, mm.Map())
+        Rcam, pcam, lastR, lastT = I3.copy(), P5.copy(), I3.copy(), np.zeros(3, np.float32)
+        saw_fallback = False
+        for f in range(1, NFRAMES):
+            data, previous = frames[f], frames[f - 1]
+            params = binding.default_params(max_nn_dist=0.1, max_iterations=MAX_ITER, threshold=THR, solve=0,
+                                            host_loop=host_loop)
+            if f == FALLBACK_FRAME:
+                params.min_pairs = 1 << 30
+            # the device side: icp_map.hpp's MapTracker, step by step
+            if ctx.map_size(binding.MAP_POINTS) == 0:
+                Rcam, pcam, lastR, lastT = I3.copy(), P5.copy(), I3.copy(), np.zeros(3, np.float32)
+                kprev = oracle.transform_points(binding.backproject_keypoints(previous, kp)[0], I3, P5)
+                ctx.map_update_points(binding.MAP_ADD_CLOUD, kprev, 180)
+                ctx.backproject(previous, which=1)
+                ctx.transform_target(I3, P5)
+                ctx.map_set_points(binding.MAP_FROM_TARGET)
+            src = oracle.transform_points(binding.backproject_keypoints(data, kp)[0], Rcam, pcam)
+            ctx.set_source(src)
+            params.last_rotation[:] = [float(v) for v in lastR.reshape(9)]
+            params.last_translation[:] = [float(v) for v in lastT]
+            T, st, rc = ctx.align_to_map(params, delta=25)
+            trace = ctx.get_trace(MAX_ITER)
+            aligned = ctx.get_source()
+            # the restatement
+            rparams = binding.default_params(max_nn_dist=0.1, max_iterations=MAX_ITER, threshold=THR, solve=0,
+                                             host_loop=host_loop, min_pairs=params.min_pairs)
+            rrc, rT, rst, rtrace, raligned = rs.frame(data, previous, kp, rparams)
+            assert rc == rrc, (f, rc, rrc)
+            assert np.array_equal(T.view(np.uint32), rT.view(np.uint32)), f
+            assert (st.iterations, st.status, st.final_pairs, st.nn_launches) == \
+                (rst.iterations, rst.status, rst.final_pairs, rst.nn_launches)
+            assert np.array_equal(np.float32(st.final_mse).view(np.uint32), np.float32(rst.final_mse).view(np.uint32))
+            assert len(trace) == len(rtrace)
+            for a, b in zip(trace, rtrace):
+                assert np.array_equal(a["R"].view(np.uint32), b["R"].view(np.uint32))
+                assert np.array_equal(a["t"].view(np.uint32), b["t"].view(np.uint32))
+                assert a["n_pairs"] == b["n_pairs"]
+            assert np.array_equal(aligned.view(np.uint32), raligned.view(np.uint32))
+            check_state(ctx, rs.model)
+            if rc == binding.W_TOO_FEW_PAIRS:
+                saw_fallback = True
+            else:
+                assert st.iterations > 0
+            for it in trace:
+                Rcam = mul3f(Rcam, inv3_pose(it["R"]))
+                pcam = (pcam - it["t"]).astype(np.float32)
+            lastT = (-T[:3, 3]).astype(np.float32)
+            if rc != binding.W_TOO_FEW_PAIRS:
+                lastR = I3.copy()
+        assert saw_fallback
+        assert ctx.map_size(binding.MAP_KEYPOINTS) == len(rs.model.lists[mm.KEYPOINTS]) > 0
+
+
+def test_map_tracker_cpp_matches_the_binding(oracle):
+    exe = build.build_map_test()
+    frames, kp = live_frames()
+    with tempfile.TemporaryDirectory() as td:
+        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
+        with open(fin, "wb") as f:
+            f.write(struct.pack("<5if", ROWS, COLS, NFRAMES, MAX_ITER, kp.shape[0], THR))
+            for d in frames:
+                f.write(d.tobytes())
+            f.write(kp.tobytes())
+        subprocess.check_call([exe, fin, fout])
+        raw = open(fout, "rb").read()
+    off = 0
+    with binding.Context(0) as ref:
+        rs = Restatement(oracle, ref)
+        for f in range(1, NFRAMES):
+            rc, iters, nk, npt, nnz = struct.unpack_from("<5i", raw, off)
+            off += 20
+            T = np.frombuffer(raw, np.float32, 16, off).reshape(4, 4)
+            off += 64
+            keyl = np.frombuffer(raw, np.float32, 3 * nk, off).reshape(3, nk)
+            off += 12 * nk
+            cells = np.frombuffer(raw, np.int32, 2 * nnz, off).reshape(nnz, 2)
+            off += 8 * nnz
+            params = binding.default_params(max_nn_dist=0.1, max_iterations=MAX_ITER, threshold=THR, solve=0)
+            rrc, rT, rst, _, _ = rs.frame(frames[f], frames[f - 1], kp, params)
+            assert rc == rrc and iters == rst.iterations, f
+            assert np.array_equal(T.view(np.uint32), rT.view(np.uint32)), f
+            assert np.array_equal(keyl.view(np.uint32), rs.model.list_array(mm.KEYPOINTS).view(np.uint32)), f
+            assert npt == len(rs.model.lists[mm.POINTS])
+            g = rs.model.grid().reshape(-1)
+            nz = np.flatnonzero(g)
+            assert np.array_equal(cells[:, 0], nz) and np.array_equal(cells[:, 1], g[nz]), f
+    assert off == len(raw)
