@@ -43,6 +43,7 @@ SYMBOLS = [
     "icpk_map_reset", "icpk_map_release", "icpk_map_update", "icpk_map_update_points", "icpk_map_set_points",
     "icpk_map_size", "icpk_map_get_list", "icpk_map_get_certainty", "icpk_map_query", "icpk_map_list_to_target",
     "icpk_map_voxel", "icpk_align_to_map",
+    "icpk_bgr_to_gray", "icpk_detect_fast", "icpk_detected_to_cloud",
 ]
 
 # voxel certainty map (map.hpp:9-13)
@@ -53,6 +54,9 @@ MAP_DELTA_CONFIDENCE = 25
 MAP_KEYPOINTS, MAP_POINTS = 0, 1
 MAP_FROM_SOURCE, MAP_FROM_TARGET = 0, 1
 MAP_ADD_CLOUD, MAP_ADD_ASSOCIATED, MAP_ADD_UNASSOCIATED = 0, 1, 2
+
+# FAST key points (SLAM.cpp:256: threshold 60, suppression on, TYPE_7_12)
+FAST_TYPE_5_8, FAST_TYPE_7_12, FAST_TYPE_9_16 = 0, 1, 2
 
 
 class Params(C.Structure):
@@ -210,6 +214,9 @@ def load():
     lib.icpk_map_voxel.argtypes = [fp, ip]
     lib.icpk_map_voxel.restype = None
     lib.icpk_align_to_map.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, fp, C.POINTER(Stats)]
+    lib.icpk_bgr_to_gray.argtypes = [C.c_void_p, u8, C.c_int32, C.c_int32, u8]
+    lib.icpk_detect_fast.argtypes = [C.c_void_p, u8] + [C.c_int32] * 7 + [fp, fp, ip]
+    lib.icpk_detected_to_cloud.argtypes = [C.c_void_p, u16, C.c_int32, C.c_int32, C.c_float, C.c_float, fp, fp, C.c_int32, ip]
     _lib = lib
     return lib
 
@@ -639,6 +646,55 @@ class Context:
         st = Stats()
         rc = self._chk(self._lib.icpk_align_to_map(self._h, C.byref(p), delta, _fp(T), C.byref(st)))
         return T.reshape(4, 4), st, rc
+
+    # -- FAST key points (SLAM.cpp:255-256) and their back-projection (pointcloud.cpp:60-98) ------------------------
+    def bgr_to_gray(self, bgr):
+        """cv::cvtColor(CV_BGR2GRAY) on the device: (rows, cols, 3) uint8 BGR -> (rows, cols) uint8"""
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        if bgr.ndim != 3 or bgr.shape[2] != 3:
+            raise ValueError("(rows, cols, 3) BGR image expected")
+        out = np.empty(bgr.shape[:2], np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        self._chk(self._lib.icpk_bgr_to_gray(self._h, bgr.ctypes.data_as(u8), bgr.shape[0], bgr.shape[1],
+                                             out.ctypes.data_as(u8)))
+        return out
+
+    def detect_fast(self, img, threshold=60, nonmax=True, type=FAST_TYPE_7_12, capacity=None):
+        """cv::FAST on a (rows, cols, 3) BGR or (rows, cols) grey uint8 image.  The key points also stay on the device
+        (input of detected_to_cloud).  Returns (kp_xy (n, 2) float32, response (n,) float32), at most `capacity`
+        entries (None: all of them)."""
+        img = np.ascontiguousarray(img, np.uint8)
+        if img.ndim == 3 and img.shape[2] == 3:
+            ch = 3
+        elif img.ndim == 2:
+            ch = 1
+        else:
+            raise ValueError("(rows, cols, 3) BGR or (rows, cols) grey image expected")
+        rows, cols = img.shape[:2]
+        u8, ip = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+        n = C.c_int32(0)
+        if capacity is None:  # count first, then fetch exactly that many (the list is on the device either way)
+            self._chk(self._lib.icpk_detect_fast(self._h, img.ctypes.data_as(u8), rows, cols, ch, int(threshold),
+                                                 int(bool(nonmax)), int(type), 0, None, None, C.byref(n)))
+            capacity = n.value
+        kp = np.zeros((max(int(capacity), 1), 2), np.float32)
+        resp = np.zeros(max(int(capacity), 1), np.float32)
+        self._chk(self._lib.icpk_detect_fast(self._h, img.ctypes.data_as(u8), rows, cols, ch, int(threshold),
+                                             int(bool(nonmax)), int(type), int(capacity), _fp(kp), _fp(resp), C.byref(n)))
+        m = min(n.value, int(capacity))
+        self.detected_count = n.value
+        return kp[:m].copy(), resp[:m].copy()
+
+    def detected_to_cloud(self, depth, R=None, t=None, which=0, fx=468.60, cx=318.27):
+        """the detected key points back-projected from `depth` (pointcloud.cpp:60-98), posed by p <- fl32(fl32(R p) + t)
+        (None: identity / zero) and made the context's source (which 0) or target (1).  Returns the point count."""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        Rm = _f(np.eye(3) if R is None else R).reshape(9)
+        tv = _f(np.zeros(3) if t is None else t).reshape(3)
+        n = C.c_int32(0)
+        self._chk(self._lib.icpk_detected_to_cloud(self._h, depth.ctypes.data_as(C.POINTER(C.c_uint16)), depth.shape[0],
+                                                   depth.shape[1], fx, cx, _fp(Rm), _fp(tv), int(which), C.byref(n)))
+        return n.value
 
     def align_query_sharded(self, params=None, **kw):
         """One pair, queries sharded over the communicator's ranks (collective call): this context's source is the

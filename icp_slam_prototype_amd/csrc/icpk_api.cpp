@@ -961,6 +961,7 @@ void icpk_destroy(icpk_ctx* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   icpk_comm_release(ctx);
   icpk_map_free(ctx);
+  icpk_fast_free(ctx);
   for (icpk_ctx* sl : ctx->slots) icpk_destroy(sl);
   ctx->slots.clear();
   for (hipStream_t st : {ctx->setup_stream[0], ctx->setup_stream[1]})

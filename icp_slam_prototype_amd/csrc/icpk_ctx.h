@@ -160,6 +160,8 @@ struct icpk_ctx {
   struct icpk_comm_state* comm = nullptr;
   // voxel certainty map (icpk_map.cpp); null until the first icpk_map_* call
   struct icpk_map_state* map = nullptr;
+  // FAST key points (icpk_fast.cpp); null until the first icpk_detect_fast / icpk_bgr_to_gray call
+  struct icpk_fast_state* fast = nullptr;
   int* qcount = nullptr;     // query counting sort by cell: counts and starts, grid_max_cells + 1 each
   int* qstart = nullptr;
   bool qcount_dirty = false; // a counting sort was cut short: clear the whole count table before the next one
@@ -203,6 +205,7 @@ int icpk_host_ensure_cloud(icpk_ctx* ctx, icpk::Cloud& c, int n);
 int icpk_host_target_replaced(icpk_ctx* ctx);
 void icpk_comm_release(icpk_ctx* ctx);  // called by icpk_destroy
 void icpk_map_free(icpk_ctx* ctx);      // called by icpk_destroy (icpk_map.cpp)
+void icpk_fast_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_fast.cpp)
 // the working source planes hold the cloud icpk_get_source would return (a device loop may leave them to be unpacked)
 int icpk_host_ensure_unpacked(icpk_ctx* ctx);
 int icpk_comm_allreduce_device(icpk_ctx* ctx, double* dev, int n);  // in-stream sum over the ranks (icpk_comm.cpp)

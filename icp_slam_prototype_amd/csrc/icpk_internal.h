@@ -431,6 +431,20 @@ void launch_grid_tscatter_batch(const SetupBatchOf<TscatterArgs>& b, int count, 
 void launch_grid_qscatter_batch(const SetupBatchOf<QscatterArgs>& b, int count, hipStream_t s);
 void launch_grid_tqscatter(const TscatterArgs& t, const QscatterArgs& q, hipStream_t s);
 
+// kernels_fast.hip -- K8: FAST key points (SLAM.cpp:255-256) and their back-projection (pointcloud.cpp:60-98)
+int fast_tiles_x(int cols);  // tile columns of a cols-wide image (64-pixel tiles)
+// img: rows x cols x channels bytes on the device; pattern 12 or 16; masks / counts: rows x fast_tiles_x(cols) entries;
+// score: rows x cols bytes; kp / resp: room for every candidate pixel; *total (device) = the number of key points
+void launch_fast_detect(const uint8_t* img, int rows, int cols, int channels, int threshold, int nonmax, int pattern,
+                        unsigned long long* masks, int* counts, uint8_t* score, int* total, float* kp, float* resp,
+                        hipStream_t s);
+void launch_bgr_to_gray(const uint8_t* bgr, int n, uint8_t* out, hipStream_t s);
+// n key points (x, y) back-projected from depth and posed, into x / y / z (and x2 / y2 / z2 unless null) padded with
+// `pad` up to the next multiple of NN_TILE; the count to *n_dev and the mapped word *n_host (or null)
+void launch_fast_cloud(const float* kp, int n, const uint16_t* depth, int rows, int cols, float fx, float cx, const Rt& rt,
+                       float* x, float* y, float* z, float* x2, float* y2, float* z2, float pad, int* n_dev, int* n_host,
+                       hipStream_t s);
+
 // kernels_map.hip -- the voxel certainty map (map.hpp, map.cpp)
 constexpr int MAP_DIM = 300;                              // map.hpp:9 MAP_HEIGHT
 constexpr int MAP_CELLS = MAP_DIM * MAP_DIM * MAP_DIM;    // keys < 2^25

@@ -12,8 +12,8 @@
 //     :98-268 loop, :237/:246 pose update), fed with raw CV_16UC1 depth buffers
 //   * icp::makeRotationMatrix / meanSquareError / toEulerianAngle helpers with the
 //     reference's names and argument meaning (icp.hpp:25-27, SLAM.hpp:44-46)
-//   * icp::Map / icp::MapTracker (icp_map.hpp, included at the end) -- the voxel certainty
-//     map and the live getTransformation against it
+//   * icp::Map / icp::MapTracker / icp::detectFAST (icp_map.hpp, included at the end) -- the
+//     voxel certainty map, the live getTransformation against it, and FAST on the device
 // icp_opencv_adapter.hpp adds the exact cv::Mat signature when OpenCV is present.
 //
 // Header-only; link with -licpk.  Errors: status codes of icpk.h, never exceptions

@@ -3,8 +3,10 @@
 //   * icp::Map         -- map::Map (map.hpp, map.cpp) on an Engine's GPU: update per rule, isOccupied,
 //                         getVoxelCoordinates, list access
 //   * icp::MapTracker  -- the live icp::getTransformation (icp.cpp:27-271): the frame's key points aligned against the
-//                         map's key points, the rejected ones folded back into the map.  FAST is OpenCV's and stays
-//                         outside: the caller hands in the key-point pixels (cv::KeyPoint::pt as (x, y) pairs).
+//                         map's key points, the rejected ones folded back into the map.  Key points either come from
+//                         the caller (cv::KeyPoint::pt as (x, y) pairs) or are detected on the device from the colour
+//                         frame (SLAM.cpp:255-256, K8)
+//   * icp::detectFAST  -- cv::cvtColor(BGR -> GRAY) + cv::FAST on the device (icpk_detect_fast)
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -14,6 +16,29 @@
 #include "icp_align.hpp"
 
 namespace icp {
+
+// cv::FAST settings (SLAM.cpp:256: threshold 60, suppression on, TYPE_7_12)
+struct FastSettings {
+  int threshold = 60;
+  bool nonmax = true;
+  int type = ICPK_FAST_TYPE_7_12;
+};
+
+// SLAM.cpp:255-256 on the device: image rows x cols, channels 3 (BGR) or 1 (grey).  kp_xy: (x, y) per key point in
+// FAST_t's order; response (or null): the score of each.  The key points also stay on the engine's device as its
+// detected list (icpk_detected_to_cloud).  Returns a status of icpk.h.
+inline int detectFAST(Engine& eng, const uint8_t* image, int rows, int cols, int channels, std::vector<float>& kp_xy,
+                      std::vector<float>* response = nullptr, const FastSettings& s = FastSettings()) {
+  const size_t cap = rows > 6 && cols > 6 ? (size_t)(rows - 6) * (size_t)(cols - 6) : 0;  // every candidate pixel
+  kp_xy.resize(2 * cap + 2);
+  if (response) response->resize(cap + 1);
+  int32_t n = 0;
+  const int rc = icpk_detect_fast(eng.ctx(), image, rows, cols, channels, s.threshold, s.nonmax ? 1 : 0, s.type,
+                                  (int32_t)cap, kp_xy.data(), response ? response->data() : nullptr, &n);
+  kp_xy.resize(rc == ICPK_OK ? 2 * (size_t)n : 0);
+  if (response) response->resize(rc == ICPK_OK ? (size_t)n : 0);
+  return rc;
+}
 
 // map::Map on the GPU of an Engine (one map per Engine; the first call allocates it, empty)
 class Map {
@@ -116,12 +141,58 @@ class MapTracker {
     pose(kp.data(), n, x, y, z);  // icp.cpp:70-71
     int rc = icpk_set_source(c, x.data(), y.data(), z.data(), n);
     if (rc != ICPK_OK) return rc;
+    return alignToMap(maxIterations, threshold, T);
+  }
+
+  // The same with the key points of the colour frame detected on the device (SLAM.cpp:255-256, `fast`): color is
+  // c_rows x c_cols with channels 3 (BGR) or 1 (grey), and may differ in size from the depth images.  As the reference,
+  // the first call back-projects the CURRENT colour frame's key points from `previous` for the map seed (icp.cpp:38-39,
+  // 58-62) and from `data` for the alignment (:70-71).  Detection -> cloud -> map update / alignment without the key
+  // points crossing PCIe.
+  int getTransformation(const uint16_t* data, const uint16_t* previous, int rows, int cols, const uint8_t* color,
+                        int c_rows, int c_cols, int channels, int maxIterations, float threshold, float T[16]) {
+    icpk_ctx* c = eng_.ctx();
+    for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.f : 0.f;
+    int rc = icpk_detect_fast(c, color, c_rows, c_cols, channels, fast.threshold, fast.nonmax ? 1 : 0, fast.type, 0, nullptr,
+                              nullptr, nullptr);
+    if (rc != ICPK_OK) return rc;
+    if (map.size(ICPK_MAP_POINTS) == 0) {  // icp.cpp:47-68
+      if (!previous) return ICPK_E_ARG;
+      reset();
+      rc = icpk_detected_to_cloud(c, previous, rows, cols, fx_, cx_, cameraRotation, cameraPosition, 0, nullptr);  // :58-59
+      if (rc == ICPK_OK) rc = map.updateFrom(ICPK_MAP_ADD_CLOUD, ICPK_MAP_FROM_SOURCE, ICPK_MAP_MAX_CONFIDENCE);  // :62
+      if (rc != ICPK_OK) return rc;
+      const float no_offset[3] = {0.f, 0.f, 0.f};
+      rc = icpk_backproject(c, previous, rows, cols, fx_, cx_, no_offset, 1);  // icp.cpp:39
+      if (rc < 0) return rc;
+      rc = icpk_transform_target(c, cameraRotation, cameraPosition);
+      if (rc == ICPK_OK) rc = map.setPoints(ICPK_MAP_FROM_TARGET);  // :63
+      if (rc != ICPK_OK) return rc;
+    }
+    rc = icpk_detected_to_cloud(c, data, rows, cols, fx_, cx_, cameraRotation, cameraPosition, 0, nullptr);  // :70-71
+    if (rc != ICPK_OK) return rc;
+    return alignToMap(maxIterations, threshold, T);
+  }
+
+  Map map;
+  FastSettings fast;  // the colour overload's cv::FAST settings
+  float cameraRotation[9];
+  float lastRotation[9];
+  float cameraPosition[3];
+  float lastTranslation[3];
+  AlignParams params;
+  icpk_stats lastStats{};
+
+ private:
+  // icp.cpp:98-271 on the engine's source against the map, then the pose kept as icp::Tracker keeps it
+  int alignToMap(int maxIterations, float threshold, float T[16]) {
+    icpk_ctx* c = eng_.ctx();
     params.max_iterations = maxIterations;
     params.threshold = threshold;
     std::memcpy(params.last_rotation, lastRotation, sizeof(lastRotation));
     std::memcpy(params.last_translation, lastTranslation, sizeof(lastTranslation));
     icpk_stats st;
-    rc = icpk_align_to_map(c, &params, ICPK_MAP_DELTA_CONFIDENCE, T, &st);
+    const int rc = icpk_align_to_map(c, &params, ICPK_MAP_DELTA_CONFIDENCE, T, &st);
     if (rc < 0) return rc;
     lastStats = st;
     int32_t niter = 0;
@@ -142,15 +213,6 @@ class MapTracker {
     return rc;
   }
 
-  Map map;
-  float cameraRotation[9];
-  float lastRotation[9];
-  float cameraPosition[3];
-  float lastTranslation[3];
-  AlignParams params;
-  icpk_stats lastStats{};
-
- private:
   // PointCloud::rotate + translate (pointcloud.cpp:321-359) as the device does it: p' = fl32(fl32(R p) + t)
   void pose(const float* xyz, int n, std::vector<float>& x, std::vector<float>& y, std::vector<float>& z) const {
     x.resize((size_t)(n > 0 ? n : 1));

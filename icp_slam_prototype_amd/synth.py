@@ -152,3 +152,70 @@ def lattice_wall(rows=60, cols=80, z=2.0, shift_px=0.5):
     src = tgt.copy()
     src[0] += np.float32(shift_px) * step
     return dict(source=src.astype(np.float32), target=tgt.astype(np.float32))
+
+
+def render_room_color(rows, cols, R_wc, c_w, fx=FX, cx=CX, noise_sigma=0.0, rng=None, cell=0.3):
+    """BGR colour frame of the room render_room_depth draws, registered to it pixel for pixel (same rays, same
+    surfaces; the depth camera's pinhole).  Texture for FAST: on every plane, a lattice of `cell`-metre squares, most
+    of which hold one bright rectangle on the darker plane -- isolated rectangles give L-corners (an ideal
+    checkerboard's X-junctions are no FAST corners).  The sphere is plain, the background (no surface within the depth
+    range) dark.  noise_sigma: Gaussian noise per channel, in grey levels.  Returns (rows, cols, 3) uint8."""
+    v, u = np.mgrid[0:rows, 0:cols].astype(np.float64)
+    d_cam = np.stack([(u - float(cx)) / float(fx), (v - float(cx)) / float(fx), np.ones_like(u)], -1)
+    w = d_cam @ np.asarray(R_wc, np.float64).T
+    o = np.asarray(c_w, np.float64)
+    t_best = np.full((rows, cols), np.inf)
+    surf = np.full((rows, cols), -1)
+
+    def hit(t, k):
+        nonlocal t_best
+        better = t < t_best
+        t_best = np.where(better, t, t_best)
+        surf[better] = k
+
+    planes = [([0, 1, 0], 1.3), ([0, 0, 1], 3.6), ([-1, 0, 0], 2.1)]  # floor, back wall, left wall
+    for k, (n, h) in enumerate(planes):
+        n = np.asarray(n, np.float64)
+        den = w @ n
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = (h - o @ n) / den
+        t[~(t > 1e-6)] = np.inf
+        hit(t, k)
+    sc = np.array([0.35, 0.45, 2.3])
+    sr = 0.55
+    oc = o - sc
+    a = np.einsum("ijk,ijk->ij", w, w)
+    b = 2.0 * (w @ oc)
+    cc = oc @ oc - sr * sr
+    disc = b * b - 4 * a * cc
+    with np.errstate(invalid="ignore"):
+        ts = (-b - np.sqrt(disc)) / (2 * a)
+    ts[~(disc > 0) | ~(ts > 1e-6)] = np.inf
+    hit(ts, 3)
+    d = np.rint(t_best * 5000.0)
+    surf[~np.isfinite(d) | (d < 1000) | (d > 25000)] = -1  # where render_room_depth has no depth
+    p = o + w * np.where(np.isfinite(t_best), t_best, 0.0)[..., None]
+    # surface coordinates (metres) of the three planes: floor (x, z), back wall (x, y), left wall (z, y)
+    su = np.select([surf == 0, surf == 1, surf == 2], [p[..., 0], p[..., 0], p[..., 2]], 0.0)
+    sv = np.select([surf == 0, surf == 1, surf == 2], [p[..., 2], p[..., 1], p[..., 1]], 0.0)
+    iu = np.floor(su / cell).astype(np.int64)
+    iv = np.floor(sv / cell).astype(np.int64)
+    fu = su / cell - iu
+    fv = sv / cell - iv
+    hsh = (iu * 73856093) ^ (iv * 19349663) ^ (surf.astype(np.int64) * 83492791)
+    hsh = (hsh ^ (hsh >> 13)) & 0xffff
+    lo_u = 0.10 + 0.15 * ((hsh & 0xf) / 15.0)
+    lo_v = 0.10 + 0.15 * (((hsh >> 4) & 0xf) / 15.0)
+    hi_u = lo_u + 0.30 + 0.25 * (((hsh >> 8) & 0xf) / 15.0)
+    hi_v = lo_v + 0.30 + 0.25 * (((hsh >> 12) & 0xf) / 15.0)
+    rect = (surf >= 0) & (surf <= 2) & (hsh % 5 != 0) & (fu > lo_u) & (fu < hi_u) & (fv > lo_v) & (fv < hi_v)
+    base = np.array([[70, 60, 50], [55, 65, 75], [60, 70, 55], [120, 130, 140]], np.float64)  # B, G, R per surface
+    img = np.full((rows, cols, 3), 25.0)
+    for k in range(4):
+        img[surf == k] = base[k]
+    tint = np.stack([(hsh & 0x3f), ((hsh >> 6) & 0x3f), ((hsh >> 10) & 0x3f)], -1).astype(np.float64)
+    img = np.where(rect[..., None], 170.0 + tint, img)
+    if noise_sigma > 0:
+        rng = rng if rng is not None else np.random.default_rng(0)
+        img = img + rng.normal(0.0, noise_sigma, img.shape)
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)

@@ -431,6 +431,37 @@ void icpk_map_voxel(const float p[3], int32_t v[3]);
  * associations.  Reference and Kabsch flavours (ICPK_E_ARG for point-to-plane: the map has no normals). */
 int icpk_align_to_map(icpk_ctx *ctx, const icpk_params *p, int32_t delta, float T_out[16], icpk_stats *stats);
 
+/* ---- FAST key points on the device (K8): SLAM.cpp:255-256 + pointcloud.cpp:60-98 -------------------------------
+ * cv::cvtColor(BGR -> GRAY) then cv::FAST(gray, keypoints, threshold, nonmax, type), restated from OpenCV 3.2's scalar
+ * FAST_t (parity with OpenCV itself is UNPINNED: no OpenCV build is available to compare with).
+ *   grey     Y = (1868 B + 9617 G + 4899 R + 8192) >> 14 (8-bit BGR, interleaved, row-major)
+ *   corners  pixels with 3 <= y <= rows - 4, 3 <= x <= cols - 4; threshold clamped to [0, 255]; OpenCV's quick test on
+ *            circle positions (0,8), (2,10), (4,12), (6,14), then (1,9) ... (7,15) of the wrapped table (for 7_12 this
+ *            rejects some pixels with a qualifying arc), then more than P/2 consecutive darker / brighter pixels
+ *   score    M - 1, M = the largest over the P arcs of P/2 + 1 circle pixels of max(min(v - x), min(x - v))
+ *   nonmax   kept if its score is strictly greater than the score of each of its 8 neighbours (non-corners score 0);
+ *            without suppression every corner is kept with response 0
+ *   order    row-major (y ascending, then x), key point = (x, y) as floats */
+#define ICPK_FAST_TYPE_5_8 0 /* out of scope: ICPK_E_ARG */
+#define ICPK_FAST_TYPE_7_12 1
+#define ICPK_FAST_TYPE_9_16 2
+/* test hook: the grey conversion alone on the device; bgr: rows x cols x 3 bytes, gray_out: rows x cols bytes */
+int icpk_bgr_to_gray(icpk_ctx *ctx, const uint8_t *bgr, int32_t rows, int32_t cols, uint8_t *gray_out);
+/* FAST on a host image (channels 3: BGR, converted to grey first; 1: grey).  The key points stay on the device as the
+ * context's detected list (input of icpk_detected_to_cloud).  kp_xy (2 floats per key point) and response may be NULL;
+ * otherwise at most `capacity` entries are written.  *n_out (may be NULL) = the full count.  ICPK_E_ARG for a bad type,
+ * channel count, size or a NULL image; an image with fewer than 7 rows or columns has no key points. */
+int icpk_detect_fast(icpk_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t channels,
+                     int32_t threshold, int32_t nonmax, int32_t type, int32_t capacity, float *kp_xy, float *response,
+                     int32_t *n_out);
+/* The detected list back-projected from a depth image (d_rows x d_cols CV_16UC1, may differ in size from the colour
+ * image) by icpk_backproject_keypoints's rule, posed by p <- fl32(fl32(R p) + t) (K3's arithmetic), and made the
+ * context's source (which = 0) or target (which = 1), all on the device with one host wait.  Equivalent, bit for bit,
+ * to icpk_backproject_keypoints on the detected list, the pose on the host, then icpk_set_source / icpk_set_target.
+ * *n_out (may be NULL) = the number of points.  ICPK_E_NOT_SET before the first icpk_detect_fast. */
+int icpk_detected_to_cloud(icpk_ctx *ctx, const uint16_t *depth, int32_t d_rows, int32_t d_cols, float fx, float cx,
+                           const float R[9], const float t[3], int32_t which, int32_t *n_out);
+
 /* ---- point-to-plane extension (BASELINE config 3; not in the reference) ---- */
 #define ICPK_NORMALS_CROSS 0     /* normalised cross product of back-projected central differences */
 #define ICPK_NORMALS_REFERENCE 1 /* SLAM.cpp:421-425 getNormalMap formula, interior pixels          */

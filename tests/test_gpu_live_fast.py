@@ -1,0 +1,193 @@
+"""The live path with key points detected on the device (K8): colour + depth frames in, T out, map updated.  Ten
+rendered frames with the camera motion of tests/test_gpu_map.py's live sequence, one fallback frame, the first call
+seeding the map.  The device-FAST path (icpk_detect_fast -> icpk_detected_to_cloud -> icpk_map_update /
+icpk_align_to_map) must equal, bit for bit, the existing path fed with the model's key points posed on the host; the
+C++ MapTracker colour overload must write the same results."""
+import os
+import struct
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import fast_model as fm
+import map_model as mm
+from icp_slam_prototype_amd import binding, build, synth
+
+pytestmark = pytest.mark.gpu
+
+ROWS, COLS, NFRAMES, MAX_ITER, THR = 240, 320, 10, 10, 1e-5
+FALLBACK_FRAME = 5
+I3 = np.eye(3, dtype=np.float32)
+P5 = np.full(3, 5, np.float32)
+
+
+def live_color_frames():
+    rng = np.random.default_rng(3)
+    depth, color = [], []
+    for k in range(NFRAMES):  # camera turning by 0.4 degree and moving 1 cm per frame
+        Rm = synth.rot_xyz_deg(0, 0.4 * k, 0)
+        c = np.array([0.01 * k, 0.0, 0.005 * k])
+        depth.append(synth.render_room_depth(ROWS, COLS, Rm, c, noise_sigma=0.001, rng=rng).astype(np.uint16))
+        color.append(synth.render_room_color(ROWS, COLS, Rm, c, noise_sigma=2.0, rng=np.random.default_rng(100 + k)))
+    return depth, color
+
+
+def mul3f(A, B):
+    A = A.astype(np.float64)
+    B = B.astype(np.float64)
+    return ((A[:, 0:1] * B[0:1, :] + A[:, 1:2] * B[1:2, :]) + A[:, 2:3] * B[2:3, :]).astype(np.float32)
+
+
+def inv3_pose(m):
+    a, b, c, d, e, f, g, h, i = (float(v) for v in np.asarray(m, np.float32).reshape(9))
+    det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g)
+    s = 1.0 / det if det != 0.0 else 0.0
+    t = [(e * i - f * h) * s, (c * h - b * i) * s, (b * f - c * e) * s,
+         (f * g - d * i) * s, (a * i - c * g) * s, (c * d - a * f) * s,
+         (d * h - e * g) * s, (b * g - a * h) * s, (a * e - b * d) * s]
+    return np.array(t, np.float64).astype(np.float32).reshape(3, 3)
+
+
+class Pose:
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.R, self.p, self.lastR, self.lastT = I3.copy(), P5.copy(), I3.copy(), np.zeros(3, np.float32)
+
+    def params(self, f):
+        p = binding.default_params(max_nn_dist=0.1, max_iterations=MAX_ITER, threshold=THR, solve=0)
+        if f == FALLBACK_FRAME:
+            p.min_pairs = 1 << 30
+        p.last_rotation[:] = [float(v) for v in self.lastR.reshape(9)]
+        p.last_translation[:] = [float(v) for v in self.lastT]
+        return p
+
+    def update(self, trace, T, rc):  # icp.cpp:235-246, 260-261
+        for it in trace:
+            self.R = mul3f(self.R, inv3_pose(it["R"]))
+            self.p = (self.p - it["t"]).astype(np.float32)
+        self.lastT = (-T[:3, 3]).astype(np.float32)
+        if rc != binding.W_TOO_FEW_PAIRS:
+            self.lastR = I3.copy()
+
+
+def device_fast_frame(ctx, pose, f, data, previous, color):
+    ctx.detect_fast(color, capacity=0)  # SLAM.cpp:255-256, the key points stay on the device
+    if ctx.map_size(binding.MAP_POINTS) == 0:  # icp.cpp:47-68
+        pose.reset()
+        ctx.detected_to_cloud(previous, pose.R, pose.p, which=0)
+        ctx.map_update(binding.MAP_ADD_CLOUD, 180, binding.MAP_FROM_SOURCE)
+        ctx.backproject(previous, which=1)
+        ctx.transform_target(I3, P5)
+        ctx.map_set_points(binding.MAP_FROM_TARGET)
+    ctx.detected_to_cloud(data, pose.R, pose.p, which=0)
+    T, st, rc = ctx.align_to_map(pose.params(f), delta=25)
+    trace = ctx.get_trace(MAX_ITER)
+    pose.update(trace, T, rc)
+    return rc, T, st, trace
+
+
+def host_kp_frame(oracle, ctx, pose, f, data, previous, color):
+    kp, _ = fm.detect(color, 60, True, fm.TYPE_7_12)
+    if ctx.map_size(binding.MAP_POINTS) == 0:
+        pose.reset()
+        kprev = oracle.transform_points(binding.backproject_keypoints(previous, kp)[0], I3, P5)
+        ctx.map_update_points(binding.MAP_ADD_CLOUD, kprev, 180)
+        ctx.backproject(previous, which=1)
+        ctx.transform_target(I3, P5)
+        ctx.map_set_points(binding.MAP_FROM_TARGET)
+    ctx.set_source(oracle.transform_points(binding.backproject_keypoints(data, kp)[0], pose.R, pose.p))
+    T, st, rc = ctx.align_to_map(pose.params(f), delta=25)
+    trace = ctx.get_trace(MAX_ITER)
+    pose.update(trace, T, rc)
+    return rc, T, st, trace
+
+
+def nonzero_cells(ctx):
+    g = ctx.map_get_certainty().reshape(-1)
+    nz = np.flatnonzero(g)
+    return nz, g[nz]
+
+
+def same(a, b):
+    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+
+
+def reference_run(oracle, depth, color):
+    """the existing path: per frame (rc, T, iterations, key-point list, point-list length, non-zero cells)"""
+    out = []
+    with binding.Context(0) as ref:
+        ref.map_reset()
+        pose = Pose()
+        for f in range(1, NFRAMES):
+            rc, T, st, _ = host_kp_frame(oracle, ref, pose, f, depth[f], depth[f - 1], color[f])
+            out.append((rc, T, st.iterations, ref.map_get_list(mm.KEYPOINTS), ref.map_size(binding.MAP_POINTS),
+                        nonzero_cells(ref), ref.map_get_list(mm.POINTS)))
+    return out
+
+
+def test_device_fast_live_sequence_equals_host_keypoint_path(oracle):
+    depth, color = live_color_frames()
+    want = reference_run(oracle, depth, color)
+    saw_fallback = False
+    with binding.Context(0) as ctx:
+        ctx.map_reset()
+        pose = Pose()
+        for f in range(1, NFRAMES):
+            rc, T, st, trace = device_fast_frame(ctx, pose, f, depth[f], depth[f - 1], color[f])
+            wrc, wT, witer, wkey, wnpt, (wnz, wval), wpts = want[f - 1]
+            assert rc == wrc and st.iterations == witer, (f, rc, wrc, st.iterations, witer)
+            assert same(T, wT), f
+            assert same(ctx.map_get_list(mm.KEYPOINTS), wkey), f
+            assert same(ctx.map_get_list(mm.POINTS), wpts), f
+            nz, val = nonzero_cells(ctx)
+            assert np.array_equal(nz, wnz) and np.array_equal(val, wval), f
+            if rc == binding.W_TOO_FEW_PAIRS:
+                saw_fallback = True
+            else:
+                assert st.iterations > 0 and st.final_pairs > 0
+        assert saw_fallback
+        assert ctx.map_size(binding.MAP_KEYPOINTS) > 0
+
+
+def test_map_tracker_fast_cpp_matches_the_binding(oracle):
+    exe = build.build_map_fast_test()
+    depth, color = live_color_frames()
+    want = reference_run(oracle, depth, color)
+    with tempfile.TemporaryDirectory() as td:
+        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
+        with open(fin, "wb") as fh:
+            fh.write(struct.pack("<5if", ROWS, COLS, NFRAMES, MAX_ITER, FALLBACK_FRAME, THR))
+            for d in depth:
+                fh.write(d.tobytes())
+            for c in color:
+                fh.write(np.ascontiguousarray(c).tobytes())
+        subprocess.check_call([exe, fin, fout])
+        raw = open(fout, "rb").read()
+        kraw = open(fout + ".kp", "rb").read()
+    off = 0
+    for f in range(1, NFRAMES):
+        rc, iters, nk, npt, nnz = struct.unpack_from("<5i", raw, off)
+        off += 20
+        T = np.frombuffer(raw, np.float32, 16, off).reshape(4, 4)
+        off += 64
+        keyl = np.frombuffer(raw, np.float32, 3 * nk, off).reshape(3, nk)
+        off += 12 * nk
+        cells = np.frombuffer(raw, np.int32, 2 * nnz, off).reshape(nnz, 2)
+        off += 8 * nnz
+        wrc, wT, witer, wkey, wnpt, (wnz, wval), _ = want[f - 1]
+        assert rc == wrc and iters == witer, f
+        assert same(T, wT), f
+        assert same(keyl, wkey), f
+        assert npt == wnpt
+        assert np.array_equal(cells[:, 0], wnz) and np.array_equal(cells[:, 1], wval), f
+    assert off == len(raw)
+    # icp::detectFAST on the last frame equals the model
+    (nk,) = struct.unpack_from("<i", kraw, 0)
+    kp = np.frombuffer(kraw, np.float32, 2 * nk, 4).reshape(nk, 2)
+    resp = np.frombuffer(kraw, np.float32, nk, 4 + 8 * nk)
+    mkp, mresp = fm.detect(color[-1], 60, True, fm.TYPE_7_12)
+    assert same(kp, mkp) and same(resp, mresp)
