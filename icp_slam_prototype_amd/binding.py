@@ -23,7 +23,7 @@ MAX_NN_KEYPOINT_DISTANCE = 0.1  # icp.hpp:10
 NORMALS_CROSS, NORMALS_REFERENCE = 0, 1
 SUBSAMPLE_FACTOR = 40  # pointcloud.hpp:11
 NP2L = 28
-NN_EXACT, NN_FILTERED, NN_PRUNED, NN_GRID = 0, 1, 2, 3
+NN_EXACT, NN_FILTERED, NN_PRUNED, NN_GRID, NN_MAP = 0, 1, 2, 3, 4
 NSUM = 19
 
 # every symbol include/icpk.h declares (tests/test_abi.py checks the header against this list)
@@ -42,7 +42,7 @@ SYMBOLS = [
     "icpk_comm_barrier", "icpk_align_query_sharded",
     "icpk_map_reset", "icpk_map_release", "icpk_map_update", "icpk_map_update_points", "icpk_map_set_points",
     "icpk_map_size", "icpk_map_get_list", "icpk_map_get_certainty", "icpk_map_query", "icpk_map_list_to_target",
-    "icpk_map_voxel", "icpk_align_to_map",
+    "icpk_map_voxel", "icpk_align_to_map", "icpk_map_nearest", "icpk_map_lookup_to_target", "icpk_align_to_map_dense",
     "icpk_bgr_to_gray", "icpk_detect_fast", "icpk_detected_to_cloud",
 ]
 
@@ -54,6 +54,7 @@ MAP_DELTA_CONFIDENCE = 25
 MAP_KEYPOINTS, MAP_POINTS = 0, 1
 MAP_FROM_SOURCE, MAP_FROM_TARGET = 0, 1
 MAP_ADD_CLOUD, MAP_ADD_ASSOCIATED, MAP_ADD_UNASSOCIATED = 0, 1, 2
+MAP_NN_EMPTY, MAP_NN_NONE = -1, -2  # icpk_map_nearest: an empty voxel's zero point won / nothing beat 0.75
 
 # FAST key points (SLAM.cpp:256: threshold 60, suppression on, TYPE_7_12)
 FAST_TYPE_5_8, FAST_TYPE_7_12, FAST_TYPE_9_16 = 0, 1, 2
@@ -214,6 +215,9 @@ def load():
     lib.icpk_map_voxel.argtypes = [fp, ip]
     lib.icpk_map_voxel.restype = None
     lib.icpk_align_to_map.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, fp, C.POINTER(Stats)]
+    lib.icpk_map_nearest.argtypes = [C.c_void_p, fp, fp, fp, C.c_int32, fp, ip, ip]
+    lib.icpk_map_lookup_to_target.argtypes = [C.c_void_p]
+    lib.icpk_align_to_map_dense.argtypes = lib.icpk_align_to_map.argtypes
     lib.icpk_bgr_to_gray.argtypes = [C.c_void_p, u8, C.c_int32, C.c_int32, u8]
     lib.icpk_detect_fast.argtypes = [C.c_void_p, u8] + [C.c_int32] * 7 + [fp, fp, ip]
     lib.icpk_detected_to_cloud.argtypes = [C.c_void_p, u16, C.c_int32, C.c_int32, C.c_float, C.c_float, fp, fp, C.c_int32, ip]
@@ -645,6 +649,33 @@ class Context:
         T = np.zeros(16, np.float32)
         st = Stats()
         rc = self._chk(self._lib.icpk_align_to_map(self._h, C.byref(p), delta, _fp(T), C.byref(st)))
+        return T.reshape(4, 4), st, rc
+
+    def map_nearest(self, pts):
+        """getNearestMappedPoint (icp.cpp:371-473, K9) per point: (dist float32, list int32, index int32); list is
+        MAP_KEYPOINTS / MAP_POINTS, MAP_NN_EMPTY (the zero point of an empty voxel won) or MAP_NN_NONE (dist 0.75)."""
+        x, y, z = (_f(pts[k]) for k in range(3))
+        n = x.size
+        d = np.zeros(n, np.float32)
+        lst = np.zeros(n, np.int32)
+        idx = np.zeros(n, np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._chk(self._lib.icpk_map_nearest(self._h, _fp(x), _fp(y), _fp(z), n, _fp(d), lst.ctypes.data_as(ip),
+                                             idx.ctypes.data_as(ip)))
+        return d, lst, idx
+
+    def map_lookup_to_target(self):
+        """the target becomes [key points | points | (0, 0, 0)]: what NN_MAP sweeps index"""
+        self._chk(self._lib.icpk_map_lookup_to_target(self._h))
+
+    def align_to_map_dense(self, params=None, delta=MAP_DELTA_CONFIDENCE, **kw):
+        """icp.cpp:155-257 with the mapped association: the context's source vs the map's lookup target (the context's
+        target is replaced), then (delta > 0) the last sweep's accepted points through ADD_ASSOCIATED.
+        Returns (T, stats, rc)."""
+        p = params if params is not None else default_params(**kw)
+        T = np.zeros(16, np.float32)
+        st = Stats()
+        rc = self._chk(self._lib.icpk_align_to_map_dense(self._h, C.byref(p), delta, _fp(T), C.byref(st)))
         return T.reshape(4, 4), st, rc
 
     # -- FAST key points (SLAM.cpp:255-256) and their back-projection (pointcloud.cpp:60-98) ------------------------

@@ -12,7 +12,7 @@ LIB = os.path.join(LIBDIR, "libicpk.so")
 
 SOURCES = ["icpk_api.cpp", "icpk_comm.cpp", "kernels_nn.hip", "kernels_reduce.hip", "kernels_transform.hip",
            "kernels_backproject.hip", "kernels_sort.hip", "kernels_nn_pruned.hip", "kernels_loop.hip", "kernels_grid.hip", "kernels_frontend.hip",
-           "icpk_map.cpp", "kernels_map.hip", "icpk_fast.cpp", "kernels_fast.hip"]
+           "icpk_map.cpp", "kernels_map.hip", "icpk_fast.cpp", "kernels_fast.hip", "kernels_map_nn.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -114,6 +114,23 @@ def build_map_fast_test(force=False):
     return MAP_FAST_TEST
 
 
+MAP_DENSE_TEST = os.path.join(LIBDIR, "test_map_tracker_dense")
+
+
+def build_map_dense_test(force=False):
+    """Host-only C++ program over icp::MapTracker with dense = true (g++, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_map_tracker_dense.cpp")
+    hdrs = [os.path.join(HERE, "include", h) for h in ("icp_align.hpp", "icp_map.hpp")]
+    build()
+    newest = max(os.path.getmtime(p) for p in [src, LIB] + hdrs)
+    if not force and os.path.exists(MAP_DENSE_TEST) and os.path.getmtime(MAP_DENSE_TEST) >= newest:
+        return MAP_DENSE_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", MAP_DENSE_TEST])
+    return MAP_DENSE_TEST
+
+
 FAKE_RCCL = os.path.join(LIBDIR, "libfake_rccl.so")
 
 
@@ -136,3 +153,4 @@ if __name__ == "__main__":
     print(build_tracker_bench(force="--force" in sys.argv))
     print(build_map_test(force="--force" in sys.argv))
     print(build_map_fast_test(force="--force" in sys.argv))
+    print(build_map_dense_test(force="--force" in sys.argv))

@@ -609,8 +609,11 @@ int enqueue_nn(icpk_ctx* ctx, int nn_mode, hipEvent_t ev0 = nullptr, hipEvent_t 
     if (e) ICPK_HIP(ctx, hipEventRecord(e, ctx->stream));
     return ICPK_OK;
   };
-  if (nn_mode != ICPK_NN_EXACT && nn_mode != ICPK_NN_FILTERED && nn_mode != ICPK_NN_PRUNED && nn_mode != ICPK_NN_GRID)
+  if (nn_mode != ICPK_NN_EXACT && nn_mode != ICPK_NN_FILTERED && nn_mode != ICPK_NN_PRUNED && nn_mode != ICPK_NN_GRID &&
+      nn_mode != ICPK_NN_MAP)
     return fail(ctx, ICPK_E_ARG, "unknown nn_mode");
+  if (nn_mode == ICPK_NN_MAP && !icpk_map_lookup_current(ctx))
+    return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP needs the map's current lookup target (icpk_map_lookup_to_target)");
   const int nq = ctx->src.n;
   int rc = ensure_assoc(ctx, nq);
   if (rc) return rc;
@@ -627,6 +630,17 @@ int enqueue_nn(icpk_ctx* ctx, int nn_mode, hipEvent_t ev0 = nullptr, hipEvent_t 
   NnArgs a = base_nn_args(ctx);
   const int ntiles = a.nt_pad / NN_TILE;
   if (nn_mode != ICPK_NN_GRID && (rc = flush_loop_init(ctx))) return rc;  // (their fills and kernels look at the state)
+  if (nn_mode == ICPK_NN_MAP) {  // K9 (icpk_map.cpp): the sweep's keys index the lookup target
+    if ((rc = mark(ev0))) return rc;
+    if ((rc = icpk_map_nn_sweep(ctx))) return rc;
+    if ((rc = mark(ev1))) return rc;
+    ICPK_HIP(ctx, hipGetLastError());
+    ctx->grid_chain = false;
+    ctx->have_assoc = true;
+    ctx->have_seed = false;  // (a lookup result is no nearest target: it must not seed a filtered sweep)
+    ctx->have_seed_m = false;
+    return ICPK_OK;
+  }
   if (nn_mode == ICPK_NN_EXACT) {
     a.tiles_per_chunk = chunking((nq + NN_THREADS - 1) / NN_THREADS, ntiles);
     a.best = ctx->best;
@@ -757,6 +771,7 @@ int icpk_host_target_replaced(icpk_ctx* ctx) {
   ctx->have_dec = false;
   ctx->have_boxes = false;
   ctx->have_grid = false;
+  ctx->tgt_lookup = false;
   ctx->have_seed = false;
   ctx->have_normals = false;
   return ICPK_OK;
@@ -1017,6 +1032,7 @@ static int set_target_impl(icpk_ctx* ctx, const float* x, const float* y, const 
   ctx->have_dec = false;
   ctx->have_boxes = false;
   ctx->have_grid = false;
+  ctx->tgt_lookup = false;
   ctx->have_seed = false;
   ctx->have_normals = false;
   return ICPK_OK;
@@ -1460,6 +1476,7 @@ int icpk_align_query_sharded(icpk_ctx* ctx, const icpk_params* p, float T_out[16
   int rc = check_ready(ctx);
   if (rc) return rc;
   if (!p || !T_out) return ICPK_E_ARG;
+  if (p->nn_mode == ICPK_NN_MAP) return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP is single-context only");
   if (!ctx->comm) return fail(ctx, ICPK_E_NOT_SET, "icpk_comm_init_rccl has not been called");
   if (p->solve != ICPK_SOLVE_REFERENCE && p->solve != ICPK_SOLVE_KABSCH)
     return fail(ctx, ICPK_E_ARG, "the query-sharded loop supports the reference and Kabsch flavours");
@@ -1537,6 +1554,7 @@ int icpk_transform_target(icpk_ctx* ctx, const float R[9], const float t[3]) {
   ctx->have_dec = false;
   ctx->have_boxes = false;
   ctx->have_grid = false;
+  ctx->tgt_lookup = false;
   ctx->have_seed = false;
   return ICPK_OK;  // stream-ordered: no host wait
 }
@@ -1561,6 +1579,8 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
     return fail(ctx, ICPK_E_ARG, "bad params");
   if (p->solve == ICPK_SOLVE_POINT_TO_PLANE && ctx && !ctx->have_normals)
     return fail(ctx, ICPK_E_NOT_SET, "point-to-plane needs target normals");
+  if (p->nn_mode == ICPK_NN_MAP && (p->solve == ICPK_SOLVE_POINT_TO_PLANE || !(p->max_nn_dist <= ICPK_MAX_NN_DISTANCE)))
+    return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP: reference or Kabsch flavour and max_nn_dist <= 0.75");
   int rc = check_ready(ctx);
   if (rc) {
     if (stats) stats->status = rc;
@@ -2237,11 +2257,13 @@ int align_batch_impl(icpk_ctx* ctx, int32_t n_pairs, const icpk_pair* pairs, con
 
 int icpk_align_batch(icpk_ctx* ctx, int32_t n_pairs, const icpk_pair* pairs, const icpk_params* p, float* T_out,
                      icpk_stats* stats) {
+  if (ctx && p && p->nn_mode == ICPK_NN_MAP) return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP has no frame-batch mode");
   return align_batch_impl(ctx, n_pairs, pairs, p, T_out, stats, hipMemcpyHostToDevice);
 }
 
 int icpk_align_batch_device(icpk_ctx* ctx, int32_t n_pairs, const icpk_pair* pairs, const icpk_params* p,
                             float* T_out, icpk_stats* stats) {
+  if (ctx && p && p->nn_mode == ICPK_NN_MAP) return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP has no frame-batch mode");
   return align_batch_impl(ctx, n_pairs, pairs, p, T_out, stats, hipMemcpyDeviceToDevice);
 }
 
@@ -2378,6 +2400,7 @@ static int backproject_impl(icpk_ctx* ctx, const uint16_t* depth, int32_t rows, 
   ctx->have_qperm = false;
   if (which == 1) {
     ctx->have_dec = ctx->have_boxes = ctx->have_grid = false;
+    ctx->tgt_lookup = false;
     ctx->have_normals = normals_mode >= 0;
     if (ctx->have_normals) ctx->nrm.n = n;
   }
@@ -2593,6 +2616,8 @@ int icpk_associate_keypoints(icpk_ctx* ctx, int32_t nn_mode, float max_dist, int
     return ICPK_OK;
   }
   if (!assoc_query || !assoc_target || !assoc_dist || (!rejected_query && rejected_capacity > 0)) return ICPK_E_ARG;
+  if (nn_mode == ICPK_NN_MAP && !(max_dist <= ICPK_MAX_NN_DISTANCE))
+    return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP: max_dist <= 0.75");
   int rc = enqueue_nn(ctx, nn_mode);
   if (rc) return rc;
   const int cap = round_up(nq, NN_TILE);

@@ -160,6 +160,9 @@ struct icpk_ctx {
   struct icpk_comm_state* comm = nullptr;
   // voxel certainty map (icpk_map.cpp); null until the first icpk_map_* call
   struct icpk_map_state* map = nullptr;
+  unsigned map_version = 0;       // bumped by every change of the map (update, set_points, reset, release)
+  bool tgt_lookup = false;        // the target is icpk_map_lookup_to_target's [key points | points | zero point] ...
+  unsigned tgt_lookup_version = 0;  // ... of this map version
   // FAST key points (icpk_fast.cpp); null until the first icpk_detect_fast / icpk_bgr_to_gray call
   struct icpk_fast_state* fast = nullptr;
   int* qcount = nullptr;     // query counting sort by cell: counts and starts, grid_max_cells + 1 each
@@ -209,3 +212,7 @@ void icpk_fast_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_fast.cpp
 // the working source planes hold the cloud icpk_get_source would return (a device loop may leave them to be unpacked)
 int icpk_host_ensure_unpacked(icpk_ctx* ctx);
 int icpk_comm_allreduce_device(icpk_ctx* ctx, double* dev, int n);  // in-stream sum over the ranks (icpk_comm.cpp)
+// ICPK_NN_MAP: one K9 sweep of the working source against the map into ctx->best (icpk_map.cpp); the target must be
+// the map's current lookup target
+int icpk_map_nn_sweep(icpk_ctx* ctx);
+bool icpk_map_lookup_current(const icpk_ctx* ctx);

@@ -259,6 +259,7 @@ int icpk_detected_to_cloud(icpk_ctx* ctx, const uint16_t* depth, int32_t d_rows,
     ctx->tgt.n = m;
     ctx->have_tgt = true;
     ctx->have_assoc = ctx->have_dec = ctx->have_boxes = ctx->have_grid = ctx->have_seed = ctx->have_normals = false;
+    ctx->tgt_lookup = false;
   }
   if (n_out) *n_out = m;
   return ICPK_OK;

@@ -483,4 +483,32 @@ void launch_map_rejected(const float* x, const float* y, const float* z, int ns,
                          float* py, float* pz, const float* tx, const float* ty, const float* tz, int nt,
                          float max_dist, float* ox, float* oy, float* oz, const MapBuffers& b, hipStream_t s);
 
+// kernels_map_nn.hip -- K9, the mapped nearest-neighbour lookup (icp.cpp:371-486)
+constexpr int MAP_BRICKS = MAP_DIM / 4;  // occupancy mask: one bit per 4^3 brick
+constexpr int MAP_MASK_WORDS = (MAP_BRICKS * MAP_BRICKS * MAP_BRICKS + 31) / 32;
+struct MapNnArgs {
+  const float* qx;
+  const float* qy;
+  const float* qz;
+  int nq;
+  const int* slot;
+  const unsigned* mask;  // MAP_MASK_WORDS, current for `slot`
+  int cells_exact;       // every filled slot names a point inside its voxel's cell (see icpk_map.cpp)
+  const float *l0x, *l0y, *l0z;  // key-point list (n0 entries)
+  int n0;
+  const float *l1x, *l1y, *l1z;  // point list (n1 entries)
+  int n1;
+  nn_key_t* best;  // per query: (bits(d) << 32) | target index in [key points | points | zero point]
+  const int* stop;  // device-loop stop flags, or nullptr
+};
+void launch_map_mask(const int* slot, unsigned* mask, hipStream_t s);
+void launch_map_nn(const MapNnArgs& a, hipStream_t s);
+// the positions of nsw sweeps of ns source points (as launch_map_rejected rebuilds them): sweep s at px + s * ns
+void launch_map_poses(const float* x, const float* y, const float* z, int ns, const Rt* motion, int nsw, float* px,
+                      float* py, float* pz, hipStream_t s);
+// icpk_align_to_map_dense: the positions of the last sweep whose key says d < max_dist, compacted in query order into
+// ox / oy / oz; *b.total = their number (b sized for n entries)
+void launch_map_accepted(const float* px, const float* py, const float* pz, int n, const nn_key_t* best,
+                         float max_dist, float* ox, float* oy, float* oz, const MapBuffers& b, hipStream_t s);
+
 }  // namespace icpk

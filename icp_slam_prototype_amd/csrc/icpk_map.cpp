@@ -36,6 +36,16 @@ struct icpk_map_state {
   int* qout = nullptr;  // icpk_map_query: certainty and slot per point
   int qout_cap = 0;
   int* total_host = nullptr;  // pinned
+  unsigned* mask = nullptr;  // K9's occupancy mask (MAP_MASK_WORDS) ...
+  bool mask_valid = false;
+  unsigned mask_version = 0;  // ... built from the slots of this map version
+  nn_key_t* nnkey = nullptr;  // icpk_map_nearest: K9's keys per query
+  int nnkey_cap = 0;
+  // K9's distance bound holds while every filled slot names a point inside its voxel's cell: true until
+  // icpk_map_set_points replaces a point list that slots filled by ADD_ASSOCIATED name (never in the reference's flow,
+  // where the list is assigned only at the seed); a reset restores it
+  bool points_named = false;  // ADD_ASSOCIATED has filled a slot since the last reset
+  bool cells_exact = true;
 };
 
 namespace {
@@ -134,6 +144,7 @@ int list_of_rule(int rule) { return rule == ICPK_MAP_ADD_ASSOCIATED ? ICPK_MAP_P
 int run_update(icpk_ctx* ctx, int rule, const MapPoints& p, int delta) {
   icpk_map_state* m = ctx->map;
   if (p.n <= 0) return ICPK_OK;
+  ++ctx->map_version;
   const int list = list_of_rule(rule);
   const int old = m->list_n[list];
   if ((long long)old + p.n > (1ll << 30)) return icpk_host_fail(ctx, ICPK_E_ARG, "map list would exceed 2^30 entries");
@@ -145,6 +156,7 @@ int run_update(icpk_ctx* ctx, int rule, const MapPoints& p, int delta) {
   float* L = m->list[list];
   launch_map_update(p, rule, delta, old, list, plane(L, cap, 0), plane(L, cap, 1), plane(L, cap, 2), m->cert, m->slot, m->b,
                     ctx->stream);
+  if (list == ICPK_MAP_POINTS) m->points_named = true;  // (possibly: a superset is safe)
   ICPK_HIP(ctx, hipGetLastError());
   ICPK_HIP(ctx, hipMemcpyAsync(m->total_host, m->b.total, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -183,14 +195,100 @@ int upload_points(icpk_ctx* ctx, const float* x, const float* y, const float* z,
   return ICPK_OK;
 }
 
+// the motion the loop of the last icpk_align applied after each completed iteration (reference flavour R^-1 and
+// -offset, icp.cpp:235-245; Kabsch the step itself), on the device; *niter = their number.  The sweeps ran at
+// P_0 .. P_niter.
+int upload_motion(icpk_ctx* ctx, const icpk_params* p, int* niter_out) {
+  icpk_map_state* m = ctx->map;
+  const int niter = (int)(ctx->trace_R.size() / 9);
+  std::vector<Rt> mo((size_t)(niter > 0 ? niter : 1));
+  for (int s = 0; s < niter; ++s) {
+    const float* R = ctx->trace_R.data() + 9 * (size_t)s;
+    const float* t = ctx->trace_t.data() + 3 * (size_t)s;
+    if (p->solve == ICPK_SOLVE_REFERENCE) {
+      invert3f(R, mo[(size_t)s].R);
+      for (int k = 0; k < 3; ++k) mo[(size_t)s].t[k] = -t[k];
+    } else {
+      std::memcpy(mo[(size_t)s].R, R, sizeof(mo[(size_t)s].R));
+      std::memcpy(mo[(size_t)s].t, t, sizeof(mo[(size_t)s].t));
+    }
+  }
+  if (niter > m->motion_cap) {
+    if (m->motion) ICPK_HIP(ctx, hipFree(m->motion));
+    m->motion = nullptr;
+    m->motion_cap = 0;
+    ICPK_HIP(ctx, hipMalloc((void**)&m->motion, (size_t)niter * sizeof(Rt)));
+    m->motion_cap = niter;
+  }
+  if (niter > 0)
+    ICPK_HIP(ctx, hipMemcpyAsync(m->motion, mo.data(), (size_t)niter * sizeof(Rt), hipMemcpyHostToDevice, ctx->stream));
+  *niter_out = niter;
+  return ICPK_OK;
+}
+
+// K9's occupancy mask, rebuilt from the slots if the map has changed since it was built
+int ensure_mask(icpk_ctx* ctx) {
+  icpk_map_state* m = ctx->map;
+  if (!m->mask) ICPK_HIP(ctx, hipMalloc((void**)&m->mask, (size_t)MAP_MASK_WORDS * sizeof(unsigned)));
+  if (m->mask_valid && m->mask_version == ctx->map_version) return ICPK_OK;
+  launch_map_mask(m->slot, m->mask, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  m->mask_valid = true;
+  m->mask_version = ctx->map_version;
+  return ICPK_OK;
+}
+
+MapNnArgs nn_args(icpk_ctx* ctx, const float* x, const float* y, const float* z, int n, nn_key_t* best,
+                  const int* stop) {
+  icpk_map_state* m = ctx->map;
+  MapNnArgs a{};
+  a.qx = x;
+  a.qy = y;
+  a.qz = z;
+  a.nq = n;
+  a.slot = m->slot;
+  a.mask = m->mask;
+  a.cells_exact = m->cells_exact ? 1 : 0;
+  for (int k = 0; k < 2; ++k) {
+    float* L = m->list[k];
+    const int cap = m->list_cap[k];
+    const float* px = L ? plane(L, cap, 0) : nullptr;
+    const float* py = L ? plane(L, cap, 1) : nullptr;
+    const float* pz = L ? plane(L, cap, 2) : nullptr;
+    if (k == 0) {
+      a.l0x = px, a.l0y = py, a.l0z = pz, a.n0 = m->list_n[0];
+    } else {
+      a.l1x = px, a.l1y = py, a.l1z = pz, a.n1 = m->list_n[1];
+    }
+  }
+  a.best = best;
+  a.stop = stop;
+  return a;
+}
+
 }  // namespace
+
+bool icpk_map_lookup_current(const icpk_ctx* ctx) {
+  return ctx->map && ctx->have_tgt && ctx->tgt_lookup && ctx->tgt_lookup_version == ctx->map_version &&
+         ctx->tgt.n == ctx->map->list_n[0] + ctx->map->list_n[1] + 1;
+}
+
+int icpk_map_nn_sweep(icpk_ctx* ctx) {
+  int rc = ensure_mask(ctx);
+  if (rc) return rc;
+  launch_map_nn(nn_args(ctx, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->src.n, ctx->best, ctx->stop), ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  return ICPK_OK;
+}
 
 void icpk_map_free(icpk_ctx* ctx) {
   icpk_map_state* m = ctx ? ctx->map : nullptr;
   if (!m) return;
+  ++ctx->map_version;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  void* dev[] = {m->cert, m->slot, m->list[0], m->list[1], m->scratch, m->idx, m->batch, m->pos, m->motion, m->qout};
+  void* dev[] = {m->cert, m->slot, m->list[0], m->list[1], m->scratch, m->idx, m->batch, m->pos, m->motion, m->qout,
+                 m->mask, m->nnkey};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   if (m->total_host) (void)hipHostFree(m->total_host);
@@ -211,6 +309,9 @@ int icpk_map_reset(icpk_ctx* ctx) {
     ICPK_HIP(ctx, hipMemsetAsync(m->slot, 0xff, (size_t)MAP_CELLS * sizeof(int), ctx->stream));
   }
   m->list_n[0] = m->list_n[1] = 0;
+  m->points_named = false;
+  m->cells_exact = true;
+  ++ctx->map_version;
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ICPK_OK;
 }
@@ -269,6 +370,8 @@ int icpk_map_set_points(icpk_ctx* ctx, int32_t from) {
   rc = cloud_of(ctx, from, &c);
   if (rc) return rc;
   icpk_map_state* m = ctx->map;
+  ++ctx->map_version;
+  if (m->points_named) m->cells_exact = false;
   m->list_n[ICPK_MAP_POINTS] = 0;  // (nothing of the old list survives the assignment)
   rc = ensure_list(ctx, ICPK_MAP_POINTS, c->n);
   if (rc) return rc;
@@ -390,31 +493,10 @@ int icpk_align_to_map(icpk_ctx* ctx, const icpk_params* p, int32_t delta, float 
   const int ns = ctx->src0.n;
   if (st.final_pairs <= 0 || ns <= 0) return status;  // map.cpp:124-126: no associations, no update
 
-  // the motion the loop applied after each completed iteration (icpk_align: reference flavour R^-1 and -offset,
-  // icp.cpp:235-245; Kabsch the step itself); the sweeps ran at P_0 .. P_niter
-  const int niter = (int)(ctx->trace_R.size() / 9);
+  int niter = 0;
+  rc = upload_motion(ctx, p, &niter);
+  if (rc) return rc;
   const int nsw = niter + 1;
-  std::vector<Rt> mo((size_t)(niter > 0 ? niter : 1));
-  for (int s = 0; s < niter; ++s) {
-    const float* R = ctx->trace_R.data() + 9 * (size_t)s;
-    const float* t = ctx->trace_t.data() + 3 * (size_t)s;
-    if (p->solve == ICPK_SOLVE_REFERENCE) {
-      invert3f(R, mo[(size_t)s].R);
-      for (int k = 0; k < 3; ++k) mo[(size_t)s].t[k] = -t[k];
-    } else {
-      std::memcpy(mo[(size_t)s].R, R, sizeof(mo[(size_t)s].R));
-      std::memcpy(mo[(size_t)s].t, t, sizeof(mo[(size_t)s].t));
-    }
-  }
-  if (niter > m->motion_cap) {
-    if (m->motion) ICPK_HIP(ctx, hipFree(m->motion));
-    m->motion = nullptr;
-    m->motion_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&m->motion, (size_t)niter * sizeof(Rt)));
-    m->motion_cap = niter;
-  }
-  if (niter > 0)
-    ICPK_HIP(ctx, hipMemcpyAsync(m->motion, mo.data(), (size_t)niter * sizeof(Rt), hipMemcpyHostToDevice, ctx->stream));
   const long long total_pos = (long long)ns * nsw;
   if (total_pos > (1ll << 30)) return icpk_host_fail(ctx, ICPK_E_ARG, "too many sweep positions");
   const int mpos = (int)total_pos;
@@ -433,6 +515,127 @@ int icpk_align_to_map(icpk_ctx* ctx, const icpk_params* p, int32_t delta, float 
   MapPoints rej{plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1), plane(m->batch, m->batch_cap, 2), nullptr,
                 nrej};
   rc = run_update(ctx, ICPK_MAP_ADD_UNASSOCIATED, rej, delta);  // icp.cpp:271
+  return rc ? rc : status;
+}
+
+int icpk_map_nearest(icpk_ctx* ctx, const float* x, const float* y, const float* z, int32_t n, float* dist_out,
+                     int32_t* list_out, int32_t* index_out) {
+  if (!ctx || n < 0 || (n > 0 && (!x || !y || !z))) return ICPK_E_ARG;
+  int rc = ensure_map(ctx);
+  if (rc || n == 0) return rc;
+  rc = upload_points(ctx, x, y, z, n);
+  if (rc) return rc;
+  icpk_map_state* m = ctx->map;
+  if (n > m->nnkey_cap) {
+    if (m->nnkey) ICPK_HIP(ctx, hipFree(m->nnkey));
+    m->nnkey = nullptr;
+    m->nnkey_cap = 0;
+    ICPK_HIP(ctx, hipMalloc((void**)&m->nnkey, (size_t)n * sizeof(nn_key_t)));
+    m->nnkey_cap = n;
+  }
+  rc = ensure_mask(ctx);
+  if (rc) return rc;
+  launch_map_nn(nn_args(ctx, plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1),
+                        plane(m->batch, m->batch_cap, 2), n, m->nnkey, nullptr),
+                ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  std::vector<nn_key_t> keys((size_t)n);
+  ICPK_HIP(ctx, hipMemcpyAsync(keys.data(), m->nnkey, keys.size() * sizeof(nn_key_t), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const unsigned n0 = (unsigned)m->list_n[0], n1 = (unsigned)m->list_n[1];
+  for (int32_t i = 0; i < n; ++i) {
+    const unsigned t = (unsigned)keys[(size_t)i], db = (unsigned)(keys[(size_t)i] >> 32);
+    float d;
+    std::memcpy(&d, &db, sizeof(d));
+    int32_t lst, idx;
+    if (t < n0) {
+      lst = ICPK_MAP_KEYPOINTS, idx = (int32_t)t;
+    } else if (t < n0 + n1) {
+      lst = ICPK_MAP_POINTS, idx = (int32_t)(t - n0);
+    } else {  // the zero point: an empty voxel won (d < 0.75), or nothing did (d = 0.75 exactly)
+      lst = d < ICPK_MAX_NN_DISTANCE ? ICPK_MAP_NN_EMPTY : ICPK_MAP_NN_NONE, idx = -1;
+    }
+    if (dist_out) dist_out[i] = d;
+    if (list_out) list_out[i] = lst;
+    if (index_out) index_out[i] = idx;
+  }
+  return ICPK_OK;
+}
+
+int icpk_map_lookup_to_target(icpk_ctx* ctx) {
+  if (!ctx) return ICPK_E_ARG;
+  int rc = ensure_map(ctx);
+  if (rc) return rc;
+  icpk_map_state* m = ctx->map;
+  const int n0 = m->list_n[0], n1 = m->list_n[1];
+  if ((long long)n0 + n1 + 1 > (1ll << 31) - 1) return icpk_host_fail(ctx, ICPK_E_ARG, "map lists too long for a target");
+  rc = icpk_host_ensure_cloud(ctx, ctx->tgt, n0 + n1 + 1);
+  if (rc) return rc;
+  Cloud& c = ctx->tgt;
+  float* dst[3] = {c.x(), c.y(), c.z()};
+  for (int k = 0; k < 3; ++k) {
+    if (n0 > 0)
+      ICPK_HIP(ctx, hipMemcpyAsync(dst[k], plane(m->list[0], m->list_cap[0], k), (size_t)n0 * sizeof(float),
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+    if (n1 > 0)
+      ICPK_HIP(ctx, hipMemcpyAsync(dst[k] + n0, plane(m->list[1], m->list_cap[1], k), (size_t)n1 * sizeof(float),
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+    ICPK_HIP(ctx, hipMemsetAsync(dst[k] + n0 + n1, 0, sizeof(float), ctx->stream));  // the zero point
+  }
+  rc = icpk_host_target_replaced(ctx);
+  if (rc) return rc;
+  ctx->tgt_lookup = true;
+  ctx->tgt_lookup_version = ctx->map_version;
+  return ICPK_OK;
+}
+
+int icpk_align_to_map_dense(icpk_ctx* ctx, const icpk_params* p, int32_t delta, float T_out[16], icpk_stats* stats) {
+  if (T_out)
+    for (int k = 0; k < 16; ++k) T_out[k] = (k % 5 == 0) ? 1.f : 0.f;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!ctx || !p || !T_out) return ICPK_E_ARG;
+  if (delta < 0 || delta > 255) return icpk_host_fail(ctx, ICPK_E_ARG, "bad delta (0 <= d <= 255)");
+  if (p->solve != ICPK_SOLVE_REFERENCE && p->solve != ICPK_SOLVE_KABSCH)
+    return icpk_host_fail(ctx, ICPK_E_ARG, "icpk_align_to_map_dense: reference or Kabsch flavour (the map has no normals)");
+  if (!(p->max_nn_dist <= ICPK_MAX_NN_DISTANCE)) return icpk_host_fail(ctx, ICPK_E_ARG, "max_nn_dist above 0.75");
+  if (!ctx->have_src) return icpk_host_fail(ctx, ICPK_E_NOT_SET, "source cloud not set");
+  int rc = icpk_map_lookup_to_target(ctx);
+  if (rc) return rc;
+  icpk_params q = *p;
+  q.nn_mode = ICPK_NN_MAP;
+  icpk_stats st;
+  const int status = icpk_align(ctx, &q, T_out, &st);
+  if (stats) *stats = st;
+  if (status < 0 || delta == 0) return status;
+  const int ns = ctx->src0.n;
+  if (ns <= 0) return status;
+  // the accepted data points of the last sweep (icp.cpp:254 then :269, map.cpp:88-119), at the positions that sweep
+  // saw: replayed from the uploaded source by the loop's own motions (after a min_pairs fallback the working source has
+  // moved on by the fallback motion)
+  icpk_map_state* m = ctx->map;
+  int niter = 0;
+  rc = upload_motion(ctx, p, &niter);
+  if (rc) return rc;
+  const int nsw = niter + 1;
+  const long long total_pos = (long long)ns * nsw;
+  if (total_pos > (1ll << 30)) return icpk_host_fail(ctx, ICPK_E_ARG, "too many sweep positions");
+  rc = ensure_scratch(ctx, ns);
+  if (!rc) rc = grow_planes(ctx, m->pos, m->pos_cap, (int)total_pos);
+  if (!rc) rc = grow_planes(ctx, m->batch, m->batch_cap, ns);
+  if (rc) return rc;
+  const int pc = m->pos_cap;
+  launch_map_poses(ctx->src0.x(), ctx->src0.y(), ctx->src0.z(), ns, m->motion, nsw, plane(m->pos, pc, 0),
+                   plane(m->pos, pc, 1), plane(m->pos, pc, 2), ctx->stream);
+  const size_t last = (size_t)niter * ns;
+  launch_map_accepted(plane(m->pos, pc, 0) + last, plane(m->pos, pc, 1) + last, plane(m->pos, pc, 2) + last, ns, ctx->best,
+                      p->max_nn_dist, plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1),
+                      plane(m->batch, m->batch_cap, 2), m->b, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ICPK_HIP(ctx, hipMemcpyAsync(m->total_host, m->b.total, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  MapPoints acc{plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1), plane(m->batch, m->batch_cap, 2),
+                nullptr, *m->total_host};
+  rc = run_update(ctx, ICPK_MAP_ADD_ASSOCIATED, acc, delta);
   return rc ? rc : status;
 }
 

@@ -17,24 +17,12 @@
 // digit comes from 9 ballots (the lanes of a wave whose digit equals this lane's) and per-wave digit counts in LDS.
 #include "icpk.h"
 #include "icpk_internal.h"
+#include "map_device.h"
 #include "nn_device.h"
 
 namespace icpk {
 
-constexpr float MAP_C = 10.0f / (float)MAP_DIM;  // map.hpp:17 CELL_PHYSICAL_HEIGHT as float(...) (map.cpp:58)
 constexpr int MAP_WAVES = MAP_TILE / 64;
-
-// map.cpp:60-82 for one axis: int(p / c) with the x86 conversion (cvttss2si: NaN, +-inf and |q| >= 2^31 give INT_MIN,
-// which the clamp sends to 0 -- v_cvt_i32_f32 would saturate +1e10 to INT_MAX and land in voxel 299), clamped to
-// [0, 299].  The division is correctly rounded (v_div_scale / v_div_fmas / v_div_fixup, no bare v_rcp_f32).
-__device__ __forceinline__ int map_axis(float p) {
-  const float q = __fdiv_rn(p, MAP_C);
-  return (q >= 0.f && q < 2147483648.f) ? min((int)q, MAP_DIM - 1) : 0;
-}
-
-__device__ __forceinline__ int map_key_of(float x, float y, float z) {
-  return (map_axis(x) * MAP_DIM + map_axis(y)) * MAP_DIM + map_axis(z);  // world[x][y][z]
-}
 
 __device__ __forceinline__ unsigned long long lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
@@ -356,6 +344,38 @@ void launch_map_rejected(const float* x, const float* y, const float* z, int ns,
                      b.flag, b.tcount);
   hipLaunchKernelGGL(map_scan_kernel, dim3(1), dim3(MAP_TILE), 0, s, b.tcount, ntiles, b.total);
   hipLaunchKernelGGL(map_compact_kernel, dim3(ntiles), dim3(MAP_TILE), 0, s, px, py, pz, m, b.flag, b.tcount, ox, oy, oz);
+}
+
+// ---- icpk_align_to_map_dense: the accepted positions of the last sweep ------------------------------------------
+__global__ __launch_bounds__(MAP_TILE) void map_accept_kernel(const nn_key_t* __restrict__ best, int n, float max_dist,
+                                                             int* __restrict__ flag, int* __restrict__ tcount) {
+  __shared__ int wc[MAP_WAVES];
+  const int g = blockIdx.x * MAP_TILE + threadIdx.x;
+  const bool acc = g < n && __uint_as_float((unsigned)(best[g] >> 32)) < max_dist;  // icp.cpp:363
+  if (g < n) flag[g] = acc ? 1 : 0;
+  const unsigned long long b = __ballot(acc);
+  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < MAP_WAVES; ++w) s += wc[w];
+    tcount[blockIdx.x] = s;
+  }
+}
+
+void launch_map_poses(const float* x, const float* y, const float* z, int ns, const Rt* motion, int nsw, float* px,
+                      float* py, float* pz, hipStream_t s) {
+  if (ns <= 0 || nsw <= 0) return;
+  hipLaunchKernelGGL(map_poses_kernel, dim3((ns + 255) / 256), dim3(256), 0, s, x, y, z, ns, motion, nsw, px, py, pz);
+}
+
+void launch_map_accepted(const float* px, const float* py, const float* pz, int n, const nn_key_t* best,
+                         float max_dist, float* ox, float* oy, float* oz, const MapBuffers& b, hipStream_t s) {
+  if (n <= 0) return;
+  const int ntiles = (n + MAP_TILE - 1) / MAP_TILE;
+  hipLaunchKernelGGL(map_accept_kernel, dim3(ntiles), dim3(MAP_TILE), 0, s, best, n, max_dist, b.flag, b.tcount);
+  hipLaunchKernelGGL(map_scan_kernel, dim3(1), dim3(MAP_TILE), 0, s, b.tcount, ntiles, b.total);
+  hipLaunchKernelGGL(map_compact_kernel, dim3(ntiles), dim3(MAP_TILE), 0, s, px, py, pz, n, b.flag, b.tcount, ox, oy, oz);
 }
 
 }  // namespace icpk

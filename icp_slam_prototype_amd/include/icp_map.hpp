@@ -139,9 +139,10 @@ class MapTracker {
     if (n < 0) return n;
     std::vector<float> x, y, z;
     pose(kp.data(), n, x, y, z);  // icp.cpp:70-71
+    if (dense) return alignDense(data, rows, cols, maxIterations, threshold, T);
     int rc = icpk_set_source(c, x.data(), y.data(), z.data(), n);
     if (rc != ICPK_OK) return rc;
-    return alignToMap(maxIterations, threshold, T);
+    return alignToMap(maxIterations, threshold, T, false);
   }
 
   // The same with the key points of the colour frame detected on the device (SLAM.cpp:255-256, `fast`): color is
@@ -169,13 +170,18 @@ class MapTracker {
       if (rc == ICPK_OK) rc = map.setPoints(ICPK_MAP_FROM_TARGET);  // :63
       if (rc != ICPK_OK) return rc;
     }
+    if (dense) return alignDense(data, rows, cols, maxIterations, threshold, T);
     rc = icpk_detected_to_cloud(c, data, rows, cols, fx_, cx_, cameraRotation, cameraPosition, 0, nullptr);  // :70-71
     if (rc != ICPK_OK) return rc;
-    return alignToMap(maxIterations, threshold, T);
+    return alignToMap(maxIterations, threshold, T, false);
   }
 
   Map map;
   FastSettings fast;  // the colour overload's cv::FAST settings
+  // true: every frame after the seed aligns its whole (subsampled: the engine's icpk_set_subsample) depth cloud
+  // against the map with the reference's mapped association (icp.cpp:150, :254; icpk_align_to_map_dense, max
+  // distance 0.75, then ADD_ASSOCIATED with d = 25) instead of its key points
+  bool dense = false;
   float cameraRotation[9];
   float lastRotation[9];
   float cameraPosition[3];
@@ -184,15 +190,34 @@ class MapTracker {
   icpk_stats lastStats{};
 
  private:
+  // the data frame back-projected (pointcloud.cpp:19-58), posed by the camera (icp.cpp:70-71) and aligned densely
+  int alignDense(const uint16_t* data, int rows, int cols, int maxIterations, float threshold, float T[16]) {
+    icpk_ctx* c = eng_.ctx();
+    const float no_offset[3] = {0.f, 0.f, 0.f};
+    int rc = icpk_backproject(c, data, rows, cols, fx_, cx_, no_offset, 0);
+    if (rc < 0) return rc;
+    rc = icpk_transform_source(c, cameraRotation, cameraPosition);
+    if (rc == ICPK_OK) rc = icpk_commit_source(c);
+    if (rc != ICPK_OK) return rc;
+    return alignToMap(maxIterations, threshold, T, true);
+  }
+
   // icp.cpp:98-271 on the engine's source against the map, then the pose kept as icp::Tracker keeps it
-  int alignToMap(int maxIterations, float threshold, float T[16]) {
+  int alignToMap(int maxIterations, float threshold, float T[16], bool mapped) {
     icpk_ctx* c = eng_.ctx();
     params.max_iterations = maxIterations;
     params.threshold = threshold;
     std::memcpy(params.last_rotation, lastRotation, sizeof(lastRotation));
     std::memcpy(params.last_translation, lastTranslation, sizeof(lastTranslation));
     icpk_stats st;
-    const int rc = icpk_align_to_map(c, &params, ICPK_MAP_DELTA_CONFIDENCE, T, &st);
+    int rc;
+    if (mapped) {
+      AlignParams q = params;
+      q.max_nn_dist = ICPK_MAX_NN_DISTANCE;  // icp.cpp:363
+      rc = icpk_align_to_map_dense(c, &q, ICPK_MAP_DELTA_CONFIDENCE, T, &st);
+    } else {
+      rc = icpk_align_to_map(c, &params, ICPK_MAP_DELTA_CONFIDENCE, T, &st);
+    }
     if (rc < 0) return rc;
     lastStats = st;
     int32_t niter = 0;

@@ -71,6 +71,9 @@ extern "C" {
 #define ICPK_NN_GRID 3     /* uniform grid over the target: only the cells that meet the cube \
                               [q - r, q + r] around a query with seed distance r are scanned; \
                               same results; default                                     */
+#define ICPK_NN_MAP 4      /* the reference's mapped lookup (icp.cpp:347-486, K9): NOT the nearest target but \
+                              what the voxel walk of icpk_map_nearest finds; only against the map's current  \
+                              lookup target (icpk_map_lookup_to_target), see there                       */
 
 /* log keys mirrored from SLAM.hpp:4-13 for the optional callback */
 #define ICPK_LOG_NEAREST_NEIGHBOR 0
@@ -430,6 +433,54 @@ void icpk_map_voxel(const float p[3], int32_t v[3]);
  * :490-491, meanSquareError of no errors is 0 (:622-638) so the loop does not run, and map.update returns on no
  * associations.  Reference and Kabsch flavours (ICPK_E_ARG for point-to-plane: the map has no normals). */
 int icpk_align_to_map(icpk_ctx *ctx, const icpk_params *p, int32_t delta, float T_out[16], icpk_stats *stats);
+
+/* ---- mapped nearest neighbours (K9): icp.cpp:347-486 over the device map -----------------------------------------
+ * getNearestMappedPoint for a query q, restated exactly; c = float(10 / 300), the voxel rule of icpk_map_voxel:
+ *   constants  maxRadius = int(1.5f / c) = 44 (1.5f / c is 44.999996): radii 1 .. 43; the walk starts from
+ *              shortest = 0.75f (MAX_NN_COLOR_DISTANCE) and stops below 0.2f (MIN_NN_COLOR_DISTANCE); the distance is
+ *              icp.cpp:606-620 with colour weight 0 (double sum of squares, correctly rounded float sqrt)
+ *   centre     voxel v = (vx, vy, vz) of q is processed; if then shortest < 0.75 the walk ends (even at >= 0.2)
+ *   shells     for r = 1, 2, ... while shortest >= 0.2 and r < 44, in this order:
+ *              block 1  for y in [vy-r, vy+r), z in [vz-r, vz+r): (vx-r, y, z) then (vx+r, y, z); the step is skipped
+ *                       if vx-r or vx+r lies outside [0, 300) or y does -- z is NOT checked (icp.cpp tests y twice)
+ *              block 2  for x in [vx-r+1, vx+r-1), z in [vz-r, vz+r): (x, vy-r, z) then (x, vy+r, z); skipped if x or
+ *                       z lies outside [0, 300) or either of vy-r, vy+r does
+ *              block 3  for x in [vx-r+1, vx+r-1), y in [vy-r+1, vy+r-1): (x, y, vz-r) then (x, y, vz+r); skipped if
+ *                       x or y lies outside [0, 300) or either of vz-r, vz+r does
+ *              (half-open ranges: shells are incomplete and asymmetric, as in the reference)
+ *   voxel      processVoxel (:476-486): a filled slot yields the point it names, read from its list as the list stands
+ *              now; an EMPTY slot yields the zero point (0, 0, 0) -- the reference's emptiness test compares a uchar
+ *              with -1 and is always true.  A candidate replaces the best only if d < shortest: the earliest voxel in
+ *              visit order wins ties.
+ *   overrun    block 1 reads pointLookupTable[x][y][z] with z outside [0, 300) at flat offset (x*300 + y)*300 + z --
+ *              another voxel -- as the reference's x86 build does.  Where that offset leaves the table (x = y = 0,
+ *              z < 0; x = y = 299, z >= 300) the reference reads memory outside it: such reads are skipped here,
+ *              PARITY UNPINNED.
+ * Slots name (list, index) (K7); the reference copied the point into the table when it filled the slot.  The two agree
+ * unless icpk_map_set_points replaces the point list after ADD_ASSOCIATED has filled slots (the reference assigns it
+ * only at the seed, before any such slot exists): the slots then name entries of the new list, and one whose index is
+ * past the new list's end reads as empty -- PARITY UNPINNED.  A map never allocated behaves as an empty one. */
+#define ICPK_MAP_NN_EMPTY (-1) /* an empty voxel's zero point won                     */
+#define ICPK_MAP_NN_NONE (-2)  /* nothing beat 0.75: dist 0.75f                       */
+/* getNearestMappedPoint for n host points: per point the distance (0.75f when nothing beat it), the list
+ * (ICPK_MAP_KEYPOINTS / ICPK_MAP_POINTS / ICPK_MAP_NN_EMPTY / ICPK_MAP_NN_NONE) and the list index (-1 for the last
+ * two).  Any output may be NULL. */
+int icpk_map_nearest(icpk_ctx *ctx, const float *x, const float *y, const float *z, int32_t n, float *dist_out,
+                     int32_t *list_out, int32_t *index_out);
+/* the context's target becomes [key-point list | point list | (0, 0, 0)] (device to device), marked as the lookup
+ * target of the map as it stands: icpk_nn, icpk_align and icpk_associate_keypoints accept ICPK_NN_MAP while no map
+ * change and no other target has come in between (else ICPK_E_ARG).  An ICPK_NN_MAP sweep's index is the element of
+ * this target the walk found; an empty voxel's win and "nothing" both point at the zero point, the latter with
+ * d = 0.75f (never accepted: ICPK_NN_MAP needs max_nn_dist <= 0.75).  The loop runs K3 unfused, as for
+ * ICPK_NN_EXACT.  Point-to-plane, max_nn_dist > 0.75, icpk_align_batch* and icpk_align_query_sharded: ICPK_E_ARG. */
+int icpk_map_lookup_to_target(icpk_ctx *ctx);
+/* icp::getTransformation with the mapped association (icp.cpp:155-257 with :150 and :254 enabled): the lookup target,
+ * then icpk_align with ICPK_NN_MAP (T_out, stats, trace and aligned source are icpk_align's).  Then, if delta > 0, the
+ * data points the LAST sweep accepted (d < p->max_nn_dist, :363), at the positions that sweep saw -- after a min_pairs
+ * fallback not the returned source -- go through ICPK_MAP_ADD_ASSOCIATED with delta, in source order (map.cpp:88-119);
+ * delta 0 leaves the map alone.  No special case for an empty map (the reference's dense path has no early return).
+ * Reference and Kabsch flavours, max_nn_dist <= 0.75 (else ICPK_E_ARG).  THE CONTEXT'S TARGET IS REPLACED. */
+int icpk_align_to_map_dense(icpk_ctx *ctx, const icpk_params *p, int32_t delta, float T_out[16], icpk_stats *stats);
 
 /* ---- FAST key points on the device (K8): SLAM.cpp:255-256 + pointcloud.cpp:60-98 -------------------------------
  * cv::cvtColor(BGR -> GRAY) then cv::FAST(gray, keypoints, threshold, nonmax, type), restated from OpenCV 3.2's scalar
