@@ -106,7 +106,7 @@ namespace {
 
 int need_comm(icpk_ctx* ctx) {
   if (!ctx) return ICPK_E_ARG;
-  if (!ctx->comm || !ctx->comm->comm) return icpk_host_fail(ctx, ICPK_E_NOT_SET, "icpk_comm_init_rccl has not been called");
+  if (!ctx->comm || !ctx->comm->comm) return fail(ctx, ICPK_E_NOT_SET, "icpk_comm_init_rccl has not been called");
   return ICPK_OK;
 }
 
@@ -167,7 +167,7 @@ int icpk_comm_unique_id(void* id_out) {
 int icpk_comm_init_rccl(icpk_ctx* ctx, const void* unique_id, int rank, int world) {
   if (!ctx || !unique_id || world < 1 || rank < 0 || rank >= world) return ICPK_E_ARG;
   RcclApi* api = rccl();
-  if (!api) return icpk_host_fail(ctx, ICPK_E_RCCL, "librccl.so.1 could not be loaded (dlopen)");
+  if (!api) return fail(ctx, ICPK_E_RCCL, "librccl.so.1 could not be loaded (dlopen)");
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   icpk_comm_release(ctx);
   ctx->comm = new icpk_comm_state();
@@ -209,8 +209,8 @@ int icpk_comm_broadcast_target(icpk_ctx* ctx, int root) {
   if (rc) return rc;
   icpk_comm_state* c = ctx->comm;
   RcclApi* api = rccl();
-  if (root < 0 || root >= c->world) return icpk_host_fail(ctx, ICPK_E_ARG, "bad root");
-  if (c->rank == root && !ctx->have_tgt) return icpk_host_fail(ctx, ICPK_E_NOT_SET, "root has no target cloud");
+  if (root < 0 || root >= c->world) return fail(ctx, ICPK_E_ARG, "bad root");
+  if (c->rank == root && !ctx->have_tgt) return fail(ctx, ICPK_E_NOT_SET, "root has no target cloud");
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   rc = ensure_staging(ctx, 64);
   if (rc) return rc;
@@ -221,11 +221,11 @@ int icpk_comm_broadcast_target(icpk_ctx* ctx, int root) {
   ICPK_HIP(ctx, hipMemcpyAsync(hn, c->dev, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const int n = *hn;
-  if (n < 0) return icpk_host_fail(ctx, ICPK_E_RCCL, "broadcast of the target size failed");
+  if (n < 0) return fail(ctx, ICPK_E_RCCL, "broadcast of the target size failed");
   // Every rank makes room first and the ranks AGREE on the outcome (one 4-byte all-reduce) before the plane
   // broadcasts: a rank that could not allocate must not leave the others waiting inside ncclBroadcast.
   int alloc_rc = ICPK_OK;
-  if (c->rank != root) alloc_rc = icpk_host_ensure_cloud(ctx, ctx->tgt, n);
+  if (c->rank != root) alloc_rc = ensure_cloud(ctx, ctx->tgt, n);
   double* hf = static_cast<double*>(c->host);  // (float64 sum: the one all-reduce flavour this layer uses anywhere)
   *hf = alloc_rc == ICPK_OK ? 0.0 : 1.0;
   ICPK_HIP(ctx, hipMemcpyAsync(c->dev, hf, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -233,7 +233,7 @@ int icpk_comm_broadcast_target(icpk_ctx* ctx, int root) {
   ICPK_HIP(ctx, hipMemcpyAsync(hf, c->dev, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (alloc_rc) return alloc_rc;
-  if (*hf != 0.0) return icpk_host_fail(ctx, ICPK_E_HIP, "another rank could not allocate the broadcast target");
+  if (*hf != 0.0) return fail(ctx, ICPK_E_HIP, "another rank could not allocate the broadcast target");
   if (n > 0) {  // plane capacities may differ from rank to rank: one message per plane, grouped
     ICPK_RCCL(ctx, api->GroupStart());
     ICPK_RCCL(ctx, api->Broadcast(ctx->tgt.x(), ctx->tgt.x(), (size_t)n, ncclFloat32, root, c->comm, ctx->stream));
@@ -242,8 +242,9 @@ int icpk_comm_broadcast_target(icpk_ctx* ctx, int root) {
     ICPK_RCCL(ctx, api->GroupEnd());
   }
   if (c->rank != root) {
-    rc = icpk_host_target_replaced(ctx);
+    rc = pad_target(ctx);
     if (rc) return rc;
+    target_changed(ctx, false);
   }
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ICPK_OK;
@@ -258,10 +259,10 @@ int icpk_comm_gather_results(icpk_ctx* ctx, const float* T_local, const icpk_sta
   icpk_comm_state* c = ctx->comm;
   RcclApi* api = rccl();
   int s0 = 0, cnt = 0;
-  if (n_total < 0) return icpk_host_fail(ctx, ICPK_E_ARG, "bad n_total");
+  if (n_total < 0) return fail(ctx, ICPK_E_ARG, "bad n_total");
   shard(n_total, c->world, c->rank, s0, cnt);
   if (n_local != cnt || (n_local > 0 && !T_local) || (n_total > 0 && !T_all))
-    return icpk_host_fail(ctx, ICPK_E_ARG, "n_local does not match this rank's block of n_total");
+    return fail(ctx, ICPK_E_ARG, "n_local does not match this rank's block of n_total");
   if (n_total == 0) return ICPK_OK;
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   const int bmax = (n_total + c->world - 1) / c->world;
@@ -301,7 +302,7 @@ int icpk_comm_gather_results(icpk_ctx* ctx, const float* T_local, const icpk_sta
 int icpk_comm_allreduce_sums(icpk_ctx* ctx, double* sums, int32_t n, int64_t* count) {
   int rc = need_comm(ctx);
   if (rc) return rc;
-  if (!sums || n < 0 || n > 64) return icpk_host_fail(ctx, ICPK_E_ARG, "bad sums");
+  if (!sums || n < 0 || n > 64) return fail(ctx, ICPK_E_ARG, "bad sums");
   icpk_comm_state* c = ctx->comm;
   RcclApi* api = rccl();
   ICPK_HIP(ctx, hipSetDevice(ctx->device));

@@ -1,10 +1,13 @@
-// icpk_ctx.h -- the context object behind the opaque icpk_ctx of include/icpk.h, shared by
-// the host-side translation units (icpk_api.cpp, icpk_comm.cpp).  Not part of the ABI.
+// icpk_ctx.h -- the context object behind the opaque icpk_ctx of include/icpk.h and the host helpers more than one
+// host-side translation unit calls (icpk_api.cpp: context and clouds; icpk_sweep.cpp: NN sweeps and reductions;
+// icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frontend.cpp: depth images;
+// icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "icpk.h"
@@ -23,6 +26,30 @@ struct Cloud {
 
 inline int round_up(int v, int m) { return ((v + m - 1) / m) * m; }
 
+// The environment knobs, read once by icpk_create (tuning_from_env) and inherited whole by the
+// frame-batch slots.  Every "diagnostic" knob selects a reference path the tests compare the default one against.
+struct Tuning {
+  int target_blocks = 16384;  // ICPK_NN_TARGET_BLOCKS: exact / filtered scan, blocks the target chunking aims at
+  int q_per_lane = 0;         // ICPK_NN_Q: filtered scan, queries per lane (0 = auto)
+  int slices = 0;             // ICPK_NN_SLICES: pruned scan, lanes per query (0 = by cloud size)
+  float grid_ppc = 8.f;       // ICPK_GRID_PPC: aimed-at targets per occupied cell (measured best on configs 2, 3 and the dense pair: 8)
+  int grid_xdiv = 4;          // ICPK_GRID_XDIV: cells are this many times finer along x (measured best on config 2: 4)
+  int grid_slices = 0;        // ICPK_GRID_SLICES: lanes per query (0 = by cloud size)
+  int merged_setup = 1;       // ICPK_MERGED_SETUP=0: a fresh pair's two counting sorts one after the other
+  int batch_group = 16;       // ICPK_BATCH_GROUP: pairs advancing in lock step (<= BATCH_MAX)
+  int batch_threads = 4;      // ICPK_BATCH_THREADS: host threads sharing a group's set-up calls
+  int batch_setup = 1;        // ICPK_BATCH_SETUP: 0 per-pair set-up launches on the slots' own streams; 2 batched launches
+                              //   for single-group host-pointer batches too; 3 as 2, replayed pair by pair (test hook)
+  bool pristine_skip = true;     // ICPK_PRISTINE_SKIP=0: always copy the committed source (diagnostic)
+  bool pixel_seeds = true;       // ICPK_PIXEL_SEEDS=0: the reference's literal seed (diagnostic)
+  bool lazy_unpack = true;       // ICPK_LAZY_UNPACK=0: unpack the records at the end of every device loop (diagnostic)
+  bool image_order = true;       // ICPK_IMAGE_ORDER=0: sort the queries of an image-ordered source by cell like any other (diagnostic)
+  bool zero_copy_upload = true;  // ICPK_ZERO_COPY_UPLOAD=0: copy-engine transfer from the staging buffer instead (diagnostic)
+  bool result_mirror = true;     // ICPK_RESULT_MIRROR=0: copy the state back and wait for the stream instead (diagnostic)
+  int loop_ahead = 1;            // ICPK_LOOP_AHEAD: iterations kept enqueued ahead of the device in a loop that may exit
+                                 //   early (0: enqueue every iteration up front)
+};
+
 }  // namespace icpk
 
 using icpk::nn_key_t;
@@ -33,6 +60,7 @@ using icpk::NSUM;
 struct icpk_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
+  icpk::Tuning tune;
   icpk::Cloud tgt, src0, src;
   icpk::Cloud nrm;  // target normals (point-to-plane), same indexing as tgt
   bool have_normals = false;
@@ -75,7 +103,6 @@ struct icpk_ctx {
   int loop_epoch = 0;            // tag of the current throttled loop in the progress words
   LoopState* st_mirror = nullptr;      // pinned + mapped: the loop's outputs as the device writes them at its end (LoopState::mirror)
   LoopState* st_mirror_dev = nullptr;  // the same memory as the device addresses it
-  bool result_mirror = true;           // ICPK_RESULT_MIRROR=0: copy the state back and wait for the stream instead (diagnostic)
   icpk::LoopInitArgs pending_init{};         // device_loop_begin(defer): the initial LoopState not launched yet
   bool init_pending = false;
   int* grid_ticket = nullptr;          // grid_begin_kernel's arrival counter (zero between launches)
@@ -88,20 +115,14 @@ struct icpk_ctx {
     const char* dev;
   };
   std::vector<HostRange> registered;
-  bool zero_copy_upload = true;        // ICPK_ZERO_COPY_UPLOAD=0: copy-engine transfer from the staging buffer instead (diagnostic)
   uint16_t* stage_depth = nullptr;     // pinned: icpk_backproject_pair's images on their way to the device
   int stage_depth_cap = 0;
   int* pix_tidx = nullptr;             // icpk_backproject_pair: the target point of every pixel (-1: none) ...
   int* pix_src = nullptr;              // ... and the pixel of every source point: image-space seeds of the alignment that follows
   int pix_cap = 0;
   bool have_pix_seed = false;          // they describe the clouds the context holds now
-  bool image_order = true;             // ICPK_IMAGE_ORDER=0: sort the queries of an image-ordered source by cell like any other (diagnostic)
-  bool lazy_unpack = true;             // ICPK_LAZY_UNPACK=0: unpack the records at the end of every device loop (diagnostic)
-  bool pixel_seeds = true;             // ICPK_PIXEL_SEEDS=0: the reference's literal seed (diagnostic)
   int pix_rows = 0, pix_cols = 0;
   bool src_pristine = false;     // the working source equals the committed one (see copy_src0_to_src)
-  bool pristine_skip = true;     // ICPK_PRISTINE_SKIP=0: always copy (diagnostic)
-  int loop_ahead = 1;            // iterations kept enqueued ahead of the device in a loop that may exit early
   const int* stop = nullptr;     // &st_dev->done while a device loop is being enqueued, else null
   LoopState* st_active = nullptr;  // st_dev while a device loop is being enqueued, else null
   float* stage_t = nullptr;  // pinned staging of host clouds (frame-batch slots): target, source
@@ -123,9 +144,6 @@ struct icpk_ctx {
   std::vector<hipEvent_t> events;
   std::vector<float> trace_R, trace_t, trace_mse;  // per-iteration record of the last align
   std::vector<int32_t> trace_pairs;
-  int target_blocks = 16384;
-  int q_per_lane = 0;  // 0 = auto
-  int slices = 0;      // pruned scan: lanes per query (0 = by cloud size)
   // grid scan (ICPK_NN_GRID): cell table + AoS copy of the target sorted by cell
   icpk::GridInfo* grid_info = nullptr;
   float* grid_bounds = nullptr;
@@ -151,9 +169,6 @@ struct icpk_ctx {
   LoopState* slot_states = nullptr;       // parent: the loop states of all slots in one allocation (slot k at [k]),
   LoopState* slot_states_host = nullptr;  //   so that a group's states come back with ONE copy; pinned mirror
   bool st_pooled = false;                 // slot: st_dev / st_host point into the parent's pools
-  int batch_setup = 1;                               // 0 (ICPK_BATCH_SETUP=0): per-pair set-up launches on the slots' own streams
-  int batch_group = 16;                // pairs advancing in lock step (ICPK_BATCH_GROUP, <= BATCH_MAX)
-  int batch_threads = 4;               // host threads sharing a group's set-up calls (ICPK_BATCH_THREADS)
   std::vector<nn_key_t*> best_of_sweep;  // device loop: which buffer each enqueued sweep wrote
   // RCCL communicator of the frame-batch / query-sharded modes (icpk_comm.cpp); null until
   // icpk_comm_init_rccl
@@ -181,10 +196,6 @@ struct icpk_ctx {
   bool grid_chain = false;   // device loop only: the previous sweep was a grid sweep (qm4 / sp_in current)
   int t4_cap = 0;
   bool have_grid = false;  // grid matches tgt
-  int grid_xdiv = 4;       // cells are this many times finer along x (ICPK_GRID_XDIV; measured best on config 2: 4)
-  float grid_ppc = 8.f;    // aimed-at targets per occupied cell (ICPK_GRID_PPC; measured best on configs 2, 3 and the dense pair: 8)
-  int grid_slices = 0;     // lanes per query (0 = by cloud size)
-  int merged_setup = 1;    // a fresh pair's two counting sorts side by side (ICPK_MERGED_SETUP=0: one after the other)
   std::string err;
   icpk_log_fn log_fn = nullptr;
   void* log_user = nullptr;
@@ -200,19 +211,82 @@ struct icpk_ctx {
     }                                                                                            \
   } while (0)
 
-// helpers of icpk_api.cpp that icpk_comm.cpp needs
-int icpk_host_fail(icpk_ctx* ctx, int code, const char* msg);
-int icpk_host_ensure_cloud(icpk_ctx* ctx, icpk::Cloud& c, int n);
-// the target cloud of ctx has been replaced on the device (n points, planes filled up to n):
-// pad it and drop everything derived from the previous target
-int icpk_host_target_replaced(icpk_ctx* ctx);
 void icpk_comm_release(icpk_ctx* ctx);  // called by icpk_destroy
 void icpk_map_free(icpk_ctx* ctx);      // called by icpk_destroy (icpk_map.cpp)
 void icpk_fast_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_fast.cpp)
-// the working source planes hold the cloud icpk_get_source would return (a device loop may leave them to be unpacked)
-int icpk_host_ensure_unpacked(icpk_ctx* ctx);
 int icpk_comm_allreduce_device(icpk_ctx* ctx, double* dev, int n);  // in-stream sum over the ranks (icpk_comm.cpp)
 // ICPK_NN_MAP: one K9 sweep of the working source against the map into ctx->best (icpk_map.cpp); the target must be
 // the map's current lookup target
 int icpk_map_nn_sweep(icpk_ctx* ctx);
 bool icpk_map_lookup_current(const icpk_ctx* ctx);
+
+namespace icpk {
+
+inline int fail(icpk_ctx* ctx, int code, const char* msg) {
+  if (ctx) ctx->err = msg;
+  return code;
+}
+
+// The host wait on words the device writes into pinned, mapped memory: spins until done() (the wait is short), yields
+// now and then, and looks at the stream every 20 ms -- not more often: a stream query may itself put a marker into the
+// queue -- so that a faulted kernel ends the wait with an error instead of hanging the caller.  A stream that has
+// drained while done() still says no: `stalled`.
+template <class Done>
+int spin_until(icpk_ctx* ctx, Done done, const char* stalled) {
+  auto t_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
+  for (unsigned spin = 1; !done(); ++spin) {
+    __builtin_ia32_pause();
+    if ((spin & 0x3ff) != 0) continue;
+    std::this_thread::yield();
+    const auto now = std::chrono::steady_clock::now();
+    if (now < t_query) continue;
+    t_query = now + std::chrono::milliseconds(20);
+    const hipError_t q = hipStreamQuery(ctx->stream);
+    if (q == hipSuccess) return done() ? ICPK_OK : fail(ctx, ICPK_E_HIP, stalled);  // (drained: the words are final)
+    if (q != hipErrorNotReady) return fail(ctx, ICPK_E_HIP, hipGetErrorString(q));
+  }
+  return ICPK_OK;
+}
+
+// ---- icpk_api.cpp: context and clouds ----
+// stream + the fixed-size buffers every context owns; `parent` != nullptr: a frame-batch slot (inherits the tuning)
+icpk_ctx* make_context(int device_id, const icpk_ctx* parent);
+int check_ready(icpk_ctx* ctx);  // both clouds set, target not empty
+// k: hipMemcpyHostToDevice or hipMemcpyDeviceToDevice; sync = false: the caller keeps the host buffers alive and
+// synchronises later (frame-batch slots)
+int set_target_impl(icpk_ctx* ctx, const float* x, const float* y, const float* z, int32_t n, hipMemcpyKind k,
+                    bool sync = true);
+int set_source_impl(icpk_ctx* ctx, const float* x, const float* y, const float* z, int32_t n, hipMemcpyKind k,
+                    bool sync = true);
+int copy_src0_to_src(icpk_ctx* ctx);  // the working source := the committed one
+// the target planes hold tgt.n points that replace the previous target: its +inf padding up to the next NN_TILE multiple
+int pad_target(icpk_ctx* ctx);
+// the target has changed (replaced, or moved with keep_normals = true): drop everything derived from it
+void target_changed(icpk_ctx* ctx, bool keep_normals);
+void reset_outputs(float T_out[16], icpk_stats* stats);  // identity, zeroed statistics (what a failed alignment returns)
+void clear_trace(icpk_ctx* ctx);                        // icpk_get_trace's record of the last alignment
+
+// ---- icpk_sweep.cpp: device buffers, NN sweeps, reductions ----
+int ensure_cloud(icpk_ctx* ctx, Cloud& c, int n);  // room for n points (the contents are undefined after a resize)
+int ensure_assoc(icpk_ctx* ctx, int nq);
+// the working source planes hold the cloud icpk_get_source would return (a device loop may leave them to be unpacked)
+int ensure_unpacked(icpk_ctx* ctx);
+int flush_loop_init(icpk_ctx* ctx);
+NnArgs base_nn_args(const icpk_ctx* ctx);
+int prepare_sorted_sweep(icpk_ctx* ctx, int nn_mode, NnArgs& a, NnBoxes& bx, int& recheck);
+GridSweepArgs grid_sweep_args(icpk_ctx* ctx, const NnArgs& a, const NnBoxes& bx);
+void after_grid_sweep(icpk_ctx* ctx);
+int enqueue_nn(icpk_ctx* ctx, int nn_mode, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+const float4* loop_rec(const icpk_ctx* ctx);
+int enqueue_reduce(icpk_ctx* ctx, float max_dist);
+int enqueue_reduce_p2l(icpk_ctx* ctx, float max_dist);
+
+// ---- icpk_align.cpp: the device-side loop, shared by the single-pair and the frame-batch path ----
+int loop_nsum(const icpk_params* p);
+int device_loop_begin(icpk_ctx* ctx, const icpk_params* p, bool throttled = false, bool mirror = false,
+                      bool defer = false);
+void device_loop_disarm(icpk_ctx* ctx);
+int device_loop_finish(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats* stats,
+                       const LoopState* h = nullptr);
+
+}  // namespace icpk

@@ -39,8 +39,6 @@ struct icpk_fast_state {
 
 namespace {
 
-int fast_fail(icpk_ctx* ctx, int code, const char* msg) { return icpk_host_fail(ctx, code, msg); }
-
 template <typename T>
 int grow_dev(icpk_ctx* ctx, T*& p, size_t& cap, size_t need) {
   if (need <= cap) return ICPK_OK;
@@ -131,7 +129,7 @@ extern "C" {
 
 int icpk_bgr_to_gray(icpk_ctx* ctx, const uint8_t* bgr, int32_t rows, int32_t cols, uint8_t* gray_out) {
   if (!ctx) return ICPK_E_ARG;
-  if (!bgr || !gray_out || bad_size(rows, cols)) return fast_fail(ctx, ICPK_E_ARG, "bad image or size");
+  if (!bgr || !gray_out || bad_size(rows, cols)) return fail(ctx, ICPK_E_ARG, "bad image or size");
   int rc = ensure_fast(ctx);
   if (rc) return rc;
   icpk_fast_state* f = ctx->fast;
@@ -151,11 +149,11 @@ int icpk_detect_fast(icpk_ctx* ctx, const uint8_t* image, int32_t rows, int32_t 
                      int32_t* n_out) {
   if (n_out) *n_out = 0;
   if (!ctx) return ICPK_E_ARG;
-  if (!image || bad_size(rows, cols)) return fast_fail(ctx, ICPK_E_ARG, "bad image or size");
-  if (channels != 1 && channels != 3) return fast_fail(ctx, ICPK_E_ARG, "channels must be 1 (grey) or 3 (BGR)");
+  if (!image || bad_size(rows, cols)) return fail(ctx, ICPK_E_ARG, "bad image or size");
+  if (channels != 1 && channels != 3) return fail(ctx, ICPK_E_ARG, "channels must be 1 (grey) or 3 (BGR)");
   if (type != ICPK_FAST_TYPE_7_12 && type != ICPK_FAST_TYPE_9_16)
-    return fast_fail(ctx, ICPK_E_ARG, "FAST type must be ICPK_FAST_TYPE_7_12 or ICPK_FAST_TYPE_9_16");
-  if (capacity < 0) return fast_fail(ctx, ICPK_E_ARG, "negative capacity");
+    return fail(ctx, ICPK_E_ARG, "FAST type must be ICPK_FAST_TYPE_7_12 or ICPK_FAST_TYPE_9_16");
+  if (capacity < 0) return fail(ctx, ICPK_E_ARG, "negative capacity");
   int rc = ensure_fast(ctx);
   if (rc) return rc;
   icpk_fast_state* f = ctx->fast;
@@ -191,9 +189,9 @@ int icpk_detected_to_cloud(icpk_ctx* ctx, const uint16_t* depth, int32_t d_rows,
                            const float R[9], const float t[3], int32_t which, int32_t* n_out) {
   if (n_out) *n_out = 0;
   if (!ctx) return ICPK_E_ARG;
-  if (!depth || bad_size(d_rows, d_cols) || !R || !t) return fast_fail(ctx, ICPK_E_ARG, "bad depth image, size or pose");
-  if (which != 0 && which != 1) return fast_fail(ctx, ICPK_E_ARG, "which must be 0 (source) or 1 (target)");
-  if (!ctx->fast || ctx->fast->n < 0) return fast_fail(ctx, ICPK_E_NOT_SET, "no detected key points (icpk_detect_fast)");
+  if (!depth || bad_size(d_rows, d_cols) || !R || !t) return fail(ctx, ICPK_E_ARG, "bad depth image, size or pose");
+  if (which != 0 && which != 1) return fail(ctx, ICPK_E_ARG, "which must be 0 (source) or 1 (target)");
+  if (!ctx->fast || ctx->fast->n < 0) return fail(ctx, ICPK_E_NOT_SET, "no detected key points (icpk_detect_fast)");
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   icpk_fast_state* f = ctx->fast;
   const int n = f->n;
@@ -212,12 +210,12 @@ int icpk_detected_to_cloud(icpk_ctx* ctx, const uint16_t* depth, int32_t d_rows,
   // room for every key point; the planes are written as icpk_set_source / icpk_set_target leave them (a source:
   // committed and working copy, padding 0; a target: padding +inf)
   Cloud* c = which == 0 ? &ctx->src0 : &ctx->tgt;
-  rc = icpk_host_ensure_cloud(ctx, *c, n);
-  if (!rc && which == 0) rc = icpk_host_ensure_cloud(ctx, ctx->src, n);
+  rc = ensure_cloud(ctx, *c, n);
+  if (!rc && which == 0) rc = ensure_cloud(ctx, ctx->src, n);
   if (rc) return rc;
   Cloud* c2 = which == 0 ? &ctx->src : nullptr;
   int* n_dev = f->counts + f->ent_cap;  // (the detection's total is read from f->n: the word is free)
-  volatile int* const nw = ctx->result_mirror && ctx->progress ? ctx->progress + 6 : nullptr;
+  volatile int* const nw = ctx->tune.result_mirror && ctx->progress ? ctx->progress + 6 : nullptr;
   if (nw) {
     nw[0] = -1;
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
@@ -228,21 +226,8 @@ int icpk_detected_to_cloud(icpk_ctx* ctx, const uint16_t* depth, int32_t d_rows,
   ICPK_HIP(ctx, hipGetLastError());
   int m = 0;
   if (nw) {  // the one host wait, on the mapped word (as icpk_backproject_pair)
-    auto t_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
-    for (unsigned spin = 1; nw[0] < 0; ++spin) {
-      __builtin_ia32_pause();
-      if ((spin & 0x3ff) != 0) continue;
-      std::this_thread::yield();
-      const auto now = std::chrono::steady_clock::now();
-      if (now < t_query) continue;
-      t_query = now + std::chrono::milliseconds(20);
-      const hipError_t q = hipStreamQuery(ctx->stream);  // (a faulted kernel must end the wait)
-      if (q == hipSuccess) {
-        if (nw[0] < 0) return fast_fail(ctx, ICPK_E_HIP, "key-point back-projection ended without its count");
-        break;
-      }
-      if (q != hipErrorNotReady) return fast_fail(ctx, ICPK_E_HIP, hipGetErrorString(q));
-    }
+    rc = spin_until(ctx, [&] { return nw[0] >= 0; }, "key-point back-projection ended without its count");
+    if (rc) return rc;
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
     m = nw[0];
   } else {
@@ -257,9 +242,7 @@ int icpk_detected_to_cloud(icpk_ctx* ctx, const uint16_t* depth, int32_t d_rows,
     ctx->have_assoc = ctx->have_seed = ctx->have_qperm = false;
   } else {  // what set_target leaves behind
     ctx->tgt.n = m;
-    ctx->have_tgt = true;
-    ctx->have_assoc = ctx->have_dec = ctx->have_boxes = ctx->have_grid = ctx->have_seed = ctx->have_normals = false;
-    ctx->tgt_lookup = false;
+    target_changed(ctx, false);
   }
   if (n_out) *n_out = m;
   return ICPK_OK;

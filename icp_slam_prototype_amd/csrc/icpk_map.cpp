@@ -147,7 +147,7 @@ int run_update(icpk_ctx* ctx, int rule, const MapPoints& p, int delta) {
   ++ctx->map_version;
   const int list = list_of_rule(rule);
   const int old = m->list_n[list];
-  if ((long long)old + p.n > (1ll << 30)) return icpk_host_fail(ctx, ICPK_E_ARG, "map list would exceed 2^30 entries");
+  if ((long long)old + p.n > (1ll << 30)) return fail(ctx, ICPK_E_ARG, "map list would exceed 2^30 entries");
   int rc = ensure_list(ctx, list, old + p.n);
   if (rc) return rc;
   rc = ensure_scratch(ctx, p.n);
@@ -167,17 +167,17 @@ int run_update(icpk_ctx* ctx, int rule, const MapPoints& p, int delta) {
 // the context's source (working copy) or target as update input
 int cloud_of(icpk_ctx* ctx, int from, const Cloud** c) {
   if (from == ICPK_MAP_FROM_SOURCE) {
-    if (!ctx->have_src) return icpk_host_fail(ctx, ICPK_E_NOT_SET, "source cloud not set");
-    if (int rc = icpk_host_ensure_unpacked(ctx)) return rc;
+    if (!ctx->have_src) return fail(ctx, ICPK_E_NOT_SET, "source cloud not set");
+    if (int rc = ensure_unpacked(ctx)) return rc;
     *c = &ctx->src;
     return ICPK_OK;
   }
   if (from == ICPK_MAP_FROM_TARGET) {
-    if (!ctx->have_tgt) return icpk_host_fail(ctx, ICPK_E_NOT_SET, "target cloud not set");
+    if (!ctx->have_tgt) return fail(ctx, ICPK_E_NOT_SET, "target cloud not set");
     *c = &ctx->tgt;
     return ICPK_OK;
   }
-  return icpk_host_fail(ctx, ICPK_E_ARG, "bad map source (ICPK_MAP_FROM_*)");
+  return fail(ctx, ICPK_E_ARG, "bad map source (ICPK_MAP_FROM_*)");
 }
 
 bool bad_rule(int rule, int delta) {
@@ -324,8 +324,8 @@ int icpk_map_release(icpk_ctx* ctx) {
 
 int icpk_map_update(icpk_ctx* ctx, int32_t rule, int32_t from, const int32_t* indices, int32_t n, int32_t delta) {
   if (!ctx) return ICPK_E_ARG;
-  if (bad_rule(rule, delta)) return icpk_host_fail(ctx, ICPK_E_ARG, "bad map rule or delta (1 <= d <= 255)");
-  if (indices && n < 0) return icpk_host_fail(ctx, ICPK_E_ARG, "negative index count");
+  if (bad_rule(rule, delta)) return fail(ctx, ICPK_E_ARG, "bad map rule or delta (1 <= d <= 255)");
+  if (indices && n < 0) return fail(ctx, ICPK_E_ARG, "negative index count");
   int rc = ensure_map(ctx);
   if (rc) return rc;
   const Cloud* c = nullptr;
@@ -334,7 +334,7 @@ int icpk_map_update(icpk_ctx* ctx, int32_t rule, int32_t from, const int32_t* in
   MapPoints p{c->x(), c->y(), c->z(), nullptr, c->n};
   if (indices) {
     for (int32_t k = 0; k < n; ++k)
-      if (indices[k] < 0 || indices[k] >= c->n) return icpk_host_fail(ctx, ICPK_E_ARG, "map index outside the cloud");
+      if (indices[k] < 0 || indices[k] >= c->n) return fail(ctx, ICPK_E_ARG, "map index outside the cloud");
     icpk_map_state* m = ctx->map;
     rc = grow_int(ctx, m->idx, m->idx_cap, n);
     if (rc) return rc;
@@ -349,8 +349,8 @@ int icpk_map_update(icpk_ctx* ctx, int32_t rule, int32_t from, const int32_t* in
 int icpk_map_update_points(icpk_ctx* ctx, int32_t rule, const float* x, const float* y, const float* z, int32_t n,
                            int32_t delta) {
   if (!ctx) return ICPK_E_ARG;
-  if (bad_rule(rule, delta)) return icpk_host_fail(ctx, ICPK_E_ARG, "bad map rule or delta (1 <= d <= 255)");
-  if (n < 0 || (n > 0 && (!x || !y || !z))) return icpk_host_fail(ctx, ICPK_E_ARG, "bad point arrays");
+  if (bad_rule(rule, delta)) return fail(ctx, ICPK_E_ARG, "bad map rule or delta (1 <= d <= 255)");
+  if (n < 0 || (n > 0 && (!x || !y || !z))) return fail(ctx, ICPK_E_ARG, "bad point arrays");
   int rc = ensure_map(ctx);
   if (rc) return rc;
   if (n == 0) return ICPK_OK;
@@ -463,24 +463,19 @@ void icpk_map_voxel(const float p[3], int32_t v[3]) {
 }
 
 int icpk_align_to_map(icpk_ctx* ctx, const icpk_params* p, int32_t delta, float T_out[16], icpk_stats* stats) {
-  if (T_out)
-    for (int k = 0; k < 16; ++k) T_out[k] = (k % 5 == 0) ? 1.f : 0.f;
-  if (stats) std::memset(stats, 0, sizeof(*stats));
+  reset_outputs(T_out, stats);
   if (!ctx || !p || !T_out) return ICPK_E_ARG;
-  if (delta < 1 || delta > 255) return icpk_host_fail(ctx, ICPK_E_ARG, "bad delta (1 <= d <= 255)");
+  if (delta < 1 || delta > 255) return fail(ctx, ICPK_E_ARG, "bad delta (1 <= d <= 255)");
   if (p->solve != ICPK_SOLVE_REFERENCE && p->solve != ICPK_SOLVE_KABSCH)
-    return icpk_host_fail(ctx, ICPK_E_ARG, "icpk_align_to_map: reference or Kabsch flavour (the map has no normals)");
-  if (!ctx->have_src) return icpk_host_fail(ctx, ICPK_E_NOT_SET, "source cloud not set");
+    return fail(ctx, ICPK_E_ARG, "icpk_align_to_map: reference or Kabsch flavour (the map has no normals)");
+  if (!ctx->have_src) return fail(ctx, ICPK_E_NOT_SET, "source cloud not set");
   int rc = ensure_map(ctx);
   if (rc) return rc;
   icpk_map_state* m = ctx->map;
   if (m->list_n[ICPK_MAP_KEYPOINTS] == 0) {  // icp.cpp:490-491, :622-638, map.cpp:124-126
     rc = icpk_reset_source(ctx);
     if (rc) return rc;
-    ctx->trace_R.clear();
-    ctx->trace_t.clear();
-    ctx->trace_mse.clear();
-    ctx->trace_pairs.clear();
+    clear_trace(ctx);
     if (stats) stats->status = ICPK_W_EMPTY_MAP;
     return ICPK_W_EMPTY_MAP;
   }
@@ -498,7 +493,7 @@ int icpk_align_to_map(icpk_ctx* ctx, const icpk_params* p, int32_t delta, float 
   if (rc) return rc;
   const int nsw = niter + 1;
   const long long total_pos = (long long)ns * nsw;
-  if (total_pos > (1ll << 30)) return icpk_host_fail(ctx, ICPK_E_ARG, "too many sweep positions");
+  if (total_pos > (1ll << 30)) return fail(ctx, ICPK_E_ARG, "too many sweep positions");
   const int mpos = (int)total_pos;
   rc = ensure_scratch(ctx, mpos);
   if (!rc) rc = grow_planes(ctx, m->pos, m->pos_cap, mpos);
@@ -568,8 +563,8 @@ int icpk_map_lookup_to_target(icpk_ctx* ctx) {
   if (rc) return rc;
   icpk_map_state* m = ctx->map;
   const int n0 = m->list_n[0], n1 = m->list_n[1];
-  if ((long long)n0 + n1 + 1 > (1ll << 31) - 1) return icpk_host_fail(ctx, ICPK_E_ARG, "map lists too long for a target");
-  rc = icpk_host_ensure_cloud(ctx, ctx->tgt, n0 + n1 + 1);
+  if ((long long)n0 + n1 + 1 > (1ll << 31) - 1) return fail(ctx, ICPK_E_ARG, "map lists too long for a target");
+  rc = ensure_cloud(ctx, ctx->tgt, n0 + n1 + 1);
   if (rc) return rc;
   Cloud& c = ctx->tgt;
   float* dst[3] = {c.x(), c.y(), c.z()};
@@ -582,23 +577,22 @@ int icpk_map_lookup_to_target(icpk_ctx* ctx) {
                                    hipMemcpyDeviceToDevice, ctx->stream));
     ICPK_HIP(ctx, hipMemsetAsync(dst[k] + n0 + n1, 0, sizeof(float), ctx->stream));  // the zero point
   }
-  rc = icpk_host_target_replaced(ctx);
+  rc = pad_target(ctx);
   if (rc) return rc;
+  target_changed(ctx, false);
   ctx->tgt_lookup = true;
   ctx->tgt_lookup_version = ctx->map_version;
   return ICPK_OK;
 }
 
 int icpk_align_to_map_dense(icpk_ctx* ctx, const icpk_params* p, int32_t delta, float T_out[16], icpk_stats* stats) {
-  if (T_out)
-    for (int k = 0; k < 16; ++k) T_out[k] = (k % 5 == 0) ? 1.f : 0.f;
-  if (stats) std::memset(stats, 0, sizeof(*stats));
+  reset_outputs(T_out, stats);
   if (!ctx || !p || !T_out) return ICPK_E_ARG;
-  if (delta < 0 || delta > 255) return icpk_host_fail(ctx, ICPK_E_ARG, "bad delta (0 <= d <= 255)");
+  if (delta < 0 || delta > 255) return fail(ctx, ICPK_E_ARG, "bad delta (0 <= d <= 255)");
   if (p->solve != ICPK_SOLVE_REFERENCE && p->solve != ICPK_SOLVE_KABSCH)
-    return icpk_host_fail(ctx, ICPK_E_ARG, "icpk_align_to_map_dense: reference or Kabsch flavour (the map has no normals)");
-  if (!(p->max_nn_dist <= ICPK_MAX_NN_DISTANCE)) return icpk_host_fail(ctx, ICPK_E_ARG, "max_nn_dist above 0.75");
-  if (!ctx->have_src) return icpk_host_fail(ctx, ICPK_E_NOT_SET, "source cloud not set");
+    return fail(ctx, ICPK_E_ARG, "icpk_align_to_map_dense: reference or Kabsch flavour (the map has no normals)");
+  if (!(p->max_nn_dist <= ICPK_MAX_NN_DISTANCE)) return fail(ctx, ICPK_E_ARG, "max_nn_dist above 0.75");
+  if (!ctx->have_src) return fail(ctx, ICPK_E_NOT_SET, "source cloud not set");
   int rc = icpk_map_lookup_to_target(ctx);
   if (rc) return rc;
   icpk_params q = *p;
@@ -618,7 +612,7 @@ int icpk_align_to_map_dense(icpk_ctx* ctx, const icpk_params* p, int32_t delta, 
   if (rc) return rc;
   const int nsw = niter + 1;
   const long long total_pos = (long long)ns * nsw;
-  if (total_pos > (1ll << 30)) return icpk_host_fail(ctx, ICPK_E_ARG, "too many sweep positions");
+  if (total_pos > (1ll << 30)) return fail(ctx, ICPK_E_ARG, "too many sweep positions");
   rc = ensure_scratch(ctx, ns);
   if (!rc) rc = grow_planes(ctx, m->pos, m->pos_cap, (int)total_pos);
   if (!rc) rc = grow_planes(ctx, m->batch, m->batch_cap, ns);

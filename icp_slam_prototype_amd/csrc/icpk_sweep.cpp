@@ -1,0 +1,785 @@
+// icpk_sweep.cpp -- host side of the nearest-neighbour sweeps (K1 in every ICPK_NN_* mode) and of the reductions
+// (K2, K5): device buffers, target and query preparation, the frame-batch set-up recorder, and the C ABI's icpk_nn,
+// icpk_reduce, icpk_reduce_p2l and icpk_get_associations.
+#include <cstring>
+#include <utility>
+
+#include "icpk_ctx.h"
+
+using namespace icpk;
+
+namespace icpk {
+
+int ensure_cloud(icpk_ctx* ctx, Cloud& c, int n) {
+  if (ctx && (&c == &ctx->src0 || &c == &ctx->src)) ctx->src_pristine = false;  // (about to be resized or rewritten)
+  if (ctx && &c == &ctx->src) ctx->rec_pending = false;  // (whatever was to be unpacked into it is superseded)
+  if (ctx && (&c == &ctx->src0 || &c == &ctx->tgt)) ctx->have_pix_seed = false;  // (other points than the pixel maps describe)
+  const int cap = round_up(n < 1 ? 1 : n, NN_TILE);
+  if (cap > c.cap) {
+    if (c.base) ICPK_HIP(ctx, hipFree(c.base));
+    c.base = nullptr;
+    c.cap = 0;
+    // +64 floats: the filtered NN kernel prefetches one group past its chunk
+    ICPK_HIP(ctx, hipMalloc((void**)&c.base, ((size_t)3 * cap + 64) * sizeof(float)));
+    c.cap = cap;
+  }
+  c.n = n;
+  return ICPK_OK;
+}
+
+int ensure_assoc(icpk_ctx* ctx, int nq) {
+  const int cap = round_up(nq < 1 ? 1 : nq, NN_TILE);
+  if (cap > ctx->assoc_cap) {
+    if (ctx->best) ICPK_HIP(ctx, hipFree(ctx->best));
+    if (ctx->seed) ICPK_HIP(ctx, hipFree(ctx->seed));
+    if (ctx->best_m) ICPK_HIP(ctx, hipFree(ctx->best_m));
+    if (ctx->seed_m) ICPK_HIP(ctx, hipFree(ctx->seed_m));
+    ctx->best_m = ctx->seed_m = nullptr;
+    if (ctx->idx) ICPK_HIP(ctx, hipFree(ctx->idx));
+    if (ctx->dist) ICPK_HIP(ctx, hipFree(ctx->dist));
+    ctx->best = ctx->seed = nullptr;
+    ctx->idx = nullptr;
+    ctx->dist = nullptr;
+    ctx->assoc_cap = 0;
+    ctx->have_seed = false;
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->best, (size_t)cap * sizeof(nn_key_t)));
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->seed, (size_t)cap * sizeof(nn_key_t)));
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->best_m, (size_t)cap * sizeof(nn_key_t)));
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->seed_m, (size_t)cap * sizeof(nn_key_t)));
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->idx, (size_t)cap * sizeof(int32_t)));
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->dist, (size_t)cap * sizeof(float)));
+    ctx->assoc_cap = cap;
+  }
+  return ICPK_OK;
+}
+
+static int ensure_sort_buffers(icpk_ctx* ctx, int n) {
+  const int cap = round_up(n < 1 ? 1 : n, NN_TILE);
+  if (cap > ctx->sort_cap) {
+    if (ctx->sort_keys) ICPK_HIP(ctx, hipFree(ctx->sort_keys));
+    if (ctx->sort_vals) ICPK_HIP(ctx, hipFree(ctx->sort_vals));
+    ctx->sort_keys = nullptr;
+    ctx->sort_vals = nullptr;
+    ctx->sort_cap = 0;
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->sort_keys, (size_t)2 * cap * sizeof(unsigned)));
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->sort_vals, (size_t)cap * sizeof(int)));
+    ctx->sort_cap = cap;
+  }
+  if (!ctx->bounds) ICPK_HIP(ctx, hipMalloc((void**)&ctx->bounds, 6 * sizeof(float)));
+  return ICPK_OK;
+}
+
+static int ensure_scan_buffers(icpk_ctx* ctx);
+
+// Morton order of `c` (cells of the target's bounding box) -> perm_out[k] = index of the k-th point; the sorted keys
+// land in sort_keys[sort_cap ...), the unsorted ones stay in sort_keys[0 ... n)
+static int enqueue_morton_order(icpk_ctx* ctx, const Cloud& c, int* perm_out) {
+  int rc = ensure_sort_buffers(ctx, c.n);
+  if (rc) return rc;
+  rc = ensure_scan_buffers(ctx);
+  if (rc) return rc;
+  if (!ctx->morton_table) ICPK_HIP(ctx, hipMalloc((void**)&ctx->morton_table, sizeof(GridInfo)));
+  unsigned* ka = ctx->sort_keys;
+  unsigned* kb = ctx->sort_keys + ctx->sort_cap;
+  const int bits = ctx->grid_max_cells >= (1 << 21) + 1 ? 7 : 6;  // 8^bits cells + 1 bin + 1 must fit the count table
+  ctx->qcount_dirty = true;
+  launch_morton_order(c.x(), c.y(), c.z(), c.n, ctx->bounds, bits, ka, ctx->sort_vals, ctx->qcount, ctx->qstart, ctx->scan_bsum,
+                      ctx->morton_table, kb, perm_out, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ctx->qcount_dirty = false;
+  return ICPK_OK;
+}
+
+// boxes + Morton-ordered target for the pruned scan (once per target cloud)
+static int prepare_pruned_target(icpk_ctx* ctx, NnBoxes& bx) {
+  const int nt = ctx->tgt.n;
+  const int nt_pad = round_up(nt, NN_TILE);
+  const int ntiles = nt_pad / NN_TILE;
+  if (ntiles > ctx->boxes_tiles_cap) {
+    if (ctx->boxes) ICPK_HIP(ctx, hipFree(ctx->boxes));
+    ctx->boxes = nullptr;
+    ctx->boxes_tiles_cap = 0;
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->boxes, (size_t)6 * (ntiles + 16) * (1 + NN_SUBS) * sizeof(float)));
+    ctx->boxes_tiles_cap = ntiles;
+    ctx->have_boxes = false;
+  }
+  if (nt_pad > ctx->tperm_cap) {
+    if (ctx->tperm) ICPK_HIP(ctx, hipFree(ctx->tperm));
+    ctx->tperm = nullptr;
+    ctx->tperm_cap = 0;
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->tperm, ((size_t)nt_pad + 64) * sizeof(int)));
+    if (ctx->tkeys) ICPK_HIP(ctx, hipFree(ctx->tkeys));
+    ctx->tkeys = nullptr;
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->tkeys, ((size_t)nt_pad + 64) * sizeof(unsigned)));
+    ctx->tperm_cap = nt_pad;
+    ctx->have_boxes = false;
+  }
+  bx.tbox_stride = ctx->boxes_tiles_cap + 16;
+  bx.sbox_stride = (ctx->boxes_tiles_cap + 16) * NN_SUBS;
+  bx.tbox = ctx->boxes;
+  bx.sbox = ctx->boxes + (size_t)6 * bx.tbox_stride;
+  bx.ox = ctx->tgt.x();
+  bx.oy = ctx->tgt.y();
+  bx.oz = ctx->tgt.z();
+  bx.tperm = ctx->tperm;
+  bx.qperm = ctx->qperm;
+  if (ctx->have_boxes) return ICPK_OK;
+  int rc = ensure_cloud(ctx, ctx->sorted, nt);
+  if (rc) return rc;
+  rc = ensure_sort_buffers(ctx, nt);
+  if (rc) return rc;
+  // bounds of the cloud from boxes of the caller's order, then sort, gather, final boxes
+  launch_tile_boxes(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), nt, ntiles, bx, ctx->stream);
+  launch_bounds(bx.tbox, bx.tbox_stride, ntiles, ctx->bounds, ctx->stream);
+  rc = enqueue_morton_order(ctx, ctx->tgt, ctx->tperm);
+  if (rc) return rc;
+  ICPK_HIP(ctx, hipMemcpyAsync(ctx->tkeys, ctx->sort_keys + ctx->sort_cap, (size_t)nt * sizeof(unsigned),
+                               hipMemcpyDeviceToDevice, ctx->stream));
+  launch_gather_planes(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), ctx->tperm, nt, nt_pad, __builtin_inff(),
+                       ctx->sorted.x(), ctx->sorted.y(), ctx->sorted.z(), ctx->tperm, ctx->stream);
+  launch_tile_boxes(ctx->sorted.x(), ctx->sorted.y(), ctx->sorted.z(), nt, ntiles, bx, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ctx->have_boxes = true;
+  return ICPK_OK;
+}
+
+// counts / starts of the counting sorts by cell (targets: cell_start; queries: qstart).  The count table is
+// all zero between two sorts (the scan hands it back zeroed); a sort that did not get as far as its scan --
+// a failed launch -- leaves it marked dirty, and the next one clears all of it first.
+static int ensure_scan_buffers(icpk_ctx* ctx) {
+  const size_t bytes = ((size_t)ctx->grid_max_cells + 1) * sizeof(int);
+  if (!ctx->qcount) {
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->qcount, bytes));
+    ctx->qcount_dirty = true;
+  }
+  if (ctx->qcount_dirty) {
+    ICPK_HIP(ctx, hipMemsetAsync(ctx->qcount, 0, bytes, ctx->stream));
+    ctx->qcount_dirty = false;
+  }
+  if (!ctx->qstart) ICPK_HIP(ctx, hipMalloc((void**)&ctx->qstart, bytes));
+  if (!ctx->scan_bsum) ICPK_HIP(ctx, hipMalloc((void**)&ctx->scan_bsum, (size_t)GRID_SCAN_BLOCKS * sizeof(int)));
+  return ICPK_OK;
+}
+
+// the grid scan's geometry, cell table and float4 copies of the target (a reallocation drops the grid)
+static int ensure_grid_buffers(icpk_ctx* ctx) {
+  const int nt = ctx->tgt.n;
+  if (nt > (1 << 28)) return fail(ctx, ICPK_E_ARG, "the grid search addresses its cell-sorted targets with 32-bit byte offsets: at most 2^28 target points");
+  if (!ctx->grid_info) ICPK_HIP(ctx, hipMalloc((void**)&ctx->grid_info, sizeof(GridInfo)));
+  if (!ctx->grid_bounds)
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->grid_bounds, (size_t)GRID_BOUNDS_PARTS * 6 * sizeof(float)));
+  if (!ctx->cell_start) ICPK_HIP(ctx, hipMalloc((void**)&ctx->cell_start, ((size_t)ctx->grid_max_cells + 1) * sizeof(int)));
+  if (nt > ctx->t4_cap) {
+    if (ctx->t4) ICPK_HIP(ctx, hipFree(ctx->t4));
+    if (ctx->o4) ICPK_HIP(ctx, hipFree(ctx->o4));
+    ctx->t4 = ctx->o4 = nullptr;
+    ctx->t4_cap = 0;
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->t4, ((size_t)round_up(nt, NN_TILE) + 64) * sizeof(float4)));
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->o4, ((size_t)round_up(nt, NN_TILE) + 64) * sizeof(float4)));
+    ctx->t4_cap = round_up(nt, NN_TILE);
+    ctx->have_grid = false;
+  }
+  return ICPK_OK;
+}
+
+// cell table + cell-sorted AoS copy of the target for the grid scan (once per target cloud).
+// Everything is enqueued: the grid's size stays on the device (GridInfo), the counting sort's
+// zero fill and scan read it there -- no host round trip, so the frame-batch mode can build the
+// next group's grids in the shadow of the running loop.
+static int prepare_grid_target(icpk_ctx* ctx) {
+  const int nt = ctx->tgt.n;
+  int rc = ensure_grid_buffers(ctx);
+  if (rc || ctx->have_grid) return rc;
+  rc = ensure_sort_buffers(ctx, nt);
+  if (rc) return rc;
+  rc = ensure_scan_buffers(ctx);
+  if (rc) return rc;
+  launch_grid_bounds(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), nt, ctx->grid_bounds, ctx->stream);
+  launch_grid_info(ctx->grid_bounds, nt, ctx->tune.grid_ppc, ctx->tune.grid_xdiv, ctx->grid_max_cells, ctx->grid_info, ctx->stream);
+  // counting sort of the targets by cell: slot within the cell by atomics (the order inside a
+  // cell is irrelevant: candidates are merged lexicographically), cell starts by an exclusive
+  // scan of the counts (entry ncells = Nt), scatter into the AoS copy
+  int* tcell = reinterpret_cast<int*>(ctx->sort_keys + ctx->sort_cap);
+  int* tslot = ctx->sort_vals;
+  ctx->qcount_dirty = true;
+  launch_grid_qslot(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), nt, ctx->grid_info, ctx->qcount, tcell, tslot, 0,
+                    ctx->stream);
+  launch_grid_scan(ctx->qcount, ctx->cell_start, ctx->scan_bsum, ctx->grid_info, 0, ctx->stream);
+  launch_grid_tscatter(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), tcell, tslot, ctx->cell_start, nt, ctx->t4, ctx->o4,
+                       ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ctx->qcount_dirty = false;
+  ctx->have_grid = true;
+  return ICPK_OK;
+}
+
+// query order for the grid scan: counting sort of the source by cell of the target's grid.
+// with_points: the scatter also writes the scan-order queries and element 0 as everybody's seed
+// (the first sweep of an alignment that has no seeds)
+static int enqueue_cell_order(icpk_ctx* ctx, bool with_points) {
+  const int nq = ctx->src.n;
+  int rc = ensure_sort_buffers(ctx, nq);
+  if (rc) return rc;
+  rc = ensure_scan_buffers(ctx);
+  if (rc) return rc;
+  int* qcell = reinterpret_cast<int*>(ctx->sort_keys + ctx->sort_cap);
+  int* qslot = ctx->sort_vals;
+  // (locality only: the coarser table, xdiv times fewer counts to scan)
+  ctx->qcount_dirty = true;
+  launch_grid_qslot(ctx->src.x(), ctx->src.y(), ctx->src.z(), nq, ctx->grid_info, ctx->qcount, qcell, qslot, 1,
+                    ctx->stream);
+  launch_grid_scan(ctx->qcount, ctx->qstart, ctx->scan_bsum, ctx->grid_info, 1, ctx->stream);
+  launch_grid_qscatter(qcell, qslot, ctx->qstart, nq, ctx->qperm, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->tgt.x(),
+                       ctx->tgt.y(), ctx->tgt.z(), with_points ? ctx->qm4 : nullptr, ctx->sp_in, ctx->seed_m, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ctx->qcount_dirty = false;
+  return ICPK_OK;
+}
+
+static int ensure_query_points(icpk_ctx* ctx, int nq);
+
+// After a device loop of grid sweeps the caller-order views -- the moved source planes, the association keys -- exist
+// only as records (ctx->rec, kernels_grid.hip); they are unpacked when something asks for them (icpk_get_source,
+// icpk_get_associations, icpk_commit_source, icpk_transform_source, icpk_nn, icpk_reduce ...) and dropped when the
+// working source is overwritten first (the next alignment, a new source): a tracker that only wants the pose never
+// pays the launch.  ICPK_LAZY_UNPACK=0: unpack at the end of every loop.
+int ensure_unpacked(icpk_ctx* ctx) {
+  if (!ctx->rec_pending) return ICPK_OK;
+  ctx->rec_pending = false;
+  launch_grid_unpack(ctx->qm4, ctx->rec, ctx->src.n, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->best, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  return ICPK_OK;
+}
+
+// the deferred initial LoopState of a device loop (device_loop_begin), if no set-up launch has carried it
+int flush_loop_init(icpk_ctx* ctx) {
+  if (!ctx->init_pending) return ICPK_OK;
+  ctx->init_pending = false;
+  launch_loop_init(ctx->pending_init, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  return ICPK_OK;
+}
+
+// A FRESH pair (new target, new source, no seeds: every frame of the drop-in path): the target's grid and the
+// query order in 6 launches instead of 10 -- the two counting sorts run side by side (cell slots of both clouds in one
+// launch, both scans in two, both scatters in one), each with its own count table.  Same kernels' bodies as
+// prepare_grid_target + enqueue_cell_order: same tables, same copies.  ~5 us of launch latency per launch saved on a
+// path that is a chain of tiny dependent kernels.
+static int build_grid_and_order(icpk_ctx* ctx) {
+  const int nt = ctx->tgt.n, nq = ctx->src.n;
+  int rc = ensure_grid_buffers(ctx);
+  if (rc) return rc;
+  rc = ensure_sort_buffers(ctx, nq > nt ? nq : nt);
+  if (rc) return rc;
+  rc = ensure_scan_buffers(ctx);
+  if (rc) return rc;
+  const size_t table = ((size_t)ctx->grid_max_cells + 1) * sizeof(int);
+  if (!ctx->qcount2) {
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->qcount2, table));
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->scan_bsum2, (size_t)GRID_SCAN_BLOCKS * sizeof(int)));
+    ctx->qcount2_dirty = true;
+  }
+  if (ctx->qcount2_dirty) {  // (first use, or a sort that was cut short: the scans hand the table back zeroed otherwise)
+    ICPK_HIP(ctx, hipMemsetAsync(ctx->qcount2, 0, table, ctx->stream));
+    ctx->qcount2_dirty = false;
+  }
+  if (ctx->sort_cap > ctx->sort_vals2_cap) {
+    if (ctx->sort_vals2) ICPK_HIP(ctx, hipFree(ctx->sort_vals2));
+    ctx->sort_vals2 = nullptr;
+    ctx->sort_vals2_cap = 0;
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->sort_vals2, (size_t)ctx->sort_cap * sizeof(int)));
+    ctx->sort_vals2_cap = ctx->sort_cap;
+  }
+  int* tcell = reinterpret_cast<int*>(ctx->sort_keys + ctx->sort_cap);
+  int* tslot = ctx->sort_vals;
+  int* qcell = reinterpret_cast<int*>(ctx->sort_keys);
+  int* qslot = ctx->sort_vals2;
+  if (!ctx->grid_ticket) {
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->grid_ticket, sizeof(int)));
+    ICPK_HIP(ctx, hipMemsetAsync(ctx->grid_ticket, 0, sizeof(int), ctx->stream));
+  }
+  // bounds + geometry (+ the pending initial LoopState of the alignment being enqueued) in ONE launch
+  launch_grid_begin(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), nt, ctx->grid_bounds, ctx->tune.grid_ppc, ctx->tune.grid_xdiv,
+                    ctx->grid_max_cells, ctx->grid_info, ctx->init_pending ? &ctx->pending_init : nullptr, ctx->grid_ticket,
+                    ctx->stream);
+  ctx->init_pending = false;
+  ctx->qcount_dirty = ctx->qcount2_dirty = true;
+  SetupBatchOf<QslotArgs> qb{};
+  qb.p[0] = QslotArgs{ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), ctx->grid_info, ctx->qcount, tcell, tslot, nt, 0};
+  qb.p[1] = QslotArgs{ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->grid_info, ctx->qcount2, qcell, qslot, nq, 1};
+  // A source that icpk_backproject_pair has just made is in row-major IMAGE order: eight consecutive points are a short
+  // run of one image row, as close together as a grid cell's -- the queries are swept in the caller's order and their
+  // counting sort is left out (-3.5 us per 92k-point pair, -14 us at 306k; ICPK_IMAGE_ORDER=0: sort them all the same).
+  const bool ident = ctx->have_pix_seed && ctx->tune.image_order;
+  launch_grid_qslot_batch(qb, ident ? 1 : 2, ctx->stream);
+  SetupBatchOf<ScanArgs> sb{};
+  sb.p[0] = ScanArgs{ctx->qcount, ctx->cell_start, ctx->scan_bsum, ctx->grid_info, 0, 0};
+  sb.p[1] = ScanArgs{ctx->qcount2, ctx->qstart, ctx->scan_bsum2, ctx->grid_info, 1, 0};
+  launch_grid_scan_batch(sb, ident ? 1 : 2, ctx->stream);
+  const TscatterArgs ta{ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), tcell, tslot, ctx->cell_start, ctx->t4, ctx->o4, nt, 0};
+  const bool pix = ctx->have_pix_seed && ctx->tune.pixel_seeds;
+  const QscatterArgs qa{ident ? nullptr : qcell,        qslot,        ctx->qstart,  ctx->qperm,   ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->tgt.x(),
+                        ctx->tgt.y(), ctx->tgt.z(), ctx->qm4,     ctx->sp_in,   ctx->seed_m,  nq,           0,
+                        pix ? ctx->pix_src : nullptr, pix ? ctx->pix_tidx : nullptr, ctx->pix_rows, ctx->pix_cols};
+  launch_grid_tqscatter(ta, qa, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ctx->qcount_dirty = ctx->qcount2_dirty = false;
+  ctx->have_grid = true;
+  return ICPK_OK;
+}
+
+// scan-order copies of the queries and of their seed points (grid scan)
+static int ensure_query_points(icpk_ctx* ctx, int nq) {
+  if (nq <= ctx->qm4_cap) return ICPK_OK;
+  for (float4** pp : {&ctx->qm4, &ctx->sp_in, &ctx->sp_out, &ctx->rec}) {
+    if (*pp) ICPK_HIP(ctx, hipFree(*pp));
+    *pp = nullptr;
+  }
+  ctx->qm4_cap = 0;
+  const size_t bytes = ((size_t)round_up(nq, NN_TILE) + 64) * sizeof(float4);
+  ICPK_HIP(ctx, hipMalloc((void**)&ctx->qm4, bytes));
+  ICPK_HIP(ctx, hipMalloc((void**)&ctx->sp_in, bytes));
+  ICPK_HIP(ctx, hipMalloc((void**)&ctx->sp_out, bytes));
+  ICPK_HIP(ctx, hipMalloc((void**)&ctx->rec, 2 * bytes));
+  ctx->qm4_cap = round_up(nq, NN_TILE);
+  ctx->grid_chain = false;
+  return ICPK_OK;
+}
+
+// Everything a pruned / grid sweep needs before its K1 launch: query order (once per alignment),
+// seeds in scan order, buffer rotation.  Enqueues on ctx->stream only for the FIRST sweep of a
+// chain; for a sweep that continues a chain of grid sweeps inside a device loop it merely
+// rotates pointers.  recheck = 1: the seeds are loose (first sweep).
+int prepare_sorted_sweep(icpk_ctx* ctx, int nn_mode, NnArgs& a, NnBoxes& bx, int& recheck) {
+  const int nq = ctx->src.n;
+  int rc = ICPK_OK;
+  if (round_up(nq, NN_TILE) > ctx->qperm_cap) {
+    if (ctx->qperm) ICPK_HIP(ctx, hipFree(ctx->qperm));
+    ctx->qperm = nullptr;
+    ctx->qperm_cap = 0;
+    ICPK_HIP(ctx, hipMalloc((void**)&ctx->qperm, (size_t)round_up(nq, NN_TILE) * sizeof(int)));
+    ctx->qperm_cap = round_up(nq, NN_TILE);
+    ctx->have_qperm = false;
+  }
+  bx = NnBoxes{};
+  bool fresh = false;
+  if (nn_mode == ICPK_NN_GRID) {
+    bx.ox = ctx->tgt.x();
+    bx.oy = ctx->tgt.y();
+    bx.oz = ctx->tgt.z();
+    // (one size for both counting sorts up front: the target's sort must not see its scratch re-allocated by
+    // the queries' -- its launches may only have been recorded so far, see SetupRecorder)
+    rc = ensure_sort_buffers(ctx, nq > ctx->tgt.n ? nq : ctx->tgt.n);
+    // a fresh pair (no grid yet, no seeds, launches not being recorded for a lock-step group): both sorts side by side
+    fresh = !rc && !ctx->have_grid && !ctx->have_seed && !setup_recorder() && ctx->tune.merged_setup && ctx->tgt.n > 0;
+    if (fresh) {
+      rc = ensure_query_points(ctx, nq);
+      if (!rc) rc = build_grid_and_order(ctx);
+    } else {
+      if (!rc) rc = prepare_grid_target(ctx);
+      if (!rc) rc = ensure_query_points(ctx, nq);
+    }
+  } else {
+    rc = prepare_pruned_target(ctx, bx);
+  }
+  if (rc) return rc;
+  bool new_order = false;
+  bool points_written = false;  // qm4 / sp_in / seed_m already hold this sweep's queries and seeds
+  const int want_kind = nn_mode == ICPK_NN_GRID ? 2 : 1;
+  if (fresh) {  // order, scan-order queries and literal seeds were written by build_grid_and_order
+    ctx->have_qperm = true;
+    ctx->qperm_kind = want_kind;
+    new_order = true;
+    points_written = true;
+  } else if (!ctx->have_qperm || !ctx->have_seed || ctx->qperm_kind != want_kind) {
+    // query order (once per alignment), from the source at its current pose: Morton order
+    // for the pruned scan (the unsorted Morton keys of the queries stay in sort_keys[0..nq)
+    // for its first-sweep seeds), order by grid cell (a cheaper counting sort) for the grid scan
+    if (nn_mode == ICPK_NN_GRID) {
+      points_written = !ctx->have_seed;
+      rc = enqueue_cell_order(ctx, points_written);
+    } else {
+      rc = enqueue_morton_order(ctx, ctx->src, ctx->qperm);
+    }
+    if (rc) return rc;
+    ctx->have_qperm = true;
+    ctx->qperm_kind = want_kind;
+    new_order = true;
+  }
+  recheck = 0;
+  if (ctx->have_seed && ctx->have_seed_m && !new_order) {
+    // matches of the previous pruned sweep, already in query Morton order
+    std::swap(ctx->seed_m, ctx->best_m);
+    std::swap(ctx->seed, ctx->best);
+  } else if (ctx->have_seed) {  // matches of a sweep by another kernel: bring them into Morton order
+    launch_seed_gather(ctx->best, ctx->qperm, nq, ctx->seed_m, ctx->stream);
+    std::swap(ctx->seed, ctx->best);
+  } else if (nn_mode == ICPK_NN_GRID) {
+    // first sweep of the grid scan: the reference's own literal seed, element 0 (icp.cpp:572);
+    // the expanding search does not depend on the seed's quality
+    if (!points_written) launch_fill_u64(ctx->seed_m, nq, 0ull, nullptr, ctx->stream);
+    recheck = 1;
+  } else {  // first sweep: the target with the nearest Morton code; loose, so re-check lazily
+    launch_seed_morton(ctx->sort_keys, ctx->qperm, nq, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->tkeys,
+                       ctx->sorted.x(), ctx->sorted.y(), ctx->sorted.z(), ctx->tperm, ctx->tgt.n, ctx->seed_m,
+                       ctx->stream);
+    recheck = 1;
+  }
+  a.tx = ctx->sorted.x();
+  a.ty = ctx->sorted.y();
+  a.tz = ctx->sorted.z();
+  a.tiles_per_chunk = a.nt_pad / NN_TILE;
+  a.best = ctx->best;
+  if (nn_mode == ICPK_NN_GRID) {
+    // inside a device loop the grid sweeps keep qm4 / the seed points current themselves;
+    // anywhere else the source may have been moved by other kernels: gather afresh
+    if (!(ctx->st_active && ctx->grid_chain) && !points_written)
+      launch_grid_query_points(ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->qperm, nq, ctx->seed_m, bx.ox, bx.oy,
+                               bx.oz, ctx->qm4, ctx->sp_in, ctx->stream);
+  }
+  ICPK_HIP(ctx, hipGetLastError());
+  return ICPK_OK;
+}
+
+// lanes per query of the grid scan (measured with cells 4x finer along x: 8 is best up to 217k queries, 4 from
+// 307k on; a launch that fills the GPU several times over is issue-bound and prefers fewer, longer lanes)
+static int grid_slices_for(const icpk_ctx* ctx, int nq) { return ctx->tune.grid_slices ? ctx->tune.grid_slices : (nq > 524288 ? 4 : 8); }
+
+// the K1d arguments of the sweep prepare_sorted_sweep has just set up, and the bookkeeping
+// that follows its launch
+GridSweepArgs grid_sweep_args(icpk_ctx* ctx, const NnArgs& a, const NnBoxes& bx) {
+  GridSweepArgs g{};
+  g.qx = const_cast<float*>(a.qx);
+  g.qy = const_cast<float*>(a.qy);
+  g.qz = const_cast<float*>(a.qz);
+  g.nq = a.nq;
+  g.qm4 = ctx->qm4;
+  g.t4 = ctx->t4;
+  g.cell_start = ctx->cell_start;
+  g.gi = ctx->grid_info;
+  g.ox = bx.ox;
+  g.oy = bx.oy;
+  g.oz = bx.oz;
+  g.sp_in = ctx->sp_in;
+  g.sp_out = ctx->sp_out;
+  g.best = a.best;
+  g.best_m = ctx->best_m;
+  g.st = ctx->st_active;
+  g.rec = ctx->st_active ? ctx->rec : nullptr;  // inside a device loop K2 reads the records; planes / keys once at the end
+  return g;
+}
+void after_grid_sweep(icpk_ctx* ctx) {
+  std::swap(ctx->sp_in, ctx->sp_out);
+  ctx->grid_chain = ctx->st_active != nullptr;
+  ctx->have_assoc = true;
+  ctx->have_seed = true;
+  ctx->have_seed_m = true;
+}
+
+NnArgs base_nn_args(const icpk_ctx* ctx) {
+  NnArgs a;
+  a.qx = ctx->src.x();
+  a.qy = ctx->src.y();
+  a.qz = ctx->src.z();
+  a.nq = ctx->src.n;
+  a.tx = ctx->tgt.x();
+  a.ty = ctx->tgt.y();
+  a.tz = ctx->tgt.z();
+  a.nt_pad = round_up(ctx->tgt.n, NN_TILE);
+  a.tiles_per_chunk = a.nt_pad / NN_TILE;
+  a.best = ctx->best;
+  a.stop = ctx->stop;
+  return a;
+}
+
+// enqueue one NN sweep (K1) over the working source; ev0/ev1 (optional) are recorded
+// immediately before/after the K1 launch itself, so that set-up kernels of a first sweep
+// (sort, seeding, fills) do not count as kernel time
+int enqueue_nn(icpk_ctx* ctx, int nn_mode, hipEvent_t ev0, hipEvent_t ev1) {
+  auto mark = [&](hipEvent_t e) -> int {
+    if (e) ICPK_HIP(ctx, hipEventRecord(e, ctx->stream));
+    return ICPK_OK;
+  };
+  if (nn_mode != ICPK_NN_EXACT && nn_mode != ICPK_NN_FILTERED && nn_mode != ICPK_NN_PRUNED && nn_mode != ICPK_NN_GRID &&
+      nn_mode != ICPK_NN_MAP)
+    return fail(ctx, ICPK_E_ARG, "unknown nn_mode");
+  if (nn_mode == ICPK_NN_MAP && !icpk_map_lookup_current(ctx))
+    return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP needs the map's current lookup target (icpk_map_lookup_to_target)");
+  const int nq = ctx->src.n;
+  int rc = ensure_assoc(ctx, nq);
+  if (rc) return rc;
+  if (nq == 0) {
+    ctx->have_assoc = true;
+    return ICPK_OK;
+  }
+  auto chunking = [&](int nqb, int ntiles) {
+    int nchunks = (ctx->tune.target_blocks + nqb - 1) / nqb;
+    if (nchunks < 1) nchunks = 1;
+    if (nchunks > ntiles) nchunks = ntiles;
+    return (ntiles + nchunks - 1) / nchunks;
+  };
+  NnArgs a = base_nn_args(ctx);
+  const int ntiles = a.nt_pad / NN_TILE;
+  if (nn_mode != ICPK_NN_GRID && (rc = flush_loop_init(ctx))) return rc;  // (their fills and kernels look at the state)
+  if (nn_mode == ICPK_NN_MAP) {  // K9 (icpk_map.cpp): the sweep's keys index the lookup target
+    if ((rc = mark(ev0))) return rc;
+    if ((rc = icpk_map_nn_sweep(ctx))) return rc;
+    if ((rc = mark(ev1))) return rc;
+    ICPK_HIP(ctx, hipGetLastError());
+    ctx->grid_chain = false;
+    ctx->have_assoc = true;
+    ctx->have_seed = false;  // (a lookup result is no nearest target: it must not seed a filtered sweep)
+    ctx->have_seed_m = false;
+    return ICPK_OK;
+  }
+  if (nn_mode == ICPK_NN_EXACT) {
+    a.tiles_per_chunk = chunking((nq + NN_THREADS - 1) / NN_THREADS, ntiles);
+    a.best = ctx->best;
+    launch_fill_u64(ctx->best, nq, NN_KEY_INIT, ctx->stop, ctx->stream);
+    if ((rc = mark(ev0))) return rc;
+    launch_nn_exact(a, ctx->stream);
+    if ((rc = mark(ev1))) return rc;
+  } else if (nn_mode == ICPK_NN_PRUNED || nn_mode == ICPK_NN_GRID) {
+    NnBoxes bx{};
+    int recheck = 0;
+    rc = prepare_sorted_sweep(ctx, nn_mode, a, bx, recheck);
+    if (rc) return rc;
+    if ((rc = flush_loop_init(ctx))) return rc;  // (unless the set-up's first launch has carried it)
+    if ((rc = mark(ev0))) return rc;
+    if (nn_mode == ICPK_NN_GRID) {
+      launch_nn_grid(grid_sweep_args(ctx, a, bx), grid_slices_for(ctx, nq), recheck, ctx->stream);
+      after_grid_sweep(ctx);
+    } else {
+      // lanes per query: as many as keep the launch at <= ~10k waves (measured best: 16 at 10k
+      // queries, 4 at 92k, 2 at 217k-307k, 1 at 10^6)
+      int slices = ctx->tune.slices;
+      if (slices == 0) {
+        slices = 16;
+        while (slices > 1 && (long long)nq * slices / 64 > 10000) slices >>= 1;
+      }
+      launch_nn_pruned(a, ctx->seed_m, ctx->best_m, bx, slices, recheck, ctx->st_active, ctx->stream);
+      ctx->grid_chain = false;
+      ctx->have_assoc = true;
+      ctx->have_seed = true;
+      ctx->have_seed_m = true;
+    }
+    if ((rc = mark(ev1))) return rc;
+    ICPK_HIP(ctx, hipGetLastError());
+    return ICPK_OK;
+  } else {
+    int seed_scale = 1;
+    if (ctx->have_seed) {
+      // matches of the previous sweep (same clouds, source possibly moved) seed this one
+      std::swap(ctx->seed, ctx->best);
+    } else {
+      // coarse pre-pass: exact NN against every NN_SEED_STRIDE-th target
+      if (!ctx->have_dec) {
+        const int nd = (ctx->tgt.n + NN_SEED_STRIDE - 1) / NN_SEED_STRIDE;
+        rc = ensure_cloud(ctx, ctx->dec, nd);
+        if (rc) return rc;
+        launch_decimate(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), ctx->tgt.n, NN_SEED_STRIDE, ctx->dec.x(),
+                        ctx->dec.y(), ctx->dec.z(), round_up(nd, NN_TILE), ctx->stream);
+        ctx->have_dec = true;
+      }
+      NnArgs c = a;
+      c.tx = ctx->dec.x();
+      c.ty = ctx->dec.y();
+      c.tz = ctx->dec.z();
+      c.nt_pad = round_up(ctx->dec.n, NN_TILE);
+      c.tiles_per_chunk = chunking((nq + NN_THREADS - 1) / NN_THREADS, c.nt_pad / NN_TILE);
+      c.best = ctx->seed;
+      launch_fill_u64(ctx->seed, nq, NN_KEY_INIT, ctx->stop, ctx->stream);
+      launch_nn_exact(c, ctx->stream);
+      seed_scale = NN_SEED_STRIDE;
+    }
+    const int q = ctx->tune.q_per_lane > 0 ? ctx->tune.q_per_lane : (nq >= 65536 ? 2 : 1);
+    a.tiles_per_chunk = chunking((nq + NN_THREADS * q - 1) / (NN_THREADS * q), ntiles);
+    a.best = ctx->best;
+    launch_fill_u64(ctx->best, nq, NN_KEY_INIT, ctx->stop, ctx->stream);
+    if ((rc = mark(ev0))) return rc;
+    launch_nn_filtered(a, ctx->seed, seed_scale, q, ctx->stream);
+    if ((rc = mark(ev1))) return rc;
+  }
+  ICPK_HIP(ctx, hipGetLastError());
+  ctx->have_assoc = true;
+  ctx->have_seed = true;
+  ctx->have_seed_m = false;  // exact / filtered sweeps leave their matches in the caller's order only
+  return ICPK_OK;
+}
+
+// the records of the grid sweep just enqueued, if it was one of a device loop (then planes and keys are stale until
+// the loop's final unpack)
+const float4* loop_rec(const icpk_ctx* ctx) { return ctx->st_active && ctx->grid_chain ? ctx->rec : nullptr; }
+
+// outside a device loop: the sums and the pair count of the reduction just enqueued into red_host (not waited for)
+static int read_back_sums(icpk_ctx* ctx, int nsum) {
+  ICPK_HIP(ctx, hipGetLastError());
+  if (!ctx->st_active)
+    ICPK_HIP(ctx, hipMemcpyAsync(ctx->red_host, ctx->red_out, (nsum + 1) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  return ICPK_OK;
+}
+
+// enqueue K2 and the 160-byte read-back; caller synchronises
+int enqueue_reduce(icpk_ctx* ctx, float max_dist) {
+  const int nq = ctx->src.n;
+  launch_assoc_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), nq, ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(),
+                      ctx->have_grid ? ctx->o4 : nullptr, loop_rec(ctx), max_dist, ctx->st_active ? nullptr : ctx->idx, ctx->st_active ? nullptr : ctx->dist, ctx->partial,
+                      ctx->pcount, ctx->st_active ? nullptr : ctx->red_out,
+                      ctx->st_active, ctx->st_active ? ctx->loop_nact : NSUM, ctx->stream);
+  return read_back_sums(ctx, NSUM);
+}
+
+// point-to-plane flavour of enqueue_reduce (K5)
+int enqueue_reduce_p2l(icpk_ctx* ctx, float max_dist) {
+  launch_p2l_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->src.n, ctx->tgt.x(), ctx->tgt.y(),
+                    ctx->tgt.z(), ctx->nrm.x(), ctx->nrm.y(), ctx->nrm.z(), loop_rec(ctx), max_dist, ctx->st_active ? nullptr : ctx->idx,
+                    ctx->st_active ? nullptr : ctx->dist, ctx->partial,
+                    ctx->pcount, ctx->st_active ? nullptr : ctx->red_out, ctx->st_active, ctx->stream);
+  return read_back_sums(ctx, NP2L);
+}
+
+// ---- deferred set-up launches (icpk_internal.h) ----
+SetupRecorder*& setup_recorder() {
+  static thread_local SetupRecorder* rec = nullptr;
+  return rec;
+}
+
+// every pair of the group recorded the same steps in the same order?
+static bool same_sequences(const SetupRecorder* recs, int count) {
+  for (int k = 0; k < count; ++k) {
+    if (recs[k].overflow || recs[k].n != recs[0].n) return false;
+    for (int j = 0; j < recs[0].n; ++j)
+      if (recs[k].calls[j].kind != recs[0].calls[j].kind) return false;
+  }
+  return true;
+}
+
+bool flush_setup_batches(const SetupRecorder* recs, int count, hipStream_t s) {
+  if (count <= 0) return true;
+  if (count > BATCH_MAX || !same_sequences(recs, count)) return false;
+  for (int j = 0; j < recs[0].n; ++j) {
+#define ICPK_STEP(KIND, FIELD, TYPE, LAUNCH)                        \
+  case KIND: {                                                      \
+    SetupBatchOf<TYPE> b;                                           \
+    for (int k = 0; k < count; ++k) b.p[k] = recs[k].calls[j].FIELD; \
+    LAUNCH(b, count, s);                                            \
+    break;                                                          \
+  }
+    switch (recs[0].calls[j].kind) {
+      ICPK_STEP(SK_INGEST, ingest, IngestArgs, launch_ingest_batch)
+      ICPK_STEP(SK_LOOP_INIT, loop_init, LoopInitArgs, launch_loop_init_batch)
+      ICPK_STEP(SK_BOUNDS, bounds, BoundsArgs, launch_grid_bounds_batch)
+      ICPK_STEP(SK_INFO, info, InfoArgs, launch_grid_info_batch)
+      ICPK_STEP(SK_QSLOT, qslot, QslotArgs, launch_grid_qslot_batch)
+      ICPK_STEP(SK_SCAN, scan, ScanArgs, launch_grid_scan_batch)
+      ICPK_STEP(SK_TSCATTER, tscatter, TscatterArgs, launch_grid_tscatter_batch)
+      ICPK_STEP(SK_QSCATTER, qscatter, QscatterArgs, launch_grid_qscatter_batch)
+      default: return false;
+    }
+#undef ICPK_STEP
+  }
+  return true;
+}
+
+// one pair's recorded steps, launched one by one (the sequences of a group differed)
+void replay_setup(const SetupRecorder& rec, hipStream_t s) {
+  SetupRecorder* const saved = setup_recorder();
+  setup_recorder() = nullptr;
+  for (int j = 0; j < rec.n; ++j) {
+    const SetupCall& c = rec.calls[j];
+    switch (c.kind) {
+      case SK_INGEST: {
+        const IngestArgs& a = c.ingest;
+        launch_ingest_cloud(a.x, a.y, a.z, a.n, a.n_pad, a.pad, a.d1, a.cap1, a.d2, a.cap2, s);
+        break;
+      }
+      case SK_LOOP_INIT: launch_loop_init(c.loop_init, s); break;
+      case SK_BOUNDS: launch_grid_bounds(c.bounds.x, c.bounds.y, c.bounds.z, c.bounds.n, c.bounds.fb, s); break;
+      case SK_INFO: launch_grid_info(c.info.fb, c.info.n, c.info.ppc, c.info.xdiv, c.info.max_cells, c.info.g, s); break;
+      case SK_QSLOT: {
+        const QslotArgs& a = c.qslot;
+        launch_grid_qslot(a.x, a.y, a.z, a.n, a.gi, a.count, a.cell, a.slot, a.coarse, s);
+        break;
+      }
+      case SK_SCAN: launch_grid_scan(c.scan.count, c.scan.out, c.scan.bsum, c.scan.g, c.scan.coarse, s); break;
+      case SK_TSCATTER: {
+        const TscatterArgs& a = c.tscatter;
+        launch_grid_tscatter(a.x, a.y, a.z, a.tcell, a.tslot, a.cell_start, a.n, a.t4, a.o4, s);
+        break;
+      }
+      case SK_QSCATTER: {
+        const QscatterArgs& a = c.qscatter;
+        launch_grid_qscatter(a.qcell, a.qslot, a.qstart, a.n, a.qperm, a.qx, a.qy, a.qz, a.ox, a.oy, a.oz, a.qm4, a.sp,
+                             a.seed_m, s);
+        break;
+      }
+      default: break;
+    }
+  }
+  setup_recorder() = saved;
+}
+}  // namespace icpk
+
+// icpk_reduce / icpk_reduce_p2l: K2 / K5 over the current associations, sums and pair count back to the host
+static int reduce_to_host(icpk_ctx* ctx, float max_dist, double* sums, int64_t* count, bool p2l) {
+  if (!ctx || !sums) return ICPK_E_ARG;
+  if (!ctx->have_assoc) return fail(ctx, ICPK_E_NOT_SET, "no nearest-neighbour sweep has run");
+  if (p2l && !ctx->have_normals) return fail(ctx, ICPK_E_NOT_SET, "no target normals");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  if (int ru = ensure_unpacked(ctx)) return ru;
+  const int nsum = p2l ? NP2L : NSUM;
+  if (ctx->src.n == 0) {
+    std::memset(sums, 0, nsum * sizeof(double));
+    if (count) *count = 0;
+    return ICPK_OK;
+  }
+  int rc = p2l ? enqueue_reduce_p2l(ctx, max_dist) : enqueue_reduce(ctx, max_dist);
+  if (rc) return rc;
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(sums, ctx->red_host, nsum * sizeof(double));
+  if (count) std::memcpy(count, ctx->red_host + nsum, sizeof(int64_t));
+  return ICPK_OK;
+}
+
+extern "C" {
+
+int icpk_get_associations(icpk_ctx* ctx, int32_t* idx_out, float* dist_out) {
+  if (!ctx) return ICPK_E_ARG;
+  if (!ctx->have_assoc) return fail(ctx, ICPK_E_NOT_SET, "no nearest-neighbour sweep has run");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const int nq = ctx->src.n;
+  if (int ru = ensure_unpacked(ctx)) return ru;  // (after a device loop of grid sweeps; a frame-batch slot after its lock-step loop)
+  if (nq > 0) {
+    // K2 unpacks (distance, index) keys into the idx/dist planes
+    int rc = enqueue_reduce(ctx, __builtin_inff());
+    if (rc) return rc;
+    if (idx_out)
+      ICPK_HIP(ctx, hipMemcpyAsync(idx_out, ctx->idx, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (dist_out)
+      ICPK_HIP(ctx, hipMemcpyAsync(dist_out, ctx->dist, (size_t)nq * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_nn(icpk_ctx* ctx, int32_t nn_mode, int32_t* idx_out, float* dist_out) {
+  int rc = check_ready(ctx);
+  if (rc) return rc;
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  if (int ru = ensure_unpacked(ctx)) return ru;
+  rc = enqueue_nn(ctx, nn_mode);
+  if (rc) return rc;
+  if (idx_out || dist_out) return icpk_get_associations(ctx, idx_out, dist_out);
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_reduce(icpk_ctx* ctx, float max_dist, double* sums, int64_t* count) {
+  return reduce_to_host(ctx, max_dist, sums, count, false);
+}
+
+int icpk_reduce_p2l(icpk_ctx* ctx, float max_dist, double* sums, int64_t* count) {
+  return reduce_to_host(ctx, max_dist, sums, count, true);
+}
+
+}  // extern "C"

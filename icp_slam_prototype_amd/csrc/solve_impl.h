@@ -1,7 +1,7 @@
 // solve_impl.h -- the O(1) dense algebra of the ICP step (what the reference delegates
 // to OpenCV: cv::SVD, cv::determinant, Mat::inv, 3x3 GEMM) and its small pose helpers,
 // float64 internally.  Header-inline and __host__ __device__: the same source runs in
-// the host loop (icpk_api.cpp) and in the device-side loop (kernels_loop.hip), compiled
+// the host loop (icpk_align.cpp) and in the device-side loop (kernels_loop.hip), compiled
 // with -ffp-contract=off on both sides so the two agree bit for bit wherever the
 // hardware's +,-,*,/ and sqrt are correctly rounded.
 #pragma once
