@@ -148,6 +148,23 @@ def build_fake_rccl(force=False):
     return FAKE_RCCL
 
 
+SOLVE_PROBE = os.path.join(LIBDIR, "libsolve_probe.so")
+
+
+def build_solve_probe(force=False):
+    """TEST INFRASTRUCTURE: tests/cpp/solve_probe.hip (csrc/solve_impl.h run over arrays of cases on the device and
+    on the host), loaded by tests/test_gpu_solve_device.py and tests/test_solve_probe_host.py only.  Compiled with
+    exactly FLAGS, so its device and host code are generated as they are for libicpk.so."""
+    src = os.path.join(ROOT, "tests", "cpp", "solve_probe.hip")
+    os.makedirs(LIBDIR, exist_ok=True)
+    newest = max(os.path.getmtime(p) for p in (src, os.path.join(CSRC, "solve_impl.h"), os.path.abspath(__file__)))
+    if not force and os.path.exists(SOLVE_PROBE) and os.path.getmtime(SOLVE_PROBE) >= newest:
+        return SOLVE_PROBE
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc] + FLAGS + ["-shared", "-x", "hip", src, "-o", SOLVE_PROBE])
+    return SOLVE_PROBE
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_cpp_test(force="--force" in sys.argv))

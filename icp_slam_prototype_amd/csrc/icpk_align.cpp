@@ -348,6 +348,7 @@ int icpk_align_query_sharded(icpk_ctx* ctx, const icpk_params* p, float T_out[16
   if (p->solve != ICPK_SOLVE_REFERENCE && p->solve != ICPK_SOLVE_KABSCH)
     return fail(ctx, ICPK_E_ARG, "the query-sharded loop supports the reference and Kabsch flavours");
   if (p->max_iterations < 0 || p->max_iterations > LOOP_MAX_ITER) return fail(ctx, ICPK_E_ARG, "max_iterations out of range");
+  if (p->min_pairs < 1) return fail(ctx, ICPK_E_ARG, "min_pairs must be >= 1");
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   reset_outputs(T_out, stats);
   icpk_params q = *p;
@@ -391,6 +392,8 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
   if (!ctx || !p || !T_out) return ICPK_E_ARG;
   if (p->max_iterations < 0 || p->solve < ICPK_SOLVE_REFERENCE || p->solve > ICPK_SOLVE_POINT_TO_PLANE)
     return fail(ctx, ICPK_E_ARG, "bad params");
+  // min_pairs < 1 would let a sweep with no pairs reach the solve, which divides by the zero count (a NaN transform)
+  if (p->min_pairs < 1) return fail(ctx, ICPK_E_ARG, "min_pairs must be >= 1");
   if (p->solve == ICPK_SOLVE_POINT_TO_PLANE && ctx && !ctx->have_normals)
     return fail(ctx, ICPK_E_NOT_SET, "point-to-plane needs target normals");
   if (p->nn_mode == ICPK_NN_MAP && (p->solve == ICPK_SOLVE_POINT_TO_PLANE || !(p->max_nn_dist <= ICPK_MAX_NN_DISTANCE)))

@@ -31,7 +31,7 @@ struct GroupRun {
 bool batch_eligible(const icpk_ctx* ctx, const icpk_params* p) {
   return p->nn_mode == ICPK_NN_GRID && !p->host_loop && !ctx->log_fn && p->profile <= 1 &&
          (p->solve == ICPK_SOLVE_REFERENCE || p->solve == ICPK_SOLVE_KABSCH) && p->max_iterations >= 0 &&
-         p->max_iterations <= LOOP_MAX_ITER;
+         p->max_iterations <= LOOP_MAX_ITER && p->min_pairs >= 1;
 }
 
 int ensure_slots(icpk_ctx* ctx, int n) {
@@ -228,6 +228,7 @@ int align_batch_impl(icpk_ctx* ctx, int32_t n_pairs, const icpk_pair* pairs, con
   if (!ctx || n_pairs < 0 || (n_pairs > 0 && (!pairs || !T_out)) || !p) return ICPK_E_ARG;
   if (p->max_iterations < 0 || p->solve < ICPK_SOLVE_REFERENCE || p->solve > ICPK_SOLVE_POINT_TO_PLANE)
     return fail(ctx, ICPK_E_ARG, "bad params");
+  if (p->min_pairs < 1) return fail(ctx, ICPK_E_ARG, "min_pairs must be >= 1");
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   int worst = ICPK_OK;
   auto note = [&](int rc) {

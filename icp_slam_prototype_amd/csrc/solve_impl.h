@@ -5,16 +5,18 @@
 // with -ffp-contract=off on both sides so the two agree bit for bit wherever the
 // hardware's +,-,*,/ and sqrt are correctly rounded.
 #pragma once
-#include <cmath>
-#include <cstdint>
-#include <cstring>
-
+// hip_runtime.h first: it makes the <cstring> / <cmath> functions used below (std::memcpy,
+// std::sqrt, ...) callable from device code, so this header compiles on its own in a HIP
+// translation unit
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define ICPK_HD __host__ __device__ inline
 #else
 #define ICPK_HD inline
 #endif
+#include <cmath>
+#include <cstdint>
+#include <cstring>
 
 namespace icpk {
 

@@ -100,7 +100,7 @@ typedef struct icpk_params {
   int32_t max_iterations;   /* SLAM.cpp:277 (16)                                  */
   float threshold;          /* SLAM.cpp:277 (1e-4): loop while mse > threshold    */
   float max_nn_dist;        /* icp.hpp:8 (0.75) or icp.hpp:10 (0.1)               */
-  int32_t min_pairs;        /* icp.cpp:163 (3)                                    */
+  int32_t min_pairs;        /* icp.cpp:163 (3); < 1: ICPK_E_ARG                   */
   int32_t solve;            /* ICPK_SOLVE_*                                       */
   int32_t fixed_iterations; /* 1: ignore threshold, run max_iterations (bench)    */
   int32_t nn_mode;          /* ICPK_NN_*                                          */
