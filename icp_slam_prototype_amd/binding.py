@@ -348,11 +348,13 @@ class Context:
             raise IcpkError(rc, "icpk_create failed (no usable HIP device: there is no CPU fallback)")
         self._h = h
         self._log_ref = None
+        self._pinned = {}  # register_host_buffer: address -> the array, alive while the library may read it
 
     def close(self):
         if getattr(self, "_h", None):
             self._lib.icpk_destroy(self._h)
             self._h = None
+            self._pinned.clear()
 
     def __del__(self):
         try:
@@ -474,13 +476,16 @@ class Context:
 
     def register_host_buffer(self, arr):
         """Pins a C-contiguous numpy array for the device (icpk_register_host_buffer): depth images that lie inside it
-        are read by icpk_backproject_pair where they are.  Keep the array alive until unregister_host_buffer / close."""
+        are read by icpk_backproject_pair where they are.  The Context holds the array until unregister_host_buffer /
+        close."""
         if not arr.flags["C_CONTIGUOUS"]:
             raise ValueError("a C-contiguous array expected")
         self._chk(self._lib.icpk_register_host_buffer(self._h, arr.ctypes.data, arr.nbytes))
+        self._pinned[arr.ctypes.data] = arr
 
     def unregister_host_buffer(self, arr):
         self._chk(self._lib.icpk_unregister_host_buffer(self._h, arr.ctypes.data))
+        self._pinned.pop(arr.ctypes.data, None)
 
     def set_subsample(self, factor=40, seed=0):
         """pointcloud.cpp:27-30 with a reproducible choice: every back-projection keeps one valid pixel in `factor`

@@ -5,6 +5,7 @@
 // sends the next 3x4 transform as kernel arguments.
 #include <chrono>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "icpk_ctx.h"
@@ -187,11 +188,8 @@ int device_loop_finish(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icp
   // the associations of the last EXECUTED sweep are the result
   const int k = h->sweeps;
   if (k >= 1 && k <= (int)ctx->best_of_sweep.size()) {
-    nn_key_t* fin = ctx->best_of_sweep[k - 1];
-    if (fin != ctx->best) {
-      ctx->seed = ctx->best;
-      ctx->best = fin;
-    }
+    // (every sweep wrote one of the two buffers that trade places as best / seed)
+    if (ctx->best_of_sweep[k - 1] != ctx->best) std::swap(ctx->seed, ctx->best);
   }
   ctx->have_seed_m = false;  // the Morton-ordered copy may belong to a skipped sweep: re-gather on demand
   const int it = h->iterations;

@@ -23,15 +23,8 @@ int upload_cloud(icpk_ctx* ctx, Cloud& c, const float* x, const float* y, const 
     // frame-batch slots: pageable host memory crosses PCIe through a staging copy inside the
     // runtime, one plane after the other and synchronously; copying into the slot's own pinned
     // buffer here (the set-up threads do it in parallel) leaves ONE truly asynchronous DMA per cloud
-    float*& stage = (&c == &ctx->tgt) ? ctx->stage_t : ctx->stage_s;
-    int& cap = (&c == &ctx->tgt) ? ctx->stage_t_cap : ctx->stage_s_cap;
-    if (c.cap > cap) {
-      if (stage) ICPK_HIP(ctx, hipHostFree(stage));
-      stage = nullptr;
-      cap = 0;
-      ICPK_HIP(ctx, hipHostMalloc((void**)&stage, (size_t)3 * c.cap * sizeof(float), hipHostMallocDefault));
-      cap = c.cap;
-    }
+    PinnedBuf<float>& stage = (&c == &ctx->tgt) ? ctx->stage_t : ctx->stage_s;
+    if ((rc = stage.reserve(ctx, (size_t)3 * c.cap))) return rc;
     std::memcpy(stage, x, (size_t)n * sizeof(float));
     std::memcpy(stage + c.cap, y, (size_t)n * sizeof(float));
     std::memcpy(stage + 2 * (size_t)c.cap, z, (size_t)n * sizeof(float));
@@ -124,16 +117,18 @@ icpk_ctx* make_context(int device_id, const icpk_ctx* parent) {
   icpk_ctx* ctx = new icpk_ctx();
   ctx->device = device_id;
   bool ok = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipMalloc((void**)&ctx->partial, (size_t)RED_MAX_BLOCKS * NSUM_MAX * sizeof(double)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&ctx->pcount, (size_t)RED_MAX_BLOCKS * sizeof(int)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&ctx->red_out, (NSUM_MAX + 1) * sizeof(double)) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&ctx->red_host, (NSUM_MAX + 1) * sizeof(double), hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&ctx->bp_n_host, 2 * sizeof(int), hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipMalloc((void**)&ctx->st_dev, sizeof(LoopState)) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&ctx->st_host, sizeof(LoopState), hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&ctx->progress, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+  ok = ok && ctx->partial.reserve(ctx, (size_t)RED_MAX_BLOCKS * NSUM_MAX) == ICPK_OK;
+  ok = ok && ctx->pcount.reserve(ctx, RED_MAX_BLOCKS) == ICPK_OK;
+  ok = ok && ctx->red_out.reserve(ctx, NSUM_MAX + 1) == ICPK_OK;
+  ok = ok && ctx->red_host.reserve(ctx, NSUM_MAX + 1) == ICPK_OK;
+  ok = ok && ctx->bp_n_host.reserve(ctx, 2) == ICPK_OK;
+  ok = ok && ctx->st_dev_mem.reserve(ctx, 1) == ICPK_OK;
+  ok = ok && ctx->st_host_mem.reserve(ctx, 1) == ICPK_OK;
+  ctx->st_dev = ctx->st_dev_mem;
+  ctx->st_host = ctx->st_host_mem;
+  ok = ok && ctx->progress.reserve(ctx, 64 / sizeof(int)) == ICPK_OK;
   ok = ok && hipHostGetDevicePointer((void**)&ctx->progress_dev, ctx->progress, 0) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&ctx->st_mirror, sizeof(LoopState), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+  ok = ok && ctx->st_mirror.reserve(ctx, 1) == ICPK_OK;
   ok = ok && hipHostGetDevicePointer((void**)&ctx->st_mirror_dev, ctx->st_mirror, 0) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->ready_ev, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->group_ev[0], hipEventDisableTiming) == hipSuccess;
@@ -276,7 +271,7 @@ void icpk_destroy(icpk_ctx* ctx) {
   icpk_comm_release(ctx);
   icpk_map_free(ctx);
   icpk_fast_free(ctx);
-  for (icpk_ctx* sl : ctx->slots) icpk_destroy(sl);
+  for (icpk_ctx* sl : ctx->slots) icpk_destroy(sl);  // (before the pools their loop states point into)
   ctx->slots.clear();
   for (hipStream_t st : {ctx->setup_stream[0], ctx->setup_stream[1]})
     if (st) (void)hipStreamDestroy(st);
@@ -284,28 +279,10 @@ void icpk_destroy(icpk_ctx* ctx) {
                        ctx->batch_t0[1], ctx->batch_t1[0], ctx->batch_t1[1]})
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->events) (void)hipEventDestroy(e);
-  void* dev[] = {ctx->qcount, ctx->qstart, ctx->scan_bsum, ctx->qcount2, ctx->scan_bsum2, ctx->sort_vals2, ctx->qm4, ctx->sp_in, ctx->sp_out, ctx->rec, ctx->grid_info, ctx->grid_bounds, ctx->cell_start, ctx->t4, ctx->o4, ctx->best_m, ctx->seed_m, ctx->st_pooled ? nullptr : (void*)ctx->st_dev, ctx->sorted.base, ctx->tkeys, ctx->tperm, ctx->qperm, ctx->bounds, ctx->sort_keys, ctx->sort_vals, ctx->morton_table,
-                 ctx->nrm.base, ctx->boxes, ctx->dec.base, ctx->tgt.base, ctx->src0.base, ctx->src.base, ctx->best,      ctx->seed,     ctx->idx,
-                 ctx->dist,     ctx->partial,   ctx->pcount,   ctx->red_out,   ctx->depth_dev, ctx->depth_flt, ctx->ks_buf, ctx->bp_counts};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  if (ctx->red_host) (void)hipHostFree(ctx->red_host);
-  if (ctx->stage_t) (void)hipHostFree(ctx->stage_t);
-  if (ctx->stage_s) (void)hipHostFree(ctx->stage_s);
-  if (ctx->bp_n_host) (void)hipHostFree(ctx->bp_n_host);
-  if (ctx->st_host && !ctx->st_pooled) (void)hipHostFree(ctx->st_host);
-  if (ctx->slot_states) (void)hipFree(ctx->slot_states);
-  if (ctx->slot_states_host) (void)hipHostFree(ctx->slot_states_host);
-  if (ctx->progress) (void)hipHostFree(ctx->progress);
-  if (ctx->st_mirror) (void)hipHostFree(ctx->st_mirror);
-  if (ctx->grid_ticket) (void)hipFree(ctx->grid_ticket);
-  if (ctx->stage_depth) (void)hipHostFree(ctx->stage_depth);
   for (const icpk_ctx::HostRange& r : ctx->registered) (void)hipHostUnregister(const_cast<char*>(r.host));
   ctx->registered.clear();
-  if (ctx->pix_tidx) (void)hipFree(ctx->pix_tidx);
-  if (ctx->pix_src) (void)hipFree(ctx->pix_src);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;  // (its buffers free themselves)
 }
 
 const char* icpk_last_error(const icpk_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -451,18 +428,16 @@ static int pair_distance_impl(icpk_ctx* ctx, const float* a, const float* b, flo
   if (!ctx || n < 0 || (n > 0 && (!a || !b || !out))) return ICPK_E_ARG;
   if (n == 0) return ICPK_OK;
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
-  float *da = nullptr, *db = nullptr, *dout = nullptr;
-  ICPK_HIP(ctx, hipMalloc((void**)&da, (size_t)3 * n * sizeof(float)));
-  ICPK_HIP(ctx, hipMalloc((void**)&db, (size_t)3 * n * sizeof(float)));
-  ICPK_HIP(ctx, hipMalloc((void**)&dout, (size_t)n * sizeof(float)));
+  DevBuf<float> da, db, dout;  // (freed on every return)
+  int rc = da.reserve(ctx, (size_t)3 * n);
+  if (!rc) rc = db.reserve(ctx, (size_t)3 * n);
+  if (!rc) rc = dout.reserve(ctx, n);
+  if (rc) return rc;
   ICPK_HIP(ctx, hipMemcpyAsync(da, a, (size_t)3 * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   ICPK_HIP(ctx, hipMemcpyAsync(db, b, (size_t)3 * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   launch_pair_distance(da, db, dout, n, point3, ctx->stream);
   ICPK_HIP(ctx, hipMemcpyAsync(out, dout, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  (void)hipFree(da);
-  (void)hipFree(db);
-  (void)hipFree(dout);
   return ICPK_OK;
 }
 

@@ -36,20 +36,18 @@ bool batch_eligible(const icpk_ctx* ctx, const icpk_params* p) {
 
 int ensure_slots(icpk_ctx* ctx, int n) {
   if (n > 2 * BATCH_MAX) return fail(ctx, ICPK_E_ARG, "too many frame-batch slots");
-  if (!ctx->slot_states) {
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->slot_states, (size_t)2 * BATCH_MAX * sizeof(LoopState)));
-    ICPK_HIP(ctx, hipHostMalloc((void**)&ctx->slot_states_host, (size_t)2 * BATCH_MAX * sizeof(LoopState), hipHostMallocDefault));
-  }
+  int rc = ctx->slot_states.reserve(ctx, 2 * BATCH_MAX);
+  if (!rc) rc = ctx->slot_states_host.reserve(ctx, 2 * BATCH_MAX);
+  if (rc) return rc;
   while ((int)ctx->slots.size() < n) {
     icpk_ctx* sl = make_context(ctx->device, ctx);
     if (!sl) return fail(ctx, ICPK_E_HIP, "frame-batch slot allocation failed");
-    // the slot's loop state lives in the parent's pools (one copy brings a whole group's states back)
+    // the slot's loop state lives in the parent's pools (one copy brings a whole group's states back): its own goes
     const size_t k = ctx->slots.size();
-    (void)hipFree(sl->st_dev);
-    (void)hipHostFree(sl->st_host);
+    (void)sl->st_dev_mem.release();
+    (void)sl->st_host_mem.release();
     sl->st_dev = ctx->slot_states + k;
     sl->st_host = ctx->slot_states_host + k;
-    sl->st_pooled = true;
     ctx->slots.push_back(sl);
   }
   return ICPK_OK;

@@ -88,9 +88,8 @@ RcclApi* rccl() {
 struct icpk_comm_state {
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1;
-  void* dev = nullptr;   // device staging (send | recv)
-  size_t dev_bytes = 0;
-  void* host = nullptr;  // pinned staging of the same size
+  DevBuf<char> dev;      // device staging (send | recv) ...
+  PinnedBuf<char> host;  // ... and its pinned twin: they grow together
 };
 
 namespace {
@@ -112,15 +111,7 @@ int need_comm(icpk_ctx* ctx) {
 
 int ensure_staging(icpk_ctx* ctx, size_t bytes) {
   icpk_comm_state* c = ctx->comm;
-  if (bytes <= c->dev_bytes) return ICPK_OK;
-  if (c->dev) ICPK_HIP(ctx, hipFree(c->dev));
-  if (c->host) ICPK_HIP(ctx, hipHostFree(c->host));
-  c->dev = c->host = nullptr;
-  c->dev_bytes = 0;
-  ICPK_HIP(ctx, hipMalloc(&c->dev, bytes));
-  ICPK_HIP(ctx, hipHostMalloc(&c->host, bytes, hipHostMallocDefault));
-  c->dev_bytes = bytes;
-  return ICPK_OK;
+  return reserve_group(ctx, nullptr, need(c->dev, bytes), need(c->host, bytes));
 }
 
 // block-wise shard of n items over `world` ranks (the same rule as batch.partition)
@@ -145,9 +136,7 @@ void icpk_comm_release(icpk_ctx* ctx) {
   if (!ctx || !ctx->comm) return;
   icpk_comm_state* c = ctx->comm;
   if (c->comm && rccl()) (void)rccl()->CommDestroy(c->comm);
-  if (c->dev) (void)hipFree(c->dev);
-  if (c->host) (void)hipHostFree(c->host);
-  delete c;
+  delete c;  // (and its staging)
   ctx->comm = nullptr;
 }
 
@@ -214,7 +203,7 @@ int icpk_comm_broadcast_target(icpk_ctx* ctx, int root) {
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   rc = ensure_staging(ctx, 64);
   if (rc) return rc;
-  int32_t* hn = static_cast<int32_t*>(c->host);
+  int32_t* hn = reinterpret_cast<int32_t*>(c->host.get());
   *hn = c->rank == root ? ctx->tgt.n : 0;
   ICPK_HIP(ctx, hipMemcpyAsync(c->dev, hn, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   ICPK_RCCL(ctx, api->Broadcast(c->dev, c->dev, 1, ncclInt32, root, c->comm, ctx->stream));
@@ -226,7 +215,7 @@ int icpk_comm_broadcast_target(icpk_ctx* ctx, int root) {
   // broadcasts: a rank that could not allocate must not leave the others waiting inside ncclBroadcast.
   int alloc_rc = ICPK_OK;
   if (c->rank != root) alloc_rc = ensure_cloud(ctx, ctx->tgt, n);
-  double* hf = static_cast<double*>(c->host);  // (float64 sum: the one all-reduce flavour this layer uses anywhere)
+  double* hf = reinterpret_cast<double*>(c->host.get());  // (float64 sum: the one all-reduce flavour this layer uses anywhere)
   *hf = alloc_rc == ICPK_OK ? 0.0 : 1.0;
   ICPK_HIP(ctx, hipMemcpyAsync(c->dev, hf, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   ICPK_RCCL(ctx, api->AllReduce(c->dev, c->dev, 1, ncclFloat64, ncclSum, c->comm, ctx->stream));
@@ -269,9 +258,9 @@ int icpk_comm_gather_results(icpk_ctx* ctx, const float* T_local, const icpk_sta
   const size_t row = 20, send = (size_t)bmax * row, recv = send * c->world;
   rc = ensure_staging(ctx, (send + recv) * sizeof(float));
   if (rc) return rc;
-  float* hs = static_cast<float*>(c->host);
+  float* hs = reinterpret_cast<float*>(c->host.get());
   float* hr = hs + send;
-  float* ds = static_cast<float*>(c->dev);
+  float* ds = reinterpret_cast<float*>(c->dev.get());
   float* dr = ds + send;
   std::memset(hs, 0, send * sizeof(float));
   for (int k = 0; k < n_local; ++k) {
@@ -308,7 +297,7 @@ int icpk_comm_allreduce_sums(icpk_ctx* ctx, double* sums, int32_t n, int64_t* co
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   rc = ensure_staging(ctx, (size_t)(n + 1) * sizeof(double));
   if (rc) return rc;
-  double* h = static_cast<double*>(c->host);
+  double* h = reinterpret_cast<double*>(c->host.get());
   std::memcpy(h, sums, (size_t)n * sizeof(double));
   h[n] = count ? (double)*count : 0.0;  // exact below 2^53
   ICPK_HIP(ctx, hipMemcpyAsync(c->dev, h, (size_t)(n + 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));

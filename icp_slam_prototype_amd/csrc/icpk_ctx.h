@@ -13,10 +13,109 @@
 #include "icpk.h"
 #include "icpk_internal.h"
 
+struct icpk_ctx;
+
 namespace icpk {
 
+inline int hip_failure(icpk_ctx* ctx, const char* what, hipError_t e);  // ctx->err = what: <HIP's message>; ICPK_E_HIP
+
+struct DeviceMem {
+  static constexpr const char* name = "hipMalloc";
+  static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  static hipError_t free(void* p) { return hipFree(p); }
+};
+template <unsigned Flags>
+struct PinnedMem {  // hipHostMalloc with these flags
+  static constexpr const char* name = "hipHostMalloc";
+  static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, Flags); }
+  static hipError_t free(void* p) { return hipHostFree(p); }
+};
+
+// The one owner of a device or pinned allocation: a pointer and its capacity in elements.  reserve() grows it (the
+// contents are lost: the old memory is freed before the new is allocated); the destructor frees it.  After a failed
+// reserve the buffer is empty with capacity 0, so that the next call allocates again.  Movable, not copyable; it
+// converts to T* so that it is handed to the launchers as the raw pointer.
+template <class T, class Mem>
+class Buf {
+ public:
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  Buf(Buf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr, o.cap_ = 0; }
+  Buf& operator=(Buf&& o) noexcept {
+    if (this != &o) {
+      (void)release();
+      p_ = o.p_, cap_ = o.cap_;
+      o.p_ = nullptr, o.cap_ = 0;
+    }
+    return *this;
+  }
+  ~Buf() { (void)release(); }
+
+  operator T*() const { return p_; }
+  T* get() const { return p_; }
+  size_t capacity() const { return cap_; }
+
+  // room for n elements: nothing happens while n <= capacity().  *grown (optional) is set when the old memory was
+  // given up, whether or not the new allocation succeeded.
+  int reserve(icpk_ctx* ctx, size_t n, bool* grown = nullptr) {
+    if (n <= cap_) return ICPK_OK;
+    if (grown) *grown = true;
+    hipError_t e = release();
+    if (e == hipSuccess) e = Mem::alloc(reinterpret_cast<void**>(&p_), n * sizeof(T));
+    if (e != hipSuccess) {
+      p_ = nullptr;
+      return hip_failure(ctx, Mem::name, e);
+    }
+    cap_ = n;
+    return ICPK_OK;
+  }
+  // frees the memory; the buffer is empty whatever HIP says
+  hipError_t release() {
+    const hipError_t e = p_ ? Mem::free(p_) : hipSuccess;
+    p_ = nullptr;
+    cap_ = 0;
+    return e;
+  }
+
+ private:
+  T* p_ = nullptr;
+  size_t cap_ = 0;
+};
+
+template <class T>
+using DevBuf = Buf<T, DeviceMem>;
+template <class T, unsigned Flags = hipHostMallocDefault>
+using PinnedBuf = Buf<T, PinnedMem<Flags>>;
+template <class T>
+using MappedBuf = PinnedBuf<T, hipHostMallocMapped>;  // pinned, and read by the device where it lies
+template <class T>
+using CoherentBuf = PinnedBuf<T, hipHostMallocMapped | hipHostMallocCoherent>;  // words the host and the device both watch
+
+template <class B>
+struct Need {
+  B& buf;
+  size_t n;
+};
+template <class B>
+Need<B> need(B& buf, size_t n) { return {buf, n}; }
+
+// Buffers that grow together: when any member is short, EVERY member is freed before any is allocated again (the peak
+// is the new set alone, as it was the old set alone).  *grown as for Buf::reserve.
+template <class... B>
+int reserve_group(icpk_ctx* ctx, bool* grown, Need<B>... m) {
+  if (((m.n <= m.buf.capacity()) && ...)) return ICPK_OK;
+  if (grown) *grown = true;
+  hipError_t e = hipSuccess;
+  for (const hipError_t r : {m.buf.release()...})
+    if (e == hipSuccess) e = r;
+  int rc = e == hipSuccess ? ICPK_OK : hip_failure(ctx, "hipFree", e);
+  ((rc = rc ? rc : m.buf.reserve(ctx, m.n)), ...);
+  return rc;
+}
+
 struct Cloud {
-  float* base = nullptr;
+  DevBuf<float> base;
   int n = 0;
   int cap = 0;  // floats per plane, multiple of NN_TILE
   float* x() const { return base; }
@@ -68,44 +167,41 @@ struct icpk_ctx {
   bool have_tgt = false, have_src = false, have_assoc = false;
   bool have_dec = false;   // dec matches tgt
   bool have_boxes = false; // boxes match tgt
-  float* boxes = nullptr;  // [6][tbox_stride] tile boxes then [6][sbox_stride] sub-tile boxes
+  icpk::DevBuf<float> boxes;  // [6][tbox_stride] tile boxes then [6][sbox_stride] sub-tile boxes
   int boxes_tiles_cap = 0;
   // pruned scan: Morton-ordered copy of the target, its permutation, the query order
   icpk::Cloud sorted;
-  int* tperm = nullptr;
-  unsigned* tkeys = nullptr;  // sorted Morton codes of the target (first-sweep seeding)
-  int tperm_cap = 0;
-  int* qperm = nullptr;
-  int qperm_cap = 0;
+  icpk::DevBuf<int> tperm;
+  icpk::DevBuf<unsigned> tkeys;    // sorted Morton codes of the target (first-sweep seeding)
+  icpk::DevBuf<int> qperm;
   bool have_qperm = false;
-  float* bounds = nullptr;  // 6 floats: lo xyz, hi xyz of the target
-  unsigned* sort_keys = nullptr;  // 2 x sort_cap
-  int* sort_vals = nullptr;       // sort_cap
+  icpk::DevBuf<float> bounds;      // 6 floats: lo xyz, hi xyz of the target
+  icpk::DevBuf<unsigned> sort_keys;  // 2 x sort_cap
+  icpk::DevBuf<int> sort_vals;       // sort_cap
   int sort_cap = 0;
-  icpk::GridInfo* morton_table = nullptr;  // device: the table size of the Morton counting sort (pruned scan), for launch_grid_scan
+  icpk::DevBuf<GridInfo> morton_table;  // the table size of the Morton counting sort (pruned scan), for launch_grid_scan
   bool have_seed = false;  // `best` holds matches of a previous sweep of the same clouds
-  nn_key_t* best = nullptr;
-  nn_key_t* seed = nullptr;
-  nn_key_t* best_m = nullptr;  // pruned scan: results / seeds in query Morton order
-  nn_key_t* seed_m = nullptr;
+  icpk::DevBuf<nn_key_t> best, seed;  // the association set (ensure_assoc): these six grow together
+  icpk::DevBuf<nn_key_t> best_m, seed_m;  // pruned scan: results / seeds in query Morton order
   bool have_seed_m = false;    // best_m holds the matches of the previous sweep under the current qperm
-  int32_t* idx = nullptr;
-  float* dist = nullptr;
-  int assoc_cap = 0;
-  double* partial = nullptr;
-  int* pcount = nullptr;
-  double* red_out = nullptr;   // device, 20 x 8 bytes
-  double* red_host = nullptr;  // pinned, 20 x 8 bytes
-  LoopState* st_dev = nullptr;   // device-side loop state
-  LoopState* st_host = nullptr;  // pinned staging copy
-  int* progress = nullptr;       // pinned, mapped: LoopState::progress of a throttled loop (see there)
-  int* progress_dev = nullptr;   // the same words as the device addresses them
-  int loop_epoch = 0;            // tag of the current throttled loop in the progress words
-  LoopState* st_mirror = nullptr;      // pinned + mapped: the loop's outputs as the device writes them at its end (LoopState::mirror)
-  LoopState* st_mirror_dev = nullptr;  // the same memory as the device addresses it
+  icpk::DevBuf<int32_t> idx;
+  icpk::DevBuf<float> dist;
+  icpk::DevBuf<double> partial;
+  icpk::DevBuf<int> pcount;
+  icpk::DevBuf<double> red_out;      // 20 x 8 bytes
+  icpk::PinnedBuf<double> red_host;  // 20 x 8 bytes
+  icpk::DevBuf<LoopState> st_dev_mem;      // this context's own loop state (released by a frame-batch slot) ...
+  icpk::PinnedBuf<LoopState> st_host_mem;  // ... and its staging copy
+  LoopState* st_dev = nullptr;   // views, not owners: the device-side loop state (st_dev_mem, or a slot's place in
+  LoopState* st_host = nullptr;  //   the parent's slot_states) and its staging copy (st_host_mem, or slot_states_host)
+  icpk::CoherentBuf<int> progress;  // LoopState::progress of a throttled loop (see there)
+  int* progress_dev = nullptr;    // view: the same words as the device addresses them
+  int loop_epoch = 0;             // tag of the current throttled loop in the progress words
+  icpk::CoherentBuf<LoopState> st_mirror;  // the loop's outputs as the device writes them at its end (LoopState::mirror)
+  LoopState* st_mirror_dev = nullptr;    // view: the same memory as the device addresses it
   icpk::LoopInitArgs pending_init{};         // device_loop_begin(defer): the initial LoopState not launched yet
   bool init_pending = false;
-  int* grid_ticket = nullptr;          // grid_begin_kernel's arrival counter (zero between launches)
+  icpk::DevBuf<int> grid_ticket;       // grid_begin_kernel's arrival counter (zero between launches)
   int sub_factor = 0;                  // icpk_set_subsample: keep one valid pixel in sub_factor (<= 1: all), chosen by ...
   unsigned long long sub_seed = 0;     // ... a hash of this seed, the image's stream number and the pixel
   unsigned long long sub_stream = 0;   // images back-projected since icpk_set_subsample (every image draws a fresh pattern, as rand() would)
@@ -115,48 +211,40 @@ struct icpk_ctx {
     const char* dev;
   };
   std::vector<HostRange> registered;
-  uint16_t* stage_depth = nullptr;     // pinned: icpk_backproject_pair's images on their way to the device
-  int stage_depth_cap = 0;
-  int* pix_tidx = nullptr;             // icpk_backproject_pair: the target point of every pixel (-1: none) ...
-  int* pix_src = nullptr;              // ... and the pixel of every source point: image-space seeds of the alignment that follows
-  int pix_cap = 0;
+  icpk::PinnedBuf<uint16_t> stage_depth;  // icpk_backproject_pair's images on their way to the device
+  icpk::DevBuf<int> pix_tidx;  // icpk_backproject_pair: the target point of every pixel (-1: none) ...
+  icpk::DevBuf<int> pix_src;   // ... and the pixel of every source point: image-space seeds of the alignment that follows
   bool have_pix_seed = false;          // they describe the clouds the context holds now
   int pix_rows = 0, pix_cols = 0;
   bool src_pristine = false;     // the working source equals the committed one (see copy_src0_to_src)
   const int* stop = nullptr;     // &st_dev->done while a device loop is being enqueued, else null
   LoopState* st_active = nullptr;  // st_dev while a device loop is being enqueued, else null
-  float* stage_t = nullptr;  // pinned staging of host clouds (frame-batch slots): target, source
-  float* stage_s = nullptr;
-  int stage_t_cap = 0, stage_s_cap = 0;
-  uint16_t* depth_dev = nullptr;
-  uint16_t* depth_flt = nullptr;  // filtered depth image (icpk_filter_depth_image / icpk_backproject_filtered)
-  int32_t* ks_buf = nullptr;      // key-point association lists: assoc_q | assoc_t | assoc_d | rej_q, ks_cap entries each
-  int ks_cap = 0;
-  int depth_cap = 0;
+  icpk::PinnedBuf<float> stage_t, stage_s;  // staging of host clouds (frame-batch slots): target, source
+  icpk::DevBuf<uint16_t> depth_dev;
+  icpk::DevBuf<uint16_t> depth_flt;  // filtered depth image (icpk_filter_depth_image / icpk_backproject_filtered)
+  icpk::DevBuf<int32_t> ks_buf;  // key-point association lists: assoc_q | assoc_t | assoc_d | rej_q, a quarter of it each
   // icpk_backproject_pair keeps the current frame's image on the device (slot frame_slot of depth_dev / depth_flt, two
-  // slots of depth_cap / 2 pixels): it is the next call's `previous` (SLAM.cpp:305) and need not cross PCIe again
+  // slots of half their capacity): it is the next call's `previous` (SLAM.cpp:305) and need not cross PCIe again
   int frame_slot = -1;               // -1: no resident frame
   int frame_rows = 0, frame_cols = 0;
   int frame_filter[6] = {0, 0, 0, 0, 0, 0};  // filter settings the resident filtered copy was made with (on, max, min, morph, ax, ay)
-  int* bp_counts = nullptr;
-  int bp_counts_cap = 0;
-  int* bp_n_host = nullptr;  // pinned
+  icpk::DevBuf<int> bp_counts;
+  icpk::PinnedBuf<int> bp_n_host;
   std::vector<hipEvent_t> events;
   std::vector<float> trace_R, trace_t, trace_mse;  // per-iteration record of the last align
   std::vector<int32_t> trace_pairs;
   // grid scan (ICPK_NN_GRID): cell table + AoS copy of the target sorted by cell
-  icpk::GridInfo* grid_info = nullptr;
-  float* grid_bounds = nullptr;
-  int* cell_start = nullptr;  // grid_max_cells + 1
+  icpk::DevBuf<GridInfo> grid_info;
+  icpk::DevBuf<float> grid_bounds;
+  icpk::DevBuf<int> cell_start;  // grid_max_cells + 1
   int grid_max_cells = icpk::GRID_MAX_CELLS;  // capacity of cell_start / qcount / qstart (a frame-batch slot: GRID_MAX_CELLS_SLOT)
-  float4* t4 = nullptr;
-  float4* o4 = nullptr;      // the target in the CALLER's order as (x, y, z, 0): K2's gather of the matched point is one 16-byte load (valid while have_grid)
-  float4* qm4 = nullptr;     // queries in scan order (x, y, z, original index)
-  float4* sp_in = nullptr;   // seeds as points, scan order: read by the next grid sweep
-  float4* sp_out = nullptr;  // ... written by it
-  float4* rec = nullptr;     // device loop behind grid sweeps: caller-order records {(query, distance), (match, index)}, 2 float4 per query -- what K2 reads
+  icpk::DevBuf<float4> t4;
+  icpk::DevBuf<float4> o4;      // the target in the CALLER's order as (x, y, z, 0): K2's gather of the matched point is one 16-byte load (valid while have_grid)
+  icpk::DevBuf<float4> qm4;     // queries in scan order (x, y, z, original index)
+  icpk::DevBuf<float4> sp_in;   // seeds as points, scan order: read by the next grid sweep
+  icpk::DevBuf<float4> sp_out;  // ... written by it
+  icpk::DevBuf<float4> rec;     // device loop behind grid sweeps: caller-order records {(query, distance), (match, index)}, 2 float4 per query -- what K2 reads
   bool rec_pending = false;  // the last device loop left planes / keys to be unpacked from qm4 / rec on demand (ensure_unpacked)
-  int qm4_cap = 0;
   // frame-batch mode: child contexts (one per pair in flight; own stream for set-up work) --
   // owned by the parent, never handed out
   std::vector<icpk_ctx*> slots;
@@ -166,9 +254,8 @@ struct icpk_ctx {
   hipEvent_t setup_ev[2] = {nullptr, nullptr};       // ... and their completion
   hipEvent_t batch_t0[2] = {nullptr, nullptr}, batch_t1[2] = {nullptr, nullptr};  // parent: params.profile = 1 in the
   bool batch_timed[2] = {false, false};                                           //   frame-batch mode: one sweep per group
-  LoopState* slot_states = nullptr;       // parent: the loop states of all slots in one allocation (slot k at [k]),
-  LoopState* slot_states_host = nullptr;  //   so that a group's states come back with ONE copy; pinned mirror
-  bool st_pooled = false;                 // slot: st_dev / st_host point into the parent's pools
+  icpk::DevBuf<LoopState> slot_states;          // parent: the loop states of all slots in one allocation (slot k at [k]),
+  icpk::PinnedBuf<LoopState> slot_states_host;  //   so that a group's states come back with ONE copy; pinned mirror
   std::vector<nn_key_t*> best_of_sweep;  // device loop: which buffer each enqueued sweep wrote
   // RCCL communicator of the frame-batch / query-sharded modes (icpk_comm.cpp); null until
   // icpk_comm_init_rccl
@@ -180,21 +267,19 @@ struct icpk_ctx {
   unsigned tgt_lookup_version = 0;  // ... of this map version
   // FAST key points (icpk_fast.cpp); null until the first icpk_detect_fast / icpk_bgr_to_gray call
   struct icpk_fast_state* fast = nullptr;
-  int* qcount = nullptr;     // query counting sort by cell: counts and starts, grid_max_cells + 1 each
-  int* qstart = nullptr;
+  icpk::DevBuf<int> qcount;     // query counting sort by cell: counts and starts, grid_max_cells + 1 each
+  icpk::DevBuf<int> qstart;
   bool qcount_dirty = false; // a counting sort was cut short: clear the whole count table before the next one
-  int* scan_bsum = nullptr;  // block sums of the cell-count scans (GRID_SCAN_BLOCKS ints)
+  icpk::DevBuf<int> scan_bsum;  // block sums of the cell-count scans (GRID_SCAN_BLOCKS ints)
   // a fresh pair sorts targets and queries side by side (build_grid_and_order): second count table, block sums and slots
-  int* qcount2 = nullptr;
+  icpk::DevBuf<int> qcount2;
   bool qcount2_dirty = false;
-  int* scan_bsum2 = nullptr;
-  int* sort_vals2 = nullptr;
-  int sort_vals2_cap = 0;
+  icpk::DevBuf<int> scan_bsum2;
+  icpk::DevBuf<int> sort_vals2;
   int loop_nact = icpk::NSUM;      // device loop: sums the running alignment's step consumes (NSUM_REF or NSUM)
   int profile_phase = 0;     // alignments profiled so far (offsets the sampled launches, see profile_stride)
   int qperm_kind = 0;        // what qperm holds: 1 Morton order (pruned scan), 2 cell order (grid scan)
   bool grid_chain = false;   // device loop only: the previous sweep was a grid sweep (qm4 / sp_in current)
-  int t4_cap = 0;
   bool have_grid = false;  // grid matches tgt
   std::string err;
   icpk_log_fn log_fn = nullptr;
@@ -225,6 +310,11 @@ namespace icpk {
 inline int fail(icpk_ctx* ctx, int code, const char* msg) {
   if (ctx) ctx->err = msg;
   return code;
+}
+
+inline int hip_failure(icpk_ctx* ctx, const char* what, hipError_t e) {
+  if (ctx) ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+  return ICPK_E_HIP;
 }
 
 // The host wait on words the device writes into pinned, mapped memory: spins until done() (the wait is short), yields

@@ -19,63 +19,35 @@
 using namespace icpk;
 
 struct icpk_fast_state {
-  uint8_t* img = nullptr;  // device: the uploaded image (rows x cols x channels)
-  size_t img_cap = 0;
-  uint8_t* stage = nullptr;  // pinned: the image on its way to the device
-  size_t stage_cap = 0;
-  uint8_t* score = nullptr;  // device: rows x cols (the score of every kept pixel; grey output of icpk_bgr_to_gray)
-  size_t score_cap = 0;
-  unsigned long long* masks = nullptr;  // device: rows x tile columns
-  int* counts = nullptr;                // device: rows x tile columns, then the total
-  size_t ent_cap = 0;
-  float* kp = nullptr;  // device: the detected list, (x, y) per key point ...
-  float* resp = nullptr;  // ... and its response
-  size_t kp_cap = 0;
-  int* total_host = nullptr;  // pinned
-  uint16_t* dstage = nullptr;  // pinned, mapped: the depth image of icpk_detected_to_cloud
-  size_t dstage_cap = 0;
+  DevBuf<uint8_t> img;       // the uploaded image (rows x cols x channels)
+  PinnedBuf<uint8_t> stage;  // the image on its way to the device
+  DevBuf<uint8_t> score;     // rows x cols (the score of every kept pixel; grey output of icpk_bgr_to_gray)
+  DevBuf<unsigned long long> masks;  // rows x tile columns
+  DevBuf<int> counts;                // rows x tile columns, then the total (total_word)
+  DevBuf<float> kp;    // the detected list, (x, y) per key point ...
+  DevBuf<float> resp;  // ... and its response
+  PinnedBuf<int> total_host;
+  MappedBuf<uint16_t> dstage;  // the depth image of icpk_detected_to_cloud
   int n = -1;  // key points in the detected list (-1: no detection yet)
 };
 
 namespace {
 
-template <typename T>
-int grow_dev(icpk_ctx* ctx, T*& p, size_t& cap, size_t need) {
-  if (need <= cap) return ICPK_OK;
-  if (p) ICPK_HIP(ctx, hipFree(p));
-  p = nullptr;
-  cap = 0;
-  ICPK_HIP(ctx, hipMalloc((void**)&p, need * sizeof(T)));
-  cap = need;
-  return ICPK_OK;
-}
-
-template <typename T>
-int grow_pinned(icpk_ctx* ctx, T*& p, size_t& cap, size_t need, unsigned flags) {
-  if (need <= cap) return ICPK_OK;
-  if (p) ICPK_HIP(ctx, hipHostFree(p));
-  p = nullptr;
-  cap = 0;
-  ICPK_HIP(ctx, hipHostMalloc((void**)&p, need * sizeof(T), flags));
-  cap = need;
-  return ICPK_OK;
-}
-
 int ensure_fast(icpk_ctx* ctx) {
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
-  if (ctx->fast) return ICPK_OK;
-  ctx->fast = new icpk_fast_state();
-  ICPK_HIP(ctx, hipHostMalloc((void**)&ctx->fast->total_host, sizeof(int), hipHostMallocDefault));
-  return ICPK_OK;
+  if (!ctx->fast) ctx->fast = new icpk_fast_state();
+  return ctx->fast->total_host.reserve(ctx, 1);
 }
+
+int* total_word(const icpk_fast_state* f) { return f->counts + (f->counts.capacity() - 1); }
 
 bool bad_size(int32_t rows, int32_t cols) { return rows <= 0 || cols <= 0 || (int64_t)rows * cols > (1 << 27); }
 
 // the image into the device buffer through the pinned staging buffer
 int upload_image(icpk_ctx* ctx, const uint8_t* image, size_t bytes) {
   icpk_fast_state* f = ctx->fast;
-  int rc = grow_pinned(ctx, f->stage, f->stage_cap, bytes, hipHostMallocDefault);
-  if (!rc) rc = grow_dev(ctx, f->img, f->img_cap, bytes);
+  int rc = f->stage.reserve(ctx, bytes);
+  if (!rc) rc = f->img.reserve(ctx, bytes);
   if (rc) return rc;
   std::memcpy(f->stage, image, bytes);
   ICPK_HIP(ctx, hipMemcpyAsync(f->img, f->stage, bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -85,27 +57,12 @@ int upload_image(icpk_ctx* ctx, const uint8_t* image, size_t bytes) {
 // per-(row, tile column) masks and counts (+ the total), and a detected list with room for every pixel
 int ensure_lists(icpk_ctx* ctx, size_t ents, size_t npix) {
   icpk_fast_state* f = ctx->fast;
-  if (ents > f->ent_cap) {
-    if (f->masks) ICPK_HIP(ctx, hipFree(f->masks));
-    if (f->counts) ICPK_HIP(ctx, hipFree(f->counts));
-    f->masks = nullptr;
-    f->counts = nullptr;
-    f->ent_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&f->masks, ents * sizeof(unsigned long long)));
-    ICPK_HIP(ctx, hipMalloc((void**)&f->counts, (ents + 1) * sizeof(int)));
-    f->ent_cap = ents;
-  }
-  if (npix > f->kp_cap) {
-    if (f->kp) ICPK_HIP(ctx, hipFree(f->kp));
-    if (f->resp) ICPK_HIP(ctx, hipFree(f->resp));
-    f->kp = f->resp = nullptr;
-    f->kp_cap = 0;
-    f->n = -1;
-    ICPK_HIP(ctx, hipMalloc((void**)&f->kp, 2 * npix * sizeof(float)));
-    ICPK_HIP(ctx, hipMalloc((void**)&f->resp, npix * sizeof(float)));
-    f->kp_cap = npix;
-  }
-  return ICPK_OK;
+  int rc = reserve_group(ctx, nullptr, need(f->masks, ents), need(f->counts, ents + 1));
+  if (rc) return rc;
+  bool grown = false;
+  rc = reserve_group(ctx, &grown, need(f->kp, 2 * npix), need(f->resp, npix));
+  if (grown) f->n = -1;
+  return rc;
 }
 
 }  // namespace
@@ -115,13 +72,7 @@ void icpk_fast_free(icpk_ctx* ctx) {
   if (!f) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  void* dev[] = {f->img, f->score, f->masks, f->counts, f->kp, f->resp};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  void* host[] = {f->stage, f->total_host, f->dstage};
-  for (void* p : host)
-    if (p) (void)hipHostFree(p);
-  delete f;
+  delete f;  // (its buffers free themselves)
   ctx->fast = nullptr;
 }
 
@@ -135,7 +86,7 @@ int icpk_bgr_to_gray(icpk_ctx* ctx, const uint8_t* bgr, int32_t rows, int32_t co
   icpk_fast_state* f = ctx->fast;
   const size_t npix = (size_t)rows * cols;
   rc = upload_image(ctx, bgr, 3 * npix);
-  if (!rc) rc = grow_dev(ctx, f->score, f->score_cap, npix);
+  if (!rc) rc = f->score.reserve(ctx, npix);
   if (rc) return rc;
   launch_bgr_to_gray(f->img, (int)npix, f->score, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
@@ -164,10 +115,10 @@ int icpk_detect_fast(icpk_ctx* ctx, const uint8_t* image, int32_t rows, int32_t 
   const size_t npix = (size_t)rows * cols;
   const size_t ents = (size_t)rows * fast_tiles_x(cols);
   rc = upload_image(ctx, image, (size_t)channels * npix);
-  if (!rc) rc = grow_dev(ctx, f->score, f->score_cap, npix);
+  if (!rc) rc = f->score.reserve(ctx, npix);
   if (!rc) rc = ensure_lists(ctx, ents, npix);
   if (rc) return rc;
-  int* total = f->counts + f->ent_cap;
+  int* total = total_word(f);
   launch_fast_detect(f->img, rows, cols, channels, t, nonmax != 0, type == ICPK_FAST_TYPE_9_16 ? 16 : 12, f->masks, f->counts,
                      f->score, total, f->kp, f->resp, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
@@ -198,7 +149,7 @@ int icpk_detected_to_cloud(icpk_ctx* ctx, const uint16_t* depth, int32_t d_rows,
   const size_t npix = (size_t)d_rows * d_cols;
   // the depth image is read where it lies, in pinned host memory: only the key points' pixels cross PCIe.  The buffer
   // is free again when this call returns (the count is written after the last read).
-  int rc = grow_pinned(ctx, f->dstage, f->dstage_cap, npix, hipHostMallocMapped);
+  int rc = f->dstage.reserve(ctx, npix);
   if (!rc) rc = ensure_lists(ctx, 1, 0);  // (the count word, should the detection have had no candidate pixel)
   if (rc) return rc;
   std::memcpy(f->dstage, depth, npix * sizeof(uint16_t));
@@ -214,7 +165,7 @@ int icpk_detected_to_cloud(icpk_ctx* ctx, const uint16_t* depth, int32_t d_rows,
   if (!rc && which == 0) rc = ensure_cloud(ctx, ctx->src, n);
   if (rc) return rc;
   Cloud* c2 = which == 0 ? &ctx->src : nullptr;
-  int* n_dev = f->counts + f->ent_cap;  // (the detection's total is read from f->n: the word is free)
+  int* n_dev = total_word(f);  // (the detection's total is read from f->n: the word is free)
   volatile int* const nw = ctx->tune.result_mirror && ctx->progress ? ctx->progress + 6 : nullptr;
   if (nw) {
     nw[0] = -1;

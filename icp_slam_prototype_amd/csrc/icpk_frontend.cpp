@@ -72,24 +72,10 @@ int icpk_set_subsample(icpk_ctx* ctx, int32_t factor, uint64_t seed) {
 }
 
 static int ensure_depth_buffers(icpk_ctx* ctx, int count, int ints) {
-  if (count > ctx->depth_cap) {
-    if (ctx->depth_dev) ICPK_HIP(ctx, hipFree(ctx->depth_dev));
-    if (ctx->depth_flt) ICPK_HIP(ctx, hipFree(ctx->depth_flt));
-    ctx->depth_dev = ctx->depth_flt = nullptr;
-    ctx->depth_cap = 0;
-    ctx->frame_slot = -1;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->depth_dev, (size_t)count * sizeof(uint16_t)));
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->depth_flt, (size_t)count * sizeof(uint16_t)));
-    ctx->depth_cap = count;
-  }
-  if (ints > ctx->bp_counts_cap) {
-    if (ctx->bp_counts) ICPK_HIP(ctx, hipFree(ctx->bp_counts));
-    ctx->bp_counts = nullptr;
-    ctx->bp_counts_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->bp_counts, (size_t)ints * sizeof(int)));
-    ctx->bp_counts_cap = ints;
-  }
-  return ICPK_OK;
+  bool grown = false;
+  const int rc = reserve_group(ctx, &grown, need(ctx->depth_dev, count), need(ctx->depth_flt, count));
+  if (grown) ctx->frame_slot = -1;
+  return rc ? rc : ctx->bp_counts.reserve(ctx, ints);
 }
 
 static int backproject_impl(icpk_ctx* ctx, const uint16_t* depth, int32_t rows, int32_t cols, float fx, float cx,
@@ -170,9 +156,10 @@ int icpk_backproject_pair(icpk_ctx* ctx, const uint16_t* depth_source, const uin
   // depth_target == NULL: the previous frame is the one this context saw as `depth_source` last time (SLAM.cpp:305,
   // previous = filtered.clone()): its image -- and its filtered copy -- are still on the device
   const bool resident = depth_target == nullptr;
-  if (resident && (ctx->frame_slot < 0 || ctx->frame_rows != rows || ctx->frame_cols != cols || 2 * npix > ctx->depth_cap))
+  const bool fits = (size_t)2 * npix <= ctx->depth_dev.capacity();
+  if (resident && (ctx->frame_slot < 0 || ctx->frame_rows != rows || ctx->frame_cols != cols || !fits))
     return fail(ctx, ICPK_E_NOT_SET, "no resident previous frame of this size (pass depth_target)");
-  if (!resident && 2 * npix > ctx->depth_cap) ctx->frame_slot = -1;  // (the buffers are about to be replaced)
+  if (!resident && !fits) ctx->frame_slot = -1;  // (the buffers are about to be replaced)
   rc = ensure_depth_buffers(ctx, 2 * npix, 2 * per_image + 2);
   if (rc) return rc;
   for (Cloud* c : {&ctx->src0, &ctx->src, &ctx->tgt}) {
@@ -193,13 +180,7 @@ int icpk_backproject_pair(icpk_ctx* ctx, const uint16_t* depth_source, const uin
   // to the runtime -- one blocking copy, then the transfer -- and was seen to take 70 us in one process and 340 us in
   // the next for the same 614 KB.)  The buffer is free again when this call returns: the counts it waits for are made
   // from the uploaded images.
-  if (2 * npix > ctx->stage_depth_cap) {
-    if (ctx->stage_depth) ICPK_HIP(ctx, hipHostFree(ctx->stage_depth));
-    ctx->stage_depth = nullptr;
-    ctx->stage_depth_cap = 0;
-    ICPK_HIP(ctx, hipHostMalloc((void**)&ctx->stage_depth, (size_t)2 * npix * sizeof(uint16_t), hipHostMallocDefault));
-    ctx->stage_depth_cap = 2 * npix;
-  }
+  if ((rc = ctx->stage_depth.reserve(ctx, (size_t)2 * npix))) return rc;
   // without the filter the images are not copied at all: the counting pass reads them from the staging buffer
   const bool zero_copy = !filter && ctx->tune.zero_copy_upload;
   // (an image inside memory the caller has registered -- icpk_register_host_buffer -- is read where it lies: no copy at all)
@@ -230,15 +211,7 @@ int icpk_backproject_pair(icpk_ctx* ctx, const uint16_t* depth_source, const uin
     img_s = flt_s;
     img_t = flt_t;
   }
-  if (npix > ctx->pix_cap) {
-    if (ctx->pix_tidx) ICPK_HIP(ctx, hipFree(ctx->pix_tidx));
-    if (ctx->pix_src) ICPK_HIP(ctx, hipFree(ctx->pix_src));
-    ctx->pix_tidx = ctx->pix_src = nullptr;
-    ctx->pix_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->pix_tidx, (size_t)npix * sizeof(int)));
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->pix_src, (size_t)npix * sizeof(int)));
-    ctx->pix_cap = npix;
-  }
+  if ((rc = reserve_group(ctx, nullptr, need(ctx->pix_tidx, npix), need(ctx->pix_src, npix)))) return rc;
   BpPair b;
   const uint16_t* stage_dev = nullptr;
   if (zero_copy) ICPK_HIP(ctx, hipHostGetDevicePointer((void**)&stage_dev, ctx->stage_depth, 0));
@@ -346,21 +319,15 @@ int icpk_associate_keypoints(icpk_ctx* ctx, int32_t nn_mode, float max_dist, int
     return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP: max_dist <= 0.75");
   int rc = enqueue_nn(ctx, nn_mode);
   if (rc) return rc;
-  const int cap = round_up(nq, NN_TILE);
-  if (cap > ctx->ks_cap) {
-    if (ctx->ks_buf) ICPK_HIP(ctx, hipFree(ctx->ks_buf));
-    ctx->ks_buf = nullptr;
-    ctx->ks_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->ks_buf, (size_t)4 * cap * sizeof(int32_t)));
-    ctx->ks_cap = cap;
-  }
+  if ((rc = ctx->ks_buf.reserve(ctx, (size_t)4 * round_up(nq, NN_TILE)))) return rc;
   const int nblocks = (nq + 1023) / 1024;
   rc = ensure_depth_buffers(ctx, 0, nblocks + 2);
   if (rc) return rc;
+  const size_t ks = ctx->ks_buf.capacity() / 4;  // entries per list
   int32_t* dq = ctx->ks_buf;
-  int32_t* dt = dq + ctx->ks_cap;
-  float* dd = reinterpret_cast<float*>(dt + ctx->ks_cap);
-  int32_t* dr = dt + 2 * (size_t)ctx->ks_cap;
+  int32_t* dt = dq + ks;
+  float* dd = reinterpret_cast<float*>(dt + ks);
+  int32_t* dr = dt + 2 * ks;
   launch_assoc_split(ctx->best, nq, max_dist, ctx->bp_counts, ctx->bp_counts + nblocks + 1, dq, dt, dd, dr, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
   ICPK_HIP(ctx, hipMemcpyAsync(ctx->bp_n_host, ctx->bp_counts + nblocks + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));

@@ -16,31 +16,36 @@
 
 using namespace icpk;
 
+namespace {
+
+// three planes of stride() floats in one device buffer (x | y | z)
+struct Planes {
+  DevBuf<float> mem;
+  int stride() const { return (int)(mem.capacity() / 3); }
+  float* plane(int k) const { return mem + (size_t)k * stride(); }
+  int reserve(icpk_ctx* ctx, int n) { return mem.reserve(ctx, (size_t)3 * n); }  // (contents lost when it grows)
+};
+
+}  // namespace
+
 struct icpk_map_state {
-  uint8_t* cert = nullptr;  // MAP_CELLS, world[x][y][z]
-  int* slot = nullptr;      // MAP_CELLS
-  float* list[2] = {nullptr, nullptr};  // three planes of list_cap[k] floats each
+  DevBuf<uint8_t> cert;  // MAP_CELLS, world[x][y][z]
+  DevBuf<int> slot;      // MAP_CELLS
+  Planes list[2];        // the two point lists, list_n[k] points each
   int list_n[2] = {0, 0};
-  int list_cap[2] = {0, 0};
-  int* scratch = nullptr;  // MapBuffers of up to scratch_cap batch elements
+  DevBuf<int> scratch;  // MapBuffers of up to scratch_cap batch elements
   int scratch_cap = 0;
-  MapBuffers b{};
-  int* idx = nullptr;  // uploaded index list
-  int idx_cap = 0;
-  float* batch = nullptr;  // three planes: uploaded points / query points / rejected positions
-  int batch_cap = 0;
-  float* pos = nullptr;  // three planes: the positions of every association sweep (icpk_align_to_map)
-  int pos_cap = 0;
-  Rt* motion = nullptr;
-  int motion_cap = 0;
-  int* qout = nullptr;  // icpk_map_query: certainty and slot per point
-  int qout_cap = 0;
-  int* total_host = nullptr;  // pinned
-  unsigned* mask = nullptr;  // K9's occupancy mask (MAP_MASK_WORDS) ...
+  MapBuffers b{};       // (views into scratch)
+  DevBuf<int> idx;      // uploaded index list
+  Planes batch;         // uploaded points / query points / rejected positions
+  Planes pos;           // the positions of every association sweep (icpk_align_to_map)
+  DevBuf<Rt> motion;
+  DevBuf<int> qout;  // icpk_map_query: certainty and slot per point
+  PinnedBuf<int> total_host;
+  DevBuf<unsigned> mask;  // K9's occupancy mask (MAP_MASK_WORDS) ...
   bool mask_valid = false;
   unsigned mask_version = 0;  // ... built from the slots of this map version
-  nn_key_t* nnkey = nullptr;  // icpk_map_nearest: K9's keys per query
-  int nnkey_cap = 0;
+  DevBuf<nn_key_t> nnkey;  // icpk_map_nearest: K9's keys per query
   // K9's distance bound holds while every filled slot names a point inside its voxel's cell: true until
   // icpk_map_set_points replaces a point list that slots filled by ADD_ASSOCIATED name (never in the reference's flow,
   // where the list is assigned only at the seed); a reset restores it
@@ -50,66 +55,40 @@ struct icpk_map_state {
 
 namespace {
 
-float* plane(float* base, int cap, int k) { return base + (size_t)k * cap; }
-
-int grow_int(icpk_ctx* ctx, int*& p, int& cap, int need) {
-  if (need <= cap) return ICPK_OK;
-  if (p) ICPK_HIP(ctx, hipFree(p));
-  p = nullptr;
-  cap = 0;
-  ICPK_HIP(ctx, hipMalloc((void**)&p, (size_t)need * sizeof(int)));
-  cap = need;
-  return ICPK_OK;
-}
-
-int grow_planes(icpk_ctx* ctx, float*& p, int& cap, int need) {
-  if (need <= cap) return ICPK_OK;
-  if (p) ICPK_HIP(ctx, hipFree(p));
-  p = nullptr;
-  cap = 0;
-  ICPK_HIP(ctx, hipMalloc((void**)&p, (size_t)3 * need * sizeof(float)));
-  cap = need;
-  return ICPK_OK;
-}
-
 int ensure_map(icpk_ctx* ctx) {
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   if (ctx->map) return ICPK_OK;
   icpk_map_state* m = new icpk_map_state();
   ctx->map = m;
-  hipError_t e = hipMalloc((void**)&m->cert, (size_t)MAP_CELLS);
-  if (e == hipSuccess) e = hipMalloc((void**)&m->slot, (size_t)MAP_CELLS * sizeof(int));
-  if (e == hipSuccess) e = hipHostMalloc((void**)&m->total_host, sizeof(int), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipMemsetAsync(m->cert, 0, (size_t)MAP_CELLS, ctx->stream);  // map.cpp:26
-  if (e == hipSuccess) e = hipMemsetAsync(m->slot, 0xff, (size_t)MAP_CELLS * sizeof(int), ctx->stream);  // map.cpp:27
-  if (e != hipSuccess) {
-    icpk_map_free(ctx);  // (no half-built map is left behind)
-    ctx->err = std::string("map allocation: ") + hipGetErrorString(e);
-    return ICPK_E_HIP;
-  }
-  return ICPK_OK;
+  int rc = m->cert.reserve(ctx, MAP_CELLS);
+  if (!rc) rc = m->slot.reserve(ctx, MAP_CELLS);
+  if (!rc) rc = m->total_host.reserve(ctx, 1);
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemsetAsync(m->cert, 0, (size_t)MAP_CELLS, ctx->stream);  // map.cpp:26
+  if (!rc && e == hipSuccess) e = hipMemsetAsync(m->slot, 0xff, (size_t)MAP_CELLS * sizeof(int), ctx->stream);  // map.cpp:27
+  if (e != hipSuccess) rc = hip_failure(ctx, "map set-up", e);
+  if (rc) icpk_map_free(ctx);  // (no half-built map is left behind)
+  return rc;
 }
 
 // room for `need` entries in a list, its first list_n entries kept (capacity doubling)
 int ensure_list(icpk_ctx* ctx, int list, int need) {
   icpk_map_state* m = ctx->map;
-  if (need <= m->list_cap[list]) return ICPK_OK;
-  int cap = m->list_cap[list] * 2;
+  Planes& L = m->list[list];
+  if (need <= L.stride()) return ICPK_OK;
+  int cap = L.stride() * 2;
   if (cap < need) cap = need;
   if (cap < 1024) cap = 1024;
-  float* p = nullptr;
-  ICPK_HIP(ctx, hipMalloc((void**)&p, (size_t)3 * cap * sizeof(float)));
+  Planes grown;
+  if (int rc = grown.reserve(ctx, cap)) return rc;
   const int n = m->list_n[list];
   if (n > 0)
     for (int k = 0; k < 3; ++k)
-      ICPK_HIP(ctx, hipMemcpyAsync(plane(p, cap, k), plane(m->list[list], m->list_cap[list], k), (size_t)n * sizeof(float),
-                                   hipMemcpyDeviceToDevice, ctx->stream));
-  if (m->list[list]) {
-    ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ICPK_HIP(ctx, hipFree(m->list[list]));
-  }
-  m->list[list] = p;
-  m->list_cap[list] = cap;
+      ICPK_HIP(ctx, hipMemcpyAsync(grown.plane(k), L.plane(k), (size_t)n * sizeof(float), hipMemcpyDeviceToDevice,
+                                   ctx->stream));
+  if (L.mem) ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::swap(L, grown);
+  ICPK_HIP(ctx, grown.mem.release());  // (the old list)
   return ICPK_OK;
 }
 
@@ -120,10 +99,8 @@ int ensure_scratch(icpk_ctx* ctx, int n) {
   if (cap < n) cap = n;
   const size_t tiles = (size_t)(cap + MAP_TILE - 1) / MAP_TILE;
   const size_t ints = (size_t)6 * cap + (size_t)MAP_RADIX * tiles + (tiles + 1) + 1;
-  if (m->scratch) ICPK_HIP(ctx, hipFree(m->scratch));
-  m->scratch = nullptr;
   m->scratch_cap = 0;
-  ICPK_HIP(ctx, hipMalloc((void**)&m->scratch, ints * sizeof(int)));
+  if (int rc = m->scratch.reserve(ctx, ints)) return rc;
   int* p = m->scratch;
   m->b.key = p;
   m->b.ka = p + (size_t)cap;
@@ -152,10 +129,8 @@ int run_update(icpk_ctx* ctx, int rule, const MapPoints& p, int delta) {
   if (rc) return rc;
   rc = ensure_scratch(ctx, p.n);
   if (rc) return rc;
-  const int cap = m->list_cap[list];
-  float* L = m->list[list];
-  launch_map_update(p, rule, delta, old, list, plane(L, cap, 0), plane(L, cap, 1), plane(L, cap, 2), m->cert, m->slot, m->b,
-                    ctx->stream);
+  const Planes& L = m->list[list];
+  launch_map_update(p, rule, delta, old, list, L.plane(0), L.plane(1), L.plane(2), m->cert, m->slot, m->b, ctx->stream);
   if (list == ICPK_MAP_POINTS) m->points_named = true;  // (possibly: a superset is safe)
   ICPK_HIP(ctx, hipGetLastError());
   ICPK_HIP(ctx, hipMemcpyAsync(m->total_host, m->b.total, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -186,11 +161,11 @@ bool bad_rule(int rule, int delta) {
 
 int upload_points(icpk_ctx* ctx, const float* x, const float* y, const float* z, int n) {
   icpk_map_state* m = ctx->map;
-  int rc = grow_planes(ctx, m->batch, m->batch_cap, n);
+  int rc = m->batch.reserve(ctx, n);
   if (rc) return rc;
   const float* src[3] = {x, y, z};
   for (int k = 0; k < 3; ++k)
-    ICPK_HIP(ctx, hipMemcpyAsync(plane(m->batch, m->batch_cap, k), src[k], (size_t)n * sizeof(float), hipMemcpyHostToDevice,
+    ICPK_HIP(ctx, hipMemcpyAsync(m->batch.plane(k), src[k], (size_t)n * sizeof(float), hipMemcpyHostToDevice,
                                  ctx->stream));
   return ICPK_OK;
 }
@@ -213,13 +188,7 @@ int upload_motion(icpk_ctx* ctx, const icpk_params* p, int* niter_out) {
       std::memcpy(mo[(size_t)s].t, t, sizeof(mo[(size_t)s].t));
     }
   }
-  if (niter > m->motion_cap) {
-    if (m->motion) ICPK_HIP(ctx, hipFree(m->motion));
-    m->motion = nullptr;
-    m->motion_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&m->motion, (size_t)niter * sizeof(Rt)));
-    m->motion_cap = niter;
-  }
+  if (int rc = m->motion.reserve(ctx, niter)) return rc;
   if (niter > 0)
     ICPK_HIP(ctx, hipMemcpyAsync(m->motion, mo.data(), (size_t)niter * sizeof(Rt), hipMemcpyHostToDevice, ctx->stream));
   *niter_out = niter;
@@ -229,7 +198,7 @@ int upload_motion(icpk_ctx* ctx, const icpk_params* p, int* niter_out) {
 // K9's occupancy mask, rebuilt from the slots if the map has changed since it was built
 int ensure_mask(icpk_ctx* ctx) {
   icpk_map_state* m = ctx->map;
-  if (!m->mask) ICPK_HIP(ctx, hipMalloc((void**)&m->mask, (size_t)MAP_MASK_WORDS * sizeof(unsigned)));
+  if (int rc = m->mask.reserve(ctx, MAP_MASK_WORDS)) return rc;
   if (m->mask_valid && m->mask_version == ctx->map_version) return ICPK_OK;
   launch_map_mask(m->slot, m->mask, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
@@ -249,18 +218,8 @@ MapNnArgs nn_args(icpk_ctx* ctx, const float* x, const float* y, const float* z,
   a.slot = m->slot;
   a.mask = m->mask;
   a.cells_exact = m->cells_exact ? 1 : 0;
-  for (int k = 0; k < 2; ++k) {
-    float* L = m->list[k];
-    const int cap = m->list_cap[k];
-    const float* px = L ? plane(L, cap, 0) : nullptr;
-    const float* py = L ? plane(L, cap, 1) : nullptr;
-    const float* pz = L ? plane(L, cap, 2) : nullptr;
-    if (k == 0) {
-      a.l0x = px, a.l0y = py, a.l0z = pz, a.n0 = m->list_n[0];
-    } else {
-      a.l1x = px, a.l1y = py, a.l1z = pz, a.n1 = m->list_n[1];
-    }
-  }
+  a.l0x = m->list[0].plane(0), a.l0y = m->list[0].plane(1), a.l0z = m->list[0].plane(2), a.n0 = m->list_n[0];
+  a.l1x = m->list[1].plane(0), a.l1y = m->list[1].plane(1), a.l1z = m->list[1].plane(2), a.n1 = m->list_n[1];
   a.best = best;
   a.stop = stop;
   return a;
@@ -287,12 +246,7 @@ void icpk_map_free(icpk_ctx* ctx) {
   ++ctx->map_version;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  void* dev[] = {m->cert, m->slot, m->list[0], m->list[1], m->scratch, m->idx, m->batch, m->pos, m->motion, m->qout,
-                 m->mask, m->nnkey};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  if (m->total_host) (void)hipHostFree(m->total_host);
-  delete m;
+  delete m;  // (its buffers free themselves)
   ctx->map = nullptr;
 }
 
@@ -336,7 +290,7 @@ int icpk_map_update(icpk_ctx* ctx, int32_t rule, int32_t from, const int32_t* in
     for (int32_t k = 0; k < n; ++k)
       if (indices[k] < 0 || indices[k] >= c->n) return fail(ctx, ICPK_E_ARG, "map index outside the cloud");
     icpk_map_state* m = ctx->map;
-    rc = grow_int(ctx, m->idx, m->idx_cap, n);
+    rc = m->idx.reserve(ctx, n);
     if (rc) return rc;
     if (n > 0)
       ICPK_HIP(ctx, hipMemcpyAsync(m->idx, indices, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -357,7 +311,7 @@ int icpk_map_update_points(icpk_ctx* ctx, int32_t rule, const float* x, const fl
   rc = upload_points(ctx, x, y, z, n);
   if (rc) return rc;
   icpk_map_state* m = ctx->map;
-  MapPoints p{plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1), plane(m->batch, m->batch_cap, 2), nullptr,
+  MapPoints p{m->batch.plane(0), m->batch.plane(1), m->batch.plane(2), nullptr,
               n};
   return run_update(ctx, rule, p, delta);
 }
@@ -375,11 +329,10 @@ int icpk_map_set_points(icpk_ctx* ctx, int32_t from) {
   m->list_n[ICPK_MAP_POINTS] = 0;  // (nothing of the old list survives the assignment)
   rc = ensure_list(ctx, ICPK_MAP_POINTS, c->n);
   if (rc) return rc;
-  const int cap = m->list_cap[ICPK_MAP_POINTS];
   const float* src[3] = {c->x(), c->y(), c->z()};
   if (c->n > 0)
     for (int k = 0; k < 3; ++k)
-      ICPK_HIP(ctx, hipMemcpyAsync(plane(m->list[ICPK_MAP_POINTS], cap, k), src[k], (size_t)c->n * sizeof(float),
+      ICPK_HIP(ctx, hipMemcpyAsync(m->list[ICPK_MAP_POINTS].plane(k), src[k], (size_t)c->n * sizeof(float),
                                    hipMemcpyDeviceToDevice, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   m->list_n[ICPK_MAP_POINTS] = c->n;
@@ -399,7 +352,7 @@ int icpk_map_get_list(icpk_ctx* ctx, int32_t list, float* x, float* y, float* z)
   icpk_map_state* m = ctx->map;
   float* dst[3] = {x, y, z};
   for (int k = 0; k < 3; ++k)
-    ICPK_HIP(ctx, hipMemcpyAsync(dst[k], plane(m->list[list], m->list_cap[list], k), (size_t)m->list_n[list] * sizeof(float),
+    ICPK_HIP(ctx, hipMemcpyAsync(dst[k], m->list[list].plane(k), (size_t)m->list_n[list] * sizeof(float),
                                  hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ICPK_OK;
@@ -422,9 +375,9 @@ int icpk_map_query(icpk_ctx* ctx, const float* x, const float* y, const float* z
   rc = upload_points(ctx, x, y, z, n);
   if (rc) return rc;
   icpk_map_state* m = ctx->map;
-  rc = grow_int(ctx, m->qout, m->qout_cap, 2 * n);
+  rc = m->qout.reserve(ctx, 2 * (size_t)n);
   if (rc) return rc;
-  launch_map_query(plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1), plane(m->batch, m->batch_cap, 2), n,
+  launch_map_query(m->batch.plane(0), m->batch.plane(1), m->batch.plane(2), n,
                    m->cert, m->slot, m->qout, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
   std::vector<int> out((size_t)2 * n);
@@ -445,10 +398,8 @@ int icpk_map_list_to_target(icpk_ctx* ctx, int32_t list) {
   int rc = ensure_map(ctx);
   if (rc) return rc;
   icpk_map_state* m = ctx->map;
-  const int cap = m->list_cap[list];
-  float* L = m->list[list];
-  return icpk_set_target_device(ctx, L ? plane(L, cap, 0) : nullptr, L ? plane(L, cap, 1) : nullptr,
-                                L ? plane(L, cap, 2) : nullptr, m->list_n[list]);
+  const Planes& L = m->list[list];
+  return icpk_set_target_device(ctx, L.plane(0), L.plane(1), L.plane(2), m->list_n[list]);
 }
 
 void icpk_map_voxel(const float p[3], int32_t v[3]) {
@@ -496,18 +447,18 @@ int icpk_align_to_map(icpk_ctx* ctx, const icpk_params* p, int32_t delta, float 
   if (total_pos > (1ll << 30)) return fail(ctx, ICPK_E_ARG, "too many sweep positions");
   const int mpos = (int)total_pos;
   rc = ensure_scratch(ctx, mpos);
-  if (!rc) rc = grow_planes(ctx, m->pos, m->pos_cap, mpos);
-  if (!rc) rc = grow_planes(ctx, m->batch, m->batch_cap, mpos);
+  if (!rc) rc = m->pos.reserve(ctx, mpos);
+  if (!rc) rc = m->batch.reserve(ctx, mpos);
   if (rc) return rc;
-  launch_map_rejected(ctx->src0.x(), ctx->src0.y(), ctx->src0.z(), ns, m->motion, nsw, plane(m->pos, m->pos_cap, 0),
-                      plane(m->pos, m->pos_cap, 1), plane(m->pos, m->pos_cap, 2), ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(),
-                      ctx->tgt.n, p->max_nn_dist, plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1),
-                      plane(m->batch, m->batch_cap, 2), m->b, ctx->stream);
+  launch_map_rejected(ctx->src0.x(), ctx->src0.y(), ctx->src0.z(), ns, m->motion, nsw, m->pos.plane(0),
+                      m->pos.plane(1), m->pos.plane(2), ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(),
+                      ctx->tgt.n, p->max_nn_dist, m->batch.plane(0), m->batch.plane(1),
+                      m->batch.plane(2), m->b, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
   ICPK_HIP(ctx, hipMemcpyAsync(m->total_host, m->b.total, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const int nrej = *m->total_host;
-  MapPoints rej{plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1), plane(m->batch, m->batch_cap, 2), nullptr,
+  MapPoints rej{m->batch.plane(0), m->batch.plane(1), m->batch.plane(2), nullptr,
                 nrej};
   rc = run_update(ctx, ICPK_MAP_ADD_UNASSOCIATED, rej, delta);  // icp.cpp:271
   return rc ? rc : status;
@@ -521,17 +472,11 @@ int icpk_map_nearest(icpk_ctx* ctx, const float* x, const float* y, const float*
   rc = upload_points(ctx, x, y, z, n);
   if (rc) return rc;
   icpk_map_state* m = ctx->map;
-  if (n > m->nnkey_cap) {
-    if (m->nnkey) ICPK_HIP(ctx, hipFree(m->nnkey));
-    m->nnkey = nullptr;
-    m->nnkey_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&m->nnkey, (size_t)n * sizeof(nn_key_t)));
-    m->nnkey_cap = n;
-  }
-  rc = ensure_mask(ctx);
+  rc = m->nnkey.reserve(ctx, n);
+  if (!rc) rc = ensure_mask(ctx);
   if (rc) return rc;
-  launch_map_nn(nn_args(ctx, plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1),
-                        plane(m->batch, m->batch_cap, 2), n, m->nnkey, nullptr),
+  launch_map_nn(nn_args(ctx, m->batch.plane(0), m->batch.plane(1),
+                        m->batch.plane(2), n, m->nnkey, nullptr),
                 ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
   std::vector<nn_key_t> keys((size_t)n);
@@ -570,10 +515,10 @@ int icpk_map_lookup_to_target(icpk_ctx* ctx) {
   float* dst[3] = {c.x(), c.y(), c.z()};
   for (int k = 0; k < 3; ++k) {
     if (n0 > 0)
-      ICPK_HIP(ctx, hipMemcpyAsync(dst[k], plane(m->list[0], m->list_cap[0], k), (size_t)n0 * sizeof(float),
+      ICPK_HIP(ctx, hipMemcpyAsync(dst[k], m->list[0].plane(k), (size_t)n0 * sizeof(float),
                                    hipMemcpyDeviceToDevice, ctx->stream));
     if (n1 > 0)
-      ICPK_HIP(ctx, hipMemcpyAsync(dst[k] + n0, plane(m->list[1], m->list_cap[1], k), (size_t)n1 * sizeof(float),
+      ICPK_HIP(ctx, hipMemcpyAsync(dst[k] + n0, m->list[1].plane(k), (size_t)n1 * sizeof(float),
                                    hipMemcpyDeviceToDevice, ctx->stream));
     ICPK_HIP(ctx, hipMemsetAsync(dst[k] + n0 + n1, 0, sizeof(float), ctx->stream));  // the zero point
   }
@@ -614,20 +559,19 @@ int icpk_align_to_map_dense(icpk_ctx* ctx, const icpk_params* p, int32_t delta, 
   const long long total_pos = (long long)ns * nsw;
   if (total_pos > (1ll << 30)) return fail(ctx, ICPK_E_ARG, "too many sweep positions");
   rc = ensure_scratch(ctx, ns);
-  if (!rc) rc = grow_planes(ctx, m->pos, m->pos_cap, (int)total_pos);
-  if (!rc) rc = grow_planes(ctx, m->batch, m->batch_cap, ns);
+  if (!rc) rc = m->pos.reserve(ctx, (int)total_pos);
+  if (!rc) rc = m->batch.reserve(ctx, ns);
   if (rc) return rc;
-  const int pc = m->pos_cap;
-  launch_map_poses(ctx->src0.x(), ctx->src0.y(), ctx->src0.z(), ns, m->motion, nsw, plane(m->pos, pc, 0),
-                   plane(m->pos, pc, 1), plane(m->pos, pc, 2), ctx->stream);
+  launch_map_poses(ctx->src0.x(), ctx->src0.y(), ctx->src0.z(), ns, m->motion, nsw, m->pos.plane(0),
+                   m->pos.plane(1), m->pos.plane(2), ctx->stream);
   const size_t last = (size_t)niter * ns;
-  launch_map_accepted(plane(m->pos, pc, 0) + last, plane(m->pos, pc, 1) + last, plane(m->pos, pc, 2) + last, ns, ctx->best,
-                      p->max_nn_dist, plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1),
-                      plane(m->batch, m->batch_cap, 2), m->b, ctx->stream);
+  launch_map_accepted(m->pos.plane(0) + last, m->pos.plane(1) + last, m->pos.plane(2) + last, ns, ctx->best,
+                      p->max_nn_dist, m->batch.plane(0), m->batch.plane(1),
+                      m->batch.plane(2), m->b, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
   ICPK_HIP(ctx, hipMemcpyAsync(m->total_host, m->b.total, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  MapPoints acc{plane(m->batch, m->batch_cap, 0), plane(m->batch, m->batch_cap, 1), plane(m->batch, m->batch_cap, 2),
+  MapPoints acc{m->batch.plane(0), m->batch.plane(1), m->batch.plane(2),
                 nullptr, *m->total_host};
   rc = run_update(ctx, ICPK_MAP_ADD_ASSOCIATED, acc, delta);
   return rc ? rc : status;

@@ -16,11 +16,9 @@ int ensure_cloud(icpk_ctx* ctx, Cloud& c, int n) {
   if (ctx && (&c == &ctx->src0 || &c == &ctx->tgt)) ctx->have_pix_seed = false;  // (other points than the pixel maps describe)
   const int cap = round_up(n < 1 ? 1 : n, NN_TILE);
   if (cap > c.cap) {
-    if (c.base) ICPK_HIP(ctx, hipFree(c.base));
-    c.base = nullptr;
     c.cap = 0;
     // +64 floats: the filtered NN kernel prefetches one group past its chunk
-    ICPK_HIP(ctx, hipMalloc((void**)&c.base, ((size_t)3 * cap + 64) * sizeof(float)));
+    if (int rc = c.base.reserve(ctx, (size_t)3 * cap + 64)) return rc;
     c.cap = cap;
   }
   c.n = n;
@@ -28,45 +26,19 @@ int ensure_cloud(icpk_ctx* ctx, Cloud& c, int n) {
 }
 
 int ensure_assoc(icpk_ctx* ctx, int nq) {
-  const int cap = round_up(nq < 1 ? 1 : nq, NN_TILE);
-  if (cap > ctx->assoc_cap) {
-    if (ctx->best) ICPK_HIP(ctx, hipFree(ctx->best));
-    if (ctx->seed) ICPK_HIP(ctx, hipFree(ctx->seed));
-    if (ctx->best_m) ICPK_HIP(ctx, hipFree(ctx->best_m));
-    if (ctx->seed_m) ICPK_HIP(ctx, hipFree(ctx->seed_m));
-    ctx->best_m = ctx->seed_m = nullptr;
-    if (ctx->idx) ICPK_HIP(ctx, hipFree(ctx->idx));
-    if (ctx->dist) ICPK_HIP(ctx, hipFree(ctx->dist));
-    ctx->best = ctx->seed = nullptr;
-    ctx->idx = nullptr;
-    ctx->dist = nullptr;
-    ctx->assoc_cap = 0;
-    ctx->have_seed = false;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->best, (size_t)cap * sizeof(nn_key_t)));
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->seed, (size_t)cap * sizeof(nn_key_t)));
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->best_m, (size_t)cap * sizeof(nn_key_t)));
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->seed_m, (size_t)cap * sizeof(nn_key_t)));
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->idx, (size_t)cap * sizeof(int32_t)));
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->dist, (size_t)cap * sizeof(float)));
-    ctx->assoc_cap = cap;
-  }
-  return ICPK_OK;
+  const size_t cap = round_up(nq < 1 ? 1 : nq, NN_TILE);
+  bool grown = false;
+  const int rc = reserve_group(ctx, &grown, need(ctx->best, cap), need(ctx->seed, cap), need(ctx->best_m, cap),
+                               need(ctx->seed_m, cap), need(ctx->idx, cap), need(ctx->dist, cap));
+  if (grown) ctx->have_seed = false;
+  return rc;
 }
 
 static int ensure_sort_buffers(icpk_ctx* ctx, int n) {
-  const int cap = round_up(n < 1 ? 1 : n, NN_TILE);
-  if (cap > ctx->sort_cap) {
-    if (ctx->sort_keys) ICPK_HIP(ctx, hipFree(ctx->sort_keys));
-    if (ctx->sort_vals) ICPK_HIP(ctx, hipFree(ctx->sort_vals));
-    ctx->sort_keys = nullptr;
-    ctx->sort_vals = nullptr;
-    ctx->sort_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->sort_keys, (size_t)2 * cap * sizeof(unsigned)));
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->sort_vals, (size_t)cap * sizeof(int)));
-    ctx->sort_cap = cap;
-  }
-  if (!ctx->bounds) ICPK_HIP(ctx, hipMalloc((void**)&ctx->bounds, 6 * sizeof(float)));
-  return ICPK_OK;
+  const size_t cap = round_up(n < 1 ? 1 : n, NN_TILE);
+  int rc = reserve_group(ctx, nullptr, need(ctx->sort_keys, 2 * cap), need(ctx->sort_vals, cap));
+  ctx->sort_cap = (int)ctx->sort_vals.capacity();
+  return rc ? rc : ctx->bounds.reserve(ctx, 6);
 }
 
 static int ensure_scan_buffers(icpk_ctx* ctx);
@@ -77,8 +49,8 @@ static int enqueue_morton_order(icpk_ctx* ctx, const Cloud& c, int* perm_out) {
   int rc = ensure_sort_buffers(ctx, c.n);
   if (rc) return rc;
   rc = ensure_scan_buffers(ctx);
+  if (!rc) rc = ctx->morton_table.reserve(ctx, 1);
   if (rc) return rc;
-  if (!ctx->morton_table) ICPK_HIP(ctx, hipMalloc((void**)&ctx->morton_table, sizeof(GridInfo)));
   unsigned* ka = ctx->sort_keys;
   unsigned* kb = ctx->sort_keys + ctx->sort_cap;
   const int bits = ctx->grid_max_cells >= (1 << 21) + 1 ? 7 : 6;  // 8^bits cells + 1 bin + 1 must fit the count table
@@ -95,25 +67,17 @@ static int prepare_pruned_target(icpk_ctx* ctx, NnBoxes& bx) {
   const int nt = ctx->tgt.n;
   const int nt_pad = round_up(nt, NN_TILE);
   const int ntiles = nt_pad / NN_TILE;
+  bool grown = false;
+  int rc = ICPK_OK;
   if (ntiles > ctx->boxes_tiles_cap) {
-    if (ctx->boxes) ICPK_HIP(ctx, hipFree(ctx->boxes));
-    ctx->boxes = nullptr;
     ctx->boxes_tiles_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->boxes, (size_t)6 * (ntiles + 16) * (1 + NN_SUBS) * sizeof(float)));
-    ctx->boxes_tiles_cap = ntiles;
-    ctx->have_boxes = false;
+    rc = ctx->boxes.reserve(ctx, (size_t)6 * (ntiles + 16) * (1 + NN_SUBS), &grown);
+    if (!rc) ctx->boxes_tiles_cap = ntiles;
   }
-  if (nt_pad > ctx->tperm_cap) {
-    if (ctx->tperm) ICPK_HIP(ctx, hipFree(ctx->tperm));
-    ctx->tperm = nullptr;
-    ctx->tperm_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->tperm, ((size_t)nt_pad + 64) * sizeof(int)));
-    if (ctx->tkeys) ICPK_HIP(ctx, hipFree(ctx->tkeys));
-    ctx->tkeys = nullptr;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->tkeys, ((size_t)nt_pad + 64) * sizeof(unsigned)));
-    ctx->tperm_cap = nt_pad;
-    ctx->have_boxes = false;
-  }
+  if (!rc) rc = ctx->tperm.reserve(ctx, (size_t)nt_pad + 64, &grown);  // (+64: read ahead)
+  if (!rc) rc = ctx->tkeys.reserve(ctx, (size_t)nt_pad + 64, &grown);
+  if (grown) ctx->have_boxes = false;
+  if (rc) return rc;
   bx.tbox_stride = ctx->boxes_tiles_cap + 16;
   bx.sbox_stride = (ctx->boxes_tiles_cap + 16) * NN_SUBS;
   bx.tbox = ctx->boxes;
@@ -124,7 +88,7 @@ static int prepare_pruned_target(icpk_ctx* ctx, NnBoxes& bx) {
   bx.tperm = ctx->tperm;
   bx.qperm = ctx->qperm;
   if (ctx->have_boxes) return ICPK_OK;
-  int rc = ensure_cloud(ctx, ctx->sorted, nt);
+  rc = ensure_cloud(ctx, ctx->sorted, nt);
   if (rc) return rc;
   rc = ensure_sort_buffers(ctx, nt);
   if (rc) return rc;
@@ -147,39 +111,32 @@ static int prepare_pruned_target(icpk_ctx* ctx, NnBoxes& bx) {
 // all zero between two sorts (the scan hands it back zeroed); a sort that did not get as far as its scan --
 // a failed launch -- leaves it marked dirty, and the next one clears all of it first.
 static int ensure_scan_buffers(icpk_ctx* ctx) {
-  const size_t bytes = ((size_t)ctx->grid_max_cells + 1) * sizeof(int);
-  if (!ctx->qcount) {
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->qcount, bytes));
-    ctx->qcount_dirty = true;
-  }
+  const size_t cells = (size_t)ctx->grid_max_cells + 1;
+  bool fresh = false;
+  int rc = ctx->qcount.reserve(ctx, cells, &fresh);
+  if (fresh) ctx->qcount_dirty = true;
+  if (rc) return rc;
   if (ctx->qcount_dirty) {
-    ICPK_HIP(ctx, hipMemsetAsync(ctx->qcount, 0, bytes, ctx->stream));
+    ICPK_HIP(ctx, hipMemsetAsync(ctx->qcount, 0, cells * sizeof(int), ctx->stream));
     ctx->qcount_dirty = false;
   }
-  if (!ctx->qstart) ICPK_HIP(ctx, hipMalloc((void**)&ctx->qstart, bytes));
-  if (!ctx->scan_bsum) ICPK_HIP(ctx, hipMalloc((void**)&ctx->scan_bsum, (size_t)GRID_SCAN_BLOCKS * sizeof(int)));
-  return ICPK_OK;
+  rc = ctx->qstart.reserve(ctx, cells);
+  return rc ? rc : ctx->scan_bsum.reserve(ctx, GRID_SCAN_BLOCKS);
 }
 
 // the grid scan's geometry, cell table and float4 copies of the target (a reallocation drops the grid)
 static int ensure_grid_buffers(icpk_ctx* ctx) {
   const int nt = ctx->tgt.n;
   if (nt > (1 << 28)) return fail(ctx, ICPK_E_ARG, "the grid search addresses its cell-sorted targets with 32-bit byte offsets: at most 2^28 target points");
-  if (!ctx->grid_info) ICPK_HIP(ctx, hipMalloc((void**)&ctx->grid_info, sizeof(GridInfo)));
-  if (!ctx->grid_bounds)
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->grid_bounds, (size_t)GRID_BOUNDS_PARTS * 6 * sizeof(float)));
-  if (!ctx->cell_start) ICPK_HIP(ctx, hipMalloc((void**)&ctx->cell_start, ((size_t)ctx->grid_max_cells + 1) * sizeof(int)));
-  if (nt > ctx->t4_cap) {
-    if (ctx->t4) ICPK_HIP(ctx, hipFree(ctx->t4));
-    if (ctx->o4) ICPK_HIP(ctx, hipFree(ctx->o4));
-    ctx->t4 = ctx->o4 = nullptr;
-    ctx->t4_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->t4, ((size_t)round_up(nt, NN_TILE) + 64) * sizeof(float4)));
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->o4, ((size_t)round_up(nt, NN_TILE) + 64) * sizeof(float4)));
-    ctx->t4_cap = round_up(nt, NN_TILE);
-    ctx->have_grid = false;
-  }
-  return ICPK_OK;
+  int rc = ctx->grid_info.reserve(ctx, 1);
+  if (!rc) rc = ctx->grid_bounds.reserve(ctx, (size_t)GRID_BOUNDS_PARTS * 6);
+  if (!rc) rc = ctx->cell_start.reserve(ctx, (size_t)ctx->grid_max_cells + 1);
+  if (rc) return rc;
+  const size_t n4 = (size_t)round_up(nt, NN_TILE) + 64;
+  bool grown = false;
+  rc = reserve_group(ctx, &grown, need(ctx->t4, n4), need(ctx->o4, n4));
+  if (grown) ctx->have_grid = false;
+  return rc;
 }
 
 // cell table + cell-sorted AoS copy of the target for the grid scan (once per target cloud).
@@ -273,30 +230,29 @@ static int build_grid_and_order(icpk_ctx* ctx) {
   if (rc) return rc;
   rc = ensure_scan_buffers(ctx);
   if (rc) return rc;
-  const size_t table = ((size_t)ctx->grid_max_cells + 1) * sizeof(int);
-  if (!ctx->qcount2) {
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->qcount2, table));
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->scan_bsum2, (size_t)GRID_SCAN_BLOCKS * sizeof(int)));
-    ctx->qcount2_dirty = true;
-  }
+  const size_t cells = (size_t)ctx->grid_max_cells + 1;
+  bool fresh = false;
+  rc = ctx->qcount2.reserve(ctx, cells, &fresh);
+  if (fresh) ctx->qcount2_dirty = true;
+  if (!rc) rc = ctx->scan_bsum2.reserve(ctx, GRID_SCAN_BLOCKS);
+  if (rc) return rc;
   if (ctx->qcount2_dirty) {  // (first use, or a sort that was cut short: the scans hand the table back zeroed otherwise)
-    ICPK_HIP(ctx, hipMemsetAsync(ctx->qcount2, 0, table, ctx->stream));
+    ICPK_HIP(ctx, hipMemsetAsync(ctx->qcount2, 0, cells * sizeof(int), ctx->stream));
     ctx->qcount2_dirty = false;
   }
-  if (ctx->sort_cap > ctx->sort_vals2_cap) {
-    if (ctx->sort_vals2) ICPK_HIP(ctx, hipFree(ctx->sort_vals2));
-    ctx->sort_vals2 = nullptr;
-    ctx->sort_vals2_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->sort_vals2, (size_t)ctx->sort_cap * sizeof(int)));
-    ctx->sort_vals2_cap = ctx->sort_cap;
-  }
+  if ((rc = ctx->sort_vals2.reserve(ctx, ctx->sort_cap))) return rc;
   int* tcell = reinterpret_cast<int*>(ctx->sort_keys + ctx->sort_cap);
   int* tslot = ctx->sort_vals;
-  int* qcell = reinterpret_cast<int*>(ctx->sort_keys);
+  int* qcell = reinterpret_cast<int*>(ctx->sort_keys.get());
   int* qslot = ctx->sort_vals2;
-  if (!ctx->grid_ticket) {
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->grid_ticket, sizeof(int)));
-    ICPK_HIP(ctx, hipMemsetAsync(ctx->grid_ticket, 0, sizeof(int), ctx->stream));
+  fresh = false;
+  if ((rc = ctx->grid_ticket.reserve(ctx, 1, &fresh))) return rc;
+  if (fresh) {  // (zero from here on: the last arrival resets it; a failed memset gives the ticket up, to be made again)
+    const hipError_t e = hipMemsetAsync(ctx->grid_ticket, 0, sizeof(int), ctx->stream);
+    if (e != hipSuccess) {
+      (void)ctx->grid_ticket.release();
+      return hip_failure(ctx, "hipMemsetAsync(grid_ticket)", e);
+    }
   }
   // bounds + geometry (+ the pending initial LoopState of the alignment being enqueued) in ONE launch
   launch_grid_begin(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), nt, ctx->grid_bounds, ctx->tune.grid_ppc, ctx->tune.grid_xdiv,
@@ -330,20 +286,12 @@ static int build_grid_and_order(icpk_ctx* ctx) {
 
 // scan-order copies of the queries and of their seed points (grid scan)
 static int ensure_query_points(icpk_ctx* ctx, int nq) {
-  if (nq <= ctx->qm4_cap) return ICPK_OK;
-  for (float4** pp : {&ctx->qm4, &ctx->sp_in, &ctx->sp_out, &ctx->rec}) {
-    if (*pp) ICPK_HIP(ctx, hipFree(*pp));
-    *pp = nullptr;
-  }
-  ctx->qm4_cap = 0;
-  const size_t bytes = ((size_t)round_up(nq, NN_TILE) + 64) * sizeof(float4);
-  ICPK_HIP(ctx, hipMalloc((void**)&ctx->qm4, bytes));
-  ICPK_HIP(ctx, hipMalloc((void**)&ctx->sp_in, bytes));
-  ICPK_HIP(ctx, hipMalloc((void**)&ctx->sp_out, bytes));
-  ICPK_HIP(ctx, hipMalloc((void**)&ctx->rec, 2 * bytes));
-  ctx->qm4_cap = round_up(nq, NN_TILE);
-  ctx->grid_chain = false;
-  return ICPK_OK;
+  const size_t n4 = (size_t)round_up(nq, NN_TILE) + 64;
+  bool grown = false;
+  const int rc = reserve_group(ctx, &grown, need(ctx->qm4, n4), need(ctx->sp_in, n4), need(ctx->sp_out, n4),
+                               need(ctx->rec, 2 * n4));
+  if (grown) ctx->grid_chain = false;
+  return rc;
 }
 
 // Everything a pruned / grid sweep needs before its K1 launch: query order (once per alignment),
@@ -352,15 +300,10 @@ static int ensure_query_points(icpk_ctx* ctx, int nq) {
 // rotates pointers.  recheck = 1: the seeds are loose (first sweep).
 int prepare_sorted_sweep(icpk_ctx* ctx, int nn_mode, NnArgs& a, NnBoxes& bx, int& recheck) {
   const int nq = ctx->src.n;
-  int rc = ICPK_OK;
-  if (round_up(nq, NN_TILE) > ctx->qperm_cap) {
-    if (ctx->qperm) ICPK_HIP(ctx, hipFree(ctx->qperm));
-    ctx->qperm = nullptr;
-    ctx->qperm_cap = 0;
-    ICPK_HIP(ctx, hipMalloc((void**)&ctx->qperm, (size_t)round_up(nq, NN_TILE) * sizeof(int)));
-    ctx->qperm_cap = round_up(nq, NN_TILE);
-    ctx->have_qperm = false;
-  }
+  bool grown = false;
+  int rc = ctx->qperm.reserve(ctx, round_up(nq, NN_TILE), &grown);
+  if (grown) ctx->have_qperm = false;
+  if (rc) return rc;
   bx = NnBoxes{};
   bool fresh = false;
   if (nn_mode == ICPK_NN_GRID) {
