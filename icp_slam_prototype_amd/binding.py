@@ -44,7 +44,9 @@ SYMBOLS = [
     "icpk_map_size", "icpk_map_get_list", "icpk_map_get_certainty", "icpk_map_query", "icpk_map_list_to_target",
     "icpk_map_voxel", "icpk_align_to_map", "icpk_map_nearest", "icpk_map_lookup_to_target", "icpk_align_to_map_dense",
     "icpk_bgr_to_gray", "icpk_detect_fast", "icpk_detected_to_cloud",
+    "icpk_align_frames_batch", "icpk_get_frames_trace", "icpk_release_frame_streams",
 ]
+MAX_FRAME_STREAMS = 256
 
 # voxel certainty map (map.hpp:9-13)
 MAP_HEIGHT = 300
@@ -99,6 +101,17 @@ class Pair(C.Structure):
         ("tx", C.POINTER(C.c_float)), ("ty", C.POINTER(C.c_float)), ("tz", C.POINTER(C.c_float)),
         ("nt", C.c_int32),
         ("idx_out", C.POINTER(C.c_int32)), ("dist_out", C.POINTER(C.c_float)),
+    ]
+
+
+class FrameJob(C.Structure):
+    """icpk_frame_job: one stream's next frame pair for icpk_align_frames_batch."""
+    _fields_ = [
+        ("stream", C.c_int32),
+        ("depth_source", C.POINTER(C.c_uint16)),
+        ("depth_target", C.POINTER(C.c_uint16)),
+        ("R", C.c_float * 9), ("t", C.c_float * 3),
+        ("last_rotation", C.c_float * 9), ("last_translation", C.c_float * 3),
     ]
 
 
@@ -189,6 +202,10 @@ def load():
                                               C.c_int32, C.c_int32] + [C.c_int32] * 5
     lib.icpk_backproject_pair.argtypes = [C.c_void_p, u16, u16, C.c_int32, C.c_int32, C.c_float, C.c_float, fp, fp, fp] + \
         [C.c_int32] * 6 + [C.POINTER(C.c_int32)] * 2
+    lib.icpk_align_frames_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(FrameJob), C.c_int32, C.c_int32, C.c_float,
+                                            C.c_float, fp] + [C.c_int32] * 6 + [C.POINTER(Params), fp, C.POINTER(Stats)]
+    lib.icpk_get_frames_trace.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), fp, fp, C.POINTER(C.c_int32), fp]
+    lib.icpk_release_frame_streams.argtypes = [C.c_void_p]
     lib.icpk_comm_unique_id.argtypes = [C.c_void_p]
     lib.icpk_comm_init_rccl.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     lib.icpk_comm_destroy.argtypes = [C.c_void_p]
@@ -453,13 +470,19 @@ class Context:
         self._chk(self._lib.icpk_transform_target(self._h, _fp(R), _fp(t)))
 
     def get_trace(self, max_iterations=64):
+        return self._trace(lambda *a: self._lib.icpk_get_trace(self._h, *a), max_iterations)
+
+    def get_frames_trace(self, job, max_iterations=64):
+        """get_trace of job `job` of the last align_frames_batch call."""
+        return self._trace(lambda *a: self._lib.icpk_get_frames_trace(self._h, int(job), *a), max_iterations)
+
+    def _trace(self, call, max_iterations):
         n = C.c_int32(0)
         R = np.zeros((max_iterations, 9), np.float32)
         t = np.zeros((max_iterations, 3), np.float32)
         pairs = np.zeros(max_iterations, np.int32)
         mse = np.zeros(max_iterations, np.float32)
-        self._chk(self._lib.icpk_get_trace(self._h, C.byref(n), _fp(R), _fp(t),
-                                           pairs.ctypes.data_as(C.POINTER(C.c_int32)), _fp(mse)))
+        self._chk(call(C.byref(n), _fp(R), _fp(t), pairs.ctypes.data_as(C.POINTER(C.c_int32)), _fp(mse)))
         k = n.value
         return [dict(R=R[i].reshape(3, 3).copy(), t=t[i].copy(), n_pairs=int(pairs[i]), mse=np.float32(mse[i]))
                 for i in range(k)]
@@ -539,6 +562,44 @@ class Context:
             None if Rm is None else _fp(Rm), None if tv is None else _fp(tv), int(bool(filter)), int(max_d), int(min_d),
             int(bool(morph)), int(anchor[0]), int(anchor[1]), C.byref(ns), C.byref(nt)))
         return ns.value, nt.value
+
+    def align_frames_batch(self, jobs, params=None, fx=468.60, cx=318.27, offset=None, filter=False, max_d=25000,
+                           min_d=1000, morph=True, anchor=(-1, -1), **kw):
+        """backproject_pair + align for many depth streams in lock step (icpk_align_frames_batch).  jobs: list of dicts
+        with stream, source (rows x cols uint16), target (same shape, or None: the stream's resident frame), R, t (the
+        camera pose), last_rotation, last_translation.  Returns (T (n, 4, 4), stats list, rc); a job that could not
+        run has its status in its stats."""
+        p = params if params is not None else default_params(**kw)
+        n = len(jobs)
+        arr = (FrameJob * max(n, 1))()
+        keep = []
+        shape = None
+        u16 = C.POINTER(C.c_uint16)
+        for k, j in enumerate(jobs):
+            ds = np.ascontiguousarray(j["source"], np.uint16)
+            dt = None if j.get("target") is None else np.ascontiguousarray(j["target"], np.uint16)
+            shape = shape or ds.shape
+            if ds.ndim != 2 or ds.shape != shape or (dt is not None and dt.shape != shape):
+                raise ValueError("depth images of one rows x cols shape expected")
+            keep.append((ds, dt))
+            arr[k].stream = int(j["stream"])
+            arr[k].depth_source = ds.ctypes.data_as(u16)
+            arr[k].depth_target = None if dt is None else dt.ctypes.data_as(u16)
+            for name, default in (("R", np.eye(3)), ("t", np.zeros(3)), ("last_rotation", np.eye(3)),
+                                  ("last_translation", np.zeros(3))):
+                v = j.get(name)
+                getattr(arr[k], name)[:] = [float(x) for x in _f(default if v is None else v).reshape(-1)]
+        rows, cols = shape if shape else (1, 1)
+        off = None if offset is None else _f(offset)
+        T = np.zeros((max(n, 1), 16), np.float32)
+        st = (Stats * max(n, 1))()
+        rc = self._lib.icpk_align_frames_batch(
+            self._h, n, arr, rows, cols, fx, cx, None if off is None else _fp(off), int(bool(filter)), int(max_d),
+            int(min_d), int(bool(morph)), int(anchor[0]), int(anchor[1]), C.byref(p), _fp(T), st)
+        return T[:n].reshape(n, 4, 4), list(st)[:n], rc
+
+    def release_frame_streams(self):
+        self._chk(self._lib.icpk_release_frame_streams(self._h))
 
     def associate_keypoints(self, max_dist=MAX_NN_KEYPOINT_DISTANCE, nn_mode=NN_GRID, rejected=None, capacity=None):
         """icp.cpp:488-515 on the context's clouds.  rejected: the caller's running list of rejected

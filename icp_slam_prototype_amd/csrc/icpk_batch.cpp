@@ -28,6 +28,10 @@ struct GroupRun {
   std::vector<int> rc;                // per pair: set-up status (< 0: failed, not in the loop)
 };
 
+}  // namespace
+
+namespace icpk {
+
 bool batch_eligible(const icpk_ctx* ctx, const icpk_params* p) {
   return p->nn_mode == ICPK_NN_GRID && !p->host_loop && !ctx->log_fn && p->profile <= 1 &&
          (p->solve == ICPK_SOLVE_REFERENCE || p->solve == ICPK_SOLVE_KABSCH) && p->max_iterations >= 0 &&
@@ -52,6 +56,10 @@ int ensure_slots(icpk_ctx* ctx, int n) {
   }
   return ICPK_OK;
 }
+
+}  // namespace icpk
+
+namespace {
 
 // uploads + everything up to (not including) the first host wait of the pair's set-up
 // device-resident pair into a slot: one launch per cloud (planes, padding and, for the source,
@@ -95,10 +103,14 @@ int slot_setup_phase1(icpk_ctx* sl, const icpk_pair& pr, hipMemcpyKind kind) {
   return ensure_assoc(sl, sl->src.n);
 }
 
+}  // namespace
+
+namespace icpk {
+
 // grid of the target (waits for its 36-byte info), query order, scan-order queries and seeds,
 // initial loop state: the slot is then ready for the group's first sweep
-int slot_setup_phase2(icpk_ctx* sl, const icpk_params* p, GridSweepArgs& first) {
-  int rc = device_loop_begin(sl, p);
+int slot_setup_phase2(icpk_ctx* sl, const icpk_params* p, GridSweepArgs& first, bool throttled) {
+  int rc = device_loop_begin(sl, p, throttled);
   if (rc) return rc;
   NnArgs a = base_nn_args(sl);
   NnBoxes bx{};
@@ -134,8 +146,30 @@ ReduceArgs slot_reduce_args(const icpk_ctx* sl) {
 }
 
 // the whole loop of a group on the parent's stream, then the read-back of every loop state
+// throttled: every slot's loop was begun throttled (its steps publish LoopState::progress); the iterations are enqueued
+// loop_ahead ahead of the slowest pair and no further once every pair has exited -- what align_device_loop does for
+// one pair.  Whatever would have followed is a no-op for every pair: same results either way.
+static int wait_group_progress(icpk_ctx* ctx, const std::vector<icpk_ctx*>& act, int steps, bool* all_exited) {
+  bool all = false;
+  const int rc = spin_until(ctx, [&] {
+    all = true;
+    for (const icpk_ctx* sl : act) {
+      const volatile int* pr = sl->progress;
+      const int e = sl->loop_epoch;
+      const int w0 = __atomic_load_n(&pr[0], __ATOMIC_ACQUIRE), w1 = pr[1];
+      const bool exited = (w1 >> 2) == e && (w1 & 1);
+      all = all && exited;
+      if (!exited && !((w0 >> 10) == e && (w0 & 1023) >= steps)) return false;
+    }
+    return true;
+  }, "frame-batch group loop made no progress");
+  *all_exited = all;
+  return rc;
+}
+
 int enqueue_group_loop(icpk_ctx* ctx, const icpk_params* p, const std::vector<icpk_ctx*>& act,
-                       const std::vector<GridSweepArgs>& first, int set, const std::vector<bool>& own_event) {
+                       const std::vector<GridSweepArgs>& first, int set, const std::vector<bool>& own_event,
+                       bool throttled) {
   const int n = (int)act.size();
   if (n == 0) return ICPK_OK;
   const int nsum = loop_nsum(p);
@@ -154,7 +188,7 @@ int enqueue_group_loop(icpk_ctx* ctx, const icpk_params* p, const std::vector<ic
   // lanes per query: a single pair is latency-bound and wants 8; a group that fills the GPU
   // several times over is issue-bound and does better with fewer, longer lanes (measured on
   // 8 config-2 pairs: 43.4k iter/s with 8, 50.6k with 4, 48.2k with 2)
-  const int slices = ctx->tune.grid_slices ? ctx->tune.grid_slices : (nq_total >= 300000 ? 4 : 8);
+  int slices = ctx->tune.grid_slices ? ctx->tune.grid_slices : (nq_total >= 300000 ? 4 : 8);
   GridSweepBatch gb{};
   ReduceBatch rb{};
   StepBatch sb{};
@@ -176,34 +210,74 @@ int enqueue_group_loop(icpk_ctx* ctx, const icpk_params* p, const std::vector<ic
     timed = ctx->profile_phase++ % (p->max_iterations + 1);
     ctx->batch_timed[set] = true;
   }
+  // the pairs still in the group's launches.  Throttled: a pair whose loop is done (its progress word says so) leaves
+  // them -- from then on its sweep, reduce and step would return before writing anything but the step counter, so
+  // results are the same; the launches of the group's slowest pairs stop paying for its finished ones' grids.
+  std::vector<int> live(n);
+  for (int k = 0; k < n; ++k) live[k] = k;
+  GridSweepBatch gl{};
+  ReduceBatch rl{};
+  StepBatch sl{};
+  // (lanes per query follow the pairs still launched: a lone slow pair is latency-bound again and wants 8; the
+  // lane count decides the speed of a sweep, not its result)
+  auto pack = [&]() {
+    long long nq_live = 0;
+    for (size_t j = 0; j < live.size(); ++j) {
+      gl.p[j] = gb.p[live[j]];
+      rl.p[j] = rb.p[live[j]];
+      sl.p[j] = sb.p[live[j]];
+      nq_live += act[live[j]]->src.n;
+    }
+    if (!ctx->tune.grid_slices) slices = nq_live >= 300000 ? 4 : 8;
+  };
   auto sweep = [&](int nth, int expand) -> int {
     if (nth == timed) ICPK_HIP(ctx, hipEventRecord(ctx->batch_t0[set], ctx->stream));
-    launch_nn_grid_batch(gb, n, slices, expand, ctx->stream);
+    launch_nn_grid_batch(throttled ? gl : gb, throttled ? (int)live.size() : n, slices, expand, ctx->stream);
     if (nth == timed) ICPK_HIP(ctx, hipEventRecord(ctx->batch_t1[set], ctx->stream));
     return ICPK_OK;
   };
+  if (throttled) pack();
   int src_ = sweep(0, 1);  // icp.cpp:98 (expanding search from element 0)
   if (src_) return src_;
-  launch_assoc_reduce_batch(rb, n, p->max_nn_dist, nact, ctx->stream);
+  launch_assoc_reduce_batch(throttled ? rl : rb, throttled ? (int)live.size() : n, p->max_nn_dist, nact, ctx->stream);
+  const int ahead = ctx->tune.loop_ahead;
   for (int i = 0; i < p->max_iterations; ++i) {
-    launch_loop_step_batch(sb, n, nsum, 0, ctx->stream);
-    for (int k = 0; k < n; ++k) {  // pointer rotation only: nothing is enqueued for a chained sweep
-      icpk_ctx* sl = act[k];
-      NnArgs a = base_nn_args(sl);
+    if (throttled && i >= ahead) {
+      bool all_exited = false;
+      const int rc = wait_group_progress(ctx, act, i - ahead + 1, &all_exited);
+      if (rc) return rc;
+      if (all_exited) break;  // (every launch from here on would find every pair done)
+      size_t w = 0;
+      for (const int k : live) {
+        const int w1 = ((const volatile int*)act[k]->progress)[1];
+        if (!((w1 >> 2) == act[k]->loop_epoch && (w1 & 2))) live[w++] = k;
+      }
+      live.resize(w);
+      if (live.empty()) break;  // (every pair finished between the wait and this look)
+      pack();
+    }
+    if (throttled)
+      launch_loop_step_batch(sl, (int)live.size(), nsum, 0, ctx->stream);
+    else
+      launch_loop_step_batch(sb, n, nsum, 0, ctx->stream);
+    for (const int k : live) {  // pointer rotation only: nothing is enqueued for a chained sweep
+      icpk_ctx* sl_k = act[k];
+      NnArgs a = base_nn_args(sl_k);
       NnBoxes bx{};
       int recheck = 0;
-      int rc = prepare_sorted_sweep(sl, ICPK_NN_GRID, a, bx, recheck);
+      int rc = prepare_sorted_sweep(sl_k, ICPK_NN_GRID, a, bx, recheck);
       if (rc) {
-        ctx->err = sl->err;
+        ctx->err = sl_k->err;
         return rc;
       }
-      gb.p[k] = grid_sweep_args(sl, a, bx);
-      after_grid_sweep(sl);
-      rb.p[k].best = sl->best;
+      gb.p[k] = grid_sweep_args(sl_k, a, bx);
+      after_grid_sweep(sl_k);
+      rb.p[k].best = sl_k->best;
     }
+    if (throttled) pack();
     src_ = sweep(i + 1, 0);  // icp.cpp:255, K3 fused
     if (src_) return src_;
-    launch_assoc_reduce_batch(rb, n, p->max_nn_dist, nact, ctx->stream);
+    launch_assoc_reduce_batch(throttled ? rl : rb, throttled ? (int)live.size() : n, p->max_nn_dist, nact, ctx->stream);
   }
   launch_loop_step_batch(sb, n, nsum, 1, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
@@ -220,6 +294,10 @@ int enqueue_group_loop(icpk_ctx* ctx, const icpk_params* p, const std::vector<ic
   ICPK_HIP(ctx, hipEventRecord(ctx->group_ev[set], ctx->stream));
   return ICPK_OK;
 }
+
+}  // namespace icpk
+
+namespace {
 
 int align_batch_impl(icpk_ctx* ctx, int32_t n_pairs, const icpk_pair* pairs, const icpk_params* p, float* T_out,
                      icpk_stats* stats, hipMemcpyKind kind) {
@@ -354,7 +432,7 @@ int align_batch_impl(icpk_ctx* ctx, int32_t n_pairs, const icpk_pair* pairs, con
         g.rc[k] = r < 0 ? r : 100 + r;
         return;
       }
-      r = slot_setup_phase2(sl, p, fargs[k]);
+      r = slot_setup_phase2(sl, p, fargs[k], false);
       if (r != ICPK_OK) device_loop_disarm(sl);
       g.rc[k] = r;
     };
@@ -429,7 +507,7 @@ int align_batch_impl(icpk_ctx* ctx, int32_t n_pairs, const icpk_pair* pairs, con
       own_event.push_back(!recorded[k]);
     }
     const auto t2 = now();
-    rc = enqueue_group_loop(ctx, p, act, first, g.set, own_event);
+    rc = enqueue_group_loop(ctx, p, act, first, g.set, own_event, false);
     if (rc) {  // enqueue failed: nothing of this group can be trusted (the previous group's results still are)
       for (icpk_ctx* sl : act) device_loop_disarm(sl);
       return bail(rc);

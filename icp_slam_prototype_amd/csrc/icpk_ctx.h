@@ -1,6 +1,7 @@
 // icpk_ctx.h -- the context object behind the opaque icpk_ctx of include/icpk.h and the host helpers more than one
 // host-side translation unit calls (icpk_api.cpp: context and clouds; icpk_sweep.cpp: NN sweeps and reductions;
-// icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frontend.cpp: depth images;
+// icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
+// entry; icpk_frontend.cpp: depth images;
 // icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -149,6 +150,22 @@ struct Tuning {
                                  //   early (0: enqueue every iteration up front)
 };
 
+// icpk_align_frames_batch: one depth stream's resident frame, kept by the parent context (slots rotate between the
+// two slot sets, a stream does not).  As icpk_backproject_pair's own: two image slots of rows x cols in raw and
+// filtered form, the new frame goes where the resident one is not.
+struct FrameStream {
+  DevBuf<uint16_t> raw, flt;
+  int slot = -1;  // -1: no resident frame
+  int rows = 0, cols = 0;
+  int filter[6] = {0, 0, 0, 0, 0, 0};  // settings the resident filtered copy was made with (as icpk_ctx::frame_filter)
+  unsigned long long sub_images = 0;   // images of this stream since icpk_set_subsample (its subsample keys)
+};
+// icpk_get_frames_trace's record of one job of the last icpk_align_frames_batch call
+struct FrameTrace {
+  std::vector<float> R, t, mse;
+  std::vector<int32_t> pairs;
+};
+
 }  // namespace icpk
 
 using icpk::nn_key_t;
@@ -257,6 +274,16 @@ struct icpk_ctx {
   icpk::DevBuf<LoopState> slot_states;          // parent: the loop states of all slots in one allocation (slot k at [k]),
   icpk::PinnedBuf<LoopState> slot_states_host;  //   so that a group's states come back with ONE copy; pinned mirror
   std::vector<nn_key_t*> best_of_sweep;  // device loop: which buffer each enqueued sweep wrote
+  // icpk_align_frames_batch (icpk_frames_batch.cpp), parent only: the streams' resident frames (ICPK_MAX_FRAME_STREAMS
+  // entries once used), the pinned staging of a group's new images, per slot set the block counts and the totals the
+  // scans publish (device and mapped), and the traces of the last call's jobs
+  std::vector<icpk::FrameStream> frame_streams;
+  icpk::PinnedBuf<uint16_t> fb_stage;
+  icpk::DevBuf<int> fb_counts[2];
+  icpk::DevBuf<int> fb_n_dev;
+  icpk::CoherentBuf<int> fb_n;  // 2 sets x 2 BATCH_MAX words
+  int* fb_n_mapped = nullptr;   // view: fb_n as the device addresses it
+  std::vector<icpk::FrameTrace> frames_trace;
   // RCCL communicator of the frame-batch / query-sharded modes (icpk_comm.cpp); null until
   // icpk_comm_init_rccl
   struct icpk_comm_state* comm = nullptr;
@@ -321,8 +348,9 @@ inline int hip_failure(icpk_ctx* ctx, const char* what, hipError_t e) {
 // now and then, and looks at the stream every 20 ms -- not more often: a stream query may itself put a marker into the
 // queue -- so that a faulted kernel ends the wait with an error instead of hanging the caller.  A stream that has
 // drained while done() still says no: `stalled`.
+// stream: the one whose work the words wait for (nullptr: ctx->stream)
 template <class Done>
-int spin_until(icpk_ctx* ctx, Done done, const char* stalled) {
+int spin_until(icpk_ctx* ctx, Done done, const char* stalled, hipStream_t stream = nullptr) {
   auto t_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
   for (unsigned spin = 1; !done(); ++spin) {
     __builtin_ia32_pause();
@@ -331,7 +359,7 @@ int spin_until(icpk_ctx* ctx, Done done, const char* stalled) {
     const auto now = std::chrono::steady_clock::now();
     if (now < t_query) continue;
     t_query = now + std::chrono::milliseconds(20);
-    const hipError_t q = hipStreamQuery(ctx->stream);
+    const hipError_t q = hipStreamQuery(stream ? stream : ctx->stream);
     if (q == hipSuccess) return done() ? ICPK_OK : fail(ctx, ICPK_E_HIP, stalled);  // (drained: the words are final)
     if (q != hipErrorNotReady) return fail(ctx, ICPK_E_HIP, hipGetErrorString(q));
   }
@@ -378,5 +406,15 @@ int device_loop_begin(icpk_ctx* ctx, const icpk_params* p, bool throttled = fals
 void device_loop_disarm(icpk_ctx* ctx);
 int device_loop_finish(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats* stats,
                        const LoopState* h = nullptr);
+
+// ---- icpk_batch.cpp: the lock-step machinery icpk_frames_batch.cpp shares ----
+bool batch_eligible(const icpk_ctx* ctx, const icpk_params* p);  // params the lock-step path runs
+int ensure_slots(icpk_ctx* ctx, int n);                           // n frame-batch slots (child contexts)
+// throttled: the slot's loop publishes its progress (device_loop_begin), for enqueue_group_loop's throttled mode
+int slot_setup_phase2(icpk_ctx* sl, const icpk_params* p, GridSweepArgs& first, bool throttled);
+// throttled: the group's iterations are enqueued a few ahead of the slowest pair and stop once all have exited
+int enqueue_group_loop(icpk_ctx* ctx, const icpk_params* p, const std::vector<icpk_ctx*>& act,
+                       const std::vector<GridSweepArgs>& first, int set, const std::vector<bool>& own_event,
+                       bool throttled);
 
 }  // namespace icpk

@@ -68,6 +68,7 @@ int icpk_set_subsample(icpk_ctx* ctx, int32_t factor, uint64_t seed) {
   ctx->sub_factor = factor;
   ctx->sub_seed = seed;
   ctx->sub_stream = 0;
+  for (icpk::FrameStream& fs : ctx->frame_streams) fs.sub_images = 0;  // (icpk_align_frames_batch: per stream)
   return ICPK_OK;
 }
 

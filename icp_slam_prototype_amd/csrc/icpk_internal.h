@@ -125,9 +125,11 @@ void launch_grid_tscatter(const float* x, const float* y, const float* z, const 
 void launch_grid_qslot(const float* x, const float* y, const float* z, int n, const GridInfo* g, int* count, int* qcell,
                        int* qslot, int coarse, hipStream_t s);
 // qm4 != nullptr: also the scan-order queries, element 0 as every query's seed point and seed key
+// spix / tidx / rows / cols: pixel seeds (QscatterArgs) or nullptr
 void launch_grid_qscatter(const int* qcell, const int* qslot, const int* qstart, int n, int* qperm, const float* qx,
                           const float* qy, const float* qz, const float* ox, const float* oy, const float* oz,
-                          float4* qm4, float4* sp, nn_key_t* seed_m, hipStream_t s);
+                          float4* qm4, float4* sp, nn_key_t* seed_m, hipStream_t s, const int* spix = nullptr,
+                          const int* tidx = nullptr, int rows = 0, int cols = 0);
 constexpr int GRID_SCAN_BLOCKS = (GRID_MAX_CELLS + 1 + 2047) / 2048 + 1;  // scratch ints of launch_grid_scan
 void launch_grid_scan(int* count, int* out, int* bsum, const GridInfo* g, int coarse, hipStream_t s);  // count[] left zero
 // one pair's arguments of a grid sweep (K1d); see nn_grid_body
@@ -302,6 +304,27 @@ struct BpPair {
 };
 void launch_backproject_pair(const BpPair& b, int rows, int cols, float fx, float cx, float ox, float oy, float oz,
                              const Rt& rt, int posed, int* n_out, int* n_host, hipStream_t s);
+// icpk_align_frames_batch: the frame pairs of a lock-step group (one per job, at most BATCH_MAX), both images of each
+// in ONE launch per pass (blockIdx.y = 2 x pair + image).  Image 0 (source) goes to the slot's src0 and src planes
+// and records pixel_of_point in pix_src; image 1 (target) goes to tgt and records point_of_pixel in pix_tidx.  The
+// per-image fields are those of BpImage; counts: image 0 at counts, image 1 at counts + per_image.
+struct BpFramePair {
+  const uint16_t* depth[2];
+  const uint16_t* host_src[2];
+  uint16_t* raw_out[2];
+  float *src0, *src, *tgt;  // plane bases (x; y at + cap; z at + 2 cap)
+  int src0_cap, src_cap, tgt_cap, sub_factor;
+  int* counts;
+  int *pix_src, *pix_tidx;
+  unsigned long long sub_key[2];
+  Rt rt;  // the pose of both clouds (always applied)
+};
+struct BpFrameBatch {
+  BpFramePair p[BATCH_MAX];
+};
+// n_out: 2 x count ints (device), n_host: 2 x count mapped words (image 2 k + i's total at [2 k + i])
+void launch_backproject_frames(const BpFrameBatch& b, int count, int rows, int cols, float fx, float cx, float ox,
+                               float oy, float oz, int* n_out, int* n_host, hipStream_t s);
 
 // kernels_frontend.hip
 // order-preserving split of a sweep's result into accepted pairs and rejected queries
@@ -311,6 +334,13 @@ void launch_assoc_split(const nn_key_t* best, int nq, float max_dist, int* block
 // SLAM.cpp:553-574: range clamp, then (morph != 0) 5x5 dilate + erode with anchor (ax, ay)
 void launch_depth_filter(const uint16_t* in, uint16_t* out, int rows, int cols, int min_d, int max_d, int ax, int ay,
                          int morph, hipStream_t s);
+// the same filter over `count` images of one size in ONE launch (blockIdx.z = image)
+struct DfBatch {
+  const uint16_t* in[2 * BATCH_MAX];
+  uint16_t* out[2 * BATCH_MAX];
+};
+void launch_depth_filter_batch(const DfBatch& b, int count, int rows, int cols, int min_d, int max_d, int ax, int ay,
+                               int morph, hipStream_t s);
 
 
 // ---- deferred set-up launches of the frame-batch mode ------------------------------------------------

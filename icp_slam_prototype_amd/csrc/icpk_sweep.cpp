@@ -181,13 +181,21 @@ static int enqueue_cell_order(icpk_ctx* ctx, bool with_points) {
   if (rc) return rc;
   int* qcell = reinterpret_cast<int*>(ctx->sort_keys + ctx->sort_cap);
   int* qslot = ctx->sort_vals;
-  // (locality only: the coarser table, xdiv times fewer counts to scan)
-  ctx->qcount_dirty = true;
-  launch_grid_qslot(ctx->src.x(), ctx->src.y(), ctx->src.z(), nq, ctx->grid_info, ctx->qcount, qcell, qslot, 1,
-                    ctx->stream);
-  launch_grid_scan(ctx->qcount, ctx->qstart, ctx->scan_bsum, ctx->grid_info, 1, ctx->stream);
-  launch_grid_qscatter(qcell, qslot, ctx->qstart, nq, ctx->qperm, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->tgt.x(),
-                       ctx->tgt.y(), ctx->tgt.z(), with_points ? ctx->qm4 : nullptr, ctx->sp_in, ctx->seed_m, ctx->stream);
+  // a source in image order with pixel maps (icpk_backproject_pair, icpk_align_frames_batch's slots): as in
+  // build_grid_and_order, the queries keep the caller's order (no counting sort) and get pixel seeds
+  const bool ident = ctx->have_pix_seed && ctx->tune.image_order;
+  const bool pix = ctx->have_pix_seed && ctx->tune.pixel_seeds && with_points;
+  if (!ident) {
+    // (locality only: the coarser table, xdiv times fewer counts to scan)
+    ctx->qcount_dirty = true;
+    launch_grid_qslot(ctx->src.x(), ctx->src.y(), ctx->src.z(), nq, ctx->grid_info, ctx->qcount, qcell, qslot, 1,
+                      ctx->stream);
+    launch_grid_scan(ctx->qcount, ctx->qstart, ctx->scan_bsum, ctx->grid_info, 1, ctx->stream);
+  }
+  launch_grid_qscatter(ident ? nullptr : qcell, qslot, ctx->qstart, nq, ctx->qperm, ctx->src.x(), ctx->src.y(),
+                       ctx->src.z(), ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), with_points ? ctx->qm4 : nullptr,
+                       ctx->sp_in, ctx->seed_m, ctx->stream, pix ? ctx->pix_src.get() : nullptr,
+                       pix ? ctx->pix_tidx.get() : nullptr, ctx->pix_rows, ctx->pix_cols);
   ICPK_HIP(ctx, hipGetLastError());
   ctx->qcount_dirty = false;
   return ICPK_OK;

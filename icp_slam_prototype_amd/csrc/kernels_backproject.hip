@@ -113,10 +113,17 @@ __global__ void bp_scan_kernel(int* __restrict__ block_counts, int nblocks, int*
 
 // n_host: pinned, mapped words the host spins on (icpk_backproject_pair returns as soon as both totals are known,
 // while the scatter still runs) or nullptr
-__global__ void bp_scan_pair_kernel(const BpPair b, int nblocks, int* __restrict__ n_out, int* __restrict__ n_host) {
-  bp_scan_body(b.im[blockIdx.x].counts, nblocks, n_out + blockIdx.x);
+// one workgroup per image (blockIdx.x): the scan of its counts, the total to n_out[blockIdx.x] and (n_host != nullptr)
+// to the mapped word n_host[blockIdx.x]
+__device__ __forceinline__ void bp_scan_publish_body(const BpImage& im, int nblocks, int* __restrict__ n_out,
+                                                     int* __restrict__ n_host) {
+  bp_scan_body(im.counts, nblocks, n_out + blockIdx.x);
   if (n_host && threadIdx.x == 0)  // (the thread that wrote the total)
-    __hip_atomic_store(n_host + blockIdx.x, b.im[blockIdx.x].counts[nblocks], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(n_host + blockIdx.x, im.counts[nblocks], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__global__ void bp_scan_pair_kernel(const BpPair b, int nblocks, int* __restrict__ n_out, int* __restrict__ n_host) {
+  bp_scan_publish_body(b.im[blockIdx.x], nblocks, n_out, n_host);
 }
 
 // Surface normal of pixel (r, c) -- point-to-plane extension (not in the reference,
@@ -217,10 +224,9 @@ __global__ __launch_bounds__(BP_THREADS) void bp_scatter_kernel(const uint16_t* 
 // written to its pristine and its working copy at once, and every plane padded up to the next multiple of
 // NN_TILE (workgroup 0 of each image: the total is on the device by now).  Replaces, bit for bit,
 // icpk_backproject x 2 + icpk_transform_target / _source + icpk_commit_source: 3 launches instead of 25.
-__global__ __launch_bounds__(BP_THREADS) void bp_scatter_pair_kernel(const BpPair b, int npix, int cols, int nblocks,
-                                                                     float fx, float cx, float ox, float oy, float oz,
-                                                                     const Rt rt, int posed) {
-  const BpImage& im = b.im[blockIdx.y];
+__device__ __forceinline__ void bp_scatter_posed_body(const BpImage& im, int npix, int cols, int nblocks,
+                                                      float fx, float cx, float ox, float oy, float oz, const Rt rt,
+                                                      int posed) {
   const uint16_t* __restrict__ depth = im.depth;
   float* __restrict__ x = im.x;
   float* __restrict__ y = im.y;
@@ -285,6 +291,69 @@ __global__ __launch_bounds__(BP_THREADS) void bp_scatter_pair_kernel(const BpPai
       if (x2) x2[i] = y2[i] = z2[i] = im.pad;
     }
   }
+}
+
+__global__ __launch_bounds__(BP_THREADS) void bp_scatter_pair_kernel(const BpPair b, int npix, int cols, int nblocks,
+                                                                     float fx, float cx, float ox, float oy, float oz,
+                                                                     const Rt rt, int posed) {
+  bp_scatter_posed_body(b.im[blockIdx.y], npix, cols, nblocks, fx, cx, ox, oy, oz, rt, posed);
+}
+
+// ---- frame-batch entry (icpk_align_frames_batch): the pairs of a lock-step group, image y & 1 of pair y >> 1 -------
+// Same bodies as the pair entry above: the same points, maps, padding and totals per image.
+// (fields picked by selects, never by a run-time index into the kernel-argument arrays: that would copy them to scratch)
+__device__ __forceinline__ BpImage bp_frame_image(const BpFramePair& f, const int which, int per_image) {
+  const bool tgt = which != 0;
+  BpImage im{};
+  im.depth = tgt ? f.depth[1] : f.depth[0];
+  im.host_src = tgt ? f.host_src[1] : f.host_src[0];
+  im.raw_out = tgt ? f.raw_out[1] : f.raw_out[0];
+  im.sub_key = tgt ? f.sub_key[1] : f.sub_key[0];
+  im.sub_factor = f.sub_factor;
+  float* const base = tgt ? f.tgt : f.src0;
+  const int cap = tgt ? f.tgt_cap : f.src0_cap;
+  im.x = base;
+  im.y = base + cap;
+  im.z = base + 2 * (size_t)cap;
+  im.x2 = tgt ? nullptr : f.src;
+  im.y2 = tgt ? nullptr : f.src + f.src_cap;
+  im.z2 = tgt ? nullptr : f.src + 2 * (size_t)f.src_cap;
+  im.counts = tgt ? f.counts + per_image : f.counts;
+  im.pad = tgt ? __builtin_inff() : 0.f;
+  im.pixel_of_point = tgt ? nullptr : f.pix_src;
+  im.point_of_pixel = tgt ? f.pix_tidx : nullptr;
+  return im;
+}
+
+__global__ __launch_bounds__(BP_THREADS) void bp_count_frames_kernel(const BpFrameBatch b, int npix, int per_image) {
+  const BpImage im = bp_frame_image(b.p[blockIdx.y >> 1], blockIdx.y & 1, per_image);
+  bp_count_body(im.depth, npix, im.counts, blockIdx.x, im.host_src, im.raw_out, im.sub_key, im.sub_factor);
+}
+
+__global__ void bp_scan_frames_kernel(const BpFrameBatch b, int nblocks, int per_image, int* __restrict__ n_out,
+                                      int* __restrict__ n_host) {
+  const BpImage im = bp_frame_image(b.p[blockIdx.x >> 1], blockIdx.x & 1, per_image);
+  bp_scan_publish_body(im, nblocks, n_out, n_host);
+}
+
+__global__ __launch_bounds__(BP_THREADS) void bp_scatter_frames_kernel(const BpFrameBatch b, int npix, int cols,
+                                                                       int nblocks, int per_image, float fx, float cx,
+                                                                       float ox, float oy, float oz) {
+  const BpFramePair& f = b.p[blockIdx.y >> 1];
+  const BpImage im = bp_frame_image(f, blockIdx.y & 1, per_image);
+  bp_scatter_posed_body(im, npix, cols, nblocks, fx, cx, ox, oy, oz, f.rt, 1);
+}
+
+void launch_backproject_frames(const BpFrameBatch& b, int count, int rows, int cols, float fx, float cx, float ox,
+                               float oy, float oz, int* n_out, int* n_host, hipStream_t s) {
+  if (count <= 0) return;
+  const int npix = rows * cols;
+  const int nblocks = (npix + BP_BLOCK - 1) / BP_BLOCK;
+  const int per_image = nblocks + 2;  // (icpk_backproject_pair's spacing of the two images' counts)
+  hipLaunchKernelGGL(bp_count_frames_kernel, dim3(nblocks, 2 * count), dim3(BP_THREADS), 0, s, b, npix, per_image);
+  hipLaunchKernelGGL(bp_scan_frames_kernel, dim3(2 * count), dim3(256), 0, s, b, nblocks, per_image, n_out, n_host);
+  hipLaunchKernelGGL(bp_scatter_frames_kernel, dim3(nblocks, 2 * count), dim3(BP_THREADS), 0, s, b, npix, cols, nblocks,
+                     per_image, fx, cx, ox, oy, oz);
 }
 
 void launch_backproject_pair(const BpPair& b, int rows, int cols, float fx, float cx, float ox, float oy, float oz,

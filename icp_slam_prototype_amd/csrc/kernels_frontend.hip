@@ -134,14 +134,14 @@ __device__ __forceinline__ unsigned df_clamp(unsigned d, unsigned min_d, unsigne
   return (d > max_d || d < min_d) ? 0u : d;  // SLAM.cpp:558-566
 }
 
-__global__ __launch_bounds__(256) void depth_filter_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
-                                                           int rows, int cols, unsigned min_d, unsigned max_d, int ax,
-                                                           int ay, int morph) {
+__device__ __forceinline__ void depth_filter_body(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, int rows,
+                                                  int cols, unsigned min_d, unsigned max_d, int ax, int ay, int morph,
+                                                  const int bx, const int by) {
   __shared__ uint16_t A[DF_IH][DF_IW];   // clamped input
   __shared__ uint16_t B[DF_IH][DF_DW];   // horizontal max
   __shared__ uint16_t C[DF_DH][DF_DW];   // dilated
   __shared__ uint16_t D[DF_DH][DF_TW];   // horizontal min
-  const int x0 = blockIdx.x * DF_TW, y0 = blockIdx.y * DF_TH;
+  const int x0 = bx * DF_TW, y0 = by * DF_TH;
   const int t = threadIdx.x;
   if (!morph) {
     for (int p = t; p < DF_TW * DF_TH; p += 256) {
@@ -196,13 +196,39 @@ __global__ __launch_bounds__(256) void depth_filter_kernel(const uint16_t* __res
   }
 }
 
+__global__ __launch_bounds__(256) void depth_filter_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
+                                                           int rows, int cols, unsigned min_d, unsigned max_d, int ax,
+                                                           int ay, int morph) {
+  depth_filter_body(in, out, rows, cols, min_d, max_d, ax, ay, morph, blockIdx.x, blockIdx.y);
+}
+
+// icpk_align_frames_batch: the images of a lock-step group in one launch (blockIdx.z = image)
+__global__ __launch_bounds__(256) void depth_filter_batch_kernel(const DfBatch b, int rows, int cols, unsigned min_d,
+                                                                 unsigned max_d, int ax, int ay, int morph) {
+  depth_filter_body(b.in[blockIdx.z], b.out[blockIdx.z], rows, cols, min_d, max_d, ax, ay, morph, blockIdx.x, blockIdx.y);
+}
+
+static void df_range(int min_d, int max_d, unsigned& lo, unsigned& hi) {
+  lo = min_d < 0 ? 0u : (unsigned)min_d;
+  hi = max_d > 65535 ? 65535u : (max_d < 0 ? 0u : (unsigned)max_d);
+}
+
 void launch_depth_filter(const uint16_t* in, uint16_t* out, int rows, int cols, int min_d, int max_d, int ax, int ay,
                          int morph, hipStream_t s) {
   if (rows <= 0 || cols <= 0) return;
-  const unsigned lo = min_d < 0 ? 0u : (unsigned)min_d;
-  const unsigned hi = max_d > 65535 ? 65535u : (max_d < 0 ? 0u : (unsigned)max_d);
+  unsigned lo, hi;
+  df_range(min_d, max_d, lo, hi);
   hipLaunchKernelGGL(depth_filter_kernel, dim3((cols + DF_TW - 1) / DF_TW, (rows + DF_TH - 1) / DF_TH), dim3(256), 0, s,
                      in, out, rows, cols, lo, hi, ax, ay, morph);
+}
+
+void launch_depth_filter_batch(const DfBatch& b, int count, int rows, int cols, int min_d, int max_d, int ax, int ay,
+                               int morph, hipStream_t s) {
+  if (rows <= 0 || cols <= 0 || count <= 0) return;
+  unsigned lo, hi;
+  df_range(min_d, max_d, lo, hi);
+  hipLaunchKernelGGL(depth_filter_batch_kernel, dim3((cols + DF_TW - 1) / DF_TW, (rows + DF_TH - 1) / DF_TH, count),
+                     dim3(256), 0, s, b, rows, cols, lo, hi, ax, ay, morph);
 }
 
 }  // namespace icpk

@@ -435,9 +435,10 @@ void launch_grid_qslot_batch(const SetupBatchOf<QslotArgs>& b, int count, hipStr
 }
 void launch_grid_qscatter(const int* qcell, const int* qslot, const int* qstart, int n, int* qperm, const float* qx,
                           const float* qy, const float* qz, const float* ox, const float* oy, const float* oz,
-                          float4* qm4, float4* sp, nn_key_t* seed_m, hipStream_t s) {
+                          float4* qm4, float4* sp, nn_key_t* seed_m, hipStream_t s, const int* spix, const int* tidx,
+                          int rows, int cols) {
   if (n <= 0) return;
-  const QscatterArgs a{qcell, qslot, qstart, qperm, qx, qy, qz, ox, oy, oz, qm4, sp, seed_m, n, 0, nullptr, nullptr, 0, 0};
+  const QscatterArgs a{qcell, qslot, qstart, qperm, qx, qy, qz, ox, oy, oz, qm4, sp, seed_m, n, 0, spix, tidx, rows, cols};
   ICPK_RECORD(SK_QSCATTER, qscatter, a)
   hipLaunchKernelGGL(grid_qscatter_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
 }

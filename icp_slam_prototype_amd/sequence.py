@@ -122,7 +122,11 @@ class SequenceRunner:
         # starting point of the alignment (one call: icpk_backproject_pair)
         c.backproject_pair(depth, self.previous, R=self.camera_rotation, t=self.camera_position, fx=self.fx, cx=self.cx)
         T, st, rc = c.align(last_rotation=self.last_rotation, last_translation=self.last_translation, **self.kw)
-        for it in c.get_trace(max(self.kw["max_iterations"], 1)):
+        return self._advance(depth, T, st, rc, c.get_trace(max(self.kw["max_iterations"], 1)), timestamp, ground_truth)
+
+    def _advance(self, depth, T, st, rc, trace, timestamp, ground_truth):
+        """The bookkeeping after one alignment (icp.cpp:235-261, SLAM.cpp:283-327): the per-frame result."""
+        for it in trace:
             self.camera_rotation = _mul3f(self.camera_rotation, _inv3f(it["R"]))   # icp.cpp:235-237
             self.camera_position = (self.camera_position - it["t"]).astype(np.float32)  # icp.cpp:246
         self.last_translation = (-T[:3, 3]).astype(np.float32)                    # icp.cpp:260
@@ -139,3 +143,58 @@ class SequenceRunner:
         vals = [st.final_mse, *icp_euler, *gt_euler]
         return dict(mse=np.float32(st.final_mse), icp_euler=icp_euler, gt_euler=gt_euler, T=T, status=rc,
                     iterations=st.iterations, csv=",".join("%g" % float(v) for v in vals))
+
+
+class MultiSequenceRunner:
+    """N independent depth sequences advanced together: one align_frames_batch call per step for the streams that
+    have a frame (icpk_align_frames_batch), each stream's previous frame resident on the device.  Stream k's results,
+    CSV rows included, are those of a SequenceRunner fed the same frames."""
+
+    def __init__(self, ctx, n_streams, max_iterations=16, threshold=1e-4, fx=468.60, cx=318.27, **params):
+        if not 0 < n_streams <= binding.MAX_FRAME_STREAMS:
+            raise ValueError(f"1 .. {binding.MAX_FRAME_STREAMS} streams")
+        self.ctx = ctx
+        self.runners = [SequenceRunner(None, max_iterations, threshold, fx, cx, **params) for _ in range(n_streams)]
+        self.kw = self.runners[0].kw
+        self.fx, self.cx = fx, cx
+        self.resident = [False] * n_streams  # the stream's previous frame is on the device
+
+    def step(self, frames, timestamps=None, ground_truths=None):
+        """frames: {stream: depth}.  Returns {stream: what SequenceRunner.step returns}.  If some streams' jobs fail,
+        raises binding.IcpkError with .results (the streams that did advance) and .failed ({stream: status}); a failed
+        stream's next frame pairs with its last good one, as SequenceRunner's would."""
+        timestamps = timestamps or {}
+        ground_truths = ground_truths or {}
+        out, jobs, order = {}, [], []
+        for k, depth in frames.items():
+            r = self.runners[k]
+            depth = np.ascontiguousarray(depth, np.uint16)
+            if r.previous is None:
+                out[k] = r.step(depth, timestamps.get(k), ground_truths.get(k))
+                continue
+            jobs.append(dict(stream=k, source=depth, target=None if self.resident[k] else r.previous,
+                             R=r.camera_rotation, t=r.camera_position, last_rotation=r.last_rotation,
+                             last_translation=r.last_translation))
+            order.append((k, depth))
+        if jobs:
+            T, st, rc = self.ctx.align_frames_batch(jobs, fx=self.fx, cx=self.cx, **self.kw)
+            failed = []
+            for j, (k, depth) in enumerate(order):
+                s = st[j]
+                if s.status < 0:
+                    # (as SequenceRunner, whose align raises: the stream's next frame pairs with its last good one)
+                    self.resident[k] = False
+                    failed.append((k, s.status))
+                    continue
+                self.resident[k] = True
+                trace = self.ctx.get_frames_trace(j, max(self.kw["max_iterations"], 1))
+                out[k] = self.runners[k]._advance(depth, T[j], s, s.status, trace, timestamps.get(k),
+                                                  ground_truths.get(k))
+            if failed:
+                # the other streams have been advanced: their results travel with the error (e.results), as
+                # e.failed = {stream: status} names the streams that were not
+                e = binding.IcpkError(failed[0][1], f"streams {[k for k, _ in failed]}: "
+                                      + self.ctx._lib.icpk_last_error(self.ctx._h).decode())
+                e.results, e.failed = out, dict(failed)
+                raise e
+        return out

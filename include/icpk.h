@@ -357,6 +357,43 @@ int icpk_backproject_pair(icpk_ctx *ctx, const uint16_t *depth_source, const uin
                           int32_t morph, int32_t anchor_x, int32_t anchor_y, int32_t *n_source,
                           int32_t *n_target);
 
+/* ---- many depth streams in lock step: icpk_backproject_pair + icpk_align for N independent streams ---------------
+ * One job = one stream's next frame pair (icp.cpp:38-71 then :98-268).  Job k's T_out[16 k ..], stats[k] and
+ * icpk_get_frames_trace(ctx, k, ...) equal, bit for bit, what icpk_backproject_pair(depth_source, depth_target, rows,
+ * cols, fx, cx, offset, R, t, filter, max_d ... anchor_y) followed by icpk_align with *p -- last_rotation /
+ * last_translation taken from the job -- return on a context whose resident frame is the stream's previous frame.
+ * The jobs advance ICPK_BATCH_GROUP (at most 16) at a time: one launch per stage for the whole group, back-projection
+ * included (as icpk_align_batch).
+ *   - stream: 0 <= stream < ICPK_MAX_FRAME_STREAMS, distinct within a call (else ICPK_E_ARG, nothing runs).  Every
+ *     stream named in a call keeps its depth_source (and its filtered copy) on the device as its new resident frame;
+ *     streams not named, the context's own clouds and its icpk_backproject_pair frame are not touched.
+ *   - depth_target == NULL: the stream's resident frame.  A job whose stream has none of this rows x cols gets
+ *     stats[k].status = ICPK_E_NOT_SET and does not stop the others.
+ *   - p: ICPK_NN_GRID, the device-side loop (host_loop = 0), reference or Kabsch flavour, no log callback: anything
+ *     else is ICPK_E_ARG (there is no one-by-one fallback).
+ *   - the depth buffers are host memory and may be reused as soon as the call returns.
+ *   - icpk_set_subsample: stream s draws its patterns as a context of its own would that had the same
+ *     icpk_set_subsample and made only this stream's icpk_backproject_pair calls -- the image counter k of the key
+ *     counts this stream's images (source, then target, per job) since icpk_set_subsample.
+ * Returns the first negative job status, else the largest. */
+#define ICPK_MAX_FRAME_STREAMS 256
+typedef struct icpk_frame_job {
+  int32_t stream;
+  const uint16_t *depth_source;  /* current frame (host)                                          */
+  const uint16_t *depth_target;  /* previous frame (host), or NULL: the stream's resident frame   */
+  float R[9], t[3];              /* camera pose applied to both clouds (icp.cpp:58-59, 70-71)     */
+  float last_rotation[9], last_translation[3]; /* this stream's icpk_params fields (icp.cpp:23-25, 176-177) */
+} icpk_frame_job;
+int icpk_align_frames_batch(icpk_ctx *ctx, int32_t n_jobs, const icpk_frame_job *jobs, int32_t rows,
+                            int32_t cols, float fx, float cx, const float offset[3], int32_t filter,
+                            int32_t max_d, int32_t min_d, int32_t morph, int32_t anchor_x, int32_t anchor_y,
+                            const icpk_params *p, float *T_out /* 16 x n_jobs */, icpk_stats *stats /* n_jobs or NULL */);
+/* icpk_get_trace of job `job` of the last icpk_align_frames_batch call (ICPK_E_ARG outside it) */
+int icpk_get_frames_trace(icpk_ctx *ctx, int32_t job, int32_t *n_iter, float *R_out, float *t_out,
+                          int32_t *pairs_out, float *mse_out);
+/* frees every stream's resident images (the next job of any stream must pass depth_target) */
+int icpk_release_frame_streams(icpk_ctx *ctx);
+
 /* ---- voxel certainty map: map::Map (map.hpp, map.cpp) on the device ------- */
 /* One map per context, allocated on first use: a 300^3 uint8 certainty grid (`world`, map.hpp:25; 27 MB) and an int32
  * slot per voxel (`pointLookupTable`, map.hpp:24; 108 MB) that holds (list index << 1) | list of the point that filled

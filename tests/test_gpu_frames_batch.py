@@ -1,0 +1,310 @@
+"""icpk_align_frames_batch against its definition: for every job, icpk_backproject_pair + icpk_align on one context
+driven pair by pair (the previous frame passed explicitly), with the per-stream pose bookkeeping of SequenceRunner --
+T, statistics (final_mse bits included) and traces bit for bit."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from icp_slam_prototype_amd import binding, sequence, synth
+
+pytestmark = pytest.mark.gpu
+
+THRESHOLD = dict(max_iterations=16, threshold=1e-4)
+FIXED = dict(max_iterations=5, fixed_iterations=1)
+FILTER = dict(max_d=25000, min_d=1000, morph=True, anchor=(-1, -1))
+
+
+def make_streams(n, steps, rows, cols, seed=0):
+    """n synthetic room sequences: own trajectory, noise seed and validity mask per stream."""
+    fx = np.float32(synth.FX * cols / 640.0)
+    cx = np.float32(synth.CX * cols / 640.0)
+    out = []
+    for s in range(n):
+        rng = np.random.default_rng(1000 * seed + s)
+        valid = 0.3 + 0.5 * ((s * 7) % 5) / 4.0
+        frames = []
+        for k in range(steps + 1):
+            d = synth.render_room_depth(rows, cols, synth.rot_xyz_deg(0.1 * s, 0.5 * k + 0.2 * s, 0.1 * k),
+                                        np.array([0.01 * k + 0.02 * s, 0.003 * k * (s % 3), 0.004 * k]), fx, cx,
+                                        noise_sigma=0.002, rng=rng)
+            d[rng.random(d.shape) > valid] = 0
+            d[::11, ::7] = 30000 if (k + s) % 2 else 300  # outside the filter's range: matters only when filtered
+            frames.append(d.astype(np.uint16))
+        out.append(frames)
+    return out, float(fx), float(cx)
+
+
+class State:
+    """One stream's tracker state (icp.cpp:22-26), advanced as SequenceRunner does."""
+
+    def __init__(self):
+        self.r = sequence.SequenceRunner(None)
+        self.previous = None
+
+    def job(self, stream, depth, explicit):
+        return dict(stream=stream, source=depth, target=self.previous if explicit else None, R=self.r.camera_rotation,
+                    t=self.r.camera_position, last_rotation=self.r.last_rotation, last_translation=self.r.last_translation)
+
+    def advance(self, depth, T, st, trace):
+        if st.status >= 0:
+            self.r._advance(depth, T, st, st.status, trace, None, None)
+        self.previous = depth
+
+
+def ref_step(ctx, state, depth, fx, cx, filt, par):
+    """The definition: backproject_pair (previous frame explicit) + align, raw statuses."""
+    lib = ctx._lib
+    u16 = C.POINTER(C.c_uint16)
+    R, t = binding._f(state.r.camera_rotation), binding._f(state.r.camera_position)
+    rc = lib.icpk_backproject_pair(ctx._h, depth.ctypes.data_as(u16), state.previous.ctypes.data_as(u16), depth.shape[0],
+                                   depth.shape[1], fx, cx, None, binding._fp(R), binding._fp(t), int(filt), 25000, 1000, 1,
+                                   -1, -1, None, None)
+    assert rc == 0, ctx._lib.icpk_last_error(ctx._h)
+    p = binding.default_params(last_rotation=state.r.last_rotation, last_translation=state.r.last_translation, **par)
+    T = np.zeros(16, np.float32)
+    st = binding.Stats()
+    lib.icpk_align(ctx._h, C.byref(p), binding._fp(T), C.byref(st))
+    return T.reshape(4, 4), st, ctx.get_trace(par["max_iterations"] + 1)
+
+
+def same_result(a, b, what):
+    (Ta, sa, ta), (Tb, sb, tb) = a, b
+    assert np.array_equal(Ta.view(np.uint32), Tb.view(np.uint32)), f"{what}: T differs\n{Ta}\n{Tb}"
+    assert (sa.iterations, sa.status, sa.final_pairs) == (sb.iterations, sb.status, sb.final_pairs), what
+    assert np.float32(sa.final_mse).view(np.uint32) == np.float32(sb.final_mse).view(np.uint32), what
+    if sa.status < 0:  # (a failed alignment leaves no trace of its own)
+        return
+    assert len(ta) == len(tb), what
+    for x, y in zip(ta, tb):
+        assert np.array_equal(x["R"].view(np.uint32), y["R"].view(np.uint32)), what
+        assert np.array_equal(x["t"].view(np.uint32), y["t"].view(np.uint32)), what
+        assert x["n_pairs"] == y["n_pairs"] and x["mse"].view(np.uint32) == y["mse"].view(np.uint32), what
+
+
+def run_case(streams, fx, cx, filt, par, explicit, subsets=None, hook=None):
+    """Drives both sides step by step; returns the number of compared jobs."""
+    n, steps = len(streams), len(streams[0]) - 1
+    with binding.Context(0) as ctx, binding.Context(0) as ref:
+        sb = [State() for _ in range(n)]
+        sr = [State() for _ in range(n)]
+        for s in range(n):
+            sb[s].previous = sr[s].previous = streams[s][0]
+        compared = 0
+        first = [True] * n
+        for k in range(1, steps + 1):
+            active = subsets(k) if subsets else range(n)
+            jobs = [sb[s].job(s, streams[s][k], explicit or first[s]) for s in active]
+            flt = FILTER if filt else {}
+            T, st, rc = ctx.align_frames_batch(jobs, fx=fx, cx=cx, filter=filt, **flt, **par)
+            assert rc != binding.E_ARG and rc != binding.E_HIP, (rc, ctx._lib.icpk_last_error(ctx._h))
+            assert rc == (min(s.status for s in st) if min(s.status for s in st) < 0 else max(s.status for s in st))
+            for j, s in enumerate(active):
+                got = (T[j], st[j], ctx.get_frames_trace(j, par["max_iterations"] + 1))
+                want = ref_step(ref, sr[s], streams[s][k], fx, cx, filt, par)
+                same_result(got, want, f"step {k} stream {s}")
+                sb[s].advance(streams[s][k], *got)
+                sr[s].advance(streams[s][k], *want)
+                first[s] = False
+                compared += 1
+            if hook:
+                hook(ctx, k)
+        return compared
+
+
+CASES = [  # n streams, rows, cols, filter, params, explicit previous frames, environment of the batch context
+    (1, 96, 128, False, THRESHOLD, False, {}),
+    (5, 96, 128, True, THRESHOLD, False, {}),
+    (5, 96, 128, True, FIXED, True, {}),
+    (16, 480, 640, False, THRESHOLD, False, {}),
+    (20, 480, 640, True, THRESHOLD, True, {}),
+    (20, 96, 128, False, FIXED, False, {}),
+    (20, 96, 128, True, THRESHOLD, False, {"ICPK_BATCH_GROUP": "4"}),
+    (20, 96, 128, False, THRESHOLD, False, {"ICPK_RESULT_MIRROR": "0"}),  # counts copied back, stream waited for
+    (6, 96, 128, False, THRESHOLD, False, {"ICPK_ZERO_COPY_UPLOAD": "0"}),  # copy-engine uploads without the filter
+    (6, 96, 128, False, THRESHOLD, False, {"ICPK_LOOP_AHEAD": "0"}),  # the whole loop enqueued up front
+    (6, 96, 128, True, THRESHOLD, False, {"ICPK_BATCH_SETUP": "3"}),  # the recorded set-up replayed pair by pair
+]
+
+
+@pytest.mark.parametrize("n,rows,cols,filt,par,explicit,env", CASES)
+def test_frames_batch_equals_pair_by_pair(monkeypatch, n, rows, cols, filt, par, explicit, env):
+    for k, v in env.items():  # (read by icpk_create: the reference context of run_case gets it too -- same results)
+        monkeypatch.setenv(k, v)
+    streams, fx, cx = make_streams(n, 6, rows, cols, seed=n + rows)
+    assert run_case(streams, fx, cx, filt, par, explicit) == 6 * n
+
+
+def test_subsample_keys_per_stream():
+    """with icpk_set_subsample, stream s draws its patterns as a context of its own that saw only its frames"""
+    n, steps = 3, 4
+    streams, fx, cx = make_streams(n, steps, 96, 128, seed=11)
+    with binding.Context(0) as ctx:
+        ctx.set_subsample(3, seed=77)
+        refs = [binding.Context(0) for _ in range(n)]
+        try:
+            for r in refs:
+                r.set_subsample(3, seed=77)
+            sb = [State() for _ in range(n)]
+            sr = [State() for _ in range(n)]
+            for s in range(n):
+                sb[s].previous = sr[s].previous = streams[s][0]
+            for k in range(1, steps + 1):
+                jobs = [sb[s].job(s, streams[s][k], k == 1) for s in range(n)]
+                T, st, rc = ctx.align_frames_batch(jobs, fx=fx, cx=cx, **THRESHOLD)
+                for s in range(n):
+                    # (the reference passes the previous frame again: a fresh subsample pattern for it, as a resident
+                    # frame gets one too -- icpk_set_subsample)
+                    got = (T[s], st[s], ctx.get_frames_trace(s, 17))
+                    want = ref_step(refs[s], sr[s], streams[s][k], fx, cx, False, THRESHOLD)
+                    same_result(got, want, f"step {k} stream {s}")
+                    sb[s].advance(streams[s][k], *got)
+                    sr[s].advance(streams[s][k], *want)
+        finally:
+            for r in refs:
+                r.close()
+
+
+@pytest.mark.parametrize("merged", ["1", "0"])
+def test_single_path_after_backproject_pair_unchanged(monkeypatch, merged):
+    """the single path's other set-up route (ICPK_MERGED_SETUP=0, or a second alignment of the same clouds) now keeps
+    the image order and uses pixel seeds as the merged one does: same bits as the default route"""
+    frames, fx, cx = make_streams(1, 3, 96, 128, seed=12)
+    frames = frames[0]
+    with binding.Context(0) as ref:
+        want = []
+        for k in (1, 2, 3):
+            ref.backproject_pair(frames[k], frames[k - 1], R=np.eye(3), t=np.full(3, 5, np.float32), fx=fx, cx=cx)
+            T, st, rc = ref.align(**THRESHOLD)
+            want.append((T.copy(), st, ref.get_trace(17)))
+    monkeypatch.setenv("ICPK_MERGED_SETUP", merged)
+    with binding.Context(0) as ctx:
+        for k in (1, 2, 3):
+            ctx.backproject_pair(frames[k], frames[k - 1], R=np.eye(3), t=np.full(3, 5, np.float32), fx=fx, cx=cx)
+            for again in range(2):  # (the second alignment of the same clouds takes the non-merged route too)
+                T, st, rc = ctx.align(**THRESHOLD)
+                same_result((T, st, ctx.get_trace(17)), want[k - 1], f"frame {k} alignment {again}")
+
+
+def test_edge_cases_fallback_empty_frames_and_subsets():
+    """an all-zero frame (empty source, then empty target), a stream with two valid pixels (< min_pairs fallback,
+    last_rotation kept for its next step), and calls that advance only some streams."""
+    streams, fx, cx = make_streams(12, 6, 96, 128, seed=3)
+    streams[2][3] = np.zeros_like(streams[2][3])
+    for k in (2, 3, 4):
+        d = np.zeros_like(streams[5][k])
+        d[40, 50] = d[41, 52] = 6000 + 10 * k
+        streams[5][k] = d
+
+    def subsets(k):
+        return [3, 7, 11] if k in (2, 5) else range(12)
+
+    assert run_case(streams, fx, cx, False, THRESHOLD, False, subsets=subsets) == 2 * 3 + 4 * 12
+
+
+def test_not_set_and_bad_arguments():
+    streams, fx, cx = make_streams(4, 2, 96, 128, seed=4)
+    small, _, _ = make_streams(1, 1, 48, 64, seed=5)
+    with binding.Context(0) as ctx:
+        jobs = [dict(stream=s, source=streams[s][1], target=streams[s][0]) for s in range(4)]
+        T, st, rc = ctx.align_frames_batch(jobs, fx=fx, cx=cx, **THRESHOLD)
+        assert rc >= 0 and all(s.status >= 0 for s in st)
+        # stream 9 has never been seen, stream 1 is resident at another size: those jobs alone are ICPK_E_NOT_SET
+        ctx.align_frames_batch([dict(stream=1, source=small[0][1], target=small[0][0])], fx=fx, cx=cx, **THRESHOLD)
+        jobs = [dict(stream=0, source=streams[0][2]), dict(stream=9, source=streams[1][2]),
+                dict(stream=1, source=streams[1][2]), dict(stream=2, source=streams[2][2])]
+        T, st, rc = ctx.align_frames_batch(jobs, fx=fx, cx=cx, **THRESHOLD)
+        assert rc == binding.E_NOT_SET
+        assert [s.status for s in st][1:3] == [binding.E_NOT_SET] * 2
+        assert st[0].status >= 0 and st[3].status >= 0 and st[0].iterations > 0 and st[3].iterations > 0
+        assert np.array_equal(T[1], np.eye(4)) and ctx.get_frames_trace(1) == []
+        # duplicate / out-of-range streams, and params the lock-step path does not run: ICPK_E_ARG, nothing runs
+        before = len(ctx.get_frames_trace(0))
+        for bad_jobs, kw in (([dict(stream=0, source=streams[0][2]), dict(stream=0, source=streams[1][2])], {}),
+                             ([dict(stream=256, source=streams[0][2])], {}),
+                             ([dict(stream=0, source=streams[0][2])], dict(nn_mode=binding.NN_EXACT)),
+                             ([dict(stream=0, source=streams[0][2])], dict(host_loop=1)),
+                             ([dict(stream=0, source=streams[0][2])], dict(solve=binding.SOLVE_POINT_TO_PLANE))):
+            T, st, rc = ctx.align_frames_batch(bad_jobs, fx=fx, cx=cx, **THRESHOLD, **kw)
+            assert rc == binding.E_ARG
+            assert len(ctx.get_frames_trace(0)) == before  # (the last call's record is untouched)
+        # the duplicate call changed nothing: stream 0's resident frame is still streams[0][2]
+        T1, st1, _ = ctx.align_frames_batch([dict(stream=0, source=streams[0][2])], fx=fx, cx=cx, **FIXED)
+        T2, st2, _ = ctx.align_frames_batch([dict(stream=0, source=streams[0][2], target=streams[0][2])], fx=fx, cx=cx,
+                                            **FIXED)
+        assert np.array_equal(T1.view(np.uint32), T2.view(np.uint32)) and st1[0].final_pairs == st2[0].final_pairs
+        ctx.release_frame_streams()
+        T, st, rc = ctx.align_frames_batch([dict(stream=0, source=streams[0][2])], fx=fx, cx=cx, **THRESHOLD)
+        assert rc == binding.E_NOT_SET
+
+
+def test_interleaved_single_path_is_unaffected():
+    """a plain backproject_pair / align on the same context, between batch calls, sees its own resident frame."""
+    streams, fx, cx = make_streams(6, 5, 96, 128, seed=6)
+    single, _, _ = make_streams(1, 5, 96, 128, seed=7)
+    single = single[0]
+    outs = []
+    with binding.Context(0) as ref:
+        ref.backproject_pair(single[1], single[0], fx=fx, cx=cx)
+        for k in range(2, 6):
+            ref.backproject_pair(single[k], None, fx=fx, cx=cx)
+            T, st, _ = ref.align(**THRESHOLD)
+            outs.append((T.copy(), st.final_pairs, ref.get_trace(17)))
+    got = []
+
+    def hook(ctx, k):
+        if k == 1:
+            ctx.backproject_pair(single[1], single[0], fx=fx, cx=cx)
+        elif k <= 5:
+            ctx.backproject_pair(single[k], None, fx=fx, cx=cx)  # resident frame: the context's own, not a stream's
+            T, st, _ = ctx.align(**THRESHOLD)
+            got.append((T.copy(), st.final_pairs, ctx.get_trace(17)))
+
+    assert run_case(streams, fx, cx, False, THRESHOLD, False, hook=hook) == 30
+    assert len(got) == len(outs) == 4
+    for (Ta, na, ta), (Tb, nb, tb) in zip(got, outs):
+        assert np.array_equal(Ta.view(np.uint32), Tb.view(np.uint32)) and na == nb and len(ta) == len(tb)
+
+
+def test_multi_sequence_runner_equals_sequence_runners():
+    streams, fx, cx = make_streams(5, 6, 96, 128, seed=8)
+    with binding.Context(0) as ctx, binding.Context(0) as ref:
+        multi = sequence.MultiSequenceRunner(ctx, 5, fx=fx, cx=cx)
+        singles = [sequence.SequenceRunner(ref, fx=fx, cx=cx) for _ in range(5)]
+        for k in range(7):
+            active = [s for s in range(5) if not (k == 3 and s == 1)]  # stream 1 skips a frame
+            res = multi.step({s: streams[s][k] for s in active})
+            for s in active:
+                want = singles[s].step(streams[s][k])
+                if want is None:
+                    assert res[s] is None
+                    continue
+                assert res[s]["csv"] == want["csv"]
+                assert np.array_equal(res[s]["T"].view(np.uint32), want["T"].view(np.uint32))
+                assert res[s]["status"] == want["status"] and res[s]["iterations"] == want["iterations"]
+
+
+def test_multi_sequence_runner_keeps_results_of_a_partial_failure():
+    streams, fx, cx = make_streams(3, 3, 96, 128, seed=9)
+    streams[1][1] = np.zeros_like(streams[1][1])  # stream 1's second pair has an empty target
+    with binding.Context(0) as ctx, binding.Context(0) as ref:
+        multi = sequence.MultiSequenceRunner(ctx, 3, fx=fx, cx=cx)
+        singles = [sequence.SequenceRunner(ref, fx=fx, cx=cx) for _ in range(3)]
+        for k in range(4):
+            try:
+                res = multi.step({s: streams[s][k] for s in range(3)})
+            except binding.IcpkError as e:
+                # (from k = 2 on stream 1 pairs its frame with the empty one, its last good frame, and fails again)
+                assert k >= 2 and e.failed == {1: binding.E_EMPTY_TARGET}
+                res = e.results
+            for s in range(3):
+                try:
+                    want = singles[s].step(streams[s][k])
+                except binding.IcpkError as e:
+                    assert k >= 2 and s == 1 and e.code == binding.E_EMPTY_TARGET and s not in res
+                    continue
+                if want is None:
+                    assert res[s] is None
+                else:
+                    assert res[s]["csv"] == want["csv"], (k, s)
+                    assert np.array_equal(res[s]["T"].view(np.uint32), want["T"].view(np.uint32))
