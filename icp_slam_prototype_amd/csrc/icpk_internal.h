@@ -104,7 +104,8 @@ void launch_decimate(const float* x, const float* y, const float* z, int n, int 
 constexpr int GRID_MAX_CELLS = 1 << ICPK_GRID_MAX_CELLS_LOG2;
 // the slots of the frame-batch mode (up to 32 child contexts) own smaller tables: Kinect-size pairs need ~0.9 M cells,
 // and 3 x 8 MB per slot instead of 3 x 32 MB keeps a 64-pair batch at 0.8 GB instead of 3.2 GB (a denser pair in a slot
-// merely gets a coarser grid: efficiency only)
+// merely gets a coarser grid: efficiency only -- tests/test_gpu_lockstep_edges.py holds a slot whose target asks for
+// more than 4 x 2^21 cells to the exact kernel)
 constexpr int GRID_MAX_CELLS_SLOT = 1 << 21;
 constexpr int GRID_BOUNDS_PARTS = 256;  // partial boxes of the bounds pass (6 floats each)
 struct GridInfo {

@@ -697,7 +697,10 @@ __device__ __forceinline__ void nn_grid_body(
       int s0 = 0, len = 0;
       if (row < nrows) {
         // row = rz * nyr + ry without an integer division (~30 instructions): the float quotient is within 1 of the
-        // true one (row < 2^20 rows, relative error of rcp and product < 2^-21), two compare-and-fix steps make it exact
+        // true one, and one compare-and-fix step makes it exact.  The bound: grid_info_body keeps h >= emax / 1023, so
+        // no axis has more than 1024 cells and a cube's rows number at most 1024 x 1024 = 2^20 (row < 2^20); rcp
+        // and product have a relative error < 2^-21, below 1 / row.  (tests/test_gpu_lockstep_edges.py,
+        // test_row_range_of_the_grid_scan_at_its_largest, scans all 2^20 rows.)
         int rz = (int)((float)row * __builtin_amdgcn_rcpf((float)nyr));
         int ry = row - rz * nyr;
         if (ry < 0) {

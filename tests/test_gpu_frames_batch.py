@@ -68,6 +68,19 @@ def ref_step(ctx, state, depth, fx, cx, filt, par):
     return T.reshape(4, 4), st, ctx.get_trace(par["max_iterations"] + 1)
 
 
+def ref_exact(ctx, state, depth, fx, cx, filt, par):
+    """The pair of ref_step rebuilt by icpk_backproject_pair, its clouds copied into a plain context's host-given
+    clouds, aligned by the exact kernel (no spatial index) and the host loop: (T, stats)."""
+    R, t = binding._f(state.r.camera_rotation), binding._f(state.r.camera_position)
+    ctx.backproject_pair(depth, state.previous, R=R, t=t, fx=fx, cx=cx, filter=filt, **(FILTER if filt else {}))
+    src, tgt = ctx.get_source(), ctx.get_target()
+    ctx.set_target(tgt)
+    ctx.set_source(src)
+    T, st, rc = ctx.align(nn_mode=binding.NN_EXACT, host_loop=1, last_rotation=state.r.last_rotation,
+                          last_translation=state.r.last_translation, **par)
+    return T.copy(), st
+
+
 def same_result(a, b, what):
     (Ta, sa, ta), (Tb, sb, tb) = a, b
     assert np.array_equal(Ta.view(np.uint32), Tb.view(np.uint32)), f"{what}: T differs\n{Ta}\n{Tb}"
@@ -82,14 +95,17 @@ def same_result(a, b, what):
         assert x["n_pairs"] == y["n_pairs"] and x["mse"].view(np.uint32) == y["mse"].view(np.uint32), what
 
 
-def run_case(streams, fx, cx, filt, par, explicit, subsets=None, hook=None):
-    """Drives both sides step by step; returns the number of compared jobs."""
+def run_case(streams, fx, cx, filt, par, explicit, subsets=None, hook=None, positions=None, exact=None):
+    """Drives both sides step by step; returns the number of compared jobs.  positions: stream -> initial camera
+    position; exact: streams whose every step is also held to brute force (ref_exact)."""
     n, steps = len(streams), len(streams[0]) - 1
-    with binding.Context(0) as ctx, binding.Context(0) as ref:
+    with binding.Context(0) as ctx, binding.Context(0) as ref, binding.Context(0) as brute:
         sb = [State() for _ in range(n)]
         sr = [State() for _ in range(n)]
         for s in range(n):
             sb[s].previous = sr[s].previous = streams[s][0]
+            if positions and s in positions:
+                sb[s].r.camera_position = sr[s].r.camera_position = np.asarray(positions[s], np.float32)
         compared = 0
         first = [True] * n
         for k in range(1, steps + 1):
@@ -101,6 +117,9 @@ def run_case(streams, fx, cx, filt, par, explicit, subsets=None, hook=None):
             assert rc == (min(s.status for s in st) if min(s.status for s in st) < 0 else max(s.status for s in st))
             for j, s in enumerate(active):
                 got = (T[j], st[j], ctx.get_frames_trace(j, par["max_iterations"] + 1))
+                if exact and s in exact:
+                    same_result(got[:2] + ([],), ref_exact(brute, sr[s], streams[s][k], fx, cx, filt, par) + ([],),
+                                f"step {k} stream {s} against brute force")
                 want = ref_step(ref, sr[s], streams[s][k], fx, cx, filt, par)
                 same_result(got, want, f"step {k} stream {s}")
                 sb[s].advance(streams[s][k], *got)
@@ -308,3 +327,53 @@ def test_multi_sequence_runner_keeps_results_of_a_partial_failure():
                 else:
                     assert res[s]["csv"] == want["csv"], (k, s)
                     assert np.array_equal(res[s]["T"].view(np.uint32), want["T"].view(np.uint32))
+
+
+def test_all_256_streams_then_sparse_ids():
+    """ICPK_MAX_FRAME_STREAMS streams on 32 x 24 frames: 16 groups of 16 over the two alternating slot sets, twice,
+    then one call with the sparse ids {0, 1, 127, 200, 255} out of id order.  Catches a stream's resident frame lost
+    or swapped between calls (every stream's third step pairs with the frame it left two calls before), and a slot
+    set that keeps a stale pair from 8 groups back."""
+    n = binding.MAX_FRAME_STREAMS
+    streams, fx, cx = make_streams(n, 3, 24, 32, seed=256)
+    sparse = [200, 0, 255, 127, 1]
+    exact = {255}
+
+    def subsets(k):
+        return sparse if k == 3 else range(n)
+
+    assert run_case(streams, fx, cx, False, THRESHOLD, False, subsets=subsets, exact=exact) == 2 * n + len(sparse)
+
+
+@pytest.mark.parametrize("par", [THRESHOLD, FIXED])
+def test_one_group_at_the_geometry_limits(par):
+    """One group mixing a full-valid 640 x 480 frame (307 200 points: a slot's 2^21-cell table clamps the grid of this
+    cloud), a flat wall at one depth (a z-constant plane: one cell layer), a frame with one valid pixel (< min_pairs
+    fallback), a frame holding depths 1 and 65535 with the filter off (0.2 mm and 13.1 m
+    scattered among the room's pixels), and a stream posed 10^3 m from the origin.  Each equals the pair-by-pair definition, and each
+    stream, every step, equals the same pair aligned by the exact kernel and the host loop."""
+    rows, cols, steps = 480, 640, 2
+    room, fx, cx = make_streams(2, steps, rows, cols, seed=99)
+    full = []
+    for k in range(steps + 1):
+        d = room[0][k].copy()
+        d[d == 0] = 7000 + k  # every pixel valid
+        d[::11, ::7] = 3000
+        full.append(d)
+    assert all(np.count_nonzero(d) == rows * cols for d in full)
+    wall = [np.full((rows, cols), 9000, np.uint16) for _ in range(steps + 1)]
+    one = []
+    for k in range(steps + 1):
+        d = np.zeros((rows, cols), np.uint16)
+        d[200 + k, 300] = 6000
+        one.append(d)
+    extremes = []
+    for k in range(steps + 1):
+        d = room[1][k].copy()
+        d[5 + k::37, ::53] = 1
+        d[17::41, 3 + k::29] = 65535
+        extremes.append(d)
+    far = [f.copy() for f in room[1]]
+    streams = [full, wall, one, extremes, far]
+    positions = {4: np.array([1000.0, -1000.0, 1000.0], np.float32)}
+    assert run_case(streams, fx, cx, False, par, False, positions=positions, exact={0, 1, 2, 3, 4}) == 5 * steps
