@@ -25,6 +25,9 @@ SUBSAMPLE_FACTOR = 40  # pointcloud.hpp:11
 NP2L = 28
 NN_EXACT, NN_FILTERED, NN_PRUNED, NN_GRID, NN_MAP = 0, 1, 2, 3, 4
 NSUM = 19
+NSUM_W, NP2L_W = 21, 30  # icpk_reduce_weighted: the weighted sums, then W and the kept count
+ROBUST_NONE, ROBUST_HUBER, ROBUST_TUKEY = 0, 1, 2
+SCALE_FIXED, SCALE_MEDIAN = 0, 1
 
 # every symbol include/icpk.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -45,6 +48,7 @@ SYMBOLS = [
     "icpk_map_voxel", "icpk_align_to_map", "icpk_map_nearest", "icpk_map_lookup_to_target", "icpk_align_to_map_dense",
     "icpk_bgr_to_gray", "icpk_detect_fast", "icpk_detected_to_cloud",
     "icpk_align_frames_batch", "icpk_get_frames_trace", "icpk_release_frame_streams",
+    "icpk_set_robust", "icpk_get_robust_trace", "icpk_reduce_weighted",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -118,6 +122,16 @@ class FrameJob(C.Structure):
 LOG_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_double, C.c_void_p)
 
 _lib = None
+
+
+class Robust(C.Structure):
+    """icpk_robust: kernel ROBUST_*, scale_mode SCALE_*, scale (> 0), trim_fraction (0, 1]."""
+    _fields_ = [
+        ("kernel", C.c_int32),
+        ("scale_mode", C.c_int32),
+        ("scale", C.c_float),
+        ("trim_fraction", C.c_float),
+    ]
 
 
 class IcpkError(RuntimeError):
@@ -238,6 +252,10 @@ def load():
     lib.icpk_bgr_to_gray.argtypes = [C.c_void_p, u8, C.c_int32, C.c_int32, u8]
     lib.icpk_detect_fast.argtypes = [C.c_void_p, u8] + [C.c_int32] * 7 + [fp, fp, ip]
     lib.icpk_detected_to_cloud.argtypes = [C.c_void_p, u16, C.c_int32, C.c_int32, C.c_float, C.c_float, fp, fp, C.c_int32, ip]
+    lib.icpk_set_robust.argtypes = [C.c_void_p, C.POINTER(Robust)]
+    lib.icpk_get_robust_trace.argtypes = [C.c_void_p, ip, ip, fp, dp, dp]
+    lib.icpk_reduce_weighted.argtypes = [C.c_void_p, C.c_float, C.c_int32, dp, C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64), fp, fp, dp]
     _lib = lib
     return lib
 
@@ -645,6 +663,36 @@ class Context:
         cnt = C.c_int64(0)
         self._chk(self._lib.icpk_reduce_p2l(self._h, max_dist, sums.ctypes.data_as(C.POINTER(C.c_double)), C.byref(cnt)))
         return sums, cnt.value
+
+    # -- robust alignment (icpk_set_robust) -----------------------------------------
+    def set_robust(self, kernel=ROBUST_NONE, scale=1.0, scale_mode=SCALE_FIXED, trim=1.0):
+        """Weights and trimming of every later alignment (include/icpk.h); set_robust(None) turns it off."""
+        if kernel is None:
+            return self._chk(self._lib.icpk_set_robust(self._h, None))
+        r = Robust(kernel, scale_mode, scale, trim)
+        return self._chk(self._lib.icpk_set_robust(self._h, C.byref(r)))
+
+    def get_robust_trace(self, max_iterations=64):
+        """Per iteration of the last robust alignment: dict(kept, cut, c, wsum)."""
+        n = C.c_int32(0)
+        kept = np.zeros(max_iterations, np.int32)
+        cut = np.zeros(max_iterations, np.float32)
+        c = np.zeros(max_iterations, np.float64)
+        w = np.zeros(max_iterations, np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self._lib.icpk_get_robust_trace(self._h, C.byref(n), kept.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  _fp(cut), c.ctypes.data_as(dp), w.ctypes.data_as(dp)))
+        return [dict(kept=int(kept[i]), cut=np.float32(cut[i]), c=float(c[i]), wsum=float(w[i])) for i in range(n.value)]
+
+    def reduce_weighted(self, max_dist=0.75, solve=SOLVE_KABSCH):
+        """One robust reduction over the last sweep's associations: (sums, accepted, kept, cut, median, c)."""
+        sums = np.zeros(NP2L_W if solve == SOLVE_POINT_TO_PLANE else NSUM_W, np.float64)
+        acc, kept = C.c_int64(0), C.c_int64(0)
+        cut, med = C.c_float(0), C.c_float(0)
+        c = C.c_double(0)
+        self._chk(self._lib.icpk_reduce_weighted(self._h, max_dist, solve, sums.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 C.byref(acc), C.byref(kept), C.byref(cut), C.byref(med), C.byref(c)))
+        return sums, acc.value, kept.value, np.float32(cut.value), np.float32(med.value), c.value
 
     # -- loop ---------------------------------------------------------------------
     def align(self, params=None, **kw):

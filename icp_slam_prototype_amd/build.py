@@ -13,7 +13,7 @@ LIB = os.path.join(LIBDIR, "libicpk.so")
 SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp", "icpk_frames_batch.cpp", "icpk_frontend.cpp", "icpk_comm.cpp",
            "kernels_nn.hip", "kernels_reduce.hip", "kernels_transform.hip", "kernels_backproject.hip", "kernels_sort.hip",
            "kernels_nn_pruned.hip", "kernels_loop.hip", "kernels_grid.hip", "kernels_frontend.hip",
-           "icpk_map.cpp", "kernels_map.hip", "icpk_fast.cpp", "kernels_fast.hip", "kernels_map_nn.hip"]
+           "icpk_map.cpp", "kernels_map.hip", "icpk_fast.cpp", "kernels_fast.hip", "kernels_map_nn.hip", "kernels_robust.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.

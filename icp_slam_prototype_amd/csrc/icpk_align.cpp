@@ -238,7 +238,8 @@ int align_device_loop(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk
   const bool prof_all = p->profile >= 2;  // 1: NN kernels only (2 events per sweep); 2: every stage
   const bool p2l = p->solve == ICPK_SOLVE_POINT_TO_PLANE;
   const bool fused = p->nn_mode == ICPK_NN_PRUNED || p->nn_mode == ICPK_NN_GRID;  // K3 runs inside the sweep
-  const int nsum = loop_nsum(p);
+  const bool robust = ctx->robust_on;
+  const int nsum = robust ? (p2l ? NP2L_W : NSUM_W) : loop_nsum(p);
   const int B = red_blocks(ctx->src.n);
   const LoopGuard guard{ctx};
   // a loop that may leave early is enqueued loop_ahead iterations ahead of the device, not all at once
@@ -265,7 +266,8 @@ int align_device_loop(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk
     if (!loop_rec(ctx)) ctx->best_of_sweep.push_back(ctx->best);  // (grid sweeps keep ONE set of records: a sweep that runs at all supersedes the previous one)
     if (progress_bit(1)) return ICPK_OK;  // (the loop has exited meanwhile: K2 would be a no-op launch)
     if (prof_all && (r = pf.stamp(&pf.red))) return r;
-    r = p2l ? enqueue_reduce_p2l(ctx, p->max_nn_dist) : enqueue_reduce(ctx, p->max_nn_dist);
+    r = robust ? enqueue_reduce_robust(ctx, p->max_nn_dist, p2l)
+               : (p2l ? enqueue_reduce_p2l(ctx, p->max_nn_dist) : enqueue_reduce(ctx, p->max_nn_dist));
     if (r) return r;
     return prof_all ? pf.stamp(nullptr) : ICPK_OK;
   };
@@ -279,7 +281,7 @@ int align_device_loop(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk
       if (rc) return rc;
       if (exited) break;  // everything from here on would find `done` set and do nothing
     }
-    launch_loop_step(ctx->partial, ctx->pcount, B, nsum, ctx->st_dev, 0, ctx->stream);
+    launch_loop_step(ctx->partial, ctx->pcount, B, nsum, ctx->st_dev, 0, ctx->stream, ctx->rsel, ctx->robust_trace_dev);
     // (done only: a step that fell back to the caller's last motion stops AFTER the next transform, which the fused
     // sweep applies -- the working source must receive it)
     if (progress_bit(2)) break;
@@ -293,7 +295,8 @@ int align_device_loop(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk
   }
   // a step that set `done` has published the outputs already: the statistics-only step would be a no-op launch
   const bool done_seen = mirror && progress_bit(2);
-  if (!done_seen) launch_loop_step(ctx->partial, ctx->pcount, B, nsum, ctx->st_dev, 1, ctx->stream);
+  if (!done_seen)
+    launch_loop_step(ctx->partial, ctx->pcount, B, nsum, ctx->st_dev, 1, ctx->stream, ctx->rsel, ctx->robust_trace_dev);
   if (loop_rec(ctx)) {  // the caller-order planes and keys the grid sweeps did not keep current: once, and only if asked for
     ctx->rec_pending = true;
     if (!ctx->tune.lazy_unpack && (rc = ensure_unpacked(ctx))) return rc;
@@ -320,6 +323,8 @@ int align_device_loop(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk
   }
 
   rc = device_loop_finish(ctx, p, T_out, stats, result);
+  if (robust)  // (written by the loop steps into mapped memory before the result was published)
+    ctx->robust_trace.assign(ctx->robust_trace_pin.get(), ctx->robust_trace_pin.get() + ctx->trace_pairs.size());
   if (stats) pf.book(stats);
   return rc;
 }
@@ -347,6 +352,7 @@ int icpk_align_query_sharded(icpk_ctx* ctx, const icpk_params* p, float T_out[16
     return fail(ctx, ICPK_E_ARG, "the query-sharded loop supports the reference and Kabsch flavours");
   if (p->max_iterations < 0 || p->max_iterations > LOOP_MAX_ITER) return fail(ctx, ICPK_E_ARG, "max_iterations out of range");
   if (p->min_pairs < 1) return fail(ctx, ICPK_E_ARG, "min_pairs must be >= 1");
+  if (ctx->robust_on) return fail(ctx, ICPK_E_ARG, "robust alignment is not available in the query-sharded loop");
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   reset_outputs(T_out, stats);
   icpk_params q = *p;
@@ -396,6 +402,9 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
     return fail(ctx, ICPK_E_NOT_SET, "point-to-plane needs target normals");
   if (p->nn_mode == ICPK_NN_MAP && (p->solve == ICPK_SOLVE_POINT_TO_PLANE || !(p->max_nn_dist <= ICPK_MAX_NN_DISTANCE)))
     return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP: reference or Kabsch flavour and max_nn_dist <= 0.75");
+  // the bug-for-bug solve has no weighted form
+  if (ctx->robust_on && p->solve == ICPK_SOLVE_REFERENCE)
+    return fail(ctx, ICPK_E_ARG, "robust alignment needs the Kabsch or point-to-plane flavour");
   int rc = check_ready(ctx);
   if (rc) {
     if (stats) stats->status = rc;
@@ -404,14 +413,18 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   rc = begin_alignment(ctx);
   if (rc) return rc;
+  const bool robust = ctx->robust_on;
+  if (robust && ctx->src.n > 0 && (rc = ensure_robust(ctx, ctx->src.n))) return rc;
   if (!p->host_loop && !ctx->log_fn && ctx->src.n > 0 && p->max_iterations <= LOOP_MAX_ITER)
     return align_device_loop(ctx, p, T_out, stats);
 
   Profiler pf(ctx, p);
   const bool p2l = p->solve == ICPK_SOLVE_POINT_TO_PLANE;
-  const int nsum = p2l ? NP2L : NSUM;
+  const int nsum = robust ? (p2l ? NP2L_W : NSUM_W) : (p2l ? NP2L : NSUM);
   double sums[NSUM_MAX];
-  int64_t npairs = 0;
+  int64_t npairs = 0, kept = 0;  // kept: pairs with a weight > 0 (robust; else the accepted ones)
+  double wsum = 0.0;             // W = sum w (robust; else the pair count)
+  RobustSel sel{};
   float mse = 0.f;
   auto sweep = [&]() -> int {
     int r = pf.sweep(p->nn_mode);
@@ -419,7 +432,8 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
     r = pf.stamp(&pf.red);  // start of reduce
     if (r) return r;
     if (ctx->src.n > 0) {
-      r = p2l ? enqueue_reduce_p2l(ctx, p->max_nn_dist) : enqueue_reduce(ctx, p->max_nn_dist);
+      r = robust ? enqueue_reduce_robust(ctx, p->max_nn_dist, p2l)
+                 : (p2l ? enqueue_reduce_p2l(ctx, p->max_nn_dist) : enqueue_reduce(ctx, p->max_nn_dist));
       if (r) return r;
     }
     r = pf.stamp(nullptr);  // end of reduce
@@ -428,10 +442,13 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
     if (ctx->src.n > 0) {
       std::memcpy(sums, ctx->red_host, nsum * sizeof(double));
       std::memcpy(&npairs, ctx->red_host + nsum, sizeof(int64_t));
+      if (robust) sel = *ctx->rsel_host;
     } else {
       std::memset(sums, 0, sizeof(sums));
       npairs = 0;
     }
+    kept = robust ? (int64_t)sums[nsum - 1] : npairs;
+    wsum = robust ? sums[nsum - 2] : (double)npairs;
     if (p2l) {  // distance sum sits in the last slot
       const float m = npairs > 0 ? (float)(sums[27] / (double)npairs) : 0.f;
       mse = (float)((double)m * (double)m);
@@ -481,7 +498,7 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
   int status = ICPK_OK;
   int i = 0;
   while ((p->fixed_iterations || mse > p->threshold) && i < p->max_iterations) {  // icp.cpp:155
-    if (npairs < p->min_pairs) {  // icp.cpp:163-182: reuse the caller's last motion
+    if (kept < p->min_pairs) {  // icp.cpp:163-182: reuse the caller's last motion
       rc = apply(p->last_rotation, p->last_translation);
       if (rc) return rc;
       for (int k = 0; k < 3; ++k) offset[k] = -p->last_translation[k];
@@ -490,6 +507,7 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
     }
     ctx->trace_pairs.push_back((int32_t)npairs);
     ctx->trace_mse.push_back(mse);
+    if (robust) ctx->robust_trace.push_back(RobustTraceEntry{(int)kept, sel.cut, sel.c, wsum});
     double Rd[9], td[3];
     if (p->solve == ICPK_SOLVE_REFERENCE) {
       float M[9], R[9], Rinv[9], neg[3];
@@ -526,7 +544,7 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
       for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) sab[3 * r + c] = sums[3 * c + r];  // sum a_r b_c = M^T
       log_delta(ctx, ICPK_LOG_RECONSTRUCT_POINT_CLOUDS, 0);
-      solve_kabsch(npairs, sa, sb, sab, Rd, td);
+      solve_kabsch(wsum, sa, sb, sab, Rd, td);
       log_delta(ctx, ICPK_LOG_SVD, 0);
       if ((rc = take(Rd, td))) return rc;
     }

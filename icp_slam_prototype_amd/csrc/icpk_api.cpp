@@ -1,6 +1,7 @@
 // icpk_api.cpp -- host side of libicpk.so: the context (one GPU + one HIP stream) and its tuning, the clouds it holds,
 // and the small entry points of the C ABI of include/icpk.h.  The NN sweeps live in icpk_sweep.cpp, the alignment
 // loops in icpk_align.cpp, the frame-batch mode in icpk_batch.cpp and the depth front end in icpk_frontend.cpp.
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -230,6 +231,7 @@ void clear_trace(icpk_ctx* ctx) {
   ctx->trace_t.clear();
   ctx->trace_mse.clear();
   ctx->trace_pairs.clear();
+  ctx->robust_trace.clear();
 }
 
 }  // namespace icpk
@@ -398,6 +400,38 @@ int icpk_get_trace(icpk_ctx* ctx, int32_t* n_iter, float* R_out, float* t_out, i
   if (t_out && n) std::memcpy(t_out, ctx->trace_t.data(), n * 3 * sizeof(float));
   if (pairs_out && n) std::memcpy(pairs_out, ctx->trace_pairs.data(), n * sizeof(int32_t));
   if (mse_out && n) std::memcpy(mse_out, ctx->trace_mse.data(), n * sizeof(float));
+  return ICPK_OK;
+}
+
+int icpk_set_robust(icpk_ctx* ctx, const icpk_robust* r) {
+  if (!ctx) return ICPK_E_ARG;
+  if (!r) {
+    ctx->robust_on = false;
+    return ICPK_OK;
+  }
+  if (r->kernel < ICPK_ROBUST_NONE || r->kernel > ICPK_ROBUST_TUKEY)
+    return fail(ctx, ICPK_E_ARG, "unknown robust kernel");
+  if (r->scale_mode != ICPK_SCALE_FIXED && r->scale_mode != ICPK_SCALE_MEDIAN)
+    return fail(ctx, ICPK_E_ARG, "unknown robust scale mode");
+  if (!(r->scale > 0.f) || !std::isfinite(r->scale)) return fail(ctx, ICPK_E_ARG, "robust scale must be finite and > 0");
+  if (!(r->trim_fraction > 0.f && r->trim_fraction <= 1.f)) return fail(ctx, ICPK_E_ARG, "trim_fraction must lie in (0, 1]");
+  ctx->robust = *r;
+  ctx->robust_on = true;
+  return ICPK_OK;
+}
+
+int icpk_get_robust_trace(icpk_ctx* ctx, int32_t* n_iter, int32_t* kept_out, float* cut_out, double* c_out,
+                          double* wsum_out) {
+  if (!ctx || !n_iter) return ICPK_E_ARG;
+  const size_t n = ctx->robust_trace.size();
+  *n_iter = (int32_t)n;
+  for (size_t i = 0; i < n; ++i) {
+    const icpk::RobustTraceEntry& e = ctx->robust_trace[i];
+    if (kept_out) kept_out[i] = e.kept;
+    if (cut_out) cut_out[i] = e.cut;
+    if (c_out) c_out[i] = e.c;
+    if (wsum_out) wsum_out[i] = e.wsum;
+  }
   return ICPK_OK;
 }
 

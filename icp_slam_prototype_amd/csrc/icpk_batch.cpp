@@ -33,7 +33,7 @@ struct GroupRun {
 namespace icpk {
 
 bool batch_eligible(const icpk_ctx* ctx, const icpk_params* p) {
-  return p->nn_mode == ICPK_NN_GRID && !p->host_loop && !ctx->log_fn && p->profile <= 1 &&
+  return p->nn_mode == ICPK_NN_GRID && !p->host_loop && !ctx->log_fn && !ctx->robust_on && p->profile <= 1 &&
          (p->solve == ICPK_SOLVE_REFERENCE || p->solve == ICPK_SOLVE_KABSCH) && p->max_iterations >= 0 &&
          p->max_iterations <= LOOP_MAX_ITER && p->min_pairs >= 1;
 }

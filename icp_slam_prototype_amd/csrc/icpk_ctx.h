@@ -250,6 +250,17 @@ struct icpk_ctx {
   std::vector<hipEvent_t> events;
   std::vector<float> trace_R, trace_t, trace_mse;  // per-iteration record of the last align
   std::vector<int32_t> trace_pairs;
+  // robust alignment (icpk_set_robust, K10): the setting, the selection's state and scratch, and the record of the last
+  // alignment (icpk_get_robust_trace; the device loop writes it straight into the mapped robust_trace_pin)
+  bool robust_on = false;
+  icpk_robust robust{};
+  icpk::DevBuf<icpk::RobustSel> rsel;
+  icpk::PinnedBuf<icpk::RobustSel> rsel_host;
+  icpk::DevBuf<int> rhist;        // 2 x SEL_BINS, zero between selections
+  icpk::DevBuf<unsigned> rdsel;   // the accepted distance patterns of the sweep being selected
+  icpk::CoherentBuf<icpk::RobustTraceEntry> robust_trace_pin;  // LOOP_MAX_ITER entries
+  icpk::RobustTraceEntry* robust_trace_dev = nullptr;          // view: the same memory as the device addresses it
+  std::vector<icpk::RobustTraceEntry> robust_trace;
   // grid scan (ICPK_NN_GRID): cell table + AoS copy of the target sorted by cell
   icpk::DevBuf<GridInfo> grid_info;
   icpk::DevBuf<float> grid_bounds;
@@ -398,6 +409,11 @@ int enqueue_nn(icpk_ctx* ctx, int nn_mode, hipEvent_t ev0 = nullptr, hipEvent_t 
 const float4* loop_rec(const icpk_ctx* ctx);
 int enqueue_reduce(icpk_ctx* ctx, float max_dist);
 int enqueue_reduce_p2l(icpk_ctx* ctx, float max_dist);
+// robust sweep (K10): room for the selection of nq queries, its histogram cleared (once per alignment / hook call) ...
+int ensure_robust(icpk_ctx* ctx, int nq);
+// ... and the selection + the weighted K2 / K5 over the current associations (NSUM_W / NP2L_W sums; outside a device
+// loop the sums, the count and the selection state are read back into red_host / rsel_host, not waited for)
+int enqueue_reduce_robust(icpk_ctx* ctx, float max_dist, bool p2l);
 
 // ---- icpk_align.cpp: the device-side loop, shared by the single-pair and the frame-batch path ----
 int loop_nsum(const icpk_params* p);

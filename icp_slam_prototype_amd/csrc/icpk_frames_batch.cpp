@@ -49,6 +49,7 @@ int align_frames_impl(icpk_ctx* ctx, int32_t n_jobs, const icpk_frame_job* jobs,
   if (p->max_iterations < 0 || p->solve < ICPK_SOLVE_REFERENCE || p->solve > ICPK_SOLVE_POINT_TO_PLANE)
     return fail(ctx, ICPK_E_ARG, "bad params");
   if (p->min_pairs < 1) return fail(ctx, ICPK_E_ARG, "min_pairs must be >= 1");
+  if (ctx->robust_on) return fail(ctx, ICPK_E_ARG, "robust alignment is not available in lock-step frame batches");
   if (!batch_eligible(ctx, p))
     return fail(ctx, ICPK_E_ARG,
                 "icpk_align_frames_batch: ICPK_NN_GRID, device-side loop, reference or Kabsch flavour, no log callback");

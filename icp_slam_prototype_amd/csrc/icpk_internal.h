@@ -39,11 +39,15 @@ struct Rt {
   float t[3];
 };
 struct LoopState;  // device-side loop state, defined below
+struct RobustSel;         // robust selection state (kernels_robust.hip), defined below
+struct RobustTraceEntry;  // ... and its per-iteration record
 
 constexpr int NSUM = 19;
 constexpr int NSUM_REF = 13;  // sums [0..12]: all the reference flavour's loop step reads
 constexpr int NP2L = 28;      // point-to-plane: 21 + 6 + 1
-constexpr int NSUM_MAX = 28;
+constexpr int NSUM_W = 21;   // robust Kabsch (ICPK_NSUM_W): NSUM weighted, [19] W, [20] kept
+constexpr int NP2L_W = 30;   // robust point-to-plane (ICPK_NP2L_W): NP2L weighted, [28] W, [29] kept
+constexpr int NSUM_MAX = 30;
 constexpr int RED_THREADS = 256;
 constexpr int RED_MAX_BLOCKS = 256;
 
@@ -223,8 +227,10 @@ struct StepArgs {
 struct StepBatch {
   StepArgs p[BATCH_MAX];
 };
+// nsum NSUM_W / NP2L_W: the robust step (kept count for min_pairs, W for the solve, one RobustTraceEntry per
+// completed iteration into rtrace, the cut and scale read from sel)
 void launch_loop_step(const double* partial, const int* pcount, int nblocks, int nsum, LoopState* st, int stats_only,
-                      hipStream_t s);
+                      hipStream_t s, const RobustSel* sel = nullptr, RobustTraceEntry* rtrace = nullptr);
 void launch_loop_step_batch(const StepBatch& b, int count, int nsum, int stats_only, hipStream_t s);
 void launch_transform_state(float* x, float* y, float* z, int n, const LoopState* st, hipStream_t s);
 void launch_reduce_final(const double* partial, const int* pcount, int nblocks, int nsum, double* out, hipStream_t s);
@@ -243,7 +249,7 @@ void launch_reduce_final_shard(const double* partial, const int* pcount, int nbl
 void launch_assoc_reduce(const nn_key_t* best, const float* ax, const float* ay, const float* az, int nq,
                          const float* tx, const float* ty, const float* tz, const float4* o4, const float4* rec, float max_dist,
                          int32_t* idx_out, float* dist_out, double* partial, int* pcount, double* out, LoopState* st,
-                         int nact, hipStream_t s);
+                         int nact, hipStream_t s, const RobustSel* sel = nullptr);  // sel: the weighted K2 (NSUM_W sums)
 // one pair's arguments of K2 inside a device loop (no idx/dist unpacking, no final stage)
 struct ReduceArgs {
   const nn_key_t* best;
@@ -265,7 +271,57 @@ void launch_assoc_reduce_batch(const ReduceBatch& b, int count, float max_dist, 
 void launch_p2l_reduce(const nn_key_t* best, const float* ax, const float* ay, const float* az, int nq, const float* tx,
                        const float* ty, const float* tz, const float* nx, const float* ny, const float* nz,
                        const float4* rec, float max_dist, int32_t* idx_out, float* dist_out, double* partial, int* pcount,
-                       double* out, LoopState* st, hipStream_t s);
+                       double* out, LoopState* st, hipStream_t s, const RobustSel* sel = nullptr);
+
+// ---- robust alignment (K10: kernels_robust.hip, the weighted K2 / K5 of kernels_reduce.hip) ----------------------
+// The exact cut tau and median m of one sweep's accepted distances by a radix select over their bit patterns
+// (non-negative floats sort as unsigned integers; the sign bit is cleared, so -0 counts as +0): three passes of
+// 11 / 10 / 10 bits (bits 30..20, 19..10, 9..0), each a histogram kernel (LDS integer atomics per block, then the
+// block's non-zero bins added into one global histogram with integer atomics -- exact, so deterministic) and a
+// one-block scan that narrows both ranks' buckets and clears the histogram for the next pass.
+constexpr int SEL_BINS = 2048;  // bins of the widest pass; the global histogram holds 2 x SEL_BINS ints (tau, m)
+struct RobustCfg {  // icpk_robust as the kernels take it
+  int kernel, scale_mode;
+  float scale, trim;
+};
+struct RobustSel {
+  unsigned prefix[2];  // high bits of tau ([0]) and m ([1]) found so far; after the last pass their full patterns
+  long long rank[2];   // 1-based ranks still to be found inside those buckets
+  long long n;         // accepted pairs of the sweep
+  int same;            // prefix[0] == prefix[1]: one histogram serves both ranks
+  int kernel;          // ICPK_ROBUST_* for the weighted reduction
+  float cut, median;   // tau and m (0 when n == 0)
+  double c;            // the scale of the weights
+};
+struct RobustTraceEntry {  // icpk_get_robust_trace, one per completed iteration
+  int kept;
+  float cut;
+  double c, wsum;
+};
+// dsel: [nq] scratch (the sweep's accepted distance patterns, 0xffffffff for the others); hist: 2 x SEL_BINS ints, zero
+// between selections; nx != nullptr: point-to-plane acceptance (non-zero target normal as well)
+void launch_robust_select(const nn_key_t* best, const float4* rec, int nq, float max_dist, const float* nx,
+                          const float* ny, const float* nz, unsigned* dsel, int* hist, RobustSel* sel, const RobustCfg& cfg,
+                          const LoopState* st, hipStream_t s);
+
+// w(d) of a kept candidate (accepted: d < max_dist): 0 beyond the cut, else the kernel's weight in float64
+struct RobustWeight {
+  int kernel;
+  float cut;
+  double c;
+  __device__ __forceinline__ double operator()(float d) const {
+    if (!(d <= cut)) return 0.0;
+    const double x = d;
+    if (kernel == 1) return x <= c ? 1.0 : c / x;  // ICPK_ROBUST_HUBER
+    if (kernel == 2) {                             // ICPK_ROBUST_TUKEY
+      if (x == 0.0) return 1.0;
+      if (!(x < c)) return 0.0;
+      const double r = x / c, u = 1.0 - r * r;
+      return u * u;
+    }
+    return 1.0;  // ICPK_ROBUST_NONE
+  }
+};
 
 // kernels_transform.hip
 void launch_transform(float* x, float* y, float* z, int n, const Rt& rt, hipStream_t s);

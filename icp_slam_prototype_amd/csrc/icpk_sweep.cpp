@@ -589,6 +589,47 @@ int enqueue_reduce_p2l(icpk_ctx* ctx, float max_dist) {
   return read_back_sums(ctx, NP2L);
 }
 
+int ensure_robust(icpk_ctx* ctx, int nq) {
+  int rc = ctx->rsel.reserve(ctx, 1);
+  if (!rc) rc = ctx->rsel_host.reserve(ctx, 1);
+  if (!rc) rc = ctx->rhist.reserve(ctx, 2 * SEL_BINS);
+  if (!rc) rc = ctx->rdsel.reserve(ctx, round_up(nq < 1 ? 1 : nq, NN_TILE));
+  if (!rc && !ctx->robust_trace_pin) {
+    rc = ctx->robust_trace_pin.reserve(ctx, LOOP_MAX_ITER);
+    void* d = nullptr;
+    if (!rc) ICPK_HIP(ctx, hipHostGetDevicePointer(&d, ctx->robust_trace_pin.get(), 0));
+    ctx->robust_trace_dev = static_cast<RobustTraceEntry*>(d);
+  }
+  if (rc) return rc;
+  // (each scan clears what its pass filled; this makes a selection cut short by an earlier error harmless)
+  ICPK_HIP(ctx, hipMemsetAsync(ctx->rhist, 0, 2 * SEL_BINS * sizeof(int), ctx->stream));
+  return ICPK_OK;
+}
+
+int enqueue_reduce_robust(icpk_ctx* ctx, float max_dist, bool p2l) {
+  const int nq = ctx->src.n;
+  const icpk_robust& r = ctx->robust;
+  const RobustCfg cfg{r.kernel, r.scale_mode, r.scale, r.trim_fraction};
+  const float4* rec = loop_rec(ctx);
+  launch_robust_select(ctx->best, rec, nq, max_dist, p2l ? ctx->nrm.x() : nullptr, p2l ? ctx->nrm.y() : nullptr,
+                       p2l ? ctx->nrm.z() : nullptr, ctx->rdsel, ctx->rhist, ctx->rsel, cfg, ctx->st_active, ctx->stream);
+  int32_t* idx_out = ctx->st_active ? nullptr : ctx->idx.get();
+  float* dist_out = ctx->st_active ? nullptr : ctx->dist.get();
+  double* out = ctx->st_active ? nullptr : ctx->red_out.get();
+  if (p2l)
+    launch_p2l_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), nq, ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(),
+                      ctx->nrm.x(), ctx->nrm.y(), ctx->nrm.z(), rec, max_dist, idx_out, dist_out, ctx->partial,
+                      ctx->pcount, out, ctx->st_active, ctx->stream, ctx->rsel);
+  else
+    launch_assoc_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), nq, ctx->tgt.x(), ctx->tgt.y(),
+                        ctx->tgt.z(), ctx->have_grid ? ctx->o4 : nullptr, rec, max_dist, idx_out, dist_out, ctx->partial,
+                        ctx->pcount, out, ctx->st_active, NSUM_W, ctx->stream, ctx->rsel);
+  const int rc = read_back_sums(ctx, p2l ? NP2L_W : NSUM_W);
+  if (rc || ctx->st_active) return rc;
+  ICPK_HIP(ctx, hipMemcpyAsync(ctx->rsel_host, ctx->rsel, sizeof(RobustSel), hipMemcpyDeviceToHost, ctx->stream));
+  return ICPK_OK;
+}
+
 // ---- deferred set-up launches (icpk_internal.h) ----
 SetupRecorder*& setup_recorder() {
   static thread_local SetupRecorder* rec = nullptr;
@@ -731,6 +772,38 @@ int icpk_reduce(icpk_ctx* ctx, float max_dist, double* sums, int64_t* count) {
 
 int icpk_reduce_p2l(icpk_ctx* ctx, float max_dist, double* sums, int64_t* count) {
   return reduce_to_host(ctx, max_dist, sums, count, true);
+}
+
+int icpk_reduce_weighted(icpk_ctx* ctx, float max_dist, int32_t solve, double* sums, int64_t* accepted, int64_t* kept,
+                         float* cut, float* median, double* c) {
+  if (!ctx || !sums || (solve != ICPK_SOLVE_KABSCH && solve != ICPK_SOLVE_POINT_TO_PLANE)) return ICPK_E_ARG;
+  if (!ctx->robust_on) return fail(ctx, ICPK_E_NOT_SET, "robust alignment is off (icpk_set_robust)");
+  if (!ctx->have_assoc) return fail(ctx, ICPK_E_NOT_SET, "no nearest-neighbour sweep has run");
+  const bool p2l = solve == ICPK_SOLVE_POINT_TO_PLANE;
+  if (p2l && !ctx->have_normals) return fail(ctx, ICPK_E_NOT_SET, "no target normals");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  if (int ru = ensure_unpacked(ctx)) return ru;
+  const int nsum = p2l ? NP2L_W : NSUM_W;
+  RobustSel sel{};
+  int64_t n = 0;
+  if (ctx->src.n == 0) {
+    std::memset(sums, 0, nsum * sizeof(double));
+    sel.c = ctx->robust.scale_mode == ICPK_SCALE_MEDIAN ? 0.0 : (double)ctx->robust.scale;
+  } else {
+    int rc = ensure_robust(ctx, ctx->src.n);
+    if (!rc) rc = enqueue_reduce_robust(ctx, max_dist, p2l);
+    if (rc) return rc;
+    ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(sums, ctx->red_host, nsum * sizeof(double));
+    std::memcpy(&n, ctx->red_host + nsum, sizeof(int64_t));
+    sel = *ctx->rsel_host;
+  }
+  if (accepted) *accepted = n;
+  if (kept) *kept = (int64_t)sums[nsum - 1];
+  if (cut) *cut = sel.cut;
+  if (median) *median = sel.median;
+  if (c) *c = sel.c;
+  return ICPK_OK;
 }
 
 }  // extern "C"

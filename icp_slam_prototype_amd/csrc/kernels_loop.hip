@@ -80,7 +80,11 @@ __global__ __launch_bounds__(256) void reduce_final_kernel(const double* __restr
 }
 
 void launch_reduce_final(const double* partial, const int* pcount, int nblocks, int nsum, double* out, hipStream_t s) {
-  if (nsum == NP2L)
+  if (nsum == NP2L_W)
+    hipLaunchKernelGGL(reduce_final_kernel<NP2L_W>, dim3(1), dim3(256), 0, s, partial, pcount, nblocks, out, 0, nullptr);
+  else if (nsum == NSUM_W)
+    hipLaunchKernelGGL(reduce_final_kernel<NSUM_W>, dim3(1), dim3(256), 0, s, partial, pcount, nblocks, out, 0, nullptr);
+  else if (nsum == NP2L)
     hipLaunchKernelGGL(reduce_final_kernel<NP2L>, dim3(1), dim3(256), 0, s, partial, pcount, nblocks, out, 0, nullptr);
   else
     hipLaunchKernelGGL(reduce_final_kernel<NSUM>, dim3(1), dim3(256), 0, s, partial, pcount, nblocks, out, 0, nullptr);
@@ -133,9 +137,16 @@ __device__ __forceinline__ void publish_result(LoopState* __restrict__ st) {
   __hip_atomic_store(st->progress + 2, (st->epoch << 1) | 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// NS == NSUM_W / NP2L_W: the step of a robust loop (K10) -- the sums are weighted, [NS - 2] = W, [NS - 1] = the kept
+// count; min_pairs applies to the kept count, the Kabsch solve takes W for the pair count, the loop test and the trace
+// stay those of the accepted pairs, and every completed iteration leaves a RobustTraceEntry in rtrace
 template <int NS, int NACT = NS>
 __device__ __forceinline__ void loop_step_body(const double* __restrict__ partial, const int* __restrict__ pcount,
-                                               int nblocks, LoopState* __restrict__ st, int stats_only) {
+                                               int nblocks, LoopState* __restrict__ st, int stats_only,
+                                               const RobustSel* __restrict__ sel = nullptr,
+                                               RobustTraceEntry* __restrict__ rtrace = nullptr) {
+  constexpr bool ROBUST = NS == NSUM_W || NS == NP2L_W;
+  constexpr bool P2L = NS == NP2L || NS == NP2L_W;
   // the control words are fetched together with the partial sums (independent loads in
   // flight at once) and only then acted upon
   const int done = st->done, stop_after = st->stop_after_transform, i = st->iterations;
@@ -173,7 +184,7 @@ __device__ __forceinline__ void loop_step_body(const double* __restrict__ partia
   // statistics of the sweep just reduced (icp.cpp:622-638 from the double sum)
   float mse = 0.f;
   if (npairs > 0) {
-    const float m = (float)(sums[NS == NP2L ? 27 : 12] / (double)npairs);
+    const float m = (float)(sums[P2L ? 27 : 12] / (double)npairs);
     mse = (float)((double)m * (double)m);
   }
   st->pairs = npairs;
@@ -189,7 +200,8 @@ __device__ __forceinline__ void loop_step_body(const double* __restrict__ partia
     publish_progress(st);
     return;
   }
-  if (npairs < min_pairs) {  // icp.cpp:163-182
+  const long long kept = ROBUST ? (long long)sums[NS - 1] : npairs;
+  if (kept < min_pairs) {  // icp.cpp:163-182
     for (int k = 0; k < 9; ++k) st->rt.R[k] = st->last_rotation[k];
     for (int k = 0; k < 3; ++k) {
       st->rt.t[k] = st->last_translation[k];
@@ -208,9 +220,17 @@ __device__ __forceinline__ void loop_step_body(const double* __restrict__ partia
     mir->trace_pairs[i] = (int)npairs;
     mir->trace_mse[i] = mse;
   }
+  if constexpr (ROBUST) {
+    RobustTraceEntry e;
+    e.kept = (int)kept;
+    e.cut = sel->cut;
+    e.c = sel->c;
+    e.wsum = sums[NS - 2];
+    rtrace[i] = e;
+  }
   float Rrec[9], trec[3];
   STEP_STAMP(i, 2);
-  if (NS == NP2L) {
+  if (P2L) {
     double Rd[9], td[3];
     if (!solve_p2l(sums, Rd, td)) {
       st->status = 2;  // ICPK_W_DEGENERATE
@@ -252,7 +272,7 @@ __device__ __forceinline__ void loop_step_body(const double* __restrict__ partia
     }
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) sab[3 * r + c] = sums[3 * c + r];
-    solve_kabsch(npairs, sa, sb, sab, Rd, td);
+    solve_kabsch(ROBUST ? sums[NS - 2] : (double)npairs, sa, sb, sab, Rd, td);  // (W == (double)npairs when every w is 1)
     for (int k = 0; k < 9; ++k) Rrec[k] = (float)Rd[k];
     for (int k = 0; k < 3; ++k) trec[k] = (float)td[k];
     for (int k = 0; k < 9; ++k) st->rt.R[k] = Rrec[k];
@@ -277,6 +297,15 @@ __global__ __launch_bounds__(256) void loop_step_kernel(const double* __restrict
                                                         const int* __restrict__ pcount, int nblocks,
                                                         LoopState* __restrict__ st, int stats_only) {
   loop_step_body<NS, NACT>(partial, pcount, nblocks, st, stats_only);
+}
+
+template <int NS>
+__global__ __launch_bounds__(256) void loop_step_robust_kernel(const double* __restrict__ partial,
+                                                               const int* __restrict__ pcount, int nblocks,
+                                                               LoopState* __restrict__ st, int stats_only,
+                                                               const RobustSel* __restrict__ sel,
+                                                               RobustTraceEntry* __restrict__ rtrace) {
+  loop_step_body<NS, NS>(partial, pcount, nblocks, st, stats_only, sel, rtrace);
 }
 
 // frame-batch mode: one workgroup per pair
@@ -306,8 +335,14 @@ void launch_loop_init_batch(const SetupBatchOf<LoopInitArgs>& b, int count, hipS
 }
 
 void launch_loop_step(const double* partial, const int* pcount, int nblocks, int nsum, LoopState* st, int stats_only,
-                      hipStream_t s) {
-  if (nsum == NP2L)
+                      hipStream_t s, const RobustSel* sel, RobustTraceEntry* rtrace) {
+  if (nsum == NSUM_W)
+    hipLaunchKernelGGL(loop_step_robust_kernel<NSUM_W>, dim3(1), dim3(256), 0, s, partial, pcount, nblocks, st,
+                       stats_only, sel, rtrace);
+  else if (nsum == NP2L_W)
+    hipLaunchKernelGGL(loop_step_robust_kernel<NP2L_W>, dim3(1), dim3(256), 0, s, partial, pcount, nblocks, st,
+                       stats_only, sel, rtrace);
+  else if (nsum == NP2L)
     hipLaunchKernelGGL(loop_step_kernel<NP2L>, dim3(1), dim3(256), 0, s, partial, pcount, nblocks, st, stats_only);
   else if (nsum == NSUM_REF)  // reference flavour: the reduction produced sums [0..12] only
     hipLaunchKernelGGL((loop_step_kernel<NSUM, NSUM_REF>), dim3(1), dim3(256), 0, s, partial, pcount, nblocks, st,

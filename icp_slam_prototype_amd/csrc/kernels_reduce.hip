@@ -30,7 +30,9 @@ extern "C" int icpk_debug_read_red_stamps(unsigned long long* out) {
 #define RED_STAMP(k)
 #endif
 
-// NACT: how many of the NSUM sums the consumer needs.  icpk_reduce and the Kabsch flavour take
+// NACT: how many of the NSUM sums the consumer needs.  NACT == NSUM_W: the weighted K2 of a robust sweep (K10): every
+// sum but the distance sum multiplied by the pair's weight w (RobustWeight of the cut and scale in `sel`), and W and
+// the kept count in [19], [20]; the int count stays the accepted pairs'.  icpk_reduce and the Kabsch flavour take
 // all 19; the reference flavour's loop step only reads [0..12] (M, mean difference, distance
 // sum), so the device loop skips the sums of a and b: a third less butterfly.
 // `block` of `nblocks` (the canonical geometry of the pair: nblocks = red_blocks(nq)); shared
@@ -41,7 +43,8 @@ __device__ __forceinline__ void assoc_reduce_body(
     const float* __restrict__ az, int nq, const float* __restrict__ tx, const float* __restrict__ ty,
     const float* __restrict__ tz, const float4* __restrict__ o4, const float4* __restrict__ rec, float max_dist,
     int32_t* __restrict__ idx_out, float* __restrict__ dist_out, double* __restrict__ partial, int* __restrict__ pcount,
-    LoopState* __restrict__ st, const int block, const int nblocks) {
+    LoopState* __restrict__ st, const int block, const int nblocks, const RobustSel* __restrict__ sel = nullptr) {
+  constexpr bool WEIGHTED = NACT == NSUM_W;
   const int tid = threadIdx.x;
   const int P = nblocks * RED_THREADS;
   // (records path: a lane's first record is asked for BEFORE the loop state is looked at -- two cold round trips side by
@@ -61,9 +64,30 @@ __device__ __forceinline__ void assoc_reduce_body(
 #pragma unroll
   for (int s = 0; s < NACT; ++s) v[s] = 0.0;
   int cnt = 0;
+  RobustWeight weight{};
+  if constexpr (WEIGHTED) weight = RobustWeight{sel->kernel, sel->cut, sel->c};
 
   // the accumulation of one accepted pair (a = moved query, b = its match, d = their distance)
   auto add_pair = [&](float a0, float a1, float a2, float b0, float b1, float b2, float d) {
+      if constexpr (WEIGHTED) {
+        v[12] += (double)d;
+        ++cnt;
+        const double w = weight(d);
+        if (!(w > 0.0)) return;  // (trimmed or zero weight: not kept, adds nothing)
+        // w * x: with w == 1 every term is the plain one, bit for bit
+        const double da0 = a0, da1 = a1, da2 = a2, wb0 = w * (double)b0, wb1 = w * (double)b1, wb2 = w * (double)b2;
+        v[0] += wb0 * da0; v[1] += wb0 * da1; v[2] += wb0 * da2;
+        v[3] += wb1 * da0; v[4] += wb1 * da1; v[5] += wb1 * da2;
+        v[6] += wb2 * da0; v[7] += wb2 * da1; v[8] += wb2 * da2;
+        v[9] += w * (double)(a0 - b0);
+        v[10] += w * (double)(a1 - b1);
+        v[11] += w * (double)(a2 - b2);
+        v[13] += w * da0; v[14] += w * da1; v[15] += w * da2;
+        v[16] += wb0; v[17] += wb1; v[18] += wb2;
+        v[19 % NACT] += w;
+        v[20 % NACT] += 1.0;
+        return;
+      }
       const double da0 = a0, da1 = a1, da2 = a2, db0 = b0, db1 = b1, db2 = b2;
       v[0] += db0 * da0; v[1] += db0 * da1; v[2] += db0 * da2;
       v[3] += db1 * da0; v[4] += db1 * da1; v[5] += db1 * da2;
@@ -137,9 +161,9 @@ __global__ __launch_bounds__(RED_THREADS) void assoc_reduce_kernel(
     const float* __restrict__ az, int nq, const float* __restrict__ tx, const float* __restrict__ ty,
     const float* __restrict__ tz, const float4* __restrict__ o4, const float4* __restrict__ rec, float max_dist,
     int32_t* __restrict__ idx_out, float* __restrict__ dist_out, double* __restrict__ partial, int* __restrict__ pcount,
-    LoopState* __restrict__ st) {
+    LoopState* __restrict__ st, const RobustSel* __restrict__ sel) {
   assoc_reduce_body<NACT>(best, ax, ay, az, nq, tx, ty, tz, o4, rec, max_dist, idx_out, dist_out, partial, pcount, st,
-                          blockIdx.x, gridDim.x);
+                          blockIdx.x, gridDim.x, sel);
 }
 
 // frame-batch mode: blockIdx.y = pair; every pair keeps ITS canonical geometry (its own
@@ -156,12 +180,17 @@ __global__ __launch_bounds__(RED_THREADS) void assoc_reduce_batch_kernel(const R
 // reference only plans it, TODO:9).  Per accepted pair (dist < max_dist and a
 // non-zero target normal n): J = [p x n ; n], r = (p - q).n; 21 upper-triangle
 // entries of J J^T, 6 of J r, 1 distance sum -- same canonical tree as K2.
+// NS == NP2L_W: the weighted K5 of a robust sweep (K10): the 27 terms multiplied by w, the distance sum unweighted,
+// W and the kept count in [28], [29].
+template <int NS>
 __global__ __launch_bounds__(RED_THREADS) void p2l_reduce_kernel(
     const nn_key_t* __restrict__ best, const float* __restrict__ ax, const float* __restrict__ ay,
     const float* __restrict__ az, int nq, const float* __restrict__ tx, const float* __restrict__ ty,
     const float* __restrict__ tz, const float* __restrict__ nxp, const float* __restrict__ nyp,
     const float* __restrict__ nzp, const float4* __restrict__ rec, float max_dist, int32_t* __restrict__ idx_out,
-    float* __restrict__ dist_out, double* __restrict__ partial, int* __restrict__ pcount, LoopState* __restrict__ st) {
+    float* __restrict__ dist_out, double* __restrict__ partial, int* __restrict__ pcount, LoopState* __restrict__ st,
+    const RobustSel* __restrict__ sel) {
+  constexpr bool WEIGHTED = NS == NP2L_W;
   const int tid = threadIdx.x;
   const int P = gridDim.x * RED_THREADS;
   // (records path: a lane's first record is asked for before the loop state is looked at, and inside the loop the NEXT
@@ -177,10 +206,12 @@ __global__ __launch_bounds__(RED_THREADS) void p2l_reduce_kernel(
     if (st->done | st->stop_after_transform) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) st->sweeps += 1;
   }
-  double v[NP2L];
+  double v[NS];
 #pragma unroll
-  for (int s = 0; s < NP2L; ++s) v[s] = 0.0;
+  for (int s = 0; s < NS; ++s) v[s] = 0.0;
   int cnt = 0;
+  RobustWeight weight{};
+  if constexpr (WEIGHTED) weight = RobustWeight{sel->kernel, sel->cut, sel->c};
   for (int i = i_first; i < nq; i += P) {
     float d, a0, a1, a2, b0 = 0.f, b1 = 0.f, b2 = 0.f;
     int j;
@@ -216,52 +247,74 @@ __global__ __launch_bounds__(RED_THREADS) void p2l_reduce_kernel(
         J[4] = n1;
         J[5] = n2;
         const double r = ((p0 - q0) * n0 + (p1 - q1) * n1) + (p2 - q2) * n2;
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-          for (int b = a; b < 6; ++b) v[k++] += J[a] * J[b];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) v[21 + a] += J[a] * r;
         v[27] += (double)d;
         ++cnt;
+        if constexpr (WEIGHTED) {
+          const double w = weight(d);
+          if (w > 0.0) {  // w * x: with w == 1 every term is the plain one, bit for bit
+            int k = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+              for (int b = a; b < 6; ++b) v[k++] += w * (J[a] * J[b]);
+#pragma unroll
+            for (int a = 0; a < 6; ++a) v[21 + a] += w * (J[a] * r);
+            v[28 % NS] += w;
+            v[29 % NS] += 1.0;
+          }
+        } else {
+          int k = 0;
+#pragma unroll
+          for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) v[k++] += J[a] * J[b];
+#pragma unroll
+          for (int a = 0; a < 6; ++a) v[21 + a] += J[a] * r;
+        }
       }
     }
   }
-  double u[WaveScatter<NP2L>::H2];
-  wave_reduce_scatter<NP2L>(v, u, cnt);
-  __shared__ double ws[RED_THREADS / 64][NP2L];
+  double u[WaveScatter<NS>::H2];
+  wave_reduce_scatter<NS>(v, u, cnt);
+  __shared__ double ws[RED_THREADS / 64][NS];
   __shared__ int wc[RED_THREADS / 64];
   const int wave = tid >> 6, lane = tid & 63;
-  wave_scatter_store<NP2L>(u, lane, ws[wave]);
+  wave_scatter_store<NS>(u, lane, ws[wave]);
   if (lane == 0) wc[wave] = cnt;
   __syncthreads();
-  if (tid < NP2L) partial[tid * RED_MAX_BLOCKS + blockIdx.x] = ((ws[0][tid] + ws[1][tid]) + ws[2][tid]) + ws[3][tid];
-  if (tid == NP2L) pcount[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+  if (tid < NS) partial[tid * RED_MAX_BLOCKS + blockIdx.x] = ((ws[0][tid] + ws[1][tid]) + ws[2][tid]) + ws[3][tid];
+  if (tid == NS) pcount[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
 
 void launch_p2l_reduce(const nn_key_t* best, const float* ax, const float* ay, const float* az, int nq, const float* tx,
                        const float* ty, const float* tz, const float* nx, const float* ny, const float* nz,
                        const float4* rec, float max_dist, int32_t* idx_out, float* dist_out, double* partial, int* pcount,
-                       double* out, LoopState* st, hipStream_t s) {
+                       double* out, LoopState* st, hipStream_t s, const RobustSel* sel) {
   const int B = red_blocks(nq);
-  hipLaunchKernelGGL(p2l_reduce_kernel, dim3(B), dim3(RED_THREADS), 0, s, best, ax, ay, az, nq, tx, ty, tz, nx, ny, nz,
-                     rec, max_dist, idx_out, dist_out, partial, pcount, st);
-  if (out) launch_reduce_final(partial, pcount, B, NP2L, out, s);
+  if (sel)
+    hipLaunchKernelGGL(p2l_reduce_kernel<NP2L_W>, dim3(B), dim3(RED_THREADS), 0, s, best, ax, ay, az, nq, tx, ty, tz, nx,
+                       ny, nz, rec, max_dist, idx_out, dist_out, partial, pcount, st, sel);
+  else
+    hipLaunchKernelGGL(p2l_reduce_kernel<NP2L>, dim3(B), dim3(RED_THREADS), 0, s, best, ax, ay, az, nq, tx, ty, tz, nx,
+                       ny, nz, rec, max_dist, idx_out, dist_out, partial, pcount, st, nullptr);
+  if (out) launch_reduce_final(partial, pcount, B, sel ? NP2L_W : NP2L, out, s);
 }
 
 void launch_assoc_reduce(const nn_key_t* best, const float* ax, const float* ay, const float* az, int nq,
                          const float* tx, const float* ty, const float* tz, const float4* o4, const float4* rec,
                          float max_dist, int32_t* idx_out, float* dist_out, double* partial, int* pcount, double* out,
-                         LoopState* st, int nact, hipStream_t s) {
+                         LoopState* st, int nact, hipStream_t s, const RobustSel* sel) {
   const int B = red_blocks(nq);
-  if (nact == NSUM_REF && !out)
+  if (sel)
+    hipLaunchKernelGGL(assoc_reduce_kernel<NSUM_W>, dim3(B), dim3(RED_THREADS), 0, s, best, ax, ay, az, nq, tx, ty, tz,
+                       o4, rec, max_dist, idx_out, dist_out, partial, pcount, st, sel);
+  else if (nact == NSUM_REF && !out)
     hipLaunchKernelGGL(assoc_reduce_kernel<NSUM_REF>, dim3(B), dim3(RED_THREADS), 0, s, best, ax, ay, az, nq, tx, ty, tz,
-                       o4, rec, max_dist, idx_out, dist_out, partial, pcount, st);
+                       o4, rec, max_dist, idx_out, dist_out, partial, pcount, st, nullptr);
   else
     hipLaunchKernelGGL(assoc_reduce_kernel<NSUM>, dim3(B), dim3(RED_THREADS), 0, s, best, ax, ay, az, nq, tx, ty, tz, o4,
-                       rec, max_dist, idx_out, dist_out, partial, pcount, st);
-  if (out) launch_reduce_final(partial, pcount, B, NSUM, out, s);
+                       rec, max_dist, idx_out, dist_out, partial, pcount, st, nullptr);
+  if (out) launch_reduce_final(partial, pcount, B, sel ? NSUM_W : NSUM, out, s);
 }
 
 void launch_assoc_reduce_batch(const ReduceBatch& b, int count, float max_dist, int nact, hipStream_t s) {

@@ -238,16 +238,17 @@ ICPK_HD void mul3f(const float A[9], const float B[9], float C[9]) {
   for (int k = 0; k < 9; ++k) C[k] = t[k];
 }
 
-ICPK_HD void solve_kabsch(int64_t n, const double sa[3], const double sb[3], const double sab[9], double R[9], double t[3]) {
+// n: the pair count as a float64 (exact below 2^53), or a robust sweep's weight total W = sum w with weighted sums
+ICPK_HD void solve_kabsch(double n, const double sa[3], const double sb[3], const double sab[9], double R[9], double t[3]) {
   double ca[3], cb[3];
   for (int k = 0; k < 3; ++k) {
-    ca[k] = sa[k] / (double)n;  // rigid_transform_3D.py:14-15
-    cb[k] = sb[k] / (double)n;
+    ca[k] = sa[k] / n;  // rigid_transform_3D.py:14-15
+    cb[k] = sb[k] / n;
   }
   Mat3 H, U, V;
   double S[3], Hd[9], Qd[9];
   for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) Hd[3 * r + c] = H.m[r][c] = sab[3 * r + c] - (double)n * ca[r] * cb[c];  // :18-22 AA^T BB
+    for (int c = 0; c < 3; ++c) Hd[3 * r + c] = H.m[r][c] = sab[3 * r + c] - n * ca[r] * cb[c];  // :18-22 AA^T BB
   // :26-28  U,S,Vt = svd(H); R = Vt.T * U.T = (U V^T)^T: the polar factor transposed, when it is
   // a proper rotation (det H > 0); the reflection branch (:31-34) flips the SMALLEST singular
   // direction, which only the SVD knows

@@ -68,6 +68,10 @@ class Engine {
   // pointcloud.cpp:27-30 (SUBSAMPLE_FACTOR, pointcloud.hpp:11) with a reproducible choice instead of rand(): every
   // cloud this engine back-projects from now on keeps one valid pixel in `factor` (0 / 1: all of them)
   int setSubsample(int factor = ICPK_SUBSAMPLE_FACTOR, uint64_t seed = 0) { return icpk_set_subsample(ctx_, factor, seed); }
+  // robust alignment (icpk_set_robust): trimmed pairs and Huber / Tukey weights for every later alignment of this
+  // engine (Kabsch and point-to-plane flavours); clearRobust() turns it off again (the default)
+  int setRobust(const icpk_robust& r) { return icpk_set_robust(ctx_, &r); }
+  int clearRobust() { return icpk_set_robust(ctx_, nullptr); }
 
  private:
   icpk_ctx* ctx_ = nullptr;

@@ -93,6 +93,13 @@ extern "C" {
                         [21..26] J r, [27] sum dist; J = [p x n ; n], r = (p - q).n      */
 #define ICPK_NSUM 19 /* [0..8] M[r][c]=sum b_r a_c, [9..11] sum (float)(a-b), \
                         [12] sum dist, [13..15] sum a, [16..18] sum b          */
+/* icpk_reduce_weighted (robust alignment, icpk_set_robust): the same sums with every term multiplied by the pair's
+ * weight w, over the accepted pairs, canonical tree -- except the distance sum, which stays unweighted (the loop test
+ * reads it) -- followed by W = sum w and the kept count (pairs with w > 0) as a float64:
+ *   ICPK_NSUM_W: [0..18] as ICPK_NSUM (weighted; [12] unweighted), [19] W, [20] kept
+ *   ICPK_NP2L_W: [0..26] as ICPK_NP2L (weighted), [27] unweighted sum dist, [28] W, [29] kept */
+#define ICPK_NSUM_W 21
+#define ICPK_NP2L_W 30
 
 typedef struct icpk_ctx icpk_ctx; /* opaque: owns device buffers + one HIP stream */
 
@@ -234,6 +241,53 @@ int icpk_align(icpk_ctx *ctx, const icpk_params *p, float T_out[16], icpk_stats 
  * Arrays sized for params.max_iterations entries; any may be NULL. */
 int icpk_get_trace(icpk_ctx *ctx, int32_t *n_iter, float *R_out, float *t_out, int32_t *pairs_out,
                    float *mse_out);
+/* ---- robust alignment (extension: the reference plans it, TODO:5 and TODO:10, icp.cpp:328-330) ----------------
+ * A setting of the context, off by default; off, every path runs exactly what it runs without it.  On, every sweep
+ * of the loop (the initial one and the one after every completed iteration) weighs its pairs:
+ *   accepted  the pairs the flavour's reduction accepts: d < max_nn_dist (point-to-plane: and a non-zero target
+ *             normal); n of them.  d is the NN distance in both flavours (not the point-to-plane residual).
+ *   cut tau   k = clamp(ceil((double)trim_fraction * n), 1, n); tau = the k-th smallest accepted d (from 1); a pair
+ *             is kept if it is accepted and d <= tau (ties at the cut are kept)
+ *   median m  the ceil(n/2)-th smallest accepted d, before trimming (n = 0: tau = m = 0)
+ *   scale c   (double)scale, or (double)scale * 1.4826 * (double)m; w(d) in float64 as below, 0 for a trimmed pair;
+ *             "kept" means w > 0
+ *   solve     Kabsch from the weighted centred sums (n -> W = sum w, sum a -> sum w a, sum b -> sum w b,
+ *             sum b a^T -> sum w b a^T); point-to-plane with its 27 normal-equation terms multiplied by w
+ *   control   unchanged: the loop test (icp.cpp:155), stats.final_pairs / final_mse and icpk_get_trace's pairs / mse
+ *             are those of the accepted pairs, unweighted; min_pairs applies to the KEPT count (below it the
+ *             fallback to the caller's last motion, ICPK_W_TOO_FEW_PAIRS)
+ * The identity setting (NONE, FIXED, any scale, trim_fraction 1) runs the robust kernels and returns T, statistics
+ * and trace bit-equal to the plain flavour.
+ * Where it applies: icpk_align (Kabsch and point-to-plane, every nn_mode, device and host loop: the same bits;
+ * ICPK_E_ARG for the reference flavour); icpk_align_to_map and icpk_align_to_map_dense (they run icpk_align's loop);
+ * icpk_align_batch / _device (the pairs run one by one, each equal to icpk_align).  icpk_align_frames_batch and
+ * icpk_align_query_sharded: ICPK_E_ARG while it is on. */
+#define ICPK_ROBUST_NONE  0   /* w = 1                                          */
+#define ICPK_ROBUST_HUBER 1   /* w = d <= c ? 1 : c / d                         */
+#define ICPK_ROBUST_TUKEY 2   /* w = d == 0 ? 1 : d < c ? (1 - (d/c)^2)^2 : 0   */
+#define ICPK_SCALE_FIXED  0   /* c = scale (metres)                             */
+#define ICPK_SCALE_MEDIAN 1   /* c = scale * 1.4826 * m   (m: median above)     */
+typedef struct icpk_robust {
+  int32_t kernel;       /* ICPK_ROBUST_*                                        */
+  int32_t scale_mode;   /* ICPK_SCALE_*                                         */
+  float scale;          /* > 0, finite                                          */
+  float trim_fraction;  /* (0, 1]: keep the closest share of accepted pairs    */
+} icpk_robust;
+/* NULL: off (the default).  ICPK_E_ARG for an unknown kernel or scale mode, a non-finite or non-positive scale, or
+ * trim_fraction outside (0, 1]; the setting is then left as it was. */
+int icpk_set_robust(icpk_ctx *ctx, const icpk_robust *r);
+/* Per iteration i < *n_iter of the last robust icpk_align (as icpk_get_trace): the kept count, the cut tau, the scale
+ * c and W = sum w of the sweep the iteration solved from.  *n_iter = 0 after an alignment with robust off.  Arrays
+ * sized for params.max_iterations entries; any may be NULL. */
+int icpk_get_robust_trace(icpk_ctx *ctx, int32_t *n_iter, int32_t *kept_out, float *cut_out, double *c_out,
+                          double *wsum_out);
+/* test hook: one robust reduction over the associations of the last icpk_nn (as icpk_reduce / icpk_reduce_p2l) with
+ * the context's setting (ICPK_E_NOT_SET while it is off).  solve: ICPK_SOLVE_KABSCH (sums: ICPK_NSUM_W doubles) or
+ * ICPK_SOLVE_POINT_TO_PLANE (ICPK_NP2L_W); accepted = n, kept, cut = tau, median = m, c as defined above.  Any
+ * output but sums may be NULL. */
+int icpk_reduce_weighted(icpk_ctx *ctx, float max_dist, int32_t solve, double *sums, int64_t *accepted, int64_t *kept,
+                         float *cut, float *median, double *c);
+
 /* frame-batch mode (the frame-pair formulation of icp.cpp:541-563): n_pairs
  * independent pairs on this context's device; T_out n_pairs x 16, stats n_pairs (or NULL).
  * With the default kernels (ICPK_NN_GRID, device-side loop, reference or Kabsch flavour) up to
