@@ -28,6 +28,7 @@ NSUM = 19
 NSUM_W, NP2L_W = 21, 30  # icpk_reduce_weighted: the weighted sums, then W and the kept count
 ROBUST_NONE, ROBUST_HUBER, ROBUST_TUKEY = 0, 1, 2
 SCALE_FIXED, SCALE_MEDIAN = 0, 1
+VOXEL_FIRST, VOXEL_CENTROID = 0, 1  # icpk_voxel_downsample: the representative / the fixed-point centroid
 
 # every symbol include/icpk.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -49,6 +50,7 @@ SYMBOLS = [
     "icpk_bgr_to_gray", "icpk_detect_fast", "icpk_detected_to_cloud",
     "icpk_align_frames_batch", "icpk_get_frames_trace", "icpk_release_frame_streams",
     "icpk_set_robust", "icpk_get_robust_trace", "icpk_reduce_weighted",
+    "icpk_voxel_downsample", "icpk_get_voxel_groups",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -256,6 +258,8 @@ def load():
     lib.icpk_get_robust_trace.argtypes = [C.c_void_p, ip, ip, fp, dp, dp]
     lib.icpk_reduce_weighted.argtypes = [C.c_void_p, C.c_float, C.c_int32, dp, C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64), fp, fp, dp]
+    lib.icpk_voxel_downsample.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_int32, ip, ip]
+    lib.icpk_get_voxel_groups.argtypes = [C.c_void_p, ip, ip, ip, ip, ip]
     _lib = lib
     return lib
 
@@ -693,6 +697,28 @@ class Context:
         self._chk(self._lib.icpk_reduce_weighted(self._h, max_dist, solve, sums.ctypes.data_as(C.POINTER(C.c_double)),
                                                  C.byref(acc), C.byref(kept), C.byref(cut), C.byref(med), C.byref(c)))
         return sums, acc.value, kept.value, np.float32(cut.value), np.float32(med.value), c.value
+
+    # -- voxel-grid downsampling (icpk_voxel_downsample) ------------------------------
+    def voxel_downsample(self, which=0, leaf=0.05, mode=VOXEL_CENTROID):
+        """One point per occupied cube of edge `leaf` (include/icpk.h) in place of the working source (which = 0) or
+        the target (1).  Returns (n_out, n_dropped)."""
+        n_out, n_drop = C.c_int32(0), C.c_int32(0)
+        self._chk(self._lib.icpk_voxel_downsample(self._h, int(which), float(leaf), int(mode), C.byref(n_out),
+                                                  C.byref(n_drop)))
+        return n_out.value, n_drop.value
+
+    def get_voxel_groups(self):
+        """The grouping of the last voxel_downsample: dict(n_in, n_out, first_index (n_out,), count (n_out,),
+        out_of_point (n_in,): -1 for a dropped point)."""
+        n_in, n_out = C.c_int32(0), C.c_int32(0)
+        self._chk(self._lib.icpk_get_voxel_groups(self._h, C.byref(n_in), C.byref(n_out), None, None, None))
+        first = np.empty(n_out.value, np.int32)
+        count = np.empty(n_out.value, np.int32)
+        oop = np.empty(n_in.value, np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._chk(self._lib.icpk_get_voxel_groups(self._h, None, None, first.ctypes.data_as(ip), count.ctypes.data_as(ip),
+                                                  oop.ctypes.data_as(ip)))
+        return dict(n_in=n_in.value, n_out=n_out.value, first_index=first, count=count, out_of_point=oop)
 
     # -- loop ---------------------------------------------------------------------
     def align(self, params=None, **kw):

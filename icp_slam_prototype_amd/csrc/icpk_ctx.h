@@ -2,7 +2,7 @@
 // host-side translation unit calls (icpk_api.cpp: context and clouds; icpk_sweep.cpp: NN sweeps and reductions;
 // icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
 // entry; icpk_frontend.cpp: depth images;
-// icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp).  Not part of the ABI.
+// icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -314,6 +314,18 @@ struct icpk_ctx {
   bool qcount2_dirty = false;
   icpk::DevBuf<int> scan_bsum2;
   icpk::DevBuf<int> sort_vals2;
+  // voxel-grid downsampling (icpk_voxel_downsample, K11; icpk_voxel.cpp): the table, the per-point scratch, the
+  // downsampled planes on their way into the cloud, and the grouping of the last call (icpk_get_voxel_groups)
+  icpk::DevBuf<icpk::VoxelSlot> vox_table;
+  icpk::DevBuf<int> vox_slot;    // [n_in]
+  icpk::DevBuf<int> vox_bsum;    // [ceil(n_in / 1024)]
+  icpk::DevBuf<int> vox_counts;  // n_out, n_dropped ...
+  icpk::PinnedBuf<int> vox_counts_host;  // ... and where the host reads them
+  icpk::DevBuf<float> vox_out;   // 3 planes of n_in floats (6 with normals)
+  icpk::DevBuf<int> vox_first, vox_count;  // [n_out]
+  icpk::DevBuf<int> vox_oop;               // [n_in]
+  bool have_vox = false;         // a downsample has run: the three above describe it
+  int vox_n_in = 0, vox_n_out = 0;
   int loop_nact = icpk::NSUM;      // device loop: sums the running alignment's step consumes (NSUM_REF or NSUM)
   int profile_phase = 0;     // alignments profiled so far (offsets the sampled launches, see profile_stride)
   int qperm_kind = 0;        // what qperm holds: 1 Morton order (pruned scan), 2 cell order (grid scan)

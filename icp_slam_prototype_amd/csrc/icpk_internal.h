@@ -598,4 +598,30 @@ void launch_map_poses(const float* x, const float* y, const float* z, int ns, co
 void launch_map_accepted(const float* px, const float* py, const float* pz, int n, const nn_key_t* best,
                          float max_dist, float* ox, float* oy, float* oz, const MapBuffers& b, hipStream_t s);
 
+// kernels_voxel.hip -- K11, voxel-grid downsampling (icpk_voxel_downsample)
+struct VoxelSlot {         // one entry of the open-addressing table: 64 bytes, one line
+  unsigned long long key;  // the packed voxel + 1; 0: empty
+  unsigned inv_first;      // 0x7fffffff - the lowest member index so far (atomicMax); 0: no member yet
+  int count;               // members
+  long long sum[6];        // centroid mode: the fixed-point sums of the members' x, y, z and of their normals
+};
+struct VoxelArgs {
+  const float *x, *y, *z;     // the cloud, n points
+  const float *nx, *ny, *nz;  // its normals, or nullptr
+  int n;
+  int centroid;               // 0: ICPK_VOXEL_FIRST, 1: ICPK_VOXEL_CENTROID
+  double leaf;
+  VoxelSlot* table;           // mask + 1 slots (a power of two >= 2 n), all zero
+  unsigned mask;
+  int* slot_of;               // [n] scratch: the slot of every point, -1 if dropped
+  int* bsum;                  // [ceil(n / 1024)] scratch
+  int* counts;                // [2]: n_out (written), n_dropped (added to: zero before the launch)
+  float *ox, *oy, *oz;        // [n_out <= n] each
+  float *onx, *ony, *onz;     // (with normals)
+  int *first_index, *count;   // [n_out <= n]
+  int* out_of_point;          // [n]
+};
+// the five launches of one downsample; n <= 0: nothing
+void launch_voxel_downsample(const VoxelArgs& a, hipStream_t s);
+
 }  // namespace icpk

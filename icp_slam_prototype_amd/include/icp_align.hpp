@@ -72,6 +72,14 @@ class Engine {
   // engine (Kabsch and point-to-plane flavours); clearRobust() turns it off again (the default)
   int setRobust(const icpk_robust& r) { return icpk_set_robust(ctx_, &r); }
   int clearRobust() { return icpk_set_robust(ctx_, nullptr); }
+  // voxel-grid downsampling (icpk_voxel_downsample): one point per occupied cube of edge `leaf` in place of the
+  // working source (which = 0) or the target (1); n_out: the size of the new cloud
+  int voxelDownsample(int which, float leaf, int mode = ICPK_VOXEL_CENTROID, int* n_out = nullptr) {
+    int32_t n = 0;
+    const int rc = icpk_voxel_downsample(ctx_, which, leaf, mode, &n, nullptr);
+    if (n_out && rc == ICPK_OK) *n_out = n;
+    return rc;
+  }
 
  private:
   icpk_ctx* ctx_ = nullptr;
@@ -296,6 +304,11 @@ class Tracker {
     int rc = icpk_backproject_pair(c, data, previous, rows, cols, fx_, cx_, nullptr, cameraRotation, cameraPosition,
                                    filterFrames ? 1 : 0, maxDistance, minDistance, 1, -1, -1, nullptr, nullptr);
     if (rc != ICPK_OK) return rc;
+    if (voxelLeaf > 0.f) {  // thin both clouds by space before the loop sees them (target first, then source)
+      rc = eng_.voxelDownsample(1, voxelLeaf, voxelMode);
+      if (rc == ICPK_OK) rc = eng_.voxelDownsample(0, voxelLeaf, voxelMode);
+      if (rc != ICPK_OK) return rc;
+    }
     params.max_iterations = maxIterations;
     params.threshold = threshold;
     std::memcpy(params.last_rotation, lastRotation, sizeof(lastRotation));
@@ -329,6 +342,10 @@ class Tracker {
   // on the device inside the same call instead (SLAM.hpp:15-16 limits)
   bool filterFrames = false;
   int maxDistance = 25000, minDistance = 1000;
+  // > 0: both clouds of every frame pair are voxel-grid downsampled with this leaf (metres) between back-projection
+  // and alignment (icpk_voxel_downsample); 0, the default: the calls are exactly those made without it
+  float voxelLeaf = 0.f;
+  int voxelMode = ICPK_VOXEL_CENTROID;
   float cameraRotation[9];
   float lastRotation[9];
   float cameraPosition[3];

@@ -96,10 +96,14 @@ class SequenceRunner:
 
     HEADER = "MSE,ICP rX,ICP rY,ICP rZ,GT rX,GT rY,GT rZ"  # SLAM.cpp:327
 
-    def __init__(self, ctx, max_iterations=16, threshold=1e-4, fx=468.60, cx=318.27, **params):
+    def __init__(self, ctx, max_iterations=16, threshold=1e-4, fx=468.60, cx=318.27, voxel_leaf=0.0,
+                 voxel_mode=binding.VOXEL_CENTROID, **params):
+        """voxel_leaf > 0: both clouds of every frame pair are voxel-grid downsampled with this leaf (metres) between
+        back-projection and alignment (Context.voxel_downsample); 0: the calls are those made without it."""
         self.ctx = ctx
         self.kw = dict(max_iterations=max_iterations, threshold=threshold, solve=binding.SOLVE_REFERENCE, **params)
         self.fx, self.cx = fx, cx
+        self.voxel_leaf, self.voxel_mode = float(voxel_leaf), voxel_mode
         self.camera_rotation = np.eye(3, dtype=np.float32)      # icp.cpp:49
         self.camera_position = np.full(3, 5, np.float32)        # icp.cpp:53
         self.last_rotation = np.eye(3, dtype=np.float32)
@@ -121,6 +125,9 @@ class SequenceRunner:
         # icp.cpp:38-39 back-project both frames, :58-59 / :70-71 pose them; the posed source is the
         # starting point of the alignment (one call: icpk_backproject_pair)
         c.backproject_pair(depth, self.previous, R=self.camera_rotation, t=self.camera_position, fx=self.fx, cx=self.cx)
+        if self.voxel_leaf > 0:
+            c.voxel_downsample(1, self.voxel_leaf, self.voxel_mode)
+            c.voxel_downsample(0, self.voxel_leaf, self.voxel_mode)
         T, st, rc = c.align(last_rotation=self.last_rotation, last_translation=self.last_translation, **self.kw)
         return self._advance(depth, T, st, rc, c.get_trace(max(self.kw["max_iterations"], 1)), timestamp, ground_truth)
 
@@ -153,6 +160,9 @@ class MultiSequenceRunner:
     def __init__(self, ctx, n_streams, max_iterations=16, threshold=1e-4, fx=468.60, cx=318.27, **params):
         if not 0 < n_streams <= binding.MAX_FRAME_STREAMS:
             raise ValueError(f"1 .. {binding.MAX_FRAME_STREAMS} streams")
+        if "voxel_leaf" in params or "voxel_mode" in params:
+            # (the streams' clouds live inside the lock-step group between back-projection and loop)
+            raise ValueError("voxel-grid downsampling is not available in the lock-step batch: use SequenceRunner")
         self.ctx = ctx
         self.runners = [SequenceRunner(None, max_iterations, threshold, fx, cx, **params) for _ in range(n_streams)]
         self.kw = self.runners[0].kw

@@ -620,6 +620,46 @@ int icpk_reduce_p2l(icpk_ctx *ctx, float max_dist, double *sums, int64_t *count)
 /* host solve of the step: 0 ok, ICPK_W_DEGENERATE if not positive definite */
 int icpk_solve_point_to_plane(const double sums[28], double R[9], double t[3]);
 
+/* ---- voxel-grid downsampling (K11; extension: the reference plans it, TODO:3 "subsample points better - Grid") ----
+ * Replaces one of the context's clouds by one point per occupied cube of edge `leaf`.  Unlike icpk_set_subsample it
+ * works on any cloud the context holds, however it got there, and thins by space, not by pixel.  The rule, with
+ * L = (double)leaf and float64 arithmetic throughout; the n input points are taken in index order:
+ *   voxel     per axis u = (double)p / L, v = floor(u); the point's voxel is (vx, vy, vz).  A point with a non-finite
+ *             coordinate, or with |v| > 2^20 on any axis, is DROPPED: it belongs to no voxel (n_dropped counts them)
+ *   order     voxels are ordered by the lowest input index among their members; output point k belongs to the k-th
+ *             voxel in that order (so the output keeps the input's order, image order included)
+ *   FIRST     output k = the member with the lowest input index, its three floats unchanged
+ *   CENTROID  per axis f = u - v (exact, in [0, 1)), q = (int64)rint(f * 2^30) (ties to even), S = the sum of q over
+ *             the members (exact, int64), m = the member count:
+ *               output coordinate = (float)(((double)v + ((double)S / (double)m) / 2^30) * L)
+ *             The sum is an integer so that it does not depend on the order in which the members arrive: the same
+ *             bits on every run.  Against the float64 mean of the members a coordinate moves by at most leaf * 2^-30
+ *             plus the rounding to float.
+ *   normals   (which = 1 and the context holds target normals; their components are finite) FIRST: the
+ *             representative's normal unchanged.  CENTROID: per component N = the sum over the members of
+ *             (int64)rint((double)n_c * 2^30); g = sqrt(Nx^2 + Ny^2 + Nz^2) in float64; the output normal is
+ *             (float)(N_c / g), or (0, 0, 0) when g == 0 (such a point never pairs)
+ * An empty cloud gives an empty cloud; if every point is dropped the cloud becomes empty (the next alignment reports
+ * what it reports for an empty source or target).
+ * After the call the downsampled cloud IS the context's cloud, as after icpk_set_source_device / icpk_set_target_device
+ * on the result: for the source it is both the uploaded and the working source; for the target the normals, if any,
+ * are replaced by the downsampled ones; everything derived from the old cloud is dropped (associations, seeds, the
+ * target's indexes; ICPK_NN_MAP needs a new icpk_map_lookup_to_target).  One host wait (the two counts).
+ * Where it does not apply: nothing downsamples inside icpk_backproject*, icpk_align_batch / _device or
+ * icpk_align_frames_batch (their clouds never become the context's own between back-projection and loop). */
+#define ICPK_VOXEL_FIRST 0
+#define ICPK_VOXEL_CENTROID 1
+/* which: 0 = the working source (as icpk_get_source returns it), 1 = the target (as icpk_get_target returns it).
+ * n_out / n_dropped: either may be NULL.  ICPK_E_ARG for another `which` or mode, or a leaf that is not finite and
+ * > 0 (nothing changes); ICPK_E_NOT_SET if that cloud has not been set. */
+int icpk_voxel_downsample(icpk_ctx *ctx, int32_t which, float leaf, int32_t mode, int32_t *n_out, int32_t *n_dropped);
+/* The grouping of the last icpk_voxel_downsample on this context (it stays on the device until asked for):
+ *   first_index[n_out], count[n_out]   per output point: lowest member index, member count
+ *   out_of_point[n_in]                 per input point: the output point of its voxel, -1 if dropped
+ * Any may be NULL; ICPK_E_NOT_SET before the first call. */
+int icpk_get_voxel_groups(icpk_ctx *ctx, int32_t *n_in, int32_t *n_out, int32_t *first_index, int32_t *count,
+                          int32_t *out_of_point);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity

@@ -1,0 +1,435 @@
+"""Voxel-grid downsampling on the device (icpk_voxel_downsample, K11) against the numpy model of the rule
+(tests/voxel_model.py): points, normals, first_index, count, out_of_point, n_out and n_dropped bit for bit -- no
+tolerance anywhere -- then the state the call leaves behind, the loop on the downsampled pair, and the layers above."""
+import os
+import struct
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import voxel_model as vm
+from icp_slam_prototype_amd import binding, build, sequence, synth
+
+pytestmark = pytest.mark.gpu
+
+MODES = [binding.VOXEL_FIRST, binding.VOXEL_CENTROID]
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    build.build()
+    c = binding.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def kinect():
+    return synth.kinect_pair()
+
+
+@pytest.fixture(scope="module")
+def dense():
+    return synth.dense_pair()
+
+
+def _library(ctx, pts, leaf, mode, which, normals=None):
+    """The cloud through the library: what vm.downsample returns, read back from the context."""
+    if which == 0:
+        ctx.set_source(pts)
+    else:
+        ctx.set_target(pts)
+        if normals is not None:
+            ctx.set_target_normals(normals)
+    return _downsample_resident(ctx, leaf, mode, which, normals is not None)
+
+
+def _downsample_resident(ctx, leaf, mode, which, with_normals=False):
+    n_out, n_dropped = ctx.voxel_downsample(which, leaf, mode)
+    g = ctx.get_voxel_groups()
+    assert g["n_out"] == n_out
+    return dict(points=ctx.get_source() if which == 0 else ctx.get_target(),
+                normals=ctx.get_target_normals() if with_normals else None, first_index=g["first_index"],
+                count=g["count"], out_of_point=g["out_of_point"], n_out=n_out, n_dropped=n_dropped)
+
+
+def _check(ctx, pts, leaf, mode, which, normals=None):
+    want = vm.downsample(pts, leaf, mode, normals)
+    got = _library(ctx, pts, leaf, mode, which, normals)
+    diff = vm.same(want, got)
+    assert diff is None, diff
+    assert (ctx.source_size if which == 0 else ctx.target_size) == want["n_out"]
+    return want
+
+
+# ------------------------------------------------------------------------------------------------ parity on clouds --
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("leaf", [0.02, 0.05, 0.2])
+@pytest.mark.parametrize("which", [0, 1])
+def test_kinect_clouds(ctx, kinect, which, leaf, mode):
+    for name in ("source", "target"):
+        assert kinect[name].shape[1] > 90000
+        want = _check(ctx, kinect[name], leaf, mode, which)
+        assert 0 < want["n_out"] < kinect[name].shape[1] and want["n_dropped"] == 0
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("leaf", [0.02, 0.05, 0.2])
+@pytest.mark.parametrize("which", [0, 1])
+def test_dense_clouds(ctx, dense, which, leaf, mode):
+    name = "source" if which == 0 else "target"
+    assert dense[name].shape[1] == 1_000_000
+    want = _check(ctx, dense[name], leaf, mode, which)
+    assert 0 < want["n_out"] < 1_000_000
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("normals_mode", [binding.NORMALS_CROSS, binding.NORMALS_REFERENCE])
+def test_target_with_normals(ctx, kinect, normals_mode, mode):
+    """The target and its normals as icpk_backproject_with_normals leaves them (zero normals included)."""
+    n = ctx.backproject_with_normals(kinect["depth_tgt"], normals_mode)
+    tgt, nrm = ctx.get_target(), ctx.get_target_normals()
+    assert tgt.shape[1] == n and (np.abs(nrm).sum(0) == 0).any() and (np.abs(nrm).sum(0) > 0).any()
+    for leaf in (0.02, 0.05, 0.2):
+        ctx.backproject_with_normals(kinect["depth_tgt"], normals_mode)
+        want = vm.downsample(tgt, leaf, mode, nrm)
+        got = _downsample_resident(ctx, leaf, mode, 1, True)
+        diff = vm.same(want, got)
+        assert diff is None, (leaf, diff)
+
+
+# -------------------------------------------------------------------------------------------------- edge geometry --
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("which", [0, 1])
+def test_all_points_in_one_voxel(ctx, which, mode):
+    """The contended case: 200 000 points, one slot."""
+    rng = np.random.default_rng(1)
+    p = rng.uniform(1.0, 1.25, (3, 200_000)).astype(np.float32)
+    p = np.minimum(p, np.nextafter(np.float32(1.25), np.float32(0)))
+    want = _check(ctx, p, 0.25, mode, which)
+    assert want["n_out"] == 1 and want["count"][0] == 200_000
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_every_point_in_its_own_voxel(ctx, mode):
+    rng = np.random.default_rng(2)
+    g = np.stack(np.meshgrid(np.arange(-20, 20), np.arange(-18, 18), np.arange(-17, 18), indexing="ij")).reshape(3, -1)
+    p = ((g + rng.uniform(0.1, 0.9, g.shape)) * 0.25).astype(np.float32)[:, rng.permutation(g.shape[1])]
+    want = _check(ctx, p, 0.25, mode, 0)
+    assert want["n_out"] == p.shape[1] == 50400 and np.array_equal(want["first_index"], np.arange(p.shape[1]))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("leaf", [0.25, 0.05])
+def test_faces_negative_coordinates_and_signed_zero(ctx, leaf, mode):
+    rng = np.random.default_rng(3)
+    k = rng.integers(-40, 41, (3, 6000))
+    p = (k.astype(np.float32) * np.float32(leaf)).astype(np.float32)   # exactly on voxel faces (as float32 has them)
+    p[:, 3000:] += rng.uniform(-1, 1, (3, 3000)).astype(np.float32) * np.float32(leaf)
+    p[0, :50] = np.float32(-0.0)
+    p[1, 50:100] = np.float32(0.0)
+    p[2, 100:150] = -np.abs(p[2, 100:150])
+    p[:, 150:300] = p[:, :150]                                           # duplicates
+    for which in (0, 1):
+        want = _check(ctx, p, leaf, mode, which)
+        assert (want["count"] > 1).any() and (want["points"] < 0).any()
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("which", [0, 1])
+def test_unusable_points_are_dropped_and_counted(ctx, which, mode):
+    rng = np.random.default_rng(4)
+    leaf = np.float32(0.05)
+    p = rng.uniform(-3, 3, (3, 20000)).astype(np.float32)
+    bad = rng.choice(20000, 600, replace=False)
+    vals = [np.nan, np.inf, -np.inf, leaf * np.float32(2 ** 20 + 2), -leaf * np.float32(2 ** 20 + 2), np.float32(3e38),
+            np.float32(-3e38)]
+    for j, i in enumerate(bad):
+        p[j % 3, i] = vals[j % len(vals)]
+    # the last voxels inside the limit stay
+    p[0, bad[0]] = leaf * np.float32(2 ** 20 - 1)
+    p[1, bad[1]] = -leaf * np.float32(2 ** 20 - 1)
+    want = _check(ctx, p, leaf, mode, which)
+    assert want["n_dropped"] == 598 and (want["out_of_point"][bad[2:]] == -1).all() and (want["out_of_point"][bad[:2]] >= 0).all()
+    # the rest is unaffected: the same voxels, members and values as the cloud without the unusable points gives
+    keep = np.setdiff1d(np.arange(20000), bad[2:])
+    got = _library(ctx, np.ascontiguousarray(p[:, keep]), leaf, mode, which)
+    assert got["n_dropped"] == 0 and got["points"].tobytes() == want["points"].tobytes()
+    assert np.array_equal(got["count"], want["count"]) and np.array_equal(keep[got["first_index"]], want["first_index"])
+    # every point dropped: the cloud becomes empty
+    q = np.full((3, 1000), np.nan, np.float32)
+    want = _check(ctx, q, leaf, mode, which)
+    assert want["n_out"] == 0 and want["n_dropped"] == 1000
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("which", [0, 1])
+def test_empty_and_single_point(ctx, which, mode):
+    want = _check(ctx, np.zeros((3, 0), np.float32), 0.05, mode, which)
+    assert want["n_out"] == 0 and want["n_dropped"] == 0
+    want = _check(ctx, np.float32([[1.5], [-2.25], [0.125]]), 0.05, mode, which)
+    assert want["n_out"] == 1 and want["count"][0] == 1
+    if mode == binding.VOXEL_FIRST:
+        assert np.array_equal(want["points"], np.float32([[1.5], [-2.25], [0.125]]))
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_quotients_that_round_differently_in_float(ctx, mode):
+    """Coordinates whose voxel differs when p / leaf is taken in float32 instead of float64: the rule says float64."""
+    leaf = np.float32(0.05)
+    c = np.random.default_rng(3).uniform(0.5, 6.0, 3_000_000).astype(np.float32)
+    v64 = np.floor(c.astype(np.float64) / np.float64(leaf))
+    v32 = np.floor(c / leaf).astype(np.float64)
+    hard = c[v64 != v32]
+    assert hard.size >= 3, hard.size  # (a few in a million)
+    # each of them on every axis in turn, among ordinary points
+    p = np.ascontiguousarray(c[:30000].reshape(3, -1))
+    for j, h in enumerate(np.tile(hard, 3)):
+        p[j % 3, 100 * j] = h
+    want = _check(ctx, p, leaf, mode, 0)
+    wrong = np.floor(p / leaf)  # what a float32 quotient would give
+    assert (wrong != vm.voxel_coords(p, leaf)[1]).any()
+    assert want["n_out"] > 0
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_repeatable(ctx, kinect, mode):
+    """Five runs, one result: nothing depends on the order in which a voxel's members arrive."""
+    nrm = np.random.default_rng(6).normal(0, 1, kinect["target"].shape).astype(np.float32)
+    runs = []
+    for _ in range(5):
+        r = _library(ctx, kinect["target"], 0.2, mode, 1, nrm)
+        runs.append(b"".join(np.ascontiguousarray(r[k]).tobytes() for k in ("points", "normals", "first_index", "count", "out_of_point")))
+    assert all(x == runs[0] for x in runs[1:])
+    one = np.random.default_rng(7).uniform(1.0, 1.2, (3, 200_000)).astype(np.float32)
+    runs = [_library(ctx, one, 0.25, mode, 0)["points"].tobytes() for _ in range(5)]
+    assert all(x == runs[0] for x in runs[1:])
+
+
+# ----------------------------------------------------------------------------------------------------------- state --
+def test_bad_arguments_change_nothing(ctx, kinect):
+    ctx.set_source(kinect["source"])
+    for kw in (dict(leaf=0.0), dict(leaf=-1.0), dict(leaf=np.inf), dict(leaf=np.nan), dict(mode=2), dict(mode=-1),
+               dict(which=2), dict(which=-1)):
+        with pytest.raises(binding.IcpkError) as e:
+            ctx.voxel_downsample(**kw)
+        assert e.value.code == binding.E_ARG
+    assert ctx.source_size == kinect["source"].shape[1]
+    assert np.array_equal(ctx.get_source().view(np.uint32), kinect["source"].view(np.uint32))
+    with binding.Context(0) as fresh:
+        for which in (0, 1):
+            with pytest.raises(binding.IcpkError) as e:
+                fresh.voxel_downsample(which)
+            assert e.value.code == binding.E_NOT_SET
+        assert fresh._lib.icpk_get_voxel_groups(fresh._h, None, None, None, None, None) == binding.E_NOT_SET
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_source_state_after_downsampling(ctx, kinect, mode):
+    ctx.set_target(kinect["target"])
+    ctx.set_source(kinect["source"])
+    ctx.nn(binding.NN_GRID, fetch=False)
+    ctx.transform_source(synth.rot_xyz_deg(0, 1, 0).astype(np.float32), np.float32([0.01, 0, 0]))
+    moved = ctx.get_source()
+    want = vm.downsample(moved, 0.05, mode)  # (the call reads the WORKING source)
+    assert ctx.voxel_downsample(0, 0.05, mode) == (want["n_out"], 0)
+    assert ctx.source_size == want["n_out"]
+    assert ctx.get_source().tobytes() == want["points"].tobytes()
+    ctx.reset_source()
+    assert ctx.source_size == want["n_out"] and ctx.get_source().tobytes() == want["points"].tobytes()
+    with pytest.raises(binding.IcpkError):  # the associations of the old cloud are gone
+        ctx.get_associations()
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_target_state_after_downsampling(ctx, kinect, oracle, mode):
+    """Every index over the target is rebuilt: the NN of every nn_mode is the brute force over the model's clouds."""
+    src = np.ascontiguousarray(kinect["source"][:, ::9])
+    want = vm.downsample(kinect["target"], 0.05, mode)
+    oidx, odist = oracle.nn_bruteforce(src, want["points"], threads=oracle.max_threads())
+    for nn_mode in (binding.NN_EXACT, binding.NN_FILTERED, binding.NN_PRUNED, binding.NN_GRID):
+        ctx.set_target(kinect["target"])
+        ctx.set_source(src)
+        ctx.nn(nn_mode, fetch=False)  # (the old target's indexes and seeds exist)
+        assert ctx.voxel_downsample(1, 0.05, mode)[0] == want["n_out"]
+        idx, dist = ctx.nn(nn_mode)
+        assert np.array_equal(idx, oidx), nn_mode
+        assert np.array_equal(dist.view(np.uint32), odist.view(np.uint32)), nn_mode
+    # the map's lookup target stops being one
+    ctx.map_reset()
+    ctx.map_update_points(binding.MAP_ADD_CLOUD, kinect["target"][:, :5000], 25)
+    ctx.map_lookup_to_target()
+    ctx.set_source(src)
+    ctx.nn(binding.NN_MAP, fetch=False)
+    ctx.voxel_downsample(1, 0.05, mode)
+    with pytest.raises(binding.IcpkError) as e:
+        ctx.nn(binding.NN_MAP)
+    assert e.value.code == binding.E_ARG
+    ctx.map_release()
+
+
+# ------------------------------------------------------------------------------------------------------------ loop --
+def _stats(st):
+    return (st.iterations, st.status, st.final_pairs, np.float32(st.final_mse).tobytes())
+
+
+def _trace_bytes(tr):
+    return [(t["R"].tobytes(), t["t"].tobytes(), t["n_pairs"], t["mse"].tobytes()) for t in tr]
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("host_loop", [0, 1])
+@pytest.mark.parametrize("solve", [binding.SOLVE_KABSCH, binding.SOLVE_REFERENCE, binding.SOLVE_POINT_TO_PLANE])
+def test_align_on_a_pair_downsampled_on_the_device(ctx, solve, host_loop, mode):
+    p = synth.kinect_pair(rows=240, cols=320, seed=4)
+    leaf = 0.05
+    p2l = solve == binding.SOLVE_POINT_TO_PLANE
+    kw = dict(solve=solve, host_loop=host_loop, max_iterations=8)
+    ctx.backproject_with_normals(p["depth_tgt"], binding.NORMALS_CROSS)
+    ctx.backproject(p["depth_src"], which=0)
+    tgt, nrm, src = ctx.get_target(), ctx.get_target_normals(), ctx.get_source()
+    ctx.voxel_downsample(1, leaf, mode)
+    ctx.voxel_downsample(0, leaf, mode)
+    T, st, rc = ctx.align(**kw)
+    tr = ctx.get_trace(8)
+    wt, ws = vm.downsample(tgt, leaf, mode, nrm), vm.downsample(src, leaf, mode)
+    with binding.Context(0) as fresh:
+        fresh.set_target(wt["points"])
+        fresh.set_target_normals(wt["normals"])
+        fresh.set_source(ws["points"])
+        T2, st2, rc2 = fresh.align(**kw)
+        tr2 = fresh.get_trace(8)
+        assert fresh.get_source().tobytes() == ctx.get_source().tobytes()
+    assert rc == rc2 and st.iterations > 0 and (st.final_pairs > 100 or p2l)
+    assert T.tobytes() == T2.tobytes() and _stats(st) == _stats(st2) and _trace_bytes(tr) == _trace_bytes(tr2)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_downsample_right_after_a_device_loop(ctx, kinect, mode):
+    """The loop leaves the aligned source packed in its records: the call unpacks it first."""
+    kw = dict(solve=binding.SOLVE_KABSCH, max_iterations=4, fixed_iterations=1)
+    ctx.set_target(kinect["target"])
+    ctx.set_source(kinect["source"])
+    ctx.align(**kw)
+    aligned = ctx.get_source()
+    assert not np.array_equal(aligned, kinect["source"])
+    want = vm.downsample(aligned, 0.05, mode)
+    ctx.set_target(kinect["target"])
+    ctx.set_source(kinect["source"])
+    ctx.align(**kw)
+    got = _downsample_resident(ctx, 0.05, mode, 0)
+    diff = vm.same(want, got)
+    assert diff is None, diff
+
+
+# ------------------------------------------------------------------------------------------------ the layers above --
+def _frames(n=4, rows=120, cols=160, seed=1):
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(n):
+        d = synth.render_room_depth(rows, cols, synth.rot_xyz_deg(0, 0.5 * k, 0), np.array([0.01 * k, 0, 0]),
+                                    noise_sigma=0.002, rng=rng)
+        d[rng.random(d.shape) > 0.5] = 0
+        out.append(d.astype(np.uint16))
+    return out
+
+
+class _PlainRunner(sequence.SequenceRunner):
+    """A runner that has never heard of the option: the step as it was before it existed."""
+
+    def step(self, depth, timestamp=None, ground_truth=None):
+        depth = np.ascontiguousarray(depth, np.uint16)
+        if self.previous is None:
+            self.previous = depth.copy()
+            return None
+        c = self.ctx
+        c.backproject_pair(depth, self.previous, R=self.camera_rotation, t=self.camera_position, fx=self.fx, cx=self.cx)
+        T, st, rc = c.align(last_rotation=self.last_rotation, last_translation=self.last_translation, **self.kw)
+        return self._advance(depth, T, st, rc, c.get_trace(max(self.kw["max_iterations"], 1)), timestamp, ground_truth)
+
+
+class _HandRunner(sequence.SequenceRunner):
+    """The calls the option stands for, made by hand."""
+
+    def __init__(self, ctx, leaf, mode, **kw):
+        super().__init__(ctx, **kw)
+        self.leaf, self.mode = leaf, mode
+        self.sizes = []
+
+    def step(self, depth, timestamp=None, ground_truth=None):
+        depth = np.ascontiguousarray(depth, np.uint16)
+        if self.previous is None:
+            self.previous = depth.copy()
+            return None
+        c = self.ctx
+        c.backproject_pair(depth, self.previous, R=self.camera_rotation, t=self.camera_position, fx=self.fx, cx=self.cx)
+        nt = c.voxel_downsample(1, self.leaf, self.mode)[0]
+        ns = c.voxel_downsample(0, self.leaf, self.mode)[0]
+        self.sizes.append((ns, nt))
+        T, st, rc = c.align(last_rotation=self.last_rotation, last_translation=self.last_translation, **self.kw)
+        return self._advance(depth, T, st, rc, c.get_trace(max(self.kw["max_iterations"], 1)), timestamp, ground_truth)
+
+
+def _run(runner, frames):
+    out = []
+    for d in frames:
+        r = runner.step(d)
+        if r is not None:
+            out.append((r["T"].tobytes(), r["status"], r["iterations"], r["mse"].tobytes(), r["csv"]))
+    return out
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_sequence_runner_option(mode):
+    frames = _frames()
+    with binding.Context(0) as a, binding.Context(0) as b, binding.Context(0) as c, binding.Context(0) as d:
+        hand = _HandRunner(b, 0.05, mode)
+        with_opt = _run(sequence.SequenceRunner(a, voxel_leaf=0.05, voxel_mode=mode), frames)
+        assert with_opt == _run(hand, frames) and len(with_opt) == 3
+        unset = _run(sequence.SequenceRunner(c), frames)
+        assert unset == _run(_PlainRunner(d), frames)
+        assert unset != with_opt and all(ns < 9000 and nt < 9000 for ns, nt in hand.sizes)
+        with pytest.raises(ValueError):
+            sequence.MultiSequenceRunner(a, 2, voxel_leaf=0.05)
+
+
+@pytest.mark.parametrize("leaf,mode", [(0.05, binding.VOXEL_CENTROID), (0.05, binding.VOXEL_FIRST), (0.0, binding.VOXEL_CENTROID)])
+def test_cpp_tracker_option(leaf, mode):
+    """icp::Tracker with voxelLeaf / voxelMode (tests/cpp/test_voxel.cpp) against the same calls made by hand; with the
+    option untouched, against a runner that never heard of it."""
+    exe = build.build_voxel_test()
+    frames = _frames()
+    rows, cols = frames[0].shape
+    with tempfile.TemporaryDirectory() as td:
+        fin, fout = os.path.join(td, "frames.u16"), os.path.join(td, "out.bin")
+        with open(fin, "wb") as f:
+            for d in frames:
+                f.write(d.tobytes())
+        out = subprocess.run([exe, fin, str(rows), str(cols), str(len(frames)), repr(leaf), str(mode), "16", fout],
+                             capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stderr
+        raw = open(fout, "rb").read()
+    with binding.Context(0) as c:
+        runner = _HandRunner(c, leaf, mode) if leaf > 0 else _PlainRunner(c)
+        off = 0
+        for i in range(1, len(frames)):
+            if i == 1:
+                runner.step(frames[0])
+            r = runner.step(frames[i])
+            rc, iters, ns, nt = struct.unpack_from("<4i", raw, off)
+            off += 16
+            vals = np.frombuffer(raw, np.float32, 16 + 9 + 3, off)
+            off += 4 * 28
+            assert (rc, iters) == (r["status"], r["iterations"])
+            assert vals[:16].tobytes() == np.ascontiguousarray(r["T"], np.float32).tobytes()
+            assert vals[16:25].tobytes() == runner.camera_rotation.tobytes() and vals[25:28].tobytes() == runner.camera_position.tobytes()
+            assert (ns, nt) == (c.source_size, c.target_size)
+            if leaf > 0:
+                assert (ns, nt) == runner.sizes[-1]
+        rc, n, size, bad_leaf, bad_mode = struct.unpack_from("<5i", raw, off)
+        off += 20
+        want = vm.downsample(c.get_source(), 0.1, vm.FIRST)
+        assert (rc, n, size) == (0, want["n_out"], want["n_out"]) and (bad_leaf, bad_mode) == (binding.E_ARG, binding.E_ARG)
+        assert off == len(raw)
