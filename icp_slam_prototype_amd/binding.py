@@ -29,6 +29,7 @@ NSUM_W, NP2L_W = 21, 30  # icpk_reduce_weighted: the weighted sums, then W and t
 ROBUST_NONE, ROBUST_HUBER, ROBUST_TUKEY = 0, 1, 2
 SCALE_FIXED, SCALE_MEDIAN = 0, 1
 VOXEL_FIRST, VOXEL_CENTROID = 0, 1  # icpk_voxel_downsample: the representative / the fixed-point centroid
+NORMALS_KEEP_MOMENTS = 1  # icpk_estimate_target_normals: keep the 10 int64 per point for icpk_get_normal_stats
 
 # every symbol include/icpk.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -51,6 +52,7 @@ SYMBOLS = [
     "icpk_align_frames_batch", "icpk_get_frames_trace", "icpk_release_frame_streams",
     "icpk_set_robust", "icpk_get_robust_trace", "icpk_reduce_weighted",
     "icpk_voxel_downsample", "icpk_get_voxel_groups",
+    "icpk_estimate_target_normals", "icpk_get_normal_stats",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -260,6 +262,8 @@ def load():
                                          C.POINTER(C.c_int64), fp, fp, dp]
     lib.icpk_voxel_downsample.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_int32, ip, ip]
     lib.icpk_get_voxel_groups.argtypes = [C.c_void_p, ip, ip, ip, ip, ip]
+    lib.icpk_estimate_target_normals.argtypes = [C.c_void_p, C.c_float, C.c_int32, fp, C.c_int32]
+    lib.icpk_get_normal_stats.argtypes = [C.c_void_p, ip, ip, ip, fp, C.POINTER(C.c_int64)]
     _lib = lib
     return lib
 
@@ -719,6 +723,31 @@ class Context:
         self._chk(self._lib.icpk_get_voxel_groups(self._h, None, None, first.ctypes.data_as(ip), count.ctypes.data_as(ip),
                                                   oop.ctypes.data_as(ip)))
         return dict(n_in=n_in.value, n_out=n_out.value, first_index=first, count=count, out_of_point=oop)
+
+    # -- target normals from the target's geometry (icpk_estimate_target_normals) -------
+    def estimate_target_normals(self, radius, min_neighbors=5, viewpoint=None, keep_moments=False):
+        """Per target point the normal of the plane fitted to its neighbours within `radius`, oriented towards
+        `viewpoint` ((3,) or None), installed as the target normals (include/icpk.h).  Stream-ordered: no host wait."""
+        v = None if viewpoint is None else _f(viewpoint).reshape(3)
+        self._keep_normals_moments = bool(keep_moments)
+        self._chk(self._lib.icpk_estimate_target_normals(self._h, float(radius), int(min_neighbors),
+                                                         None if v is None else _fp(v),
+                                                         NORMALS_KEEP_MOMENTS if keep_moments else 0))
+
+    def get_normal_stats(self):
+        """What the last estimate_target_normals found: dict(n, n_valid, count (n,) int32, curvature (n,) float32, and
+        moments (n, 10) int64 -- m, S_x S_y S_z, S_xx S_xy S_xz S_yy S_yz S_zz -- if they were kept)."""
+        n, nv = C.c_int32(0), C.c_int32(0)
+        self._chk(self._lib.icpk_get_normal_stats(self._h, C.byref(n), C.byref(nv), None, None, None))
+        count = np.empty(n.value, np.int32)
+        curv = np.empty(n.value, np.float32)
+        mom = np.empty((n.value, 10), np.int64) if getattr(self, "_keep_normals_moments", False) else None
+        self._chk(self._lib.icpk_get_normal_stats(self._h, None, None, count.ctypes.data_as(C.POINTER(C.c_int32)), _fp(curv),
+                                                  None if mom is None else mom.ctypes.data_as(C.POINTER(C.c_int64))))
+        out = dict(n=n.value, n_valid=nv.value, count=count, curvature=curv)
+        if mom is not None:
+            out["moments"] = mom
+        return out
 
     # -- loop ---------------------------------------------------------------------
     def align(self, params=None, **kw):

@@ -14,7 +14,7 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "kernels_nn.hip", "kernels_reduce.hip", "kernels_transform.hip", "kernels_backproject.hip", "kernels_sort.hip",
            "kernels_nn_pruned.hip", "kernels_loop.hip", "kernels_grid.hip", "kernels_frontend.hip",
            "icpk_map.cpp", "kernels_map.hip", "icpk_fast.cpp", "kernels_fast.hip", "kernels_map_nn.hip", "kernels_robust.hip",
-           "icpk_voxel.cpp", "kernels_voxel.hip"]
+           "icpk_voxel.cpp", "kernels_voxel.hip", "icpk_normals.cpp", "kernels_normals.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -150,6 +150,23 @@ def build_voxel_test(force=False):
     return VOXEL_TEST
 
 
+NORMALS_TEST = os.path.join(LIBDIR, "test_normals")
+
+
+def build_normals_test(force=False):
+    """Host-only C++ program over icp::Engine::estimateTargetNormals / normalStats (g++, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_normals.cpp")
+    hdr = os.path.join(HERE, "include", "icp_align.hpp")
+    build()
+    newest = max(os.path.getmtime(p) for p in (src, hdr, LIB))
+    if not force and os.path.exists(NORMALS_TEST) and os.path.getmtime(NORMALS_TEST) >= newest:
+        return NORMALS_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", NORMALS_TEST])
+    return NORMALS_TEST
+
+
 FAKE_RCCL = os.path.join(LIBDIR, "libfake_rccl.so")
 
 
@@ -191,3 +208,4 @@ if __name__ == "__main__":
     print(build_map_fast_test(force="--force" in sys.argv))
     print(build_map_dense_test(force="--force" in sys.argv))
     print(build_voxel_test(force="--force" in sys.argv))
+    print(build_normals_test(force="--force" in sys.argv))

@@ -218,6 +218,7 @@ void target_changed(icpk_ctx* ctx, bool keep_normals) {
   ctx->tgt_lookup = false;
   ctx->have_seed = false;
   if (!keep_normals) ctx->have_normals = false;
+  ctx->have_nstats = false;  // (icpk_get_normal_stats speaks of the target it was estimated on)
 }
 
 void reset_outputs(float T_out[16], icpk_stats* stats) {
@@ -443,6 +444,7 @@ int icpk_set_target_normals(icpk_ctx* ctx, const float* nx, const float* ny, con
   int rc = upload_cloud(ctx, ctx->nrm, nx, ny, nz, n, 0.f, hipMemcpyHostToDevice);
   if (rc) return rc;
   ctx->have_normals = true;
+  ctx->have_nstats = false;
   return ICPK_OK;
 }
 

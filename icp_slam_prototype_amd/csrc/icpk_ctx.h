@@ -2,7 +2,7 @@
 // host-side translation unit calls (icpk_api.cpp: context and clouds; icpk_sweep.cpp: NN sweeps and reductions;
 // icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
 // entry; icpk_frontend.cpp: depth images;
-// icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp).  Not part of the ABI.
+// icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -326,6 +326,16 @@ struct icpk_ctx {
   icpk::DevBuf<int> vox_oop;               // [n_in]
   bool have_vox = false;         // a downsample has run: the three above describe it
   int vox_n_in = 0, vox_n_out = 0;
+  // target normals from the target's geometry (icpk_estimate_target_normals, K12; icpk_normals.cpp): what
+  // icpk_get_normal_stats returns, kept on the device until asked for
+  icpk::DevBuf<long long> nrm_moments;   // [n][NRM_MOMENTS]
+  icpk::DevBuf<int> nrm_count;           // [n]
+  icpk::DevBuf<float> nrm_curv;          // [n]
+  icpk::DevBuf<int> nrm_valid;           // points with a normal ...
+  icpk::PinnedBuf<int> nrm_valid_host;   // ... and where the host reads it
+  bool have_nstats = false;      // the four above describe the normals of the target the context holds now
+  bool nstats_moments = false;   // ... and the caller asked for the moments to be kept
+  int nstats_n = 0;
   int loop_nact = icpk::NSUM;      // device loop: sums the running alignment's step consumes (NSUM_REF or NSUM)
   int profile_phase = 0;     // alignments profiled so far (offsets the sampled launches, see profile_stride)
   int qperm_kind = 0;        // what qperm holds: 1 Morton order (pruned scan), 2 cell order (grid scan)
@@ -410,6 +420,8 @@ void clear_trace(icpk_ctx* ctx);                        // icpk_get_trace's reco
 // ---- icpk_sweep.cpp: device buffers, NN sweeps, reductions ----
 int ensure_cloud(icpk_ctx* ctx, Cloud& c, int n);  // room for n points (the contents are undefined after a resize)
 int ensure_assoc(icpk_ctx* ctx, int nq);
+// K1d's index of the target (geometry, cell table, cell-sorted copy): built unless have_grid; everything is enqueued
+int prepare_grid_target(icpk_ctx* ctx);
 // the working source planes hold the cloud icpk_get_source would return (a device loop may leave them to be unpacked)
 int ensure_unpacked(icpk_ctx* ctx);
 int flush_loop_init(icpk_ctx* ctx);

@@ -624,4 +624,25 @@ struct VoxelArgs {
 // the five launches of one downsample; n <= 0: nothing
 void launch_voxel_downsample(const VoxelArgs& a, hipStream_t s);
 
+// kernels_normals.hip -- K12, target normals from the target's own geometry (icpk_estimate_target_normals)
+constexpr int NRM_MOMENTS = 10;  // per point: m, S_x S_y S_z, S_xx S_xy S_xz S_yy S_yz S_zz (int64 each)
+struct NormalsArgs {
+  const float4* t4;           // the target sorted by cell (x, y, z, original index): K1d's index
+  const int* cell_start;
+  const GridInfo* gi;
+  const float *x, *y, *z;     // the target in the caller's order, n points
+  int n;
+  float radius;
+  int min_neighbors;
+  int has_viewpoint;
+  float viewpoint[3];
+  long long* moments;         // [n][NRM_MOMENTS], caller's order
+  float *nx, *ny, *nz;        // [n]
+  int* count;                 // [n]
+  float* curvature;           // [n]
+  int* n_valid;               // added to: zero before the launch
+};
+// the two launches of one estimate (moments, then the eigen-solve); n <= 0: nothing
+void launch_estimate_normals(const NormalsArgs& a, hipStream_t s);
+
 }  // namespace icpk

@@ -143,7 +143,7 @@ static int ensure_grid_buffers(icpk_ctx* ctx) {
 // Everything is enqueued: the grid's size stays on the device (GridInfo), the counting sort's
 // zero fill and scan read it there -- no host round trip, so the frame-batch mode can build the
 // next group's grids in the shadow of the running loop.
-static int prepare_grid_target(icpk_ctx* ctx) {
+int prepare_grid_target(icpk_ctx* ctx) {
   const int nt = ctx->tgt.n;
   int rc = ensure_grid_buffers(ctx);
   if (rc || ctx->have_grid) return rc;

@@ -168,15 +168,7 @@ __global__ void grid_info_batch_kernel(const SetupBatchOf<InfoArgs> b) {
   grid_info_body(a.fb, a.nparts, a.n, a.ppc, a.xdiv, a.max_cells, a.g);
 }
 
-// The ONE mapping coordinate -> cell index along an axis, used for targets and for the
-// corners of a query's cube alike.  Every step is monotone non-decreasing in v (float
-// subtraction, multiplication by a positive constant, clamp, truncation of a non-negative
-// value), so a <= t <= b implies cell(a) <= cell(t) <= cell(b).  NaN maps to cell 0.
-__device__ __forceinline__ int grid_cell(float v, float lo, float inv_h, int n) {
-  float f = (v - lo) * inv_h;
-  f = __builtin_fminf(__builtin_fmaxf(f, 0.f), (float)(n - 1));
-  return (int)f;
-}
+// (grid_cell, the ONE mapping coordinate -> cell index along an axis, and cube_cells live in nn_device.h: K12 shares them)
 
 // Counting sort by cell, used for the targets (set-up) and for the query order (once per
 // alignment): slot within the cell by atomics -- the order inside a cell may be whatever the
@@ -535,12 +527,6 @@ __device__ __forceinline__ float axis_gap(float q, float lo, float h, int i, int
   const float below = i > 0 ? a - q : 0.f;           // (cell 0 extends to -inf)
   const float above = i < n - 1 ? q - (a + h) : 0.f;  // (cell n - 1 extends to +inf)
   return __builtin_fmaxf(__builtin_fmaxf(below, above) - slop, 0.f);
-}
-
-__device__ __forceinline__ void cube_cells(float q, float r, float lo, float inv_h, int n, int& c0, int& c1) {
-  const float rr = __builtin_fmaf(r, 1.0f + 0x1p-19f, __builtin_fmaf(__builtin_fabsf(q), 0x1p-21f, 0x1p-74f));
-  c0 = grid_cell(q - rr, lo, inv_h, n);
-  c1 = grid_cell(q + rr, lo, inv_h, n);
 }
 
 // S adjacent lanes per query; queries in cell order (neighbouring queries read the same

@@ -126,4 +126,23 @@ __device__ __forceinline__ bool box_may_hit(const float (&qx)[Q], const float (&
   return hit;
 }
 
+// ---- uniform grid over the target (kernels_grid.hip K1d, kernels_normals.hip K12) -------
+// The ONE mapping coordinate -> cell index along an axis, used for targets and for the
+// corners of a query's cube alike.  Every step is monotone non-decreasing in v (float
+// subtraction, multiplication by a positive constant, clamp, truncation of a non-negative
+// value), so a <= t <= b implies cell(a) <= cell(t) <= cell(b).  NaN maps to cell 0.
+__device__ __forceinline__ int grid_cell(float v, float lo, float inv_h, int n) {
+  float f = (v - lo) * inv_h;
+  f = __builtin_fminf(__builtin_fmaxf(f, 0.f), (float)(n - 1));
+  return (int)f;
+}
+
+// Cells of one axis met by the cube [q - rr, q + rr], rr slightly above r: a superset of the cells of every target
+// with pair_dist <= r (the proof stands in front of the sweep in kernels_grid.hip, "Cells met by the cube").
+__device__ __forceinline__ void cube_cells(float q, float r, float lo, float inv_h, int n, int& c0, int& c1) {
+  const float rr = __builtin_fmaf(r, 1.0f + 0x1p-19f, __builtin_fmaf(__builtin_fabsf(q), 0x1p-21f, 0x1p-74f));
+  c0 = grid_cell(q - rr, lo, inv_h, n);
+  c1 = grid_cell(q + rr, lo, inv_h, n);
+}
+
 }  // namespace icpk

@@ -80,6 +80,21 @@ class Engine {
     if (n_out && rc == ICPK_OK) *n_out = n;
     return rc;
   }
+  // target normals from the target's own geometry (icpk_estimate_target_normals): the plane fitted to every target
+  // point's neighbours within `radius`, oriented towards `viewpoint` (3 floats, or nullptr), installed as the target
+  // normals ICPK_SOLVE_POINT_TO_PLANE reads; no host wait
+  int estimateTargetNormals(float radius, int minNeighbors = 5, const float* viewpoint = nullptr, int flags = 0) {
+    return icpk_estimate_target_normals(ctx_, radius, minNeighbors, viewpoint, flags);
+  }
+  // ... and what it found (icpk_get_normal_stats): any pointer may be null; count / curvature sized for the target,
+  // moments for 10 words per point (only after flags = ICPK_NORMALS_KEEP_MOMENTS)
+  int normalStats(int* n, int* n_valid, int32_t* count = nullptr, float* curvature = nullptr, int64_t* moments = nullptr) {
+    int32_t a = 0, b = 0;
+    const int rc = icpk_get_normal_stats(ctx_, &a, &b, count, curvature, moments);
+    if (rc == ICPK_OK && n) *n = a;
+    if (rc == ICPK_OK && n_valid) *n_valid = b;
+    return rc;
+  }
 
  private:
   icpk_ctx* ctx_ = nullptr;

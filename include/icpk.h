@@ -660,6 +660,55 @@ int icpk_voxel_downsample(icpk_ctx *ctx, int32_t which, float leaf, int32_t mode
 int icpk_get_voxel_groups(icpk_ctx *ctx, int32_t *n_in, int32_t *n_out, int32_t *first_index, int32_t *count,
                           int32_t *out_of_point);
 
+/* ---- target normals from the target's own geometry (K12; extension: the reference plans it, TODO:9 "Look into Point
+ * to Plane") ----
+ * ICPK_SOLVE_POINT_TO_PLANE needs one normal per target point.  icpk_backproject_with_normals gives them to a cloud
+ * that is still a depth image, icpk_set_target_normals takes them from the host; this call computes them on the device
+ * for ANY target the context holds (icpk_set_target*, a downsampled one, icpk_map_list_to_target, a broadcast key
+ * frame): per point the plane fitted to its neighbours within a radius, oriented towards a viewpoint, written where
+ * those two calls write theirs.  The rule, for target points p_0 .. p_{n-1} (floats, as icpk_get_target returns them),
+ * r = radius and F = 2^15:
+ *   neighbourhood  of i: every j (i itself and duplicates included) with d(i, j) <= r, d the pair distance of
+ *                  icp.cpp:606-620 exactly as every NN search here evaluates it (float differences, float64 sum of
+ *                  squares, narrowed, correctly rounded float sqrt), `<=` a float compare.  A point with a non-finite
+ *                  coordinate is in no neighbourhood and has an empty one.  m_i = its size.
+ *   moments        per neighbour and axis u = ((double)p_j - (double)p_i) / (double)r, q = (int64)rint(u * F) (ties to
+ *                  even); S_a = sum q_a (3 words), S_ab = sum q_a q_b (6 words, a <= b), all int64.  Integers, so that
+ *                  they do not depend on the order in which the neighbours arrive: the same bits on every run and for
+ *                  every order of the cloud.  |q| <= F + 1 and m < 2^31, so |S_a| < 2^47 and S_ab < 2^62: nothing
+ *                  overflows for any cloud an int32 size can describe.
+ *   covariance     float64: C_ab = (double)S_ab - (double)S_a * (double)S_b / (double)m.  The offsets are taken from
+ *                  p_i, which lies inside the neighbourhood, so the difference does not cancel catastrophically.
+ *   eigen-solve    of the symmetric 3x3 C in float64 on the device (cyclic Jacobi): eigenvalues l0 <= l1 <= l2, unit
+ *                  eigenvector e0 of l0
+ *   no normal      (0, 0, 0), which never pairs: when m < min_neighbors, when l1 <= 2^-20 * l2 as the device computed
+ *                  them (the neighbourhood is a line or a point), or when anything above is not finite
+ *   orientation    with a viewpoint v: s = e0 . ((double)v - (double)p_i); s < 0 flips e0.  Without one (NULL), or when
+ *                  s == 0: the sign that makes the component of largest magnitude positive (lowest axis on a tie).
+ *                  The normal is the three components narrowed to float.
+ *   curvature      (float)(l0 / (l0 + l1 + l2)) ("surface variation"), 0 where there is no normal
+ * The moments, the counts and hence the m-test are exact; e0, the line test and the curvature carry the rounding of the
+ * float64 eigen-solve.
+ * Stream-ordered, no host wait.  The search walks the uniform grid ICPK_NN_GRID indexes the target with and builds it
+ * if the target has none yet: the alignment that follows finds it built.  Afterwards the context holds target normals
+ * exactly as after icpk_set_target_normals (icpk_transform_target rotates them, icpk_voxel_downsample carries them
+ * along, icpk_get_target_normals returns them); an empty target gets empty normals.
+ * ICPK_E_NOT_SET without a target; ICPK_E_ARG for a radius that is not finite and > 0, min_neighbors < 3 or an unknown
+ * flag (nothing changes). */
+#define ICPK_NORMALS_KEEP_MOMENTS 1 /* flags: keep the 10 int64 per point for icpk_get_normal_stats */
+int icpk_estimate_target_normals(icpk_ctx *ctx, float radius, int32_t min_neighbors, const float viewpoint[3] /* or NULL */,
+                                 int32_t flags);
+/* What the last icpk_estimate_target_normals found (it stays on the device until asked for; this call waits):
+ *   n, n_valid       target points, and how many of them got a normal
+ *   count[n]         m_i
+ *   curvature[n]
+ *   moments[10 * n]  per point i the ten words moments[10 i ..]: m, S_x, S_y, S_z, S_xx, S_xy, S_xz, S_yy, S_yz, S_zz
+ * Any may be NULL.  The record belongs to the target it was estimated on: ICPK_E_NOT_SET before the first estimate and
+ * after any later change of the target or its normals (a new target, icpk_transform_target, icpk_voxel_downsample,
+ * icpk_set_target_normals); ICPK_E_ARG for `moments` when the estimate ran without ICPK_NORMALS_KEEP_MOMENTS. */
+int icpk_get_normal_stats(icpk_ctx *ctx, int32_t *n, int32_t *n_valid, int32_t *count, float *curvature,
+                          int64_t *moments);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
