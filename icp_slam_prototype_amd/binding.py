@@ -30,6 +30,9 @@ ROBUST_NONE, ROBUST_HUBER, ROBUST_TUKEY = 0, 1, 2
 SCALE_FIXED, SCALE_MEDIAN = 0, 1
 VOXEL_FIRST, VOXEL_CENTROID = 0, 1  # icpk_voxel_downsample: the representative / the fixed-point centroid
 NORMALS_KEEP_MOMENTS = 1  # icpk_estimate_target_normals: keep the 10 int64 per point for icpk_get_normal_stats
+FILTER_STATISTICAL, FILTER_RADIUS = 0, 1  # icpk_remove_outliers: mean k-NN distance / neighbour count within a radius
+FILTER_MAX_K = 64
+FILTER_STATS_ONLY = 1  # icpk_remove_outliers: compute and keep the statistics, leave the cloud as it is
 
 # every symbol include/icpk.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -53,6 +56,7 @@ SYMBOLS = [
     "icpk_set_robust", "icpk_get_robust_trace", "icpk_reduce_weighted",
     "icpk_voxel_downsample", "icpk_get_voxel_groups",
     "icpk_estimate_target_normals", "icpk_get_normal_stats",
+    "icpk_remove_outliers", "icpk_get_outlier_stats",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -135,6 +139,17 @@ class Robust(C.Structure):
         ("scale_mode", C.c_int32),
         ("scale", C.c_float),
         ("trim_fraction", C.c_float),
+    ]
+
+
+class OutlierFilter(C.Structure):
+    """icpk_outlier_filter: kind FILTER_*, k and std_ratio (statistical), radius and min_neighbors (radius)."""
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("k", C.c_int32),
+        ("std_ratio", C.c_float),
+        ("radius", C.c_float),
+        ("min_neighbors", C.c_int32),
     ]
 
 
@@ -264,6 +279,8 @@ def load():
     lib.icpk_get_voxel_groups.argtypes = [C.c_void_p, ip, ip, ip, ip, ip]
     lib.icpk_estimate_target_normals.argtypes = [C.c_void_p, C.c_float, C.c_int32, fp, C.c_int32]
     lib.icpk_get_normal_stats.argtypes = [C.c_void_p, ip, ip, ip, fp, C.POINTER(C.c_int64)]
+    lib.icpk_remove_outliers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(OutlierFilter), C.c_int32, ip, ip]
+    lib.icpk_get_outlier_stats.argtypes = [C.c_void_p, ip, ip, C.POINTER(C.c_double), fp, ip, C.POINTER(C.c_double)]
     _lib = lib
     return lib
 
@@ -748,6 +765,37 @@ class Context:
         if mom is not None:
             out["moments"] = mom
         return out
+
+    # -- outlier removal (icpk_remove_outliers) ----------------------------------------
+    def remove_outliers(self, which=0, kind=FILTER_STATISTICAL, k=16, std_ratio=2.0, radius=0.05, min_neighbors=5,
+                        stats_only=False):
+        """Removes stray points from the working source (which = 0) or the target (1): the statistical filter on the
+        mean distance to the k nearest neighbours, or the radius filter on the neighbour count (include/icpk.h).
+        stats_only: the cloud stays as it is, only outlier_stats() changes.  Returns (n_out, n_dropped)."""
+        f = OutlierFilter(int(kind), int(k), float(std_ratio), float(radius), int(min_neighbors))
+        n_out, n_drop = C.c_int32(0), C.c_int32(0)
+        self._chk(self._lib.icpk_remove_outliers(self._h, int(which), C.byref(f), FILTER_STATS_ONLY if stats_only else 0,
+                                                 C.byref(n_out), C.byref(n_drop)))
+        self._filter_kind = int(kind)
+        return n_out.value, n_drop.value
+
+    def outlier_stats(self):
+        """What the last remove_outliers found: dict(n_in, n_out, value (n_in,) float64 -- the mean k-NN distance or the
+        neighbour count --, kth (n_in,) float32 (statistical filter only, else None), out_index (n_in,) int32: -1 for a
+        removed or dropped point, summary (4,) float64: N, mu, sigma, T / N, 0, 0, min_neighbors)."""
+        n_in, n_out = C.c_int32(0), C.c_int32(0)
+        summary = np.zeros(4, np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self._lib.icpk_get_outlier_stats(self._h, C.byref(n_in), C.byref(n_out), None, None, None,
+                                                   summary.ctypes.data_as(dp)))
+        value = np.zeros(n_in.value, np.float64)
+        kth = np.zeros(n_in.value, np.float32)
+        oidx = np.empty(n_in.value, np.int32)
+        self._chk(self._lib.icpk_get_outlier_stats(self._h, None, None, value.ctypes.data_as(dp), _fp(kth),
+                                                   oidx.ctypes.data_as(C.POINTER(C.c_int32)), None))
+        statistical = getattr(self, "_filter_kind", FILTER_STATISTICAL) == FILTER_STATISTICAL
+        return dict(n_in=n_in.value, n_out=n_out.value, value=value, kth=kth if statistical else None, out_index=oidx,
+                    summary=summary)
 
     # -- loop ---------------------------------------------------------------------
     def align(self, params=None, **kw):

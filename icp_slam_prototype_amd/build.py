@@ -14,7 +14,8 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "kernels_nn.hip", "kernels_reduce.hip", "kernels_transform.hip", "kernels_backproject.hip", "kernels_sort.hip",
            "kernels_nn_pruned.hip", "kernels_loop.hip", "kernels_grid.hip", "kernels_frontend.hip",
            "icpk_map.cpp", "kernels_map.hip", "icpk_fast.cpp", "kernels_fast.hip", "kernels_map_nn.hip", "kernels_robust.hip",
-           "icpk_voxel.cpp", "kernels_voxel.hip", "icpk_normals.cpp", "kernels_normals.hip"]
+           "icpk_voxel.cpp", "kernels_voxel.hip", "icpk_normals.cpp", "kernels_normals.hip",
+           "icpk_filter.cpp", "kernels_filter.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -167,6 +168,24 @@ def build_normals_test(force=False):
     return NORMALS_TEST
 
 
+FILTER_TEST = os.path.join(LIBDIR, "test_filter")
+
+
+def build_filter_test(force=False):
+    """Host-only C++ program over icp::Engine::removeOutliers / outlierStats and icp::Tracker's outlierFilter (g++,
+    links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_filter.cpp")
+    hdr = os.path.join(HERE, "include", "icp_align.hpp")
+    build()
+    newest = max(os.path.getmtime(p) for p in (src, hdr, LIB))
+    if not force and os.path.exists(FILTER_TEST) and os.path.getmtime(FILTER_TEST) >= newest:
+        return FILTER_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", FILTER_TEST])
+    return FILTER_TEST
+
+
 FAKE_RCCL = os.path.join(LIBDIR, "libfake_rccl.so")
 
 
@@ -209,3 +228,4 @@ if __name__ == "__main__":
     print(build_map_dense_test(force="--force" in sys.argv))
     print(build_voxel_test(force="--force" in sys.argv))
     print(build_normals_test(force="--force" in sys.argv))
+    print(build_filter_test(force="--force" in sys.argv))

@@ -2,7 +2,7 @@
 // host-side translation unit calls (icpk_api.cpp: context and clouds; icpk_sweep.cpp: NN sweeps and reductions;
 // icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
 // entry; icpk_frontend.cpp: depth images;
-// icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp).  Not part of the ABI.
+// icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -336,6 +336,27 @@ struct icpk_ctx {
   bool have_nstats = false;      // the four above describe the normals of the target the context holds now
   bool nstats_moments = false;   // ... and the caller asked for the moments to be kept
   int nstats_n = 0;
+  // outlier removal (icpk_remove_outliers, K13; icpk_filter.cpp): the statistics of the last call
+  // (icpk_get_outlier_stats), the scratch of the threshold and the compaction, the filtered planes on their way into
+  // the cloud, and -- for the working source only -- an index of the filter's own (the target's is ctx->t4 ...)
+  icpk::DevBuf<double> flt_value;    // [n_in]
+  icpk::DevBuf<float> flt_kth;       // [n_in]
+  icpk::DevBuf<int> flt_oidx;        // [n_in]
+  icpk::DevBuf<double> flt_summary;  // 4
+  icpk::PinnedBuf<double> flt_summary_host;
+  icpk::DevBuf<double> flt_partial;  // 2 x RED_MAX_BLOCKS
+  icpk::DevBuf<int> flt_pcount;      // RED_MAX_BLOCKS
+  icpk::DevBuf<int> flt_bsum;        // [ceil(n_in / 1024)]
+  icpk::DevBuf<int> flt_counts;      // n_out, n_dropped ...
+  icpk::PinnedBuf<int> flt_counts_host;  // ... and where the host reads them
+  icpk::DevBuf<float> flt_out;       // 3 planes of n_in floats (6 with normals)
+  icpk::DevBuf<GridInfo> flt_grid_info;
+  icpk::DevBuf<float> flt_grid_bounds;
+  icpk::DevBuf<int> flt_cell_start;  // grid_max_cells + 1
+  icpk::DevBuf<int> flt_cell;        // 2 x n: the counting sort's cell and slot of every point
+  icpk::DevBuf<float4> flt_t4, flt_o4;
+  bool have_flt = false;             // a filter has run: the record describes it
+  int flt_n_in = 0, flt_n_out = 0, flt_n_finite = 0, flt_kind = 0, flt_min_neighbors = 0;
   int loop_nact = icpk::NSUM;      // device loop: sums the running alignment's step consumes (NSUM_REF or NSUM)
   int profile_phase = 0;     // alignments profiled so far (offsets the sampled launches, see profile_stride)
   int qperm_kind = 0;        // what qperm holds: 1 Morton order (pruned scan), 2 cell order (grid scan)
@@ -422,6 +443,11 @@ int ensure_cloud(icpk_ctx* ctx, Cloud& c, int n);  // room for n points (the con
 int ensure_assoc(icpk_ctx* ctx, int nq);
 // K1d's index of the target (geometry, cell table, cell-sorted copy): built unless have_grid; everything is enqueued
 int prepare_grid_target(icpk_ctx* ctx);
+// the same index of ANY cloud of n points, into buffers of the caller's (K13 indexes the working source): bounds
+// GRID_BOUNDS_PARTS x 6 floats, cell / slot n ints each, cell_start grid_max_cells + 1, t4 / o4 n points.  Of the
+// context's own state only the count table's scratch is used, which every sort leaves as it found it
+int build_grid_index(icpk_ctx* ctx, const float* x, const float* y, const float* z, int n, float* bounds, GridInfo* gi,
+                     int* cell, int* slot, int* cell_start, float4* t4, float4* o4);
 // the working source planes hold the cloud icpk_get_source would return (a device loop may leave them to be unpacked)
 int ensure_unpacked(icpk_ctx* ctx);
 int flush_loop_init(icpk_ctx* ctx);

@@ -645,4 +645,44 @@ struct NormalsArgs {
 // the two launches of one estimate (moments, then the eigen-solve); n <= 0: nothing
 void launch_estimate_normals(const NormalsArgs& a, hipStream_t s);
 
+// kernels_filter.hip -- K13, outlier removal (icpk_remove_outliers)
+constexpr int FILTER_MAX_K = 64;  // ICPK_FILTER_MAX_K
+// the k nearest neighbours of every query in an indexed cloud.  Queries and indexed cloud are separate arguments: the
+// filter passes the index's own cell-sorted copy as the queries (every point against its own cloud)
+struct KnnArgs {
+  const float4* q4;        // queries (x, y, z, w): the indexed point of index bits(w) is not a neighbour (-1: none is)
+  int nq;
+  int k;                   // 1 .. FILTER_MAX_K
+  float r0_scale;          // first search radius = h sqrt((k + 1) r0_scale), h the cell edge (efficiency only)
+  int pad0;
+  const float4* t4;       // the indexed cloud sorted by cell (x, y, z, original index): K1d's index
+  const int* cell_start;
+  const GridInfo* gi;
+  double* mean;            // [.] at bits(w) of the query: the mean of its k' smallest distances (0: none, or not finite)
+  float* kth;              // [.] the k'-th
+};
+void launch_knn_mean(const KnnArgs& a, hipStream_t s);
+struct FilterArgs {
+  const float *x, *y, *z;     // the cloud, n points
+  const float *nx, *ny, *nz;  // its normals, or nullptr
+  int n;
+  int kind;                   // ICPK_FILTER_*
+  int min_neighbors;
+  float std_ratio;
+  double* value;              // [n]: mean_i / (double)m_i
+  double* partial;            // [2][RED_MAX_BLOCKS] scratch of the canonical tree
+  int* pcount;                // [RED_MAX_BLOCKS]
+  double* summary;            // [4]: N, mu, sigma, T (STATISTICAL)
+  int* bsum;                  // [ceil(n / 1024)] scratch
+  int* counts;                // [2]: n_out (written), n_dropped (added to: zero before the launch)
+  float *ox, *oy, *oz;        // [n_out <= n] each
+  float *onx, *ony, *onz;     // (with normals)
+  int* out_index;             // [n]
+};
+// RADIUS: value[i] = (double)m_i over K1d's index of the same cloud (K12's neighbourhood)
+void launch_radius_count(const float4* t4, const int* cell_start, const GridInfo* gi, int n, float radius, double* value,
+                         hipStream_t s);
+// threshold (STATISTICAL: the canonical sums, then mu, sigma, T on one lane) and the order-preserving compaction
+void launch_filter_compact(const FilterArgs& a, hipStream_t s);
+
 }  // namespace icpk

@@ -170,6 +170,22 @@ int prepare_grid_target(icpk_ctx* ctx) {
   return ICPK_OK;
 }
 
+int build_grid_index(icpk_ctx* ctx, const float* x, const float* y, const float* z, int n, float* bounds, GridInfo* gi,
+                     int* cell, int* slot, int* cell_start, float4* t4, float4* o4) {
+  if (n > (1 << 28)) return fail(ctx, ICPK_E_ARG, "the grid search addresses its cell-sorted points with 32-bit byte offsets: at most 2^28 points");
+  int rc = ensure_scan_buffers(ctx);
+  if (rc) return rc;
+  launch_grid_bounds(x, y, z, n, bounds, ctx->stream);
+  launch_grid_info(bounds, n, ctx->tune.grid_ppc, ctx->tune.grid_xdiv, ctx->grid_max_cells, gi, ctx->stream);
+  ctx->qcount_dirty = true;
+  launch_grid_qslot(x, y, z, n, gi, ctx->qcount, cell, slot, 0, ctx->stream);
+  launch_grid_scan(ctx->qcount, cell_start, ctx->scan_bsum, gi, 0, ctx->stream);
+  launch_grid_tscatter(x, y, z, cell, slot, cell_start, n, t4, o4, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ctx->qcount_dirty = false;
+  return ICPK_OK;
+}
+
 // query order for the grid scan: counting sort of the source by cell of the target's grid.
 // with_points: the scatter also writes the scan-order queries and element 0 as everybody's seed
 // (the first sweep of an alignment that has no seeds)

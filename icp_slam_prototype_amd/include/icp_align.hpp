@@ -80,6 +80,30 @@ class Engine {
     if (n_out && rc == ICPK_OK) *n_out = n;
     return rc;
   }
+  // outlier removal (icpk_remove_outliers): the statistical or the radius filter on the working source (which = 0) or
+  // the target (1); statsOnly: the cloud stays as it is and only outlierStats changes
+  int removeOutliers(int which, const icpk_outlier_filter& f, bool statsOnly = false, int* n_out = nullptr,
+                     int* n_dropped = nullptr) {
+    int32_t n = 0, d = 0;
+    const int rc = icpk_remove_outliers(ctx_, which, &f, statsOnly ? ICPK_FILTER_STATS_ONLY : 0, &n, &d);
+    if (n_out && rc == ICPK_OK) *n_out = n;
+    if (n_dropped && rc == ICPK_OK) *n_dropped = d;
+    return rc;
+  }
+  // what the last removeOutliers found (icpk_get_outlier_stats): the vectors are resized to n_in; summary: 4 doubles
+  int outlierStats(std::vector<double>* value, std::vector<float>* kth, std::vector<int32_t>* out_index,
+                   double* summary = nullptr, int* n_out = nullptr) {
+    int32_t n_in = 0, m = 0;
+    int rc = icpk_get_outlier_stats(ctx_, &n_in, &m, nullptr, nullptr, nullptr, nullptr);
+    if (rc != ICPK_OK) return rc;
+    if (value) value->assign((size_t)n_in, 0.0);
+    if (kth) kth->assign((size_t)n_in, 0.f);
+    if (out_index) out_index->assign((size_t)n_in, -1);
+    rc = icpk_get_outlier_stats(ctx_, nullptr, nullptr, value ? value->data() : nullptr, kth ? kth->data() : nullptr,
+                                out_index ? out_index->data() : nullptr, summary);
+    if (n_out && rc == ICPK_OK) *n_out = m;
+    return rc;
+  }
   // target normals from the target's own geometry (icpk_estimate_target_normals): the plane fitted to every target
   // point's neighbours within `radius`, oriented towards `viewpoint` (3 floats, or nullptr), installed as the target
   // normals ICPK_SOLVE_POINT_TO_PLANE reads; no host wait
@@ -319,6 +343,11 @@ class Tracker {
     int rc = icpk_backproject_pair(c, data, previous, rows, cols, fx_, cx_, nullptr, cameraRotation, cameraPosition,
                                    filterFrames ? 1 : 0, maxDistance, minDistance, 1, -1, -1, nullptr, nullptr);
     if (rc != ICPK_OK) return rc;
+    if (outlierFilter) {  // strays go before anything reads neighbourhoods (target first, then source)
+      rc = eng_.removeOutliers(1, outlierSetting);
+      if (rc == ICPK_OK) rc = eng_.removeOutliers(0, outlierSetting);
+      if (rc != ICPK_OK) return rc;
+    }
     if (voxelLeaf > 0.f) {  // thin both clouds by space before the loop sees them (target first, then source)
       rc = eng_.voxelDownsample(1, voxelLeaf, voxelMode);
       if (rc == ICPK_OK) rc = eng_.voxelDownsample(0, voxelLeaf, voxelMode);
@@ -361,6 +390,10 @@ class Tracker {
   // and alignment (icpk_voxel_downsample); 0, the default: the calls are exactly those made without it
   float voxelLeaf = 0.f;
   int voxelMode = ICPK_VOXEL_CENTROID;
+  // true: both clouds of every frame pair go through icpk_remove_outliers with outlierSetting between back-projection
+  // and the voxel downsample; false, the default: the calls are exactly those made without it
+  bool outlierFilter = false;
+  icpk_outlier_filter outlierSetting{ICPK_FILTER_STATISTICAL, 16, 2.0f, 0.05f, 5};
   float cameraRotation[9];
   float lastRotation[9];
   float cameraPosition[3];

@@ -97,13 +97,17 @@ class SequenceRunner:
     HEADER = "MSE,ICP rX,ICP rY,ICP rZ,GT rX,GT rY,GT rZ"  # SLAM.cpp:327
 
     def __init__(self, ctx, max_iterations=16, threshold=1e-4, fx=468.60, cx=318.27, voxel_leaf=0.0,
-                 voxel_mode=binding.VOXEL_CENTROID, **params):
-        """voxel_leaf > 0: both clouds of every frame pair are voxel-grid downsampled with this leaf (metres) between
+                 voxel_mode=binding.VOXEL_CENTROID, outlier_filter=None, **params):
+        """outlier_filter: a dict of Context.remove_outliers' settings (kind, k, std_ratio, radius, min_neighbors), or
+        None; both clouds of every frame pair are filtered with it (target first, then source) between back-projection
+        and the voxel downsample, if any.
+        voxel_leaf > 0: both clouds of every frame pair are voxel-grid downsampled with this leaf (metres) between
         back-projection and alignment (Context.voxel_downsample); 0: the calls are those made without it."""
         self.ctx = ctx
         self.kw = dict(max_iterations=max_iterations, threshold=threshold, solve=binding.SOLVE_REFERENCE, **params)
         self.fx, self.cx = fx, cx
         self.voxel_leaf, self.voxel_mode = float(voxel_leaf), voxel_mode
+        self.outlier_filter = None if outlier_filter is None else dict(outlier_filter)
         self.camera_rotation = np.eye(3, dtype=np.float32)      # icp.cpp:49
         self.camera_position = np.full(3, 5, np.float32)        # icp.cpp:53
         self.last_rotation = np.eye(3, dtype=np.float32)
@@ -125,6 +129,9 @@ class SequenceRunner:
         # icp.cpp:38-39 back-project both frames, :58-59 / :70-71 pose them; the posed source is the
         # starting point of the alignment (one call: icpk_backproject_pair)
         c.backproject_pair(depth, self.previous, R=self.camera_rotation, t=self.camera_position, fx=self.fx, cx=self.cx)
+        if self.outlier_filter is not None:
+            c.remove_outliers(1, **self.outlier_filter)
+            c.remove_outliers(0, **self.outlier_filter)
         if self.voxel_leaf > 0:
             c.voxel_downsample(1, self.voxel_leaf, self.voxel_mode)
             c.voxel_downsample(0, self.voxel_leaf, self.voxel_mode)
@@ -163,6 +170,8 @@ class MultiSequenceRunner:
         if "voxel_leaf" in params or "voxel_mode" in params:
             # (the streams' clouds live inside the lock-step group between back-projection and loop)
             raise ValueError("voxel-grid downsampling is not available in the lock-step batch: use SequenceRunner")
+        if "outlier_filter" in params:
+            raise ValueError("outlier removal is not available in the lock-step batch: use SequenceRunner")
         self.ctx = ctx
         self.runners = [SequenceRunner(None, max_iterations, threshold, fx, cx, **params) for _ in range(n_streams)]
         self.kw = self.runners[0].kw

@@ -709,6 +709,68 @@ int icpk_estimate_target_normals(icpk_ctx *ctx, float radius, int32_t min_neighb
 int icpk_get_normal_stats(icpk_ctx *ctx, int32_t *n, int32_t *n_valid, int32_t *count, float *curvature,
                           int64_t *moments);
 
+/* ---- outlier removal (K13; extension: the reference plans it, TODO:16 "Filter points better") ----
+ * Removes stray points from one of the context's clouds, whichever way it got there: the statistical filter on the mean
+ * distance to the k nearest neighbours, or the radius filter on the neighbour count.  A filter acts on POINTS, once per
+ * cloud, before the index, the normals and the loop see them (icpk_set_robust acts on pairs, every iteration).
+ * The rule.  Input: the n points of the cloud in index order, as icpk_get_source / icpk_get_target return them.
+ * d(i, j) is the pair distance of icp.cpp:606-620 exactly as every NN search here evaluates it (float differences,
+ * float64 sum of squares, narrowed, correctly rounded float sqrt) -- the function K12's neighbourhood test uses.
+ *   dropped      a point with a non-finite coordinate belongs to no neighbourhood, has none, and is removed (n_dropped
+ *                counts them; its statistics read value = 0, kth = 0).  N = the number of finite points.
+ *   STATISTICAL  (k, alpha = std_ratio) for finite point i, k' = min(k, N - 1).  Its neighbours are the finite j != i
+ *                (by INDEX: a duplicate at the same position is a neighbour at distance 0), ordered by (d(i, j), j).
+ *                D_i = the float64 sum of the first k' distances, added in ascending order; mean_i = D_i / k' (float64),
+ *                kth_i = the k'-th distance (float).  Both depend only on the multiset of the k' smallest distances, so
+ *                ties at the k-th place do not matter.  k' = 0 (N = 1): mean_i = 0, kth_i = 0.
+ *                S1 = sum mean_i and S2 = sum mean_i^2 over the points in index order through the canonical reduction
+ *                tree (ICPK_RED_THREADS / ICPK_RED_MAX_BLOCKS, the tree of icpk_reduce, with n elements; a dropped point
+ *                contributes +0.0 at its index).  mu = S1 / N; variance = max(0, (S2 - S1 * S1 / N) / (N - 1)), 0 when
+ *                N < 2; sigma = sqrt(variance); T = mu + (double)alpha * sigma; all float64 (N = 0: mu = sigma = T = 0).
+ *                Point i is KEPT iff mean_i <= T.
+ *   RADIUS       (r, min_neighbors) m_i = #{ finite j : d(i, j) <= r }, i itself and duplicates included -- K12's
+ *                neighbourhood, K12's float `<=`.  Kept iff m_i >= min_neighbors.
+ *   output       the kept points in input order, their three floats unchanged; for which = 1 with target normals held,
+ *                each kept point's normal unchanged.
+ * What is exact: kth_i, mean_i and m_i (hence RADIUS's keep mask) for every order of the cloud; and, for a GIVEN order of
+ * the cloud, S1, S2, T and STATISTICAL's keep mask -- the same bits on every run.  S1 / S2 follow the index order: a
+ * permuted cloud may move T in its last bits.
+ * Afterwards (unless ICPK_FILTER_STATS_ONLY) the filtered cloud IS the context's cloud exactly as after
+ * icpk_voxel_downsample: everything derived from the old cloud is dropped (associations, seeds, indexes, K12's statistics
+ * record; ICPK_NN_MAP needs a new icpk_map_lookup_to_target).  One host wait (the two counts).  With
+ * ICPK_FILTER_STATS_ONLY the cloud, its normals and its index stay as they are; only the statistics record is replaced.
+ * An empty cloud gives an empty cloud; if every point is removed the cloud becomes empty (the next alignment reports what
+ * it reports for one).  The search walks the uniform grid of ICPK_NN_GRID: for the target the context's own (built if the
+ * target has none yet, and found built by the alignment that follows a STATS_ONLY call), for the source one in buffers
+ * of the filter's own -- the target's index is not disturbed.
+ * Where it does not apply: nothing filters inside icpk_backproject*, icpk_align_batch / _device or
+ * icpk_align_frames_batch (their clouds never become the context's own between back-projection and loop). */
+#define ICPK_FILTER_STATISTICAL 0
+#define ICPK_FILTER_RADIUS 1
+#define ICPK_FILTER_MAX_K 64
+#define ICPK_FILTER_STATS_ONLY 1 /* flags: compute and keep the statistics, leave the cloud as it is */
+typedef struct icpk_outlier_filter {
+  int32_t kind;          /* ICPK_FILTER_*                                              */
+  int32_t k;             /* STATISTICAL: neighbours per point, 1 .. ICPK_FILTER_MAX_K  */
+  float std_ratio;       /* STATISTICAL: alpha >= 0, finite                            */
+  float radius;          /* RADIUS: finite, > 0                                        */
+  int32_t min_neighbors; /* RADIUS: >= 1                                               */
+} icpk_outlier_filter;
+/* which: 0 = the working source, 1 = the target (as icpk_voxel_downsample).  n_out / n_dropped: either may be NULL.
+ * Only the fields of f->kind are read.  ICPK_E_ARG for another `which`, kind or flag, k outside 1 .. ICPK_FILTER_MAX_K,
+ * a negative or non-finite std_ratio, a non-finite or non-positive radius, min_neighbors < 1, a NULL f (nothing
+ * changes); ICPK_E_NOT_SET if that cloud has not been set. */
+int icpk_remove_outliers(icpk_ctx *ctx, int32_t which, const icpk_outlier_filter *f, int32_t flags, int32_t *n_out,
+                         int32_t *n_dropped);
+/* What the last icpk_remove_outliers on this context found (it stays on the device until asked for; this call waits):
+ *   value[n_in]      STATISTICAL: mean_i; RADIUS: (double)m_i; 0 for a dropped point
+ *   kth[n_in]        STATISTICAL: the distance of the k'-th neighbour; RADIUS: not written
+ *   out_index[n_in]  the point's position in the filtered cloud, -1 if removed or dropped
+ *   summary[4]       STATISTICAL: N, mu, sigma, T; RADIUS: N, 0, 0, min_neighbors
+ * Any may be NULL; ICPK_E_NOT_SET before the first call. */
+int icpk_get_outlier_stats(icpk_ctx *ctx, int32_t *n_in, int32_t *n_out, double *value, float *kth, int32_t *out_index,
+                           double summary[4]);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity

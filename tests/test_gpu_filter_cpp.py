@@ -1,0 +1,141 @@
+"""icp::Engine::removeOutliers / outlierStats and icp::Tracker's outlierFilter (tests/cpp/test_filter.cpp) against the
+same calls made by hand through the Python binding, bit for bit; and SequenceRunner(outlier_filter=...) likewise."""
+import os
+import struct
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import filter_model as fm
+from icp_slam_prototype_amd import binding, build, sequence, synth
+
+pytestmark = pytest.mark.gpu
+
+SETTINGS = [None, dict(kind=binding.FILTER_STATISTICAL, k=16, std_ratio=1.0, radius=0.05, min_neighbors=5),
+            dict(kind=binding.FILTER_RADIUS, k=16, std_ratio=1.0, radius=0.08, min_neighbors=6)]
+
+
+def _frames(n=4, rows=120, cols=160, seed=1):
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(n):
+        d = synth.render_room_depth(rows, cols, synth.rot_xyz_deg(0, 0.5 * k, 0), np.array([0.01 * k, 0, 0]),
+                                    noise_sigma=0.002, rng=rng)
+        d[rng.random(d.shape) > 0.5] = 0
+        out.append(d.astype(np.uint16))
+    return out
+
+
+class _PlainRunner(sequence.SequenceRunner):
+    """A runner that has never heard of the option: the step as it was before it existed."""
+
+    def step(self, depth, timestamp=None, ground_truth=None):
+        depth = np.ascontiguousarray(depth, np.uint16)
+        if self.previous is None:
+            self.previous = depth.copy()
+            return None
+        c = self.ctx
+        c.backproject_pair(depth, self.previous, R=self.camera_rotation, t=self.camera_position, fx=self.fx, cx=self.cx)
+        T, st, rc = c.align(last_rotation=self.last_rotation, last_translation=self.last_translation, **self.kw)
+        return self._advance(depth, T, st, rc, c.get_trace(max(self.kw["max_iterations"], 1)), timestamp, ground_truth)
+
+
+class _HandRunner(sequence.SequenceRunner):
+    """The calls the option stands for, made by hand; the filtered clouds are held to the model on the way."""
+
+    def __init__(self, ctx, setting, **kw):
+        super().__init__(ctx, **kw)
+        self.setting = setting
+        self.sizes = []
+
+    def step(self, depth, timestamp=None, ground_truth=None):
+        depth = np.ascontiguousarray(depth, np.uint16)
+        if self.previous is None:
+            self.previous = depth.copy()
+            return None
+        c = self.ctx
+        c.backproject_pair(depth, self.previous, R=self.camera_rotation, t=self.camera_position, fx=self.fx, cx=self.cx)
+        tgt, src = c.get_target(), c.get_source()
+        nt = c.remove_outliers(1, **self.setting)[0]
+        ns = c.remove_outliers(0, **self.setting)[0]
+        assert c.get_target().tobytes() == fm.remove_outliers(tgt, **self.setting)["points"].tobytes()
+        assert c.get_source().tobytes() == fm.remove_outliers(src, **self.setting)["points"].tobytes()
+        self.sizes.append((ns, nt))
+        T, st, rc = c.align(last_rotation=self.last_rotation, last_translation=self.last_translation, **self.kw)
+        return self._advance(depth, T, st, rc, c.get_trace(max(self.kw["max_iterations"], 1)), timestamp, ground_truth)
+
+
+def _hand(c, setting):
+    return _HandRunner(c, setting) if setting else _PlainRunner(c)
+
+
+@pytest.mark.parametrize("setting", SETTINGS)
+def test_sequence_runner_equals_calls_by_hand(setting):
+    frames = _frames()
+    with binding.Context(0) as a, binding.Context(0) as b:
+        ra = sequence.SequenceRunner(a, outlier_filter=setting)
+        rb = _hand(b, setting)
+        for d in frames:
+            x, y = ra.step(d), rb.step(d)
+            assert (x is None) == (y is None)
+            if x is not None:
+                assert np.asarray(x["T"], np.float32).tobytes() == np.asarray(y["T"], np.float32).tobytes()
+                assert (x["status"], x["iterations"]) == (y["status"], y["iterations"])
+                assert (a.source_size, a.target_size) == (b.source_size, b.target_size)
+        assert ra.camera_rotation.tobytes() == rb.camera_rotation.tobytes()
+        if setting:
+            assert all(ns < 120 * 160 and nt < 120 * 160 for ns, nt in rb.sizes)
+    with pytest.raises(ValueError):
+        sequence.MultiSequenceRunner(None, 2, outlier_filter=SETTINGS[1])
+
+
+@pytest.mark.parametrize("setting", SETTINGS)
+def test_cpp_tracker_and_engine(setting):
+    exe = build.build_filter_test()
+    frames = _frames()
+    rows, cols = frames[0].shape
+    s = setting or dict(kind=-1, k=0, std_ratio=0.0, radius=0.0, min_neighbors=0)
+    with tempfile.TemporaryDirectory() as td:
+        fin, fout = os.path.join(td, "frames.u16"), os.path.join(td, "out.bin")
+        with open(fin, "wb") as f:
+            for d in frames:
+                f.write(d.tobytes())
+        out = subprocess.run([exe, fin, str(rows), str(cols), str(len(frames)), str(s["kind"]), str(s["k"]),
+                              repr(s["std_ratio"]), repr(s["radius"]), str(s["min_neighbors"]), "16", fout],
+                             capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stderr
+        raw = open(fout, "rb").read()
+    with binding.Context(0) as c:
+        runner = _hand(c, setting)
+        off = 0
+        for i in range(1, len(frames)):
+            if i == 1:
+                runner.step(frames[0])
+            r = runner.step(frames[i])
+            rc, iters, ns, nt = struct.unpack_from("<4i", raw, off)
+            off += 16
+            vals = np.frombuffer(raw, np.float32, 16 + 9 + 3, off)
+            off += 4 * 28
+            assert (rc, iters) == (r["status"], r["iterations"])
+            assert vals[:16].tobytes() == np.ascontiguousarray(r["T"], np.float32).tobytes()
+            assert vals[16:25].tobytes() == runner.camera_rotation.tobytes() and vals[25:28].tobytes() == runner.camera_position.tobytes()
+            assert (ns, nt) == (c.source_size, c.target_size)
+            if setting:
+                assert (ns, nt) == runner.sizes[-1]
+        rc, n_out, n_drop, size, n_in = struct.unpack_from("<5i", raw, off)
+        off += 20
+        src = c.get_source()
+        want = fm.remove_outliers(src, fm.RADIUS, radius=0.1, min_neighbors=6)
+        assert (rc, n_out, n_drop, size, n_in) == (0, want["n_out"], 0, src.shape[1], src.shape[1])
+        summary = np.frombuffer(raw, np.float64, 4, off)
+        off += 32
+        value = np.frombuffer(raw, np.float64, n_in, off)
+        off += 8 * n_in
+        oidx = np.frombuffer(raw, np.int32, n_in, off)
+        off += 4 * n_in
+        assert np.array_equal(summary, want["summary"]) and np.array_equal(value, want["value"])
+        assert np.array_equal(oidx, want["out_index"])
+        assert struct.unpack_from("<2i", raw, off) == (binding.E_ARG, binding.E_ARG)
+        assert off + 8 == len(raw)
