@@ -186,6 +186,24 @@ def build_filter_test(force=False):
     return FILTER_TEST
 
 
+THREADS_TEST = os.path.join(LIBDIR, "test_threads")
+
+
+def build_threads_test(force=False):
+    """Host-only C++ program: one icp::Engine + icp::Tracker per std::thread against the same sequences one after the
+    other (g++ -pthread, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_threads.cpp")
+    hdr = os.path.join(HERE, "include", "icp_align.hpp")
+    build()
+    newest = max(os.path.getmtime(p) for p in (src, hdr, LIB))
+    if not force and os.path.exists(THREADS_TEST) and os.path.getmtime(THREADS_TEST) >= newest:
+        return THREADS_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-pthread", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", THREADS_TEST])
+    return THREADS_TEST
+
+
 FAKE_RCCL = os.path.join(LIBDIR, "libfake_rccl.so")
 
 
@@ -229,3 +247,4 @@ if __name__ == "__main__":
     print(build_voxel_test(force="--force" in sys.argv))
     print(build_normals_test(force="--force" in sys.argv))
     print(build_filter_test(force="--force" in sys.argv))
+    print(build_threads_test(force="--force" in sys.argv))

@@ -51,6 +51,34 @@ def test_no_cpu_fallback_without_gpu(lib):
     assert e.value.code == binding.E_NO_DEVICE
 
 
+def test_context_holds_the_host_buffers_it_has_registered():
+    """register_host_buffer keeps the array alive until unregister_host_buffer / close (the bookkeeping alone: a
+    stand-in library that accepts every call)"""
+    import gc
+    import weakref
+
+    class _Accepts:
+        icpk_register_host_buffer = icpk_unregister_host_buffer = staticmethod(lambda *a: binding.OK)
+        icpk_destroy = staticmethod(lambda h: None)
+
+    c = object.__new__(binding.Context)
+    c._lib, c._h, c._log_ref, c._pinned = _Accepts(), 1, None, {}
+    a, b = np.zeros(64, np.uint16), np.zeros(64, np.uint16)
+    ra, rb = weakref.ref(a), weakref.ref(b)
+    c.register_host_buffer(a)
+    c.register_host_buffer(b)
+    assert c._pinned[a.ctypes.data] is a and len(c._pinned) == 2
+    del a, b
+    gc.collect()
+    assert ra() is not None and rb() is not None  # the caller dropped them: the context has not
+    c.unregister_host_buffer(ra())
+    gc.collect()
+    assert ra() is None and list(c._pinned.values()) == [rb()]
+    c.close()
+    gc.collect()
+    assert rb() is None and not c._pinned
+
+
 def test_null_arguments_are_rejected(lib):
     assert lib.icpk_create(None, 0) == binding.E_ARG
     T = np.zeros(16, np.float32)

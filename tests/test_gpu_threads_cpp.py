@@ -1,0 +1,88 @@
+"""One icp::Engine + icp::Tracker per std::thread (tests/cpp/test_threads.cpp): six depth sequences tracked by six
+threads started together (and, their engines made, starting to track together) give, byte for byte, what the same
+program gets tracking them one after the other, and both equal SequenceRunner on the same frames through the binding -- which ties the threaded C++ result to what the rest of
+the suite holds to the oracle."""
+import os
+import struct
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from icp_slam_prototype_amd import binding, build, sequence, synth
+
+pytestmark = pytest.mark.gpu
+
+S, F, ROWS, COLS = 6, 6, 120, 160
+ODD = dict(voxel_leaf=0.03, outlier_filter=dict(kind=binding.FILTER_STATISTICAL, k=16, std_ratio=2.0, radius=0.05,
+                                                 min_neighbors=5))  # icp::Tracker's outlierSetting as constructed
+
+
+def _sequence(seed):
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(F):
+        d = synth.render_room_depth(ROWS, COLS, synth.rot_xyz_deg(0, 0.5 * k, 0), np.array([0.01 * k, 0, 0.002 * k]),
+                                    noise_sigma=0.002, rng=rng)
+        d[rng.random(d.shape) > 0.5] = 0
+        out.append(np.ascontiguousarray(d, np.uint16))
+    return out
+
+
+def _through_the_binding(frames, src, tgt, odd):
+    """the calls of test_threads.cpp's track() on a fresh context"""
+    recs = []
+    with binding.Context(0) as c:
+        c.set_target(tgt)
+        c.set_source(src)
+        T, st, rc = c.align()
+        recs.append((rc, st.iterations, T.tobytes()))
+        runner = sequence.SequenceRunner(c, **(ODD if odd else {}))
+        for d in frames:
+            r = runner.step(d)
+            if r is not None:
+                recs.append((r["status"], r["iterations"], np.ascontiguousarray(r["T"], np.float32).tobytes()))
+        return recs, runner.camera_rotation.tobytes() + runner.camera_position.tobytes()
+
+
+def test_engines_on_threads_equal_the_serial_pass_and_the_binding():
+    exe = build.build_threads_test()
+    seqs = [_sequence(300 + s) for s in range(S)]
+    clouds = [(synth.backproject(q[1]) + synth.CAMERA_START, synth.backproject(q[0]) + synth.CAMERA_START) for q in seqs]
+    with tempfile.TemporaryDirectory() as td:
+        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
+        with open(fin, "wb") as f:
+            f.write(struct.pack("<4i", S, F, ROWS, COLS))
+            for q in seqs:
+                for d in q:
+                    f.write(d.tobytes())
+            for src, tgt in clouds:
+                f.write(struct.pack("<2i", src.shape[1], tgt.shape[1]))
+                f.write(np.ascontiguousarray(src, np.float32).tobytes())
+                f.write(np.ascontiguousarray(tgt, np.float32).tobytes())
+        # (a time-out or a signal is a failure: the program is not run again)
+        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, (out.returncode, out.stderr)
+        raw = open(fout, "rb").read()
+    per_seq = F * (8 + 64) + 48  # icp::align + F - 1 frame pairs, then camR and camP
+    assert len(raw) == 2 * S * per_seq + 16 * S
+    # the threads did track side by side: each one's tracking loop shares time with another's (they start it together)
+    spans = np.frombuffer(raw, np.float64, 2 * S, 2 * S * per_seq).reshape(S, 2)
+    print("\ntracking loops of the threads, ms from the first start:", np.round(1e3 * (spans - spans[:, 0].min()), 2).tolist())
+    for s in range(S):
+        assert spans[s, 1] > spans[s, 0]
+        assert any(k != s and spans[k, 0] < spans[s, 1] and spans[s, 0] < spans[k, 1] for k in range(S)), (s, spans)
+    serial, threaded = raw[:S * per_seq], raw[S * per_seq:2 * S * per_seq]
+    for s in range(S):
+        a, b = serial[s * per_seq:(s + 1) * per_seq], threaded[s * per_seq:(s + 1) * per_seq]
+        assert a == b, f"sequence {s}: its thread's result differs from the serial pass at byte {_first(a, b)}"
+        recs, pose = _through_the_binding(seqs[s], clouds[s][0], clouds[s][1], s % 2 == 1)
+        assert len(recs) == F
+        want = b"".join(struct.pack("<2i", rc, it) + T for rc, it, T in recs) + pose
+        assert b == want, f"sequence {s}: the C++ passes differ from the binding at byte {_first(b, want)}"
+        assert max(it for _, it, _ in recs) > 0
+
+
+def _first(a, b):
+    return next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
