@@ -16,7 +16,7 @@ OK = 0
 W_TOO_FEW_PAIRS = 1
 E_ARG, E_EMPTY_TARGET, E_HIP, E_NOT_SET, E_NO_DEVICE, E_RCCL = -1, -2, -3, -4, -5, -6
 COMM_ID_BYTES = 128
-SOLVE_REFERENCE, SOLVE_KABSCH, SOLVE_POINT_TO_PLANE = 0, 1, 2
+SOLVE_REFERENCE, SOLVE_KABSCH, SOLVE_POINT_TO_PLANE, SOLVE_PLANE_TO_PLANE = 0, 1, 2, 3
 W_DEGENERATE = 2
 W_EMPTY_MAP = 3
 MAX_NN_KEYPOINT_DISTANCE = 0.1  # icp.hpp:10
@@ -57,6 +57,8 @@ SYMBOLS = [
     "icpk_voxel_downsample", "icpk_get_voxel_groups",
     "icpk_estimate_target_normals", "icpk_get_normal_stats",
     "icpk_remove_outliers", "icpk_get_outlier_stats",
+    "icpk_estimate_source_normals", "icpk_set_source_normals", "icpk_get_source_normals", "icpk_set_plane_to_plane",
+    "icpk_reduce_plane_to_plane",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -281,6 +283,11 @@ def load():
     lib.icpk_get_normal_stats.argtypes = [C.c_void_p, ip, ip, ip, fp, C.POINTER(C.c_int64)]
     lib.icpk_remove_outliers.argtypes = [C.c_void_p, C.c_int32, C.POINTER(OutlierFilter), C.c_int32, ip, ip]
     lib.icpk_get_outlier_stats.argtypes = [C.c_void_p, ip, ip, C.POINTER(C.c_double), fp, ip, C.POINTER(C.c_double)]
+    lib.icpk_estimate_source_normals.argtypes = [C.c_void_p, C.c_float, C.c_int32, fp, C.c_int32]
+    lib.icpk_set_source_normals.argtypes = [C.c_void_p, fp, fp, fp, C.c_int32]
+    lib.icpk_get_source_normals.argtypes = [C.c_void_p, fp, fp, fp]
+    lib.icpk_set_plane_to_plane.argtypes = [C.c_void_p, C.c_float]
+    lib.icpk_reduce_plane_to_plane.argtypes = [C.c_void_p, C.c_float, fp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     _lib = lib
     return lib
 
@@ -796,6 +803,37 @@ class Context:
         statistical = getattr(self, "_filter_kind", FILTER_STATISTICAL) == FILTER_STATISTICAL
         return dict(n_in=n_in.value, n_out=n_out.value, value=value, kth=kth if statistical else None, out_index=oidx,
                     summary=summary)
+
+    # -- plane-to-plane flavour (SOLVE_PLANE_TO_PLANE; include/icpk.h) ------------------
+    def estimate_source_normals(self, radius, min_neighbors=5, viewpoint=None):
+        """estimate_target_normals' rule applied to the uploaded source; the result stays with the source until it is
+        replaced.  Stream-ordered: no host wait."""
+        v = None if viewpoint is None else _f(viewpoint).reshape(3)
+        self._chk(self._lib.icpk_estimate_source_normals(self._h, float(radius), int(min_neighbors),
+                                                         None if v is None else _fp(v), 0))
+
+    def set_source_normals(self, nrm):
+        x, y, z = (_f(nrm[k]) for k in range(3))
+        self._chk(self._lib.icpk_set_source_normals(self._h, _fp(x), _fp(y), _fp(z), x.size))
+
+    def get_source_normals(self):
+        out = np.empty((3, self.source_size), np.float32)
+        self._chk(self._lib.icpk_get_source_normals(self._h, _fp(out[0]), _fp(out[1]), _fp(out[2])))
+        return out
+
+    def set_plane_to_plane(self, epsilon=1e-3):
+        """epsilon of the surface model C(n) = I - (1 - epsilon) n n^T, finite and in (0, 1]."""
+        return self._chk(self._lib.icpk_set_plane_to_plane(self._h, float(epsilon)))
+
+    def reduce_plane_to_plane(self, max_dist=0.75, R_acc=None):
+        """The 28 sums of the plane-to-plane step over the last sweep's associations and the accepted count; R_acc:
+        the rotation accumulated so far ((3, 3), default the identity)."""
+        sums = np.zeros(NP2L, np.float64)
+        cnt = C.c_int64(0)
+        R = None if R_acc is None else _f(np.asarray(R_acc, np.float32).reshape(9))
+        self._chk(self._lib.icpk_reduce_plane_to_plane(self._h, max_dist, None if R is None else _fp(R),
+                                                       sums.ctypes.data_as(C.POINTER(C.c_double)), C.byref(cnt)))
+        return sums, cnt.value
 
     # -- loop ---------------------------------------------------------------------
     def align(self, params=None, **kw):

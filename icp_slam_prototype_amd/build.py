@@ -15,7 +15,7 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "kernels_nn_pruned.hip", "kernels_loop.hip", "kernels_grid.hip", "kernels_frontend.hip",
            "icpk_map.cpp", "kernels_map.hip", "icpk_fast.cpp", "kernels_fast.hip", "kernels_map_nn.hip", "kernels_robust.hip",
            "icpk_voxel.cpp", "kernels_voxel.hip", "icpk_normals.cpp", "kernels_normals.hip",
-           "icpk_filter.cpp", "kernels_filter.hip"]
+           "icpk_filter.cpp", "kernels_filter.hip", "icpk_gicp.cpp", "kernels_gicp.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -186,6 +186,24 @@ def build_filter_test(force=False):
     return FILTER_TEST
 
 
+GICP_TEST = os.path.join(LIBDIR, "test_gicp")
+
+
+def build_gicp_test(force=False):
+    """Host-only C++ program over icp::Engine's plane-to-plane surface: estimateSourceNormals / setSourceNormals /
+    sourceNormals / setPlaneToPlane (g++, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_gicp.cpp")
+    hdr = os.path.join(HERE, "include", "icp_align.hpp")
+    build()
+    newest = max(os.path.getmtime(p) for p in (src, hdr, LIB))
+    if not force and os.path.exists(GICP_TEST) and os.path.getmtime(GICP_TEST) >= newest:
+        return GICP_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", GICP_TEST])
+    return GICP_TEST
+
+
 THREADS_TEST = os.path.join(LIBDIR, "test_threads")
 
 
@@ -247,4 +265,5 @@ if __name__ == "__main__":
     print(build_voxel_test(force="--force" in sys.argv))
     print(build_normals_test(force="--force" in sys.argv))
     print(build_filter_test(force="--force" in sys.argv))
+    print(build_gicp_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

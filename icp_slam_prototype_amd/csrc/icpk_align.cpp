@@ -135,7 +135,8 @@ namespace icpk {
 // ---- device-side loop: begin / finish, shared by the single-pair and the frame-batch path ----
 // sums the loop step of this flavour consumes: the reference flavour reads [0..12] only
 int loop_nsum(const icpk_params* p) {
-  return p->solve == ICPK_SOLVE_POINT_TO_PLANE ? NP2L : (p->solve == ICPK_SOLVE_REFERENCE ? NSUM_REF : NSUM);
+  if (p->solve == ICPK_SOLVE_POINT_TO_PLANE || p->solve == ICPK_SOLVE_PLANE_TO_PLANE) return NP2L;  // (solve_p2l's layout)
+  return p->solve == ICPK_SOLVE_REFERENCE ? NSUM_REF : NSUM;
 }
 
 // initial LoopState -> device (on ctx->stream), stop flags armed
@@ -237,6 +238,7 @@ int align_device_loop(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk
   const bool prof = p->profile != 0;
   const bool prof_all = p->profile >= 2;  // 1: NN kernels only (2 events per sweep); 2: every stage
   const bool p2l = p->solve == ICPK_SOLVE_POINT_TO_PLANE;
+  const bool gicp = p->solve == ICPK_SOLVE_PLANE_TO_PLANE;  // (never robust: icpk_align refuses the combination)
   const bool fused = p->nn_mode == ICPK_NN_PRUNED || p->nn_mode == ICPK_NN_GRID;  // K3 runs inside the sweep
   const bool robust = ctx->robust_on;
   const int nsum = robust ? (p2l ? NP2L_W : NSUM_W) : loop_nsum(p);
@@ -266,8 +268,11 @@ int align_device_loop(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk
     if (!loop_rec(ctx)) ctx->best_of_sweep.push_back(ctx->best);  // (grid sweeps keep ONE set of records: a sweep that runs at all supersedes the previous one)
     if (progress_bit(1)) return ICPK_OK;  // (the loop has exited meanwhile: K2 would be a no-op launch)
     if (prof_all && (r = pf.stamp(&pf.red))) return r;
-    r = robust ? enqueue_reduce_robust(ctx, p->max_nn_dist, p2l)
-               : (p2l ? enqueue_reduce_p2l(ctx, p->max_nn_dist) : enqueue_reduce(ctx, p->max_nn_dist));
+    if (gicp)  // (R_acc is read from the loop state)
+      r = enqueue_reduce_gicp(ctx, p->max_nn_dist, nullptr);
+    else
+      r = robust ? enqueue_reduce_robust(ctx, p->max_nn_dist, p2l)
+                 : (p2l ? enqueue_reduce_p2l(ctx, p->max_nn_dist) : enqueue_reduce(ctx, p->max_nn_dist));
     if (r) return r;
     return prof_all ? pf.stamp(nullptr) : ICPK_OK;
   };
@@ -347,6 +352,7 @@ int icpk_align_query_sharded(icpk_ctx* ctx, const icpk_params* p, float T_out[16
   if (rc) return rc;
   if (!p || !T_out) return ICPK_E_ARG;
   if (p->nn_mode == ICPK_NN_MAP) return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP is single-context only");
+  if (p->solve == ICPK_SOLVE_PLANE_TO_PLANE) return fail(ctx, ICPK_E_ARG, "the query-sharded loop has no plane-to-plane flavour");
   if (!ctx->comm) return fail(ctx, ICPK_E_NOT_SET, "icpk_comm_init_rccl has not been called");
   if (p->solve != ICPK_SOLVE_REFERENCE && p->solve != ICPK_SOLVE_KABSCH)
     return fail(ctx, ICPK_E_ARG, "the query-sharded loop supports the reference and Kabsch flavours");
@@ -394,14 +400,18 @@ int icpk_align_query_sharded(icpk_ctx* ctx, const icpk_params* p, float T_out[16
 int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats* stats) {
   reset_outputs(T_out, stats);  // (what a failure returns)
   if (!ctx || !p || !T_out) return ICPK_E_ARG;
-  if (p->max_iterations < 0 || p->solve < ICPK_SOLVE_REFERENCE || p->solve > ICPK_SOLVE_POINT_TO_PLANE)
+  if (p->max_iterations < 0 || p->solve < ICPK_SOLVE_REFERENCE || p->solve > ICPK_SOLVE_PLANE_TO_PLANE)
     return fail(ctx, ICPK_E_ARG, "bad params");
   // min_pairs < 1 would let a sweep with no pairs reach the solve, which divides by the zero count (a NaN transform)
   if (p->min_pairs < 1) return fail(ctx, ICPK_E_ARG, "min_pairs must be >= 1");
   if (p->solve == ICPK_SOLVE_POINT_TO_PLANE && ctx && !ctx->have_normals)
     return fail(ctx, ICPK_E_NOT_SET, "point-to-plane needs target normals");
-  if (p->nn_mode == ICPK_NN_MAP && (p->solve == ICPK_SOLVE_POINT_TO_PLANE || !(p->max_nn_dist <= ICPK_MAX_NN_DISTANCE)))
+  const bool gicp = p->solve == ICPK_SOLVE_PLANE_TO_PLANE;
+  if (p->nn_mode == ICPK_NN_MAP && (p->solve == ICPK_SOLVE_POINT_TO_PLANE || gicp || !(p->max_nn_dist <= ICPK_MAX_NN_DISTANCE)))
     return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP: reference or Kabsch flavour and max_nn_dist <= 0.75");
+  if (gicp && ctx->robust_on) return fail(ctx, ICPK_E_ARG, "plane-to-plane has no robust form (icpk_set_robust is on)");
+  if (gicp && (!ctx->have_normals || !ctx->have_src_normals))
+    return fail(ctx, ICPK_E_NOT_SET, "plane-to-plane needs source and target normals");
   // the bug-for-bug solve has no weighted form
   if (ctx->robust_on && p->solve == ICPK_SOLVE_REFERENCE)
     return fail(ctx, ICPK_E_ARG, "robust alignment needs the Kabsch or point-to-plane flavour");
@@ -420,7 +430,8 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
 
   Profiler pf(ctx, p);
   const bool p2l = p->solve == ICPK_SOLVE_POINT_TO_PLANE;
-  const int nsum = robust ? (p2l ? NP2L_W : NSUM_W) : (p2l ? NP2L : NSUM);
+  const int nsum = robust ? (p2l ? NP2L_W : NSUM_W) : (p2l || gicp ? NP2L : NSUM);
+  double Tk[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
   double sums[NSUM_MAX];
   int64_t npairs = 0, kept = 0;  // kept: pairs with a weight > 0 (robust; else the accepted ones)
   double wsum = 0.0;             // W = sum w (robust; else the pair count)
@@ -432,8 +443,15 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
     r = pf.stamp(&pf.red);  // start of reduce
     if (r) return r;
     if (ctx->src.n > 0) {
-      r = robust ? enqueue_reduce_robust(ctx, p->max_nn_dist, p2l)
-                 : (p2l ? enqueue_reduce_p2l(ctx, p->max_nn_dist) : enqueue_reduce(ctx, p->max_nn_dist));
+      if (gicp) {  // R_acc: the floats T_out would hold now, as the device loop's kernel reads them from its state
+        float Racc[9];
+        for (int a = 0; a < 3; ++a)
+          for (int b = 0; b < 3; ++b) Racc[3 * a + b] = (float)Tk[4 * a + b];
+        r = enqueue_reduce_gicp(ctx, p->max_nn_dist, Racc);
+      } else {
+        r = robust ? enqueue_reduce_robust(ctx, p->max_nn_dist, p2l)
+                   : (p2l ? enqueue_reduce_p2l(ctx, p->max_nn_dist) : enqueue_reduce(ctx, p->max_nn_dist));
+      }
       if (r) return r;
     }
     r = pf.stamp(nullptr);  // end of reduce
@@ -449,7 +467,7 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
     }
     kept = robust ? (int64_t)sums[nsum - 1] : npairs;
     wsum = robust ? sums[nsum - 2] : (double)npairs;
-    if (p2l) {  // distance sum sits in the last slot
+    if (p2l || gicp) {  // distance sum sits in the last slot
       const float m = npairs > 0 ? (float)(sums[27] / (double)npairs) : 0.f;
       mse = (float)((double)m * (double)m);
     } else {
@@ -476,7 +494,6 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
 
   float Trot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   float offset[3] = {0, 0, 0};
-  double Tk[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
   // the motion of a Kabsch / point-to-plane solve: applied and recorded in float, accumulated into Tk in double
   auto take = [&](const double Rd[9], const double td[3]) -> int {
     float Rf[9], tf[3];
@@ -528,7 +545,7 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
       if (rc) return rc;
       ctx->trace_R.insert(ctx->trace_R.end(), R, R + 9);
       ctx->trace_t.insert(ctx->trace_t.end(), offset, offset + 3);
-    } else if (p2l) {
+    } else if (p2l || gicp) {
       if (!solve_p2l(sums, Rd, td)) {
         status = ICPK_W_DEGENERATE;
         break;

@@ -336,6 +336,7 @@ int icpk_commit_source(icpk_ctx* ctx) {
   ICPK_HIP(ctx, hipMemcpyAsync(b.y(), a.y(), (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   ICPK_HIP(ctx, hipMemcpyAsync(b.z(), a.z(), (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   ctx->src_pristine = a.n == b.n;  // (the two copies are equal again)
+  ctx->have_src_normals = false;   // (the uploaded source is another cloud now)
   return ICPK_OK;  // stream-ordered: no host wait
 }
 

@@ -2,7 +2,8 @@
 // host-side translation unit calls (icpk_api.cpp: context and clouds; icpk_sweep.cpp: NN sweeps and reductions;
 // icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
 // entry; icpk_frontend.cpp: depth images;
-// icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp).  Not part of the ABI.
+// icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp, icpk_gicp.cpp).  Not
+// part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -357,6 +358,21 @@ struct icpk_ctx {
   icpk::DevBuf<float4> flt_t4, flt_o4;
   bool have_flt = false;             // a filter has run: the record describes it
   int flt_n_in = 0, flt_n_out = 0, flt_n_finite = 0, flt_kind = 0, flt_min_neighbors = 0;
+  // plane-to-plane flavour (ICPK_SOLVE_PLANE_TO_PLANE, K14; icpk_gicp.cpp): the normals of the UPLOADED source in the
+  // caller's order (dropped with it: ensure_cloud, icpk_commit_source), the setting, and -- for
+  // icpk_estimate_source_normals only -- K1d's index of the uploaded source and K12's scratch in buffers of their own
+  icpk::Cloud snrm;
+  bool have_src_normals = false;
+  float gicp_epsilon = 1e-3f;
+  icpk::DevBuf<GridInfo> sn_grid_info;
+  icpk::DevBuf<float> sn_grid_bounds;
+  icpk::DevBuf<int> sn_cell_start;  // grid_max_cells + 1
+  icpk::DevBuf<int> sn_cell;        // 2 x n: the counting sort's cell and slot of every point
+  icpk::DevBuf<float4> sn_t4, sn_o4;
+  icpk::DevBuf<long long> sn_moments;  // [n][NRM_MOMENTS]
+  icpk::DevBuf<int> sn_count;          // [n]
+  icpk::DevBuf<float> sn_curv;         // [n]
+  icpk::DevBuf<int> sn_valid;          // 1
   int loop_nact = icpk::NSUM;      // device loop: sums the running alignment's step consumes (NSUM_REF or NSUM)
   int profile_phase = 0;     // alignments profiled so far (offsets the sampled launches, see profile_stride)
   int qperm_kind = 0;        // what qperm holds: 1 Morton order (pruned scan), 2 cell order (grid scan)
@@ -459,6 +475,9 @@ int enqueue_nn(icpk_ctx* ctx, int nn_mode, hipEvent_t ev0 = nullptr, hipEvent_t 
 const float4* loop_rec(const icpk_ctx* ctx);
 int enqueue_reduce(icpk_ctx* ctx, float max_dist);
 int enqueue_reduce_p2l(icpk_ctx* ctx, float max_dist);
+// plane-to-plane flavour of enqueue_reduce (K14).  R_acc: the rotation accumulated so far (9 floats); inside a device
+// loop the kernel reads it from the loop state and this may be null
+int enqueue_reduce_gicp(icpk_ctx* ctx, float max_dist, const float* R_acc);
 // robust sweep (K10): room for the selection of nq queries, its histogram cleared (once per alignment / hook call) ...
 int ensure_robust(icpk_ctx* ctx, int nq);
 // ... and the selection + the weighted K2 / K5 over the current associations (NSUM_W / NP2L_W sums; outside a device

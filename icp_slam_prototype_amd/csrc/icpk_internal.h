@@ -273,6 +273,20 @@ void launch_p2l_reduce(const nn_key_t* best, const float* ax, const float* ay, c
                        const float4* rec, float max_dist, int32_t* idx_out, float* dist_out, double* partial, int* pcount,
                        double* out, LoopState* st, hipStream_t s, const RobustSel* sel = nullptr);
 
+// kernels_gicp.hip -- K14, the plane-to-plane (generalized ICP) step (ICPK_SOLVE_PLANE_TO_PLANE; the rule is spelled
+// out in include/icpk.h).  NP2L sums in the layout solve_p2l reads.
+struct GicpArgs {
+  const float *snx, *sny, *snz;  // source normals, caller's order (same indexing as the working source)
+  const float *tnx, *tny, *tnz;  // target normals
+  float R[9];                    // R_acc when st == nullptr (a device loop reads LoopState::Tk instead)
+  float epsilon;
+};
+// arguments as launch_p2l_reduce's; rec != nullptr: the caller-order records of a device loop's grid sweep
+void launch_gicp_reduce(const nn_key_t* best, const float* ax, const float* ay, const float* az, int nq, const float* tx,
+                        const float* ty, const float* tz, const GicpArgs& g, const float4* rec, float max_dist,
+                        int32_t* idx_out, float* dist_out, double* partial, int* pcount, double* out, LoopState* st,
+                        hipStream_t s);
+
 // ---- robust alignment (K10: kernels_robust.hip, the weighted K2 / K5 of kernels_reduce.hip) ----------------------
 // The exact cut tau and median m of one sweep's accepted distances by a radix select over their bit patterns
 // (non-negative floats sort as unsigned integers; the sign bit is cleared, so -0 counts as +0): three passes of

@@ -1,5 +1,5 @@
 // icpk_sweep.cpp -- host side of the nearest-neighbour sweeps (K1 in every ICPK_NN_* mode) and of the reductions
-// (K2, K5): device buffers, target and query preparation, the frame-batch set-up recorder, and the C ABI's icpk_nn,
+// (K2, K5, K14): device buffers, target and query preparation, the frame-batch set-up recorder, and the C ABI's icpk_nn,
 // icpk_reduce, icpk_reduce_p2l and icpk_get_associations.
 #include <cstring>
 #include <utility>
@@ -13,6 +13,7 @@ namespace icpk {
 int ensure_cloud(icpk_ctx* ctx, Cloud& c, int n) {
   if (ctx && (&c == &ctx->src0 || &c == &ctx->src)) ctx->src_pristine = false;  // (about to be resized or rewritten)
   if (ctx && &c == &ctx->src) ctx->rec_pending = false;  // (whatever was to be unpacked into it is superseded)
+  if (ctx && &c == &ctx->src0) ctx->have_src_normals = false;  // (they describe the uploaded source that is being replaced)
   if (ctx && (&c == &ctx->src0 || &c == &ctx->tgt)) ctx->have_pix_seed = false;  // (other points than the pixel maps describe)
   const int cap = round_up(n < 1 ? 1 : n, NN_TILE);
   if (cap > c.cap) {
@@ -602,6 +603,19 @@ int enqueue_reduce_p2l(icpk_ctx* ctx, float max_dist) {
                     ctx->tgt.z(), ctx->nrm.x(), ctx->nrm.y(), ctx->nrm.z(), loop_rec(ctx), max_dist, ctx->st_active ? nullptr : ctx->idx,
                     ctx->st_active ? nullptr : ctx->dist, ctx->partial,
                     ctx->pcount, ctx->st_active ? nullptr : ctx->red_out, ctx->st_active, ctx->stream);
+  return read_back_sums(ctx, NP2L);
+}
+
+int enqueue_reduce_gicp(icpk_ctx* ctx, float max_dist, const float* R_acc) {
+  GicpArgs g{};
+  g.snx = ctx->snrm.x(), g.sny = ctx->snrm.y(), g.snz = ctx->snrm.z();
+  g.tnx = ctx->nrm.x(), g.tny = ctx->nrm.y(), g.tnz = ctx->nrm.z();
+  for (int k = 0; k < 9; ++k) g.R[k] = R_acc ? R_acc[k] : (k % 4 == 0 ? 1.f : 0.f);
+  g.epsilon = ctx->gicp_epsilon;
+  launch_gicp_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->src.n, ctx->tgt.x(), ctx->tgt.y(),
+                     ctx->tgt.z(), g, loop_rec(ctx), max_dist, ctx->st_active ? nullptr : ctx->idx,
+                     ctx->st_active ? nullptr : ctx->dist, ctx->partial, ctx->pcount,
+                     ctx->st_active ? nullptr : ctx->red_out, ctx->st_active, ctx->stream);
   return read_back_sums(ctx, NP2L);
 }
 

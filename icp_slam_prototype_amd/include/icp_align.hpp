@@ -119,6 +119,25 @@ class Engine {
     if (rc == ICPK_OK && n_valid) *n_valid = b;
     return rc;
   }
+  // plane-to-plane flavour (ICPK_SOLVE_PLANE_TO_PLANE): normals of the uploaded source -- estimated by
+  // estimateTargetNormals' rule (no host wait) or given from the host (n = the source size) --, their read-back
+  // (resized to 3 planes of icpk_source_size floats: x | y | z) and epsilon of the surface model, finite and in (0, 1].
+  // The normals stay with the source until it is replaced: set the source, then its normals, then icpk_align.
+  int estimateSourceNormals(float radius, int minNeighbors = 5, const float* viewpoint = nullptr) {
+    return icpk_estimate_source_normals(ctx_, radius, minNeighbors, viewpoint, 0);
+  }
+  int setSourceNormals(const float* nx, const float* ny, const float* nz, int32_t n) {
+    return icpk_set_source_normals(ctx_, nx, ny, nz, n);
+  }
+  int sourceNormals(std::vector<float>* planes) {
+    if (!planes) return ICPK_E_ARG;
+    const size_t n = (size_t)icpk_source_size(ctx_);
+    planes->assign(3 * n + 1, 0.f);  // (+1: valid pointers for an empty source)
+    const int rc = icpk_get_source_normals(ctx_, planes->data(), planes->data() + n, planes->data() + 2 * n);
+    planes->resize(3 * n);
+    return rc;
+  }
+  int setPlaneToPlane(float epsilon = 1e-3f) { return icpk_set_plane_to_plane(ctx_, epsilon); }
 
  private:
   icpk_ctx* ctx_ = nullptr;

@@ -62,6 +62,8 @@ extern "C" {
 #define ICPK_SOLVE_KABSCH 1    /* centred Kabsch, rigid_transform_3D.py:9-40         */
 #define ICPK_SOLVE_POINT_TO_PLANE 2 /* linearised point-to-plane (extension: TODO:9 of the \
                                        reference only plans it); needs target normals     */
+#define ICPK_SOLVE_PLANE_TO_PLANE 3 /* plane-to-plane step of Generalized-ICP (extension, K14): \
+                                       needs source AND target normals; see the section below */
 
 /* nearest-neighbour kernel selection */
 #define ICPK_NN_EXACT 0    /* literal double-precision distance per pair             */
@@ -770,6 +772,82 @@ int icpk_remove_outliers(icpk_ctx *ctx, int32_t which, const icpk_outlier_filter
  * Any may be NULL; ICPK_E_NOT_SET before the first call. */
 int icpk_get_outlier_stats(icpk_ctx *ctx, int32_t *n_in, int32_t *n_out, double *value, float *kth, int32_t *out_index,
                            double summary[4]);
+
+/* ---- plane-to-plane (generalized) ICP (K14; extension: the estimator of Segal, Haehnel and Thrun, "Generalized-ICP",
+ * RSS 2009, as pcl::GeneralizedIterativeClosestPoint and Open3D's registration_generalized_icp offer it) ----
+ * ICPK_SOLVE_POINT_TO_PLANE models the target's surface only.  This flavour models both: every point is a sample of a
+ * locally planar patch, known well along its normal and badly in the plane, and a pair's residual is weighed by the
+ * combined uncertainty of the two patches.  It needs one normal per point of BOTH clouds.
+ *
+ * Source normals.  They belong to the UPLOADED source -- the cloud icpk_align and icpk_reset_source start from --, are
+ * stored in the caller's order and stay as they are under icpk_transform_source, icpk_reset_source and the loop: the
+ * step rotates them by the accumulated pose itself.  (0,0,0) means "no normal".
+ *   icpk_estimate_source_normals  K12's rule (icpk_estimate_target_normals above), word for word, applied to the
+ *       uploaded source: neighbourhood, integer moments with F = 2^15, float64 Jacobi, line test, orientation, (0,0,0)
+ *       for no normal.  The search walks a uniform grid over the source in buffers of its own: the target's index is not
+ *       disturbed.  Stream-ordered, no host wait.  flags must be 0: there is no statistics record for the source, and
+ *       icpk_get_normal_stats stays the target's.  Argument errors as icpk_estimate_target_normals; ICPK_E_NOT_SET
+ *       without a source.
+ *   icpk_set_source_normals       from host arrays; n must equal the source size (else ICPK_E_ARG)
+ *   icpk_get_source_normals       to host arrays of icpk_source_size entries
+ *   lifetime   every call that replaces or re-indexes the uploaded source drops them: icpk_set_source*,
+ *       icpk_backproject* into the source, icpk_backproject_pair, icpk_detected_to_cloud(which = 0),
+ *       icpk_commit_source, and icpk_voxel_downsample / icpk_remove_outliers with which = 0 (unless STATS_ONLY).  The
+ *       getter, the hook and the flavour then return ICPK_E_NOT_SET.  Estimate after thinning and filtering.
+ *
+ * The setting.  icpk_set_plane_to_plane holds epsilon (the default, 1e-3, is the paper's): the variance a patch is given
+ * along its normal when the variance in its plane is 1.  ICPK_E_ARG unless it is finite and in (0, 1]; the setting is
+ * then left as it was.
+ *
+ * The rule, per sweep and per pair (i, j = the nearest target of working source point i, d their NN distance), float64
+ * throughout; every product and sum below is one rounded operation, in the association the parentheses show, and none
+ * is fused:
+ *   inputs     p = working source point i, q = target point j, a = source normal i, b = target normal j, all floats
+ *              widened.  R = R_acc, the rotation of the pose the loop has accumulated so far as icpk_align would return
+ *              it (the nine floats T_out[0..2], [4..6], [8..10] at that moment; the identity at the first sweep),
+ *              widened.  c = 1.0 - (double)epsilon.
+ *   m          m_u = (R[3u] a_0 + R[3u+1] a_1) + R[3u+2] a_2, u = 0, 1, 2.  Not renormalised.
+ *   S          the sum of the two patches' models C(n) = I - (1 - epsilon) n n^T (= V diag(epsilon, 1, 1) V^T for a unit
+ *              normal, I for the zero normal), upper triangle:
+ *                g_uv = m_u m_v + b_u b_v;   S_uu = 2.0 - c g_uu;   S_uv = 0.0 - c g_uv  (u < v)
+ *   M = S^-1   by the adjugate of the symmetric 3x3 and one determinant:
+ *                K_00 = S_11 S_22 - S_12 S_12    K_01 = S_02 S_12 - S_01 S_22    K_02 = S_01 S_12 - S_02 S_11
+ *                K_11 = S_00 S_22 - S_02 S_02    K_12 = S_01 S_02 - S_00 S_12    K_22 = S_00 S_11 - S_01 S_01
+ *                det = (S_00 K_00 + S_01 K_01) + S_02 K_02;   inv = 1.0 / det;   M_uv = K_uv inv  (M_vu = M_uv)
+ *   accepted   iff d < max_nn_dist (the float compare of icp.cpp:553) and det is finite and > 0.  A missing normal does
+ *              not reject a pair: a zero normal makes that side isotropic.  The determinant test can only fail for
+ *              non-unit normals given from the host.
+ *   step       r = p - q (r_u = p_u - q_u), J = [-[p]x | I] (3x6; the motion is x = (rotation vector, translation) and
+ *              p + J x its first order).  J is not formed; with
+ *                w_u  = (M_u0 r_0 + M_u1 r_1) + M_u2 r_2
+ *                B_0c = p_1 M_2c - p_2 M_1c;   B_1c = p_2 M_0c - p_0 M_2c;   B_2c = p_0 M_1c - p_1 M_0c   (B = [p]x M)
+ *                A_a0 = p_1 B_a2 - p_2 B_a1;   A_a1 = p_2 B_a0 - p_0 B_a2;   A_a2 = p_0 B_a1 - p_1 B_a0   (A = B [p]x^T)
+ *              the pair adds these 28 terms (6 + 9 + 6 entries of J^T M J, 6 of J^T M r, the distance):
+ *                [0..5]   A_00 A_01 A_02 B_00 B_01 B_02      [15..17] M_00 M_01 M_02
+ *                [6..10]  A_11 A_12 B_10 B_11 B_12           [18..19] M_11 M_12
+ *                [11..14] A_22 B_20 B_21 B_22                [20]     M_22
+ *                [21..23] p_1 w_2 - p_2 w_1,  p_2 w_0 - p_0 w_2,  p_0 w_1 - p_1 w_0     [24..26] w_0 w_1 w_2
+ *                [27]     (double)d
+ *              which is the ICPK_NP2L layout: [0..20] the upper triangle of sum J^T M J row-major, [21..26] sum J^T M r,
+ *              [27] sum d.  The sums go through the canonical tree (ICPK_RED_THREADS / ICPK_RED_MAX_BLOCKS) over the
+ *              source points in index order, a pair that is not accepted adding nothing.
+ *   solve      icpk_solve_point_to_plane's, unchanged ((sum J^T M J) x = -(sum J^T M r), Rodrigues); the loop takes the
+ *              path it takes for point-to-plane: the motion applied and recorded in float, accumulated in float64,
+ *              ICPK_W_DEGENERATE with the transform so far when the 6x6 is not positive definite, min_pairs and the
+ *              loop test on the accepted pairs, mse from [27].
+ * epsilon = 1 gives M = I/2 exactly and the step of point-to-point least squares; so do zero normals on both sides.
+ * Where it applies: icpk_align with ICPK_NN_EXACT / FILTERED / PRUNED / GRID and host_loop 0 and 1 -- every combination
+ * returns the same bits.  ICPK_E_NOT_SET without source or target normals.  ICPK_E_ARG with ICPK_NN_MAP, while
+ * icpk_set_robust is on (robust weights for this flavour are not implemented), and in icpk_align_batch / _device,
+ * icpk_align_frames_batch, icpk_align_query_sharded and icpk_align_to_map*: those clouds carry no normals. */
+int icpk_estimate_source_normals(icpk_ctx *ctx, float radius, int32_t min_neighbors, const float viewpoint[3] /* or NULL */,
+                                 int32_t flags);
+int icpk_set_source_normals(icpk_ctx *ctx, const float *nx, const float *ny, const float *nz, int32_t n);
+int icpk_get_source_normals(icpk_ctx *ctx, float *nx, float *ny, float *nz);
+int icpk_set_plane_to_plane(icpk_ctx *ctx, float epsilon);
+/* test hook: the 28 sums of the rule above and the accepted count over the associations of the last icpk_nn (as
+ * icpk_reduce_p2l), with the context's epsilon and the given R_acc (row-major; NULL: the identity) */
+int icpk_reduce_plane_to_plane(icpk_ctx *ctx, float max_dist, const float R_acc[9], double sums[28], int64_t *count);
 
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
