@@ -33,6 +33,9 @@ NORMALS_KEEP_MOMENTS = 1  # icpk_estimate_target_normals: keep the 10 int64 per 
 FILTER_STATISTICAL, FILTER_RADIUS = 0, 1  # icpk_remove_outliers: mean k-NN distance / neighbour count within a radius
 FILTER_MAX_K = 64
 FILTER_STATS_ONLY = 1  # icpk_remove_outliers: compute and keep the statistics, leave the cloud as it is
+SCORE_MAX_POSES = 4096  # icpk_score_poses: poses per call
+NSCORE = 11  # ... sums per pose: sum d, sum d^2, sum q (3), sum q q^T (upper triangle, 6)
+SCORE_KEEP_ASSOC = 1  # ... keep every pose's (index, distance) for icpk_get_score_associations
 
 # every symbol include/icpk.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -59,6 +62,7 @@ SYMBOLS = [
     "icpk_remove_outliers", "icpk_get_outlier_stats",
     "icpk_estimate_source_normals", "icpk_set_source_normals", "icpk_get_source_normals", "icpk_set_plane_to_plane",
     "icpk_reduce_plane_to_plane",
+    "icpk_score_poses", "icpk_get_score_associations", "icpk_score_metrics", "icpk_information_matrix",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -288,6 +292,12 @@ def load():
     lib.icpk_get_source_normals.argtypes = [C.c_void_p, fp, fp, fp]
     lib.icpk_set_plane_to_plane.argtypes = [C.c_void_p, C.c_float]
     lib.icpk_reduce_plane_to_plane.argtypes = [C.c_void_p, C.c_float, fp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    lib.icpk_score_poses.argtypes = [C.c_void_p, C.c_int32, fp, C.c_float, C.c_int32, dp, C.POINTER(C.c_int64)]
+    lib.icpk_get_score_associations.argtypes = [C.c_void_p, C.c_int32, ip, fp]
+    lib.icpk_score_metrics.argtypes = [dp, C.c_int64, C.c_int32, fp, fp, fp]
+    lib.icpk_score_metrics.restype = None
+    lib.icpk_information_matrix.argtypes = [dp, C.c_int64, dp]
+    lib.icpk_information_matrix.restype = None
     _lib = lib
     return lib
 
@@ -402,6 +412,24 @@ def solve_kabsch(n, sa, sb, sab):
     load().icpk_solve_kabsch(int(n), sa.ctypes.data_as(dp), sb.ctypes.data_as(dp), sab.ctypes.data_as(dp),
                              R.ctypes.data_as(dp), t.ctypes.data_as(dp))
     return R.reshape(3, 3), t
+
+
+def score_metrics(sums, inliers, n_source):
+    """icpk_score_metrics (host only): (fitness, inlier_rmse, mean_dist) as float32 from one pose's NSCORE sums."""
+    dp = C.POINTER(C.c_double)
+    sums = np.ascontiguousarray(sums, np.float64).reshape(NSCORE)
+    f, r, m = C.c_float(0), C.c_float(0), C.c_float(0)
+    load().icpk_score_metrics(sums.ctypes.data_as(dp), int(inliers), int(n_source), C.byref(f), C.byref(r), C.byref(m))
+    return np.float32(f.value), np.float32(r.value), np.float32(m.value)
+
+
+def information_matrix(sums, inliers):
+    """icpk_information_matrix (host only): the (6, 6) float64 sum G^T G, G = [-[q]x | I], from one pose's NSCORE sums."""
+    dp = C.POINTER(C.c_double)
+    sums = np.ascontiguousarray(sums, np.float64).reshape(NSCORE)
+    info = np.zeros(36, np.float64)
+    load().icpk_information_matrix(sums.ctypes.data_as(dp), int(inliers), info.ctypes.data_as(dp))
+    return info.reshape(6, 6)
 
 
 class Context:
@@ -834,6 +862,38 @@ class Context:
         self._chk(self._lib.icpk_reduce_plane_to_plane(self._h, max_dist, None if R is None else _fp(R),
                                                        sums.ctypes.data_as(C.POINTER(C.c_double)), C.byref(cnt)))
         return sums, cnt.value
+
+    # -- pose scoring (icpk_score_poses) -----------------------------------------------
+    def score_poses(self, T=None, max_dist=0.75, keep_assoc=False):
+        """Scores candidate poses of the uploaded source against the target (include/icpk.h): T (n, 4, 4) or (4, 4)
+        float32 row-major, or None for the working source as it stands (after align: the alignment just computed).
+        The context's state is not touched.  Returns dict(sums (n, 11) float64, inliers (n,) int64, fitness,
+        inlier_rmse, mean_dist (n,) float32, information (n, 6, 6) float64)."""
+        if T is None:
+            n, Tp = 1, None
+        else:
+            Tf = _f(T).reshape(-1, 16)
+            n, Tp = Tf.shape[0], _fp(Tf)
+        sums = np.zeros((max(n, 1), NSCORE), np.float64)
+        inl = np.zeros(max(n, 1), np.int64)
+        self._chk(self._lib.icpk_score_poses(self._h, n, Tp, float(max_dist), SCORE_KEEP_ASSOC if keep_assoc else 0,
+                                             sums.ctypes.data_as(C.POINTER(C.c_double)),
+                                             inl.ctypes.data_as(C.POINTER(C.c_int64))))
+        ns = self.source_size
+        met = np.array([score_metrics(sums[k], inl[k], ns) for k in range(n)], np.float32).reshape(n, 3)
+        info = np.stack([information_matrix(sums[k], inl[k]) for k in range(n)]) if n else np.zeros((0, 6, 6))
+        return dict(sums=sums[:n], inliers=inl[:n], fitness=met[:, 0].copy(), inlier_rmse=met[:, 1].copy(),
+                    mean_dist=met[:, 2].copy(), information=info)
+
+    def score_associations(self, pose=0):
+        """(index (ns,) int32, distance (ns,) float32) of pose `pose` of the last score_poses(keep_assoc=True): -1 and
+        +inf for a point without a partner within max_dist."""
+        n = self.source_size
+        idx = np.empty(n, np.int32)
+        dist = np.empty(n, np.float32)
+        self._chk(self._lib.icpk_get_score_associations(self._h, int(pose), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        _fp(dist)))
+        return idx, dist
 
     # -- loop ---------------------------------------------------------------------
     def align(self, params=None, **kw):

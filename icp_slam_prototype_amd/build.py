@@ -15,7 +15,8 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "kernels_nn_pruned.hip", "kernels_loop.hip", "kernels_grid.hip", "kernels_frontend.hip",
            "icpk_map.cpp", "kernels_map.hip", "icpk_fast.cpp", "kernels_fast.hip", "kernels_map_nn.hip", "kernels_robust.hip",
            "icpk_voxel.cpp", "kernels_voxel.hip", "icpk_normals.cpp", "kernels_normals.hip",
-           "icpk_filter.cpp", "kernels_filter.hip", "icpk_gicp.cpp", "kernels_gicp.hip"]
+           "icpk_filter.cpp", "kernels_filter.hip", "icpk_gicp.cpp", "kernels_gicp.hip",
+           "icpk_score.cpp", "kernels_score.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -204,6 +205,23 @@ def build_gicp_test(force=False):
     return GICP_TEST
 
 
+SCORE_TEST = os.path.join(LIBDIR, "test_score")
+
+
+def build_score_test(force=False):
+    """Host-only C++ program over icp::Engine::scorePoses / scoreCurrent (g++, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_score.cpp")
+    hdr = os.path.join(HERE, "include", "icp_align.hpp")
+    build()
+    newest = max(os.path.getmtime(p) for p in (src, hdr, LIB))
+    if not force and os.path.exists(SCORE_TEST) and os.path.getmtime(SCORE_TEST) >= newest:
+        return SCORE_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", SCORE_TEST])
+    return SCORE_TEST
+
+
 THREADS_TEST = os.path.join(LIBDIR, "test_threads")
 
 
@@ -266,4 +284,5 @@ if __name__ == "__main__":
     print(build_normals_test(force="--force" in sys.argv))
     print(build_filter_test(force="--force" in sys.argv))
     print(build_gicp_test(force="--force" in sys.argv))
+    print(build_score_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

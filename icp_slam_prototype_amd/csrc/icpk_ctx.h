@@ -2,7 +2,8 @@
 // host-side translation unit calls (icpk_api.cpp: context and clouds; icpk_sweep.cpp: NN sweeps and reductions;
 // icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
 // entry; icpk_frontend.cpp: depth images;
-// icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp, icpk_gicp.cpp).  Not
+// icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp, icpk_gicp.cpp,
+// icpk_score.cpp).  Not
 // part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -373,6 +374,19 @@ struct icpk_ctx {
   icpk::DevBuf<int> sn_count;          // [n]
   icpk::DevBuf<float> sn_curv;         // [n]
   icpk::DevBuf<int> sn_valid;          // 1
+  // pose scoring (icpk_score_poses, K15; icpk_score.cpp): the poses on their way to the device, the keys of every
+  // (pose, point) -- of one chunk of poses, or of the whole call when the associations are kept --, the canonical
+  // tree's scratch and the results
+  icpk::PinnedBuf<float> score_T_host;   // 16 x n_poses
+  icpk::DevBuf<float> score_T;
+  icpk::DevBuf<nn_key_t> score_keys;     // [chunk][ns] ...
+  icpk::DevBuf<nn_key_t> score_kept;     // ... or, with ICPK_SCORE_KEEP_ASSOC, [n_poses][ns] in a buffer of their own
+  icpk::DevBuf<double> score_partial;    // [chunk][NSCORE][RED_MAX_BLOCKS]
+  icpk::DevBuf<int> score_pcount;        // [chunk][RED_MAX_BLOCKS]
+  icpk::DevBuf<double> score_out;        // [n_poses][NSCORE + 1]
+  icpk::PinnedBuf<double> score_out_host;
+  bool have_score_assoc = false;   // score_kept holds every pose of the last ICPK_SCORE_KEEP_ASSOC call on the current clouds
+  int score_n_poses = 0, score_ns = 0;
   int loop_nact = icpk::NSUM;      // device loop: sums the running alignment's step consumes (NSUM_REF or NSUM)
   int profile_phase = 0;     // alignments profiled so far (offsets the sampled launches, see profile_stride)
   int qperm_kind = 0;        // what qperm holds: 1 Morton order (pruned scan), 2 cell order (grid scan)

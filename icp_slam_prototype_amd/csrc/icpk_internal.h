@@ -38,6 +38,11 @@ struct Rt {
   float R[9];
   float t[3];
 };
+// one row of K3's p' = fl32(fl32(R p) + t) (kernels_transform.hip; K15 moves its points with the same operations):
+// products of two floats are exact in double; two double roundings, then one to float
+__device__ __forceinline__ float rot_row(float r0, float r1, float r2, float x, float y, float z) {
+  return (float)__builtin_fma((double)r2, (double)z, __builtin_fma((double)r1, (double)y, (double)r0 * (double)x));
+}
 struct LoopState;  // device-side loop state, defined below
 struct RobustSel;         // robust selection state (kernels_robust.hip), defined below
 struct RobustTraceEntry;  // ... and its per-iteration record
@@ -698,5 +703,26 @@ void launch_radius_count(const float4* t4, const int* cell_start, const GridInfo
                          hipStream_t s);
 // threshold (STATISTICAL: the canonical sums, then mu, sigma, T on one lane) and the order-preserving compaction
 void launch_filter_compact(const FilterArgs& a, hipStream_t s);
+
+// kernels_score.hip -- K15, scoring of candidate poses (icpk_score_poses)
+constexpr int NSCORE = 11;             // ICPK_NSCORE
+constexpr int SCORE_CHUNK_POSES = 256;      // poses per launch at most (the partials' scratch: 11 x 256 doubles per pose) ...
+constexpr size_t SCORE_CHUNK_KEYS = 1 << 24;  // ... and (pose, point) keys per launch (128 MiB of scratch)
+struct ScoreArgs {
+  const float *sx, *sy, *sz;  // the source points, caller's order
+  int ns;
+  float max_dist;
+  const float* T;             // 16 floats per pose of this launch (row-major 4 x 4), or nullptr: the points as they stand
+  const float4* t4;           // the target sorted by cell (x, y, z, original index): K1d's index
+  const int* cell_start;
+  const GridInfo* gi;
+  const float4* o4;           // the target in the caller's order
+  nn_key_t* keys;             // [poses][ns]: an inlier's (distance bits << 32) | index, NN_KEY_INIT for the others
+  double* partial;            // [poses][NSCORE][RED_MAX_BLOCKS] scratch of the canonical tree
+  int* pcount;                // [poses][RED_MAX_BLOCKS]
+  double* out;                // [poses][NSCORE + 1]: the sums, then the inlier count as an int64
+};
+// the three launches of one chunk of poses (search, per-block sums, final sums); n_poses <= 0: nothing
+void launch_score_poses(const ScoreArgs& a, int n_poses, hipStream_t s);
 
 }  // namespace icpk

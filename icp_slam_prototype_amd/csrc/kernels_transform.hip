@@ -9,11 +9,7 @@
 
 namespace icpk {
 
-__device__ __forceinline__ float rot_row(float r0, float r1, float r2, float x, float y, float z) {
-  // products of two floats are exact in double; two double roundings, then one to float
-  return (float)__builtin_fma((double)r2, (double)z, __builtin_fma((double)r1, (double)y, (double)r0 * (double)x));
-}
-
+// (rot_row: icpk_internal.h)
 __global__ __launch_bounds__(256) void transform_kernel(float* __restrict__ x, float* __restrict__ y,
                                                         float* __restrict__ z, int n4, Rt rt) {
   float4* x4 = reinterpret_cast<float4*>(x);

@@ -52,6 +52,15 @@ struct AlignResult {
   float (*rotation())[4] { return reinterpret_cast<float(*)[4]>(T); }
 };
 
+// one candidate pose as icpk_score_poses judges it: the inliers within maxDist, the metrics of icpk_score_metrics, the
+// 6x6 information matrix of the pair (row-major; rotation vector, then translation) and the sums they are made of
+struct PoseScore {
+  int64_t inliers = 0;
+  float fitness = 0.f, inlierRmse = 0.f, meanDist = 0.f;
+  double information[36] = {};
+  double sums[ICPK_NSCORE] = {};
+};
+
 // RAII owner of one icpk_ctx (one GPU, one HIP stream).  One Engine per host
 // thread / per GPU; calls on one Engine are serialised.
 class Engine {
@@ -138,6 +147,36 @@ class Engine {
     return rc;
   }
   int setPlaneToPlane(float epsilon = 1e-3f) { return icpk_set_plane_to_plane(ctx_, epsilon); }
+  // pose scoring (icpk_score_poses): n candidate poses (T: 16 floats each, row-major 4x4) of the uploaded source
+  // against the target in one call -- fitness, inlier RMSE, mean distance and the information matrix of each; the
+  // engine's clouds, associations and seeds stay as they are.  flags: ICPK_SCORE_KEEP_ASSOC.
+  int scorePoses(const float* T, int n, float maxDist, std::vector<PoseScore>* out, int flags = 0) {
+    if (!out) return ICPK_E_ARG;
+    const size_t m = n > 0 ? (size_t)n : 1;
+    std::vector<double> sums(m * ICPK_NSCORE, 0.0);
+    std::vector<int64_t> inl(m, 0);
+    const int rc = icpk_score_poses(ctx_, n, T, maxDist, flags, sums.data(), inl.data());
+    if (rc != ICPK_OK) return rc;
+    const int32_t ns = icpk_source_size(ctx_);
+    out->assign((size_t)n, PoseScore{});
+    for (int k = 0; k < n; ++k) {
+      PoseScore& s = (*out)[(size_t)k];
+      const double* sk = sums.data() + (size_t)k * ICPK_NSCORE;
+      s.inliers = inl[(size_t)k];
+      std::memcpy(s.sums, sk, sizeof(s.sums));
+      icpk_score_metrics(sk, s.inliers, ns, &s.fitness, &s.inlierRmse, &s.meanDist);
+      icpk_information_matrix(sk, s.inliers, s.information);
+    }
+    return ICPK_OK;
+  }
+  // ... and the working source as it stands (after icpk_align: the alignment just computed)
+  int scoreCurrent(float maxDist, PoseScore* out) {
+    if (!out) return ICPK_E_ARG;
+    std::vector<PoseScore> v;
+    const int rc = scorePoses(nullptr, 1, maxDist, &v);
+    if (rc == ICPK_OK) *out = v[0];
+    return rc;
+  }
 
  private:
   icpk_ctx* ctx_ = nullptr;

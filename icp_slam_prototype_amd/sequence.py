@@ -97,8 +97,11 @@ class SequenceRunner:
     HEADER = "MSE,ICP rX,ICP rY,ICP rZ,GT rX,GT rY,GT rZ"  # SLAM.cpp:327
 
     def __init__(self, ctx, max_iterations=16, threshold=1e-4, fx=468.60, cx=318.27, voxel_leaf=0.0,
-                 voxel_mode=binding.VOXEL_CENTROID, outlier_filter=None, **params):
-        """outlier_filter: a dict of Context.remove_outliers' settings (kind, k, std_ratio, radius, min_neighbors), or
+                 voxel_mode=binding.VOXEL_CENTROID, outlier_filter=None, score_max_dist=None, **params):
+        """score_max_dist: a distance (metres) or None; when given, every step's record gains `fitness` and
+        `inlier_rmse` of the alignment just computed (Context.score_poses(None, score_max_dist) after the alignment);
+        None: the record and the calls made are those without it.
+        outlier_filter: a dict of Context.remove_outliers' settings (kind, k, std_ratio, radius, min_neighbors), or
         None; both clouds of every frame pair are filtered with it (target first, then source) between back-projection
         and the voxel downsample, if any.
         voxel_leaf > 0: both clouds of every frame pair are voxel-grid downsampled with this leaf (metres) between
@@ -108,6 +111,7 @@ class SequenceRunner:
         self.fx, self.cx = fx, cx
         self.voxel_leaf, self.voxel_mode = float(voxel_leaf), voxel_mode
         self.outlier_filter = None if outlier_filter is None else dict(outlier_filter)
+        self.score_max_dist = None if score_max_dist is None else float(score_max_dist)
         self.camera_rotation = np.eye(3, dtype=np.float32)      # icp.cpp:49
         self.camera_position = np.full(3, 5, np.float32)        # icp.cpp:53
         self.last_rotation = np.eye(3, dtype=np.float32)
@@ -136,7 +140,11 @@ class SequenceRunner:
             c.voxel_downsample(1, self.voxel_leaf, self.voxel_mode)
             c.voxel_downsample(0, self.voxel_leaf, self.voxel_mode)
         T, st, rc = c.align(last_rotation=self.last_rotation, last_translation=self.last_translation, **self.kw)
-        return self._advance(depth, T, st, rc, c.get_trace(max(self.kw["max_iterations"], 1)), timestamp, ground_truth)
+        out = self._advance(depth, T, st, rc, c.get_trace(max(self.kw["max_iterations"], 1)), timestamp, ground_truth)
+        if self.score_max_dist is not None:
+            sc = c.score_poses(None, self.score_max_dist)
+            out["fitness"], out["inlier_rmse"] = sc["fitness"][0], sc["inlier_rmse"][0]
+        return out
 
     def _advance(self, depth, T, st, rc, trace, timestamp, ground_truth):
         """The bookkeeping after one alignment (icp.cpp:235-261, SLAM.cpp:283-327): the per-frame result."""
@@ -172,6 +180,8 @@ class MultiSequenceRunner:
             raise ValueError("voxel-grid downsampling is not available in the lock-step batch: use SequenceRunner")
         if "outlier_filter" in params:
             raise ValueError("outlier removal is not available in the lock-step batch: use SequenceRunner")
+        if "score_max_dist" in params:
+            raise ValueError("pose scoring is not available in the lock-step batch: use SequenceRunner")
         self.ctx = ctx
         self.runners = [SequenceRunner(None, max_iterations, threshold, fx, cx, **params) for _ in range(n_streams)]
         self.kw = self.runners[0].kw

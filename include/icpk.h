@@ -849,6 +849,64 @@ int icpk_set_plane_to_plane(icpk_ctx *ctx, float epsilon);
  * icpk_reduce_p2l), with the context's epsilon and the given R_acc (row-major; NULL: the identity) */
 int icpk_reduce_plane_to_plane(icpk_ctx *ctx, float max_dist, const float R_acc[9], double sums[28], int64_t *count);
 
+/* ---- pose scoring (K15; extension: what Open3D's evaluate_registration / GetInformationMatrixFromPointClouds and PCL's
+ * getFitnessScore answer) ----
+ * How good is a pose?  For every one of n_poses candidate poses: how many source points find a target within max_dist,
+ * how far away, and the eleven sums from which fitness, inlier RMSE, mean distance and the 6x6 information matrix of
+ * the pair follow.  Many poses are scored in one call (one launch covers poses x source points); the context's state
+ * is not touched, and no seeds are needed: a candidate pose may be anywhere.  The rule:
+ *   points     for pose k, T_k = T[16 k ..] row-major with R = entries [0..2], [4..6], [8..10] and t = [3], [7], [11]
+ *              (row 3 is ignored).  Source point i of the UPLOADED source (the cloud icpk_align and icpk_reset_source
+ *              start from) gives p = fl32(fl32(R s) + t): icpk_transform_source's arithmetic, operation for operation.
+ *              T == NULL requires n_poses == 1 and scores the WORKING source exactly as it stands (no transform): after
+ *              icpk_align this scores the alignment just computed.
+ *   partner    the target j that minimises (d, j) lexicographically, d the pair distance of icp.cpp:606-620 exactly as
+ *              every NN search here evaluates it (float differences, float64 sum of squares, narrowed, correctly
+ *              rounded float sqrt), among the targets with d < max_dist (the float compare of icp.cpp:553).  If there is
+ *              none the point is not an inlier.  A non-finite p, or a non-finite target, never pairs.  For an inlier
+ *              this is the pair icpk_nn would report for p, bit for bit.
+ *   terms      per inlier, with q = target j widened to float64 and dd = (double)d, the ICPK_NSCORE = 11 terms
+ *                [0] dd   [1] dd dd   [2..4] q_x q_y q_z   [5..10] q_x q_x, q_x q_y, q_x q_z, q_y q_y, q_y q_z, q_z q_z
+ *              each product one rounded operation.  A point that is not an inlier adds +0.0.
+ *   sums       per pose each term through the canonical reduction tree (ICPK_RED_THREADS / ICPK_RED_MAX_BLOCKS, the tree
+ *              of icpk_reduce) over the source points in index order: sums[ICPK_NSCORE k ..].  inliers[k] is the exact
+ *              count.
+ *   metrics    (icpk_score_metrics; float64, then narrowed) fitness = inliers / n_source (0 for n_source <= 0);
+ *              inlier_rmse = sqrt(sums[1] / inliers); mean_dist = sums[0] / inliers; both 0 with no inliers.
+ *   information (icpk_information_matrix; row-major 6x6, order: rotation vector, translation) sum G^T G over the
+ *              inliers with G = [-[q]x | I], the matrix Open3D's GetInformationMatrixFromPointClouds forms, assembled
+ *              from the sums (Sxx = sums[5] and so on, Sx = sums[2] ...), symmetric:
+ *                rotation block              [0][0] = Syy + Szz   [0][1] = -Sxy        [0][2] = -Sxz
+ *                                            [1][1] = Sxx + Szz   [1][2] = -Syz        [2][2] = Sxx + Syy
+ *                rotation / translation      [0][3] = 0    [0][4] = -Sz  [0][5] = Sy
+ *                                            [1][3] = Sz   [1][4] = 0    [1][5] = -Sx
+ *                                            [2][3] = -Sy  [2][4] = Sx   [2][5] = 0
+ *                translation block           inliers * I
+ * What is exact: every partner and distance for any order of the target; inliers; and, for a given order of the
+ * source, every sum -- the same bits on every run.
+ * The call leaves the working source, the uploaded source, both normals, the associations and the seeds of the last
+ * sweep and the target's index exactly as they were.  The search walks the uniform grid of ICPK_NN_GRID and builds it
+ * if the target has none yet: the alignment that follows finds it built.  Stream-ordered, one host wait (the results).
+ * ICPK_E_ARG (nothing changes) for n_poses outside 1 .. ICPK_SCORE_MAX_POSES, T == NULL with n_poses != 1, a max_dist
+ * that is not finite and > 0, an unknown flag, NULL sums or inliers; ICPK_E_NOT_SET without a source or a target; an
+ * empty target returns what icpk_nn returns for it; an empty source gives zero sums and zero inliers; a pose with a
+ * non-finite entry simply scores zero inliers wherever that entry reaches a point. */
+#define ICPK_SCORE_MAX_POSES 4096
+#define ICPK_NSCORE 11
+#define ICPK_SCORE_KEEP_ASSOC 1 /* flags: keep every pose's (index, distance) for icpk_get_score_associations */
+int icpk_score_poses(icpk_ctx *ctx, int32_t n_poses, const float *T /* 16 * n_poses, or NULL */, float max_dist,
+                     int32_t flags, double *sums /* ICPK_NSCORE * n_poses */, int64_t *inliers /* n_poses */);
+/* Pose `pose` of the last icpk_score_poses made with ICPK_SCORE_KEEP_ASSOC (8 bytes per pose and source point stay on
+ * the device until the next such call): per source point the partner's index and distance, -1 and +inf for a point
+ * without one.  Either array may be NULL.  ICPK_E_NOT_SET before such a call, or after the uploaded source or the
+ * target changed; ICPK_E_ARG for a pose outside that call. */
+int icpk_get_score_associations(icpk_ctx *ctx, int32_t pose, int32_t *idx_out, float *dist_out);
+/* host only (no device work): the metrics and the information matrix of the rule above from one pose's sums; any
+ * output of icpk_score_metrics may be NULL */
+void icpk_score_metrics(const double sums[ICPK_NSCORE], int64_t inliers, int32_t n_source, float *fitness,
+                        float *inlier_rmse, float *mean_dist);
+void icpk_information_matrix(const double sums[ICPK_NSCORE], int64_t inliers, double info[36]);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity

@@ -1,0 +1,70 @@
+"""icp::Engine::scorePoses / scoreCurrent (tests/cpp/test_score.cpp) against the C ABI's output and against the same
+calls made through the Python binding, bit for bit."""
+import os
+import struct
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import gicp_model as gm
+from icp_slam_prototype_amd import binding, build
+from test_gpu_score import pose
+
+pytestmark = pytest.mark.gpu
+
+REC = 8 + 16 + 36 * 8 + 11 * 8
+
+
+def records(raw, first, n):
+    out = []
+    for k in range(first, first + n):
+        o = k * REC
+        out.append(dict(inliers=struct.unpack_from("<q", raw, o)[0], metrics=np.frombuffer(raw, np.float32, 3, o + 8),
+                        information=np.frombuffer(raw, np.float64, 36, o + 24).reshape(6, 6),
+                        sums=np.frombuffer(raw, np.float64, 11, o + 24 + 288)))
+    return out
+
+
+def same(a, b):
+    return (a["inliers"] == b["inliers"] and a["metrics"].tobytes() == b["metrics"].tobytes()
+            and a["information"].tobytes() == b["information"].tobytes() and a["sums"].tobytes() == b["sums"].tobytes())
+
+
+def test_cpp_engine_equals_c_abi_and_binding():
+    exe = build.build_score_test()
+    p = gm.quarter_pair()
+    src, tgt = p["source"], p["target"]
+    ns, nt = src.shape[1], tgt.shape[1]
+    T = np.stack([pose(), pose(0, 2.0, 0, (0.03, 0, 0)), pose(0.5, -1.0, 0.3, (-0.02, 0.01, 0.0))])
+    max_dist, iters = 0.25, 5
+    with tempfile.TemporaryDirectory() as td:
+        fin, fout = os.path.join(td, "in.f32"), os.path.join(td, "out.bin")
+        with open(fin, "wb") as f:
+            f.write(np.ascontiguousarray(src, np.float32).tobytes())
+            f.write(np.ascontiguousarray(tgt, np.float32).tobytes())
+            f.write(np.ascontiguousarray(T, np.float32).tobytes())
+        out = subprocess.run([exe, fin, str(ns), str(nt), "3", str(max_dist), str(iters), fout], capture_output=True,
+                             text=True, timeout=120)
+        assert out.returncode == 0, out.stderr
+        raw = open(fout, "rb").read()
+    assert len(raw) == 8 * REC + 16
+    eng, abi, cur = records(raw, 0, 3), records(raw, 3, 3), records(raw, 6, 2)
+    status, bad_n, final_pairs, _ = struct.unpack_from("<4i", raw, 8 * REC)
+    with binding.Context(0) as c:
+        c.set_target(tgt)
+        c.set_source(src)
+        want = c.score_poses(T, max_dist)
+        _, st, rc = c.align(solve=binding.SOLVE_KABSCH, max_iterations=iters, fixed_iterations=1, max_nn_dist=max_dist)
+        wcur = c.score_poses(None, max_dist)
+
+    def from_binding(w, k):
+        return dict(inliers=int(w["inliers"][k]), information=w["information"][k], sums=w["sums"][k],
+                    metrics=np.array([w["fitness"][k], w["inlier_rmse"][k], w["mean_dist"][k]], np.float32))
+
+    for k in range(3):
+        assert same(eng[k], abi[k]) and same(eng[k], from_binding(want, k)), k
+        assert eng[k]["inliers"] > 0
+    assert same(cur[0], cur[1]) and same(cur[0], from_binding(wcur, 0))
+    assert (status, bad_n, final_pairs) == (rc, binding.E_ARG, st.final_pairs) and cur[0]["inliers"] == st.final_pairs
