@@ -36,6 +36,10 @@ FILTER_STATS_ONLY = 1  # icpk_remove_outliers: compute and keep the statistics, 
 SCORE_MAX_POSES = 4096  # icpk_score_poses: poses per call
 NSCORE = 11  # ... sums per pose: sum d, sum d^2, sum q (3), sum q q^T (upper triangle, 6)
 SCORE_KEEP_ASSOC = 1  # ... keep every pose's (index, distance) for icpk_get_score_associations
+FPFH_BINS = 33  # icpk_compute_fpfh: floats per descriptor (three sub-histograms of 11 bins)
+FPFH_KEEP_SPFH = 1  # ... keep the SPFH counts and m for icpk_get_spfh
+MATCH_MUTUAL = 1  # icpk_match_features: keep a pair only if each is the other's best
+GLOBAL_MAX_HYPOTHESES = 1 << 20  # icpk_register_global
 
 # every symbol include/icpk.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -63,6 +67,8 @@ SYMBOLS = [
     "icpk_estimate_source_normals", "icpk_set_source_normals", "icpk_get_source_normals", "icpk_set_plane_to_plane",
     "icpk_reduce_plane_to_plane",
     "icpk_score_poses", "icpk_get_score_associations", "icpk_score_metrics", "icpk_information_matrix",
+    "icpk_default_global_params", "icpk_compute_fpfh", "icpk_get_fpfh", "icpk_get_spfh", "icpk_match_features",
+    "icpk_get_feature_matches", "icpk_register_global", "icpk_global_hypotheses",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -120,6 +126,18 @@ class Pair(C.Structure):
         ("nt", C.c_int32),
         ("idx_out", C.POINTER(C.c_int32)), ("dist_out", C.POINTER(C.c_float)),
     ]
+
+
+class GlobalParams(C.Structure):
+    """icpk_global_params"""
+    _fields_ = [("seed", C.c_uint64), ("n_hypotheses", C.c_int32), ("max_dist", C.c_float),
+                ("edge_similarity", C.c_float), ("reserved", C.c_int32)]
+
+
+class GlobalResult(C.Structure):
+    """icpk_global_result"""
+    _fields_ = [("T", C.c_float * 16), ("hypothesis", C.c_int32), ("n_valid", C.c_int32), ("n_matches", C.c_int32),
+                ("reserved", C.c_int32), ("inliers", C.c_int64), ("sums", C.c_double * 11)]
 
 
 class FrameJob(C.Structure):
@@ -298,6 +316,16 @@ def load():
     lib.icpk_score_metrics.restype = None
     lib.icpk_information_matrix.argtypes = [dp, C.c_int64, dp]
     lib.icpk_information_matrix.restype = None
+    lib.icpk_default_global_params.argtypes = [C.POINTER(GlobalParams)]
+    lib.icpk_default_global_params.restype = None
+    lib.icpk_compute_fpfh.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_int32]
+    lib.icpk_get_fpfh.argtypes = [C.c_void_p, C.c_int32, fp, u8, ip]
+    lib.icpk_get_spfh.argtypes = [C.c_void_p, C.c_int32, ip, ip]
+    lib.icpk_match_features.argtypes = [C.c_void_p, C.c_int32]
+    lib.icpk_get_feature_matches.argtypes = [C.c_void_p, ip, ip, fp, ip]
+    lib.icpk_register_global.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(GlobalResult)]
+    lib.icpk_global_hypotheses.argtypes = [ip, ip, C.c_int32, fp, fp, fp, C.c_int32, fp, fp, fp, C.c_int32, C.c_uint64,
+                                           C.c_float, C.c_int64, C.c_int32, ip, u8, fp]
     _lib = lib
     return lib
 
@@ -430,6 +458,28 @@ def information_matrix(sums, inliers):
     info = np.zeros(36, np.float64)
     load().icpk_information_matrix(sums.ctypes.data_as(dp), int(inliers), info.ctypes.data_as(dp))
     return info.reshape(6, 6)
+
+
+def global_hypotheses(matches, src, tgt, seed, edge_similarity=0.9, h0=0, count=1):
+    """icpk_global_hypotheses (host only): hypotheses h0 .. h0 + count - 1 of icpk_register_global's draw over `matches`
+    ((src_index, tgt_index) int arrays) and the clouds src, tgt ((3, n) float32).  Returns (samples (count, 3) int32,
+    valid (count,) bool, T (count, 4, 4) float32)."""
+    ip, u8 = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    ms = np.ascontiguousarray(matches[0], np.int32).reshape(-1)
+    mt = np.ascontiguousarray(matches[1], np.int32).reshape(-1)
+    s = [_f(src[k]) for k in range(3)]
+    t = [_f(tgt[k]) for k in range(3)]
+    count = int(count)
+    samples = np.zeros((max(count, 1), 3), np.int32)
+    valid = np.zeros(max(count, 1), np.uint8)
+    T = np.zeros((max(count, 1), 16), np.float32)
+    rc = load().icpk_global_hypotheses(ms.ctypes.data_as(ip), mt.ctypes.data_as(ip), ms.size, _fp(s[0]), _fp(s[1]),
+                                       _fp(s[2]), s[0].size, _fp(t[0]), _fp(t[1]), _fp(t[2]), t[0].size, int(seed),
+                                       float(edge_similarity), int(h0), count, samples.ctypes.data_as(ip),
+                                       valid.ctypes.data_as(u8), _fp(T))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_global_hypotheses")
+    return samples[:count], valid[:count].astype(bool), T[:count].reshape(count, 4, 4)
 
 
 class Context:
@@ -894,6 +944,54 @@ class Context:
         self._chk(self._lib.icpk_get_score_associations(self._h, int(pose), idx.ctypes.data_as(C.POINTER(C.c_int32)),
                                                         _fp(dist)))
         return idx, dist
+
+    # -- global registration (icpk_compute_fpfh / icpk_match_features / icpk_register_global) ----
+    def compute_fpfh(self, which, radius, keep_spfh=False):
+        """FPFH descriptors of the uploaded source (which = 0, needs source normals) or the target (which = 1, needs
+        target normals) over the neighbours within `radius` (include/icpk.h, K16).  Stream-ordered: no host wait."""
+        return self._chk(self._lib.icpk_compute_fpfh(self._h, int(which), float(radius), FPFH_KEEP_SPFH if keep_spfh else 0))
+
+    def get_fpfh(self, which):
+        """(desc (n, 33) float32 in the caller's point order, valid (n,) bool)"""
+        n = self.source_size if which == 0 else self.target_size
+        desc = np.zeros((max(n, 1), FPFH_BINS), np.float32)
+        valid = np.zeros(max(n, 1), np.uint8)
+        m = C.c_int32(0)
+        self._chk(self._lib.icpk_get_fpfh(self._h, int(which), _fp(desc), valid.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(m)))
+        return desc[:m.value], valid[:m.value].astype(bool)
+
+    def get_spfh(self, which):
+        """(counts (n, 33) int32, m (n,) int32) of the last compute_fpfh(which, keep_spfh=True)"""
+        n = self.source_size if which == 0 else self.target_size
+        counts = np.zeros((max(n, 1), FPFH_BINS), np.int32)
+        m = np.zeros(max(n, 1), np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._chk(self._lib.icpk_get_spfh(self._h, int(which), counts.ctypes.data_as(ip), m.ctypes.data_as(ip)))
+        return counts[:n], m[:n]
+
+    def match_features(self, mutual=False):
+        """Pairs every valid source descriptor with its nearest valid target descriptor (ties: the lowest index);
+        mutual: only pairs that are each other's best.  Returns (src_index, tgt_index int32, D float32), source order;
+        the pairs stay on the device for register_global."""
+        self._chk(self._lib.icpk_match_features(self._h, MATCH_MUTUAL if mutual else 0))
+        n = max(self.source_size, 1)
+        si, ti, D = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+        m = C.c_int32(0)
+        ip = C.POINTER(C.c_int32)
+        self._chk(self._lib.icpk_get_feature_matches(self._h, si.ctypes.data_as(ip), ti.ctypes.data_as(ip), _fp(D), C.byref(m)))
+        return si[:m.value].copy(), ti[:m.value].copy(), D[:m.value].copy()
+
+    def register_global(self, n_hypotheses=4096, seed=0, max_dist=0.75, edge_similarity=0.9):
+        """Seeded RANSAC over the matches of match_features, ranked by score_poses' path (include/icpk.h, K16).
+        Returns (dict(T (4, 4) float32, hypothesis, inliers, sums (11,) float64, n_valid, n_matches), rc); rc is
+        W_TOO_FEW_PAIRS (T the identity) with fewer than 3 matches or no valid hypothesis."""
+        p = GlobalParams()
+        self._lib.icpk_default_global_params(C.byref(p))
+        p.n_hypotheses, p.seed, p.max_dist, p.edge_similarity = int(n_hypotheses), int(seed), float(max_dist), float(edge_similarity)
+        r = GlobalResult()
+        rc = self._chk(self._lib.icpk_register_global(self._h, C.byref(p), C.byref(r)))
+        return dict(T=np.array(r.T, np.float32).reshape(4, 4), hypothesis=r.hypothesis, inliers=int(r.inliers),
+                    sums=np.array(r.sums, np.float64), n_valid=r.n_valid, n_matches=r.n_matches), rc
 
     # -- loop ---------------------------------------------------------------------
     def align(self, params=None, **kw):

@@ -16,7 +16,7 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_map.cpp", "kernels_map.hip", "icpk_fast.cpp", "kernels_fast.hip", "kernels_map_nn.hip", "kernels_robust.hip",
            "icpk_voxel.cpp", "kernels_voxel.hip", "icpk_normals.cpp", "kernels_normals.hip",
            "icpk_filter.cpp", "kernels_filter.hip", "icpk_gicp.cpp", "kernels_gicp.hip",
-           "icpk_score.cpp", "kernels_score.hip"]
+           "icpk_score.cpp", "kernels_score.hip", "icpk_fpfh.cpp", "kernels_fpfh.hip", "icpk_global.cpp"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -222,6 +222,23 @@ def build_score_test(force=False):
     return SCORE_TEST
 
 
+FPFH_TEST = os.path.join(LIBDIR, "test_fpfh")
+
+
+def build_fpfh_test(force=False):
+    """Host-only C++ program over icp::Engine::computeFPFH / matchFeatures / registerGlobal (g++, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_fpfh.cpp")
+    hdr = os.path.join(HERE, "include", "icp_align.hpp")
+    build()
+    newest = max(os.path.getmtime(p) for p in (src, hdr, LIB))
+    if not force and os.path.exists(FPFH_TEST) and os.path.getmtime(FPFH_TEST) >= newest:
+        return FPFH_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", FPFH_TEST])
+    return FPFH_TEST
+
+
 THREADS_TEST = os.path.join(LIBDIR, "test_threads")
 
 
@@ -285,4 +302,5 @@ if __name__ == "__main__":
     print(build_filter_test(force="--force" in sys.argv))
     print(build_gicp_test(force="--force" in sys.argv))
     print(build_score_test(force="--force" in sys.argv))
+    print(build_fpfh_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

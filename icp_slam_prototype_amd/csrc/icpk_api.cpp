@@ -220,6 +220,7 @@ void target_changed(icpk_ctx* ctx, bool keep_normals) {
   if (!keep_normals) ctx->have_normals = false;
   ctx->have_nstats = false;  // (icpk_get_normal_stats speaks of the target it was estimated on)
   ctx->have_score_assoc = false;  // (as icpk_get_score_associations of the target it scored against)
+  fpfh_dropped(ctx, 1);           // (and K16's descriptors of the target and its normals)
 }
 
 void reset_outputs(float T_out[16], icpk_stats* stats) {
@@ -338,6 +339,7 @@ int icpk_commit_source(icpk_ctx* ctx) {
   ICPK_HIP(ctx, hipMemcpyAsync(b.z(), a.z(), (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   ctx->src_pristine = a.n == b.n;  // (the two copies are equal again)
   ctx->have_src_normals = false;   // (the uploaded source is another cloud now)
+  fpfh_dropped(ctx, 0);
   ctx->have_score_assoc = false;
   return ICPK_OK;  // stream-ordered: no host wait
 }
@@ -448,6 +450,7 @@ int icpk_set_target_normals(icpk_ctx* ctx, const float* nx, const float* ny, con
   if (rc) return rc;
   ctx->have_normals = true;
   ctx->have_nstats = false;
+  fpfh_dropped(ctx, 1);
   return ICPK_OK;
 }
 

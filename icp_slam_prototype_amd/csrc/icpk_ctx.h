@@ -3,7 +3,7 @@
 // icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
 // entry; icpk_frontend.cpp: depth images;
 // icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp, icpk_gicp.cpp,
-// icpk_score.cpp).  Not
+// icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp).  Not
 // part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -387,6 +387,25 @@ struct icpk_ctx {
   icpk::PinnedBuf<double> score_out_host;
   bool have_score_assoc = false;   // score_kept holds every pose of the last ICPK_SCORE_KEEP_ASSOC call on the current clouds
   int score_n_poses = 0, score_ns = 0;
+  // FPFH descriptors and their matches (icpk_compute_fpfh / icpk_match_features / icpk_register_global, K16;
+  // icpk_fpfh.cpp, icpk_global.cpp): per cloud ([0] the uploaded source, [1] the target) the normals in cell order, the
+  // 16-bit SPFH, the kept counts and the descriptors; the best keys of both directions and the kept pairs
+  struct FpfhSide {
+    icpk::DevBuf<float4> n4;          // [n] cell order
+    icpk::DevBuf<unsigned short> g;   // [n][FPFH_G_STRIDE] cell order
+    icpk::DevBuf<int> counts, m;      // [n][FPFH_BINS], [n] (ICPK_FPFH_KEEP_SPFH)
+    icpk::DevBuf<float> desc;         // [n][FPFH_BINS] caller's order
+    icpk::DevBuf<uint8_t> valid;      // [n]
+    bool have = false;                // they describe the cloud and the normals the context holds now
+    bool kept_spfh = false;
+    int n = 0;
+  } fpfh[2];
+  icpk::DevBuf<nn_key_t> match_best[2];  // [ns], [nt]
+  icpk::DevBuf<int> match_src, match_tgt;  // [ns]
+  icpk::DevBuf<float> match_D;             // [ns]
+  icpk::DevBuf<int> match_n;               // the number of kept pairs ...
+  icpk::PinnedBuf<int> match_n_host;       // ... and where the host reads it
+  bool have_matches = false;       // the pairs belong to the descriptors both sides hold now
   int loop_nact = icpk::NSUM;      // device loop: sums the running alignment's step consumes (NSUM_REF or NSUM)
   int profile_phase = 0;     // alignments profiled so far (offsets the sampled launches, see profile_stride)
   int qperm_kind = 0;        // what qperm holds: 1 Morton order (pruned scan), 2 cell order (grid scan)
@@ -421,6 +440,13 @@ namespace icpk {
 inline int fail(icpk_ctx* ctx, int code, const char* msg) {
   if (ctx) ctx->err = msg;
   return code;
+}
+
+// the cloud `which` (0 the uploaded source, 1 the target) or its normals have changed: K16's descriptors and matches
+// speak of what was there before
+inline void fpfh_dropped(icpk_ctx* ctx, int which) {
+  ctx->fpfh[which].have = false;
+  ctx->have_matches = false;
 }
 
 inline int hip_failure(icpk_ctx* ctx, const char* what, hipError_t e) {
@@ -497,6 +523,11 @@ int ensure_robust(icpk_ctx* ctx, int nq);
 // ... and the selection + the weighted K2 / K5 over the current associations (NSUM_W / NP2L_W sums; outside a device
 // loop the sums, the count and the selection state are read back into red_host / rsel_host, not waited for)
 int enqueue_reduce_robust(icpk_ctx* ctx, float max_dist, bool p2l);
+
+// ---- icpk_gicp.cpp ----
+// K1d's index of the UPLOADED source in the sn_* buffers (K14's source normals, K16's source descriptors): neither the
+// target's index nor the filter's is touched
+int build_uploaded_source_index(icpk_ctx* ctx);
 
 // ---- icpk_align.cpp: the device-side loop, shared by the single-pair and the frame-batch path ----
 int loop_nsum(const icpk_params* p);

@@ -9,9 +9,8 @@
 
 using namespace icpk;
 
-namespace {
+namespace icpk {
 
-// K1d's index of the UPLOADED source in this file's buffers: neither the target's index nor the filter's is touched
 int build_uploaded_source_index(icpk_ctx* ctx) {
   const Cloud& c = ctx->src0;
   const size_t n = (size_t)c.n;
@@ -25,6 +24,10 @@ int build_uploaded_source_index(icpk_ctx* ctx) {
   return build_grid_index(ctx, c.x(), c.y(), c.z(), c.n, ctx->sn_grid_bounds, ctx->sn_grid_info, ctx->sn_cell,
                           ctx->sn_cell + n, ctx->sn_cell_start, ctx->sn_t4, ctx->sn_o4);
 }
+
+}  // namespace icpk
+
+namespace {
 
 // the planes of ctx->snrm beyond n, up to the capacity: zero (no normal)
 int pad_source_normals(icpk_ctx* ctx, int n) {
@@ -56,6 +59,7 @@ int icpk_estimate_source_normals(icpk_ctx* ctx, float radius, int32_t min_neighb
   if (!rc) rc = ensure_cloud(ctx, ctx->snrm, n);
   if (rc) return rc;
   ctx->have_src_normals = false;  // (the planes are about to be rewritten)
+  fpfh_dropped(ctx, 0);
   const Cloud& c = ctx->snrm;
   if (n > 0) {
     if ((rc = build_uploaded_source_index(ctx))) return rc;
@@ -91,6 +95,7 @@ int icpk_set_source_normals(icpk_ctx* ctx, const float* nx, const float* ny, con
   int rc = ensure_cloud(ctx, ctx->snrm, n);
   if (rc) return rc;
   ctx->have_src_normals = false;
+  fpfh_dropped(ctx, 0);
   const Cloud& c = ctx->snrm;
   const float* const from[3] = {nx, ny, nz};
   float* const planes[3] = {c.x(), c.y(), c.z()};

@@ -725,4 +725,38 @@ struct ScoreArgs {
 // the three launches of one chunk of poses (search, per-block sums, final sums); n_poses <= 0: nothing
 void launch_score_poses(const ScoreArgs& a, int n_poses, hipStream_t s);
 
+// kernels_fpfh.hip -- K16, FPFH descriptors of a cloud and their matching (icpk_compute_fpfh, icpk_match_features)
+constexpr int FPFH_BINS = 33;       // ICPK_FPFH_BINS: three sub-histograms of 11 bins
+constexpr int FPFH_G_STRIDE = 34;   // 16-bit words per point of the normalised SPFH: the 33 bins, then "m > 0"
+struct FpfhArgs {
+  const float4* t4;           // the cloud sorted by cell (x, y, z, original index): K1d's index
+  const int* cell_start;
+  const GridInfo* gi;
+  const float *nx, *ny, *nz;  // its normals in the caller's order, n each
+  int n;
+  float radius;
+  float4* n4;                 // [n] cell order: the normal, w = 1 for a described point and 0 for any other
+  unsigned short* g;          // [n][FPFH_G_STRIDE] cell order
+  int* counts;                // [n][FPFH_BINS] caller's order, or nullptr (ICPK_FPFH_KEEP_SPFH)
+  int* m;                     // [n] caller's order, or nullptr
+  float* desc;                // [n][FPFH_BINS] caller's order
+  uint8_t* valid;             // [n]
+};
+// the three launches of one cloud's descriptors (normals into cell order, SPFH, FPFH); n <= 0: nothing
+void launch_compute_fpfh(const FpfhArgs& a, hipStream_t s);
+struct MatchArgs {
+  const float* fa;            // descriptors of the side that searches, [na][FPFH_BINS] ...
+  const uint8_t* va;          // ... and which of its points are valid
+  int na;
+  int nb;
+  const float* fb;            // the side that is searched
+  const uint8_t* vb;
+  nn_key_t* best;             // [na], pre-set to NN_KEY_INIT: (bits(D) << 32) | index of the best valid b
+};
+void launch_match_features(const MatchArgs& a, hipStream_t s);
+// the kept pairs in source order: every valid source with a partner, under `mutual` only where the partner's own best
+// is that source.  *n_out (device) = their number; msrc / mtgt / mD: room for ns entries
+void launch_match_compact(const nn_key_t* best_s, int ns, const nn_key_t* best_t, int mutual, int* msrc, int* mtgt,
+                          float* mD, int* n_out, hipStream_t s);
+
 }  // namespace icpk

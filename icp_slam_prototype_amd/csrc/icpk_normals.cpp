@@ -19,6 +19,7 @@ int icpk_estimate_target_normals(icpk_ctx* ctx, float radius, int32_t min_neighb
   if (!ctx->have_tgt) return fail(ctx, ICPK_E_NOT_SET, "target cloud not set");
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   ctx->have_nstats = false;
+  fpfh_dropped(ctx, 1);
   const int n = ctx->tgt.n;
   const size_t cap = n < 1 ? 1 : (size_t)n;
   int rc = ctx->nrm_moments.reserve(ctx, cap * NRM_MOMENTS);

@@ -14,6 +14,7 @@ int ensure_cloud(icpk_ctx* ctx, Cloud& c, int n) {
   if (ctx && (&c == &ctx->src0 || &c == &ctx->src)) ctx->src_pristine = false;  // (about to be resized or rewritten)
   if (ctx && &c == &ctx->src) ctx->rec_pending = false;  // (whatever was to be unpacked into it is superseded)
   if (ctx && &c == &ctx->src0) ctx->have_src_normals = false;  // (they describe the uploaded source that is being replaced)
+  if (ctx && &c == &ctx->src0) fpfh_dropped(ctx, 0);           // (as K16's descriptors and matches do)
   if (ctx && (&c == &ctx->src0 || &c == &ctx->tgt)) ctx->have_pix_seed = false;  // (other points than the pixel maps describe)
   if (ctx && (&c == &ctx->src0 || &c == &ctx->tgt)) ctx->have_score_assoc = false;  // (K15's kept associations speak of the clouds they were scored on)
   const int cap = round_up(n < 1 ? 1 : n, NN_TILE);

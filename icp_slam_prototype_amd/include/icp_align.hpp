@@ -52,6 +52,12 @@ struct AlignResult {
   float (*rotation())[4] { return reinterpret_cast<float(*)[4]>(T); }
 };
 
+// one pair of Engine::matchFeatures: source index, target index, the squared descriptor distance
+struct FeatureMatch {
+  int32_t source, target;
+  float distance;
+};
+
 // one candidate pose as icpk_score_poses judges it: the inliers within maxDist, the metrics of icpk_score_metrics, the
 // 6x6 information matrix of the pair (row-major; rotation vector, then translation) and the sums they are made of
 struct PoseScore {
@@ -176,6 +182,37 @@ class Engine {
     const int rc = scorePoses(nullptr, 1, maxDist, &v);
     if (rc == ICPK_OK) *out = v[0];
     return rc;
+  }
+  // global registration (include/icpk.h, K16): FPFH descriptors of the uploaded source (which = 0, needs source
+  // normals) or of the target (which = 1, needs target normals); their matches, brought to the host if asked for; and
+  // the seeded RANSAC over the matches that scorePoses' path ranks.  The pose of *out moves the source onto the target:
+  // icpk_transform_source with it, then icpk_align, refines it.
+  int computeFPFH(int which, float radius, int flags = 0) { return icpk_compute_fpfh(ctx_, which, radius, flags); }
+  int fpfh(int which, std::vector<float>* desc, std::vector<uint8_t>* valid) {
+    const size_t n = (size_t)(which == 0 ? icpk_source_size(ctx_) : icpk_target_size(ctx_));
+    if (desc) desc->assign(n * ICPK_FPFH_BINS + 1, 0.f);  // (+1: valid pointers for an empty cloud)
+    if (valid) valid->assign(n + 1, 0);
+    int32_t m = 0;
+    const int rc = icpk_get_fpfh(ctx_, which, desc ? desc->data() : nullptr, valid ? valid->data() : nullptr, &m);
+    if (desc) desc->resize(rc == ICPK_OK ? (size_t)m * ICPK_FPFH_BINS : 0);
+    if (valid) valid->resize(rc == ICPK_OK ? (size_t)m : 0);
+    return rc;
+  }
+  int matchFeatures(bool mutual, std::vector<FeatureMatch>* out = nullptr) {
+    int rc = icpk_match_features(ctx_, mutual ? ICPK_MATCH_MUTUAL : 0);
+    if (rc != ICPK_OK || !out) return rc;
+    const size_t cap = (size_t)icpk_source_size(ctx_) + 1;
+    std::vector<int32_t> si(cap), ti(cap);
+    std::vector<float> D(cap);
+    int32_t m = 0;
+    rc = icpk_get_feature_matches(ctx_, si.data(), ti.data(), D.data(), &m);
+    if (rc != ICPK_OK) return rc;
+    out->resize((size_t)m);
+    for (int32_t k = 0; k < m; ++k) (*out)[(size_t)k] = FeatureMatch{si[(size_t)k], ti[(size_t)k], D[(size_t)k]};
+    return ICPK_OK;
+  }
+  int registerGlobal(const icpk_global_params& params, icpk_global_result* out) {
+    return icpk_register_global(ctx_, &params, out);
   }
 
  private:

@@ -907,6 +907,115 @@ void icpk_score_metrics(const double sums[ICPK_NSCORE], int64_t inliers, int32_t
                         float *inlier_rmse, float *mean_dist);
 void icpk_information_matrix(const double sums[ICPK_NSCORE], int64_t inliers, double info[36]);
 
+/* ---- global registration (K16; extension: what Open3D's compute_fpfh_feature + registration_ransac_based_on_feature_
+ * matching and PCL's FPFHEstimation + SampleConsensusPrerejective answer) ----
+ * Every alignment above needs a starting pose inside ICP's basin of convergence.  These calls find one without any:
+ * a local shape descriptor per point (FPFH: Rusu, Blodow, Beetz, "Fast Point Feature Histograms (FPFH) for 3D
+ * Registration", ICRA 2009), descriptor matching, and a seeded RANSAC whose hypotheses icpk_score_poses (K15) ranks.
+ * The rules are this library's own restatement: integer wherever an order could matter, so that every result is the
+ * same bits on every run and the bits of the CPU model in tests/fpfh_model.py.
+ *
+ * 1. icpk_compute_fpfh(ctx, which, radius, flags).  which = 0: the UPLOADED source with its source normals (K14's
+ * lifetime rules); which = 1: the target with its target normals.  d(i, j) is the pair distance of icp.cpp:606-620 as
+ * every search here evaluates it, a float; "<=" on it is a float compare.  Everything else is float64, every product,
+ * sum and quotient one rounded operation, none fused; x . y = (x0 y0 + x1 y1) + x2 y2; x X y = (x1 y2 - x2 y1,
+ * x2 y0 - x0 y2, x0 y1 - x1 y0).
+ *   described  point i is described iff its coordinates and its normal are finite and the normal is not (0, 0, 0).
+ *   stage 1 (SPFH counts, integers)  for a described i and every described j with 0 < d(i, j) <= r:
+ *              dp = p_j - p_i (floats widened);  f4 = sqrt((dp0^2 + dp1^2) + dp2^2);  skip if f4 == 0
+ *              a1 = (n_i . dp) / f4;  a2 = (n_j . dp) / f4
+ *              if |a1| < |a2|: (n1, n2) = (n_j, n_i), dp = -dp, f3 = -a2;  else: (n1, n2) = (n_i, n_j), f3 = a1
+ *              v = dp X n1;  vn = sqrt(v . v);  skip if vn == 0;  v = v / vn (per component)
+ *              w = n1 X v;  f2 = v . n2;  a = w . n2;  b = n1 . n2
+ *              B2 = bin(f2), B3 = bin(f3) with bin(f) = t >= 10 ? 10 : (t >= 1 ? (int)t : 0),
+ *                t = floor(11.0 * ((f + 1.0) * 0.5))        (clamp((int)floor(.), 0, 10); NaN gives 0)
+ *              B1 = the sector of atan2(a, b) among 11 equal sectors of [-pi, pi], WITHOUT any libm call: with
+ *                beta_k = -pi + 2 pi k / 11 and C_k, S_k the doubles nearest cos(beta_k), sin(beta_k) (tabulated as hex
+ *                literals in csrc/fpfh_table.h, which the model parses) and e_k = C_k a - S_k b:
+ *                  a == 0 and b == 0:  B1 = 5
+ *                  else a >= 0:        B1 = 5 + #{k in 6..10 : e_k >= 0}
+ *                  else:               B1 = 5 - #{k in 1..5 : e_k < 0}
+ *              c_i[B1]++, c_i[11 + B2]++, c_i[22 + B3]++, m_i++
+ *   stage 2 (FPFH)  g_j[b] = m_j > 0 ? (c_j[b] * 32768) / m_j : 0  (integer division; <= 32768, 16 bits).
+ *              For a described i and every j with 0 < d(i, j) <= r and m_j > 0:
+ *                u = ((double)r (double)r) / ((double)d (double)d);  q = (int64)rint(fmin(u, 16384.0) * 1024.0)
+ *                A_i[b] += q g_j[b];  Q_i += q        (int64; no overflow below 2^23 neighbours)
+ *              raw_b = (double)g_i[b] + (Q_i > 0 ? (double)A_i[b] / (double)Q_i : 0.0)
+ *              per sub-histogram (bins 0..10, 11..21, 22..32) tot = the 11 raw values added in bin order;
+ *              out_b = tot > 0 ? (float)((100.0 raw_b) / tot) : 0
+ *   valid      iff described and m_i > 0.  Every other point gets 33 zeros and is never matched.
+ * Deviations from PCL / Open3D: the neighbour weights are r^2 / d^2, capped at 2^14 and normalised by their sum (theirs:
+ * 1 / d^2 divided by the neighbour count, which depends on the unit of length); zero-distance neighbours are skipped
+ * (theirs divide by zero or special-case them); the histograms are fixed-point (theirs: float accumulation in search
+ * order); the sector B1 is decided by signs against tabulated boundaries instead of atan2.
+ * The source walks a uniform grid in buffers of its own (K14's), the target the context's grid (ICPK_NN_GRID), built
+ * if absent: the alignment that follows finds it built.  Stream-ordered, no host wait.  An empty cloud gives empty
+ * descriptors.  ICPK_E_NOT_SET without that cloud or its normals; ICPK_E_ARG for another `which`, a radius that is not
+ * finite and > 0, or an unknown flag.
+ * icpk_get_fpfh: desc n x ICPK_FPFH_BINS floats in the caller's point order, valid n bytes, *n the count; any may be
+ * NULL.  icpk_get_spfh (after ICPK_FPFH_KEEP_SPFH, else ICPK_E_ARG): counts n x 33 and m n int32.  Both wait, and both
+ * return ICPK_E_NOT_SET once the cloud or its normals have changed: the events that drop K12's statistics record (target)
+ * and K14's source normals (source).
+ *
+ * 2. icpk_match_features(ctx, flags).  Both clouds must hold current descriptors (else ICPK_E_NOT_SET).  For every valid
+ * source i: the valid target j that minimises (D, j) lexicographically, D = (float)(sum over b = 0..32 in order of
+ * ((double)fs_b - (double)ft_b)^2), the sum starting from +0.0.  With ICPK_MATCH_MUTUAL the pair is kept only if i is, by
+ * the same rule with the roles exchanged, the best source of j.  The kept pairs, in source order, stay on the device for
+ * icpk_register_global; icpk_get_feature_matches (waits; arrays of icpk_source_size entries or NULL) brings them to the
+ * host as (src_index, tgt_index, D).  No valid point on one side gives zero pairs, not an error.  Stream-ordered.
+ *
+ * 3. icpk_register_global(ctx, p, out).  Per hypothesis h = 0 .. n_hypotheses - 1:
+ *   draws      d = 0 .. 15:  z = seed + (h + 1) * 0x9E3779B97F4A7C15 + d * 0xD1B54A32D192ED03, then icpk_set_subsample's
+ *              finaliser (z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31);
+ *              c = (uint32)(z >> 32) % n_matches.  The first three DISTINCT c in draw order are the sample; fewer than
+ *              three in 16 draws: the hypothesis is invalid.
+ *   edges      for the pairs (0,1), (0,2), (1,2) of the sample: ls, lt = icpk_distance3 of the two source points and of
+ *              the two target points; valid iff ls >= e lt and lt >= e ls for all three (float products,
+ *              e = edge_similarity).
+ *   pose       icpk_solve_kabsch(3, sum a, sum b, sum a b^T) with a the source and b the target points widened, every sum
+ *              started at +0.0 and added in sample order (the convention icpk_reduce's Kabsch path feeds the solve: the
+ *              pose moves source onto target), narrowed to a row-major float 4x4 with the last row (0, 0, 0, 1).
+ *   scoring    the valid hypotheses, in order of h, through icpk_score_poses in chunks of ICPK_SCORE_MAX_POSES at
+ *              p->max_dist.  The best pose has the most inliers, then the smallest sums[1], then the lowest h.
+ * Fewer than 3 matches, or no valid hypothesis: ICPK_W_TOO_FEW_PAIRS with the identity and hypothesis = -1.
+ * ICPK_E_ARG for n_hypotheses outside 1 .. ICPK_GLOBAL_MAX_HYPOTHESES, a max_dist that is not finite and > 0 or an
+ * edge_similarity outside [0, 1]; ICPK_E_NOT_SET without current matches.  The call leaves clouds, normals, associations
+ * and seeds exactly as icpk_score_poses leaves them; refine with icpk_transform_source(R, t of out->T) + icpk_align.
+ * icpk_global_hypotheses is the draw on its own, host only (no device work, no context): hypotheses h0 .. h0 + count - 1
+ * over the given matches and point arrays; samples 3 per hypothesis (indices into the matches, -1 where the draws gave
+ * none), valid one byte, T 16 floats (the identity unless valid); any output may be NULL. */
+#define ICPK_FPFH_BINS 33
+#define ICPK_FPFH_KEEP_SPFH 1 /* flags of icpk_compute_fpfh: keep the counts and m for icpk_get_spfh */
+#define ICPK_MATCH_MUTUAL 1   /* flags of icpk_match_features */
+#define ICPK_GLOBAL_MAX_HYPOTHESES (1 << 20)
+typedef struct icpk_global_params {
+  uint64_t seed;
+  int32_t n_hypotheses;  /* 1 .. ICPK_GLOBAL_MAX_HYPOTHESES */
+  float max_dist;        /* the inlier distance of the scoring */
+  float edge_similarity; /* in [0, 1]; icpk_default_global_params: 0.9 */
+  int32_t reserved;
+} icpk_global_params;
+typedef struct icpk_global_result {
+  float T[16];         /* row-major 4x4: moves the uploaded source onto the target */
+  int32_t hypothesis;  /* the winner's h, -1: none */
+  int32_t n_valid;     /* hypotheses that passed the draw and the edge check */
+  int32_t n_matches;
+  int32_t reserved;
+  int64_t inliers;
+  double sums[ICPK_NSCORE]; /* the winner's sums as icpk_score_poses returns them */
+} icpk_global_result;
+void icpk_default_global_params(icpk_global_params *p); /* 4096 hypotheses, seed 0, max_dist 0.75, edge_similarity 0.9 */
+int icpk_compute_fpfh(icpk_ctx *ctx, int32_t which, float radius, int32_t flags);
+int icpk_get_fpfh(icpk_ctx *ctx, int32_t which, float *desc, uint8_t *valid, int32_t *n);
+int icpk_get_spfh(icpk_ctx *ctx, int32_t which, int32_t *counts, int32_t *m);
+int icpk_match_features(icpk_ctx *ctx, int32_t flags);
+int icpk_get_feature_matches(icpk_ctx *ctx, int32_t *src_index, int32_t *tgt_index, float *D, int32_t *n);
+int icpk_register_global(icpk_ctx *ctx, const icpk_global_params *p, icpk_global_result *out);
+int icpk_global_hypotheses(const int32_t *match_src, const int32_t *match_tgt, int32_t n_matches, const float *sx,
+                           const float *sy, const float *sz, int32_t ns, const float *tx, const float *ty,
+                           const float *tz, int32_t nt, uint64_t seed, float edge_similarity, int64_t h0, int32_t count,
+                           int32_t *samples, uint8_t *valid, float *T);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
