@@ -37,6 +37,7 @@ SCORE_MAX_POSES = 4096  # icpk_score_poses: poses per call
 NSCORE = 11  # ... sums per pose: sum d, sum d^2, sum q (3), sum q q^T (upper triangle, 6)
 SCORE_KEEP_ASSOC = 1  # ... keep every pose's (index, distance) for icpk_get_score_associations
 FPFH_BINS = 33  # icpk_compute_fpfh: floats per descriptor (three sub-histograms of 11 bins)
+COLOR_KEEP_SUMS = 1  # icpk_estimate_target_color_gradients: keep the ten sums per point
 FPFH_KEEP_SPFH = 1  # ... keep the SPFH counts and m for icpk_get_spfh
 MATCH_MUTUAL = 1  # icpk_match_features: keep a pair only if each is the other's best
 GLOBAL_MAX_HYPOTHESES = 1 << 20  # icpk_register_global
@@ -66,6 +67,9 @@ SYMBOLS = [
     "icpk_remove_outliers", "icpk_get_outlier_stats",
     "icpk_estimate_source_normals", "icpk_set_source_normals", "icpk_get_source_normals", "icpk_set_plane_to_plane",
     "icpk_reduce_plane_to_plane",
+    "icpk_intensity_from_bgr", "icpk_set_target_colors", "icpk_set_source_colors", "icpk_get_target_colors",
+    "icpk_get_source_colors", "icpk_estimate_target_color_gradients", "icpk_get_target_color_gradients",
+    "icpk_get_color_gradient_sums", "icpk_set_colored", "icpk_reduce_colored",
     "icpk_score_poses", "icpk_get_score_associations", "icpk_score_metrics", "icpk_information_matrix",
     "icpk_default_global_params", "icpk_compute_fpfh", "icpk_get_fpfh", "icpk_get_spfh", "icpk_match_features",
     "icpk_get_feature_matches", "icpk_register_global", "icpk_global_hypotheses",
@@ -310,6 +314,17 @@ def load():
     lib.icpk_get_source_normals.argtypes = [C.c_void_p, fp, fp, fp]
     lib.icpk_set_plane_to_plane.argtypes = [C.c_void_p, C.c_float]
     lib.icpk_reduce_plane_to_plane.argtypes = [C.c_void_p, C.c_float, fp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    lib.icpk_intensity_from_bgr.argtypes = [C.POINTER(C.c_uint8), C.c_int32, fp]
+    lib.icpk_intensity_from_bgr.restype = None
+    lib.icpk_set_target_colors.argtypes = [C.c_void_p, fp, C.c_int32]
+    lib.icpk_set_source_colors.argtypes = [C.c_void_p, fp, C.c_int32]
+    lib.icpk_get_target_colors.argtypes = [C.c_void_p, fp]
+    lib.icpk_get_source_colors.argtypes = [C.c_void_p, fp]
+    lib.icpk_estimate_target_color_gradients.argtypes = [C.c_void_p, C.c_float, C.c_int32, C.c_int32]
+    lib.icpk_get_target_color_gradients.argtypes = [C.c_void_p, fp, fp, fp]
+    lib.icpk_get_color_gradient_sums.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.icpk_set_colored.argtypes = [C.c_void_p, C.c_int32, C.c_float]
+    lib.icpk_reduce_colored.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.icpk_score_poses.argtypes = [C.c_void_p, C.c_int32, fp, C.c_float, C.c_int32, dp, C.POINTER(C.c_int64)]
     lib.icpk_get_score_associations.argtypes = [C.c_void_p, C.c_int32, ip, fp]
     lib.icpk_score_metrics.argtypes = [dp, C.c_int64, C.c_int32, fp, fp, fp]
@@ -385,6 +400,14 @@ def map_voxel(p):
     v = np.zeros(3, np.int32)
     load().icpk_map_voxel(_fp(p), v.ctypes.data_as(C.POINTER(C.c_int32)))
     return v
+
+
+def intensity_from_bgr(bgr):
+    """(..., 3) uint8 BGR -> (n,) float32 intensities (b + g + r) / 765 in [0, 1], as the colour calls take them."""
+    px = np.ascontiguousarray(bgr, np.uint8).reshape(-1, 3)
+    out = np.zeros(len(px), np.float32)
+    load().icpk_intensity_from_bgr(px.ctypes.data_as(C.POINTER(C.c_uint8)), len(px), _fp(out))
+    return out
 
 
 def make_rotation_matrix(x, y, z):
@@ -911,6 +934,59 @@ class Context:
         R = None if R_acc is None else _f(np.asarray(R_acc, np.float32).reshape(9))
         self._chk(self._lib.icpk_reduce_plane_to_plane(self._h, max_dist, None if R is None else _fp(R),
                                                        sums.ctypes.data_as(C.POINTER(C.c_double)), C.byref(cnt)))
+        return sums, cnt.value
+
+    # -- colored ICP (icpk_set_colored; include/icpk.h) ---------------------------------
+    def set_target_colors(self, intensity):
+        """One intensity in [0, 1] per target point ((n,) float32)."""
+        v = _f(intensity).reshape(-1)
+        self._chk(self._lib.icpk_set_target_colors(self._h, _fp(v), v.size))
+
+    def set_source_colors(self, intensity):
+        """One intensity in [0, 1] per point of the uploaded source, in its order; they stay with it until it is
+        replaced."""
+        v = _f(intensity).reshape(-1)
+        self._chk(self._lib.icpk_set_source_colors(self._h, _fp(v), v.size))
+
+    def get_target_colors(self):
+        out = np.empty(self.target_size, np.float32)
+        self._chk(self._lib.icpk_get_target_colors(self._h, _fp(out)))
+        return out
+
+    def get_source_colors(self):
+        out = np.empty(self.source_size, np.float32)
+        self._chk(self._lib.icpk_get_source_colors(self._h, _fp(out)))
+        return out
+
+    def estimate_target_color_gradients(self, radius, min_neighbors=4, keep_sums=False):
+        """Per target point the gradient of the intensity over its tangent plane, fitted to the neighbours within
+        `radius` (needs target normals and colours).  min_neighbors must be at least 1 (E_ARG otherwise); a point with
+        fewer neighbours gets the zero gradient.  Stream-ordered: no host wait."""
+        self._chk(self._lib.icpk_estimate_target_color_gradients(self._h, float(radius), int(min_neighbors),
+                                                                 COLOR_KEEP_SUMS if keep_sums else 0))
+
+    def get_target_color_gradients(self):
+        out = np.empty((3, self.target_size), np.float32)
+        self._chk(self._lib.icpk_get_target_color_gradients(self._h, _fp(out[0]), _fp(out[1]), _fp(out[2])))
+        return out
+
+    def color_gradient_sums(self):
+        """(n, 10) int64 -- m, S_00 S_01 S_02 S_11 S_12 S_22, T_0 T_1 T_2 -- of the last estimate (keep_sums=True)."""
+        out = np.empty((self.target_size, 10), np.int64)
+        self._chk(self._lib.icpk_get_color_gradient_sums(self._h, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
+    def set_colored(self, on=True, lambda_geometric=0.968):
+        """While on, SOLVE_POINT_TO_PLANE alignments run the joint geometric + photometric step; lambda_geometric in
+        [0, 1] weighs the geometric part."""
+        return self._chk(self._lib.icpk_set_colored(self._h, 1 if on else 0, float(lambda_geometric)))
+
+    def reduce_colored(self, max_dist=0.75):
+        """The 28 sums of the joint step over the last sweep's associations and the accepted count."""
+        sums = np.zeros(NP2L, np.float64)
+        cnt = C.c_int64(0)
+        self._chk(self._lib.icpk_reduce_colored(self._h, max_dist, sums.ctypes.data_as(C.POINTER(C.c_double)),
+                                                C.byref(cnt)))
         return sums, cnt.value
 
     # -- pose scoring (icpk_score_poses) -----------------------------------------------

@@ -16,7 +16,8 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_map.cpp", "kernels_map.hip", "icpk_fast.cpp", "kernels_fast.hip", "kernels_map_nn.hip", "kernels_robust.hip",
            "icpk_voxel.cpp", "kernels_voxel.hip", "icpk_normals.cpp", "kernels_normals.hip",
            "icpk_filter.cpp", "kernels_filter.hip", "icpk_gicp.cpp", "kernels_gicp.hip",
-           "icpk_score.cpp", "kernels_score.hip", "icpk_fpfh.cpp", "kernels_fpfh.hip", "icpk_global.cpp"]
+           "icpk_score.cpp", "kernels_score.hip", "icpk_fpfh.cpp", "kernels_fpfh.hip", "icpk_global.cpp",
+           "icpk_color.cpp", "kernels_color.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -205,6 +206,24 @@ def build_gicp_test(force=False):
     return GICP_TEST
 
 
+COLOR_TEST = os.path.join(LIBDIR, "test_color")
+
+
+def build_color_test(force=False):
+    """Host-only C++ program over icp::Engine's colored ICP surface: setTargetColors / setSourceColors /
+    estimateTargetColorGradients / setColored (g++, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_color.cpp")
+    hdr = os.path.join(HERE, "include", "icp_align.hpp")
+    build()
+    newest = max(os.path.getmtime(p) for p in (src, hdr, LIB))
+    if not force and os.path.exists(COLOR_TEST) and os.path.getmtime(COLOR_TEST) >= newest:
+        return COLOR_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", COLOR_TEST])
+    return COLOR_TEST
+
+
 SCORE_TEST = os.path.join(LIBDIR, "test_score")
 
 
@@ -301,6 +320,7 @@ if __name__ == "__main__":
     print(build_normals_test(force="--force" in sys.argv))
     print(build_filter_test(force="--force" in sys.argv))
     print(build_gicp_test(force="--force" in sys.argv))
+    print(build_color_test(force="--force" in sys.argv))
     print(build_score_test(force="--force" in sys.argv))
     print(build_fpfh_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

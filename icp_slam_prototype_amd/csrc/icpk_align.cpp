@@ -239,6 +239,7 @@ int align_device_loop(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk
   const bool prof_all = p->profile >= 2;  // 1: NN kernels only (2 events per sweep); 2: every stage
   const bool p2l = p->solve == ICPK_SOLVE_POINT_TO_PLANE;
   const bool gicp = p->solve == ICPK_SOLVE_PLANE_TO_PLANE;  // (never robust: icpk_align refuses the combination)
+  const bool colored = colored_step(ctx, p);                // (nor this: the joint step in place of K5, K17)
   const bool fused = p->nn_mode == ICPK_NN_PRUNED || p->nn_mode == ICPK_NN_GRID;  // K3 runs inside the sweep
   const bool robust = ctx->robust_on;
   const int nsum = robust ? (p2l ? NP2L_W : NSUM_W) : loop_nsum(p);
@@ -270,6 +271,8 @@ int align_device_loop(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk
     if (prof_all && (r = pf.stamp(&pf.red))) return r;
     if (gicp)  // (R_acc is read from the loop state)
       r = enqueue_reduce_gicp(ctx, p->max_nn_dist, nullptr);
+    else if (colored)
+      r = enqueue_reduce_colored(ctx, p->max_nn_dist);
     else
       r = robust ? enqueue_reduce_robust(ctx, p->max_nn_dist, p2l)
                  : (p2l ? enqueue_reduce_p2l(ctx, p->max_nn_dist) : enqueue_reduce(ctx, p->max_nn_dist));
@@ -353,6 +356,7 @@ int icpk_align_query_sharded(icpk_ctx* ctx, const icpk_params* p, float T_out[16
   if (!p || !T_out) return ICPK_E_ARG;
   if (p->nn_mode == ICPK_NN_MAP) return fail(ctx, ICPK_E_ARG, "ICPK_NN_MAP is single-context only");
   if (p->solve == ICPK_SOLVE_PLANE_TO_PLANE) return fail(ctx, ICPK_E_ARG, "the query-sharded loop has no plane-to-plane flavour");
+  if (colored_step(ctx, p)) return fail(ctx, ICPK_E_ARG, "the query-sharded loop has no colored flavour (icpk_set_colored is on)");
   if (!ctx->comm) return fail(ctx, ICPK_E_NOT_SET, "icpk_comm_init_rccl has not been called");
   if (p->solve != ICPK_SOLVE_REFERENCE && p->solve != ICPK_SOLVE_KABSCH)
     return fail(ctx, ICPK_E_ARG, "the query-sharded loop supports the reference and Kabsch flavours");
@@ -412,6 +416,10 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
   if (gicp && ctx->robust_on) return fail(ctx, ICPK_E_ARG, "plane-to-plane has no robust form (icpk_set_robust is on)");
   if (gicp && (!ctx->have_normals || !ctx->have_src_normals))
     return fail(ctx, ICPK_E_NOT_SET, "plane-to-plane needs source and target normals");
+  const bool colored = colored_step(ctx, p);  // (ICPK_NN_MAP has been refused with point-to-plane above)
+  if (colored && ctx->robust_on) return fail(ctx, ICPK_E_ARG, "colored ICP has no robust form (icpk_set_robust is on)");
+  if (colored && (!ctx->have_src_colors || !ctx->have_tgt_colors || !ctx->have_color_gradients))
+    return fail(ctx, ICPK_E_NOT_SET, "colored ICP needs source colours, target colours and target colour gradients");
   // the bug-for-bug solve has no weighted form
   if (ctx->robust_on && p->solve == ICPK_SOLVE_REFERENCE)
     return fail(ctx, ICPK_E_ARG, "robust alignment needs the Kabsch or point-to-plane flavour");
@@ -448,6 +456,8 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
         for (int a = 0; a < 3; ++a)
           for (int b = 0; b < 3; ++b) Racc[3 * a + b] = (float)Tk[4 * a + b];
         r = enqueue_reduce_gicp(ctx, p->max_nn_dist, Racc);
+      } else if (colored) {
+        r = enqueue_reduce_colored(ctx, p->max_nn_dist);
       } else {
         r = robust ? enqueue_reduce_robust(ctx, p->max_nn_dist, p2l)
                    : (p2l ? enqueue_reduce_p2l(ctx, p->max_nn_dist) : enqueue_reduce(ctx, p->max_nn_dist));

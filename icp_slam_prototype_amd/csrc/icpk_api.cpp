@@ -221,6 +221,10 @@ void target_changed(icpk_ctx* ctx, bool keep_normals) {
   ctx->have_nstats = false;  // (icpk_get_normal_stats speaks of the target it was estimated on)
   ctx->have_score_assoc = false;  // (as icpk_get_score_associations of the target it scored against)
   fpfh_dropped(ctx, 1);           // (and K16's descriptors of the target and its normals)
+  // K17: a target that was only moved keeps its intensities and its (rotated) colour gradients; the integer sums
+  // behind them were taken along the old axes
+  ctx->have_cg_sums = false;
+  if (!keep_normals) ctx->have_tgt_colors = ctx->have_color_gradients = false;
 }
 
 void reset_outputs(float T_out[16], icpk_stats* stats) {
@@ -392,6 +396,11 @@ int icpk_transform_target(icpk_ctx* ctx, const float R[9], const float t[3]) {
     Rt rn = rt;
     rn.t[0] = rn.t[1] = rn.t[2] = 0.f;
     launch_transform(ctx->nrm.x(), ctx->nrm.y(), ctx->nrm.z(), c.n, rn, ctx->stream);
+  }
+  if (ctx->have_color_gradients) {  // as do the colour gradients (K17)
+    Rt rn = rt;
+    rn.t[0] = rn.t[1] = rn.t[2] = 0.f;
+    launch_transform(ctx->cgrad.x(), ctx->cgrad.y(), ctx->cgrad.z(), c.n, rn, ctx->stream);
   }
   ICPK_HIP(ctx, hipGetLastError());
   target_changed(ctx, true);

@@ -374,6 +374,17 @@ struct icpk_ctx {
   icpk::DevBuf<int> sn_count;          // [n]
   icpk::DevBuf<float> sn_curv;         // [n]
   icpk::DevBuf<int> sn_valid;          // 1
+  // colored ICP (K17; icpk_color.cpp): one intensity per point of the target and of the UPLOADED source (caller's
+  // order; dropped with their cloud: target_changed, ensure_cloud), the target's colour gradients (rotated with the
+  // target's normals, dropped with the target or its colours), the ten sums per point behind them and the setting
+  icpk::DevBuf<float> tcol, scol;        // [n]
+  icpk::DevBuf<float> tcol_sorted;       // [n] the target's intensities in cell order (scratch of the estimate)
+  icpk::Cloud cgrad;
+  icpk::DevBuf<long long> cg_sums;       // [n][COLOR_SUMS]
+  bool have_tgt_colors = false, have_src_colors = false, have_color_gradients = false;
+  bool have_cg_sums = false;             // cg_sums describes the target as it stands, and the caller asked to keep it
+  bool colored_on = false;
+  float lambda_geometric = 0.968f;
   // pose scoring (icpk_score_poses, K15; icpk_score.cpp): the poses on their way to the device, the keys of every
   // (pose, point) -- of one chunk of poses, or of the whole call when the associations are kept --, the canonical
   // tree's scratch and the results
@@ -518,6 +529,12 @@ int enqueue_reduce_p2l(icpk_ctx* ctx, float max_dist);
 // plane-to-plane flavour of enqueue_reduce (K14).  R_acc: the rotation accumulated so far (9 floats); inside a device
 // loop the kernel reads it from the loop state and this may be null
 int enqueue_reduce_gicp(icpk_ctx* ctx, float max_dist, const float* R_acc);
+// the joint step of colored ICP in place of enqueue_reduce_p2l (K17), with the context's lambda_geometric
+int enqueue_reduce_colored(icpk_ctx* ctx, float max_dist);
+// icpk_set_colored is on and this alignment is the flavour it applies to
+inline bool colored_step(const icpk_ctx* ctx, const icpk_params* p) {
+  return ctx->colored_on && p->solve == ICPK_SOLVE_POINT_TO_PLANE;
+}
 // robust sweep (K10): room for the selection of nq queries, its histogram cleared (once per alignment / hook call) ...
 int ensure_robust(icpk_ctx* ctx, int nq);
 // ... and the selection + the weighted K2 / K5 over the current associations (NSUM_W / NP2L_W sums; outside a device

@@ -292,6 +292,37 @@ void launch_gicp_reduce(const nn_key_t* best, const float* ax, const float* ay, 
                         int32_t* idx_out, float* dist_out, double* partial, int* pcount, double* out, LoopState* st,
                         hipStream_t s);
 
+// kernels_color.hip -- K17, colored ICP (icpk_estimate_target_color_gradients, icpk_set_colored; the rule is spelled
+// out in include/icpk.h)
+constexpr int COLOR_SUMS = 10;  // per point: m, S_00 S_01 S_02 S_11 S_12 S_22, T_0 T_1 T_2 (int64 each)
+struct ColorGradArgs {
+  const float4* t4;  // the target sorted by cell (x, y, z, original index): K1d's index
+  const int* cell_start;
+  const GridInfo* gi;
+  const float *nx, *ny, *nz;  // target normals, caller's order
+  const float* col;           // target intensities, caller's order
+  float* col_sorted;          // [n] scratch: the intensities in cell order
+  int n;
+  float radius;
+  int min_neighbors;
+  long long* sums;      // [n][COLOR_SUMS], caller's order
+  float *gx, *gy, *gz;  // [n]
+};
+// the three launches of one estimate (gather, sums, solve); n <= 0: nothing
+void launch_color_gradients(const ColorGradArgs& a, hipStream_t s);
+struct ColoredArgs {
+  const float *tnx, *tny, *tnz;  // target normals
+  const float *gx, *gy, *gz;     // target colour gradients
+  const float* tcol;             // target intensities
+  const float* scol;             // source intensities, caller's order (same indexing as the working source)
+  float lambda_geometric;
+};
+// arguments as launch_gicp_reduce's; NP2L sums in the layout solve_p2l reads
+void launch_colored_reduce(const nn_key_t* best, const float* ax, const float* ay, const float* az, int nq,
+                           const float* tx, const float* ty, const float* tz, const ColoredArgs& g, const float4* rec,
+                           float max_dist, int32_t* idx_out, float* dist_out, double* partial, int* pcount, double* out,
+                           LoopState* st, hipStream_t s);
+
 // ---- robust alignment (K10: kernels_robust.hip, the weighted K2 / K5 of kernels_reduce.hip) ----------------------
 // The exact cut tau and median m of one sweep's accepted distances by a radix select over their bit patterns
 // (non-negative floats sort as unsigned integers; the sign bit is cleared, so -0 counts as +0): three passes of

@@ -15,6 +15,7 @@ int ensure_cloud(icpk_ctx* ctx, Cloud& c, int n) {
   if (ctx && &c == &ctx->src) ctx->rec_pending = false;  // (whatever was to be unpacked into it is superseded)
   if (ctx && &c == &ctx->src0) ctx->have_src_normals = false;  // (they describe the uploaded source that is being replaced)
   if (ctx && &c == &ctx->src0) fpfh_dropped(ctx, 0);           // (as K16's descriptors and matches do)
+  if (ctx && &c == &ctx->src0) ctx->have_src_colors = false;   // (as K17's intensities do)
   if (ctx && (&c == &ctx->src0 || &c == &ctx->tgt)) ctx->have_pix_seed = false;  // (other points than the pixel maps describe)
   if (ctx && (&c == &ctx->src0 || &c == &ctx->tgt)) ctx->have_score_assoc = false;  // (K15's kept associations speak of the clouds they were scored on)
   const int cap = round_up(n < 1 ? 1 : n, NN_TILE);
@@ -618,6 +619,20 @@ int enqueue_reduce_gicp(icpk_ctx* ctx, float max_dist, const float* R_acc) {
                      ctx->tgt.z(), g, loop_rec(ctx), max_dist, ctx->st_active ? nullptr : ctx->idx,
                      ctx->st_active ? nullptr : ctx->dist, ctx->partial, ctx->pcount,
                      ctx->st_active ? nullptr : ctx->red_out, ctx->st_active, ctx->stream);
+  return read_back_sums(ctx, NP2L);
+}
+
+int enqueue_reduce_colored(icpk_ctx* ctx, float max_dist) {
+  ColoredArgs g{};
+  g.tnx = ctx->nrm.x(), g.tny = ctx->nrm.y(), g.tnz = ctx->nrm.z();
+  g.gx = ctx->cgrad.x(), g.gy = ctx->cgrad.y(), g.gz = ctx->cgrad.z();
+  g.tcol = ctx->tcol;
+  g.scol = ctx->scol;
+  g.lambda_geometric = ctx->lambda_geometric;
+  launch_colored_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->src.n, ctx->tgt.x(), ctx->tgt.y(),
+                        ctx->tgt.z(), g, loop_rec(ctx), max_dist, ctx->st_active ? nullptr : ctx->idx,
+                        ctx->st_active ? nullptr : ctx->dist, ctx->partial, ctx->pcount,
+                        ctx->st_active ? nullptr : ctx->red_out, ctx->st_active, ctx->stream);
   return read_back_sums(ctx, NP2L);
 }
 

@@ -153,6 +153,18 @@ class Engine {
     return rc;
   }
   int setPlaneToPlane(float epsilon = 1e-3f) { return icpk_set_plane_to_plane(ctx_, epsilon); }
+  // colored ICP (icpk_set_colored): one intensity in [0, 1] per point of the target and of the uploaded source (n = the
+  // cloud's size; they stay with the cloud until it is replaced), the target's colour gradients from its normals and
+  // intensities (no host wait), and the setting: while on, ICPK_SOLVE_POINT_TO_PLANE runs the joint geometric +
+  // photometric step with lambdaGeometric in [0, 1] on the geometric part.  Set the clouds, the target normals, the
+  // colours, estimate the gradients, then icpk_align.  minNeighbors must be at least 1 (ICPK_E_ARG otherwise): a point
+  // with fewer neighbours within the radius gets the zero gradient.
+  int setTargetColors(const float* intensity, int32_t n) { return icpk_set_target_colors(ctx_, intensity, n); }
+  int setSourceColors(const float* intensity, int32_t n) { return icpk_set_source_colors(ctx_, intensity, n); }
+  int estimateTargetColorGradients(float radius, int minNeighbors = 4, int flags = 0) {
+    return icpk_estimate_target_color_gradients(ctx_, radius, minNeighbors, flags);
+  }
+  int setColored(bool on, float lambdaGeometric = 0.968f) { return icpk_set_colored(ctx_, on ? 1 : 0, lambdaGeometric); }
   // pose scoring (icpk_score_poses): n candidate poses (T: 16 floats each, row-major 4x4) of the uploaded source
   // against the target in one call -- fitness, inlier RMSE, mean distance and the information matrix of each; the
   // engine's clouds, associations and seeds stay as they are.  flags: ICPK_SCORE_KEEP_ASSOC.

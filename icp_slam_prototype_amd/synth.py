@@ -219,3 +219,36 @@ def render_room_color(rows, cols, R_wc, c_w, fx=FX, cx=CX, noise_sigma=0.0, rng=
         rng = rng if rng is not None else np.random.default_rng(0)
         img = img + rng.normal(0.0, noise_sigma, img.shape)
     return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+def textured_wall_pair(rows=60, cols=80, relief=0.0, seed=1, jitter=0.002, step=0.01, z=2.0, shift=(0.012, -0.008, 0.004),
+                       rot_z_deg=0.5):
+    """A textured wall for colored ICP: geometry that leaves the in-plane motion free, and a smooth intensity that pins
+    it.  The target is a rows x cols lattice (`step` metres) at depth z, every point moved in the plane by up to
+    +-jitter (uniform, from `seed`); the source samples the same wall on the lattice offset by half a step, with a
+    jitter of its own, seen from a camera that has moved: source = T_true^-1 (wall points).  relief: amplitude (metres)
+    of a smooth height field z += relief * (sin(2 pi x / 0.4) + cos(2 pi y / 0.3)) / 2 -- 0 is an exact plane.
+    Intensity of a wall point: 0.5 + 0.25 sin(2 pi x / 0.2) + 0.2 cos(2 pi y / 0.15), in [0.05, 0.95].
+    T_true: rot_z_deg about the wall's centre, then `shift`; aligning source onto target should return it.
+    Returns dict(source, target (3, n) float32, source_intensity, target_intensity (n,) float32, T_true (4, 4) float64)."""
+    rng = np.random.default_rng(seed)
+    v, u = np.mgrid[0:rows, 0:cols].astype(np.float64)
+
+    def wall(offset):
+        x = (u.ravel() + offset) * step + rng.uniform(-jitter, jitter, rows * cols)
+        y = (v.ravel() + offset) * step + rng.uniform(-jitter, jitter, rows * cols)
+        zz = z + relief * 0.5 * (np.sin(2 * np.pi * x / 0.4) + np.cos(2 * np.pi * y / 0.3))
+        inten = 0.5 + 0.25 * np.sin(2 * np.pi * x / 0.2) + 0.2 * np.cos(2 * np.pi * y / 0.15)
+        return np.stack([x, y, zz]), inten
+
+    tgt, it = wall(0.0)
+    ws, is_ = wall(0.5)
+    a = np.deg2rad(rot_z_deg)
+    R = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
+    c = np.array([0.5 * (cols - 1) * step, 0.5 * (rows - 1) * step, z])
+    T = np.eye(4)
+    T[:3, :3] = R
+    T[:3, 3] = c - R @ c + np.asarray(shift, np.float64)
+    src = R.T @ (ws - T[:3, 3:4])
+    return dict(source=src.astype(np.float32), target=tgt.astype(np.float32), source_intensity=is_.astype(np.float32),
+                target_intensity=it.astype(np.float32), T_true=T)

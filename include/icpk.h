@@ -14,7 +14,9 @@
  *
  * Data layout: point clouds are xyz structure-of-arrays (three float planes),
  * replacing the reference's 16-byte AoS color_point_t (pointcloud.hpp:13-19);
- * colour is dropped because COLOR_WEIGHT is 0.0f (icp.hpp:6).  Coordinates are
+ * colour is dropped from the pair distance because COLOR_WEIGHT is 0.0f
+ * (icp.hpp:6); colored ICP (K17) takes one intensity per point in arrays of its
+ * own.  Coordinates are
  * expected to be finite (the reference produces them from uint16 depth): a NaN/inf
  * point never faults or hangs a kernel and never pairs, but which index it reports
  * is unspecified.
@@ -848,6 +850,95 @@ int icpk_set_plane_to_plane(icpk_ctx *ctx, float epsilon);
 /* test hook: the 28 sums of the rule above and the accepted count over the associations of the last icpk_nn (as
  * icpk_reduce_p2l), with the context's epsilon and the given R_acc (row-major; NULL: the identity) */
 int icpk_reduce_plane_to_plane(icpk_ctx *ctx, float max_dist, const float R_acc[9], double sums[28], int64_t *count);
+
+/* ---- colored ICP (K17; extension: the estimator of Park, Zhou and Koltun, "Colored Point Cloud Registration
+ * Revisited", ICCV 2017, as Open3D's registration_colored_icp offers it) ----
+ * Geometry alone leaves a wall, a floor or a table top free to slide in its plane, and on an exact plane the 6x6 of
+ * ICPK_SOLVE_POINT_TO_PLANE is singular (ICPK_W_DEGENERATE at the first step).  A depth camera comes with a colour
+ * frame; this setting of the point-to-plane flavour keeps its residual and adds a photometric one along the target's
+ * tangent plane.  It needs one intensity per point of both clouds and one intensity gradient per target point.
+ *
+ * Intensities.  One float in [0, 1] per point; icpk_intensity_from_bgr makes them from n BGR triples as
+ * (float)(((double)b + (double)g + (double)r) / 765.0) (host helper, no device work).
+ *   icpk_set_target_colors / icpk_set_source_colors   n must equal the cloud's size, every value must be finite and in
+ *       [0, 1] (a host scan before the upload; the bound is what keeps the integer sums below from overflowing), else
+ *       ICPK_E_ARG and nothing changes; ICPK_E_NOT_SET without that cloud.  Setting the target's drops its gradients.
+ *   icpk_get_target_colors / icpk_get_source_colors   to a host array of icpk_target_size / icpk_source_size entries;
+ *       ICPK_E_NOT_SET when the cloud has none.
+ *   lifetime   the source's belong to the UPLOADED source in the caller's order, as K14's source normals do.  An
+ *       intensity does not depend on the pose: both clouds' survive icpk_transform_*, icpk_reset_source,
+ *       icpk_commit_source and the loop.  Every call that replaces or re-indexes a cloud drops that cloud's
+ *       intensities, and for the target its gradients too: icpk_set_source* / icpk_set_target*, icpk_backproject* and
+ *       icpk_detected_to_cloud into that cloud, icpk_backproject_pair (both), icpk_voxel_downsample /
+ *       icpk_remove_outliers on it (unless STATS_ONLY), icpk_map_list_to_target, icpk_map_lookup_to_target and
+ *       icpk_comm_broadcast_target on every rank but the root (the root's target is not replaced: it keeps its
+ *       intensities, gradients and kept sums).  They are not carried through thinning: gather them on the host by
+ *       icpk_get_voxel_groups' first_index or icpk_get_outlier_stats' out_index and set them again.
+ *
+ * Gradients.  icpk_estimate_target_color_gradients fits, per target point, the intensity of its neighbours as a linear
+ * function over its tangent plane.  It needs a target, target normals and target intensities (else ICPK_E_NOT_SET);
+ * ICPK_E_ARG for a radius that is not finite and > 0, min_neighbors < 1 or an unknown flag (nothing changes).
+ * Stream-ordered, no host wait; it walks the uniform grid ICPK_NN_GRID indexes the target with and builds it if the
+ * target has none yet.  The rule for target point i with normal n (floats widened), r = radius, F = 2^15:
+ *   usable normal  nn = (n_0 n_0 + n_1 n_1) + n_2 n_2 in float64 lies in [1 - 2^-10, 1 + 2^-10] (false for NaN): the
+ *                  zero normal and a grossly non-unit host normal are not usable.
+ *   neighbourhood  K12's, word for word: every j with d(i, j) <= r, d the pair distance of icp.cpp:606-620, `<=` a float
+ *                  compare, i itself and duplicates included, a non-finite point in none and with none.  m = its size.
+ *   per neighbour  (only with a usable normal) float64, one rounded operation per symbol, none fused:
+ *                    e_a = (double)p_j,a - (double)p_i,a;   h = (e_0 n_0 + e_1 n_1) + e_2 n_2;   u_a = e_a - h n_a
+ *                    q_a = (int64)rint((u_a / r) F);        c = (int64)rint(((double)I_j - (double)I_i) F)
+ *   sums           int64: S_ab = sum q_a q_b (a <= b), T_a = sum q_a c; all zero without a usable normal.  With m that is
+ *                  ten words per point: m, S_00 S_01 S_02 S_11 S_12 S_22, T_0 T_1 T_2.  |u| <= |e| for a usable normal,
+ *                  so |q| <= 2^15 + 2^7 with room to spare, |c| <= 2^15 because the intensities lie in [0, 1], and
+ *                  m < 2^31: every sum stays below 2^62.  Integers: the same bits on every run and for every order of
+ *                  the cloud.
+ *   solve          float64: w = (double)m F, w2 = w w, H_ab = (double)S_ab + (w2 n_a) n_b -- the reference method's extra
+ *                  row that pins the component along the normal to zero --; the adjugate K of H and det exactly as K14
+ *                  writes them for S (K_00 = H_11 H_22 - H_12 H_12, ..., det = (H_00 K_00 + H_01 K_01) + H_02 K_02),
+ *                  inv = 1.0 / det, g'_a = ((K_a0 T_0 + K_a1 T_1) + K_a2 T_2) inv, gradient_a = (float)(g'_a / r):
+ *                  intensity per metre.
+ *   no gradient    (0, 0, 0) when m < min_neighbors, without a usable normal, when det is not finite or <= 0, or when
+ *                  a component of the result is not finite.  A zero gradient removes the photometric term of a pair,
+ *                  not the pair.
+ * icpk_get_target_color_gradients returns them; with the flag ICPK_COLOR_KEEP_SUMS icpk_get_color_gradient_sums returns
+ * the ten words per point (10 * n int64; ICPK_E_NOT_SET without the flag, or once the target has changed or moved).
+ * icpk_transform_target rotates the gradients as it rotates the normals.  They are those of the normals and
+ * intensities they were estimated with: setting the intensities again drops them, changing the normals does not --
+ * estimate again.
+ *
+ * The joint step.  icpk_set_colored(on, lambda_geometric): off by default, lambda_geometric 0.968 (Open3D's value) by
+ * default; it must be finite and in [0, 1], else ICPK_E_ARG and the setting stays.  While it is on,
+ * ICPK_SOLVE_POINT_TO_PLANE in icpk_align runs the joint step; the other flavours ignore the setting.  Per sweep and
+ * pair (i = working source point p, j = its nearest target q with normal n, gradient g and intensity I_t, I_s the
+ * intensity of source point i, d the NN distance), float64, unfused, lg = (double)lambda_geometric, lc = 1.0 - lg:
+ *   accepted   exactly when point-to-plane accepts the pair: d < max_nn_dist and n != (0, 0, 0)
+ *   geometric  e_a = p_a - q_a;  h = (e_0 n_0 + e_1 n_1) + e_2 n_2;  G = [p x n | n]  (p x n = (p_1 n_2 - p_2 n_1,
+ *              p_2 n_0 - p_0 n_2, p_0 n_1 - p_1 n_0)): K5's operations and signs
+ *   photometric u_a = e_a - h n_a;  rc = (I_t + ((g_0 u_0 + g_1 u_1) + g_2 u_2)) - I_s;
+ *              gn = (g_0 n_0 + g_1 n_1) + g_2 n_2;  M_a = g_a - gn n_a;  C = [p x M | M]
+ *   sums       ICPK_NP2L's layout through the canonical tree: [0..20] += lg (G_a G_b) + lc (C_a C_b) (a <= b, row-major),
+ *              [21..26] += lg (G_a h) + lc (C_a rc), [27] += (double)d
+ *   solve      icpk_solve_point_to_plane's; the loop, the trace, min_pairs, ICPK_W_DEGENERATE and final_mse are the
+ *              point-to-plane path's, unchanged.
+ * lambda_geometric = 1 gives the sums of icpk_reduce_p2l bit for bit.
+ * Where it applies: icpk_align with ICPK_NN_EXACT / FILTERED / PRUNED / GRID and host_loop 0 and 1 -- every combination
+ * returns the same bits.  While the setting is on and solve is ICPK_SOLVE_POINT_TO_PLANE: ICPK_E_NOT_SET without source
+ * intensities, target intensities, target normals or gradients; ICPK_E_ARG with ICPK_NN_MAP and while icpk_set_robust
+ * is on.  icpk_align_query_sharded and icpk_align_to_map* refuse point-to-plane as they always did; the batch paths
+ * carry no colours and ignore the setting. */
+#define ICPK_COLOR_KEEP_SUMS 1 /* flags: keep the 10 int64 per point for icpk_get_color_gradient_sums */
+void icpk_intensity_from_bgr(const uint8_t *bgr, int32_t n, float *out);
+int icpk_set_target_colors(icpk_ctx *ctx, const float *intensity, int32_t n);
+int icpk_set_source_colors(icpk_ctx *ctx, const float *intensity, int32_t n);
+int icpk_get_target_colors(icpk_ctx *ctx, float *intensity);
+int icpk_get_source_colors(icpk_ctx *ctx, float *intensity);
+int icpk_estimate_target_color_gradients(icpk_ctx *ctx, float radius, int32_t min_neighbors, int32_t flags);
+int icpk_get_target_color_gradients(icpk_ctx *ctx, float *gx, float *gy, float *gz);
+int icpk_get_color_gradient_sums(icpk_ctx *ctx, int64_t *sums);
+int icpk_set_colored(icpk_ctx *ctx, int32_t on, float lambda_geometric);
+/* test hook: the 28 sums of the joint step and the accepted count over the associations of the last icpk_nn (as
+ * icpk_reduce_p2l), with the context's lambda_geometric (whether or not the setting is on) */
+int icpk_reduce_colored(icpk_ctx *ctx, float max_dist, double sums[28], int64_t *count);
 
 /* ---- pose scoring (K15; extension: what Open3D's evaluate_registration / GetInformationMatrixFromPointClouds and PCL's
  * getFitnessScore answer) ----

@@ -1,0 +1,110 @@
+"""Colored ICP's lifetime rule for icpk_comm_broadcast_target (include/icpk.h, K17) with TWO ranks on one GPU, the
+collectives from tests/cpp/fake_rccl.cpp as in tests/test_gpu_comm_two_ranks.py: the non-root rank's target is replaced,
+so its intensities, gradients and kept sums are dropped and its source's intensities stay; the root's target is not
+replaced, so it keeps all of them."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RADIUS, MIN_NB = 0.035, 4
+
+
+def _wall(rank):
+    """every rank starts with a target of its own (rank 1's is larger, so its buffers are stale after the broadcast)"""
+    from icp_slam_prototype_amd import synth
+
+    p = synth.textured_wall_pair(rows=20 + 6 * rank, cols=30 + 6 * rank, relief=0.003, seed=3 + rank)
+    p["target_normals"] = np.tile(np.float32([[0], [0], [-1]]), (1, p["target"].shape[1]))
+    return p
+
+
+def _code(fn, *a, **kw):
+    from icp_slam_prototype_amd import binding
+
+    try:
+        r = fn(*a, **kw)
+    except binding.IcpkError as e:
+        return e.code
+    return r[2] if isinstance(r, tuple) and len(r) == 3 else 0
+
+
+def _worker(rank, world, fake, q_id, q_out):
+    sys.path.insert(0, ROOT)
+    os.environ["ICPK_TEST_HOOKS"] = "1"  # the switch without which icpk_comm_* ignores ICPK_RCCL_LIB
+    os.environ["ICPK_RCCL_LIB"] = fake
+    from icp_slam_prototype_amd import batch, binding
+
+    def exchange(uid):
+        if rank == 0:
+            for _ in range(world - 1):
+                q_id.put(uid)
+            return uid
+        return q_id.get(timeout=120)
+
+    ctx = binding.Context(0)
+    comm = batch.RcclComm(ctx, rank, world, exchange)
+    p = _wall(rank)
+    ctx.set_target(p["target"])
+    ctx.set_target_normals(p["target_normals"])
+    ctx.set_target_colors(p["target_intensity"])
+    ctx.estimate_target_color_gradients(RADIUS, MIN_NB, keep_sums=True)
+    ctx.set_source(p["source"])
+    ctx.set_source_colors(p["source_intensity"])
+    ctx.set_colored(True)
+    kw = dict(solve=binding.SOLVE_POINT_TO_PLANE, max_iterations=2, fixed_iterations=1)
+    res = {"before": (ctx.get_target_color_gradients(), ctx.color_gradient_sums(), _code(ctx.align, **kw))}
+    comm.broadcast_target(0)
+    res["target"] = ctx.get_target()
+    res["source_colors"] = ctx.get_source_colors()
+    res["codes"] = (_code(ctx.get_target_colors), _code(ctx.get_target_color_gradients), _code(ctx.color_gradient_sums),
+                    _code(ctx.align, **kw))
+    if rank == 0:
+        res["after"] = (ctx.get_target_colors(), ctx.get_target_color_gradients(), ctx.color_gradient_sums())
+    else:  # the broadcast target takes the root's colours like any new target
+        root = _wall(0)
+        ctx.set_target_normals(root["target_normals"])
+        ctx.set_target_colors(root["target_intensity"])
+        ctx.estimate_target_color_gradients(RADIUS, MIN_NB, keep_sums=True)
+        res["after"] = (ctx.get_target_colors(), ctx.get_target_color_gradients(), ctx.color_gradient_sums())
+    comm.barrier()
+    comm.close()
+    ctx.close()
+    q_out.put((rank, res))
+
+
+def test_broadcast_target_drops_the_colours_of_the_ranks_that_receive():
+    import multiprocessing as mp
+
+    from icp_slam_prototype_amd import binding, build
+
+    build.build()
+    fake = build.build_fake_rccl()
+    mpc = mp.get_context("spawn")
+    q_id, q_out = mpc.Queue(), mpc.Queue()
+    procs = [mpc.Process(target=_worker, args=(r, 2, fake, q_id, q_out)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = dict(q_out.get(timeout=300) for _ in procs)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    walls = [_wall(0), _wall(1)]
+    for r in (0, 1):
+        assert got[r]["before"][2] == 0 and got[r]["before"][0].any(), r
+        assert np.array_equal(got[r]["target"], walls[0]["target"]), r
+        assert got[r]["source_colors"].tobytes() == walls[r]["source_intensity"].tobytes(), r  # (the source's stay)
+    # the root: nothing of its target was replaced
+    g0, S0, _ = got[0]["before"]
+    assert got[0]["codes"] == (0, 0, 0, 0)
+    tc, g, S = got[0]["after"]
+    assert tc.tobytes() == walls[0]["target_intensity"].tobytes() and g.tobytes() == g0.tobytes() and np.array_equal(S, S0)
+    # the rank that received: colours, gradients and sums are gone, and the colored step says so
+    E = binding.E_NOT_SET
+    assert got[1]["codes"] == (E, E, E, E)
+    # ... and the new target takes colours as any other: the root's, and then the root's gradients and sums
+    tc, g, S = got[1]["after"]
+    assert tc.tobytes() == walls[0]["target_intensity"].tobytes() and g.tobytes() == g0.tobytes() and np.array_equal(S, S0)
