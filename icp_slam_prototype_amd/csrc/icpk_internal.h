@@ -245,16 +245,25 @@ void launch_reduce_final_shard(const double* partial, const int* pcount, int nbl
                                hipStream_t s);
 
 // kernels_reduce.hip
-// partial: [NSUM_MAX][RED_MAX_BLOCKS] doubles (sum-major: stage 2 reads it coalesced), pcount: [RED_MAX_BLOCKS] ints,
-// out: nsum doubles followed by one int64 count ((NSUM_MAX + 1) x 8 bytes).
-// out == nullptr: only the per-block partials are produced (the device loop sums them
-// in launch_loop_step); stop: device-loop stop flags or nullptr
-// o4: the target as caller-order (x, y, z, 0) points or nullptr (then tx / ty / tz are gathered)
-// rec != nullptr (device loop behind a grid sweep): everything comes from the sweep's caller-order records instead
-void launch_assoc_reduce(const nn_key_t* best, const float* ax, const float* ay, const float* az, int nq,
-                         const float* tx, const float* ty, const float* tz, const float4* o4, const float4* rec, float max_dist,
-                         int32_t* idx_out, float* dist_out, double* partial, int* pcount, double* out, LoopState* st,
-                         int nact, hipStream_t s, const RobustSel* sel = nullptr);  // sel: the weighted K2 (NSUM_W sums)
+// What every reduction over one sweep's pairs takes (K2, K5, K14, K17; the device side is pair_reduce.h).
+struct PairArgs {
+  const nn_key_t* best;        // the sweep's (distance bits, index) keys, caller's order
+  const float *ax, *ay, *az;   // the moved source
+  const float *tx, *ty, *tz;   // the target
+  const float4* o4;            // the target as caller-order (x, y, z, 0) points or nullptr (then tx / ty / tz are gathered)
+  const float4* rec;           // != nullptr (device loop behind a grid sweep): everything comes from the sweep's caller-order records instead
+  int nq;
+  float max_dist;
+  int32_t* idx_out;            // the keys unpacked, or nullptr (both)
+  float* dist_out;
+  double* partial;             // [NSUM_MAX][RED_MAX_BLOCKS] doubles (sum-major: stage 2 reads it coalesced)
+  int* pcount;                 // [RED_MAX_BLOCKS] ints
+  double* out;                 // nsum doubles followed by one int64 count ((NSUM_MAX + 1) x 8 bytes); nullptr: only the
+                               // per-block partials are produced (the device loop sums them in launch_loop_step)
+  LoopState* st;               // the device loop's state or nullptr
+};
+// nact: NSUM, or NSUM_REF inside a device loop of the reference flavour; sel: the weighted K2 (NSUM_W sums)
+void launch_assoc_reduce(const PairArgs& a, int nact, hipStream_t s, const RobustSel* sel = nullptr);
 // one pair's arguments of K2 inside a device loop (no idx/dist unpacking, no final stage)
 struct ReduceArgs {
   const nn_key_t* best;
@@ -273,10 +282,9 @@ struct ReduceBatch {
 };
 void launch_assoc_reduce_batch(const ReduceBatch& b, int count, float max_dist, int nact, hipStream_t s);
 
-void launch_p2l_reduce(const nn_key_t* best, const float* ax, const float* ay, const float* az, int nq, const float* tx,
-                       const float* ty, const float* tz, const float* nx, const float* ny, const float* nz,
-                       const float4* rec, float max_dist, int32_t* idx_out, float* dist_out, double* partial, int* pcount,
-                       double* out, LoopState* st, hipStream_t s, const RobustSel* sel = nullptr);
+// K5: nx / ny / nz the target's normals; sel: the weighted K5 (NP2L_W sums)
+void launch_p2l_reduce(const PairArgs& a, const float* nx, const float* ny, const float* nz, hipStream_t s,
+                       const RobustSel* sel = nullptr);
 
 // kernels_gicp.hip -- K14, the plane-to-plane (generalized ICP) step (ICPK_SOLVE_PLANE_TO_PLANE; the rule is spelled
 // out in include/icpk.h).  NP2L sums in the layout solve_p2l reads.
@@ -286,11 +294,7 @@ struct GicpArgs {
   float R[9];                    // R_acc when st == nullptr (a device loop reads LoopState::Tk instead)
   float epsilon;
 };
-// arguments as launch_p2l_reduce's; rec != nullptr: the caller-order records of a device loop's grid sweep
-void launch_gicp_reduce(const nn_key_t* best, const float* ax, const float* ay, const float* az, int nq, const float* tx,
-                        const float* ty, const float* tz, const GicpArgs& g, const float4* rec, float max_dist,
-                        int32_t* idx_out, float* dist_out, double* partial, int* pcount, double* out, LoopState* st,
-                        hipStream_t s);
+void launch_gicp_reduce(const PairArgs& a, const GicpArgs& g, hipStream_t s);
 
 // kernels_color.hip -- K17, colored ICP (icpk_estimate_target_color_gradients, icpk_set_colored; the rule is spelled
 // out in include/icpk.h)
@@ -317,11 +321,8 @@ struct ColoredArgs {
   const float* scol;             // source intensities, caller's order (same indexing as the working source)
   float lambda_geometric;
 };
-// arguments as launch_gicp_reduce's; NP2L sums in the layout solve_p2l reads
-void launch_colored_reduce(const nn_key_t* best, const float* ax, const float* ay, const float* az, int nq,
-                           const float* tx, const float* ty, const float* tz, const ColoredArgs& g, const float4* rec,
-                           float max_dist, int32_t* idx_out, float* dist_out, double* partial, int* pcount, double* out,
-                           LoopState* st, hipStream_t s);
+// NP2L sums in the layout solve_p2l reads
+void launch_colored_reduce(const PairArgs& a, const ColoredArgs& g, hipStream_t s);
 
 // ---- robust alignment (K10: kernels_robust.hip, the weighted K2 / K5 of kernels_reduce.hip) ----------------------
 // The exact cut tau and median m of one sweep's accepted distances by a radix select over their bit patterns

@@ -590,22 +590,36 @@ static int read_back_sums(icpk_ctx* ctx, int nsum) {
   return ICPK_OK;
 }
 
+// what every reduction takes from the context; inside a device loop nothing is unpacked and no final stage runs (the
+// loop step sums the partials)
+static PairArgs reduce_args(icpk_ctx* ctx, float max_dist) {
+  const bool loop = ctx->st_active;
+  PairArgs a{};
+  a.best = ctx->best;
+  a.ax = ctx->src.x(), a.ay = ctx->src.y(), a.az = ctx->src.z();
+  a.tx = ctx->tgt.x(), a.ty = ctx->tgt.y(), a.tz = ctx->tgt.z();
+  a.o4 = ctx->have_grid ? ctx->o4.get() : nullptr;
+  a.rec = loop_rec(ctx);
+  a.nq = ctx->src.n;
+  a.max_dist = max_dist;
+  a.idx_out = loop ? nullptr : ctx->idx.get();
+  a.dist_out = loop ? nullptr : ctx->dist.get();
+  a.partial = ctx->partial;
+  a.pcount = ctx->pcount;
+  a.out = loop ? nullptr : ctx->red_out.get();
+  a.st = ctx->st_active;
+  return a;
+}
+
 // enqueue K2 and the 160-byte read-back; caller synchronises
 int enqueue_reduce(icpk_ctx* ctx, float max_dist) {
-  const int nq = ctx->src.n;
-  launch_assoc_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), nq, ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(),
-                      ctx->have_grid ? ctx->o4 : nullptr, loop_rec(ctx), max_dist, ctx->st_active ? nullptr : ctx->idx, ctx->st_active ? nullptr : ctx->dist, ctx->partial,
-                      ctx->pcount, ctx->st_active ? nullptr : ctx->red_out,
-                      ctx->st_active, ctx->st_active ? ctx->loop_nact : NSUM, ctx->stream);
+  launch_assoc_reduce(reduce_args(ctx, max_dist), ctx->st_active ? ctx->loop_nact : NSUM, ctx->stream);
   return read_back_sums(ctx, NSUM);
 }
 
 // point-to-plane flavour of enqueue_reduce (K5)
 int enqueue_reduce_p2l(icpk_ctx* ctx, float max_dist) {
-  launch_p2l_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->src.n, ctx->tgt.x(), ctx->tgt.y(),
-                    ctx->tgt.z(), ctx->nrm.x(), ctx->nrm.y(), ctx->nrm.z(), loop_rec(ctx), max_dist, ctx->st_active ? nullptr : ctx->idx,
-                    ctx->st_active ? nullptr : ctx->dist, ctx->partial,
-                    ctx->pcount, ctx->st_active ? nullptr : ctx->red_out, ctx->st_active, ctx->stream);
+  launch_p2l_reduce(reduce_args(ctx, max_dist), ctx->nrm.x(), ctx->nrm.y(), ctx->nrm.z(), ctx->stream);
   return read_back_sums(ctx, NP2L);
 }
 
@@ -615,10 +629,7 @@ int enqueue_reduce_gicp(icpk_ctx* ctx, float max_dist, const float* R_acc) {
   g.tnx = ctx->nrm.x(), g.tny = ctx->nrm.y(), g.tnz = ctx->nrm.z();
   for (int k = 0; k < 9; ++k) g.R[k] = R_acc ? R_acc[k] : (k % 4 == 0 ? 1.f : 0.f);
   g.epsilon = ctx->gicp_epsilon;
-  launch_gicp_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->src.n, ctx->tgt.x(), ctx->tgt.y(),
-                     ctx->tgt.z(), g, loop_rec(ctx), max_dist, ctx->st_active ? nullptr : ctx->idx,
-                     ctx->st_active ? nullptr : ctx->dist, ctx->partial, ctx->pcount,
-                     ctx->st_active ? nullptr : ctx->red_out, ctx->st_active, ctx->stream);
+  launch_gicp_reduce(reduce_args(ctx, max_dist), g, ctx->stream);
   return read_back_sums(ctx, NP2L);
 }
 
@@ -629,10 +640,7 @@ int enqueue_reduce_colored(icpk_ctx* ctx, float max_dist) {
   g.tcol = ctx->tcol;
   g.scol = ctx->scol;
   g.lambda_geometric = ctx->lambda_geometric;
-  launch_colored_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->src.n, ctx->tgt.x(), ctx->tgt.y(),
-                        ctx->tgt.z(), g, loop_rec(ctx), max_dist, ctx->st_active ? nullptr : ctx->idx,
-                        ctx->st_active ? nullptr : ctx->dist, ctx->partial, ctx->pcount,
-                        ctx->st_active ? nullptr : ctx->red_out, ctx->st_active, ctx->stream);
+  launch_colored_reduce(reduce_args(ctx, max_dist), g, ctx->stream);
   return read_back_sums(ctx, NP2L);
 }
 
@@ -660,17 +668,11 @@ int enqueue_reduce_robust(icpk_ctx* ctx, float max_dist, bool p2l) {
   const float4* rec = loop_rec(ctx);
   launch_robust_select(ctx->best, rec, nq, max_dist, p2l ? ctx->nrm.x() : nullptr, p2l ? ctx->nrm.y() : nullptr,
                        p2l ? ctx->nrm.z() : nullptr, ctx->rdsel, ctx->rhist, ctx->rsel, cfg, ctx->st_active, ctx->stream);
-  int32_t* idx_out = ctx->st_active ? nullptr : ctx->idx.get();
-  float* dist_out = ctx->st_active ? nullptr : ctx->dist.get();
-  double* out = ctx->st_active ? nullptr : ctx->red_out.get();
+  const PairArgs a = reduce_args(ctx, max_dist);
   if (p2l)
-    launch_p2l_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), nq, ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(),
-                      ctx->nrm.x(), ctx->nrm.y(), ctx->nrm.z(), rec, max_dist, idx_out, dist_out, ctx->partial,
-                      ctx->pcount, out, ctx->st_active, ctx->stream, ctx->rsel);
+    launch_p2l_reduce(a, ctx->nrm.x(), ctx->nrm.y(), ctx->nrm.z(), ctx->stream, ctx->rsel);
   else
-    launch_assoc_reduce(ctx->best, ctx->src.x(), ctx->src.y(), ctx->src.z(), nq, ctx->tgt.x(), ctx->tgt.y(),
-                        ctx->tgt.z(), ctx->have_grid ? ctx->o4 : nullptr, rec, max_dist, idx_out, dist_out, ctx->partial,
-                        ctx->pcount, out, ctx->st_active, NSUM_W, ctx->stream, ctx->rsel);
+    launch_assoc_reduce(a, NSUM_W, ctx->stream, ctx->rsel);
   const int rc = read_back_sums(ctx, p2l ? NP2L_W : NSUM_W);
   if (rc || ctx->st_active) return rc;
   ICPK_HIP(ctx, hipMemcpyAsync(ctx->rsel_host, ctx->rsel, sizeof(RobustSel), hipMemcpyDeviceToHost, ctx->stream));

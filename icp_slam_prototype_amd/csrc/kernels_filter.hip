@@ -11,8 +11,9 @@
 //      filter_emit_kernel    n_out; then the kept points (and normals) go to their rank in input order
 // Nothing here is an atomic on a float and no sum depends on the order in which candidates arrive: a point's k smallest
 // distances are selected as 64-bit (distance bits, index) keys, which are all different, and added in ascending order.
+#include "grid_walk.h"
 #include "icpk_internal.h"
-#include "nn_device.h"
+#include "pair_reduce.h"
 
 namespace icpk {
 
@@ -23,27 +24,22 @@ constexpr int KNN_BLOCK = 64;  // one wave per workgroup: its lists are KNN_BLOC
 constexpr int KNN_UNROLL = 4;  // candidates per lane and round trip
 constexpr int KNN_MAX_ROUNDS = 256;  // (a guard: doubling any float radius reaches +inf, hence the whole grid, sooner)
 
-// (x - x is 0 for a finite x and NaN otherwise)
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return ((x - x) + (y - y)) + (z - z) == 0.f; }
-
 // The exact k nearest neighbours of a query over the uniform grid.
 //
-// Exactness.  After the rows of cube_cells(q, R) on all three axes have been scanned, every indexed point with
-// pair_dist <= R has been seen (the superset proof in front of K1d's sweep in kernels_grid.hip; cube_cells is the same
-// function).  So if at least k of the points seen (the query's own index left out) have d <= R, the k smallest keys
+// Exactness.  After the cube of radius R has been walked, every indexed point with pair_dist <= R has been seen
+// (grid_walk.h).  So if at least k of the points seen (the query's own index left out) have d <= R, the k smallest keys
 // among THOSE are the k smallest of the whole cloud: every point not seen, and every point seen with d > R, is further
 // than all of them.  Otherwise R doubles and the scan starts again; when the cube is the whole grid on all three axes
 // every point of the cloud has been seen and whatever was found is final -- with fewer than k other finite points,
 // all of them (k' = min(k, N - 1)).  A key is (distance bits << 32) | index: distances are non-negative floats, so the
 // bit pattern orders like the value, and the index makes every key different, so "the k smallest keys" is one set.
 //
-// Shape.  Queries are taken in cell order, KNN_S adjacent lanes per query, so that the lanes of a wave read the same
-// few rows of cells; a query's lanes deal its (y, z) rows among themselves, every row one contiguous range of the
-// sorted copy.  Each lane keeps the k smallest keys it has met in its own column of an LDS array (unsorted, with the
-// largest remembered: a candidate is compared with one register, and only a candidate that enters costs a walk of the
-// column).  At the end a key's rank among the keys of the query's KNN_S columns is counted directly -- the keys are
-// different, so the ranks are a permutation -- and the k smallest distances go to their places in a second LDS array,
-// from where one lane adds them in ascending order.
+// Shape.  Queries are taken in cell order, KNN_S adjacent lanes per query (the walk of grid_walk.h).  Each lane keeps
+// the k smallest keys it has met in its own column of an LDS array (unsorted, with the largest remembered: a
+// candidate is compared with one register, and only a candidate that enters costs a walk of the column).  At the end
+// a key's rank among the keys of the query's KNN_S columns is counted directly -- the keys are different, so the ranks
+// are a permutation -- and the k smallest distances go to their places in a second LDS array, from where one lane
+// adds them in ascending order.
 // The first radius is taken from the cell edge h and k: the grid is sized for `ppc` points per h x h of surface, so a
 // ball of radius R holds about pi R^2 ppc / h^2 of them; r0_scale = 2.5 / (pi ppc) aims at 2.5 (k + 1).
 template <int KCAP>
@@ -66,34 +62,22 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_mean_kernel(const KnnArgs a) {
   bool active = scan;
   int cnt = 0;  // keys in this lane's column
   for (int round = 0; round < KNN_MAX_ROUNDS && __builtin_amdgcn_ballot_w64(active) != 0; ++round) {
-    int x0, x1, y0, y1, z0, z1;
-    cube_cells(px, R, g.lo[0], g.inv_hx, g.nx, x0, x1);
-    cube_cells(py, R, g.lo[1], g.inv_h, g.ny, y0, y1);
-    cube_cells(pz, R, g.lo[2], g.inv_h, g.nz, z0, z1);
-    const bool whole = x0 == 0 && x1 == g.nx - 1 && y0 == 0 && y1 == g.ny - 1 && z0 == 0 && z1 == g.nz - 1;
-    const int nyr = y1 - y0 + 1;
-    const int nrows = active ? nyr * (z1 - z0 + 1) : 0;  // <= 1024 x 1024 (grid_info_body)
+    const Walk walk = make_walk(g, px, py, pz, R, active);
+    const bool whole = walk.whole(g);
     int within = 0;  // candidates with d <= R met by this lane
     nn_key_t cur_max = 0;
     int max_at = 0;
     if (active) cnt = 0;
-    for (int row = slice; row < nrows; row += KNN_S) {
-      const int rz = row / nyr, ry = row - rz * nyr;
-      const int base = ((z0 + rz) * g.ny + (y0 + ry)) * g.nx;  // cells base + x0 .. base + x1 < ncells, one range
-      const int s0 = a.cell_start[base + x0], s1 = a.cell_start[base + x1 + 1];  // s1 <= the indexed cloud's size
-      for (int j = s0; j < s1; j += KNN_UNROLL) {
-        float4 c[KNN_UNROLL];
-#pragma unroll
-        for (int u = 0; u < KNN_UNROLL; ++u) c[u] = a.t4[min(j + u, s1 - 1)];
-#pragma unroll
-        for (int u = 0; u < KNN_UNROLL; ++u) {
-          const float d = pair_dist(px, py, pz, c[u].x, c[u].y, c[u].z);
-          const int cj = __float_as_int(c[u].w);
+    walk_candidates<KNN_S, KNN_UNROLL>(
+        walk, g, a.cell_start, slice, [&](int jj) { return a.t4[jj]; },
+        [&](const float4 c, bool in_range) {
+          const float d = pair_dist(px, py, pz, c.x, c.y, c.z);
+          const int cj = __float_as_int(c.w);
           // a neighbour: a finite point other than the query itself, by index
-          const bool nb = j + u < s1 && cj != self && finite3(c[u].x, c[u].y, c[u].z);
+          const bool nb = in_range && cj != self && finite3(c.x, c.y, c.z);
           const bool in = nb && d <= R;
           within += in;
-          if (!(in || (nb && whole))) continue;  // (beyond R nothing is final unless this is the whole cloud)
+          if (!(in || (nb && whole))) return;  // (beyond R nothing is final unless this is the whole cloud)
           const nn_key_t key = ((nn_key_t)__float_as_uint(d) << 32) | (unsigned)cj;
           if (cnt < k) {
             list[cnt][lane] = key;
@@ -101,7 +85,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_mean_kernel(const KnnArgs a) {
           } else if (key < cur_max) {
             list[max_at][lane] = key;
           } else {
-            continue;
+            return;
           }
           if (cnt == k) {  // the column is full: its largest key is the one a candidate has to beat
             cur_max = list[0][lane];
@@ -111,9 +95,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_mean_kernel(const KnnArgs a) {
               if (v > cur_max) cur_max = v, max_at = e;
             }
           }
-        }
-      }
-    }
+        });
 #pragma unroll
     for (int m = 1; m < KNN_S; m <<= 1) within += __shfl_xor(within, m, 64);
     if (active) {
@@ -163,81 +145,41 @@ __global__ __launch_bounds__(RAD_BLOCK) void radius_count_kernel(const float4* _
   const GridInfo g = *gi;
   const float px = p4.x, py = p4.y, pz = p4.z;
   const bool scan = live && finite3(px, py, pz);
-  int x0, x1, y0, y1, z0, z1;
-  cube_cells(px, r, g.lo[0], g.inv_hx, g.nx, x0, x1);
-  cube_cells(py, r, g.lo[1], g.inv_h, g.ny, y0, y1);
-  cube_cells(pz, r, g.lo[2], g.inv_h, g.nz, z0, z1);
-  const int nyr = y1 - y0 + 1;
-  const int nrows = scan ? nyr * (z1 - z0 + 1) : 0;
+  const Walk walk = make_walk(g, px, py, pz, r, scan);
   int m = 0;
-  for (int row = slice; row < nrows; row += RAD_S) {
-    const int rz = row / nyr, ry = row - rz * nyr;
-    const int base = ((z0 + rz) * g.ny + (y0 + ry)) * g.nx;
-    const int s0 = cell_start[base + x0], s1 = cell_start[base + x1 + 1];
-    for (int j = s0; j < s1; j += RAD_UNROLL) {
-      float4 c[RAD_UNROLL];
-#pragma unroll
-      for (int u = 0; u < RAD_UNROLL; ++u) c[u] = t4[min(j + u, s1 - 1)];
-#pragma unroll
-      for (int u = 0; u < RAD_UNROLL; ++u)  // (NaN and inf compare false: a non-finite point is nobody's neighbour)
-        m += j + u < s1 && pair_dist(px, py, pz, c[u].x, c[u].y, c[u].z) <= r;
-    }
-  }
+  walk_candidates<RAD_S, RAD_UNROLL>(
+      walk, g, cell_start, slice, [&](int jj) { return t4[jj]; },
+      [&](const float4 c, bool in_range) {  // (NaN and inf compare false: a non-finite point is nobody's neighbour)
+        m += in_range && pair_dist(px, py, pz, c.x, c.y, c.z) <= r;
+      });
 #pragma unroll
   for (int s = 1; s < RAD_S; s <<= 1) m += __shfl_xor(m, s, 64);
   if (live && slice == 0) value[__float_as_int(p4.w)] = (double)m;
 }
 
-// ---- the canonical tree over mean_i and mean_i^2 ----------------------------------------------------------------
-// 64-lane xor butterfly (32, 16, ..., 1), then ((w0 + w1) + w2) + w3: the tree of include/icpk.h
-__device__ __forceinline__ double block_tree_256(double v, double* ws) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  __syncthreads();  // (ws of a previous call has been read)
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
-__device__ __forceinline__ int block_count_256(int v, int* wc) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return wc[0] + wc[1] + wc[2] + wc[3];
-}
-
+// ---- the canonical tree over mean_i and mean_i^2 (pair_reduce.h's epilogue with two sums) -----------------------
 __global__ __launch_bounds__(RED_THREADS) void filter_sums_kernel(const FilterArgs a) {
-  __shared__ double ws[4];
-  __shared__ int wc[4];
   const int P = gridDim.x * RED_THREADS;
-  double v1 = 0.0, v2 = 0.0;
+  double v[2] = {0.0, 0.0};
   int cnt = 0;
   for (int i = blockIdx.x * RED_THREADS + threadIdx.x; i < a.n; i += P) {
     const bool fin = finite3(a.x[i], a.y[i], a.z[i]);
     const double m = fin ? a.value[i] : 0.0;  // (a dropped point adds +0.0 at its index)
-    v1 += m;
-    v2 += m * m;
+    v[0] += m;
+    v[1] += m * m;
     cnt += fin;
   }
-  const double s1 = block_tree_256(v1, ws), s2 = block_tree_256(v2, ws);
-  const int c = block_count_256(cnt, wc);
-  if (threadIdx.x == 0) {
-    a.partial[blockIdx.x] = s1;
-    a.partial[RED_MAX_BLOCKS + blockIdx.x] = s2;
-    a.pcount[blockIdx.x] = c;
-  }
+  block_partials<2>(v, cnt, a.partial + blockIdx.x, RED_MAX_BLOCKS, a.pcount + blockIdx.x);
 }
 
 // stage 2: slot b = the sums of block b, +0.0 beyond nblocks, one slot per lane; lane 0 goes on to the threshold
 __global__ __launch_bounds__(RED_THREADS) void filter_threshold_kernel(const FilterArgs a, int nblocks) {
-  __shared__ double ws[4];
-  __shared__ int wc[4];
   const int tid = threadIdx.x;
-  const double S1 = block_tree_256(tid < nblocks ? a.partial[tid] : 0.0, ws);
-  const double S2 = block_tree_256(tid < nblocks ? a.partial[RED_MAX_BLOCKS + tid] : 0.0, ws);
-  const int N = block_count_256(tid < nblocks ? a.pcount[tid] : 0, wc);
+  const double v[2] = {tid < nblocks ? a.partial[tid] : 0.0, tid < nblocks ? a.partial[RED_MAX_BLOCKS + tid] : 0.0};
+  const BlockTotals<2> t = block_tree<2>(v, tid < nblocks ? a.pcount[tid] : 0);
   if (tid != 0) return;
+  const double S1 = t.sum(0), S2 = t.sum(1);
+  const int N = (int)t.count();
   const double Nd = (double)N;
   const double mu = N > 0 ? S1 / Nd : 0.0;
   double var = N >= 2 ? (S2 - S1 * S1 / Nd) / (Nd - 1.0) : 0.0;

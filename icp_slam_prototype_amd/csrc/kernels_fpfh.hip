@@ -19,8 +19,8 @@
 //                         the order.
 //   5. match_compact_kernel  the kept pairs in source order (one workgroup: a ballot scan per 1024 sources).
 #include "fpfh_table.h"
+#include "grid_walk.h"
 #include "icpk_internal.h"
-#include "nn_device.h"
 
 namespace icpk {
 
@@ -31,8 +31,6 @@ constexpr int FP_BLOCK = 256;
 constexpr int FP_PTS = FP_BLOCK / FP_S;
 constexpr int FP_UNROLL = 2;  // candidates per lane and round trip
 constexpr int FP_CNT = FPFH_BINS + 1;  // LDS words per point: the bins, then m
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return ((x - x) + (y - y)) + (z - z) == 0.f; }
 
 __global__ __launch_bounds__(FP_BLOCK) void fpfh_prep_kernel(const FpfhArgs a) {
   const int ip = blockIdx.x * FP_BLOCK + threadIdx.x;
@@ -95,22 +93,6 @@ __device__ __forceinline__ void spfh_pair(int* cnt, float px, float py, float pz
   atomicAdd(&cnt[FPFH_BINS], 1);
 }
 
-// the rows of the cube of point (px, py, pz) and radius r, dealt to the point's lanes
-struct Walk {
-  int x0, x1, y0, nyr, z0, nrows;
-};
-__device__ __forceinline__ Walk make_walk(const GridInfo& g, float px, float py, float pz, float r, bool scan) {
-  int x0, x1, y0, y1, z0, z1;
-  cube_cells(px, r, g.lo[0], g.inv_hx, g.nx, x0, x1);
-  cube_cells(py, r, g.lo[1], g.inv_h, g.ny, y0, y1);
-  cube_cells(pz, r, g.lo[2], g.inv_h, g.nz, z0, z1);
-  Walk w;
-  w.x0 = x0, w.x1 = x1, w.y0 = y0, w.z0 = z0;
-  w.nyr = y1 - y0 + 1;
-  w.nrows = scan ? w.nyr * (z1 - z0 + 1) : 0;  // <= 1024 x 1024 (grid_info_body)
-  return w;
-}
-
 __global__ __launch_bounds__(FP_BLOCK) void fpfh_spfh_kernel(const FpfhArgs a) {
   __shared__ int cnt[FP_PTS][FP_CNT];
   for (int e = threadIdx.x; e < FP_PTS * FP_CNT; e += FP_BLOCK) (&cnt[0][0])[e] = 0;
@@ -124,22 +106,12 @@ __global__ __launch_bounds__(FP_BLOCK) void fpfh_spfh_kernel(const FpfhArgs a) {
   const float px = p4.x, py = p4.y, pz = p4.z, r = a.radius;
   const bool scan = live && ni.w != 0.f;  // only a described point counts pairs (described: finite, so is its cube)
   const Walk w = make_walk(g, px, py, pz, r, scan);
-  for (int row = slice; row < w.nrows; row += FP_S) {
-    const int rz = row / w.nyr, ry = row - rz * w.nyr;
-    const int base = ((w.z0 + rz) * g.ny + (w.y0 + ry)) * g.nx;  // cells base + x0 .. base + x1 < ncells, one range
-    const int s0 = a.cell_start[base + w.x0], s1 = a.cell_start[base + w.x1 + 1];  // s1 <= n
-    for (int j = s0; j < s1; j += FP_UNROLL) {
-      float4 c[FP_UNROLL], nj[FP_UNROLL];
-#pragma unroll
-      for (int u = 0; u < FP_UNROLL; ++u) {
-        const int jj = min(j + u, s1 - 1);
-        c[u] = a.t4[jj];
-        nj[u] = a.n4[jj];
-      }
-#pragma unroll
-      for (int u = 0; u < FP_UNROLL; ++u) spfh_pair(cnt[lp], px, py, pz, ni, c[u], nj[u], j + u < s1, r);
-    }
-  }
+  struct Cand {
+    float4 c, nj;
+  };
+  walk_candidates<FP_S, FP_UNROLL>(
+      w, g, a.cell_start, slice, [&](int jj) { return Cand{a.t4[jj], a.n4[jj]}; },
+      [&](const Cand& k, bool in_range) { spfh_pair(cnt[lp], px, py, pz, ni, k.c, k.nj, in_range, r); });
   __syncthreads();
   if (!live) return;
   const int i = __float_as_int(p4.w);
@@ -152,12 +124,6 @@ __global__ __launch_bounds__(FP_BLOCK) void fpfh_spfh_kernel(const FpfhArgs a) {
     if (a.counts && b < FPFH_BINS) a.counts[(size_t)i * FPFH_BINS + b] = c;
     if (a.m && b == FPFH_BINS) a.m[i] = m;
   }
-}
-
-__device__ __forceinline__ long long sum_over_point(long long v) {
-#pragma unroll
-  for (int k = 1; k < FP_S; k <<= 1) v += __shfl_xor(v, k, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(FP_BLOCK) void fpfh_final_kernel(const FpfhArgs a) {
@@ -177,32 +143,33 @@ __global__ __launch_bounds__(FP_BLOCK) void fpfh_final_kernel(const FpfhArgs a) 
 #pragma unroll
   for (int b = 0; b <= FPFH_BINS; ++b) A[b] = 0;
   long long Q = 0;
-  for (int row = slice; row < w.nrows; row += FP_S) {
-    const int rz = row / w.nyr, ry = row - rz * w.nyr;
-    const int base = ((w.z0 + rz) * g.ny + (w.y0 + ry)) * g.nx;
-    const int s0 = a.cell_start[base + w.x0], s1 = a.cell_start[base + w.x1 + 1];  // s1 <= n
-    for (int j = s0; j < s1; ++j) {
-      const float4 c = a.t4[j];
-      const float d = pair_dist(px, py, pz, c.x, c.y, c.z);
-      if (!(d > 0.f && d <= r)) continue;
-      const unsigned* const gj = reinterpret_cast<const unsigned*>(a.g + (size_t)j * FPFH_G_STRIDE);
-      unsigned v[FPFH_G_STRIDE / 2];
+  // (one candidate at a time: its 68 bytes of g are gathered only if it is a neighbour)
+  struct Cand {
+    float4 c;
+    int j;
+  };
+  walk_candidates<FP_S, 1>(
+      w, g, a.cell_start, slice, [&](int j) { return Cand{a.t4[j], j}; },
+      [&](const Cand& k, bool) {
+        const float d = pair_dist(px, py, pz, k.c.x, k.c.y, k.c.z);
+        if (!(d > 0.f && d <= r)) return;
+        const unsigned* const gj = reinterpret_cast<const unsigned*>(a.g + (size_t)k.j * FPFH_G_STRIDE);
+        unsigned v[FPFH_G_STRIDE / 2];
 #pragma unroll
-      for (int k = 0; k < FPFH_G_STRIDE / 2; ++k) v[k] = gj[k];
-      if ((v[FPFH_BINS / 2] >> 16) == 0) continue;  // m_j == 0
-      const double u = rr / ((double)d * (double)d);
-      const long long q = (long long)__builtin_rint(__builtin_fmin(u, 16384.0) * 1024.0);
+        for (int e = 0; e < FPFH_G_STRIDE / 2; ++e) v[e] = gj[e];
+        if ((v[FPFH_BINS / 2] >> 16) == 0) return;  // m_j == 0
+        const double u = rr / ((double)d * (double)d);
+        const long long q = (long long)__builtin_rint(__builtin_fmin(u, 16384.0) * 1024.0);
 #pragma unroll
-      for (int k = 0; k < FPFH_G_STRIDE / 2; ++k) {
-        A[2 * k] += q * (long long)(v[k] & 0xffffu);
-        A[2 * k + 1] += q * (long long)(v[k] >> 16);
-      }
-      Q += q;
-    }
-  }
+        for (int e = 0; e < FPFH_G_STRIDE / 2; ++e) {
+          A[2 * e] += q * (long long)(v[e] & 0xffffu);
+          A[2 * e + 1] += q * (long long)(v[e] >> 16);
+        }
+        Q += q;
+      });
 #pragma unroll
-  for (int b = 0; b < FPFH_BINS; ++b) A[b] = sum_over_point(A[b]);
-  Q = sum_over_point(Q);
+  for (int b = 0; b < FPFH_BINS; ++b) A[b] = sum_over_point<FP_S>(A[b]);
+  Q = sum_over_point<FP_S>(Q);
   if (!live || slice != 0) return;
   const int i = __float_as_int(p4.w);
   float* const out = a.desc + (size_t)i * FPFH_BINS;

@@ -12,7 +12,7 @@
 #include "icpk_internal.h"
 #include "loop_init.h"
 #include "solve_impl.h"
-#include "wave_sum.h"
+#include "pair_reduce.h"
 
 namespace icpk {
 
@@ -37,23 +37,17 @@ template <int NS, int NACT = NS>
 __device__ __forceinline__ void tree_stage2(const double* __restrict__ partial, const int* __restrict__ pcount,
                                             int nblocks, double (&sums)[NS], long long& count) {
   // only the first NACT sums were produced (and are consumed); the others read as 0
-  __shared__ double ws[4][NACT];
-  __shared__ int wc[4];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   double v[NACT];
   int c = 0;
 #pragma unroll
   for (int s = 0; s < NACT; ++s) v[s] = tid < nblocks ? partial[s * RED_MAX_BLOCKS + tid] : 0.0;  // [sum][block]: coalesced
   if (tid < nblocks) c = pcount[tid];
-  double u[WaveScatter<NACT>::H2];
-  wave_reduce_scatter<NACT>(v, u, c);
-  wave_scatter_store<NACT>(u, lane, ws[wave]);
-  if (lane == 0) wc[wave] = c;
-  __syncthreads();
+  const BlockTotals<NACT> t = block_tree<NACT>(v, c);
   if (tid == 0) {
 #pragma unroll
-    for (int s = 0; s < NS; ++s) sums[s] = s < NACT ? ((ws[0][s] + ws[1][s]) + ws[2][s]) + ws[3][s] : 0.0;
-    count = (long long)wc[0] + wc[1] + wc[2] + wc[3];
+    for (int s = 0; s < NS; ++s) sums[s] = s < NACT ? t.sum(s) : 0.0;
+    count = t.count();
   }
 }
 

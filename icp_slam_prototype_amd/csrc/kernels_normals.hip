@@ -4,9 +4,8 @@
 //   1. normals_moments_kernel  the radius search and the moment sums, the hot path.  It walks K1d's index of the target
 //                              (kernels_grid.hip: the target sorted by cell, `cell_start`): the points are taken in cell
 //                              order, NRM_S adjacent lanes per point, so that the lanes of a wave read the same few rows
-//                              of cells.  A point's lanes share the (y, z) rows of the cube [p - rr, p + rr] (cube_cells,
-//                              the superset K1d proves sufficient for pair_dist <= r); every row is one contiguous range
-//                              of the sorted copy.  Each lane keeps ten integer partial sums; a butterfly over the
+//                              of cells.  A point's lanes share the (y, z) rows of the cube [p - rr, p + rr] (the walk
+//                              of grid_walk.h).  Each lane keeps ten integer partial sums; a butterfly over the
 //                              point's lanes adds them, and the lanes store the ten words side by side.
 //   2. normals_solve_kernel    one lane per point: covariance, cyclic Jacobi eigen-solve of the symmetric 3x3 in
 //                              float64, the tests of the rule, orientation, curvature.  A launch of its own and not the
@@ -15,8 +14,8 @@
 // Every sum is an integer sum, so nothing depends on the order in which neighbours arrive or on how a point's rows are
 // dealt to its lanes: the moments are the same bits on every run, for every order of the cloud, and the bits of the
 // CPU model.
+#include "grid_walk.h"
 #include "icpk_internal.h"
-#include "nn_device.h"
 
 namespace icpk {
 
@@ -27,20 +26,6 @@ constexpr int NRM_BLOCK = 256;
 constexpr int NRM_UNROLL = 4;     // candidates per lane and round trip
 constexpr double NRM_FIX = 32768.0;  // F = 2^15
 
-// q = (int64)rint(((double)pj - (double)pi) / (double)r * F), the quotient taken as the rule says -- by a division --
-// only where that can matter.  t = (dd * fl(1 / r)) * F differs from the rule's fl(dd / r) * F by less than 2^-36
-// (|dd / r| <= 1 + 2^-20 for an accepted neighbour, three roundings of 2^-53 each, times 2^15; the scaling by F is exact),
-// so whenever t is further than 2^-30 from a rounding boundary k + 1/2 both round to the same integer, ties included.
-__device__ __forceinline__ int quantise(double dd, double rd, double inv_r) {
-  double t = (dd * inv_r) * NRM_FIX;
-  double k = __builtin_rint(t);
-  if (!(__builtin_fabs(t - k) < 0.5 - 0x1p-30)) {
-    t = (dd / rd) * NRM_FIX;
-    k = __builtin_rint(t);
-  }
-  return (int)k;
-}
-
 struct Moments {
   long long m, sx, sy, sz, sxx, sxy, sxz, syy, syz, szz;
 };
@@ -49,9 +34,9 @@ __device__ __forceinline__ void accumulate(Moments& M, float px, float py, float
                                            double rd, double inv_r) {
   const float d = pair_dist(px, py, pz, c.x, c.y, c.z);
   if (in_range && d <= r) {  // (NaN and inf compare false: a non-finite point is nobody's neighbour)
-    const int qx = quantise((double)c.x - (double)px, rd, inv_r);
-    const int qy = quantise((double)c.y - (double)py, rd, inv_r);
-    const int qz = quantise((double)c.z - (double)pz, rd, inv_r);
+    const int qx = quantise((double)c.x - (double)px, rd, inv_r, NRM_FIX);
+    const int qy = quantise((double)c.y - (double)py, rd, inv_r, NRM_FIX);
+    const int qz = quantise((double)c.z - (double)pz, rd, inv_r, NRM_FIX);
     // |q| <= F + 1: the products fit 32 bits, the sums of fewer than 2^31 of them 64
     M.m += 1;
     M.sx += qx;
@@ -66,12 +51,6 @@ __device__ __forceinline__ void accumulate(Moments& M, float px, float py, float
   }
 }
 
-__device__ __forceinline__ long long sum_over_point(long long v) {
-#pragma unroll
-  for (int k = 1; k < NRM_S; k <<= 1) v += __shfl_xor(v, k, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(NRM_BLOCK) void normals_moments_kernel(const NormalsArgs a) {
   const int slice = threadIdx.x & (NRM_S - 1);
   const int ip = (int)((blockIdx.x * (unsigned)NRM_BLOCK + threadIdx.x) / NRM_S);  // position in cell order
@@ -83,39 +62,17 @@ __global__ __launch_bounds__(NRM_BLOCK) void normals_moments_kernel(const Normal
   const double rd = (double)r, inv_r = 1.0 / rd;
   // a non-finite point has an empty neighbourhood (and its cube would be the whole grid)
   const bool scan = live && __builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz);
-  int x0, x1, y0, y1, z0, z1;
-  cube_cells(px, r, g.lo[0], g.inv_hx, g.nx, x0, x1);
-  cube_cells(py, r, g.lo[1], g.inv_h, g.ny, y0, y1);
-  cube_cells(pz, r, g.lo[2], g.inv_h, g.nz, z0, z1);
-  const int nyr = y1 - y0 + 1;
-  const int nrows = scan ? nyr * (z1 - z0 + 1) : 0;  // <= 1024 x 1024 (grid_info_body)
+  const Walk walk = make_walk(g, px, py, pz, r, scan);
   Moments M{};
-  for (int row = slice; row < nrows; row += NRM_S) {
-    const int rz = row / nyr, ry = row - rz * nyr;
-    const int base = ((z0 + rz) * g.ny + (y0 + ry)) * g.nx;  // cells base + x0 .. base + x1 < ncells, one range
-    const int s0 = a.cell_start[base + x0], s1 = a.cell_start[base + x1 + 1];  // s1 <= n
-    for (int j = s0; j < s1; j += NRM_UNROLL) {
-      float4 c[NRM_UNROLL];
-#pragma unroll
-      for (int u = 0; u < NRM_UNROLL; ++u) c[u] = a.t4[min(j + u, s1 - 1)];
-#pragma unroll
-      for (int u = 0; u < NRM_UNROLL; ++u) accumulate(M, px, py, pz, c[u], j + u < s1, r, rd, inv_r);
-    }
-  }
+  walk_candidates<NRM_S, NRM_UNROLL>(
+      walk, g, a.cell_start, slice, [&](int jj) { return a.t4[jj]; },
+      [&](const float4 c, bool in_range) { accumulate(M, px, py, pz, c, in_range, r, rd, inv_r); });
   long long w[NRM_MOMENTS] = {M.m, M.sx, M.sy, M.sz, M.sxx, M.sxy, M.sxz, M.syy, M.syz, M.szz};
 #pragma unroll
-  for (int k = 0; k < NRM_MOMENTS; ++k) w[k] = sum_over_point(w[k]);
+  for (int k = 0; k < NRM_MOMENTS; ++k) w[k] = sum_over_point<NRM_S>(w[k]);
   if (!live) return;
-  // the point's lanes store its ten words side by side: lane k word k, lanes 0 and 1 also words 8 and 9
-  long long* const out = a.moments + (size_t)__float_as_int(p4.w) * NRM_MOMENTS;
-  long long mine = w[0], late = w[NRM_S];
-#pragma unroll
-  for (int k = 1; k < NRM_S; ++k) mine = slice == k ? w[k] : mine;
-  late = slice == 1 ? w[NRM_S + 1] : late;
-  out[slice] = mine;
-  if (slice < NRM_MOMENTS - NRM_S) out[NRM_S + slice] = late;
+  store_point_words<NRM_S>(a.moments + (size_t)__float_as_int(p4.w) * NRM_MOMENTS, slice, w);
 }
-static_assert(NRM_S == 8 && NRM_MOMENTS == 10, "the store above deals ten words to eight lanes");
 
 // one Jacobi rotation of the symmetric 3x3 in the plane (p, q); r is the third axis.  Rutishauser's formulas: the
 // smaller root t of t^2 + 2 theta t - 1 = 0, so |angle| <= pi / 4.

@@ -12,9 +12,9 @@
 //                           per-block partials, then the 256 slots on one workgroup per pose.
 // The keys are the interface between the two: the search may deal a point to any number of lanes in any order (its
 // result is a minimum over different keys), the sums follow the source's index order whatever the search did.
+#include "grid_walk.h"
 #include "icpk_internal.h"
-#include "nn_device.h"
-#include "wave_sum.h"
+#include "pair_reduce.h"
 
 namespace icpk {
 
@@ -39,14 +39,10 @@ constexpr int SC_BLOCK = 256;
 constexpr int SC_UNROLL = 4;   // candidates per lane and round trip
 constexpr int SC_MAX_ROUNDS = 256;  // (a guard: a radius that doubles reaches max_dist, a finite float, sooner)
 
-// (x - x is 0 for a finite x and NaN otherwise)
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return ((x - x) + (y - y)) + (z - z) == 0.f; }
-
 // The exact nearest target with d < max_dist of one moved point, without a seed.
 //
-// Exactness.  After the rows of cube_cells(p, R) on all three axes have been scanned, every target with
-// pair_dist <= R has been seen (the superset proof in front of K1d's sweep in kernels_grid.hip, "Cells met by the
-// cube"; cube_cells is the same function).  `best` is the smallest (d, j) key among the targets seen so far that have
+// Exactness.  After the cube of radius R has been walked, every target with pair_dist <= R has been seen
+// (grid_walk.h).  `best` is the smallest (d, j) key among the targets seen so far that have
 // d < max_dist.  Three ways out:
 //   best.d <= R         every target that could beat or tie best has d <= best.d <= R and has been seen: best is final.
 //   best.d >  R         (a target from a corner of the cube) one more round with R := best.d -- which is < max_dist, so
@@ -57,9 +53,7 @@ __device__ __forceinline__ bool finite3(float x, float y, float z) { return ((x 
 // Cost.  The first radius is one cell edge h: the grid is sized for `ppc` targets per h x h of surface, so where a
 // target lies within h -- every point of a pose near the truth -- the walk ends after one round of ~4 ppc candidates,
 // whatever max_dist is.  Only a point with nothing near pays for its growing cube (each round at most twice the last).
-// Shape.  SC_S adjacent lanes share a (pose, point) and deal the (y, z) rows of its cube among themselves, every row one
-// contiguous range of the sorted copy; consecutive points of the source are neighbours in space for a depth camera's
-// cloud, so the lanes of a wave read the same few rows of cells.
+// Shape.  SC_S adjacent lanes share a (pose, point): the walk of grid_walk.h, the points in the source's order.
 __global__ __launch_bounds__(SC_BLOCK) void score_search_kernel(const ScoreArgs a) {
   const int slice = threadIdx.x & (SC_S - 1);
   const int i = (int)((blockIdx.x * (unsigned)SC_BLOCK + threadIdx.x) / SC_S);
@@ -81,18 +75,15 @@ __global__ __launch_bounds__(SC_BLOCK) void score_search_kernel(const ScoreArgs 
   bool last = false;  // this round is the one after a find beyond R
   nn_key_t best = NN_KEY_INIT;
   for (int round = 0; round < SC_MAX_ROUNDS && __builtin_amdgcn_ballot_w64(active) != 0; ++round) {
-    int x0, x1, y0, y1, z0, z1;
-    cube_cells(px, R, g.lo[0], g.inv_hx, g.nx, x0, x1);
-    cube_cells(py, R, g.lo[1], g.inv_h, g.ny, y0, y1);
-    cube_cells(pz, R, g.lo[2], g.inv_h, g.nz, z0, z1);
-    const bool whole = x0 == 0 && x1 == g.nx - 1 && y0 == 0 && y1 == g.ny - 1 && z0 == 0 && z1 == g.nz - 1;
-    const int nyr = y1 - y0 + 1;
-    const int nrows = active ? nyr * (z1 - z0 + 1) : 0;  // <= 1024 x 1024 (grid_info_body)
+    // (the rows and candidates by hand, not through grid_walk.h's iterators: with them the fourth load of a batch
+    // went behind a branch)
+    const Walk w = make_walk(g, px, py, pz, R, active);
+    const bool whole = w.whole(g);
     if (active && slice == 0) SCORE_COUNT(1, 1);
-    for (int row = slice; row < nrows; row += SC_S) {
-      const int rz = row / nyr, ry = row - rz * nyr;
-      const int base = ((z0 + rz) * g.ny + (y0 + ry)) * g.nx;  // cells base + x0 .. base + x1 < ncells, one range
-      const int s0 = a.cell_start[base + x0], s1 = a.cell_start[base + x1 + 1];  // s1 <= the target's size
+    for (int row = slice; row < w.nrows; row += SC_S) {
+      const int rz = row / w.nyr, ry = row - rz * w.nyr;
+      const int base = ((w.z0 + rz) * g.ny + (w.y0 + ry)) * g.nx;  // cells base + x0 .. base + x1 < ncells, one range
+      const int s0 = a.cell_start[base + w.x0], s1 = a.cell_start[base + w.x1 + 1];  // s1 <= the target's size
       SCORE_COUNT(0, s1 - s0);
       for (int j = s0; j < s1; j += SC_UNROLL) {
         float4 c[SC_UNROLL];
@@ -159,16 +150,7 @@ __global__ __launch_bounds__(RED_THREADS) void score_reduce_kernel(const nn_key_
     v[10] += qz * qz;
     ++cnt;
   }
-  double u[WaveScatter<NSCORE>::H2];
-  wave_reduce_scatter<NSCORE>(v, u, cnt);
-  __shared__ double ws[RED_THREADS / 64][NSCORE];
-  __shared__ int wc[RED_THREADS / 64];
-  const int wave = tid >> 6, lane = tid & 63;
-  wave_scatter_store<NSCORE>(u, lane, ws[wave]);
-  if (lane == 0) wc[wave] = cnt;
-  __syncthreads();
-  if (tid < NSCORE) partial[tid * RED_MAX_BLOCKS + blockIdx.x] = ((ws[0][tid] + ws[1][tid]) + ws[2][tid]) + ws[3][tid];
-  if (tid == NSCORE) pcount[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+  block_partials<NSCORE>(v, cnt, partial + blockIdx.x, RED_MAX_BLOCKS, pcount + blockIdx.x);
 }
 
 // stage 2, one workgroup per pose: slot b = the sums of block b, +0.0 beyond nblocks, one slot per lane;
@@ -184,16 +166,7 @@ __global__ __launch_bounds__(RED_THREADS) void score_final_kernel(const double* 
 #pragma unroll
   for (int s = 0; s < NSCORE; ++s) v[s] = tid < nblocks ? partial[s * RED_MAX_BLOCKS + tid] : 0.0;
   int cnt = tid < nblocks ? pcount[tid] : 0;
-  double u[WaveScatter<NSCORE>::H2];
-  wave_reduce_scatter<NSCORE>(v, u, cnt);
-  __shared__ double ws[RED_THREADS / 64][NSCORE];
-  __shared__ int wc[RED_THREADS / 64];
-  const int wave = tid >> 6, lane = tid & 63;
-  wave_scatter_store<NSCORE>(u, lane, ws[wave]);
-  if (lane == 0) wc[wave] = cnt;
-  __syncthreads();
-  if (tid < NSCORE) out[tid] = ((ws[0][tid] + ws[1][tid]) + ws[2][tid]) + ws[3][tid];
-  if (tid == NSCORE) reinterpret_cast<long long*>(out)[NSCORE] = (long long)wc[0] + wc[1] + wc[2] + wc[3];
+  block_partials<NSCORE>(v, cnt, out, 1, reinterpret_cast<long long*>(out) + NSCORE);
 }
 
 }  // namespace

@@ -144,7 +144,7 @@ def scene():
     c.close()
 
 
-@pytest.mark.parametrize("n", [1, 200, 256, 3000, 65536, 70001])
+@pytest.mark.parametrize("n", [1, 200, 255, 256, 257, 3000, 65536, 70001])
 def test_hook_sizes_and_lambdas(scene, n):
     """1, several and 256 blocks (and more than one element per lane); zero normals and zero gradients mixed in; the
     working source at the uploaded pose and moved; lambda_geometric 0, 0.5, 0.968 and 1"""
@@ -245,6 +245,15 @@ def test_flat_wall_in_every_mode_and_against_the_model(ctx, wall, oracle):
     assert err[0] < 1e-5 and err[1] < 1e-5
     assert [t["n_pairs"] for t in ref["trace"]] == m["pairs"]
     assert np.array_equal(ref["idx"], m["final_idx"])
+    # more than 65536 queries: a lane of K17 takes several pairs; the device loop reads the sweep's records, the host
+    # loop the keys
+    _install(ctx, cm.wall_pair(rows=240, cols=300))
+    ctx.set_colored(True)
+    few = dict(nn_mode=binding.NN_GRID, max_iterations=4, fixed_iterations=1)
+    dev = _run(ctx, host_loop=0, **few)
+    assert dev["rc"] == 0 and dev["stats"][0] == 4 and dev["src"].shape[1] > 65536
+    _assert_same(dev, _run(ctx, host_loop=1, **few), "more than 65536 queries")
+    ctx.set_colored(False)
 
 
 def test_setting_off_and_other_flavours_return_todays_bytes(ctx):

@@ -195,7 +195,7 @@ def test_hook_on_quarter_pair(ctx, quarter):
     assert np.array_equal(got[:27], 0.5 * ident[:27])
 
 
-@pytest.mark.parametrize("n", [1, 200, 256, 3000, 65536, 70001])
+@pytest.mark.parametrize("n", [1, 200, 255, 256, 257, 3000, 65536, 70001])
 def test_hook_sizes_and_mixed_normals(ctx, n):
     """1, several and 256 blocks (and more than one element per lane); zero normals mixed into both clouds; a
     non-identity R_acc; a non-unit and a non-finite host normal that trip the determinant rule"""
@@ -283,6 +283,13 @@ def test_loop_same_bits_in_every_mode_and_against_the_model(ctx, quarter, oracle
     print("kabsch", k, "point-to-plane", el, "plane-to-plane (device)", eg)
     assert eg[0] < k[0] / 5 and eg[1] < k[1] / 5
     assert eg[0] <= el[0] and eg[1] <= el[1]
+    # more than 65536 queries: a lane of K14 takes several pairs; the device loop reads the sweep's records, the host
+    # loop the keys
+    _prepare(ctx, synth.kinect_pair(rows=240, cols=320, valid=0.9, seed=4, fx=synth.FX / 2, cx=synth.CX / 2))
+    few = dict(nn_mode=binding.NN_GRID, max_iterations=4, fixed_iterations=1)
+    dev = _run(ctx, host_loop=0, **few)
+    assert dev["rc"] == 0 and dev["stats"][0] == 4 and dev["src"].shape[1] > 65536
+    _assert_same(dev, _run(ctx, host_loop=1, **few), "more than 65536 queries")
 
 
 # --------------------------------------------------------------------------------------------------------- edges --

@@ -1,5 +1,6 @@
 """Robust alignment on the device (include/icpk.h, icpk_set_robust) against the float64 model
 (tests/robust_model.py), the plain flavours and itself (device loop == host loop)."""
+import functools
 import itertools
 import math
 
@@ -41,14 +42,21 @@ def cloud(n, seed, nt=3000):
     return src, tgt
 
 
-def check_reduce_weighted(ctx, src, tgt, cfg, max_dist):
-    """icpk_reduce_weighted against the model: tau, m, c bit-exact, counts exact, sums within the tree's bound"""
+def check_reduce_weighted(ctx, src, tgt, cfg, max_dist, tn=None):
+    """icpk_reduce_weighted against the model: tau, m, c bit-exact, counts exact, sums within the tree's bound.
+    tn: the target's normals, for the point-to-plane flavour (K5's 30 sums) in place of Kabsch's 21"""
     set_robust(ctx, cfg)
     ctx.set_target(tgt)
+    if tn is not None:
+        ctx.set_target_normals(tn)
     ctx.set_source(src)
     idx, dist = ctx.nn(binding.NN_EXACT)
-    sums, n, kept, cut, med, c = ctx.reduce_weighted(max_dist)
-    acc, w, tau, m, mc = rm.robust_weights(dist, max_dist, cfg)
+    if tn is None:
+        sums, n, kept, cut, med, c = ctx.reduce_weighted(max_dist)
+        acc, w, tau, m, mc = rm.robust_weights(dist, max_dist, cfg)
+    else:
+        sums, n, kept, cut, med, c = ctx.reduce_weighted(max_dist, solve=binding.SOLVE_POINT_TO_PLANE)
+        acc, w, tau, m, mc = rm.robust_weights(dist, max_dist, cfg, idx, tn)
     assert n == np.count_nonzero(acc)
     assert kept == np.count_nonzero(w > 0)
     assert cut.view(np.uint32) == np.float32(tau).view(np.uint32) and med.view(np.uint32) == np.float32(m).view(np.uint32)
@@ -58,26 +66,42 @@ def check_reduce_weighted(ctx, src, tgt, cfg, max_dist):
     b = tgt[:, idx[acc]].astype(np.float64)
     ww = w[acc]
     k = ww > 0
-    wb = [ww * b[r] for r in range(3)]
-    terms = [(wb[r] * a[cc])[k] for r in range(3) for cc in range(3)]
-    terms += [(ww * (src[cc, acc] - tgt[cc, idx[acc]]).astype(np.float64))[k] for cc in range(3)]
-    terms += [dist[acc].astype(np.float64)]
-    terms += [(ww * a[cc])[k] for cc in range(3)] + [wb[cc][k] for cc in range(3)] + [ww[k], np.ones(int(k.sum()))]
+    if tn is None:
+        wb = [ww * b[r] for r in range(3)]
+        terms = [(wb[r] * a[cc])[k] for r in range(3) for cc in range(3)]
+        terms += [(ww * (src[cc, acc] - tgt[cc, idx[acc]]).astype(np.float64))[k] for cc in range(3)]
+        terms += [dist[acc].astype(np.float64)]
+        terms += [(ww * a[cc])[k] for cc in range(3)] + [wb[cc][k] for cc in range(3)]
+    else:
+        nr = tn[:, idx[acc]].astype(np.float64)
+        J = [a[1] * nr[2] - a[2] * nr[1], a[2] * nr[0] - a[0] * nr[2], a[0] * nr[1] - a[1] * nr[0], nr[0], nr[1], nr[2]]
+        r = ((a[0] - b[0]) * nr[0] + (a[1] - b[1]) * nr[1]) + (a[2] - b[2]) * nr[2]
+        terms = [(ww * (J[i] * J[j]))[k] for i in range(6) for j in range(i, 6)]
+        terms += [(ww * (J[i] * r))[k] for i in range(6)]
+        terms += [dist[acc].astype(np.float64)]
+    terms += [ww[k], np.ones(int(k.sum()))]
     nb = min(max((len(dist) + 255) // 256, 1), 256)
     chain = -(-len(dist) // (256 * nb)) + 18
     for s, t in enumerate(terms):
         exact = math.fsum(t.tolist())
         assert abs(sums[s] - exact) <= chain * U * float(np.sum(np.abs(t))), (len(dist), s, sums[s], exact)
-    assert sums[20] == kept
+    assert len(sums) == len(terms) and sums[-1] == kept
 
 
 @pytest.mark.parametrize("n", [1, 255, 256, 257, 65537, 92000, 1_000_003])
 def test_reduce_weighted_against_model(ctx, n):
+    """both flavours (the point-to-plane one with unit normals and, every fifth, none) at one pair, on each side of a
+    block, and beyond 65536 pairs, where a lane takes more than one"""
     src, tgt = cloud(n, seed=n)
     if n >= 255:
         src[:, n // 3] = np.nan  # never accepted
+    tn = np.random.default_rng(n).normal(size=tgt.shape)
+    tn = (tn / np.linalg.norm(tn, axis=0)).astype(np.float32)
+    tn[:, 2::5] = 0  # never accepted
     for cfg in (TUKEY_MEDIAN_08, HUBER_MEDIAN, dict(kernel=rm.TUKEY, scale=0.05, scale_mode=rm.FIXED, trim=0.5)):
         check_reduce_weighted(ctx, src, tgt, cfg, 0.75)
+        if n < 1_000_000:  # (the model of a million pairs once is enough)
+            check_reduce_weighted(ctx, src, tgt, cfg, 0.75, tn)
 
 
 def test_reduce_weighted_ties_zeros_and_gate(ctx):
@@ -118,6 +142,12 @@ def test_reduce_weighted_p2l_selection(ctx, oracle):
 
 def kinect_small(seed=3):
     return synth.kinect_pair(rows=120, cols=160, valid=0.6, seed=seed)
+
+
+@functools.lru_cache(maxsize=None)
+def kinect_big():
+    """more than 65536 points: a lane of the reduction takes several pairs"""
+    return synth.kinect_pair(rows=240, cols=320, valid=0.9, seed=5, fx=synth.FX / 2, cx=synth.CX / 2)
 
 
 def load_pair(ctx, p, p2l):
@@ -179,6 +209,14 @@ def test_device_loop_equals_host_loop(ctx, kernel, scale_mode, trim):
         host = run(ctx, cfg, host_loop=1, **kw)
         same(dev, host)
         assert len(dev[3]) == dev[1][0] > 0
+    for p2l in (False, True):
+        load_pair(ctx, kinect_big(), p2l)
+        assert ctx.get_source().shape[1] > 65536
+        kw = dict(solve=binding.SOLVE_POINT_TO_PLANE if p2l else binding.SOLVE_KABSCH, max_iterations=4,
+                  fixed_iterations=1, max_nn_dist=0.3 if p2l else 0.75)
+        dev = run(ctx, cfg, host_loop=0, **kw)
+        same(dev, run(ctx, cfg, host_loop=1, **kw))
+        assert len(dev[3]) == dev[1][0] == 4
 
 
 @pytest.mark.parametrize("which", ["contaminated", "kinect"])
