@@ -19,6 +19,9 @@ COMM_ID_BYTES = 128
 SOLVE_REFERENCE, SOLVE_KABSCH, SOLVE_POINT_TO_PLANE, SOLVE_PLANE_TO_PLANE = 0, 1, 2, 3
 W_DEGENERATE = 2
 W_EMPTY_MAP = 3
+W_NOT_CONVERGED = 4  # icpk_pose_graph_optimize ran into max_iterations
+PG_PRUNE = 1  # icpk_pg_params.flags: drop the uncertain edges the line process switched off, optimise once more
+PG_MAX_NODES, PG_MAX_EDGES = 1 << 20, 1 << 22
 MAX_NN_KEYPOINT_DISTANCE = 0.1  # icp.hpp:10
 NORMALS_CROSS, NORMALS_REFERENCE = 0, 1
 SUBSAMPLE_FACTOR = 40  # pointcloud.hpp:11
@@ -73,6 +76,8 @@ SYMBOLS = [
     "icpk_score_poses", "icpk_get_score_associations", "icpk_score_metrics", "icpk_information_matrix",
     "icpk_default_global_params", "icpk_compute_fpfh", "icpk_get_fpfh", "icpk_get_spfh", "icpk_match_features",
     "icpk_get_feature_matches", "icpk_register_global", "icpk_global_hypotheses",
+    "icpk_default_pg_params", "icpk_pose_graph_check", "icpk_pose_graph_optimize", "icpk_pose_graph_evaluate",
+    "icpk_get_pose_graph_trace",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -142,6 +147,27 @@ class GlobalResult(C.Structure):
     """icpk_global_result"""
     _fields_ = [("T", C.c_float * 16), ("hypothesis", C.c_int32), ("n_valid", C.c_int32), ("n_matches", C.c_int32),
                 ("reserved", C.c_int32), ("inliers", C.c_int64), ("sums", C.c_double * 11)]
+
+
+class PgEdge(C.Structure):
+    """icpk_pg_edge: T moves cloud `source` onto cloud `target`; info is the 6 x 6 information matrix, rotation first."""
+    _fields_ = [("source", C.c_int32), ("target", C.c_int32), ("uncertain", C.c_int32), ("reserved", C.c_int32),
+                ("T", C.c_double * 16), ("info", C.c_double * 36)]
+
+
+class PgParams(C.Structure):
+    """icpk_pg_params"""
+    _fields_ = [("max_iterations", C.c_int32), ("max_pcg_iterations", C.c_int32), ("pcg_tolerance", C.c_double),
+                ("tau", C.c_double), ("cost_tolerance", C.c_double), ("step_tolerance", C.c_double),
+                ("gradient_tolerance", C.c_double), ("preference_loop_closure", C.c_double),
+                ("edge_prune_threshold", C.c_double), ("reference_node", C.c_int32), ("flags", C.c_int32)]
+
+
+class PgResult(C.Structure):
+    """icpk_pg_result"""
+    _fields_ = [("iterations", C.c_int32), ("accepted", C.c_int32), ("pcg_iterations", C.c_int32),
+                ("n_pruned", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("final_lambda", C.c_double)]
 
 
 class FrameJob(C.Structure):
@@ -341,6 +367,14 @@ def load():
     lib.icpk_register_global.argtypes = [C.c_void_p, C.POINTER(GlobalParams), C.POINTER(GlobalResult)]
     lib.icpk_global_hypotheses.argtypes = [ip, ip, C.c_int32, fp, fp, fp, C.c_int32, fp, fp, fp, C.c_int32, C.c_uint64,
                                            C.c_float, C.c_int64, C.c_int32, ip, u8, fp]
+    lib.icpk_default_pg_params.argtypes = [C.POINTER(PgParams)]
+    lib.icpk_default_pg_params.restype = None
+    lib.icpk_pose_graph_check.argtypes = [C.c_int32, dp, C.c_int32, C.POINTER(PgEdge), C.POINTER(PgParams)]
+    lib.icpk_pose_graph_optimize.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, C.POINTER(PgEdge), C.POINTER(PgParams),
+                                             C.POINTER(PgResult), dp, dp, u8]
+    lib.icpk_pose_graph_evaluate.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, C.POINTER(PgEdge), C.c_double, dp, dp,
+                                             dp, dp]
+    lib.icpk_get_pose_graph_trace.argtypes = [C.c_void_p, ip, dp, dp, ip, ip]
     _lib = lib
     return lib
 
@@ -481,6 +515,40 @@ def information_matrix(sums, inliers):
     info = np.zeros(36, np.float64)
     load().icpk_information_matrix(sums.ctypes.data_as(dp), int(inliers), info.ctypes.data_as(dp))
     return info.reshape(6, 6)
+
+
+def default_pg_params(**kw):
+    """icpk_default_pg_params with the given fields replaced."""
+    p = PgParams()
+    load().icpk_default_pg_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"icpk_pg_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def pg_edges(edges):
+    """A sequence of (source, target, T (4, 4), info (6, 6), uncertain) as an array of icpk_pg_edge."""
+    arr = (PgEdge * max(len(edges), 1))()
+    v = np.frombuffer(arr, dtype=np.dtype([("source", "<i4"), ("target", "<i4"), ("uncertain", "<i4"), ("reserved", "<i4"),
+                                           ("T", "<f8", 16), ("info", "<f8", 36)]))
+    for k, (s, t, T, info, unc) in enumerate(edges):
+        v[k] = (int(s), int(t), int(bool(unc)), 0, np.asarray(T, np.float64).reshape(16),
+                np.asarray(info, np.float64).reshape(36))
+    return arr
+
+
+def pose_graph_check(poses, edges, params=None, n_nodes=None, n_edges=None):
+    """icpk_pose_graph_check (host only): the status icpk_pose_graph_optimize / _evaluate would refuse the graph with
+    (OK or E_ARG).  poses (n, 4, 4) float64 or None, edges as pg_edges takes them or None."""
+    dp = C.POINTER(C.c_double)
+    P = None if poses is None else np.ascontiguousarray(poses, np.float64)
+    n = int(n_nodes) if n_nodes is not None else (0 if P is None else P.size // 16)
+    m = int(n_edges) if n_edges is not None else (0 if edges is None else len(edges))
+    return load().icpk_pose_graph_check(n, None if P is None else P.ctypes.data_as(dp), m,
+                                        None if edges is None else pg_edges(edges),
+                                        None if params is None else C.byref(params))
 
 
 def global_hypotheses(matches, src, tgt, seed, edge_similarity=0.9, h0=0, count=1):
@@ -1070,6 +1138,46 @@ class Context:
                     sums=np.array(r.sums, np.float64), n_valid=r.n_valid, n_matches=r.n_matches), rc
 
     # -- loop ---------------------------------------------------------------------
+    def pose_graph_optimize(self, poses, edges, params=None, **kw):
+        """icpk_pose_graph_optimize (K18).  poses (n, 4, 4) float64, edges a sequence of (source, target, T, info,
+        uncertain); params a PgParams or its fields as keywords.  Returns (poses (n, 4, 4), result PgResult, weights
+        (m,), chi2 (m,), pruned (m,) bool, status OK or W_NOT_CONVERGED)."""
+        dp = C.POINTER(C.c_double)
+        p = params if params is not None else default_pg_params(**kw)
+        P = np.array(poses, np.float64, order="C").reshape(-1, 4, 4)
+        m = len(edges)
+        res = PgResult()
+        w, chi2, pruned = np.zeros(max(m, 1)), np.zeros(max(m, 1)), np.zeros(max(m, 1), np.uint8)
+        rc = self._chk(self._lib.icpk_pose_graph_optimize(self._h, P.shape[0], P.ctypes.data_as(dp), m, pg_edges(edges),
+                                                          C.byref(p), C.byref(res), w.ctypes.data_as(dp),
+                                                          chi2.ctypes.data_as(dp),
+                                                          pruned.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return P, res, w[:m], chi2[:m], pruned[:m].astype(bool), rc
+
+    def pose_graph_evaluate(self, poses, edges, mu=0.0):
+        """icpk_pose_graph_evaluate: (chi2 (m,), weights (m,), cost, gradient (n, 6)) at the given poses; nothing moves."""
+        dp = C.POINTER(C.c_double)
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 4, 4)
+        m = len(edges)
+        chi2, w, g = np.zeros(max(m, 1)), np.zeros(max(m, 1)), np.zeros((P.shape[0], 6))
+        cost = C.c_double(0)
+        self._chk(self._lib.icpk_pose_graph_evaluate(self._h, P.shape[0], P.ctypes.data_as(dp), m, pg_edges(edges),
+                                                     float(mu), chi2.ctypes.data_as(dp), w.ctypes.data_as(dp),
+                                                     C.byref(cost), g.ctypes.data_as(dp)))
+        return chi2[:m], w[:m], cost.value, g
+
+    def get_pose_graph_trace(self):
+        """Per LM iteration of the last pose_graph_optimize: dict(cost, lam, pcg_iterations, accepted)."""
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        n = C.c_int32(0)
+        self._chk(self._lib.icpk_get_pose_graph_trace(self._h, C.byref(n), None, None, None, None))
+        k = max(n.value, 1)
+        cost, lam, pcg, acc = np.zeros(k), np.zeros(k), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        self._chk(self._lib.icpk_get_pose_graph_trace(self._h, C.byref(n), cost.ctypes.data_as(dp), lam.ctypes.data_as(dp),
+                                                      pcg.ctypes.data_as(ip), acc.ctypes.data_as(ip)))
+        return [dict(cost=float(cost[i]), lam=float(lam[i]), pcg_iterations=int(pcg[i]), accepted=bool(acc[i]))
+                for i in range(n.value)]
+
     def align(self, params=None, **kw):
         p = params if params is not None else default_params(**kw)
         T = np.zeros(16, np.float32)

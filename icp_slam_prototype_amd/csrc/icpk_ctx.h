@@ -3,7 +3,7 @@
 // icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
 // entry; icpk_frontend.cpp: depth images;
 // icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp, icpk_gicp.cpp,
-// icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp).  Not
+// icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp, icpk_posegraph.cpp).  Not
 // part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -417,6 +417,19 @@ struct icpk_ctx {
   icpk::DevBuf<int> match_n;               // the number of kept pairs ...
   icpk::PinnedBuf<int> match_n_host;       // ... and where the host reads it
   bool have_matches = false;       // the pairs belong to the descriptors both sides hold now
+  // pose-graph optimisation (icpk_pose_graph_optimize / _evaluate, K18; icpk_posegraph.cpp): the edges and the
+  // adjacency list on the device, per edge two linearisations' blocks, per node the two sets of poses, two
+  // linearisations' blocks and the solver's vectors, the reductions' slots, the words the host reads once per LM
+  // iteration, and the record of the last optimize (icpk_get_pose_graph_trace).  Nothing else of the context is used
+  icpk::DevBuf<icpk::PgEdge> pg_edges;   // [n_edges]
+  icpk::DevBuf<int> pg_adj;              // [n_nodes + 1] starts, then [2 n_edges] entries
+  icpk::DevBuf<double> pg_edge_f64;      // 2 x n_edges x 44: A, b, chi2, l of either linearisation
+  icpk::DevBuf<double> pg_node_f64;      // n_nodes x (2 x 16 + 2 x 42 + 36 + 5 x 6)
+  icpk::DevBuf<double> pg_partial;       // PG_NPARTIAL x RED_MAX_BLOCKS
+  icpk::DevBuf<icpk::PgScalars> pg_scal;
+  icpk::PinnedBuf<icpk::PgScalars> pg_scal_host;
+  std::vector<double> pg_trace_cost, pg_trace_lambda;
+  std::vector<int32_t> pg_trace_pcg, pg_trace_accepted;
   int loop_nact = icpk::NSUM;      // device loop: sums the running alignment's step consumes (NSUM_REF or NSUM)
   int profile_phase = 0;     // alignments profiled so far (offsets the sampled launches, see profile_stride)
   int qperm_kind = 0;        // what qperm holds: 1 Morton order (pruned scan), 2 cell order (grid scan)

@@ -791,4 +791,52 @@ void launch_match_features(const MatchArgs& a, hipStream_t s);
 void launch_match_compact(const nn_key_t* best_s, int ns, const nn_key_t* best_t, int mutual, int* msrc, int* mtgt,
                           float* mD, int* n_out, hipStream_t s);
 
+// kernels_posegraph.hip -- K18, pose-graph optimisation (icpk_pose_graph_optimize / _evaluate); float64 throughout
+struct PgEdge {  // icpk_pg_edge as the device reads it (icpk_posegraph.cpp asserts the layout)
+  int32_t source, target, uncertain, reserved;
+  double T[16];
+  double info[36];
+};
+// one linearisation, left by an edge pass and a node pass over one set of poses.  Explicit blocks: J_t = -J_s, so an
+// edge is ONE 6 x 6 block A and one 6-vector b (include/icpk.h): 44 doubles = 352 bytes per edge with chi2 and l
+struct PgLin {
+  const double* poses;  // [n_nodes][16] the poses it was taken at
+  double* A;            // [n_edges][36]
+  double* b;            // [n_edges][6]
+  double* chi2;         // [n_edges]
+  double* l;            // [n_edges]
+  double* D;            // [n_nodes][36] sum of the incident edges' A
+  double* g;            // [n_nodes][6]  sum of the incident edges' +-b
+};
+enum { PG_P_COST = 0, PG_P_PRED, PG_P_PQ, PG_P_RZ, PG_P_RR, PG_P_DMAX, PG_P_GMAX, PG_P_HMAX, PG_NPARTIAL };
+struct PgScalars {  // the words of one LM iteration; the host reads them after its one wait
+  double cost, pred, dmax, gmax, hmax;  // of the trial linearisation / step (pg_finish_kernel)
+  double rz[2];                         // PCG: r . z of iteration k in rz[k & 1]
+  double gnorm2;                        // |g|^2 over the free nodes
+  int done[2];                          // PCG: iteration k does nothing when done[k & 1]
+  int pcg_iters;
+  int breakdown;                        // p . (H + lambda D) p was not > 0
+};
+struct PgArgs {
+  int n_nodes, n_edges, ref;
+  double mu;
+  const PgEdge* edges;
+  const int* adj_start;  // [n_nodes + 1]
+  const int* adj;        // [2 n_edges]: 2 * edge + (1 where the node is the edge's target), ascending per node
+  double* x;             // PCG vectors, [n_nodes][6] each
+  double* r;
+  double* z;
+  double* p;
+  double* q;
+  double* L;             // [n_nodes][36] Cholesky factors of the damped diagonal blocks
+  double* partial;       // [PG_NPARTIAL][RED_MAX_BLOCKS]
+  PgScalars* scal;
+};
+// edge pass + node pass over lin.poses; with_finish: pg_finish_kernel behind them (cost, |g|inf, max diag H into scal)
+void launch_pg_linearise(const PgArgs& a, const PgLin& lin, bool with_finish, hipStream_t s);
+// one LM iteration's launches up to the trial poses: damping + factors + PCG start, max_pcg x 3 PCG launches, the
+// trial update lin.poses -> trial.  Nothing waits in between
+void launch_pg_solve(const PgArgs& a, const PgLin& lin, double lambda, double pcg_tol, int max_pcg, double* trial,
+                     hipStream_t s);
+
 }  // namespace icpk

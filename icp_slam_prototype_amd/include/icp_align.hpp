@@ -534,3 +534,4 @@ class Tracker {
 }  // namespace icp
 
 #include "icp_map.hpp"
+#include "icp_pose_graph.hpp"

@@ -1107,6 +1107,132 @@ int icpk_global_hypotheses(const int32_t *match_src, const int32_t *match_tgt, i
                            const float *tz, int32_t nt, uint64_t seed, float edge_similarity, int64_t h0, int32_t count,
                            int32_t *samples, uint8_t *valid, float *T);
 
+/* ---- pose-graph optimisation (extension, K18) ------------------------------------------------------------------
+ * The consumer of K15's information matrix and of K16's loop closures: a graph of pairwise alignments, each weighted
+ * by its information matrix, optimised by Levenberg-Marquardt with a line process that switches wrong loop closures
+ * off (multiway registration).  Everything is float64 on the host and on the device; poses are 4 x 4, row-major.
+ *
+ * THE RULE
+ *   nodes      P_i, i in [0, n_nodes), maps node i's cloud into the world.
+ *   edges      (s, t, T_st, L, uncertain).  T_st moves cloud s onto cloud t: what icpk_align returns with s as source
+ *              and t as target.  The edge is satisfied when P_s = P_t T_st.  L is the 6 x 6 information matrix,
+ *              rotation first and translation second: icpk_information_matrix's order (G = [-[q]x | I], q in the
+ *              target's frame).  Only finiteness is asked of L; the rule reads all 36 entries as given.
+ *   residual   E = P_t^-1 P_s T_st^-1 (the error on the left, in the target's frame: the frame L is expressed in);
+ *              r = (rotation vector of R_E, t_E) in R^6; chi2 = r^T L r.  The inverse of a pose [R | t] is taken as
+ *              [R^T | -R^T t].  Rotation vector: v = (R32 - R23, R13 - R31, R21 - R12) / 2, s = |v|,
+ *              c = (trace R - 1) / 2, theta = the angle of (c, s), w = v * (theta / s); for s < 1e-8 and c > 0:
+ *              w = v * (1 + s^2 / 6); s = 0 otherwise: w = 0.  (theta -> pi is not treated: an edge whose error is a
+ *              half turn says nothing.)
+ *   no libm    The rule is +, -, *, / and sqrt in a fixed order, so that it gives the same bytes on the device and on
+ *              any IEEE host (tests/posegraph_model.py restates it operation for operation).  The angle of (c, s):
+ *              atan(s / c) for c > 0, else pi/2 + atan(-c / s); atan(x), x >= 0: the reciprocal above 1 (pi/2 - ...),
+ *              three halvings x <- x / (1 + sqrt(1 + x^2)), then 8 x (1 - x^2/3 + ... - x^26/27) by Horner.
+ *              sin(th) / th and (1 - cos th) / th^2: their power series in th^2, 20 terms in nested form
+ *              (1 - th^2/(2 3) (1 - th^2/(4 5) (...))): accurate to a few ulps for th <= pi (held against libm in
+ *              tests/test_posegraph_host.py), usable to 2 pi.  Well beyond 2 pi the 20 terms no longer reach the
+ *              series' tail and Rodrigues(w) is no rotation; the rule does not bound |w| of an LM step (a step of
+ *              more than a turn means the linearisation said nothing, and the gain ratio rejects it or not as for
+ *              any other step).
+ *              Every 3-term product is (a0 b0 + a1 b1) + a2 b2, every longer one is summed left to right from 0.
+ *   line process (uncertain edges, mu = preference_loop_closure > 0): l = (mu / (mu + chi2))^2, recomputed from the
+ *              poses at every evaluation and held constant inside a linearisation; every other edge, and every edge
+ *              when mu = 0, has l = 1.  Cost = sum over certain edges of chi2 + sum over uncertain edges of
+ *              (l chi2 + mu (sqrt(l) - 1)^2), the edges' terms summed in edge order through the canonical tree
+ *              (ICPK_RED_THREADS / ICPK_RED_MAX_BLOCKS) with n_edges elements.
+ *   update     P_i <- Exp(d_i) P_i, d = (w, v), Exp(d) = [Rodrigues(w) | v]: R' = Rodrigues(w) R, t' = Rodrigues(w) t
+ *              + v -- the same split as the residual; the full SE(3) exponential is not needed.  Rodrigues(w) = I +
+ *              a [w]x + b [w]x^2, a = sin(th) / th, b = (1 - cos(th)) / th^2 (th = |w|; the series above).  d of
+ *              reference_node is identically zero: that pose comes back with the bytes it
+ *              went in with.
+ *   Jacobians  analytic and exact to first order.  With B = P_s T_st^-1 and th = rotation vector of R_E:
+ *              J_s = [ Jl^-1(th) R_t^T , 0 ; -R_t^T [t_B]x , R_t^T ],  J_t = -J_s,  where Jl^-1(th) = I - [th]x / 2 +
+ *              k [th]x^2 is the inverse left Jacobian of SO(3), k = 1 / |th|^2 - (1 + cos|th|) / (2 |th| sin|th|)
+ *              with sin and cos from the series above (|th| < 1e-2: k = 1/12 + |th|^2 / 720 + |th|^4 / 30240).  Because J_t = -J_s an edge contributes ONE
+ *              block A = J_s^T (l L) J_s and one vector b = J_s^T (l L) r: H_ss = H_tt = A, H_st = H_ts = -A, g_s = b,
+ *              g_t = -b.  A node sums its incident edges' A and +-b in ascending edge index.
+ *   LM         Nielsen's schedule on (H + lambda diag H) d = -g: lambda_0 = tau max diag(H), nu = 2.  Gain ratio
+ *              rho = (F - F_trial) / pred, pred = sum_i d_i . (lambda diag(H_ii) d_i - g_i) (canonical tree over the
+ *              nodes); a step is accepted when pred > 0 and rho > 0: lambda <- lambda max(1/3, 1 - (2 rho - 1)^3),
+ *              nu = 2; otherwise lambda <- lambda nu, nu <- 2 nu.  The loop stops before its first iteration when
+ *              |g|inf < gradient_tolerance; after an accepted step when (F - F_trial) / F < cost_tolerance,
+ *              max |d| < step_tolerance or |g|inf < gradient_tolerance; after a rejected one when max |d| <
+ *              step_tolerance; and at max_iterations, which returns ICPK_W_NOT_CONVERGED.
+ *   linear solve  preconditioned conjugate gradients from d = 0, the preconditioner block Jacobi (one 6 x 6 Cholesky
+ *              of H_ii + lambda diag H_ii per node; a pivot that is not > 0 is replaced by 1 and its column's
+ *              off-diagonal entries by 0).  It stops when |residual|_2 <= pcg_tolerance |g|_2 (checked before the
+ *              first iteration too) or at max_pcg_iterations.  H p is a gather per node: sum over the incident edges
+ *              in ascending index of A (p_i - p_other), plus lambda diag(H_ii) p_i.  The dot products go through the
+ *              canonical tree over the nodes (a node's term is its six products added in order).  The rows of
+ *              reference_node are those of the identity with right-hand side 0.
+ *   pruning    (ICPK_PG_PRUNE) after convergence the uncertain edges with l < edge_prune_threshold are dropped and the
+ *              optimisation runs once more from where it stands over the remaining edges (lambda starts again from
+ *              tau max diag H).  The final l and chi2 of EVERY edge, dropped ones included, are evaluated at the final
+ *              poses.  When the remaining edges would no longer join every node to reference_node (the dropped ones
+ *              were the only way to some node), nothing is pruned: the mask is all zero, n_pruned is 0, there is no
+ *              second run and the first run's poses are the result.
+ *   exact      no floating-point atomics; the same bytes on every run and on every context.
+ *
+ * icpk_pose_graph_check is the host-side refusal both calls start with (no device work, no context): ICPK_E_ARG for a
+ * NULL pointer, n_nodes < 2 or > ICPK_PG_MAX_NODES, n_edges < 1 or > ICPK_PG_MAX_EDGES, an edge with s == t or an index
+ * out of range, a non-finite pose, T_st or L, a node the reference node cannot reach through the edges, a
+ * reference_node out of range, an unknown flag, max_iterations < 0, max_pcg_iterations < 1, or a tolerance, tau,
+ * preference_loop_closure or edge_prune_threshold that is negative or not finite (tau must be > 0).  params may be NULL
+ * (icpk_default_pg_params).  Nothing is launched and nothing written when it refuses.
+ *
+ * icpk_pose_graph_optimize   poses: in, out.  result and the three per-edge outputs may be NULL.  Returns ICPK_OK, or
+ *     ICPK_W_NOT_CONVERGED when a run of the loop ended at max_iterations.  One host wait per LM iteration.
+ * icpk_pose_graph_evaluate   one edge pass and one node pass at the given poses, nothing moves: per edge chi2 and l
+ *     (mu as preference_loop_closure; every edge counts as given by its `uncertain`), the cost and the gradient
+ *     (6 n_nodes: g_i = sum of +-b, reference node included; any output may be NULL).
+ * icpk_get_pose_graph_trace  per LM iteration of the last optimize: the cost after it, the lambda it ran with, its PCG
+ *     iterations and whether its step was accepted.  Arrays need room for *n_iter entries as returned by a call with
+ *     NULL arrays (at most 2 max_iterations); any may be NULL.
+ * The calls read and write nothing else the context holds. */
+#define ICPK_W_NOT_CONVERGED 4 /* icpk_pose_graph_optimize ran into max_iterations */
+#define ICPK_PG_PRUNE 1        /* flags of icpk_pg_params */
+#define ICPK_PG_MAX_NODES (1 << 20)
+#define ICPK_PG_MAX_EDGES (1 << 22)
+typedef struct icpk_pg_edge {
+  int32_t source, target;
+  int32_t uncertain; /* != 0: a loop closure the line process may switch off */
+  int32_t reserved;
+  double T[16];    /* row-major 4x4: moves cloud `source` onto cloud `target` */
+  double info[36]; /* row-major 6x6, rotation first */
+} icpk_pg_edge;
+typedef struct icpk_pg_params {
+  int32_t max_iterations;     /* 100 */
+  int32_t max_pcg_iterations; /* 200 */
+  double pcg_tolerance;       /* 1e-8 */
+  double tau;                 /* 1e-3 */
+  double cost_tolerance;      /* 1e-9 */
+  double step_tolerance;      /* 1e-10 */
+  double gradient_tolerance;  /* 1e-10 */
+  double preference_loop_closure; /* 0: no line process */
+  double edge_prune_threshold;    /* 0.25 */
+  int32_t reference_node;     /* 0 */
+  int32_t flags;              /* 0 */
+} icpk_pg_params;
+typedef struct icpk_pg_result {
+  int32_t iterations;     /* LM iterations, both runs of a pruning call */
+  int32_t accepted;       /* ... of which accepted */
+  int32_t pcg_iterations; /* total */
+  int32_t n_pruned;
+  double initial_cost, final_cost;
+  double final_lambda;
+} icpk_pg_result;
+void icpk_default_pg_params(icpk_pg_params *p);
+int icpk_pose_graph_check(int32_t n_nodes, const double *poses, int32_t n_edges, const icpk_pg_edge *edges,
+                          const icpk_pg_params *params);
+int icpk_pose_graph_optimize(icpk_ctx *ctx, int32_t n_nodes, double *poses /* in, out: 16 * n_nodes */, int32_t n_edges,
+                             const icpk_pg_edge *edges, const icpk_pg_params *params, icpk_pg_result *result,
+                             double *edge_weight_out, double *edge_chi2_out, uint8_t *pruned_out);
+int icpk_pose_graph_evaluate(icpk_ctx *ctx, int32_t n_nodes, const double *poses, int32_t n_edges,
+                             const icpk_pg_edge *edges, double mu, double *chi2_out, double *weight_out,
+                             double *cost_out, double *gradient_out /* 6 * n_nodes or NULL */);
+int icpk_get_pose_graph_trace(icpk_ctx *ctx, int32_t *n_iter, double *cost_out, double *lambda_out,
+                              int32_t *pcg_iterations_out, int32_t *accepted_out);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
