@@ -22,6 +22,9 @@ W_EMPTY_MAP = 3
 W_NOT_CONVERGED = 4  # icpk_pose_graph_optimize ran into max_iterations
 PG_PRUNE = 1  # icpk_pg_params.flags: drop the uncertain edges the line process switched off, optimise once more
 PG_MAX_NODES, PG_MAX_EDGES = 1 << 20, 1 << 22
+TSDF_COLOR = 1  # icpk_tsdf_params.flags: one intensity per voxel
+TSDF_MAX_VOXELS, TSDF_MAX_SURFACE = 1 << 30, 1 << 28
+DEPTH_SCALE = 5000.0  # pointcloud.cpp:37
 MAX_NN_KEYPOINT_DISTANCE = 0.1  # icp.hpp:10
 NORMALS_CROSS, NORMALS_REFERENCE = 0, 1
 SUBSAMPLE_FACTOR = 40  # pointcloud.hpp:11
@@ -78,6 +81,9 @@ SYMBOLS = [
     "icpk_get_feature_matches", "icpk_register_global", "icpk_global_hypotheses",
     "icpk_default_pg_params", "icpk_pose_graph_check", "icpk_pose_graph_optimize", "icpk_pose_graph_evaluate",
     "icpk_get_pose_graph_trace",
+    "icpk_default_tsdf_params", "icpk_tsdf_create", "icpk_tsdf_reset", "icpk_tsdf_release", "icpk_tsdf_integrate",
+    "icpk_tsdf_get", "icpk_tsdf_extract_surface", "icpk_tsdf_get_surface", "icpk_tsdf_surface_to_target",
+    "icpk_tsdf_invert_pose", "icpk_tsdf_voxel_update",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -168,6 +174,12 @@ class PgResult(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("accepted", C.c_int32), ("pcg_iterations", C.c_int32),
                 ("n_pruned", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
                 ("final_lambda", C.c_double)]
+
+
+class TsdfParams(C.Structure):
+    """icpk_tsdf_params"""
+    _fields_ = [("dims", C.c_int32 * 3), ("voxel", C.c_float), ("origin", C.c_float * 3), ("trunc", C.c_float),
+                ("max_weight", C.c_int32), ("depth_scale", C.c_float), ("flags", C.c_int32)]
 
 
 class FrameJob(C.Structure):
@@ -375,6 +387,20 @@ def load():
     lib.icpk_pose_graph_evaluate.argtypes = [C.c_void_p, C.c_int32, dp, C.c_int32, C.POINTER(PgEdge), C.c_double, dp, dp,
                                              dp, dp]
     lib.icpk_get_pose_graph_trace.argtypes = [C.c_void_p, ip, dp, dp, ip, ip]
+    u16 = C.POINTER(C.c_uint16)
+    lib.icpk_default_tsdf_params.argtypes = [C.POINTER(TsdfParams)]
+    lib.icpk_default_tsdf_params.restype = None
+    lib.icpk_tsdf_create.argtypes = [C.c_void_p, C.POINTER(TsdfParams)]
+    lib.icpk_tsdf_reset.argtypes = [C.c_void_p]
+    lib.icpk_tsdf_release.argtypes = [C.c_void_p]
+    lib.icpk_tsdf_integrate.argtypes = [C.c_void_p, u16, fp, C.c_int32, C.c_int32, C.c_float, C.c_float, dp, ip]
+    lib.icpk_tsdf_get.argtypes = [C.c_void_p, fp, u16, fp]
+    lib.icpk_tsdf_extract_surface.argtypes = [C.c_void_p, C.c_int32, ip, ip]
+    lib.icpk_tsdf_get_surface.argtypes = [C.c_void_p, fp, fp, fp, fp, fp, fp, fp, ip, u8]
+    lib.icpk_tsdf_surface_to_target.argtypes = [C.c_void_p]
+    lib.icpk_tsdf_invert_pose.argtypes = [dp, fp, fp]
+    lib.icpk_tsdf_voxel_update.argtypes = [C.POINTER(TsdfParams), fp, fp, u16, fp, C.c_int32, C.c_int32, C.c_float,
+                                           C.c_float, C.c_int64, C.c_int32, fp, u16, fp]
     _lib = lib
     return lib
 
@@ -551,6 +577,55 @@ def pose_graph_check(poses, edges, params=None, n_nodes=None, n_edges=None):
                                         None if params is None else C.byref(params))
 
 
+def tsdf_params(dims=None, voxel=None, origin=None, trunc=None, max_weight=None, depth_scale=None, flags=None):
+    """icpk_default_tsdf_params with the given fields replaced."""
+    p = TsdfParams()
+    load().icpk_default_tsdf_params(C.byref(p))
+    if dims is not None:
+        p.dims[:] = [int(v) for v in dims]
+    if origin is not None:
+        p.origin[:] = [float(v) for v in origin]
+    for k, v in (("voxel", voxel), ("trunc", trunc), ("max_weight", max_weight), ("depth_scale", depth_scale),
+                 ("flags", flags)):
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def tsdf_invert_pose(pose):
+    """icpk_tsdf_invert_pose (host only): the camera-to-world pose (4, 4) float64 inverted in double and rounded to
+    float once, as icpk_tsdf_integrate takes it.  Returns (R (3, 3), t (3,)) float32."""
+    P = np.ascontiguousarray(pose, np.float64).reshape(16)
+    R, t = np.zeros(9, np.float32), np.zeros(3, np.float32)
+    rc = load().icpk_tsdf_invert_pose(P.ctypes.data_as(C.POINTER(C.c_double)), _fp(R), _fp(t))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_tsdf_invert_pose: the pose is not finite")
+    return R.reshape(3, 3), t
+
+
+def tsdf_voxel_update(params, R, t, depth, tsdf, weight, intensity=None, intensity_value=None, fx=468.60, cx=318.27,
+                      first=0, count=None):
+    """icpk_tsdf_voxel_update (host only): the per-voxel rule for `count` voxels from linear index `first` (default:
+    all that tsdf holds).  tsdf float32, weight uint16 and intensity_value float32 arrays of count entries are updated
+    in place.  Returns the number of voxels written."""
+    depth = np.ascontiguousarray(depth, np.uint16)
+    rows, cols = depth.shape
+    R, t = _f(R).reshape(9), _f(t).reshape(3)
+    img = None if intensity is None else _f(intensity).reshape(-1)
+    for a, dt in ((tsdf, np.float32), (weight, np.uint16), (intensity_value, np.float32)):
+        if a is not None and (a.dtype != dt or not a.flags.c_contiguous):
+            raise ValueError("the voxel state arrays must be contiguous float32 / uint16 / float32")
+    count = tsdf.size if count is None else int(count)
+    u16 = C.POINTER(C.c_uint16)
+    rc = load().icpk_tsdf_voxel_update(C.byref(params), _fp(R), _fp(t), depth.ctypes.data_as(u16),
+                                       None if img is None else _fp(img), rows, cols, fx, cx, int(first), count,
+                                       _fp(tsdf), weight.ctypes.data_as(u16),
+                                       None if intensity_value is None else _fp(intensity_value))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_tsdf_voxel_update")
+    return rc
+
+
 def global_hypotheses(matches, src, tgt, seed, edge_similarity=0.9, h0=0, count=1):
     """icpk_global_hypotheses (host only): hypotheses h0 .. h0 + count - 1 of icpk_register_global's draw over `matches`
     ((src_index, tgt_index) int arrays) and the clouds src, tgt ((3, n) float32).  Returns (samples (count, 3) int32,
@@ -585,6 +660,8 @@ class Context:
         self._h = h
         self._log_ref = None
         self._pinned = {}  # register_host_buffer: address -> the array, alive while the library may read it
+        self._tsdf = None    # the TsdfParams of the volume the context holds (tsdf_create) ...
+        self._tsdf_n = None  # ... and the length of its surface list (tsdf_extract_surface)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1177,6 +1254,78 @@ class Context:
                                                       pcg.ctypes.data_as(ip), acc.ctypes.data_as(ip)))
         return [dict(cost=float(cost[i]), lam=float(lam[i]), pcg_iterations=int(pcg[i]), accepted=bool(acc[i]))
                 for i in range(n.value)]
+
+    # -- TSDF volume (K19) ---------------------------------------------------------
+    def tsdf_create(self, params=None, **kw):
+        """icpk_tsdf_create: the context's TSDF volume (replaces the one it held).  params: TsdfParams, or the fields
+        of tsdf_params as keywords.  Returns the TsdfParams in force."""
+        p = params if params is not None else tsdf_params(**kw)
+        self._chk(self._lib.icpk_tsdf_create(self._h, C.byref(p)))
+        self._tsdf, self._tsdf_n = p, None
+        return p
+
+    def tsdf_reset(self):
+        self._chk(self._lib.icpk_tsdf_reset(self._h))
+        self._tsdf_n = None
+
+    def tsdf_release(self):
+        self._chk(self._lib.icpk_tsdf_release(self._h))
+        self._tsdf, self._tsdf_n = None, None
+
+    def tsdf_integrate(self, depth, pose, intensity=None, fx=468.60, cx=318.27, shape=None, count=True):
+        """icpk_tsdf_integrate: one frame into the volume.  depth (rows, cols) uint16, or None: the frame
+        backproject_pair left resident (shape = (rows, cols) then).  pose (4, 4) float64, camera-to-world.  intensity
+        (rows, cols) float32 on a TSDF_COLOR volume.  Returns the number of voxels written (None with count=False)."""
+        d = None if depth is None else np.ascontiguousarray(depth, np.uint16)
+        rows, cols = d.shape if d is not None else shape
+        P = np.ascontiguousarray(pose, np.float64).reshape(16)
+        img = None if intensity is None else _f(intensity).reshape(-1)
+        if img is not None and img.size != rows * cols:
+            raise ValueError("one intensity per pixel expected")
+        n = C.c_int32(-1)
+        self._chk(self._lib.icpk_tsdf_integrate(self._h, None if d is None else d.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                None if img is None else _fp(img), rows, cols, fx, cx,
+                                                P.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n) if count else None))
+        return n.value if count else None
+
+    def tsdf_get(self, tsdf=True, weight=True, intensity=False):
+        """icpk_tsdf_get: (tsdf float32, weight uint16, intensity float32) of shape (dz, dy, dx); None where not asked."""
+        p = self._tsdf
+        if p is None:
+            self._chk(self._lib.icpk_tsdf_get(self._h, None, None, None))  # (ICPK_E_NOT_SET)
+        shape = (p.dims[2], p.dims[1], p.dims[0])
+        f = np.empty(shape, np.float32) if tsdf else None
+        w = np.empty(shape, np.uint16) if weight else None
+        c = np.empty(shape, np.float32) if intensity else None
+        self._chk(self._lib.icpk_tsdf_get(self._h, None if f is None else _fp(f),
+                                          None if w is None else w.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                          None if c is None else _fp(c)))
+        return f, w, c
+
+    def tsdf_extract_surface(self, min_weight=1):
+        """icpk_tsdf_extract_surface: (n_points, n_no_normal); the list stays on the device."""
+        n, m = C.c_int32(-1), C.c_int32(-1)
+        self._chk(self._lib.icpk_tsdf_extract_surface(self._h, int(min_weight), C.byref(n), C.byref(m)))
+        self._tsdf_n = n.value
+        return n.value, m.value
+
+    def tsdf_get_surface(self):
+        """icpk_tsdf_get_surface: dict(points (3, n), normals (3, n), intensity (n,), voxel (n,) int32, axis (n,) uint8)
+        of the last extraction."""
+        n = self._tsdf_n
+        if n is None:
+            self._chk(self._lib.icpk_tsdf_get_surface(self._h, *([None] * 9)))  # (ICPK_E_NOT_SET)
+            n = 0
+        m = max(n, 1)
+        pts, nrm = np.zeros((3, m), np.float32), np.zeros((3, m), np.float32)
+        inten, vox, axis = np.zeros(m, np.float32), np.zeros(m, np.int32), np.zeros(m, np.uint8)
+        self._chk(self._lib.icpk_tsdf_get_surface(self._h, _fp(pts[0]), _fp(pts[1]), _fp(pts[2]), _fp(nrm[0]), _fp(nrm[1]),
+                                                  _fp(nrm[2]), _fp(inten), vox.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  axis.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return dict(points=pts[:, :n], normals=nrm[:, :n], intensity=inten[:n], voxel=vox[:n], axis=axis[:n])
+
+    def tsdf_surface_to_target(self):
+        self._chk(self._lib.icpk_tsdf_surface_to_target(self._h))
 
     def align(self, params=None, **kw):
         p = params if params is not None else default_params(**kw)

@@ -17,7 +17,8 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_voxel.cpp", "kernels_voxel.hip", "icpk_normals.cpp", "kernels_normals.hip",
            "icpk_filter.cpp", "kernels_filter.hip", "icpk_gicp.cpp", "kernels_gicp.hip",
            "icpk_score.cpp", "kernels_score.hip", "icpk_fpfh.cpp", "kernels_fpfh.hip", "icpk_global.cpp",
-           "icpk_color.cpp", "kernels_color.hip", "icpk_posegraph.cpp", "kernels_posegraph.hip"]
+           "icpk_color.cpp", "kernels_color.hip", "icpk_posegraph.cpp", "kernels_posegraph.hip",
+           "icpk_tsdf.cpp", "kernels_tsdf.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -275,6 +276,23 @@ def build_pose_graph_test(force=False):
     return POSE_GRAPH_TEST
 
 
+TSDF_TEST = os.path.join(LIBDIR, "test_tsdf")
+
+
+def build_tsdf_test(force=False):
+    """Host-only C++ program over icp::TsdfVolume (icp_tsdf.hpp, K19) (g++, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_tsdf.cpp")
+    hdrs = [os.path.join(HERE, "include", h) for h in ("icp_align.hpp", "icp_tsdf.hpp")]
+    build()
+    newest = max(os.path.getmtime(p) for p in [src, LIB] + hdrs)
+    if not force and os.path.exists(TSDF_TEST) and os.path.getmtime(TSDF_TEST) >= newest:
+        return TSDF_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", TSDF_TEST])
+    return TSDF_TEST
+
+
 THREADS_TEST = os.path.join(LIBDIR, "test_threads")
 
 
@@ -341,4 +359,5 @@ if __name__ == "__main__":
     print(build_score_test(force="--force" in sys.argv))
     print(build_fpfh_test(force="--force" in sys.argv))
     print(build_pose_graph_test(force="--force" in sys.argv))
+    print(build_tsdf_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

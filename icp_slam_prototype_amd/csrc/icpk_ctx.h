@@ -3,7 +3,7 @@
 // icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
 // entry; icpk_frontend.cpp: depth images;
 // icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp, icpk_gicp.cpp,
-// icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp, icpk_posegraph.cpp).  Not
+// icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp, icpk_posegraph.cpp, icpk_tsdf.cpp).  Not
 // part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -430,6 +430,8 @@ struct icpk_ctx {
   icpk::PinnedBuf<icpk::PgScalars> pg_scal_host;
   std::vector<double> pg_trace_cost, pg_trace_lambda;
   std::vector<int32_t> pg_trace_pcg, pg_trace_accepted;
+  // TSDF volume (icpk_tsdf.cpp, K19); null until icpk_tsdf_create
+  struct icpk_tsdf_state* tsdf = nullptr;
   int loop_nact = icpk::NSUM;      // device loop: sums the running alignment's step consumes (NSUM_REF or NSUM)
   int profile_phase = 0;     // alignments profiled so far (offsets the sampled launches, see profile_stride)
   int qperm_kind = 0;        // what qperm holds: 1 Morton order (pruned scan), 2 cell order (grid scan)
@@ -453,6 +455,7 @@ struct icpk_ctx {
 void icpk_comm_release(icpk_ctx* ctx);  // called by icpk_destroy
 void icpk_map_free(icpk_ctx* ctx);      // called by icpk_destroy (icpk_map.cpp)
 void icpk_fast_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_fast.cpp)
+void icpk_tsdf_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_tsdf.cpp)
 int icpk_comm_allreduce_device(icpk_ctx* ctx, double* dev, int n);  // in-stream sum over the ranks (icpk_comm.cpp)
 // ICPK_NN_MAP: one K9 sweep of the working source against the map into ctx->best (icpk_map.cpp); the target must be
 // the map's current lookup target

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tsdf_rule.h"
+
 namespace icpk {
 
 // ---- K1 geometry ----------------------------------------------------------
@@ -838,5 +840,42 @@ void launch_pg_linearise(const PgArgs& a, const PgLin& lin, bool with_finish, hi
 // trial update lin.poses -> trial.  Nothing waits in between
 void launch_pg_solve(const PgArgs& a, const PgLin& lin, double lambda, double pcg_tol, int max_pcg, double* trial,
                      hipStream_t s);
+
+// kernels_tsdf.hip -- K19, the dense TSDF volume (icpk_tsdf_*); the rule itself is tsdf_rule.h
+constexpr int TSDF_THREADS = 256;
+constexpr int TSDF_MAX_BLOCKS = 8192;  // chunks a volume is cut into: also the length of the extraction's scan
+// voxels per chunk: a multiple of TSDF_THREADS, at most TSDF_MAX_BLOCKS chunks (n <= 2^30: at most 2^17)
+inline long long tsdf_chunk(long long n) {
+  const long long per = (n + TSDF_MAX_BLOCKS - 1) / TSDF_MAX_BLOCKS;
+  const long long c = (per + TSDF_THREADS - 1) / TSDF_THREADS * TSDF_THREADS;
+  return c < TSDF_THREADS ? TSDF_THREADS : c;
+}
+inline int tsdf_blocks(long long n) { return (int)((n + tsdf_chunk(n) - 1) / tsdf_chunk(n)); }
+struct TsdfIntegrateArgs {
+  TsdfFrame fr;
+  const uint16_t* depth;           // rows x cols
+  const float* intensity_image;    // rows x cols, or null ...
+  float* tsdf;
+  uint16_t* weight;
+  float* intensity;                // ... as the volume's intensity plane is
+  long long n, chunk;
+  int* slots;                      // [nblocks] voxels written per chunk
+};
+// one frame into the volume; *n_updated (device) = the voxels written
+void launch_tsdf_integrate(const TsdfIntegrateArgs& a, int nblocks, long long* n_updated, hipStream_t s);
+struct TsdfExtractArgs {
+  TsdfPlanes v;
+  long long n, chunk;
+  int* counts;         // [nblocks] crossings listed per chunk
+  int* dropped;        // [nblocks] crossings without a normal per chunk
+  long long* offsets;  // [nblocks + 1] the scan of counts
+  long long capacity;  // entries the list has room for
+  float *x, *y, *z, *nx, *ny, *nz, *intensity;
+  int* voxel_index;
+  uint8_t* axis;
+};
+// count pass + scan: totals[0] = crossings to list, totals[1] = crossings dropped (device)
+void launch_tsdf_count(const TsdfExtractArgs& a, int nblocks, long long* totals, hipStream_t s);
+void launch_tsdf_scatter(const TsdfExtractArgs& a, int nblocks, hipStream_t s);
 
 }  // namespace icpk

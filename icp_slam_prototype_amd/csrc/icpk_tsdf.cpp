@@ -1,0 +1,335 @@
+// icpk_tsdf.cpp -- host side of the TSDF volume (K19; kernels_tsdf.hip): the volume a context owns, the refusals, the
+// inversion of the pose, integration of a frame (uploaded, or the one icpk_backproject_pair left resident), extraction
+// of the surface list and its hand-over as the context's target.  The rules are written out in include/icpk.h and
+// stated once, in tsdf_rule.h, for the device and for icpk_tsdf_voxel_update.
+#include <cmath>
+#include <cstring>
+
+#include "icpk_ctx.h"
+
+using namespace icpk;
+
+struct icpk_tsdf_state {
+  icpk_tsdf_params p{};
+  long long n = 0;  // voxels
+  DevBuf<float> tsdf, intensity;
+  DevBuf<uint16_t> weight;
+  // a frame on its way into the volume (the resident frame of icpk_backproject_pair is read where it lies)
+  DevBuf<uint16_t> depth;
+  DevBuf<float> intensity_image;
+  // per chunk: integrate's written voxels / extract's listed crossings, extract's dropped ones; the scan; the totals
+  DevBuf<int> slots, dropped;
+  DevBuf<long long> offsets;
+  DevBuf<long long> totals;  // 2
+  PinnedBuf<long long> totals_host;
+  // the surface list of the last extraction: 7 planes of surf_cap floats, the voxel and the axis of every entry
+  DevBuf<float> surf;
+  DevBuf<int> surf_voxel;
+  DevBuf<uint8_t> surf_axis;
+  size_t surf_cap = 0;
+  bool have_surface = false;
+  int surf_n = 0, surf_dropped = 0;
+  float* plane(int k) const { return surf + (size_t)k * surf_cap; }
+};
+
+void icpk_tsdf_free(icpk_ctx* ctx) {
+  delete ctx->tsdf;  // (its buffers free themselves)
+  ctx->tsdf = nullptr;
+}
+
+namespace {
+
+bool positive(float v) { return std::isfinite(v) && v > 0.f; }
+
+// nullptr: fine; else what is wrong
+const char* check_params(const icpk_tsdf_params& p) {
+  long long n = 1;
+  for (int a = 0; a < 3; ++a) {
+    if (p.dims[a] < 1) return "a dim is < 1";
+    n *= p.dims[a];  // (each factor <= 2^31 and the running product is checked: no overflow)
+    if (n > ICPK_TSDF_MAX_VOXELS) return "more than ICPK_TSDF_MAX_VOXELS voxels";
+    if (!std::isfinite(p.origin[a])) return "the origin is not finite";
+  }
+  if (!positive(p.voxel) || !positive(p.trunc) || !positive(p.depth_scale)) return "voxel, trunc and depth_scale must be finite and > 0";
+  if (p.max_weight < 1 || p.max_weight > 65535) return "max_weight outside 1 .. 65535";
+  if (p.flags & ~ICPK_TSDF_COLOR) return "unknown TSDF flag";
+  return nullptr;
+}
+
+const char* check_camera(int32_t rows, int32_t cols, float fx, float cx) {
+  if (rows < 1 || cols < 1 || (int64_t)rows * cols > (1 << 28)) return "rows or cols < 1, or more than 2^28 pixels";
+  if (!positive(fx) || !std::isfinite(cx)) return "fx must be finite and > 0, cx finite";
+  return nullptr;
+}
+
+TsdfFrame make_frame(const icpk_tsdf_params& p, const float R[9], const float t[3], int rows, int cols, float fx, float cx) {
+  TsdfFrame fr{};
+  for (int a = 0; a < 3; ++a) fr.dims[a] = p.dims[a], fr.origin[a] = p.origin[a], fr.t[a] = t[a];
+  std::memcpy(fr.R, R, sizeof(fr.R));
+  fr.voxel = p.voxel, fr.trunc = p.trunc, fr.depth_scale = p.depth_scale, fr.max_weight = p.max_weight;
+  fr.rows = rows, fr.cols = cols, fr.fx = fx, fr.cx = cx;
+  return fr;
+}
+
+int clear_volume(icpk_ctx* ctx, icpk_tsdf_state* v) {
+  ICPK_HIP(ctx, hipMemsetAsync(v->tsdf, 0, (size_t)v->n * sizeof(float), ctx->stream));
+  ICPK_HIP(ctx, hipMemsetAsync(v->weight, 0, (size_t)v->n * sizeof(uint16_t), ctx->stream));
+  if (v->p.flags & ICPK_TSDF_COLOR) ICPK_HIP(ctx, hipMemsetAsync(v->intensity, 0, (size_t)v->n * sizeof(float), ctx->stream));
+  v->have_surface = false;
+  return ICPK_OK;
+}
+
+bool intensities_ok(const float* v, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!(v[i] >= 0.f && v[i] <= 1.f)) return false;  // (false for NaN)
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+void icpk_default_tsdf_params(icpk_tsdf_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->dims[0] = p->dims[1] = p->dims[2] = 256;
+  p->voxel = 0.02f;
+  p->origin[0] = p->origin[1] = -2.56f;
+  p->origin[2] = 0.f;
+  p->trunc = 0.08f;
+  p->max_weight = 255;
+  p->depth_scale = ICPK_DEPTH_SCALE;
+  p->flags = 0;
+}
+
+int icpk_tsdf_create(icpk_ctx* ctx, const icpk_tsdf_params* params) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_params p;
+  icpk_default_tsdf_params(&p);
+  if (params) p = *params;
+  if (const char* why = check_params(p)) return fail(ctx, ICPK_E_ARG, why);
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (nothing still reads the volume that is replaced)
+  icpk_tsdf_free(ctx);
+  icpk_tsdf_state* v = new icpk_tsdf_state();
+  v->p = p;
+  v->n = (long long)p.dims[0] * p.dims[1] * p.dims[2];
+  const size_t n = (size_t)v->n;
+  int rc = v->tsdf.reserve(ctx, n);
+  if (!rc) rc = v->weight.reserve(ctx, n);
+  if (!rc && (p.flags & ICPK_TSDF_COLOR)) rc = v->intensity.reserve(ctx, n);
+  if (!rc) rc = v->slots.reserve(ctx, TSDF_MAX_BLOCKS);
+  if (!rc) rc = v->dropped.reserve(ctx, TSDF_MAX_BLOCKS);
+  if (!rc) rc = v->offsets.reserve(ctx, TSDF_MAX_BLOCKS + 1);
+  if (!rc) rc = v->totals.reserve(ctx, 2);
+  if (!rc) rc = v->totals_host.reserve(ctx, 2);
+  if (!rc) rc = clear_volume(ctx, v);
+  if (rc) {
+    delete v;
+    return rc;
+  }
+  ctx->tsdf = v;
+  return ICPK_OK;
+}
+
+int icpk_tsdf_reset(icpk_ctx* ctx) {
+  if (!ctx) return ICPK_E_ARG;
+  if (!ctx->tsdf) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  return clear_volume(ctx, ctx->tsdf);
+}
+
+int icpk_tsdf_release(icpk_ctx* ctx) {
+  if (!ctx) return ICPK_E_ARG;
+  if (!ctx->tsdf) return ICPK_OK;
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  icpk_tsdf_free(ctx);
+  return ICPK_OK;
+}
+
+int icpk_tsdf_invert_pose(const double pose[16], float R[9], float t[3]) {
+  if (!pose || !R || !t) return ICPK_E_ARG;
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(pose[k])) return ICPK_E_ARG;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) R[3 * r + c] = (float)pose[4 * c + r];
+    t[r] = (float)-((pose[r] * pose[3] + pose[4 + r] * pose[7]) + pose[8 + r] * pose[11]);
+  }
+  return ICPK_OK;
+}
+
+int icpk_tsdf_integrate(icpk_ctx* ctx, const uint16_t* depth, const float* intensity, int32_t rows, int32_t cols, float fx,
+                        float cx, const double pose[16], int32_t* n_updated) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  if (const char* why = check_camera(rows, cols, fx, cx)) return fail(ctx, ICPK_E_ARG, why);
+  float R[9], t[3];
+  if (icpk_tsdf_invert_pose(pose, R, t)) return fail(ctx, ICPK_E_ARG, "the pose is NULL or not finite");
+  const bool color = (v->p.flags & ICPK_TSDF_COLOR) != 0;
+  if (color != (intensity != nullptr))
+    return fail(ctx, ICPK_E_ARG, color ? "a colour volume needs the frame's intensities" : "intensities given to a volume without ICPK_TSDF_COLOR");
+  const size_t npix = (size_t)rows * cols;
+  if (intensity && !intensities_ok(intensity, npix)) return fail(ctx, ICPK_E_ARG, "intensities must be finite and in [0, 1]");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const uint16_t* image = nullptr;
+  if (depth) {
+    if (int rc = v->depth.reserve(ctx, npix)) return rc;
+    ICPK_HIP(ctx, hipMemcpyAsync(v->depth, depth, npix * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+    image = v->depth;
+  } else {
+    if (ctx->frame_slot < 0 || ctx->frame_rows != rows || ctx->frame_cols != cols)
+      return fail(ctx, ICPK_E_NOT_SET, "no resident frame of this size (icpk_backproject_pair), pass depth");
+    // (two slots of rows x cols in either buffer; the filtered copy is the frame when the filter was on)
+    image = (ctx->frame_filter[0] ? ctx->depth_flt.get() : ctx->depth_dev.get()) + (size_t)ctx->frame_slot * npix;
+  }
+  if (intensity) {
+    if (int rc = v->intensity_image.reserve(ctx, npix)) return rc;
+    ICPK_HIP(ctx, hipMemcpyAsync(v->intensity_image, intensity, npix * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  TsdfIntegrateArgs a{};
+  a.fr = make_frame(v->p, R, t, rows, cols, fx, cx);
+  a.depth = image;
+  a.intensity_image = color ? v->intensity_image.get() : nullptr;
+  a.tsdf = v->tsdf, a.weight = v->weight, a.intensity = color ? v->intensity.get() : nullptr;
+  a.n = v->n, a.chunk = tsdf_chunk(v->n);
+  a.slots = v->slots;
+  launch_tsdf_integrate(a, tsdf_blocks(v->n), v->totals, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  if (!depth && !intensity && !n_updated) return ICPK_OK;  // (nothing of the caller's is in flight, nothing is asked)
+  ICPK_HIP(ctx, hipMemcpyAsync(v->totals_host, v->totals, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (n_updated) *n_updated = (int32_t)v->totals_host[0];
+  return ICPK_OK;
+}
+
+int icpk_tsdf_get(icpk_ctx* ctx, float* tsdf, uint16_t* weight, float* intensity) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  if (intensity && !(v->p.flags & ICPK_TSDF_COLOR)) return fail(ctx, ICPK_E_ARG, "the volume keeps no intensities");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t n = (size_t)v->n;
+  if (tsdf) ICPK_HIP(ctx, hipMemcpyAsync(tsdf, v->tsdf, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (weight) ICPK_HIP(ctx, hipMemcpyAsync(weight, v->weight, n * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (intensity) ICPK_HIP(ctx, hipMemcpyAsync(intensity, v->intensity, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_tsdf_extract_surface(icpk_ctx* ctx, int32_t min_weight, int32_t* n_points, int32_t* n_no_normal) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  if (min_weight < 1 || min_weight > 65535) return fail(ctx, ICPK_E_ARG, "min_weight outside 1 .. 65535");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  v->have_surface = false;
+  TsdfExtractArgs a{};
+  a.v.tsdf = v->tsdf, a.v.weight = v->weight;
+  a.v.intensity = (v->p.flags & ICPK_TSDF_COLOR) ? v->intensity.get() : nullptr;
+  for (int k = 0; k < 3; ++k) a.v.dims[k] = v->p.dims[k], a.v.origin[k] = v->p.origin[k];
+  a.v.voxel = v->p.voxel;
+  a.v.min_weight = min_weight;
+  a.n = v->n, a.chunk = tsdf_chunk(v->n);
+  a.counts = v->slots, a.dropped = v->dropped, a.offsets = v->offsets;
+  const int nblocks = tsdf_blocks(v->n);
+  launch_tsdf_count(a, nblocks, v->totals, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  // the one host wait: the list is allocated for the count
+  ICPK_HIP(ctx, hipMemcpyAsync(v->totals_host, v->totals, 2 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const long long listed = v->totals_host[0], dropped = v->totals_host[1];
+  if (listed > ICPK_TSDF_MAX_SURFACE) return fail(ctx, ICPK_E_ARG, "more than ICPK_TSDF_MAX_SURFACE crossings");
+  if ((size_t)listed > v->surf_cap) {
+    const size_t cap = (size_t)listed;
+    v->surf_cap = 0;
+    int rc = reserve_group(ctx, nullptr, need(v->surf, 7 * cap), need(v->surf_voxel, cap), need(v->surf_axis, cap));
+    if (rc) return rc;
+    v->surf_cap = cap;
+  }
+  if (listed > 0) {
+    a.capacity = listed;
+    a.x = v->plane(0), a.y = v->plane(1), a.z = v->plane(2);
+    a.nx = v->plane(3), a.ny = v->plane(4), a.nz = v->plane(5);
+    a.intensity = v->plane(6);
+    a.voxel_index = v->surf_voxel, a.axis = v->surf_axis;
+    launch_tsdf_scatter(a, nblocks, ctx->stream);
+    ICPK_HIP(ctx, hipGetLastError());
+  }
+  v->surf_n = (int)listed;
+  v->surf_dropped = dropped > INT32_MAX ? INT32_MAX : (int)dropped;
+  v->have_surface = true;
+  if (n_points) *n_points = v->surf_n;
+  if (n_no_normal) *n_no_normal = v->surf_dropped;
+  return ICPK_OK;
+}
+
+int icpk_tsdf_get_surface(icpk_ctx* ctx, float* x, float* y, float* z, float* nx, float* ny, float* nz, float* intensity,
+                          int32_t* voxel_index, uint8_t* axis) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v || !v->have_surface) return fail(ctx, ICPK_E_NOT_SET, "no surface list (icpk_tsdf_extract_surface)");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t n = (size_t)v->surf_n;
+  float* const out[7] = {x, y, z, nx, ny, nz, intensity};
+  for (int k = 0; k < 7 && n > 0; ++k)
+    if (out[k]) ICPK_HIP(ctx, hipMemcpyAsync(out[k], v->plane(k), n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (voxel_index && n > 0)
+    ICPK_HIP(ctx, hipMemcpyAsync(voxel_index, v->surf_voxel, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (axis && n > 0) ICPK_HIP(ctx, hipMemcpyAsync(axis, v->surf_axis, n, hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_tsdf_surface_to_target(icpk_ctx* ctx) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v || !v->have_surface) return fail(ctx, ICPK_E_NOT_SET, "no surface list (icpk_tsdf_extract_surface)");
+  if (v->surf_n == 0) return fail(ctx, ICPK_E_EMPTY_TARGET, "the surface list is empty");
+  const int n = v->surf_n;
+  const size_t bytes = (size_t)n * sizeof(float);
+  // (the target first: target_changed drops the normals and the colours the old target had)
+  int rc = set_target_impl(ctx, v->plane(0), v->plane(1), v->plane(2), n, hipMemcpyDeviceToDevice, false);
+  if (!rc) rc = ensure_cloud(ctx, ctx->nrm, n);
+  if (rc) return rc;
+  const Cloud& m = ctx->nrm;
+  float* const planes[3] = {m.x(), m.y(), m.z()};
+  for (int k = 0; k < 3; ++k) {
+    ICPK_HIP(ctx, hipMemcpyAsync(planes[k], v->plane(3 + k), bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    launch_fill_f32(planes[k] + n, m.cap - n, 0.f, ctx->stream);  // (as icpk_set_target_normals pads them)
+  }
+  ICPK_HIP(ctx, hipGetLastError());
+  ctx->have_normals = true;
+  ctx->have_nstats = false;
+  fpfh_dropped(ctx, 1);
+  if (v->p.flags & ICPK_TSDF_COLOR) {
+    if ((rc = ctx->tcol.reserve(ctx, (size_t)n))) return rc;
+    ICPK_HIP(ctx, hipMemcpyAsync(ctx->tcol, v->plane(6), bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->have_tgt_colors = true;
+  }
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_tsdf_voxel_update(const icpk_tsdf_params* params, const float R[9], const float t[3], const uint16_t* depth,
+                           const float* intensity, int32_t rows, int32_t cols, float fx, float cx, int64_t first,
+                           int32_t count, float* tsdf, uint16_t* weight, float* intensity_value) {
+  if (!params || !R || !t || !depth || !tsdf || !weight || count < 0 || first < 0) return ICPK_E_ARG;
+  if (check_params(*params) || check_camera(rows, cols, fx, cx)) return ICPK_E_ARG;
+  const bool color = (params->flags & ICPK_TSDF_COLOR) != 0;
+  if (color != (intensity != nullptr) || color != (intensity_value != nullptr)) return ICPK_E_ARG;
+  const long long n = (long long)params->dims[0] * params->dims[1] * params->dims[2];
+  if (first + count > n) return ICPK_E_ARG;
+  const TsdfFrame fr = make_frame(*params, R, t, rows, cols, fx, cx);
+  const long long dx = fr.dims[0], dxy = dx * fr.dims[1];
+  int written = 0;
+  for (int32_t e = 0; e < count; ++e) {
+    const long long at = first + e;
+    const int k = (int)(at / dxy), j = (int)((at - k * dxy) / dx), i = (int)(at - k * dxy - j * dx);
+    written += tsdf_voxel_update(fr, i, j, k, depth, intensity, &tsdf[e], &weight[e], color ? &intensity_value[e] : nullptr);
+  }
+  return written;
+}
+
+}  // extern "C"

@@ -1,0 +1,210 @@
+// kernels_tsdf.hip -- K19: the dense TSDF volume.  Integration of one posed depth frame (one thread per voxel, the rule
+// of tsdf_rule.h from the voxel's own indices) and extraction of the zero crossings as an ordered point list with
+// normals (count / scan / scatter, as K4 compacts an image).  A voxel is owned by one thread: no atomic of any kind,
+// the same bytes on every run.
+//
+// Both walks share one geometry: the volume is a line of n = dx dy dz voxels in linear order (x fastest), cut into at
+// most TSDF_MAX_BLOCKS contiguous chunks of a multiple of TSDF_THREADS voxels, one workgroup per chunk, which it
+// sweeps TSDF_THREADS voxels at a time.  A wave therefore reads and writes 64 consecutive voxels: 256 contiguous bytes
+// of the tsdf plane, 128 of the weight plane.
+#include "icpk_internal.h"
+#include "tsdf_rule.h"
+
+namespace icpk {
+
+namespace {
+
+struct VoxelIndex {
+  unsigned dx, dxy;
+  __device__ __forceinline__ void split(unsigned idx, int c[3]) const {  // (idx < 2^30: 32-bit divisions)
+    const unsigned k = idx / dxy, rem = idx - k * dxy, j = rem / dx;
+    c[0] = (int)(rem - j * dx), c[1] = (int)j, c[2] = (int)k;
+  }
+};
+
+// the sum of v over the workgroup, valid in thread 0 (integers: the order does not matter)
+__device__ __forceinline__ int block_sum(int v, int* lds4) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return lds4[0] + lds4[1] + lds4[2] + lds4[3];
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_integrate_kernel(const TsdfIntegrateArgs a) {
+  const long long begin = (long long)blockIdx.x * a.chunk;
+  const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
+  const VoxelIndex vi{(unsigned)a.fr.dims[0], (unsigned)a.fr.dims[0] * (unsigned)a.fr.dims[1]};
+  int written = 0;
+  for (long long base = begin; base < end; base += TSDF_THREADS) {
+    const long long at = base + threadIdx.x;
+    if (at >= end) continue;
+    int c[3];
+    vi.split((unsigned)at, c);
+    float f;
+    int pix;
+    if (!tsdf_sample(a.fr, c[0], c[1], c[2], a.depth, &f, &pix)) continue;  // (nothing of the volume read or written)
+    const int w = a.weight[at];
+    a.tsdf[at] = tsdf_blend(a.tsdf[at], w, f);
+    if (a.intensity) a.intensity[at] = tsdf_blend(a.intensity[at], w, a.intensity_image[pix]);
+    a.weight[at] = (uint16_t)(w + 1 < a.fr.max_weight ? w + 1 : a.fr.max_weight);
+    written += 1;
+  }
+  __shared__ int lds4[4];
+  const int total = block_sum(written, lds4);
+  if (threadIdx.x == 0) a.slots[blockIdx.x] = total;
+}
+
+// out[0] = the sum of the nslots block slots (one workgroup)
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_sum_slots_kernel(const int* __restrict__ slots, int nslots,
+                                                                       long long* __restrict__ out) {
+  int v = 0;
+  for (int i = threadIdx.x; i < nslots; i += TSDF_THREADS) v += slots[i];
+  __shared__ int lds4[4];
+  const int total = block_sum(v, lds4);
+  if (threadIdx.x == 0) out[0] = total;
+}
+
+// the statuses of voxel `at`'s three crossings (TSDF_NO_CROSSING where the voxel itself is below min_weight)
+__device__ __forceinline__ void crossing_statuses(const TsdfPlanes& v, const VoxelIndex& vi, long long at, bool valid,
+                                                  int c[3], float& fv, int st[3]) {
+  st[0] = st[1] = st[2] = TSDF_NO_CROSSING;
+  if (!valid || (int)v.weight[at] < v.min_weight) return;
+  vi.split((unsigned)at, c);
+  fv = v.tsdf[at];
+#pragma unroll
+  for (int axis = 0; axis < 3; ++axis) st[axis] = tsdf_crossing(v, c, at, fv, axis, nullptr);
+}
+
+// pass 1: per chunk, the crossings that will be listed and those dropped for want of a normal
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_count_kernel(const TsdfExtractArgs a) {
+  const long long begin = (long long)blockIdx.x * a.chunk;
+  const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
+  const VoxelIndex vi{(unsigned)a.v.dims[0], (unsigned)a.v.dims[0] * (unsigned)a.v.dims[1]};
+  int listed = 0, dropped = 0;
+  for (long long base = begin; base < end; base += TSDF_THREADS) {
+    const long long at = base + threadIdx.x;
+    int c[3] = {0, 0, 0}, st[3];
+    float fv = 0.f;
+    crossing_statuses(a.v, vi, at, at < end, c, fv, st);
+#pragma unroll
+    for (int axis = 0; axis < 3; ++axis) {
+      listed += st[axis] == TSDF_CROSSING;
+      dropped += st[axis] == TSDF_NO_NORMAL;
+    }
+  }
+  __shared__ int lds4[2][4];
+  const int nl = block_sum(listed, lds4[0]);
+  const int nd = block_sum(dropped, lds4[1]);
+  if (threadIdx.x == 0) {
+    a.counts[blockIdx.x] = nl;
+    a.dropped[blockIdx.x] = nd;
+  }
+}
+
+// pass 2 (one workgroup; the shape of K4's bp_scan_body): offsets[b] = the crossings listed by the chunks before b,
+// offsets[nblocks] = totals[0] = their number; totals[1] = the sum of the dropped ones.  64-bit: 3 x 2^30 crossings
+// do not fit an int
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_scan_kernel(const int* __restrict__ counts,
+                                                                  const int* __restrict__ dropped, int nblocks,
+                                                                  long long* __restrict__ offsets,
+                                                                  long long* __restrict__ totals) {
+  __shared__ long long carry;
+  __shared__ int wsum[4];
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  long long nd = 0;
+  for (int base = 0; base < nblocks; base += TSDF_THREADS) {
+    const int i = base + threadIdx.x;
+    const int v = i < nblocks ? counts[i] : 0;
+    nd += i < nblocks ? dropped[i] : 0;
+    int incl = v;  // wave64 inclusive scan (a round sums 256 chunks of at most 3 x 2^17 crossings each: below 2^31)
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64);
+      if ((threadIdx.x & 63) >= d) incl += up;
+    }
+    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    int woff = 0;
+    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
+    const long long c = carry;
+    if (i < nblocks) offsets[i] = c + woff + incl - v;
+    __syncthreads();
+    if (threadIdx.x == TSDF_THREADS - 1) carry = c + woff + incl;
+    __syncthreads();
+  }
+  // the dropped ones: a 64-bit sum over the workgroup through LDS
+  __shared__ long long dsum[TSDF_THREADS];
+  dsum[threadIdx.x] = nd;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long long t = 0;
+    for (int i = 0; i < TSDF_THREADS; ++i) t += dsum[i];
+    offsets[nblocks] = carry;
+    totals[0] = carry;
+    totals[1] = t;
+  }
+}
+
+// pass 3: the chunk's crossings again, each to its place: the chunk's offset, then voxel order, then axis order
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_scatter_kernel(const TsdfExtractArgs a) {
+  const long long begin = (long long)blockIdx.x * a.chunk;
+  const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
+  const VoxelIndex vi{(unsigned)a.v.dims[0], (unsigned)a.v.dims[0] * (unsigned)a.v.dims[1]};
+  if (a.offsets[blockIdx.x + 1] == a.offsets[blockIdx.x]) return;  // (uniform: nothing of this chunk is listed)
+  __shared__ int wsum[4];
+  long long run = a.offsets[blockIdx.x];
+  for (long long base = begin; base < end; base += TSDF_THREADS) {
+    const long long at = base + threadIdx.x;
+    int c[3] = {0, 0, 0}, st[3];
+    float fv = 0.f;
+    crossing_statuses(a.v, vi, at, at < end, c, fv, st);
+    const int mine = (st[0] == TSDF_CROSSING) + (st[1] == TSDF_CROSSING) + (st[2] == TSDF_CROSSING);
+    int incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64);
+      if ((threadIdx.x & 63) >= d) incl += up;
+    }
+    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    int woff = 0;
+    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
+    const int round_total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    long long pos = run + woff + incl - mine;
+    for (int axis = 0; axis < 3; ++axis) {
+      if (st[axis] != TSDF_CROSSING) continue;
+      TsdfCrossing cr;
+      tsdf_crossing(a.v, c, at, fv, axis, &cr);  // (again, now with its outputs: crossings are few)
+      if (pos < a.capacity) {                    // (always: the capacity is the scan's total)
+        a.x[pos] = cr.p[0], a.y[pos] = cr.p[1], a.z[pos] = cr.p[2];
+        a.nx[pos] = cr.n[0], a.ny[pos] = cr.n[1], a.nz[pos] = cr.n[2];
+        a.intensity[pos] = cr.intensity;
+        a.voxel_index[pos] = (int)at;
+        a.axis[pos] = (uint8_t)axis;
+      }
+      pos += 1;
+    }
+    run += round_total;
+    __syncthreads();  // (wsum is rewritten by the next round)
+  }
+}
+
+void launch_tsdf_integrate(const TsdfIntegrateArgs& a, int nblocks, long long* n_updated, hipStream_t s) {
+  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+  hipLaunchKernelGGL(tsdf_sum_slots_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.slots, nblocks, n_updated);
+}
+
+void launch_tsdf_count(const TsdfExtractArgs& a, int nblocks, long long* totals, hipStream_t s) {
+  hipLaunchKernelGGL(tsdf_count_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.counts, a.dropped, nblocks, a.offsets, totals);
+}
+
+void launch_tsdf_scatter(const TsdfExtractArgs& a, int nblocks, hipStream_t s) {
+  hipLaunchKernelGGL(tsdf_scatter_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+}
+
+}  // namespace icpk

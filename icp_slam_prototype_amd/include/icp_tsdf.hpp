@@ -1,0 +1,88 @@
+// icp_tsdf.hpp -- C++ host side of the TSDF volume (icpk_tsdf_* of include/icpk.h, K19).  Include it next to
+// icp_align.hpp.
+//
+//   * icp::TsdfVolume -- the dense volume of truncated signed distances an Engine's context owns: posed depth frames
+//                        are fused into it on the GPU (integrate), the surface comes back as points with normals
+//                        (surface) or becomes the Engine's target for scan-to-model alignment (toTarget).  An Engine
+//                        holds one volume: constructing another replaces it.
+#pragma once
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "icp_align.hpp"
+
+namespace icp {
+
+// the surface list of one extraction: structure of arrays, ordered by voxel, then axis
+struct TsdfSurface {
+  std::vector<float> x, y, z, nx, ny, nz, intensity;
+  std::vector<int32_t> voxel;  // linear index of the voxel the crossing starts at
+  std::vector<uint8_t> axis;   // 0, 1, 2: towards its +1 neighbour along x, y, z
+  int32_t noNormal = 0;        // crossings not listed: an end without a gradient
+  size_t size() const { return x.size(); }
+};
+
+class TsdfVolume {
+ public:
+  static icpk_tsdf_params defaults() {
+    icpk_tsdf_params p;
+    icpk_default_tsdf_params(&p);
+    return p;
+  }
+  // fx, cx: the depth camera's intrinsics (cx and fx serve both axes, as in Engine::backproject).  Throws
+  // std::runtime_error when the parameters are refused or the memory is not there
+  TsdfVolume(Engine& eng, const icpk_tsdf_params& p, float fx, float cx) : eng_(eng), p_(p), fx_(fx), cx_(cx) {
+    const int rc = icpk_tsdf_create(eng_.ctx(), &p_);
+    if (rc != ICPK_OK) throw std::runtime_error("icpk_tsdf_create failed (status " + std::to_string(rc) + "): " + eng_.last_error());
+  }
+  TsdfVolume(const TsdfVolume&) = delete;
+  TsdfVolume& operator=(const TsdfVolume&) = delete;
+  ~TsdfVolume() { icpk_tsdf_release(eng_.ctx()); }
+
+  const icpk_tsdf_params& params() const { return p_; }
+  size_t voxels() const { return (size_t)p_.dims[0] * p_.dims[1] * p_.dims[2]; }
+
+  // one rows x cols frame at the camera-to-world pose (16 doubles, row-major); intensity: rows x cols floats on a colour
+  // volume, else null.  nUpdated (optional): the voxels written.  Returns a status of icpk.h
+  int integrate(const uint16_t* depth, int rows, int cols, const double* pose, const float* intensity = nullptr,
+                int32_t* nUpdated = nullptr) {
+    return icpk_tsdf_integrate(eng_.ctx(), depth, intensity, rows, cols, fx_, cx_, pose, nUpdated);
+  }
+  // the frame Engine's backproject_pair path has just left on the device, without a second upload
+  int integrateResident(int rows, int cols, const double* pose, const float* intensity = nullptr, int32_t* nUpdated = nullptr) {
+    return icpk_tsdf_integrate(eng_.ctx(), nullptr, intensity, rows, cols, fx_, cx_, pose, nUpdated);
+  }
+  // frames and their poses (16 doubles each), e.g. PoseGraph::poses()
+  int integrateAll(const std::vector<const uint16_t*>& depths, int rows, int cols, const std::vector<double>& poses) {
+    if (poses.size() != 16 * depths.size()) return ICPK_E_ARG;
+    for (size_t k = 0; k < depths.size(); ++k)
+      if (int rc = integrate(depths[k], rows, cols, poses.data() + 16 * k)) return rc;
+    return ICPK_OK;
+  }
+  // the zero crossings between voxels of weight >= minWeight; the list also stays on the device for toTarget()
+  int surface(TsdfSurface& s, int minWeight = 1) {
+    int32_t n = 0;
+    int rc = icpk_tsdf_extract_surface(eng_.ctx(), minWeight, &n, &s.noNormal);
+    if (rc) return rc;
+    for (std::vector<float>* v : {&s.x, &s.y, &s.z, &s.nx, &s.ny, &s.nz, &s.intensity}) v->assign((size_t)n, 0.f);
+    s.voxel.assign((size_t)n, 0);
+    s.axis.assign((size_t)n, 0);
+    return icpk_tsdf_get_surface(eng_.ctx(), s.x.data(), s.y.data(), s.z.data(), s.nx.data(), s.ny.data(), s.nz.data(),
+                                 s.intensity.data(), s.voxel.data(), s.axis.data());
+  }
+  // the last extraction's list becomes the Engine's target, with its normals (and colours): device to device.
+  // ICPK_E_EMPTY_TARGET (the target stays) when the list is empty
+  int toTarget() { return icpk_tsdf_surface_to_target(eng_.ctx()); }
+  // the planes, voxels() entries each, x fastest; any pointer may be null
+  int planes(float* tsdf, uint16_t* weight, float* intensity = nullptr) { return icpk_tsdf_get(eng_.ctx(), tsdf, weight, intensity); }
+  int reset() { return icpk_tsdf_reset(eng_.ctx()); }
+
+ private:
+  Engine& eng_;
+  icpk_tsdf_params p_;
+  float fx_, cx_;
+};
+
+}  // namespace icp

@@ -1233,6 +1233,99 @@ int icpk_pose_graph_evaluate(icpk_ctx *ctx, int32_t n_nodes, const double *poses
 int icpk_get_pose_graph_trace(icpk_ctx *ctx, int32_t *n_iter, double *cost_out, double *lambda_out,
                               int32_t *pcg_iterations_out, int32_t *accepted_out);
 
+/* ---- TSDF volume (extension, K19) ---------------------------------------------------------------------------------
+ * What the poses of K18 are for: the posed depth frames fused into one model.  One dense volume of truncated signed
+ * distances per context, owned by it like the map: created by icpk_tsdf_create, released by icpk_tsdf_release or
+ * icpk_destroy, and touched by no other call.  Every voxel is owned by one thread: no atomic, the same bytes on every
+ * run and on every context.
+ *
+ * THE PER-VOXEL RULE (icpk_tsdf_integrate; float32, every operation rounded once, in the order written; no fused
+ * multiply-add, correctly rounded division, no libm).  Voxel (i, j, k), linear index i + dims[0] (j + dims[1] k):
+ *   1. centre   p_a = fl(fl((float)i_a + 0.5f) * voxel) + origin_a for the three axes.
+ *   2. camera   q_r = fl(fl(fl(R_r0 p_x + R_r1 p_y) + R_r2 p_z) + t_r) for the three rows of the INVERTED pose.  The
+ *               pose is double[16], row-major, camera-to-world [R | t] (icpk_pose_graph_optimize's layout); the library
+ *               inverts it on the host in double, R' = R^T and t'_r = -((R_0r t_0 + R_1r t_1) + R_2r t_2), and rounds
+ *               the twelve numbers to float once (icpk_tsdf_invert_pose).
+ *   3. q_z <= 0 (or NaN) leaves the voxel alone.
+ *   4. pixel    u = fl(fl(q_x fx) / q_z) + cx,  v = fl(fl(q_y fx) / q_z) + cx: cx and fx serve both axes, as in
+ *               icpk_backproject (pointcloud.cpp:37-39), so that a back-projected pixel projects onto itself.
+ *   5. col = floor(u + 0.5f), row = floor(v + 0.5f); outside [0, cols) x [0, rows), or depth d == 0 there: alone.
+ *   6. sdf = fl((float)d / depth_scale) - q_z;  sdf < -trunc: alone.
+ *   7. f = min(1, sdf / trunc).
+ *   8. tsdf <- fl(fl(fl(tsdf * (float)w) + f) / fl((float)w + 1)), w the voxel's weight before the frame.
+ *   9. with ICPK_TSDF_COLOR the voxel's intensity takes the pixel's intensity the same way.
+ *  10. w <- min(w + 1, max_weight).
+ *  11. n_updated = the number of voxels written (an integer count).
+ * A fresh or reset volume holds tsdf = 0, w = 0, intensity = 0 everywhere.  A voxel is computed from its own indices.
+ *
+ * THE SURFACE RULE (icpk_tsdf_extract_surface).  For every voxel V with w >= min_weight (min_weight >= 1), in ascending
+ * linear index, and for its +1 neighbour N along x, then y, then z, where N is in bounds and has w >= min_weight too:
+ *   crossing   iff (f_V < 0) != (f_N < 0);  t = f_V / (f_V - f_N).
+ *   point      V's centre (rule 1), plus fl(t * voxel) along the axis.
+ *   intensity  I_V + fl(t * fl(I_N - I_V)) on a colour volume, else 0.
+ *   gradient   of a voxel: g_a = tsdf(+1 along a) - tsdf(-1 along a), a = x, y, z (not scaled: only its direction is
+ *              used); defined only where all six neighbours are in bounds with w >= min_weight.
+ *   normal     m_a = g_V,a + fl(t * fl(g_N,a - g_V,a));  len = sqrt(fl(fl(m_x m_x + m_y m_y) + m_z m_z));  n = m / len
+ *              (correctly rounded sqrt and division).  It points towards positive distance: towards the cameras.
+ *   A crossing one of whose ends lacks a gradient, or with len == 0, is not listed and counted in n_no_normal.
+ *   order      ascending linear voxel index, then axis: fixed by a count pass, a scan of the chunk counts and a scatter.
+ * The list stays on the device until the next extraction, icpk_tsdf_create, _reset or _release.
+ *
+ * icpk_tsdf_create   ICPK_E_ARG for a dim < 1, more than ICPK_TSDF_MAX_VOXELS voxels, a voxel, trunc or depth_scale
+ *     that is not finite and > 0, a non-finite origin, max_weight outside 1 .. 65535 or an unknown flag; the volume the
+ *     context held stays then.  Otherwise it replaces that volume.  params NULL: icpk_default_tsdf_params.
+ * icpk_tsdf_reset    the volume back to its fresh state (ICPK_E_NOT_SET without one); icpk_tsdf_release frees it (fine
+ *     without one).
+ * icpk_tsdf_integrate   depth: rows x cols host uint16, or NULL: the frame icpk_backproject_pair left resident on this
+ *     context -- its filtered copy when the filter was on -- and ICPK_E_NOT_SET when there is none of this size.
+ *     intensity: rows x cols host floats, finite and in [0, 1]; ICPK_E_ARG when given on a volume without
+ *     ICPK_TSDF_COLOR, missing on one with it, or out of range.  ICPK_E_ARG also for a non-finite pose, fx that is not
+ *     finite and > 0, a non-finite cx, rows or cols < 1 or more than 2^28 pixels.  ICPK_E_NOT_SET without a volume.
+ *     n_updated may be NULL; with the resident frame, no intensity and n_updated == NULL the call does not wait.
+ * icpk_tsdf_get      the planes as float32 / uint16 / float32 (the last: ICPK_E_ARG on a volume without colour), each
+ *     of dims[0] dims[1] dims[2] entries; any pointer may be NULL.
+ * icpk_tsdf_extract_surface   ICPK_E_ARG for min_weight outside 1 .. 65535, or when more than ICPK_TSDF_MAX_SURFACE
+ *     crossings would be listed.  One host wait (the counts).  Either output may be NULL; n_no_normal stops at INT32_MAX.
+ * icpk_tsdf_get_surface   the list of the last extraction (ICPK_E_NOT_SET before it): arrays of n_points entries, any
+ *     may be NULL.  voxel_index: V's linear index; axis: 0, 1, 2.
+ * icpk_tsdf_surface_to_target   the list becomes the context's target, its normals the target's normals and, on a colour
+ *     volume, its intensities the target's colours: device-to-device, as icpk_map_list_to_target hands a list over,
+ *     and everything a new target invalidates is invalidated the same way.  An empty list: ICPK_E_EMPTY_TARGET and the
+ *     target stays.  ICPK_E_NOT_SET before the first extraction.
+ * icpk_tsdf_voxel_update   host only, no context: rules 1 - 10 for the `count` voxels from linear index `first`, given
+ *     the inverted float pose (R, t), the image and the voxels' state (tsdf, weight, intensity_value: arrays of `count`
+ *     entries, in and out; intensity and intensity_value both NULL without colour).  Compiled from the header the
+ *     kernel includes (csrc/tsdf_rule.h).  Returns the number of voxels written, or ICPK_E_ARG.
+ * Integration and extraction read and write nothing else the context holds. */
+#define ICPK_TSDF_COLOR 1 /* flags of icpk_tsdf_params: one intensity per voxel */
+#define ICPK_TSDF_MAX_VOXELS (1 << 30)
+#define ICPK_TSDF_MAX_SURFACE (1 << 28)
+typedef struct icpk_tsdf_params {
+  int32_t dims[3];   /* voxels, x fastest (256, 256, 256) */
+  float voxel;       /* metres (0.02) */
+  float origin[3];   /* world position of the corner of voxel (0, 0, 0) (-2.56, -2.56, 0) */
+  float trunc;       /* metres (0.08) */
+  int32_t max_weight; /* 1 .. 65535 (255) */
+  float depth_scale; /* ICPK_DEPTH_SCALE */
+  int32_t flags;     /* 0 */
+} icpk_tsdf_params;
+void icpk_default_tsdf_params(icpk_tsdf_params *p);
+int icpk_tsdf_create(icpk_ctx *ctx, const icpk_tsdf_params *params);
+int icpk_tsdf_reset(icpk_ctx *ctx);
+int icpk_tsdf_release(icpk_ctx *ctx);
+int icpk_tsdf_integrate(icpk_ctx *ctx, const uint16_t *depth, const float *intensity, int32_t rows, int32_t cols,
+                        float fx, float cx, const double pose[16], int32_t *n_updated);
+int icpk_tsdf_get(icpk_ctx *ctx, float *tsdf, uint16_t *weight, float *intensity);
+int icpk_tsdf_extract_surface(icpk_ctx *ctx, int32_t min_weight, int32_t *n_points, int32_t *n_no_normal);
+int icpk_tsdf_get_surface(icpk_ctx *ctx, float *x, float *y, float *z, float *nx, float *ny, float *nz,
+                          float *intensity, int32_t *voxel_index, uint8_t *axis);
+int icpk_tsdf_surface_to_target(icpk_ctx *ctx);
+/* host only: the inverse of a camera-to-world pose as rule 2 takes it; ICPK_E_ARG for a non-finite pose */
+int icpk_tsdf_invert_pose(const double pose[16], float R[9], float t[3]);
+int icpk_tsdf_voxel_update(const icpk_tsdf_params *params, const float R[9], const float t[3], const uint16_t *depth,
+                           const float *intensity, int32_t rows, int32_t cols, float fx, float cx, int64_t first,
+                           int32_t count, float *tsdf, uint16_t *weight, float *intensity_value);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
