@@ -24,6 +24,7 @@ PG_PRUNE = 1  # icpk_pg_params.flags: drop the uncertain edges the line process 
 PG_MAX_NODES, PG_MAX_EDGES = 1 << 20, 1 << 22
 TSDF_COLOR = 1  # icpk_tsdf_params.flags: one intensity per voxel
 TSDF_MAX_VOXELS, TSDF_MAX_SURFACE = 1 << 30, 1 << 28
+TSDF_MAX_RAY_SAMPLES, TSDF_MAX_RAYCAST_PIXELS = 4096, 1 << 21
 DEPTH_SCALE = 5000.0  # pointcloud.cpp:37
 MAX_NN_KEYPOINT_DISTANCE = 0.1  # icp.hpp:10
 NORMALS_CROSS, NORMALS_REFERENCE = 0, 1
@@ -84,6 +85,8 @@ SYMBOLS = [
     "icpk_default_tsdf_params", "icpk_tsdf_create", "icpk_tsdf_reset", "icpk_tsdf_release", "icpk_tsdf_integrate",
     "icpk_tsdf_get", "icpk_tsdf_extract_surface", "icpk_tsdf_get_surface", "icpk_tsdf_surface_to_target",
     "icpk_tsdf_invert_pose", "icpk_tsdf_voxel_update",
+    "icpk_default_tsdf_raycast_params", "icpk_tsdf_raycast", "icpk_tsdf_get_raycast", "icpk_tsdf_raycast_to_target",
+    "icpk_tsdf_raycast_pixels",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -180,6 +183,12 @@ class TsdfParams(C.Structure):
     """icpk_tsdf_params"""
     _fields_ = [("dims", C.c_int32 * 3), ("voxel", C.c_float), ("origin", C.c_float * 3), ("trunc", C.c_float),
                 ("max_weight", C.c_int32), ("depth_scale", C.c_float), ("flags", C.c_int32)]
+
+
+class TsdfRaycastParams(C.Structure):
+    """icpk_tsdf_raycast_params"""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("fx", C.c_float), ("cx", C.c_float), ("z_near", C.c_float),
+                ("z_far", C.c_float), ("step", C.c_float), ("min_weight", C.c_int32)]
 
 
 class FrameJob(C.Structure):
@@ -401,6 +410,13 @@ def load():
     lib.icpk_tsdf_invert_pose.argtypes = [dp, fp, fp]
     lib.icpk_tsdf_voxel_update.argtypes = [C.POINTER(TsdfParams), fp, fp, u16, fp, C.c_int32, C.c_int32, C.c_float,
                                            C.c_float, C.c_int64, C.c_int32, fp, u16, fp]
+    lib.icpk_default_tsdf_raycast_params.argtypes = [C.POINTER(TsdfRaycastParams)]
+    lib.icpk_default_tsdf_raycast_params.restype = None
+    lib.icpk_tsdf_raycast.argtypes = [C.c_void_p, C.POINTER(TsdfRaycastParams), dp, ip, ip]
+    lib.icpk_tsdf_get_raycast.argtypes = [C.c_void_p, fp, fp, fp, fp, fp, fp, fp, fp]
+    lib.icpk_tsdf_raycast_to_target.argtypes = [C.c_void_p]
+    lib.icpk_tsdf_raycast_pixels.argtypes = [C.POINTER(TsdfParams), C.POINTER(TsdfRaycastParams), dp, fp, u16, fp,
+                                             C.c_int64, C.c_int32, fp]
     _lib = lib
     return lib
 
@@ -626,6 +642,39 @@ def tsdf_voxel_update(params, R, t, depth, tsdf, weight, intensity=None, intensi
     return rc
 
 
+def tsdf_raycast_params(shape=None, fx=None, cx=None, z_near=None, z_far=None, step=None, min_weight=None):
+    """icpk_default_tsdf_raycast_params with the given fields replaced; shape = (rows, cols)."""
+    p = TsdfRaycastParams()
+    load().icpk_default_tsdf_raycast_params(C.byref(p))
+    if shape is not None:
+        p.rows, p.cols = int(shape[0]), int(shape[1])
+    for k, v in (("fx", fx), ("cx", cx), ("z_near", z_near), ("z_far", z_far), ("step", step), ("min_weight", min_weight)):
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def tsdf_raycast_pixels(params, ray, pose, tsdf, weight, intensity=None, first=0, count=None):
+    """icpk_tsdf_raycast_pixels (host only): the ray rule for `count` pixels from row-major pixel `first` (default: all
+    from there on) over the host planes tsdf float32, weight uint16 (and intensity float32 on a TSDF_COLOR volume).
+    params: TsdfParams, ray: TsdfRaycastParams.  Returns (maps (8, count) float32: x, y, z, nx, ny, nz, depth, intensity;
+    the number of listed hits)."""
+    f, w = _f(tsdf).reshape(-1), np.ascontiguousarray(weight, np.uint16).reshape(-1)
+    ci = None if intensity is None else _f(intensity).reshape(-1)
+    n = params.dims[0] * params.dims[1] * params.dims[2]
+    if f.size != n or w.size != n or (ci is not None and ci.size != n):
+        raise ValueError("the planes must hold one entry per voxel")
+    count = ray.rows * ray.cols - int(first) if count is None else int(count)
+    out = np.zeros((8, max(count, 0)), np.float32)
+    P = np.ascontiguousarray(pose, np.float64).reshape(16)
+    rc = load().icpk_tsdf_raycast_pixels(C.byref(params), C.byref(ray), P.ctypes.data_as(C.POINTER(C.c_double)), _fp(f),
+                                         w.ctypes.data_as(C.POINTER(C.c_uint16)), None if ci is None else _fp(ci),
+                                         int(first), count, _fp(out))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_tsdf_raycast_pixels")
+    return out, rc
+
+
 def global_hypotheses(matches, src, tgt, seed, edge_similarity=0.9, h0=0, count=1):
     """icpk_global_hypotheses (host only): hypotheses h0 .. h0 + count - 1 of icpk_register_global's draw over `matches`
     ((src_index, tgt_index) int arrays) and the clouds src, tgt ((3, n) float32).  Returns (samples (count, 3) int32,
@@ -662,6 +711,7 @@ class Context:
         self._pinned = {}  # register_host_buffer: address -> the array, alive while the library may read it
         self._tsdf = None    # the TsdfParams of the volume the context holds (tsdf_create) ...
         self._tsdf_n = None  # ... and the length of its surface list (tsdf_extract_surface)
+        self._tsdf_ray = None  # ... and the (rows, cols) of its last ray cast (tsdf_raycast)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1261,16 +1311,16 @@ class Context:
         of tsdf_params as keywords.  Returns the TsdfParams in force."""
         p = params if params is not None else tsdf_params(**kw)
         self._chk(self._lib.icpk_tsdf_create(self._h, C.byref(p)))
-        self._tsdf, self._tsdf_n = p, None
+        self._tsdf, self._tsdf_n, self._tsdf_ray = p, None, None
         return p
 
     def tsdf_reset(self):
         self._chk(self._lib.icpk_tsdf_reset(self._h))
-        self._tsdf_n = None
+        self._tsdf_n = self._tsdf_ray = None
 
     def tsdf_release(self):
         self._chk(self._lib.icpk_tsdf_release(self._h))
-        self._tsdf, self._tsdf_n = None, None
+        self._tsdf, self._tsdf_n, self._tsdf_ray = None, None, None
 
     def tsdf_integrate(self, depth, pose, intensity=None, fx=468.60, cx=318.27, shape=None, count=True):
         """icpk_tsdf_integrate: one frame into the volume.  depth (rows, cols) uint16, or None: the frame
@@ -1326,6 +1376,35 @@ class Context:
 
     def tsdf_surface_to_target(self):
         self._chk(self._lib.icpk_tsdf_surface_to_target(self._h))
+
+    # -- ray cast of the TSDF volume (K20) -------------------------------------------
+    def tsdf_raycast(self, pose, params=None, count=True, **kw):
+        """icpk_tsdf_raycast: the volume seen from the camera-to-world pose (4, 4) float64, as maps that stay on the
+        device.  params: TsdfRaycastParams, or the fields of tsdf_raycast_params as keywords.  Returns (n_hits,
+        n_no_normal), or None with count=False (the call does not wait then)."""
+        p = params if params is not None else tsdf_raycast_params(**kw)
+        P = np.ascontiguousarray(pose, np.float64).reshape(16)
+        n, m = C.c_int32(-1), C.c_int32(-1)
+        self._chk(self._lib.icpk_tsdf_raycast(self._h, C.byref(p), P.ctypes.data_as(C.POINTER(C.c_double)),
+                                              C.byref(n) if count else None, C.byref(m) if count else None))
+        self._tsdf_ray = (p.rows, p.cols)
+        return (n.value, m.value) if count else None
+
+    def tsdf_get_raycast(self):
+        """icpk_tsdf_get_raycast: dict(points (3, rows, cols), normals (3, rows, cols), depth (rows, cols), intensity
+        (rows, cols)) of the last ray cast; a pixel without a hit holds 0 everywhere.  Without TSDF_COLOR the
+        intensity is not asked for and comes back 0."""
+        if self._tsdf_ray is None:
+            self._chk(self._lib.icpk_tsdf_get_raycast(self._h, *([None] * 8)))  # (ICPK_E_NOT_SET)
+            raise IcpkError(E_NOT_SET, "no ray cast (tsdf_raycast)")
+        rows, cols = self._tsdf_ray
+        maps = np.zeros((8, rows, cols), np.float32)
+        color = self._tsdf is not None and (self._tsdf.flags & TSDF_COLOR)
+        self._chk(self._lib.icpk_tsdf_get_raycast(self._h, *[_fp(maps[k]) for k in range(7)], _fp(maps[7]) if color else None))
+        return dict(points=maps[0:3], normals=maps[3:6], depth=maps[6], intensity=maps[7])
+
+    def tsdf_raycast_to_target(self):
+        self._chk(self._lib.icpk_tsdf_raycast_to_target(self._h))
 
     def align(self, params=None, **kw):
         p = params if params is not None else default_params(**kw)

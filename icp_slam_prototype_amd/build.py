@@ -293,6 +293,24 @@ def build_tsdf_test(force=False):
     return TSDF_TEST
 
 
+TSDF_RAYCAST_TEST = os.path.join(LIBDIR, "test_tsdf_raycast")
+
+
+def build_tsdf_raycast_test(force=False):
+    """Host-only C++ program over icp::TsdfVolume::raycast / getRaycast / raycastToTarget (icp_tsdf.hpp, K20) (g++,
+    links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_tsdf_raycast.cpp")
+    hdrs = [os.path.join(HERE, "include", h) for h in ("icp_align.hpp", "icp_tsdf.hpp")]
+    build()
+    newest = max(os.path.getmtime(p) for p in [src, LIB] + hdrs)
+    if not force and os.path.exists(TSDF_RAYCAST_TEST) and os.path.getmtime(TSDF_RAYCAST_TEST) >= newest:
+        return TSDF_RAYCAST_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", TSDF_RAYCAST_TEST])
+    return TSDF_RAYCAST_TEST
+
+
 THREADS_TEST = os.path.join(LIBDIR, "test_threads")
 
 
@@ -360,4 +378,5 @@ if __name__ == "__main__":
     print(build_fpfh_test(force="--force" in sys.argv))
     print(build_pose_graph_test(force="--force" in sys.argv))
     print(build_tsdf_test(force="--force" in sys.argv))
+    print(build_tsdf_raycast_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

@@ -878,4 +878,39 @@ struct TsdfExtractArgs {
 void launch_tsdf_count(const TsdfExtractArgs& a, int nblocks, long long* totals, hipStream_t s);
 void launch_tsdf_scatter(const TsdfExtractArgs& a, int nblocks, hipStream_t s);
 
+// K20, the ray cast of the volume (the ray rule of tsdf_rule.h).  A workgroup of TSDF_THREADS covers a tile of
+// TSDF_RAY_TILE x TSDF_RAY_TILE pixels, each of its four waves an 8 x 8 quarter; the tiles are dealt out to at most
+// TSDF_MAX_BLOCKS workgroups, so that the counts fit K19's slots
+constexpr int TSDF_RAY_TILE = 16;
+inline int tsdf_ray_tiles(int n) { return (n + TSDF_RAY_TILE - 1) / TSDF_RAY_TILE; }
+inline int tsdf_ray_blocks(int rows, int cols) {
+  const long long t = (long long)tsdf_ray_tiles(rows) * tsdf_ray_tiles(cols);
+  return (int)(t < TSDF_MAX_BLOCKS ? t : TSDF_MAX_BLOCKS);
+}
+struct TsdfRaycastArgs {
+  TsdfPlanes v;
+  TsdfRay r;
+  float* maps;    // 8 planes of rows x cols: x, y, z, nx, ny, nz, depth, intensity
+  int tiles_x;    // tiles per row of tiles
+  int ntiles;
+  int* hits;      // [nblocks] listed hits per workgroup
+  int* dropped;   // [nblocks] crossings without a normal per workgroup
+};
+// the maps; totals[0] = listed hits, totals[1] = crossings without a normal (device)
+void launch_tsdf_raycast(const TsdfRaycastArgs& a, int nblocks, long long* totals, hipStream_t s);
+// the valid pixels of the maps (depth > 0) as a list in row-major pixel order: chunks of TSDF_THREADS consecutive pixels
+struct TsdfRayCompactArgs {
+  const float* maps;
+  int npix;            // <= TSDF_MAX_BLOCKS * TSDF_THREADS
+  int* counts;         // [nblocks] valid pixels per chunk
+  int* dropped;        // [nblocks] zeroed (the scan sums it)
+  long long* offsets;  // [nblocks + 1] the scan of counts
+  long long capacity;  // entries of each of the list's planes
+  float* list;         // 7 planes: x, y, z, nx, ny, nz, intensity
+};
+inline int tsdf_ray_chunks(int npix) { return (npix + TSDF_THREADS - 1) / TSDF_THREADS; }
+// count pass + scan: totals[0] = the valid pixels (device)
+void launch_tsdf_ray_count(const TsdfRayCompactArgs& a, long long* totals, hipStream_t s);
+void launch_tsdf_ray_scatter(const TsdfRayCompactArgs& a, hipStream_t s);
+
 }  // namespace icpk

@@ -1,7 +1,8 @@
-// icpk_tsdf.cpp -- host side of the TSDF volume (K19; kernels_tsdf.hip): the volume a context owns, the refusals, the
-// inversion of the pose, integration of a frame (uploaded, or the one icpk_backproject_pair left resident), extraction
-// of the surface list and its hand-over as the context's target.  The rules are written out in include/icpk.h and
-// stated once, in tsdf_rule.h, for the device and for icpk_tsdf_voxel_update.
+// icpk_tsdf.cpp -- host side of the TSDF volume (K19, K20; kernels_tsdf.hip): the volume a context owns, the refusals,
+// the inversion of the pose, integration of a frame (uploaded, or the one icpk_backproject_pair left resident),
+// extraction of the surface list, the ray cast of the volume into vertex and normal maps, and the hand-over of either
+// as the context's target.  The rules are written out in include/icpk.h and stated once, in tsdf_rule.h, for the device
+// and for icpk_tsdf_voxel_update / icpk_tsdf_raycast_pixels.
 #include <cmath>
 #include <cstring>
 
@@ -30,6 +31,12 @@ struct icpk_tsdf_state {
   bool have_surface = false;
   int surf_n = 0, surf_dropped = 0;
   float* plane(int k) const { return surf + (size_t)k * surf_cap; }
+  // the maps of the last ray cast (K20): 8 planes of ray_rows x ray_cols floats; their valid pixels as a list of 7
+  // planes of ray_list_cap floats, made by icpk_tsdf_raycast_to_target
+  DevBuf<float> ray_maps, ray_list;
+  size_t ray_list_cap = 0;
+  bool have_raycast = false;
+  int ray_rows = 0, ray_cols = 0;
 };
 
 void icpk_tsdf_free(icpk_ctx* ctx) {
@@ -76,6 +83,66 @@ int clear_volume(icpk_ctx* ctx, icpk_tsdf_state* v) {
   ICPK_HIP(ctx, hipMemsetAsync(v->weight, 0, (size_t)v->n * sizeof(uint16_t), ctx->stream));
   if (v->p.flags & ICPK_TSDF_COLOR) ICPK_HIP(ctx, hipMemsetAsync(v->intensity, 0, (size_t)v->n * sizeof(float), ctx->stream));
   v->have_surface = false;
+  v->have_raycast = false;
+  return ICPK_OK;
+}
+
+TsdfPlanes make_planes(const icpk_tsdf_params& p, const float* tsdf, const uint16_t* weight, const float* intensity, int min_weight) {
+  TsdfPlanes v{};
+  v.tsdf = tsdf, v.weight = weight, v.intensity = intensity;
+  for (int k = 0; k < 3; ++k) v.dims[k] = p.dims[k], v.origin[k] = p.origin[k];
+  v.voxel = p.voxel;
+  v.min_weight = min_weight;
+  return v;
+}
+
+// the refusals of a ray cast's own parameters (nullptr: fine), and the camera of the ray rule: rules 0 and 3
+const char* make_ray(const icpk_tsdf_params& p, const icpk_tsdf_raycast_params& rp, const double pose[16], TsdfRay* r) {
+  if (const char* why = check_camera(rp.rows, rp.cols, rp.fx, rp.cx)) return why;
+  if ((int64_t)rp.rows * rp.cols > ICPK_TSDF_MAX_RAYCAST_PIXELS) return "more than ICPK_TSDF_MAX_RAYCAST_PIXELS pixels";
+  if (!pose) return "the pose is NULL";
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(pose[k])) return "the pose is not finite";
+  if (!std::isfinite(rp.z_near) || !std::isfinite(rp.z_far) || !std::isfinite(rp.step)) return "z_near, z_far and step must be finite";
+  if (!(rp.z_near > 0.f) || !(rp.z_far > rp.z_near) || rp.step < 0.f) return "0 < z_near < z_far and step >= 0 expected";
+  if (rp.min_weight < 1 || rp.min_weight > 65535) return "min_weight outside 1 .. 65535";
+  const float step = rp.step == 0.f ? p.trunc * 0.5f : rp.step;
+  if (!(step > 0.f)) return "trunc / 2 is not a step";  // (a denormal trunc)
+  const double n = std::floor(((double)rp.z_far - (double)rp.z_near) / (double)step) + 1.0;
+  if (!(n <= (double)ICPK_TSDF_MAX_RAY_SAMPLES)) return "more than ICPK_TSDF_MAX_RAY_SAMPLES samples per ray";
+  r->rows = rp.rows, r->cols = rp.cols, r->fx = rp.fx, r->cx = rp.cx;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) r->R[3 * i + j] = (float)pose[4 * i + j];
+    r->c[i] = (float)pose[4 * i + 3];
+  }
+  r->z_near = rp.z_near, r->step = step, r->nsamples = (int)n;
+  return nullptr;
+}
+
+// a list of n points with normals and intensities on the device (7 planes: x, y, z, nx, ny, nz, intensity) becomes the
+// context's target
+int list_to_target(icpk_ctx* ctx, const icpk_tsdf_state* v, float* const list[7], int n) {
+  const size_t bytes = (size_t)n * sizeof(float);
+  // (the target first: target_changed drops the normals and the colours the old target had)
+  int rc = set_target_impl(ctx, list[0], list[1], list[2], n, hipMemcpyDeviceToDevice, false);
+  if (!rc) rc = ensure_cloud(ctx, ctx->nrm, n);
+  if (rc) return rc;
+  const Cloud& m = ctx->nrm;
+  float* const planes[3] = {m.x(), m.y(), m.z()};
+  for (int k = 0; k < 3; ++k) {
+    ICPK_HIP(ctx, hipMemcpyAsync(planes[k], list[3 + k], bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    launch_fill_f32(planes[k] + n, m.cap - n, 0.f, ctx->stream);  // (as icpk_set_target_normals pads them)
+  }
+  ICPK_HIP(ctx, hipGetLastError());
+  ctx->have_normals = true;
+  ctx->have_nstats = false;
+  fpfh_dropped(ctx, 1);
+  if (v->p.flags & ICPK_TSDF_COLOR) {
+    if ((rc = ctx->tcol.reserve(ctx, (size_t)n))) return rc;
+    ICPK_HIP(ctx, hipMemcpyAsync(ctx->tcol, list[6], bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->have_tgt_colors = true;
+  }
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ICPK_OK;
 }
 
@@ -287,29 +354,8 @@ int icpk_tsdf_surface_to_target(icpk_ctx* ctx) {
   icpk_tsdf_state* v = ctx->tsdf;
   if (!v || !v->have_surface) return fail(ctx, ICPK_E_NOT_SET, "no surface list (icpk_tsdf_extract_surface)");
   if (v->surf_n == 0) return fail(ctx, ICPK_E_EMPTY_TARGET, "the surface list is empty");
-  const int n = v->surf_n;
-  const size_t bytes = (size_t)n * sizeof(float);
-  // (the target first: target_changed drops the normals and the colours the old target had)
-  int rc = set_target_impl(ctx, v->plane(0), v->plane(1), v->plane(2), n, hipMemcpyDeviceToDevice, false);
-  if (!rc) rc = ensure_cloud(ctx, ctx->nrm, n);
-  if (rc) return rc;
-  const Cloud& m = ctx->nrm;
-  float* const planes[3] = {m.x(), m.y(), m.z()};
-  for (int k = 0; k < 3; ++k) {
-    ICPK_HIP(ctx, hipMemcpyAsync(planes[k], v->plane(3 + k), bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    launch_fill_f32(planes[k] + n, m.cap - n, 0.f, ctx->stream);  // (as icpk_set_target_normals pads them)
-  }
-  ICPK_HIP(ctx, hipGetLastError());
-  ctx->have_normals = true;
-  ctx->have_nstats = false;
-  fpfh_dropped(ctx, 1);
-  if (v->p.flags & ICPK_TSDF_COLOR) {
-    if ((rc = ctx->tcol.reserve(ctx, (size_t)n))) return rc;
-    ICPK_HIP(ctx, hipMemcpyAsync(ctx->tcol, v->plane(6), bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    ctx->have_tgt_colors = true;
-  }
-  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ICPK_OK;
+  float* const list[7] = {v->plane(0), v->plane(1), v->plane(2), v->plane(3), v->plane(4), v->plane(5), v->plane(6)};
+  return list_to_target(ctx, v, list, v->surf_n);
 }
 
 int icpk_tsdf_voxel_update(const icpk_tsdf_params* params, const float R[9], const float t[3], const uint16_t* depth,
@@ -330,6 +376,117 @@ int icpk_tsdf_voxel_update(const icpk_tsdf_params* params, const float R[9], con
     written += tsdf_voxel_update(fr, i, j, k, depth, intensity, &tsdf[e], &weight[e], color ? &intensity_value[e] : nullptr);
   }
   return written;
+}
+
+void icpk_default_tsdf_raycast_params(icpk_tsdf_raycast_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->rows = 480, p->cols = 640;
+  p->fx = 468.60f, p->cx = 318.27f;
+  p->z_near = 0.25f, p->z_far = 6.0f;
+  p->step = 0.f;
+  p->min_weight = 1;
+}
+
+int icpk_tsdf_raycast(icpk_ctx* ctx, const icpk_tsdf_raycast_params* params, const double pose[16], int32_t* n_hits,
+                      int32_t* n_no_normal) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  icpk_tsdf_raycast_params rp;
+  icpk_default_tsdf_raycast_params(&rp);
+  if (params) rp = *params;
+  TsdfRaycastArgs a{};
+  if (const char* why = make_ray(v->p, rp, pose, &a.r)) return fail(ctx, ICPK_E_ARG, why);
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t npix = (size_t)rp.rows * rp.cols;
+  bool grown = false;
+  if (int rc = v->ray_maps.reserve(ctx, 8 * npix, &grown)) {
+    if (grown) v->have_raycast = false;
+    return rc;
+  }
+  v->have_raycast = false;  // (the planes change place with the image's size)
+  a.v = make_planes(v->p, v->tsdf, v->weight, (v->p.flags & ICPK_TSDF_COLOR) ? v->intensity.get() : nullptr, rp.min_weight);
+  a.maps = v->ray_maps;
+  a.tiles_x = tsdf_ray_tiles(rp.cols);
+  a.ntiles = a.tiles_x * tsdf_ray_tiles(rp.rows);
+  a.hits = v->slots, a.dropped = v->dropped;
+  launch_tsdf_raycast(a, tsdf_ray_blocks(rp.rows, rp.cols), v->totals, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  v->ray_rows = rp.rows, v->ray_cols = rp.cols;
+  v->have_raycast = true;
+  if (!n_hits && !n_no_normal) return ICPK_OK;  // (nothing is asked: the call does not wait)
+  ICPK_HIP(ctx, hipMemcpyAsync(v->totals_host, v->totals, 2 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (n_hits) *n_hits = (int32_t)v->totals_host[0];
+  if (n_no_normal) *n_no_normal = (int32_t)v->totals_host[1];
+  return ICPK_OK;
+}
+
+int icpk_tsdf_get_raycast(icpk_ctx* ctx, float* x, float* y, float* z, float* nx, float* ny, float* nz, float* depth,
+                          float* intensity) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v || !v->have_raycast) return fail(ctx, ICPK_E_NOT_SET, "no ray cast (icpk_tsdf_raycast)");
+  if (intensity && !(v->p.flags & ICPK_TSDF_COLOR)) return fail(ctx, ICPK_E_ARG, "the volume keeps no intensities");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t npix = (size_t)v->ray_rows * v->ray_cols;
+  float* const out[8] = {x, y, z, nx, ny, nz, depth, intensity};
+  for (int k = 0; k < 8; ++k)
+    if (out[k])
+      ICPK_HIP(ctx, hipMemcpyAsync(out[k], v->ray_maps + (size_t)k * npix, npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_tsdf_raycast_to_target(icpk_ctx* ctx) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v || !v->have_raycast) return fail(ctx, ICPK_E_NOT_SET, "no ray cast (icpk_tsdf_raycast)");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  TsdfRayCompactArgs a{};
+  a.maps = v->ray_maps;
+  a.npix = v->ray_rows * v->ray_cols;
+  a.counts = v->slots, a.dropped = v->dropped, a.offsets = v->offsets;
+  launch_tsdf_ray_count(a, v->totals, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  // the one host wait: the target is allocated for the count
+  ICPK_HIP(ctx, hipMemcpyAsync(v->totals_host, v->totals, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const long long n = v->totals_host[0];
+  if (n == 0) return fail(ctx, ICPK_E_EMPTY_TARGET, "the ray cast hit nothing");
+  if ((size_t)n > v->ray_list_cap) {
+    v->ray_list_cap = 0;
+    if (int rc = v->ray_list.reserve(ctx, 7 * (size_t)n)) return rc;
+    v->ray_list_cap = (size_t)n;
+  }
+  a.capacity = (long long)v->ray_list_cap;
+  a.list = v->ray_list;
+  launch_tsdf_ray_scatter(a, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  float* list[7];
+  for (int k = 0; k < 7; ++k) list[k] = v->ray_list + (size_t)k * v->ray_list_cap;
+  return list_to_target(ctx, v, list, (int)n);
+}
+
+int icpk_tsdf_raycast_pixels(const icpk_tsdf_params* params, const icpk_tsdf_raycast_params* ray, const double pose[16],
+                             const float* tsdf, const uint16_t* weight, const float* intensity, int64_t first, int32_t count,
+                             float* out) {
+  if (!params || !ray || !tsdf || !weight || !out || count < 0 || first < 0) return ICPK_E_ARG;
+  if (check_params(*params)) return ICPK_E_ARG;
+  if (((params->flags & ICPK_TSDF_COLOR) != 0) != (intensity != nullptr)) return ICPK_E_ARG;
+  TsdfRay r{};
+  if (make_ray(*params, *ray, pose, &r)) return ICPK_E_ARG;
+  if (first + count > (int64_t)r.rows * r.cols) return ICPK_E_ARG;
+  const TsdfPlanes v = make_planes(*params, tsdf, weight, intensity, ray->min_weight);
+  int listed = 0;
+  for (int32_t e = 0; e < count; ++e) {
+    const int64_t pix = first + e;
+    float px[8];
+    listed += tsdf_raycast_pixel(v, r, (int)(pix / r.cols), (int)(pix % r.cols), px) == TSDF_RAY_HIT;
+    for (int k = 0; k < 8; ++k) out[(size_t)k * count + e] = px[k];
+  }
+  return listed;
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
-// kernels_tsdf.hip -- K19: the dense TSDF volume.  Integration of one posed depth frame (one thread per voxel, the rule
-// of tsdf_rule.h from the voxel's own indices) and extraction of the zero crossings as an ordered point list with
+// kernels_tsdf.hip -- K19, K20: the dense TSDF volume.  Integration of one posed depth frame (one thread per voxel, the
+// rule of tsdf_rule.h from the voxel's own indices) and extraction of the zero crossings as an ordered point list with
 // normals (count / scan / scatter, as K4 compacts an image).  A voxel is owned by one thread: no atomic of any kind,
-// the same bytes on every run.
+// the same bytes on every run.  K20 casts one ray per pixel through the volume (the ray rule of tsdf_rule.h) into eight
+// image planes, a pixel owned by one thread, and compacts their valid pixels into a list with K19's scan.
 //
 // Both walks share one geometry: the volume is a line of n = dx dy dz voxels in linear order (x fastest), cut into at
 // most TSDF_MAX_BLOCKS contiguous chunks of a multiple of TSDF_THREADS voxels, one workgroup per chunk, which it
@@ -193,6 +194,68 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_scatter_kernel(const TsdfEx
   }
 }
 
+// ---- K20: the ray cast ----
+// One thread owns one pixel and writes only that pixel's eight words.  A wave is an 8 x 8 quarter of the workgroup's
+// tile, so that neighbouring rays read neighbouring cells; the cell gathers are left to L2 / Infinity Cache.  The march
+// is tsdf_raycast_pixel: a lane whose ray has ended idles until its wave's last ray has.
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_raycast_kernel(const TsdfRaycastArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ty = (wave >> 1) * 8 + (lane >> 3), tx = (wave & 1) * 8 + (lane & 7);
+  const long long npix = (long long)a.r.rows * a.r.cols;
+  int hits = 0, dropped = 0;
+  for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
+    const int row = (t / a.tiles_x) * TSDF_RAY_TILE + ty, col = (t % a.tiles_x) * TSDF_RAY_TILE + tx;
+    if (row >= a.r.rows || col >= a.r.cols) continue;
+    float out[8];
+    const int st = tsdf_raycast_pixel(a.v, a.r, row, col, out);
+    const long long pix = (long long)row * a.r.cols + col;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a.maps[k * npix + pix] = out[k];
+    hits += st == TSDF_RAY_HIT;
+    dropped += st == TSDF_RAY_NO_NORMAL;
+  }
+  __shared__ int lds4[2][4];
+  const int nh = block_sum(hits, lds4[0]);
+  const int nd = block_sum(dropped, lds4[1]);
+  if (threadIdx.x == 0) {
+    a.hits[blockIdx.x] = nh;
+    a.dropped[blockIdx.x] = nd;
+  }
+}
+
+// the hand-over's pass 1: the valid pixels of chunk blockIdx.x
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_ray_count_kernel(const TsdfRayCompactArgs a) {
+  const int pix = blockIdx.x * TSDF_THREADS + threadIdx.x;
+  const int mine = pix < a.npix && a.maps[6LL * a.npix + pix] > 0.f;
+  __shared__ int lds4[4];
+  const int total = block_sum(mine, lds4);
+  if (threadIdx.x == 0) {
+    a.counts[blockIdx.x] = total;
+    a.dropped[blockIdx.x] = 0;
+  }
+}
+
+// pass 3: every valid pixel to its place, the chunk's offset plus its rank among the chunk's valid pixels
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_ray_scatter_kernel(const TsdfRayCompactArgs a) {
+  const int pix = blockIdx.x * TSDF_THREADS + threadIdx.x;
+  const int mine = pix < a.npix && a.maps[6LL * a.npix + pix] > 0.f;
+  __shared__ int wsum[4];
+  int incl = mine;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int up = __shfl_up(incl, d, 64);
+    if ((threadIdx.x & 63) >= d) incl += up;
+  }
+  if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  int woff = 0;
+  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
+  const long long pos = a.offsets[blockIdx.x] + woff + incl - mine;
+  if (!mine || pos >= a.capacity) return;  // (pos < capacity always: the capacity is the scan's total)
+#pragma unroll
+  for (int k = 0; k < 7; ++k) a.list[k * a.capacity + pos] = a.maps[(long long)(k < 6 ? k : 7) * a.npix + pix];
+}
+
 void launch_tsdf_integrate(const TsdfIntegrateArgs& a, int nblocks, long long* n_updated, hipStream_t s) {
   hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
   hipLaunchKernelGGL(tsdf_sum_slots_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.slots, nblocks, n_updated);
@@ -205,6 +268,22 @@ void launch_tsdf_count(const TsdfExtractArgs& a, int nblocks, long long* totals,
 
 void launch_tsdf_scatter(const TsdfExtractArgs& a, int nblocks, hipStream_t s) {
   hipLaunchKernelGGL(tsdf_scatter_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+}
+
+void launch_tsdf_raycast(const TsdfRaycastArgs& a, int nblocks, long long* totals, hipStream_t s) {
+  hipLaunchKernelGGL(tsdf_raycast_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+  hipLaunchKernelGGL(tsdf_sum_slots_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.hits, nblocks, totals);
+  hipLaunchKernelGGL(tsdf_sum_slots_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.dropped, nblocks, totals + 1);
+}
+
+void launch_tsdf_ray_count(const TsdfRayCompactArgs& a, long long* totals, hipStream_t s) {
+  const int nblocks = tsdf_ray_chunks(a.npix);
+  hipLaunchKernelGGL(tsdf_ray_count_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.counts, a.dropped, nblocks, a.offsets, totals);
+}
+
+void launch_tsdf_ray_scatter(const TsdfRayCompactArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(tsdf_ray_scatter_kernel, dim3(tsdf_ray_chunks(a.npix)), dim3(TSDF_THREADS), 0, s, a);
 }
 
 }  // namespace icpk

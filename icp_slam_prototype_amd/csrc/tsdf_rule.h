@@ -1,7 +1,9 @@
-// tsdf_rule.h -- the per-voxel rule and the surface rule of the TSDF volume (K19; include/icpk.h writes both out).
+// tsdf_rule.h -- the per-voxel rule, the surface rule (K19) and the ray rule (K20) of the TSDF volume; include/icpk.h
+// writes all three out.
 // Header-inline and __host__ __device__: kernels_tsdf.hip runs it per voxel on the device, icpk_tsdf.cpp exports it
-// for one voxel on the host (icpk_tsdf_voxel_update), compiled with -ffp-contract=off on both sides.  float32 only,
-// +, -, *, / and sqrt in the order written, no libm: the same bits wherever those five are correctly rounded.
+// for one voxel and for one pixel on the host (icpk_tsdf_voxel_update, icpk_tsdf_raycast_pixels), compiled with
+// -ffp-contract=off on both sides.  float32 only, +, -, *, / and sqrt in the order written, no libm: the same bits
+// wherever those five are correctly rounded.
 #pragma once
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -135,6 +137,140 @@ ICPK_HD int tsdf_crossing(const TsdfPlanes& v, const int c[3], long long at, flo
     out->intensity = v.intensity ? v.intensity[at] + t * (v.intensity[nb] - v.intensity[at]) : 0.f;
   }
   return TSDF_CROSSING;
+}
+
+// ---- the ray rule (K20) ----
+// the camera of one ray cast: camera-to-world, its nine R and three c rounded to float once (rule 0)
+struct TsdfRay {
+  int rows, cols;
+  float fx, cx;
+  float R[9], c[3];
+  float z_near, step;
+  int nsamples;  // N of rule 3
+};
+
+enum { TSDF_RAY_NONE = 0, TSDF_RAY_HIT = 1, TSDF_RAY_NO_NORMAL = 2, TSDF_RAY_BACK_FACE = 3 };
+
+ICPK_HD float tsdf_lerp(float u, float v, float w) { return u + w * (v - u); }
+
+// e[x + 2 y + 4 z]: along x for the four (y, z) pairs, then along y, then along z
+ICPK_HD float tsdf_trilerp(const float e[8], const float w[3]) {
+  const float c00 = tsdf_lerp(e[0], e[1], w[0]), c10 = tsdf_lerp(e[2], e[3], w[0]);
+  const float c01 = tsdf_lerp(e[4], e[5], w[0]), c11 = tsdf_lerp(e[6], e[7], w[0]);
+  return tsdf_lerp(tsdf_lerp(c00, c10, w[1]), tsdf_lerp(c01, c11, w[1]), w[2]);
+}
+
+// the cell of rule 5: its lowest corner, that corner's linear index and the three fractions
+struct TsdfCell {
+  int c[3];
+  long long at;
+  float w[3];
+};
+
+// rule 5's range test; no index is formed before it has passed on all three axes
+ICPK_HD bool tsdf_cell(const TsdfPlanes& v, const float p[3], TsdfCell* cell) {
+  float g[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    g[a] = (p[a] - v.origin[a]) / v.voxel - 0.5f;
+    if (!(g[a] >= 0.f && g[a] < (float)(v.dims[a] - 1))) return false;  // (false for NaN; never true for a dim of 1)
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    cell->c[a] = (int)g[a];  // (0 <= g < dims - 1: the conversion truncates to the floor, and c + 1 is in bounds)
+    cell->w[a] = g[a] - (float)cell->c[a];
+  }
+  cell->at = cell->c[0] + (long long)v.dims[0] * (cell->c[1] + (long long)v.dims[1] * cell->c[2]);
+  return true;
+}
+
+// the linear index of corner e (x + 2 y + 4 z) of a cell
+ICPK_HD long long tsdf_corner(const TsdfPlanes& v, const TsdfCell& cell, int e) {
+  return cell.at + (e & 1) + (long long)v.dims[0] * (((e >> 1) & 1) + (long long)v.dims[1] * (e >> 2));
+}
+
+// whether all eight corners have weight >= min_weight
+ICPK_HD bool tsdf_cell_known(const TsdfPlanes& v, const TsdfCell& cell) {
+  bool known = true;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) known = known && (int)v.weight[tsdf_corner(v, cell, e)] >= v.min_weight;
+  return known;
+}
+
+// SAMPLE(p): false when p is out of range or its cell is not known
+ICPK_HD bool tsdf_sample_point(const TsdfPlanes& v, const float p[3], float* f) {
+  TsdfCell cell;
+  if (!tsdf_cell(v, p, &cell) || !tsdf_cell_known(v, cell)) return false;
+  float e[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) e[k] = v.tsdf[tsdf_corner(v, cell, k)];
+  *f = tsdf_trilerp(e, cell.w);
+  return true;
+}
+
+// rule 8 at p: the normal, and the intensity; false when the crossing is not to be listed
+ICPK_HD bool tsdf_ray_normal(const TsdfPlanes& v, const float p[3], float n[3], float* intensity) {
+  TsdfCell cell;
+  if (!tsdf_cell(v, p, &cell) || !tsdf_cell_known(v, cell)) return false;
+  float gx[8], gy[8], gz[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int c[3] = {cell.c[0] + (e & 1), cell.c[1] + ((e >> 1) & 1), cell.c[2] + (e >> 2)};
+    float g[3];
+    if (!tsdf_gradient(v, c, tsdf_corner(v, cell, e), g)) return false;
+    gx[e] = g[0], gy[e] = g[1], gz[e] = g[2];
+  }
+  const float m[3] = {tsdf_trilerp(gx, cell.w), tsdf_trilerp(gy, cell.w), tsdf_trilerp(gz, cell.w)};
+  const float len = __builtin_sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+  if (!(len > 0.f)) return false;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) n[a] = m[a] / len;
+  *intensity = 0.f;
+  if (v.intensity) {
+    float e[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) e[k] = v.intensity[tsdf_corner(v, cell, k)];
+    *intensity = tsdf_trilerp(e, cell.w);
+  }
+  return true;
+}
+
+// Rules 1 - 8 for pixel (row, col).  out: x, y, z, nx, ny, nz, depth, intensity -- all 0 unless TSDF_RAY_HIT comes back
+ICPK_HD int tsdf_raycast_pixel(const TsdfPlanes& v, const TsdfRay& r, int row, int col, float out[8]) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) out[k] = 0.f;
+  const float a = ((float)col - r.cx) / r.fx, b = ((float)row - r.cx) / r.fx;
+  float d[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) d[k] = (r.R[3 * k] * a + r.R[3 * k + 1] * b) + r.R[3 * k + 2];
+  bool have_prev = false;
+  float f_prev = 0.f, z_prev = 0.f;
+  for (int n = 0; n < r.nsamples; ++n) {
+    const float z = (float)n * r.step + r.z_near;
+    const float p[3] = {r.c[0] + z * d[0], r.c[1] + z * d[1], r.c[2] + z * d[2]};
+    float f;
+    if (!tsdf_sample_point(v, p, &f)) {
+      have_prev = false;
+      continue;
+    }
+    if (have_prev) {
+      if (f_prev < 0.f) {
+        if (!(f < 0.f)) return TSDF_RAY_BACK_FACE;
+      } else if (f < 0.f) {
+        const float t = f_prev / (f_prev - f);
+        const float zs = z_prev + t * (z - z_prev);
+        const float ps[3] = {r.c[0] + zs * d[0], r.c[1] + zs * d[1], r.c[2] + zs * d[2]};
+        float nrm[3], inten;
+        if (!tsdf_ray_normal(v, ps, nrm, &inten)) return TSDF_RAY_NO_NORMAL;
+        out[0] = ps[0], out[1] = ps[1], out[2] = ps[2];
+        out[3] = nrm[0], out[4] = nrm[1], out[5] = nrm[2];
+        out[6] = zs, out[7] = inten;
+        return TSDF_RAY_HIT;
+      }
+    }
+    have_prev = true, f_prev = f, z_prev = z;
+  }
+  return TSDF_RAY_NONE;
 }
 
 }  // namespace icpk

@@ -1,10 +1,11 @@
-// icp_tsdf.hpp -- C++ host side of the TSDF volume (icpk_tsdf_* of include/icpk.h, K19).  Include it next to
+// icp_tsdf.hpp -- C++ host side of the TSDF volume (icpk_tsdf_* of include/icpk.h, K19 and K20).  Include it next to
 // icp_align.hpp.
 //
 //   * icp::TsdfVolume -- the dense volume of truncated signed distances an Engine's context owns: posed depth frames
 //                        are fused into it on the GPU (integrate), the surface comes back as points with normals
 //                        (surface) or becomes the Engine's target for scan-to-model alignment (toTarget).  An Engine
-//                        holds one volume: constructing another replaces it.
+//                        holds one volume: constructing another replaces it.  raycast gives the surface visible from
+//                        one pose as vertex and normal maps (K20); raycastToTarget makes it the Engine's target.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -22,6 +23,14 @@ struct TsdfSurface {
   std::vector<uint8_t> axis;   // 0, 1, 2: towards its +1 neighbour along x, y, z
   int32_t noNormal = 0;        // crossings not listed: an end without a gradient
   size_t size() const { return x.size(); }
+};
+
+// the maps of one ray cast: rows x cols entries each, row-major; a pixel without a hit holds 0 everywhere
+struct TsdfRaycast {
+  int rows = 0, cols = 0;
+  std::vector<float> x, y, z, nx, ny, nz, depth, intensity;
+  int32_t hits = 0;      // pixels that hold a hit (depth > 0)
+  int32_t noNormal = 0;  // crossings not listed: no normal where the ray met the surface
 };
 
 class TsdfVolume {
@@ -75,14 +84,48 @@ class TsdfVolume {
   // the last extraction's list becomes the Engine's target, with its normals (and colours): device to device.
   // ICPK_E_EMPTY_TARGET (the target stays) when the list is empty
   int toTarget() { return icpk_tsdf_surface_to_target(eng_.ctx()); }
+  // the ray cast's parameters with this volume's intrinsics (z_near 0.25, z_far 6, step 0: trunc / 2, min_weight 1)
+  icpk_tsdf_raycast_params raycastDefaults(int rows, int cols) const {
+    icpk_tsdf_raycast_params r;
+    icpk_default_tsdf_raycast_params(&r);
+    r.rows = rows, r.cols = cols, r.fx = fx_, r.cx = cx_;
+    return r;
+  }
+  // the volume seen from the camera-to-world pose (16 doubles, row-major); the maps stay on the device.  nHits,
+  // nNoNormal (optional): the counts -- with both null the call does not wait
+  int raycast(const icpk_tsdf_raycast_params& r, const double* pose, int32_t* nHits = nullptr, int32_t* nNoNormal = nullptr) {
+    const int rc = icpk_tsdf_raycast(eng_.ctx(), &r, pose, nHits, nNoNormal);
+    if (rc == ICPK_OK) rayRows_ = r.rows, rayCols_ = r.cols;
+    return rc;
+  }
+  // the maps of the last ray cast (the intensity plane stays 0 on a volume without colour)
+  int getRaycast(TsdfRaycast& m) {
+    const size_t n = (size_t)rayRows_ * rayCols_;
+    m.rows = rayRows_, m.cols = rayCols_;
+    for (std::vector<float>* v : {&m.x, &m.y, &m.z, &m.nx, &m.ny, &m.nz, &m.depth, &m.intensity}) v->assign(n, 0.f);
+    const bool color = (p_.flags & ICPK_TSDF_COLOR) != 0;
+    const int rc = icpk_tsdf_get_raycast(eng_.ctx(), m.x.data(), m.y.data(), m.z.data(), m.nx.data(), m.ny.data(), m.nz.data(),
+                                         m.depth.data(), color ? m.intensity.data() : nullptr);
+    if (rc) return rc;
+    m.hits = 0;
+    for (float d : m.depth) m.hits += d > 0.f;
+    return ICPK_OK;
+  }
+  // the last ray cast's hits become the Engine's target, with their normals (and colours), in row-major pixel order:
+  // device to device.  ICPK_E_EMPTY_TARGET (the target stays) without a hit
+  int raycastToTarget() { return icpk_tsdf_raycast_to_target(eng_.ctx()); }
   // the planes, voxels() entries each, x fastest; any pointer may be null
   int planes(float* tsdf, uint16_t* weight, float* intensity = nullptr) { return icpk_tsdf_get(eng_.ctx(), tsdf, weight, intensity); }
-  int reset() { return icpk_tsdf_reset(eng_.ctx()); }
+  int reset() {
+    rayRows_ = rayCols_ = 0;
+    return icpk_tsdf_reset(eng_.ctx());
+  }
 
  private:
   Engine& eng_;
   icpk_tsdf_params p_;
   float fx_, cx_;
+  int rayRows_ = 0, rayCols_ = 0;
 };
 
 }  // namespace icp

@@ -6,6 +6,14 @@ depth frames are fused (Context.tsdf_integrate) and from which the surface comes
     vol.integrate_all(depths, graph.poses())   # the optimised poses of posegraph.PoseGraph, camera-to-world
     model = vol.surface(min_weight=2)          # dict(points, normals, intensity, voxel, axis)
     vol.to_target()                            # ... or: the next frame is aligned against the model
+
+The model seen from one pose (K20) -- vertex and normal maps of the visible surface, at the cost of the image and not of
+the model -- and the tracking loop it closes:
+
+    view = vol.raycast(pose, shape=(480, 640))  # dict(points (3, rows, cols), normals, depth, intensity, n_hits, ...)
+    tracker = ModelTracker(vol, pose=first_pose)
+    for depth in frames:
+        pose = tracker.track(depth)             # ray-cast at the last pose, align the frame, integrate it
 """
 import numpy as np
 
@@ -65,6 +73,28 @@ class TsdfVolume:
         self.ctx.tsdf_surface_to_target()
         return self.n_points
 
+    def _ray_params(self, shape, z_near, z_far, step, min_weight):
+        shape = self.shape if shape is None else shape
+        if shape is None:
+            raise ValueError("the image's (rows, cols) is not known: pass shape")
+        return binding.tsdf_raycast_params(shape=shape, fx=self.fx, cx=self.cx, z_near=z_near, z_far=z_far,
+                                           step=0.0 if step is None else step, min_weight=min_weight)
+
+    def raycast(self, pose, shape=None, z_near=0.25, z_far=6.0, step=None, min_weight=1):
+        """The surface visible from the camera-to-world pose (4, 4), one ray per pixel of a (rows, cols) image with the
+        volume's intrinsics (shape default: the last integrated frame's).  step: metres of camera depth between samples
+        (default trunc / 2).  Returns dict(points (3, rows, cols), normals (3, rows, cols), depth, intensity, n_hits,
+        n_no_normal); depth > 0 marks the pixels that hold a hit."""
+        n_hits, n_no_normal = self.ctx.tsdf_raycast(pose, self._ray_params(shape, z_near, z_far, step, min_weight))
+        return dict(self.ctx.tsdf_get_raycast(), n_hits=n_hits, n_no_normal=n_no_normal)
+
+    def raycast_to_target(self, pose, shape=None, z_near=0.25, z_far=6.0, step=None, min_weight=1):
+        """raycast, and its hits become the context's target with their normals (and colours), in row-major pixel
+        order: device to device.  Returns n_hits; raises IcpkError (E_EMPTY_TARGET, the target stays) without any."""
+        n_hits, _ = self.ctx.tsdf_raycast(pose, self._ray_params(shape, z_near, z_far, step, min_weight))
+        self.ctx.tsdf_raycast_to_target()
+        return n_hits
+
     def planes(self, intensity=False):
         """(tsdf, weight, intensity) as (dz, dy, dx) arrays."""
         return self.ctx.tsdf_get(intensity=intensity)
@@ -76,3 +106,39 @@ class TsdfVolume:
 
     def release(self):
         self.ctx.tsdf_release()
+
+
+class ModelTracker:
+    """Frame-to-model tracking over a TsdfVolume: every frame is aligned point-to-plane against the model ray-cast at
+    the last pose, then fused into the model at the pose found.  pose: the first frame's camera-to-world pose; z_near,
+    z_far, step, min_weight: the ray cast's; align_kw: fields of icpk_params for the alignment (max_iterations,
+    max_nn_dist, min_pairs, ...).  Keep max_nn_dist at a voxel or two: the target is the model seen from the LAST pose,
+    so surfaces the new frame sees for the first time have no counterpart in it, and a wide gate pairs them with the
+    view's border, which biases the pose (icpk_params' default, 0.75 m, is meant for frame-to-frame clouds)."""
+
+    def __init__(self, vol, pose=None, z_near=0.25, z_far=6.0, step=None, min_weight=1, **align_kw):
+        self.vol = vol
+        self.pose = np.eye(4) if pose is None else np.array(pose, np.float64).reshape(4, 4)
+        self.ray = dict(z_near=z_near, z_far=z_far, step=step, min_weight=min_weight)
+        self.align_kw = align_kw
+        self.frames = 0
+        self.n_hits = self.stats = None
+
+    def track(self, depth, intensity=None):
+        """One (rows, cols) uint16 frame (with its (rows, cols) intensities on a colour volume).  Returns the frame's
+        camera-to-world pose (4, 4) float64; the first frame takes the initial pose."""
+        vol, ctx = self.vol, self.vol.ctx
+        if self.frames > 0:
+            params = binding.default_params(solve=binding.SOLVE_POINT_TO_PLANE, **self.align_kw)
+            self.n_hits, _ = ctx.tsdf_raycast(self.pose, vol._ray_params(np.shape(depth), **self.ray))
+            if self.n_hits < params.min_pairs:
+                raise RuntimeError(f"the ray cast hit the model in {self.n_hits} pixels, fewer than min_pairs = {params.min_pairs}")
+            ctx.tsdf_raycast_to_target()
+            ctx.backproject(depth, which=0, fx=vol.fx, cx=vol.cx)
+            ctx.transform_source(self.pose[:3, :3], self.pose[:3, 3])
+            ctx.commit_source()
+            T, self.stats, _ = ctx.align(params)
+            self.pose = T.astype(np.float64) @ self.pose
+        vol.integrate(depth, self.pose, intensity)
+        self.frames += 1
+        return self.pose.copy()

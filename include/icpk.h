@@ -1233,7 +1233,7 @@ int icpk_pose_graph_evaluate(icpk_ctx *ctx, int32_t n_nodes, const double *poses
 int icpk_get_pose_graph_trace(icpk_ctx *ctx, int32_t *n_iter, double *cost_out, double *lambda_out,
                               int32_t *pcg_iterations_out, int32_t *accepted_out);
 
-/* ---- TSDF volume (extension, K19) ---------------------------------------------------------------------------------
+/* ---- TSDF volume (extension, K19, K20) ----------------------------------------------------------------------------
  * What the poses of K18 are for: the posed depth frames fused into one model.  One dense volume of truncated signed
  * distances per context, owned by it like the map: created by icpk_tsdf_create, released by icpk_tsdf_release or
  * icpk_destroy, and touched by no other call.  Every voxel is owned by one thread: no atomic, the same bytes on every
@@ -1296,7 +1296,64 @@ int icpk_get_pose_graph_trace(icpk_ctx *ctx, int32_t *n_iter, double *cost_out, 
  *     the inverted float pose (R, t), the image and the voxels' state (tsdf, weight, intensity_value: arrays of `count`
  *     entries, in and out; intensity and intensity_value both NULL without colour).  Compiled from the header the
  *     kernel includes (csrc/tsdf_rule.h).  Returns the number of voxels written, or ICPK_E_ARG.
- * Integration and extraction read and write nothing else the context holds. */
+ * Integration and extraction read and write nothing else the context holds.
+ *
+ * THE RAY RULE (icpk_tsdf_raycast, K20): the surface visible from one pose, as vertex and normal maps of rows x cols
+ * pixels -- the prediction step of frame-to-model tracking.  float32, every operation rounded once, in the order
+ * written; no fused multiply-add, correctly rounded / and sqrt, no libm; a floor is a comparison and a truncating
+ * conversion of a non-negative number.  Pixel (row, col) of a camera with fx, cx (cx and fx serve both axes, rule 4
+ * above):
+ *   0. pose     double[16], row-major, camera-to-world [R | c]; its nine R and three c are rounded to float once.
+ *               Nothing is inverted.
+ *   1. a = fl(fl((float)col - cx) / fx),  b = fl(fl((float)row - cx) / fx).
+ *   2. direction per unit depth  d_r = fl(fl(fl(R_r0 a) + fl(R_r1 b)) + R_r2).  It is not normalised: the ray's
+ *               parameter is the camera-frame depth z.
+ *   3. samples  z_n = fl(fl((float)n step) + z_near), n = 0 .. N - 1, N = floor((z_far - z_near) / step) + 1 computed
+ *               on the host in double from the float parameters.  Nothing is accumulated along the ray.
+ *   4. point    p_r(z) = fl(c_r + fl(z d_r)).
+ *   5. SAMPLE(p)   g_a = fl(fl(fl(p_a - origin_a) / voxel) - 0.5f); in range iff g_a >= 0 && g_a < (float)(dims_a - 1)
+ *               on all three axes (NaN compares false; a volume with a dim of 1 is never in range).  i_a = (int)g_a,
+ *               w_a = fl(g_a - (float)i_a).  KNOWN iff in range and all eight voxels (i_x + {0,1}, i_y + {0,1},
+ *               i_z + {0,1}) have weight >= min_weight.  Its value is the trilinear interpolation of their tsdf with
+ *               lerp(u, v, w) = fl(u + fl(w fl(v - u))): along x for the four (y, z) pairs, then along y, then along z.
+ *   6. march    in ascending n.  An unknown sample forgets the previous one.  Two consecutive known samples with
+ *               !(f_prev < 0) and f_cur < 0 are a crossing (the surface rule's sign convention); with f_prev < 0 and
+ *               !(f_cur < 0) they end the ray without a hit (a back face).  Anything else goes on; a ray that uses up
+ *               its samples has no hit.
+ *   7. hit      t = fl(f_prev / fl(f_prev - f_cur)) (the divisor is > 0), z* = fl(z_prev + fl(t fl(z_cur - z_prev))),
+ *               p* = p(z*).  The bracket is not refined.
+ *   8. normal and intensity at p*: in SAMPLE's cell at p*, the surface rule's gradient at the eight corners (same
+ *               min_weight); m_a = the trilinear lerp of the eight g_a; len = sqrt(fl(fl(m_x m_x + m_y m_y) + m_z m_z));
+ *               n = m / len.  The intensity is the trilinear lerp of the intensity plane, or 0 without colour.  A
+ *               crossing whose cell at p* is out of range or not known, one of whose eight corners lacks a gradient,
+ *               or with len not > 0 is NOT LISTED and counted in n_no_normal; its ray ends there.
+ *   9. output   eight planes of rows x cols floats: x, y, z, nx, ny, nz, depth (= z*), intensity.  A pixel without a
+ *               listed hit holds 0 in all eight; depth > 0 is the validity test (z_near > 0).  Two integer counts:
+ *               n_hits (listed) and n_no_normal.
+ * One thread owns one pixel; the samples sit on the fixed lattice z_n, so the bits do not depend on how the image is
+ * cut into workgroups.  The maps are a snapshot: they stay on the device until the next ray cast, icpk_tsdf_create,
+ * _reset or _release; integration leaves them alone.
+ *
+ * icpk_tsdf_raycast   params NULL: icpk_default_tsdf_raycast_params.  step == 0: trunc / 2.  ICPK_E_NOT_SET without a
+ *     volume.  ICPK_E_ARG for a NULL or non-finite pose; rows or cols < 1, fx that is not finite and > 0, a non-finite
+ *     cx, more than ICPK_TSDF_MAX_RAYCAST_PIXELS pixels; z_near, z_far or step that is not finite; z_near <= 0,
+ *     z_far <= z_near or step < 0; N > ICPK_TSDF_MAX_RAY_SAMPLES; min_weight outside 1 .. 65535.  A refused call leaves
+ *     the maps of the last ray cast, the target and the volume as they were.  Either count may be NULL; with both NULL
+ *     the call does not wait on the host.  It reads the planes and writes only its maps: nothing else the context
+ *     holds is touched, the surface list of icpk_tsdf_extract_surface included.
+ * icpk_tsdf_get_raycast   the eight planes of the last ray cast, rows x cols floats each, any pointer may be NULL.
+ *     ICPK_E_NOT_SET without a volume, before the first ray cast and after icpk_tsdf_create, _reset or _release;
+ *     ICPK_E_ARG when intensity is asked from a volume without colour.
+ * icpk_tsdf_raycast_to_target   the valid pixels of the maps (depth > 0), in row-major pixel order, become the
+ *     context's target, their normals the target's normals and, on a colour volume, their intensities the target's
+ *     colours: exactly what icpk_tsdf_surface_to_target does with its list, device to device.  The order is a function
+ *     of the maps alone (a count per 256 consecutive pixels, a scan, a scatter).  ICPK_E_NOT_SET as for
+ *     icpk_tsdf_get_raycast; no valid pixel: ICPK_E_EMPTY_TARGET and the target stays.
+ * icpk_tsdf_raycast_pixels   host only, no context: rules 0 - 9 for the `count` pixels from row-major pixel `first`,
+ *     over host planes (intensity NULL exactly when params has no ICPK_TSDF_COLOR).  out: 8 planes of `count` floats.
+ *     Compiled from the header the kernel includes (csrc/tsdf_rule.h).  Returns the number of listed hits, or
+ *     ICPK_E_ARG: for what icpk_tsdf_create and icpk_tsdf_raycast refuse, a NULL array, first < 0, count < 0 or
+ *     first + count > rows cols. */
 #define ICPK_TSDF_COLOR 1 /* flags of icpk_tsdf_params: one intensity per voxel */
 #define ICPK_TSDF_MAX_VOXELS (1 << 30)
 #define ICPK_TSDF_MAX_SURFACE (1 << 28)
@@ -1325,6 +1382,24 @@ int icpk_tsdf_invert_pose(const double pose[16], float R[9], float t[3]);
 int icpk_tsdf_voxel_update(const icpk_tsdf_params *params, const float R[9], const float t[3], const uint16_t *depth,
                            const float *intensity, int32_t rows, int32_t cols, float fx, float cx, int64_t first,
                            int32_t count, float *tsdf, uint16_t *weight, float *intensity_value);
+#define ICPK_TSDF_MAX_RAY_SAMPLES 4096
+#define ICPK_TSDF_MAX_RAYCAST_PIXELS (1 << 21)
+typedef struct icpk_tsdf_raycast_params {
+  int32_t rows, cols; /* 480 x 640 */
+  float fx, cx;       /* 468.60, 318.27 */
+  float z_near, z_far; /* metres of camera depth; 0 < z_near < z_far (0.25, 6.0) */
+  float step;         /* metres of camera depth; 0: trunc / 2 (0) */
+  int32_t min_weight; /* 1 .. 65535 (1) */
+} icpk_tsdf_raycast_params;
+void icpk_default_tsdf_raycast_params(icpk_tsdf_raycast_params *p);
+int icpk_tsdf_raycast(icpk_ctx *ctx, const icpk_tsdf_raycast_params *params, const double pose[16], int32_t *n_hits,
+                      int32_t *n_no_normal);
+int icpk_tsdf_get_raycast(icpk_ctx *ctx, float *x, float *y, float *z, float *nx, float *ny, float *nz, float *depth,
+                          float *intensity);
+int icpk_tsdf_raycast_to_target(icpk_ctx *ctx);
+int icpk_tsdf_raycast_pixels(const icpk_tsdf_params *params, const icpk_tsdf_raycast_params *ray, const double pose[16],
+                             const float *tsdf, const uint16_t *weight, const float *intensity, int64_t first,
+                             int32_t count, float *out /* 8 x count */);
 
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
