@@ -87,6 +87,7 @@ SYMBOLS = [
     "icpk_tsdf_invert_pose", "icpk_tsdf_voxel_update",
     "icpk_default_tsdf_raycast_params", "icpk_tsdf_raycast", "icpk_tsdf_get_raycast", "icpk_tsdf_raycast_to_target",
     "icpk_tsdf_raycast_pixels",
+    "icpk_tsdf_extract_mesh", "icpk_tsdf_get_mesh", "icpk_tsdf_set", "icpk_tsdf_mesh_host",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -417,6 +418,11 @@ def load():
     lib.icpk_tsdf_raycast_to_target.argtypes = [C.c_void_p]
     lib.icpk_tsdf_raycast_pixels.argtypes = [C.POINTER(TsdfParams), C.POINTER(TsdfRaycastParams), dp, fp, u16, fp,
                                              C.c_int64, C.c_int32, fp]
+    lib.icpk_tsdf_extract_mesh.argtypes = [C.c_void_p, C.c_int32, ip, ip, ip]
+    lib.icpk_tsdf_get_mesh.argtypes = [C.c_void_p, fp, fp, fp, fp, fp, fp, fp, ip, u8, ip]
+    lib.icpk_tsdf_set.argtypes = [C.c_void_p, fp, u16, fp]
+    lib.icpk_tsdf_mesh_host.argtypes = [C.POINTER(TsdfParams), C.c_int32, fp, u16, fp, C.c_int64, C.c_int64, fp, fp, fp,
+                                        fp, fp, fp, fp, ip, u8, ip, C.POINTER(C.c_int64)]
     _lib = lib
     return lib
 
@@ -675,6 +681,48 @@ def tsdf_raycast_pixels(params, ray, pose, tsdf, weight, intensity=None, first=0
     return out, rc
 
 
+def tsdf_mesh_host(params, tsdf, weight, intensity=None, min_weight=1, cap_vertices=None, cap_triangles=None):
+    """icpk_tsdf_mesh_host (host only): the mesh rule over the host planes tsdf float32, weight uint16 (and intensity
+    float32 on a TSDF_COLOR volume).  Returns dict(vertices (3, n), normals (3, n), intensity (n,), voxel_index (n,)
+    int32, edge (n,) uint8, triangles (m, 3) int32, n_vertices, n_triangles, n_no_normal).  cap_vertices / cap_triangles:
+    the room the arrays are given (default: what a first, counting call asks for); when the mesh does not fit, IcpkError
+    is raised with the counts in its `counts` attribute."""
+    f, w = _f(tsdf).reshape(-1), np.ascontiguousarray(weight, np.uint16).reshape(-1)
+    ci = None if intensity is None else _f(intensity).reshape(-1)
+    n = params.dims[0] * params.dims[1] * params.dims[2]
+    if f.size != n or w.size != n or (ci is not None and ci.size != n):
+        raise ValueError("the planes must hold one entry per voxel")
+    lib = load()
+    counts = np.full(3, -1, np.int64)
+    planes = (_fp(f), w.ctypes.data_as(C.POINTER(C.c_uint16)), None if ci is None else _fp(ci))
+    cp = counts.ctypes.data_as(C.POINTER(C.c_int64))
+
+    def refuse(rc):
+        e = IcpkError(rc, "icpk_tsdf_mesh_host")
+        e.counts = tuple(int(c) for c in counts)
+        raise e
+
+    if cap_vertices is None or cap_triangles is None:
+        lib.icpk_tsdf_mesh_host(C.byref(params), int(min_weight), *planes, 0, 0, *([None] * 10), cp)
+        if counts[0] < 0:
+            refuse(E_ARG)
+        cap_vertices = int(counts[0]) if cap_vertices is None else cap_vertices
+        cap_triangles = int(counts[1]) if cap_triangles is None else cap_triangles
+    nv, nt = max(int(cap_vertices), 1), max(int(cap_triangles), 1)
+    pts, nrm = np.zeros((3, nv), np.float32), np.zeros((3, nv), np.float32)
+    inten, vox, edge = np.zeros(nv, np.float32), np.zeros(nv, np.int32), np.zeros(nv, np.uint8)
+    tri = np.zeros((nt, 3), np.int32)
+    i32 = C.POINTER(C.c_int32)
+    rc = lib.icpk_tsdf_mesh_host(C.byref(params), int(min_weight), *planes, int(cap_vertices), int(cap_triangles),
+                                 _fp(pts[0]), _fp(pts[1]), _fp(pts[2]), _fp(nrm[0]), _fp(nrm[1]), _fp(nrm[2]), _fp(inten),
+                                 vox.ctypes.data_as(i32), edge.ctypes.data_as(C.POINTER(C.c_uint8)), tri.ctypes.data_as(i32), cp)
+    if rc < 0:
+        refuse(rc)
+    n, m = int(counts[0]), int(counts[1])
+    return dict(vertices=pts[:, :n], normals=nrm[:, :n], intensity=inten[:n], voxel_index=vox[:n], edge=edge[:n],
+                triangles=tri[:m], n_vertices=n, n_triangles=m, n_no_normal=int(counts[2]))
+
+
 def global_hypotheses(matches, src, tgt, seed, edge_similarity=0.9, h0=0, count=1):
     """icpk_global_hypotheses (host only): hypotheses h0 .. h0 + count - 1 of icpk_register_global's draw over `matches`
     ((src_index, tgt_index) int arrays) and the clouds src, tgt ((3, n) float32).  Returns (samples (count, 3) int32,
@@ -712,6 +760,7 @@ class Context:
         self._tsdf = None    # the TsdfParams of the volume the context holds (tsdf_create) ...
         self._tsdf_n = None  # ... and the length of its surface list (tsdf_extract_surface)
         self._tsdf_ray = None  # ... and the (rows, cols) of its last ray cast (tsdf_raycast)
+        self._tsdf_mesh = None  # ... and the three counts of its last mesh (tsdf_extract_mesh)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1311,16 +1360,16 @@ class Context:
         of tsdf_params as keywords.  Returns the TsdfParams in force."""
         p = params if params is not None else tsdf_params(**kw)
         self._chk(self._lib.icpk_tsdf_create(self._h, C.byref(p)))
-        self._tsdf, self._tsdf_n, self._tsdf_ray = p, None, None
+        self._tsdf, self._tsdf_n, self._tsdf_ray, self._tsdf_mesh = p, None, None, None
         return p
 
     def tsdf_reset(self):
         self._chk(self._lib.icpk_tsdf_reset(self._h))
-        self._tsdf_n = self._tsdf_ray = None
+        self._tsdf_n = self._tsdf_ray = self._tsdf_mesh = None
 
     def tsdf_release(self):
         self._chk(self._lib.icpk_tsdf_release(self._h))
-        self._tsdf, self._tsdf_n, self._tsdf_ray = None, None, None
+        self._tsdf, self._tsdf_n, self._tsdf_ray, self._tsdf_mesh = None, None, None, None
 
     def tsdf_integrate(self, depth, pose, intensity=None, fx=468.60, cx=318.27, shape=None, count=True):
         """icpk_tsdf_integrate: one frame into the volume.  depth (rows, cols) uint16, or None: the frame
@@ -1351,6 +1400,46 @@ class Context:
                                           None if w is None else w.ctypes.data_as(C.POINTER(C.c_uint16)),
                                           None if c is None else _fp(c)))
         return f, w, c
+
+    def tsdf_set(self, tsdf, weight, intensity=None):
+        """icpk_tsdf_set: the planes from arrays of one entry per voxel ((dz, dy, dx), or flat): tsdf float32 in
+        [-1, 1], weight uint16, intensity float32 in [0, 1] on a TSDF_COLOR volume.  Drops the surface list, the ray-cast
+        maps and the mesh."""
+        p = self._tsdf
+        if p is None:
+            self._chk(self._lib.icpk_tsdf_set(self._h, None, None, None))  # (ICPK_E_NOT_SET)
+        n = p.dims[0] * p.dims[1] * p.dims[2]
+        f, w = _f(tsdf).reshape(-1), np.ascontiguousarray(weight, np.uint16).reshape(-1)
+        c = None if intensity is None else _f(intensity).reshape(-1)
+        if f.size != n or w.size != n or (c is not None and c.size != n):
+            raise ValueError("the planes must hold one entry per voxel")
+        self._chk(self._lib.icpk_tsdf_set(self._h, _fp(f), w.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                          None if c is None else _fp(c)))
+        self._tsdf_n = self._tsdf_ray = self._tsdf_mesh = None
+
+    def tsdf_extract_mesh(self, min_weight=1):
+        """icpk_tsdf_extract_mesh: (n_vertices, n_triangles, n_no_normal); the mesh stays on the device."""
+        nv, nt, nn = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+        self._chk(self._lib.icpk_tsdf_extract_mesh(self._h, int(min_weight), C.byref(nv), C.byref(nt), C.byref(nn)))
+        self._tsdf_mesh = (nv.value, nt.value, nn.value)
+        return self._tsdf_mesh
+
+    def tsdf_get_mesh(self):
+        """icpk_tsdf_get_mesh: dict(vertices (3, n), normals (3, n), intensity (n,), voxel_index (n,) int32, edge (n,)
+        uint8, triangles (m, 3) int32, n_vertices, n_triangles, n_no_normal) of the last mesh extraction."""
+        if self._tsdf_mesh is None:
+            self._chk(self._lib.icpk_tsdf_get_mesh(self._h, *([None] * 10)))  # (ICPK_E_NOT_SET)
+            raise IcpkError(E_NOT_SET, "no mesh (tsdf_extract_mesh)")
+        n, m, nn = self._tsdf_mesh
+        pts, nrm = np.zeros((3, max(n, 1)), np.float32), np.zeros((3, max(n, 1)), np.float32)
+        inten, vox, edge = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+        tri = np.zeros((max(m, 1), 3), np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._chk(self._lib.icpk_tsdf_get_mesh(self._h, _fp(pts[0]), _fp(pts[1]), _fp(pts[2]), _fp(nrm[0]), _fp(nrm[1]),
+                                               _fp(nrm[2]), _fp(inten), vox.ctypes.data_as(i32),
+                                               edge.ctypes.data_as(C.POINTER(C.c_uint8)), tri.ctypes.data_as(i32)))
+        return dict(vertices=pts[:, :n], normals=nrm[:, :n], intensity=inten[:n], voxel_index=vox[:n], edge=edge[:n],
+                    triangles=tri[:m], n_vertices=n, n_triangles=m, n_no_normal=nn)
 
     def tsdf_extract_surface(self, min_weight=1):
         """icpk_tsdf_extract_surface: (n_points, n_no_normal); the list stays on the device."""

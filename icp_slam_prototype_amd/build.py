@@ -311,6 +311,47 @@ def build_tsdf_raycast_test(force=False):
     return TSDF_RAYCAST_TEST
 
 
+TSDF_MESH_TEST = os.path.join(LIBDIR, "test_tsdf_mesh")
+
+
+def build_tsdf_mesh_test(force=False):
+    """Host-only C++ program over icp::TsdfVolume::extractMesh / getMesh / setPlanes (icp_tsdf.hpp, K21) (g++, links
+    -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_tsdf_mesh.cpp")
+    hdrs = [os.path.join(HERE, "include", h) for h in ("icp_align.hpp", "icp_tsdf.hpp")]
+    build()
+    newest = max(os.path.getmtime(p) for p in [src, LIB] + hdrs)
+    if not force and os.path.exists(TSDF_MESH_TEST) and os.path.getmtime(TSDF_MESH_TEST) >= newest:
+        return TSDF_MESH_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", TSDF_MESH_TEST])
+    return TSDF_MESH_TEST
+
+
+TSDF_MESH_HOST_SANITIZED = os.path.join(LIBDIR, "tsdf_mesh_host_sanitized")
+
+
+def build_tsdf_mesh_host_sanitized(force=False):
+    """DIAGNOSTIC, not part of build(): tests/cpp/tsdf_mesh_host_main.cpp (its own main, no GPU) with icpk_tsdf.cpp --
+    and so csrc/tsdf_rule.h -- compiled under -fsanitize=address,undefined on the host side; everything else icpk_tsdf.cpp
+    refers to comes from libicpk.so as it is.  Run the program it returns directly."""
+    src = os.path.join(ROOT, "tests", "cpp", "tsdf_mesh_host_main.cpp")
+    build()
+    newest = max(os.path.getmtime(p) for p in (src, LIB))
+    if not force and os.path.exists(TSDF_MESH_HOST_SANITIZED) and os.path.getmtime(TSDF_MESH_HOST_SANITIZED) >= newest:
+        return TSDF_MESH_HOST_SANITIZED
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-omit-frame-pointer", "-g"]
+    objs = []
+    for path, name in ((os.path.join(CSRC, "icpk_tsdf.cpp"), "icpk_tsdf_sanitized.o"), (src, "tsdf_mesh_host_main.o")):
+        objs.append(os.path.join(LIBDIR, name))
+        subprocess.check_call([hipcc] + FLAGS + san + ["-x", "hip", "-c", path, "-o", objs[-1]])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-fsanitize=address,undefined"] + objs +
+                          ["-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN", "-o", TSDF_MESH_HOST_SANITIZED])
+    return TSDF_MESH_HOST_SANITIZED
+
+
 THREADS_TEST = os.path.join(LIBDIR, "test_threads")
 
 
@@ -379,4 +420,5 @@ if __name__ == "__main__":
     print(build_pose_graph_test(force="--force" in sys.argv))
     print(build_tsdf_test(force="--force" in sys.argv))
     print(build_tsdf_raycast_test(force="--force" in sys.argv))
+    print(build_tsdf_mesh_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

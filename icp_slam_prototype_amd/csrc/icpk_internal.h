@@ -913,4 +913,25 @@ inline int tsdf_ray_chunks(int npix) { return (npix + TSDF_THREADS - 1) / TSDF_T
 void launch_tsdf_ray_count(const TsdfRayCompactArgs& a, long long* totals, hipStream_t s);
 void launch_tsdf_ray_scatter(const TsdfRayCompactArgs& a, hipStream_t s);
 
+// K21, the triangle mesh of the volume (the mesh rule of tsdf_rule.h), over K19's chunks
+struct TsdfMeshArgs {
+  TsdfPlanes v;
+  long long n, chunk;
+  int* vcounts;         // [nblocks] vertices listed per chunk
+  int* tcounts;         // [nblocks] triangles per chunk
+  int* nonormal;        // [nblocks] listed vertices without a normal per chunk
+  long long* voffsets;  // [nblocks + 1] the scan of vcounts: also the range a vertex look-up searches
+  long long* toffsets;  // [nblocks + 1] the scan of tcounts
+  long long vcapacity, tcapacity;  // entries the vertex list / the triangle list has room for
+  float *x, *y, *z, *nx, *ny, *nz, *intensity;
+  int* voxel_index;     // the key of every vertex: its owner voxel ...
+  uint8_t* edge;        // ... and its edge type 1 .. 7
+  int* triangles;       // 3 per triangle
+};
+// count pass + two scans: totals[0] = vertices, totals[1] = vertices without a normal, totals[2] = triangles (device;
+// totals holds 4)
+void launch_tsdf_mesh_count(const TsdfMeshArgs& a, int nblocks, long long* totals, hipStream_t s);
+// the vertices, then the triangles
+void launch_tsdf_mesh_scatter(const TsdfMeshArgs& a, int nblocks, hipStream_t s);
+
 }  // namespace icpk

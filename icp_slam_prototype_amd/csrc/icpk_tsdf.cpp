@@ -1,10 +1,14 @@
-// icpk_tsdf.cpp -- host side of the TSDF volume (K19, K20; kernels_tsdf.hip): the volume a context owns, the refusals,
-// the inversion of the pose, integration of a frame (uploaded, or the one icpk_backproject_pair left resident),
-// extraction of the surface list, the ray cast of the volume into vertex and normal maps, and the hand-over of either
-// as the context's target.  The rules are written out in include/icpk.h and stated once, in tsdf_rule.h, for the device
-// and for icpk_tsdf_voxel_update / icpk_tsdf_raycast_pixels.
+// icpk_tsdf.cpp -- host side of the TSDF volume (K19, K20, K21; kernels_tsdf.hip): the volume a context owns, the
+// refusals, the inversion of the pose, integration of a frame (uploaded, or the one icpk_backproject_pair left
+// resident), extraction of the surface list, the ray cast of the volume into vertex and normal maps, the hand-over of
+// either as the context's target, and the extraction of the triangle mesh.  The rules are written out in include/icpk.h
+// and stated once, in tsdf_rule.h, for the device and for icpk_tsdf_voxel_update / icpk_tsdf_raycast_pixels /
+// icpk_tsdf_mesh_host.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <utility>
+#include <vector>
 
 #include "icpk_ctx.h"
 
@@ -37,6 +41,18 @@ struct icpk_tsdf_state {
   size_t ray_list_cap = 0;
   bool have_raycast = false;
   int ray_rows = 0, ray_cols = 0;
+  // the mesh of the last mesh extraction (K21): 7 planes of mesh_vcap floats, every vertex's key (owner voxel, edge
+  // type), 3 x mesh_tcap indices; and its own per-chunk counts, scans and totals, so that K19's stay as they are
+  DevBuf<float> mesh;
+  DevBuf<int> mesh_voxel, mesh_tri;
+  DevBuf<uint8_t> mesh_edge;
+  size_t mesh_vcap = 0, mesh_tcap = 0;
+  DevBuf<int> mesh_vcounts, mesh_tcounts, mesh_nonormal;
+  DevBuf<long long> mesh_voffsets, mesh_toffsets, mesh_totals;  // (mesh_totals: 4)
+  PinnedBuf<long long> mesh_totals_host;
+  bool have_mesh = false;
+  int mesh_nv = 0, mesh_nt = 0, mesh_nn = 0;
+  float* mesh_plane(int k) const { return mesh + (size_t)k * mesh_vcap; }
 };
 
 void icpk_tsdf_free(icpk_ctx* ctx) {
@@ -84,6 +100,7 @@ int clear_volume(icpk_ctx* ctx, icpk_tsdf_state* v) {
   if (v->p.flags & ICPK_TSDF_COLOR) ICPK_HIP(ctx, hipMemsetAsync(v->intensity, 0, (size_t)v->n * sizeof(float), ctx->stream));
   v->have_surface = false;
   v->have_raycast = false;
+  v->have_mesh = false;
   return ICPK_OK;
 }
 
@@ -285,6 +302,29 @@ int icpk_tsdf_get(icpk_ctx* ctx, float* tsdf, uint16_t* weight, float* intensity
   return ICPK_OK;
 }
 
+int icpk_tsdf_set(icpk_ctx* ctx, const float* tsdf, const uint16_t* weight, const float* intensity) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  if (!tsdf || !weight) return fail(ctx, ICPK_E_ARG, "tsdf or weight is NULL");
+  const bool color = (v->p.flags & ICPK_TSDF_COLOR) != 0;
+  if (color != (intensity != nullptr))
+    return fail(ctx, ICPK_E_ARG, color ? "a colour volume needs the intensity plane" : "intensities given to a volume without ICPK_TSDF_COLOR");
+  const size_t n = (size_t)v->n;
+  for (size_t i = 0; i < n; ++i)
+    if (!(tsdf[i] >= -1.f && tsdf[i] <= 1.f)) return fail(ctx, ICPK_E_ARG, "tsdf must be finite and in [-1, 1]");  // (false for NaN)
+  if (intensity && !intensities_ok(intensity, n)) return fail(ctx, ICPK_E_ARG, "intensities must be finite and in [0, 1]");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  ICPK_HIP(ctx, hipMemcpyAsync(v->tsdf, tsdf, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  ICPK_HIP(ctx, hipMemcpyAsync(v->weight, weight, n * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+  if (intensity) ICPK_HIP(ctx, hipMemcpyAsync(v->intensity, intensity, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller's arrays are free again)
+  v->have_surface = false;
+  v->have_raycast = false;
+  v->have_mesh = false;
+  return ICPK_OK;
+}
+
 int icpk_tsdf_extract_surface(icpk_ctx* ctx, int32_t min_weight, int32_t* n_points, int32_t* n_no_normal) {
   if (!ctx) return ICPK_E_ARG;
   icpk_tsdf_state* v = ctx->tsdf;
@@ -356,6 +396,150 @@ int icpk_tsdf_surface_to_target(icpk_ctx* ctx) {
   if (v->surf_n == 0) return fail(ctx, ICPK_E_EMPTY_TARGET, "the surface list is empty");
   float* const list[7] = {v->plane(0), v->plane(1), v->plane(2), v->plane(3), v->plane(4), v->plane(5), v->plane(6)};
   return list_to_target(ctx, v, list, v->surf_n);
+}
+
+int icpk_tsdf_extract_mesh(icpk_ctx* ctx, int32_t min_weight, int32_t* n_vertices, int32_t* n_triangles, int32_t* n_no_normal) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  if (min_weight < 1 || min_weight > 65535) return fail(ctx, ICPK_E_ARG, "min_weight outside 1 .. 65535");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  v->have_mesh = false;
+  int rc = v->mesh_vcounts.reserve(ctx, TSDF_MAX_BLOCKS);
+  if (!rc) rc = v->mesh_tcounts.reserve(ctx, TSDF_MAX_BLOCKS);
+  if (!rc) rc = v->mesh_nonormal.reserve(ctx, TSDF_MAX_BLOCKS);
+  if (!rc) rc = v->mesh_voffsets.reserve(ctx, TSDF_MAX_BLOCKS + 1);
+  if (!rc) rc = v->mesh_toffsets.reserve(ctx, TSDF_MAX_BLOCKS + 1);
+  if (!rc) rc = v->mesh_totals.reserve(ctx, 4);
+  if (!rc) rc = v->mesh_totals_host.reserve(ctx, 4);
+  if (rc) return rc;
+  TsdfMeshArgs a{};
+  a.v = make_planes(v->p, v->tsdf, v->weight, (v->p.flags & ICPK_TSDF_COLOR) ? v->intensity.get() : nullptr, min_weight);
+  a.n = v->n, a.chunk = tsdf_chunk(v->n);
+  a.vcounts = v->mesh_vcounts, a.tcounts = v->mesh_tcounts, a.nonormal = v->mesh_nonormal;
+  a.voffsets = v->mesh_voffsets, a.toffsets = v->mesh_toffsets;
+  const int nblocks = tsdf_blocks(v->n);
+  launch_tsdf_mesh_count(a, nblocks, v->mesh_totals, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  // the one host wait: the lists are allocated for the counts
+  ICPK_HIP(ctx, hipMemcpyAsync(v->mesh_totals_host, v->mesh_totals, 4 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const long long nv = v->mesh_totals_host[0], nn = v->mesh_totals_host[1], nt = v->mesh_totals_host[2];
+  if (nv > ICPK_TSDF_MAX_SURFACE || nt > ICPK_TSDF_MAX_SURFACE)
+    return fail(ctx, ICPK_E_ARG, "more than ICPK_TSDF_MAX_SURFACE vertices or triangles");
+  if ((size_t)nv > v->mesh_vcap) {
+    const size_t cap = (size_t)nv;
+    v->mesh_vcap = 0;
+    rc = reserve_group(ctx, nullptr, need(v->mesh, 7 * cap), need(v->mesh_voxel, cap), need(v->mesh_edge, cap));
+    if (rc) return rc;
+    v->mesh_vcap = cap;
+  }
+  if ((size_t)nt > v->mesh_tcap) {
+    v->mesh_tcap = 0;
+    if ((rc = v->mesh_tri.reserve(ctx, 3 * (size_t)nt))) return rc;
+    v->mesh_tcap = (size_t)nt;
+  }
+  if (nv > 0) {
+    a.vcapacity = nv, a.tcapacity = nt;
+    a.x = v->mesh_plane(0), a.y = v->mesh_plane(1), a.z = v->mesh_plane(2);
+    a.nx = v->mesh_plane(3), a.ny = v->mesh_plane(4), a.nz = v->mesh_plane(5);
+    a.intensity = v->mesh_plane(6);
+    a.voxel_index = v->mesh_voxel, a.edge = v->mesh_edge, a.triangles = v->mesh_tri;
+    launch_tsdf_mesh_scatter(a, nblocks, ctx->stream);
+    ICPK_HIP(ctx, hipGetLastError());
+  }
+  v->mesh_nv = (int)nv, v->mesh_nt = (int)nt, v->mesh_nn = (int)nn;
+  v->have_mesh = true;
+  if (n_vertices) *n_vertices = v->mesh_nv;
+  if (n_triangles) *n_triangles = v->mesh_nt;
+  if (n_no_normal) *n_no_normal = v->mesh_nn;
+  return ICPK_OK;
+}
+
+int icpk_tsdf_get_mesh(icpk_ctx* ctx, float* x, float* y, float* z, float* nx, float* ny, float* nz, float* intensity,
+                       int32_t* voxel_index, uint8_t* edge, int32_t* triangles) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v || !v->have_mesh) return fail(ctx, ICPK_E_NOT_SET, "no mesh (icpk_tsdf_extract_mesh)");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t n = (size_t)v->mesh_nv, m = (size_t)v->mesh_nt;
+  float* const out[7] = {x, y, z, nx, ny, nz, intensity};
+  for (int k = 0; k < 7 && n > 0; ++k)
+    if (out[k]) ICPK_HIP(ctx, hipMemcpyAsync(out[k], v->mesh_plane(k), n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (voxel_index && n > 0)
+    ICPK_HIP(ctx, hipMemcpyAsync(voxel_index, v->mesh_voxel, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (edge && n > 0) ICPK_HIP(ctx, hipMemcpyAsync(edge, v->mesh_edge, n, hipMemcpyDeviceToHost, ctx->stream));
+  if (triangles && m > 0)
+    ICPK_HIP(ctx, hipMemcpyAsync(triangles, v->mesh_tri, 3 * m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_tsdf_mesh_host(const icpk_tsdf_params* params, int32_t min_weight, const float* tsdf, const uint16_t* weight,
+                        const float* intensity, int64_t cap_vertices, int64_t cap_triangles, float* x, float* y, float* z,
+                        float* nx, float* ny, float* nz, float* intensity_out, int32_t* voxel_index, uint8_t* edge,
+                        int32_t* triangles, int64_t counts[3]) {
+  if (!params || !tsdf || !weight || !counts || cap_vertices < 0 || cap_triangles < 0) return ICPK_E_ARG;
+  if (check_params(*params) || min_weight < 1 || min_weight > 65535) return ICPK_E_ARG;
+  if (((params->flags & ICPK_TSDF_COLOR) != 0) != (intensity != nullptr)) return ICPK_E_ARG;
+  const TsdfPlanes v = make_planes(*params, tsdf, weight, intensity, min_weight);
+  const long long dx = v.dims[0], dxy = dx * v.dims[1], n = dxy * v.dims[2];
+  // the count pass
+  long long nv = 0, nt = 0, nn = 0;
+  for (long long at = 0; at < n; ++at) {
+    const int k = (int)(at / dxy), j = (int)((at - k * dxy) / dx);
+    const int c[3] = {(int)(at - k * dxy - j * dx), j, k};
+    TsdfMeshVoxel mv;
+    tsdf_mesh_voxel(v, c, at, true, &mv);
+    nt += mv.triangles;
+    for (int m = 1; m < 8; ++m)
+      if ((mv.vertices >> (m - 1)) & 1) nv += 1, nn += !tsdf_mesh_vertex(v, c, at, m, nullptr);
+  }
+  counts[0] = nv, counts[1] = nt, counts[2] = nn;
+  if (nv > cap_vertices || nt > cap_triangles || nv > ICPK_TSDF_MAX_SURFACE || nt > ICPK_TSDF_MAX_SURFACE) return ICPK_E_ARG;
+  // the vertices in (voxel, m) order, with their keys, then the triangles by a search over the keys
+  std::vector<long long> keys;
+  keys.reserve((size_t)nv);
+  std::vector<std::pair<long long, TsdfMeshVoxel>> cells;
+  for (long long at = 0; at < n; ++at) {
+    const int k = (int)(at / dxy), j = (int)((at - k * dxy) / dx);
+    const int c[3] = {(int)(at - k * dxy - j * dx), j, k};
+    TsdfMeshVoxel mv;
+    tsdf_mesh_voxel(v, c, at, true, &mv);
+    if (mv.triangles > 0) cells.emplace_back(at, mv);
+    for (int m = 1; m < 8; ++m) {
+      if (!((mv.vertices >> (m - 1)) & 1)) continue;
+      TsdfMeshVertex vx;
+      tsdf_mesh_vertex(v, c, at, m, &vx);
+      const size_t pos = keys.size();
+      keys.push_back(at * 8 + m);
+      float* const out[7] = {x, y, z, nx, ny, nz, intensity_out};
+      const float val[7] = {vx.p[0], vx.p[1], vx.p[2], vx.n[0], vx.n[1], vx.n[2], vx.intensity};
+      for (int q = 0; q < 7; ++q)
+        if (out[q]) out[q][pos] = val[q];
+      if (voxel_index) voxel_index[pos] = (int32_t)at;
+      if (edge) edge[pos] = (uint8_t)m;
+    }
+  }
+  if (!triangles) return ICPK_OK;
+  long long pos = 0;
+  for (const auto& cell : cells) {
+    for (int tet = 0; tet < 6; ++tet) {
+      int vc[4];
+      tsdf_tet_corners(tet, vc);
+      const int cs = tsdf_tet_case(cell.second.signs, vc);
+      const unsigned code = tsdf_case_table(cs);
+      for (int tri = 0; tri < tsdf_case_triangles(cs); ++tri, ++pos)
+        for (int q = 0; q < 3; ++q) {
+          int corner, m;
+          tsdf_triangle_edge(vc, tsdf_tet_odd(tet), code, tri, q, &corner, &m);
+          const long long key = (cell.first + tsdf_mask_offset(v, corner)) * 8 + m;
+          const auto it = std::lower_bound(keys.begin(), keys.end(), key);
+          triangles[3 * pos + q] = it != keys.end() && *it == key ? (int32_t)(it - keys.begin()) : -1;
+        }
+    }
+  }
+  return ICPK_OK;
 }
 
 int icpk_tsdf_voxel_update(const icpk_tsdf_params* params, const float R[9], const float t[3], const uint16_t* depth,

@@ -1,8 +1,9 @@
-// kernels_tsdf.hip -- K19, K20: the dense TSDF volume.  Integration of one posed depth frame (one thread per voxel, the
-// rule of tsdf_rule.h from the voxel's own indices) and extraction of the zero crossings as an ordered point list with
+// kernels_tsdf.hip -- K19, K20, K21: the dense TSDF volume.  Integration of one posed depth frame (one thread per voxel,
+// the rule of tsdf_rule.h from the voxel's own indices) and extraction of the zero crossings as an ordered point list with
 // normals (count / scan / scatter, as K4 compacts an image).  A voxel is owned by one thread: no atomic of any kind,
 // the same bytes on every run.  K20 casts one ray per pixel through the volume (the ray rule of tsdf_rule.h) into eight
-// image planes, a pixel owned by one thread, and compacts their valid pixels into a list with K19's scan.
+// image planes, a pixel owned by one thread, and compacts their valid pixels into a list with K19's scan.  K21 extracts
+// a triangle mesh (the mesh rule of tsdf_rule.h): K19's count / scan / scatter for the vertices and for the triangles.
 //
 // Both walks share one geometry: the volume is a line of n = dx dy dz voxels in linear order (x fastest), cut into at
 // most TSDF_MAX_BLOCKS contiguous chunks of a multiple of TSDF_THREADS voxels, one workgroup per chunk, which it
@@ -254,6 +255,172 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_ray_scatter_kernel(const Ts
   if (!mine || pos >= a.capacity) return;  // (pos < capacity always: the capacity is the scan's total)
 #pragma unroll
   for (int k = 0; k < 7; ++k) a.list[k * a.capacity + pos] = a.maps[(long long)(k < 6 ? k : 7) * a.npix + pix];
+}
+
+// ---- K21: the triangle mesh ----
+// K19's chunk geometry and its count / scan / scatter, twice over: once for the vertices a voxel owns (the crossings on
+// its seven edges), once for the triangles of the cell it is the lower corner of.  Both are a function of the voxel's
+// own neighbourhood (tsdf_mesh_voxel), so the count pass and the two scatters agree without talking to each other.
+
+// the exclusive rank of `mine` among the workgroup's threads and the workgroup's total (wsum: 4 ints of LDS; the
+// caller synchronises before the next use of wsum)
+__device__ __forceinline__ int block_rank(int mine, int* wsum, int* total) {
+  int incl = mine;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int up = __shfl_up(incl, d, 64);
+    if ((threadIdx.x & 63) >= d) incl += up;
+  }
+  if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  int woff = 0;
+  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
+  *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  return woff + incl - mine;
+}
+
+// pass 1: per chunk, the listed vertices, those among them without a normal, and the triangles
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_mesh_count_kernel(const TsdfMeshArgs a) {
+  const long long begin = (long long)blockIdx.x * a.chunk;
+  const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
+  const VoxelIndex vi{(unsigned)a.v.dims[0], (unsigned)a.v.dims[0] * (unsigned)a.v.dims[1]};
+  int nv = 0, nt = 0, nn = 0;
+  for (long long base = begin; base < end; base += TSDF_THREADS) {
+    const long long at = base + threadIdx.x;
+    if (at >= end) continue;
+    int c[3];
+    vi.split((unsigned)at, c);
+    TsdfMeshVoxel mv;
+    tsdf_mesh_voxel(a.v, c, at, true, &mv);
+    nt += mv.triangles;
+    for (int m = 1; m < 8; ++m) {
+      if (!((mv.vertices >> (m - 1)) & 1)) continue;
+      nv += 1;
+      nn += !tsdf_mesh_vertex(a.v, c, at, m, nullptr);
+    }
+  }
+  __shared__ int lds4[3][4];
+  const int tv = block_sum(nv, lds4[0]);
+  const int tt = block_sum(nt, lds4[1]);
+  const int tn = block_sum(nn, lds4[2]);
+  if (threadIdx.x == 0) {
+    a.vcounts[blockIdx.x] = tv;
+    a.tcounts[blockIdx.x] = tt;
+    a.nonormal[blockIdx.x] = tn;
+  }
+}
+
+// pass 3a: the chunk's vertices again, each to its place (the chunk's offset, then voxel order, then edge type), with
+// its key next to it
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_mesh_vertex_kernel(const TsdfMeshArgs a) {
+  const long long begin = (long long)blockIdx.x * a.chunk;
+  const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
+  const VoxelIndex vi{(unsigned)a.v.dims[0], (unsigned)a.v.dims[0] * (unsigned)a.v.dims[1]};
+  if (a.voffsets[blockIdx.x + 1] == a.voffsets[blockIdx.x]) return;  // (uniform: the chunk owns no vertex)
+  __shared__ int wsum[4];
+  long long run = a.voffsets[blockIdx.x];
+  for (long long base = begin; base < end; base += TSDF_THREADS) {
+    const long long at = base + threadIdx.x;
+    int c[3] = {0, 0, 0};
+    TsdfMeshVoxel mv{0, 0, 0};
+    if (at < end) {
+      vi.split((unsigned)at, c);
+      tsdf_mesh_voxel(a.v, c, at, true, &mv);
+    }
+    int round_total;
+    long long pos = run + block_rank(__popc((unsigned)mv.vertices), wsum, &round_total);
+    for (int m = 1; m < 8; ++m) {
+      if (!((mv.vertices >> (m - 1)) & 1)) continue;
+      TsdfMeshVertex vx;
+      tsdf_mesh_vertex(a.v, c, at, m, &vx);
+      if (pos < a.vcapacity) {  // (always: the capacity is the scan's total)
+        a.x[pos] = vx.p[0], a.y[pos] = vx.p[1], a.z[pos] = vx.p[2];
+        a.nx[pos] = vx.n[0], a.ny[pos] = vx.n[1], a.nz[pos] = vx.n[2];
+        a.intensity[pos] = vx.intensity;
+        a.voxel_index[pos] = (int)at;
+        a.edge[pos] = (uint8_t)m;
+      }
+      pos += 1;
+    }
+    run += round_total;
+    __syncthreads();  // (wsum is rewritten by the next round)
+  }
+}
+
+// the place of vertex (voxel, m) in the list: a binary search over the vertices of the voxel's chunk, which are sorted
+// by (voxel, m).  -1 if it is not there (never: a triangle's cell is known, so its vertices are listed)
+__device__ __forceinline__ int mesh_find_vertex(const TsdfMeshArgs& a, long long voxel, int m) {
+  const long long ch = voxel / a.chunk;  // (voxel < n: ch < nblocks)
+  long long lo = a.voffsets[ch];
+  const long long last = a.voffsets[ch + 1];
+  long long hi = last < a.vcapacity ? last : a.vcapacity;
+  const long long key = voxel * 8 + m;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    const long long k = (long long)a.voxel_index[mid] * 8 + a.edge[mid];
+    if (k < key) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo >= last || lo >= a.vcapacity) return -1;
+  return (long long)a.voxel_index[lo] * 8 + a.edge[lo] == key ? (int)lo : -1;
+}
+
+// pass 3b (after 3a on the same stream): the chunk's triangles, cell by cell, tetrahedron by tetrahedron, in the
+// table's order
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_mesh_triangle_kernel(const TsdfMeshArgs a) {
+  const long long begin = (long long)blockIdx.x * a.chunk;
+  const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
+  const VoxelIndex vi{(unsigned)a.v.dims[0], (unsigned)a.v.dims[0] * (unsigned)a.v.dims[1]};
+  if (a.toffsets[blockIdx.x + 1] == a.toffsets[blockIdx.x]) return;  // (uniform: no triangle in this chunk)
+  __shared__ int wsum[4];
+  long long run = a.toffsets[blockIdx.x];
+  for (long long base = begin; base < end; base += TSDF_THREADS) {
+    const long long at = base + threadIdx.x;
+    TsdfMeshVoxel mv{0, 0, 0};
+    if (at < end) {
+      int c[3];
+      vi.split((unsigned)at, c);
+      tsdf_mesh_voxel(a.v, c, at, false, &mv);
+    }
+    int round_total;
+    long long pos = run + block_rank(mv.triangles, wsum, &round_total);
+    if (mv.triangles > 0) {
+      for (int tet = 0; tet < 6; ++tet) {
+        int vc[4];
+        tsdf_tet_corners(tet, vc);
+        const int cs = tsdf_tet_case(mv.signs, vc);
+        const unsigned code = tsdf_case_table(cs);
+        const int ntri = tsdf_case_triangles(cs);
+        for (int tri = 0; tri < ntri; ++tri) {
+          int idx[3];
+          for (int k = 0; k < 3; ++k) {
+            int corner, m;
+            tsdf_triangle_edge(vc, tsdf_tet_odd(tet), code, tri, k, &corner, &m);
+            idx[k] = mesh_find_vertex(a, at + tsdf_mask_offset(a.v, corner), m);  // (a corner of cell V: in range)
+          }
+          if (pos < a.tcapacity) {  // (always: the capacity is the scan's total)
+            a.triangles[3 * pos] = idx[0], a.triangles[3 * pos + 1] = idx[1], a.triangles[3 * pos + 2] = idx[2];
+          }
+          pos += 1;
+        }
+      }
+    }
+    run += round_total;
+    __syncthreads();  // (wsum is rewritten by the next round)
+  }
+}
+
+void launch_tsdf_mesh_count(const TsdfMeshArgs& a, int nblocks, long long* totals, hipStream_t s) {
+  hipLaunchKernelGGL(tsdf_mesh_count_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+  // totals[0] = vertices, [1] = those without a normal; totals[2] = triangles ([3]: the same sum again, unused)
+  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.vcounts, a.nonormal, nblocks, a.voffsets, totals);
+  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.tcounts, a.nonormal, nblocks, a.toffsets,
+                     totals + 2);
+}
+
+void launch_tsdf_mesh_scatter(const TsdfMeshArgs& a, int nblocks, hipStream_t s) {
+  hipLaunchKernelGGL(tsdf_mesh_vertex_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+  hipLaunchKernelGGL(tsdf_mesh_triangle_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
 }
 
 void launch_tsdf_integrate(const TsdfIntegrateArgs& a, int nblocks, long long* n_updated, hipStream_t s) {

@@ -1,9 +1,9 @@
-// tsdf_rule.h -- the per-voxel rule, the surface rule (K19) and the ray rule (K20) of the TSDF volume; include/icpk.h
-// writes all three out.
+// tsdf_rule.h -- the per-voxel rule, the surface rule (K19), the ray rule (K20) and the mesh rule (K21) of the TSDF
+// volume; include/icpk.h writes all four out.
 // Header-inline and __host__ __device__: kernels_tsdf.hip runs it per voxel on the device, icpk_tsdf.cpp exports it
-// for one voxel and for one pixel on the host (icpk_tsdf_voxel_update, icpk_tsdf_raycast_pixels), compiled with
-// -ffp-contract=off on both sides.  float32 only, +, -, *, / and sqrt in the order written, no libm: the same bits
-// wherever those five are correctly rounded.
+// for one voxel, for one pixel and for a whole mesh on the host (icpk_tsdf_voxel_update, icpk_tsdf_raycast_pixels,
+// icpk_tsdf_mesh_host), compiled with -ffp-contract=off on both sides.  float32 only, +, -, *, / and sqrt in the order
+// written, no libm: the same bits wherever those five are correctly rounded.
 #pragma once
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -271,6 +271,151 @@ ICPK_HD int tsdf_raycast_pixel(const TsdfPlanes& v, const TsdfRay& r, int row, i
     have_prev = true, f_prev = f, z_prev = z;
   }
   return TSDF_RAY_NONE;
+}
+
+// ---- the mesh rule (K21) ----
+// Marching tetrahedra over the Kuhn split of a cell.  Corners and edge types are masks e = x + 2 y + 4 z (K20's corner
+// order); the edge (V, m) joins voxel V to V + m and is owned by V.
+
+// the distance of V + e from V in linear index
+ICPK_HD long long tsdf_mask_offset(const TsdfPlanes& v, int e) {
+  return (e & 1) + (long long)v.dims[0] * (((e >> 1) & 1) + (long long)v.dims[1] * (e >> 2));
+}
+
+// whether the cell with lower corner cc is in range and known; no index is formed before the range test has passed
+ICPK_HD bool tsdf_cell_known_at(const TsdfPlanes& v, const int cc[3]) {
+  for (int a = 0; a < 3; ++a)
+    if (cc[a] < 0 || cc[a] + 1 >= v.dims[a]) return false;
+  TsdfCell cell;
+  cell.c[0] = cc[0], cell.c[1] = cc[1], cell.c[2] = cc[2];
+  cell.at = cc[0] + (long long)v.dims[0] * (cc[1] + (long long)v.dims[1] * cc[2]);
+  return tsdf_cell_known(v, cell);
+}
+
+// rule 2: the four corners of tetrahedron `tet` (0 .. 5: xyz, xzy, yxz, yzx, zxy, zyx) and whether it is odd
+ICPK_HD void tsdf_tet_corners(int tet, int vc[4]) {
+  vc[0] = 0, vc[1] = (0x442211 >> (4 * tet)) & 7, vc[2] = (0x656353 >> (4 * tet)) & 7, vc[3] = 7;
+}
+ICPK_HD bool tsdf_tet_odd(int tet) { return (0x26 >> tet) & 1; }
+
+// the case of a tetrahedron (rule 4) from the cell's sign mask (bit e: corner e is negative)
+ICPK_HD int tsdf_tet_case(int signs, const int vc[4]) {
+  return (signs & 1) | (((signs >> vc[1]) & 1) << 1) | (((signs >> vc[2]) & 1) << 2) | (((signs >> 7) & 1) << 3);
+}
+
+ICPK_HD int tsdf_case_triangles(int cs) {
+  const int inside = (cs & 1) + ((cs >> 1) & 1) + ((cs >> 2) & 1) + (cs >> 3);
+  return inside == 2 ? 2 : inside == 0 || inside == 4 ? 0 : 1;
+}
+
+// rule 4's table for an even tetrahedron: six nibbles, the vertices of the first triangle and then of the second, each
+// the edge between two positions: 0 = 01, 1 = 02, 2 = 03, 3 = 12, 4 = 13, 5 = 23
+ICPK_HD unsigned tsdf_case_table(int cs) {
+  switch (cs) {
+    case 1: return 0x210u;      // (01,02,03)
+    case 2: return 0x340u;      // (10,13,12)
+    case 3: return 0x341421u;   // (02,03,13) (02,13,12)
+    case 4: return 0x531u;      // (20,21,23)
+    case 5: return 0x530250u;   // (01,23,03) (01,21,23)
+    case 6: return 0x150540u;   // (10,13,23) (10,23,20)
+    case 7: return 0x542u;      // (30,31,32)
+    case 8: return 0x452u;      // (30,32,31)
+    case 9: return 0x450510u;   // (01,02,32) (01,32,31)
+    case 10: return 0x520350u;  // (10,32,12) (10,30,32)
+    case 11: return 0x351u;     // (20,23,21)
+    case 12: return 0x241431u;  // (20,21,31) (20,31,30)
+    case 13: return 0x430u;     // (10,12,13)
+    case 14: return 0x120u;     // (01,03,02)
+    default: return 0u;
+  }
+}
+
+// vertex k (0 .. 2) of triangle `tri` of a tetrahedron with corners vc and table entry `code`: the corner that owns
+// its edge and the edge type.  An odd tetrahedron swaps the second and the third vertex
+ICPK_HD void tsdf_triangle_edge(const int vc[4], bool odd, unsigned code, int tri, int k, int* corner, int* m) {
+  const int kk = odd && k > 0 ? 3 - k : k;
+  const int id = (int)(code >> (4 * (3 * tri + kk))) & 7;
+  const int p = (0x940 >> (2 * id)) & 3, q = (0xfb9 >> (2 * id)) & 3;  // (p < q: vc[p] is a subset of vc[q])
+  *corner = vc[p];
+  *m = vc[q] ^ vc[p];
+}
+
+// what voxel V contributes: as the owner of seven edges and as the lower corner of a cell
+struct TsdfMeshVoxel {
+  int vertices;   // bit m - 1: the vertex on edge (V, m) is listed
+  int triangles;  // of cell V: 0 .. 12
+  int signs;      // of cell V, where triangles > 0: bit e = corner e is negative
+};
+
+// Rules 1 - 4 for voxel V = (c[0], c[1], c[2]) with linear index `at`.  The cheap test comes first: no crossing on the
+// seven edges V owns means no vertex of V's and no triangle of cell V's.  with_vertices false: only triangles and signs
+ICPK_HD void tsdf_mesh_voxel(const TsdfPlanes& v, const int c[3], long long at, bool with_vertices, TsdfMeshVoxel* o) {
+  o->vertices = o->triangles = o->signs = 0;
+  const bool up[3] = {c[0] + 1 < v.dims[0], c[1] + 1 < v.dims[1], c[2] + 1 < v.dims[2]};
+  int inr = 0, neg = 0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    if (((e & 1) && !up[0]) || ((e & 2) && !up[1]) || ((e & 4) && !up[2])) continue;
+    inr |= 1 << e;
+    neg |= (int)(v.tsdf[at + tsdf_mask_offset(v, e)] < 0.f) << e;  // (V + e is in range)
+  }
+  const int cross = ((neg & 1) ? ~neg : neg) & inr & 0xfe;  // bit m: (f_V < 0) != (f_{V + m} < 0)
+  if (!cross) return;  // (nearly every voxel ends here, with the distances read and no weight)
+  bool self = inr == 0xff;  // cell V is in range ...
+  if (self) {
+    TsdfCell cell;
+    cell.c[0] = c[0], cell.c[1] = c[1], cell.c[2] = c[2], cell.at = at;
+    self = tsdf_cell_known(v, cell);  // ... and known
+  }
+  if (self) {
+    o->signs = neg;
+#pragma unroll
+    for (int tet = 0; tet < 6; ++tet) {
+      int vc[4];
+      tsdf_tet_corners(tet, vc);
+      o->triangles += tsdf_case_triangles(tsdf_tet_case(neg, vc));
+    }
+  }
+  if (!with_vertices) return;
+  for (int m = 1; m < 8; ++m) {
+    if (!((cross >> m) & 1)) continue;
+    bool listed = self;
+    for (int u = 1; u < 8 && !listed; ++u) {
+      if (u & m) continue;
+      const int cc[3] = {c[0] - (u & 1), c[1] - ((u >> 1) & 1), c[2] - (u >> 2)};
+      listed = tsdf_cell_known_at(v, cc);
+    }
+    if (listed) o->vertices |= 1 << (m - 1);
+  }
+}
+
+struct TsdfMeshVertex {
+  float p[3], n[3], intensity;
+};
+
+// rule 3 for the listed vertex on edge (V, m): false when it has no normal (out->n is then 0).  out may be null
+ICPK_HD bool tsdf_mesh_vertex(const TsdfPlanes& v, const int c[3], long long at, int m, TsdfMeshVertex* out) {
+  const long long nb = at + tsdf_mask_offset(v, m);
+  const float fv = v.tsdf[at], fn = v.tsdf[nb];
+  const float t = fv / (fv - fn);
+  if (out) {
+    const float step = t * v.voxel;
+    for (int a = 0; a < 3; ++a) {
+      out->p[a] = tsdf_centre(c[a], v.voxel, v.origin[a]);
+      if ((m >> a) & 1) out->p[a] = out->p[a] + step;
+      out->n[a] = 0.f;
+    }
+    out->intensity = v.intensity ? v.intensity[at] + t * (v.intensity[nb] - v.intensity[at]) : 0.f;
+  }
+  const int cn[3] = {c[0] + (m & 1), c[1] + ((m >> 1) & 1), c[2] + (m >> 2)};
+  float gv[3], gn[3], n[3];
+  if (!tsdf_gradient(v, c, at, gv) || !tsdf_gradient(v, cn, nb, gn)) return false;
+  for (int a = 0; a < 3; ++a) n[a] = gv[a] + t * (gn[a] - gv[a]);
+  const float len = __builtin_sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+  if (!(len > 0.f)) return false;
+  if (out)
+    for (int a = 0; a < 3; ++a) out->n[a] = n[a] / len;
+  return true;
 }
 
 }  // namespace icpk

@@ -1,4 +1,4 @@
-// icp_tsdf.hpp -- C++ host side of the TSDF volume (icpk_tsdf_* of include/icpk.h, K19 and K20).  Include it next to
+// icp_tsdf.hpp -- C++ host side of the TSDF volume (icpk_tsdf_* of include/icpk.h, K19 - K21).  Include it next to
 // icp_align.hpp.
 //
 //   * icp::TsdfVolume -- the dense volume of truncated signed distances an Engine's context owns: posed depth frames
@@ -6,6 +6,8 @@
 //                        (surface) or becomes the Engine's target for scan-to-model alignment (toTarget).  An Engine
 //                        holds one volume: constructing another replaces it.  raycast gives the surface visible from
 //                        one pose as vertex and normal maps (K20); raycastToTarget makes it the Engine's target.
+//                        extractMesh / getMesh give the surface as a triangle mesh (K21); setPlanes restores a saved
+//                        model.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -31,6 +33,18 @@ struct TsdfRaycast {
   std::vector<float> x, y, z, nx, ny, nz, depth, intensity;
   int32_t hits = 0;      // pixels that hold a hit (depth > 0)
   int32_t noNormal = 0;  // crossings not listed: no normal where the ray met the surface
+};
+
+// the triangle mesh of one extraction: vertices ordered by owner voxel, then edge type; a vertex without a normal holds
+// (0, 0, 0)
+struct TsdfMesh {
+  std::vector<float> x, y, z, nx, ny, nz, intensity;
+  std::vector<int32_t> voxel;      // linear index of the voxel that owns the vertex's edge
+  std::vector<uint8_t> edge;       // the edge's type 1 .. 7: bit 0 +x, bit 1 +y, bit 2 +z
+  std::vector<int32_t> triangles;  // three vertex indices each
+  int32_t noNormal = 0;            // vertices listed without a normal
+  size_t vertices() const { return x.size(); }
+  size_t size() const { return triangles.size() / 3; }
 };
 
 class TsdfVolume {
@@ -114,18 +128,50 @@ class TsdfVolume {
   // the last ray cast's hits become the Engine's target, with their normals (and colours), in row-major pixel order:
   // device to device.  ICPK_E_EMPTY_TARGET (the target stays) without a hit
   int raycastToTarget() { return icpk_tsdf_raycast_to_target(eng_.ctx()); }
+  // the surface as a triangle mesh over the cells whose eight voxels have weight >= minWeight; it stays on the device
+  // for getMesh.  Any count may be null
+  int extractMesh(int minWeight = 1, int32_t* nVertices = nullptr, int32_t* nTriangles = nullptr, int32_t* nNoNormal = nullptr) {
+    int32_t nv = 0, nt = 0, nn = 0;
+    const int rc = icpk_tsdf_extract_mesh(eng_.ctx(), minWeight, &nv, &nt, &nn);
+    if (rc) return rc;
+    meshVertices_ = nv, meshTriangles_ = nt, meshNoNormal_ = nn;
+    if (nVertices) *nVertices = nv;
+    if (nTriangles) *nTriangles = nt;
+    if (nNoNormal) *nNoNormal = nn;
+    return ICPK_OK;
+  }
+  // the mesh of the last extractMesh (ICPK_E_NOT_SET before it)
+  int getMesh(TsdfMesh& m) {
+    const size_t n = (size_t)meshVertices_;
+    for (std::vector<float>* v : {&m.x, &m.y, &m.z, &m.nx, &m.ny, &m.nz, &m.intensity}) v->assign(n, 0.f);
+    m.voxel.assign(n, 0);
+    m.edge.assign(n, 0);
+    m.triangles.assign(3 * (size_t)meshTriangles_, 0);
+    m.noNormal = meshNoNormal_;
+    return icpk_tsdf_get_mesh(eng_.ctx(), m.x.data(), m.y.data(), m.z.data(), m.nx.data(), m.ny.data(), m.nz.data(),
+                              m.intensity.data(), m.voxel.data(), m.edge.data(), m.triangles.data());
+  }
+  // the counterpart of planes(): voxels() entries each, x fastest; intensity exactly on a colour volume.  Drops the surface
+  // list, the maps and the mesh
+  int setPlanes(const float* tsdf, const uint16_t* weight, const float* intensity = nullptr) {
+    const int rc = icpk_tsdf_set(eng_.ctx(), tsdf, weight, intensity);
+    if (rc == ICPK_OK) forget();
+    return rc;
+  }
   // the planes, voxels() entries each, x fastest; any pointer may be null
   int planes(float* tsdf, uint16_t* weight, float* intensity = nullptr) { return icpk_tsdf_get(eng_.ctx(), tsdf, weight, intensity); }
   int reset() {
-    rayRows_ = rayCols_ = 0;
+    forget();
     return icpk_tsdf_reset(eng_.ctx());
   }
 
  private:
+  void forget() { rayRows_ = rayCols_ = 0, meshVertices_ = meshTriangles_ = meshNoNormal_ = 0; }
   Engine& eng_;
   icpk_tsdf_params p_;
   float fx_, cx_;
   int rayRows_ = 0, rayCols_ = 0;
+  int32_t meshVertices_ = 0, meshTriangles_ = 0, meshNoNormal_ = 0;
 };
 
 }  // namespace icp

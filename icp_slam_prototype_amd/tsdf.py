@@ -14,6 +14,12 @@ the model -- and the tracking loop it closes:
     tracker = ModelTracker(vol, pose=first_pose)
     for depth in frames:
         pose = tracker.track(depth)             # ray-cast at the last pose, align the frame, integrate it
+
+The model as something to keep (K21) -- a triangle mesh, consistently oriented and closed inside the known cells (it is
+open where the surface leaves them or the volume), extracted on the device:
+
+    mesh = vol.mesh(min_weight=2)               # dict(vertices (3, n), normals, intensity, ..., triangles (m, 3))
+    write_ply("model.ply", mesh)
 """
 import numpy as np
 
@@ -95,6 +101,19 @@ class TsdfVolume:
         self.ctx.tsdf_raycast_to_target()
         return n_hits
 
+    def mesh(self, min_weight=1):
+        """The surface as a triangle mesh (marching tetrahedra over the cells whose eight voxels have weight >=
+        min_weight): dict(vertices (3, n), normals (3, n), intensity, voxel_index, edge, triangles (m, 3) int32,
+        n_vertices, n_triangles, n_no_normal).  Vertices are ordered by owner voxel, then edge type; a vertex without a
+        normal holds (0, 0, 0) and is counted in n_no_normal.  color: whether the intensities mean anything."""
+        self.ctx.tsdf_extract_mesh(min_weight)
+        return dict(self.ctx.tsdf_get_mesh(), color=bool(self.params.flags & binding.TSDF_COLOR))
+
+    def set_planes(self, tsdf, weight, intensity=None):
+        """The counterpart of planes(): a saved model, or an analytic field, becomes the volume's content."""
+        self.ctx.tsdf_set(tsdf, weight, intensity)
+        self.n_points = self.n_no_normal = None
+
     def planes(self, intensity=False):
         """(tsdf, weight, intensity) as (dz, dy, dx) arrays."""
         return self.ctx.tsdf_get(intensity=intensity)
@@ -142,3 +161,63 @@ class ModelTracker:
         vol.integrate(depth, self.pose, intensity)
         self.frames += 1
         return self.pose.copy()
+
+
+_PLY_TYPES = {"float": "<f4", "float32": "<f4", "int": "<i4", "int32": "<i4", "uchar": "u1", "uint8": "u1"}
+
+
+def write_ply(path, mesh, color=None):
+    """A mesh of TsdfVolume.mesh as binary little-endian PLY: per vertex x, y, z, nx, ny, nz (and `intensity`, a float
+    scalar, when the mesh comes from a colour volume; color overrides mesh["color"]), per face a list of three int32
+    vertex indices."""
+    color = bool(mesh.get("color", False)) if color is None else bool(color)
+    v, nrm = np.asarray(mesh["vertices"], "<f4"), np.asarray(mesh["normals"], "<f4")
+    tri = np.asarray(mesh["triangles"], "<i4").reshape(-1, 3)
+    names = ["x", "y", "z", "nx", "ny", "nz"] + (["intensity"] if color else [])
+    vert = np.empty(v.shape[1], [(k, "<f4") for k in names])
+    for k in range(3):
+        vert[names[k]], vert[names[3 + k]] = v[k], nrm[k]
+    if color:
+        vert["intensity"] = np.asarray(mesh["intensity"], "<f4")
+    face = np.empty(tri.shape[0], [("n", "u1"), ("i", "<i4", (3,))])
+    face["n"], face["i"] = 3, tri
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {vert.size}"] + \
+        [f"property float {k}" for k in names] + [f"element face {face.size}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(vert.tobytes())
+        fh.write(face.tobytes())
+
+
+def read_ply(path):
+    """What write_ply wrote (binary little-endian, float vertex properties, triangles only), back as dict(vertices (3, n),
+    normals (3, n), intensity, triangles (m, 3), color)."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").split("\n")
+    if lines[0] != "ply" or lines[1] != "format binary_little_endian 1.0":
+        raise ValueError("not a binary little-endian PLY file")
+    nvert = nface = 0
+    props, element = [], None
+    for ln in lines[2:]:
+        w = ln.split()
+        if w[:1] == ["element"]:
+            element = w[1]
+            if element == "vertex":
+                nvert = int(w[2])
+            elif element == "face":
+                nface = int(w[2])
+        elif w[:1] == ["property"] and element == "vertex":
+            props.append((w[2], _PLY_TYPES[w[1]]))
+        elif w[:1] == ["property"] and element == "face" and w[1:4] != ["list", "uchar", "int"]:
+            raise ValueError("faces must be lists of uchar counts and int indices")
+    vert = np.frombuffer(data, np.dtype(props), nvert, end)
+    face = np.frombuffer(data, np.dtype([("n", "u1"), ("i", "<i4", (3,))]), nface, end + vert.nbytes)
+    if nface and not np.all(face["n"] == 3):
+        raise ValueError("only triangles are read")
+    color = "intensity" in vert.dtype.names
+    f32 = np.float32
+    return dict(vertices=np.stack([vert[k] for k in "xyz"]).astype(f32), normals=np.stack([vert[k] for k in ("nx", "ny", "nz")]).astype(f32),
+                intensity=vert["intensity"].astype(f32) if color else np.zeros(nvert, f32),
+                triangles=face["i"].astype(np.int32).reshape(-1, 3), color=color)

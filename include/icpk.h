@@ -1233,7 +1233,7 @@ int icpk_pose_graph_evaluate(icpk_ctx *ctx, int32_t n_nodes, const double *poses
 int icpk_get_pose_graph_trace(icpk_ctx *ctx, int32_t *n_iter, double *cost_out, double *lambda_out,
                               int32_t *pcg_iterations_out, int32_t *accepted_out);
 
-/* ---- TSDF volume (extension, K19, K20) ----------------------------------------------------------------------------
+/* ---- TSDF volume (extension, K19 - K21) ---------------------------------------------------------------------------
  * What the poses of K18 are for: the posed depth frames fused into one model.  One dense volume of truncated signed
  * distances per context, owned by it like the map: created by icpk_tsdf_create, released by icpk_tsdf_release or
  * icpk_destroy, and touched by no other call.  Every voxel is owned by one thread: no atomic, the same bytes on every
@@ -1353,7 +1353,68 @@ int icpk_get_pose_graph_trace(icpk_ctx *ctx, int32_t *n_iter, double *cost_out, 
  *     over host planes (intensity NULL exactly when params has no ICPK_TSDF_COLOR).  out: 8 planes of `count` floats.
  *     Compiled from the header the kernel includes (csrc/tsdf_rule.h).  Returns the number of listed hits, or
  *     ICPK_E_ARG: for what icpk_tsdf_create and icpk_tsdf_raycast refuse, a NULL array, first < 0, count < 0 or
- *     first + count > rows cols. */
+ *     first + count > rows cols.
+ *
+ * THE MESH RULE (icpk_tsdf_extract_mesh, K21): the surface as a triangle mesh, by marching tetrahedra over the Kuhn
+ * (Freudenthal) split of every cell.  float32, every operation rounded once, in the order written, no fused
+ * multiply-add, no libm, as the surface rule.  A corner or an edge type is a mask e = x + 2 y + 4 z (bit 0: +x).
+ *   1. cell     C = (i, j, k), 0 <= i_a <= dims_a - 2, with the corners C + e, e = 0 .. 7 (rule 5's order above).  KNOWN
+ *               iff all eight have w >= min_weight.  Only known cells emit triangles; a dim of 1 has no cells.
+ *   2. tetrahedra   six per cell, one per permutation (a, b, c) of the axes in lexicographic order xyz, xzy, yxz, yzx,
+ *               zxy, zyx: v0 = 0, v1 = 1 << a, v2 = v1 | 1 << b, v3 = 7.  xyz, yzx, zxy are EVEN, the others ODD.
+ *               Every edge of a tetrahedron joins a voxel V to V + m, m in 1 .. 7: V OWNS the edge, m is its type.
+ *   3. vertex   on edge (V, m), N = V + m: a crossing iff (f_V < 0) != (f_N < 0);  t = f_V / (f_V - f_N).
+ *               point      V's centre, plus fl(t * voxel) along every axis in m.
+ *               intensity  I_V + fl(t * fl(I_N - I_V)) on a colour volume, else 0.
+ *               normal     the surface rule's, from the gradients of V and N.  Where an end lacks a gradient or len is
+ *                          not > 0 the normal is (0, 0, 0) and the vertex is counted in n_no_normal -- and STILL LISTED.
+ *               listed     iff it is a crossing and at least one KNOWN cell contains the edge: the cells V - u, u & m == 0,
+ *                          that are in range (four for an axis edge, two for a face diagonal, one for the body diagonal).
+ *               order      ascending linear index of V, then ascending m.
+ *   4. triangles   the known cells in ascending linear index of their lower corner, their tetrahedra in rule 2's order.
+ *               The case is the mask whose bit n is f(v_n) < 0.  For an EVEN tetrahedron, pq naming the vertex on the
+ *               edge between positions p and q:
+ *                  0, 15  none                      8   (30,32,31)
+ *                  1   (01,02,03)                   9   (01,02,32) (01,32,31)
+ *                  2   (10,13,12)                   10  (10,32,12) (10,30,32)
+ *                  3   (02,03,13) (02,13,12)        11  (20,23,21)
+ *                  4   (20,21,23)                   12  (20,21,31) (20,31,30)
+ *                  5   (01,23,03) (01,21,23)        13  (10,12,13)
+ *                  6   (10,13,23) (10,23,20)        14  (01,03,02)
+ *                  7   (30,31,32)
+ *               An ODD tetrahedron swaps the second and the third vertex of every triangle.  With this winding
+ *               (b - a) x (c - a) points towards positive distance, as the normals do.  Behind the table: a position p
+ *               alone on its side gives the triangle on its edges to the other three in ascending order, second and
+ *               third swapped iff (p odd) != (the lone one is the positive one); two negative positions p < q and two
+ *               others r < s give (pr, ps, qs) (pr, qs, qr), both swapped iff p + q is even.
+ *               A triangle is three int32 indices into the vertex list.  A voxel Z with f == 0 puts the vertices of all
+ *               crossing edges into Z at Z in exact arithmetic: triangles without area, which are kept so that the mesh
+ *               stays closed.  IN FLOAT32 they coincide bit for bit only where centre(V) + voxel == centre(V + 1)
+ *               exactly, i.e. on a dyadic voxel and origin.  Elsewhere such a triangle is a sliver of rounding-error
+ *               size whose winding is decided by the rounding and may face inwards (voxel 0.05, a sphere through 30
+ *               lattice points: 152 triangles of area 0, 76 slivers, 39 of them inwards).  A consumer that needs strict
+ *               orientation drops triangles below an area threshold; the index list stays orientable either way.
+ *   5. counts   n_vertices, n_triangles, n_no_normal: integers.
+ * The mesh is closed inside the known cells -- open where the surface leaves them or the volume -- and consistently
+ * oriented: no directed edge occurs twice.  A vertex on an axis edge (m = 1, 2, 4) with a normal is the surface rule's crossing (V, log2 m), bit
+ * for bit.
+ *
+ * icpk_tsdf_extract_mesh   ICPK_E_NOT_SET without a volume; ICPK_E_ARG for min_weight outside 1 .. 65535, or when more
+ *     than ICPK_TSDF_MAX_SURFACE vertices or triangles would be listed.  Any output may be NULL.  One host wait (the
+ *     counts).  The mesh stays on the device until the next mesh extraction, icpk_tsdf_create, _reset, _set or _release.
+ *     It reads the planes and writes only the mesh: the surface list, the ray-cast maps and everything else the context
+ *     holds stay as they are, and icpk_tsdf_extract_surface and icpk_tsdf_raycast leave the mesh alone.
+ * icpk_tsdf_get_mesh   the mesh of the last extraction (ICPK_E_NOT_SET before it): arrays of n_vertices entries, edge the
+ *     type m; triangles: 3 n_triangles indices.  Any pointer may be NULL.
+ * icpk_tsdf_set      the counterpart of icpk_tsdf_get: the planes from host arrays of dims[0] dims[1] dims[2] entries (a
+ *     saved model, or an analytic field).  ICPK_E_NOT_SET without a volume; ICPK_E_ARG for a NULL tsdf or weight, a tsdf
+ *     that is not finite or outside [-1, 1], intensity given to a volume without colour, missing on one with it, or
+ *     outside [0, 1]; the volume stays then.  It drops the surface list, the ray-cast maps and the mesh, as _reset does.
+ * icpk_tsdf_mesh_host   host only, no context: rules 1 - 5 over host planes (intensity NULL exactly when params has no
+ *     ICPK_TSDF_COLOR), compiled from the header the kernels include (csrc/tsdf_rule.h).  counts = {n_vertices,
+ *     n_triangles, n_no_normal} is always filled once the arguments are accepted; the arrays (any may be NULL) are filled
+ *     when n_vertices <= cap_vertices and n_triangles <= cap_triangles, else ICPK_E_ARG.  ICPK_E_ARG also for what
+ *     icpk_tsdf_create and icpk_tsdf_extract_mesh refuse, a NULL tsdf, weight or counts, or a negative capacity. */
 #define ICPK_TSDF_COLOR 1 /* flags of icpk_tsdf_params: one intensity per voxel */
 #define ICPK_TSDF_MAX_VOXELS (1 << 30)
 #define ICPK_TSDF_MAX_SURFACE (1 << 28)
@@ -1400,6 +1461,15 @@ int icpk_tsdf_raycast_to_target(icpk_ctx *ctx);
 int icpk_tsdf_raycast_pixels(const icpk_tsdf_params *params, const icpk_tsdf_raycast_params *ray, const double pose[16],
                              const float *tsdf, const uint16_t *weight, const float *intensity, int64_t first,
                              int32_t count, float *out /* 8 x count */);
+int icpk_tsdf_extract_mesh(icpk_ctx *ctx, int32_t min_weight, int32_t *n_vertices, int32_t *n_triangles,
+                           int32_t *n_no_normal);
+int icpk_tsdf_get_mesh(icpk_ctx *ctx, float *x, float *y, float *z, float *nx, float *ny, float *nz, float *intensity,
+                       int32_t *voxel_index, uint8_t *edge, int32_t *triangles /* 3 x n_triangles */);
+int icpk_tsdf_set(icpk_ctx *ctx, const float *tsdf, const uint16_t *weight, const float *intensity);
+int icpk_tsdf_mesh_host(const icpk_tsdf_params *params, int32_t min_weight, const float *tsdf, const uint16_t *weight,
+                        const float *intensity, int64_t cap_vertices, int64_t cap_triangles, float *x, float *y, float *z,
+                        float *nx, float *ny, float *nz, float *intensity_out, int32_t *voxel_index, uint8_t *edge,
+                        int32_t *triangles, int64_t counts[3]);
 
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
