@@ -403,6 +403,23 @@ def build_solve_probe(force=False):
     return SOLVE_PROBE
 
 
+SCAN_PROBE = os.path.join(LIBDIR, "libscan_probe.so")
+
+
+def build_scan_probe(force=False):
+    """TEST INFRASTRUCTURE: tests/cpp/scan_probe.hip (csrc/block_scan.h run by one workgroup over host arrays), loaded by
+    tests/test_gpu_scan_probe.py only.  Compiled with exactly FLAGS, so its device code is generated as it is for
+    libicpk.so."""
+    src = os.path.join(ROOT, "tests", "cpp", "scan_probe.hip")
+    os.makedirs(LIBDIR, exist_ok=True)
+    newest = max(os.path.getmtime(p) for p in (src, os.path.join(CSRC, "block_scan.h"), os.path.abspath(__file__)))
+    if not force and os.path.exists(SCAN_PROBE) and os.path.getmtime(SCAN_PROBE) >= newest:
+        return SCAN_PROBE
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc] + FLAGS + ["-shared", "-x", "hip", src, "-o", SCAN_PROBE])
+    return SCAN_PROBE
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_cpp_test(force="--force" in sys.argv))

@@ -903,7 +903,6 @@ struct TsdfRayCompactArgs {
   const float* maps;
   int npix;            // <= TSDF_MAX_BLOCKS * TSDF_THREADS
   int* counts;         // [nblocks] valid pixels per chunk
-  int* dropped;        // [nblocks] zeroed (the scan sums it)
   long long* offsets;  // [nblocks + 1] the scan of counts
   long long capacity;  // entries of each of the list's planes
   float* list;         // 7 planes: x, y, z, nx, ny, nz, intensity
@@ -928,8 +927,7 @@ struct TsdfMeshArgs {
   uint8_t* edge;        // ... and its edge type 1 .. 7
   int* triangles;       // 3 per triangle
 };
-// count pass + two scans: totals[0] = vertices, totals[1] = vertices without a normal, totals[2] = triangles (device;
-// totals holds 4)
+// count pass + two scans: totals[0] = vertices, totals[1] = vertices without a normal, totals[2] = triangles (device)
 void launch_tsdf_mesh_count(const TsdfMeshArgs& a, int nblocks, long long* totals, hipStream_t s);
 // the vertices, then the triangles
 void launch_tsdf_mesh_scatter(const TsdfMeshArgs& a, int nblocks, hipStream_t s);

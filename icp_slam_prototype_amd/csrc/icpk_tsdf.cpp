@@ -48,11 +48,13 @@ struct icpk_tsdf_state {
   DevBuf<uint8_t> mesh_edge;
   size_t mesh_vcap = 0, mesh_tcap = 0;
   DevBuf<int> mesh_vcounts, mesh_tcounts, mesh_nonormal;
-  DevBuf<long long> mesh_voffsets, mesh_toffsets, mesh_totals;  // (mesh_totals: 4)
+  DevBuf<long long> mesh_voffsets, mesh_toffsets, mesh_totals;  // (mesh_totals: 3)
   PinnedBuf<long long> mesh_totals_host;
   bool have_mesh = false;
   int mesh_nv = 0, mesh_nt = 0, mesh_nn = 0;
   float* mesh_plane(int k) const { return mesh + (size_t)k * mesh_vcap; }
+  // the volume's intensity plane; null for a volume without ICPK_TSDF_COLOR
+  float* intensity_plane() const { return (p.flags & ICPK_TSDF_COLOR) ? intensity.get() : nullptr; }
 };
 
 void icpk_tsdf_free(icpk_ctx* ctx) {
@@ -160,6 +162,25 @@ int list_to_target(icpk_ctx* ctx, const icpk_tsdf_state* v, float* const list[7]
     ctx->have_tgt_colors = true;
   }
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+// a list on the device: seven planes of cap floats (plane k at planes + k * cap), the voxel of every entry and its byte
+// plane (the axis, or the edge type)
+struct DevList {
+  const float* planes;
+  size_t cap;
+  const int* voxel;
+  const uint8_t* byte;
+};
+
+// the first n entries of the list to the host; a null destination is skipped.  The caller synchronises
+int download_list(icpk_ctx* ctx, const DevList& l, size_t n, float* const out[7], int32_t* voxel_out, uint8_t* byte_out) {
+  if (n == 0) return ICPK_OK;
+  for (int k = 0; k < 7; ++k)
+    if (out[k]) ICPK_HIP(ctx, hipMemcpyAsync(out[k], l.planes + (size_t)k * l.cap, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (voxel_out) ICPK_HIP(ctx, hipMemcpyAsync(voxel_out, l.voxel, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (byte_out) ICPK_HIP(ctx, hipMemcpyAsync(byte_out, l.byte, n, hipMemcpyDeviceToHost, ctx->stream));
   return ICPK_OK;
 }
 
@@ -276,7 +297,7 @@ int icpk_tsdf_integrate(icpk_ctx* ctx, const uint16_t* depth, const float* inten
   a.fr = make_frame(v->p, R, t, rows, cols, fx, cx);
   a.depth = image;
   a.intensity_image = color ? v->intensity_image.get() : nullptr;
-  a.tsdf = v->tsdf, a.weight = v->weight, a.intensity = color ? v->intensity.get() : nullptr;
+  a.tsdf = v->tsdf, a.weight = v->weight, a.intensity = v->intensity_plane();
   a.n = v->n, a.chunk = tsdf_chunk(v->n);
   a.slots = v->slots;
   launch_tsdf_integrate(a, tsdf_blocks(v->n), v->totals, ctx->stream);
@@ -333,11 +354,7 @@ int icpk_tsdf_extract_surface(icpk_ctx* ctx, int32_t min_weight, int32_t* n_poin
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   v->have_surface = false;
   TsdfExtractArgs a{};
-  a.v.tsdf = v->tsdf, a.v.weight = v->weight;
-  a.v.intensity = (v->p.flags & ICPK_TSDF_COLOR) ? v->intensity.get() : nullptr;
-  for (int k = 0; k < 3; ++k) a.v.dims[k] = v->p.dims[k], a.v.origin[k] = v->p.origin[k];
-  a.v.voxel = v->p.voxel;
-  a.v.min_weight = min_weight;
+  a.v = make_planes(v->p, v->tsdf, v->weight, v->intensity_plane(), min_weight);
   a.n = v->n, a.chunk = tsdf_chunk(v->n);
   a.counts = v->slots, a.dropped = v->dropped, a.offsets = v->offsets;
   const int nblocks = tsdf_blocks(v->n);
@@ -378,13 +395,9 @@ int icpk_tsdf_get_surface(icpk_ctx* ctx, float* x, float* y, float* z, float* nx
   icpk_tsdf_state* v = ctx->tsdf;
   if (!v || !v->have_surface) return fail(ctx, ICPK_E_NOT_SET, "no surface list (icpk_tsdf_extract_surface)");
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t n = (size_t)v->surf_n;
   float* const out[7] = {x, y, z, nx, ny, nz, intensity};
-  for (int k = 0; k < 7 && n > 0; ++k)
-    if (out[k]) ICPK_HIP(ctx, hipMemcpyAsync(out[k], v->plane(k), n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  if (voxel_index && n > 0)
-    ICPK_HIP(ctx, hipMemcpyAsync(voxel_index, v->surf_voxel, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (axis && n > 0) ICPK_HIP(ctx, hipMemcpyAsync(axis, v->surf_axis, n, hipMemcpyDeviceToHost, ctx->stream));
+  const DevList surface{v->surf, v->surf_cap, v->surf_voxel, v->surf_axis};
+  if (int rc = download_list(ctx, surface, (size_t)v->surf_n, out, voxel_index, axis)) return rc;
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ICPK_OK;
 }
@@ -410,11 +423,11 @@ int icpk_tsdf_extract_mesh(icpk_ctx* ctx, int32_t min_weight, int32_t* n_vertice
   if (!rc) rc = v->mesh_nonormal.reserve(ctx, TSDF_MAX_BLOCKS);
   if (!rc) rc = v->mesh_voffsets.reserve(ctx, TSDF_MAX_BLOCKS + 1);
   if (!rc) rc = v->mesh_toffsets.reserve(ctx, TSDF_MAX_BLOCKS + 1);
-  if (!rc) rc = v->mesh_totals.reserve(ctx, 4);
-  if (!rc) rc = v->mesh_totals_host.reserve(ctx, 4);
+  if (!rc) rc = v->mesh_totals.reserve(ctx, 3);
+  if (!rc) rc = v->mesh_totals_host.reserve(ctx, 3);
   if (rc) return rc;
   TsdfMeshArgs a{};
-  a.v = make_planes(v->p, v->tsdf, v->weight, (v->p.flags & ICPK_TSDF_COLOR) ? v->intensity.get() : nullptr, min_weight);
+  a.v = make_planes(v->p, v->tsdf, v->weight, v->intensity_plane(), min_weight);
   a.n = v->n, a.chunk = tsdf_chunk(v->n);
   a.vcounts = v->mesh_vcounts, a.tcounts = v->mesh_tcounts, a.nonormal = v->mesh_nonormal;
   a.voffsets = v->mesh_voffsets, a.toffsets = v->mesh_toffsets;
@@ -422,7 +435,7 @@ int icpk_tsdf_extract_mesh(icpk_ctx* ctx, int32_t min_weight, int32_t* n_vertice
   launch_tsdf_mesh_count(a, nblocks, v->mesh_totals, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
   // the one host wait: the lists are allocated for the counts
-  ICPK_HIP(ctx, hipMemcpyAsync(v->mesh_totals_host, v->mesh_totals, 4 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipMemcpyAsync(v->mesh_totals_host, v->mesh_totals, 3 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const long long nv = v->mesh_totals_host[0], nn = v->mesh_totals_host[1], nt = v->mesh_totals_host[2];
   if (nv > ICPK_TSDF_MAX_SURFACE || nt > ICPK_TSDF_MAX_SURFACE)
@@ -462,13 +475,10 @@ int icpk_tsdf_get_mesh(icpk_ctx* ctx, float* x, float* y, float* z, float* nx, f
   icpk_tsdf_state* v = ctx->tsdf;
   if (!v || !v->have_mesh) return fail(ctx, ICPK_E_NOT_SET, "no mesh (icpk_tsdf_extract_mesh)");
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t n = (size_t)v->mesh_nv, m = (size_t)v->mesh_nt;
+  const size_t m = (size_t)v->mesh_nt;
   float* const out[7] = {x, y, z, nx, ny, nz, intensity};
-  for (int k = 0; k < 7 && n > 0; ++k)
-    if (out[k]) ICPK_HIP(ctx, hipMemcpyAsync(out[k], v->mesh_plane(k), n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  if (voxel_index && n > 0)
-    ICPK_HIP(ctx, hipMemcpyAsync(voxel_index, v->mesh_voxel, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (edge && n > 0) ICPK_HIP(ctx, hipMemcpyAsync(edge, v->mesh_edge, n, hipMemcpyDeviceToHost, ctx->stream));
+  const DevList vertices{v->mesh, v->mesh_vcap, v->mesh_voxel, v->mesh_edge};
+  if (int rc = download_list(ctx, vertices, (size_t)v->mesh_nv, out, voxel_index, edge)) return rc;
   if (triangles && m > 0)
     ICPK_HIP(ctx, hipMemcpyAsync(triangles, v->mesh_tri, 3 * m * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -590,7 +600,7 @@ int icpk_tsdf_raycast(icpk_ctx* ctx, const icpk_tsdf_raycast_params* params, con
     return rc;
   }
   v->have_raycast = false;  // (the planes change place with the image's size)
-  a.v = make_planes(v->p, v->tsdf, v->weight, (v->p.flags & ICPK_TSDF_COLOR) ? v->intensity.get() : nullptr, rp.min_weight);
+  a.v = make_planes(v->p, v->tsdf, v->weight, v->intensity_plane(), rp.min_weight);
   a.maps = v->ray_maps;
   a.tiles_x = tsdf_ray_tiles(rp.cols);
   a.ntiles = a.tiles_x * tsdf_ray_tiles(rp.rows);
@@ -631,7 +641,7 @@ int icpk_tsdf_raycast_to_target(icpk_ctx* ctx) {
   TsdfRayCompactArgs a{};
   a.maps = v->ray_maps;
   a.npix = v->ray_rows * v->ray_cols;
-  a.counts = v->slots, a.dropped = v->dropped, a.offsets = v->offsets;
+  a.counts = v->slots, a.offsets = v->offsets;
   launch_tsdf_ray_count(a, v->totals, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
   // the one host wait: the target is allocated for the count

@@ -8,6 +8,7 @@
 //   pass 1: per-1024-pixel block count (wave64 ballot + popcount)
 //   pass 2: exclusive scan of the block counts (one workgroup)
 //   pass 3: in-block rank from ballots, scatter.
+#include "block_scan.h"
 #include "icpk_internal.h"
 
 namespace icpk {
@@ -76,38 +77,18 @@ __global__ __launch_bounds__(BP_THREADS) void bp_count_pair_kernel(const BpPair 
   bp_count_body(im.depth, npix, im.counts, blockIdx.x, im.host_src, im.raw_out, im.sub_key, im.sub_factor);
 }
 
-// exclusive scan in place; block_counts[nblocks] receives the total
-__device__ __forceinline__ void bp_scan_body(int* __restrict__ block_counts, int nblocks, int* __restrict__ n_out) {
-  __shared__ int carry;
-  __shared__ int wsum[4];
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nblocks; base += 256) {
-    const int i = base + threadIdx.x;
-    const int v = i < nblocks ? block_counts[i] : 0;
-    int incl = v;  // wave64 inclusive scan
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if ((threadIdx.x & 63) >= d) incl += up;
-    }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
-    const int c = carry;
-    if (i < nblocks) block_counts[i] = c + woff + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 255) carry = c + woff + incl;
-    __syncthreads();
-  }
+// exclusive scan in place; block_counts[nblocks] and *n_out receive the total (thread 0), which is returned
+__device__ __forceinline__ int bp_scan_body(int* __restrict__ block_counts, int nblocks, int* __restrict__ n_out) {
+  const int total = scan_rounds<BP_THREADS>(block_counts, block_counts, nblocks);
   if (threadIdx.x == 0) {
-    block_counts[nblocks] = carry;
-    *n_out = carry;
+    block_counts[nblocks] = total;
+    *n_out = total;
   }
+  return total;
 }
 
-__global__ void bp_scan_kernel(int* __restrict__ block_counts, int nblocks, int* __restrict__ n_out) {
+__global__ __launch_bounds__(BP_THREADS) void bp_scan_kernel(int* __restrict__ block_counts, int nblocks,
+                                                             int* __restrict__ n_out) {
   bp_scan_body(block_counts, nblocks, n_out);
 }
 
@@ -117,12 +98,13 @@ __global__ void bp_scan_kernel(int* __restrict__ block_counts, int nblocks, int*
 // to the mapped word n_host[blockIdx.x]
 __device__ __forceinline__ void bp_scan_publish_body(const BpImage& im, int nblocks, int* __restrict__ n_out,
                                                      int* __restrict__ n_host) {
-  bp_scan_body(im.counts, nblocks, n_out + blockIdx.x);
+  const int total = bp_scan_body(im.counts, nblocks, n_out + blockIdx.x);
   if (n_host && threadIdx.x == 0)  // (the thread that wrote the total)
-    __hip_atomic_store(n_host + blockIdx.x, im.counts[nblocks], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(n_host + blockIdx.x, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-__global__ void bp_scan_pair_kernel(const BpPair b, int nblocks, int* __restrict__ n_out, int* __restrict__ n_host) {
+__global__ __launch_bounds__(BP_THREADS) void bp_scan_pair_kernel(const BpPair b, int nblocks, int* __restrict__ n_out,
+                                                                  int* __restrict__ n_host) {
   bp_scan_publish_body(b.im[blockIdx.x], nblocks, n_out, n_host);
 }
 
@@ -330,8 +312,8 @@ __global__ __launch_bounds__(BP_THREADS) void bp_count_frames_kernel(const BpFra
   bp_count_body(im.depth, npix, im.counts, blockIdx.x, im.host_src, im.raw_out, im.sub_key, im.sub_factor);
 }
 
-__global__ void bp_scan_frames_kernel(const BpFrameBatch b, int nblocks, int per_image, int* __restrict__ n_out,
-                                      int* __restrict__ n_host) {
+__global__ __launch_bounds__(BP_THREADS) void bp_scan_frames_kernel(const BpFrameBatch b, int nblocks, int per_image,
+                                                                    int* __restrict__ n_out, int* __restrict__ n_host) {
   const BpImage im = bp_frame_image(b.p[blockIdx.x >> 1], blockIdx.x & 1, per_image);
   bp_scan_publish_body(im, nblocks, n_out, n_host);
 }
@@ -351,7 +333,7 @@ void launch_backproject_frames(const BpFrameBatch& b, int count, int rows, int c
   const int nblocks = (npix + BP_BLOCK - 1) / BP_BLOCK;
   const int per_image = nblocks + 2;  // (icpk_backproject_pair's spacing of the two images' counts)
   hipLaunchKernelGGL(bp_count_frames_kernel, dim3(nblocks, 2 * count), dim3(BP_THREADS), 0, s, b, npix, per_image);
-  hipLaunchKernelGGL(bp_scan_frames_kernel, dim3(2 * count), dim3(256), 0, s, b, nblocks, per_image, n_out, n_host);
+  hipLaunchKernelGGL(bp_scan_frames_kernel, dim3(2 * count), dim3(BP_THREADS), 0, s, b, nblocks, per_image, n_out, n_host);
   hipLaunchKernelGGL(bp_scatter_frames_kernel, dim3(nblocks, 2 * count), dim3(BP_THREADS), 0, s, b, npix, cols, nblocks,
                      per_image, fx, cx, ox, oy, oz);
 }
@@ -361,7 +343,7 @@ void launch_backproject_pair(const BpPair& b, int rows, int cols, float fx, floa
   const int npix = rows * cols;
   const int nblocks = (npix + BP_BLOCK - 1) / BP_BLOCK;
   hipLaunchKernelGGL(bp_count_pair_kernel, dim3(nblocks, 2), dim3(BP_THREADS), 0, s, b, npix);
-  hipLaunchKernelGGL(bp_scan_pair_kernel, dim3(2), dim3(256), 0, s, b, nblocks, n_out, n_host);
+  hipLaunchKernelGGL(bp_scan_pair_kernel, dim3(2), dim3(BP_THREADS), 0, s, b, nblocks, n_out, n_host);
   hipLaunchKernelGGL(bp_scatter_pair_kernel, dim3(nblocks, 2), dim3(BP_THREADS), 0, s, b, npix, cols, nblocks, fx, cx, ox,
                      oy, oz, rt, posed);
 }
@@ -372,7 +354,7 @@ void launch_backproject(const uint16_t* depth, int rows, int cols, float fx, flo
   const int npix = rows * cols;
   const int nblocks = (npix + BP_BLOCK - 1) / BP_BLOCK;
   hipLaunchKernelGGL(bp_count_kernel, dim3(nblocks), dim3(BP_THREADS), 0, s, depth, npix, block_counts, sub_key, sub_factor);
-  hipLaunchKernelGGL(bp_scan_kernel, dim3(1), dim3(256), 0, s, block_counts, nblocks, n_out);
+  hipLaunchKernelGGL(bp_scan_kernel, dim3(1), dim3(BP_THREADS), 0, s, block_counts, nblocks, n_out);
   if (nx)
     hipLaunchKernelGGL(bp_scatter_kernel<true>, dim3(nblocks), dim3(BP_THREADS), 0, s, depth, npix, cols, fx, cx, ox, oy,
                        oz, block_counts, x, y, z, nx, ny, nz, normals_mode, sub_key, sub_factor);

@@ -11,6 +11,7 @@
 //   fast_scatter  (x, y, response) of every kept pixel at its rank: row-major order                   1 launch
 //   fast_cloud    the detected list back-projected from a depth image, posed, compacted in list order
 //                 into the context's source / target planes, padded; the count to a mapped word       1 launch
+#include "block_scan.h"
 #include "icpk.h"
 #include "icpk_internal.h"
 
@@ -147,31 +148,10 @@ __global__ __launch_bounds__(FT_THREADS) void fast_tile_kernel(const uint8_t* __
   }
 }
 
-// exclusive scan in place of m ints by one workgroup: lane t owns the contiguous run [t * per, (t + 1) * per)
+// exclusive scan in place of m ints by one workgroup, one contiguous run per lane; *total = the sum
 __global__ __launch_bounds__(FT_SCAN_THREADS) void fast_scan_kernel(int* __restrict__ a, int m, int* __restrict__ total) {
-  __shared__ int wsum[FT_SCAN_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int per = (m + FT_SCAN_THREADS - 1) / FT_SCAN_THREADS;
-  const int b = threadIdx.x * per, e = min(b + per, m);
-  int s = 0;
-  for (int k = b; k < e; ++k) s += a[k];
-  int incl = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += up;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int woff = 0;
-  for (int w = 0; w < wave; ++w) woff += wsum[w];
-  int run = woff + incl - s;
-  for (int k = b; k < e; ++k) {
-    const int v = a[k];
-    a[k] = run;
-    run += v;
-  }
-  if (threadIdx.x == FT_SCAN_THREADS - 1) *total = woff + incl;
+  const int sum = scan_runs<FT_SCAN_THREADS>(a, m);
+  if (threadIdx.x == 0) *total = sum;
 }
 
 // one wave per (row, tile column): the kept pixels of its mask at offset + rank among them

@@ -11,6 +11,7 @@
 //      filter_emit_kernel    n_out; then the kept points (and normals) go to their rank in input order
 // Nothing here is an atomic on a float and no sum depends on the order in which candidates arrive: a point's k smallest
 // distances are selected as 64-bit (distance bits, index) keys, which are all different, and added in ascending order.
+#include "block_scan.h"
 #include "grid_walk.h"
 #include "icpk_internal.h"
 #include "pair_reduce.h"
@@ -191,25 +192,7 @@ __global__ __launch_bounds__(RED_THREADS) void filter_threshold_kernel(const Fil
   a.summary[3] = mu + (double)a.std_ratio * sigma;
 }
 
-// ---- order-preserving compaction (the pattern of K4 and K11) ----------------------------------------------------
-// exclusive scan of one int per lane over a workgroup of 256; *total: the sum over the workgroup
-__device__ __forceinline__ int block_scan_256(int v, int* total) {
-  __shared__ int wsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(inc, d);
-    if (lane >= d) inc += t;
-  }
-  __syncthreads();  // (wsum of a previous call has been read)
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; ++w) base += wsum[w];
-  *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  return base + inc - v;
-}
-
+// ---- order-preserving compaction (count per block, scan, emit by rank: block_scan.h) -----------------------------
 __device__ __forceinline__ bool filter_keeps(const FilterArgs& a, int i, double T, bool* dropped) {
   const bool fin = finite3(a.x[i], a.y[i], a.z[i]);
   *dropped = !fin;
@@ -231,24 +214,15 @@ __global__ __launch_bounds__(256) void filter_flag_kernel(const FilterArgs a) {
     mine += keep;
     gone += dropped;
   }
-  int total;
-  block_scan_256(mine, &total);
+  const int total = block_total<256>(mine);
   if (threadIdx.x == 0) a.bsum[blockIdx.x] = total;
   if (gone) atomicAdd(&a.counts[1], gone);  // (an integer count: the order of arrival does not show)
 }
 
 // bsum[nb] -> its exclusive scan in place; counts[0] := the total
 __global__ __launch_bounds__(256) void filter_scan_kernel(int* __restrict__ bsum, int nb, int* __restrict__ counts) {
-  int carry = 0;
-  for (int base = 0; base < nb; base += 256) {
-    const int k = base + threadIdx.x;
-    const int v = k < nb ? bsum[k] : 0;
-    int total;
-    const int ex = block_scan_256(v, &total);
-    if (k < nb) bsum[k] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) counts[0] = carry;
+  const int total = scan_rounds<256>(bsum, bsum, nb);
+  if (threadIdx.x == 0) counts[0] = total;
 }
 
 __global__ __launch_bounds__(256) void filter_emit_kernel(const FilterArgs a) {
@@ -261,7 +235,7 @@ __global__ __launch_bounds__(256) void filter_emit_kernel(const FilterArgs a) {
     mine += keep[k];
   }
   int total;
-  int pos = a.bsum[blockIdx.x] + block_scan_256(mine, &total);
+  int pos = a.bsum[blockIdx.x] + block_excl_scan<256>(mine, &total);
   for (int k = 0; k < 4; ++k) {
     const int i = i0 + k;
     if (i >= a.n) break;

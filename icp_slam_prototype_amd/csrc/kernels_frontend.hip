@@ -9,6 +9,7 @@
 //   * depth filter: SLAM.cpp:553-574 filterDepthImage = range clamp to [min, max] (else 0), then
 //     cv::dilate and cv::erode with a 5x5 rectangle, fused into ONE LDS-tiled pass over the
 //     uint16 image (separable max then min, halo of 4 pixels).
+#include "block_scan.h"
 #include "icpk_internal.h"
 
 namespace icpk {
@@ -78,33 +79,12 @@ __global__ __launch_bounds__(AS_THREADS) void as_scatter_kernel(const nn_key_t* 
 }
 
 // exclusive scan in place of <= a few thousand block counts; counts[nblocks] and *total = sum
-__global__ void as_scan_kernel(int* __restrict__ counts, int nblocks, int* __restrict__ total) {
-  __shared__ int carry;
-  __shared__ int wsum[4];
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nblocks; base += 256) {
-    const int i = base + threadIdx.x;
-    const int v = i < nblocks ? counts[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if ((threadIdx.x & 63) >= d) incl += up;
-    }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
-    const int c = carry;
-    if (i < nblocks) counts[i] = c + woff + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 255) carry = c + woff + incl;
-    __syncthreads();
-  }
+__global__ __launch_bounds__(AS_THREADS) void as_scan_kernel(int* __restrict__ counts, int nblocks,
+                                                             int* __restrict__ total) {
+  const int sum = scan_rounds<AS_THREADS>(counts, counts, nblocks);
   if (threadIdx.x == 0) {
-    counts[nblocks] = carry;
-    *total = carry;
+    counts[nblocks] = sum;
+    *total = sum;
   }
 }
 
@@ -113,7 +93,7 @@ void launch_assoc_split(const nn_key_t* best, int nq, float max_dist, int* block
   if (nq <= 0) return;
   const int nblocks = (nq + AS_BLOCK - 1) / AS_BLOCK;
   hipLaunchKernelGGL(as_count_kernel, dim3(nblocks), dim3(AS_THREADS), 0, s, best, nq, max_dist, block_counts);
-  hipLaunchKernelGGL(as_scan_kernel, dim3(1), dim3(256), 0, s, block_counts, nblocks, n_accepted);
+  hipLaunchKernelGGL(as_scan_kernel, dim3(1), dim3(AS_THREADS), 0, s, block_counts, nblocks, n_accepted);
   hipLaunchKernelGGL(as_scatter_kernel, dim3(nblocks), dim3(AS_THREADS), 0, s, best, nq, max_dist, block_counts, assoc_q,
                      assoc_t, assoc_d, rej_q);
 }

@@ -15,6 +15,7 @@
 // batch-sized buffers is the grid and the slots themselves.
 // Tiles are 1024 items (16 wave64), one per lane.  The rank of an item among the items of its tile with the same
 // digit comes from 9 ballots (the lanes of a wave whose digit equals this lane's) and per-wave digit counts in LDS.
+#include "block_scan.h"
 #include "icpk.h"
 #include "icpk_internal.h"
 #include "map_device.h"
@@ -85,32 +86,10 @@ __global__ __launch_bounds__(MAP_TILE) void map_hist_kernel(const int* __restric
   tile_hist(valid ? ((unsigned)keys[i] >> shift) & (MAP_RADIX - 1) : 0u, valid, hist, ntiles);
 }
 
-// exclusive scan in place of m ints by one workgroup: lane t owns the contiguous run [t * per, (t + 1) * per);
-// *total (if given) = the sum
+// exclusive scan in place of m ints by one workgroup, one contiguous run per lane; *total (if given) = the sum
 __global__ __launch_bounds__(MAP_TILE) void map_scan_kernel(int* __restrict__ a, int m, int* __restrict__ total) {
-  __shared__ int wsum[MAP_WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int per = (m + MAP_TILE - 1) / MAP_TILE;
-  const int b = threadIdx.x * per, e = min(b + per, m);
-  int s = 0;
-  for (int k = b; k < e; ++k) s += a[k];
-  int incl = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += up;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int woff = 0;
-  for (int w = 0; w < wave; ++w) woff += wsum[w];
-  int run = woff + incl - s;
-  for (int k = b; k < e; ++k) {
-    const int v = a[k];
-    a[k] = run;
-    run += v;
-  }
-  if (threadIdx.x == MAP_TILE - 1 && total) *total = woff + incl;
+  const int sum = scan_runs<MAP_TILE>(a, m);
+  if (threadIdx.x == 0 && total) *total = sum;
 }
 
 // one stable radix pass: item i of tile t with digit d goes to base[d][t] + (items of tile t with digit d before it)

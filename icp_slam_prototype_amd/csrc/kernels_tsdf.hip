@@ -9,6 +9,7 @@
 // most TSDF_MAX_BLOCKS contiguous chunks of a multiple of TSDF_THREADS voxels, one workgroup per chunk, which it
 // sweeps TSDF_THREADS voxels at a time.  A wave therefore reads and writes 64 consecutive voxels: 256 contiguous bytes
 // of the tsdf plane, 128 of the weight plane.
+#include "block_scan.h"
 #include "icpk_internal.h"
 #include "tsdf_rule.h"
 
@@ -24,7 +25,9 @@ struct VoxelIndex {
   }
 };
 
-// the sum of v over the workgroup, valid in thread 0 (integers: the order does not matter)
+// the sum of v over the workgroup, in every thread (integers: the order does not matter).  One barrier, on the caller's
+// own four words of LDS: the count kernels below call it once per sum, at their end, and never again on the same words,
+// so they do not pay for block_scan.h's barrier in front of the store
 __device__ __forceinline__ int block_sum(int v, int* lds4) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
@@ -106,48 +109,25 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_count_kernel(const TsdfExtr
   }
 }
 
-// pass 2 (one workgroup; the shape of K4's bp_scan_body): offsets[b] = the crossings listed by the chunks before b,
-// offsets[nblocks] = totals[0] = their number; totals[1] = the sum of the dropped ones.  64-bit: 3 x 2^30 crossings
-// do not fit an int
+// pass 2 (one workgroup): offsets[b] = the crossings listed by the chunks before b, offsets[nblocks] = totals[0] =
+// their number; totals[1] = the sum of `extra` (the dropped ones), or untouched where extra is null.  64-bit: 3 x 2^30
+// crossings do not fit an int, while a round sums 256 chunks of at most 3 x 2^17 each, and a thread's share of
+// `extra` is at most 32 such chunks: both below 2^31
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_scan_kernel(const int* __restrict__ counts,
-                                                                  const int* __restrict__ dropped, int nblocks,
+                                                                  const int* __restrict__ extra, int nblocks,
                                                                   long long* __restrict__ offsets,
                                                                   long long* __restrict__ totals) {
-  __shared__ long long carry;
-  __shared__ int wsum[4];
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  long long nd = 0;
-  for (int base = 0; base < nblocks; base += TSDF_THREADS) {
-    const int i = base + threadIdx.x;
-    const int v = i < nblocks ? counts[i] : 0;
-    nd += i < nblocks ? dropped[i] : 0;
-    int incl = v;  // wave64 inclusive scan (a round sums 256 chunks of at most 3 x 2^17 crossings each: below 2^31)
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if ((threadIdx.x & 63) >= d) incl += up;
-    }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
-    const long long c = carry;
-    if (i < nblocks) offsets[i] = c + woff + incl - v;
-    __syncthreads();
-    if (threadIdx.x == TSDF_THREADS - 1) carry = c + woff + incl;
-    __syncthreads();
+  const long long listed = scan_rounds<TSDF_THREADS>(counts, offsets, nblocks);
+  long long ne = 0;
+  if (extra) {  // (uniform)
+    int mine = 0;
+    for (int i = threadIdx.x; i < nblocks; i += TSDF_THREADS) mine += extra[i];
+    ne = block_total<TSDF_THREADS>((long long)mine);
   }
-  // the dropped ones: a 64-bit sum over the workgroup through LDS
-  __shared__ long long dsum[TSDF_THREADS];
-  dsum[threadIdx.x] = nd;
-  __syncthreads();
   if (threadIdx.x == 0) {
-    long long t = 0;
-    for (int i = 0; i < TSDF_THREADS; ++i) t += dsum[i];
-    offsets[nblocks] = carry;
-    totals[0] = carry;
-    totals[1] = t;
+    offsets[nblocks] = listed;
+    totals[0] = listed;
+    if (extra) totals[1] = ne;
   }
 }
 
@@ -157,7 +137,6 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_scatter_kernel(const TsdfEx
   const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
   const VoxelIndex vi{(unsigned)a.v.dims[0], (unsigned)a.v.dims[0] * (unsigned)a.v.dims[1]};
   if (a.offsets[blockIdx.x + 1] == a.offsets[blockIdx.x]) return;  // (uniform: nothing of this chunk is listed)
-  __shared__ int wsum[4];
   long long run = a.offsets[blockIdx.x];
   for (long long base = begin; base < end; base += TSDF_THREADS) {
     const long long at = base + threadIdx.x;
@@ -165,18 +144,8 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_scatter_kernel(const TsdfEx
     float fv = 0.f;
     crossing_statuses(a.v, vi, at, at < end, c, fv, st);
     const int mine = (st[0] == TSDF_CROSSING) + (st[1] == TSDF_CROSSING) + (st[2] == TSDF_CROSSING);
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if ((threadIdx.x & 63) >= d) incl += up;
-    }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
-    const int round_total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    long long pos = run + woff + incl - mine;
+    int round_total;
+    long long pos = run + block_excl_scan<TSDF_THREADS>(mine, &round_total);
     for (int axis = 0; axis < 3; ++axis) {
       if (st[axis] != TSDF_CROSSING) continue;
       TsdfCrossing cr;
@@ -191,7 +160,6 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_scatter_kernel(const TsdfEx
       pos += 1;
     }
     run += round_total;
-    __syncthreads();  // (wsum is rewritten by the next round)
   }
 }
 
@@ -230,28 +198,15 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_ray_count_kernel(const Tsdf
   const int mine = pix < a.npix && a.maps[6LL * a.npix + pix] > 0.f;
   __shared__ int lds4[4];
   const int total = block_sum(mine, lds4);
-  if (threadIdx.x == 0) {
-    a.counts[blockIdx.x] = total;
-    a.dropped[blockIdx.x] = 0;
-  }
+  if (threadIdx.x == 0) a.counts[blockIdx.x] = total;
 }
 
 // pass 3: every valid pixel to its place, the chunk's offset plus its rank among the chunk's valid pixels
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_ray_scatter_kernel(const TsdfRayCompactArgs a) {
   const int pix = blockIdx.x * TSDF_THREADS + threadIdx.x;
   const int mine = pix < a.npix && a.maps[6LL * a.npix + pix] > 0.f;
-  __shared__ int wsum[4];
-  int incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d, 64);
-    if ((threadIdx.x & 63) >= d) incl += up;
-  }
-  if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  int woff = 0;
-  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
-  const long long pos = a.offsets[blockIdx.x] + woff + incl - mine;
+  int total;
+  const long long pos = a.offsets[blockIdx.x] + block_excl_scan<TSDF_THREADS>(mine, &total);
   if (!mine || pos >= a.capacity) return;  // (pos < capacity always: the capacity is the scan's total)
 #pragma unroll
   for (int k = 0; k < 7; ++k) a.list[k * a.capacity + pos] = a.maps[(long long)(k < 6 ? k : 7) * a.npix + pix];
@@ -261,23 +216,6 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_ray_scatter_kernel(const Ts
 // K19's chunk geometry and its count / scan / scatter, twice over: once for the vertices a voxel owns (the crossings on
 // its seven edges), once for the triangles of the cell it is the lower corner of.  Both are a function of the voxel's
 // own neighbourhood (tsdf_mesh_voxel), so the count pass and the two scatters agree without talking to each other.
-
-// the exclusive rank of `mine` among the workgroup's threads and the workgroup's total (wsum: 4 ints of LDS; the
-// caller synchronises before the next use of wsum)
-__device__ __forceinline__ int block_rank(int mine, int* wsum, int* total) {
-  int incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d, 64);
-    if ((threadIdx.x & 63) >= d) incl += up;
-  }
-  if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-  __syncthreads();
-  int woff = 0;
-  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
-  *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  return woff + incl - mine;
-}
 
 // pass 1: per chunk, the listed vertices, those among them without a normal, and the triangles
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_mesh_count_kernel(const TsdfMeshArgs a) {
@@ -317,7 +255,6 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_mesh_vertex_kernel(const Ts
   const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
   const VoxelIndex vi{(unsigned)a.v.dims[0], (unsigned)a.v.dims[0] * (unsigned)a.v.dims[1]};
   if (a.voffsets[blockIdx.x + 1] == a.voffsets[blockIdx.x]) return;  // (uniform: the chunk owns no vertex)
-  __shared__ int wsum[4];
   long long run = a.voffsets[blockIdx.x];
   for (long long base = begin; base < end; base += TSDF_THREADS) {
     const long long at = base + threadIdx.x;
@@ -328,7 +265,7 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_mesh_vertex_kernel(const Ts
       tsdf_mesh_voxel(a.v, c, at, true, &mv);
     }
     int round_total;
-    long long pos = run + block_rank(__popc((unsigned)mv.vertices), wsum, &round_total);
+    long long pos = run + block_excl_scan<TSDF_THREADS>((int)__popc((unsigned)mv.vertices), &round_total);
     for (int m = 1; m < 8; ++m) {
       if (!((mv.vertices >> (m - 1)) & 1)) continue;
       TsdfMeshVertex vx;
@@ -343,7 +280,6 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_mesh_vertex_kernel(const Ts
       pos += 1;
     }
     run += round_total;
-    __syncthreads();  // (wsum is rewritten by the next round)
   }
 }
 
@@ -372,7 +308,6 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_mesh_triangle_kernel(const 
   const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
   const VoxelIndex vi{(unsigned)a.v.dims[0], (unsigned)a.v.dims[0] * (unsigned)a.v.dims[1]};
   if (a.toffsets[blockIdx.x + 1] == a.toffsets[blockIdx.x]) return;  // (uniform: no triangle in this chunk)
-  __shared__ int wsum[4];
   long long run = a.toffsets[blockIdx.x];
   for (long long base = begin; base < end; base += TSDF_THREADS) {
     const long long at = base + threadIdx.x;
@@ -383,7 +318,7 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_mesh_triangle_kernel(const 
       tsdf_mesh_voxel(a.v, c, at, false, &mv);
     }
     int round_total;
-    long long pos = run + block_rank(mv.triangles, wsum, &round_total);
+    long long pos = run + block_excl_scan<TSDF_THREADS>(mv.triangles, &round_total);
     if (mv.triangles > 0) {
       for (int tet = 0; tet < 6; ++tet) {
         int vc[4];
@@ -406,16 +341,15 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_mesh_triangle_kernel(const 
       }
     }
     run += round_total;
-    __syncthreads();  // (wsum is rewritten by the next round)
   }
 }
 
 void launch_tsdf_mesh_count(const TsdfMeshArgs& a, int nblocks, long long* totals, hipStream_t s) {
   hipLaunchKernelGGL(tsdf_mesh_count_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
-  // totals[0] = vertices, [1] = those without a normal; totals[2] = triangles ([3]: the same sum again, unused)
+  // totals[0] = vertices, [1] = those without a normal; totals[2] = triangles
   hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.vcounts, a.nonormal, nblocks, a.voffsets, totals);
-  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.tcounts, a.nonormal, nblocks, a.toffsets,
-                     totals + 2);
+  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.tcounts, (const int*)nullptr, nblocks,
+                     a.toffsets, totals + 2);
 }
 
 void launch_tsdf_mesh_scatter(const TsdfMeshArgs& a, int nblocks, hipStream_t s) {
@@ -446,7 +380,8 @@ void launch_tsdf_raycast(const TsdfRaycastArgs& a, int nblocks, long long* total
 void launch_tsdf_ray_count(const TsdfRayCompactArgs& a, long long* totals, hipStream_t s) {
   const int nblocks = tsdf_ray_chunks(a.npix);
   hipLaunchKernelGGL(tsdf_ray_count_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
-  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.counts, a.dropped, nblocks, a.offsets, totals);
+  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.counts, (const int*)nullptr, nblocks, a.offsets,
+                     totals);
 }
 
 void launch_tsdf_ray_scatter(const TsdfRayCompactArgs& a, hipStream_t s) {

@@ -16,6 +16,7 @@
 //      voxel_resolve_kernel  every other point looks its output position up at its representative
 // Every atomic is an integer operation, so nothing depends on the order in which members arrive: the outputs are the
 // same bits on every run, and the bits of the CPU model.  All words of one slot share one 64-byte line.
+#include "block_scan.h"
 #include "icpk_internal.h"
 
 namespace icpk {
@@ -58,24 +59,6 @@ __device__ __forceinline__ unsigned voxel_hash(unsigned long long k) {
 }
 
 __device__ __forceinline__ long long voxel_fix(double f) { return (long long)__builtin_rint(f * VOXEL_FIX); }
-
-// exclusive scan of one int per lane over a workgroup of 256; *total: the sum over the workgroup
-__device__ __forceinline__ int block_scan_256(int v, int* total) {
-  __shared__ int wsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(inc, d);
-    if (lane >= d) inc += t;
-  }
-  __syncthreads();  // (wsum of a previous call has been read)
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; ++w) base += wsum[w];
-  *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  return base + inc - v;
-}
 
 }  // namespace
 
@@ -153,23 +136,14 @@ __global__ __launch_bounds__(256) void voxel_first_kernel(const VoxelArgs a) {
     a.out_of_point[i] = first;
     mine += first == i;
   }
-  int total;
-  block_scan_256(mine, &total);
+  const int total = block_total<256>(mine);
   if (threadIdx.x == 0) a.bsum[blockIdx.x] = total;
 }
 
 // bsum[nb] -> its exclusive scan in place; counts[0] := the total
 __global__ __launch_bounds__(256) void voxel_scan_kernel(int* __restrict__ bsum, int nb, int* __restrict__ counts) {
-  int carry = 0;
-  for (int base = 0; base < nb; base += 256) {
-    const int k = base + threadIdx.x;
-    const int v = k < nb ? bsum[k] : 0;
-    int total;
-    const int ex = block_scan_256(v, &total);
-    if (k < nb) bsum[k] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) counts[0] = carry;
+  const int total = scan_rounds<256>(bsum, bsum, nb);
+  if (threadIdx.x == 0) counts[0] = total;
 }
 
 __global__ __launch_bounds__(256) void voxel_emit_kernel(const VoxelArgs a) {
@@ -182,7 +156,7 @@ __global__ __launch_bounds__(256) void voxel_emit_kernel(const VoxelArgs a) {
     mine += first[k] == i;  // (i >= 0: a dropped point never counts)
   }
   int total;
-  int pos = a.bsum[blockIdx.x] + block_scan_256(mine, &total);
+  int pos = a.bsum[blockIdx.x] + block_excl_scan<256>(mine, &total);
   for (int k = 0; k < 4; ++k) {
     const int i = i0 + k;
     if (i >= a.n) break;

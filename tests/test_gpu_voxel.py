@@ -176,6 +176,27 @@ def test_empty_and_single_point(ctx, which, mode):
 
 
 @pytest.mark.parametrize("mode", MODES)
+def test_block_counts_cross_a_scan_round(ctx, mode):
+    """256 * 1024 + 1 points: 257 block counts, one more than a round of the scan takes, and the last block holds one
+    point -- once a representative of its own voxel, once a point that is dropped.  The uniform points fill their 16^3
+    voxels within the first few dozen blocks; 3 000 points in fresh voxels of their own sit in the last three blocks
+    before the boundary, so that the first round's last counts and its carry are not zero."""
+    n = 256 * 1024 + 1
+    rng = np.random.default_rng(8)
+    p = rng.uniform(-1, 1, (3, n)).astype(np.float32)  # 16^3 voxels of 0.125
+    late = np.arange(253 * 1024 + 7, 253 * 1024 + 7 + 3000)  # blocks 253, 254 and 255
+    p[:, late] = np.stack([2.0 + 0.125 * (np.arange(3000) % 40), 2.0 + 0.125 * (np.arange(3000) // 40), np.full(3000, 0.5)])
+    p[:, late] += rng.uniform(0.01, 0.1, (3, 3000))
+    p[:, -1] = np.float32([5.0, 5.0, 5.0])
+    want = _check(ctx, p, 0.125, mode, 0)
+    assert 5000 < want["n_out"] <= 4096 + 3001 and want["n_dropped"] == 0
+    assert want["first_index"][-1] == n - 1 and np.array_equal(want["first_index"][-3001:-1], late)
+    p[1, -1] = np.nan
+    want = _check(ctx, p, 0.125, mode, 0)
+    assert np.array_equal(want["first_index"][-3000:], late) and want["out_of_point"][-1] == -1 and want["n_dropped"] == 1
+
+
+@pytest.mark.parametrize("mode", MODES)
 def test_quotients_that_round_differently_in_float(ctx, mode):
     """Coordinates whose voxel differs when p / leaf is taken in float32 instead of float64: the rule says float64."""
     leaf = np.float32(0.05)
