@@ -708,8 +708,10 @@ int icpk_estimate_target_normals(icpk_ctx *ctx, float radius, int32_t min_neighb
  *   curvature[n]
  *   moments[10 * n]  per point i the ten words moments[10 i ..]: m, S_x, S_y, S_z, S_xx, S_xy, S_xz, S_yy, S_yz, S_zz
  * Any may be NULL.  The record belongs to the target it was estimated on: ICPK_E_NOT_SET before the first estimate and
- * after any later change of the target or its normals (a new target, icpk_transform_target, icpk_voxel_downsample,
- * icpk_set_target_normals); ICPK_E_ARG for `moments` when the estimate ran without ICPK_NORMALS_KEEP_MOMENTS. */
+ * after any later change of the target or its normals (a new target -- icpk_tsdf_surface_to_target and
+ * icpk_tsdf_raycast_to_target are two: they bring normals of their own and no record --, icpk_transform_target,
+ * icpk_voxel_downsample, icpk_set_target_normals); ICPK_E_ARG for `moments` when the estimate ran without
+ * ICPK_NORMALS_KEEP_MOMENTS. */
 int icpk_get_normal_stats(icpk_ctx *ctx, int32_t *n, int32_t *n_valid, int32_t *count, float *curvature,
                           int64_t *moments);
 
@@ -795,7 +797,10 @@ int icpk_get_outlier_stats(icpk_ctx *ctx, int32_t *n_in, int32_t *n_out, double 
  *   lifetime   every call that replaces or re-indexes the uploaded source drops them: icpk_set_source*,
  *       icpk_backproject* into the source, icpk_backproject_pair, icpk_detected_to_cloud(which = 0),
  *       icpk_commit_source, and icpk_voxel_downsample / icpk_remove_outliers with which = 0 (unless STATS_ONLY).  The
- *       getter, the hook and the flavour then return ICPK_E_NOT_SET.  Estimate after thinning and filtering.
+ *       getter, the hook and the flavour then return ICPK_E_NOT_SET.  Estimate after thinning and filtering.  The calls
+ *       that replace the TARGET alone leave them as they are: icpk_set_target*, icpk_map_list_to_target,
+ *       icpk_map_lookup_to_target, icpk_comm_broadcast_target, and icpk_tsdf_surface_to_target /
+ *       icpk_tsdf_raycast_to_target, whose target comes with its own normals (the flavour can run at once).
  *
  * The setting.  icpk_set_plane_to_plane holds epsilon (the default, 1e-3, is the paper's): the variance a patch is given
  * along its normal when the variance in its plane is 1.  ICPK_E_ARG unless it is finite and in (0, 1]; the setting is
@@ -870,9 +875,12 @@ int icpk_reduce_plane_to_plane(icpk_ctx *ctx, float max_dist, const float R_acc[
  *       icpk_commit_source and the loop.  Every call that replaces or re-indexes a cloud drops that cloud's
  *       intensities, and for the target its gradients too: icpk_set_source* / icpk_set_target*, icpk_backproject* and
  *       icpk_detected_to_cloud into that cloud, icpk_backproject_pair (both), icpk_voxel_downsample /
- *       icpk_remove_outliers on it (unless STATS_ONLY), icpk_map_list_to_target, icpk_map_lookup_to_target and
- *       icpk_comm_broadcast_target on every rank but the root (the root's target is not replaced: it keeps its
- *       intensities, gradients and kept sums).  They are not carried through thinning: gather them on the host by
+ *       icpk_remove_outliers on it (unless STATS_ONLY), icpk_map_list_to_target, icpk_map_lookup_to_target,
+ *       icpk_tsdf_surface_to_target, icpk_tsdf_raycast_to_target and icpk_comm_broadcast_target on every rank but the
+ *       root (the root's target is not replaced: it keeps its intensities, gradients and kept sums).  The two TSDF
+ *       hand-overs drop the old target's intensities, gradients and kept sums like any new target; from a volume with
+ *       ICPK_TSDF_COLOR the new target then holds the volume's intensities (one per handed-over point) and no
+ *       gradients: estimate them again.  They are not carried through thinning: gather them on the host by
  *       icpk_get_voxel_groups' first_index or icpk_get_outlier_stats' out_index and set them again.
  *
  * Gradients.  icpk_estimate_target_color_gradients fits, per target point, the intensity of its neighbours as a linear
@@ -990,7 +998,11 @@ int icpk_score_poses(icpk_ctx *ctx, int32_t n_poses, const float *T /* 16 * n_po
 /* Pose `pose` of the last icpk_score_poses made with ICPK_SCORE_KEEP_ASSOC (8 bytes per pose and source point stay on
  * the device until the next such call): per source point the partner's index and distance, -1 and +inf for a point
  * without one.  Either array may be NULL.  ICPK_E_NOT_SET before such a call, or after the uploaded source or the
- * target changed; ICPK_E_ARG for a pose outside that call. */
+ * target changed -- every call that replaces or re-indexes one of them: icpk_set_source* / icpk_set_target*,
+ * icpk_backproject*, icpk_backproject_pair, icpk_detected_to_cloud, icpk_commit_source, icpk_voxel_downsample /
+ * icpk_remove_outliers (unless STATS_ONLY), icpk_transform_target, icpk_map_list_to_target,
+ * icpk_map_lookup_to_target, icpk_tsdf_surface_to_target, icpk_tsdf_raycast_to_target, icpk_comm_broadcast_target off
+ * the root --; ICPK_E_ARG for a pose outside that call. */
 int icpk_get_score_associations(icpk_ctx *ctx, int32_t pose, int32_t *idx_out, float *dist_out);
 /* host only (no device work): the metrics and the information matrix of the rule above from one pose's sums; any
  * output of icpk_score_metrics may be NULL */
@@ -1045,8 +1057,9 @@ void icpk_information_matrix(const double sums[ICPK_NSCORE], int64_t inliers, do
  * finite and > 0, or an unknown flag.
  * icpk_get_fpfh: desc n x ICPK_FPFH_BINS floats in the caller's point order, valid n bytes, *n the count; any may be
  * NULL.  icpk_get_spfh (after ICPK_FPFH_KEEP_SPFH, else ICPK_E_ARG): counts n x 33 and m n int32.  Both wait, and both
- * return ICPK_E_NOT_SET once the cloud or its normals have changed: the events that drop K12's statistics record (target)
- * and K14's source normals (source).
+ * return ICPK_E_NOT_SET once the cloud or its normals have changed: the events that drop K12's statistics record (target;
+ * icpk_tsdf_surface_to_target and icpk_tsdf_raycast_to_target among them: a new target with new normals) and K14's
+ * source normals (source).
  *
  * 2. icpk_match_features(ctx, flags).  Both clouds must hold current descriptors (else ICPK_E_NOT_SET).  For every valid
  * source i: the valid target j that minimises (D, j) lexicographically, D = (float)(sum over b = 0..32 in order of

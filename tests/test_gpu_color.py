@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import color_model as cm
+import tsdf_cases
 from icp_slam_prototype_amd import binding, build, synth
 
 pytestmark = pytest.mark.gpu
@@ -437,6 +438,8 @@ def test_lifetime(ctx):
         "remove_outliers": lambda: ctx.remove_outliers(1, kind=binding.FILTER_RADIUS, radius=0.1, min_neighbors=2),
         "map_list_to_target": lambda: map_target(False),
         "map_lookup_to_target": lambda: map_target(True),
+        "tsdf_surface_to_target": lambda: tsdf_cases.hand_over(ctx, raycast=False),
+        "tsdf_raycast_to_target": lambda: tsdf_cases.hand_over(ctx, raycast=True),
     }
     for name, act in drops_source.items():
         install()
@@ -451,6 +454,18 @@ def test_lifetime(ctx):
         assert _code(ctx.get_target_color_gradients) == binding.E_NOT_SET, name
         assert _code(ctx.color_gradient_sums) == binding.E_NOT_SET, name
         assert ctx.get_source_colors().tobytes() == sc.tobytes(), name
+    # a TSDF volume with ICPK_TSDF_COLOR hands its own intensities over with the points: the new target has colours
+    # (the volume's, one per point), and neither the old target's gradients nor their sums
+    for raycast in (False, True):
+        install()
+        n = tsdf_cases.hand_over(ctx, raycast=raycast, color=True)
+        got = ctx.get_target_colors()
+        assert got.shape == (n,) and got.tobytes() != tc[:n].tobytes() and np.all(np.abs(got - 0.5) < 1e-6), raycast
+        assert _code(ctx.get_target_color_gradients) == binding.E_NOT_SET, raycast
+        assert _code(ctx.color_gradient_sums) == binding.E_NOT_SET, raycast
+        assert ctx.get_target_normals().shape == (3, n), raycast
+        assert ctx.get_source_colors().tobytes() == sc.tobytes(), raycast
+    ctx.tsdf_release()
     install()
     ctx.backproject_pair(depth, p["depth_tgt"])
     assert _code(ctx.get_source_colors) == binding.E_NOT_SET and _code(ctx.get_target_colors) == binding.E_NOT_SET

@@ -6,6 +6,7 @@ import pytest
 
 import fpfh_cases as fc
 import fpfh_model as fm
+import tsdf_cases
 from icp_slam_prototype_amd import binding
 
 pytestmark = pytest.mark.gpu
@@ -178,7 +179,11 @@ def test_descriptors_are_dropped_with_their_cloud_or_normals():
         c.get_fpfh(0), c.get_fpfh(1), c.get_spfh(0)  # an argument error drops nothing
         for which, drop in ((1, lambda: c.set_target(pts)), (1, lambda: c.set_target_normals(nrm)),
                             (1, lambda: c.transform_target(np.eye(3, dtype=np.float32), np.zeros(3, np.float32))),
-                            (1, lambda: c.estimate_target_normals(0.2)), (0, lambda: c.set_source(o)),
+                            (1, lambda: c.estimate_target_normals(0.2)),
+                            (1, lambda: tsdf_cases.hand_over(c, raycast=False)),
+                            (1, lambda: tsdf_cases.hand_over(c, raycast=True)),
+                            (1, lambda: tsdf_cases.hand_over(c, raycast=False, color=True)),
+                            (1, lambda: tsdf_cases.hand_over(c, raycast=True, color=True)), (0, lambda: c.set_source(o)),
                             (0, lambda: c.set_source_normals(on)), (0, lambda: c.commit_source()),
                             (0, lambda: c.estimate_source_normals(0.2))):
             fresh(c)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import gicp_model as gm
+import tsdf_cases
 from icp_slam_prototype_amd import binding, build, synth
 
 pytestmark = pytest.mark.gpu
@@ -164,6 +165,12 @@ def test_lifetime(ctx):
     ctx.transform_source(np.eye(3, dtype=np.float32), np.float32([0.01, 0, 0]))
     ctx.align(solve=binding.SOLVE_KABSCH, max_iterations=2)
     assert np.array_equal(_bits(ctx.get_source_normals()), _bits(keep))
+    # ... and the TSDF hand-overs, which replace the target alone and bring its normals: the flavour runs at once
+    for raycast in (False, True):
+        tsdf_cases.hand_over(ctx, raycast=raycast, color=raycast)
+        assert np.array_equal(_bits(ctx.get_source_normals()), _bits(keep)), raycast
+        assert _code(ctx.align, solve=P2P, max_iterations=2) >= 0, raycast
+    ctx.tsdf_release()
 
 
 # ---------------------------------------------------------------------------------------------------------- hook --

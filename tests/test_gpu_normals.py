@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import normals_model as nm
+import tsdf_cases
 import voxel_model as vm
 from icp_slam_prototype_amd import binding, build, synth
 
@@ -227,6 +228,19 @@ def test_refusals(kinect):
         c.estimate_target_normals(0.05, 5, CAM)
         c.voxel_downsample(1, 0.05)
         assert _raw_stats(c) == binding.E_NOT_SET
+        c.estimate_target_normals(0.15, 5, CAM)
+        assert _raw_stats(c) == binding.OK
+        # a TSDF hand-over is a new target with normals of its own: the record of the old one is gone, with and
+        # without ICPK_TSDF_COLOR
+        for raycast in (False, True):
+            for color in (False, True):
+                c.set_target(tgt)
+                c.estimate_target_normals(0.15, 5, CAM)
+                assert _raw_stats(c) == binding.OK
+                n = tsdf_cases.hand_over(c, raycast=raycast, color=color)
+                assert _raw_stats(c) == binding.E_NOT_SET, (raycast, color)
+                assert c.get_target_normals().shape == (3, n)
+        c.tsdf_release()
         c.estimate_target_normals(0.15, 5, CAM)
         assert _raw_stats(c) == binding.OK
         # a new target drops the normals and the record

@@ -8,6 +8,7 @@ import pytest
 
 import gicp_model as gm
 import score_model as sm
+import tsdf_cases
 from icp_slam_prototype_amd import binding, sequence, synth
 
 pytestmark = pytest.mark.gpu
@@ -275,6 +276,17 @@ def test_argument_errors():
         with pytest.raises(binding.IcpkError) as e:
             c.score_associations(0)
         assert e.value.code == binding.E_NOT_SET
+        # ... and a TSDF hand-over is a new target (with and without ICPK_TSDF_COLOR)
+        for raycast in (False, True):
+            for color in (False, True):
+                c.set_target(tgt)
+                c.score_poses(T, 0.1, keep_assoc=True)
+                assert still_there()
+                tsdf_cases.hand_over(c, raycast=raycast, color=color)
+                with pytest.raises(binding.IcpkError) as e:
+                    c.score_associations(0)
+                assert e.value.code == binding.E_NOT_SET, (raycast, color)
+        c.tsdf_release()
 
 
 def test_sequence_runner_reports_fitness_when_asked():

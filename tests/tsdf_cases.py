@@ -83,6 +83,29 @@ def case(name):
     raise KeyError(name)
 
 
+def hand_over(ctx, raycast=False, color=False):
+    """The `plane` case fused on the context and handed over as its target: the surface list
+    (icpk_tsdf_surface_to_target) or the ray cast from the frame's own pose (icpk_tsdf_raycast_to_target).  color: a
+    volume with ICPK_TSDF_COLOR and a flat intensity of 0.5.  Returns the new target's size.  (For the lifetime tests
+    of the features whose records speak of the target: a hand-over replaces it like any other new target.)"""
+    from icp_slam_prototype_amd import binding
+
+    c = case("plane")
+    v = c["volume"]
+    d, P, _ = c["frames"][0]
+    ctx.tsdf_create(dims=v["dims"], voxel=v["voxel"], origin=v["origin"], trunc=v["trunc"],
+                    flags=binding.TSDF_COLOR if color else 0)
+    ctx.tsdf_integrate(d, P, np.full(d.shape, 0.5, np.float32) if color else None, fx=c["fx"], cx=c["cx"])
+    if raycast:
+        ctx.tsdf_raycast(P, shape=d.shape, fx=c["fx"], cx=c["cx"], z_near=0.25, z_far=3.0, step=0.1875, min_weight=1)
+        ctx.tsdf_raycast_to_target()
+    else:
+        ctx.tsdf_extract_surface(1)
+        ctx.tsdf_surface_to_target()
+    assert ctx.target_size > 0
+    return ctx.target_size
+
+
 SMALL_CASES = ("room", "room_color", "odd", "boundary", "holes", "saturation", "plane", "plane_edge")
 
 
