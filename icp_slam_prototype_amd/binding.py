@@ -88,6 +88,8 @@ SYMBOLS = [
     "icpk_default_tsdf_raycast_params", "icpk_tsdf_raycast", "icpk_tsdf_get_raycast", "icpk_tsdf_raycast_to_target",
     "icpk_tsdf_raycast_pixels",
     "icpk_tsdf_extract_mesh", "icpk_tsdf_get_mesh", "icpk_tsdf_set", "icpk_tsdf_mesh_host",
+    "icpk_default_bilateral_params", "icpk_bilateral_depth_image", "icpk_backproject_smoothed", "icpk_bilateral_tables",
+    "icpk_bilateral_host",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -190,6 +192,15 @@ class TsdfRaycastParams(C.Structure):
     """icpk_tsdf_raycast_params"""
     _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("fx", C.c_float), ("cx", C.c_float), ("z_near", C.c_float),
                 ("z_far", C.c_float), ("step", C.c_float), ("min_weight", C.c_int32)]
+
+
+BILATERAL_MAX_RADIUS = 6  # icpk_bilateral_params.radius
+BILATERAL_MAX_RANGE = 4096  # ... and the largest K: entries of the range table
+
+
+class BilateralParams(C.Structure):
+    """icpk_bilateral_params"""
+    _fields_ = [("radius", C.c_int32), ("sigma_space", C.c_float), ("sigma_range", C.c_float), ("range_cutoff", C.c_int32)]
 
 
 class FrameJob(C.Structure):
@@ -423,6 +434,14 @@ def load():
     lib.icpk_tsdf_set.argtypes = [C.c_void_p, fp, u16, fp]
     lib.icpk_tsdf_mesh_host.argtypes = [C.POINTER(TsdfParams), C.c_int32, fp, u16, fp, C.c_int64, C.c_int64, fp, fp, fp,
                                         fp, fp, fp, fp, ip, u8, ip, C.POINTER(C.c_int64)]
+    bp = C.POINTER(BilateralParams)
+    lib.icpk_default_bilateral_params.argtypes = [bp]
+    lib.icpk_default_bilateral_params.restype = None
+    lib.icpk_bilateral_depth_image.argtypes = [C.c_void_p, bp, u16, u16, C.c_int32, C.c_int32]
+    lib.icpk_backproject_smoothed.argtypes = [C.c_void_p, u16, C.c_int32, C.c_int32, C.c_float, C.c_float, fp, C.c_int32,
+                                              C.c_int32, bp]
+    lib.icpk_bilateral_tables.argtypes = [bp, u16, u16, ip]
+    lib.icpk_bilateral_host.argtypes = [bp, u16, C.c_int32, C.c_int32, u16]
     _lib = lib
     return lib
 

@@ -18,7 +18,7 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_filter.cpp", "kernels_filter.hip", "icpk_gicp.cpp", "kernels_gicp.hip",
            "icpk_score.cpp", "kernels_score.hip", "icpk_fpfh.cpp", "kernels_fpfh.hip", "icpk_global.cpp",
            "icpk_color.cpp", "kernels_color.hip", "icpk_posegraph.cpp", "kernels_posegraph.hip",
-           "icpk_tsdf.cpp", "kernels_tsdf.hip"]
+           "icpk_tsdf.cpp", "kernels_tsdf.hip", "icpk_bilateral.cpp", "kernels_bilateral.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -352,6 +352,50 @@ def build_tsdf_mesh_host_sanitized(force=False):
     return TSDF_MESH_HOST_SANITIZED
 
 
+BILATERAL_TEST = os.path.join(LIBDIR, "test_bilateral")
+
+
+def build_bilateral_test(force=False):
+    """Host-only C++ program over icp::Engine::bilateralDepthImage / backprojectSmoothed (icp_align.hpp, K22) (g++, links
+    -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_bilateral.cpp")
+    hdr = os.path.join(HERE, "include", "icp_align.hpp")
+    build()
+    newest = max(os.path.getmtime(p) for p in (src, hdr, LIB))
+    if not force and os.path.exists(BILATERAL_TEST) and os.path.getmtime(BILATERAL_TEST) >= newest:
+        return BILATERAL_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", BILATERAL_TEST])
+    return BILATERAL_TEST
+
+
+BILATERAL_HOST_SANITIZED = os.path.join(LIBDIR, "bilateral_host_sanitized")
+
+
+def build_bilateral_host_sanitized(force=False):
+    """DIAGNOSTIC, not part of build(): tests/cpp/bilateral_host_main.cpp (its own main, no GPU) with icpk_bilateral.cpp
+    -- and so csrc/bilateral_rule.h -- compiled under -fsanitize=address,undefined on the host side.  icpk_bilateral.cpp
+    is host only and refers to nothing else of the library, so the program does not link it.  Run the program it returns
+    directly."""
+    src = os.path.join(ROOT, "tests", "cpp", "bilateral_host_main.cpp")
+    deps = [src, os.path.join(CSRC, "icpk_bilateral.cpp"), os.path.join(CSRC, "bilateral_rule.h"),
+            os.path.join(ROOT, "include", "icpk.h")]
+    os.makedirs(LIBDIR, exist_ok=True)
+    if not force and os.path.exists(BILATERAL_HOST_SANITIZED) and \
+            os.path.getmtime(BILATERAL_HOST_SANITIZED) >= max(os.path.getmtime(p) for p in deps):
+        return BILATERAL_HOST_SANITIZED
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-omit-frame-pointer", "-g"]
+    objs = []
+    for path, name in ((os.path.join(CSRC, "icpk_bilateral.cpp"), "icpk_bilateral_sanitized.o"), (src, "bilateral_host_main.o")):
+        objs.append(os.path.join(LIBDIR, name))
+        subprocess.check_call([hipcc] + FLAGS + san + ["-x", "hip", "-c", path, "-o", objs[-1]])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-fsanitize=address,undefined"] + objs +
+                          ["-o", BILATERAL_HOST_SANITIZED])
+    return BILATERAL_HOST_SANITIZED
+
+
 THREADS_TEST = os.path.join(LIBDIR, "test_threads")
 
 
@@ -438,4 +482,5 @@ if __name__ == "__main__":
     print(build_tsdf_test(force="--force" in sys.argv))
     print(build_tsdf_raycast_test(force="--force" in sys.argv))
     print(build_tsdf_mesh_test(force="--force" in sys.argv))
+    print(build_bilateral_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

@@ -241,6 +241,11 @@ struct icpk_ctx {
   icpk::PinnedBuf<float> stage_t, stage_s;  // staging of host clouds (frame-batch slots): target, source
   icpk::DevBuf<uint16_t> depth_dev;
   icpk::DevBuf<uint16_t> depth_flt;  // filtered depth image (icpk_filter_depth_image / icpk_backproject_filtered)
+  // K22: the two tables of the bilateral rule on the device (ws, then wr), made again only when the parameters change
+  icpk::DevBuf<uint16_t> bil_tables;
+  std::vector<uint16_t> bil_tables_host;  // what the upload reads: it lives as long as a copy may be in flight
+  icpk_bilateral_params bil_params = {0, 0.f, 0.f, 0};  // radius 0: no tables yet
+  int bil_K = 0;
   icpk::DevBuf<int32_t> ks_buf;  // key-point association lists: assoc_q | assoc_t | assoc_d | rej_q, a quarter of it each
   // icpk_backproject_pair keeps the current frame's image on the device (slot frame_slot of depth_dev / depth_flt, two
   // slots of half their capacity): it is the next call's `previous` (SLAM.cpp:305) and need not cross PCIe again

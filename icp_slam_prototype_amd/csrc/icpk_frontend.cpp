@@ -1,4 +1,5 @@
-// icpk_frontend.cpp -- the depth front end (SLAM.cpp, pointcloud.cpp): depth filter, back-projection of one image or
+// icpk_frontend.cpp -- the depth front end (SLAM.cpp, pointcloud.cpp): depth filter, bilateral filter (K22; its host-only
+// half is icpk_bilateral.cpp), back-projection of one image or
 // of a frame pair (with the frame kept resident for the next call), subsampling, registered host buffers, and the
 // key-point entry points icpk_associate_keypoints and icpk_backproject_keypoints.
 #include <cmath>
@@ -79,9 +80,41 @@ static int ensure_depth_buffers(icpk_ctx* ctx, int count, int ints) {
   return rc ? rc : ctx->bp_counts.reserve(ctx, ints);
 }
 
+// K22: params (NULL: the defaults) checked into *p
+static int check_bilateral(icpk_ctx* ctx, const icpk_bilateral_params* params, icpk_bilateral_params* p) {
+  if (params)
+    *p = *params;
+  else
+    icpk_default_bilateral_params(p);
+  if (icpk_bilateral_tables(p, nullptr, nullptr, nullptr) != ICPK_OK)
+    return fail(ctx, ICPK_E_ARG, "bilateral parameters outside their ranges (see THE BILATERAL RULE)");
+  return ICPK_OK;
+}
+
+// the tables of `p` (checked) on the device.  A change of parameters waits for the stream first: an earlier upload may
+// still be reading the host copy that is about to be rewritten.
+static int ensure_bilateral_tables(icpk_ctx* ctx, const icpk_bilateral_params& p) {
+  if (ctx->bil_params.radius != 0 && std::memcmp(&ctx->bil_params, &p, sizeof(p)) == 0) return ICPK_OK;
+  constexpr int side_max = 2 * ICPK_BILATERAL_MAX_RADIUS + 1;
+  constexpr size_t words = side_max * side_max + ICPK_BILATERAL_MAX_RANGE;
+  const int rc = ctx->bil_tables.reserve(ctx, words);
+  if (rc) return rc;
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->bil_params.radius = 0;
+  ctx->bil_tables_host.resize(words);
+  uint16_t* const h = ctx->bil_tables_host.data();
+  const int n_ws = (2 * p.radius + 1) * (2 * p.radius + 1);
+  int32_t K = 0;
+  icpk_bilateral_tables(&p, h, h + n_ws, &K);
+  ICPK_HIP(ctx, hipMemcpyAsync(ctx->bil_tables, h, (size_t)(n_ws + K) * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+  ctx->bil_params = p;
+  ctx->bil_K = K;
+  return ICPK_OK;
+}
+
 static int backproject_impl(icpk_ctx* ctx, const uint16_t* depth, int32_t rows, int32_t cols, float fx, float cx,
                             const float offset[3], int32_t which, int normals_mode /* <0: none */,
-                            const DepthFilter* flt = nullptr) {
+                            const DepthFilter* flt = nullptr, const icpk_bilateral_params* bil = nullptr /* checked */) {
   if (!ctx || !depth || rows <= 0 || cols <= 0 || (which != 0 && which != 1) || (int64_t)rows * cols > (1 << 28) ||
       normals_mode > ICPK_NORMALS_REFERENCE)
     return ICPK_E_ARG;
@@ -93,9 +126,14 @@ static int backproject_impl(icpk_ctx* ctx, const uint16_t* depth, int32_t rows, 
   Cloud& c = which == 0 ? ctx->src0 : ctx->tgt;
   rc = ensure_cloud(ctx, c, npix);  // worst case: every pixel valid
   if (rc) return rc;
+  if (bil && (rc = ensure_bilateral_tables(ctx, *bil))) return rc;
   ctx->frame_slot = -1;  // (the image buffers are shared with icpk_backproject_pair's resident frame)
   ICPK_HIP(ctx, hipMemcpyAsync(ctx->depth_dev, depth, (size_t)npix * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
   const uint16_t* dimg = ctx->depth_dev;
+  if (bil) {  // K22: the cloud (and its normals) come from the smoothed frame
+    launch_depth_bilateral(ctx->depth_dev, ctx->depth_flt, rows, cols, bil->radius, ctx->bil_K, ctx->bil_tables, ctx->stream);
+    dimg = ctx->depth_flt;
+  }
   if (flt) {  // SLAM.cpp:229,553-574: the frame is filtered before it is back-projected
     launch_depth_filter(ctx->depth_dev, ctx->depth_flt, rows, cols, flt->min_d, flt->max_d, flt->ax, flt->ay, flt->morph,
                         ctx->stream);
@@ -298,6 +336,37 @@ int icpk_filter_depth_image(icpk_ctx* ctx, const uint16_t* depth_in, uint16_t* d
   ICPK_HIP(ctx, hipMemcpyAsync(depth_out, ctx->depth_flt, (size_t)npix * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ICPK_OK;
+}
+
+int icpk_bilateral_depth_image(icpk_ctx* ctx, const icpk_bilateral_params* params, const uint16_t* depth_in,
+                               uint16_t* depth_out, int32_t rows, int32_t cols) {
+  if (!ctx || !depth_in || !depth_out || rows <= 0 || cols <= 0 || (int64_t)rows * cols > (1 << 28)) return ICPK_E_ARG;
+  icpk_bilateral_params p;
+  int rc = check_bilateral(ctx, params, &p);
+  if (rc) return rc;
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const int npix = rows * cols;
+  rc = ensure_depth_buffers(ctx, npix, 0);
+  if (rc) return rc;
+  if ((rc = ensure_bilateral_tables(ctx, p))) return rc;
+  ctx->frame_slot = -1;  // (the image buffers are shared with icpk_backproject_pair's resident frame)
+  ICPK_HIP(ctx, hipMemcpyAsync(ctx->depth_dev, depth_in, (size_t)npix * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+  launch_depth_bilateral(ctx->depth_dev, ctx->depth_flt, rows, cols, p.radius, ctx->bil_K, ctx->bil_tables, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ICPK_HIP(ctx, hipMemcpyAsync(depth_out, ctx->depth_flt, (size_t)npix * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_backproject_smoothed(icpk_ctx* ctx, const uint16_t* depth, int32_t rows, int32_t cols, float fx, float cx,
+                              const float offset[3], int32_t which, int32_t normals_mode,
+                              const icpk_bilateral_params* params) {
+  if (!ctx) return ICPK_E_ARG;
+  if (normals_mode >= 0 && which != 1) return fail(ctx, ICPK_E_ARG, "normals belong to the target cloud");
+  icpk_bilateral_params p;
+  const int rc = check_bilateral(ctx, params, &p);
+  if (rc) return rc;
+  return backproject_impl(ctx, depth, rows, cols, fx, cx, offset, which, normals_mode < 0 ? -1 : normals_mode, nullptr, &p);
 }
 
 /* icp.cpp:488-515 on the context's clouds (source = the frame's key points, target = the map's) */

@@ -451,6 +451,9 @@ struct DfBatch {
 };
 void launch_depth_filter_batch(const DfBatch& b, int count, int rows, int cols, int min_d, int max_d, int ax, int ay,
                                int morph, hipStream_t s);
+// K22, THE BILATERAL RULE: tables = (2 radius + 1)^2 spatial weights, then K range weights (device; in != out)
+void launch_depth_bilateral(const uint16_t* in, uint16_t* out, int rows, int cols, int radius, int K,
+                            const uint16_t* tables, hipStream_t s);
 
 
 // ---- deferred set-up launches of the frame-batch mode ------------------------------------------------

@@ -83,6 +83,19 @@ class Engine {
   // pointcloud.cpp:27-30 (SUBSAMPLE_FACTOR, pointcloud.hpp:11) with a reproducible choice instead of rand(): every
   // cloud this engine back-projects from now on keeps one valid pixel in `factor` (0 / 1: all of them)
   int setSubsample(int factor = ICPK_SUBSAMPLE_FACTOR, uint64_t seed = 0) { return icpk_set_subsample(ctx_, factor, seed); }
+  // the bilateral filter of a CV_16UC1 depth buffer (icpk_bilateral_depth_image, K22): holes stay holes, noise is
+  // averaged, never across a depth step; out may be the input buffer; params nullptr: icpk_default_bilateral_params
+  int bilateralDepthImage(const uint16_t* image, uint16_t* out, int rows, int cols,
+                          const icpk_bilateral_params* params = nullptr) {
+    return icpk_bilateral_depth_image(ctx_, params, image, out, rows, cols);
+  }
+  // ... and the cloud of the smoothed frame without the image leaving the device (icpk_backproject_smoothed): the source
+  // (which = 0) or the target (1; normalsMode >= 0: with its normals, as icpk_backproject_with_normals).  Returns the
+  // number of points or a negative status.
+  int backprojectSmoothed(const uint16_t* image, int rows, int cols, float fx, float cx, const float* offset, int which,
+                          int normalsMode = -1, const icpk_bilateral_params* params = nullptr) {
+    return icpk_backproject_smoothed(ctx_, image, rows, cols, fx, cx, offset, which, normalsMode, params);
+  }
   // robust alignment (icpk_set_robust): trimmed pairs and Huber / Tukey weights for every later alignment of this
   // engine (Kabsch and point-to-plane flavours); clearRobust() turns it off again (the default)
   int setRobust(const icpk_robust& r) { return icpk_set_robust(ctx_, &r); }

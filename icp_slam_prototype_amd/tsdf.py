@@ -23,7 +23,7 @@ open where the surface leaves them or the volume), extracted on the device:
 """
 import numpy as np
 
-from . import binding
+from . import binding, depth as depth_front
 
 
 class TsdfVolume:
@@ -133,13 +133,17 @@ class ModelTracker:
     z_far, step, min_weight: the ray cast's; align_kw: fields of icpk_params for the alignment (max_iterations,
     max_nn_dist, min_pairs, ...).  Keep max_nn_dist at a voxel or two: the target is the model seen from the LAST pose,
     so surfaces the new frame sees for the first time have no counterpart in it, and a wide gate pairs them with the
-    view's border, which biases the pose (icpk_params' default, 0.75 m, is meant for frame-to-frame clouds)."""
+    view's border, which biases the pose (icpk_params' default, 0.75 m, is meant for frame-to-frame clouds).
+    bilateral: a depth.bilateral_params object (True: the defaults) -- the cloud that is aligned then comes from the
+    smoothed frame (depth.backproject_smoothed, K22) while the RAW frame is what the volume fuses, KinectFusion's order;
+    None: the raw frame serves both."""
 
-    def __init__(self, vol, pose=None, z_near=0.25, z_far=6.0, step=None, min_weight=1, **align_kw):
+    def __init__(self, vol, pose=None, z_near=0.25, z_far=6.0, step=None, min_weight=1, bilateral=None, **align_kw):
         self.vol = vol
         self.pose = np.eye(4) if pose is None else np.array(pose, np.float64).reshape(4, 4)
         self.ray = dict(z_near=z_near, z_far=z_far, step=step, min_weight=min_weight)
         self.align_kw = align_kw
+        self.bilateral = depth_front.bilateral_params() if bilateral is True else bilateral
         self.frames = 0
         self.n_hits = self.stats = None
 
@@ -153,7 +157,10 @@ class ModelTracker:
             if self.n_hits < params.min_pairs:
                 raise RuntimeError(f"the ray cast hit the model in {self.n_hits} pixels, fewer than min_pairs = {params.min_pairs}")
             ctx.tsdf_raycast_to_target()
-            ctx.backproject(depth, which=0, fx=vol.fx, cx=vol.cx)
+            if self.bilateral is None:
+                ctx.backproject(depth, which=0, fx=vol.fx, cx=vol.cx)
+            else:
+                depth_front.backproject_smoothed(ctx, depth, which=0, fx=vol.fx, cx=vol.cx, params=self.bilateral)
             ctx.transform_source(self.pose[:3, :3], self.pose[:3, 3])
             ctx.commit_source()
             T, self.stats, _ = ctx.align(params)

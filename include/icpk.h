@@ -1484,6 +1484,65 @@ int icpk_tsdf_mesh_host(const icpk_tsdf_params *params, int32_t min_weight, cons
                         float *nx, float *ny, float *nz, float *intensity_out, int32_t *voxel_index, uint8_t *edge,
                         int32_t *triangles, int64_t counts[3]);
 
+/* ---- K22: smoothing a depth frame before its vertex and normal maps are made -----------------------------------------
+ * KinectFusion's first stage: a bilateral filter in front of the cloud (and the cross-product normals) that tracking
+ * reads, while the RAW frame is what goes into the volume.  K6 (icpk_filter_depth_image) repairs holes and leaves noise
+ * alone; this one leaves holes alone and averages noise, never across a depth step.
+ *
+ * THE BILATERAL RULE (icpk_bilateral_depth_image; integers only, so the result is a function of the image and the two
+ * tables alone: tile shape, tap order and who computes it do not matter).
+ *   Parameters (icpk_bilateral_params; defaults from icpk_default_bilateral_params):
+ *     radius        1 .. ICPK_BILATERAL_MAX_RADIUS (3): the window is (2 radius + 1)^2 pixels
+ *     sigma_space   pixels, finite and > 0 (2.0)
+ *     sigma_range   depth units, finite and > 0 (30: 6 mm at ICPK_DEPTH_SCALE)
+ *     range_cutoff  0, or 1 .. ICPK_BILATERAL_MAX_RANGE (0).  0: K = floor(3 sigma_range) + 1; otherwise K = range_cutoff.
+ *                   A K above ICPK_BILATERAL_MAX_RANGE is refused, not clamped.
+ *   Tables, computed once per call on the host in double (icpk_bilateral_tables returns them):
+ *     ws[dy][dx] = (int)floor(4096 exp(-(dx^2 + dy^2) / (2 sigma_space^2)) + 0.5)   for dy, dx = -radius .. radius
+ *     wr[k]      = (int)floor(4096 exp(-k^2 / (2 sigma_range^2)) + 0.5)             for k = 0 .. K - 1
+ *     Both centres are 4096.
+ *   Pixel p of depth d_p:
+ *     d_p == 0 gives 0: holes are not filled.
+ *     Otherwise tap q of the window contributes iff it lies inside the image, d_q != 0 and k = |d_q - d_p| < K.
+ *     Its weight is W = ws * wr[k] (<= 2^24).  S_w = sum W (< 2^32 at 169 taps), S_wd = sum W d_q (< 2^48).
+ *     out = floor((2 S_wd + S_w) / (2 S_w)): the weighted mean, rounded to nearest, halves up.
+ *   The centre always contributes, so S_w > 0, out >= 1 and |out - d_p| <= K - 1: the validity mask of the image is
+ *   preserved exactly, and a depth step of K or more is never averaged across.
+ *
+ * icpk_bilateral_depth_image   depth_in / depth_out: host arrays of rows x cols (may be the same array).  params NULL:
+ *     the defaults.
+ * icpk_backproject_smoothed    upload, filter, back-project, without the image leaving the device: as icpk_backproject
+ *     (normals_mode < 0) or icpk_backproject_with_normals (normals_mode >= 0, which must be 1) on the smoothed image --
+ *     icpk_backproject_filtered's convention.  Equivalent, bit for bit, to icpk_bilateral_depth_image followed by that
+ *     call.  Both calls use the image buffers icpk_backproject_pair keeps its resident frame in: as after
+ *     icpk_backproject_filtered, no frame is resident afterwards.
+ * icpk_bilateral_tables        host only: ws receives (2 radius + 1)^2 entries, row-major (room for 169 covers every
+ *     radius), wr receives *K entries (room for ICPK_BILATERAL_MAX_RANGE covers every K).  ws, wr or K may be NULL.
+ * icpk_bilateral_host          host only: the rule over a host image, through the header the kernel includes
+ *     (csrc/bilateral_rule.h).  depth_out may be depth_in.
+ * Refusals (ICPK_E_ARG; a refused call leaves the context, its clouds and the output array as they were): a NULL
+ *     image; rows or cols < 1, or more than 2^28 pixels; a radius outside 1 .. ICPK_BILATERAL_MAX_RADIUS; a sigma_space
+ *     or sigma_range that is not finite and > 0; a range_cutoff outside 0 .. ICPK_BILATERAL_MAX_RANGE, or K above it;
+ *     for icpk_backproject_smoothed also `which` outside 0 / 1, normals_mode >= 0 with which == 0, and a normals_mode
+ *     icpk_backproject_with_normals does not know. */
+#define ICPK_BILATERAL_MAX_RADIUS 6
+#define ICPK_BILATERAL_MAX_RANGE 4096
+typedef struct icpk_bilateral_params {
+  int32_t radius;       /* 1 .. ICPK_BILATERAL_MAX_RADIUS (3) */
+  float sigma_space;    /* pixels (2.0) */
+  float sigma_range;    /* depth units (30) */
+  int32_t range_cutoff; /* 0: floor(3 sigma_range) + 1 (0) */
+} icpk_bilateral_params;
+void icpk_default_bilateral_params(icpk_bilateral_params *p);
+int icpk_bilateral_depth_image(icpk_ctx *ctx, const icpk_bilateral_params *params, const uint16_t *depth_in,
+                               uint16_t *depth_out, int32_t rows, int32_t cols);
+int icpk_backproject_smoothed(icpk_ctx *ctx, const uint16_t *depth, int32_t rows, int32_t cols, float fx, float cx,
+                              const float offset[3], int32_t which, int32_t normals_mode,
+                              const icpk_bilateral_params *params);
+int icpk_bilateral_tables(const icpk_bilateral_params *params, uint16_t *ws, uint16_t *wr, int32_t *K);
+int icpk_bilateral_host(const icpk_bilateral_params *params, const uint16_t *depth_in, int32_t rows, int32_t cols,
+                        uint16_t *depth_out);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
