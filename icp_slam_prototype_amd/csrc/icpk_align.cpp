@@ -557,6 +557,10 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
       ctx->trace_t.insert(ctx->trace_t.end(), offset, offset + 3);
     } else if (p2l || gicp) {
       if (!solve_p2l(sums, Rd, td)) {
+        // not a completed iteration: it leaves no entry in the trace or the robust trace (as the device loop's step)
+        ctx->trace_pairs.pop_back();
+        ctx->trace_mse.pop_back();
+        if (robust) ctx->robust_trace.pop_back();
         status = ICPK_W_DEGENERATE;
         break;
       }

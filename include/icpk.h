@@ -281,7 +281,9 @@ typedef struct icpk_robust {
  * trim_fraction outside (0, 1]; the setting is then left as it was. */
 int icpk_set_robust(icpk_ctx *ctx, const icpk_robust *r);
 /* Per iteration i < *n_iter of the last robust icpk_align (as icpk_get_trace): the kept count, the cut tau, the scale
- * c and W = sum w of the sweep the iteration solved from.  *n_iter = 0 after an alignment with robust off.  Arrays
+ * c and W = sum w of the sweep the iteration solved from.  *n_iter is icpk_get_trace's: the completed iterations -- an
+ * iteration that ends in the min_pairs fallback or in ICPK_W_DEGENERATE leaves no entry, in the device and the host
+ * loop alike.  *n_iter = 0 after an alignment with robust off.  Arrays
  * sized for params.max_iterations entries; any may be NULL. */
 int icpk_get_robust_trace(icpk_ctx *ctx, int32_t *n_iter, int32_t *kept_out, float *cut_out, double *c_out,
                           double *wsum_out);

@@ -275,6 +275,29 @@ def test_too_few_kept_pairs_fall_back(ctx):
     assert dev[4] == binding.W_TOO_FEW_PAIRS and dev[1][0] == stop > 0
 
 
+def test_degenerate_step_leaves_no_robust_trace_entry(ctx):
+    """Found by soak_cases.soak_flavours("robust_p2l", seed 32074: a plane, one normal everywhere): the 6 x 6 system is
+    singular at the first step.  That iteration is not completed, so it has no entry in the trace or in the robust
+    trace; the host loop used to leave a robust entry for it, the device loop none."""
+    w = synth.lattice_wall(rows=30, cols=40)
+    tn = np.tile(np.float32([[0], [0], [-1]]), (1, w["target"].shape[1]))
+    try:
+        for cfg in (HUBER_MEDIAN, TUKEY_MEDIAN_08, dict(rm.IDENTITY, trim=0.5)):
+            runs = []
+            for nn_mode, host_loop in ((binding.NN_GRID, 0), (binding.NN_EXACT, 1), (binding.NN_GRID, 1)):
+                ctx.set_target(w["target"])
+                ctx.set_target_normals(tn)
+                ctx.set_source(w["source"])
+                runs.append(run(ctx, cfg, solve=binding.SOLVE_POINT_TO_PLANE, nn_mode=nn_mode, host_loop=host_loop,
+                                max_iterations=5, fixed_iterations=1))
+            for r in runs:
+                assert r[4] == binding.W_DEGENERATE and r[1][:2] == (0, binding.W_DEGENERATE) and r[1][2] > 1000
+                assert r[2] == [] and r[3] == []
+                assert r[0].tobytes() == runs[0][0].tobytes() and r[1][:4] == runs[0][1][:4]
+    finally:
+        set_robust(ctx, None)
+
+
 def test_refusals_and_reset(ctx):
     p = kinect_small(seed=7)
     load_pair(ctx, p, False)

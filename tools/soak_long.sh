@@ -6,3 +6,5 @@ echo "== soak_align 8000"; timeout -k 10 1000 python3 tools/soak_align.py 8000 3
 echo "== soak_batch 500"; timeout -k 10 1000 python3 tools/soak_batch.py 500 304000 2>/dev/null | tail -1
 echo "== soak_batch device 400"; timeout -k 10 1000 python3 tools/soak_batch.py --device 400 305000 2>/dev/null | tail -1
 echo "== soak_pair 2500"; timeout -k 10 1000 python3 tools/soak_pair.py 2500 306000 2>&1 | tail -1
+echo "== soak_flavours 5 x 4000"; timeout -k 10 1000 python3 tools/soak_flavours.py 4000 307000 | tail -6
+echo "== soak_neighbourhoods 6 x 720"; timeout -k 10 1000 python3 tools/soak_neighbourhoods.py 720 313000 | tail -7
