@@ -72,11 +72,11 @@ int slot_ingest_device(icpk_ctx* sl, const icpk_pair& pr) {
   if (rc == ICPK_OK) rc = ensure_cloud(sl, sl->src0, pr.ns);
   if (rc == ICPK_OK) rc = ensure_cloud(sl, sl->src, pr.ns);
   if (rc) return rc;
-  launch_ingest_cloud(pr.tx, pr.ty, pr.tz, pr.nt, sl->tgt.cap, __builtin_inff(), sl->tgt.base, sl->tgt.cap, nullptr, 0,
+  launch_ingest_cloud(IngestArgs{pr.tx, pr.ty, pr.tz, pr.nt, sl->tgt.cap, __builtin_inff(), sl->tgt.cap, sl->tgt.base, nullptr, 0, 0},
                       sl->stream);
   // (src.cap <= src0.cap always; both paddings reach their own capacity's first NN_TILE multiple above n)
   const int spad = round_up(pr.ns < 1 ? 1 : pr.ns, NN_TILE);
-  launch_ingest_cloud(pr.sx, pr.sy, pr.sz, pr.ns, spad, 0.f, sl->src0.base, sl->src0.cap, sl->src.base, sl->src.cap,
+  launch_ingest_cloud(IngestArgs{pr.sx, pr.sy, pr.sz, pr.ns, spad, 0.f, sl->src0.cap, sl->src0.base, sl->src.base, sl->src.cap, 0},
                       sl->stream);
   ICPK_HIP(sl, hipGetLastError());
   sl->have_src = true;
@@ -135,7 +135,7 @@ ReduceArgs slot_reduce_args(const icpk_ctx* sl) {
   r.tx = sl->tgt.x();
   r.ty = sl->tgt.y();
   r.tz = sl->tgt.z();
-  r.o4 = sl->have_grid ? sl->o4 : nullptr;
+  r.o4 = sl->have_grid ? sl->grid.o4.get() : nullptr;
   r.rec = sl->rec;
   r.partial = sl->partial;
   r.pcount = sl->pcount;

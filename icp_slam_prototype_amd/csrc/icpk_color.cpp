@@ -101,11 +101,10 @@ int icpk_estimate_target_color_gradients(icpk_ctx* ctx, float radius, int32_t mi
   const Cloud& c = ctx->cgrad;
   if (n > 0) {
     // K1d's index of the target: built here if the target has none yet, and then valid for the alignment that follows
-    if ((rc = prepare_grid_target(ctx))) return rc;
+    GridView v;
+    if ((rc = index_target(ctx, &v))) return rc;
     ColorGradArgs a{};
-    a.t4 = ctx->t4;
-    a.cell_start = ctx->cell_start;
-    a.gi = ctx->grid_info;
+    a.index = v;
     a.nx = ctx->nrm.x(), a.ny = ctx->nrm.y(), a.nz = ctx->nrm.z();
     a.col = ctx->tcol;
     a.col_sorted = ctx->tcol_sorted;

@@ -128,6 +128,21 @@ struct Cloud {
 
 inline int round_up(int v, int m) { return ((v + m - 1) / m) * m; }
 
+// K1d's index of one cloud (kernels_grid.hip): the grid's geometry, the partial boxes it is made from, the cell table
+// and the cloud's two float4 copies.  index_cloud (icpk_sweep.cpp) is the one place that builds into it; kernels that
+// walk it take view().
+struct GridIndex {
+  DevBuf<GridInfo> info;
+  DevBuf<float> bounds;    // GRID_BOUNDS_PARTS x 6
+  DevBuf<int> cell_start;  // grid_max_cells + 1
+  DevBuf<float4> t4;       // the cloud sorted by cell (x, y, z, original index)
+  DevBuf<float4> o4;       // the cloud in the CALLER's order as (x, y, z, 0): K2's gather of the matched point is one 16-byte load
+  GridView view() const { return GridView{t4, cell_start, info}; }
+  // room for the index of n points: t4 / o4 hold round_up(n, NN_TILE) + 64 points and grow as a group; *grown
+  // (optional) is set when their old contents are gone
+  int reserve(icpk_ctx* ctx, int n, bool* grown = nullptr);
+};
+
 // The environment knobs, read once by icpk_create (tuning_from_env) and inherited whole by the
 // frame-batch slots.  Every "diagnostic" knob selects a reference path the tests compare the default one against.
 struct Tuning {
@@ -268,13 +283,11 @@ struct icpk_ctx {
   icpk::CoherentBuf<icpk::RobustTraceEntry> robust_trace_pin;  // LOOP_MAX_ITER entries
   icpk::RobustTraceEntry* robust_trace_dev = nullptr;          // view: the same memory as the device addresses it
   std::vector<icpk::RobustTraceEntry> robust_trace;
-  // grid scan (ICPK_NN_GRID): cell table + AoS copy of the target sorted by cell
-  icpk::DevBuf<GridInfo> grid_info;
-  icpk::DevBuf<float> grid_bounds;
-  icpk::DevBuf<int> cell_start;  // grid_max_cells + 1
-  int grid_max_cells = icpk::GRID_MAX_CELLS;  // capacity of cell_start / qcount / qstart (a frame-batch slot: GRID_MAX_CELLS_SLOT)
-  icpk::DevBuf<float4> t4;
-  icpk::DevBuf<float4> o4;      // the target in the CALLER's order as (x, y, z, 0): K2's gather of the matched point is one 16-byte load (valid while have_grid)
+  // K1d's index (grid scan ICPK_NN_GRID, K12 .. K17): `grid` is the target's, valid while have_grid.  `aux_grid` is the
+  // index of any OTHER cloud (K13: the working source; K14 / K16: the uploaded source): index_aux builds it, the call
+  // that built it reads it, and the next call that builds one overwrites it -- nothing caches it or reads it later
+  icpk::GridIndex grid, aux_grid;
+  int grid_max_cells = icpk::GRID_MAX_CELLS;  // capacity of the cell tables / qcount / qstart (a frame-batch slot: GRID_MAX_CELLS_SLOT)
   icpk::DevBuf<float4> qm4;     // queries in scan order (x, y, z, original index)
   icpk::DevBuf<float4> sp_in;   // seeds as points, scan order: read by the next grid sweep
   icpk::DevBuf<float4> sp_out;  // ... written by it
@@ -345,7 +358,7 @@ struct icpk_ctx {
   int nstats_n = 0;
   // outlier removal (icpk_remove_outliers, K13; icpk_filter.cpp): the statistics of the last call
   // (icpk_get_outlier_stats), the scratch of the threshold and the compaction, the filtered planes on their way into
-  // the cloud, and -- for the working source only -- an index of the filter's own (the target's is ctx->t4 ...)
+  // the cloud (the index it walks is the target's, or aux_grid for the working source)
   icpk::DevBuf<double> flt_value;    // [n_in]
   icpk::DevBuf<float> flt_kth;       // [n_in]
   icpk::DevBuf<int> flt_oidx;        // [n_in]
@@ -357,24 +370,14 @@ struct icpk_ctx {
   icpk::DevBuf<int> flt_counts;      // n_out, n_dropped ...
   icpk::PinnedBuf<int> flt_counts_host;  // ... and where the host reads them
   icpk::DevBuf<float> flt_out;       // 3 planes of n_in floats (6 with normals)
-  icpk::DevBuf<GridInfo> flt_grid_info;
-  icpk::DevBuf<float> flt_grid_bounds;
-  icpk::DevBuf<int> flt_cell_start;  // grid_max_cells + 1
-  icpk::DevBuf<int> flt_cell;        // 2 x n: the counting sort's cell and slot of every point
-  icpk::DevBuf<float4> flt_t4, flt_o4;
   bool have_flt = false;             // a filter has run: the record describes it
   int flt_n_in = 0, flt_n_out = 0, flt_n_finite = 0, flt_kind = 0, flt_min_neighbors = 0;
   // plane-to-plane flavour (ICPK_SOLVE_PLANE_TO_PLANE, K14; icpk_gicp.cpp): the normals of the UPLOADED source in the
   // caller's order (dropped with it: ensure_cloud, icpk_commit_source), the setting, and -- for
-  // icpk_estimate_source_normals only -- K1d's index of the uploaded source and K12's scratch in buffers of their own
+  // icpk_estimate_source_normals only -- K12's scratch in buffers of their own (the index it walks is aux_grid)
   icpk::Cloud snrm;
   bool have_src_normals = false;
   float gicp_epsilon = 1e-3f;
-  icpk::DevBuf<GridInfo> sn_grid_info;
-  icpk::DevBuf<float> sn_grid_bounds;
-  icpk::DevBuf<int> sn_cell_start;  // grid_max_cells + 1
-  icpk::DevBuf<int> sn_cell;        // 2 x n: the counting sort's cell and slot of every point
-  icpk::DevBuf<float4> sn_t4, sn_o4;
   icpk::DevBuf<long long> sn_moments;  // [n][NRM_MOMENTS]
   icpk::DevBuf<int> sn_count;          // [n]
   icpk::DevBuf<float> sn_curv;         // [n]
@@ -529,13 +532,15 @@ void clear_trace(icpk_ctx* ctx);                        // icpk_get_trace's reco
 // ---- icpk_sweep.cpp: device buffers, NN sweeps, reductions ----
 int ensure_cloud(icpk_ctx* ctx, Cloud& c, int n);  // room for n points (the contents are undefined after a resize)
 int ensure_assoc(icpk_ctx* ctx, int nq);
-// K1d's index of the target (geometry, cell table, cell-sorted copy): built unless have_grid; everything is enqueued
-int prepare_grid_target(icpk_ctx* ctx);
-// the same index of ANY cloud of n points, into buffers of the caller's (K13 indexes the working source): bounds
-// GRID_BOUNDS_PARTS x 6 floats, cell / slot n ints each, cell_start grid_max_cells + 1, t4 / o4 n points.  Of the
-// context's own state only the count table's scratch is used, which every sort leaves as it found it
-int build_grid_index(icpk_ctx* ctx, const float* x, const float* y, const float* z, int n, float* bounds, GridInfo* gi,
-                     int* cell, int* slot, int* cell_start, float4* t4, float4* o4);
+// K1d's index of n points into g (reserved by the caller), everything enqueued: bounds, geometry, cell slots, scan,
+// scatter.  The counting sort's cell and slot of every point go through the context's sort scratch, which nothing reads
+// after the build that wrote it; the count table is left as it was found
+int index_cloud(icpk_ctx* ctx, const float* x, const float* y, const float* z, int n, GridIndex& g);
+// the target's index in ctx->grid: built unless have_grid, and then valid until the target changes
+int index_target(icpk_ctx* ctx, GridView* out);
+// the index of any other cloud the context holds, in ctx->aux_grid: valid until the next index_aux call, so *out is
+// used up inside the call that asked for it.  Neither have_grid nor the target's index is touched
+int index_aux(icpk_ctx* ctx, const Cloud& c, GridView* out);
 // the working source planes hold the cloud icpk_get_source would return (a device loop may leave them to be unpacked)
 int ensure_unpacked(icpk_ctx* ctx);
 int flush_loop_init(icpk_ctx* ctx);
@@ -561,11 +566,6 @@ int ensure_robust(icpk_ctx* ctx, int nq);
 // ... and the selection + the weighted K2 / K5 over the current associations (NSUM_W / NP2L_W sums; outside a device
 // loop the sums, the count and the selection state are read back into red_host / rsel_host, not waited for)
 int enqueue_reduce_robust(icpk_ctx* ctx, float max_dist, bool p2l);
-
-// ---- icpk_gicp.cpp ----
-// K1d's index of the UPLOADED source in the sn_* buffers (K14's source normals, K16's source descriptors): neither the
-// target's index nor the filter's is touched
-int build_uploaded_source_index(icpk_ctx* ctx);
 
 // ---- icpk_align.cpp: the device-side loop, shared by the single-pair and the frame-batch path ----
 int loop_nsum(const icpk_params* p);

@@ -28,21 +28,6 @@ int ensure_filter_buffers(icpk_ctx* ctx, int n_in, bool normals) {
   return rc;
 }
 
-// K1d's index of the working source in buffers of the filter's own: the target's have_grid state is not touched
-int build_source_index(icpk_ctx* ctx) {
-  const Cloud& c = ctx->src;
-  const size_t n = (size_t)c.n;
-  int rc = ctx->flt_grid_info.reserve(ctx, 1);
-  if (!rc) rc = ctx->flt_grid_bounds.reserve(ctx, (size_t)GRID_BOUNDS_PARTS * 6);
-  if (!rc) rc = ctx->flt_cell_start.reserve(ctx, (size_t)ctx->grid_max_cells + 1);
-  if (!rc) rc = ctx->flt_cell.reserve(ctx, 2 * n);
-  if (!rc) rc = ctx->flt_t4.reserve(ctx, n + 64);
-  if (!rc) rc = ctx->flt_o4.reserve(ctx, n + 64);
-  if (rc) return rc;
-  return build_grid_index(ctx, c.x(), c.y(), c.z(), c.n, ctx->flt_grid_bounds, ctx->flt_grid_info, ctx->flt_cell,
-                          ctx->flt_cell + n, ctx->flt_cell_start, ctx->flt_t4, ctx->flt_o4);
-}
-
 }  // namespace
 
 extern "C" {
@@ -79,26 +64,22 @@ int icpk_remove_outliers(icpk_ctx* ctx, int32_t which, const icpk_outlier_filter
   ICPK_HIP(ctx, hipMemsetAsync(ctx->flt_summary, 0, 4 * sizeof(double), ctx->stream));
   if (n > 0) {
     // the index: the target's own (built here if it has none yet, and then valid for the alignment that follows), or
-    // one of the working source in the filter's buffers
-    if ((rc = which == 1 ? prepare_grid_target(ctx) : build_source_index(ctx))) return rc;
-    const float4* t4 = which == 1 ? ctx->t4.get() : ctx->flt_t4.get();
-    const int* cell_start = which == 1 ? ctx->cell_start.get() : ctx->flt_cell_start.get();
-    const GridInfo* gi = which == 1 ? ctx->grid_info.get() : ctx->flt_grid_info.get();
+    // one of the working source in aux_grid (the target's have_grid state is not touched)
+    GridView v;
+    if ((rc = which == 1 ? index_target(ctx, &v) : index_aux(ctx, ctx->src, &v))) return rc;
     ICPK_HIP(ctx, hipMemsetAsync(ctx->flt_counts, 0, 2 * sizeof(int), ctx->stream));
     if (f->kind == ICPK_FILTER_STATISTICAL) {
       KnnArgs q{};
-      q.q4 = t4;  // every point against its own cloud
+      q.q4 = v.t4;  // every point against its own cloud
       q.nq = n;
       q.k = f->k;
       q.r0_scale = 2.5f / (3.14159265f * ctx->tune.grid_ppc);
-      q.t4 = t4;
-      q.cell_start = cell_start;
-      q.gi = gi;
+      q.index = v;
       q.mean = ctx->flt_value;
       q.kth = ctx->flt_kth;
       launch_knn_mean(q, ctx->stream);
     } else {
-      launch_radius_count(t4, cell_start, gi, n, f->radius, ctx->flt_value, ctx->stream);
+      launch_radius_count(v, n, f->radius, ctx->flt_value, ctx->stream);
     }
     o = ctx->flt_out;
     FilterArgs a{};

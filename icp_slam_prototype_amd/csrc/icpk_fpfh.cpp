@@ -37,20 +37,12 @@ int icpk_compute_fpfh(icpk_ctx* ctx, int32_t which, float radius, int32_t flags)
   if (!rc && keep) rc = f.m.reserve(ctx, cap);
   if (rc) return rc;
   if (n > 0) {
+    // the source walks an index of its own (aux_grid): the target's is not disturbed.  K1d's index of the target: built
+    // here if the target has none yet, and then valid for the alignment that follows
+    GridView v;
+    if ((rc = which == 0 ? index_aux(ctx, ctx->src0, &v) : index_target(ctx, &v))) return rc;
     FpfhArgs a{};
-    if (which == 0) {
-      // the source walks an index of its own (K14's buffers): the target's is not disturbed
-      if ((rc = build_uploaded_source_index(ctx))) return rc;
-      a.t4 = ctx->sn_t4;
-      a.cell_start = ctx->sn_cell_start;
-      a.gi = ctx->sn_grid_info;
-    } else {
-      // K1d's index of the target: built here if the target has none yet, and then valid for the alignment that follows
-      if ((rc = prepare_grid_target(ctx))) return rc;
-      a.t4 = ctx->t4;
-      a.cell_start = ctx->cell_start;
-      a.gi = ctx->grid_info;
-    }
+    a.index = v;
     a.nx = nrm.x(), a.ny = nrm.y(), a.nz = nrm.z();
     a.n = n;
     a.radius = radius;

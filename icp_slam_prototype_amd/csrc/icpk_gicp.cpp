@@ -1,5 +1,5 @@
 // icpk_gicp.cpp -- host side of the plane-to-plane flavour (ICPK_SOLVE_PLANE_TO_PLANE, K14; kernels_gicp.hip): the
-// normals of the uploaded source (estimated by K12's kernels over an index of the source in buffers of their own, or
+// normals of the uploaded source (estimated by K12's kernels over an index of the source in the context's aux_grid, or
 // taken from the host), the epsilon setting and the test hook icpk_reduce_plane_to_plane.  The loop itself is
 // icpk_align's (icpk_align.cpp).
 #include <cmath>
@@ -8,24 +8,6 @@
 #include "icpk_ctx.h"
 
 using namespace icpk;
-
-namespace icpk {
-
-int build_uploaded_source_index(icpk_ctx* ctx) {
-  const Cloud& c = ctx->src0;
-  const size_t n = (size_t)c.n;
-  int rc = ctx->sn_grid_info.reserve(ctx, 1);
-  if (!rc) rc = ctx->sn_grid_bounds.reserve(ctx, (size_t)GRID_BOUNDS_PARTS * 6);
-  if (!rc) rc = ctx->sn_cell_start.reserve(ctx, (size_t)ctx->grid_max_cells + 1);
-  if (!rc) rc = ctx->sn_cell.reserve(ctx, 2 * n);
-  if (!rc) rc = ctx->sn_t4.reserve(ctx, n + 64);
-  if (!rc) rc = ctx->sn_o4.reserve(ctx, n + 64);
-  if (rc) return rc;
-  return build_grid_index(ctx, c.x(), c.y(), c.z(), c.n, ctx->sn_grid_bounds, ctx->sn_grid_info, ctx->sn_cell,
-                          ctx->sn_cell + n, ctx->sn_cell_start, ctx->sn_t4, ctx->sn_o4);
-}
-
-}  // namespace icpk
 
 namespace {
 
@@ -62,12 +44,11 @@ int icpk_estimate_source_normals(icpk_ctx* ctx, float radius, int32_t min_neighb
   fpfh_dropped(ctx, 0);
   const Cloud& c = ctx->snrm;
   if (n > 0) {
-    if ((rc = build_uploaded_source_index(ctx))) return rc;
+    GridView v;  // (the uploaded source's index, in aux_grid: the target's is not disturbed)
+    if ((rc = index_aux(ctx, ctx->src0, &v))) return rc;
     ICPK_HIP(ctx, hipMemsetAsync(ctx->sn_valid, 0, sizeof(int), ctx->stream));
     NormalsArgs a{};
-    a.t4 = ctx->sn_t4;
-    a.cell_start = ctx->sn_cell_start;
-    a.gi = ctx->sn_grid_info;
+    a.index = v;
     a.x = ctx->src0.x(), a.y = ctx->src0.y(), a.z = ctx->src0.z();
     a.n = n;
     a.radius = radius;

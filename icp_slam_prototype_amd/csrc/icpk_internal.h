@@ -2,6 +2,7 @@
 // kernels.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "tsdf_rule.h"
@@ -130,20 +131,15 @@ struct GridInfo {
   int nxq;       // cells along x of the coarser grid that orders the queries (nx / xdiv)
   int ncells_q;
 };
-void launch_grid_bounds(const float* x, const float* y, const float* z, int n, float* fb, hipStream_t s);
-void launch_grid_info(const float* fb, int n, float ppc, int xdiv, int max_cells, GridInfo* g, hipStream_t s);
-void launch_grid_tscatter(const float* x, const float* y, const float* z, const int* tcell, const int* tslot,
-                          const int* cell_start, int n, float4* t4, float4* o4, hipStream_t s);
-void launch_grid_qslot(const float* x, const float* y, const float* z, int n, const GridInfo* g, int* count, int* qcell,
-                       int* qslot, int coarse, hipStream_t s);
-// qm4 != nullptr: also the scan-order queries, element 0 as every query's seed point and seed key
-// spix / tidx / rows / cols: pixel seeds (QscatterArgs) or nullptr
-void launch_grid_qscatter(const int* qcell, const int* qslot, const int* qstart, int n, int* qperm, const float* qx,
-                          const float* qy, const float* qz, const float* ox, const float* oy, const float* oz,
-                          float4* qm4, float4* sp, nn_key_t* seed_m, hipStream_t s, const int* spix = nullptr,
-                          const int* tidx = nullptr, int rows = 0, int cols = 0);
+// K1d's index of a cloud as a kernel that walks it takes it (K12, K13, K14, K15, K16, K17; GridIndex::view, icpk_ctx.h)
+struct GridView {
+  const float4* t4;       // the cloud sorted by cell (x, y, z, original index)
+  const int* cell_start;  // ncells + 1 entries
+  const GridInfo* gi;
+};
 constexpr int GRID_SCAN_BLOCKS = (GRID_MAX_CELLS + 1 + 2047) / 2048 + 1;  // scratch ints of launch_grid_scan
-void launch_grid_scan(int* count, int* out, int* bsum, const GridInfo* g, int coarse, hipStream_t s);  // count[] left zero
+// (the index's set-up steps -- bounds, info, cell slots, scan, scatters -- take their argument structs: see the deferred
+// set-up launches below)
 // one pair's arguments of a grid sweep (K1d); see nn_grid_body
 struct GridSweepArgs {
   float *qx, *qy, *qz;  // the caller's source planes (kept in step when K3 is fused)
@@ -302,9 +298,7 @@ void launch_gicp_reduce(const PairArgs& a, const GicpArgs& g, hipStream_t s);
 // out in include/icpk.h)
 constexpr int COLOR_SUMS = 10;  // per point: m, S_00 S_01 S_02 S_11 S_12 S_22, T_0 T_1 T_2 (int64 each)
 struct ColorGradArgs {
-  const float4* t4;  // the target sorted by cell (x, y, z, original index): K1d's index
-  const int* cell_start;
-  const GridInfo* gi;
+  GridView index;             // K1d's index of the target
   const float *nx, *ny, *nz;  // target normals, caller's order
   const float* col;           // target intensities, caller's order
   float* col_sorted;          // [n] scratch: the intensities in cell order
@@ -314,6 +308,7 @@ struct ColorGradArgs {
   long long* sums;      // [n][COLOR_SUMS], caller's order
   float *gx, *gy, *gz;  // [n]
 };
+static_assert(sizeof(ColorGradArgs) == 112 && offsetof(ColorGradArgs, index) == 0, "the kernarg layout is pinned");
 // the three launches of one estimate (gather, sums, solve); n <= 0: nothing
 void launch_color_gradients(const ColorGradArgs& a, hipStream_t s);
 struct ColoredArgs {
@@ -379,8 +374,6 @@ struct RobustWeight {
 // kernels_transform.hip
 void launch_transform(float* x, float* y, float* z, int n, const Rt& rt, hipStream_t s);
 void launch_fill_f32(float* p, int n, float v, hipStream_t s);
-void launch_ingest_cloud(const float* x, const float* y, const float* z, int n, int n_pad, float pad, float* d1, int cap1,
-                         float* d2, int cap2, hipStream_t s);
 
 // kernels_backproject.hip
 // counts: [ceil(npix/1024)+1] ints scratch.  Returns nothing; *n_out (device)
@@ -553,13 +546,50 @@ struct SetupRecorder {
   bool overflow = false;
 };
 SetupRecorder*& setup_recorder();  // of the calling thread; nullptr: launch at once
+// THE record point, shared by every step launcher below: with a recorder installed the step's arguments are kept
+// instead of launched (true: the launcher has nothing left to do).  A launcher whose step has nothing to do (n <= 0)
+// returns before it gets here: an empty step is never recorded, and that decides whether a group's sequences are equal
+template <typename A>
+bool record_setup_step(int kind, A SetupCall::*field, const A& a) {
+  SetupRecorder* const r = setup_recorder();
+  if (!r) return false;
+  if (r->n < SETUP_MAX_CALLS) {
+    r->calls[r->n].kind = kind;
+    r->calls[r->n++].*field = a;
+  } else {
+    r->overflow = true;
+  }
+  return true;
+}
 template <typename A>
 struct SetupBatchOf {
   A p[BATCH_MAX];
 };
-void launch_grid_begin(const float* x, const float* y, const float* z, int n, float* fb, float ppc, int xdiv, int max_cells,
-                       GridInfo* g, const LoopInitArgs* init, int* ticket, hipStream_t s);
-void launch_loop_init(const LoopInitArgs& a, hipStream_t s);
+// the two steps whose arguments are normalised: every caller makes them here
+inline int grid_bounds_parts(int n) {  // one 1024-thread block per 2048 points, at most GRID_BOUNDS_PARTS
+  const int nb = (n + 2047) / 2048;
+  return nb < 1 ? 1 : (nb > GRID_BOUNDS_PARTS ? GRID_BOUNDS_PARTS : nb);
+}
+inline BoundsArgs bounds_args(const float* x, const float* y, const float* z, int n, float* fb) {
+  return BoundsArgs{x, y, z, fb, n, grid_bounds_parts(n)};
+}
+// (fb: the partial boxes a bounds step over the same n points leaves)
+inline InfoArgs info_args(const float* fb, int n, float ppc, int xdiv, int max_cells, GridInfo* g) {
+  return InfoArgs{fb, g, grid_bounds_parts(n), n, ppc, xdiv < 1 ? 1 : xdiv, max_cells < 64 ? 64 : max_cells, 0};
+}
+// Every step has ONE shape: its argument struct and a stream (recorded or launched, see above), and a _batch form that
+// takes the structs of `count` pairs.  tscatter, qslot and qscatter do nothing for n <= 0, ingest for n_pad <= 0.
+void launch_ingest_cloud(const IngestArgs& a, hipStream_t s);  // kernels_transform.hip
+void launch_loop_init(const LoopInitArgs& a, hipStream_t s);   // kernels_loop.hip
+void launch_grid_bounds(const BoundsArgs& a, hipStream_t s);
+void launch_grid_info(const InfoArgs& a, hipStream_t s);
+void launch_grid_qslot(const QslotArgs& a, hipStream_t s);
+void launch_grid_scan(const ScanArgs& a, hipStream_t s);  // count[] is left zero; bsum: GRID_SCAN_BLOCKS ints
+void launch_grid_tscatter(const TscatterArgs& a, hipStream_t s);
+// qm4 != nullptr: also the scan-order queries and every query's seed point and seed key
+void launch_grid_qscatter(const QscatterArgs& a, hipStream_t s);
+// bounds + info (+ the initial LoopState, init != nullptr) of a fresh pair in one launch; never recorded
+void launch_grid_begin(const BoundsArgs& a, const InfoArgs& info, const LoopInitArgs* init, int* ticket, hipStream_t s);
 // one launch per recorded step for `count` pairs, in recording order; returns false if the sequences differ
 // (nothing launched then: replay them with replay_setup)
 bool flush_setup_batches(const SetupRecorder* recs, int count, hipStream_t s);
@@ -683,9 +713,7 @@ void launch_voxel_downsample(const VoxelArgs& a, hipStream_t s);
 // kernels_normals.hip -- K12, target normals from the target's own geometry (icpk_estimate_target_normals)
 constexpr int NRM_MOMENTS = 10;  // per point: m, S_x S_y S_z, S_xx S_xy S_xz S_yy S_yz S_zz (int64 each)
 struct NormalsArgs {
-  const float4* t4;           // the target sorted by cell (x, y, z, original index): K1d's index
-  const int* cell_start;
-  const GridInfo* gi;
+  GridView index;             // K1d's index of the cloud
   const float *x, *y, *z;     // the target in the caller's order, n points
   int n;
   float radius;
@@ -698,6 +726,7 @@ struct NormalsArgs {
   float* curvature;           // [n]
   int* n_valid;               // added to: zero before the launch
 };
+static_assert(sizeof(NormalsArgs) == 136 && offsetof(NormalsArgs, index) == 0, "the kernarg layout is pinned");
 // the two launches of one estimate (moments, then the eigen-solve); n <= 0: nothing
 void launch_estimate_normals(const NormalsArgs& a, hipStream_t s);
 
@@ -711,12 +740,11 @@ struct KnnArgs {
   int k;                   // 1 .. FILTER_MAX_K
   float r0_scale;          // first search radius = h sqrt((k + 1) r0_scale), h the cell edge (efficiency only)
   int pad0;
-  const float4* t4;       // the indexed cloud sorted by cell (x, y, z, original index): K1d's index
-  const int* cell_start;
-  const GridInfo* gi;
+  GridView index;          // K1d's index of the indexed cloud
   double* mean;            // [.] at bits(w) of the query: the mean of its k' smallest distances (0: none, or not finite)
   float* kth;              // [.] the k'-th
 };
+static_assert(sizeof(KnnArgs) == 64 && offsetof(KnnArgs, index) == 24, "the kernarg layout is pinned");
 void launch_knn_mean(const KnnArgs& a, hipStream_t s);
 struct FilterArgs {
   const float *x, *y, *z;     // the cloud, n points
@@ -736,8 +764,7 @@ struct FilterArgs {
   int* out_index;             // [n]
 };
 // RADIUS: value[i] = (double)m_i over K1d's index of the same cloud (K12's neighbourhood)
-void launch_radius_count(const float4* t4, const int* cell_start, const GridInfo* gi, int n, float radius, double* value,
-                         hipStream_t s);
+void launch_radius_count(const GridView& index, int n, float radius, double* value, hipStream_t s);
 // threshold (STATISTICAL: the canonical sums, then mu, sigma, T on one lane) and the order-preserving compaction
 void launch_filter_compact(const FilterArgs& a, hipStream_t s);
 
@@ -750,15 +777,14 @@ struct ScoreArgs {
   int ns;
   float max_dist;
   const float* T;             // 16 floats per pose of this launch (row-major 4 x 4), or nullptr: the points as they stand
-  const float4* t4;           // the target sorted by cell (x, y, z, original index): K1d's index
-  const int* cell_start;
-  const GridInfo* gi;
+  GridView index;             // K1d's index of the target
   const float4* o4;           // the target in the caller's order
   nn_key_t* keys;             // [poses][ns]: an inlier's (distance bits << 32) | index, NN_KEY_INIT for the others
   double* partial;            // [poses][NSCORE][RED_MAX_BLOCKS] scratch of the canonical tree
   int* pcount;                // [poses][RED_MAX_BLOCKS]
   double* out;                // [poses][NSCORE + 1]: the sums, then the inlier count as an int64
 };
+static_assert(sizeof(ScoreArgs) == 104 && offsetof(ScoreArgs, index) == 40, "the kernarg layout is pinned");
 // the three launches of one chunk of poses (search, per-block sums, final sums); n_poses <= 0: nothing
 void launch_score_poses(const ScoreArgs& a, int n_poses, hipStream_t s);
 
@@ -766,9 +792,7 @@ void launch_score_poses(const ScoreArgs& a, int n_poses, hipStream_t s);
 constexpr int FPFH_BINS = 33;       // ICPK_FPFH_BINS: three sub-histograms of 11 bins
 constexpr int FPFH_G_STRIDE = 34;   // 16-bit words per point of the normalised SPFH: the 33 bins, then "m > 0"
 struct FpfhArgs {
-  const float4* t4;           // the cloud sorted by cell (x, y, z, original index): K1d's index
-  const int* cell_start;
-  const GridInfo* gi;
+  GridView index;             // K1d's index of the cloud
   const float *nx, *ny, *nz;  // its normals in the caller's order, n each
   int n;
   float radius;
@@ -779,6 +803,7 @@ struct FpfhArgs {
   float* desc;                // [n][FPFH_BINS] caller's order
   uint8_t* valid;             // [n]
 };
+static_assert(sizeof(FpfhArgs) == 104 && offsetof(FpfhArgs, index) == 0, "the kernarg layout is pinned");
 // the three launches of one cloud's descriptors (normals into cell order, SPFH, FPFH); n <= 0: nothing
 void launch_compute_fpfh(const FpfhArgs& a, hipStream_t s);
 struct MatchArgs {

@@ -34,11 +34,10 @@ int icpk_estimate_target_normals(icpk_ctx* ctx, float radius, int32_t min_neighb
   ICPK_HIP(ctx, hipMemsetAsync(ctx->nrm_valid, 0, sizeof(int), ctx->stream));
   if (n > 0) {
     // K1d's index of the target: built here if the target has none yet, and then valid for the alignment that follows
-    if ((rc = prepare_grid_target(ctx))) return rc;
+    GridView v;
+    if ((rc = index_target(ctx, &v))) return rc;
     NormalsArgs a{};
-    a.t4 = ctx->t4;
-    a.cell_start = ctx->cell_start;
-    a.gi = ctx->grid_info;
+    a.index = v;
     a.x = ctx->tgt.x(), a.y = ctx->tgt.y(), a.z = ctx->tgt.z();
     a.n = n;
     a.radius = radius;

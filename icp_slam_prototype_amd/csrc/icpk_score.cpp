@@ -46,7 +46,8 @@ int icpk_score_poses(icpk_ctx* ctx, int32_t n_poses, const float* T, float max_d
   if (!rc && T) rc = ctx->score_T_host.reserve(ctx, (size_t)n_poses * 16);
   if (rc) return rc;
   // K1d's index of the target: built here if the target has none yet, and then valid for the alignment that follows
-  if ((rc = prepare_grid_target(ctx))) return rc;
+  GridView v;
+  if ((rc = index_target(ctx, &v))) return rc;
   if (T) {
     std::memcpy(ctx->score_T_host, T, (size_t)n_poses * 16 * sizeof(float));
     ICPK_HIP(ctx, hipMemcpyAsync(ctx->score_T, ctx->score_T_host, (size_t)n_poses * 16 * sizeof(float),
@@ -56,10 +57,8 @@ int icpk_score_poses(icpk_ctx* ctx, int32_t n_poses, const float* T, float max_d
   a.sx = src.x(), a.sy = src.y(), a.sz = src.z();
   a.ns = ns;
   a.max_dist = max_dist;
-  a.t4 = ctx->t4;
-  a.cell_start = ctx->cell_start;
-  a.gi = ctx->grid_info;
-  a.o4 = ctx->o4;
+  a.index = v;
+  a.o4 = ctx->grid.o4;
   a.partial = ctx->score_partial;
   a.pcount = ctx->score_pcount;
   for (int k0 = 0; k0 < n_poses; k0 += chunk) {

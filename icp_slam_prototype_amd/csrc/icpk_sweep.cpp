@@ -128,66 +128,73 @@ static int ensure_scan_buffers(icpk_ctx* ctx) {
   return rc ? rc : ctx->scan_bsum.reserve(ctx, GRID_SCAN_BLOCKS);
 }
 
-// the grid scan's geometry, cell table and float4 copies of the target (a reallocation drops the grid)
-static int ensure_grid_buffers(icpk_ctx* ctx) {
-  const int nt = ctx->tgt.n;
-  if (nt > (1 << 28)) return fail(ctx, ICPK_E_ARG, "the grid search addresses its cell-sorted targets with 32-bit byte offsets: at most 2^28 target points");
-  int rc = ctx->grid_info.reserve(ctx, 1);
-  if (!rc) rc = ctx->grid_bounds.reserve(ctx, (size_t)GRID_BOUNDS_PARTS * 6);
-  if (!rc) rc = ctx->cell_start.reserve(ctx, (size_t)ctx->grid_max_cells + 1);
+int GridIndex::reserve(icpk_ctx* ctx, int n, bool* grown) {
+  int rc = info.reserve(ctx, 1);
+  if (!rc) rc = bounds.reserve(ctx, (size_t)GRID_BOUNDS_PARTS * 6);
+  if (!rc) rc = cell_start.reserve(ctx, (size_t)ctx->grid_max_cells + 1);
   if (rc) return rc;
-  const size_t n4 = (size_t)round_up(nt, NN_TILE) + 64;
+  const size_t n4 = (size_t)round_up(n, NN_TILE) + 64;
+  return reserve_group(ctx, grown, need(t4, n4), need(o4, n4));
+}
+
+// room for the target's index (a reallocation drops the grid)
+static int reserve_target_index(icpk_ctx* ctx) {
+  if (ctx->tgt.n > (1 << 28)) return fail(ctx, ICPK_E_ARG, "the grid search addresses its cell-sorted targets with 32-bit byte offsets: at most 2^28 target points");
   bool grown = false;
-  rc = reserve_group(ctx, &grown, need(ctx->t4, n4), need(ctx->o4, n4));
+  const int rc = ctx->grid.reserve(ctx, ctx->tgt.n, &grown);
   if (grown) ctx->have_grid = false;
   return rc;
 }
 
-// cell table + cell-sorted AoS copy of the target for the grid scan (once per target cloud).
 // Everything is enqueued: the grid's size stays on the device (GridInfo), the counting sort's
 // zero fill and scan read it there -- no host round trip, so the frame-batch mode can build the
 // next group's grids in the shadow of the running loop.
-int prepare_grid_target(icpk_ctx* ctx) {
-  const int nt = ctx->tgt.n;
-  int rc = ensure_grid_buffers(ctx);
-  if (rc || ctx->have_grid) return rc;
-  rc = ensure_sort_buffers(ctx, nt);
+int index_cloud(icpk_ctx* ctx, const float* x, const float* y, const float* z, int n, GridIndex& g) {
+  int rc = ensure_sort_buffers(ctx, n);
+  if (!rc) rc = ensure_scan_buffers(ctx);
   if (rc) return rc;
-  rc = ensure_scan_buffers(ctx);
-  if (rc) return rc;
-  launch_grid_bounds(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), nt, ctx->grid_bounds, ctx->stream);
-  launch_grid_info(ctx->grid_bounds, nt, ctx->tune.grid_ppc, ctx->tune.grid_xdiv, ctx->grid_max_cells, ctx->grid_info, ctx->stream);
-  // counting sort of the targets by cell: slot within the cell by atomics (the order inside a
+  launch_grid_bounds(bounds_args(x, y, z, n, g.bounds), ctx->stream);
+  launch_grid_info(info_args(g.bounds, n, ctx->tune.grid_ppc, ctx->tune.grid_xdiv, ctx->grid_max_cells, g.info), ctx->stream);
+  // counting sort of the points by cell: slot within the cell by atomics (the order inside a
   // cell is irrelevant: candidates are merged lexicographically), cell starts by an exclusive
-  // scan of the counts (entry ncells = Nt), scatter into the AoS copy
-  int* tcell = reinterpret_cast<int*>(ctx->sort_keys + ctx->sort_cap);
-  int* tslot = ctx->sort_vals;
+  // scan of the counts (entry ncells = n), scatter into the AoS copy
+  int* cell = reinterpret_cast<int*>(ctx->sort_keys + ctx->sort_cap);
+  int* slot = ctx->sort_vals;
   ctx->qcount_dirty = true;
-  launch_grid_qslot(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), nt, ctx->grid_info, ctx->qcount, tcell, tslot, 0,
-                    ctx->stream);
-  launch_grid_scan(ctx->qcount, ctx->cell_start, ctx->scan_bsum, ctx->grid_info, 0, ctx->stream);
-  launch_grid_tscatter(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), tcell, tslot, ctx->cell_start, nt, ctx->t4, ctx->o4,
-                       ctx->stream);
+  launch_grid_qslot(QslotArgs{x, y, z, g.info, ctx->qcount, cell, slot, n, 0}, ctx->stream);
+  launch_grid_scan(ScanArgs{ctx->qcount, g.cell_start, ctx->scan_bsum, g.info, 0, 0}, ctx->stream);
+  launch_grid_tscatter(TscatterArgs{x, y, z, cell, slot, g.cell_start, g.t4, g.o4, n, 0}, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
   ctx->qcount_dirty = false;
-  ctx->have_grid = true;
   return ICPK_OK;
 }
 
-int build_grid_index(icpk_ctx* ctx, const float* x, const float* y, const float* z, int n, float* bounds, GridInfo* gi,
-                     int* cell, int* slot, int* cell_start, float4* t4, float4* o4) {
-  if (n > (1 << 28)) return fail(ctx, ICPK_E_ARG, "the grid search addresses its cell-sorted points with 32-bit byte offsets: at most 2^28 points");
-  int rc = ensure_scan_buffers(ctx);
-  if (rc) return rc;
-  launch_grid_bounds(x, y, z, n, bounds, ctx->stream);
-  launch_grid_info(bounds, n, ctx->tune.grid_ppc, ctx->tune.grid_xdiv, ctx->grid_max_cells, gi, ctx->stream);
-  ctx->qcount_dirty = true;
-  launch_grid_qslot(x, y, z, n, gi, ctx->qcount, cell, slot, 0, ctx->stream);
-  launch_grid_scan(ctx->qcount, cell_start, ctx->scan_bsum, gi, 0, ctx->stream);
-  launch_grid_tscatter(x, y, z, cell, slot, cell_start, n, t4, o4, ctx->stream);
-  ICPK_HIP(ctx, hipGetLastError());
-  ctx->qcount_dirty = false;
-  return ICPK_OK;
+// (once per target cloud)
+int index_target(icpk_ctx* ctx, GridView* out) {
+  int rc = reserve_target_index(ctx);
+  if (!rc && !ctx->have_grid) {
+    rc = index_cloud(ctx, ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), ctx->tgt.n, ctx->grid);
+    ctx->have_grid = !rc;
+  }
+  if (!rc && out) *out = ctx->grid.view();
+  return rc;
+}
+
+int index_aux(icpk_ctx* ctx, const Cloud& c, GridView* out) {
+  if (c.n > (1 << 28)) return fail(ctx, ICPK_E_ARG, "the grid search addresses its cell-sorted points with 32-bit byte offsets: at most 2^28 points");
+  int rc = ctx->aux_grid.reserve(ctx, c.n);
+  if (!rc) rc = index_cloud(ctx, c.x(), c.y(), c.z(), c.n, ctx->aux_grid);
+  if (!rc) *out = ctx->aux_grid.view();
+  return rc;
+}
+
+// the scatter of the working source into scan order (qm4 != nullptr: with the scan-order queries and their seeds; pix: the
+// seeds come from the pixel maps)
+static QscatterArgs query_scatter_args(icpk_ctx* ctx, const int* qcell, const int* qslot, float4* qm4, bool pix) {
+  return QscatterArgs{qcell,        qslot,        ctx->qstart,  ctx->qperm, ctx->src.x(), ctx->src.y(), ctx->src.z(),
+                      ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), qm4,        ctx->sp_in,   ctx->seed_m,  ctx->src.n,
+                      0,            pix ? ctx->pix_src.get() : nullptr,     pix ? ctx->pix_tidx.get() : nullptr,
+                      ctx->pix_rows, ctx->pix_cols};
 }
 
 // query order for the grid scan: counting sort of the source by cell of the target's grid.
@@ -208,14 +215,12 @@ static int enqueue_cell_order(icpk_ctx* ctx, bool with_points) {
   if (!ident) {
     // (locality only: the coarser table, xdiv times fewer counts to scan)
     ctx->qcount_dirty = true;
-    launch_grid_qslot(ctx->src.x(), ctx->src.y(), ctx->src.z(), nq, ctx->grid_info, ctx->qcount, qcell, qslot, 1,
+    launch_grid_qslot(QslotArgs{ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->grid.info, ctx->qcount, qcell, qslot, nq, 1},
                       ctx->stream);
-    launch_grid_scan(ctx->qcount, ctx->qstart, ctx->scan_bsum, ctx->grid_info, 1, ctx->stream);
+    launch_grid_scan(ScanArgs{ctx->qcount, ctx->qstart, ctx->scan_bsum, ctx->grid.info, 1, 0}, ctx->stream);
   }
-  launch_grid_qscatter(ident ? nullptr : qcell, qslot, ctx->qstart, nq, ctx->qperm, ctx->src.x(), ctx->src.y(),
-                       ctx->src.z(), ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), with_points ? ctx->qm4 : nullptr,
-                       ctx->sp_in, ctx->seed_m, ctx->stream, pix ? ctx->pix_src.get() : nullptr,
-                       pix ? ctx->pix_tidx.get() : nullptr, ctx->pix_rows, ctx->pix_cols);
+  launch_grid_qscatter(query_scatter_args(ctx, ident ? nullptr : qcell, qslot, with_points ? ctx->qm4.get() : nullptr, pix),
+                       ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
   ctx->qcount_dirty = false;
   return ICPK_OK;
@@ -248,11 +253,11 @@ int flush_loop_init(icpk_ctx* ctx) {
 // A FRESH pair (new target, new source, no seeds: every frame of the drop-in path): the target's grid and the
 // query order in 6 launches instead of 10 -- the two counting sorts run side by side (cell slots of both clouds in one
 // launch, both scans in two, both scatters in one), each with its own count table.  Same kernels' bodies as
-// prepare_grid_target + enqueue_cell_order: same tables, same copies.  ~5 us of launch latency per launch saved on a
+// index_target + enqueue_cell_order: same tables, same copies.  ~5 us of launch latency per launch saved on a
 // path that is a chain of tiny dependent kernels.
 static int build_grid_and_order(icpk_ctx* ctx) {
   const int nt = ctx->tgt.n, nq = ctx->src.n;
-  int rc = ensure_grid_buffers(ctx);
+  int rc = reserve_target_index(ctx);
   if (rc) return rc;
   rc = ensure_sort_buffers(ctx, nq > nt ? nq : nt);
   if (rc) return rc;
@@ -283,29 +288,27 @@ static int build_grid_and_order(icpk_ctx* ctx) {
     }
   }
   // bounds + geometry (+ the pending initial LoopState of the alignment being enqueued) in ONE launch
-  launch_grid_begin(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), nt, ctx->grid_bounds, ctx->tune.grid_ppc, ctx->tune.grid_xdiv,
-                    ctx->grid_max_cells, ctx->grid_info, ctx->init_pending ? &ctx->pending_init : nullptr, ctx->grid_ticket,
-                    ctx->stream);
+  GridIndex& g = ctx->grid;
+  launch_grid_begin(bounds_args(ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), nt, g.bounds),
+                    info_args(g.bounds, nt, ctx->tune.grid_ppc, ctx->tune.grid_xdiv, ctx->grid_max_cells, g.info),
+                    ctx->init_pending ? &ctx->pending_init : nullptr, ctx->grid_ticket, ctx->stream);
   ctx->init_pending = false;
   ctx->qcount_dirty = ctx->qcount2_dirty = true;
   SetupBatchOf<QslotArgs> qb{};
-  qb.p[0] = QslotArgs{ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), ctx->grid_info, ctx->qcount, tcell, tslot, nt, 0};
-  qb.p[1] = QslotArgs{ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->grid_info, ctx->qcount2, qcell, qslot, nq, 1};
+  qb.p[0] = QslotArgs{ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), g.info, ctx->qcount, tcell, tslot, nt, 0};
+  qb.p[1] = QslotArgs{ctx->src.x(), ctx->src.y(), ctx->src.z(), g.info, ctx->qcount2, qcell, qslot, nq, 1};
   // A source that icpk_backproject_pair has just made is in row-major IMAGE order: eight consecutive points are a short
   // run of one image row, as close together as a grid cell's -- the queries are swept in the caller's order and their
   // counting sort is left out (-3.5 us per 92k-point pair, -14 us at 306k; ICPK_IMAGE_ORDER=0: sort them all the same).
   const bool ident = ctx->have_pix_seed && ctx->tune.image_order;
   launch_grid_qslot_batch(qb, ident ? 1 : 2, ctx->stream);
   SetupBatchOf<ScanArgs> sb{};
-  sb.p[0] = ScanArgs{ctx->qcount, ctx->cell_start, ctx->scan_bsum, ctx->grid_info, 0, 0};
-  sb.p[1] = ScanArgs{ctx->qcount2, ctx->qstart, ctx->scan_bsum2, ctx->grid_info, 1, 0};
+  sb.p[0] = ScanArgs{ctx->qcount, g.cell_start, ctx->scan_bsum, g.info, 0, 0};
+  sb.p[1] = ScanArgs{ctx->qcount2, ctx->qstart, ctx->scan_bsum2, g.info, 1, 0};
   launch_grid_scan_batch(sb, ident ? 1 : 2, ctx->stream);
-  const TscatterArgs ta{ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), tcell, tslot, ctx->cell_start, ctx->t4, ctx->o4, nt, 0};
+  const TscatterArgs ta{ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), tcell, tslot, g.cell_start, g.t4, g.o4, nt, 0};
   const bool pix = ctx->have_pix_seed && ctx->tune.pixel_seeds;
-  const QscatterArgs qa{ident ? nullptr : qcell,        qslot,        ctx->qstart,  ctx->qperm,   ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->tgt.x(),
-                        ctx->tgt.y(), ctx->tgt.z(), ctx->qm4,     ctx->sp_in,   ctx->seed_m,  nq,           0,
-                        pix ? ctx->pix_src : nullptr, pix ? ctx->pix_tidx : nullptr, ctx->pix_rows, ctx->pix_cols};
-  launch_grid_tqscatter(ta, qa, ctx->stream);
+  launch_grid_tqscatter(ta, query_scatter_args(ctx, ident ? nullptr : qcell, qslot, ctx->qm4, pix), ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
   ctx->qcount_dirty = ctx->qcount2_dirty = false;
   ctx->have_grid = true;
@@ -347,7 +350,7 @@ int prepare_sorted_sweep(icpk_ctx* ctx, int nn_mode, NnArgs& a, NnBoxes& bx, int
       rc = ensure_query_points(ctx, nq);
       if (!rc) rc = build_grid_and_order(ctx);
     } else {
-      if (!rc) rc = prepare_grid_target(ctx);
+      if (!rc) rc = index_target(ctx, nullptr);
       if (!rc) rc = ensure_query_points(ctx, nq);
     }
   } else {
@@ -425,9 +428,9 @@ GridSweepArgs grid_sweep_args(icpk_ctx* ctx, const NnArgs& a, const NnBoxes& bx)
   g.qz = const_cast<float*>(a.qz);
   g.nq = a.nq;
   g.qm4 = ctx->qm4;
-  g.t4 = ctx->t4;
-  g.cell_start = ctx->cell_start;
-  g.gi = ctx->grid_info;
+  g.t4 = ctx->grid.t4;
+  g.cell_start = ctx->grid.cell_start;
+  g.gi = ctx->grid.info;
   g.ox = bx.ox;
   g.oy = bx.oy;
   g.oz = bx.oz;
@@ -598,7 +601,7 @@ static PairArgs reduce_args(icpk_ctx* ctx, float max_dist) {
   a.best = ctx->best;
   a.ax = ctx->src.x(), a.ay = ctx->src.y(), a.az = ctx->src.z();
   a.tx = ctx->tgt.x(), a.ty = ctx->tgt.y(), a.tz = ctx->tgt.z();
-  a.o4 = ctx->have_grid ? ctx->o4.get() : nullptr;
+  a.o4 = ctx->have_grid ? ctx->grid.o4.get() : nullptr;
   a.rec = loop_rec(ctx);
   a.nq = ctx->src.n;
   a.max_dist = max_dist;
@@ -695,29 +698,33 @@ static bool same_sequences(const SetupRecorder* recs, int count) {
   return true;
 }
 
+// THE table of the set-up steps: kind, the union's member, its type, the single launch, the batch launch
+#define ICPK_SETUP_STEPS(X)                                                                   \
+  X(SK_INGEST, ingest, IngestArgs, launch_ingest_cloud, launch_ingest_batch)                  \
+  X(SK_LOOP_INIT, loop_init, LoopInitArgs, launch_loop_init, launch_loop_init_batch)          \
+  X(SK_BOUNDS, bounds, BoundsArgs, launch_grid_bounds, launch_grid_bounds_batch)              \
+  X(SK_INFO, info, InfoArgs, launch_grid_info, launch_grid_info_batch)                        \
+  X(SK_QSLOT, qslot, QslotArgs, launch_grid_qslot, launch_grid_qslot_batch)                   \
+  X(SK_SCAN, scan, ScanArgs, launch_grid_scan, launch_grid_scan_batch)                        \
+  X(SK_TSCATTER, tscatter, TscatterArgs, launch_grid_tscatter, launch_grid_tscatter_batch)    \
+  X(SK_QSCATTER, qscatter, QscatterArgs, launch_grid_qscatter, launch_grid_qscatter_batch)
+
 bool flush_setup_batches(const SetupRecorder* recs, int count, hipStream_t s) {
   if (count <= 0) return true;
   if (count > BATCH_MAX || !same_sequences(recs, count)) return false;
   for (int j = 0; j < recs[0].n; ++j) {
-#define ICPK_STEP(KIND, FIELD, TYPE, LAUNCH)                        \
+#define ICPK_BATCH_STEP(KIND, FIELD, TYPE, LAUNCH, BATCH)            \
   case KIND: {                                                      \
     SetupBatchOf<TYPE> b;                                           \
     for (int k = 0; k < count; ++k) b.p[k] = recs[k].calls[j].FIELD; \
-    LAUNCH(b, count, s);                                            \
+    BATCH(b, count, s);                                             \
     break;                                                          \
   }
     switch (recs[0].calls[j].kind) {
-      ICPK_STEP(SK_INGEST, ingest, IngestArgs, launch_ingest_batch)
-      ICPK_STEP(SK_LOOP_INIT, loop_init, LoopInitArgs, launch_loop_init_batch)
-      ICPK_STEP(SK_BOUNDS, bounds, BoundsArgs, launch_grid_bounds_batch)
-      ICPK_STEP(SK_INFO, info, InfoArgs, launch_grid_info_batch)
-      ICPK_STEP(SK_QSLOT, qslot, QslotArgs, launch_grid_qslot_batch)
-      ICPK_STEP(SK_SCAN, scan, ScanArgs, launch_grid_scan_batch)
-      ICPK_STEP(SK_TSCATTER, tscatter, TscatterArgs, launch_grid_tscatter_batch)
-      ICPK_STEP(SK_QSCATTER, qscatter, QscatterArgs, launch_grid_qscatter_batch)
+      ICPK_SETUP_STEPS(ICPK_BATCH_STEP)
       default: return false;
     }
-#undef ICPK_STEP
+#undef ICPK_BATCH_STEP
   }
   return true;
 }
@@ -725,40 +732,20 @@ bool flush_setup_batches(const SetupRecorder* recs, int count, hipStream_t s) {
 // one pair's recorded steps, launched one by one (the sequences of a group differed)
 void replay_setup(const SetupRecorder& rec, hipStream_t s) {
   SetupRecorder* const saved = setup_recorder();
-  setup_recorder() = nullptr;
+  setup_recorder() = nullptr;  // (the launchers launch)
   for (int j = 0; j < rec.n; ++j) {
     const SetupCall& c = rec.calls[j];
+#define ICPK_REPLAY_STEP(KIND, FIELD, TYPE, LAUNCH, BATCH) \
+  case KIND: LAUNCH(c.FIELD, s); break;
     switch (c.kind) {
-      case SK_INGEST: {
-        const IngestArgs& a = c.ingest;
-        launch_ingest_cloud(a.x, a.y, a.z, a.n, a.n_pad, a.pad, a.d1, a.cap1, a.d2, a.cap2, s);
-        break;
-      }
-      case SK_LOOP_INIT: launch_loop_init(c.loop_init, s); break;
-      case SK_BOUNDS: launch_grid_bounds(c.bounds.x, c.bounds.y, c.bounds.z, c.bounds.n, c.bounds.fb, s); break;
-      case SK_INFO: launch_grid_info(c.info.fb, c.info.n, c.info.ppc, c.info.xdiv, c.info.max_cells, c.info.g, s); break;
-      case SK_QSLOT: {
-        const QslotArgs& a = c.qslot;
-        launch_grid_qslot(a.x, a.y, a.z, a.n, a.gi, a.count, a.cell, a.slot, a.coarse, s);
-        break;
-      }
-      case SK_SCAN: launch_grid_scan(c.scan.count, c.scan.out, c.scan.bsum, c.scan.g, c.scan.coarse, s); break;
-      case SK_TSCATTER: {
-        const TscatterArgs& a = c.tscatter;
-        launch_grid_tscatter(a.x, a.y, a.z, a.tcell, a.tslot, a.cell_start, a.n, a.t4, a.o4, s);
-        break;
-      }
-      case SK_QSCATTER: {
-        const QscatterArgs& a = c.qscatter;
-        launch_grid_qscatter(a.qcell, a.qslot, a.qstart, a.n, a.qperm, a.qx, a.qy, a.qz, a.ox, a.oy, a.oz, a.qm4, a.sp,
-                             a.seed_m, s);
-        break;
-      }
+      ICPK_SETUP_STEPS(ICPK_REPLAY_STEP)
       default: break;
     }
+#undef ICPK_REPLAY_STEP
   }
   setup_recorder() = saved;
 }
+#undef ICPK_SETUP_STEPS
 }  // namespace icpk
 
 // icpk_reduce / icpk_reduce_p2l: K2 / K5 over the current associations, sums and pair count back to the host

@@ -45,9 +45,9 @@ __global__ __launch_bounds__(CG_BLOCK) void color_gradient_sums_kernel(const Col
   const int slice = threadIdx.x & (CG_S - 1);
   const int ip = (int)((blockIdx.x * (unsigned)CG_BLOCK + threadIdx.x) / CG_S);  // position in cell order
   const bool live = ip < a.n;
-  const float4 p4 = live ? a.t4[ip] : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 p4 = live ? a.index.t4[ip] : make_float4(0.f, 0.f, 0.f, 0.f);
   const int orig = live ? min(max(__float_as_int(p4.w), 0), a.n - 1) : 0;
-  const GridInfo g = *a.gi;
+  const GridInfo g = *a.index.gi;
   const float px = p4.x, py = p4.y, pz = p4.z;
   const float r = a.radius;
   const double rd = (double)r, inv_r = 1.0 / rd;
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(CG_BLOCK) void color_gradient_sums_kernel(const Col
     float ic;
   };
   walk_candidates<CG_S, CG_UNROLL>(
-      walk, g, a.cell_start, slice, [&](int jj) { return Cand{a.t4[jj], a.col_sorted[jj]}; },
+      walk, g, a.index.cell_start, slice, [&](int jj) { return Cand{a.index.t4[jj], a.col_sorted[jj]}; },
       [&](const Cand& k, bool in_range) {
         const float4 c = k.c;
         const float d = pair_dist(px, py, pz, c.x, c.y, c.z);
@@ -189,7 +189,7 @@ void launch_color_gradients(const ColorGradArgs& a, hipStream_t s) {
   if (a.n <= 0) return;
   const unsigned point_blocks = (unsigned)((a.n + CG_BLOCK - 1) / CG_BLOCK);
   const unsigned lanes_blocks = (unsigned)(((size_t)a.n * CG_S + CG_BLOCK - 1) / CG_BLOCK);
-  hipLaunchKernelGGL(color_gather_kernel, dim3(point_blocks), dim3(CG_BLOCK), 0, s, a.t4, a.col, a.n, a.col_sorted);
+  hipLaunchKernelGGL(color_gather_kernel, dim3(point_blocks), dim3(CG_BLOCK), 0, s, a.index.t4, a.col, a.n, a.col_sorted);
   hipLaunchKernelGGL(color_gradient_sums_kernel, dim3(lanes_blocks), dim3(CG_BLOCK), 0, s, a);
   hipLaunchKernelGGL(color_gradient_solve_kernel, dim3(point_blocks), dim3(CG_BLOCK), 0, s, a);
 }

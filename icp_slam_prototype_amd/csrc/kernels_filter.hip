@@ -54,7 +54,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_mean_kernel(const KnnArgs a) {
   const bool live = iq < a.nq;
   const float4 p4 = live ? a.q4[iq] : make_float4(0.f, 0.f, 0.f, 0.f);
   const int self = __float_as_int(p4.w);
-  const GridInfo g = *a.gi;
+  const GridInfo g = *a.index.gi;
   const float px = p4.x, py = p4.y, pz = p4.z;
   const int k = a.k;  // <= KCAP (launch_knn_mean)
   // a non-finite query has no neighbours (and its cube would be the whole grid)
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_mean_kernel(const KnnArgs a) {
     int max_at = 0;
     if (active) cnt = 0;
     walk_candidates<KNN_S, KNN_UNROLL>(
-        walk, g, a.cell_start, slice, [&](int jj) { return a.t4[jj]; },
+        walk, g, a.index.cell_start, slice, [&](int jj) { return a.index.t4[jj]; },
         [&](const float4 c, bool in_range) {
           const float d = pair_dist(px, py, pz, c.x, c.y, c.z);
           const int cj = __float_as_int(c.w);
@@ -266,11 +266,11 @@ void launch_knn_mean(const KnnArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(knn_mean_kernel<64>, dim3(blocks), dim3(KNN_BLOCK), 0, s, a);
 }
 
-void launch_radius_count(const float4* t4, const int* cell_start, const GridInfo* gi, int n, float radius, double* value,
-                         hipStream_t s) {
+void launch_radius_count(const GridView& index, int n, float radius, double* value, hipStream_t s) {
   if (n <= 0) return;
   const unsigned blocks = (unsigned)(((size_t)n * RAD_S + RAD_BLOCK - 1) / RAD_BLOCK);
-  hipLaunchKernelGGL(radius_count_kernel, dim3(blocks), dim3(RAD_BLOCK), 0, s, t4, cell_start, gi, n, radius, value);
+  hipLaunchKernelGGL(radius_count_kernel, dim3(blocks), dim3(RAD_BLOCK), 0, s, index.t4, index.cell_start, index.gi, n,
+                     radius, value);
 }
 
 void launch_filter_compact(const FilterArgs& a, hipStream_t s) {

@@ -35,7 +35,7 @@ constexpr int FP_CNT = FPFH_BINS + 1;  // LDS words per point: the bins, then m
 __global__ __launch_bounds__(FP_BLOCK) void fpfh_prep_kernel(const FpfhArgs a) {
   const int ip = blockIdx.x * FP_BLOCK + threadIdx.x;
   if (ip >= a.n) return;
-  const float4 p = a.t4[ip];
+  const float4 p = a.index.t4[ip];
   const int i = __float_as_int(p.w);
   const float nx = a.nx[i], ny = a.ny[i], nz = a.nz[i];
   const bool described = finite3(p.x, p.y, p.z) && finite3(nx, ny, nz) && !(nx == 0.f && ny == 0.f && nz == 0.f);
@@ -100,9 +100,9 @@ __global__ __launch_bounds__(FP_BLOCK) void fpfh_spfh_kernel(const FpfhArgs a) {
   const int slice = threadIdx.x & (FP_S - 1), lp = threadIdx.x / FP_S;
   const int ip = (int)((blockIdx.x * (unsigned)FP_BLOCK + threadIdx.x) / FP_S);  // position in cell order
   const bool live = ip < a.n;
-  const float4 p4 = live ? a.t4[ip] : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 p4 = live ? a.index.t4[ip] : make_float4(0.f, 0.f, 0.f, 0.f);
   const float4 ni = live ? a.n4[ip] : make_float4(0.f, 0.f, 0.f, 0.f);
-  const GridInfo g = *a.gi;
+  const GridInfo g = *a.index.gi;
   const float px = p4.x, py = p4.y, pz = p4.z, r = a.radius;
   const bool scan = live && ni.w != 0.f;  // only a described point counts pairs (described: finite, so is its cube)
   const Walk w = make_walk(g, px, py, pz, r, scan);
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(FP_BLOCK) void fpfh_spfh_kernel(const FpfhArgs a) {
     float4 c, nj;
   };
   walk_candidates<FP_S, FP_UNROLL>(
-      w, g, a.cell_start, slice, [&](int jj) { return Cand{a.t4[jj], a.n4[jj]}; },
+      w, g, a.index.cell_start, slice, [&](int jj) { return Cand{a.index.t4[jj], a.n4[jj]}; },
       [&](const Cand& k, bool in_range) { spfh_pair(cnt[lp], px, py, pz, ni, k.c, k.nj, in_range, r); });
   __syncthreads();
   if (!live) return;
@@ -130,10 +130,10 @@ __global__ __launch_bounds__(FP_BLOCK) void fpfh_final_kernel(const FpfhArgs a) 
   const int slice = threadIdx.x & (FP_S - 1);
   const int ip = (int)((blockIdx.x * (unsigned)FP_BLOCK + threadIdx.x) / FP_S);
   const bool live = ip < a.n;
-  const float4 p4 = live ? a.t4[ip] : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 p4 = live ? a.index.t4[ip] : make_float4(0.f, 0.f, 0.f, 0.f);
   const unsigned* const gi32 = reinterpret_cast<const unsigned*>(a.g + (size_t)(live ? ip : 0) * FPFH_G_STRIDE);
   const bool valid = live && a.n > 0 && (gi32[FPFH_BINS / 2] >> 16) != 0;  // described and m > 0
-  const GridInfo g = *a.gi;
+  const GridInfo g = *a.index.gi;
   const float px = p4.x, py = p4.y, pz = p4.z, r = a.radius;
   const double rr = (double)r * (double)r;
   // the rule walks for every described i; a described point with m_i == 0 gets 33 zeros whatever its walk finds, so
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(FP_BLOCK) void fpfh_final_kernel(const FpfhArgs a) 
     int j;
   };
   walk_candidates<FP_S, 1>(
-      w, g, a.cell_start, slice, [&](int j) { return Cand{a.t4[j], j}; },
+      w, g, a.index.cell_start, slice, [&](int j) { return Cand{a.index.t4[j], j}; },
       [&](const Cand& k, bool) {
         const float d = pair_dist(px, py, pz, k.c.x, k.c.y, k.c.z);
         if (!(d > 0.f && d <= r)) return;

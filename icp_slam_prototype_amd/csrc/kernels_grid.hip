@@ -360,20 +360,8 @@ __global__ __launch_bounds__(256) void grid_scan_apply_batch_kernel(const SetupB
 
 // coarse = 1: the table of the query order (ncells_q entries), else the targets' (ncells).
 // out[i] = sum of count[0 .. i) for i in [0, size]; count[] is zero afterwards; bsum: GRID_SCAN_BLOCKS ints
-#define ICPK_RECORD(KIND, FIELD, VALUE)           \
-  if (SetupRecorder* r__ = setup_recorder()) {    \
-    if (r__->n < SETUP_MAX_CALLS) {                            \
-      r__->calls[r__->n].kind = KIND;             \
-      r__->calls[r__->n++].FIELD = VALUE;         \
-    } else {                                      \
-      r__->overflow = true;                       \
-    }                                             \
-    return;                                       \
-  }
-
-void launch_grid_scan(int* count, int* out, int* bsum, const GridInfo* g, int coarse, hipStream_t s) {
-  const ScanArgs a{count, out, bsum, g, coarse, 0};
-  ICPK_RECORD(SK_SCAN, scan, a)
+void launch_grid_scan(const ScanArgs& a, hipStream_t s) {
+  if (record_setup_step(SK_SCAN, &SetupCall::scan, a)) return;
   hipLaunchKernelGGL(grid_scan_sums_kernel, dim3(GSCAN_LAUNCH_BLOCKS), dim3(256), 0, s, a);
   hipLaunchKernelGGL(grid_scan_apply_kernel, dim3(GSCAN_LAUNCH_BLOCKS), dim3(256), 0, s, a);
 }
@@ -402,37 +390,26 @@ static int max_n(const SetupBatchOf<A>& b, int count) {
   return m;
 }
 
-void launch_grid_tscatter(const float* x, const float* y, const float* z, const int* tcell, const int* tslot,
-                          const int* cell_start, int n, float4* t4, float4* o4, hipStream_t s) {
-  if (n <= 0) return;
-  const TscatterArgs a{x, y, z, tcell, tslot, cell_start, t4, o4, n, 0};
-  ICPK_RECORD(SK_TSCATTER, tscatter, a)
-  hipLaunchKernelGGL(grid_tscatter_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
+void launch_grid_tscatter(const TscatterArgs& a, hipStream_t s) {
+  if (a.n <= 0 || record_setup_step(SK_TSCATTER, &SetupCall::tscatter, a)) return;
+  hipLaunchKernelGGL(grid_tscatter_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
 }
 void launch_grid_tscatter_batch(const SetupBatchOf<TscatterArgs>& b, int count, hipStream_t s) {
   const int m = max_n(b, count);
   if (count > 0 && m > 0) hipLaunchKernelGGL(grid_tscatter_batch_kernel, dim3((m + 255) / 256, count), dim3(256), 0, s, b);
 }
 
-void launch_grid_qslot(const float* x, const float* y, const float* z, int n, const GridInfo* g, int* count, int* qcell,
-                       int* qslot, int coarse, hipStream_t s) {
-  if (n <= 0) return;
-  const QslotArgs a{x, y, z, g, count, qcell, qslot, n, coarse};
-  ICPK_RECORD(SK_QSLOT, qslot, a)
-  hipLaunchKernelGGL(grid_qslot_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
+void launch_grid_qslot(const QslotArgs& a, hipStream_t s) {
+  if (a.n <= 0 || record_setup_step(SK_QSLOT, &SetupCall::qslot, a)) return;
+  hipLaunchKernelGGL(grid_qslot_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
 }
 void launch_grid_qslot_batch(const SetupBatchOf<QslotArgs>& b, int count, hipStream_t s) {
   const int m = max_n(b, count);
   if (count > 0 && m > 0) hipLaunchKernelGGL(grid_qslot_batch_kernel, dim3((m + 255) / 256, count), dim3(256), 0, s, b);
 }
-void launch_grid_qscatter(const int* qcell, const int* qslot, const int* qstart, int n, int* qperm, const float* qx,
-                          const float* qy, const float* qz, const float* ox, const float* oy, const float* oz,
-                          float4* qm4, float4* sp, nn_key_t* seed_m, hipStream_t s, const int* spix, const int* tidx,
-                          int rows, int cols) {
-  if (n <= 0) return;
-  const QscatterArgs a{qcell, qslot, qstart, qperm, qx, qy, qz, ox, oy, oz, qm4, sp, seed_m, n, 0, spix, tidx, rows, cols};
-  ICPK_RECORD(SK_QSCATTER, qscatter, a)
-  hipLaunchKernelGGL(grid_qscatter_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
+void launch_grid_qscatter(const QscatterArgs& a, hipStream_t s) {
+  if (a.n <= 0 || record_setup_step(SK_QSCATTER, &SetupCall::qscatter, a)) return;
+  hipLaunchKernelGGL(grid_qscatter_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
 }
 void launch_grid_qscatter_batch(const SetupBatchOf<QscatterArgs>& b, int count, hipStream_t s) {
   const int m = max_n(b, count);
@@ -451,13 +428,8 @@ void launch_grid_tqscatter(const TscatterArgs& t, const QscatterArgs& q, hipStre
   if (m > 0) hipLaunchKernelGGL(grid_tqscatter_kernel, dim3((m + 255) / 256, 2), dim3(256), 0, s, t, q);
 }
 
-int grid_bounds_parts(int n) {  // one 1024-thread block per 2048 points, at most GRID_BOUNDS_PARTS
-  int nb = (n + 2047) / 2048;
-  return nb < 1 ? 1 : (nb > GRID_BOUNDS_PARTS ? GRID_BOUNDS_PARTS : nb);
-}
-void launch_grid_bounds(const float* x, const float* y, const float* z, int n, float* fb, hipStream_t s) {
-  const BoundsArgs a{x, y, z, fb, n, grid_bounds_parts(n)};
-  ICPK_RECORD(SK_BOUNDS, bounds, a)
+void launch_grid_bounds(const BoundsArgs& a, hipStream_t s) {
+  if (record_setup_step(SK_BOUNDS, &SetupCall::bounds, a)) return;
   hipLaunchKernelGGL(grid_bounds_kernel, dim3(a.nparts), dim3(1024), 0, s, a);
 }
 void launch_grid_bounds_batch(const SetupBatchOf<BoundsArgs>& b, int count, hipStream_t s) {
@@ -465,22 +437,17 @@ void launch_grid_bounds_batch(const SetupBatchOf<BoundsArgs>& b, int count, hipS
   for (int k = 0; k < count; ++k) m = b.p[k].nparts > m ? b.p[k].nparts : m;
   if (count > 0 && m > 0) hipLaunchKernelGGL(grid_bounds_batch_kernel, dim3(m, count), dim3(1024), 0, s, b);
 }
-void launch_grid_begin(const float* x, const float* y, const float* z, int n, float* fb, float ppc, int xdiv, int max_cells,
-                       GridInfo* g, const LoopInitArgs* init, int* ticket, hipStream_t s) {
-  const BoundsArgs a{x, y, z, fb, n, grid_bounds_parts(n)};
-  const InfoArgs info{fb, g, a.nparts, n, ppc, xdiv < 1 ? 1 : xdiv, max_cells < 64 ? 64 : max_cells, 0};
+void launch_grid_begin(const BoundsArgs& a, const InfoArgs& info, const LoopInitArgs* init, int* ticket, hipStream_t s) {
   hipLaunchKernelGGL(grid_begin_kernel, dim3(a.nparts), dim3(1024), 0, s, a, info, init ? *init : LoopInitArgs{}, init ? 1 : 0,
                      ticket);
 }
-void launch_grid_info(const float* fb, int n, float ppc, int xdiv, int max_cells, GridInfo* g, hipStream_t s) {
-  const InfoArgs a{fb, g, grid_bounds_parts(n), n, ppc, xdiv < 1 ? 1 : xdiv, max_cells < 64 ? 64 : max_cells, 0};
-  ICPK_RECORD(SK_INFO, info, a)
+void launch_grid_info(const InfoArgs& a, hipStream_t s) {
+  if (record_setup_step(SK_INFO, &SetupCall::info, a)) return;
   hipLaunchKernelGGL(grid_info_kernel, dim3(1), dim3(64), 0, s, a);
 }
 void launch_grid_info_batch(const SetupBatchOf<InfoArgs>& b, int count, hipStream_t s) {
   if (count > 0) hipLaunchKernelGGL(grid_info_batch_kernel, dim3(count), dim3(64), 0, s, b);
 }
-#undef ICPK_RECORD
 
 // ---- the sweep --------------------------------------------------------------------------
 // Cells met by the cube [q - rr, q + rr], rr slightly above the current best distance r.

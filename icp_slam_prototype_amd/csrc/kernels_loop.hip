@@ -313,15 +313,7 @@ __global__ __launch_bounds__(64) void loop_init_kernel(const LoopInitArgs a) { l
 __global__ __launch_bounds__(64) void loop_init_batch_kernel(const SetupBatchOf<LoopInitArgs> b) { loop_init_body(b.p[blockIdx.x]); }
 
 void launch_loop_init(const LoopInitArgs& a, hipStream_t s) {
-  if (SetupRecorder* r = setup_recorder()) {
-    if (r->n < SETUP_MAX_CALLS) {
-      r->calls[r->n].kind = SK_LOOP_INIT;
-      r->calls[r->n++].loop_init = a;
-    } else {
-      r->overflow = true;
-    }
-    return;
-  }
+  if (record_setup_step(SK_LOOP_INIT, &SetupCall::loop_init, a)) return;
   hipLaunchKernelGGL(loop_init_kernel, dim3(1), dim3(64), 0, s, a);
 }
 void launch_loop_init_batch(const SetupBatchOf<LoopInitArgs>& b, int count, hipStream_t s) {

@@ -55,8 +55,8 @@ __global__ __launch_bounds__(NRM_BLOCK) void normals_moments_kernel(const Normal
   const int slice = threadIdx.x & (NRM_S - 1);
   const int ip = (int)((blockIdx.x * (unsigned)NRM_BLOCK + threadIdx.x) / NRM_S);  // position in cell order
   const bool live = ip < a.n;
-  const float4 p4 = live ? a.t4[ip] : make_float4(0.f, 0.f, 0.f, 0.f);
-  const GridInfo g = *a.gi;
+  const float4 p4 = live ? a.index.t4[ip] : make_float4(0.f, 0.f, 0.f, 0.f);
+  const GridInfo g = *a.index.gi;
   const float px = p4.x, py = p4.y, pz = p4.z;
   const float r = a.radius;
   const double rd = (double)r, inv_r = 1.0 / rd;
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(NRM_BLOCK) void normals_moments_kernel(const Normal
   const Walk walk = make_walk(g, px, py, pz, r, scan);
   Moments M{};
   walk_candidates<NRM_S, NRM_UNROLL>(
-      walk, g, a.cell_start, slice, [&](int jj) { return a.t4[jj]; },
+      walk, g, a.index.cell_start, slice, [&](int jj) { return a.index.t4[jj]; },
       [&](const float4 c, bool in_range) { accumulate(M, px, py, pz, c, in_range, r, rd, inv_r); });
   long long w[NRM_MOMENTS] = {M.m, M.sx, M.sy, M.sz, M.sxx, M.sxy, M.sxz, M.syy, M.syz, M.szz};
 #pragma unroll

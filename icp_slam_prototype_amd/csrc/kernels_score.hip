@@ -67,7 +67,7 @@ __global__ __launch_bounds__(SC_BLOCK) void score_search_kernel(const ScoreArgs 
     py = rot_row(T[4], T[5], T[6], sx, sy, sz) + T[7];
     pz = rot_row(T[8], T[9], T[10], sx, sy, sz) + T[11];
   }
-  const GridInfo g = *a.gi;
+  const GridInfo g = *a.index.gi;
   const float max_dist = a.max_dist;
   // a non-finite point never pairs (and its cube would be the whole grid)
   bool active = live && finite3(px, py, pz);
@@ -83,12 +83,12 @@ __global__ __launch_bounds__(SC_BLOCK) void score_search_kernel(const ScoreArgs 
     for (int row = slice; row < w.nrows; row += SC_S) {
       const int rz = row / w.nyr, ry = row - rz * w.nyr;
       const int base = ((w.z0 + rz) * g.ny + (w.y0 + ry)) * g.nx;  // cells base + x0 .. base + x1 < ncells, one range
-      const int s0 = a.cell_start[base + w.x0], s1 = a.cell_start[base + w.x1 + 1];  // s1 <= the target's size
+      const int s0 = a.index.cell_start[base + w.x0], s1 = a.index.cell_start[base + w.x1 + 1];  // s1 <= the target's size
       SCORE_COUNT(0, s1 - s0);
       for (int j = s0; j < s1; j += SC_UNROLL) {
         float4 c[SC_UNROLL];
 #pragma unroll
-        for (int u = 0; u < SC_UNROLL; ++u) c[u] = a.t4[min(j + u, s1 - 1)];
+        for (int u = 0; u < SC_UNROLL; ++u) c[u] = a.index.t4[min(j + u, s1 - 1)];
 #pragma unroll
         for (int u = 0; u < SC_UNROLL; ++u) {
           const float d = pair_dist(px, py, pz, c[u].x, c[u].y, c[u].z);

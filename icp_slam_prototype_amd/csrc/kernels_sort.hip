@@ -107,7 +107,7 @@ void launch_morton_order(const float* x, const float* y, const float* z, int n, 
   if (n <= 0) return;
   hipLaunchKernelGGL(morton_table_kernel, dim3(1), dim3(64), 0, s, table, bits);
   hipLaunchKernelGGL(morton_slot_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, y, z, n, bounds, bits, keys, slot, count);
-  launch_grid_scan(count, start, bsum, table, 0, s);
+  launch_grid_scan(ScanArgs{count, start, bsum, table, 0, 0}, s);
   hipLaunchKernelGGL(morton_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, s, keys, slot, start, n, keys_out, perm_out);
 }
 

@@ -83,20 +83,9 @@ static inline int ingest_blocks(int n_pad) {
   return blocks > 2048 ? 2048 : blocks;
 }
 
-void launch_ingest_cloud(const float* x, const float* y, const float* z, int n, int n_pad, float pad, float* d1, int cap1,
-                         float* d2, int cap2, hipStream_t s) {
-  if (n_pad <= 0) return;
-  IngestArgs a{x, y, z, n, n_pad, pad, cap1, d1, d2, cap2, 0};
-  if (SetupRecorder* r = setup_recorder()) {
-    if (r->n < SETUP_MAX_CALLS) {
-      r->calls[r->n].kind = SK_INGEST;
-      r->calls[r->n++].ingest = a;
-    } else {
-      r->overflow = true;
-    }
-    return;
-  }
-  hipLaunchKernelGGL(ingest_cloud_kernel, dim3(ingest_blocks(n_pad)), dim3(256), 0, s, a);
+void launch_ingest_cloud(const IngestArgs& a, hipStream_t s) {
+  if (a.n_pad <= 0 || record_setup_step(SK_INGEST, &SetupCall::ingest, a)) return;
+  hipLaunchKernelGGL(ingest_cloud_kernel, dim3(ingest_blocks(a.n_pad)), dim3(256), 0, s, a);
 }
 
 void launch_ingest_batch(const SetupBatchOf<IngestArgs>& b, int count, hipStream_t s) {

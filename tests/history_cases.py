@@ -36,6 +36,9 @@ icpk_score_poses refuses more than SCORE_MAX_POSES poses per call (ICPK_E_ARG), 
 SCORE_MAX_POSES, the refusal is part of `early_refusals`, and the chunking beyond SCORE_MAX_POSES is crossed by the
 FPFH probe's register_global (more valid hypotheses than one chunk).
 
+Shared-state histories (SHARED): `shared_aux_index` leaves the index that the source normals (K14), the source's
+descriptors (K16) and the filter of the working source (K13) build in turn as the last of them built it on Q.
+
 COVERAGE maps every public name of binding.Context to the probes and histories that call it, or to EXEMPT with a
 reason; tests/test_history_host.py holds it against the class."""
 import functools
@@ -1024,11 +1027,26 @@ EARLY = {
     "early_one_rank_communicator": early_one_rank_communicator,
 }
 
+def shared_aux_index(ctx):
+    """the context's one index of "any other cloud" (csrc/icpk_ctx.h: aux_grid) as its OTHER user left it: on Q the
+    source normals index the uploaded source, then the filter's statistics index the working source -- the last call
+    that builds an index.  The probes on P then find that index holding a larger cloud with another bounding box."""
+    s = scene("Q")
+    settings(ctx)
+    clouds(ctx, s)
+    ctx.estimate_source_normals(radius(s), 5, viewpoint=s["viewpoint"])
+    ctx.remove_outliers(0, stats_only=True, **filter_kw(s, FILTERS[0][1]))
+
+
+# histories that hand a piece of state two features share from one to the other
+SHARED = {"shared_aux_index": shared_aux_index}
+
 HISTORIES = {}
 for _s in ("Q", "S"):
     for _p in PROBE_ORDER:
         HISTORIES[f"{_s}.{_p}"] = make_scene_history(_s, _p)
 HISTORIES.update(EARLY)
+HISTORIES.update(SHARED)
 
 
 # ------------------------------------------------------------------------------------------------------ models --
@@ -1314,8 +1332,8 @@ COVERAGE = {
     "set_robust": PROBE_ORDER, "get_robust_trace": ("align_robust",), "reduce_weighted": ("align_robust",),
     "voxel_downsample": ("voxel",), "get_voxel_groups": ("voxel",),
     "estimate_target_normals": ("normals", "align_point_to_plane", "fpfh"), "get_normal_stats": ("normals",),
-    "remove_outliers": ("filter", "early_filter_leaves_nothing"), "outlier_stats": ("filter",),
-    "estimate_source_normals": ("normals", "align_plane_to_plane", "fpfh"), "set_source_normals": ("normals",),
+    "remove_outliers": ("filter", "early_filter_leaves_nothing", "shared_aux_index"), "outlier_stats": ("filter",),
+    "estimate_source_normals": ("normals", "align_plane_to_plane", "fpfh", "shared_aux_index"), "set_source_normals": ("normals",),
     "get_source_normals": ("normals",), "set_plane_to_plane": PROBE_ORDER,
     "reduce_plane_to_plane": ("align_plane_to_plane",),
     "set_target_colors": ("color", "align_colored"), "set_source_colors": ("color", "align_colored"),

@@ -60,7 +60,7 @@ def source_of(user):
 
     helpers = {k: v for k, v in vars(hc).items() if inspect.isfunction(v) and v.__module__ == hc.__name__}
     helpers["RcclComm"] = batch.RcclComm
-    fn = hc.PROBES.get(user) or hc.EARLY[user]
+    fn = hc.PROBES.get(user) or hc.EARLY.get(user) or hc.SHARED[user]
     text = inspect.getsource(fn)
     if user in hc.PROBES and fn.__name__ == "probe":  # (made by make_nn_probe / make_align_probe: the enclosing maker)
         text = inspect.getsource(hc.make_nn_probe if user.startswith("nn_") else hc.make_align_probe)
@@ -79,7 +79,7 @@ def source_of(user):
 def test_every_entry_names_probes_or_histories_that_exist_and_call_it():
     import re
 
-    known = set(hc.PROBES) | set(hc.EARLY)
+    known = set(hc.PROBES) | set(hc.EARLY) | set(hc.SHARED)
     source = {u: source_of(u) for u in known}
     for name, users in hc.COVERAGE.items():
         if isinstance(users, hc.Exempt):
@@ -95,8 +95,8 @@ def test_every_entry_names_probes_or_histories_that_exist_and_call_it():
 
 
 def test_histories_are_every_probe_on_q_and_s_and_the_early_paths():
-    assert set(hc.HISTORIES) == {f"{s}.{p}" for s in "QS" for p in hc.PROBES} | set(hc.EARLY)
-    assert len(hc.PROBES) == 22 and len(hc.EARLY) == 12
+    assert set(hc.HISTORIES) == {f"{s}.{p}" for s in "QS" for p in hc.PROBES} | set(hc.EARLY) | set(hc.SHARED)
+    assert len(hc.PROBES) == 22 and len(hc.EARLY) == 12 and len(hc.SHARED) == 1
     assert set(hc.CHAIN_PROBES) == set(hc.PROBES) - {"tsdf", "map", "frontend", "batch", "posegraph"}
     assert set(hc.MODELS) == set(hc.PROBES) - {"batch"}
 
