@@ -88,6 +88,7 @@ SYMBOLS = [
     "icpk_default_tsdf_raycast_params", "icpk_tsdf_raycast", "icpk_tsdf_get_raycast", "icpk_tsdf_raycast_to_target",
     "icpk_tsdf_raycast_pixels",
     "icpk_tsdf_extract_mesh", "icpk_tsdf_get_mesh", "icpk_tsdf_set", "icpk_tsdf_mesh_host",
+    "icpk_tsdf_shift", "icpk_tsdf_extract_leaving", "icpk_tsdf_get_params", "icpk_tsdf_get_box",
     "icpk_default_bilateral_params", "icpk_bilateral_depth_image", "icpk_backproject_smoothed", "icpk_bilateral_tables",
     "icpk_bilateral_host",
 ]
@@ -434,6 +435,10 @@ def load():
     lib.icpk_tsdf_set.argtypes = [C.c_void_p, fp, u16, fp]
     lib.icpk_tsdf_mesh_host.argtypes = [C.POINTER(TsdfParams), C.c_int32, fp, u16, fp, C.c_int64, C.c_int64, fp, fp, fp,
                                         fp, fp, fp, fp, ip, u8, ip, C.POINTER(C.c_int64)]
+    lib.icpk_tsdf_shift.argtypes = [C.c_void_p, ip]
+    lib.icpk_tsdf_extract_leaving.argtypes = [C.c_void_p, C.c_int32, ip, ip, ip]
+    lib.icpk_tsdf_get_params.argtypes = [C.c_void_p, C.POINTER(TsdfParams), C.POINTER(C.c_int64)]
+    lib.icpk_tsdf_get_box.argtypes = [C.c_void_p, ip, ip, fp, u16, fp]
     bp = C.POINTER(BilateralParams)
     lib.icpk_default_bilateral_params.argtypes = [bp]
     lib.icpk_default_bilateral_params.restype = None
@@ -762,6 +767,57 @@ def global_hypotheses(matches, src, tgt, seed, edge_similarity=0.9, h0=0, count=
     if rc < 0:
         raise IcpkError(rc, "icpk_global_hypotheses")
     return samples[:count], valid[:count].astype(bool), T[:count].reshape(count, 4, 4)
+
+
+# -- the moving volume (K23): functions over a Context, which gains no name ------------------------------------------
+def _i3(v, what):
+    a = np.ascontiguousarray(v, np.int32).reshape(-1)
+    if a.size != 3:
+        raise ValueError(f"{what}: three integers expected")
+    return a
+
+
+def tsdf_shift(ctx, s):
+    """icpk_tsdf_shift: the context's volume moved by s = (s_x, s_y, s_z) whole voxels -- the new voxel v holds the old
+    voxel v + s, or nothing.  Drops the surface list, the ray-cast maps and the mesh (s = 0: a no-op).  No host wait."""
+    s = _i3(s, "s")
+    ctx._chk(ctx._lib.icpk_tsdf_shift(ctx._h, s.ctypes.data_as(C.POINTER(C.c_int32))))
+    if s.any():
+        ctx._tsdf_n = ctx._tsdf_ray = ctx._tsdf_mesh = None
+
+
+def tsdf_extract_leaving(ctx, s, min_weight=1):
+    """icpk_tsdf_extract_leaving: the surface list restricted to the crossings a shift by s would lose; it replaces the
+    surface list (Context.tsdf_get_surface, tsdf_surface_to_target).  Returns (n_points, n_no_normal)."""
+    s = _i3(s, "s")
+    n, m = C.c_int32(-1), C.c_int32(-1)
+    ctx._chk(ctx._lib.icpk_tsdf_extract_leaving(ctx._h, int(min_weight), s.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                C.byref(n), C.byref(m)))
+    ctx._tsdf_n = n.value
+    return n.value, m.value
+
+
+def tsdf_get_params(ctx):
+    """icpk_tsdf_get_params: (TsdfParams with the current origin, total (3,) int64: the cumulative shift)."""
+    p, total = TsdfParams(), np.zeros(3, np.int64)
+    ctx._chk(ctx._lib.icpk_tsdf_get_params(ctx._h, C.byref(p), total.ctypes.data_as(C.POINTER(C.c_int64))))
+    return p, total
+
+
+def tsdf_get_box(ctx, lo, hi, tsdf=True, weight=True, intensity=False):
+    """icpk_tsdf_get_box: (tsdf, weight, intensity) of the sub-box lo <= (x, y, z) < hi as (hi_z - lo_z, hi_y - lo_y,
+    hi_x - lo_x) arrays; None where not asked."""
+    lo, hi = _i3(lo, "lo"), _i3(hi, "hi")
+    shape = tuple(max(int(hi[a]) - int(lo[a]), 1) for a in (2, 1, 0))  # (an empty box: the call refuses it)
+    f = np.empty(shape, np.float32) if tsdf else None
+    w = np.empty(shape, np.uint16) if weight else None
+    c = np.empty(shape, np.float32) if intensity else None
+    i32 = C.POINTER(C.c_int32)
+    ctx._chk(ctx._lib.icpk_tsdf_get_box(ctx._h, lo.ctypes.data_as(i32), hi.ctypes.data_as(i32),
+                                        None if f is None else _fp(f),
+                                        None if w is None else w.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                        None if c is None else _fp(c)))
+    return f, w, c
 
 
 class Context:

@@ -329,6 +329,24 @@ def build_tsdf_mesh_test(force=False):
     return TSDF_MESH_TEST
 
 
+TSDF_SHIFT_TEST = os.path.join(LIBDIR, "test_tsdf_shift")
+
+
+def build_tsdf_shift_test(force=False):
+    """Host-only C++ program over icp::TsdfVolume::shift / extractLeaving / params / getBox (icp_tsdf.hpp, K23) (g++,
+    links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_tsdf_shift.cpp")
+    hdrs = [os.path.join(HERE, "include", h) for h in ("icp_align.hpp", "icp_tsdf.hpp")]
+    build()
+    newest = max(os.path.getmtime(p) for p in [src, LIB] + hdrs)
+    if not force and os.path.exists(TSDF_SHIFT_TEST) and os.path.getmtime(TSDF_SHIFT_TEST) >= newest:
+        return TSDF_SHIFT_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", TSDF_SHIFT_TEST])
+    return TSDF_SHIFT_TEST
+
+
 TSDF_MESH_HOST_SANITIZED = os.path.join(LIBDIR, "tsdf_mesh_host_sanitized")
 
 
@@ -350,6 +368,26 @@ def build_tsdf_mesh_host_sanitized(force=False):
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-fsanitize=address,undefined"] + objs +
                           ["-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN", "-o", TSDF_MESH_HOST_SANITIZED])
     return TSDF_MESH_HOST_SANITIZED
+
+
+TSDF_SHIFT_HOST_SANITIZED = os.path.join(LIBDIR, "tsdf_shift_host_sanitized")
+
+
+def build_tsdf_shift_host_sanitized(force=False):
+    """DIAGNOSTIC, not part of build(): tests/cpp/tsdf_shift_host_main.cpp (its own main, no GPU) over the host-callable
+    shift rule of csrc/tsdf_rule.h (the kept box, its predicates, the origin), compiled under
+    -fsanitize=address,undefined with -ffp-contract=off as the library is.  Header only: nothing is linked.  Run the
+    program it returns directly."""
+    src = os.path.join(ROOT, "tests", "cpp", "tsdf_shift_host_main.cpp")
+    hdr = os.path.join(CSRC, "tsdf_rule.h")
+    os.makedirs(LIBDIR, exist_ok=True)
+    newest = max(os.path.getmtime(p) for p in (src, hdr))
+    if not force and os.path.exists(TSDF_SHIFT_HOST_SANITIZED) and os.path.getmtime(TSDF_SHIFT_HOST_SANITIZED) >= newest:
+        return TSDF_SHIFT_HOST_SANITIZED
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off", "-fno-omit-frame-pointer",
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", CSRC, src, "-o",
+                           TSDF_SHIFT_HOST_SANITIZED])
+    return TSDF_SHIFT_HOST_SANITIZED
 
 
 BILATERAL_TEST = os.path.join(LIBDIR, "test_bilateral")
@@ -482,5 +520,6 @@ if __name__ == "__main__":
     print(build_tsdf_test(force="--force" in sys.argv))
     print(build_tsdf_raycast_test(force="--force" in sys.argv))
     print(build_tsdf_mesh_test(force="--force" in sys.argv))
+    print(build_tsdf_shift_test(force="--force" in sys.argv))
     print(build_bilateral_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

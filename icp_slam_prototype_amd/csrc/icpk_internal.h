@@ -901,10 +901,34 @@ struct TsdfExtractArgs {
   float *x, *y, *z, *nx, *ny, *nz, *intensity;
   int* voxel_index;
   uint8_t* axis;
+  bool leaving;        // K23: only the crossings a shift would lose ...
+  TsdfKeep keep;       // ... that keeps this box of voxels (read only when leaving)
 };
 // count pass + scan: totals[0] = crossings to list, totals[1] = crossings dropped (device)
 void launch_tsdf_count(const TsdfExtractArgs& a, int nblocks, long long* totals, hipStream_t s);
 void launch_tsdf_scatter(const TsdfExtractArgs& a, int nblocks, hipStream_t s);
+
+// K23, the shift of the volume by whole voxels: out of place, every destination voxel written once (moved or fresh)
+constexpr int TSDF_SHIFT_RUN = 4;  // consecutive voxels a thread owns: one 16-byte store to the tsdf plane
+struct TsdfShiftArgs {
+  const float* tsdf_in;
+  const uint16_t* weight_in;
+  const float* intensity_in;  // or null, with intensity_out
+  float* tsdf_out;
+  uint16_t* weight_out;
+  float* intensity_out;
+  int dims[3];
+  int s[3];                   // clamped to -dims .. dims
+  long long n, chunk;
+};
+void launch_tsdf_shift(const TsdfShiftArgs& a, int nblocks, hipStream_t s);
+// the sub-box [lo, lo + size) of a plane, packed x fastest into out (size[0] size[1] size[2] entries)
+struct TsdfBoxArgs {
+  int dims[3], lo[3], size[3];
+  long long m;                // entries of the box
+};
+void launch_tsdf_box(const TsdfBoxArgs& a, const float* plane, float* out, hipStream_t s);
+void launch_tsdf_box(const TsdfBoxArgs& a, const uint16_t* plane, uint16_t* out, hipStream_t s);
 
 // K20, the ray cast of the volume (the ray rule of tsdf_rule.h).  A workgroup of TSDF_THREADS covers a tile of
 // TSDF_RAY_TILE x TSDF_RAY_TILE pixels, each of its four waves an 8 x 8 quarter; the tiles are dealt out to at most

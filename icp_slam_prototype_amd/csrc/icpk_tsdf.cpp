@@ -1,7 +1,8 @@
 // icpk_tsdf.cpp -- host side of the TSDF volume (K19, K20, K21; kernels_tsdf.hip): the volume a context owns, the
 // refusals, the inversion of the pose, integration of a frame (uploaded, or the one icpk_backproject_pair left
 // resident), extraction of the surface list, the ray cast of the volume into vertex and normal maps, the hand-over of
-// either as the context's target, and the extraction of the triangle mesh.  The rules are written out in include/icpk.h
+// either as the context's target, the extraction of the triangle mesh, and the moving volume (K23: the shift, the leaving
+// list, the parameters in force, a sub-box of the planes).  The rules are written out in include/icpk.h
 // and stated once, in tsdf_rule.h, for the device and for icpk_tsdf_voxel_update / icpk_tsdf_raycast_pixels /
 // icpk_tsdf_mesh_host.
 #include <algorithm>
@@ -19,6 +20,12 @@ struct icpk_tsdf_state {
   long long n = 0;  // voxels
   DevBuf<float> tsdf, intensity;
   DevBuf<uint16_t> weight;
+  // K23: the origin the volume was created with and the voxels it has been shifted by since (p.origin follows from
+  // the two); the second set of planes a shift writes, allocated by the first one, and the staging of icpk_tsdf_get_box
+  float origin0[3] = {0.f, 0.f, 0.f};
+  long long total[3] = {0, 0, 0};
+  DevBuf<float> tsdf_next, intensity_next, box_f;
+  DevBuf<uint16_t> weight_next, box_w;
   // a frame on its way into the volume (the resident frame of icpk_backproject_pair is read where it lies)
   DevBuf<uint16_t> depth;
   DevBuf<float> intensity_image;
@@ -103,6 +110,7 @@ int clear_volume(icpk_ctx* ctx, icpk_tsdf_state* v) {
   v->have_surface = false;
   v->have_raycast = false;
   v->have_mesh = false;
+  for (int a = 0; a < 3; ++a) v->total[a] = 0, v->p.origin[a] = v->origin0[a];  // (the box is back where it was created)
   return ICPK_OK;
 }
 
@@ -218,6 +226,7 @@ int icpk_tsdf_create(icpk_ctx* ctx, const icpk_tsdf_params* params) {
   icpk_tsdf_free(ctx);
   icpk_tsdf_state* v = new icpk_tsdf_state();
   v->p = p;
+  for (int a = 0; a < 3; ++a) v->origin0[a] = p.origin[a];
   v->n = (long long)p.dims[0] * p.dims[1] * p.dims[2];
   const size_t n = (size_t)v->n;
   int rc = v->tsdf.reserve(ctx, n);
@@ -346,15 +355,18 @@ int icpk_tsdf_set(icpk_ctx* ctx, const float* tsdf, const uint16_t* weight, cons
   return ICPK_OK;
 }
 
-int icpk_tsdf_extract_surface(icpk_ctx* ctx, int32_t min_weight, int32_t* n_points, int32_t* n_no_normal) {
-  if (!ctx) return ICPK_E_ARG;
+// icpk_tsdf_extract_surface (s null), or icpk_tsdf_extract_leaving: the crossings a shift by s would lose
+static int extract_list(icpk_ctx* ctx, int32_t min_weight, const int32_t* s, int32_t* n_points, int32_t* n_no_normal) {
   icpk_tsdf_state* v = ctx->tsdf;
   if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
   if (min_weight < 1 || min_weight > 65535) return fail(ctx, ICPK_E_ARG, "min_weight outside 1 .. 65535");
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const bool had_surface = v->have_surface;
   v->have_surface = false;
   TsdfExtractArgs a{};
   a.v = make_planes(v->p, v->tsdf, v->weight, v->intensity_plane(), min_weight);
+  a.leaving = s != nullptr;
+  if (s) a.keep = tsdf_keep_box(v->p.dims, s);
   a.n = v->n, a.chunk = tsdf_chunk(v->n);
   a.counts = v->slots, a.dropped = v->dropped, a.offsets = v->offsets;
   const int nblocks = tsdf_blocks(v->n);
@@ -364,7 +376,10 @@ int icpk_tsdf_extract_surface(icpk_ctx* ctx, int32_t min_weight, int32_t* n_poin
   ICPK_HIP(ctx, hipMemcpyAsync(v->totals_host, v->totals, 2 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const long long listed = v->totals_host[0], dropped = v->totals_host[1];
-  if (listed > ICPK_TSDF_MAX_SURFACE) return fail(ctx, ICPK_E_ARG, "more than ICPK_TSDF_MAX_SURFACE crossings");
+  if (listed > ICPK_TSDF_MAX_SURFACE) {
+    if (s) v->have_surface = had_surface;  // (a refused icpk_tsdf_extract_leaving: the list is as it was, nothing was written)
+    return fail(ctx, ICPK_E_ARG, "more than ICPK_TSDF_MAX_SURFACE crossings");
+  }
   if ((size_t)listed > v->surf_cap) {
     const size_t cap = (size_t)listed;
     v->surf_cap = 0;
@@ -386,6 +401,101 @@ int icpk_tsdf_extract_surface(icpk_ctx* ctx, int32_t min_weight, int32_t* n_poin
   v->have_surface = true;
   if (n_points) *n_points = v->surf_n;
   if (n_no_normal) *n_no_normal = v->surf_dropped;
+  return ICPK_OK;
+}
+
+int icpk_tsdf_extract_surface(icpk_ctx* ctx, int32_t min_weight, int32_t* n_points, int32_t* n_no_normal) {
+  if (!ctx) return ICPK_E_ARG;
+  return extract_list(ctx, min_weight, nullptr, n_points, n_no_normal);
+}
+
+int icpk_tsdf_extract_leaving(icpk_ctx* ctx, int32_t min_weight, const int32_t s[3], int32_t* n_points, int32_t* n_no_normal) {
+  if (!ctx) return ICPK_E_ARG;
+  if (!ctx->tsdf) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  if (!s) return fail(ctx, ICPK_E_ARG, "the shift is NULL");
+  return extract_list(ctx, min_weight, s, n_points, n_no_normal);
+}
+
+int icpk_tsdf_shift(icpk_ctx* ctx, const int32_t s[3]) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  if (!s) return fail(ctx, ICPK_E_ARG, "the shift is NULL");
+  if (s[0] == 0 && s[1] == 0 && s[2] == 0) return ICPK_OK;
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const bool color = (v->p.flags & ICPK_TSDF_COLOR) != 0;
+  const size_t n = (size_t)v->n;
+  // (the second set of planes: by the first shift, kept with the volume.  A failure here leaves the volume as it was)
+  int rc = v->tsdf_next.reserve(ctx, n);
+  if (!rc) rc = v->weight_next.reserve(ctx, n);
+  if (!rc && color) rc = v->intensity_next.reserve(ctx, n);
+  if (rc) return rc;
+  TsdfShiftArgs a{};
+  a.tsdf_in = v->tsdf, a.weight_in = v->weight, a.intensity_in = v->intensity_plane();
+  a.tsdf_out = v->tsdf_next, a.weight_out = v->weight_next, a.intensity_out = color ? v->intensity_next.get() : nullptr;
+  const TsdfKeep box = tsdf_keep_box(v->p.dims, s);
+  for (int k = 0; k < 3; ++k) a.dims[k] = v->p.dims[k], a.s[k] = box.lo[k];  // (lo: s clamped to -dims .. dims)
+  a.n = v->n, a.chunk = tsdf_chunk(v->n);
+  launch_tsdf_shift(a, tsdf_blocks(v->n), ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  // the sets change places: everything later on the stream reads the new one, the old one is the next shift's room
+  std::swap(v->tsdf, v->tsdf_next);
+  std::swap(v->weight, v->weight_next);
+  if (color) std::swap(v->intensity, v->intensity_next);
+  for (int k = 0; k < 3; ++k) {
+    v->total[k] += s[k];
+    v->p.origin[k] = tsdf_shifted_origin(v->origin0[k], v->total[k], v->p.voxel);
+  }
+  v->have_surface = false;
+  v->have_raycast = false;
+  v->have_mesh = false;
+  return ICPK_OK;
+}
+
+int icpk_tsdf_get_params(icpk_ctx* ctx, icpk_tsdf_params* out, int64_t total[3]) {
+  if (!ctx) return ICPK_E_ARG;
+  const icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  if (out) *out = v->p;
+  if (total)
+    for (int k = 0; k < 3; ++k) total[k] = v->total[k];
+  return ICPK_OK;
+}
+
+int icpk_tsdf_get_box(icpk_ctx* ctx, const int32_t lo[3], const int32_t hi[3], float* tsdf, uint16_t* weight, float* intensity) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  if (!lo || !hi) return fail(ctx, ICPK_E_ARG, "lo or hi is NULL");
+  TsdfBoxArgs a{};
+  a.m = 1;
+  for (int k = 0; k < 3; ++k) {
+    if (lo[k] < 0 || hi[k] > v->p.dims[k] || lo[k] >= hi[k]) return fail(ctx, ICPK_E_ARG, "the box is empty or out of bounds");
+    a.dims[k] = v->p.dims[k], a.lo[k] = lo[k], a.size[k] = hi[k] - lo[k];
+    a.m *= a.size[k];  // (<= n <= 2^30)
+  }
+  if (intensity && !(v->p.flags & ICPK_TSDF_COLOR)) return fail(ctx, ICPK_E_ARG, "the volume keeps no intensities");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t m = (size_t)a.m;
+  if (tsdf || intensity)
+    if (int rc = v->box_f.reserve(ctx, m)) return rc;
+  if (weight)
+    if (int rc = v->box_w.reserve(ctx, m)) return rc;
+  // (one staging buffer for both float planes: the copy of the first is in front of the second's kernel on the stream)
+  const float* const planes[2] = {v->tsdf.get(), v->intensity.get()};
+  float* const out[2] = {tsdf, intensity};
+  for (int k = 0; k < 2; ++k) {
+    if (!out[k]) continue;
+    launch_tsdf_box(a, planes[k], v->box_f.get(), ctx->stream);
+    ICPK_HIP(ctx, hipGetLastError());
+    ICPK_HIP(ctx, hipMemcpyAsync(out[k], v->box_f, m * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (weight) {
+    launch_tsdf_box(a, v->weight.get(), v->box_w.get(), ctx->stream);
+    ICPK_HIP(ctx, hipGetLastError());
+    ICPK_HIP(ctx, hipMemcpyAsync(weight, v->box_w, m * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ICPK_OK;
 }
 

@@ -4,6 +4,8 @@
 // the same bytes on every run.  K20 casts one ray per pixel through the volume (the ray rule of tsdf_rule.h) into eight
 // image planes, a pixel owned by one thread, and compacts their valid pixels into a list with K19's scan.  K21 extracts
 // a triangle mesh (the mesh rule of tsdf_rule.h): K19's count / scan / scatter for the vertices and for the triangles.
+// K23 moves the volume by whole voxels into a second set of planes (the shift rule of tsdf_rule.h), lists the crossings
+// such a move would lose with K19's three passes, and packs a sub-box of a plane for download.
 //
 // Both walks share one geometry: the volume is a line of n = dx dy dz voxels in linear order (x fastest), cut into at
 // most TSDF_MAX_BLOCKS contiguous chunks of a multiple of TSDF_THREADS voxels, one workgroup per chunk, which it
@@ -72,18 +74,24 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_sum_slots_kernel(const int*
   if (threadIdx.x == 0) out[0] = total;
 }
 
-// the statuses of voxel `at`'s three crossings (TSDF_NO_CROSSING where the voxel itself is below min_weight)
-__device__ __forceinline__ void crossing_statuses(const TsdfPlanes& v, const VoxelIndex& vi, long long at, bool valid,
-                                                  int c[3], float& fv, int st[3]) {
+// the statuses of voxel `at`'s three crossings (TSDF_NO_CROSSING where the voxel itself is below min_weight).  LEAVING
+// (K23): as the leaving list sees them -- the crossings the shift keeps are no crossings
+template <bool LEAVING>
+__device__ __forceinline__ void crossing_statuses(const TsdfPlanes& v, const TsdfKeep& keep, const VoxelIndex& vi,
+                                                  long long at, bool valid, int c[3], float& fv, int st[3]) {
   st[0] = st[1] = st[2] = TSDF_NO_CROSSING;
   if (!valid || (int)v.weight[at] < v.min_weight) return;
   vi.split((unsigned)at, c);
   fv = v.tsdf[at];
 #pragma unroll
-  for (int axis = 0; axis < 3; ++axis) st[axis] = tsdf_crossing(v, c, at, fv, axis, nullptr);
+  for (int axis = 0; axis < 3; ++axis) {
+    st[axis] = tsdf_crossing(v, c, at, fv, axis, nullptr);
+    if (LEAVING) st[axis] = tsdf_leaving_status(keep, c, axis, st[axis]);
+  }
 }
 
 // pass 1: per chunk, the crossings that will be listed and those dropped for want of a normal
+template <bool LEAVING>
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_count_kernel(const TsdfExtractArgs a) {
   const long long begin = (long long)blockIdx.x * a.chunk;
   const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
@@ -93,7 +101,7 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_count_kernel(const TsdfExtr
     const long long at = base + threadIdx.x;
     int c[3] = {0, 0, 0}, st[3];
     float fv = 0.f;
-    crossing_statuses(a.v, vi, at, at < end, c, fv, st);
+    crossing_statuses<LEAVING>(a.v, a.keep, vi, at, at < end, c, fv, st);
 #pragma unroll
     for (int axis = 0; axis < 3; ++axis) {
       listed += st[axis] == TSDF_CROSSING;
@@ -132,6 +140,7 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_scan_kernel(const int* __re
 }
 
 // pass 3: the chunk's crossings again, each to its place: the chunk's offset, then voxel order, then axis order
+template <bool LEAVING>
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_scatter_kernel(const TsdfExtractArgs a) {
   const long long begin = (long long)blockIdx.x * a.chunk;
   const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
@@ -142,7 +151,7 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_scatter_kernel(const TsdfEx
     const long long at = base + threadIdx.x;
     int c[3] = {0, 0, 0}, st[3];
     float fv = 0.f;
-    crossing_statuses(a.v, vi, at, at < end, c, fv, st);
+    crossing_statuses<LEAVING>(a.v, a.keep, vi, at, at < end, c, fv, st);
     const int mine = (st[0] == TSDF_CROSSING) + (st[1] == TSDF_CROSSING) + (st[2] == TSDF_CROSSING);
     int round_total;
     long long pos = run + block_excl_scan<TSDF_THREADS>(mine, &round_total);
@@ -161,6 +170,85 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_scatter_kernel(const TsdfEx
     }
     run += round_total;
   }
+}
+
+// ---- K23: the shift ----
+// The new voxel (i, j, k) takes the old voxel (i + s_x, j + s_y, k + s_z), or the fresh state where that one is out of
+// bounds.  Out of place: a thread owns TSDF_SHIFT_RUN consecutive destination voxels of the linear order (the run
+// starts at a multiple of 4, so that its stores are one aligned 16-byte word to the float planes and one 8-byte word to
+// the weights) and writes them once; no atomic, no LDS.  Where the run lies in one row and so do its four sources, they
+// are four consecutive words s_x + dx (s_y + dy s_z) further on: one load, misaligned by s_x mod 4 words, which the
+// hardware takes.  Elsewhere (a row's ends, the slab that comes in fresh, the volume's last voxels) voxel by voxel.
+struct __attribute__((packed, aligned(4))) F4u {  // four floats wherever a float may lie
+  float v[4];
+};
+struct __attribute__((packed, aligned(2))) H4u {  // four weights wherever a weight may lie
+  uint16_t v[4];
+};
+
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_shift_kernel(const TsdfShiftArgs a) {
+  const long long begin = (long long)blockIdx.x * a.chunk;
+  const long long end = begin + a.chunk < a.n ? begin + a.chunk : a.n;
+  const int dx = a.dims[0], dy = a.dims[1], dz = a.dims[2];
+  const VoxelIndex vi{(unsigned)dx, (unsigned)dx * (unsigned)dy};
+  const long long delta = a.s[0] + (long long)dx * (a.s[1] + (long long)dy * a.s[2]);
+  for (long long base = begin; base < end; base += TSDF_THREADS * TSDF_SHIFT_RUN) {
+    const long long at = base + (long long)threadIdx.x * TSDF_SHIFT_RUN;  // (a multiple of 4: chunks are multiples of 256)
+    if (at >= end) continue;
+    int c[3];
+    vi.split((unsigned)at, c);
+    float f[TSDF_SHIFT_RUN], ci[TSDF_SHIFT_RUN];
+    uint16_t w[TSDF_SHIFT_RUN];
+    const int sy = c[1] + a.s[1], sz = c[2] + a.s[2], sx = c[0] + a.s[0];  // (|s| <= dims: no overflow)
+    const bool row = c[0] + TSDF_SHIFT_RUN <= dx && sy >= 0 && sy < dy && sz >= 0 && sz < dz;
+    if (row && sx >= 0 && sx + TSDF_SHIFT_RUN <= dx) {
+      // (one row of the destination, one row of the source, all of it in bounds: at + delta .. + 3 are its indices)
+      const F4u ff = *reinterpret_cast<const F4u*>(a.tsdf_in + (at + delta));
+      const H4u ww = *reinterpret_cast<const H4u*>(a.weight_in + (at + delta));
+#pragma unroll
+      for (int q = 0; q < TSDF_SHIFT_RUN; ++q) f[q] = ff.v[q], w[q] = ww.v[q], ci[q] = 0.f;
+      if (a.intensity_in) {
+        const F4u cc = *reinterpret_cast<const F4u*>(a.intensity_in + (at + delta));
+#pragma unroll
+        for (int q = 0; q < TSDF_SHIFT_RUN; ++q) ci[q] = cc.v[q];
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < TSDF_SHIFT_RUN; ++q) {
+        f[q] = 0.f, w[q] = 0, ci[q] = 0.f;
+        if (at + q >= end) continue;
+        int cq[3];
+        vi.split((unsigned)(at + q), cq);
+        const int qx = cq[0] + a.s[0], qy = cq[1] + a.s[1], qz = cq[2] + a.s[2];
+        if (qx < 0 || qx >= dx || qy < 0 || qy >= dy || qz < 0 || qz >= dz) continue;  // (fresh)
+        const long long from = qx + (long long)dx * (qy + (long long)dy * qz);          // (in bounds: < n)
+        f[q] = a.tsdf_in[from], w[q] = a.weight_in[from];
+        if (a.intensity_in) ci[q] = a.intensity_in[from];
+      }
+    }
+    if (at + TSDF_SHIFT_RUN <= end) {
+      *reinterpret_cast<float4*>(a.tsdf_out + at) = make_float4(f[0], f[1], f[2], f[3]);
+      *reinterpret_cast<ushort4*>(a.weight_out + at) = make_ushort4(w[0], w[1], w[2], w[3]);
+      if (a.intensity_out) *reinterpret_cast<float4*>(a.intensity_out + at) = make_float4(ci[0], ci[1], ci[2], ci[3]);
+    } else {  // (the volume's last one to three voxels)
+      for (int q = 0; at + q < end; ++q) {
+        a.tsdf_out[at + q] = f[q], a.weight_out[at + q] = w[q];
+        if (a.intensity_out) a.intensity_out[at + q] = ci[q];
+      }
+    }
+  }
+}
+
+// one thread per voxel of the box: x fastest, so a wave reads runs of a row and writes 64 consecutive entries
+inline int tsdf_box_blocks(long long m) { return (int)((m + TSDF_THREADS - 1) / TSDF_THREADS); }
+template <class T>
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_box_kernel(const TsdfBoxArgs a, const T* __restrict__ plane,
+                                                                 T* __restrict__ out) {
+  const long long e = (long long)blockIdx.x * TSDF_THREADS + threadIdx.x;
+  if (e >= a.m) return;
+  const long long sxy = (long long)a.size[0] * a.size[1];
+  const long long k = e / sxy, rem = e - k * sxy, j = rem / a.size[0], i = rem - j * a.size[0];
+  out[e] = plane[(a.lo[0] + i) + (long long)a.dims[0] * ((a.lo[1] + j) + (long long)a.dims[1] * (a.lo[2] + k))];
 }
 
 // ---- K20: the ray cast ----
@@ -363,12 +451,26 @@ void launch_tsdf_integrate(const TsdfIntegrateArgs& a, int nblocks, long long* n
 }
 
 void launch_tsdf_count(const TsdfExtractArgs& a, int nblocks, long long* totals, hipStream_t s) {
-  hipLaunchKernelGGL(tsdf_count_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+  if (a.leaving) hipLaunchKernelGGL(tsdf_count_kernel<true>, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+  else hipLaunchKernelGGL(tsdf_count_kernel<false>, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
   hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(TSDF_THREADS), 0, s, a.counts, a.dropped, nblocks, a.offsets, totals);
 }
 
 void launch_tsdf_scatter(const TsdfExtractArgs& a, int nblocks, hipStream_t s) {
-  hipLaunchKernelGGL(tsdf_scatter_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+  if (a.leaving) hipLaunchKernelGGL(tsdf_scatter_kernel<true>, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+  else hipLaunchKernelGGL(tsdf_scatter_kernel<false>, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+}
+
+void launch_tsdf_shift(const TsdfShiftArgs& a, int nblocks, hipStream_t s) {
+  hipLaunchKernelGGL(tsdf_shift_kernel, dim3(nblocks), dim3(TSDF_THREADS), 0, s, a);
+}
+
+void launch_tsdf_box(const TsdfBoxArgs& a, const float* plane, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(tsdf_box_kernel<float>, dim3(tsdf_box_blocks(a.m)), dim3(TSDF_THREADS), 0, s, a, plane, out);
+}
+
+void launch_tsdf_box(const TsdfBoxArgs& a, const uint16_t* plane, uint16_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(tsdf_box_kernel<uint16_t>, dim3(tsdf_box_blocks(a.m)), dim3(TSDF_THREADS), 0, s, a, plane, out);
 }
 
 void launch_tsdf_raycast(const TsdfRaycastArgs& a, int nblocks, long long* totals, hipStream_t s) {

@@ -139,6 +139,50 @@ ICPK_HD int tsdf_crossing(const TsdfPlanes& v, const int c[3], long long at, flo
   return TSDF_CROSSING;
 }
 
+// ---- the shift rule (K23) ----
+// the old voxel indices a shift by s keeps: lo[a] <= v_a < hi[a], lo = s and hi = dims + s with s clamped to
+// -dims .. dims (a larger shift keeps nothing either way, and the sums stay ints)
+struct TsdfKeep {
+  int lo[3], hi[3];
+};
+
+ICPK_HD TsdfKeep tsdf_keep_box(const int dims[3], const int s[3]) {
+  TsdfKeep b;
+  for (int a = 0; a < 3; ++a) {
+    const int sa = s[a] < -dims[a] ? -dims[a] : s[a] > dims[a] ? dims[a] : s[a];
+    b.lo[a] = sa, b.hi[a] = dims[a] + sa;
+  }
+  return b;
+}
+
+// the origin after a cumulative shift of `total` voxels: from the creation origin, in double, rounded once
+ICPK_HD float tsdf_shifted_origin(float origin0, long long total, float voxel) {
+  return (float)((double)origin0 + (double)total * (double)voxel);
+}
+
+// stays(V) and stays(N) for the crossing between V = c and its +1 neighbour N along `axis`
+ICPK_HD bool tsdf_ends_stay(const TsdfKeep& b, const int c[3], int axis) {
+  for (int a = 0; a < 3; ++a)
+    if (c[a] < b.lo[a] || c[a] + (a == axis) >= b.hi[a]) return false;
+  return true;
+}
+
+// whether the shift keeps that crossing: V, N and the six axis neighbours of each stay, so that both gradients are
+// still there in the shifted volume
+ICPK_HD bool tsdf_crossing_kept(const TsdfKeep& b, const int c[3], int axis) {
+  for (int a = 0; a < 3; ++a)
+    if (c[a] - 1 < b.lo[a] || c[a] + 1 + (a == axis) >= b.hi[a]) return false;
+  return true;
+}
+
+// what the leaving list makes of a crossing's status: a listed crossing the shift keeps, and a dropped one whose two
+// ends stay, are none of its business
+ICPK_HD int tsdf_leaving_status(const TsdfKeep& b, const int c[3], int axis, int status) {
+  if (status == TSDF_CROSSING && tsdf_crossing_kept(b, c, axis)) return TSDF_NO_CROSSING;
+  if (status == TSDF_NO_NORMAL && tsdf_ends_stay(b, c, axis)) return TSDF_NO_CROSSING;
+  return status;
+}
+
 // ---- the ray rule (K20) ----
 // the camera of one ray cast: camera-to-world, its nine R and three c rounded to float once (rule 0)
 struct TsdfRay {

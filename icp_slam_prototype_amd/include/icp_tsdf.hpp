@@ -7,7 +7,8 @@
 //                        holds one volume: constructing another replaces it.  raycast gives the surface visible from
 //                        one pose as vertex and normal maps (K20); raycastToTarget makes it the Engine's target.
 //                        extractMesh / getMesh give the surface as a triangle mesh (K21); setPlanes restores a saved
-//                        model.
+//                        model.  shift / extractLeaving / getBox let the volume follow the camera (K23): the box
+//                        moves by whole voxels, what is about to leave it is listed first.
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -162,13 +163,43 @@ class TsdfVolume {
   int planes(float* tsdf, uint16_t* weight, float* intensity = nullptr) { return icpk_tsdf_get(eng_.ctx(), tsdf, weight, intensity); }
   int reset() {
     forget();
-    return icpk_tsdf_reset(eng_.ctx());
+    const int rc = icpk_tsdf_reset(eng_.ctx());
+    if (rc == ICPK_OK) refresh();  // (the box is back where it was created)
+    return rc;
+  }
+  // the moving volume (K23).  shift: the new voxel v holds the old voxel v + s (three ints), what falls off is gone, the
+  // origin follows (params(), total()); drops the surface list, the maps and the mesh.  No host wait
+  int shift(const int32_t s[3]) {
+    const int rc = icpk_tsdf_shift(eng_.ctx(), s);
+    if (rc != ICPK_OK) return rc;
+    if (s[0] || s[1] || s[2]) forget();
+    return refresh();
+  }
+  // the crossings a shift by s would lose, as surface() lists them (voxel: the index before the shift); the list also
+  // replaces the one on the device (toTarget).  Call it before shift(s)
+  int extractLeaving(TsdfSurface& out, const int32_t s[3], int minWeight = 1) {
+    int32_t n = 0;
+    int rc = icpk_tsdf_extract_leaving(eng_.ctx(), minWeight, s, &n, &out.noNormal);
+    if (rc) return rc;
+    for (std::vector<float>* v : {&out.x, &out.y, &out.z, &out.nx, &out.ny, &out.nz, &out.intensity}) v->assign((size_t)n, 0.f);
+    out.voxel.assign((size_t)n, 0);
+    out.axis.assign((size_t)n, 0);
+    return icpk_tsdf_get_surface(eng_.ctx(), out.x.data(), out.y.data(), out.z.data(), out.nx.data(), out.ny.data(),
+                                 out.nz.data(), out.intensity.data(), out.voxel.data(), out.axis.data());
+  }
+  // the cumulative shift since the volume was created or reset (params().origin is the origin it amounts to)
+  const int64_t* total() const { return total_; }
+  // the planes of the sub-box lo <= (x, y, z) < hi, x fastest, (hi - lo) entries per axis; any pointer may be null
+  int getBox(const int32_t lo[3], const int32_t hi[3], float* tsdf, uint16_t* weight, float* intensity = nullptr) {
+    return icpk_tsdf_get_box(eng_.ctx(), lo, hi, tsdf, weight, intensity);
   }
 
  private:
   void forget() { rayRows_ = rayCols_ = 0, meshVertices_ = meshTriangles_ = meshNoNormal_ = 0; }
+  int refresh() { return icpk_tsdf_get_params(eng_.ctx(), &p_, total_); }
   Engine& eng_;
   icpk_tsdf_params p_;
+  int64_t total_[3] = {0, 0, 0};
   float fx_, cx_;
   int rayRows_ = 0, rayCols_ = 0;
   int32_t meshVertices_ = 0, meshTriangles_ = 0, meshNoNormal_ = 0;

@@ -20,6 +20,14 @@ open where the surface leaves them or the volume), extracted on the device:
 
     mesh = vol.mesh(min_weight=2)               # dict(vertices (3, n), normals, intensity, ..., triangles (m, 3))
     write_ply("model.ply", mesh)
+
+A scene larger than the box (K23) -- the volume follows the camera by whole voxels, and what is about to fall off is
+streamed out first as points with normals:
+
+    tracker = ModelTracker(vol, pose=first_pose, follow=16)   # shift once the camera has moved 16 voxels
+    for depth in frames:
+        pose = tracker.track(depth)
+    parts = tracker.streamed + [vol.surface()]                # the model: what left, and what the box still holds
 """
 import numpy as np
 
@@ -39,6 +47,9 @@ class TsdfVolume:
                                       depth_scale=depth_scale, flags=binding.TSDF_COLOR if color else 0)
         self.frames = 0
         self.n_points = self.n_no_normal = None
+        self.total = np.zeros(3, np.int64)  # the cumulative shift (K23); params.origin is kept up to date with it
+        self.follow_ref = None              # follow()'s reference camera centre: the first pose it sees
+        self.follow_min_weight = 1          # ... and the min_weight of the leaving lists it extracts
 
     def integrate(self, depth, pose, intensity=None):
         """One (rows, cols) uint16 frame at the camera-to-world pose (4, 4).  Returns the number of voxels written."""
@@ -118,8 +129,52 @@ class TsdfVolume:
         """(tsdf, weight, intensity) as (dz, dy, dx) arrays."""
         return self.ctx.tsdf_get(intensity=intensity)
 
+    def box(self, lo, hi, intensity=False):
+        """(tsdf, weight, intensity) of the sub-box lo <= (x, y, z) < hi, as (nz, ny, nx) arrays: what a caller who
+        stitches a larger model offline archives of a slab before it leaves."""
+        return binding.tsdf_get_box(self.ctx, lo, hi, intensity=intensity)
+
+    def shift(self, s, min_weight=None):
+        """The volume moves by s = (s_x, s_y, s_z) whole voxels (K23): the new voxel v holds the old voxel v + s, what
+        falls off is gone and what comes in is fresh; the origin follows.  min_weight: first extract and download the
+        leaving list -- the crossings the shift loses -- and return it as surface() does (else None)."""
+        left = None
+        if min_weight is not None:
+            binding.tsdf_extract_leaving(self.ctx, s, min_weight)
+            left = self.ctx.tsdf_get_surface()
+        binding.tsdf_shift(self.ctx, s)
+        self.params, self.total = binding.tsdf_get_params(self.ctx)
+        self.n_points = self.n_no_normal = None
+        return left
+
+    @staticmethod
+    def follow_steps(centre, ref, voxel):
+        """k_a = round((c_a - ref_a) / voxel) in float64, halves away from zero: the whole voxels the camera centre
+        has moved from the reference."""
+        q = (np.asarray(centre, np.float64) - np.asarray(ref, np.float64)) / np.float64(voxel)
+        return (np.sign(q) * np.floor(np.abs(q) + 0.5)).astype(np.int64)
+
+    def follow(self, pose, every):
+        """Keeps the volume around the camera: the first pose seen sets a reference centre; once the centre of `pose`
+        (4, 4, camera-to-world) is `every` voxels or more from it along any axis, the volume shifts by the whole voxels
+        k it has moved (all three axes) and the reference advances by k * voxel.  Returns the leaving list of that shift
+        (extracted with self.follow_min_weight), or None when the volume stayed."""
+        c = np.asarray(pose, np.float64).reshape(4, 4)[:3, 3]
+        if self.follow_ref is None:
+            self.follow_ref = c.copy()
+        voxel = np.float64(self.params.voxel)
+        k = self.follow_steps(c, self.follow_ref, voxel)
+        if not (np.abs(k) >= int(every)).any():
+            return None
+        left = self.shift(k, min_weight=self.follow_min_weight)
+        self.follow_ref = self.follow_ref + k.astype(np.float64) * voxel
+        return left
+
     def reset(self):
         self.ctx.tsdf_reset()
+        if self.total.any():  # (the box is back where it was created)
+            self.params, self.total = binding.tsdf_get_params(self.ctx)
+        self.follow_ref = None
         self.frames = 0
         self.n_points = self.n_no_normal = None
 
@@ -136,9 +191,13 @@ class ModelTracker:
     view's border, which biases the pose (icpk_params' default, 0.75 m, is meant for frame-to-frame clouds).
     bilateral: a depth.bilateral_params object (True: the defaults) -- the cloud that is aligned then comes from the
     smoothed frame (depth.backproject_smoothed, K22) while the RAW frame is what the volume fuses, KinectFusion's order;
-    None: the raw frame serves both."""
+    None: the raw frame serves both.
+    follow: an integer `every` -- the volume follows the camera (TsdfVolume.follow, K23): once a pose is found and before
+    its frame is fused, the volume shifts when the camera has moved `every` voxels or more, and a non-empty leaving list
+    goes to on_leave(list) (default: appended to self.streamed).  None: the volume stays where it was created."""
 
-    def __init__(self, vol, pose=None, z_near=0.25, z_far=6.0, step=None, min_weight=1, bilateral=None, **align_kw):
+    def __init__(self, vol, pose=None, z_near=0.25, z_far=6.0, step=None, min_weight=1, bilateral=None, follow=None,
+                 on_leave=None, **align_kw):
         self.vol = vol
         self.pose = np.eye(4) if pose is None else np.array(pose, np.float64).reshape(4, 4)
         self.ray = dict(z_near=z_near, z_far=z_far, step=step, min_weight=min_weight)
@@ -146,6 +205,10 @@ class ModelTracker:
         self.bilateral = depth_front.bilateral_params() if bilateral is True else bilateral
         self.frames = 0
         self.n_hits = self.stats = None
+        self.follow = follow
+        self.streamed = []
+        self.on_leave = self.streamed.append if on_leave is None else on_leave
+        self.shifts = 0  # the shifts `follow` has made
 
     def track(self, depth, intensity=None):
         """One (rows, cols) uint16 frame (with its (rows, cols) intensities on a colour volume).  Returns the frame's
@@ -165,6 +228,12 @@ class ModelTracker:
             ctx.commit_source()
             T, self.stats, _ = ctx.align(params)
             self.pose = T.astype(np.float64) @ self.pose
+        if self.follow is not None:
+            before = vol.total.copy()
+            left = vol.follow(self.pose, self.follow)
+            self.shifts += bool((vol.total != before).any())
+            if left is not None and left["points"].shape[1] > 0:
+                self.on_leave(left)
         vol.integrate(depth, self.pose, intensity)
         self.frames += 1
         return self.pose.copy()

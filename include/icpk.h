@@ -1248,7 +1248,7 @@ int icpk_pose_graph_evaluate(icpk_ctx *ctx, int32_t n_nodes, const double *poses
 int icpk_get_pose_graph_trace(icpk_ctx *ctx, int32_t *n_iter, double *cost_out, double *lambda_out,
                               int32_t *pcg_iterations_out, int32_t *accepted_out);
 
-/* ---- TSDF volume (extension, K19 - K21) ---------------------------------------------------------------------------
+/* ---- TSDF volume (extension, K19 - K23) ---------------------------------------------------------------------------
  * What the poses of K18 are for: the posed depth frames fused into one model.  One dense volume of truncated signed
  * distances per context, owned by it like the map: created by icpk_tsdf_create, released by icpk_tsdf_release or
  * icpk_destroy, and touched by no other call.  Every voxel is owned by one thread: no atomic, the same bytes on every
@@ -1429,7 +1429,46 @@ int icpk_get_pose_graph_trace(icpk_ctx *ctx, int32_t *n_iter, double *cost_out, 
  *     ICPK_TSDF_COLOR), compiled from the header the kernels include (csrc/tsdf_rule.h).  counts = {n_vertices,
  *     n_triangles, n_no_normal} is always filled once the arguments are accepted; the arrays (any may be NULL) are filled
  *     when n_vertices <= cap_vertices and n_triangles <= cap_triangles, else ICPK_E_ARG.  ICPK_E_ARG also for what
- *     icpk_tsdf_create and icpk_tsdf_extract_mesh refuse, a NULL tsdf, weight or counts, or a negative capacity. */
+ *     icpk_tsdf_create and icpk_tsdf_extract_mesh refuse, a NULL tsdf, weight or counts, or a negative capacity.
+ *
+ * THE SHIFT RULE (icpk_tsdf_shift, K23): the volume follows the camera by whole voxels (KinectFusion's moving volume).
+ * A volume remembers the origin it was created with, origin0 (float[3]), and a cumulative shift, total (int64[3]; zero
+ * after icpk_tsdf_create and after icpk_tsdf_reset; icpk_tsdf_set leaves it).  icpk_tsdf_shift(ctx, s):
+ *   content     the new voxel (i, j, k) takes tsdf, weight and (ICPK_TSDF_COLOR) intensity of the old voxel
+ *               (i + s_x, j + s_y, k + s_z) where that voxel is in bounds; elsewhere it is fresh (0, 0, 0).  Any sign;
+ *               |s_a| >= dims_a empties the volume; s = 0 is a no-op that succeeds (and drops nothing).
+ *   origin      total += s;  origin_a = (float)((double)origin0_a + (double)total_a * (double)voxel): always from
+ *               origin0 and total, never accumulated, so shifting there and back returns the creation origin bit for
+ *               bit.  Every other rule (rule 1, the ray rule's SAMPLE, the mesh rule) reads this origin exactly as it
+ *               read params.origin before.
+ *   dropped     the surface list, the ray-cast maps and the mesh (they index the old volume): their getters answer
+ *               ICPK_E_NOT_SET afterwards, as after icpk_tsdf_reset.  Nothing else the context holds is touched: source
+ *               and target (even a target handed over from this volume earlier), normals, colours, associations, seeds,
+ *               map lists, the resident frame.  Stream-ordered: no host wait.  The first shift allocates a second set
+ *               of planes (the move is out of place; the two sets change places), which the volume keeps.
+ * THE LEAVING LIST (icpk_tsdf_extract_leaving): the surface rule on the volume as it stands, restricted to the crossings
+ * a shift by s would lose.  stays(v): s_a <= v_a < dims_a + s_a on all three axes, for an old voxel index v.  A listed
+ * crossing (V, N) is KEPT by the shift iff stays holds for V, for N and for the six axis neighbours of each -- only then
+ * does it still have both gradients in the shifted volume.  The leaving list is every crossing the surface rule lists
+ * that is not kept, in the surface rule's order; n_no_normal counts the crossings dropped for want of a normal one of
+ * whose ends (V or N) does not stay.  So the surface list before a shift is the leaving list plus the surface list after
+ * it (voxel indices mapped back), exactly and disjointly; kept normals and intensities are the same bits, kept points
+ * differ by the rounding of the new origin.  The result REPLACES the context's surface list: icpk_tsdf_get_surface and
+ * icpk_tsdf_surface_to_target work on it unchanged, voxel_index is the OLD linear index.  A crossing streamed out from
+ * the rim may be listed again later, when new frames re-fill the fresh slab next to it and give it back its gradients:
+ * a consumer that stitches streamed lists must expect such repeats near slab borders.
+ *
+ * icpk_tsdf_shift    ICPK_E_NOT_SET without a volume, ICPK_E_ARG for a NULL s.  A refused call leaves everything as it
+ *     was.
+ * icpk_tsdf_extract_leaving   ICPK_E_NOT_SET without a volume; ICPK_E_ARG for a NULL s, min_weight outside 1 .. 65535, or
+ *     when more than ICPK_TSDF_MAX_SURFACE crossings would be listed; a refused call leaves everything, the surface list
+ *     included, as it was.  One host wait (the count), as icpk_tsdf_extract_surface.
+ * icpk_tsdf_get_params   the parameters in force (with the CURRENT origin) and the cumulative shift; either pointer may
+ *     be NULL.  ICPK_E_NOT_SET without a volume.
+ * icpk_tsdf_get_box  the planes of the sub-box lo_a <= v_a < hi_a, x fastest, (hi_x - lo_x)(hi_y - lo_y)(hi_z - lo_z)
+ *     entries each: a leaving slab can be archived losslessly with it.  Any plane pointer may be NULL.  ICPK_E_NOT_SET
+ *     without a volume; ICPK_E_ARG for a NULL lo or hi, an empty or out-of-bounds box, or intensity on a volume without
+ *     colour. */
 #define ICPK_TSDF_COLOR 1 /* flags of icpk_tsdf_params: one intensity per voxel */
 #define ICPK_TSDF_MAX_VOXELS (1 << 30)
 #define ICPK_TSDF_MAX_SURFACE (1 << 28)
@@ -1485,6 +1524,12 @@ int icpk_tsdf_mesh_host(const icpk_tsdf_params *params, int32_t min_weight, cons
                         const float *intensity, int64_t cap_vertices, int64_t cap_triangles, float *x, float *y, float *z,
                         float *nx, float *ny, float *nz, float *intensity_out, int32_t *voxel_index, uint8_t *edge,
                         int32_t *triangles, int64_t counts[3]);
+int icpk_tsdf_shift(icpk_ctx *ctx, const int32_t s[3]);
+int icpk_tsdf_extract_leaving(icpk_ctx *ctx, int32_t min_weight, const int32_t s[3], int32_t *n_points,
+                              int32_t *n_no_normal);
+int icpk_tsdf_get_params(icpk_ctx *ctx, icpk_tsdf_params *out, int64_t total[3]);
+int icpk_tsdf_get_box(icpk_ctx *ctx, const int32_t lo[3], const int32_t hi[3], float *tsdf, uint16_t *weight,
+                      float *intensity);
 
 /* ---- K22: smoothing a depth frame before its vertex and normal maps are made -----------------------------------------
  * KinectFusion's first stage: a bilateral filter in front of the cloud (and the cross-product normals) that tracking
