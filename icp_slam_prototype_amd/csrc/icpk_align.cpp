@@ -117,9 +117,13 @@ void pack_pose(float T_out[16], int solve, const float Trot[9], const float offs
   T_out[15] = 1.f;
 }
 
-// every alignment starts from the source as set / committed, with no seeds or query order of an earlier pose
-int begin_alignment(icpk_ctx* ctx) {
-  const int rc = copy_src0_to_src(ctx);
+// every alignment starts from the source as set / committed, with no seeds or query order of an earlier pose.
+// rec_loop: a device loop of grid sweeps follows -- it neither reads nor writes the working planes (the set-up takes the
+// queries from the committed source, the sweeps keep records, the unpack rewrites every point), so a copy that
+// copy_src0_to_src has deferred stays deferred; every other loop gets its planes here
+int begin_alignment(icpk_ctx* ctx, bool rec_loop) {
+  int rc = copy_src0_to_src(ctx);
+  if (!rc && !(rec_loop && ctx->src.n > 0)) rc = ensure_unpacked(ctx);
   if (rc) return rc;
   ctx->src_pristine = false;  // (the loop moves the working copy)
   ctx->have_seed = false;     // matches of an earlier alignment belong to a different source pose
@@ -140,8 +144,8 @@ int loop_nsum(const icpk_params* p) {
 }
 
 // initial LoopState -> device (on ctx->stream), stop flags armed
-// defer: the launch is left to the first set-up launch that can carry it (build_grid_and_order) or, failing that, to
-// flush_loop_init right before the first kernel that reads the state
+// defer: the launch is left to the first set-up launch that can carry it (build_grid_and_order, enqueue_cell_order)
+// or, failing that, to flush_loop_init right before the first kernel that reads the state
 int device_loop_begin(icpk_ctx* ctx, const icpk_params* p, bool throttled, bool mirror, bool defer) {
   LoopInitArgs a{};
   a.st = ctx->st_dev;
@@ -151,6 +155,7 @@ int device_loop_begin(icpk_ctx* ctx, const icpk_params* p, bool throttled, bool 
     a.progress = ctx->progress_dev;
     a.mirror = mirror ? ctx->st_mirror_dev : nullptr;
   }
+  a.throttled = throttled;  // (only then does a step store its progress words: nothing reads them otherwise)
   a.max_iterations = p->max_iterations;
   a.min_pairs = p->min_pairs;
   a.solve = p->solve;
@@ -367,7 +372,7 @@ int icpk_align_query_sharded(icpk_ctx* ctx, const icpk_params* p, float T_out[16
   reset_outputs(T_out, stats);
   icpk_params q = *p;
   q.nn_mode = ICPK_NN_GRID;
-  rc = begin_alignment(ctx);
+  rc = begin_alignment(ctx, false);  // (this loop unpacks into the planes itself)
   if (rc) return rc;
   const LoopGuard guard{ctx};
   rc = device_loop_begin(ctx, &q, false);
@@ -429,12 +434,12 @@ int icpk_align(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats*
     return rc;
   }
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
-  rc = begin_alignment(ctx);
+  const bool device_loop = !p->host_loop && !ctx->log_fn && p->max_iterations <= LOOP_MAX_ITER;  // (and a source that is not empty)
+  rc = begin_alignment(ctx, device_loop && p->nn_mode == ICPK_NN_GRID);
   if (rc) return rc;
   const bool robust = ctx->robust_on;
   if (robust && ctx->src.n > 0 && (rc = ensure_robust(ctx, ctx->src.n))) return rc;
-  if (!p->host_loop && !ctx->log_fn && ctx->src.n > 0 && p->max_iterations <= LOOP_MAX_ITER)
-    return align_device_loop(ctx, p, T_out, stats);
+  if (device_loop && ctx->src.n > 0) return align_device_loop(ctx, p, T_out, stats);
 
   Profiler pf(ctx, p);
   const bool p2l = p->solve == ICPK_SOLVE_POINT_TO_PLANE;

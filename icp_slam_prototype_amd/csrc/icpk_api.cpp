@@ -167,7 +167,7 @@ int set_source_impl(icpk_ctx* ctx, const float* x, const float* y, const float* 
   ctx->have_seed = false;
   ctx->have_qperm = false;
   // (no second wait: the host buffers have been consumed by upload_cloud; the device-side copy of the
-  // working source is stream-ordered before anything that uses it)
+  // working source, made when something first reads it, is stream-ordered like any other)
   return copy_src0_to_src(ctx);
 }
 
@@ -179,16 +179,29 @@ int copy_src0_to_src(icpk_ctx* ctx) {
   if (ctx->src_pristine && ctx->tune.pristine_skip && ctx->src.n == ctx->src0.n) return ICPK_OK;
   int rc = ensure_cloud(ctx, ctx->src, ctx->src0.n);
   if (rc) return rc;
+  ctx->src_pristine = true;
+  // The copy itself waits for a reader (ensure_unpacked): the next alignment's device loop of grid sweeps is none, so a
+  // tracker that sets a source and aligns never pays it.  ICPK_PRISTINE_SKIP=0 copies here and now, as ever.
+  ctx->src_deferred = ctx->tune.pristine_skip;
+  return ctx->src_deferred ? ICPK_OK : copy_source_planes(ctx, false);
+}
+
+int copy_source_planes(icpk_ctx* ctx, bool tail_only) {
   const Cloud &a = ctx->src0, &b = ctx->src;
-  if (a.cap == b.cap) {
+  const int m = round_up(a.n < 1 ? 1 : a.n, NN_TILE);
+  if (tail_only) {  // the padding behind the n points an unpack is about to rewrite
+    if (m == a.n) return ICPK_OK;
+    const size_t bytes = (size_t)(m - a.n) * sizeof(float);
+    ICPK_HIP(ctx, hipMemcpyAsync(b.x() + a.n, a.x() + a.n, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    ICPK_HIP(ctx, hipMemcpyAsync(b.y() + a.n, a.y() + a.n, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    ICPK_HIP(ctx, hipMemcpyAsync(b.z() + a.n, a.z() + a.n, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  } else if (a.cap == b.cap) {
     ICPK_HIP(ctx, hipMemcpyAsync(b.base, a.base, (size_t)3 * a.cap * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   } else {  // capacities can differ after a shrink: copy plane by plane, padded part included
-    const int m = round_up(a.n < 1 ? 1 : a.n, NN_TILE);
     ICPK_HIP(ctx, hipMemcpyAsync(b.x(), a.x(), (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     ICPK_HIP(ctx, hipMemcpyAsync(b.y(), a.y(), (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     ICPK_HIP(ctx, hipMemcpyAsync(b.z(), a.z(), (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   }
-  ctx->src_pristine = true;
   return ICPK_OK;
 }
 
@@ -329,7 +342,7 @@ int icpk_reset_source(icpk_ctx* ctx) {
   ctx->have_assoc = false;
   ctx->have_seed = false;
   ctx->have_qperm = false;
-  return ICPK_OK;  // device-side copy, stream-ordered: no host wait
+  return ICPK_OK;  // (the device-side copy is left to whoever reads the working source first: no host wait)
 }
 
 int icpk_commit_source(icpk_ctx* ctx) {

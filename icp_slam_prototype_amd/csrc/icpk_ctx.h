@@ -251,6 +251,10 @@ struct icpk_ctx {
   bool have_pix_seed = false;          // they describe the clouds the context holds now
   int pix_rows = 0, pix_cols = 0;
   bool src_pristine = false;     // the working source equals the committed one (see copy_src0_to_src)
+  // the working source logically equals the committed one but its planes have not been written (copy_src0_to_src
+  // defers the copy): ensure_unpacked brings them up to date for whoever reads them; a device loop of grid sweeps never
+  // does (its set-up takes the queries from src0, see query_cloud, and its unpack rewrites every entry)
+  bool src_deferred = false;
   const int* stop = nullptr;     // &st_dev->done while a device loop is being enqueued, else null
   LoopState* st_active = nullptr;  // st_dev while a device loop is being enqueued, else null
   icpk::PinnedBuf<float> stage_t, stage_s;  // staging of host clouds (frame-batch slots): target, source
@@ -521,7 +525,9 @@ int set_target_impl(icpk_ctx* ctx, const float* x, const float* y, const float* 
                     bool sync = true);
 int set_source_impl(icpk_ctx* ctx, const float* x, const float* y, const float* z, int32_t n, hipMemcpyKind k,
                     bool sync = true);
-int copy_src0_to_src(icpk_ctx* ctx);  // the working source := the committed one
+int copy_src0_to_src(icpk_ctx* ctx);  // the working source := the committed one (its planes on demand: src_deferred)
+// the planes of the committed source into the working one, now (tail_only: just the padding behind the n points)
+int copy_source_planes(icpk_ctx* ctx, bool tail_only);
 // the target planes hold tgt.n points that replace the previous target: its +inf padding up to the next NN_TILE multiple
 int pad_target(icpk_ctx* ctx);
 // the target has changed (replaced, or moved with keep_normals = true): drop everything derived from it
@@ -543,6 +549,8 @@ int index_target(icpk_ctx* ctx, GridView* out);
 int index_aux(icpk_ctx* ctx, const Cloud& c, GridView* out);
 // the working source planes hold the cloud icpk_get_source would return (a device loop may leave them to be unpacked)
 int ensure_unpacked(icpk_ctx* ctx);
+// where the grid set-up reads the query coordinates: the committed source while the working copy is deferred
+inline const icpk::Cloud& query_cloud(const icpk_ctx* ctx) { return ctx->src_deferred ? ctx->src0 : ctx->src; }
 int flush_loop_init(icpk_ctx* ctx);
 NnArgs base_nn_args(const icpk_ctx* ctx);
 int prepare_sorted_sweep(icpk_ctx* ctx, int nn_mode, NnArgs& a, NnBoxes& bx, int& recheck);

@@ -190,7 +190,7 @@ struct LoopState {
   float mse;                 // icp.cpp:622-638 of the latest sweep
   int epoch;                 // tag of this alignment in the progress words (see below)
   // host-visible (pinned, mapped) progress words or nullptr: [0] = loop steps executed, [1] = loop has
-  // exited.  With a loop that may exit early (threshold mode) the host enqueues only a couple of
+  // exited, written only while `throttled`.  With a loop that may exit early (threshold mode) the host enqueues only a couple of
   // iterations ahead of them instead of all max_iterations: every launch after the exit is a no-op that
   // still costs its dispatch (~3 us each: 100 us for the reference's 16 / 1e-4 setting leaving after 5).
   // Both words carry `epoch` ([0] = epoch << 10 | steps, [1] = epoch << 2 | done << 1 | exited), so that words still
@@ -198,7 +198,8 @@ struct LoopState {
   int* progress;
   // host-visible (pinned, mapped) copy of the OUTPUT fields of this struct or nullptr: the step that ends the loop
   // writes them there and then sets progress[2] = epoch << 1 | 1 with a system-scope release, so the host has the
-  // result the moment the loop ends -- no copy kernel, no stream wait (trace entries go there as they are made)
+  // result the moment the loop ends -- no copy kernel, no stream wait (the trace of the completed iterations goes
+  // there with them, copied from this state: an iteration stores nothing in host memory)
   LoopState* mirror;
   Rt rt;                     // transform to apply in this iteration
   double Rd[9];              // rt.R widened (exact) by the step: the sweeps' fused K3 takes the rotation as float64 scalars
@@ -208,6 +209,7 @@ struct LoopState {
   // parameters
   int max_iterations, min_pairs, solve, fixed_iterations;
   float threshold;
+  int throttled;             // the host enqueues this loop a few iterations ahead and watches progress[0], [1]
   float last_rotation[9], last_translation[3];
   // per-iteration record (icpk_get_trace)
   float trace_R[LOOP_MAX_ITER * 9];
@@ -474,6 +476,7 @@ struct LoopInitArgs {
   int max_iterations, min_pairs, solve, fixed_iterations;
   float threshold;
   int epoch;
+  int throttled;  // LoopState::throttled
   float last_rotation[9], last_translation[3];
 };
 struct BoundsArgs {
@@ -584,6 +587,9 @@ void launch_loop_init(const LoopInitArgs& a, hipStream_t s);   // kernels_loop.h
 void launch_grid_bounds(const BoundsArgs& a, hipStream_t s);
 void launch_grid_info(const InfoArgs& a, hipStream_t s);
 void launch_grid_qslot(const QslotArgs& a, hipStream_t s);
+// the same step with the initial LoopState of the alignment being enqueued on the side (workgroup 0); never recorded:
+// false, and nothing launched, while a recorder is installed or when the step has nothing to do
+bool launch_grid_qslot_init(const QslotArgs& a, const LoopInitArgs& init, hipStream_t s);
 void launch_grid_scan(const ScanArgs& a, hipStream_t s);  // count[] is left zero; bsum: GRID_SCAN_BLOCKS ints
 void launch_grid_tscatter(const TscatterArgs& a, hipStream_t s);
 // qm4 != nullptr: also the scan-order queries and every query's seed point and seed key

@@ -13,6 +13,9 @@ namespace icpk {
 int ensure_cloud(icpk_ctx* ctx, Cloud& c, int n) {
   if (ctx && (&c == &ctx->src0 || &c == &ctx->src)) ctx->src_pristine = false;  // (about to be resized or rewritten)
   if (ctx && &c == &ctx->src) ctx->rec_pending = false;  // (whatever was to be unpacked into it is superseded)
+  // (as is a copy of the committed source still owed to it; and one owed FROM a source that is being replaced is dropped:
+  // every such call goes on to write the working source too, or to copy_src0_to_src)
+  if (ctx && (&c == &ctx->src0 || &c == &ctx->src)) ctx->src_deferred = false;
   if (ctx && &c == &ctx->src0) ctx->have_src_normals = false;  // (they describe the uploaded source that is being replaced)
   if (ctx && &c == &ctx->src0) fpfh_dropped(ctx, 0);           // (as K16's descriptors and matches do)
   if (ctx && &c == &ctx->src0) ctx->have_src_colors = false;   // (as K17's intensities do)
@@ -191,7 +194,8 @@ int index_aux(icpk_ctx* ctx, const Cloud& c, GridView* out) {
 // the scatter of the working source into scan order (qm4 != nullptr: with the scan-order queries and their seeds; pix: the
 // seeds come from the pixel maps)
 static QscatterArgs query_scatter_args(icpk_ctx* ctx, const int* qcell, const int* qslot, float4* qm4, bool pix) {
-  return QscatterArgs{qcell,        qslot,        ctx->qstart,  ctx->qperm, ctx->src.x(), ctx->src.y(), ctx->src.z(),
+  const Cloud& q = query_cloud(ctx);
+  return QscatterArgs{qcell,        qslot,        ctx->qstart,  ctx->qperm, q.x(),        q.y(),        q.z(),
                       ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), qm4,        ctx->sp_in,   ctx->seed_m,  ctx->src.n,
                       0,            pix ? ctx->pix_src.get() : nullptr,     pix ? ctx->pix_tidx.get() : nullptr,
                       ctx->pix_rows, ctx->pix_cols};
@@ -215,8 +219,14 @@ static int enqueue_cell_order(icpk_ctx* ctx, bool with_points) {
   if (!ident) {
     // (locality only: the coarser table, xdiv times fewer counts to scan)
     ctx->qcount_dirty = true;
-    launch_grid_qslot(QslotArgs{ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->grid.info, ctx->qcount, qcell, qslot, nq, 1},
-                      ctx->stream);
+    const Cloud& q = query_cloud(ctx);
+    const QslotArgs qa{q.x(), q.y(), q.z(), ctx->grid.info, ctx->qcount, qcell, qslot, nq, 1};
+    // (a new source pose against an indexed target: this is the alignment's first launch, and it carries the pending
+    // initial LoopState as grid_begin_kernel does for a fresh pair)
+    if (ctx->init_pending && launch_grid_qslot_init(qa, ctx->pending_init, ctx->stream))
+      ctx->init_pending = false;
+    else
+      launch_grid_qslot(qa, ctx->stream);
     launch_grid_scan(ScanArgs{ctx->qcount, ctx->qstart, ctx->scan_bsum, ctx->grid.info, 1, 0}, ctx->stream);
   }
   launch_grid_qscatter(query_scatter_args(ctx, ident ? nullptr : qcell, qslot, with_points ? ctx->qm4.get() : nullptr, pix),
@@ -233,7 +243,13 @@ static int ensure_query_points(icpk_ctx* ctx, int nq);
 // icpk_get_associations, icpk_commit_source, icpk_transform_source, icpk_nn, icpk_reduce ...) and dropped when the
 // working source is overwritten first (the next alignment, a new source): a tracker that only wants the pose never
 // pays the launch.  ICPK_LAZY_UNPACK=0: unpack at the end of every loop.
+// It is also the one place that makes a deferred copy of the committed source (src_deferred): all of it when nothing has
+// moved the source since, only the padding when the unpack is about to write every point.
 int ensure_unpacked(icpk_ctx* ctx) {
+  if (ctx->src_deferred) {
+    ctx->src_deferred = false;
+    if (int rc = copy_source_planes(ctx, /*tail_only=*/ctx->rec_pending)) return rc;
+  }
   if (!ctx->rec_pending) return ICPK_OK;
   ctx->rec_pending = false;
   launch_grid_unpack(ctx->qm4, ctx->rec, ctx->src.n, ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->best, ctx->stream);
@@ -296,7 +312,8 @@ static int build_grid_and_order(icpk_ctx* ctx) {
   ctx->qcount_dirty = ctx->qcount2_dirty = true;
   SetupBatchOf<QslotArgs> qb{};
   qb.p[0] = QslotArgs{ctx->tgt.x(), ctx->tgt.y(), ctx->tgt.z(), g.info, ctx->qcount, tcell, tslot, nt, 0};
-  qb.p[1] = QslotArgs{ctx->src.x(), ctx->src.y(), ctx->src.z(), g.info, ctx->qcount2, qcell, qslot, nq, 1};
+  const Cloud& q = query_cloud(ctx);
+  qb.p[1] = QslotArgs{q.x(), q.y(), q.z(), g.info, ctx->qcount2, qcell, qslot, nq, 1};
   // A source that icpk_backproject_pair has just made is in row-major IMAGE order: eight consecutive points are a short
   // run of one image row, as close together as a grid cell's -- the queries are swept in the caller's order and their
   // counting sort is left out (-3.5 us per 92k-point pair, -14 us at 306k; ICPK_IMAGE_ORDER=0: sort them all the same).
@@ -407,9 +424,11 @@ int prepare_sorted_sweep(icpk_ctx* ctx, int nn_mode, NnArgs& a, NnBoxes& bx, int
   if (nn_mode == ICPK_NN_GRID) {
     // inside a device loop the grid sweeps keep qm4 / the seed points current themselves;
     // anywhere else the source may have been moved by other kernels: gather afresh
-    if (!(ctx->st_active && ctx->grid_chain) && !points_written)
-      launch_grid_query_points(ctx->src.x(), ctx->src.y(), ctx->src.z(), ctx->qperm, nq, ctx->seed_m, bx.ox, bx.oy,
-                               bx.oz, ctx->qm4, ctx->sp_in, ctx->stream);
+    if (!(ctx->st_active && ctx->grid_chain) && !points_written) {
+      const Cloud& q = query_cloud(ctx);
+      launch_grid_query_points(q.x(), q.y(), q.z(), ctx->qperm, nq, ctx->seed_m, bx.ox, bx.oy, bx.oz, ctx->qm4, ctx->sp_in,
+                               ctx->stream);
+    }
   }
   ICPK_HIP(ctx, hipGetLastError());
   return ICPK_OK;

@@ -185,7 +185,12 @@ __device__ __forceinline__ void grid_qslot_body(const QslotArgs& a, const int bl
   a.cell[i] = c;
   a.slot[i] = atomicAdd(&a.count[c], 1);
 }
-__global__ void grid_qslot_kernel(const QslotArgs a) { grid_qslot_body(a, blockIdx.x); }
+// has_init: the query sort of a new source pose against an indexed target (enqueue_cell_order) is the alignment's
+// first launch; workgroup 0 writes the initial LoopState on the side, as grid_begin_kernel does for a fresh pair
+__global__ void grid_qslot_kernel(const QslotArgs a, const LoopInitArgs li, const int has_init) {
+  if (has_init && blockIdx.x == 0) loop_init_body(li);
+  grid_qslot_body(a, blockIdx.x);
+}
 __global__ void grid_qslot_batch_kernel(const SetupBatchOf<QslotArgs> b) { grid_qslot_body(b.p[blockIdx.y], blockIdx.x); }
 
 // qm4 != nullptr: the first sweep of an alignment without seeds -- the queries in scan order (x, y, z, index),
@@ -401,7 +406,12 @@ void launch_grid_tscatter_batch(const SetupBatchOf<TscatterArgs>& b, int count, 
 
 void launch_grid_qslot(const QslotArgs& a, hipStream_t s) {
   if (a.n <= 0 || record_setup_step(SK_QSLOT, &SetupCall::qslot, a)) return;
-  hipLaunchKernelGGL(grid_qslot_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(grid_qslot_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a, LoopInitArgs{}, 0);
+}
+bool launch_grid_qslot_init(const QslotArgs& a, const LoopInitArgs& init, hipStream_t s) {
+  if (a.n <= 0 || setup_recorder()) return false;
+  hipLaunchKernelGGL(grid_qslot_kernel, dim3((a.n + 255) / 256), dim3(256), 0, s, a, init, 1);
+  return true;
 }
 void launch_grid_qslot_batch(const SetupBatchOf<QslotArgs>& b, int count, hipStream_t s) {
   const int m = max_n(b, count);

@@ -99,14 +99,15 @@ __device__ void compose_rt(const float Rf[9], const float tf[3], double Tk[12]) 
   for (int k = 0; k < 12; ++k) Tk[k] = Tn[k];
 }
 
-// thread 0, on every way out of a loop step: tell the host (see LoopState::progress).  The words are hints
+// thread 0, on every way out of a loop step: count it and, in a throttled loop, tell the host (see
+// LoopState::progress; nobody looks at the words of a loop that is enqueued whole).  The words are hints
 // that only decide how much the host enqueues -- a stale read costs a no-op launch, never a result -- so
 // the stores are relaxed: no release, which at system scope would write the whole L2 back.
 __device__ __forceinline__ void publish_progress(LoopState* __restrict__ st) {
   const int k = st->steps + 1;
   st->steps = k;
   int* pr = st->progress;
-  if (pr) {
+  if (pr && st->throttled) {
     const int e = st->epoch;
     __hip_atomic_store(pr + 1, (e << 2) | ((st->done != 0) << 1) | ((st->done | st->stop_after_transform) != 0), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_SYSTEM);
@@ -114,31 +115,47 @@ __device__ __forceinline__ void publish_progress(LoopState* __restrict__ st) {
   }
 }
 
-// thread 0, when the outputs are final (the step that sets `done`, or the statistics-only step behind the last sweep):
-// the host-visible copy (LoopState::mirror), then its ready word with a system-scope release -- once per alignment
+// wave 0, when the outputs are final (the step that sets `done`, or the statistics-only step behind the last sweep):
+// the host-visible copy (LoopState::mirror) with the trace of the completed iterations, then its ready word behind a
+// system-scope release -- once per alignment (the iterations themselves store nothing across the bus).  The trace is
+// spread over the wave's lanes: one lane storing 14 words per iteration one after the other took longer than the
+// per-iteration stores it replaces.  One wave, so that the fence's wait covers every lane's stores.
 __device__ __forceinline__ void publish_result(LoopState* __restrict__ st) {
   LoopState* __restrict__ m = st->mirror;
   if (!m) return;
-  m->done = st->done;
-  m->iterations = st->iterations;
-  m->status = st->status;
-  m->sweeps = st->sweeps;
-  m->pairs = st->pairs;
-  m->mse = st->mse;
-  for (int k = 0; k < 9; ++k) m->Trot[k] = st->Trot[k];
-  for (int k = 0; k < 3; ++k) m->offset[k] = st->offset[k];
-  for (int k = 0; k < 12; ++k) m->Tk[k] = st->Tk[k];
-  __hip_atomic_store(st->progress + 2, (st->epoch << 1) | 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  const int lane = threadIdx.x, it = st->iterations;
+  if (lane == 0) {
+    m->done = st->done;
+    m->iterations = it;
+    m->status = st->status;
+    m->sweeps = st->sweeps;
+    m->pairs = st->pairs;
+    m->mse = st->mse;
+    for (int k = 0; k < 9; ++k) m->Trot[k] = st->Trot[k];
+    for (int k = 0; k < 3; ++k) m->offset[k] = st->offset[k];
+    for (int k = 0; k < 12; ++k) m->Tk[k] = st->Tk[k];
+  }
+  for (int k = lane; k < it; k += 64) {
+    m->trace_pairs[k] = st->trace_pairs[k];
+    m->trace_mse[k] = st->trace_mse[k];
+  }
+  for (int k = lane; k < 9 * it; k += 64) m->trace_R[k] = st->trace_R[k];
+  for (int k = lane; k < 3 * it; k += 64) m->trace_t[k] = st->trace_t[k];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  if (lane == 0) __hip_atomic_store(st->progress + 2, (st->epoch << 1) | 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+
+// what thread 0 of a loop step has decided to tell the host (loop_step_body acts on it)
+enum : int { PUB_RESULT = 1, PUB_PROGRESS = 2 };
 
 // NS == NSUM_W / NP2L_W: the step of a robust loop (K10) -- the sums are weighted, [NS - 2] = W, [NS - 1] = the kept
 // count; min_pairs applies to the kept count, the Kabsch solve takes W for the pair count, the loop test and the trace
 // stay those of the accepted pairs, and every completed iteration leaves a RobustTraceEntry in rtrace
+// returns, in thread 0, what is to be published (PUB_*); 0 in every other thread
 template <int NS, int NACT = NS>
-__device__ __forceinline__ void loop_step_body(const double* __restrict__ partial, const int* __restrict__ pcount,
-                                               int nblocks, LoopState* __restrict__ st, int stats_only,
-                                               const RobustSel* __restrict__ sel = nullptr,
-                                               RobustTraceEntry* __restrict__ rtrace = nullptr) {
+__device__ __forceinline__ int loop_step_decide(const double* __restrict__ partial, const int* __restrict__ pcount,
+                                                int nblocks, LoopState* __restrict__ st, int stats_only,
+                                                const RobustSel* __restrict__ sel, RobustTraceEntry* __restrict__ rtrace) {
   constexpr bool ROBUST = NS == NSUM_W || NS == NP2L_W;
   constexpr bool P2L = NS == NP2L || NS == NP2L_W;
   // the control words are fetched together with the partial sums (independent loads in
@@ -161,19 +178,12 @@ __device__ __forceinline__ void loop_step_body(const double* __restrict__ partia
     tree_stage2<NS, NACT>(partial, pcount, nblocks, sums, npairs);  // sums [NACT..NS) read as 0
   }
   STEP_STAMP(i, 1);
-  if (done) {
-    if (threadIdx.x == 0) publish_progress(st);
-    return;
-  }
+  if (threadIdx.x != 0) return 0;
+  if (done) return PUB_PROGRESS;
   if (stop_after) {  // the fallback motion has been applied by the previous transform
-    if (threadIdx.x == 0) {
-      st->done = 1;
-      publish_result(st);
-      publish_progress(st);
-    }
-    return;
+    st->done = 1;
+    return PUB_RESULT | PUB_PROGRESS;
   }
-  if (threadIdx.x != 0) return;
 
   // statistics of the sweep just reduced (icp.cpp:622-638 from the double sum)
   float mse = 0.f;
@@ -183,16 +193,11 @@ __device__ __forceinline__ void loop_step_body(const double* __restrict__ partia
   }
   st->pairs = npairs;
   st->mse = mse;
-  if (stats_only) {
-    publish_result(st);
-    return;
-  }
+  if (stats_only) return PUB_RESULT;
 
   if (!((fixed || mse > threshold) && i < max_iterations)) {  // icp.cpp:155
     st->done = 1;
-    publish_result(st);
-    publish_progress(st);
-    return;
+    return PUB_RESULT | PUB_PROGRESS;
   }
   const long long kept = ROBUST ? (long long)sums[NS - 1] : npairs;
   if (kept < min_pairs) {  // icp.cpp:163-182
@@ -204,16 +209,10 @@ __device__ __forceinline__ void loop_step_body(const double* __restrict__ partia
     for (int k = 0; k < 9; ++k) st->Rd[k] = (double)st->rt.R[k];
     st->status = 1;  // ICPK_W_TOO_FEW_PAIRS
     st->stop_after_transform = 1;
-    publish_progress(st);
-    return;
+    return PUB_PROGRESS;
   }
   st->trace_pairs[i] = (int)npairs;
   st->trace_mse[i] = mse;
-  LoopState* __restrict__ mir = st->mirror;
-  if (mir) {
-    mir->trace_pairs[i] = (int)npairs;
-    mir->trace_mse[i] = mse;
-  }
   if constexpr (ROBUST) {
     RobustTraceEntry e;
     e.kept = (int)kept;
@@ -229,9 +228,7 @@ __device__ __forceinline__ void loop_step_body(const double* __restrict__ partia
     if (!solve_p2l(sums, Rd, td)) {
       st->status = 2;  // ICPK_W_DEGENERATE
       st->done = 1;
-      publish_result(st);
-      publish_progress(st);
-      return;
+      return PUB_RESULT | PUB_PROGRESS;
     }
     for (int k = 0; k < 9; ++k) Rrec[k] = (float)Rd[k];
     for (int k = 0; k < 3; ++k) trec[k] = (float)td[k];
@@ -277,13 +274,21 @@ __device__ __forceinline__ void loop_step_body(const double* __restrict__ partia
   for (int k = 0; k < 9; ++k) st->Rd[k] = (double)st->rt.R[k];
   for (int k = 0; k < 9; ++k) st->trace_R[9 * i + k] = Rrec[k];
   for (int k = 0; k < 3; ++k) st->trace_t[3 * i + k] = trec[k];
-  if (mir) {
-    for (int k = 0; k < 9; ++k) mir->trace_R[9 * i + k] = Rrec[k];
-    for (int k = 0; k < 3; ++k) mir->trace_t[3 * i + k] = trec[k];
-  }
   st->iterations = i + 1;  // icp.cpp:257 (the sweep that follows is already enqueued)
-  publish_progress(st);
   STEP_STAMP(i, 4);
+  return PUB_PROGRESS;
+}
+
+template <int NS, int NACT = NS>
+__device__ __forceinline__ void loop_step_body(const double* __restrict__ partial, const int* __restrict__ pcount,
+                                               int nblocks, LoopState* __restrict__ st, int stats_only,
+                                               const RobustSel* __restrict__ sel = nullptr,
+                                               RobustTraceEntry* __restrict__ rtrace = nullptr) {
+  const int mine = loop_step_decide<NS, NACT>(partial, pcount, nblocks, st, stats_only, sel, rtrace);
+  if (threadIdx.x >= 64) return;
+  const int what = __builtin_amdgcn_readfirstlane(mine);  // (thread 0's, for its wave)
+  if (what & PUB_RESULT) publish_result(st);
+  if (threadIdx.x == 0 && (what & PUB_PROGRESS)) publish_progress(st);
 }
 
 template <int NS, int NACT = NS>

@@ -1,5 +1,5 @@
 // loop_init.h -- the initial LoopState, shared by kernels_loop.hip (loop_init_kernel) and kernels_grid.hip
-// (grid_begin_kernel: the first launch of a fresh frame pair's set-up does it on the side).
+// (grid_begin_kernel, grid_qslot_kernel: the first launch of an alignment's set-up does it on the side).
 #pragma once
 #include <cstddef>
 
@@ -23,6 +23,7 @@ __device__ __forceinline__ void loop_init_body(const LoopInitArgs& a) {
   st->solve = a.solve;
   st->fixed_iterations = a.fixed_iterations;
   st->threshold = a.threshold;
+  st->throttled = a.throttled;
   st->epoch = a.epoch;
   st->progress = a.progress;
   st->mirror = a.mirror;
