@@ -91,6 +91,8 @@ SYMBOLS = [
     "icpk_tsdf_shift", "icpk_tsdf_extract_leaving", "icpk_tsdf_get_params", "icpk_tsdf_get_box",
     "icpk_default_bilateral_params", "icpk_bilateral_depth_image", "icpk_backproject_smoothed", "icpk_bilateral_tables",
     "icpk_bilateral_host",
+    "icpk_default_pyramid_params", "icpk_depth_pyramid_build", "icpk_depth_pyramid_shape", "icpk_depth_pyramid_get",
+    "icpk_depth_pyramid_backproject", "icpk_depth_pyramid_host",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -202,6 +204,14 @@ BILATERAL_MAX_RANGE = 4096  # ... and the largest K: entries of the range table
 class BilateralParams(C.Structure):
     """icpk_bilateral_params"""
     _fields_ = [("radius", C.c_int32), ("sigma_space", C.c_float), ("sigma_range", C.c_float), ("range_cutoff", C.c_int32)]
+
+
+PYRAMID_MAX_LEVELS = 8  # icpk_pyramid_params.levels
+
+
+class PyramidParams(C.Structure):
+    """icpk_pyramid_params"""
+    _fields_ = [("levels", C.c_int32), ("range_cutoff", C.c_int32)]
 
 
 class FrameJob(C.Structure):
@@ -447,6 +457,14 @@ def load():
                                               C.c_int32, bp]
     lib.icpk_bilateral_tables.argtypes = [bp, u16, u16, ip]
     lib.icpk_bilateral_host.argtypes = [bp, u16, C.c_int32, C.c_int32, u16]
+    pp = C.POINTER(PyramidParams)
+    lib.icpk_default_pyramid_params.argtypes = [pp]
+    lib.icpk_default_pyramid_params.restype = None
+    lib.icpk_depth_pyramid_build.argtypes = [C.c_void_p, u16, C.c_int32, C.c_int32, pp, bp]
+    lib.icpk_depth_pyramid_shape.argtypes = [C.c_void_p, C.c_int32, ip, ip]
+    lib.icpk_depth_pyramid_get.argtypes = [C.c_void_p, C.c_int32, u16]
+    lib.icpk_depth_pyramid_backproject.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float, fp, C.c_int32, C.c_int32]
+    lib.icpk_depth_pyramid_host.argtypes = [pp, u16, C.c_int32, C.c_int32, C.c_int32, u16]
     _lib = lib
     return lib
 

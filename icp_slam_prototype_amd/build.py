@@ -18,7 +18,8 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_filter.cpp", "kernels_filter.hip", "icpk_gicp.cpp", "kernels_gicp.hip",
            "icpk_score.cpp", "kernels_score.hip", "icpk_fpfh.cpp", "kernels_fpfh.hip", "icpk_global.cpp",
            "icpk_color.cpp", "kernels_color.hip", "icpk_posegraph.cpp", "kernels_posegraph.hip",
-           "icpk_tsdf.cpp", "kernels_tsdf.hip", "icpk_bilateral.cpp", "kernels_bilateral.hip"]
+           "icpk_tsdf.cpp", "kernels_tsdf.hip", "icpk_bilateral.cpp", "kernels_bilateral.hip",
+           "icpk_pyramid.cpp", "kernels_pyramid.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -434,6 +435,50 @@ def build_bilateral_host_sanitized(force=False):
     return BILATERAL_HOST_SANITIZED
 
 
+PYRAMID_TEST = os.path.join(LIBDIR, "test_pyramid")
+
+
+def build_pyramid_test(force=False):
+    """Host-only C++ program over icp::Engine::buildDepthPyramid / depthPyramidLevel / backprojectPyramidLevel
+    (icp_align.hpp, K24) (g++, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_pyramid.cpp")
+    hdr = os.path.join(HERE, "include", "icp_align.hpp")
+    build()
+    newest = max(os.path.getmtime(p) for p in (src, hdr, LIB))
+    if not force and os.path.exists(PYRAMID_TEST) and os.path.getmtime(PYRAMID_TEST) >= newest:
+        return PYRAMID_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", PYRAMID_TEST])
+    return PYRAMID_TEST
+
+
+PYRAMID_HOST_SANITIZED = os.path.join(LIBDIR, "pyramid_host_sanitized")
+
+
+def build_pyramid_host_sanitized(force=False):
+    """DIAGNOSTIC, not part of build(): tests/cpp/pyramid_host_main.cpp (its own main, no GPU) with icpk_pyramid.cpp --
+    and so csrc/pyramid_rule.h -- compiled under -fsanitize=address,undefined on the host side.  icpk_pyramid.cpp is
+    host only and refers to nothing else of the library, so the program does not link it.  Run the program it returns
+    directly."""
+    src = os.path.join(ROOT, "tests", "cpp", "pyramid_host_main.cpp")
+    deps = [src, os.path.join(CSRC, "icpk_pyramid.cpp"), os.path.join(CSRC, "pyramid_rule.h"),
+            os.path.join(ROOT, "include", "icpk.h")]
+    os.makedirs(LIBDIR, exist_ok=True)
+    if not force and os.path.exists(PYRAMID_HOST_SANITIZED) and \
+            os.path.getmtime(PYRAMID_HOST_SANITIZED) >= max(os.path.getmtime(p) for p in deps):
+        return PYRAMID_HOST_SANITIZED
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-omit-frame-pointer", "-g"]
+    objs = []
+    for path, name in ((os.path.join(CSRC, "icpk_pyramid.cpp"), "icpk_pyramid_sanitized.o"), (src, "pyramid_host_main.o")):
+        objs.append(os.path.join(LIBDIR, name))
+        subprocess.check_call([hipcc] + FLAGS + san + ["-x", "hip", "-c", path, "-o", objs[-1]])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-fsanitize=address,undefined"] + objs +
+                          ["-o", PYRAMID_HOST_SANITIZED])
+    return PYRAMID_HOST_SANITIZED
+
+
 THREADS_TEST = os.path.join(LIBDIR, "test_threads")
 
 
@@ -522,4 +567,5 @@ if __name__ == "__main__":
     print(build_tsdf_mesh_test(force="--force" in sys.argv))
     print(build_tsdf_shift_test(force="--force" in sys.argv))
     print(build_bilateral_test(force="--force" in sys.argv))
+    print(build_pyramid_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

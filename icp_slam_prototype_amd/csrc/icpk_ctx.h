@@ -453,6 +453,13 @@ struct icpk_ctx {
   icpk_log_fn log_fn = nullptr;
   void* log_user = nullptr;
   std::chrono::steady_clock::time_point log_last;
+  // K24: the depth pyramid of the last icpk_depth_pyramid_build, every level in this one buffer (level l at pyr_off[l]),
+  // resident until the next build.  (Kept behind every older member: the code that does not use the pyramid is compiled
+  // against the offsets it had before.)
+  icpk::DevBuf<uint16_t> pyr;
+  int pyr_levels = 0;  // 0: no pyramid yet
+  int pyr_rows[ICPK_PYRAMID_MAX_LEVELS] = {0}, pyr_cols[ICPK_PYRAMID_MAX_LEVELS] = {0};
+  size_t pyr_off[ICPK_PYRAMID_MAX_LEVELS] = {0};
 };
 
 #define ICPK_HIP(ctx, call)                                                                      \

@@ -114,22 +114,24 @@ static int ensure_bilateral_tables(icpk_ctx* ctx, const icpk_bilateral_params& p
 
 static int backproject_impl(icpk_ctx* ctx, const uint16_t* depth, int32_t rows, int32_t cols, float fx, float cx,
                             const float offset[3], int32_t which, int normals_mode /* <0: none */,
-                            const DepthFilter* flt = nullptr, const icpk_bilateral_params* bil = nullptr /* checked */) {
-  if (!ctx || !depth || rows <= 0 || cols <= 0 || (which != 0 && which != 1) || (int64_t)rows * cols > (1 << 28) ||
+                            const DepthFilter* flt = nullptr, const icpk_bilateral_params* bil = nullptr /* checked */,
+                            const uint16_t* dev_image = nullptr /* K24: an image on the device in place of `depth` */) {
+  if (!ctx || (!depth && !dev_image) || rows <= 0 || cols <= 0 || (which != 0 && which != 1) || (int64_t)rows * cols > (1 << 28) ||
       normals_mode > ICPK_NORMALS_REFERENCE)
     return ICPK_E_ARG;
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
   const int npix = rows * cols;
   const int nblocks = (npix + 1023) / 1024;
-  int rc = ensure_depth_buffers(ctx, npix, nblocks + 2);
+  int rc = ensure_depth_buffers(ctx, dev_image ? 0 : npix, nblocks + 2);
   if (rc) return rc;
   Cloud& c = which == 0 ? ctx->src0 : ctx->tgt;
   rc = ensure_cloud(ctx, c, npix);  // worst case: every pixel valid
   if (rc) return rc;
   if (bil && (rc = ensure_bilateral_tables(ctx, *bil))) return rc;
   ctx->frame_slot = -1;  // (the image buffers are shared with icpk_backproject_pair's resident frame)
-  ICPK_HIP(ctx, hipMemcpyAsync(ctx->depth_dev, depth, (size_t)npix * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
-  const uint16_t* dimg = ctx->depth_dev;
+  if (!dev_image)
+    ICPK_HIP(ctx, hipMemcpyAsync(ctx->depth_dev, depth, (size_t)npix * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+  const uint16_t* dimg = dev_image ? dev_image : ctx->depth_dev.get();
   if (bil) {  // K22: the cloud (and its normals) come from the smoothed frame
     launch_depth_bilateral(ctx->depth_dev, ctx->depth_flt, rows, cols, bil->radius, ctx->bil_K, ctx->bil_tables, ctx->stream);
     dimg = ctx->depth_flt;
@@ -367,6 +369,98 @@ int icpk_backproject_smoothed(icpk_ctx* ctx, const uint16_t* depth, int32_t rows
   const int rc = check_bilateral(ctx, params, &p);
   if (rc) return rc;
   return backproject_impl(ctx, depth, rows, cols, fx, cx, offset, which, normals_mode < 0 ? -1 : normals_mode, nullptr, &p);
+}
+
+// ---- K24: the depth pyramid (include/icpk.h, THE PYRAMID RULE; its host-only half is icpk_pyramid.cpp) ----
+int icpk_depth_pyramid_build(icpk_ctx* ctx, const uint16_t* depth, int32_t rows, int32_t cols,
+                             const icpk_pyramid_params* params, const icpk_bilateral_params* smooth) {
+  if (!ctx || !depth || rows <= 0 || cols <= 0 || (int64_t)rows * cols > (1 << 28)) return ICPK_E_ARG;
+  icpk_pyramid_params p;
+  if (params)
+    p = *params;
+  else
+    icpk_default_pyramid_params(&p);
+  if (p.levels < 1 || p.levels > ICPK_PYRAMID_MAX_LEVELS || p.range_cutoff < 1 || p.range_cutoff > 65536)
+    return fail(ctx, ICPK_E_ARG, "pyramid parameters outside their ranges (see THE PYRAMID RULE)");
+  icpk_bilateral_params bil;
+  int rc = smooth ? check_bilateral(ctx, smooth, &bil) : ICPK_OK;
+  if (rc) return rc;
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  int lr[ICPK_PYRAMID_MAX_LEVELS], lc[ICPK_PYRAMID_MAX_LEVELS];
+  size_t off[ICPK_PYRAMID_MAX_LEVELS], total = 0;
+  for (int l = 0; l < p.levels; ++l) {
+    lr[l] = l ? (lr[l - 1] + 1) / 2 : rows;
+    lc[l] = l ? (lc[l - 1] + 1) / 2 : cols;
+    off[l] = total;
+    total += (size_t)lr[l] * lc[l];
+  }
+  const size_t npix = (size_t)rows * cols;
+  if (smooth) {
+    if ((rc = ensure_depth_buffers(ctx, (int)npix, 0))) return rc;
+    if ((rc = ensure_bilateral_tables(ctx, bil))) return rc;
+  }
+  if (total > ctx->pyr.capacity()) ctx->pyr_levels = 0;  // (the old pyramid goes with its memory)
+  if ((rc = ctx->pyr.reserve(ctx, total))) return rc;
+  ctx->pyr_levels = 0;  // (nothing is resident until this call has enqueued everything)
+  uint16_t* const base = ctx->pyr;
+  if (smooth) {  // K22 writes level 0
+    ctx->frame_slot = -1;  // (the image buffers are shared with icpk_backproject_pair's resident frame)
+    ICPK_HIP(ctx, hipMemcpyAsync(ctx->depth_dev, depth, npix * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+    launch_depth_bilateral(ctx->depth_dev, base, rows, cols, bil.radius, ctx->bil_K, ctx->bil_tables, ctx->stream);
+  } else {
+    ICPK_HIP(ctx, hipMemcpyAsync(base, depth, npix * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+  }
+  // two levels per launch from the deepest level written; a last odd level with the second stage switched off
+  for (int l = 0; l + 1 < p.levels; l += 2)
+    launch_depth_pyramid(base + off[l], lr[l], lc[l], base + off[l + 1], l + 2 < p.levels ? base + off[l + 2] : nullptr,
+                         p.range_cutoff, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller's image has been consumed)
+  for (int l = 0; l < p.levels; ++l) {
+    ctx->pyr_rows[l] = lr[l];
+    ctx->pyr_cols[l] = lc[l];
+    ctx->pyr_off[l] = off[l];
+  }
+  ctx->pyr_levels = p.levels;
+  return ICPK_OK;
+}
+
+// the resident pyramid has this level
+static int check_pyramid_level(icpk_ctx* ctx, int32_t level) {
+  if (!ctx) return ICPK_E_ARG;
+  if (ctx->pyr_levels == 0) return fail(ctx, ICPK_E_NOT_SET, "no depth pyramid (icpk_depth_pyramid_build)");
+  if (level < 0 || level >= ctx->pyr_levels) return fail(ctx, ICPK_E_ARG, "the pyramid has no such level");
+  return ICPK_OK;
+}
+
+int icpk_depth_pyramid_shape(icpk_ctx* ctx, int32_t level, int32_t* rows, int32_t* cols) {
+  const int rc = check_pyramid_level(ctx, level);
+  if (rc) return rc;
+  if (rows) *rows = ctx->pyr_rows[level];
+  if (cols) *cols = ctx->pyr_cols[level];
+  return ICPK_OK;
+}
+
+int icpk_depth_pyramid_get(icpk_ctx* ctx, int32_t level, uint16_t* out) {
+  if (!ctx || !out) return ICPK_E_ARG;
+  const int rc = check_pyramid_level(ctx, level);
+  if (rc) return rc;
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  ICPK_HIP(ctx, hipMemcpyAsync(out, ctx->pyr + ctx->pyr_off[level],
+                               (size_t)ctx->pyr_rows[level] * ctx->pyr_cols[level] * sizeof(uint16_t), hipMemcpyDeviceToHost,
+                               ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_depth_pyramid_backproject(icpk_ctx* ctx, int32_t level, float fx, float cx, const float offset[3], int32_t which,
+                                   int32_t normals_mode) {
+  const int rc = check_pyramid_level(ctx, level);
+  if (rc) return rc;
+  if (normals_mode >= 0 && which != 1) return fail(ctx, ICPK_E_ARG, "normals belong to the target cloud");
+  const float scale = (float)(1 << level);  // (a power of two: both quotients are exact)
+  return backproject_impl(ctx, nullptr, ctx->pyr_rows[level], ctx->pyr_cols[level], fx / scale, cx / scale, offset, which,
+                          normals_mode < 0 ? -1 : normals_mode, nullptr, nullptr, ctx->pyr + ctx->pyr_off[level]);
 }
 
 /* icp.cpp:488-515 on the context's clouds (source = the frame's key points, target = the map's) */

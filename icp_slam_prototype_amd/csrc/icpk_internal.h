@@ -449,7 +449,9 @@ void launch_depth_filter_batch(const DfBatch& b, int count, int rows, int cols, 
 // K22, THE BILATERAL RULE: tables = (2 radius + 1)^2 spatial weights, then K range weights (device; in != out)
 void launch_depth_bilateral(const uint16_t* in, uint16_t* out, int rows, int cols, int radius, int K,
                             const uint16_t* tables, hipStream_t s);
-
+// K24, THE PYRAMID RULE: level l (rows x cols) gives level l + 1 into out1 and, unless out2 is null, level l + 2 into
+// out2, in one launch (device; three different images)
+void launch_depth_pyramid(const uint16_t* in, int rows, int cols, uint16_t* out1, uint16_t* out2, int K, hipStream_t s);
 
 // ---- deferred set-up launches of the frame-batch mode ------------------------------------------------
 // A lock-step group's pairs go through the SAME sequence of small set-up kernels (ingest x 2, loop-state

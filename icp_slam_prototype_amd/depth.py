@@ -6,6 +6,15 @@ averaged across; everything is integer, so the device, the host function and a m
     n = backproject_smoothed(ctx, depth, which=1, normals_mode=binding.NORMALS_CROSS)   # ... or straight to the cloud
     tracker = tsdf.ModelTracker(vol, bilateral=True)                 # smoothed frames are tracked, raw frames fused
 
+A depth pyramid for coarse-to-fine tracking (K24): include/icpk.h, THE PYRAMID RULE.  Level l + 1 is level l at half the
+size, every pixel a range-gated 3 x 3 mean centred on pixel (2 r, 2 c) below, so that level l is the frame seen through
+(fx / 2^l, cx / 2^l); integers again, the same bytes from the device, the host function and numpy.
+
+    shapes = build_pyramid(ctx, depth, pyramid_params(levels=3), smooth=bilateral_params())   # stays on the device
+    half = pyramid_level(ctx, 1)                                     # (rows, cols) uint16 of one level
+    n = backproject_level(ctx, 2, which=0, fx=fx, cx=cx)             # fx, cx: the LEVEL-0 intrinsics
+    tracker = tsdf.ModelTracker(vol, pyramid=(10, 5, 4))             # 4 iterations at level 2, then 5, then 10 at level 0
+
 The functions take the Context as an argument: the class itself gains no method.
 """
 import ctypes as C
@@ -86,3 +95,71 @@ def backproject_smoothed(ctx, depth, which=0, normals_mode=None, fx=468.60, cx=3
         ctx._h, depth.ctypes.data_as(_u16), depth.shape[0], depth.shape[1], fx, cx,
         None if off is None else off.ctypes.data_as(C.POINTER(C.c_float)), int(which),
         -1 if normals_mode is None else int(normals_mode), _ref(params)))
+
+
+def pyramid_params(**kw):
+    """icpk_default_pyramid_params with the given fields replaced: levels, range_cutoff."""
+    p = binding.PyramidParams()
+    binding.load().icpk_default_pyramid_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in ("levels", "range_cutoff"):
+            raise TypeError(f"icpk_pyramid_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def pyramid_shapes(shape, levels):
+    """The (rows, cols) of every level of a pyramid over an image of `shape`: level l + 1 halves level l, rounding up."""
+    out = [(int(shape[0]), int(shape[1]))]
+    for _ in range(1, int(levels)):
+        out.append(((out[-1][0] + 1) // 2, (out[-1][1] + 1) // 2))
+    return out
+
+
+def pyramid_host(depth, level, params=None):
+    """icpk_depth_pyramid_host (host only): level `level` of the pyramid of a (rows, cols) uint16 image."""
+    depth = _image(depth)
+    levels = 3 if params is None else params.levels
+    if 0 <= int(level) < max(levels, 0) <= binding.PYRAMID_MAX_LEVELS:
+        out = np.empty(pyramid_shapes(depth.shape, levels)[int(level)], np.uint16)
+    else:
+        out = np.empty((1, 1), np.uint16)  # (the call is refused before it writes)
+    rc = binding.load().icpk_depth_pyramid_host(_ref(params), depth.ctypes.data_as(_u16), depth.shape[0], depth.shape[1],
+                                                int(level), out.ctypes.data_as(_u16))
+    if rc < 0:
+        raise binding.IcpkError(rc, "icpk_depth_pyramid_host: an empty image, parameters outside their ranges or no such level")
+    return out
+
+
+def build_pyramid(ctx, depth, params=None, smooth=None):
+    """icpk_depth_pyramid_build: the pyramid of the frame on the device, resident until the next build.  smooth: a
+    bilateral_params object -- level 0 is then the frame after K22; None: the frame as given.  Returns the list of the
+    levels' (rows, cols)."""
+    depth = _image(depth)
+    ctx._chk(ctx._lib.icpk_depth_pyramid_build(ctx._h, depth.ctypes.data_as(_u16), depth.shape[0], depth.shape[1],
+                                               _ref(params), _ref(smooth)))
+    return pyramid_shapes(depth.shape, 3 if params is None else params.levels)
+
+
+def pyramid_shape(ctx, level):
+    """icpk_depth_pyramid_shape: (rows, cols) of one level of the resident pyramid."""
+    r, c = C.c_int32(0), C.c_int32(0)
+    ctx._chk(ctx._lib.icpk_depth_pyramid_shape(ctx._h, int(level), C.byref(r), C.byref(c)))
+    return r.value, c.value
+
+
+def pyramid_level(ctx, level):
+    """icpk_depth_pyramid_get: one level of the resident pyramid as a (rows, cols) uint16 array."""
+    out = np.empty(pyramid_shape(ctx, level), np.uint16)
+    ctx._chk(ctx._lib.icpk_depth_pyramid_get(ctx._h, int(level), out.ctypes.data_as(_u16)))
+    return out
+
+
+def backproject_level(ctx, level, which=0, normals_mode=None, fx=468.60, cx=318.27, offset=None):
+    """icpk_depth_pyramid_backproject: Context.backproject (normals_mode None) or Context.backproject_with_normals
+    (normals_mode NORMALS_*, which must be 1) of the resident level, read where it lies.  fx, cx: the LEVEL-0 intrinsics;
+    the level is seen through (fx / 2^level, cx / 2^level).  Returns the number of points."""
+    off = None if offset is None else np.ascontiguousarray(offset, np.float32)
+    return ctx._chk(ctx._lib.icpk_depth_pyramid_backproject(
+        ctx._h, int(level), fx, cx, None if off is None else off.ctypes.data_as(C.POINTER(C.c_float)), int(which),
+        -1 if normals_mode is None else int(normals_mode)))

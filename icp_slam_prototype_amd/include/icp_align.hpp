@@ -96,6 +96,23 @@ class Engine {
                           int normalsMode = -1, const icpk_bilateral_params* params = nullptr) {
     return icpk_backproject_smoothed(ctx_, image, rows, cols, fx, cx, offset, which, normalsMode, params);
   }
+  // the depth pyramid of a CV_16UC1 depth buffer on the device (icpk_depth_pyramid_build, K24), resident until the
+  // next build; params nullptr: icpk_default_pyramid_params; smooth non-null: level 0 is the frame after the bilateral
+  // filter
+  int buildDepthPyramid(const uint16_t* image, int rows, int cols, const icpk_pyramid_params* params = nullptr,
+                        const icpk_bilateral_params* smooth = nullptr) {
+    return icpk_depth_pyramid_build(ctx_, image, rows, cols, params, smooth);
+  }
+  // one level of it: its shape (out nullptr: the shape alone) and its pixels into `out`, rows x cols of that level
+  int depthPyramidLevel(int level, int* rows, int* cols, uint16_t* out = nullptr) {
+    const int rc = icpk_depth_pyramid_shape(ctx_, level, rows, cols);
+    return rc != ICPK_OK || !out ? rc : icpk_depth_pyramid_get(ctx_, level, out);
+  }
+  // ... and the cloud of a level read where it lies (icpk_depth_pyramid_backproject): fx, cx are the LEVEL-0 intrinsics.
+  // Returns the number of points or a negative status.
+  int backprojectPyramidLevel(int level, float fx, float cx, const float* offset, int which, int normalsMode = -1) {
+    return icpk_depth_pyramid_backproject(ctx_, level, fx, cx, offset, which, normalsMode);
+  }
   // robust alignment (icpk_set_robust): trimmed pairs and Huber / Tukey weights for every later alignment of this
   // engine (Kabsch and point-to-plane flavours); clearRobust() turns it off again (the default)
   int setRobust(const icpk_robust& r) { return icpk_set_robust(ctx_, &r); }

@@ -194,10 +194,17 @@ class ModelTracker:
     None: the raw frame serves both.
     follow: an integer `every` -- the volume follows the camera (TsdfVolume.follow, K23): once a pose is found and before
     its frame is fused, the volume shifts when the camera has moved `every` voxels or more, and a non-empty leaving list
-    goes to on_leave(list) (default: appended to self.streamed).  None: the volume stays where it was created."""
+    goes to on_leave(list) (default: appended to self.streamed).  None: the volume stays where it was created.
+    pyramid: a tuple of iteration counts, finest level first -- coarse-to-fine tracking over a depth pyramid (K24):
+    (10, 5, 4) runs 4 iterations at level 2, then 5 at level 1, then 10 at level 0, each level against the model
+    ray-cast at the LAST pose through (fx / 2^l, cx / 2^l) and through a gate of max_nn_dist * 2^l, since a pixel's
+    footprint doubles per level; align_kw's max_iterations is not used then.  A level whose ray cast hits fewer pixels
+    than min_pairs is skipped and counted in self.levels_skipped; only level 0 raises.  pyramid_cutoff: the rule's K
+    (default: icpk_default_pyramid_params').  With bilateral, level 0 is the smoothed frame.  None: one alignment on
+    the full frame."""
 
     def __init__(self, vol, pose=None, z_near=0.25, z_far=6.0, step=None, min_weight=1, bilateral=None, follow=None,
-                 on_leave=None, **align_kw):
+                 on_leave=None, pyramid=None, pyramid_cutoff=None, **align_kw):
         self.vol = vol
         self.pose = np.eye(4) if pose is None else np.array(pose, np.float64).reshape(4, 4)
         self.ray = dict(z_near=z_near, z_far=z_far, step=step, min_weight=min_weight)
@@ -209,12 +216,54 @@ class ModelTracker:
         self.streamed = []
         self.on_leave = self.streamed.append if on_leave is None else on_leave
         self.shifts = 0  # the shifts `follow` has made
+        self.pyramid = None if pyramid is None else tuple(int(n) for n in pyramid)
+        if self.pyramid is not None and not 1 <= len(self.pyramid) <= binding.PYRAMID_MAX_LEVELS:
+            raise ValueError(f"pyramid: 1 .. {binding.PYRAMID_MAX_LEVELS} iteration counts, finest level first")
+        self.pyramid_params = None
+        if self.pyramid is not None:
+            kw = {} if pyramid_cutoff is None else dict(range_cutoff=int(pyramid_cutoff))
+            self.pyramid_params = depth_front.pyramid_params(levels=len(self.pyramid), **kw)
+        self.levels_skipped = 0  # pyramid levels whose ray cast hit fewer pixels than min_pairs
+        self.level_hits = self.level_stats = None  # per level of the last frame, finest first (None: skipped)
+
+    def _track_pyramid(self, depth):
+        """The pose of one frame, coarse to fine: one build, then per level a ray cast of the model at the last pose,
+        the level's cloud moved by the running estimate, and an alignment that refines the estimate."""
+        vol, ctx = self.vol, self.vol.ctx
+        shapes = depth_front.build_pyramid(ctx, depth, self.pyramid_params, smooth=self.bilateral)
+        gate = binding.default_params(**self.align_kw).max_nn_dist
+        estimate = self.pose
+        self.level_hits, self.level_stats = [None] * len(shapes), [None] * len(shapes)
+        for l in range(len(shapes) - 1, -1, -1):
+            scale = float(2 ** l)
+            params = binding.default_params(**dict(self.align_kw, solve=binding.SOLVE_POINT_TO_PLANE,
+                                                   max_iterations=self.pyramid[l], max_nn_dist=gate * scale))
+            ray = binding.tsdf_raycast_params(shape=shapes[l], fx=vol.fx / scale, cx=vol.cx / scale, z_near=self.ray["z_near"],
+                                              z_far=self.ray["z_far"], step=0.0 if self.ray["step"] is None else self.ray["step"],
+                                              min_weight=self.ray["min_weight"])
+            n_hits, _ = ctx.tsdf_raycast(self.pose, ray)
+            self.level_hits[l] = n_hits
+            if n_hits < params.min_pairs:
+                if l == 0:
+                    raise RuntimeError(f"the ray cast hit the model in {n_hits} pixels, fewer than min_pairs = {params.min_pairs}")
+                self.levels_skipped += 1
+                continue
+            ctx.tsdf_raycast_to_target()
+            depth_front.backproject_level(ctx, l, which=0, fx=vol.fx, cx=vol.cx)
+            ctx.transform_source(estimate[:3, :3], estimate[:3, 3])
+            ctx.commit_source()
+            T, self.level_stats[l], _ = ctx.align(params)
+            estimate = T.astype(np.float64) @ estimate
+        self.n_hits, self.stats = self.level_hits[0], self.level_stats[0]
+        return estimate
 
     def track(self, depth, intensity=None):
         """One (rows, cols) uint16 frame (with its (rows, cols) intensities on a colour volume).  Returns the frame's
         camera-to-world pose (4, 4) float64; the first frame takes the initial pose."""
         vol, ctx = self.vol, self.vol.ctx
-        if self.frames > 0:
+        if self.frames > 0 and self.pyramid is not None:
+            self.pose = self._track_pyramid(depth)
+        elif self.frames > 0:
             params = binding.default_params(solve=binding.SOLVE_POINT_TO_PLANE, **self.align_kw)
             self.n_hits, _ = ctx.tsdf_raycast(self.pose, vol._ray_params(np.shape(depth), **self.ray))
             if self.n_hits < params.min_pairs:

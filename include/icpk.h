@@ -1590,6 +1590,72 @@ int icpk_bilateral_tables(const icpk_bilateral_params *params, uint16_t *ws, uin
 int icpk_bilateral_host(const icpk_bilateral_params *params, const uint16_t *depth_in, int32_t rows, int32_t cols,
                         uint16_t *depth_out);
 
+/* ---- K24: a depth pyramid on the device, for coarse-to-fine tracking ------------------------------------------------
+ * KinectFusion's second stage: the frame at half and a quarter of its size, so that the first iterations of an
+ * alignment run on a sixteenth of the points through a wide gate and only the last ones on the full frame through a
+ * tight one.  The pyramid stays on the device; each level is back-projected from where it lies.
+ *
+ * THE PYRAMID RULE (icpk_depth_pyramid_build; integers only, so the result is a function of the image and K alone:
+ * tile shape, tap order and who computes it do not matter).
+ *   Parameters (icpk_pyramid_params; defaults from icpk_default_pyramid_params):
+ *     levels        1 .. ICPK_PYRAMID_MAX_LEVELS (3): the number of images, level 0 included
+ *     range_cutoff  K, 1 .. 65536 (91, the K of the bilateral defaults)
+ *   Level 0 is the input image, uint16, 0 a hole.  Level l + 1 has (rows_l + 1) / 2 by (cols_l + 1) / 2 pixels; a level
+ *   that has shrunk to 1 x 1 stays 1 x 1.
+ *   Pixel (r, c) of level l + 1 is centred on pixel (2 r, 2 c) of level l, of depth d_c; that pixel is always inside
+ *   the image.
+ *     d_c == 0 gives 0.
+ *     Otherwise tap (dy, dx) in {-1, 0, 1}^2 counts iff (2 r + dy, 2 c + dx) lies inside the image, its depth d_q != 0
+ *     and |d_q - d_c| < K.  Its weight is w = (2 - |dy|)(2 - |dx|): 1, 2 or 4.
+ *     S = sum w (4 .. 16), D = sum w (d_q - d_c);  out = d_c + floor((2 D + S) / (2 S)), floor towards minus infinity:
+ *     the weighted mean, rounded to nearest, halves up.
+ *   Consequences:
+ *     the validity mask of a level is the mask of the level below, subsampled exactly (out != 0 iff d_c != 0);
+ *     |out - d_c| <= K - 1;
+ *     K == 1 is plain subsampling: level l + 1 is level l at its even rows and columns;
+ *     a depth step of K or more is never averaged across.
+ *   The window is symmetric about the centre pixel, so pixel (r, c) of level l IS pixel (r 2^l, c 2^l) of level 0, and
+ *   the level's intrinsics are fx / 2^l and cx / 2^l, both exact in float.  (A rule that averages the 2 x 2 block, with
+ *   block-centre intrinsics, is biased towards one corner by any range gate wherever the depths of one block differ by
+ *   more than K, as on a slanted floor; the centred window is not.)  On the noiseless 120 x 160 room of
+ *   synth.render_room_depth (fx, cx = 117.15, 79.5), against a direct render at the level's shape and intrinsics:
+ *   K = 1 gives the render exactly at levels 1 and 2; K = 91 differs by at most 36 units at level 1 and 29 at level 2.
+ *
+ * icpk_depth_pyramid_build     depth: a host image of rows x cols.  params NULL: the defaults.  smooth NULL: level 0 is
+ *     the frame as given, uploaded straight into the pyramid; otherwise level 0 is the frame after K22 with these
+ *     parameters (the upload then goes through the image buffers icpk_backproject_pair keeps its resident frame in,
+ *     and, as after icpk_bilateral_depth_image, no frame is resident afterwards).  The call touches no cloud, no
+ *     association and no seed; when it returns the caller's image has been consumed.  The pyramid replaces the previous
+ *     one and stays resident until the next build; it is freed with the context.
+ * icpk_depth_pyramid_shape     rows, cols of a level (either may be NULL).
+ * icpk_depth_pyramid_get       out: a host array of the level's rows x cols.
+ * icpk_depth_pyramid_backproject  fx, cx: the LEVEL-0 intrinsics.  In every effect on the context it equals
+ *     icpk_backproject (normals_mode < 0) or icpk_backproject_with_normals (normals_mode >= 0, which must be 1) of
+ *     icpk_depth_pyramid_get(level) at (fx / 2^level, cx / 2^level): the cloud, the normals, the subsample key it draws,
+ *     the associations and seeds it drops, the resident frame it gives up.  Returns the number of points.
+ * icpk_depth_pyramid_host      host only: level `level` of the pyramid of depth_in, through the header the kernel
+ *     includes (csrc/pyramid_rule.h), into out, a host array of exactly that level's size.
+ * ICPK_E_NOT_SET: shape, get or backproject before the first build.
+ * Refusals (ICPK_E_ARG; a refused call leaves the context, its clouds, the pyramid and the output array as they were):
+ *     a NULL context or image; rows or cols < 1, or more than 2^28 pixels; levels outside 1 .. ICPK_PYRAMID_MAX_LEVELS;
+ *     range_cutoff outside 1 .. 65536; bilateral parameters THE BILATERAL RULE refuses; a level the pyramid does not
+ *     have; for icpk_depth_pyramid_backproject also `which` outside 0 / 1, normals_mode >= 0 with which == 0, and a
+ *     normals_mode icpk_backproject_with_normals does not know. */
+#define ICPK_PYRAMID_MAX_LEVELS 8
+typedef struct icpk_pyramid_params {
+  int32_t levels;       /* 1 .. ICPK_PYRAMID_MAX_LEVELS (3) */
+  int32_t range_cutoff; /* K: 1 .. 65536 (91) */
+} icpk_pyramid_params;
+void icpk_default_pyramid_params(icpk_pyramid_params *p);
+int icpk_depth_pyramid_build(icpk_ctx *ctx, const uint16_t *depth, int32_t rows, int32_t cols,
+                             const icpk_pyramid_params *params, const icpk_bilateral_params *smooth);
+int icpk_depth_pyramid_shape(icpk_ctx *ctx, int32_t level, int32_t *rows, int32_t *cols);
+int icpk_depth_pyramid_get(icpk_ctx *ctx, int32_t level, uint16_t *out);
+int icpk_depth_pyramid_backproject(icpk_ctx *ctx, int32_t level, float fx, float cx, const float offset[3],
+                                   int32_t which, int32_t normals_mode);
+int icpk_depth_pyramid_host(const icpk_pyramid_params *params, const uint16_t *depth_in, int32_t rows, int32_t cols,
+                            int32_t level, uint16_t *out);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
