@@ -93,6 +93,8 @@ SYMBOLS = [
     "icpk_bilateral_host",
     "icpk_default_pyramid_params", "icpk_depth_pyramid_build", "icpk_depth_pyramid_shape", "icpk_depth_pyramid_get",
     "icpk_depth_pyramid_backproject", "icpk_depth_pyramid_host",
+    "icpk_default_projective_params", "icpk_projective_associate", "icpk_projective_reduce", "icpk_align_projective",
+    "icpk_get_projective_trace", "icpk_projective_pixels",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -212,6 +214,28 @@ PYRAMID_MAX_LEVELS = 8  # icpk_pyramid_params.levels
 class PyramidParams(C.Structure):
     """icpk_pyramid_params"""
     _fields_ = [("levels", C.c_int32), ("range_cutoff", C.c_int32)]
+
+
+PROJECTIVE_MAX_ITERATIONS = 64  # icpk_projective_params.max_iterations
+# icpk_projective_associate: why a pixel has no pair
+PROJ_NO_DEPTH, PROJ_BEHIND, PROJ_OUTSIDE, PROJ_NO_MODEL, PROJ_TOO_FAR, PROJ_NO_NORMAL, PROJ_NORMAL = -1, -2, -3, -4, -5, -6, -7
+
+
+class ProjectiveParams(C.Structure):
+    """icpk_projective_params"""
+    _fields_ = [("level", C.c_int32), ("fx", C.c_float), ("cx", C.c_float), ("max_iterations", C.c_int32),
+                ("max_dist", C.c_float), ("min_normal_cos", C.c_float), ("min_pairs", C.c_int32)]
+
+
+class ProjectiveResult(C.Structure):
+    """icpk_projective_result: count and mean_dist are those of the last evaluated iteration"""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("count", C.c_int64), ("mean_dist", C.c_double)]
+
+
+class ProjectiveIter(C.Structure):
+    """icpk_projective_iter"""
+    _fields_ = [("pose", C.c_double * 12), ("sums", C.c_double * 28), ("count", C.c_int64), ("status", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class FrameJob(C.Structure):
@@ -465,6 +489,15 @@ def load():
     lib.icpk_depth_pyramid_get.argtypes = [C.c_void_p, C.c_int32, u16]
     lib.icpk_depth_pyramid_backproject.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float, fp, C.c_int32, C.c_int32]
     lib.icpk_depth_pyramid_host.argtypes = [pp, u16, C.c_int32, C.c_int32, C.c_int32, u16]
+    jp = C.POINTER(ProjectiveParams)
+    lib.icpk_default_projective_params.argtypes = [jp]
+    lib.icpk_default_projective_params.restype = None
+    lib.icpk_projective_associate.argtypes = [C.c_void_p, jp, dp, ip, fp]
+    lib.icpk_projective_reduce.argtypes = [C.c_void_p, jp, dp, dp, C.POINTER(C.c_int64)]
+    lib.icpk_align_projective.argtypes = [C.c_void_p, jp, dp, dp, C.POINTER(ProjectiveResult)]
+    lib.icpk_get_projective_trace.argtypes = [C.c_void_p, C.POINTER(ProjectiveIter), C.c_int32]
+    lib.icpk_projective_pixels.argtypes = [jp, dp, u16, C.c_int32, C.c_int32, C.POINTER(fp), C.c_int32, C.c_int32,
+                                           C.c_float, C.c_float, dp, C.c_int64, C.c_int32, ip, fp, dp]
     _lib = lib
     return lib
 
@@ -723,6 +756,47 @@ def tsdf_raycast_pixels(params, ray, pose, tsdf, weight, intensity=None, first=0
     return out, rc
 
 
+def default_projective_params(**kw):
+    """icpk_default_projective_params with the given fields replaced (level, fx, cx, max_iterations, max_dist,
+    min_normal_cos, min_pairs)."""
+    p = ProjectiveParams()
+    load().icpk_default_projective_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _pose16(pose):
+    return np.ascontiguousarray(pose, np.float64).reshape(16)
+
+
+def projective_pixels(params, pose, level, view, view_shape, view_fx, view_cx, view_pose, first=0, count=None,
+                      terms=False):
+    """icpk_projective_pixels (host only): the projective rule for `count` pixels from row-major pixel `first` of the
+    (rows, cols) uint16 image `level` (default: all from there on).  view: seven float32 planes x, y, z, nx, ny, nz,
+    depth of view_shape.  Returns (pixel (count,) int32: the view pixel or the PROJ_* code; dist (count,) float32;
+    terms (count, 28) float64 or None; the number of pairs)."""
+    img = np.ascontiguousarray(level, np.uint16)
+    rows_s, cols_s = img.shape
+    rows_v, cols_v = int(view_shape[0]), int(view_shape[1])
+    planes = [_f(view[k]).reshape(-1) for k in range(7)]
+    if any(a.size != rows_v * cols_v for a in planes):
+        raise ValueError("every plane of the view must hold rows x cols entries")
+    count = rows_s * cols_s - int(first) if count is None else int(count)
+    n = max(count, 0)
+    pixel, dist = np.zeros(n, np.int32), np.zeros(n, np.float32)
+    tm = np.zeros((n, 28), np.float64) if terms else None
+    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+    rc = load().icpk_projective_pixels(C.byref(params), _pose16(pose).ctypes.data_as(dp), img.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                       rows_s, cols_s, (fp * 7)(*[_fp(a) for a in planes]), rows_v, cols_v, view_fx, view_cx,
+                                       _pose16(view_pose).ctypes.data_as(dp), int(first), count,
+                                       pixel.ctypes.data_as(C.POINTER(C.c_int32)), _fp(dist),
+                                       None if tm is None else tm.ctypes.data_as(dp))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_projective_pixels")
+    return pixel, dist, tm, rc
+
+
 def tsdf_mesh_host(params, tsdf, weight, intensity=None, min_weight=1, cap_vertices=None, cap_triangles=None):
     """icpk_tsdf_mesh_host (host only): the mesh rule over the host planes tsdf float32, weight uint16 (and intensity
     float32 on a TSDF_COLOR volume).  Returns dict(vertices (3, n), normals (3, n), intensity (n,), voxel_index (n,)
@@ -836,6 +910,60 @@ def tsdf_get_box(ctx, lo, hi, tsdf=True, weight=True, intensity=False):
                                         None if w is None else w.ctypes.data_as(C.POINTER(C.c_uint16)),
                                         None if c is None else _fp(c)))
     return f, w, c
+
+
+# ---- projective frame-to-model alignment (K25): functions of a context, like the moving volume's above ----------------
+def _projective(params, kw):
+    return params if params is not None else default_projective_params(**kw)
+
+
+def projective_associate(ctx, pose, params=None, **kw):
+    """icpk_projective_associate at the camera-to-world pose (4, 4) float64: (pixel (rows, cols) int32 -- the view pixel
+    every pixel of the pyramid level pairs with, or its PROJ_* code --, dist (rows, cols) float32).  params:
+    ProjectiveParams, or its fields as keywords."""
+    p = _projective(params, kw)
+    P = _pose16(pose)
+    dp = C.POINTER(C.c_double)
+    r, c = C.c_int32(0), C.c_int32(0)
+    if ctx._lib.icpk_depth_pyramid_shape(ctx._h, int(p.level), C.byref(r), C.byref(c)) != OK:
+        # (no such level: the call states its own refusal, and needs no arrays for it)
+        ctx._chk(ctx._lib.icpk_projective_associate(ctx._h, C.byref(p), P.ctypes.data_as(dp), None, None))
+        raise IcpkError(E_ARG, "a level the pyramid does not have")
+    pixel, dist = np.zeros((r.value, c.value), np.int32), np.zeros((r.value, c.value), np.float32)
+    ctx._chk(ctx._lib.icpk_projective_associate(ctx._h, C.byref(p), P.ctypes.data_as(dp),
+                                                pixel.ctypes.data_as(C.POINTER(C.c_int32)), _fp(dist)))
+    return pixel, dist
+
+
+def projective_reduce(ctx, pose, params=None, **kw):
+    """icpk_projective_reduce: (28 float64 sums, pair count) of one evaluation at the pose."""
+    p = _projective(params, kw)
+    P = _pose16(pose)
+    sums, n = np.zeros(28, np.float64), C.c_int64(-1)
+    dp = C.POINTER(C.c_double)
+    ctx._chk(ctx._lib.icpk_projective_reduce(ctx._h, C.byref(p), P.ctypes.data_as(dp), sums.ctypes.data_as(dp), C.byref(n)))
+    return sums, n.value
+
+
+def align_projective(ctx, pose, params=None, **kw):
+    """icpk_align_projective from the camera-to-world pose (4, 4) float64: (pose (4, 4) float64, ProjectiveResult).  The
+    result's status is OK, W_TOO_FEW_PAIRS or W_DEGENERATE; its count and mean_dist are those of the last evaluated
+    iteration, i.e. at the estimate before the last update."""
+    p = _projective(params, kw)
+    P = _pose16(pose)
+    out, res = np.zeros(16, np.float64), ProjectiveResult()
+    dp = C.POINTER(C.c_double)
+    ctx._chk(ctx._lib.icpk_align_projective(ctx._h, C.byref(p), P.ctypes.data_as(dp), out.ctypes.data_as(dp), C.byref(res)))
+    return out.reshape(4, 4), res
+
+
+def projective_trace(ctx):
+    """icpk_get_projective_trace: the evaluated iterations of the last align_projective, a list of dict(pose (3, 4)
+    float64 E_k, sums (28,), count, status)."""
+    buf = (ProjectiveIter * PROJECTIVE_MAX_ITERATIONS)()
+    n = ctx._chk(ctx._lib.icpk_get_projective_trace(ctx._h, buf, PROJECTIVE_MAX_ITERATIONS))
+    return [dict(pose=np.array(buf[k].pose, np.float64).reshape(3, 4), sums=np.array(buf[k].sums, np.float64),
+                 count=int(buf[k].count), status=int(buf[k].status)) for k in range(n)]
 
 
 class Context:

@@ -3,7 +3,7 @@
 // icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
 // entry; icpk_frontend.cpp: depth images;
 // icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp, icpk_gicp.cpp,
-// icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp, icpk_posegraph.cpp, icpk_tsdf.cpp).  Not
+// icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp, icpk_posegraph.cpp, icpk_tsdf.cpp, icpk_projective.cpp).  Not
 // part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -460,6 +460,18 @@ struct icpk_ctx {
   int pyr_levels = 0;  // 0: no pyramid yet
   int pyr_rows[ICPK_PYRAMID_MAX_LEVELS] = {0}, pyr_cols[ICPK_PYRAMID_MAX_LEVELS] = {0};
   size_t pyr_off[ICPK_PYRAMID_MAX_LEVELS] = {0};
+  // K25 (icpk_projective.cpp), behind the pyramid for the same reason: the canonical tree's scratch of the projective
+  // reduction, its final sums, the loop's state + trace on the device and where the host reads them, the per-pixel
+  // outputs of icpk_projective_associate, and the record of the last icpk_align_projective
+  icpk::DevBuf<double> proj_partial;  // NP2L x RED_MAX_BLOCKS
+  icpk::DevBuf<int> proj_pcount;      // RED_MAX_BLOCKS
+  icpk::DevBuf<double> proj_out;      // NP2L sums, then the count as an int64
+  icpk::PinnedBuf<double> proj_out_host;
+  icpk::DevBuf<icpk::ProjBlock> proj_block;
+  icpk::PinnedBuf<icpk::ProjBlock> proj_block_host;
+  icpk::DevBuf<int32_t> proj_pixel;  // [rows_s cols_s]
+  icpk::DevBuf<float> proj_dist;     // [rows_s cols_s]
+  std::vector<icpk_projective_iter> proj_trace;
 };
 
 #define ICPK_HIP(ctx, call)                                                                      \
@@ -589,6 +601,17 @@ int device_loop_begin(icpk_ctx* ctx, const icpk_params* p, bool throttled = fals
 void device_loop_disarm(icpk_ctx* ctx);
 int device_loop_finish(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats* stats,
                        const LoopState* h = nullptr);
+
+// ---- icpk_tsdf.cpp: the last ray cast as K25 reads it ----
+// the eight planes where they lie, their shape, and the camera and pose icpk_tsdf_raycast was given
+struct TsdfRayView {
+  const float* maps;
+  int rows, cols;
+  float fx, cx;
+  double pose[16];
+};
+// ICPK_E_NOT_SET (with the reason in ctx->err) without a volume or without a ray cast
+int tsdf_raycast_view(icpk_ctx* ctx, TsdfRayView* out);
 
 // ---- icpk_batch.cpp: the lock-step machinery icpk_frames_batch.cpp shares ----
 bool batch_eligible(const icpk_ctx* ctx, const icpk_params* p);  // params the lock-step path runs

@@ -992,4 +992,49 @@ void launch_tsdf_mesh_count(const TsdfMeshArgs& a, int nblocks, long long* total
 // the vertices, then the triangles
 void launch_tsdf_mesh_scatter(const TsdfMeshArgs& a, int nblocks, hipStream_t s);
 
+// kernels_projective.hip -- K25, projective frame-to-model alignment (the projective rule is projective_rule.h)
+constexpr int PROJ_MAX_ITER = 64;  // ICPK_PROJECTIVE_MAX_ITERATIONS
+// The loop's state on the device: the reduce launch reads `done` and the float pose, the step launch behind it writes
+// the trace entry of its iteration and either the next pose or done + status.
+struct ProjState {
+  int done;
+  int status;
+  int iterations;  // updates made
+  int pad0;
+  float R[9], t[3];  // E_k rounded to float once: what the reduce launch moves the vertices by
+  double E[12];      // E_k, rows of [R | t]
+};
+struct ProjIter {  // icpk_projective_iter
+  double E[12];
+  double sums[NP2L];
+  long long count;
+  int status;
+  int pad0;
+};
+// state and trace in one allocation, so that both come back with one copy
+struct ProjBlock {
+  ProjState st;
+  ProjIter trace[PROJ_MAX_ITER];
+};
+struct ProjArgs {
+  const uint16_t* depth;  // the level
+  int rows, cols;
+  float fx, cx;           // fx / 2^l, cx / 2^l
+  const float* maps;      // the ray cast's planes, npix_v floats each: x, y, z, nx, ny, nz, depth, intensity
+  int rows_v, cols_v;
+  float fx_v, cx_v;
+  float Q[9], s[3];       // the view's pose inverted
+  float max_dist, min_normal_cos;
+  double* partial;        // [NP2L][RED_MAX_BLOCKS]
+  int* pcount;            // [RED_MAX_BLOCKS]
+  const ProjState* st;
+};
+// red_blocks(rows cols) workgroups: the per-block partials of one evaluation at the state's pose (nothing once done)
+void launch_proj_reduce(const ProjArgs& a, hipStream_t s);
+// one workgroup: the canonical stage 2, then iteration k of the loop rule on one lane
+void launch_proj_step(const double* partial, const int* pcount, int nblocks, ProjBlock* blk, int k, int min_pairs,
+                      hipStream_t s);
+// every pixel's code or view pixel, and its distance, at the state's pose (device arrays of rows cols entries)
+void launch_proj_associate(const ProjArgs& a, int32_t* pixel, float* dist, hipStream_t s);
+
 }  // namespace icpk

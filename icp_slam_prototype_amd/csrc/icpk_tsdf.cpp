@@ -48,6 +48,8 @@ struct icpk_tsdf_state {
   size_t ray_list_cap = 0;
   bool have_raycast = false;
   int ray_rows = 0, ray_cols = 0;
+  float ray_fx = 0.f, ray_cx = 0.f;  // ... and the camera and pose they were cast with (K25 projects into them)
+  double ray_pose[16] = {0};
   // the mesh of the last mesh extraction (K21): 7 planes of mesh_vcap floats, every vertex's key (owner voxel, edge
   // type), 3 x mesh_tcap indices; and its own per-chunk counts, scans and totals, so that K19's stay as they are
   DevBuf<float> mesh;
@@ -67,6 +69,17 @@ struct icpk_tsdf_state {
 void icpk_tsdf_free(icpk_ctx* ctx) {
   delete ctx->tsdf;  // (its buffers free themselves)
   ctx->tsdf = nullptr;
+}
+
+int icpk::tsdf_raycast_view(icpk_ctx* ctx, TsdfRayView* out) {
+  const icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  if (!v->have_raycast) return fail(ctx, ICPK_E_NOT_SET, "no ray cast (icpk_tsdf_raycast)");
+  out->maps = v->ray_maps;
+  out->rows = v->ray_rows, out->cols = v->ray_cols;
+  out->fx = v->ray_fx, out->cx = v->ray_cx;
+  std::memcpy(out->pose, v->ray_pose, sizeof(out->pose));
+  return ICPK_OK;
 }
 
 namespace {
@@ -718,6 +731,8 @@ int icpk_tsdf_raycast(icpk_ctx* ctx, const icpk_tsdf_raycast_params* params, con
   launch_tsdf_raycast(a, tsdf_ray_blocks(rp.rows, rp.cols), v->totals, ctx->stream);
   ICPK_HIP(ctx, hipGetLastError());
   v->ray_rows = rp.rows, v->ray_cols = rp.cols;
+  v->ray_fx = rp.fx, v->ray_cx = rp.cx;
+  std::memcpy(v->ray_pose, pose, sizeof(v->ray_pose));
   v->have_raycast = true;
   if (!n_hits && !n_no_normal) return ICPK_OK;  // (nothing is asked: the call does not wait)
   ICPK_HIP(ctx, hipMemcpyAsync(v->totals_host, v->totals, 2 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));

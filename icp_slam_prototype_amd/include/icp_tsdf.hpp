@@ -6,6 +6,8 @@
 //                        (surface) or becomes the Engine's target for scan-to-model alignment (toTarget).  An Engine
 //                        holds one volume: constructing another replaces it.  raycast gives the surface visible from
 //                        one pose as vertex and normal maps (K20); raycastToTarget makes it the Engine's target.
+//                        alignProjective / projectiveAssociate pair a level of the Engine's depth pyramid with those maps
+//                        pixel by pixel and refine a pose against the model (K25).
 //                        extractMesh / getMesh give the surface as a triangle mesh (K21); setPlanes restores a saved
 //                        model.  shift / extractLeaving / getBox let the volume follow the camera (K23): the box
 //                        moves by whole voxels, what is about to leave it is listed first.
@@ -129,6 +131,39 @@ class TsdfVolume {
   // the last ray cast's hits become the Engine's target, with their normals (and colours), in row-major pixel order:
   // device to device.  ICPK_E_EMPTY_TARGET (the target stays) without a hit
   int raycastToTarget() { return icpk_tsdf_raycast_to_target(eng_.ctx()); }
+  // projective frame-to-model alignment (K25): the parameters with this volume's intrinsics as the LEVEL-0 ones
+  // (10 iterations, max_dist 0.5, the normal gate off, min_pairs 6)
+  icpk_projective_params projectiveDefaults(int level = 0) const {
+    icpk_projective_params p;
+    icpk_default_projective_params(&p);
+    p.level = level, p.fx = fx_, p.cx = cx_;
+    return p;
+  }
+  // a level of the Engine's resident depth pyramid (Engine::buildDepthPyramid) against the maps of the last ray cast,
+  // from the camera-to-world estimate poseIn (16 doubles, row-major) to poseOut; nothing of the Engine's clouds is
+  // touched.  Returns ICPK_OK, ICPK_W_TOO_FEW_PAIRS, ICPK_W_DEGENERATE or a negative status
+  int alignProjective(const icpk_projective_params& p, const double* poseIn, double* poseOut,
+                      icpk_projective_result* result = nullptr) {
+    return icpk_align_projective(eng_.ctx(), &p, poseIn, poseOut, result);
+  }
+  // per pixel of that level at `pose`: the view pixel it pairs with or its ICPK_PROJ_* code, and the distance (0
+  // without a pair); both vectors are sized to the level
+  int projectiveAssociate(const icpk_projective_params& p, const double* pose, std::vector<int32_t>& pixel,
+                          std::vector<float>& dist) {
+    int32_t rows = 0, cols = 0;
+    if (icpk_depth_pyramid_shape(eng_.ctx(), p.level, &rows, &cols) != ICPK_OK)
+      return icpk_projective_associate(eng_.ctx(), &p, pose, nullptr, nullptr);  // (its own refusal)
+    pixel.assign((size_t)rows * cols, 0);
+    dist.assign((size_t)rows * cols, 0.f);
+    return icpk_projective_associate(eng_.ctx(), &p, pose, pixel.data(), dist.data());
+  }
+  // the iterations the last alignProjective evaluated: E_k, the sums and count at E_k, the status
+  std::vector<icpk_projective_iter> projectiveTrace() {
+    std::vector<icpk_projective_iter> t(ICPK_PROJECTIVE_MAX_ITERATIONS);
+    const int n = icpk_get_projective_trace(eng_.ctx(), t.data(), (int32_t)t.size());
+    t.resize(n > 0 ? (size_t)n : 0);
+    return t;
+  }
   // the surface as a triangle mesh over the cells whose eight voxels have weight >= minWeight; it stays on the device
   // for getMesh.  Any count may be null
   int extractMesh(int minWeight = 1, int32_t* nVertices = nullptr, int32_t* nTriangles = nullptr, int32_t* nNoNormal = nullptr) {

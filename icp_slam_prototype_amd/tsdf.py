@@ -201,10 +201,19 @@ class ModelTracker:
     footprint doubles per level; align_kw's max_iterations is not used then.  A level whose ray cast hits fewer pixels
     than min_pairs is skipped and counted in self.levels_skipped; only level 0 raises.  pyramid_cutoff: the rule's K
     (default: icpk_default_pyramid_params').  With bilateral, level 0 is the smoothed frame.  None: one alignment on
-    the full frame."""
+    the full frame.
+    projective: True, or a dict of icpk_projective_params fields (max_dist, min_pairs, min_normal_cos) -- projective data
+    association (K25) in place of the cloud-to-cloud alignment: the frame goes into a pyramid of len(pyramid) levels (1
+    when pyramid is None; smoothed when bilateral is given), and per level, coarse to fine, the model is ray-cast at
+    the LAST pose at the level's shape and intrinsics and binding.align_projective refines the estimate with
+    pyramid[l] iterations (align_kw's max_iterations when pyramid is None).  No target list, no cloud, no index.  The
+    gate max_dist is the SAME at every level and defaults to 0.5 m: a projective pair is as far apart as the frame has
+    slid along a surface, so the gate must be wider than the frame's displacement (a tight one makes the first step
+    nearly degenerate).  levels_skipped, level_hits and the level-0 RuntimeError are as above; level_stats holds
+    ProjectiveResult objects.  None: the paths above, untouched."""
 
     def __init__(self, vol, pose=None, z_near=0.25, z_far=6.0, step=None, min_weight=1, bilateral=None, follow=None,
-                 on_leave=None, pyramid=None, pyramid_cutoff=None, **align_kw):
+                 on_leave=None, pyramid=None, pyramid_cutoff=None, projective=None, **align_kw):
         self.vol = vol
         self.pose = np.eye(4) if pose is None else np.array(pose, np.float64).reshape(4, 4)
         self.ray = dict(z_near=z_near, z_far=z_far, step=step, min_weight=min_weight)
@@ -225,6 +234,41 @@ class ModelTracker:
             self.pyramid_params = depth_front.pyramid_params(levels=len(self.pyramid), **kw)
         self.levels_skipped = 0  # pyramid levels whose ray cast hit fewer pixels than min_pairs
         self.level_hits = self.level_stats = None  # per level of the last frame, finest first (None: skipped)
+        self.projective = None if projective is None else ({} if projective is True else dict(projective))
+        if self.projective is not None:
+            self.projective.setdefault("max_dist", 0.5)
+            if "min_pairs" in align_kw:
+                self.projective.setdefault("min_pairs", align_kw["min_pairs"])
+            self.projective_counts = self.pyramid if self.pyramid is not None else \
+                (int(align_kw.get("max_iterations", binding.default_projective_params().max_iterations)),)
+            if self.pyramid_params is None:
+                kw = {} if pyramid_cutoff is None else dict(range_cutoff=int(pyramid_cutoff))
+                self.pyramid_params = depth_front.pyramid_params(levels=1, **kw)
+
+    def _track_projective(self, depth):
+        """The pose of one frame by projective association, coarse to fine: one build, then per level a ray cast of the
+        model at the last pose and the device loop over the level and the maps, both where they lie."""
+        vol, ctx = self.vol, self.vol.ctx
+        shapes = depth_front.build_pyramid(ctx, depth, self.pyramid_params, smooth=self.bilateral)
+        estimate = self.pose
+        self.level_hits, self.level_stats = [None] * len(shapes), [None] * len(shapes)
+        for l in range(len(shapes) - 1, -1, -1):
+            scale = float(2 ** l)
+            params = binding.default_projective_params(**dict(self.projective, level=l, fx=vol.fx, cx=vol.cx,
+                                                              max_iterations=self.projective_counts[l]))
+            ray = binding.tsdf_raycast_params(shape=shapes[l], fx=vol.fx / scale, cx=vol.cx / scale, z_near=self.ray["z_near"],
+                                              z_far=self.ray["z_far"], step=0.0 if self.ray["step"] is None else self.ray["step"],
+                                              min_weight=self.ray["min_weight"])
+            n_hits, _ = ctx.tsdf_raycast(self.pose, ray)
+            self.level_hits[l] = n_hits
+            if n_hits < params.min_pairs:
+                if l == 0:
+                    raise RuntimeError(f"the ray cast hit the model in {n_hits} pixels, fewer than min_pairs = {params.min_pairs}")
+                self.levels_skipped += 1
+                continue
+            estimate, self.level_stats[l] = binding.align_projective(ctx, estimate, params)
+        self.n_hits, self.stats = self.level_hits[0], self.level_stats[0]
+        return estimate
 
     def _track_pyramid(self, depth):
         """The pose of one frame, coarse to fine: one build, then per level a ray cast of the model at the last pose,
@@ -261,7 +305,9 @@ class ModelTracker:
         """One (rows, cols) uint16 frame (with its (rows, cols) intensities on a colour volume).  Returns the frame's
         camera-to-world pose (4, 4) float64; the first frame takes the initial pose."""
         vol, ctx = self.vol, self.vol.ctx
-        if self.frames > 0 and self.pyramid is not None:
+        if self.frames > 0 and self.projective is not None:
+            self.pose = self._track_projective(depth)
+        elif self.frames > 0 and self.pyramid is not None:
             self.pose = self._track_pyramid(depth)
         elif self.frames > 0:
             params = binding.default_params(solve=binding.SOLVE_POINT_TO_PLANE, **self.align_kw)

@@ -1656,6 +1656,112 @@ int icpk_depth_pyramid_backproject(icpk_ctx *ctx, int32_t level, float fx, float
 int icpk_depth_pyramid_host(const icpk_pyramid_params *params, const uint16_t *depth_in, int32_t rows, int32_t cols,
                             int32_t level, uint16_t *out);
 
+/* ---- K25: projective frame-to-model alignment on the resident depth pyramid ----------------------------------------
+ * KinectFusion's data association: a pixel of the frame is paired with the pixel of the ray-cast view of the model it
+ * projects onto.  A pixel that projects outside the view, or onto a hole of it, has no pair, so nothing pairs with
+ * the view's border.  Both inputs lie on the device already -- a level of the pyramid (K24) and the eight planes of the
+ * last ray cast (K20) -- and no list, no index and no search is made.
+ *
+ * THE PROJECTIVE RULE.  float32; every operation rounded once, in the order written (fl(.) is one rounding); no fused
+ * multiply-add; correctly rounded / and sqrt; a floor is a comparison plus a truncating conversion of a value already
+ * known to be in range.
+ *   Inputs:
+ *     level l of the resident pyramid, rows_s x cols_s, uint16, seen through fx_s = fx / 2^l, cx_s = cx / 2^l (fx, cx:
+ *       the LEVEL-0 intrinsics of icpk_projective_params, as for icpk_depth_pyramid_backproject);
+ *     the planes x, y, z, nx, ny, nz, depth of the last icpk_tsdf_raycast (rows_v x cols_v; the shape need not equal the
+ *       level's) with that ray cast's own fx_v, cx_v and pose P_v, which the context keeps next to the maps;
+ *     an estimate E, double[16], camera-to-world: its nine R and three t rounded to float once;
+ *     (Q, s) = P_v inverted by icpk_tsdf_invert_pose.
+ *   Source pixel i = r cols_s + c; the first failing test decides its code (ICPK_PROJ_*, negative):
+ *     1. d == 0: NO_DEPTH.
+ *     2. the vertex, K4's arithmetic: v_z = fl((float)d / 5000.0f), v_x = fl(fl(fl((float)c - cx_s) v_z) / fx_s),
+ *        v_y = fl(fl(fl((float)r - cx_s) v_z) / fx_s)   (cx_s for the rows as well).
+ *     3. the world point: p_a = fl(fl(fl(fl(E_a0 v_x) + fl(E_a1 v_y)) + fl(E_a2 v_z)) + t_a)   (integration rule 2's form).
+ *     4. q = the same form with (Q, s) and p.  !(q_z > 0): BEHIND.
+ *     5. u = fl(fl(fl(q_x fx_v) / q_z) + cx_v), v = fl(fl(fl(q_y fx_v) / q_z) + cx_v); a = fl(u + 0.5f), b = fl(v + 0.5f);
+ *        !(a >= 0 && a < (float)cols_v && b >= 0 && b < (float)rows_v): OUTSIDE (in float, before any conversion; NaN
+ *        fails).  col = (int)a, row = (int)b.
+ *     6. j = row cols_v + col; !(depth_v[j] > 0): NO_MODEL.
+ *     7. e_a = fl(p_a - m_a), m = (x, y, z)[j]; dist = sqrt(fl(fl(fl(e_x e_x) + fl(e_y e_y)) + fl(e_z e_z)));
+ *        !(dist < max_dist): TOO_FAR.
+ *     8. only when min_normal_cos > -1 (default -2: off): s = the ICPK_NORMALS_CROSS normal of pixel (r, c) of the level
+ *        through (fx_s, cx_s); zero (a border pixel, a hole among the four neighbours, a zero cross product): NO_NORMAL.
+ *        s is negated when fl(fl(fl(s_x v_x) + fl(s_y v_y)) + fl(s_z v_z)) > 0 (the cross normal points away from the
+ *        camera, the model's normals towards it), rotated by E's R in the 3-term form (a0 b0 + a1 b1) + a2 b2, and
+ *        cosv = its 3-term dot with (nx, ny, nz)[j]; !(cosv >= min_normal_cos): NORMAL.
+ *     9. accepted: the pair (i, j, dist).  Its terms are K5's with p, m, n = (nx, ny, nz)[j] widened to double:
+ *        J = [p x n ; n], r = (p - m) . n, in the ICPK_NP2L layout with [27] = (double)dist.  A pixel without a pair adds
+ *        +0.0.  The sums go through the canonical tree (ICPK_RED_THREADS / ICPK_RED_MAX_BLOCKS) over i = 0 ..
+ *        rows_s cols_s - 1; the count is an exact integer.
+ *   The loop (icpk_align_projective): E_0 = the given pose.  Iteration k: sums and count at E_k; count < min_pairs stops
+ *   with ICPK_W_TOO_FEW_PAIRS and E stays; a solve (icpk_solve_point_to_plane) that fails stops with ICPK_W_DEGENERATE
+ *   and E stays; otherwise E_{k+1} = dT E_k in double: R' = dR R with 3-term products,
+ *   t'_r = ((dR_r0 t_0 + dR_r1 t_1) + dR_r2 t_2) + dt_r.  Exactly max_iterations iterations run otherwise: there is no
+ *   threshold test.  No working source is moved: every iteration recomputes the vertices from the level and E_k.
+ *   The gate must be wider than the frame's displacement: a wall that slides sideways is at nearest-neighbour distance
+ *   0 but at projective distance equal to the slide.  Hence the default of 0.5 m.
+ *
+ * icpk_projective_associate  per source pixel, at `pose`: pixel[i] = j or the code, dist[i] = the distance (0 without a
+ *     pair).  Host arrays of rows_s cols_s entries; either may be NULL.
+ * icpk_projective_reduce     one evaluation at `pose`: the ICPK_NP2L sums and the count.
+ * icpk_align_projective      the loop; pose_out (double[16], last row 0 0 0 1) is the last estimate.  The result's count
+ *     and mean_dist (sums[27] / count, 0 for no pair) are those of the LAST EVALUATED iteration, i.e. taken at the
+ *     estimate before the last update, not at pose_out.  iterations: the updates made.  Returns the status.
+ * icpk_get_projective_trace  the evaluated iterations of the last icpk_align_projective, at most cap of them: E_k, the
+ *     sums and count at E_k, and ICPK_OK or the warning that stopped the loop there.  Returns their number.
+ * icpk_projective_pixels     host only, no context: rules 1 - 9 for `count` source pixels from pixel `first` over a host
+ *     level (rows_s x cols_s: the level's own shape; params->level only scales fx, cx) and seven host planes view[0..6]
+ *     = x, y, z, nx, ny, nz, depth of rows_v x cols_v.  pixel / dist: count entries; terms (or NULL): count x ICPK_NP2L
+ *     doubles, zeros for a pixel without a pair.  Returns the number of pairs.  Compiled from the header the kernel
+ *     includes (csrc/projective_rule.h).
+ * None of these calls touches the context's source, target, associations, records, seeds, surface list or ray-cast
+ * maps; they use scratch of their own.
+ * ICPK_E_NOT_SET: no volume, no ray cast (as icpk_tsdf_get_raycast), or no pyramid.
+ * Refusals (ICPK_E_ARG; a refused call leaves everything as it was): a NULL or non-finite pose; a level the pyramid
+ *     lacks; fx not finite and > 0; a non-finite cx; max_dist not > 0; min_pairs < 1; max_iterations outside
+ *     1 .. ICPK_PROJECTIVE_MAX_ITERATIONS; a NaN min_normal_cos. */
+#define ICPK_PROJECTIVE_MAX_ITERATIONS 64
+#define ICPK_PROJ_NO_DEPTH (-1)
+#define ICPK_PROJ_BEHIND (-2)
+#define ICPK_PROJ_OUTSIDE (-3)
+#define ICPK_PROJ_NO_MODEL (-4)
+#define ICPK_PROJ_TOO_FAR (-5)
+#define ICPK_PROJ_NO_NORMAL (-6)
+#define ICPK_PROJ_NORMAL (-7)
+typedef struct icpk_projective_params {
+  int32_t level;          /* of the resident pyramid (0) */
+  float fx, cx;           /* LEVEL-0 intrinsics (468.60, 318.27) */
+  int32_t max_iterations; /* 1 .. ICPK_PROJECTIVE_MAX_ITERATIONS (10) */
+  float max_dist;         /* the gate, metres (0.5) */
+  float min_normal_cos;   /* > -1: the normal gate (-2: off) */
+  int32_t min_pairs;      /* >= 1 (6) */
+} icpk_projective_params;
+typedef struct icpk_projective_result {
+  int32_t status;     /* ICPK_OK, ICPK_W_TOO_FEW_PAIRS, ICPK_W_DEGENERATE */
+  int32_t iterations; /* updates made */
+  int64_t count;      /* pairs of the last evaluated iteration ... */
+  double mean_dist;   /* ... and their mean distance */
+} icpk_projective_result;
+typedef struct icpk_projective_iter {
+  double pose[12];         /* E_k: rows of [R | t] */
+  double sums[ICPK_NP2L];  /* at E_k */
+  int64_t count;
+  int32_t status;
+  int32_t reserved;
+} icpk_projective_iter;
+void icpk_default_projective_params(icpk_projective_params *p);
+int icpk_projective_associate(icpk_ctx *ctx, const icpk_projective_params *params, const double pose[16],
+                              int32_t *pixel, float *dist);
+int icpk_projective_reduce(icpk_ctx *ctx, const icpk_projective_params *params, const double pose[16],
+                           double sums[ICPK_NP2L], int64_t *count);
+int icpk_align_projective(icpk_ctx *ctx, const icpk_projective_params *params, const double pose_in[16],
+                          double pose_out[16], icpk_projective_result *result);
+int icpk_get_projective_trace(icpk_ctx *ctx, icpk_projective_iter *out, int32_t cap);
+int icpk_projective_pixels(const icpk_projective_params *params, const double pose[16], const uint16_t *level,
+                           int32_t rows_s, int32_t cols_s, const float *const view[7], int32_t rows_v, int32_t cols_v,
+                           float fx_v, float cx_v, const double view_pose[16], int64_t first, int32_t count,
+                           int32_t *pixel, float *dist, double *terms);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity

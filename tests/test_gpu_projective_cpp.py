@@ -1,0 +1,54 @@
+"""icp::TsdfVolume::alignProjective / projectiveAssociate / projectiveTrace (tests/cpp/test_projective.cpp) against the
+same calls made through the Python binding, byte for byte: the pose, the result, every trace entry and the per-pixel
+pairs of the room at level 1."""
+import os
+import struct
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import projective_cases as pc
+import tsdf_cases as tc
+from icp_slam_prototype_amd import binding, build, depth
+
+pytestmark = pytest.mark.gpu
+
+
+def test_cpp_projective_equals_binding():
+    exe = build.build_projective_test()
+    name, iters = "room_l1", 6
+    c, t = pc.case(name), tc.case("room")
+    v, view = t["volume"], c["view"]
+    rows, cols = t["frames"][0][0].shape
+    blob = struct.pack("<8i", *v["dims"], 255, 0, rows, cols, len(t["frames"]))
+    blob += struct.pack("<8f", v["voxel"], *v["origin"], v["trunc"], t["fx"], t["cx"], 0.0)
+    for d, P, _ in t["frames"]:
+        blob += np.ascontiguousarray(P, np.float64).tobytes() + np.ascontiguousarray(d, np.uint16).tobytes()
+    blob += struct.pack("<4i", *view["shape"], view["min_weight"], 0) + struct.pack("<4f", view["z_near"], view["z_far"], view["step"], 0.0)
+    blob += c["view_pose"].tobytes()
+    blob += struct.pack("<8i", *c["depth"].shape, c["level"] + 1, c["level"], iters, 6, 0, 0)
+    blob += struct.pack("<4f", c["fx"], c["cx"], c["max_dist"], c["min_normal_cos"]) + c["estimate"].tobytes() + c["depth"].tobytes()
+    with tempfile.TemporaryDirectory() as td:
+        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
+        with open(fin, "wb") as f:
+            f.write(blob)
+        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stderr
+        raw = open(fout, "rb").read()
+    with binding.Context(0) as ctx:
+        assert ctx.tsdf_create(dims=v["dims"], voxel=v["voxel"], origin=v["origin"], trunc=v["trunc"]).max_weight == 255
+        p = pc.device_setup(ctx, name, depth, binding)
+        p.max_iterations = iters
+        pose, res = binding.align_projective(ctx, c["estimate"], p)
+        trace = binding.projective_trace(ctx)
+        pixel, dist = binding.projective_associate(ctx, c["estimate"], p)
+    pairs = int((pixel >= 0).sum())
+    assert struct.unpack_from("<4i", raw, 0) == (binding.OK, iters, iters, pairs) and pairs == pc.expected(name)["count"]
+    want = struct.pack("<qd", res.count, res.mean_dist) + pose.tobytes()
+    for e in trace:
+        want += e["pose"].tobytes() + e["sums"].tobytes() + struct.pack("<q2i", e["count"], e["status"], 0)
+    want += pixel.tobytes() + dist.tobytes()
+    assert raw[16:] == want
+    assert f"projective level 1: status 0 after {iters} updates, {res.count} pairs at the last evaluation, {pairs} at the estimate" in out.stdout
