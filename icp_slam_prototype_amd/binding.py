@@ -95,6 +95,10 @@ SYMBOLS = [
     "icpk_depth_pyramid_backproject", "icpk_depth_pyramid_host",
     "icpk_default_projective_params", "icpk_projective_associate", "icpk_projective_reduce", "icpk_align_projective",
     "icpk_get_projective_trace", "icpk_projective_pixels",
+    "icpk_default_projective_color_params", "icpk_depth_pyramid_set_intensity", "icpk_depth_pyramid_get_intensity",
+    "icpk_intensity_pyramid_host", "icpk_tsdf_raycast_color_gradients", "icpk_tsdf_get_raycast_color_gradients",
+    "icpk_tsdf_get_raycast_color_gradient_sums", "icpk_raycast_color_gradients_host", "icpk_projective_reduce_colored",
+    "icpk_align_projective_colored", "icpk_projective_pixels_colored",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -236,6 +240,11 @@ class ProjectiveIter(C.Structure):
     """icpk_projective_iter"""
     _fields_ = [("pose", C.c_double * 12), ("sums", C.c_double * 28), ("count", C.c_int64), ("status", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class ProjectiveColorParams(C.Structure):
+    """icpk_projective_color_params"""
+    _fields_ = [("lambda_geometric", C.c_float)]
 
 
 class FrameJob(C.Structure):
@@ -498,6 +507,23 @@ def load():
     lib.icpk_get_projective_trace.argtypes = [C.c_void_p, C.POINTER(ProjectiveIter), C.c_int32]
     lib.icpk_projective_pixels.argtypes = [jp, dp, u16, C.c_int32, C.c_int32, C.POINTER(fp), C.c_int32, C.c_int32,
                                            C.c_float, C.c_float, dp, C.c_int64, C.c_int32, ip, fp, dp]
+    kp = C.POINTER(ProjectiveColorParams)
+    i64 = C.POINTER(C.c_int64)
+    lib.icpk_default_projective_color_params.argtypes = [kp]
+    lib.icpk_default_projective_color_params.restype = None
+    lib.icpk_depth_pyramid_set_intensity.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32]
+    lib.icpk_depth_pyramid_get_intensity.argtypes = [C.c_void_p, C.c_int32, fp]
+    lib.icpk_intensity_pyramid_host.argtypes = [pp, u16, fp, C.c_int32, C.c_int32, C.c_int32, fp]
+    lib.icpk_tsdf_raycast_color_gradients.argtypes = [C.c_void_p, C.c_float, C.c_int32, C.c_int32]
+    lib.icpk_tsdf_get_raycast_color_gradients.argtypes = [C.c_void_p, fp, fp, fp]
+    lib.icpk_tsdf_get_raycast_color_gradient_sums.argtypes = [C.c_void_p, i64]
+    lib.icpk_raycast_color_gradients_host.argtypes = [C.POINTER(fp), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int64,
+                                                      C.c_int32, i64, fp]
+    lib.icpk_projective_reduce_colored.argtypes = [C.c_void_p, jp, kp, dp, dp, i64]
+    lib.icpk_align_projective_colored.argtypes = [C.c_void_p, jp, kp, dp, dp, C.POINTER(ProjectiveResult)]
+    lib.icpk_projective_pixels_colored.argtypes = [jp, dp, u16, C.c_int32, C.c_int32, C.POINTER(fp), C.c_int32, C.c_int32,
+                                                   C.c_float, C.c_float, dp, C.c_int64, C.c_int32, ip, fp, dp, fp, fp,
+                                                   C.POINTER(fp), kp]
     _lib = lib
     return lib
 
@@ -964,6 +990,153 @@ def projective_trace(ctx):
     n = ctx._chk(ctx._lib.icpk_get_projective_trace(ctx._h, buf, PROJECTIVE_MAX_ITERATIONS))
     return [dict(pose=np.array(buf[k].pose, np.float64).reshape(3, 4), sums=np.array(buf[k].sums, np.float64),
                  count=int(buf[k].count), status=int(buf[k].status)) for k in range(n)]
+
+
+# ---- the photometric term of the projective alignment (K26): functions of a context and three host-only ones ---------
+def default_projective_color_params(**kw):
+    """icpk_default_projective_color_params with the given fields replaced (lambda_geometric)."""
+    c = ProjectiveColorParams()
+    load().icpk_default_projective_color_params(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def _projective_color(color):
+    if color is None:
+        return default_projective_color_params()
+    return color if isinstance(color, ProjectiveColorParams) else default_projective_color_params(**dict(color))
+
+
+def set_pyramid_intensity(ctx, intensity):
+    """icpk_depth_pyramid_set_intensity: the (rows, cols) float32 image in [0, 1] beside the resident depth pyramid's
+    level 0; every level the depth pyramid has is built.  The next depth_front.build_pyramid drops them."""
+    img = _f(intensity)
+    if img.ndim != 2:
+        raise ValueError("intensity must be a (rows, cols) image")
+    ctx._chk(ctx._lib.icpk_depth_pyramid_set_intensity(ctx._h, _fp(img), img.shape[0], img.shape[1]))
+
+
+def pyramid_intensity(ctx, level):
+    """icpk_depth_pyramid_get_intensity: the level's (rows, cols) float32 intensities."""
+    r, c = C.c_int32(1), C.c_int32(1)
+    if ctx._lib.icpk_depth_pyramid_shape(ctx._h, int(level), C.byref(r), C.byref(c)) != OK:
+        r, c = C.c_int32(1), C.c_int32(1)  # (the call states its own refusal)
+    out = np.zeros((r.value, c.value), np.float32)
+    ctx._chk(ctx._lib.icpk_depth_pyramid_get_intensity(ctx._h, int(level), _fp(out)))
+    return out
+
+
+def intensity_pyramid_host(depth, intensity, level, params=None):
+    """icpk_intensity_pyramid_host (host only): level `level` of the intensity pyramid of the two (rows, cols) images."""
+    d, img = np.ascontiguousarray(depth, np.uint16), _f(intensity)
+    if d.ndim != 2 or d.shape != img.shape:
+        raise ValueError("depth and intensity must be (rows, cols) images of one shape")
+    p = params
+    if p is None:
+        p = PyramidParams()
+        load().icpk_default_pyramid_params(C.byref(p))
+    r, c = d.shape
+    for _ in range(max(int(level), 0)):
+        r, c = (r + 1) // 2, (c + 1) // 2
+    out = np.zeros((r, c), np.float32)
+    rc = load().icpk_intensity_pyramid_host(C.byref(p), d.ctypes.data_as(C.POINTER(C.c_uint16)), _fp(img), d.shape[0], d.shape[1],
+                                            int(level), _fp(out))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_intensity_pyramid_host")
+    return out
+
+
+def raycast_color_gradients(ctx, radius, min_neighbors=4, keep_sums=False):
+    """icpk_tsdf_raycast_color_gradients: the colour gradients of the last ray cast, kept on the device.  No host wait."""
+    ctx._chk(ctx._lib.icpk_tsdf_raycast_color_gradients(ctx._h, float(radius), int(min_neighbors),
+                                                        COLOR_KEEP_SUMS if keep_sums else 0))
+
+
+def get_raycast_color_gradients(ctx, sums=False):
+    """icpk_tsdf_get_raycast_color_gradients: (3, rows, cols) float32; sums=True: also the (rows, cols, 10) int64 words of
+    icpk_tsdf_get_raycast_color_gradient_sums."""
+    shape = ctx._tsdf_ray
+    if shape is None:
+        ctx._chk(ctx._lib.icpk_tsdf_get_raycast_color_gradients(ctx._h, None, None, None))  # (ICPK_E_NOT_SET)
+        raise IcpkError(E_NOT_SET, "no ray cast (tsdf_raycast)")
+    g = np.zeros((3,) + tuple(shape), np.float32)
+    ctx._chk(ctx._lib.icpk_tsdf_get_raycast_color_gradients(ctx._h, _fp(g[0]), _fp(g[1]), _fp(g[2])))
+    if not sums:
+        return g
+    S = np.zeros(tuple(shape) + (10,), np.int64)
+    ctx._chk(ctx._lib.icpk_tsdf_get_raycast_color_gradient_sums(ctx._h, S.ctypes.data_as(C.POINTER(C.c_int64))))
+    return g, S
+
+
+def raycast_color_gradients_host(view, radius, min_neighbors=4, first=0, count=None):
+    """icpk_raycast_color_gradients_host (host only): view (8, rows, cols) float32.  Returns (sums (count, 10) int64,
+    gradients (count, 3) float32, the number of pixels with a non-zero gradient)."""
+    v = _f(view)
+    if v.ndim != 3 or v.shape[0] != 8:
+        raise ValueError("view must be (8, rows, cols)")
+    rows, cols = v.shape[1:]
+    count = rows * cols - int(first) if count is None else int(count)
+    n = max(count, 0)
+    S, g = np.zeros((n, 10), np.int64), np.zeros((n, 3), np.float32)
+    fp = C.POINTER(C.c_float)
+    rc = load().icpk_raycast_color_gradients_host((fp * 8)(*[_fp(v[k]) for k in range(8)]), rows, cols, float(radius),
+                                                  int(min_neighbors), int(first), count, S.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  _fp(g))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_raycast_color_gradients_host")
+    return S, g, rc
+
+
+def projective_reduce_colored(ctx, pose, params=None, color=None, **kw):
+    """icpk_projective_reduce_colored: (28 float64 sums, pair count) of one evaluation of the joint step at the pose.
+    color: ProjectiveColorParams, a dict of its fields, or None for the defaults."""
+    p, c = _projective(params, kw), _projective_color(color)
+    P = _pose16(pose)
+    sums, n = np.zeros(28, np.float64), C.c_int64(-1)
+    dp = C.POINTER(C.c_double)
+    ctx._chk(ctx._lib.icpk_projective_reduce_colored(ctx._h, C.byref(p), C.byref(c), P.ctypes.data_as(dp), sums.ctypes.data_as(dp),
+                                                     C.byref(n)))
+    return sums, n.value
+
+
+def align_projective_colored(ctx, pose, params=None, color=None, **kw):
+    """icpk_align_projective_colored: align_projective with the joint step; projective_trace reads its iterations."""
+    p, c = _projective(params, kw), _projective_color(color)
+    P = _pose16(pose)
+    out, res = np.zeros(16, np.float64), ProjectiveResult()
+    dp = C.POINTER(C.c_double)
+    ctx._chk(ctx._lib.icpk_align_projective_colored(ctx._h, C.byref(p), C.byref(c), P.ctypes.data_as(dp), out.ctypes.data_as(dp),
+                                                    C.byref(res)))
+    return out.reshape(4, 4), res
+
+
+def projective_pixels_colored(params, pose, level, view, view_shape, view_fx, view_cx, view_pose, level_intensity, gradient,
+                              color=None, first=0, count=None, terms=False):
+    """icpk_projective_pixels_colored (host only): projective_pixels with the coloured rule 9.  view: EIGHT planes (the
+    eighth is the view's intensity); level_intensity: the level's (rows, cols) float32; gradient: (3, rows_v, cols_v)."""
+    img = np.ascontiguousarray(level, np.uint16)
+    rows_s, cols_s = img.shape
+    rows_v, cols_v = int(view_shape[0]), int(view_shape[1])
+    planes = [_f(view[k]).reshape(-1) for k in range(8)]
+    grads = [_f(gradient[k]).reshape(-1) for k in range(3)]
+    li = _f(level_intensity).reshape(-1)
+    if any(a.size != rows_v * cols_v for a in planes + grads) or li.size != rows_s * cols_s:
+        raise ValueError("every plane must hold rows x cols entries")
+    count = rows_s * cols_s - int(first) if count is None else int(count)
+    n = max(count, 0)
+    pixel, dist = np.zeros(n, np.int32), np.zeros(n, np.float32)
+    tm = np.zeros((n, 28), np.float64) if terms else None
+    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+    c = _projective_color(color)
+    rc = load().icpk_projective_pixels_colored(
+        C.byref(params), _pose16(pose).ctypes.data_as(dp), img.ctypes.data_as(C.POINTER(C.c_uint16)), rows_s, cols_s,
+        (fp * 7)(*[_fp(a) for a in planes[:7]]), rows_v, cols_v, view_fx, view_cx, _pose16(view_pose).ctypes.data_as(dp),
+        int(first), count, pixel.ctypes.data_as(C.POINTER(C.c_int32)), _fp(dist), None if tm is None else tm.ctypes.data_as(dp),
+        _fp(li), _fp(planes[7]), (fp * 3)(*[_fp(a) for a in grads]), C.byref(c))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_projective_pixels_colored")
+    return pixel, dist, tm, rc
 
 
 class Context:

@@ -19,7 +19,8 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_score.cpp", "kernels_score.hip", "icpk_fpfh.cpp", "kernels_fpfh.hip", "icpk_global.cpp",
            "icpk_color.cpp", "kernels_color.hip", "icpk_posegraph.cpp", "kernels_posegraph.hip",
            "icpk_tsdf.cpp", "kernels_tsdf.hip", "icpk_bilateral.cpp", "kernels_bilateral.hip",
-           "icpk_pyramid.cpp", "kernels_pyramid.hip", "icpk_projective.cpp", "kernels_projective.hip"]
+           "icpk_pyramid.cpp", "kernels_pyramid.hip", "icpk_projective.cpp", "kernels_projective.hip",
+           "kernels_pyramid_color.hip", "icpk_raycast_color.cpp", "kernels_raycast_color.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -522,6 +523,52 @@ def build_projective_host_sanitized(force=False):
     return PROJECTIVE_HOST_SANITIZED
 
 
+PROJECTIVE_COLOR_TEST = os.path.join(LIBDIR, "test_projective_color")
+
+
+def build_projective_color_test(force=False):
+    """Host-only C++ program over icp::Engine::setPyramidIntensity and icp::TsdfVolume::raycastColorGradients /
+    alignProjectiveColored (icp_align.hpp, icp_tsdf.hpp, K26) (g++, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_projective_color.cpp")
+    hdrs = [os.path.join(HERE, "include", h) for h in ("icp_align.hpp", "icp_tsdf.hpp")]
+    build()
+    newest = max(os.path.getmtime(p) for p in [src, LIB] + hdrs)
+    if not force and os.path.exists(PROJECTIVE_COLOR_TEST) and os.path.getmtime(PROJECTIVE_COLOR_TEST) >= newest:
+        return PROJECTIVE_COLOR_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", PROJECTIVE_COLOR_TEST])
+    return PROJECTIVE_COLOR_TEST
+
+
+PROJECTIVE_COLOR_HOST_SANITIZED = os.path.join(LIBDIR, "projective_color_host_sanitized")
+
+
+def build_projective_color_host_sanitized(force=False):
+    """DIAGNOSTIC, not part of build(): tests/cpp/projective_color_host_main.cpp (its own main, no GPU) with
+    icpk_pyramid.cpp, icpk_raycast_color.cpp and icpk_projective.cpp -- and so csrc/pyramid_rule.h, raycast_color_rule.h
+    and projective_rule.h -- compiled under -fsanitize=address,undefined on the host side; everything else
+    icpk_projective.cpp refers to (the pose inversion, the launchers its device entry points call) comes from libicpk.so
+    as it is.  The program calls the three host-only entry points of K26 alone.  Run the program it returns directly."""
+    src = os.path.join(ROOT, "tests", "cpp", "projective_color_host_main.cpp")
+    build()
+    host = ["icpk_pyramid.cpp", "icpk_raycast_color.cpp", "icpk_projective.cpp"]
+    deps = [src, LIB] + [os.path.join(CSRC, f) for f in host + ["pyramid_rule.h", "raycast_color_rule.h", "projective_rule.h"]]
+    if not force and os.path.exists(PROJECTIVE_COLOR_HOST_SANITIZED) and \
+            os.path.getmtime(PROJECTIVE_COLOR_HOST_SANITIZED) >= max(os.path.getmtime(p) for p in deps):
+        return PROJECTIVE_COLOR_HOST_SANITIZED
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-omit-frame-pointer", "-g"]
+    objs = []
+    for path, name in [(os.path.join(CSRC, f), f.rsplit(".", 1)[0] + "_color_sanitized.o") for f in host] + \
+            [(src, "projective_color_host_main.o")]:
+        objs.append(os.path.join(LIBDIR, name))
+        subprocess.check_call([hipcc] + FLAGS + san + ["-x", "hip", "-c", path, "-o", objs[-1]])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-fsanitize=address,undefined"] + objs +
+                          ["-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN", "-o", PROJECTIVE_COLOR_HOST_SANITIZED])
+    return PROJECTIVE_COLOR_HOST_SANITIZED
+
+
 THREADS_TEST = os.path.join(LIBDIR, "test_threads")
 
 
@@ -612,4 +659,5 @@ if __name__ == "__main__":
     print(build_bilateral_test(force="--force" in sys.argv))
     print(build_pyramid_test(force="--force" in sys.argv))
     print(build_projective_test(force="--force" in sys.argv))
+    print(build_projective_color_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

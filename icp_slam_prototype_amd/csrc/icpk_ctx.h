@@ -472,6 +472,11 @@ struct icpk_ctx {
   icpk::DevBuf<int32_t> proj_pixel;  // [rows_s cols_s]
   icpk::DevBuf<float> proj_dist;     // [rows_s cols_s]
   std::vector<icpk_projective_iter> proj_trace;
+  // K26: the intensity pyramid beside the depth pyramid (level l at pyr_off[l], floats), set by
+  // icpk_depth_pyramid_set_intensity and dropped by the next build; the K the resident depth pyramid was built with
+  icpk::DevBuf<float> pyr_int;
+  bool pyr_have_int = false;
+  int pyr_K = 0;
 };
 
 #define ICPK_HIP(ctx, call)                                                                      \
@@ -612,6 +617,9 @@ struct TsdfRayView {
 };
 // ICPK_E_NOT_SET (with the reason in ctx->err) without a volume or without a ray cast
 int tsdf_raycast_view(icpk_ctx* ctx, TsdfRayView* out);
+// K26, after tsdf_raycast_view has succeeded: whether the volume keeps intensities, and the three gradient planes of
+// icpk_tsdf_raycast_color_gradients for the current ray cast (nullptr without them)
+void tsdf_raycast_color_view(icpk_ctx* ctx, bool* color, const float** grad);
 
 // ---- icpk_batch.cpp: the lock-step machinery icpk_frames_batch.cpp shares ----
 bool batch_eligible(const icpk_ctx* ctx, const icpk_params* p);  // params the lock-step path runs

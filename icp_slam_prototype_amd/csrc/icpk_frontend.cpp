@@ -402,6 +402,7 @@ int icpk_depth_pyramid_build(icpk_ctx* ctx, const uint16_t* depth, int32_t rows,
   if (total > ctx->pyr.capacity()) ctx->pyr_levels = 0;  // (the old pyramid goes with its memory)
   if ((rc = ctx->pyr.reserve(ctx, total))) return rc;
   ctx->pyr_levels = 0;  // (nothing is resident until this call has enqueued everything)
+  ctx->pyr_have_int = false;  // (K26: the intensity levels belong to the pyramid they were set beside)
   uint16_t* const base = ctx->pyr;
   if (smooth) {  // K22 writes level 0
     ctx->frame_slot = -1;  // (the image buffers are shared with icpk_backproject_pair's resident frame)
@@ -422,6 +423,45 @@ int icpk_depth_pyramid_build(icpk_ctx* ctx, const uint16_t* depth, int32_t rows,
     ctx->pyr_off[l] = off[l];
   }
   ctx->pyr_levels = p.levels;
+  ctx->pyr_K = p.range_cutoff;
+  return ICPK_OK;
+}
+
+// ---- K26: the intensity pyramid beside it (include/icpk.h, THE INTENSITY PYRAMID RULE) ----
+int icpk_depth_pyramid_set_intensity(icpk_ctx* ctx, const float* intensity, int32_t rows, int32_t cols) {
+  if (!ctx || !intensity) return ICPK_E_ARG;
+  if (ctx->pyr_levels == 0) return fail(ctx, ICPK_E_NOT_SET, "no depth pyramid (icpk_depth_pyramid_build)");
+  if (rows != ctx->pyr_rows[0] || cols != ctx->pyr_cols[0]) return fail(ctx, ICPK_E_ARG, "the image's shape is not level 0's");
+  const size_t npix = (size_t)rows * cols;
+  for (size_t i = 0; i < npix; ++i)
+    if (!(intensity[i] >= 0.f && intensity[i] <= 1.f)) return fail(ctx, ICPK_E_ARG, "an intensity is not in [0, 1]");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const int L = ctx->pyr_levels;
+  const size_t total = ctx->pyr_off[L - 1] + (size_t)ctx->pyr_rows[L - 1] * ctx->pyr_cols[L - 1];
+  if (total > ctx->pyr_int.capacity()) ctx->pyr_have_int = false;  // (the old levels go with their memory)
+  if (int rc = ctx->pyr_int.reserve(ctx, total)) return rc;
+  ctx->pyr_have_int = false;
+  float* const base = ctx->pyr_int;
+  ICPK_HIP(ctx, hipMemcpyAsync(base, intensity, npix * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  for (int l = 0; l + 1 < L; ++l)
+    launch_intensity_pyramid(ctx->pyr + ctx->pyr_off[l], base + ctx->pyr_off[l], ctx->pyr_rows[l], ctx->pyr_cols[l],
+                             base + ctx->pyr_off[l + 1], ctx->pyr_K, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller's image has been consumed)
+  ctx->pyr_have_int = true;
+  return ICPK_OK;
+}
+
+int icpk_depth_pyramid_get_intensity(icpk_ctx* ctx, int32_t level, float* out) {
+  if (!ctx || !out) return ICPK_E_ARG;
+  if (ctx->pyr_levels == 0 || !ctx->pyr_have_int)
+    return fail(ctx, ICPK_E_NOT_SET, "no intensity pyramid (icpk_depth_pyramid_set_intensity)");
+  if (level < 0 || level >= ctx->pyr_levels) return fail(ctx, ICPK_E_ARG, "the pyramid has no such level");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  ICPK_HIP(ctx, hipMemcpyAsync(out, ctx->pyr_int + ctx->pyr_off[level],
+                               (size_t)ctx->pyr_rows[level] * ctx->pyr_cols[level] * sizeof(float), hipMemcpyDeviceToHost,
+                               ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ICPK_OK;
 }
 

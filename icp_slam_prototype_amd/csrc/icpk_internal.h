@@ -452,6 +452,13 @@ void launch_depth_bilateral(const uint16_t* in, uint16_t* out, int rows, int col
 // K24, THE PYRAMID RULE: level l (rows x cols) gives level l + 1 into out1 and, unless out2 is null, level l + 2 into
 // out2, in one launch (device; three different images)
 void launch_depth_pyramid(const uint16_t* in, int rows, int cols, uint16_t* out1, uint16_t* out2, int K, hipStream_t s);
+// kernels_pyramid_color.hip -- K26: level l + 1 of the intensity pyramid from level l of both pyramids
+void launch_intensity_pyramid(const uint16_t* depth, const float* inten, int rows, int cols, float* out, int K,
+                              hipStream_t s);
+// kernels_raycast_color.hip -- K26: the colour gradients of a ray-cast view (8 planes of rows x cols floats) into three
+// planes of grad, and the ten int64 per pixel into sums unless it is nullptr
+void launch_raycast_color_gradients(const float* maps, int rows, int cols, float radius, int min_neighbors, float* grad,
+                                    long long* sums, hipStream_t s);
 
 // ---- deferred set-up launches of the frame-batch mode ------------------------------------------------
 // A lock-step group's pairs go through the SAME sequence of small set-up kernels (ingest x 2, loop-state
@@ -1028,6 +1035,11 @@ struct ProjArgs {
   double* partial;        // [NP2L][RED_MAX_BLOCKS]
   int* pcount;            // [RED_MAX_BLOCKS]
   const ProjState* st;
+  // K26, the coloured step (grad == nullptr: the geometric one): the level's intensities, the view's three gradient
+  // planes (npix_v floats each) and lambda_geometric; the view's intensity is plane 7 of maps
+  const float* inten;
+  const float* grad;
+  float lambda_geometric;
 };
 // red_blocks(rows cols) workgroups: the per-block partials of one evaluation at the state's pose (nothing once done)
 void launch_proj_reduce(const ProjArgs& a, hipStream_t s);

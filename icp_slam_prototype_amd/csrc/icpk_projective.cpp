@@ -2,7 +2,9 @@
 // kernels_projective.hip): the defaults, the refusals, the rule over host images through the header the kernel includes
 // (icpk_projective_pixels -- the host-only half: it needs no context and no device), and the three entry points that
 // run on the device over a level of the resident pyramid (K24) and the maps of the last ray cast (K20).  They read
-// both where they lie and write only the scratch the context keeps for them.
+// both where they lie and write only the scratch the context keeps for them.  K26's coloured entry points
+// (icpk_projective_reduce_colored, icpk_align_projective_colored, icpk_projective_pixels_colored) share every line with
+// them but the refusals of their own and the choice of rule 9.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -93,24 +95,88 @@ int begin_state(icpk_ctx* ctx, const double pose[16], ProjArgs* a) {
   return ICPK_OK;
 }
 
-}  // namespace
+bool lambda_ok(float l) { return std::isfinite(l) && l >= 0.f && l <= 1.f; }
 
-extern "C" {
-
-void icpk_default_projective_params(icpk_projective_params* p) {
-  if (!p) return;
-  p->level = 0;
-  p->fx = 468.60f, p->cx = 318.27f;
-  p->max_iterations = 10;
-  p->max_dist = 0.5f;
-  p->min_normal_cos = -2.f;
-  p->min_pairs = 6;
+icpk_projective_color_params color_or_defaults(const icpk_projective_color_params* color) {
+  icpk_projective_color_params c;
+  icpk_default_projective_color_params(&c);
+  if (color) c = *color;
+  return c;
 }
 
-int icpk_projective_pixels(const icpk_projective_params* params, const double pose[16], const uint16_t* level,
-                           int32_t rows_s, int32_t cols_s, const float* const view[7], int32_t rows_v, int32_t cols_v,
-                           float fx_v, float cx_v, const double view_pose[16], int64_t first, int32_t count,
-                           int32_t* pixel, float* dist, double* terms) {
+// K26: prepare's refusals first, unchanged; then what the coloured step needs beside them
+int prepare_colored(icpk_ctx* ctx, const icpk_projective_params& p, const icpk_projective_color_params& c, const double* pose,
+                    ProjArgs* a) {
+  if (!lambda_ok(c.lambda_geometric)) return fail(ctx, ICPK_E_ARG, "lambda_geometric must be finite and in [0, 1]");
+  if (int rc = prepare(ctx, p, pose, a)) return rc;
+  bool color = false;
+  const float* grad = nullptr;
+  tsdf_raycast_color_view(ctx, &color, &grad);
+  if (!color) return fail(ctx, ICPK_E_ARG, "the volume keeps no intensities");
+  if (!ctx->pyr_have_int) return fail(ctx, ICPK_E_NOT_SET, "no intensity pyramid (icpk_depth_pyramid_set_intensity)");
+  if (!grad) return fail(ctx, ICPK_E_NOT_SET, "no colour gradients of this ray cast (icpk_tsdf_raycast_color_gradients)");
+  a->inten = ctx->pyr_int + ctx->pyr_off[p.level];
+  a->grad = grad;
+  a->lambda_geometric = c.lambda_geometric;
+  return ICPK_OK;
+}
+
+// one evaluation at the state's pose: a.grad decides the step
+int reduce_impl(icpk_ctx* ctx, ProjArgs& a, const double* pose, double sums[28], int64_t* count) {
+  if (int rc = begin_state(ctx, pose, &a)) return rc;
+  launch_proj_reduce(a, ctx->stream);
+  launch_reduce_final(a.partial, a.pcount, red_blocks(a.rows * a.cols), NP2L, ctx->proj_out, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  ICPK_HIP(ctx, hipMemcpyAsync(ctx->proj_out_host.get(), ctx->proj_out.get(), (NP2L + 1) * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (sums) std::memcpy(sums, ctx->proj_out_host.get(), NP2L * sizeof(double));
+  if (count) std::memcpy(count, ctx->proj_out_host.get() + NP2L, sizeof(int64_t));
+  return ICPK_OK;
+}
+
+// the loop: a.grad decides the reduce launch, everything else is one code
+int align_impl(icpk_ctx* ctx, const icpk_projective_params& p, ProjArgs& a, const double* pose_in, double pose_out[16],
+               icpk_projective_result* result) {
+  if (int rc = begin_state(ctx, pose_in, &a)) return rc;
+  // every launch of every iteration up front; once the state says done the rest are no-ops
+  const int B = red_blocks(a.rows * a.cols);
+  for (int k = 0; k < p.max_iterations; ++k) {
+    launch_proj_reduce(a, ctx->stream);
+    launch_proj_step(a.partial, a.pcount, B, ctx->proj_block, k, p.min_pairs, ctx->stream);
+  }
+  ICPK_HIP(ctx, hipGetLastError());
+  // one copy (state + the trace entries that can have been written) and one wait
+  ProjBlock* h = ctx->proj_block_host;
+  const size_t bytes = offsetof(ProjBlock, trace) + (size_t)p.max_iterations * sizeof(ProjIter);
+  ICPK_HIP(ctx, hipMemcpyAsync(h, ctx->proj_block.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int evaluated = h->st.done ? h->st.iterations + 1 : h->st.iterations;
+  ctx->proj_trace.resize((size_t)evaluated);
+  if (evaluated > 0) std::memcpy(ctx->proj_trace.data(), h->trace, (size_t)evaluated * sizeof(ProjIter));
+  if (pose_out) {
+    std::memcpy(pose_out, h->st.E, 12 * sizeof(double));
+    pose_out[12] = pose_out[13] = pose_out[14] = 0.0, pose_out[15] = 1.0;
+  }
+  if (result) {
+    const ProjIter& last = h->trace[evaluated - 1];  // (max_iterations >= 1: at least one was evaluated)
+    result->status = h->st.status;
+    result->iterations = h->st.iterations;
+    result->count = last.count;
+    result->mean_dist = last.count > 0 ? last.sums[27] / (double)last.count : 0.0;
+  }
+  return h->st.status;
+}
+
+// rules 1 - 9 over host images; cv == nullptr: the geometric terms
+struct HostColor {
+  const float *level_intensity, *view_intensity, *gx, *gy, *gz;
+  double lg, lc;
+};
+int pixels_impl(const icpk_projective_params* params, const double pose[16], const uint16_t* level, int32_t rows_s,
+                int32_t cols_s, const float* const view[7], int32_t rows_v, int32_t cols_v, float fx_v, float cx_v,
+                const double view_pose[16], int64_t first, int32_t count, int32_t* pixel, float* dist, double* terms,
+                const HostColor* cv) {
   if (!level || !view || !view_pose || !pixel || !dist || count < 0 || first < 0) return ICPK_E_ARG;
   for (int k = 0; k < 7; ++k)
     if (!view[k]) return ICPK_E_ARG;
@@ -141,11 +207,58 @@ int icpk_projective_pixels(const icpk_projective_params* params, const double po
     pairs += j >= 0;
     if (terms) {
       double v[28] = {0.0};
-      if (j >= 0) proj_add_terms(pr, v);
+      if (j >= 0 && cv) {
+        const ProjColor pc{{cv->gx[j], cv->gy[j], cv->gz[j]}, cv->view_intensity[j], cv->level_intensity[i]};
+        proj_add_terms_colored(pr, pc, cv->lg, cv->lc, v);
+      } else if (j >= 0) {
+        proj_add_terms(pr, v);
+      }
       std::memcpy(terms + (size_t)e * 28, v, sizeof(v));
     }
   }
   return pairs;
+}
+
+}  // namespace
+
+extern "C" {
+
+void icpk_default_projective_color_params(icpk_projective_color_params* c) {
+  if (!c) return;
+  c->lambda_geometric = 0.968f;
+}
+
+void icpk_default_projective_params(icpk_projective_params* p) {
+  if (!p) return;
+  p->level = 0;
+  p->fx = 468.60f, p->cx = 318.27f;
+  p->max_iterations = 10;
+  p->max_dist = 0.5f;
+  p->min_normal_cos = -2.f;
+  p->min_pairs = 6;
+}
+
+int icpk_projective_pixels(const icpk_projective_params* params, const double pose[16], const uint16_t* level,
+                           int32_t rows_s, int32_t cols_s, const float* const view[7], int32_t rows_v, int32_t cols_v,
+                           float fx_v, float cx_v, const double view_pose[16], int64_t first, int32_t count,
+                           int32_t* pixel, float* dist, double* terms) {
+  return pixels_impl(params, pose, level, rows_s, cols_s, view, rows_v, cols_v, fx_v, cx_v, view_pose, first, count, pixel, dist,
+                     terms, nullptr);
+}
+
+int icpk_projective_pixels_colored(const icpk_projective_params* params, const double pose[16], const uint16_t* level,
+                                   int32_t rows_s, int32_t cols_s, const float* const view[7], int32_t rows_v,
+                                   int32_t cols_v, float fx_v, float cx_v, const double view_pose[16], int64_t first,
+                                   int32_t count, int32_t* pixel, float* dist, double* terms, const float* level_intensity,
+                                   const float* view_intensity, const float* const gradient[3],
+                                   const icpk_projective_color_params* color) {
+  if (!level_intensity || !view_intensity || !gradient || !gradient[0] || !gradient[1] || !gradient[2]) return ICPK_E_ARG;
+  const icpk_projective_color_params c = color_or_defaults(color);
+  if (!lambda_ok(c.lambda_geometric)) return ICPK_E_ARG;
+  const double lg = (double)c.lambda_geometric;
+  const HostColor cv{level_intensity, view_intensity, gradient[0], gradient[1], gradient[2], lg, 1.0 - lg};
+  return pixels_impl(params, pose, level, rows_s, cols_s, view, rows_v, cols_v, fx_v, cx_v, view_pose, first, count, pixel, dist,
+                     terms, &cv);
 }
 
 int icpk_projective_associate(icpk_ctx* ctx, const icpk_projective_params* params, const double pose[16], int32_t* pixel,
@@ -174,16 +287,17 @@ int icpk_projective_reduce(icpk_ctx* ctx, const icpk_projective_params* params, 
   const icpk_projective_params p = params_or_defaults(params);
   ProjArgs a{};
   if (int rc = prepare(ctx, p, pose, &a)) return rc;
-  if (int rc = begin_state(ctx, pose, &a)) return rc;
-  launch_proj_reduce(a, ctx->stream);
-  launch_reduce_final(a.partial, a.pcount, red_blocks(a.rows * a.cols), NP2L, ctx->proj_out, ctx->stream);
-  ICPK_HIP(ctx, hipGetLastError());
-  ICPK_HIP(ctx, hipMemcpyAsync(ctx->proj_out_host.get(), ctx->proj_out.get(), (NP2L + 1) * sizeof(double), hipMemcpyDeviceToHost,
-                               ctx->stream));
-  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (sums) std::memcpy(sums, ctx->proj_out_host.get(), NP2L * sizeof(double));
-  if (count) std::memcpy(count, ctx->proj_out_host.get() + NP2L, sizeof(int64_t));
-  return ICPK_OK;
+  return reduce_impl(ctx, a, pose, sums, count);
+}
+
+int icpk_projective_reduce_colored(icpk_ctx* ctx, const icpk_projective_params* params,
+                                   const icpk_projective_color_params* color, const double pose[16], double sums[28],
+                                   int64_t* count) {
+  if (!ctx) return ICPK_E_ARG;
+  const icpk_projective_params p = params_or_defaults(params);
+  ProjArgs a{};
+  if (int rc = prepare_colored(ctx, p, color_or_defaults(color), pose, &a)) return rc;
+  return reduce_impl(ctx, a, pose, sums, count);
 }
 
 int icpk_align_projective(icpk_ctx* ctx, const icpk_projective_params* params, const double pose_in[16], double pose_out[16],
@@ -192,34 +306,17 @@ int icpk_align_projective(icpk_ctx* ctx, const icpk_projective_params* params, c
   const icpk_projective_params p = params_or_defaults(params);
   ProjArgs a{};
   if (int rc = prepare(ctx, p, pose_in, &a)) return rc;
-  if (int rc = begin_state(ctx, pose_in, &a)) return rc;
-  // every launch of every iteration up front; once the state says done the rest are no-ops
-  const int B = red_blocks(a.rows * a.cols);
-  for (int k = 0; k < p.max_iterations; ++k) {
-    launch_proj_reduce(a, ctx->stream);
-    launch_proj_step(a.partial, a.pcount, B, ctx->proj_block, k, p.min_pairs, ctx->stream);
-  }
-  ICPK_HIP(ctx, hipGetLastError());
-  // one copy (state + the trace entries that can have been written) and one wait
-  ProjBlock* h = ctx->proj_block_host;
-  const size_t bytes = offsetof(ProjBlock, trace) + (size_t)p.max_iterations * sizeof(ProjIter);
-  ICPK_HIP(ctx, hipMemcpyAsync(h, ctx->proj_block.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
-  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const int evaluated = h->st.done ? h->st.iterations + 1 : h->st.iterations;
-  ctx->proj_trace.resize((size_t)evaluated);
-  if (evaluated > 0) std::memcpy(ctx->proj_trace.data(), h->trace, (size_t)evaluated * sizeof(ProjIter));
-  if (pose_out) {
-    std::memcpy(pose_out, h->st.E, 12 * sizeof(double));
-    pose_out[12] = pose_out[13] = pose_out[14] = 0.0, pose_out[15] = 1.0;
-  }
-  if (result) {
-    const ProjIter& last = h->trace[evaluated - 1];  // (max_iterations >= 1: at least one was evaluated)
-    result->status = h->st.status;
-    result->iterations = h->st.iterations;
-    result->count = last.count;
-    result->mean_dist = last.count > 0 ? last.sums[27] / (double)last.count : 0.0;
-  }
-  return h->st.status;
+  return align_impl(ctx, p, a, pose_in, pose_out, result);
+}
+
+int icpk_align_projective_colored(icpk_ctx* ctx, const icpk_projective_params* params,
+                                  const icpk_projective_color_params* color, const double pose_in[16], double pose_out[16],
+                                  icpk_projective_result* result) {
+  if (!ctx) return ICPK_E_ARG;
+  const icpk_projective_params p = params_or_defaults(params);
+  ProjArgs a{};
+  if (int rc = prepare_colored(ctx, p, color_or_defaults(color), pose_in, &a)) return rc;
+  return align_impl(ctx, p, a, pose_in, pose_out, result);
 }
 
 int icpk_get_projective_trace(icpk_ctx* ctx, icpk_projective_iter* out, int32_t cap) {

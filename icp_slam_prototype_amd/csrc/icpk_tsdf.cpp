@@ -50,6 +50,11 @@ struct icpk_tsdf_state {
   int ray_rows = 0, ray_cols = 0;
   float ray_fx = 0.f, ray_cx = 0.f;  // ... and the camera and pose they were cast with (K25 projects into them)
   double ray_pose[16] = {0};
+  // K26, behind the maps: the colour gradients of the current ray cast (3 planes) and, with ICPK_COLOR_KEEP_SUMS, the
+  // ten int64 per pixel; both dropped by the next ray cast and with the maps
+  DevBuf<float> ray_grad;
+  DevBuf<long long> ray_grad_sums;
+  bool have_ray_grad = false, have_ray_grad_sums = false;
   // the mesh of the last mesh extraction (K21): 7 planes of mesh_vcap floats, every vertex's key (owner voxel, edge
   // type), 3 x mesh_tcap indices; and its own per-chunk counts, scans and totals, so that K19's stay as they are
   DevBuf<float> mesh;
@@ -80,6 +85,12 @@ int icpk::tsdf_raycast_view(icpk_ctx* ctx, TsdfRayView* out) {
   out->fx = v->ray_fx, out->cx = v->ray_cx;
   std::memcpy(out->pose, v->ray_pose, sizeof(out->pose));
   return ICPK_OK;
+}
+
+void icpk::tsdf_raycast_color_view(icpk_ctx* ctx, bool* color, const float** grad) {
+  const icpk_tsdf_state* v = ctx->tsdf;
+  *color = v && (v->p.flags & ICPK_TSDF_COLOR);
+  *grad = v && v->have_raycast && v->have_ray_grad ? v->ray_grad.get() : nullptr;
 }
 
 namespace {
@@ -723,6 +734,7 @@ int icpk_tsdf_raycast(icpk_ctx* ctx, const icpk_tsdf_raycast_params* params, con
     return rc;
   }
   v->have_raycast = false;  // (the planes change place with the image's size)
+  v->have_ray_grad = v->have_ray_grad_sums = false;  // (K26: the gradients are those of the maps they were made from)
   a.v = make_planes(v->p, v->tsdf, v->weight, v->intensity_plane(), rp.min_weight);
   a.maps = v->ray_maps;
   a.tiles_x = tsdf_ray_tiles(rp.cols);
@@ -754,6 +766,57 @@ int icpk_tsdf_get_raycast(icpk_ctx* ctx, float* x, float* y, float* z, float* nx
   for (int k = 0; k < 8; ++k)
     if (out[k])
       ICPK_HIP(ctx, hipMemcpyAsync(out[k], v->ray_maps + (size_t)k * npix, npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+// ---- K26: the colour gradients of the view (include/icpk.h, THE VIEW GRADIENT RULE; kernels_raycast_color.hip) ----
+int icpk_tsdf_raycast_color_gradients(icpk_ctx* ctx, float radius, int32_t min_neighbors, int32_t flags) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  if (!v->have_raycast) return fail(ctx, ICPK_E_NOT_SET, "no ray cast (icpk_tsdf_raycast)");
+  if (!(v->p.flags & ICPK_TSDF_COLOR)) return fail(ctx, ICPK_E_ARG, "the volume keeps no intensities");
+  if (!positive(radius) || min_neighbors < 1 || (flags & ~ICPK_COLOR_KEEP_SUMS))
+    return fail(ctx, ICPK_E_ARG, "radius must be finite and > 0, min_neighbors >= 1, flags known");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t npix = (size_t)v->ray_rows * v->ray_cols;
+  const bool keep = (flags & ICPK_COLOR_KEEP_SUMS) != 0;
+  v->have_ray_grad = v->have_ray_grad_sums = false;
+  if (int rc = v->ray_grad.reserve(ctx, 3 * npix)) return rc;
+  if (keep)
+    if (int rc = v->ray_grad_sums.reserve(ctx, (size_t)COLOR_SUMS * npix)) return rc;
+  launch_raycast_color_gradients(v->ray_maps, v->ray_rows, v->ray_cols, radius, min_neighbors, v->ray_grad,
+                                 keep ? v->ray_grad_sums.get() : nullptr, ctx->stream);
+  ICPK_HIP(ctx, hipGetLastError());
+  v->have_ray_grad = true;
+  v->have_ray_grad_sums = keep;
+  return ICPK_OK;
+}
+
+int icpk_tsdf_get_raycast_color_gradients(icpk_ctx* ctx, float* gx, float* gy, float* gz) {
+  if (!ctx) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v || !v->have_raycast || !v->have_ray_grad)
+    return fail(ctx, ICPK_E_NOT_SET, "no colour gradients of the view (icpk_tsdf_raycast_color_gradients)");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t npix = (size_t)v->ray_rows * v->ray_cols;
+  float* const out[3] = {gx, gy, gz};
+  for (int k = 0; k < 3; ++k)
+    if (out[k])
+      ICPK_HIP(ctx, hipMemcpyAsync(out[k], v->ray_grad + (size_t)k * npix, npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ICPK_OK;
+}
+
+int icpk_tsdf_get_raycast_color_gradient_sums(icpk_ctx* ctx, int64_t* sums) {
+  if (!ctx || !sums) return ICPK_E_ARG;
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v || !v->have_raycast || !v->have_ray_grad || !v->have_ray_grad_sums)
+    return fail(ctx, ICPK_E_NOT_SET, "no kept sums (icpk_tsdf_raycast_color_gradients with ICPK_COLOR_KEEP_SUMS)");
+  ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t npix = (size_t)v->ray_rows * v->ray_cols;
+  ICPK_HIP(ctx, hipMemcpyAsync(sums, v->ray_grad_sums.get(), npix * COLOR_SUMS * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return ICPK_OK;
 }

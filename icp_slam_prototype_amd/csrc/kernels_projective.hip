@@ -42,8 +42,10 @@ __device__ __forceinline__ ProjPose proj_pose(const ProjState* __restrict__ st) 
 
 }  // namespace
 
-// WITH_NORMAL: rule 8 is on (four more depth loads per paired pixel); the default path is compiled without it
-template <bool WITH_NORMAL>
+// WITH_NORMAL: rule 8 is on (four more depth loads per paired pixel); the default path is compiled without it.
+// COLORED (K26): rule 9 is K17's joint step -- one more coalesced float per pixel (the level's intensity, prefetched
+// with the depth) and four more gathers per pair (the view's intensity and its three gradient planes at j).
+template <bool WITH_NORMAL, bool COLORED>
 __global__ __launch_bounds__(RED_THREADS) void proj_reduce_kernel(const ProjArgs a) {
   if (a.st->done) return;  // (uniform)
   const int npix = a.rows * a.cols;
@@ -51,6 +53,9 @@ __global__ __launch_bounds__(RED_THREADS) void proj_reduce_kernel(const ProjArgs
   int i = (int)blockIdx.x * RED_THREADS + (int)threadIdx.x;
   // a lane's first depth is asked for before the pose is read: two cold round trips side by side
   uint16_t d_next = i < npix ? a.depth[i] : (uint16_t)0;
+  float I_next = COLORED && i < npix ? a.inten[i] : 0.f;
+  const size_t nv = (size_t)a.rows_v * a.cols_v;
+  const double lg = (double)a.lambda_geometric, lc = 1.0 - lg;
   const ProjLevel lv{a.depth, a.rows, a.cols, a.fx, a.cx};
   const ProjView vw = proj_view(a);
   const ProjPose E = proj_pose(a.st);
@@ -61,11 +66,21 @@ __global__ __launch_bounds__(RED_THREADS) void proj_reduce_kernel(const ProjArgs
   int cnt = 0;
   for (; i < npix; i += P) {
     const uint16_t d = d_next;
-    if (i + P < npix) d_next = a.depth[i + P];  // the NEXT pixel is on its way while this one is consumed
+    const float Is = I_next;
+    if (i + P < npix) {  // the NEXT pixel is on its way while this one is consumed
+      d_next = a.depth[i + P];
+      if (COLORED) I_next = a.inten[i + P];
+    }
     const int r = i / a.cols, c = i - r * a.cols;
     ProjPair pr;
-    if (proj_pixel<WITH_NORMAL>(lv, vw, E, g, r, c, d, &pr) >= 0) {
-      proj_add_terms(pr, v);
+    const int j = proj_pixel<WITH_NORMAL>(lv, vw, E, g, r, c, d, &pr);
+    if (j >= 0) {
+      if (COLORED) {
+        const ProjColor pc{{a.grad[j], a.grad[nv + j], a.grad[2 * nv + j]}, a.maps[7 * nv + j], Is};
+        proj_add_terms_colored(pr, pc, lg, lc, v);
+      } else {
+        proj_add_terms(pr, v);
+      }
       ++cnt;
     }
   }
@@ -74,10 +89,13 @@ __global__ __launch_bounds__(RED_THREADS) void proj_reduce_kernel(const ProjArgs
 
 void launch_proj_reduce(const ProjArgs& a, hipStream_t s) {
   const int B = red_blocks(a.rows * a.cols);
-  if (a.min_normal_cos > -1.f)
-    hipLaunchKernelGGL(proj_reduce_kernel<true>, dim3(B), dim3(RED_THREADS), 0, s, a);
-  else
-    hipLaunchKernelGGL(proj_reduce_kernel<false>, dim3(B), dim3(RED_THREADS), 0, s, a);
+  const bool normal = a.min_normal_cos > -1.f;
+  void (*kernel)(const ProjArgs) = proj_reduce_kernel<false, false>;
+  if (a.grad)  // the coloured step
+    kernel = normal ? proj_reduce_kernel<true, true> : proj_reduce_kernel<false, true>;
+  else if (normal)
+    kernel = proj_reduce_kernel<true, false>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(RED_THREADS), 0, s, a);
 }
 
 // canonical stage 2 (slot b = the sums of block b, +0.0 beyond nblocks, one slot per lane), then the loop rule

@@ -141,6 +141,46 @@ ICPK_HD void proj_add_terms(const ProjPair& pr, double (&v)[28]) {
   v[27] += (double)pr.dist;
 }
 
+// what the coloured rule 9 (K26) reads beside the pair: the view's gradient and intensity at j, the level's at i
+struct ProjColor {
+  float g[3], It, Is;
+};
+
+// rule 9 of the coloured path: K17's joint terms of an accepted pair, ICPK_NP2L layout, added to v.  lg = 1, lc = 0
+// adds proj_add_terms' values bit for bit (x + 0.0 == x for every x a sum that started at +0.0 can hold).
+ICPK_HD void proj_add_terms_colored(const ProjPair& pr, const ProjColor& pc, double lg, double lc, double (&v)[28]) {
+  const double p0 = pr.p[0], p1 = pr.p[1], p2 = pr.p[2];
+  const double n0 = pr.n[0], n1 = pr.n[1], n2 = pr.n[2];
+  const double g0 = pc.g[0], g1 = pc.g[1], g2 = pc.g[2];
+  const double e0 = p0 - (double)pr.m[0], e1 = p1 - (double)pr.m[1], e2 = p2 - (double)pr.m[2];
+  const double h = (e0 * n0 + e1 * n1) + e2 * n2;
+  double G[6], C[6];
+  G[0] = p1 * n2 - p2 * n1;
+  G[1] = p2 * n0 - p0 * n2;
+  G[2] = p0 * n1 - p1 * n0;
+  G[3] = n0;
+  G[4] = n1;
+  G[5] = n2;
+  const double u0 = e0 - h * n0, u1 = e1 - h * n1, u2 = e2 - h * n2;
+  const double rc = ((double)pc.It + ((g0 * u0 + g1 * u1) + g2 * u2)) - (double)pc.Is;
+  const double gn = (g0 * n0 + g1 * n1) + g2 * n2;
+  const double M0 = g0 - gn * n0, M1 = g1 - gn * n1, M2 = g2 - gn * n2;
+  C[0] = p1 * M2 - p2 * M1;
+  C[1] = p2 * M0 - p0 * M2;
+  C[2] = p0 * M1 - p1 * M0;
+  C[3] = M0;
+  C[4] = M1;
+  C[5] = M2;
+  int k = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a)
+#pragma unroll
+    for (int b = a; b < 6; ++b) v[k++] += lg * (G[a] * G[b]) + lc * (C[a] * C[b]);
+#pragma unroll
+  for (int a = 0; a < 6; ++a) v[21 + a] += lg * (G[a] * h) + lc * (C[a] * rc);
+  v[27] += (double)pr.dist;
+}
+
 // the loop's update E' = dT E in double (rows of [R | t], 12 entries): 3-term products
 ICPK_HD void proj_compose(const double dR[9], const double dt[3], const double E[12], double out[12]) {
   for (int r = 0; r < 3; ++r) {

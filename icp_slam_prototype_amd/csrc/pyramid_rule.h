@@ -47,4 +47,24 @@ ICPK_HD uint16_t pyramid_pixel(int K, Tap tap) {
   return (uint16_t)(dc + pyramid_floor_div(2 * D + S, 2 * S));
 }
 
+// THE INTENSITY PYRAMID RULE (K26) for one pixel of level l + 1.  dtap as above; itap(dy, dx): the intensity of level l
+// at that offset, asked for only where the depth tap counts (so never outside the image).  The taps that count and
+// their weights are pyramid_pixel's; integers up to the one final division.  |c_q| <= 2^15 and S <= 16: N fits an int.
+template <class DTap, class ITap>
+ICPK_HD float pyramid_intensity_pixel(int K, DTap dtap, ITap itap) {
+  const int dc = dtap(0, 0);
+  if (dc == 0) return 0.f;  // the mask is the depth level's
+  int S = 0, N = 0;
+  for (int dy = -1; dy <= 1; ++dy)
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int dq = dtap(dy, dx);
+      const int diff = dq - dc, k = diff < 0 ? -diff : diff;
+      if (dq == 0 || k >= K) continue;
+      const int w = (2 - (dy < 0 ? -dy : dy)) * (2 - (dx < 0 ? -dx : dx));
+      S += w;
+      N += w * (int)__builtin_rint((double)itap(dy, dx) * 32768.0);
+    }
+  return (float)((double)N / ((double)S * 32768.0));
+}
+
 }  // namespace icpk

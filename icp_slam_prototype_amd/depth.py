@@ -131,13 +131,16 @@ def pyramid_host(depth, level, params=None):
     return out
 
 
-def build_pyramid(ctx, depth, params=None, smooth=None):
+def build_pyramid(ctx, depth, params=None, smooth=None, intensity=None):
     """icpk_depth_pyramid_build: the pyramid of the frame on the device, resident until the next build.  smooth: a
-    bilateral_params object -- level 0 is then the frame after K22; None: the frame as given.  Returns the list of the
-    levels' (rows, cols)."""
+    bilateral_params object -- level 0 is then the frame after K22; None: the frame as given.  intensity: the frame's
+    (rows, cols) float32 image in [0, 1], set beside the pyramid (binding.set_pyramid_intensity; it is never smoothed).
+    Returns the list of the levels' (rows, cols)."""
     depth = _image(depth)
     ctx._chk(ctx._lib.icpk_depth_pyramid_build(ctx._h, depth.ctypes.data_as(_u16), depth.shape[0], depth.shape[1],
                                                _ref(params), _ref(smooth)))
+    if intensity is not None:
+        binding.set_pyramid_intensity(ctx, intensity)
     return pyramid_shapes(depth.shape, 3 if params is None else params.levels)
 
 

@@ -108,6 +108,12 @@ class Engine {
     const int rc = icpk_depth_pyramid_shape(ctx_, level, rows, cols);
     return rc != ICPK_OK || !out ? rc : icpk_depth_pyramid_get(ctx_, level, out);
   }
+  // the frame's intensities (rows x cols floats in [0, 1], level 0's shape) beside the resident pyramid, every level
+  // built (icpk_depth_pyramid_set_intensity, K26); the next buildDepthPyramid drops them.  out: one level of them
+  int setPyramidIntensity(const float* intensity, int rows, int cols) {
+    return icpk_depth_pyramid_set_intensity(ctx_, intensity, rows, cols);
+  }
+  int pyramidIntensityLevel(int level, float* out) { return icpk_depth_pyramid_get_intensity(ctx_, level, out); }
   // ... and the cloud of a level read where it lies (icpk_depth_pyramid_backproject): fx, cx are the LEVEL-0 intrinsics.
   // Returns the number of points or a negative status.
   int backprojectPyramidLevel(int level, float fx, float cx, const float* offset, int which, int normalsMode = -1) {

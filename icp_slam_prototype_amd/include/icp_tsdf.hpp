@@ -157,7 +157,21 @@ class TsdfVolume {
     dist.assign((size_t)rows * cols, 0.f);
     return icpk_projective_associate(eng_.ctx(), &p, pose, pixel.data(), dist.data());
   }
-  // the iterations the last alignProjective evaluated: E_k, the sums and count at E_k, the status
+  // K26: the colour gradients of the last ray cast (a colour volume), kept on the device behind the maps; no host wait.
+  // gx / gy / gz (any may be null): rows x cols floats of that ray cast
+  int raycastColorGradients(float radius, int minNeighbors = 4, int flags = 0) {
+    return icpk_tsdf_raycast_color_gradients(eng_.ctx(), radius, minNeighbors, flags);
+  }
+  int getRaycastColorGradients(float* gx, float* gy, float* gz) {
+    return icpk_tsdf_get_raycast_color_gradients(eng_.ctx(), gx, gy, gz);
+  }
+  // alignProjective with K17's photometric term beside every pair: it needs Engine::setPyramidIntensity and
+  // raycastColorGradients for the current ray cast.  color null: the defaults.  projectiveTrace reads its iterations
+  int alignProjectiveColored(const icpk_projective_params& p, const icpk_projective_color_params* color, const double* poseIn,
+                             double* poseOut, icpk_projective_result* result = nullptr) {
+    return icpk_align_projective_colored(eng_.ctx(), &p, color, poseIn, poseOut, result);
+  }
+  // the iterations the last alignProjective / alignProjectiveColored evaluated: E_k, the sums and count at E_k, the status
   std::vector<icpk_projective_iter> projectiveTrace() {
     std::vector<icpk_projective_iter> t(ICPK_PROJECTIVE_MAX_ITERATIONS);
     const int n = icpk_get_projective_trace(eng_.ctx(), t.data(), (int32_t)t.size());

@@ -252,3 +252,30 @@ def textured_wall_pair(rows=60, cols=80, relief=0.0, seed=1, jitter=0.002, step=
     src = R.T @ (ws - T[:3, 3:4])
     return dict(source=src.astype(np.float32), target=tgt.astype(np.float32), source_intensity=is_.astype(np.float32),
                 target_intensity=it.astype(np.float32), T_true=T)
+
+
+def textured_wall_frames(poses, rows=60, cols=80, fx=60.0, cx=None, z=1.0, relief=0.0):
+    """Depth and intensity frames of textured_wall_pair's wall seen through a pinhole (fx, cx for both axes, as
+    everywhere here) from the given camera-to-world poses ((4, 4) each).  The wall is the surface
+    z_w = z + relief * (sin(2 pi x / 0.4) + cos(2 pi y / 0.3)) / 2 of the world frame -- relief 0 is the exact plane
+    z_w = z -- without a border: it covers the whole image at every pose that looks at it.  The intensity of a wall
+    point is 0.5 + 0.25 sin(2 pi x / 0.2) + 0.2 cos(2 pi y / 0.15).  cx None: (cols - 1) / 2.
+    Returns a list of (depth (rows, cols) uint16 at 5000 per metre, intensity (rows, cols) float32)."""
+    cx = 0.5 * (cols - 1) if cx is None else cx
+    v, u = np.mgrid[0:rows, 0:cols].astype(np.float64)
+    ray = np.stack([(u - cx) / fx, (v - cx) / fx, np.ones_like(u)])  # camera frame, z component 1: s is the depth
+    out = []
+    for P in poses:
+        P = np.asarray(P, np.float64).reshape(4, 4)
+        d = np.einsum("ab,brc->arc", P[:3, :3], ray)
+        o = P[:3, 3]
+        s = (z - o[2]) / d[2]
+        for _ in range(20 if relief else 0):  # fixed point on the height field: it moves the hit by relief per step at most
+            x, y = o[0] + s * d[0], o[1] + s * d[1]
+            s = (z + relief * 0.5 * (np.sin(2 * np.pi * x / 0.4) + np.cos(2 * np.pi * y / 0.3)) - o[2]) / d[2]
+        x, y = o[0] + s * d[0], o[1] + s * d[1]
+        inten = 0.5 + 0.25 * np.sin(2 * np.pi * x / 0.2) + 0.2 * np.cos(2 * np.pi * y / 0.15)
+        if not ((s > 0).all() and (s * 5000.0 < 65535).all()):
+            raise ValueError("a pose that does not look at the wall")
+        out.append((np.rint(s * 5000.0).astype(np.uint16), inten.astype(np.float32)))
+    return out

@@ -210,10 +210,15 @@ class ModelTracker:
     gate max_dist is the SAME at every level and defaults to 0.5 m: a projective pair is as far apart as the frame has
     slid along a surface, so the gate must be wider than the frame's displacement (a tight one makes the first step
     nearly degenerate).  levels_skipped, level_hits and the level-0 RuntimeError are as above; level_stats holds
-    ProjectiveResult objects.  None: the paths above, untouched."""
+    ProjectiveResult objects.  None: the paths above, untouched.
+    projective_color: True, or dict(lambda_geometric=, gradient_radius=, min_neighbors=) -- the photometric term beside
+    the projective pairs (K26); it needs `projective` and a colour volume (ValueError otherwise), and track needs the
+    frame's intensity.  Per frame the intensity goes beside the pyramid (never smoothed); per level, after the ray cast,
+    binding.raycast_color_gradients (radius gradient_radius * 2^l, default 2 voxels at level 0; min_neighbors 4) and
+    binding.align_projective_colored.  None: the projective path above, untouched."""
 
     def __init__(self, vol, pose=None, z_near=0.25, z_far=6.0, step=None, min_weight=1, bilateral=None, follow=None,
-                 on_leave=None, pyramid=None, pyramid_cutoff=None, projective=None, **align_kw):
+                 on_leave=None, pyramid=None, pyramid_cutoff=None, projective=None, projective_color=None, **align_kw):
         self.vol = vol
         self.pose = np.eye(4) if pose is None else np.array(pose, np.float64).reshape(4, 4)
         self.ray = dict(z_near=z_near, z_far=z_far, step=step, min_weight=min_weight)
@@ -244,12 +249,29 @@ class ModelTracker:
             if self.pyramid_params is None:
                 kw = {} if pyramid_cutoff is None else dict(range_cutoff=int(pyramid_cutoff))
                 self.pyramid_params = depth_front.pyramid_params(levels=1, **kw)
+        # K26: the photometric term beside the projective pairs -- None, True or dict(lambda_geometric=, gradient_radius=
+        # (at level 0; level l takes 2^l times it; default 2 voxels), min_neighbors= (4))
+        self.projective_color = None if projective_color is None else ({} if projective_color is True else dict(projective_color))
+        if self.projective_color is not None:
+            if self.projective is None:
+                raise ValueError("projective_color needs projective")
+            if not vol.params.flags & binding.TSDF_COLOR:
+                raise ValueError("projective_color needs a colour volume")
+            unknown = set(self.projective_color) - {"lambda_geometric", "gradient_radius", "min_neighbors"}
+            if unknown:
+                raise ValueError(f"projective_color has no setting {sorted(unknown)}")
 
-    def _track_projective(self, depth):
+    def _track_projective(self, depth, intensity=None):
         """The pose of one frame by projective association, coarse to fine: one build, then per level a ray cast of the
         model at the last pose and the device loop over the level and the maps, both where they lie."""
         vol, ctx = self.vol, self.vol.ctx
-        shapes = depth_front.build_pyramid(ctx, depth, self.pyramid_params, smooth=self.bilateral)
+        color = self.projective_color
+        # (with `bilateral` the depth is smoothed and the intensity is not)
+        shapes = depth_front.build_pyramid(ctx, depth, self.pyramid_params, smooth=self.bilateral,
+                                           intensity=None if color is None else intensity)
+        if color is not None:
+            cparams = binding.default_projective_color_params(**{k: color[k] for k in ("lambda_geometric",) if k in color})
+            radius0 = float(color.get("gradient_radius", 2.0 * vol.params.voxel))
         estimate = self.pose
         self.level_hits, self.level_stats = [None] * len(shapes), [None] * len(shapes)
         for l in range(len(shapes) - 1, -1, -1):
@@ -266,7 +288,11 @@ class ModelTracker:
                     raise RuntimeError(f"the ray cast hit the model in {n_hits} pixels, fewer than min_pairs = {params.min_pairs}")
                 self.levels_skipped += 1
                 continue
-            estimate, self.level_stats[l] = binding.align_projective(ctx, estimate, params)
+            if color is None:
+                estimate, self.level_stats[l] = binding.align_projective(ctx, estimate, params)
+            else:
+                binding.raycast_color_gradients(ctx, radius0 * scale, int(color.get("min_neighbors", 4)))
+                estimate, self.level_stats[l] = binding.align_projective_colored(ctx, estimate, params, cparams)
         self.n_hits, self.stats = self.level_hits[0], self.level_stats[0]
         return estimate
 
@@ -305,8 +331,10 @@ class ModelTracker:
         """One (rows, cols) uint16 frame (with its (rows, cols) intensities on a colour volume).  Returns the frame's
         camera-to-world pose (4, 4) float64; the first frame takes the initial pose."""
         vol, ctx = self.vol, self.vol.ctx
+        if self.projective_color is not None and intensity is None:
+            raise ValueError("projective_color needs the frame's intensity")
         if self.frames > 0 and self.projective is not None:
-            self.pose = self._track_projective(depth)
+            self.pose = self._track_projective(depth, intensity)
         elif self.frames > 0 and self.pyramid is not None:
             self.pose = self._track_pyramid(depth)
         elif self.frames > 0:

@@ -1762,6 +1762,121 @@ int icpk_projective_pixels(const icpk_projective_params *params, const double po
                            float fx_v, float cx_v, const double view_pose[16], int64_t first, int32_t count,
                            int32_t *pixel, float *dist, double *terms);
 
+/* ---- K26: the photometric term in projective frame-to-model alignment ------------------------------------------------
+ * K25 is purely geometric: a wall, a floor or a table top leaves the in-plane motion free, and on an exact plane its
+ * 6x6 is singular.  K26 adds K17's photometric term to it.  It needs three things beside K25's inputs: an intensity
+ * per pixel of the pyramid level, the intensity of the ray-cast view (plane 8 of K20's maps, from a volume with
+ * ICPK_TSDF_COLOR), and the gradient of that intensity over the view's surface.
+ *
+ * THE INTENSITY PYRAMID RULE (icpk_depth_pyramid_set_intensity; integers up to one final division, so the result is a
+ * function of the two images and K alone).  K is the range_cutoff the resident depth pyramid was built with.
+ *   Level 0 is the input image: one float in [0, 1] per pixel of depth level 0.
+ *   Pixel (r, c) of level l + 1 is 0.0 where pixel (r, c) of depth level l + 1 is 0, i.e. where d_c, the depth of pixel
+ *   (2 r, 2 c) of level l, is 0.
+ *   Otherwise the taps that count are exactly those that count in THE PYRAMID RULE at that pixel: (2 r + dy, 2 c + dx)
+ *   inside the image, d_q != 0 and |d_q - d_c| < K, d the DEPTH level l; the weights are the same,
+ *   w = (2 - |dy|)(2 - |dx|).
+ *     c_q = (int32)rint((double)I_q * 32768.0), I_q the intensity of level l at the tap (rint: to nearest, ties to even);
+ *     N = sum w c_q (int32: at most 16 * 32768), S = sum w (4 .. 16);
+ *     out = (float)((double)N / ((double)S * 32768.0)).
+ *   Consequences: a depth step of K or more is never averaged across in intensity either; the validity mask is the
+ *   depth level's mask; K == 1 is plain subsampling up to the quantisation (out = (float)(c_q / 32768.0) of the centre)
+ *   wherever no other tap has the centre's very depth -- with K == 1 a tap counts iff its depth equals the centre's,
+ *   which averages the depth to itself but not the intensity; the result lies in [0, 1].
+ * icpk_depth_pyramid_set_intensity  after icpk_depth_pyramid_build: a host image of level 0's shape (else ICPK_E_ARG;
+ *     ICPK_E_NOT_SET without a pyramid), every value finite and in [0, 1] (a host scan before the upload, else ICPK_E_ARG
+ *     and nothing changes).  It builds every level the depth pyramid has, one launch per level (the launch runs once per
+ *     frame; see csrc/kernels_pyramid_color.hip), from the depth levels as they lie on the device -- after a build with
+ *     `smooth` those are the smoothed depths; the intensity is never smoothed.  The next icpk_depth_pyramid_build drops
+ *     the intensity levels.
+ * icpk_depth_pyramid_get_intensity  out: a host array of the level's rows x cols floats; ICPK_E_NOT_SET without
+ *     intensity levels, ICPK_E_ARG for a level the pyramid lacks.
+ * icpk_intensity_pyramid_host       host only: level `level` of the intensity pyramid of (depth_in, intensity_in), the
+ *     depth pyramid taken without smoothing, through the header the kernel includes (csrc/pyramid_rule.h), into out, a
+ *     host array of exactly that level's size.  Refusals as icpk_depth_pyramid_host's, and an intensity outside [0, 1].
+ *
+ * THE VIEW GRADIENT RULE (icpk_tsdf_raycast_color_gradients) is K17's gradient rule with the neighbourhood replaced.
+ *   Pixel j = (r, c) of the last ray cast has a gradient only where depth[j] > 0.  Its point is (x, y, z)[j], its normal
+ *   n = (nx, ny, nz)[j], its intensity I_j = intensity[j].
+ *   neighbourhood  the view pixels q = (r + dy, c + dx), dy, dx in {-1, 0, 1}, that lie inside the view, have
+ *                  depth[q] > 0, and whose distance to pixel j's point in the form of projective rule 7 -- float32:
+ *                  f_a = fl(p_q,a - p_j,a), d = sqrt(fl(fl(fl(f_x f_x) + fl(f_y f_y)) + fl(f_z f_z))) -- is <= radius
+ *                  (a float compare; NaN fails).  Pixel j itself counts.  m = the neighbourhood's size (1 .. 9).
+ *   From there on the rule is K17's, word for word (colored ICP above), F = 2^15, r = radius:
+ *   usable normal  nn = (n_0 n_0 + n_1 n_1) + n_2 n_2 in float64 lies in [1 - 2^-10, 1 + 2^-10] (false for NaN).
+ *   per neighbour  (only with a usable normal) float64, one rounded operation per symbol, none fused:
+ *                    e_a = (double)p_q,a - (double)p_j,a;   h = (e_0 n_0 + e_1 n_1) + e_2 n_2;   u_a = e_a - h n_a
+ *                    q_a = (int64)rint((u_a / r) F);        c = (int64)rint(((double)I_q - (double)I_j) F)
+ *   sums           int64: S_ab = sum q_a q_b (a <= b), T_a = sum q_a c; ten words per pixel: m, S_00 S_01 S_02 S_11 S_12
+ *                  S_22, T_0 T_1 T_2; all nine sums zero without a usable normal, m kept; all ten zero for a non-hit
+ *                  pixel.  The distance test bounds |e| by the radius, so K17's overflow argument carries over (|q| <=
+ *                  2^15 + 2^7, and m <= 9).  The ray cast's intensity is a lerp of values in [0, 1], so |c| <= 2^15.
+ *   solve          float64: w = (double)m F, w2 = w w, H_ab = (double)S_ab + (w2 n_a) n_b; the adjugate K of H and det as
+ *                  K14 writes them (K_00 = H_11 H_22 - H_12 H_12, K_01 = H_02 H_12 - H_01 H_22, K_02 = H_01 H_12 -
+ *                  H_02 H_11, K_11 = H_00 H_22 - H_02 H_02, K_12 = H_01 H_02 - H_00 H_12, K_22 = H_00 H_11 - H_01 H_01,
+ *                  det = (H_00 K_00 + H_01 K_01) + H_02 K_02), inv = 1.0 / det,
+ *                  g'_a = ((K_a0 T_0 + K_a1 T_1) + K_a2 T_2) inv, gradient_a = (float)(g'_a / r): intensity per metre.
+ *   no gradient    (0, 0, 0) when m < min_neighbors, without a usable normal, when det is not finite or <= 0, or when
+ *                  a component of the result is not finite.  Every non-hit pixel gets (0, 0, 0).
+ * icpk_tsdf_raycast_color_gradients  stream-ordered, no host wait: three float planes gx, gy, gz of the last ray cast's
+ *     shape, kept by the context behind the maps.  flags: ICPK_COLOR_KEEP_SUMS keeps the ten int64 per pixel.
+ *     ICPK_E_NOT_SET without a volume or a ray cast; ICPK_E_ARG on a volume without ICPK_TSDF_COLOR, for a radius that is
+ *     not finite and > 0, min_neighbors < 1 or an unknown flag (nothing changes).  The next icpk_tsdf_raycast drops the
+ *     gradients and the kept sums, and so does everything that drops the maps.
+ * icpk_tsdf_get_raycast_color_gradients      three host planes of rows x cols floats (any may be NULL); ICPK_E_NOT_SET
+ *     without gradients of the current ray cast.
+ * icpk_tsdf_get_raycast_color_gradient_sums  10 int64 per pixel, pixel-major; ICPK_E_NOT_SET without the flag.
+ * icpk_raycast_color_gradients_host  host only, no context: the rule for `count` pixels from row-major pixel `first`
+ *     over eight host planes view[0..7] = x, y, z, nx, ny, nz, depth, intensity of rows x cols.  sums (or NULL): count x
+ *     10 int64; g (or NULL): count x 3 floats, (gx, gy, gz) per pixel.  Returns the number of pixels with a non-zero
+ *     gradient.  Compiled from the header the kernel includes (csrc/raycast_color_rule.h).
+ *
+ * THE COLOURED PROJECTIVE RULE.  Rules 1 - 8 of THE PROJECTIVE RULE decide the pair, unchanged: the coloured path accepts
+ * exactly the pixels K25 accepts, so counts, codes and [27] are K25's.  Rule 9 becomes K17's joint terms, float64,
+ * unfused, lg = (double)lambda_geometric, lc = 1.0 - lg.  With p the world point of rule 3, q = m = (x, y, z)[j],
+ * n = (nx, ny, nz)[j], g the view gradient at j, I_t = intensity_v[j] and I_s the intensity level's pixel i, all widened:
+ *   geometric   e_a = p_a - q_a;  h = (e_0 n_0 + e_1 n_1) + e_2 n_2;  G = [p x n | n]
+ *   photometric u_a = e_a - h n_a;  rc = (I_t + ((g_0 u_0 + g_1 u_1) + g_2 u_2)) - I_s;
+ *               gn = (g_0 n_0 + g_1 n_1) + g_2 n_2;  M_a = g_a - gn n_a;  C = [p x M | M]
+ *   sums        [0..20] += lg (G_a G_b) + lc (C_a C_b) (a <= b, row-major), [21..26] += lg (G_a h) + lc (C_a rc),
+ *               [27] += (double)dist, through the canonical tree over the pixel index.
+ * lambda_geometric = 1 gives icpk_projective_reduce's sums bit for bit.  A zero gradient removes a pair's photometric
+ * term, not the pair.  The loop is THE PROJECTIVE RULE's loop exactly: the same state, the same step launch,
+ * 2 max_iterations launches enqueued up front, one copy and one wait, the same stop rules and the same
+ * icpk_get_projective_trace; only the reduce launch differs.
+ * icpk_projective_reduce_colored / icpk_align_projective_colored  as their K25 namesakes; color NULL: the defaults.
+ *     ICPK_E_ARG for a lambda_geometric that is not finite and in [0, 1] and on a volume without ICPK_TSDF_COLOR;
+ *     ICPK_E_NOT_SET without an intensity pyramid or without view gradients for the current ray cast; everything K25
+ *     refuses is refused the same way, first.  None of these calls touches source, target, associations, records,
+ *     seeds, surface list, maps, pyramid or volume.
+ * icpk_projective_pixels_colored  host only: icpk_projective_pixels with the coloured rule 9; level_intensity: rows_s x
+ *     cols_s floats, view_intensity and gradient[0..2] = gx, gy, gz: rows_v x cols_v floats each. */
+typedef struct icpk_projective_color_params {
+  float lambda_geometric; /* [0, 1] (0.968) */
+} icpk_projective_color_params;
+void icpk_default_projective_color_params(icpk_projective_color_params *c);
+int icpk_depth_pyramid_set_intensity(icpk_ctx *ctx, const float *intensity, int32_t rows, int32_t cols);
+int icpk_depth_pyramid_get_intensity(icpk_ctx *ctx, int32_t level, float *out);
+int icpk_intensity_pyramid_host(const icpk_pyramid_params *params, const uint16_t *depth_in, const float *intensity_in,
+                                int32_t rows, int32_t cols, int32_t level, float *out);
+int icpk_tsdf_raycast_color_gradients(icpk_ctx *ctx, float radius, int32_t min_neighbors, int32_t flags);
+int icpk_tsdf_get_raycast_color_gradients(icpk_ctx *ctx, float *gx, float *gy, float *gz);
+int icpk_tsdf_get_raycast_color_gradient_sums(icpk_ctx *ctx, int64_t *sums);
+int icpk_raycast_color_gradients_host(const float *const view[8], int32_t rows, int32_t cols, float radius,
+                                      int32_t min_neighbors, int64_t first, int32_t count, int64_t *sums, float *g);
+int icpk_projective_reduce_colored(icpk_ctx *ctx, const icpk_projective_params *params,
+                                   const icpk_projective_color_params *color, const double pose[16],
+                                   double sums[ICPK_NP2L], int64_t *count);
+int icpk_align_projective_colored(icpk_ctx *ctx, const icpk_projective_params *params,
+                                  const icpk_projective_color_params *color, const double pose_in[16],
+                                  double pose_out[16], icpk_projective_result *result);
+int icpk_projective_pixels_colored(const icpk_projective_params *params, const double pose[16], const uint16_t *level,
+                                   int32_t rows_s, int32_t cols_s, const float *const view[7], int32_t rows_v,
+                                   int32_t cols_v, float fx_v, float cx_v, const double view_pose[16], int64_t first,
+                                   int32_t count, int32_t *pixel, float *dist, double *terms,
+                                   const float *level_intensity, const float *view_intensity,
+                                   const float *const gradient[3], const icpk_projective_color_params *color);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity

@@ -1,0 +1,55 @@
+"""icp::Engine::setPyramidIntensity and icp::TsdfVolume::raycastColorGradients / alignProjectiveColored
+(tests/cpp/test_projective_color.cpp) against the same calls made through the Python binding, byte for byte: the pose,
+the result, every trace entry, the view's gradients and the level's intensities of the colour room at level 1."""
+import os
+import struct
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import projective_color_cases as kc
+from icp_slam_prototype_amd import binding, build, depth
+
+pytestmark = pytest.mark.gpu
+
+
+def test_cpp_projective_color_equals_binding():
+    exe = build.build_projective_color_test()
+    name, iters, lam = "room_l1", 6, 0.9
+    c = kc.case(name)
+    t = kc.volume_case(c["volume"])
+    v, view = t["volume"], c["view"]
+    rows, cols = t["frames"][0][0].shape
+    blob = struct.pack("<8i", *v["dims"], 255, binding.TSDF_COLOR, rows, cols, len(t["frames"]))
+    blob += struct.pack("<8f", v["voxel"], *v["origin"], v["trunc"], t["fx"], t["cx"], 0.0)
+    for d, P, inten in t["frames"]:
+        blob += np.ascontiguousarray(P, np.float64).tobytes() + np.ascontiguousarray(d, np.uint16).tobytes() + \
+            np.ascontiguousarray(inten, np.float32).tobytes()
+    blob += struct.pack("<4i", *view["shape"], view["min_weight"], c["min_neighbors"])
+    blob += struct.pack("<4f", view["z_near"], view["z_far"], view["step"], c["radius"]) + c["view_pose"].tobytes()
+    blob += struct.pack("<8i", *c["depth"].shape, c["level"] + 1, c["level"], iters, 6, 0, 0)
+    blob += struct.pack("<4f", c["fx"], c["cx"], c["max_dist"], lam) + c["estimate"].tobytes() + c["depth"].tobytes() + c["intensity"].tobytes()
+    with tempfile.TemporaryDirectory() as td:
+        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
+        with open(fin, "wb") as f:
+            f.write(blob)
+        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stderr
+        raw = open(fout, "rb").read()
+    with binding.Context(0) as ctx:
+        p = kc.device_setup(ctx, name, depth, binding)
+        p.max_iterations = iters
+        pose, res = binding.align_projective_colored(ctx, c["estimate"], p, dict(lambda_geometric=lam))
+        trace = binding.projective_trace(ctx)
+        grad = binding.get_raycast_color_gradients(ctx)
+        level = binding.pyramid_intensity(ctx, c["level"])
+    assert struct.unpack_from("<4i", raw, 0) == (binding.OK, iters, iters, 0)
+    want = struct.pack("<qd", res.count, res.mean_dist) + pose.tobytes()
+    for e in trace:
+        want += e["pose"].tobytes() + e["sums"].tobytes() + struct.pack("<q2i", e["count"], e["status"], 0)
+    want += grad.tobytes() + level.tobytes()
+    assert raw[16:] == want
+    assert grad.tobytes() == kc.gradients_of(name).tobytes() and level.tobytes() == kc.case(name)["level_intensity"].tobytes()
+    assert f"coloured projective level 1: status 0 after {iters} updates, {res.count} pairs at the last evaluation" in out.stdout
