@@ -99,6 +99,9 @@ SYMBOLS = [
     "icpk_intensity_pyramid_host", "icpk_tsdf_raycast_color_gradients", "icpk_tsdf_get_raycast_color_gradients",
     "icpk_tsdf_get_raycast_color_gradient_sums", "icpk_raycast_color_gradients_host", "icpk_projective_reduce_colored",
     "icpk_align_projective_colored", "icpk_projective_pixels_colored",
+    "icpk_default_fern_params", "icpk_fern_create", "icpk_fern_reset", "icpk_fern_destroy", "icpk_fern_count",
+    "icpk_fern_encode", "icpk_fern_query", "icpk_fern_add", "icpk_fern_process", "icpk_fern_add_code",
+    "icpk_fern_get_keyframe", "icpk_fern_table", "icpk_fern_encode_host", "icpk_fern_dissimilarity_host",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -245,6 +248,16 @@ class ProjectiveIter(C.Structure):
 class ProjectiveColorParams(C.Structure):
     """icpk_projective_color_params"""
     _fields_ = [("lambda_geometric", C.c_float)]
+
+
+FERN_MAX_K = 8  # icpk_fern_query / icpk_fern_process: the most keyframes a search returns
+FERN_MAX_FERNS, FERN_MAX_KEYFRAMES = 1024, 65536
+
+
+class FernParams(C.Structure):
+    """icpk_fern_params"""
+    _fields_ = [("level", C.c_int32), ("n_ferns", C.c_int32), ("seed", C.c_uint64), ("d_min", C.c_int32), ("d_max", C.c_int32),
+                ("capacity", C.c_int32), ("harvest_above", C.c_int32), ("min_valid", C.c_int32), ("reserved", C.c_int32)]
 
 
 class FrameJob(C.Structure):
@@ -524,6 +537,22 @@ def load():
     lib.icpk_projective_pixels_colored.argtypes = [jp, dp, u16, C.c_int32, C.c_int32, C.POINTER(fp), C.c_int32, C.c_int32,
                                                    C.c_float, C.c_float, dp, C.c_int64, C.c_int32, ip, fp, dp, fp, fp,
                                                    C.POINTER(fp), kp]
+    ep = C.POINTER(FernParams)
+    u32 = C.POINTER(C.c_uint32)
+    lib.icpk_default_fern_params.argtypes = [ep]
+    lib.icpk_default_fern_params.restype = None
+    lib.icpk_fern_create.argtypes = [C.c_void_p, ep, C.c_int32, C.c_int32]
+    for name in ("icpk_fern_reset", "icpk_fern_destroy", "icpk_fern_count"):
+        getattr(lib, name).argtypes = [C.c_void_p]
+    lib.icpk_fern_encode.argtypes = [C.c_void_p, u32, ip]
+    lib.icpk_fern_query.argtypes = [C.c_void_p, C.c_int32, ip, ip, ip]
+    lib.icpk_fern_add.argtypes = [C.c_void_p, dp, ip]
+    lib.icpk_fern_process.argtypes = [C.c_void_p, dp, C.c_int32, ip, ip, ip, ip, ip]
+    lib.icpk_fern_add_code.argtypes = [C.c_void_p, u32, dp, ip]
+    lib.icpk_fern_get_keyframe.argtypes = [C.c_void_p, C.c_int32, u32, dp]
+    lib.icpk_fern_table.argtypes = [ep, C.c_int32, C.c_int32, ip]
+    lib.icpk_fern_encode_host.argtypes = [ep, u16, C.c_int32, C.c_int32, u32, ip]
+    lib.icpk_fern_dissimilarity_host.argtypes = [u32, u32, C.c_int32]
     _lib = lib
     return lib
 
@@ -794,6 +823,75 @@ def default_projective_params(**kw):
 
 def _pose16(pose):
     return np.ascontiguousarray(pose, np.float64).reshape(16)
+
+
+_FERN_FIELDS = ("level", "n_ferns", "seed", "d_min", "d_max", "capacity", "harvest_above", "min_valid")
+
+
+def default_fern_params(**kw):
+    """icpk_default_fern_params with the given fields replaced (level, n_ferns, seed, d_min, d_max, capacity,
+    harvest_above, min_valid).  harvest_above and min_valid follow n_ferns (F / 5, F / 2) unless given."""
+    p = FernParams()
+    load().icpk_default_fern_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in _FERN_FIELDS:
+            raise TypeError(f"icpk_fern_params has no field {k!r}")
+        setattr(p, k, int(v))
+    if "n_ferns" in kw:
+        if "harvest_above" not in kw:
+            p.harvest_above = p.n_ferns // 5
+        if "min_valid" not in kw:
+            p.min_valid = p.n_ferns // 2
+    return p
+
+
+def _fern_words(params):
+    """the uint32 words of a code; 1 for an n_ferns the call will refuse before it writes"""
+    F = 256 if params is None else params.n_ferns
+    return F // 8 if 8 <= F <= FERN_MAX_FERNS and F % 8 == 0 else 1
+
+
+def _u32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def _fern_ref(params):
+    return None if params is None else C.byref(params)
+
+
+def fern_table(params, rows, cols):
+    """icpk_fern_table (host only): (F, 6) int32 -- each fern's row, col and four thresholds on a level of rows x cols."""
+    out = np.zeros((_fern_words(params) * 8, 6), np.int32)
+    rc = load().icpk_fern_table(_fern_ref(params), int(rows), int(cols), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_fern_table: parameters outside their ranges or an empty level")
+    return out
+
+
+def fern_encode_host(params, level):
+    """icpk_fern_encode_host (host only): (code (F / 8,) uint32, V) of a (rows, cols) uint16 level."""
+    level = np.ascontiguousarray(level, np.uint16)
+    if level.ndim != 2:
+        raise ValueError("a (rows, cols) level expected")
+    code = np.zeros(_fern_words(params), np.uint32)
+    V = C.c_int32(0)
+    rc = load().icpk_fern_encode_host(_fern_ref(params), level.ctypes.data_as(C.POINTER(C.c_uint16)), level.shape[0],
+                                      level.shape[1], _u32p(code), C.byref(V))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_fern_encode_host: parameters outside their ranges or an empty level")
+    return code, V.value
+
+
+def fern_dissimilarity_host(a, b, n_ferns=None):
+    """icpk_fern_dissimilarity_host (host only): the ferns whose nibbles differ between two packed codes."""
+    a, b = np.ascontiguousarray(a, np.uint32).reshape(-1), np.ascontiguousarray(b, np.uint32).reshape(-1)
+    n_ferns = 8 * a.size if n_ferns is None else int(n_ferns)
+    if a.size != b.size or (8 <= n_ferns <= FERN_MAX_FERNS and n_ferns != 8 * a.size):
+        raise ValueError("two codes of n_ferns / 8 words expected")
+    rc = load().icpk_fern_dissimilarity_host(_u32p(a), _u32p(b), n_ferns)
+    if rc < 0:
+        raise IcpkError(rc, "icpk_fern_dissimilarity_host: n_ferns is not a multiple of 8 in 8 .. 1024")
+    return rc
 
 
 def projective_pixels(params, pose, level, view, view_shape, view_fx, view_cx, view_pose, first=0, count=None,
@@ -1137,6 +1235,94 @@ def projective_pixels_colored(params, pose, level, view, view_shape, view_fx, vi
     if rc < 0:
         raise IcpkError(rc, "icpk_projective_pixels_colored")
     return pixel, dist, tm, rc
+
+
+# ---- K27: fern keyframe relocalisation.  Functions over a context: the class itself gains no method ----
+def fern_create(ctx, rows, cols, params=None, **kw):
+    """icpk_fern_create: a keyframe database for levels of rows x cols (it replaces the context's previous one).
+    params: a FernParams, or fields of default_fern_params as keywords.  Returns the FernParams in force."""
+    p = default_fern_params(**kw) if params is None else params
+    ctx._chk(ctx._lib.icpk_fern_create(ctx._h, C.byref(p), int(rows), int(cols)))
+    ctx._fern = FernParams.from_buffer_copy(p)
+    return ctx._fern
+
+
+def _fern_w(ctx):
+    p = getattr(ctx, "_fern", None)
+    return 1 if p is None else p.n_ferns // 8
+
+
+def fern_reset(ctx):
+    ctx._chk(ctx._lib.icpk_fern_reset(ctx._h))
+
+
+def fern_destroy(ctx):
+    ctx._chk(ctx._lib.icpk_fern_destroy(ctx._h))
+    ctx._fern = None
+
+
+def fern_count(ctx):
+    return ctx._chk(ctx._lib.icpk_fern_count(ctx._h))
+
+
+def fern_encode(ctx):
+    """icpk_fern_encode: the database's level of the resident pyramid into the current code.  Returns (code
+    (F / 8,) uint32, V)."""
+    code, V = np.zeros(_fern_w(ctx), np.uint32), C.c_int32(0)
+    ctx._chk(ctx._lib.icpk_fern_encode(ctx._h, _u32p(code), C.byref(V)))
+    return code, V.value
+
+
+def _fern_lists(n, idx, diss):
+    return idx[:n.value].copy(), diss[:n.value].copy()
+
+
+def fern_query(ctx, k=3):
+    """icpk_fern_query: the min(k, n) nearest keyframes of the current code, (index, diss) int32 arrays in ascending
+    (diss, index) order."""
+    idx, diss, n = np.zeros(FERN_MAX_K, np.int32), np.zeros(FERN_MAX_K, np.int32), C.c_int32(0)
+    ip = C.POINTER(C.c_int32)
+    ctx._chk(ctx._lib.icpk_fern_query(ctx._h, int(k), idx.ctypes.data_as(ip), diss.ctypes.data_as(ip), C.byref(n)))
+    return _fern_lists(n, idx, diss)
+
+
+def fern_add(ctx, pose):
+    """icpk_fern_add: the current code becomes a keyframe with this (4, 4) pose.  Returns its index."""
+    i = C.c_int32(-1)
+    ctx._chk(ctx._lib.icpk_fern_add(ctx._h, _pose16(pose).ctypes.data_as(C.POINTER(C.c_double)), C.byref(i)))
+    return i.value
+
+
+def fern_process(ctx, pose=None, k=3):
+    """icpk_fern_process: encode, search and -- with a pose, when the harvest rule says so -- append.  Returns
+    dict(index, diss (the search BEFORE the append), valid, added (the new keyframe's index or -1))."""
+    idx, diss, n = np.zeros(FERN_MAX_K, np.int32), np.zeros(FERN_MAX_K, np.int32), C.c_int32(0)
+    V, added = C.c_int32(0), C.c_int32(-1)
+    ip = C.POINTER(C.c_int32)
+    pp = None if pose is None else _pose16(pose)
+    ctx._chk(ctx._lib.icpk_fern_process(ctx._h, None if pp is None else pp.ctypes.data_as(C.POINTER(C.c_double)), int(k),
+                                          idx.ctypes.data_as(ip), diss.ctypes.data_as(ip), C.byref(n), C.byref(V),
+                                          C.byref(added)))
+    index, diss = _fern_lists(n, idx, diss)
+    return dict(index=index, diss=diss, valid=V.value, added=added.value)
+
+
+def fern_add_code(ctx, code, pose):
+    """icpk_fern_add_code: a host code (F / 8,) uint32 becomes a keyframe.  Returns its index."""
+    code = np.ascontiguousarray(code, np.uint32).reshape(-1)
+    if getattr(ctx, "_fern", None) is not None and code.size != _fern_w(ctx):
+        raise ValueError("a code of n_ferns / 8 words expected")
+    i = C.c_int32(-1)
+    ctx._chk(ctx._lib.icpk_fern_add_code(ctx._h, _u32p(code), _pose16(pose).ctypes.data_as(C.POINTER(C.c_double)),
+                                           C.byref(i)))
+    return i.value
+
+
+def fern_keyframe(ctx, index):
+    """icpk_fern_get_keyframe: (code (F / 8,) uint32, pose (4, 4) float64) of one keyframe."""
+    code, pose = np.zeros(_fern_w(ctx), np.uint32), np.zeros(16, np.float64)
+    ctx._chk(ctx._lib.icpk_fern_get_keyframe(ctx._h, int(index), _u32p(code), pose.ctypes.data_as(C.POINTER(C.c_double))))
+    return code, pose.reshape(4, 4)
 
 
 class Context:

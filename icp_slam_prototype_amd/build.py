@@ -20,7 +20,8 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_color.cpp", "kernels_color.hip", "icpk_posegraph.cpp", "kernels_posegraph.hip",
            "icpk_tsdf.cpp", "kernels_tsdf.hip", "icpk_bilateral.cpp", "kernels_bilateral.hip",
            "icpk_pyramid.cpp", "kernels_pyramid.hip", "icpk_projective.cpp", "kernels_projective.hip",
-           "kernels_pyramid_color.hip", "icpk_raycast_color.cpp", "kernels_raycast_color.hip"]
+           "kernels_pyramid_color.hip", "icpk_raycast_color.cpp", "kernels_raycast_color.hip",
+           "icpk_fern.cpp", "kernels_fern.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -569,6 +570,49 @@ def build_projective_color_host_sanitized(force=False):
     return PROJECTIVE_COLOR_HOST_SANITIZED
 
 
+FERN_TEST = os.path.join(LIBDIR, "test_fern")
+
+
+def build_fern_test(force=False):
+    """Host-only C++ program over icp::FernDatabase and icp::TsdfVolume::relocalise (icp_tsdf.hpp, K27) (g++, links
+    -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_fern.cpp")
+    hdrs = [os.path.join(HERE, "include", h) for h in ("icp_align.hpp", "icp_tsdf.hpp")]
+    build()
+    newest = max(os.path.getmtime(p) for p in [src, LIB] + hdrs)
+    if not force and os.path.exists(FERN_TEST) and os.path.getmtime(FERN_TEST) >= newest:
+        return FERN_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", FERN_TEST])
+    return FERN_TEST
+
+
+FERN_HOST_SANITIZED = os.path.join(LIBDIR, "fern_host_sanitized")
+
+
+def build_fern_host_sanitized(force=False):
+    """DIAGNOSTIC, not part of build(): tests/cpp/fern_host_main.cpp (its own main, no GPU) with icpk_fern.cpp -- and so
+    csrc/fern_rule.h -- compiled under -fsanitize=address,undefined on the host side; everything else icpk_fern.cpp
+    refers to (the launchers its device entry points call) comes from libicpk.so as it is.  The program calls the three
+    host-only entry points alone.  Run the program it returns directly."""
+    src = os.path.join(ROOT, "tests", "cpp", "fern_host_main.cpp")
+    build()
+    deps = [src, LIB, os.path.join(CSRC, "icpk_fern.cpp"), os.path.join(CSRC, "fern_rule.h")]
+    if not force and os.path.exists(FERN_HOST_SANITIZED) and \
+            os.path.getmtime(FERN_HOST_SANITIZED) >= max(os.path.getmtime(p) for p in deps):
+        return FERN_HOST_SANITIZED
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-omit-frame-pointer", "-g"]
+    objs = []
+    for path, name in ((os.path.join(CSRC, "icpk_fern.cpp"), "icpk_fern_sanitized.o"), (src, "fern_host_main.o")):
+        objs.append(os.path.join(LIBDIR, name))
+        subprocess.check_call([hipcc] + FLAGS + san + ["-x", "hip", "-c", path, "-o", objs[-1]])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-fsanitize=address,undefined"] + objs +
+                          ["-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN", "-o", FERN_HOST_SANITIZED])
+    return FERN_HOST_SANITIZED
+
+
 THREADS_TEST = os.path.join(LIBDIR, "test_threads")
 
 
@@ -660,4 +704,5 @@ if __name__ == "__main__":
     print(build_pyramid_test(force="--force" in sys.argv))
     print(build_projective_test(force="--force" in sys.argv))
     print(build_projective_color_test(force="--force" in sys.argv))
+    print(build_fern_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

@@ -3,7 +3,7 @@
 // icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
 // entry; icpk_frontend.cpp: depth images;
 // icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp, icpk_gicp.cpp,
-// icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp, icpk_posegraph.cpp, icpk_tsdf.cpp, icpk_projective.cpp).  Not
+// icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp, icpk_posegraph.cpp, icpk_tsdf.cpp, icpk_projective.cpp, icpk_fern.cpp).  Not
 // part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -477,6 +477,22 @@ struct icpk_ctx {
   icpk::DevBuf<float> pyr_int;
   bool pyr_have_int = false;
   int pyr_K = 0;
+  // K27 (icpk_fern.cpp), behind everything older for the same reason: the keyframe database of icpk_fern_create -- the
+  // table the codes are drawn with, the codes transposed (word w of keyframe k at w * capacity + k), the poses on the
+  // host beside them --, the current code (F / 8 words, then V), the search's lists and answer, and where the host
+  // reads code, V and answer.  A pyramid build clears fern_code_current and touches nothing else of these
+  bool have_fern = false;
+  icpk_fern_params fern_params{};
+  int fern_rows = 0, fern_cols = 0;
+  int fern_n = 0;
+  icpk::DevBuf<int32_t> fern_table;    // F x 6
+  icpk::DevBuf<uint32_t> fern_db;      // F / 8 x capacity
+  icpk::DevBuf<uint32_t> fern_code;    // F / 8 code words | V | the answer's 8 keys
+  icpk::DevBuf<uint32_t> fern_lists;   // ceil(capacity / 256) x 8
+  icpk::PinnedBuf<uint32_t> fern_host; // fern_code's mirror
+  std::vector<double> fern_poses;      // 16 per keyframe
+  bool fern_code_current = false;      // the current code is of the resident pyramid
+  int fern_code_valid = 0;             // ... and its V
 };
 
 #define ICPK_HIP(ctx, call)                                                                      \

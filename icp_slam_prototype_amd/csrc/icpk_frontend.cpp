@@ -403,6 +403,7 @@ int icpk_depth_pyramid_build(icpk_ctx* ctx, const uint16_t* depth, int32_t rows,
   if ((rc = ctx->pyr.reserve(ctx, total))) return rc;
   ctx->pyr_levels = 0;  // (nothing is resident until this call has enqueued everything)
   ctx->pyr_have_int = false;  // (K26: the intensity levels belong to the pyramid they were set beside)
+  ctx->fern_code_current = false;  // (K27: and so does the current fern code; the database stays)
   uint16_t* const base = ctx->pyr;
   if (smooth) {  // K22 writes level 0
     ctx->frame_slot = -1;  // (the image buffers are shared with icpk_backproject_pair's resident frame)

@@ -459,6 +459,18 @@ void launch_intensity_pyramid(const uint16_t* depth, const float* inten, int row
 // planes of grad, and the ten int64 per pixel into sums unless it is nullptr
 void launch_raycast_color_gradients(const float* maps, int rows, int cols, float radius, int min_neighbors, float* grad,
                                     long long* sums, hipStream_t s);
+// kernels_fern.hip -- K27, THE FERN RULE.  A code on the device is F / 8 words followed by one word that holds V.
+constexpr int FERN_MAX_F = 1024;           // ferns: the encode workgroup's size
+constexpr int FERN_TOPK = 8;               // ICPK_FERN_MAX_K: keys a workgroup of the search leaves
+constexpr int FERN_SEARCH_THREADS = 256;   // keyframes per workgroup of the search; 65536 / 256 lists fit the merge
+// level: the level the table (F x FERN_ENTRY int32, device) was drawn for; code: F / 8 + 1 words
+void launch_fern_encode(const uint16_t* level, int cols, const int32_t* table, int F, uint32_t* code, hipStream_t s);
+// the min(FERN_TOPK, n) smallest keys diss << 16 | index of the n keyframes against `code`, ascending, then FERN_NO_KEY,
+// into out[0 .. FERN_TOPK): two launches.  db: W x capacity words; lists: ceil(n / FERN_SEARCH_THREADS) x FERN_TOPK
+// words of scratch.  n <= 0: nothing is launched
+void launch_fern_search(const uint32_t* db, int capacity, int n, const uint32_t* code, int W, uint32_t* lists, uint32_t* out,
+                        hipStream_t s);
+void launch_fern_append(uint32_t* db, int capacity, int column, const uint32_t* code, int W, hipStream_t s);
 
 // ---- deferred set-up launches of the frame-batch mode ------------------------------------------------
 // A lock-step group's pairs go through the SAME sequence of small set-up kernels (ingest x 2, loop-state

@@ -158,6 +158,58 @@ def pyramid_level(ctx, level):
     return out
 
 
+class Relocaliser:
+    """Fern keyframe relocalisation (K27) over one Context: a keyframe database for levels of `shape` (rows, cols) --
+    the shape of level params.level of the pyramids the context will hold -- and its parameters (a binding.FernParams,
+    or fields of binding.default_fern_params as keywords).
+
+        reloc = Relocaliser(ctx, pyramid_shapes(frame.shape, 3)[2])
+        build_pyramid(ctx, frame, pyramid_params(levels=3))
+        reloc.process(pose)                 # a tracked frame: encoded, looked up, and harvested when it is new enough
+        r = reloc.process(None, k=3)        # a lost frame: r["poses"] are the restarts to try, nearest code first
+    """
+
+    def __init__(self, ctx, shape, params=None, **kw):
+        self.ctx, self.shape = ctx, (int(shape[0]), int(shape[1]))
+        self.params = binding.fern_create(ctx, self.shape[0], self.shape[1], params, **kw)
+
+    @property
+    def count(self):
+        return binding.fern_count(self.ctx)
+
+    def poses(self, index):
+        """the (4, 4) poses of the keyframes `index`"""
+        return [binding.fern_keyframe(self.ctx, int(i))[1] for i in index]
+
+    def process(self, pose=None, k=3):
+        """binding.fern_process on the resident pyramid, with the poses of the returned keyframes: dict(index, diss,
+        valid, added, poses)."""
+        r = binding.fern_process(self.ctx, pose, k)
+        r["poses"] = self.poses(r["index"])
+        return r
+
+    def reset(self):
+        binding.fern_reset(self.ctx)
+
+    def save(self, path):
+        """the parameters, the level's shape, the codes and the poses as one .npz"""
+        kf = [binding.fern_keyframe(self.ctx, i) for i in range(self.count)]
+        W = self.params.n_ferns // 8
+        np.savez(path, params=np.array([getattr(self.params, f) for f in binding._FERN_FIELDS], np.uint64),
+                 shape=np.array(self.shape, np.int64), codes=np.array([c for c, _ in kf], np.uint32).reshape(len(kf), W),
+                 poses=np.array([p for _, p in kf], np.float64).reshape(len(kf), 4, 4))
+
+    @classmethod
+    def load(cls, ctx, path):
+        """a saved database into `ctx` (through binding.fern_add_code, keyframe by keyframe, in order)"""
+        with np.load(path) as z:
+            fields = {f: int(v) for f, v in zip(binding._FERN_FIELDS, z["params"].astype(np.uint64))}
+            self = cls(ctx, tuple(int(v) for v in z["shape"]), **fields)
+            for code, pose in zip(z["codes"], z["poses"]):
+                binding.fern_add_code(ctx, code, pose)
+        return self
+
+
 def backproject_level(ctx, level, which=0, normals_mode=None, fx=468.60, cx=318.27, offset=None):
     """icpk_depth_pyramid_backproject: Context.backproject (normals_mode None) or Context.backproject_with_normals
     (normals_mode NORMALS_*, which must be 1) of the resident level, read where it lies.  fx, cx: the LEVEL-0 intrinsics;

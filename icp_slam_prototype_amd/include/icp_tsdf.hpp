@@ -11,6 +11,9 @@
 //                        extractMesh / getMesh give the surface as a triangle mesh (K21); setPlanes restores a saved
 //                        model.  shift / extractLeaving / getBox let the volume follow the camera (K23): the box
 //                        moves by whole voxels, what is about to leave it is listed first.
+//   * icp::FernDatabase -- the fern keyframe database of an Engine's context (icpk_fern_*, K27): every tracked frame's
+//                        coarse pyramid level is encoded, looked up and harvested on the GPU (process); a tracker
+//                        that has lost the camera restarts from the nearest keyframes' poses (TsdfVolume::relocalise).
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -48,6 +51,68 @@ struct TsdfMesh {
   int32_t noNormal = 0;            // vertices listed without a normal
   size_t vertices() const { return x.size(); }
   size_t size() const { return triangles.size() / 3; }
+};
+
+// K27: the fern keyframe database of an Engine's context (icpk_fern_* of include/icpk.h, THE FERN RULE): the codes on
+// the device, the poses on the host beside them.  An Engine holds one database: constructing another replaces it.
+struct FernMatches {
+  std::vector<int32_t> index, diss;  // the nearest keyframes in ascending (diss, index) order
+  int32_t valid = 0;                 // V of the frame
+  int32_t added = -1;                // the keyframe the frame became, or -1
+};
+
+class FernDatabase {
+ public:
+  static icpk_fern_params defaults() {
+    icpk_fern_params p;
+    icpk_default_fern_params(&p);
+    return p;
+  }
+  // rows, cols: the shape of level p.level of the pyramids the Engine will hold.  Throws std::runtime_error when the
+  // parameters are refused or the memory is not there
+  FernDatabase(Engine& eng, const icpk_fern_params& p, int rows, int cols) : eng_(eng), p_(p) {
+    const int rc = icpk_fern_create(eng_.ctx(), &p_, rows, cols);
+    if (rc != ICPK_OK) throw std::runtime_error("icpk_fern_create failed (status " + std::to_string(rc) + "): " + eng_.last_error());
+  }
+  FernDatabase(const FernDatabase&) = delete;
+  FernDatabase& operator=(const FernDatabase&) = delete;
+  ~FernDatabase() { icpk_fern_destroy(eng_.ctx()); }
+
+  const icpk_fern_params& params() const { return p_; }
+  size_t words() const { return (size_t)p_.n_ferns / 8; }
+  int size() { return icpk_fern_count(eng_.ctx()); }
+  int reset() { return icpk_fern_reset(eng_.ctx()); }
+  // the database's level of the Engine's resident pyramid into the current code; code: words() entries
+  int encode(std::vector<uint32_t>* code = nullptr, int32_t* valid = nullptr) {
+    if (code) code->assign(words(), 0u);
+    return icpk_fern_encode(eng_.ctx(), code ? code->data() : nullptr, valid);
+  }
+  int query(int k, FernMatches& m) {
+    int32_t n = 0;
+    m.index.assign(ICPK_FERN_MAX_K, 0), m.diss.assign(ICPK_FERN_MAX_K, 0);
+    const int rc = icpk_fern_query(eng_.ctx(), k, m.index.data(), m.diss.data(), &n);
+    m.index.resize(rc == ICPK_OK ? (size_t)n : 0), m.diss.resize(rc == ICPK_OK ? (size_t)n : 0);
+    return rc;
+  }
+  int add(const double* pose, int32_t* index = nullptr) { return icpk_fern_add(eng_.ctx(), pose, index); }
+  // the per-frame call: encode, search and -- with a pose (16 doubles, row-major), when the harvest rule says so -- append
+  int process(const double* pose, int k, FernMatches& m) {
+    int32_t n = 0;
+    m.index.assign(ICPK_FERN_MAX_K, 0), m.diss.assign(ICPK_FERN_MAX_K, 0);
+    m.valid = 0, m.added = -1;
+    const int rc = icpk_fern_process(eng_.ctx(), pose, k, m.index.data(), m.diss.data(), &n, &m.valid, &m.added);
+    m.index.resize(rc == ICPK_OK ? (size_t)n : 0), m.diss.resize(rc == ICPK_OK ? (size_t)n : 0);
+    return rc;
+  }
+  int addCode(const uint32_t* code, const double* pose, int32_t* index = nullptr) {
+    return icpk_fern_add_code(eng_.ctx(), code, pose, index);
+  }
+  // one keyframe back: code (words() entries) and pose (16 doubles), either may be null
+  int keyframe(int index, uint32_t* code, double* pose) { return icpk_fern_get_keyframe(eng_.ctx(), index, code, pose); }
+
+ private:
+  Engine& eng_;
+  icpk_fern_params p_;
 };
 
 class TsdfVolume {
@@ -145,6 +210,35 @@ class TsdfVolume {
   int alignProjective(const icpk_projective_params& p, const double* poseIn, double* poseOut,
                       icpk_projective_result* result = nullptr) {
     return icpk_align_projective(eng_.ctx(), &p, poseIn, poseOut, result);
+  }
+  // K27, for a tracker that has lost the camera: the frame of the Engine's resident pyramid is looked up in `db`
+  // (FernDatabase::process without a pose) and, for each of its k nearest keyframes in order, the volume is ray-cast at
+  // the keyframe's pose (r: the ray cast's parameters for level p.level) and alignProjective starts from it.  The first
+  // keyframe whose alignment ends with ICPK_OK, at least minPairs pairs and a mean distance of at most maxMeanDist
+  // wins: *keyframe is its index, poseOut its refined pose.  None (or a frame with fewer than min_valid valid ferns):
+  // *keyframe = -1 and poseOut is untouched.  Returns ICPK_OK or a negative status
+  int relocalise(FernDatabase& db, int k, const icpk_tsdf_raycast_params& r, const icpk_projective_params& p,
+                 double* poseOut, int32_t* keyframe, icpk_projective_result* result = nullptr, int64_t minPairs = 0,
+                 double maxMeanDist = 1e300) {
+    *keyframe = -1;
+    FernMatches m;
+    int rc = db.process(nullptr, k, m);
+    if (rc != ICPK_OK || m.valid < db.params().min_valid) return rc;
+    for (size_t c = 0; c < m.index.size(); ++c) {
+      double start[16], found[16];
+      icpk_projective_result res;
+      int32_t hits = 0;
+      if ((rc = db.keyframe(m.index[c], nullptr, start)) != ICPK_OK) return rc;
+      if ((rc = raycast(r, start, &hits)) != ICPK_OK) return rc;
+      if (hits < p.min_pairs) continue;
+      if ((rc = alignProjective(p, start, found, &res)) < 0) return rc;
+      if (rc != ICPK_OK || res.count < minPairs || !(res.mean_dist <= maxMeanDist)) continue;
+      for (int i = 0; i < 16; ++i) poseOut[i] = found[i];
+      if (result) *result = res;
+      *keyframe = m.index[c];
+      return ICPK_OK;
+    }
+    return ICPK_OK;
   }
   // per pixel of that level at `pose`: the view pixel it pairs with or its ICPK_PROJ_* code, and the distance (0
   // without a pair); both vectors are sized to the level

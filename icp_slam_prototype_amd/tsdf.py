@@ -28,6 +28,15 @@ streamed out first as points with normals:
     for depth in frames:
         pose = tracker.track(depth)
     parts = tracker.streamed + [vol.surface()]                # the model: what left, and what the box still holds
+
+A tracker that finds the camera again (K27) -- every frame it believes is encoded as a fern code and harvested as a
+keyframe when it is new enough; a frame it cannot place is not fused, and the next ones restart from the nearest
+keyframes' poses:
+
+    tracker = ModelTracker(vol, pose=first_pose, projective=True, pyramid=(10, 5, 4), relocalise=True)
+    for depth in frames:
+        pose = tracker.track(depth)
+        if tracker.lost: ...                                  # the pose is the last believed one; nothing was fused
 """
 import numpy as np
 
@@ -182,6 +191,15 @@ class TsdfVolume:
         self.ctx.tsdf_release()
 
 
+# K27's lost test: the defaults of ModelTracker(relocalise=...)'s min_overlap (pairs of level 0's last evaluated iteration
+# over the frame's valid pixels) and max_mean_dist (their mean distance, metres).  Both are OFF: on the room arc the
+# tracked frames and the wrong starts overlap in either quantity (DESIGN.md K27 holds the two tables: overlap 0.405 ..
+# 0.772 tracked against 0.035 .. 0.682 from wrong starts, mean_dist 8.5 .. 11.9 mm against 9.9 .. 30.3 mm), so neither
+# separates them and the test rests on level 0's status.
+RELOCALISE_MIN_OVERLAP = 0.0
+RELOCALISE_MAX_MEAN_DIST = float("inf")
+
+
 class ModelTracker:
     """Frame-to-model tracking over a TsdfVolume: every frame is aligned point-to-plane against the model ray-cast at
     the last pose, then fused into the model at the pose found.  pose: the first frame's camera-to-world pose; z_near,
@@ -215,10 +233,22 @@ class ModelTracker:
     the projective pairs (K26); it needs `projective` and a colour volume (ValueError otherwise), and track needs the
     frame's intensity.  Per frame the intensity goes beside the pyramid (never smoothed); per level, after the ray cast,
     binding.raycast_color_gradients (radius gradient_radius * 2^l, default 2 voxels at level 0; min_neighbors 4) and
-    binding.align_projective_colored.  None: the projective path above, untouched."""
+    binding.align_projective_colored.  None: the projective path above, untouched.
+    relocalise: True, or dict(fern= (a dict of FernParams fields; level defaults to the coarsest pyramid level), k= (3),
+    min_overlap=, max_mean_dist=) -- fern keyframe relocalisation (K27); it needs `projective` (ValueError otherwise).
+    A frame's alignment is accepted iff level 0's status is ICPK_OK, its count >= min_overlap * (the frame's valid
+    pixels) and its mean_dist <= max_mean_dist.  An accepted frame is fused as above and goes through
+    binding.fern_process(ctx, pose): keyframes are harvested from frames the tracker believes, the first frame included.  A
+    frame that fails -- a level-0 ray cast below min_pairs included, which raises without relocalise -- is not fused,
+    leaves the pose alone and sets self.lost.  While lost, a frame goes to the relocaliser first: its k nearest keyframes
+    (none when the frame has fewer than min_valid valid ferns) are tried in order, each as both the ray casts' pose and
+    the start of the same coarse-to-fine loop, and the first that passes the test becomes the pose; the frame is fused
+    and lost is cleared.  track returns the pose either way: callers read self.lost, and self.relocalisations,
+    self.frames_lost, self.keyframes count.  None: every path above, untouched."""
 
     def __init__(self, vol, pose=None, z_near=0.25, z_far=6.0, step=None, min_weight=1, bilateral=None, follow=None,
-                 on_leave=None, pyramid=None, pyramid_cutoff=None, projective=None, projective_color=None, **align_kw):
+                 on_leave=None, pyramid=None, pyramid_cutoff=None, projective=None, projective_color=None, relocalise=None,
+                 **align_kw):
         self.vol = vol
         self.pose = np.eye(4) if pose is None else np.array(pose, np.float64).reshape(4, 4)
         self.ray = dict(z_near=z_near, z_far=z_far, step=step, min_weight=min_weight)
@@ -260,19 +290,41 @@ class ModelTracker:
             unknown = set(self.projective_color) - {"lambda_geometric", "gradient_radius", "min_neighbors"}
             if unknown:
                 raise ValueError(f"projective_color has no setting {sorted(unknown)}")
+        # K27: None, True or dict(fern= (FernParams fields; level: the coarsest pyramid level), k= (3), min_overlap=,
+        # max_mean_dist=)
+        self.relocalise = None if relocalise is None else ({} if relocalise is True else dict(relocalise))
+        self.lost = False
+        self.relocalisations = self.frames_lost = 0
+        self._reloc = None  # the depth.Relocaliser, made with the first frame (its level's shape is the frame's)
+        if self.relocalise is not None:
+            if self.projective is None:
+                raise ValueError("relocalise needs projective")
+            unknown = set(self.relocalise) - {"fern", "k", "min_overlap", "max_mean_dist"}
+            if unknown:
+                raise ValueError(f"relocalise has no setting {sorted(unknown)}")
+            self.relocalise_k = int(self.relocalise.get("k", 3))
+            if not 1 <= self.relocalise_k <= binding.FERN_MAX_K:
+                raise ValueError(f"relocalise: k in 1 .. {binding.FERN_MAX_K}")
+            self.min_overlap = float(self.relocalise.get("min_overlap", RELOCALISE_MIN_OVERLAP))
+            self.max_mean_dist = float(self.relocalise.get("max_mean_dist", RELOCALISE_MAX_MEAN_DIST))
 
     def _track_projective(self, depth, intensity=None):
         """The pose of one frame by projective association, coarse to fine: one build, then per level a ray cast of the
         model at the last pose and the device loop over the level and the maps, both where they lie."""
+        # (with `bilateral` the depth is smoothed and the intensity is not)
+        shapes = depth_front.build_pyramid(self.vol.ctx, depth, self.pyramid_params, smooth=self.bilateral,
+                                           intensity=None if self.projective_color is None else intensity)
+        return self._projective_levels(shapes, self.pose)
+
+    def _projective_levels(self, shapes, pose, soft=False):
+        """The coarse-to-fine loop over the resident pyramid: `pose` is both the ray casts' pose and the start.  soft
+        (K27): a level-0 ray cast below min_pairs returns None in place of raising."""
         vol, ctx = self.vol, self.vol.ctx
         color = self.projective_color
-        # (with `bilateral` the depth is smoothed and the intensity is not)
-        shapes = depth_front.build_pyramid(ctx, depth, self.pyramid_params, smooth=self.bilateral,
-                                           intensity=None if color is None else intensity)
         if color is not None:
             cparams = binding.default_projective_color_params(**{k: color[k] for k in ("lambda_geometric",) if k in color})
             radius0 = float(color.get("gradient_radius", 2.0 * vol.params.voxel))
-        estimate = self.pose
+        estimate = pose
         self.level_hits, self.level_stats = [None] * len(shapes), [None] * len(shapes)
         for l in range(len(shapes) - 1, -1, -1):
             scale = float(2 ** l)
@@ -281,10 +333,13 @@ class ModelTracker:
             ray = binding.tsdf_raycast_params(shape=shapes[l], fx=vol.fx / scale, cx=vol.cx / scale, z_near=self.ray["z_near"],
                                               z_far=self.ray["z_far"], step=0.0 if self.ray["step"] is None else self.ray["step"],
                                               min_weight=self.ray["min_weight"])
-            n_hits, _ = ctx.tsdf_raycast(self.pose, ray)
+            n_hits, _ = ctx.tsdf_raycast(pose, ray)
             self.level_hits[l] = n_hits
             if n_hits < params.min_pairs:
                 if l == 0:
+                    if soft:
+                        self.n_hits, self.stats = n_hits, None
+                        return None
                     raise RuntimeError(f"the ray cast hit the model in {n_hits} pixels, fewer than min_pairs = {params.min_pairs}")
                 self.levels_skipped += 1
                 continue
@@ -295,6 +350,66 @@ class ModelTracker:
                 estimate, self.level_stats[l] = binding.align_projective_colored(ctx, estimate, params, cparams)
         self.n_hits, self.stats = self.level_hits[0], self.level_stats[0]
         return estimate
+
+    # ---- K27: the lost test and the way back ----
+    def accepted(self, valid):
+        """The lost test on the last alignment: level 0's status is ICPK_OK, its pairs are at least min_overlap of the
+        frame's `valid` pixels, and their mean distance is at most max_mean_dist."""
+        st = self.stats
+        return st is not None and st.status == binding.OK and st.count >= self.min_overlap * valid and \
+            st.mean_dist <= self.max_mean_dist
+
+    @property
+    def keyframes(self):
+        return 0 if self._reloc is None else self._reloc.count
+
+    def _fuse(self, depth, intensity):
+        vol = self.vol
+        if self.follow is not None:
+            before = vol.total.copy()
+            left = vol.follow(self.pose, self.follow)
+            self.shifts += bool((vol.total != before).any())
+            if left is not None and left["points"].shape[1] > 0:
+                self.on_leave(left)
+        vol.integrate(depth, self.pose, intensity)
+        self.frames += 1
+
+    def _track_relocalise(self, depth, intensity):
+        """track() with relocalise: a frame whose alignment fails the lost test is not fused and leaves the pose alone;
+        while lost, a frame is looked up among the keyframes and the alignment restarts from their poses."""
+        ctx = self.vol.ctx
+        shapes = depth_front.build_pyramid(ctx, depth, self.pyramid_params, smooth=self.bilateral,
+                                           intensity=None if self.projective_color is None else intensity)
+        if self._reloc is None:
+            fern = dict(self.relocalise.get("fern", {}))
+            fern.setdefault("level", len(shapes) - 1)
+            self._reloc = depth_front.Relocaliser(ctx, shapes[fern["level"]] if 0 <= fern["level"] < len(shapes) else (0, 0),
+                                                  **fern)
+        if self.frames > 0:
+            valid = int(np.count_nonzero(depth))
+            found = None
+            if not self.lost:
+                estimate = self._projective_levels(shapes, self.pose, soft=True)
+                if estimate is not None and self.accepted(valid):
+                    found = estimate
+            else:
+                r = self._reloc.process(None, self.relocalise_k)
+                if r["valid"] >= self._reloc.params.min_valid:  # (a frame with too few valid ferns is not tried)
+                    for candidate in r["poses"]:
+                        estimate = self._projective_levels(shapes, candidate, soft=True)
+                        if estimate is not None and self.accepted(valid):
+                            found = estimate
+                            self.relocalisations += 1
+                            break
+            if found is None:
+                self.lost = True
+                self.frames_lost += 1
+                return self.pose.copy()
+            self.lost = False
+            self.pose = found
+        self._fuse(depth, intensity)
+        self._reloc.process(self.pose, 1)  # keyframes come from frames the tracker believes, the first one included
+        return self.pose.copy()
 
     def _track_pyramid(self, depth):
         """The pose of one frame, coarse to fine: one build, then per level a ray cast of the model at the last pose,
@@ -333,6 +448,8 @@ class ModelTracker:
         vol, ctx = self.vol, self.vol.ctx
         if self.projective_color is not None and intensity is None:
             raise ValueError("projective_color needs the frame's intensity")
+        if self.relocalise is not None:
+            return self._track_relocalise(depth, intensity)
         if self.frames > 0 and self.projective is not None:
             self.pose = self._track_projective(depth, intensity)
         elif self.frames > 0 and self.pyramid is not None:
@@ -351,14 +468,7 @@ class ModelTracker:
             ctx.commit_source()
             T, self.stats, _ = ctx.align(params)
             self.pose = T.astype(np.float64) @ self.pose
-        if self.follow is not None:
-            before = vol.total.copy()
-            left = vol.follow(self.pose, self.follow)
-            self.shifts += bool((vol.total != before).any())
-            if left is not None and left["points"].shape[1] > 0:
-                self.on_leave(left)
-        vol.integrate(depth, self.pose, intensity)
-        self.frames += 1
+        self._fuse(depth, intensity)
         return self.pose.copy()
 
 

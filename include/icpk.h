@@ -1877,6 +1877,95 @@ int icpk_projective_pixels_colored(const icpk_projective_params *params, const d
                                    const float *level_intensity, const float *view_intensity,
                                    const float *const gradient[3], const icpk_projective_color_params *color);
 
+/* ---- K27: fern keyframe relocalisation ------------------------------------------------------------------------------
+ * A tracker that has lost the camera (a covered lens, a fast turn, dropped frames) finds it again by looking the frame
+ * up among keyframes it harvested while it tracked (Glocker et al., "Real-time RGB-D camera relocalization via
+ * randomized ferns for keyframe encoding").  A frame is a short binary code of a coarse level of the resident pyramid
+ * (K24); the database of codes lies on the device, the pose of every keyframe on the host beside it.
+ *
+ * THE FERN RULE (integers only, so a code is a function of the level and the parameters alone and a search's answer a
+ * function of the codes alone: block shape, and which thread looked at which keyframe, do not matter).
+ *   Parameters (icpk_fern_params; defaults from icpk_default_fern_params):
+ *     level          a level of the resident pyramid (2)
+ *     n_ferns        F, a multiple of 8 in 8 .. ICPK_FERN_MAX_FERNS (256)
+ *     seed           uint64 (27)
+ *     d_min, d_max   uint16 depth units, 0 <= d_min < d_max <= 65535 (1000, 20000)
+ *     capacity       1 .. ICPK_FERN_MAX_KEYFRAMES keyframes (4096)
+ *     harvest_above  0 .. F (F / 5 = 51)
+ *     min_valid      0 .. F (F / 2 = 128)
+ *   The table is a function of the parameters and the level's shape rows x cols.
+ *     draw(f, j) = (uint32)(mix(seed + (f + 1) * 0x9E3779B97F4A7C15 + j * 0xD1B54A32D192ED03) >> 32), mod 2^64, mix being
+ *     icpk_set_subsample's finaliser (z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *     z ^= z >> 31).
+ *     Fern f tests pixel (draw(f, 0) % rows, draw(f, 1) % cols); its thresholds are
+ *     tau_k = d_min + draw(f, 2 + k) % (d_max - d_min), k = 0 .. 3.
+ *   The code comes from the depth d of that pixel in the level (0 a hole):
+ *     nibble n_f has bit k set iff d > tau_k (strict); a hole gives 0;
+ *     V = the number of ferns with d != 0;
+ *     packed: word w of F / 8 uint32 words holds fern 8 w + j in bits 4 j .. 4 j + 3.
+ *   Dissimilarity: diss(a, b) = the number of ferns whose nibbles differ, 0 .. F.  On packed words:
+ *     x = a ^ b; x |= x >> 1; x |= x >> 2; popcount(x & 0x11111111), summed over the words.
+ *   Search: for a query code and keyframes 0 .. n - 1 the answer is the min(k, n) keyframes in ascending (diss, index)
+ *     order; ties go to the lower index.
+ *   Harvest: a frame's code becomes keyframe n iff V >= min_valid, n < capacity, and n == 0 or its smallest
+ *     dissimilarity to the database exceeds harvest_above.
+ *
+ * A context holds one database and one "current code", the code of the last encode; both stay on the device.
+ * icpk_fern_create        rows, cols: the shape of the level that will be encoded.  params NULL: the defaults.  Replaces
+ *     any previous database of the context; the memory for `capacity` keyframes is taken here (65536 keyframes of 1024
+ *     ferns: 32 MB, the largest).
+ * icpk_fern_reset         empties the database.      icpk_fern_destroy  frees it.
+ * icpk_fern_count         the number of keyframes (>= 0), or a negative status.
+ * icpk_fern_encode        level params.level of the resident pyramid into the current code; code_out (F / 8 words) and
+ *     valid_out may be NULL.
+ * icpk_fern_query         the search with the current code: index_out, diss_out (k entries each), *n_out = min(k, n).
+ * icpk_fern_add           appends the current code unconditionally, with its pose (camera-to-world, double[16]).
+ * icpk_fern_process       the per-frame call: encode, search and -- when pose is not NULL and the harvest rule says so --
+ *     append; *added_out is the new index or -1 (valid_out, added_out may be NULL).  The search it reports is the one
+ *     BEFORE the append.  Three launches (encode, search, merge), one copy, one host wait, no host round trip between
+ *     the launches; an append is a fourth launch nobody waits for.
+ * icpk_fern_add_code      appends a host code (F / 8 words): restores a saved database.
+ * icpk_fern_get_keyframe  one keyframe back: code_out (F / 8 words) and pose_out (double[16]), either may be NULL.
+ * icpk_fern_table, icpk_fern_encode_host, icpk_fern_dissimilarity_host  host only, no context, no device, through the
+ *     header the kernels include (csrc/fern_rule.h): the table as F x 6 int32 (row, col, tau_0 .. tau_3); the code and V
+ *     of a host level of rows x cols; diss(a, b), >= 0 (or ICPK_E_ARG).  params NULL: the defaults.
+ * No fern call touches the context's clouds, associations, records, seeds, surface list, ray-cast maps, the pyramid or
+ * its intensity.  A pyramid build does not touch the database: it only invalidates the current code.
+ * ICPK_E_NOT_SET: no database; no pyramid; no current code, or one that dates from before the last pyramid build.
+ * Refusals (ICPK_E_ARG; a refused call leaves everything as it was): NULL arguments; parameters outside the ranges
+ *     above; rows or cols < 1 or more than 2^28 pixels; a level the pyramid lacks; a resident level whose shape is not
+ *     the database's; k outside 1 .. ICPK_FERN_MAX_K; a non-finite pose; an index outside 0 .. n - 1; icpk_fern_add /
+ *     icpk_fern_add_code on a full database (icpk_fern_process on a full database adds nothing and is no error). */
+#define ICPK_FERN_MAX_K 8
+#define ICPK_FERN_MAX_FERNS 1024
+#define ICPK_FERN_MAX_KEYFRAMES 65536
+typedef struct icpk_fern_params {
+  int32_t level;         /* of the resident pyramid (2) */
+  int32_t n_ferns;       /* F: a multiple of 8 in 8 .. 1024 (256) */
+  uint64_t seed;         /* (27) */
+  int32_t d_min, d_max;  /* depth units (1000, 20000) */
+  int32_t capacity;      /* keyframes: 1 .. 65536 (4096) */
+  int32_t harvest_above; /* 0 .. F (F / 5) */
+  int32_t min_valid;     /* 0 .. F (F / 2) */
+  int32_t reserved;      /* 0 */
+} icpk_fern_params;
+void icpk_default_fern_params(icpk_fern_params *p);
+int icpk_fern_create(icpk_ctx *ctx, const icpk_fern_params *params, int32_t rows, int32_t cols);
+int icpk_fern_reset(icpk_ctx *ctx);
+int icpk_fern_destroy(icpk_ctx *ctx);
+int icpk_fern_count(icpk_ctx *ctx);
+int icpk_fern_encode(icpk_ctx *ctx, uint32_t *code_out, int32_t *valid_out);
+int icpk_fern_query(icpk_ctx *ctx, int32_t k, int32_t *index_out, int32_t *diss_out, int32_t *n_out);
+int icpk_fern_add(icpk_ctx *ctx, const double pose[16], int32_t *index_out);
+int icpk_fern_process(icpk_ctx *ctx, const double *pose, int32_t k, int32_t *index_out, int32_t *diss_out,
+                      int32_t *n_out, int32_t *valid_out, int32_t *added_out);
+int icpk_fern_add_code(icpk_ctx *ctx, const uint32_t *code, const double pose[16], int32_t *index_out);
+int icpk_fern_get_keyframe(icpk_ctx *ctx, int32_t index, uint32_t *code_out, double *pose_out);
+int icpk_fern_table(const icpk_fern_params *params, int32_t rows, int32_t cols, int32_t *table_out);
+int icpk_fern_encode_host(const icpk_fern_params *params, const uint16_t *level, int32_t rows, int32_t cols,
+                          uint32_t *code_out, int32_t *valid_out);
+int icpk_fern_dissimilarity_host(const uint32_t *a, const uint32_t *b, int32_t n_ferns);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
