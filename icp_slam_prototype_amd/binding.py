@@ -102,6 +102,9 @@ SYMBOLS = [
     "icpk_default_fern_params", "icpk_fern_create", "icpk_fern_reset", "icpk_fern_destroy", "icpk_fern_count",
     "icpk_fern_encode", "icpk_fern_query", "icpk_fern_add", "icpk_fern_process", "icpk_fern_add_code",
     "icpk_fern_get_keyframe", "icpk_fern_table", "icpk_fern_encode_host", "icpk_fern_dissimilarity_host",
+    "icpk_frame_view_build", "icpk_frame_view_levels", "icpk_frame_view_shape", "icpk_frame_view_get",
+    "icpk_frame_view_release", "icpk_frame_view_color_gradients", "icpk_frame_view_get_color_gradients",
+    "icpk_projective_set_view", "icpk_frame_view_pixels",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -224,6 +227,7 @@ class PyramidParams(C.Structure):
 
 
 PROJECTIVE_MAX_ITERATIONS = 64  # icpk_projective_params.max_iterations
+VIEW_RAYCAST, VIEW_FRAME = 0, 1  # icpk_projective_set_view: which planes the projective calls read (K28)
 # icpk_projective_associate: why a pixel has no pair
 PROJ_NO_DEPTH, PROJ_BEHIND, PROJ_OUTSIDE, PROJ_NO_MODEL, PROJ_TOO_FAR, PROJ_NO_NORMAL, PROJ_NORMAL = -1, -2, -3, -4, -5, -6, -7
 
@@ -553,6 +557,16 @@ def load():
     lib.icpk_fern_table.argtypes = [ep, C.c_int32, C.c_int32, ip]
     lib.icpk_fern_encode_host.argtypes = [ep, u16, C.c_int32, C.c_int32, u32, ip]
     lib.icpk_fern_dissimilarity_host.argtypes = [u32, u32, C.c_int32]
+    lib.icpk_frame_view_build.argtypes = [C.c_void_p, C.c_float, C.c_float, dp, ip, ip]
+    lib.icpk_frame_view_levels.argtypes = [C.c_void_p]
+    lib.icpk_frame_view_shape.argtypes = [C.c_void_p, C.c_int32, ip, ip]
+    lib.icpk_frame_view_get.argtypes = [C.c_void_p, C.c_int32, C.POINTER(fp)]
+    lib.icpk_frame_view_release.argtypes = [C.c_void_p]
+    lib.icpk_frame_view_color_gradients.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32]
+    lib.icpk_frame_view_get_color_gradients.argtypes = [C.c_void_p, C.c_int32, fp, fp, fp]
+    lib.icpk_projective_set_view.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.icpk_frame_view_pixels.argtypes = [C.c_float, C.c_float, C.c_int32, dp, u16, fp, C.c_int32, C.c_int32, C.c_int64,
+                                           C.c_int32, fp, ip]
     _lib = lib
     return lib
 
@@ -1323,6 +1337,87 @@ def fern_keyframe(ctx, index):
     code, pose = np.zeros(_fern_w(ctx), np.uint32), np.zeros(16, np.float64)
     ctx._chk(ctx._lib.icpk_fern_get_keyframe(ctx._h, int(index), _u32p(code), pose.ctypes.data_as(C.POINTER(C.c_double))))
     return code, pose.reshape(4, 4)
+
+
+# ---- the frame view (K28): functions of a context, like the projective calls above, and a host-only one -----------------
+def frame_view_pixels(depth, pose, fx=468.60, cx=318.27, level=0, intensity=None, first=0, count=None):
+    """icpk_frame_view_pixels (host only): THE FRAME VIEW RULE for `count` pixels from row-major pixel `first` of the
+    (rows, cols) uint16 image `depth` -- the level's own image; `level` only scales fx, cx -- at the camera-to-world
+    `pose`.  intensity: the level's (rows, cols) float32, or None.  Returns (planes (8, count) float32: x, y, z, nx, ny,
+    nz, depth, intensity; n_valid; n_no_normal)."""
+    img = np.ascontiguousarray(depth, np.uint16)
+    if img.ndim != 2:
+        raise ValueError("depth: a (rows, cols) image expected")
+    inten = None if intensity is None else _f(intensity).reshape(img.shape)
+    count = img.size - int(first) if count is None else int(count)
+    out, none = np.zeros((8, max(count, 1)), np.float32), C.c_int32(-1)
+    P = None if pose is None else _pose16(pose)
+    rc = load().icpk_frame_view_pixels(float(fx), float(cx), int(level), None if P is None else P.ctypes.data_as(C.POINTER(C.c_double)),
+                                       img.ctypes.data_as(C.POINTER(C.c_uint16)), None if inten is None else _fp(inten),
+                                       img.shape[0], img.shape[1], int(first), count, _fp(out), C.byref(none))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_frame_view_pixels")
+    return out[:, :count], rc, none.value
+
+
+def frame_view_build(ctx, pose, fx=468.60, cx=318.27, counts=True):
+    """icpk_frame_view_build: every level of the resident pyramid as eight planes in world coordinates at the
+    camera-to-world `pose`, kept by the context until the next build or frame_view_release.  Returns (n_valid,
+    n_no_normal), one int per level; counts=False: None, and the call does not wait."""
+    P = None if pose is None else _pose16(pose)
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    nv, nn = np.full(PYRAMID_MAX_LEVELS, -1, np.int32), np.full(PYRAMID_MAX_LEVELS, -1, np.int32)
+    ctx._chk(ctx._lib.icpk_frame_view_build(ctx._h, float(fx), float(cx), None if P is None else P.ctypes.data_as(dp),
+                                              nv.ctypes.data_as(ip) if counts else None,
+                                              nn.ctypes.data_as(ip) if counts else None))
+    if not counts:
+        return None
+    L = frame_view_levels(ctx)
+    return [int(x) for x in nv[:L]], [int(x) for x in nn[:L]]
+
+
+def frame_view_levels(ctx):
+    """icpk_frame_view_levels: the levels of the snapshot (0 without one)."""
+    return ctx._chk(ctx._lib.icpk_frame_view_levels(ctx._h))
+
+
+def frame_view_shape(ctx, level):
+    """icpk_frame_view_shape: (rows, cols) of a level of the snapshot."""
+    r, c = C.c_int32(0), C.c_int32(0)
+    ctx._chk(ctx._lib.icpk_frame_view_shape(ctx._h, int(level), C.byref(r), C.byref(c)))
+    return r.value, c.value
+
+
+def frame_view(ctx, level):
+    """icpk_frame_view_get: the (8, rows, cols) float32 planes x, y, z, nx, ny, nz, depth, intensity of a level."""
+    rows, cols = frame_view_shape(ctx, level)
+    out = np.zeros((8, rows, cols), np.float32)
+    ctx._chk(ctx._lib.icpk_frame_view_get(ctx._h, int(level), (C.POINTER(C.c_float) * 8)(*[_fp(out[k]) for k in range(8)])))
+    return out
+
+
+def frame_view_release(ctx):
+    """icpk_frame_view_release: drops the snapshot and its memory."""
+    ctx._chk(ctx._lib.icpk_frame_view_release(ctx._h))
+
+
+def frame_view_color_gradients(ctx, level, radius, min_neighbors=4):
+    """icpk_frame_view_color_gradients: THE VIEW GRADIENT RULE over a level of the snapshot, kept beside it.  No wait."""
+    ctx._chk(ctx._lib.icpk_frame_view_color_gradients(ctx._h, int(level), float(radius), int(min_neighbors), 0))
+
+
+def frame_view_get_color_gradients(ctx, level):
+    """icpk_frame_view_get_color_gradients: (3, rows, cols) float32."""
+    rows, cols = frame_view_shape(ctx, level)
+    g = np.zeros((3, rows, cols), np.float32)
+    ctx._chk(ctx._lib.icpk_frame_view_get_color_gradients(ctx._h, int(level), _fp(g[0]), _fp(g[1]), _fp(g[2])))
+    return g
+
+
+def projective_set_view(ctx, which, view_level=0):
+    """icpk_projective_set_view: VIEW_RAYCAST (the default) or VIEW_FRAME with the snapshot's level the projective
+    calls (align_projective and its neighbours) then read."""
+    ctx._chk(ctx._lib.icpk_projective_set_view(ctx._h, int(which), int(view_level)))
 
 
 class Context:

@@ -21,7 +21,7 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_tsdf.cpp", "kernels_tsdf.hip", "icpk_bilateral.cpp", "kernels_bilateral.hip",
            "icpk_pyramid.cpp", "kernels_pyramid.hip", "icpk_projective.cpp", "kernels_projective.hip",
            "kernels_pyramid_color.hip", "icpk_raycast_color.cpp", "kernels_raycast_color.hip",
-           "icpk_fern.cpp", "kernels_fern.hip"]
+           "icpk_fern.cpp", "kernels_fern.hip", "icpk_frame_view.cpp", "kernels_frame_view.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -499,6 +499,24 @@ def build_projective_test(force=False):
     return PROJECTIVE_TEST
 
 
+FRAME_ODOMETRY_TEST = os.path.join(LIBDIR, "test_frame_odometry")
+
+
+def build_frame_odometry_test(force=False):
+    """Host-only C++ program over icp::Engine::buildFrameView / setProjectiveView and icp::FrameOdometry (icp_align.hpp,
+    icp_odometry.hpp, K28) (g++, links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_frame_odometry.cpp")
+    hdrs = [os.path.join(HERE, "include", h) for h in ("icp_align.hpp", "icp_odometry.hpp")]
+    build()
+    newest = max(os.path.getmtime(p) for p in [src, LIB] + hdrs)
+    if not force and os.path.exists(FRAME_ODOMETRY_TEST) and os.path.getmtime(FRAME_ODOMETRY_TEST) >= newest:
+        return FRAME_ODOMETRY_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", FRAME_ODOMETRY_TEST])
+    return FRAME_ODOMETRY_TEST
+
+
 PROJECTIVE_HOST_SANITIZED = os.path.join(LIBDIR, "projective_host_sanitized")
 
 
@@ -705,4 +723,5 @@ if __name__ == "__main__":
     print(build_projective_test(force="--force" in sys.argv))
     print(build_projective_color_test(force="--force" in sys.argv))
     print(build_fern_test(force="--force" in sys.argv))
+    print(build_frame_odometry_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

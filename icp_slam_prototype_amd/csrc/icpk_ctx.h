@@ -493,6 +493,12 @@ struct icpk_ctx {
   std::vector<double> fern_poses;      // 16 per keyframe
   bool fern_code_current = false;      // the current code is of the resident pyramid
   int fern_code_valid = 0;             // ... and its V
+  // K28 (icpk_frame_view.cpp), behind everything older for the same reason: the frame view -- a snapshot of the pyramid
+  // as eight planes per level, null until the first icpk_frame_view_build, outside the TSDF state and untouched by it
+  // and by the pyramid builds -- and which view the projective calls read (icpk_projective_set_view)
+  struct icpk_frame_view_state* fview = nullptr;
+  int proj_view_which = ICPK_VIEW_RAYCAST;
+  int proj_view_level = 0;
 };
 
 #define ICPK_HIP(ctx, call)                                                                      \
@@ -508,6 +514,7 @@ void icpk_comm_release(icpk_ctx* ctx);  // called by icpk_destroy
 void icpk_map_free(icpk_ctx* ctx);      // called by icpk_destroy (icpk_map.cpp)
 void icpk_fast_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_fast.cpp)
 void icpk_tsdf_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_tsdf.cpp)
+void icpk_frame_view_free(icpk_ctx* ctx);  // called by icpk_destroy (icpk_frame_view.cpp)
 int icpk_comm_allreduce_device(icpk_ctx* ctx, double* dev, int n);  // in-stream sum over the ranks (icpk_comm.cpp)
 // ICPK_NN_MAP: one K9 sweep of the working source against the map into ctx->best (icpk_map.cpp); the target must be
 // the map's current lookup target
@@ -636,6 +643,13 @@ int tsdf_raycast_view(icpk_ctx* ctx, TsdfRayView* out);
 // K26, after tsdf_raycast_view has succeeded: whether the volume keeps intensities, and the three gradient planes of
 // icpk_tsdf_raycast_color_gradients for the current ray cast (nullptr without them)
 void tsdf_raycast_color_view(icpk_ctx* ctx, bool* color, const float** grad);
+
+// ---- icpk_frame_view.cpp: the view the projective calls read (K28) ----
+// With ICPK_VIEW_RAYCAST exactly tsdf_raycast_view / tsdf_raycast_color_view.  With ICPK_VIEW_FRAME the selected level
+// of the frame view in the same terms -- its eight planes, shape, fx / 2^l, cx / 2^l and pose; ICPK_E_NOT_SET without a
+// snapshot or for a level it lacks --, whether the snapshot carries intensities, and that level's gradient planes
+int projective_view(icpk_ctx* ctx, TsdfRayView* out);
+void projective_color_view(icpk_ctx* ctx, bool* color, const float** grad);
 
 // ---- icpk_batch.cpp: the lock-step machinery icpk_frames_batch.cpp shares ----
 bool batch_eligible(const icpk_ctx* ctx, const icpk_params* p);  // params the lock-step path runs

@@ -1061,4 +1061,25 @@ void launch_proj_step(const double* partial, const int* pcount, int nblocks, Pro
 // every pixel's code or view pixel, and its distance, at the state's pose (device arrays of rows cols entries)
 void launch_proj_associate(const ProjArgs& a, int32_t* pixel, float* dist, hipStream_t s);
 
+// kernels_frame_view.hip -- K28, the frame view (the frame view rule is frame_view_rule.h)
+constexpr int FRAME_VIEW_THREADS = 256;
+constexpr int FRAME_VIEW_MAX_LEVELS = 8;  // ICPK_PYRAMID_MAX_LEVELS
+struct FrameViewLevel {
+  const uint16_t* depth;  // the pyramid's level ...
+  const float* inten;     // ... and its intensities (nullptr: the view's intensity plane holds 0)
+  float* planes;          // 8 planes of rows cols floats: x, y, z, nx, ny, nz, depth, intensity
+  int rows, cols;
+  float fx, cx;           // fx / 2^l, cx / 2^l
+};
+struct FrameViewArgs {
+  FrameViewLevel level[FRAME_VIEW_MAX_LEVELS];
+  int block0[FRAME_VIEW_MAX_LEVELS + 1];  // level l owns workgroups block0[l] .. block0[l + 1); [levels]: the grid
+  int levels;
+  float R[9], t[3];  // the pose rounded to float once
+  int* slots;        // [2 x grid] listed pixels, pixels without a normal, per workgroup
+};
+inline int frame_view_blocks(int npix) { return (npix + FRAME_VIEW_THREADS - 1) / FRAME_VIEW_THREADS; }
+// every level in one launch, then totals[2 l], totals[2 l + 1] = level l's two counts (device, 2 x levels ints)
+void launch_frame_view(const FrameViewArgs& a, int* totals, hipStream_t s);
+
 }  // namespace icpk

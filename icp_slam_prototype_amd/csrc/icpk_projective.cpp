@@ -1,7 +1,8 @@
 // icpk_projective.cpp -- K25, host side of the projective frame-to-model alignment (include/icpk.h, THE PROJECTIVE RULE;
 // kernels_projective.hip): the defaults, the refusals, the rule over host images through the header the kernel includes
 // (icpk_projective_pixels -- the host-only half: it needs no context and no device), and the three entry points that
-// run on the device over a level of the resident pyramid (K24) and the maps of the last ray cast (K20).  They read
+// run on the device over a level of the resident pyramid (K24) and the maps of the last ray cast (K20) -- or, when
+// icpk_projective_set_view says so, a level of the frame view (K28; icpk_frame_view.cpp resolves which).  They read
 // both where they lie and write only the scratch the context keeps for them.  K26's coloured entry points
 // (icpk_projective_reduce_colored, icpk_align_projective_colored, icpk_projective_pixels_colored) share every line with
 // them but the refusals of their own and the choice of rule 9.
@@ -47,20 +48,12 @@ icpk_projective_params params_or_defaults(const icpk_projective_params* params) 
   return p;
 }
 
-// the nine R and three t of a camera-to-world pose rounded to float once
-void round_pose(const double pose[16], float R[9], float t[3]) {
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) R[3 * r + c] = (float)pose[4 * r + c];
-    t[r] = (float)pose[4 * r + 3];
-  }
-}
-
 // Everything a device call needs, checked in the header's order of refusals: nothing of the context has changed when
 // this fails.  a.partial / a.pcount / a.st are left for the caller.
 int prepare(icpk_ctx* ctx, const icpk_projective_params& p, const double* pose, ProjArgs* a) {
   if (const char* why = check_params(p, pose)) return fail(ctx, ICPK_E_ARG, why);
   TsdfRayView view;
-  if (int rc = tsdf_raycast_view(ctx, &view)) return rc;
+  if (int rc = projective_view(ctx, &view)) return rc;  // (K28: the ray cast's planes, or a level of the frame view)
   if (ctx->pyr_levels == 0) return fail(ctx, ICPK_E_NOT_SET, "no depth pyramid (icpk_depth_pyramid_build)");
   if (p.level >= ctx->pyr_levels) return fail(ctx, ICPK_E_ARG, "a level the pyramid does not have");
   const float scale = (float)(1 << p.level);  // (a power of two: both quotients are exact)
@@ -85,7 +78,7 @@ int begin_state(icpk_ctx* ctx, const double pose[16], ProjArgs* a) {
   if (int rc = ctx->proj_block_host.reserve(ctx, 1)) return rc;
   ProjState& st = ctx->proj_block_host.get()->st;
   std::memset(&st, 0, sizeof(st));
-  round_pose(pose, st.R, st.t);
+  proj_round_pose(pose, st.R, st.t);
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 4; ++c) st.E[4 * r + c] = pose[4 * r + c];
   // (the staging copy is read by this copy alone, and every call ends with a wait on the stream)
@@ -111,9 +104,13 @@ int prepare_colored(icpk_ctx* ctx, const icpk_projective_params& p, const icpk_p
   if (int rc = prepare(ctx, p, pose, a)) return rc;
   bool color = false;
   const float* grad = nullptr;
-  tsdf_raycast_color_view(ctx, &color, &grad);
+  const bool frame = ctx->proj_view_which == ICPK_VIEW_FRAME;
+  projective_color_view(ctx, &color, &grad);
+  if (!color && frame) return fail(ctx, ICPK_E_NOT_SET, "the frame view was built without an intensity pyramid");
   if (!color) return fail(ctx, ICPK_E_ARG, "the volume keeps no intensities");
   if (!ctx->pyr_have_int) return fail(ctx, ICPK_E_NOT_SET, "no intensity pyramid (icpk_depth_pyramid_set_intensity)");
+  if (!grad && frame)
+    return fail(ctx, ICPK_E_NOT_SET, "no colour gradients of this frame-view level (icpk_frame_view_color_gradients)");
   if (!grad) return fail(ctx, ICPK_E_NOT_SET, "no colour gradients of this ray cast (icpk_tsdf_raycast_color_gradients)");
   a->inten = ctx->pyr_int + ctx->pyr_off[p.level];
   a->grad = grad;
@@ -192,7 +189,7 @@ int pixels_impl(const icpk_projective_params* params, const double pose[16], con
   ProjView vw{view[0], view[1], view[2], view[3], view[4], view[5], view[6], rows_v, cols_v, fx_v, cx_v, {}, {}};
   if (icpk_tsdf_invert_pose(view_pose, vw.Q, vw.s) != ICPK_OK) return ICPK_E_ARG;
   ProjPose E;
-  round_pose(pose, E.R, E.t);
+  proj_round_pose(pose, E.R, E.t);
   const ProjGate g{p.max_dist, p.min_normal_cos};
   const bool with_normal = p.min_normal_cos > -1.f;
   int pairs = 0;

@@ -50,6 +50,14 @@ struct ProjPair {
   float p[3], m[3], n[3], dist;
 };
 
+// the nine R and three t of a camera-to-world pose (double[16]) rounded to float once
+ICPK_HD void proj_round_pose(const double pose[16], float R[9], float t[3]) {
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) R[3 * r + c] = (float)pose[4 * r + c];
+    t[r] = (float)pose[4 * r + 3];
+  }
+}
+
 // R v + t in the form of integration rule 2
 ICPK_HD void proj_move(const float R[9], const float t[3], const float v[3], float out[3]) {
 #pragma unroll

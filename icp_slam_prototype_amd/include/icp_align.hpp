@@ -119,6 +119,32 @@ class Engine {
   int backprojectPyramidLevel(int level, float fx, float cx, const float* offset, int which, int normalsMode = -1) {
     return icpk_depth_pyramid_backproject(ctx_, level, fx, cx, offset, which, normalsMode);
   }
+  // the frame view (icpk_frame_view_build, K28): every level of the resident pyramid as eight planes in world coordinates
+  // at `pose` (double[16], camera-to-world), kept by the engine until the next build or releaseFrameView; fx, cx are
+  // the LEVEL-0 intrinsics.  nValid / nNoNormal: one entry per level, or nullptr (both nullptr: no host wait)
+  int buildFrameView(float fx, float cx, const double* pose, int32_t* nValid = nullptr, int32_t* nNoNormal = nullptr) {
+    return icpk_frame_view_build(ctx_, fx, cx, pose, nValid, nNoNormal);
+  }
+  int frameViewLevels() { return icpk_frame_view_levels(ctx_); }
+  // one level of it: its shape, and its eight planes into `out` (8 x rows x cols floats; nullptr: the shape alone)
+  int frameViewLevel(int level, int* rows, int* cols, float* out = nullptr) {
+    int r = 0, c = 0;
+    const int rc = icpk_frame_view_shape(ctx_, level, &r, &c);
+    if (rc != ICPK_OK) return rc;
+    if (rows) *rows = r;
+    if (cols) *cols = c;
+    if (!out) return ICPK_OK;
+    float* planes[8];
+    for (int k = 0; k < 8; ++k) planes[k] = out + (size_t)k * r * c;
+    return icpk_frame_view_get(ctx_, level, planes);
+  }
+  int releaseFrameView() { return icpk_frame_view_release(ctx_); }
+  int frameViewColorGradients(int level, float radius, int minNeighbors = 4) {
+    return icpk_frame_view_color_gradients(ctx_, level, radius, minNeighbors, 0);
+  }
+  // which planes the projective calls read (icpk_projective_set_view): ICPK_VIEW_RAYCAST (the default) or
+  // ICPK_VIEW_FRAME with the level of the frame view
+  int setProjectiveView(int which, int viewLevel = 0) { return icpk_projective_set_view(ctx_, which, viewLevel); }
   // robust alignment (icpk_set_robust): trimmed pairs and Huber / Tukey weights for every later alignment of this
   // engine (Kabsch and point-to-plane flavours); clearRobust() turns it off again (the default)
   int setRobust(const icpk_robust& r) { return icpk_set_robust(ctx_, &r); }

@@ -1966,6 +1966,77 @@ int icpk_fern_encode_host(const icpk_fern_params *params, const uint16_t *level,
                           uint32_t *code_out, int32_t *valid_out);
 int icpk_fern_dissimilarity_host(const uint32_t *a, const uint32_t *b, int32_t n_ferns);
 
+/* ---- K28: the frame view -- projective frame-to-frame odometry -----------------------------------------------------
+ * K25 / K26 project a frame into "the view": eight planes x, y, z, nx, ny, nz, depth, intensity in world coordinates,
+ * with a camera and a pose.  Until here the only view was the last ray cast of a TSDF volume.  The frame view is the
+ * same eight planes made from a depth frame alone -- KinectFusion's frame-to-frame prediction, the vertex and normal
+ * map of the previous frame --, one set per level of the resident pyramid (K24; with the intensities of K26 where the
+ * pyramid carries them), kept as a snapshot the context owns so that the next frame's pyramid can overwrite the levels.
+ * No volume is needed.
+ *
+ * THE FRAME VIEW RULE.  THE PROJECTIVE RULE's own arithmetic: float32; every operation rounded once, in the order
+ * written (fl(.) is one rounding); no fused multiply-add; correctly rounded / and sqrt; no libm.
+ *   Inputs: level l of the pyramid, rows x cols, uint16, seen through fx_l = fx / 2^l, cx_l = cx / 2^l (fx, cx: the
+ *     LEVEL-0 intrinsics); a pose P, double[16], camera-to-world: its nine R and three t rounded to float once.
+ *   Pixel (r, c), i = r cols + c, depth d:
+ *     1. d == 0 (a hole): all eight planes hold 0 at i.
+ *     2. the vertex, THE PROJECTIVE RULE's step 2: v_z = fl((float)d / 5000.0f),
+ *        v_x = fl(fl(fl((float)c - cx_l) v_z) / fx_l), v_y = fl(fl(fl((float)r - cx_l) v_z) / fx_l).
+ *     3. the normal: s = the ICPK_NORMALS_CROSS normal of pixel (r, c) of the level through (fx_l, cx_l), exactly
+ *        THE PROJECTIVE RULE's step 8's.  Without one (a border pixel, a hole among the four neighbours, a zero cross
+ *        product) all eight planes hold 0 at i and the pixel counts in n_no_normal: such a pixel can never be paired.
+ *        s is negated when fl(fl(fl(s_x v_x) + fl(s_y v_y)) + fl(s_z v_z)) > 0, so that it faces the camera as a
+ *        ray-cast normal does (a dot of exactly 0 leaves it).
+ *     4. listed: (x, y, z)_a = fl(fl(fl(fl(R_a0 v_x) + fl(R_a1 v_y)) + fl(R_a2 v_z)) + t_a)   (step 3's form);
+ *        (nx, ny, nz)_a = fl(fl(fl(R_a0 s_x) + fl(R_a1 s_y)) + fl(R_a2 s_z)); depth = v_z; intensity = the intensity
+ *        pyramid's value at level l, pixel i, when the pyramid carries one, else 0.
+ *   depth > 0 is the validity test, as for the ray cast.  n_valid counts the listed pixels.
+ *   A consequence: with an estimate E == P, a listed pixel's world point (THE PROJECTIVE RULE's step 3) is the view's
+ *   point bit for bit, so it pairs at distance exactly 0 whenever it projects onto itself.
+ *
+ * icpk_frame_view_build    snapshots every level the resident pyramid has, at `pose`, through (fx, cx).  One launch for
+ *     all levels; buffers are reused while they fit.  n_valid / n_no_normal: one entry per level, or NULL; with both NULL
+ *     the call does not wait.  A pyramid rebuilt afterwards leaves the snapshot as it was; so does every TSDF call.
+ * icpk_frame_view_levels   the levels of the snapshot (0 without one).
+ * icpk_frame_view_shape / icpk_frame_view_get   a level's shape; its planes into host arrays of rows cols floats (any
+ *     may be NULL).
+ * icpk_frame_view_release  drops the snapshot and its memory (icpk_destroy does too).
+ * icpk_frame_view_color_gradients   THE VIEW GRADIENT RULE (K26), the same kernel, over the eight planes of one level;
+ *     the three planes are kept beside that level until the next build.  flags must be 0.  No host wait.
+ *     icpk_frame_view_get_color_gradients returns them.
+ * icpk_projective_set_view  decides which planes icpk_projective_associate, icpk_projective_reduce,
+ *     icpk_align_projective, icpk_projective_reduce_colored and icpk_align_projective_colored read (and so what
+ *     icpk_get_projective_trace records).  ICPK_VIEW_RAYCAST (the default): the last ray cast, nothing changes, byte for
+ *     byte; view_level is ignored.  ICPK_VIEW_FRAME: level view_level of the snapshot, with its own shape, fx / 2^view_level,
+ *     cx / 2^view_level (the build's fx, cx) and the build's pose; the calls then need no volume.  The kernels are the
+ *     same; they are handed other pointers.
+ * icpk_frame_view_pixels   host only, no context: the rule for `count` pixels from row-major pixel `first` of a host
+ *     image (rows x cols: the level's own shape; `level` only scales fx, cx).  intensity: the level's, or NULL.  out:
+ *     8 x count floats, plane k at out + k count.  Returns the number of listed pixels; *n_no_normal (or NULL) the
+ *     pixels of step 3.  Compiled from the header the kernel includes (csrc/frame_view_rule.h).
+ * None of these calls touches the context's source, target, associations, seeds, surface list, ray-cast maps, pyramid
+ * or fern database.
+ * ICPK_E_NOT_SET: no pyramid (build); no snapshot, or a level it lacks (every other call, and the projective calls
+ *     under ICPK_VIEW_FRAME); for the gradients and the coloured calls, a snapshot built without an intensity pyramid,
+ *     no intensity pyramid, or no gradients of the level.
+ * Refusals (ICPK_E_ARG; a refused call leaves everything as it was): a NULL or non-finite pose; fx not finite and > 0;
+ *     a non-finite cx; an unknown `which`; a level outside 0 .. ICPK_PYRAMID_MAX_LEVELS - 1; radius not finite and > 0;
+ *     min_neighbors < 1; flags != 0. */
+#define ICPK_VIEW_RAYCAST 0
+#define ICPK_VIEW_FRAME 1
+int icpk_frame_view_build(icpk_ctx *ctx, float fx, float cx, const double pose[16], int32_t *n_valid,
+                          int32_t *n_no_normal);
+int icpk_frame_view_levels(icpk_ctx *ctx);
+int icpk_frame_view_shape(icpk_ctx *ctx, int32_t level, int32_t *rows, int32_t *cols);
+int icpk_frame_view_get(icpk_ctx *ctx, int32_t level, float *const planes[8]);
+int icpk_frame_view_release(icpk_ctx *ctx);
+int icpk_frame_view_color_gradients(icpk_ctx *ctx, int32_t level, float radius, int32_t min_neighbors, int32_t flags);
+int icpk_frame_view_get_color_gradients(icpk_ctx *ctx, int32_t level, float *gx, float *gy, float *gz);
+int icpk_projective_set_view(icpk_ctx *ctx, int32_t which, int32_t view_level);
+int icpk_frame_view_pixels(float fx, float cx, int32_t level, const double pose[16], const uint16_t *depth,
+                           const float *intensity, int32_t rows, int32_t cols, int64_t first, int32_t count, float *out,
+                           int32_t *n_no_normal);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
