@@ -105,6 +105,8 @@ SYMBOLS = [
     "icpk_frame_view_build", "icpk_frame_view_levels", "icpk_frame_view_shape", "icpk_frame_view_get",
     "icpk_frame_view_release", "icpk_frame_view_color_gradients", "icpk_frame_view_get_color_gradients",
     "icpk_projective_set_view", "icpk_frame_view_pixels",
+    "icpk_default_sdf_params", "icpk_sdf_associate", "icpk_sdf_reduce", "icpk_align_sdf", "icpk_get_sdf_trace",
+    "icpk_sdf_pixels",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -247,6 +249,17 @@ class ProjectiveIter(C.Structure):
     """icpk_projective_iter"""
     _fields_ = [("pose", C.c_double * 12), ("sums", C.c_double * 28), ("count", C.c_int64), ("status", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+# icpk_sdf_associate: why a pixel is rejected (K29)
+SDF_NO_DEPTH, SDF_OUTSIDE, SDF_UNKNOWN, SDF_TOO_FAR, SDF_NO_GRADIENT, SDF_NO_NORMAL, SDF_NORMAL = -1, -2, -3, -4, -5, -6, -7
+
+
+class SdfParams(C.Structure):
+    """icpk_sdf_params"""
+    _fields_ = [("level", C.c_int32), ("fx", C.c_float), ("cx", C.c_float), ("max_iterations", C.c_int32),
+                ("max_abs_tsdf", C.c_float), ("min_weight", C.c_int32), ("min_normal_cos", C.c_float),
+                ("min_pairs", C.c_int32)]
 
 
 class ProjectiveColorParams(C.Structure):
@@ -567,6 +580,15 @@ def load():
     lib.icpk_projective_set_view.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     lib.icpk_frame_view_pixels.argtypes = [C.c_float, C.c_float, C.c_int32, dp, u16, fp, C.c_int32, C.c_int32, C.c_int64,
                                            C.c_int32, fp, ip]
+    sp = C.POINTER(SdfParams)
+    lib.icpk_default_sdf_params.argtypes = [sp]
+    lib.icpk_default_sdf_params.restype = None
+    lib.icpk_sdf_associate.argtypes = [C.c_void_p, sp, dp, ip, fp]
+    lib.icpk_sdf_reduce.argtypes = [C.c_void_p, sp, dp, dp, i64]
+    lib.icpk_align_sdf.argtypes = [C.c_void_p, sp, dp, dp, C.POINTER(ProjectiveResult)]
+    lib.icpk_get_sdf_trace.argtypes = [C.c_void_p, C.POINTER(ProjectiveIter), C.c_int32]
+    lib.icpk_sdf_pixels.argtypes = [sp, C.POINTER(TsdfParams), dp, u16, C.c_int32, C.c_int32, fp, u16, C.c_int64, C.c_int32,
+                                    ip, fp, dp]
     _lib = lib
     return lib
 
@@ -1418,6 +1440,95 @@ def projective_set_view(ctx, which, view_level=0):
     """icpk_projective_set_view: VIEW_RAYCAST (the default) or VIEW_FRAME with the snapshot's level the projective
     calls (align_projective and its neighbours) then read."""
     ctx._chk(ctx._lib.icpk_projective_set_view(ctx._h, int(which), int(view_level)))
+
+
+# ---- depth frames tracked directly against the TSDF (K29): functions of a context and one host-only one ---------------
+def default_sdf_params(**kw):
+    """icpk_default_sdf_params with the given fields replaced (level, fx, cx, max_iterations, max_abs_tsdf, min_weight,
+    min_normal_cos, min_pairs)."""
+    p = SdfParams()
+    load().icpk_default_sdf_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _sdf(params, kw):
+    return params if params is not None else default_sdf_params(**kw)
+
+
+def sdf_associate(ctx, pose, params=None, **kw):
+    """icpk_sdf_associate at the camera-to-world pose (4, 4) float64: (cell (rows, cols) int32 -- the linear index of the
+    lowest corner of the cell every pixel of the pyramid level lands in, or its SDF_* code --, value (rows, cols) float32:
+    the signed distance D there, 0 for a rejected pixel).  params: SdfParams, or its fields as keywords."""
+    p = _sdf(params, kw)
+    P = _pose16(pose)
+    dp = C.POINTER(C.c_double)
+    r, c = C.c_int32(0), C.c_int32(0)
+    if ctx._lib.icpk_depth_pyramid_shape(ctx._h, int(p.level), C.byref(r), C.byref(c)) != OK:
+        # (no such level: the call states its own refusal, and needs no arrays for it)
+        ctx._chk(ctx._lib.icpk_sdf_associate(ctx._h, C.byref(p), P.ctypes.data_as(dp), None, None))
+        raise IcpkError(E_ARG, "a level the pyramid does not have")
+    cell, value = np.zeros((r.value, c.value), np.int32), np.zeros((r.value, c.value), np.float32)
+    ctx._chk(ctx._lib.icpk_sdf_associate(ctx._h, C.byref(p), P.ctypes.data_as(dp), cell.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         _fp(value)))
+    return cell, value
+
+
+def sdf_reduce(ctx, pose, params=None, **kw):
+    """icpk_sdf_reduce: (28 float64 sums, accepted pixels) of one evaluation at the pose."""
+    p = _sdf(params, kw)
+    P = _pose16(pose)
+    sums, n = np.zeros(28, np.float64), C.c_int64(-1)
+    dp = C.POINTER(C.c_double)
+    ctx._chk(ctx._lib.icpk_sdf_reduce(ctx._h, C.byref(p), P.ctypes.data_as(dp), sums.ctypes.data_as(dp), C.byref(n)))
+    return sums, n.value
+
+
+def align_sdf(ctx, pose, params=None, **kw):
+    """icpk_align_sdf from the camera-to-world pose (4, 4) float64: (pose (4, 4) float64, ProjectiveResult).  The result's
+    status is OK, W_TOO_FEW_PAIRS or W_DEGENERATE; its count and mean_dist (the mean |D|) are those of the last evaluated
+    iteration, i.e. at the estimate before the last update."""
+    p = _sdf(params, kw)
+    P = _pose16(pose)
+    out, res = np.zeros(16, np.float64), ProjectiveResult()
+    dp = C.POINTER(C.c_double)
+    ctx._chk(ctx._lib.icpk_align_sdf(ctx._h, C.byref(p), P.ctypes.data_as(dp), out.ctypes.data_as(dp), C.byref(res)))
+    return out.reshape(4, 4), res
+
+
+def sdf_trace(ctx):
+    """icpk_get_sdf_trace: the evaluated iterations of the last align_sdf, a list of dict(pose (3, 4) float64 E_k, sums
+    (28,), count, status)."""
+    buf = (ProjectiveIter * PROJECTIVE_MAX_ITERATIONS)()
+    n = ctx._chk(ctx._lib.icpk_get_sdf_trace(ctx._h, buf, PROJECTIVE_MAX_ITERATIONS))
+    return [dict(pose=np.array(buf[k].pose, np.float64).reshape(3, 4), sums=np.array(buf[k].sums, np.float64),
+                 count=int(buf[k].count), status=int(buf[k].status)) for k in range(n)]
+
+
+def sdf_pixels(params, volume, pose, level, tsdf, weight, first=0, count=None, terms=False):
+    """icpk_sdf_pixels (host only): the SDF tracking rule for `count` pixels from row-major pixel `first` of the (rows,
+    cols) uint16 image `level` (default: all from there on) over the host planes tsdf float32, weight uint16 of `volume`,
+    a TsdfParams whose origin is the one to use.  Returns (cell (count,) int32: the cell or the SDF_* code; value
+    (count,) float32; terms (count, 28) float64 or None; the number of accepted pixels)."""
+    img = np.ascontiguousarray(level, np.uint16)
+    rows_s, cols_s = img.shape
+    f, w = _f(tsdf).reshape(-1), np.ascontiguousarray(weight, np.uint16).reshape(-1)
+    n = volume.dims[0] * volume.dims[1] * volume.dims[2]
+    if f.size != n or w.size != n:
+        raise ValueError("the planes must hold one entry per voxel")
+    count = rows_s * cols_s - int(first) if count is None else int(count)
+    m = max(count, 0)
+    cell, value = np.zeros(m, np.int32), np.zeros(m, np.float32)
+    tm = np.zeros((m, 28), np.float64) if terms else None
+    dp, u16 = C.POINTER(C.c_double), C.POINTER(C.c_uint16)
+    rc = load().icpk_sdf_pixels(C.byref(params), C.byref(volume), _pose16(pose).ctypes.data_as(dp), img.ctypes.data_as(u16),
+                                rows_s, cols_s, _fp(f), w.ctypes.data_as(u16), int(first), count,
+                                cell.ctypes.data_as(C.POINTER(C.c_int32)), _fp(value),
+                                None if tm is None else tm.ctypes.data_as(dp))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_sdf_pixels")
+    return cell, value, tm, rc
 
 
 class Context:

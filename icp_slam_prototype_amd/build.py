@@ -21,7 +21,8 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_tsdf.cpp", "kernels_tsdf.hip", "icpk_bilateral.cpp", "kernels_bilateral.hip",
            "icpk_pyramid.cpp", "kernels_pyramid.hip", "icpk_projective.cpp", "kernels_projective.hip",
            "kernels_pyramid_color.hip", "icpk_raycast_color.cpp", "kernels_raycast_color.hip",
-           "icpk_fern.cpp", "kernels_fern.hip", "icpk_frame_view.cpp", "kernels_frame_view.hip"]
+           "icpk_fern.cpp", "kernels_fern.hip", "icpk_frame_view.cpp", "kernels_frame_view.hip",
+           "icpk_sdf_track.cpp", "kernels_sdf_track.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -517,6 +518,51 @@ def build_frame_odometry_test(force=False):
     return FRAME_ODOMETRY_TEST
 
 
+SDF_TRACK_TEST = os.path.join(LIBDIR, "test_sdf_track")
+
+
+def build_sdf_track_test(force=False):
+    """Host-only C++ program over icp::TsdfVolume::alignSdf / sdfReduce / sdfAssociate / sdfTrace (icp_tsdf.hpp, K29) (g++,
+    links -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_sdf_track.cpp")
+    hdrs = [os.path.join(HERE, "include", h) for h in ("icp_align.hpp", "icp_tsdf.hpp")]
+    build()
+    newest = max(os.path.getmtime(p) for p in [src, LIB] + hdrs)
+    if not force and os.path.exists(SDF_TRACK_TEST) and os.path.getmtime(SDF_TRACK_TEST) >= newest:
+        return SDF_TRACK_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", SDF_TRACK_TEST])
+    return SDF_TRACK_TEST
+
+
+SDF_TRACK_HOST_SANITIZED = os.path.join(LIBDIR, "sdf_track_host_sanitized")
+
+
+def build_sdf_track_host_sanitized(force=False):
+    """DIAGNOSTIC, not part of build(): tests/cpp/sdf_track_host_main.cpp (its own main, no GPU) with icpk_sdf_track.cpp
+    -- and so csrc/sdf_track_rule.h, projective_rule.h and tsdf_rule.h -- compiled under -fsanitize=address,undefined on
+    the host side; everything else icpk_sdf_track.cpp refers to (the volume's accessor, the launchers its device entry
+    points call) comes from libicpk.so as it is.  The program calls the host-only entry point alone, every array
+    allocated at exactly its size.  Run the program it returns directly."""
+    src = os.path.join(ROOT, "tests", "cpp", "sdf_track_host_main.cpp")
+    build()
+    deps = [src, LIB, os.path.join(CSRC, "icpk_sdf_track.cpp")] + \
+        [os.path.join(CSRC, h) for h in ("sdf_track_rule.h", "projective_rule.h", "tsdf_rule.h")]
+    if not force and os.path.exists(SDF_TRACK_HOST_SANITIZED) and \
+            os.path.getmtime(SDF_TRACK_HOST_SANITIZED) >= max(os.path.getmtime(p) for p in deps):
+        return SDF_TRACK_HOST_SANITIZED
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-omit-frame-pointer", "-g"]
+    objs = []
+    for path, name in ((os.path.join(CSRC, "icpk_sdf_track.cpp"), "icpk_sdf_track_sanitized.o"), (src, "sdf_track_host_main.o")):
+        objs.append(os.path.join(LIBDIR, name))
+        subprocess.check_call([hipcc] + FLAGS + san + ["-x", "hip", "-c", path, "-o", objs[-1]])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-fsanitize=address,undefined"] + objs +
+                          ["-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN", "-o", SDF_TRACK_HOST_SANITIZED])
+    return SDF_TRACK_HOST_SANITIZED
+
+
 PROJECTIVE_HOST_SANITIZED = os.path.join(LIBDIR, "projective_host_sanitized")
 
 
@@ -724,4 +770,5 @@ if __name__ == "__main__":
     print(build_projective_color_test(force="--force" in sys.argv))
     print(build_fern_test(force="--force" in sys.argv))
     print(build_frame_odometry_test(force="--force" in sys.argv))
+    print(build_sdf_track_test(force="--force" in sys.argv))
     print(build_threads_test(force="--force" in sys.argv))

@@ -499,6 +499,18 @@ struct icpk_ctx {
   struct icpk_frame_view_state* fview = nullptr;
   int proj_view_which = ICPK_VIEW_RAYCAST;
   int proj_view_level = 0;
+  // K29 (icpk_sdf_track.cpp), behind everything older for the same reason: the scratch of the SDF tracking calls -- the
+  // tree's partials, the final sums, the loop's state + trace (K25's block type) and where the host reads them, the
+  // per-pixel outputs of icpk_sdf_associate -- and the record of the last icpk_align_sdf.  K25's own stay as they are
+  icpk::DevBuf<double> sdf_partial;  // NP2L x RED_MAX_BLOCKS
+  icpk::DevBuf<int> sdf_pcount;      // RED_MAX_BLOCKS
+  icpk::DevBuf<double> sdf_out;      // NP2L sums, then the count as an int64
+  icpk::PinnedBuf<double> sdf_out_host;
+  icpk::DevBuf<icpk::ProjBlock> sdf_block;
+  icpk::PinnedBuf<icpk::ProjBlock> sdf_block_host;
+  icpk::DevBuf<int32_t> sdf_cell;  // [rows_s cols_s]
+  icpk::DevBuf<float> sdf_value;   // [rows_s cols_s]
+  std::vector<icpk_projective_iter> sdf_trace;
 };
 
 #define ICPK_HIP(ctx, call)                                                                      \
@@ -643,6 +655,14 @@ int tsdf_raycast_view(icpk_ctx* ctx, TsdfRayView* out);
 // K26, after tsdf_raycast_view has succeeded: whether the volume keeps intensities, and the three gradient planes of
 // icpk_tsdf_raycast_color_gradients for the current ray cast (nullptr without them)
 void tsdf_raycast_color_view(icpk_ctx* ctx, bool* color, const float** grad);
+// K29: the volume itself as the SDF tracking calls read it -- the two planes where they lie and the parameters with the
+// CURRENT origin (K23).  ICPK_E_NOT_SET (with the reason in ctx->err) without a volume
+struct TsdfVolumeView {
+  const float* tsdf;
+  const uint16_t* weight;
+  icpk_tsdf_params p;
+};
+int tsdf_volume_view(icpk_ctx* ctx, TsdfVolumeView* out);
 
 // ---- icpk_frame_view.cpp: the view the projective calls read (K28) ----
 // With ICPK_VIEW_RAYCAST exactly tsdf_raycast_view / tsdf_raycast_color_view.  With ICPK_VIEW_FRAME the selected level

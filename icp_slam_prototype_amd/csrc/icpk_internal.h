@@ -1082,4 +1082,21 @@ inline int frame_view_blocks(int npix) { return (npix + FRAME_VIEW_THREADS - 1) 
 // every level in one launch, then totals[2 l], totals[2 l + 1] = level l's two counts (device, 2 x levels ints)
 void launch_frame_view(const FrameViewArgs& a, int* totals, hipStream_t s);
 
+// kernels_sdf_track.hip -- K29, frames tracked directly against the TSDF (the SDF tracking rule is sdf_track_rule.h).
+// The loop's state, trace and step launch are K25's (ProjState, ProjBlock, launch_proj_step), on a block of its own.
+struct SdfArgs {
+  const uint16_t* depth;  // the level
+  int rows, cols;
+  float fx, cx;           // fx / 2^l, cx / 2^l
+  TsdfPlanes vol;         // the volume's planes, dims, voxel, CURRENT origin and min_weight
+  float trunc, max_abs_tsdf, min_normal_cos;
+  double* partial;        // [NP2L][RED_MAX_BLOCKS]
+  int* pcount;            // [RED_MAX_BLOCKS]
+  const ProjState* st;
+};
+// red_blocks(rows cols) workgroups: the per-block partials of one evaluation at the state's pose (nothing once done)
+void launch_sdf_reduce(const SdfArgs& a, hipStream_t s);
+// every pixel's cell or code, and its distance D, at the state's pose (device arrays of rows cols entries)
+void launch_sdf_associate(const SdfArgs& a, int32_t* cell, float* value, hipStream_t s);
+
 }  // namespace icpk

@@ -87,6 +87,14 @@ int icpk::tsdf_raycast_view(icpk_ctx* ctx, TsdfRayView* out) {
   return ICPK_OK;
 }
 
+int icpk::tsdf_volume_view(icpk_ctx* ctx, TsdfVolumeView* out) {
+  const icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  out->tsdf = v->tsdf, out->weight = v->weight;
+  out->p = v->p;
+  return ICPK_OK;
+}
+
 void icpk::tsdf_raycast_color_view(icpk_ctx* ctx, bool* color, const float** grad) {
   const icpk_tsdf_state* v = ctx->tsdf;
   *color = v && (v->p.flags & ICPK_TSDF_COLOR);

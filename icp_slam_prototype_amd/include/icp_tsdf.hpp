@@ -7,7 +7,8 @@
 //                        holds one volume: constructing another replaces it.  raycast gives the surface visible from
 //                        one pose as vertex and normal maps (K20); raycastToTarget makes it the Engine's target.
 //                        alignProjective / projectiveAssociate pair a level of the Engine's depth pyramid with those maps
-//                        pixel by pixel and refine a pose against the model (K25).
+//                        pixel by pixel and refine a pose against the model (K25).  alignSdf / sdfAssociate refine
+//                        it against the distance field itself, with no ray cast (K29).
 //                        extractMesh / getMesh give the surface as a triangle mesh (K21); setPlanes restores a saved
 //                        model.  shift / extractLeaving / getBox let the volume follow the camera (K23): the box
 //                        moves by whole voxels, what is about to leave it is listed first.
@@ -269,6 +270,41 @@ class TsdfVolume {
   std::vector<icpk_projective_iter> projectiveTrace() {
     std::vector<icpk_projective_iter> t(ICPK_PROJECTIVE_MAX_ITERATIONS);
     const int n = icpk_get_projective_trace(eng_.ctx(), t.data(), (int32_t)t.size());
+    t.resize(n > 0 ? (size_t)n : 0);
+    return t;
+  }
+  // K29, the frame aligned directly against the distance field, with no ray cast: the parameters with this volume's
+  // intrinsics as the LEVEL-0 ones (10 iterations, max_abs_tsdf 1, min_weight 1, the normal gate off, min_pairs 6)
+  icpk_sdf_params sdfDefaults(int level = 0) const {
+    icpk_sdf_params p;
+    icpk_default_sdf_params(&p);
+    p.level = level, p.fx = fx_, p.cx = cx_;
+    return p;
+  }
+  // a level of the Engine's resident depth pyramid against the volume's own planes at its current origin, from the
+  // camera-to-world estimate poseIn (16 doubles, row-major) to poseOut; the maps, the lists, the projective trace and
+  // the Engine's clouds are not touched.  Returns ICPK_OK, ICPK_W_TOO_FEW_PAIRS, ICPK_W_DEGENERATE or a negative status
+  int alignSdf(const icpk_sdf_params& p, const double* poseIn, double* poseOut, icpk_projective_result* result = nullptr) {
+    return icpk_align_sdf(eng_.ctx(), &p, poseIn, poseOut, result);
+  }
+  // one evaluation at `pose`: the ICPK_NP2L sums and the accepted pixels
+  int sdfReduce(const icpk_sdf_params& p, const double* pose, double* sums, int64_t* count) {
+    return icpk_sdf_reduce(eng_.ctx(), &p, pose, sums, count);
+  }
+  // per pixel of that level at `pose`: the linear index of the cell it lands in or its ICPK_SDF_* code, and the signed
+  // distance there (0 when rejected); both vectors are sized to the level
+  int sdfAssociate(const icpk_sdf_params& p, const double* pose, std::vector<int32_t>& cell, std::vector<float>& value) {
+    int32_t rows = 0, cols = 0;
+    if (icpk_depth_pyramid_shape(eng_.ctx(), p.level, &rows, &cols) != ICPK_OK)
+      return icpk_sdf_associate(eng_.ctx(), &p, pose, nullptr, nullptr);  // (its own refusal)
+    cell.assign((size_t)rows * cols, 0);
+    value.assign((size_t)rows * cols, 0.f);
+    return icpk_sdf_associate(eng_.ctx(), &p, pose, cell.data(), value.data());
+  }
+  // the iterations the last alignSdf evaluated: E_k, the sums and count at E_k, the status
+  std::vector<icpk_projective_iter> sdfTrace() {
+    std::vector<icpk_projective_iter> t(ICPK_PROJECTIVE_MAX_ITERATIONS);
+    const int n = icpk_get_sdf_trace(eng_.ctx(), t.data(), (int32_t)t.size());
     t.resize(n > 0 ? (size_t)n : 0);
     return t;
   }

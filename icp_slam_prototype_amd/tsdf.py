@@ -244,11 +244,22 @@ class ModelTracker:
     (none when the frame has fewer than min_valid valid ferns) are tried in order, each as both the ray casts' pose and
     the start of the same coarse-to-fine loop, and the first that passes the test becomes the pose; the frame is fused
     and lost is cleared.  track returns the pose either way: callers read self.lost, and self.relocalisations,
-    self.frames_lost, self.keyframes count.  None: every path above, untouched."""
+    self.frames_lost, self.keyframes count.  None: every path above, untouched.
+    sdf: True, or dict(max_abs_tsdf=, min_pairs=, min_normal_cos=) -- the frame is aligned directly against the distance
+    field (K29), with no ray cast at any level: the frame goes into a pyramid of len(pyramid) levels (1 when pyramid is
+    None; smoothed when bilateral is given), and per level, coarse to fine, binding.align_sdf runs pyramid[l] iterations
+    (align_kw's max_iterations when pyramid is None) from the estimate so far, through the tracker's min_weight.  The
+    frame is then fused as before; `follow` works, because the rule reads the volume's current origin.  level_stats
+    holds the ProjectiveResult objects; n_hits and level_hits stay None.  Together with projective, projective_color or
+    relocalise it raises ValueError.  None: every path above, untouched."""
 
     def __init__(self, vol, pose=None, z_near=0.25, z_far=6.0, step=None, min_weight=1, bilateral=None, follow=None,
                  on_leave=None, pyramid=None, pyramid_cutoff=None, projective=None, projective_color=None, relocalise=None,
-                 **align_kw):
+                 sdf=None, **align_kw):
+        if sdf is not None:  # (K29: said before anything the other settings have to say)
+            for name, other in (("projective", projective), ("projective_color", projective_color), ("relocalise", relocalise)):
+                if other is not None:
+                    raise ValueError(f"sdf does not go together with {name}")
         self.vol = vol
         self.pose = np.eye(4) if pose is None else np.array(pose, np.float64).reshape(4, 4)
         self.ray = dict(z_near=z_near, z_far=z_far, step=step, min_weight=min_weight)
@@ -307,6 +318,33 @@ class ModelTracker:
                 raise ValueError(f"relocalise: k in 1 .. {binding.FERN_MAX_K}")
             self.min_overlap = float(self.relocalise.get("min_overlap", RELOCALISE_MIN_OVERLAP))
             self.max_mean_dist = float(self.relocalise.get("max_mean_dist", RELOCALISE_MAX_MEAN_DIST))
+        # K29: None, True or dict(max_abs_tsdf=, min_pairs=, min_normal_cos=)
+        self.sdf = None if sdf is None else ({} if sdf is True else dict(sdf))
+        if self.sdf is not None:
+            unknown = set(self.sdf) - {"max_abs_tsdf", "min_pairs", "min_normal_cos"}
+            if unknown:
+                raise ValueError(f"sdf has no setting {sorted(unknown)}")
+            if "min_pairs" in align_kw:
+                self.sdf.setdefault("min_pairs", align_kw["min_pairs"])
+            self.sdf_counts = self.pyramid if self.pyramid is not None else \
+                (int(align_kw.get("max_iterations", binding.default_sdf_params().max_iterations)),)
+            if self.pyramid_params is None:
+                kw = {} if pyramid_cutoff is None else dict(range_cutoff=int(pyramid_cutoff))
+                self.pyramid_params = depth_front.pyramid_params(levels=1, **kw)
+
+    def _track_sdf(self, depth):
+        """The pose of one frame against the distance field itself, coarse to fine: one build, then per level the device
+        loop over the level and the volume's planes, both where they lie.  No ray cast."""
+        vol, ctx = self.vol, self.vol.ctx
+        shapes = depth_front.build_pyramid(ctx, depth, self.pyramid_params, smooth=self.bilateral)
+        estimate = self.pose
+        self.level_hits, self.level_stats = None, [None] * len(shapes)
+        for l in range(len(shapes) - 1, -1, -1):
+            params = binding.default_sdf_params(**dict(self.sdf, level=l, fx=vol.fx, cx=vol.cx, max_iterations=self.sdf_counts[l],
+                                                       min_weight=self.ray["min_weight"]))
+            estimate, self.level_stats[l] = binding.align_sdf(ctx, estimate, params)
+        self.n_hits, self.stats = None, self.level_stats[0]
+        return estimate
 
     def _track_projective(self, depth, intensity=None):
         """The pose of one frame by projective association, coarse to fine: one build, then per level a ray cast of the
@@ -450,7 +488,9 @@ class ModelTracker:
             raise ValueError("projective_color needs the frame's intensity")
         if self.relocalise is not None:
             return self._track_relocalise(depth, intensity)
-        if self.frames > 0 and self.projective is not None:
+        if self.frames > 0 and self.sdf is not None:
+            self.pose = self._track_sdf(depth)
+        elif self.frames > 0 and self.projective is not None:
             self.pose = self._track_projective(depth, intensity)
         elif self.frames > 0 and self.pyramid is not None:
             self.pose = self._track_pyramid(depth)

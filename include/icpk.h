@@ -2037,6 +2037,101 @@ int icpk_frame_view_pixels(float fx, float cx, int32_t level, const double pose[
                            const float *intensity, int32_t rows, int32_t cols, int64_t first, int32_t count, float *out,
                            int32_t *n_no_normal);
 
+/* ---- K29: depth frames tracked directly against the TSDF, with no ray cast ------------------------------------------
+ * Every tracker above reaches the volume through a ray cast: a march of up to N samples per view pixel, per level, per
+ * frame, and a view that holds only what the last pose could see.  The volume already holds what an alignment needs at
+ * any world point: the signed distance D to the surface, and its gradient, the surface normal there.  Direct alignment
+ * against the distance field (Bylow, Sturm, Kerl, Kahl, Cremers: "Real-time camera tracking and 3D reconstruction using
+ * signed distance functions", RSS 2013) minimises sum_i D(E v_i)^2 over the frame's pixels: no view, no pairs, no
+ * search, sub-voxel residuals from the trilinear interpolant, and everything fused so far takes part.  With
+ * n = grad D / |grad D| and r = D(p) the Gauss-Newton step is K5's point-to-plane step, term for term.
+ *
+ * THE SDF TRACKING RULE.  THE PROJECTIVE RULE's conventions: float32; every operation rounded once, in the order written
+ * (fl(.) is one rounding); no fused multiply-add; correctly rounded / and sqrt; no libm.
+ *   Inputs:
+ *     level l of the resident pyramid, rows_s x cols_s, uint16, seen through fx_s = fx / 2^l, cx_s = cx / 2^l (fx, cx:
+ *       the LEVEL-0 intrinsics of icpk_sdf_params);
+ *     the volume's tsdf and weight planes, its dims, voxel and trunc, and its CURRENT origin (K23: the origin after every
+ *       shift made so far, what icpk_tsdf_get_params returns);
+ *     min_weight; an estimate E, double[16], camera-to-world: its nine R and three t rounded to float once.
+ *   Source pixel i = r cols_s + c; the first failing test decides its code (ICPK_SDF_*, negative):
+ *     1. d == 0: NO_DEPTH.
+ *     2. the vertex v: THE PROJECTIVE RULE's step 2.
+ *     3. the world point p: THE PROJECTIVE RULE's step 3.
+ *     4. THE RAY RULE's SAMPLE cell at p (its rule 5): g_a = fl(fl(fl(p_a - origin_a) / voxel) - 0.5f);
+ *        !(g_a >= 0 && g_a < (float)(dims_a - 1)) on any axis: OUTSIDE (NaN fails; no index is formed before all three
+ *        axes have passed).  c_a = (int)g_a, w_a = fl(g_a - (float)c_a), at = c_x + dims_x (c_y + dims_y c_z).  Any of
+ *        the eight corner weights < min_weight: UNKNOWN.
+ *     5. f = THE RAY RULE's trilinear value over the eight corners e[x + 2 y + 4 z] with the fractions w;
+ *        D = fl(f trunc).  !(fabsf(f) < max_abs_tsdf): TOO_FAR.  The default max_abs_tsdf is 1.0: a fully saturated
+ *        sample, f == +-1 exactly, is rejected and nothing else is.
+ *     6. the gradient of that interpolant inside the cell, from the same eight corners.  With
+ *        lerp(u, v, w) = fl(u + fl(w fl(v - u))); c00, c10, c01, c11 = the four lerps along x the trilinear value forms
+ *        (c_yz = lerp(e[2 y + 4 z], e[1 + 2 y + 4 z], w_x)); b0 = lerp(c00, c10, w_y), b1 = lerp(c01, c11, w_y);
+ *        dx_yz = fl(e[1 + 2 y + 4 z] - e[2 y + 4 z]):
+ *          g_x = lerp(lerp(dx00, dx10, w_y), lerp(dx01, dx11, w_y), w_z),
+ *          g_y = lerp(fl(c10 - c00), fl(c11 - c01), w_z),
+ *          g_z = fl(b1 - b0);
+ *        len = sqrt(fl(fl(fl(g_x g_x) + fl(g_y g_y)) + fl(g_z g_z))); !(len > 0): NO_GRADIENT.  n = g / len: it points
+ *        towards positive distance, towards the cameras, as every model normal here does.
+ *     7. only when min_normal_cos > -1 (default -2: off): THE PROJECTIVE RULE's step 8 with n in place of the view's
+ *        normal -- the cross normal of pixel (r, c), the flip, the 3-term rotation by E's R, the 3-term dot with n;
+ *        NO_NORMAL and NORMAL.
+ *     8. accepted.  The pixel's entry is `at`, the linear index of its cell's lowest corner: >= 0 and < 2^30.  Its
+ *        terms are K5's with p and n widened to double and r = (double)D: J = [p x n ; n], in the ICPK_NP2L layout with
+ *        [27] = (double)fabsf(D).  A rejected pixel adds +0.0.  The sums go through the canonical tree
+ *        (ICPK_RED_THREADS / ICPK_RED_MAX_BLOCKS) over i = 0 .. rows_s cols_s - 1; the count is an exact integer.
+ *   The loop (icpk_align_sdf) is THE PROJECTIVE RULE's loop, word for word: the same count < min_pairs
+ *   (ICPK_W_TOO_FEW_PAIRS), the same ICPK_W_DEGENERATE, the same E_{k+1} = dT E_k in double, exactly max_iterations
+ *   iterations, no threshold test.  The step launch is K25's own.
+ *
+ * icpk_sdf_associate  per source pixel, at `pose`: cell[i] = at or the code, value[i] = D (0 when rejected).  Host arrays
+ *     of rows_s cols_s entries; either may be NULL.
+ * icpk_sdf_reduce     one evaluation at `pose`: the ICPK_NP2L sums and the count.
+ * icpk_align_sdf      the loop; pose_out (double[16], last row 0 0 0 1) is the last estimate.  The result is K25's:
+ *     count and mean_dist (the mean |D|, 0 for no accepted pixel) are those of the LAST EVALUATED iteration.  Returns
+ *     the status.
+ * icpk_get_sdf_trace  the evaluated iterations of the last icpk_align_sdf, as icpk_get_projective_trace's.
+ * icpk_sdf_pixels     host only, no context: rules 1 - 8 for `count` source pixels from pixel `first` over a host level
+ *     (rows_s x cols_s: the level's own shape; params->level only scales fx, cx) and the host planes tsdf, weight of
+ *     `volume` (its dims, voxel, trunc and the origin TO USE; one entry per voxel).  cell / value: count entries; terms
+ *     (or NULL): count x ICPK_NP2L doubles, zeros for a rejected pixel.  Returns the number of accepted pixels.  Compiled
+ *     from the header the kernel includes (csrc/sdf_track_rule.h).
+ * The device calls use scratch and a trace of their own: they leave the ray-cast maps, the surface list, the mesh, the
+ * frame view, the trace of the last icpk_align_projective, and the source, target and associations bit for bit.
+ * ICPK_E_NOT_SET: no volume, or no pyramid.
+ * Refusals (ICPK_E_ARG; a refused call leaves everything as it was): a NULL or non-finite pose; a level the pyramid
+ *     lacks; fx not finite and > 0; a non-finite cx; min_pairs < 1; max_iterations outside
+ *     1 .. ICPK_PROJECTIVE_MAX_ITERATIONS; a NaN min_normal_cos; max_abs_tsdf not in (0, 1] (NaN included); min_weight
+ *     outside 1 .. 65535. */
+#define ICPK_SDF_NO_DEPTH (-1)
+#define ICPK_SDF_OUTSIDE (-2)
+#define ICPK_SDF_UNKNOWN (-3)
+#define ICPK_SDF_TOO_FAR (-4)
+#define ICPK_SDF_NO_GRADIENT (-5)
+#define ICPK_SDF_NO_NORMAL (-6)
+#define ICPK_SDF_NORMAL (-7)
+typedef struct icpk_sdf_params {
+  int32_t level;          /* of the resident pyramid (0) */
+  float fx, cx;           /* LEVEL-0 intrinsics (468.60, 318.27) */
+  int32_t max_iterations; /* 1 .. ICPK_PROJECTIVE_MAX_ITERATIONS (10) */
+  float max_abs_tsdf;     /* in (0, 1]: |f| must stay below it (1.0) */
+  int32_t min_weight;     /* 1 .. 65535 (1) */
+  float min_normal_cos;   /* > -1: the normal gate (-2: off) */
+  int32_t min_pairs;      /* >= 1 (6) */
+} icpk_sdf_params;
+void icpk_default_sdf_params(icpk_sdf_params *p);
+int icpk_sdf_associate(icpk_ctx *ctx, const icpk_sdf_params *params, const double pose[16], int32_t *cell,
+                       float *value);
+int icpk_sdf_reduce(icpk_ctx *ctx, const icpk_sdf_params *params, const double pose[16], double sums[ICPK_NP2L],
+                    int64_t *count);
+int icpk_align_sdf(icpk_ctx *ctx, const icpk_sdf_params *params, const double pose_in[16], double pose_out[16],
+                   icpk_projective_result *result);
+int icpk_get_sdf_trace(icpk_ctx *ctx, icpk_projective_iter *out, int32_t cap);
+int icpk_sdf_pixels(const icpk_sdf_params *params, const icpk_tsdf_params *volume, const double pose[16],
+                    const uint16_t *level, int32_t rows_s, int32_t cols_s, const float *tsdf, const uint16_t *weight,
+                    int64_t first, int32_t count, int32_t *cell, float *value, double *terms);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
