@@ -89,6 +89,7 @@ SYMBOLS = [
     "icpk_tsdf_raycast_pixels",
     "icpk_tsdf_extract_mesh", "icpk_tsdf_get_mesh", "icpk_tsdf_set", "icpk_tsdf_mesh_host",
     "icpk_tsdf_shift", "icpk_tsdf_extract_leaving", "icpk_tsdf_get_params", "icpk_tsdf_get_box",
+    "icpk_tsdf_apply", "icpk_tsdf_deintegrate", "icpk_tsdf_voxel_apply",
     "icpk_default_bilateral_params", "icpk_bilateral_depth_image", "icpk_backproject_smoothed", "icpk_bilateral_tables",
     "icpk_bilateral_host",
     "icpk_default_pyramid_params", "icpk_depth_pyramid_build", "icpk_depth_pyramid_shape", "icpk_depth_pyramid_get",
@@ -203,6 +204,10 @@ class TsdfParams(C.Structure):
     """icpk_tsdf_params"""
     _fields_ = [("dims", C.c_int32 * 3), ("voxel", C.c_float), ("origin", C.c_float * 3), ("trunc", C.c_float),
                 ("max_weight", C.c_int32), ("depth_scale", C.c_float), ("flags", C.c_int32)]
+
+
+class TsdfOp(C.Structure):
+    _fields_ = [("sign", C.c_int32), ("frame", C.c_int32), ("pose", C.c_double * 16)]
 
 
 class TsdfRaycastParams(C.Structure):
@@ -512,6 +517,12 @@ def load():
     lib.icpk_tsdf_extract_leaving.argtypes = [C.c_void_p, C.c_int32, ip, ip, ip]
     lib.icpk_tsdf_get_params.argtypes = [C.c_void_p, C.POINTER(TsdfParams), C.POINTER(C.c_int64)]
     lib.icpk_tsdf_get_box.argtypes = [C.c_void_p, ip, ip, fp, u16, fp]
+    lib.icpk_tsdf_apply.argtypes = [C.c_void_p, C.c_int32, C.POINTER(u16), C.POINTER(fp), C.c_int32, C.c_int32, C.c_float,
+                                    C.c_float, C.c_int32, C.POINTER(TsdfOp), C.POINTER(C.c_int64)]
+    lib.icpk_tsdf_deintegrate.argtypes = lib.icpk_tsdf_integrate.argtypes
+    lib.icpk_tsdf_voxel_apply.argtypes = [C.POINTER(TsdfParams), C.c_int32, C.POINTER(u16), C.POINTER(fp), C.c_int32,
+                                          C.c_int32, C.c_float, C.c_float, C.c_int32, C.POINTER(TsdfOp), C.c_int64,
+                                          C.c_int32, fp, u16, fp, C.POINTER(C.c_int64)]
     bp = C.POINTER(BilateralParams)
     lib.icpk_default_bilateral_params.argtypes = [bp]
     lib.icpk_default_bilateral_params.restype = None
@@ -1070,6 +1081,83 @@ def tsdf_get_box(ctx, lo, hi, tsdf=True, weight=True, intensity=False):
                                         None if w is None else w.ctypes.data_as(C.POINTER(C.c_uint16)),
                                         None if c is None else _fp(c)))
     return f, w, c
+
+
+# -- signed updates of the volume (K30): functions over a Context, like the moving volume's above ---------------------
+TSDF_MAX_OPS = 16
+
+
+def tsdf_ops(ops):
+    """A list of (sign, frame, pose (4, 4) float64) as a TsdfOp array."""
+    arr = (TsdfOp * max(len(ops), 1))()
+    for k, (sign, frame, pose) in enumerate(ops):
+        arr[k].sign, arr[k].frame = int(sign), int(frame)
+        arr[k].pose[:] = np.ascontiguousarray(pose, np.float64).reshape(16).tolist()
+    return arr
+
+
+def _tsdf_frames(frames, intensities):
+    """The images of an op-list call as ctypes pointer tables (and the arrays that keep them alive)."""
+    d = [np.ascontiguousarray(f, np.uint16) for f in frames]
+    if not d or d[0].ndim != 2 or any(f.shape != d[0].shape for f in d):
+        raise ValueError("frames: at least one (rows, cols) depth image, all of one shape")
+    u16 = C.POINTER(C.c_uint16)
+    dt = (u16 * len(d))(*[f.ctypes.data_as(u16) for f in d])
+    img, it = None, None
+    if intensities is not None:
+        img = [_f(i).reshape(-1) for i in intensities]
+        if len(img) != len(d) or any(i.size != d[0].size for i in img):
+            raise ValueError("one intensity image per frame, one intensity per pixel expected")
+        it = (C.POINTER(C.c_float) * len(img))(*[_fp(i) for i in img])
+    return d, img, dt, it
+
+
+def tsdf_apply(ctx, frames, ops, intensities=None, fx=468.60, cx=318.27):
+    """icpk_tsdf_apply: the signed ops -- a list of (sign, frame, pose): +1 integrates, -1 de-integrates frames[frame]
+    at pose -- applied to the context's volume in order, in one pass over it.  frames: (rows, cols) uint16 images of
+    one shape; intensities: as many float32 images on a TSDF_COLOR volume.  Returns the voxels every op wrote
+    (n_ops,) int64."""
+    d, img, dt, it = _tsdf_frames(frames, intensities)
+    n = np.zeros(max(len(ops), 1), np.int64)
+    ctx._chk(ctx._lib.icpk_tsdf_apply(ctx._h, len(d), dt, it, d[0].shape[0], d[0].shape[1], fx, cx, len(ops), tsdf_ops(ops),
+                                      n.ctypes.data_as(C.POINTER(C.c_int64))))
+    return n[:len(ops)]
+
+
+def tsdf_deintegrate(ctx, depth, pose, intensity=None, fx=468.60, cx=318.27):
+    """icpk_tsdf_deintegrate: one frame taken out of the volume again -- the inverse of Context.tsdf_integrate with the
+    same arguments, up to rounding (exact on voxels the frame alone had written).  Returns the voxels written."""
+    d = np.ascontiguousarray(depth, np.uint16)
+    rows, cols = d.shape
+    P = np.ascontiguousarray(pose, np.float64).reshape(16)
+    img = None if intensity is None else _f(intensity).reshape(-1)
+    if img is not None and img.size != rows * cols:
+        raise ValueError("one intensity per pixel expected")
+    n = C.c_int32(-1)
+    ctx._chk(ctx._lib.icpk_tsdf_deintegrate(ctx._h, d.ctypes.data_as(C.POINTER(C.c_uint16)), None if img is None else _fp(img),
+                                            rows, cols, fx, cx, P.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+    return n.value
+
+
+def tsdf_voxel_apply(params, frames, ops, tsdf, weight, intensities=None, intensity_value=None, fx=468.60, cx=318.27,
+                     first=0, count=None):
+    """icpk_tsdf_voxel_apply (host only): the signed update rule for `count` voxels from linear index `first` (default:
+    all that tsdf holds); tsdf float32, weight uint16 and intensity_value float32 arrays of count entries are updated in
+    place.  Returns the voxels every op wrote among them (n_ops,) int64."""
+    d, img, dt, it = _tsdf_frames(frames, intensities)
+    for a, t in ((tsdf, np.float32), (weight, np.uint16), (intensity_value, np.float32)):
+        if a is not None and (a.dtype != t or not a.flags.c_contiguous):
+            raise ValueError("the voxel state arrays must be contiguous float32 / uint16 / float32")
+    count = tsdf.size if count is None else int(count)
+    n = np.zeros(max(len(ops), 1), np.int64)
+    rc = load().icpk_tsdf_voxel_apply(C.byref(params), len(d), dt, it, d[0].shape[0], d[0].shape[1], fx, cx, len(ops),
+                                      tsdf_ops(ops), int(first), count, _fp(tsdf),
+                                      weight.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                      None if intensity_value is None else _fp(intensity_value),
+                                      n.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc < 0:
+        raise IcpkError(rc, "icpk_tsdf_voxel_apply")
+    return n[:len(ops)]
 
 
 # ---- projective frame-to-model alignment (K25): functions of a context, like the moving volume's above ----------------

@@ -22,7 +22,7 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_pyramid.cpp", "kernels_pyramid.hip", "icpk_projective.cpp", "kernels_projective.hip",
            "kernels_pyramid_color.hip", "icpk_raycast_color.cpp", "kernels_raycast_color.hip",
            "icpk_fern.cpp", "kernels_fern.hip", "icpk_frame_view.cpp", "kernels_frame_view.hip",
-           "icpk_sdf_track.cpp", "kernels_sdf_track.hip"]
+           "icpk_sdf_track.cpp", "kernels_sdf_track.hip", "icpk_tsdf_apply.cpp", "kernels_tsdf_apply.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -351,6 +351,24 @@ def build_tsdf_shift_test(force=False):
     return TSDF_SHIFT_TEST
 
 
+TSDF_REFUSE_TEST = os.path.join(LIBDIR, "test_tsdf_refuse")
+
+
+def build_tsdf_refuse_test(force=False):
+    """Host-only C++ program over icp::TsdfVolume::deintegrate / apply / refuse (icp_tsdf.hpp, K30) (g++, links
+    -licpk)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_tsdf_refuse.cpp")
+    hdrs = [os.path.join(HERE, "include", h) for h in ("icp_align.hpp", "icp_tsdf.hpp")]
+    build()
+    newest = max(os.path.getmtime(p) for p in [src, LIB] + hdrs)
+    if not force and os.path.exists(TSDF_REFUSE_TEST) and os.path.getmtime(TSDF_REFUSE_TEST) >= newest:
+        return TSDF_REFUSE_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "include"), "-I",
+                           os.path.join(HERE, "include"), src, "-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN",
+                           "-Wl,-rpath-link,/opt/rocm/lib", "-o", TSDF_REFUSE_TEST])
+    return TSDF_REFUSE_TEST
+
+
 TSDF_MESH_HOST_SANITIZED = os.path.join(LIBDIR, "tsdf_mesh_host_sanitized")
 
 
@@ -392,6 +410,30 @@ def build_tsdf_shift_host_sanitized(force=False):
                            "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", CSRC, src, "-o",
                            TSDF_SHIFT_HOST_SANITIZED])
     return TSDF_SHIFT_HOST_SANITIZED
+
+
+TSDF_APPLY_HOST_SANITIZED = os.path.join(LIBDIR, "tsdf_apply_host_sanitized")
+
+
+def build_tsdf_apply_host_sanitized(force=False):
+    """DIAGNOSTIC, not part of build(): tests/cpp/tsdf_apply_host_main.cpp (its own main, no GPU) with icpk_tsdf_apply.cpp
+    -- the op-list validation, icpk_tsdf_voxel_apply and so the signed update rule of csrc/tsdf_rule.h -- compiled under
+    -fsanitize=address,undefined on the host side; everything else icpk_tsdf_apply.cpp refers to comes from libicpk.so as
+    it is.  Run the program it returns directly."""
+    src = os.path.join(ROOT, "tests", "cpp", "tsdf_apply_host_main.cpp")
+    build()
+    newest = max(os.path.getmtime(p) for p in (src, LIB))
+    if not force and os.path.exists(TSDF_APPLY_HOST_SANITIZED) and os.path.getmtime(TSDF_APPLY_HOST_SANITIZED) >= newest:
+        return TSDF_APPLY_HOST_SANITIZED
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-omit-frame-pointer", "-g"]
+    objs = []
+    for path, name in ((os.path.join(CSRC, "icpk_tsdf_apply.cpp"), "icpk_tsdf_apply_sanitized.o"), (src, "tsdf_apply_host_main.o")):
+        objs.append(os.path.join(LIBDIR, name))
+        subprocess.check_call([hipcc] + FLAGS + san + ["-x", "hip", "-c", path, "-o", objs[-1]])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-fsanitize=address,undefined"] + objs +
+                          ["-L", LIBDIR, "-licpk", "-Wl,-rpath,$ORIGIN", "-o", TSDF_APPLY_HOST_SANITIZED])
+    return TSDF_APPLY_HOST_SANITIZED
 
 
 BILATERAL_TEST = os.path.join(LIBDIR, "test_bilateral")
@@ -764,6 +806,7 @@ if __name__ == "__main__":
     print(build_tsdf_raycast_test(force="--force" in sys.argv))
     print(build_tsdf_mesh_test(force="--force" in sys.argv))
     print(build_tsdf_shift_test(force="--force" in sys.argv))
+    print(build_tsdf_refuse_test(force="--force" in sys.argv))
     print(build_bilateral_test(force="--force" in sys.argv))
     print(build_pyramid_test(force="--force" in sys.argv))
     print(build_projective_test(force="--force" in sys.argv))

@@ -663,6 +663,30 @@ struct TsdfVolumeView {
   icpk_tsdf_params p;
 };
 int tsdf_volume_view(icpk_ctx* ctx, TsdfVolumeView* out);
+// K30: what icpk_tsdf_apply (icpk_tsdf_apply.cpp) keeps with the volume -- the device stack of a call's frames, reused
+// while the shape fits, and the per-chunk, per-op counts with their totals -- and the volume as that call writes it
+struct TsdfApplyBufs {
+  DevBuf<uint16_t> depth;    // n_frames x rows x cols
+  DevBuf<float> intensity;   // the same, on a colour volume
+  DevBuf<int> slots;         // TSDF_MAX_BLOCKS x TSDF_MAX_OPS
+  DevBuf<long long> totals;  // TSDF_MAX_OPS
+  PinnedBuf<long long> totals_host;
+};
+struct TsdfApplyView {
+  float* tsdf;
+  uint16_t* weight;
+  float* intensity;  // null without ICPK_TSDF_COLOR
+  long long n;
+  icpk_tsdf_params p;  // with the CURRENT origin
+  TsdfApplyBufs* bufs;
+};
+int tsdf_apply_view(icpk_ctx* ctx, TsdfApplyView* out);
+// the refusals of icpk_tsdf_create and of icpk_tsdf_integrate's camera (nullptr: fine; else what is wrong), its range
+// test of the intensities, and the frame the per-voxel rule reads
+const char* tsdf_check_volume(const icpk_tsdf_params& p);
+const char* tsdf_check_camera(int32_t rows, int32_t cols, float fx, float cx);
+bool tsdf_intensities_ok(const float* v, size_t n);
+TsdfFrame tsdf_make_frame(const icpk_tsdf_params& p, const float R[9], const float t[3], int rows, int cols, float fx, float cx);
 
 // ---- icpk_frame_view.cpp: the view the projective calls read (K28) ----
 // With ICPK_VIEW_RAYCAST exactly tsdf_raycast_view / tsdf_raycast_color_view.  With ICPK_VIEW_FRAME the selected level

@@ -1011,6 +1011,30 @@ void launch_tsdf_mesh_count(const TsdfMeshArgs& a, int nblocks, long long* total
 // the vertices, then the triangles
 void launch_tsdf_mesh_scatter(const TsdfMeshArgs& a, int nblocks, hipStream_t s);
 
+// kernels_tsdf_apply.hip -- K30, several signed frame updates in one pass over the volume (the signed update rule of
+// tsdf_rule.h), over K19's chunks
+constexpr int TSDF_MAX_OPS = 16;  // ICPK_TSDF_MAX_OPS
+struct TsdfApplyOp {
+  float R[9], t[3];  // world -> camera, as TsdfFrame's
+  int sign;          // +1 or -1
+  int frame;         // which image of the stack: < n_frames
+};
+struct TsdfApplyArgs {
+  TsdfFrame fr;                  // the geometry and the camera; its R and t are taken from the op
+  const uint16_t* depth;         // the stack: n_frames x rows x cols
+  const float* intensity_image;  // the same, or null ...
+  float* tsdf;
+  uint16_t* weight;
+  float* intensity;              // ... as the volume's intensity plane is
+  long long n, chunk;
+  long long npix;                // rows x cols: one image of the stack
+  int n_ops;
+  int* slots;                    // [nblocks][TSDF_MAX_OPS] voxels written per chunk and op
+  TsdfApplyOp ops[TSDF_MAX_OPS];
+};
+// the ops in order, voxel by voxel; n_updated[k] (device, n_ops entries) = the voxels op k wrote
+void launch_tsdf_apply(const TsdfApplyArgs& a, int nblocks, long long* n_updated, hipStream_t s);
+
 // kernels_projective.hip -- K25, projective frame-to-model alignment (the projective rule is projective_rule.h)
 constexpr int PROJ_MAX_ITER = 64;  // ICPK_PROJECTIVE_MAX_ITERATIONS
 // The loop's state on the device: the reduce launch reads `done` and the float pose, the step launch behind it writes

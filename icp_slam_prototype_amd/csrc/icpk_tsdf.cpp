@@ -67,6 +67,8 @@ struct icpk_tsdf_state {
   bool have_mesh = false;
   int mesh_nv = 0, mesh_nt = 0, mesh_nn = 0;
   float* mesh_plane(int k) const { return mesh + (size_t)k * mesh_vcap; }
+  // K30: the frame stack and the counts of icpk_tsdf_apply (icpk_tsdf_apply.cpp), allocated by its first call
+  TsdfApplyBufs apply;
   // the volume's intensity plane; null for a volume without ICPK_TSDF_COLOR
   float* intensity_plane() const { return (p.flags & ICPK_TSDF_COLOR) ? intensity.get() : nullptr; }
 };
@@ -92,6 +94,16 @@ int icpk::tsdf_volume_view(icpk_ctx* ctx, TsdfVolumeView* out) {
   if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
   out->tsdf = v->tsdf, out->weight = v->weight;
   out->p = v->p;
+  return ICPK_OK;
+}
+
+int icpk::tsdf_apply_view(icpk_ctx* ctx, TsdfApplyView* out) {
+  icpk_tsdf_state* v = ctx->tsdf;
+  if (!v) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
+  out->tsdf = v->tsdf, out->weight = v->weight, out->intensity = v->intensity_plane();
+  out->n = v->n;
+  out->p = v->p;
+  out->bufs = &v->apply;
   return ICPK_OK;
 }
 
@@ -231,6 +243,14 @@ bool intensities_ok(const float* v, size_t n) {
 }
 
 }  // namespace
+
+// K30: the refusals and the frame above, for icpk_tsdf_apply.cpp
+const char* icpk::tsdf_check_volume(const icpk_tsdf_params& p) { return check_params(p); }
+const char* icpk::tsdf_check_camera(int32_t rows, int32_t cols, float fx, float cx) { return check_camera(rows, cols, fx, cx); }
+bool icpk::tsdf_intensities_ok(const float* v, size_t n) { return intensities_ok(v, n); }
+TsdfFrame icpk::tsdf_make_frame(const icpk_tsdf_params& p, const float R[9], const float t[3], int rows, int cols, float fx, float cx) {
+  return make_frame(p, R, t, rows, cols, fx, cx);
+}
 
 extern "C" {
 

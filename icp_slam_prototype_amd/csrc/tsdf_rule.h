@@ -1,5 +1,5 @@
-// tsdf_rule.h -- the per-voxel rule, the surface rule (K19), the ray rule (K20) and the mesh rule (K21) of the TSDF
-// volume; include/icpk.h writes all four out.
+// tsdf_rule.h -- the per-voxel rule, the surface rule (K19), the ray rule (K20), the mesh rule (K21) and the signed
+// update rule (K30, kernels_tsdf_apply.hip and icpk_tsdf_voxel_apply) of the TSDF volume; include/icpk.h writes them out.
 // Header-inline and __host__ __device__: kernels_tsdf.hip runs it per voxel on the device, icpk_tsdf.cpp exports it
 // for one voxel, for one pixel and for a whole mesh on the host (icpk_tsdf_voxel_update, icpk_tsdf_raycast_pixels,
 // icpk_tsdf_mesh_host), compiled with -ffp-contract=off on both sides.  float32 only, +, -, *, / and sqrt in the order
@@ -76,6 +76,39 @@ ICPK_HD bool tsdf_voxel_update(const TsdfFrame& fr, int i, int j, int k, const u
   *tsdf = tsdf_blend(*tsdf, w, f);
   if (intensity && intensity_image) *intensity = tsdf_blend(*intensity, w, intensity_image[pix]);
   *weight = (uint16_t)(w + 1 < fr.max_weight ? w + 1 : fr.max_weight);
+  return true;
+}
+
+// ---- the signed update rule (K30) ----
+// the inverse of tsdf_blend: the running mean of w >= 2 samples gives `sample` back, clamped to [lo, 1] (the mean of
+// the samples that stay lies there; the rounding of the three operations may not)
+ICPK_HD float tsdf_unblend(float value, int w, float sample, float lo) {
+  const float r = (value * (float)w - sample) / ((float)w - 1.f);
+  return r < lo ? lo : r > 1.f ? 1.f : r;
+}
+
+// One op on a voxel's state, after rules 1 - 7 have produced the sample f (and the pixel's intensity c).  color: whether
+// the volume keeps intensities; *intensity is read and written only then (it points somewhere either way).  sign +1:
+// rules 8 - 10 as they are.  sign -1: w == 0 leaves the voxel alone, w == 1 gives the fresh state back, else the
+// inverse of the blend and w - 1.  Returns whether the voxel was written.
+ICPK_HD bool tsdf_state_apply(int sign, int max_weight, float f, float c, bool color, float* tsdf, int* weight, float* intensity) {
+  const int w = *weight;
+  if (sign > 0) {
+    *tsdf = tsdf_blend(*tsdf, w, f);
+    if (color) *intensity = tsdf_blend(*intensity, w, c);
+    *weight = w + 1 < max_weight ? w + 1 : max_weight;
+    return true;
+  }
+  if (w == 0) return false;
+  if (w == 1) {
+    *tsdf = 0.f;
+    if (color) *intensity = 0.f;
+    *weight = 0;
+    return true;
+  }
+  *tsdf = tsdf_unblend(*tsdf, w, f, -1.f);
+  if (color) *intensity = tsdf_unblend(*intensity, w, c, 0.f);
+  *weight = w - 1;
   return true;
 }
 

@@ -16,6 +16,7 @@
 //                        coarse pyramid level is encoded, looked up and harvested on the GPU (process); a tracker
 //                        that has lost the camera restarts from the nearest keyframes' poses (TsdfVolume::relocalise).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -151,6 +152,49 @@ class TsdfVolume {
     if (poses.size() != 16 * depths.size()) return ICPK_E_ARG;
     for (size_t k = 0; k < depths.size(); ++k)
       if (int rc = integrate(depths[k], rows, cols, poses.data() + 16 * k)) return rc;
+    return ICPK_OK;
+  }
+  // K30 -- the inverse of integrate: the frame taken out again at the pose it was fused at (exact on voxels the frame
+  // alone had written, up to rounding elsewhere, no inverse on voxels that reached max_weight)
+  int deintegrate(const uint16_t* depth, int rows, int cols, const double* pose, const float* intensity = nullptr,
+                  int32_t* nUpdated = nullptr) {
+    return icpk_tsdf_deintegrate(eng_.ctx(), depth, intensity, rows, cols, fx_, cx_, pose, nUpdated);
+  }
+  // signed updates in one pass over the volume: op k integrates (sign +1) or de-integrates (-1) depths[ops[k].frame] at
+  // ops[k].pose; at most ICPK_TSDF_MAX_OPS ops over at most as many frames.  intensities: one image per frame on a
+  // colour volume, else empty.  nUpdated (optional): the voxels every op wrote
+  int apply(const std::vector<const uint16_t*>& depths, int rows, int cols, const std::vector<icpk_tsdf_op>& ops,
+            const std::vector<const float*>& intensities = {}, std::vector<int64_t>* nUpdated = nullptr) {
+    if (!intensities.empty() && intensities.size() != depths.size()) return ICPK_E_ARG;
+    if (nUpdated) nUpdated->assign(ops.size(), 0);
+    return icpk_tsdf_apply(eng_.ctx(), (int32_t)depths.size(), depths.data(), intensities.empty() ? nullptr : intensities.data(),
+                           rows, cols, fx_, cx_, (int32_t)ops.size(), ops.data(), nUpdated ? nUpdated->data() : nullptr);
+  }
+  // frames fused at oldPoses moved to newPoses (16 doubles each, e.g. PoseGraph::poses() after a loop closure): each is
+  // taken out at its old pose and put in at its new one, ICPK_TSDF_MAX_OPS / 2 frames per pass over the volume, every
+  // frame uploaded once.  nUpdated (optional): per frame the voxels removed, then the voxels added
+  int refuse(const std::vector<const uint16_t*>& depths, int rows, int cols, const std::vector<double>& oldPoses,
+             const std::vector<double>& newPoses, const std::vector<const float*>& intensities = {},
+             std::vector<int64_t>* nUpdated = nullptr) {
+    const size_t n = depths.size(), batch = ICPK_TSDF_MAX_OPS / 2;
+    if (oldPoses.size() != 16 * n || newPoses.size() != 16 * n || (!intensities.empty() && intensities.size() != n)) return ICPK_E_ARG;
+    if (nUpdated) nUpdated->assign(2 * n, 0);
+    for (size_t lo = 0; lo < n; lo += batch) {
+      const size_t m = std::min(batch, n - lo);
+      std::vector<icpk_tsdf_op> ops(2 * m);
+      for (size_t k = 0; k < m; ++k) {
+        ops[k].sign = -1, ops[m + k].sign = +1;
+        ops[k].frame = ops[m + k].frame = (int32_t)k;
+        std::copy_n(oldPoses.data() + 16 * (lo + k), 16, ops[k].pose);
+        std::copy_n(newPoses.data() + 16 * (lo + k), 16, ops[m + k].pose);
+      }
+      const std::vector<const uint16_t*> d(depths.begin() + lo, depths.begin() + lo + m);
+      std::vector<const float*> c;
+      if (!intensities.empty()) c.assign(intensities.begin() + lo, intensities.begin() + lo + m);
+      std::vector<int64_t> wrote;
+      if (int rc = apply(d, rows, cols, ops, c, &wrote)) return rc;
+      for (size_t k = 0; k < m && nUpdated; ++k) (*nUpdated)[2 * (lo + k)] = wrote[k], (*nUpdated)[2 * (lo + k) + 1] = wrote[m + k];
+    }
     return ICPK_OK;
   }
   // the zero crossings between voxels of weight >= minWeight; the list also stays on the device for toTarget()

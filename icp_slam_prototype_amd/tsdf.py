@@ -85,6 +85,41 @@ class TsdfVolume:
         return [self.integrate(d, poses[k], None if intensities is None else intensities[k])
                 for k, d in enumerate(depths)]
 
+    def deintegrate(self, depth, pose, intensity=None):
+        """The inverse of integrate (K30): the frame taken out again at the pose it was fused at.  Exact on voxels the
+        frame alone had written, up to rounding elsewhere, and no inverse on voxels that reached max_weight.  Returns
+        the number of voxels written."""
+        n = binding.tsdf_deintegrate(self.ctx, depth, pose, intensity, fx=self.fx, cx=self.cx)
+        self.frames = max(self.frames - 1, 0)  # (a count of calls, not of content: it never goes below 0)
+        return n
+
+    def apply(self, frames, ops, intensities=None):
+        """Signed updates in one pass over the volume (K30): ops is a list of (sign, frame, pose) -- +1 integrates and -1
+        de-integrates frames[frame] at pose --, at most binding.TSDF_MAX_OPS of them over at most as many frames.  Returns
+        the voxels every op wrote."""
+        n = binding.tsdf_apply(self.ctx, frames, ops, intensities, fx=self.fx, cx=self.cx)
+        self.shape = tuple(np.shape(frames[0]))
+        self.frames = max(self.frames + sum(int(op[0]) for op in ops), 0)  # (calls, as in deintegrate)
+        return n
+
+    REFUSE_BATCH = 8  # frames per call of refuse: two ops each, binding.TSDF_MAX_OPS in all
+
+    def refuse(self, depths, old_poses, new_poses, intensities=None):
+        """Frames fused at old_poses moved to new_poses (e.g. PoseGraph.poses() after a loop closure): each is taken out
+        at its old pose and put in at its new one, REFUSE_BATCH frames per pass over the volume, every frame uploaded
+        once.  Returns the voxels written, (n, 2) int64: removed, added."""
+        old = np.asarray(old_poses, np.float64).reshape(-1, 4, 4)
+        new = np.asarray(new_poses, np.float64).reshape(-1, 4, 4)
+        if not (len(depths) == old.shape[0] == new.shape[0]) or (intensities is not None and len(intensities) != len(depths)):
+            raise ValueError("an old pose, a new pose (and an intensity image) per depth frame")
+        out = np.zeros((len(depths), 2), np.int64)
+        for lo in range(0, len(depths), self.REFUSE_BATCH):
+            hi = min(lo + self.REFUSE_BATCH, len(depths))
+            ops = [(-1, k - lo, old[k]) for k in range(lo, hi)] + [(+1, k - lo, new[k]) for k in range(lo, hi)]
+            n = self.apply(depths[lo:hi], ops, None if intensities is None else intensities[lo:hi])
+            out[lo:hi, 0], out[lo:hi, 1] = n[:hi - lo], n[hi - lo:]
+        return out
+
     def surface(self, min_weight=1):
         """The zero crossings between voxels of weight >= min_weight: dict(points (3, n), normals (3, n), intensity,
         voxel, axis), ordered by voxel then axis."""

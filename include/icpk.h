@@ -1531,6 +1531,62 @@ int icpk_tsdf_get_params(icpk_ctx *ctx, icpk_tsdf_params *out, int64_t total[3])
 int icpk_tsdf_get_box(icpk_ctx *ctx, const int32_t lo[3], const int32_t hi[3], float *tsdf, uint16_t *weight,
                       float *intensity);
 
+/* ---- K30: signed updates of the volume -- de-integration, and several frames in one pass ---------------------------
+ * What a pose graph's corrections (K18) are for: a frame fused at a drifted pose is taken out again and fused at the
+ * corrected one, without resetting the volume.
+ *
+ * THE SIGNED UPDATE RULE (icpk_tsdf_apply; float32, one rounding per operation in the order written, no fused
+ * multiply-add, correctly rounded division, no libm, like THE PER-VOXEL RULE).  A call carries n_frames images and
+ * n_ops ops; an op is a sign, the index of one of the call's images and a pose.  Every voxel takes the ops
+ * 0 .. n_ops - 1 in the order listed, each on the state the op before it left:
+ *   - steps 1 - 7 of THE PER-VOXEL RULE with the op's pose (inverted by icpk_tsdf_invert_pose) and the op's image,
+ *     unchanged: they produce the sample f (and the pixel's intensity) or leave the voxel alone;
+ *   - sign == +1: steps 8 - 10 as they are;
+ *   - sign == -1, on the voxel's weight w:
+ *       w == 0     the voxel is left alone and not counted;
+ *       w == 1     tsdf <- +0.0f, intensity <- +0.0f, w <- 0: the bytes of the fresh state;
+ *       otherwise  tsdf <- clamp(fl(fl(fl(tsdf * (float)w) - f) / fl((float)w - 1)), -1, 1), with ICPK_TSDF_COLOR the
+ *                  intensity the same way with the pixel's intensity, clamped to [0, 1], and w <- w - 1.
+ *   - n_updated[k] = the number of voxels op k wrote.
+ * One call with n ops gives, by construction, the bytes of n calls with one op each in that order, and a single +1 op
+ * gives icpk_tsdf_integrate's bytes.  On a fresh voxel +A then -A gives the fresh bytes back.  Otherwise a removal is
+ * the inverse of the integration up to rounding: a few ulp of 1 per op, amplified by w / (w - 1).  A voxel whose weight
+ * has reached max_weight has forgotten how many frames it holds: the rule still applies there (w <- max_weight - 1) and
+ * is NOT an inverse.
+ *
+ * icpk_tsdf_apply   depth: n_frames pointers to rows x cols host uint16 images; intensity: n_frames pointers to
+ *     rows x cols host floats in [0, 1] on a volume with ICPK_TSDF_COLOR, NULL on one without.  The images go into one
+ *     device stack the volume owns (reused while the shape fits), so that "remove at the old pose, add at the new one"
+ *     uploads its frame once; the volume is then crossed once for all ops.  ICPK_E_ARG for n_ops outside
+ *     1 .. ICPK_TSDF_MAX_OPS, n_frames outside 1 .. n_ops, a sign other than +1 and -1, a frame index outside
+ *     0 .. n_frames - 1, a NULL image (the resident frame of icpk_backproject_pair is not taken here), a NULL ops, and
+ *     everything icpk_tsdf_integrate refuses; ICPK_E_NOT_SET without a volume.  A refused call leaves the volume's bytes
+ *     as they were.  n_updated: n_ops entries, or NULL.  The call waits for the device.  It uses the volume's CURRENT
+ *     origin (K23) and, like integration, touches nothing else the context holds: the surface list, the ray-cast maps,
+ *     the mesh, the pyramid and the frame view stay as they are (snapshots of the volume before the call).
+ * icpk_tsdf_deintegrate   icpk_tsdf_integrate's signature (depth must not be NULL): one op with sign -1.
+ * icpk_tsdf_voxel_apply   host only, no context: the rule for the `count` voxels from linear index `first`, given the
+ *     images, the ops and the voxels' state (tsdf, weight, intensity_value: arrays of `count` entries, in and out;
+ *     intensity and intensity_value both NULL without colour).  Compiled from the header the kernel includes
+ *     (csrc/tsdf_rule.h).  n_updated: n_ops entries (or NULL), set to the counts over these voxels.  Returns ICPK_OK, or
+ *     ICPK_E_ARG for what icpk_tsdf_create and icpk_tsdf_apply refuse, a NULL state array, first < 0, count < 0 or a
+ *     range past the volume. */
+#define ICPK_TSDF_MAX_OPS 16
+typedef struct icpk_tsdf_op {
+  int32_t sign;    /* +1 integrate, -1 de-integrate */
+  int32_t frame;   /* index into the call's frames */
+  double pose[16]; /* camera-to-world, row-major, as icpk_tsdf_integrate's */
+} icpk_tsdf_op;
+int icpk_tsdf_apply(icpk_ctx *ctx, int32_t n_frames, const uint16_t *const *depth, const float *const *intensity,
+                    int32_t rows, int32_t cols, float fx, float cx, int32_t n_ops, const icpk_tsdf_op *ops,
+                    int64_t *n_updated);
+int icpk_tsdf_deintegrate(icpk_ctx *ctx, const uint16_t *depth, const float *intensity, int32_t rows, int32_t cols,
+                          float fx, float cx, const double pose[16], int32_t *n_updated);
+int icpk_tsdf_voxel_apply(const icpk_tsdf_params *params, int32_t n_frames, const uint16_t *const *depth,
+                          const float *const *intensity, int32_t rows, int32_t cols, float fx, float cx, int32_t n_ops,
+                          const icpk_tsdf_op *ops, int64_t first, int32_t count, float *tsdf, uint16_t *weight,
+                          float *intensity_value, int64_t *n_updated);
+
 /* ---- K22: smoothing a depth frame before its vertex and normal maps are made -----------------------------------------
  * KinectFusion's first stage: a bilateral filter in front of the cloud (and the cross-product normals) that tracking
  * reads, while the RAW frame is what goes into the volume.  K6 (icpk_filter_depth_image) repairs holes and leaves noise
