@@ -1,4 +1,4 @@
-// tests/cpp/bilateral_host_main.cpp -- DIAGNOSTIC (build.build_bilateral_host_sanitized): icpk_bilateral_tables and
+// tests/cpp/bilateral_host_main.cpp -- DIAGNOSTIC (build.program("bilateral_host_sanitized")): icpk_bilateral_tables and
 // icpk_bilateral_host over the shapes of the host cases, in a program of its own so that the host code can run under
 // -fsanitize=address,undefined without anything being loaded into an interpreter.  No GPU.  The arrays are exactly as
 // large as the header says they must be, so a read or write past them is caught; the rule's invariants are checked on

@@ -1,6 +1,6 @@
 // tests/cpp/fern_host_main.cpp -- the host half of K27 (icpk_fern_table, icpk_fern_encode_host,
 // icpk_fern_dissimilarity_host: csrc/icpk_fern.cpp through csrc/fern_rule.h) as a stand-alone program with its own main
-// and no GPU, for build.build_fern_host_sanitized(): compiled under -fsanitize=address,undefined, every array allocated
+// and no GPU, for build.program("fern_host_sanitized"): compiled under -fsanitize=address,undefined, every array allocated
 // at exactly the size include/icpk.h asks for, so that one word read or written past an end is reported.  The values
 // are checked against the rule restated here from the table (the bytes are the business of tests/test_fern_host.py).
 #include <cstdio>

@@ -1,4 +1,4 @@
-// tests/cpp/projective_color_host_main.cpp -- DIAGNOSTIC (build.build_projective_color_host_sanitized): the three
+// tests/cpp/projective_color_host_main.cpp -- DIAGNOSTIC (build.program("projective_color_host_sanitized")): the three
 // host-only functions of K26 -- icpk_intensity_pyramid_host, icpk_raycast_color_gradients_host and
 // icpk_projective_pixels_colored -- in a program of its own, so that the host code (icpk_pyramid.cpp,
 // icpk_raycast_color.cpp, icpk_projective.cpp and so csrc/pyramid_rule.h, raycast_color_rule.h, projective_rule.h) can

@@ -1,4 +1,4 @@
-// tests/cpp/projective_host_main.cpp -- DIAGNOSTIC (build.build_projective_host_sanitized): icpk_projective_pixels over
+// tests/cpp/projective_host_main.cpp -- DIAGNOSTIC (build.program("projective_host_sanitized")): icpk_projective_pixels over
 // the shapes of the cases of tests/projective_cases.py, in a program of its own so that the host code (icpk_projective.cpp
 // and so csrc/projective_rule.h) can run under -fsanitize=address,undefined without anything being loaded into an
 // interpreter.  No GPU.  Every array is allocated at exactly the size the header asks for -- the level rows_s x cols_s,

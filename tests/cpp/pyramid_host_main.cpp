@@ -1,4 +1,4 @@
-// tests/cpp/pyramid_host_main.cpp -- DIAGNOSTIC (build.build_pyramid_host_sanitized): icpk_depth_pyramid_host over the
+// tests/cpp/pyramid_host_main.cpp -- DIAGNOSTIC (build.program("pyramid_host_sanitized")): icpk_depth_pyramid_host over the
 // shapes of the host and tile cases, in a program of its own so that the host code can run under
 // -fsanitize=address,undefined without anything being loaded into an interpreter.  No GPU.  Every image is allocated
 // at exactly the size the header asks for -- the input rows x cols, the output its level's (rows + 1) / 2 by

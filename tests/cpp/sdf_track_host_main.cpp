@@ -1,4 +1,4 @@
-// tests/cpp/sdf_track_host_main.cpp -- DIAGNOSTIC (build.build_sdf_track_host_sanitized): icpk_sdf_pixels over the shapes
+// tests/cpp/sdf_track_host_main.cpp -- DIAGNOSTIC (build.program("sdf_track_host_sanitized")): icpk_sdf_pixels over the shapes
 // of the cases of tests/sdf_track_cases.py, in a program of its own so that the host code (icpk_sdf_track.cpp and so
 // csrc/sdf_track_rule.h, projective_rule.h, tsdf_rule.h) can run under -fsanitize=address,undefined without anything
 // being loaded into an interpreter.  No GPU.  Every array is allocated at exactly the size the header asks for -- the level

@@ -1,6 +1,6 @@
 // tests/cpp/tsdf_apply_host_main.cpp -- a stand-alone program over icpk_tsdf_voxel_apply (the host half of the signed
 // update rule, csrc/tsdf_rule.h, and the op-list validation icpk_tsdf_apply shares with it) for sanitizer runs:
-// build.build_tsdf_apply_host_sanitized() compiles it together with icpk_tsdf_apply.cpp under
+// build.program("tsdf_apply_host_sanitized") compiles it together with icpk_tsdf_apply.cpp under
 // -fsanitize=address,undefined.  No GPU is touched.  Every array is allocated at exactly its size, so that a read past
 // an image, the op list or the voxel state is a heap overflow the sanitizer sees.
 //

@@ -1,5 +1,5 @@
 // tests/cpp/tsdf_mesh_host_main.cpp -- a stand-alone program over icpk_tsdf_mesh_host (the host half of the mesh rule,
-// csrc/tsdf_rule.h) for sanitizer runs: build.build_tsdf_mesh_host_sanitized() compiles it together with icpk_tsdf.cpp
+// csrc/tsdf_rule.h) for sanitizer runs: build.program("tsdf_mesh_host_sanitized") compiles it together with icpk_tsdf.cpp
 // under -fsanitize=address,undefined.  No GPU is touched.  Every output array is allocated at exactly the size the
 // counting call asked for, so that a write past the mesh is a heap overflow the sanitizer sees.
 //

@@ -1,6 +1,6 @@
 // tests/cpp/tsdf_shift_host_main.cpp -- the shift rule's host-callable half (csrc/tsdf_rule.h: tsdf_keep_box,
 // tsdf_ends_stay, tsdf_crossing_kept, tsdf_leaving_status, tsdf_shifted_origin) with a main of its own and no GPU, meant
-// to be compiled under -fsanitize=address,undefined (build.build_tsdf_shift_host_sanitized) and run directly.  The box
+// to be compiled under -fsanitize=address,undefined (build.program("tsdf_shift_host_sanitized")) and run directly.  The box
 // tests are held against the rule as include/icpk.h words it -- stays(v) asked of V, of N and of the six axis
 // neighbours of each, one voxel at a time -- for every voxel, axis and shift of a small volume, the extreme shifts an
 // int32 can hold among them; the origin goes there and back.

@@ -22,7 +22,7 @@ class Probe:
     """solve_impl.h over arrays of n cases: on_device=False runs the host code, True one thread per case on GPU 0."""
 
     def __init__(self):
-        self.lib = C.CDLL(build.build_solve_probe())
+        self.lib = C.CDLL(build.program("solve_probe"))
         for name in ("polar3", "svd3", "solve_reference", "solve_kabsch", "solve_p2l", "invert3f", "mul3f",
                      "sqrt_f64", "div_f64", "sqrt_f32", "div_f32"):
             getattr(self.lib, "probe_" + name).restype = C.c_int

@@ -49,7 +49,7 @@ def test_two_rank_frame_batch_line_through_the_c_abi_communicator():
     shared-memory stand-in for the collectives (tests/cpp/fake_rccl.cpp), two ranks on one GPU"""
     from icp_slam_prototype_amd import build
 
-    d = _run({"ICPK_TEST_HOOKS": "1", "ICPK_RCCL_LIB": build.build_fake_rccl()})
+    d = _run({"ICPK_TEST_HOOKS": "1", "ICPK_RCCL_LIB": build.program("fake_rccl")})
     assert d["collectives"].startswith("icpk_comm") and d["collectives_fallback_reason"] is None
     assert d["keyframe_broadcast_ms"] is not None and d["keyframe_broadcast_error"] is None
     assert d["keyframe_broadcast_bytes"] > 0
@@ -60,5 +60,5 @@ def test_two_rank_query_sharded_line_through_the_device_side_loop():
     through the C-ABI communicator (shared-memory stand-in for the collectives, two ranks on one GPU)"""
     from icp_slam_prototype_amd import build
 
-    d = _run({"ICPK_TEST_HOOKS": "1", "ICPK_RCCL_LIB": build.build_fake_rccl()}, ("--shard", "queries", "--iters", "5"))
+    d = _run({"ICPK_TEST_HOOKS": "1", "ICPK_RCCL_LIB": build.program("fake_rccl")}, ("--shard", "queries", "--iters", "5"))
     assert d["loop"].startswith("device-side") and d["collectives"].startswith("icpk_comm")

@@ -1,34 +1,25 @@
 """icp::Engine::bilateralDepthImage / backprojectSmoothed (tests/cpp/test_bilateral.cpp) against the same calls made
 through the Python binding, byte for byte: the smoothed image (filtered in place there) and the smoothed target cloud
 with its normals."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import bilateral_model as bm
-from icp_slam_prototype_amd import binding, build, depth
+import mirror
+from icp_slam_prototype_amd import binding, depth
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("name", ["room_masked", "radius_6"])
 def test_cpp_bilateral_equals_binding(name):
-    exe = build.build_bilateral_test()
     img, fields = bm.case(name)
     p = depth.bilateral_params(**fields)
     rows, cols = img.shape
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.u16"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(np.ascontiguousarray(img).tobytes())
-        out = subprocess.run([exe, fin, str(rows), str(cols), str(p.radius), repr(p.sigma_space), repr(p.sigma_range),
-                              str(p.range_cutoff), fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    raw, stdout = mirror.run("test_bilateral", np.ascontiguousarray(img).tobytes(), str(rows), str(cols), str(p.radius),
+                             repr(p.sigma_space), repr(p.sigma_range), str(p.range_cutoff))
     with binding.Context(0) as ctx:
         smooth = depth.bilateral_depth_image(ctx, img, p)
         n = depth.backproject_smoothed(ctx, img, which=1, normals_mode=binding.NORMALS_CROSS, params=p)
@@ -37,4 +28,4 @@ def test_cpp_bilateral_equals_binding(name):
     want = smooth.tobytes() + pts.tobytes() + nrm.tobytes()
     assert len(want) == 2 * rows * cols + 24 * n and raw[16:] == want
     assert smooth.tobytes() == bm.bilateral(img, *depth.bilateral_tables(p)).tobytes()
-    assert f"bilateral {rows} x {cols}, radius {p.radius}: smoothed target of {n} points" in out.stdout
+    assert f"bilateral {rows} x {cols}, radius {p.radius}: smoothed target of {n} points" in stdout

@@ -1,33 +1,25 @@
 """icp::Engine's colored ICP surface (tests/cpp/test_color.cpp) on the flat wall against the same calls made through
 the Python binding, bit for bit."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import color_model as cm
-from icp_slam_prototype_amd import binding, build
+import mirror
+from icp_slam_prototype_amd import binding
 
 pytestmark = pytest.mark.gpu
 
 
 def test_cpp_engine_equals_binding():
-    exe = build.build_color_test()
     p = cm.wall_pair()
     src, tgt = p["source"], p["target"]
     ns, nt = src.shape[1], tgt.shape[1]
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "pair.f32"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            for a in (src, p["source_intensity"], tgt, p["target_normals"], p["target_intensity"]):
-                f.write(np.ascontiguousarray(a, np.float32).tobytes())
-        out = subprocess.run([exe, fin, str(ns), str(nt), str(cm.WALL_RADIUS), str(cm.WALL_MIN_NB), str(cm.LAMBDA),
-                              str(cm.WALL_MAX_DIST), str(cm.WALL_ITER), fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    cloud = (src, p["source_intensity"], tgt, p["target_normals"], p["target_intensity"])
+    blob = b"".join(np.ascontiguousarray(a, np.float32).tobytes() for a in cloud)
+    raw, _ = mirror.run("test_color", blob, str(ns), str(nt), str(cm.WALL_RADIUS), str(cm.WALL_MIN_NB),
+                        str(cm.LAMBDA), str(cm.WALL_MAX_DIST), str(cm.WALL_ITER))
     assert len(raw) == 28 + 64
     head = struct.unpack_from("<7i", raw, 0)
     T = np.frombuffer(raw, np.float32, 16, 28).reshape(4, 4)

@@ -82,7 +82,7 @@ def test_broadcast_target_drops_the_colours_of_the_ranks_that_receive():
     from icp_slam_prototype_amd import binding, build
 
     build.build()
-    fake = build.build_fake_rccl()
+    fake = build.program("fake_rccl")
     mpc = mp.get_context("spawn")
     q_id, q_out = mpc.Queue(), mpc.Queue()
     procs = [mpc.Process(target=_worker, args=(r, 2, fake, q_id, q_out)) for r in range(2)]

@@ -97,7 +97,7 @@ def test_two_ranks_on_one_gpu_through_the_c_abi(oracle):
     from icp_slam_prototype_amd import binding, build, synth
 
     build.build()
-    fake = build.build_fake_rccl()
+    fake = build.program("fake_rccl")
     mpc = mp.get_context("spawn")
     q_id, q_out = mpc.Queue(), mpc.Queue()
     procs = [mpc.Process(target=_worker, args=(r, 2, fake, q_id, q_out)) for r in range(2)]

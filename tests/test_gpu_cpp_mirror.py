@@ -1,7 +1,6 @@
 """The C++ host mirror (icp_slam_prototype_amd/include/icp_align.hpp): a sequence
 of depth frames through icp::Tracker -- the getTransformation-shaped entry point
 -- compared with the same procedure restated in Python over the oracle."""
-import os
 import struct
 import subprocess
 import tempfile
@@ -9,6 +8,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import mirror
 from icp_slam_prototype_amd import build, synth
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +21,6 @@ def mul3f(A, B):
 
 
 def test_tracker_sequence_and_align(oracle):
-    exe = build.build_cpp_test()
     rows, cols, max_iter, thr = 120, 160, 6, 1e-5
     rng = np.random.default_rng(0)
     frames = []
@@ -31,17 +30,13 @@ def test_tracker_sequence_and_align(oracle):
         d[rng.random(d.shape) > 0.5] = 0
         frames.append(d.astype(np.uint16))
     p = synth.frustum_pair(1500, seed=3, rot_deg=(0, 1, 0), shift=(0.01, 0, 0))
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<4if", rows, cols, len(frames), max_iter, thr))
-            for d in frames:
-                f.write(d.tobytes())
-            f.write(struct.pack("<2i", p["source"].shape[1], p["target"].shape[1]))
-            f.write(np.ascontiguousarray(p["source"], np.float32).tobytes())
-            f.write(np.ascontiguousarray(p["target"], np.float32).tobytes())
-        subprocess.check_call([exe, fin, fout])
-        raw = open(fout, "rb").read()
+    parts = [struct.pack("<4if", rows, cols, len(frames), max_iter, thr)]
+    for d in frames:
+        parts.append(d.tobytes())
+    parts.append(struct.pack("<2i", p["source"].shape[1], p["target"].shape[1]))
+    parts.append(np.ascontiguousarray(p["source"], np.float32).tobytes())
+    parts.append(np.ascontiguousarray(p["target"], np.float32).tobytes())
+    raw, _ = mirror.run("test_icp_align", b"".join(parts), timeout=None)
     off = 0
     Rcam = np.eye(3, dtype=np.float32)
     pcam = np.full(3, 5, np.float32)
@@ -119,7 +114,7 @@ def test_native_tracker_bench_matches_the_python_path(filt, resident):
 
     from icp_slam_prototype_amd import binding
 
-    exe = build.build_tracker_bench()
+    exe = build.program("tracker_bench")
     rows, cols, rounds = 120, 160, 2
     rng = np.random.default_rng(1)
     frames = []

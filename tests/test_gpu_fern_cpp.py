@@ -1,16 +1,14 @@
 """icp::FernDatabase and icp::TsdfVolume::relocalise (tests/cpp/test_fern.cpp) against the same calls made through the
 Python binding, byte for byte, on the first 12 frames of the scene of tests/fern_model.py and one query frame."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import fern_model as fm
+import mirror
 import tsdf_cases as tc
-from icp_slam_prototype_amd import binding, build, depth
+from icp_slam_prototype_amd import binding, depth
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +24,6 @@ def matches(r):
 
 
 def test_cpp_fern_database_equals_binding():
-    exe = build.build_fern_test()
     s, v = fm.scene(), tc.ROOM_VOLUME
     rows, cols = tc.ROOM_SHAPE
     blob = struct.pack("<8i", *v["dims"], rows, cols, COUNT, K, LEVEL)
@@ -34,13 +31,7 @@ def test_cpp_fern_database_equals_binding():
     for i in range(COUNT):
         blob += np.ascontiguousarray(s["poses"][i], np.float64).tobytes() + np.ascontiguousarray(s["frames"][i], np.uint16).tobytes()
     blob += np.ascontiguousarray(s["queries"][QUERY], np.uint16).tobytes()
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(blob)
-        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    raw, stdout = mirror.run("test_fern", blob)
     pp = depth.pyramid_params(levels=LEVEL + 1)
     shape = depth.pyramid_shapes((rows, cols), LEVEL + 1)[LEVEL]
     want = b""
@@ -77,4 +68,4 @@ def test_cpp_fern_database_equals_binding():
         want += np.ascontiguousarray(pose, np.float64).tobytes()
     assert n == 3 and keyframe == r["index"][0] and abs(fm.SCENE_KEYFRAMES[keyframe] - QUERY) <= fm.SCENE_MAX_GAP
     assert len(raw) == len(want) and raw == want
-    assert f"fern database: {n} keyframes of {COUNT} frames; the query restarted from keyframe {keyframe} with {res.count} pairs" in out.stdout
+    assert f"fern database: {n} keyframes of {COUNT} frames; the query restarted from keyframe {keyframe} with {res.count} pairs" in stdout

@@ -1,15 +1,13 @@
 """icp::Engine::removeOutliers / outlierStats and icp::Tracker's outlierFilter (tests/cpp/test_filter.cpp) against the
 same calls made by hand through the Python binding, bit for bit; and SequenceRunner(outlier_filter=...) likewise."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import filter_model as fm
-from icp_slam_prototype_amd import binding, build, sequence, synth
+import mirror
+from icp_slam_prototype_amd import binding, sequence, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -93,20 +91,11 @@ def test_sequence_runner_equals_calls_by_hand(setting):
 
 @pytest.mark.parametrize("setting", SETTINGS)
 def test_cpp_tracker_and_engine(setting):
-    exe = build.build_filter_test()
     frames = _frames()
     rows, cols = frames[0].shape
     s = setting or dict(kind=-1, k=0, std_ratio=0.0, radius=0.0, min_neighbors=0)
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "frames.u16"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            for d in frames:
-                f.write(d.tobytes())
-        out = subprocess.run([exe, fin, str(rows), str(cols), str(len(frames)), str(s["kind"]), str(s["k"]),
-                              repr(s["std_ratio"]), repr(s["radius"]), str(s["min_neighbors"]), "16", fout],
-                             capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    raw, _ = mirror.run("test_filter", b"".join(d.tobytes() for d in frames), str(rows), str(cols), str(len(frames)), str(s["kind"]),
+                        str(s["k"]), repr(s["std_ratio"]), repr(s["radius"]), str(s["min_neighbors"]), "16")
     with binding.Context(0) as c:
         runner = _hand(c, setting)
         off = 0

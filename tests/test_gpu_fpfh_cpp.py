@@ -1,34 +1,24 @@
 """icp::Engine::computeFPFH / fpfh / matchFeatures / registerGlobal (tests/cpp/test_fpfh.cpp) against the C ABI's output
 and against the same calls made through the Python binding, bit for bit."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import fpfh_cases as fc
-from icp_slam_prototype_amd import binding, build
+import mirror
+from icp_slam_prototype_amd import binding
 
 pytestmark = pytest.mark.gpu
 
 
 def test_cpp_engine_equals_c_abi_and_binding():
-    exe = build.build_fpfh_test()
     p = fc.e2e_pair(n_plane=55, n_clutter=140, normal_radius=0.35)
     src, tgt = p["source"], p["target"]
     ns, nt = src.shape[1], tgt.shape[1]
     radius, n_hyp, seed, max_dist = 0.45, 300, 12, 0.05
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.f32"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            for a in (src, p["ns"], tgt, p["nt"]):
-                f.write(np.ascontiguousarray(a, np.float32).tobytes())
-        out = subprocess.run([exe, fin, str(ns), str(nt), str(radius), str(n_hyp), str(seed), str(max_dist), fout],
-                             capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    blob = b"".join(np.ascontiguousarray(a, np.float32).tobytes() for a in (src, p["ns"], tgt, p["nt"]))
+    raw, _ = mirror.run("test_fpfh", blob, str(ns), str(nt), str(radius), str(n_hyp), str(seed), str(max_dist))
     with binding.Context(0) as c:
         c.set_target(tgt)
         c.set_target_normals(p["nt"])

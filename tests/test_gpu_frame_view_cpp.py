@@ -3,16 +3,14 @@ odometry.ProjectiveOdometry and the binding's calls, byte for byte: every frame'
 built, the planes of the last view and the pairs of the last frame against it -- frame to frame, and with a keyframe
 bound."""
 import ctypes as C
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import mirror
 import tsdf_cases as tc
-from icp_slam_prototype_amd import binding, build, depth
+from icp_slam_prototype_amd import binding, depth
 from icp_slam_prototype_amd.odometry import ProjectiveOdometry
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +20,6 @@ COUNTS = (6, 4, 3)
 
 @pytest.mark.parametrize("bound", [None, 4.2])
 def test_cpp_frame_odometry_equals_binding(bound):
-    exe = build.build_frame_odometry_test()
     frames = [tc.room_frame(*m) for m in list(tc.ROOM_MOTIONS) + [tc.ROOM_FOURTH]]
     rows, cols = frames[0][0].shape
     P0 = frames[0][1]
@@ -30,13 +27,7 @@ def test_cpp_frame_odometry_equals_binding(bound):
     blob += struct.pack("<4f", tc.ROOM_FX, tc.ROOM_CX, bound or 0.0, 0.0) + np.ascontiguousarray(P0, np.float64).tobytes()
     for d, _ in frames:
         blob += np.ascontiguousarray(d, np.uint16).tobytes()
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(blob)
-        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    raw, stdout = mirror.run("test_frame_odometry", blob)
     want = b""
     with binding.Context(0) as ctx:
         odo = ProjectiveOdometry(ctx, pose=P0, pyramid=COUNTS, keyframe=None if bound is None else dict(max_angle_deg=bound),
@@ -58,4 +49,4 @@ def test_cpp_frame_odometry_equals_binding(bound):
         want += struct.pack("<i", int((pixel >= 0).sum()))
     assert raw == want
     assert built == ([1, 2, 3, 4] if bound is None else [1, 1, 2, 3])  # 4.0, then 4.5 (> 4.2), then 6.1 degrees from the view
-    assert f"frame 3: t = {pose[0, 3]:.6f} {pose[1, 3]:.6f} {pose[2, 3]:.6f}, {built[-1]} views built" in out.stdout
+    assert f"frame 3: t = {pose[0, 3]:.6f} {pose[1, 3]:.6f} {pose[2, 3]:.6f}, {built[-1]} views built" in stdout

@@ -1,33 +1,24 @@
 """icp::Engine's plane-to-plane surface (tests/cpp/test_gicp.cpp) against the same calls made through the Python
 binding, bit for bit."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import gicp_model as gm
-from icp_slam_prototype_amd import binding, build
+import mirror
+from icp_slam_prototype_amd import binding
 
 pytestmark = pytest.mark.gpu
 
 
 def test_cpp_engine_equals_binding():
-    exe = build.build_gicp_test()
     p = gm.quarter_pair()
     src, tgt = p["source"], p["target"]
     ns, nt = src.shape[1], tgt.shape[1]
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "pair.f32"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(np.ascontiguousarray(src, np.float32).tobytes())
-            f.write(np.ascontiguousarray(tgt, np.float32).tobytes())
-        out = subprocess.run([exe, fin, str(ns), str(nt), "0.08", "5", "0.001", "0.3", "20", fout], capture_output=True,
-                             text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    parts = [np.ascontiguousarray(src, np.float32).tobytes(),
+             np.ascontiguousarray(tgt, np.float32).tobytes()]
+    raw, _ = mirror.run("test_gicp", b"".join(parts), str(ns), str(nt), "0.08", "5", "0.001", "0.3", "20")
     head = struct.unpack_from("<7i", raw, 0)
     T = np.frombuffer(raw, np.float32, 16, 28).reshape(4, 4)
     nrm = np.frombuffer(raw, np.float32, 3 * ns, 28 + 64).reshape(3, ns)

@@ -154,7 +154,7 @@ def test_device_fast_live_sequence_equals_host_keypoint_path(oracle):
 
 
 def test_map_tracker_fast_cpp_matches_the_binding(oracle):
-    exe = build.build_map_fast_test()
+    exe = build.program("test_map_tracker_fast")
     depth, color = live_color_frames()
     want = reference_run(oracle, depth, color)
     with tempfile.TemporaryDirectory() as td:

@@ -1,16 +1,14 @@
 """The voxel certainty map on the device (icpk_map_*, icpk_align_to_map, icp::MapTracker) against the sequential
 model of tests/map_model.py: after every update the whole 27 MB grid, both lists in order and the slots must be bit
 equal; the live path (icp.cpp:27-271) against a restatement composed from the model and oracle primitives."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import map_model as mm
-from icp_slam_prototype_amd import binding, build, synth
+import mirror
+from icp_slam_prototype_amd import binding, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -291,17 +289,12 @@ def test_align_to_map_live_sequence(oracle, host_loop):
 
 
 def test_map_tracker_cpp_matches_the_binding(oracle):
-    exe = build.build_map_test()
     frames, kp = live_frames()
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<5if", ROWS, COLS, NFRAMES, MAX_ITER, kp.shape[0], THR))
-            for d in frames:
-                f.write(d.tobytes())
-            f.write(kp.tobytes())
-        subprocess.check_call([exe, fin, fout])
-        raw = open(fout, "rb").read()
+    parts = [struct.pack("<5if", ROWS, COLS, NFRAMES, MAX_ITER, kp.shape[0], THR)]
+    for d in frames:
+        parts.append(d.tobytes())
+    parts.append(kp.tobytes())
+    raw, _ = mirror.run("test_map_tracker", b"".join(parts), timeout=None)
     off = 0
     with binding.Context(0) as ref:
         rs = Restatement(oracle, ref)

@@ -1,14 +1,12 @@
 """icp::MapTracker with dense = true (icp_map.hpp, tests/cpp/test_map_tracker_dense.cpp) against the same frames
 through the binding, call for call: status, iterations, T and the point list after every fold must be bit equal."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from icp_slam_prototype_amd import binding, build
+import mirror
+from icp_slam_prototype_amd import binding
 from test_gpu_map import I3, P5, inv3_pose, live_frames, mul3f
 
 pytestmark = pytest.mark.gpu
@@ -17,18 +15,13 @@ MAX_ITER, THR, FACTOR, SEED = 10, 1e-5, 40, 17
 
 
 def test_dense_map_tracker_cpp_matches_the_binding(oracle):
-    exe = build.build_map_dense_test()
     frames, kp = live_frames()
     rows, cols = frames[0].shape
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<6ifQ", rows, cols, len(frames), MAX_ITER, kp.shape[0], FACTOR, THR, SEED))
-            for d in frames:
-                f.write(d.tobytes())
-            f.write(kp.tobytes())
-        subprocess.check_call([exe, fin, fout])
-        raw = open(fout, "rb").read()
+    parts = [struct.pack("<6ifQ", rows, cols, len(frames), MAX_ITER, kp.shape[0], FACTOR, THR, SEED)]
+    for d in frames:
+        parts.append(d.tobytes())
+    parts.append(kp.tobytes())
+    raw, _ = mirror.run("test_map_tracker_dense", b"".join(parts), timeout=None)
     off = 0
     with binding.Context(0) as ctx:
         ctx.set_subsample(FACTOR, SEED)

@@ -15,14 +15,12 @@ The bounds (derived, not measured):
 The points left out of the direction comparison (small gap, small |s|, near the line test) are AT MOST 1 % of a cloud,
 asserted per cloud.  Without a viewpoint the sign comes from the largest component; where the two largest magnitudes lie
 within 1e-6 of each other the comparison is up to sign and the point counts towards the same cap."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import mirror
 import normals_model as nm
 import tsdf_cases
 import voxel_model as vm
@@ -377,15 +375,8 @@ def test_thinned_pair_and_map_list_align_point_to_plane(kinect):
 
 def test_cpp_mirror(kinect):
     """icp::Engine::estimateTargetNormals / normalStats (tests/cpp/test_normals.cpp) against the same calls made here."""
-    exe = build.build_normals_test()
     tgt = np.ascontiguousarray(kinect["target"][:, :30000])
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "cloud.f32"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(tgt.tobytes())
-        out = subprocess.run([exe, fin, str(tgt.shape[1]), "0.05", "6", fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    raw, _ = mirror.run("test_normals", tgt.tobytes(), str(tgt.shape[1]), "0.05", "6")
     n = tgt.shape[1]
     with binding.Context(0) as c:
         c.set_target(tgt)

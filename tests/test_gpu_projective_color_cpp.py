@@ -1,22 +1,19 @@
 """icp::Engine::setPyramidIntensity and icp::TsdfVolume::raycastColorGradients / alignProjectiveColored
 (tests/cpp/test_projective_color.cpp) against the same calls made through the Python binding, byte for byte: the pose,
 the result, every trace entry, the view's gradients and the level's intensities of the colour room at level 1."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import mirror
 import projective_color_cases as kc
-from icp_slam_prototype_amd import binding, build, depth
+from icp_slam_prototype_amd import binding, depth
 
 pytestmark = pytest.mark.gpu
 
 
 def test_cpp_projective_color_equals_binding():
-    exe = build.build_projective_color_test()
     name, iters, lam = "room_l1", 6, 0.9
     c = kc.case(name)
     t = kc.volume_case(c["volume"])
@@ -31,13 +28,7 @@ def test_cpp_projective_color_equals_binding():
     blob += struct.pack("<4f", view["z_near"], view["z_far"], view["step"], c["radius"]) + c["view_pose"].tobytes()
     blob += struct.pack("<8i", *c["depth"].shape, c["level"] + 1, c["level"], iters, 6, 0, 0)
     blob += struct.pack("<4f", c["fx"], c["cx"], c["max_dist"], lam) + c["estimate"].tobytes() + c["depth"].tobytes() + c["intensity"].tobytes()
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(blob)
-        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    raw, stdout = mirror.run("test_projective_color", blob)
     with binding.Context(0) as ctx:
         p = kc.device_setup(ctx, name, depth, binding)
         p.max_iterations = iters
@@ -52,4 +43,4 @@ def test_cpp_projective_color_equals_binding():
     want += grad.tobytes() + level.tobytes()
     assert raw[16:] == want
     assert grad.tobytes() == kc.gradients_of(name).tobytes() and level.tobytes() == kc.case(name)["level_intensity"].tobytes()
-    assert f"coloured projective level 1: status 0 after {iters} updates, {res.count} pairs at the last evaluation" in out.stdout
+    assert f"coloured projective level 1: status 0 after {iters} updates, {res.count} pairs at the last evaluation" in stdout

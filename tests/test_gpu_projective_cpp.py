@@ -1,23 +1,20 @@
 """icp::TsdfVolume::alignProjective / projectiveAssociate / projectiveTrace (tests/cpp/test_projective.cpp) against the
 same calls made through the Python binding, byte for byte: the pose, the result, every trace entry and the per-pixel
 pairs of the room at level 1."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import mirror
 import projective_cases as pc
 import tsdf_cases as tc
-from icp_slam_prototype_amd import binding, build, depth
+from icp_slam_prototype_amd import binding, depth
 
 pytestmark = pytest.mark.gpu
 
 
 def test_cpp_projective_equals_binding():
-    exe = build.build_projective_test()
     name, iters = "room_l1", 6
     c, t = pc.case(name), tc.case("room")
     v, view = t["volume"], c["view"]
@@ -30,13 +27,7 @@ def test_cpp_projective_equals_binding():
     blob += c["view_pose"].tobytes()
     blob += struct.pack("<8i", *c["depth"].shape, c["level"] + 1, c["level"], iters, 6, 0, 0)
     blob += struct.pack("<4f", c["fx"], c["cx"], c["max_dist"], c["min_normal_cos"]) + c["estimate"].tobytes() + c["depth"].tobytes()
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(blob)
-        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    raw, stdout = mirror.run("test_projective", blob)
     with binding.Context(0) as ctx:
         assert ctx.tsdf_create(dims=v["dims"], voxel=v["voxel"], origin=v["origin"], trunc=v["trunc"]).max_weight == 255
         p = pc.device_setup(ctx, name, depth, binding)
@@ -51,4 +42,4 @@ def test_cpp_projective_equals_binding():
         want += e["pose"].tobytes() + e["sums"].tobytes() + struct.pack("<q2i", e["count"], e["status"], 0)
     want += pixel.tobytes() + dist.tobytes()
     assert raw[16:] == want
-    assert f"projective level 1: status 0 after {iters} updates, {res.count} pairs at the last evaluation, {pairs} at the estimate" in out.stdout
+    assert f"projective level 1: status 0 after {iters} updates, {res.count} pairs at the last evaluation, {pairs} at the estimate" in stdout

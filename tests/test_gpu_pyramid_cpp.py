@@ -1,33 +1,24 @@
 """icp::Engine::buildDepthPyramid / depthPyramidLevel / backprojectPyramidLevel (tests/cpp/test_pyramid.cpp) against the
 same calls made through the Python binding, byte for byte: every level of the pyramid and the target cloud of its last
 level with its normals."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import mirror
 import pyramid_model as pm
-from icp_slam_prototype_amd import binding, build, depth
+from icp_slam_prototype_amd import binding, depth
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("name,levels,smooth", [("room_masked", 3, 0), ("65x131", 4, 1)])
 def test_cpp_pyramid_equals_binding(name, levels, smooth):
-    exe = build.build_pyramid_test()
     img, K = pm.case(name)
     rows, cols = img.shape
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.u16"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(np.ascontiguousarray(img).tobytes())
-        out = subprocess.run([exe, fin, str(rows), str(cols), str(levels), str(K), str(smooth), fout], capture_output=True,
-                             text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    raw, stdout = mirror.run("test_pyramid", np.ascontiguousarray(img).tobytes(), str(rows), str(cols), str(levels),
+                             str(K), str(smooth))
     p = depth.pyramid_params(levels=levels, range_cutoff=K)
     b = depth.bilateral_params() if smooth else None
     with binding.Context(0) as ctx:
@@ -41,4 +32,4 @@ def test_cpp_pyramid_equals_binding(name, levels, smooth):
     assert raw[24:] == want
     model = pm.pyramid(depth.bilateral_host(img, b) if smooth else img, levels, K)
     assert all(g.tobytes() == m.tobytes() for g, m in zip(got, model))
-    assert f"pyramid {rows} x {cols}, {levels} levels: target of {n} points from level {levels - 1}" in out.stdout
+    assert f"pyramid {rows} x {cols}, {levels} levels: target of {n} points from level {levels - 1}" in stdout

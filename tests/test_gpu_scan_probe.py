@@ -20,7 +20,7 @@ def _p(a):
 
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build.build_scan_probe())
+    lib = C.CDLL(build.program("scan_probe"))
     for name in ("pair", "rounds_i32", "rounds_i64", "runs"):
         getattr(lib, "probe_scan_" + name).restype = C.c_int
     return lib

@@ -1,15 +1,13 @@
 """icp::Engine::scorePoses / scoreCurrent (tests/cpp/test_score.cpp) against the C ABI's output and against the same
 calls made through the Python binding, bit for bit."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import gicp_model as gm
-from icp_slam_prototype_amd import binding, build
+import mirror
+from icp_slam_prototype_amd import binding
 from test_gpu_score import pose
 
 pytestmark = pytest.mark.gpu
@@ -33,22 +31,15 @@ def same(a, b):
 
 
 def test_cpp_engine_equals_c_abi_and_binding():
-    exe = build.build_score_test()
     p = gm.quarter_pair()
     src, tgt = p["source"], p["target"]
     ns, nt = src.shape[1], tgt.shape[1]
     T = np.stack([pose(), pose(0, 2.0, 0, (0.03, 0, 0)), pose(0.5, -1.0, 0.3, (-0.02, 0.01, 0.0))])
     max_dist, iters = 0.25, 5
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.f32"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(np.ascontiguousarray(src, np.float32).tobytes())
-            f.write(np.ascontiguousarray(tgt, np.float32).tobytes())
-            f.write(np.ascontiguousarray(T, np.float32).tobytes())
-        out = subprocess.run([exe, fin, str(ns), str(nt), "3", str(max_dist), str(iters), fout], capture_output=True,
-                             text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    parts = [np.ascontiguousarray(src, np.float32).tobytes(),
+             np.ascontiguousarray(tgt, np.float32).tobytes(),
+             np.ascontiguousarray(T, np.float32).tobytes()]
+    raw, _ = mirror.run("test_score", b"".join(parts), str(ns), str(nt), "3", str(max_dist), str(iters))
     assert len(raw) == 8 * REC + 16
     eng, abi, cur = records(raw, 0, 3), records(raw, 3, 3), records(raw, 6, 2)
     status, bad_n, final_pairs, _ = struct.unpack_from("<4i", raw, 8 * REC)

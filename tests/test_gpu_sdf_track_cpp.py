@@ -1,23 +1,20 @@
 """icp::TsdfVolume::alignSdf / sdfReduce / sdfAssociate / sdfTrace (tests/cpp/test_sdf_track.cpp) against the same calls
 made through the Python binding, byte for byte: the pose, the result, every trace entry, the per-pixel cells and the sums
 of the room at level 1."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import mirror
 import sdf_track_cases as sc
 import tsdf_cases as tc
-from icp_slam_prototype_amd import binding, build, depth
+from icp_slam_prototype_amd import binding, depth
 
 pytestmark = pytest.mark.gpu
 
 
 def test_cpp_sdf_track_equals_binding():
-    exe = build.build_sdf_track_test()
     name, iters = "room_l1", 6
     c, t = sc.case(name), tc.case("room")
     v = t["volume"]
@@ -28,13 +25,7 @@ def test_cpp_sdf_track_equals_binding():
         blob += np.ascontiguousarray(P, np.float64).tobytes() + np.ascontiguousarray(d, np.uint16).tobytes()
     blob += struct.pack("<8i", *c["depth"].shape, c["level"] + 1, c["level"], iters, 6, c["min_weight"], 0)
     blob += struct.pack("<4f", c["fx"], c["cx"], c["max_abs_tsdf"], c["min_normal_cos"]) + c["estimate"].tobytes() + c["depth"].tobytes()
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(blob)
-        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    raw, stdout = mirror.run("test_sdf_track", blob)
     with binding.Context(0) as ctx:
         # the volume fused on the device from the same frames, as the program does (the model's bytes: test_gpu_tsdf.py)
         assert ctx.tsdf_create(dims=v["dims"], voxel=v["voxel"], origin=v["origin"], trunc=v["trunc"]).max_weight == 255
@@ -53,4 +44,4 @@ def test_cpp_sdf_track_equals_binding():
         want += e["pose"].tobytes() + e["sums"].tobytes() + struct.pack("<q2i", e["count"], e["status"], 0)
     want += cell.tobytes() + value.tobytes() + sums.tobytes() + struct.pack("<q", count)
     assert raw[16:] == want
-    assert f"sdf level 1: status 0 after {iters} updates, {res.count} accepted at the last evaluation, {accepted} at the estimate" in out.stdout
+    assert f"sdf level 1: status 0 after {iters} updates, {res.count} accepted at the last evaluation, {accepted} at the estimate" in stdout

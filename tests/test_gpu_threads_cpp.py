@@ -2,15 +2,13 @@
 threads started together (and, their engines made, starting to track together) give, byte for byte, what the same
 program gets tracking them one after the other, and both equal SequenceRunner on the same frames through the binding -- which ties the threaded C++ result to what the rest of
 the suite holds to the oracle."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from icp_slam_prototype_amd import binding, build, sequence, synth
+import mirror
+from icp_slam_prototype_amd import binding, sequence, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -47,24 +45,18 @@ def _through_the_binding(frames, src, tgt, odd):
 
 
 def test_engines_on_threads_equal_the_serial_pass_and_the_binding():
-    exe = build.build_threads_test()
     seqs = [_sequence(300 + s) for s in range(S)]
     clouds = [(synth.backproject(q[1]) + synth.CAMERA_START, synth.backproject(q[0]) + synth.CAMERA_START) for q in seqs]
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<4i", S, F, ROWS, COLS))
-            for q in seqs:
-                for d in q:
-                    f.write(d.tobytes())
-            for src, tgt in clouds:
-                f.write(struct.pack("<2i", src.shape[1], tgt.shape[1]))
-                f.write(np.ascontiguousarray(src, np.float32).tobytes())
-                f.write(np.ascontiguousarray(tgt, np.float32).tobytes())
-        # (a time-out or a signal is a failure: the program is not run again)
-        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, (out.returncode, out.stderr)
-        raw = open(fout, "rb").read()
+    parts = [struct.pack("<4i", S, F, ROWS, COLS)]
+    for q in seqs:
+        for d in q:
+            parts.append(d.tobytes())
+    for src, tgt in clouds:
+        parts.append(struct.pack("<2i", src.shape[1], tgt.shape[1]))
+        parts.append(np.ascontiguousarray(src, np.float32).tobytes())
+        parts.append(np.ascontiguousarray(tgt, np.float32).tobytes())
+    # (a time-out or a signal is a failure: the program is not run again)
+    raw, _ = mirror.run("test_threads", b"".join(parts))
     per_seq = F * (8 + 64) + 48  # icp::align + F - 1 frame pairs, then camR and camP
     assert len(raw) == 2 * S * per_seq + 16 * S
     # the threads did track side by side: each one's tracking loop shares time with another's (they start it together)

@@ -1,40 +1,32 @@
 """icp::TsdfVolume (tests/cpp/test_tsdf.cpp) on the room case against the same calls made through the Python binding,
 byte for byte: the planes, the counts and the surface list."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import mirror
 import tsdf_cases as tc
-from icp_slam_prototype_amd import binding, build
+from icp_slam_prototype_amd import binding
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("name", ["room", "room_color"])
 def test_cpp_tsdf_volume_equals_binding(name):
-    exe = build.build_tsdf_test()
     c = tc.case(name)
     v = c["volume"]
     color = bool(v.get("color"))
     rows, cols = c["frames"][0][0].shape
     n = int(np.prod(v["dims"]))
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<8i", *v["dims"], 255, binding.TSDF_COLOR if color else 0, rows, cols, len(c["frames"])))
-            f.write(np.float32([v["voxel"], *v["origin"], v["trunc"], c["fx"], c["cx"], 0]).tobytes())
-            for d, P, img in c["frames"]:
-                f.write(np.ascontiguousarray(P, np.float64).tobytes())
-                f.write(np.ascontiguousarray(d, np.uint16).tobytes())
-                if color:
-                    f.write(np.ascontiguousarray(img, np.float32).tobytes())
-        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    parts = [struct.pack("<8i", *v["dims"], 255, binding.TSDF_COLOR if color else 0, rows, cols, len(c["frames"])),
+             np.float32([v["voxel"], *v["origin"], v["trunc"], c["fx"], c["cx"], 0]).tobytes()]
+    for d, P, img in c["frames"]:
+        parts.append(np.ascontiguousarray(P, np.float64).tobytes())
+        parts.append(np.ascontiguousarray(d, np.uint16).tobytes())
+        if color:
+            parts.append(np.ascontiguousarray(img, np.float32).tobytes())
+    raw, stdout = mirror.run("test_tsdf", b"".join(parts))
     with binding.Context(0) as ctx:
         ctx.tsdf_create(dims=v["dims"], voxel=v["voxel"], origin=v["origin"], trunc=v["trunc"],
                         flags=binding.TSDF_COLOR if color else 0)
@@ -51,4 +43,4 @@ def test_cpp_tsdf_volume_equals_binding(name):
     want += s["voxel"].tobytes() + s["axis"].tobytes()
     assert len(raw) == 4 * k + 8 + len(want) and len(want) == n * (10 if color else 6) + 33 * npts
     assert raw[4 * k + 8:] == want
-    assert out.stdout.count("frame ") == k and f"surface: {npts} points, {ndrop} without a normal" in out.stdout
+    assert stdout.count("frame ") == k and f"surface: {npts} points, {ndrop} without a normal" in stdout

@@ -1,16 +1,14 @@
 """icp::TsdfVolume::deintegrate / apply / refuse (tests/cpp/test_tsdf_refuse.cpp) on ten frames of the room -- two
 batches of refuse -- against the same calls made through the Python binding, byte for byte."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import mirror
 import tsdf_apply_cases as ac
 import tsdf_cases as tc
-from icp_slam_prototype_amd import binding, build
+from icp_slam_prototype_amd import binding
 from icp_slam_prototype_amd.tsdf import TsdfVolume
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +16,6 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("color", [False, True])
 def test_cpp_refuse_equals_binding(color):
-    exe = build.build_tsdf_refuse_test()
     v = tc.ROOM_VOLUME
     motions = [((0.0, 2.0 * k - 9.0, 0.0), (0.03 * k - 0.1, 0.0, 0.01 * k)) for k in range(10)]
     depths = [tc.room_frame(*m)[0] for m in motions]
@@ -26,19 +23,14 @@ def test_cpp_refuse_equals_binding(color):
     old = [ac.drift(P, (0.2 * k, -0.3 * k, 0.1 * k), (0.005 * k, -0.002 * k, 0.0)) for k, P in enumerate(new)]
     inten = [tc.room_intensity(*m) for m in motions] if color else None
     rows, cols = depths[0].shape
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<8i", *v["dims"], 255, binding.TSDF_COLOR if color else 0, rows, cols, len(depths)))
-            f.write(np.float32([v["voxel"], *v["origin"], v["trunc"], tc.ROOM_FX, tc.ROOM_CX, 0]).tobytes())
-            for k, d in enumerate(depths):
-                f.write(np.ascontiguousarray(old[k], np.float64).tobytes() + np.ascontiguousarray(new[k], np.float64).tobytes())
-                f.write(np.ascontiguousarray(d, np.uint16).tobytes())
-                if color:
-                    f.write(np.ascontiguousarray(inten[k], np.float32).tobytes())
-        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    parts = [struct.pack("<8i", *v["dims"], 255, binding.TSDF_COLOR if color else 0, rows, cols, len(depths)),
+             np.float32([v["voxel"], *v["origin"], v["trunc"], tc.ROOM_FX, tc.ROOM_CX, 0]).tobytes()]
+    for k, d in enumerate(depths):
+        parts.append(np.ascontiguousarray(old[k], np.float64).tobytes() + np.ascontiguousarray(new[k], np.float64).tobytes())
+        parts.append(np.ascontiguousarray(d, np.uint16).tobytes())
+        if color:
+            parts.append(np.ascontiguousarray(inten[k], np.float32).tobytes())
+    raw, stdout = mirror.run("test_tsdf_refuse", b"".join(parts))
     with binding.Context(0) as ctx:
         vol = TsdfVolume(ctx, color=color, fx=tc.ROOM_FX, cx=tc.ROOM_CX, **v)
         vol.integrate_all(depths, old, inten)
@@ -49,4 +41,4 @@ def test_cpp_refuse_equals_binding(color):
     want = moved.astype(np.int64).tobytes() + struct.pack("<i", taken) + put.astype(np.int64).tobytes()
     want += b"".join(a.tobytes() for a in planes if a is not None)
     assert taken == put[0] > 1000 and moved.min() > 1000 and planes[1].max() == 10 and raw == want
-    assert f"refused 10 frames; the last one: {taken} voxels out, {put[0]} back in" in out.stdout
+    assert f"refused 10 frames; the last one: {taken} voxels out, {put[0]} back in" in stdout

@@ -1,41 +1,33 @@
 """icp::TsdfVolume::extractLeaving / getBox / shift / params (tests/cpp/test_tsdf_shift.cpp) on the room cases against
 the same calls made through the Python binding, byte for byte."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import mirror
 import tsdf_cases as tc
-from icp_slam_prototype_amd import binding, build
+from icp_slam_prototype_amd import binding
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("name,s", [("room", (3, -2, 1)), ("room_color", (-1, 0, 0))])
 def test_cpp_shift_equals_binding(name, s):
-    exe = build.build_tsdf_shift_test()
     c = tc.case(name)
     v = c["volume"]
     color = bool(v.get("color"))
     rows, cols = c["frames"][0][0].shape
     lo, hi = (60, 0, 10), (64, 64, 50)
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "in.bin"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<8i", *v["dims"], 255, binding.TSDF_COLOR if color else 0, rows, cols, len(c["frames"])))
-            f.write(np.float32([v["voxel"], *v["origin"], v["trunc"], c["fx"], c["cx"], 0]).tobytes())
-            f.write(struct.pack("<9i", *s, *lo, *hi))
-            for d, P, img in c["frames"]:
-                f.write(np.ascontiguousarray(P, np.float64).tobytes())
-                f.write(np.ascontiguousarray(d, np.uint16).tobytes())
-                if color:
-                    f.write(np.ascontiguousarray(img, np.float32).tobytes())
-        out = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    parts = [struct.pack("<8i", *v["dims"], 255, binding.TSDF_COLOR if color else 0, rows, cols, len(c["frames"])),
+             np.float32([v["voxel"], *v["origin"], v["trunc"], c["fx"], c["cx"], 0]).tobytes(),
+             struct.pack("<9i", *s, *lo, *hi)]
+    for d, P, img in c["frames"]:
+        parts.append(np.ascontiguousarray(P, np.float64).tobytes())
+        parts.append(np.ascontiguousarray(d, np.uint16).tobytes())
+        if color:
+            parts.append(np.ascontiguousarray(img, np.float32).tobytes())
+    raw, stdout = mirror.run("test_tsdf_shift", b"".join(parts))
     with binding.Context(0) as ctx:
         ctx.tsdf_create(dims=v["dims"], voxel=v["voxel"], origin=v["origin"], trunc=v["trunc"],
                         flags=binding.TSDF_COLOR if color else 0)
@@ -54,4 +46,4 @@ def test_cpp_shift_equals_binding(name, s):
     want += total.astype(np.int64).tobytes() + np.array(p.origin[:], np.float32).tobytes()
     want += b"".join(a.tobytes() for a in planes if a is not None)
     assert counts[0] > 40 and total.tolist() == list(s) and raw == want
-    assert f"leaving: {counts[0]} points, {counts[1]} without a normal; shifted by {s[0]} {s[1]} {s[2]}" in out.stdout
+    assert f"leaving: {counts[0]} points, {counts[1]} without a normal; shifted by {s[0]} {s[1]} {s[2]}" in stdout

@@ -1,14 +1,12 @@
 """Voxel-grid downsampling on the device (icpk_voxel_downsample, K11) against the numpy model of the rule
 (tests/voxel_model.py): points, normals, first_index, count, out_of_point, n_out and n_dropped bit for bit -- no
 tolerance anywhere -- then the state the call leaves behind, the loop on the downsampled pair, and the layers above."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import mirror
 import voxel_model as vm
 from icp_slam_prototype_amd import binding, build, sequence, synth
 
@@ -420,18 +418,10 @@ def test_sequence_runner_option(mode):
 def test_cpp_tracker_option(leaf, mode):
     """icp::Tracker with voxelLeaf / voxelMode (tests/cpp/test_voxel.cpp) against the same calls made by hand; with the
     option untouched, against a runner that never heard of it."""
-    exe = build.build_voxel_test()
     frames = _frames()
     rows, cols = frames[0].shape
-    with tempfile.TemporaryDirectory() as td:
-        fin, fout = os.path.join(td, "frames.u16"), os.path.join(td, "out.bin")
-        with open(fin, "wb") as f:
-            for d in frames:
-                f.write(d.tobytes())
-        out = subprocess.run([exe, fin, str(rows), str(cols), str(len(frames)), repr(leaf), str(mode), "16", fout],
-                             capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0, out.stderr
-        raw = open(fout, "rb").read()
+    raw, _ = mirror.run("test_voxel", b"".join(d.tobytes() for d in frames), str(rows), str(cols), str(len(frames)), repr(leaf),
+                        str(mode), "16")
     with binding.Context(0) as c:
         runner = _HandRunner(c, leaf, mode) if leaf > 0 else _PlainRunner(c)
         off = 0

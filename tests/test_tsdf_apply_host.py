@@ -1,9 +1,7 @@
 """The signed update rule of the TSDF volume (K30) without a GPU: icpk_tsdf_voxel_apply -- the host half of
 csrc/tsdf_rule.h, the header the kernel includes -- against tests/tsdf_apply_model.py bit for bit; a lone +1 op against
-icpk_tsdf_voxel_update; the exact properties of the rule on the model; the derived bound of a removal; and the
-stand-alone sanitizer program over the op-list validation and the host rule."""
-import subprocess
-
+icpk_tsdf_voxel_update; the exact properties of the rule on the model; and the derived bound of a removal.  (The
+stand-alone sanitizer program over the op-list validation and the host rule: tests/test_sanitized_programs_host.py.)"""
 import numpy as np
 import pytest
 
@@ -119,11 +117,3 @@ def test_error_bound_recurrence():
     assert am.error_bound([+1, +1, -1]) == pytest.approx(11, rel=1e-4)
     assert am.error_bound([+1, +1, +1, -1]) == pytest.approx(11, rel=1e-4)
     assert am.worst_error_bound([(+1, "a"), (+1, "b"), (+1, "c"), (-1, "b")]) == pytest.approx(11, rel=1e-4)
-
-
-def test_sanitized_host_program_exits_clean(lib):
-    exe = build.build_tsdf_apply_host_sanitized()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    print(r.stdout, r.stderr)
-    assert r.returncode == 0 and "FAILED" not in r.stdout and "refusals" in r.stdout
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
