@@ -108,6 +108,8 @@ SYMBOLS = [
     "icpk_projective_set_view", "icpk_frame_view_pixels",
     "icpk_default_sdf_params", "icpk_sdf_associate", "icpk_sdf_reduce", "icpk_align_sdf", "icpk_get_sdf_trace",
     "icpk_sdf_pixels",
+    "icpk_default_esdf_params", "icpk_esdf_compute", "icpk_esdf_get", "icpk_esdf_get_box", "icpk_esdf_query",
+    "icpk_esdf_release", "icpk_esdf_host", "icpk_esdf_query_host",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -208,6 +210,19 @@ class TsdfParams(C.Structure):
 
 class TsdfOp(C.Structure):
     _fields_ = [("sign", C.c_int32), ("frame", C.c_int32), ("pose", C.c_double * 16)]
+
+
+ESDF_UNKNOWN_OCCUPIED = 1  # icpk_esdf_params.flags: a voxel of unknown class counts as an obstacle
+ESDF_MAX_RADIUS = 1024     # the largest max_distance / voxel
+ESDF_FAR = 2 ** 31 - 1     # |q| of a voxel with nothing of the other kind within the radius
+ESDF_UNKNOWN, ESDF_FREE, ESDF_OCCUPIED = 0, 1, 2  # the class plane
+ESDF_Q_FAR, ESDF_Q_UNKNOWN, ESDF_Q_OUTSIDE = 1, 2, 0x80  # the query's status bits
+ESDF_MAX_QUERY = 1 << 24   # points per icpk_esdf_query
+
+
+class EsdfParams(C.Structure):
+    """icpk_esdf_params"""
+    _fields_ = [("min_weight", C.c_int32), ("max_distance", C.c_float), ("flags", C.c_int32)]
 
 
 class TsdfRaycastParams(C.Structure):
@@ -600,6 +615,16 @@ def load():
     lib.icpk_get_sdf_trace.argtypes = [C.c_void_p, C.POINTER(ProjectiveIter), C.c_int32]
     lib.icpk_sdf_pixels.argtypes = [sp, C.POINTER(TsdfParams), dp, u16, C.c_int32, C.c_int32, fp, u16, C.c_int64, C.c_int32,
                                     ip, fp, dp]
+    xp = C.POINTER(EsdfParams)
+    lib.icpk_default_esdf_params.argtypes = [xp]
+    lib.icpk_default_esdf_params.restype = None
+    lib.icpk_esdf_compute.argtypes = [C.c_void_p, xp, i64]
+    lib.icpk_esdf_get.argtypes = [C.c_void_p, ip, u8, fp]
+    lib.icpk_esdf_get_box.argtypes = [C.c_void_p, ip, ip, ip, u8, fp]
+    lib.icpk_esdf_query.argtypes = [C.c_void_p, fp, fp, fp, C.c_int32, fp, fp, fp, fp, u8]
+    lib.icpk_esdf_release.argtypes = [C.c_void_p]
+    lib.icpk_esdf_host.argtypes = [C.POINTER(TsdfParams), xp, fp, u16, ip, u8, fp, i64]
+    lib.icpk_esdf_query_host.argtypes = [C.POINTER(TsdfParams), xp, ip, u8, fp, fp, fp, C.c_int32, fp, fp, fp, fp, u8]
     _lib = lib
     return lib
 
@@ -1617,6 +1642,127 @@ def sdf_pixels(params, volume, pose, level, tsdf, weight, first=0, count=None, t
     if rc < 0:
         raise IcpkError(rc, "icpk_sdf_pixels")
     return cell, value, tm, rc
+
+
+# -- the Euclidean distance map of the volume (K31): the host-only entry points, then the device calls -------------
+def esdf_params(max_distance=None, min_weight=None, flags=None):
+    """icpk_default_esdf_params, overridden by what is given."""
+    p = EsdfParams()
+    load().icpk_default_esdf_params(C.byref(p))
+    if max_distance is not None:
+        p.max_distance = max_distance
+    if min_weight is not None:
+        p.min_weight = min_weight
+    if flags is not None:
+        p.flags = flags
+    return p
+
+
+def _esdf(params, kw):
+    return params if params is not None else esdf_params(**kw)
+
+
+def _query_points(points):
+    """world points as (3, n) float32: three contiguous planes, as every cloud here is passed"""
+    pts = _f(points)
+    if pts.ndim != 2 or pts.shape[0] != 3:
+        raise ValueError("points: (3, n) expected")
+    return pts
+
+
+def esdf_host(volume, tsdf, weight, params=None, **kw):
+    """icpk_esdf_host (host only): THE DISTANCE RULE over host planes of the TsdfParams `volume` (its dims and voxel).
+    Returns (sq int32, cls uint8, dist float32, each (dz, dy, dx), counts (4,) int64: unknown, free, occupied, far)."""
+    p = _esdf(params, kw)
+    n = volume.dims[0] * volume.dims[1] * volume.dims[2]
+    f, w = _f(tsdf).reshape(-1), np.ascontiguousarray(weight, np.uint16).reshape(-1)
+    if f.size != n or w.size != n:
+        raise ValueError("the planes must hold one entry per voxel")
+    shape = (volume.dims[2], volume.dims[1], volume.dims[0])
+    sq, cls, dist = np.empty(shape, np.int32), np.empty(shape, np.uint8), np.empty(shape, np.float32)
+    counts = np.zeros(4, np.int64)
+    rc = load().icpk_esdf_host(C.byref(volume), C.byref(p), _fp(f), w.ctypes.data_as(C.POINTER(C.c_uint16)),
+                               sq.ctypes.data_as(C.POINTER(C.c_int32)), cls.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(dist),
+                               counts.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != OK:
+        raise IcpkError(rc, "icpk_esdf_host")
+    return sq, cls, dist, counts
+
+
+def esdf_query_host(volume, sq, cls, points, params=None, **kw):
+    """icpk_esdf_query_host (host only): THE QUERY RULE for the world points (3, n) over host sq and cls planes of the
+    TsdfParams `volume` (dims, voxel and the origin to use).  Returns dict(dist (n,), grad (3, n), status (n,) uint8)."""
+    p = _esdf(params, kw)
+    pts = _query_points(points)
+    n = pts.shape[1]
+    nvox = volume.dims[0] * volume.dims[1] * volume.dims[2]
+    q, c = np.ascontiguousarray(sq, np.int32).reshape(-1), np.ascontiguousarray(cls, np.uint8).reshape(-1)
+    if q.size != nvox or c.size != nvox:
+        raise ValueError("the planes must hold one entry per voxel")
+    dist, grad, status = np.zeros(n, np.float32), np.zeros((3, n), np.float32), np.zeros(n, np.uint8)
+    rc = load().icpk_esdf_query_host(C.byref(volume), C.byref(p), q.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     c.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(pts[0]), _fp(pts[1]), _fp(pts[2]), n, _fp(dist),
+                                     _fp(grad[0]), _fp(grad[1]), _fp(grad[2]), status.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != OK:
+        raise IcpkError(rc, "icpk_esdf_query_host")
+    return dict(dist=dist, grad=grad, status=status)
+
+
+# ... and the device calls: functions over a Context, like the moving volume's and the signed updates' above
+def esdf_compute(ctx, params=None, counts=True, **kw):
+    """icpk_esdf_compute: the distance map of the volume as it stands; it stays on the device, a snapshot.  params:
+    EsdfParams, or max_distance / min_weight / flags as keywords.  Returns counts (4,) int64 -- unknown, free,
+    occupied, far --, or None with counts=False (no host wait)."""
+    p = _esdf(params, kw)
+    out = np.zeros(4, np.int64)
+    ctx._chk(ctx._lib.icpk_esdf_compute(ctx._h, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_int64)) if counts else None))
+    return out if counts else None
+
+
+def esdf_get(ctx, sq=True, cls=True, dist=True):
+    """icpk_esdf_get: (sq int32, cls uint8, dist float32) of shape (dz, dy, dx); None where not asked."""
+    p = ctx._tsdf
+    if p is None:
+        ctx._chk(ctx._lib.icpk_esdf_get(ctx._h, None, None, None))  # (ICPK_E_NOT_SET)
+    shape = (p.dims[2], p.dims[1], p.dims[0])
+    q = np.empty(shape, np.int32) if sq else None
+    c = np.empty(shape, np.uint8) if cls else None
+    d = np.empty(shape, np.float32) if dist else None
+    ctx._chk(ctx._lib.icpk_esdf_get(ctx._h, None if q is None else q.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    None if c is None else c.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                    None if d is None else _fp(d)))
+    return q, c, d
+
+
+def esdf_get_box(ctx, lo, hi, sq=True, cls=True, dist=True):
+    """icpk_esdf_get_box: the same of the sub-box lo <= (x, y, z) < hi, as (hi_z - lo_z, hi_y - lo_y, hi_x - lo_x)
+    arrays."""
+    lo, hi = _i3(lo, "lo"), _i3(hi, "hi")
+    shape = tuple(max(int(hi[a]) - int(lo[a]), 1) for a in (2, 1, 0))  # (an empty box: the call refuses it)
+    q = np.empty(shape, np.int32) if sq else None
+    c = np.empty(shape, np.uint8) if cls else None
+    d = np.empty(shape, np.float32) if dist else None
+    i32 = C.POINTER(C.c_int32)
+    ctx._chk(ctx._lib.icpk_esdf_get_box(ctx._h, lo.ctypes.data_as(i32), hi.ctypes.data_as(i32),
+                                        None if q is None else q.ctypes.data_as(i32),
+                                        None if c is None else c.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        None if d is None else _fp(d)))
+    return q, c, d
+
+
+def esdf_query(ctx, points):
+    """icpk_esdf_query: THE QUERY RULE for the world points (3, n).  Returns dict(dist (n,), grad (3, n), status
+    (n,) uint8: ESDF_Q_OUTSIDE, or ESDF_Q_FAR | ESDF_Q_UNKNOWN of the cell's corners)."""
+    pts = _query_points(points)
+    n = pts.shape[1]
+    dist, grad, status = np.zeros(n, np.float32), np.zeros((3, n), np.float32), np.zeros(n, np.uint8)
+    ctx._chk(ctx._lib.icpk_esdf_query(ctx._h, _fp(pts[0]), _fp(pts[1]), _fp(pts[2]), n, _fp(dist), _fp(grad[0]),
+                                      _fp(grad[1]), _fp(grad[2]), status.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return dict(dist=dist, grad=grad, status=status)
+
+
+def esdf_release(ctx):
+    ctx._chk(ctx._lib.icpk_esdf_release(ctx._h))
 
 
 class Context:

@@ -24,7 +24,8 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_pyramid.cpp", "kernels_pyramid.hip", "icpk_projective.cpp", "kernels_projective.hip",
            "kernels_pyramid_color.hip", "icpk_raycast_color.cpp", "kernels_raycast_color.hip",
            "icpk_fern.cpp", "kernels_fern.hip", "icpk_frame_view.cpp", "kernels_frame_view.hip",
-           "icpk_sdf_track.cpp", "kernels_sdf_track.hip", "icpk_tsdf_apply.cpp", "kernels_tsdf_apply.hip"]
+           "icpk_sdf_track.cpp", "kernels_sdf_track.hip", "icpk_tsdf_apply.cpp", "kernels_tsdf_apply.hip",
+           "icpk_esdf.cpp", "kernels_esdf.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -149,13 +150,25 @@ PROGRAMS = {
 # What __graft_entry__.build() builds, in this order: everything but the sanitized diagnostics.
 DEFAULT = [name for name, row in PROGRAMS.items() if not row["kind"].startswith("sanitized")]
 
+# The rows added since the tests pinned PROGRAMS and DEFAULT as they stand (tests/test_build_recipes_host.py,
+# tests/test_sanitized_programs_host.py): the same shape, the same kinds, resolved by the same plan() and program().
+LATER_PROGRAMS = {
+    "test_tsdf_esdf": _mirror("icp::TsdfVolume::computeEsdf / esdfPlanes / esdfBox / queryEsdf (icp_tsdf.hpp, K31)"),
+    "esdf_host_sanitized": _sanitized(["icpk_esdf.cpp"], "icpk_esdf.cpp and so csrc/esdf_rule.h and tsdf_rule.h; the "
+                                      "volume's refusals and the launchers come from the library; the program calls the two "
+                                      "host-only entry points alone, every array allocated at exactly its size"),
+}
+
+# What __graft_entry__.build() builds after DEFAULT: the later rows but the sanitized diagnostics.
+LATER_DEFAULT = [name for name, row in LATER_PROGRAMS.items() if not row["kind"].startswith("sanitized")]
+
 Plan = collections.namedtuple("Plan", "out sources deps commands links_lib")
 
 
 def plan(name):
-    """How PROGRAMS[name] is built: its output, the sources its row names, what it is rebuilt after (one rule per kind)
-    and the compiler commands.  Runs nothing."""
-    row = PROGRAMS[name]
+    """How PROGRAMS[name] (or LATER_PROGRAMS[name]) is built: its output, the sources its row names, what it is rebuilt
+    after (one rule per kind) and the compiler commands.  Runs nothing."""
+    row = PROGRAMS[name] if name in PROGRAMS else LATER_PROGRAMS[name]
     kind = row["kind"]
     cpp = os.path.join(ROOT, "tests", "cpp")
     abi = os.path.join(ROOT, "include", "icpk.h")
@@ -199,7 +212,7 @@ def plan(name):
 
 
 def program(name, force=False):
-    """Build PROGRAMS[name] if it is older than anything plan(name) says it depends on; returns its path under lib/."""
+    """Build PROGRAMS[name] (or LATER_PROGRAMS[name]) if it is older than anything plan(name) says it depends on; returns its path under lib/."""
     p = plan(name)
     os.makedirs(LIBDIR, exist_ok=True)
     if p.links_lib:
@@ -243,5 +256,5 @@ globals().update({former: functools.partial(program, name) for former, name in _
 
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
-    for name in DEFAULT:
+    for name in DEFAULT + LATER_DEFAULT:
         print(program(name, force="--force" in sys.argv))

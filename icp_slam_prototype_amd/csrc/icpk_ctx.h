@@ -511,6 +511,10 @@ struct icpk_ctx {
   icpk::DevBuf<int32_t> sdf_cell;  // [rows_s cols_s]
   icpk::DevBuf<float> sdf_value;   // [rows_s cols_s]
   std::vector<icpk_projective_iter> sdf_trace;
+  // K31 (icpk_esdf.cpp), behind everything older for the same reason: the Euclidean distance map of the TSDF volume -- a
+  // snapshot in a state of its own, null until the first icpk_esdf_compute.  icpk_tsdf.cpp drops it (icpk_esdf_drop)
+  // where the volume is created, reset, set, shifted or released; nothing else of the context reads or writes it
+  struct icpk_esdf_state* esdf = nullptr;
 };
 
 #define ICPK_HIP(ctx, call)                                                                      \
@@ -527,6 +531,8 @@ void icpk_map_free(icpk_ctx* ctx);      // called by icpk_destroy (icpk_map.cpp)
 void icpk_fast_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_fast.cpp)
 void icpk_tsdf_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_tsdf.cpp)
 void icpk_frame_view_free(icpk_ctx* ctx);  // called by icpk_destroy (icpk_frame_view.cpp)
+void icpk_esdf_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_esdf.cpp)
+void icpk_esdf_drop(icpk_ctx* ctx);     // the distance map no longer describes the volume: its getters answer ICPK_E_NOT_SET
 int icpk_comm_allreduce_device(icpk_ctx* ctx, double* dev, int n);  // in-stream sum over the ranks (icpk_comm.cpp)
 // ICPK_NN_MAP: one K9 sweep of the working source against the map into ctx->best (icpk_map.cpp); the target must be
 // the map's current lookup target

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "esdf_rule.h"
 #include "tsdf_rule.h"
 
 namespace icpk {
@@ -1122,5 +1123,36 @@ struct SdfArgs {
 void launch_sdf_reduce(const SdfArgs& a, hipStream_t s);
 // every pixel's cell or code, and its distance D, at the state's pose (device arrays of rows cols entries)
 void launch_sdf_associate(const SdfArgs& a, int32_t* cell, float* value, hipStream_t s);
+
+// kernels_esdf.hip -- K31, the Euclidean distance map of the TSDF volume (the distance rule and the query rule are
+// esdf_rule.h), over K19's chunks: a thread owns a voxel in every pass
+#ifndef ICPK_ESDF_STEP
+#define ICPK_ESDF_STEP 4  // (a diagnostic build may set another: DESIGN.md K31 has what 1 .. 16 measured)
+#endif
+constexpr int ESDF_STEP = ICPK_ESDF_STEP;  // offsets a lane takes between two looks at its bound (esdf_line_min's STEP)
+struct EsdfArgs {
+  const float* tsdf;       // the volume's planes: read by the classification alone
+  const uint16_t* weight;
+  uint8_t* cls;            // the class plane
+  int32_t* plane[2];       // the signed plane of the passes: x writes [0], y [1], z [0] again, which then holds q
+  int dims[3];
+  long long n, chunk;
+  int min_weight, flags, R;
+  int* slots;              // [4][TSDF_MAX_BLOCKS] per chunk: voxels of class 0, 1, 2; voxels with |q| == FAR
+};
+// classification, the three passes and counts[4] (device) = n_unknown, n_free, n_occupied, n_far
+void launch_esdf_compute(const EsdfArgs& a, int nblocks, long long* counts, hipStream_t s);
+// sq, cls and m(q) of the sub-box into packed arrays of a.m entries (device; any may be null)
+struct EsdfBoxArgs {
+  TsdfBoxArgs box;
+  const int32_t* sq;
+  const uint8_t* cls;
+  int R;
+  float voxel;
+};
+void launch_esdf_box(const EsdfBoxArgs& a, int32_t* sq_out, uint8_t* cls_out, float* dist_out, hipStream_t s);
+// THE QUERY RULE for n points: xyz three planes of n floats in, out five planes of n words: dist, gx, gy, gz and the
+// status widened to an int
+void launch_esdf_query(const EsdfMap& m, const float* xyz, int n, float* out, hipStream_t s);
 
 }  // namespace icpk

@@ -76,6 +76,7 @@ struct icpk_tsdf_state {
 void icpk_tsdf_free(icpk_ctx* ctx) {
   delete ctx->tsdf;  // (its buffers free themselves)
   ctx->tsdf = nullptr;
+  icpk_esdf_drop(ctx);  // (K31: the map of a volume that is gone)
 }
 
 int icpk::tsdf_raycast_view(icpk_ctx* ctx, TsdfRayView* out) {
@@ -302,6 +303,7 @@ int icpk_tsdf_reset(icpk_ctx* ctx) {
   if (!ctx) return ICPK_E_ARG;
   if (!ctx->tsdf) return fail(ctx, ICPK_E_NOT_SET, "no TSDF volume (icpk_tsdf_create)");
   ICPK_HIP(ctx, hipSetDevice(ctx->device));
+  icpk_esdf_drop(ctx);
   return clear_volume(ctx, ctx->tsdf);
 }
 
@@ -401,6 +403,7 @@ int icpk_tsdf_set(icpk_ctx* ctx, const float* tsdf, const uint16_t* weight, cons
   ICPK_HIP(ctx, hipMemcpyAsync(v->weight, weight, n * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
   if (intensity) ICPK_HIP(ctx, hipMemcpyAsync(v->intensity, intensity, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   ICPK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller's arrays are free again)
+  icpk_esdf_drop(ctx);
   v->have_surface = false;
   v->have_raycast = false;
   v->have_mesh = false;
@@ -498,6 +501,7 @@ int icpk_tsdf_shift(icpk_ctx* ctx, const int32_t s[3]) {
     v->total[k] += s[k];
     v->p.origin[k] = tsdf_shifted_origin(v->origin0[k], v->total[k], v->p.voxel);
   }
+  icpk_esdf_drop(ctx);
   v->have_surface = false;
   v->have_raycast = false;
   v->have_mesh = false;

@@ -24,17 +24,7 @@ struct SdfHit {
   float p[3], n[3], D;
 };
 
-// rule 6: the gradient of tsdf_trilerp's interpolant at the fractions w, from the same eight corners e[x + 2 y + 4 z]
-// (per voxel; only its direction is used)
-ICPK_HD void sdf_gradient(const float e[8], const float w[3], float g[3]) {
-  const float c00 = tsdf_lerp(e[0], e[1], w[0]), c10 = tsdf_lerp(e[2], e[3], w[0]);
-  const float c01 = tsdf_lerp(e[4], e[5], w[0]), c11 = tsdf_lerp(e[6], e[7], w[0]);
-  const float b0 = tsdf_lerp(c00, c10, w[1]), b1 = tsdf_lerp(c01, c11, w[1]);
-  const float dx00 = e[1] - e[0], dx10 = e[3] - e[2], dx01 = e[5] - e[4], dx11 = e[7] - e[6];
-  g[0] = tsdf_lerp(tsdf_lerp(dx00, dx10, w[1]), tsdf_lerp(dx01, dx11, w[1]), w[2]);
-  g[1] = tsdf_lerp(c10 - c00, c11 - c01, w[2]);
-  g[2] = b1 - b0;
-}
+// (rule 6's sdf_gradient: tsdf_rule.h holds it, beside tsdf_trilerp, for THE QUERY RULE of esdf_rule.h too)
 
 // Rules 1 - 8 for source pixel (r, c) of depth d: the linear index of its cell's lowest corner (>= 0, and *out filled),
 // or its code.  No index into the planes is formed before tsdf_cell's range test has passed on all three axes; the

@@ -11,7 +11,9 @@
 //                        it against the distance field itself, with no ray cast (K29).
 //                        extractMesh / getMesh give the surface as a triangle mesh (K21); setPlanes restores a saved
 //                        model.  shift / extractLeaving / getBox let the volume follow the camera (K23): the box
-//                        moves by whole voxels, what is about to leave it is listed first.
+//                        moves by whole voxels, what is about to leave it is listed first.  computeEsdf / esdfPlanes /
+//                        queryEsdf give the exact Euclidean distance map of the volume (K31): how far a voxel, or
+//                        any point, is from the nearest obstacle.
 //   * icp::FernDatabase -- the fern keyframe database of an Engine's context (icpk_fern_*, K27): every tracked frame's
 //                        coarse pyramid level is encoded, looked up and harvested on the GPU (process); a tracker
 //                        that has lost the camera restarts from the nearest keyframes' poses (TsdfVolume::relocalise).
@@ -416,6 +418,33 @@ class TsdfVolume {
   int getBox(const int32_t lo[3], const int32_t hi[3], float* tsdf, uint16_t* weight, float* intensity = nullptr) {
     return icpk_tsdf_get_box(eng_.ctx(), lo, hi, tsdf, weight, intensity);
   }
+  // K31 -- the exact Euclidean distance map of the volume as it stands: per voxel the signed squared distance, in voxels,
+  // to the nearest voxel of the other kind, exact up to p.max_distance and ICPK_ESDF_FAR beyond.  It stays on the device,
+  // a snapshot: integrate leaves it as it was (stale); setPlanes, shift, reset and the destructor drop it
+  static icpk_esdf_params esdfDefaults() {
+    icpk_esdf_params p;
+    icpk_default_esdf_params(&p);
+    return p;
+  }
+  // counts (optional): voxels of class unknown, free, occupied, and those with |q| == FAR; null: the call does not wait
+  int computeEsdf(const icpk_esdf_params& p, int64_t* counts = nullptr) { return icpk_esdf_compute(eng_.ctx(), &p, counts); }
+  // the map, voxels() entries each, x fastest: sq, the class (0 unknown, 1 free, 2 occupied), the metric distance; any
+  // pointer may be null
+  int esdfPlanes(int32_t* sq, uint8_t* cls, float* dist) { return icpk_esdf_get(eng_.ctx(), sq, cls, dist); }
+  int esdfBox(const int32_t lo[3], const int32_t hi[3], int32_t* sq, uint8_t* cls, float* dist) {
+    return icpk_esdf_get_box(eng_.ctx(), lo, hi, sq, cls, dist);
+  }
+  // the map at n world points, trilinear between voxel centres; all five vectors are sized to n.  status: 0x80 outside
+  // (dist and gradient 0), else bit 0 a FAR corner, bit 1 a corner of unknown class
+  int queryEsdf(const std::vector<float>& x, const std::vector<float>& y, const std::vector<float>& z, std::vector<float>& dist,
+                std::vector<float>& gx, std::vector<float>& gy, std::vector<float>& gz, std::vector<uint8_t>& status) {
+    if (y.size() != x.size() || z.size() != x.size()) return ICPK_E_ARG;
+    for (std::vector<float>* v : {&dist, &gx, &gy, &gz}) v->assign(x.size(), 0.f);
+    status.assign(x.size(), 0);
+    return icpk_esdf_query(eng_.ctx(), x.data(), y.data(), z.data(), (int32_t)x.size(), dist.data(), gx.data(), gy.data(),
+                           gz.data(), status.data());
+  }
+  int releaseEsdf() { return icpk_esdf_release(eng_.ctx()); }
 
  private:
   void forget() { rayRows_ = rayCols_ = 0, meshVertices_ = meshTriangles_ = meshNoNormal_ = 0; }

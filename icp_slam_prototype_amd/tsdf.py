@@ -178,6 +178,34 @@ class TsdfVolume:
         stitches a larger model offline archives of a slab before it leaves."""
         return binding.tsdf_get_box(self.ctx, lo, hi, intensity=intensity)
 
+    def esdf(self, max_distance=2.0, min_weight=1, unknown_occupied=False, counts=True):
+        """The exact Euclidean distance map of the volume as it stands (K31): per voxel the signed squared distance, in
+        voxels, to the nearest voxel of the other kind -- occupied (weight >= min_weight and tsdf < 0; with
+        unknown_occupied also every voxel below min_weight) against the rest --, exact up to max_distance metres and
+        binding.ESDF_FAR beyond.  The map stays on the device, a snapshot: integrating further frames leaves it as it
+        was (stale), and set_planes, shift, reset and release drop it.  Returns dict(unknown, free, occupied, far), the
+        voxel counts, or None with counts=False (no host wait)."""
+        n = binding.esdf_compute(self.ctx, max_distance=max_distance, min_weight=min_weight,
+                                  flags=binding.ESDF_UNKNOWN_OCCUPIED if unknown_occupied else 0, counts=counts)
+        return None if n is None else dict(unknown=int(n[0]), free=int(n[1]), occupied=int(n[2]), far=int(n[3]))
+
+    def esdf_planes(self):
+        """(sq int32, cls uint8, dist float32) of the last esdf(), as (dz, dy, dx) arrays: the signed squared distance,
+        the class (0 unknown, 1 free, 2 occupied) and the metric distance in metres, positive outside the obstacles and
+        zero half a voxel from an occupied voxel's centre."""
+        return binding.esdf_get(self.ctx)
+
+    def esdf_box(self, lo, hi):
+        """esdf_planes() of the sub-box lo <= (x, y, z) < hi, as (nz, ny, nx) arrays."""
+        return binding.esdf_get_box(self.ctx, lo, hi)
+
+    def esdf_query(self, points):
+        """The distance map at the world points (3, n), trilinear between voxel centres: dict(dist (n,) metres, grad
+        (3, n): the gradient of that interpolant, pointing away from the obstacles, status (n,) uint8:
+        binding.ESDF_Q_OUTSIDE for a point outside the centres' box (dist and grad 0), else ESDF_Q_FAR and
+        ESDF_Q_UNKNOWN where a corner of the cell is beyond max_distance or of unknown class)."""
+        return binding.esdf_query(self.ctx, points)
+
     def shift(self, s, min_weight=None):
         """The volume moves by s = (s_x, s_y, s_z) whole voxels (K23): the new voxel v holds the old voxel v + s, what
         falls off is gone and what comes in is fresh; the origin follows.  min_weight: first extract and download the

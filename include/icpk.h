@@ -2188,6 +2188,78 @@ int icpk_sdf_pixels(const icpk_sdf_params *params, const icpk_tsdf_params *volum
                     const uint16_t *level, int32_t rows_s, int32_t cols_s, const float *tsdf, const uint16_t *weight,
                     int64_t first, int32_t count, int32_t *cell, float *value, double *terms);
 
+/* ---- K31: an exact Euclidean distance map of the TSDF volume ---------------------------------------------------------
+ * Everything above reads the truncation band, |sdf| <= trunc; outside it a voxel holds tsdf = 1 or nothing.  "How far
+ * is this point from anything solid?" -- the question a planner, a collision checker or a clearance query asks -- has
+ * no answer in a truncated field.  The distance map (an ESDF, as voxblox and nvblox keep beside their TSDF) answers it:
+ * per voxel the exact Euclidean distance, in whole voxels squared, to the nearest voxel of the other kind.  It is an
+ * integer result: any correct algorithm gives the same bytes.
+ *
+ * THE DISTANCE RULE.  Integers only, up to the metric value of step 4.
+ *   Parameters (icpk_esdf_params): min_weight, max_distance (metres), flags (ICPK_ESDF_UNKNOWN_OCCUPIED).
+ *   0. The radius R = floor((double)max_distance / (double)voxel), on the host.  1 <= R <= ICPK_ESDF_MAX_RADIUS, else
+ *      ICPK_E_ARG: it is not clamped.
+ *   1. The class of voxel v with value f and weight w (uint8): 0 UNKNOWN: w < min_weight.  1 FREE: w >= min_weight &&
+ *      !(f < 0).  2 OCCUPIED: w >= min_weight && f < 0.  (The surface rule's sign convention.)
+ *   2. The obstacle set O: the voxels of class 2; with ICPK_ESDF_UNKNOWN_OCCUPIED every voxel whose class is not 1.
+ *      Outside the volume there are no voxels, neither in O nor outside it.
+ *   3. The signed squared distance q(v) (int32); |v - u|^2 is the squared Euclidean distance of the integer indices.
+ *        v not in O: q = +min over u in O of |v - u|^2 if that is <= R^2, else +ICPK_ESDF_FAR (an empty O: +FAR);
+ *        v in O:     q = -min over u not in O of |v - u|^2 if that is <= R^2, else -ICPK_ESDF_FAR.
+ *      q is never 0.
+ *   4. The metric distance m(q) (float32, one rounding per operation, no fused multiply-add): a = (float)|q| (exact:
+ *      |q| <= 2^20); s = sqrtf(a), correctly rounded -- for +-FAR s = (float)(R + 1) --; m = +-fl(fl(s - 0.5f) voxel).
+ *      The half voxel puts the zero between a free voxel and its occupied neighbour.  m is a function of q, R and voxel
+ *      alone and is not stored.
+ *   5. counts[4] = {n_unknown, n_free, n_occupied, n_far}, int64; n_far counts the voxels with |q| == FAR.
+ *
+ * THE QUERY RULE, for a world point p:
+ *   THE RAY RULE's SAMPLE cell at p (its rule 5), read with the volume's CURRENT origin (K23).  Out of range, NaN
+ *   included: dist = 0, grad = 0, status = 0x80.  Otherwise e[k] = m(q(corner k)) in the ray rule's corner order
+ *   e[x + 2 y + 4 z]; dist = the ray rule's trilinear value of e at the fractions w; grad_a = fl(g_a / voxel) with g
+ *   THE SDF TRACKING RULE's gradient (its rule 6) of the same e and w.  Status bit 0: a corner is FAR; bit 1: a corner
+ *   is of class 0.
+ *
+ * The map is a SNAPSHOT, like the ray-cast maps: icpk_esdf_compute reads the tsdf and weight planes and writes buffers
+ * of its own, behind a state of its own; it touches nothing else the context holds.  icpk_tsdf_create, _reset, _set,
+ * _shift and _release drop it (its getters then answer ICPK_E_NOT_SET); icpk_esdf_release and icpk_destroy free it.
+ * Integration, icpk_tsdf_apply, the extractions, the ray cast and the mesh leave it alone: after them it is STALE --
+ * it describes the volume as it was -- until the next icpk_esdf_compute.
+ *
+ * icpk_esdf_compute     the map of the volume as it stands.  counts (or NULL: the call does not wait for the device).
+ * icpk_esdf_get         sq (int32), cls (uint8), dist (float, m(q)): one entry per voxel, x fastest; any may be NULL.
+ * icpk_esdf_get_box     the same of the sub-box lo <= (x, y, z) < hi, as icpk_tsdf_get_box's.
+ * icpk_esdf_query       THE QUERY RULE for n <= 2^24 host points; any output may be NULL.
+ * icpk_esdf_release     frees the map (ICPK_OK without one).
+ * icpk_esdf_host        host only, no context: the distance rule over host planes (params: the volume's dims and
+ *     voxel); sq, cls, dist, counts: any may be NULL.  Compiled from the header the kernels include (csrc/esdf_rule.h).
+ * icpk_esdf_query_host  host only: THE QUERY RULE over host sq and cls planes (params: dims, voxel and the origin TO
+ *     USE; esdf: max_distance gives R).
+ * ICPK_E_NOT_SET: no volume; get, get_box and query before a compute.
+ * Refusals (ICPK_E_ARG; a refused call leaves everything as it was): min_weight outside 1 .. 65535; max_distance not
+ *     finite or not > 0; R outside 1 .. ICPK_ESDF_MAX_RADIUS; an unknown flag; an empty or out-of-bounds box; NULL
+ *     coordinate arrays with n > 0; n < 0 or n > 2^24. */
+#define ICPK_ESDF_UNKNOWN_OCCUPIED 1
+#define ICPK_ESDF_MAX_RADIUS 1024
+#define ICPK_ESDF_FAR INT32_MAX
+typedef struct icpk_esdf_params {
+  int32_t min_weight; /* 1 .. 65535 (1) */
+  float max_distance; /* metres, finite and > 0 (2.0) */
+  int32_t flags;      /* ICPK_ESDF_UNKNOWN_OCCUPIED (0) */
+} icpk_esdf_params;
+void icpk_default_esdf_params(icpk_esdf_params *p);
+int icpk_esdf_compute(icpk_ctx *ctx, const icpk_esdf_params *params, int64_t counts[4]);
+int icpk_esdf_get(icpk_ctx *ctx, int32_t *sq, uint8_t *cls, float *dist);
+int icpk_esdf_get_box(icpk_ctx *ctx, const int32_t lo[3], const int32_t hi[3], int32_t *sq, uint8_t *cls, float *dist);
+int icpk_esdf_query(icpk_ctx *ctx, const float *x, const float *y, const float *z, int32_t n, float *dist, float *gx,
+                    float *gy, float *gz, uint8_t *status);
+int icpk_esdf_release(icpk_ctx *ctx);
+int icpk_esdf_host(const icpk_tsdf_params *params, const icpk_esdf_params *esdf, const float *tsdf,
+                   const uint16_t *weight, int32_t *sq, uint8_t *cls, float *dist, int64_t counts[4]);
+int icpk_esdf_query_host(const icpk_tsdf_params *params, const icpk_esdf_params *esdf, const int32_t *sq,
+                         const uint8_t *cls, const float *x, const float *y, const float *z, int32_t n, float *dist,
+                         float *gx, float *gy, float *gz, uint8_t *status);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
