@@ -48,6 +48,10 @@ COLOR_KEEP_SUMS = 1  # icpk_estimate_target_color_gradients: keep the ten sums p
 FPFH_KEEP_SPFH = 1  # ... keep the SPFH counts and m for icpk_get_spfh
 MATCH_MUTUAL = 1  # icpk_match_features: keep a pair only if each is the other's best
 GLOBAL_MAX_HYPOTHESES = 1 << 20  # icpk_register_global
+BRIEF_WORDS = 8  # K32: uint32 words per descriptor
+BRIEF_MAX_KEYPOINTS = 65536
+BRIEF_UPRIGHT = 1  # the describe calls: bin 0 everywhere
+BRIEF_MUTUAL, BRIEF_TO_CLOUDS = 1, 2  # BriefMatchParams.flags
 
 # every symbol include/icpk.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -110,6 +114,10 @@ SYMBOLS = [
     "icpk_sdf_pixels",
     "icpk_default_esdf_params", "icpk_esdf_compute", "icpk_esdf_get", "icpk_esdf_get_box", "icpk_esdf_query",
     "icpk_esdf_release", "icpk_esdf_host", "icpk_esdf_query_host",
+    "icpk_default_brief_match_params", "icpk_describe_keypoints", "icpk_describe_points", "icpk_get_descriptors",
+    "icpk_set_descriptors", "icpk_described_to_cloud", "icpk_get_descriptor_cloud_map", "icpk_match_descriptors",
+    "icpk_get_descriptor_matches", "icpk_brief_pattern", "icpk_brief_boundaries", "icpk_brief_bin",
+    "icpk_brief_describe_host", "icpk_brief_match_host",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -338,6 +346,11 @@ class IcpkError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"icpk status {code}: {msg}")
         self.code = code
+
+
+class BriefMatchParams(C.Structure):
+    """icpk_brief_match_params (K32)"""
+    _fields_ = [("max_hamming", C.c_int32), ("ratio_num", C.c_int32), ("ratio_den", C.c_int32), ("flags", C.c_int32)]
 
 
 def load():
@@ -625,6 +638,24 @@ def load():
     lib.icpk_esdf_release.argtypes = [C.c_void_p]
     lib.icpk_esdf_host.argtypes = [C.POINTER(TsdfParams), xp, fp, u16, ip, u8, fp, i64]
     lib.icpk_esdf_query_host.argtypes = [C.POINTER(TsdfParams), xp, ip, u8, fp, fp, fp, C.c_int32, fp, fp, fp, fp, u8]
+    bp, u32 = C.POINTER(BriefMatchParams), C.POINTER(C.c_uint32)
+    lib.icpk_default_brief_match_params.argtypes = [bp]
+    lib.icpk_default_brief_match_params.restype = None
+    lib.icpk_describe_keypoints.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.icpk_describe_points.argtypes = [C.c_void_p, C.c_int32, u8, C.c_int32, C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32]
+    lib.icpk_get_descriptors.argtypes = [C.c_void_p, C.c_int32, fp, u32, u8, u8, ip]
+    lib.icpk_set_descriptors.argtypes = [C.c_void_p, C.c_int32, fp, u32, u8, u8, C.c_int32]
+    lib.icpk_described_to_cloud.argtypes = [C.c_void_p, C.c_int32, u16, C.c_int32, C.c_int32, C.c_float, C.c_float, fp, fp, ip]
+    lib.icpk_get_descriptor_cloud_map.argtypes = [C.c_void_p, C.c_int32, ip, ip]
+    lib.icpk_match_descriptors.argtypes = [C.c_void_p, bp, ip]
+    lib.icpk_get_descriptor_matches.argtypes = [C.c_void_p, ip, ip, ip, ip, ip]
+    lib.icpk_brief_pattern.argtypes = [C.POINTER(C.c_int8)]
+    lib.icpk_brief_pattern.restype = None
+    lib.icpk_brief_boundaries.argtypes = [ip]
+    lib.icpk_brief_boundaries.restype = None
+    lib.icpk_brief_bin.argtypes = [C.c_int32, C.c_int32]
+    lib.icpk_brief_describe_host.argtypes = [u8, C.c_int32, C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32, u32, u8, u8]
+    lib.icpk_brief_match_host.argtypes = [u32, u8, C.c_int32, u32, u8, C.c_int32, bp, ip, ip, ip, ip, ip]
     _lib = lib
     return lib
 
@@ -1668,6 +1699,75 @@ def _query_points(points):
     if pts.ndim != 2 or pts.shape[0] != 3:
         raise ValueError("points: (3, n) expected")
     return pts
+
+
+def brief_match_params(max_hamming=48, ratio=None, mutual=True, to_clouds=False):
+    """icpk_brief_match_params: ratio None (no ratio test) or (num, den)."""
+    p = BriefMatchParams()
+    load().icpk_default_brief_match_params(C.byref(p))
+    p.max_hamming = int(max_hamming)
+    p.ratio_num, p.ratio_den = (0, 1) if ratio is None else (int(ratio[0]), int(ratio[1]))
+    p.flags = (BRIEF_MUTUAL if mutual else 0) | (BRIEF_TO_CLOUDS if to_clouds else 0)
+    return p
+
+
+def brief_pattern():
+    """icpk_brief_pattern: the committed (32, 256, 4) int8 table of THE BRIEF RULE, (ax, ay, bx, by) per bin and test."""
+    out = np.zeros((32, 256, 4), np.int8)
+    load().icpk_brief_pattern(out.ctypes.data_as(C.POINTER(C.c_int8)))
+    return out
+
+
+def brief_boundaries():
+    """icpk_brief_boundaries: the (8, 2) int32 boundary directions (x, y) of the first quadrant."""
+    out = np.zeros((8, 2), np.int32)
+    load().icpk_brief_boundaries(out.ctypes.data_as(C.POINTER(C.c_int32)))
+    return out
+
+
+def brief_bin(m10, m01):
+    """icpk_brief_bin: the orientation bin of a pair of int32 moments."""
+    return load().icpk_brief_bin(int(m10), int(m01))
+
+
+def _image_arg(img):
+    img = np.ascontiguousarray(img, np.uint8)
+    if img.ndim == 3 and img.shape[2] == 3:
+        return img, 3
+    if img.ndim == 2:
+        return img, 1
+    raise ValueError("(rows, cols, 3) BGR or (rows, cols) grey image expected")
+
+
+def brief_describe_host(img, kp_xy, upright=False):
+    """icpk_brief_describe_host (host only): (words (n, 8) uint32, bin (n,) uint8, valid (n,) uint8)."""
+    img, ch = _image_arg(img)
+    kp = np.ascontiguousarray(kp_xy, np.float32).reshape(-1, 2)
+    n = len(kp)
+    words, b, v = np.zeros((max(n, 1), 8), np.uint32), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+    u8 = C.POINTER(C.c_uint8)
+    rc = load().icpk_brief_describe_host(img.ctypes.data_as(u8), img.shape[0], img.shape[1], ch, _fp(kp), n,
+                                         BRIEF_UPRIGHT if upright else 0, words.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                         b.ctypes.data_as(u8), v.ctypes.data_as(u8))
+    if rc != OK:
+        raise IcpkError(rc, "icpk_brief_describe_host")
+    return words[:n], b[:n], v[:n]
+
+
+def brief_match_host(words_s, valid_s, words_t, valid_t, params=None, **kw):
+    """icpk_brief_match_host (host only): (src_kp, tgt_kp, H, H2) int32 arrays of the kept pairs, source order."""
+    p = params if params is not None else brief_match_params(**kw)
+    ws = np.ascontiguousarray(words_s, np.uint32).reshape(-1, 8)
+    wt = np.ascontiguousarray(words_t, np.uint32).reshape(-1, 8)
+    vs, vt = np.ascontiguousarray(valid_s, np.uint8), np.ascontiguousarray(valid_t, np.uint8)
+    out = [np.zeros(max(len(ws), 1), np.int32) for _ in range(4)]
+    m = C.c_int32(0)
+    ip, u8, u32 = C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    rc = load().icpk_brief_match_host(ws.ctypes.data_as(u32), vs.ctypes.data_as(u8), len(ws), wt.ctypes.data_as(u32),
+                                      vt.ctypes.data_as(u8), len(wt), C.byref(p), *[o.ctypes.data_as(ip) for o in out], C.byref(m))
+    if rc != OK:
+        raise IcpkError(rc, "icpk_brief_match_host")
+    return tuple(o[:m.value].copy() for o in out)
 
 
 def esdf_host(volume, tsdf, weight, params=None, **kw):

@@ -25,7 +25,7 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "kernels_pyramid_color.hip", "icpk_raycast_color.cpp", "kernels_raycast_color.hip",
            "icpk_fern.cpp", "kernels_fern.hip", "icpk_frame_view.cpp", "kernels_frame_view.hip",
            "icpk_sdf_track.cpp", "kernels_sdf_track.hip", "icpk_tsdf_apply.cpp", "kernels_tsdf_apply.hip",
-           "icpk_esdf.cpp", "kernels_esdf.hip"]
+           "icpk_esdf.cpp", "kernels_esdf.hip", "icpk_brief.cpp", "kernels_brief.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -157,6 +157,11 @@ LATER_PROGRAMS = {
     "esdf_host_sanitized": _sanitized(["icpk_esdf.cpp"], "icpk_esdf.cpp and so csrc/esdf_rule.h and tsdf_rule.h; the "
                                       "volume's refusals and the launchers come from the library; the program calls the two "
                                       "host-only entry points alone, every array allocated at exactly its size"),
+    "test_brief": _mirror("icp::Engine::describeKeypoints / describePoints / describedToCloud / matchDescriptors "
+                          "(icp_align.hpp, K32)"),
+    "brief_host_sanitized": _sanitized(["icpk_brief.cpp"], "icpk_brief.cpp and so csrc/brief_rule.h and brief_table.h; the "
+                                       "slots' plumbing and the launchers come from the library; the program calls the two "
+                                       "host-only entry points alone, every array allocated at exactly its size"),
 }
 
 # What __graft_entry__.build() builds after DEFAULT: the later rows but the sanitized diagnostics.

@@ -296,6 +296,7 @@ void icpk_destroy(icpk_ctx* ctx) {
   icpk_tsdf_free(ctx);
   icpk_frame_view_free(ctx);
   icpk_esdf_free(ctx);
+  icpk_brief_free(ctx);
   for (icpk_ctx* sl : ctx->slots) icpk_destroy(sl);  // (before the pools their loop states point into)
   ctx->slots.clear();
   for (hipStream_t st : {ctx->setup_stream[0], ctx->setup_stream[1]})

@@ -3,7 +3,8 @@
 // icpk_align.cpp: the alignment loops; icpk_batch.cpp: the frame-batch mode; icpk_frames_batch.cpp: its depth-stream
 // entry; icpk_frontend.cpp: depth images;
 // icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp, icpk_gicp.cpp,
-// icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp, icpk_posegraph.cpp, icpk_tsdf.cpp, icpk_projective.cpp, icpk_fern.cpp).  Not
+// icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp, icpk_posegraph.cpp, icpk_tsdf.cpp, icpk_projective.cpp, icpk_fern.cpp,
+// icpk_brief.cpp).  Not
 // part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -515,6 +516,12 @@ struct icpk_ctx {
   // snapshot in a state of its own, null until the first icpk_esdf_compute.  icpk_tsdf.cpp drops it (icpk_esdf_drop)
   // where the volume is created, reset, set, shifted or released; nothing else of the context reads or writes it
   struct icpk_esdf_state* esdf = nullptr;
+  // K32 (icpk_brief.cpp), behind everything older for the same reason: the two descriptor slots, the image of
+  // icpk_describe_points and the match lists, in a state of their own, null until the first describe or set call.
+  // brief_map[w]: slot w's key point -> cloud index map describes cloud w as it stands (icpk_described_to_cloud);
+  // fpfh_dropped clears it with everything else that speaks of a cloud that is being replaced
+  struct icpk_brief_state* brief = nullptr;
+  bool brief_map[2] = {false, false};
 };
 
 #define ICPK_HIP(ctx, call)                                                                      \
@@ -533,6 +540,7 @@ void icpk_tsdf_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_tsdf.cpp
 void icpk_frame_view_free(icpk_ctx* ctx);  // called by icpk_destroy (icpk_frame_view.cpp)
 void icpk_esdf_free(icpk_ctx* ctx);     // called by icpk_destroy (icpk_esdf.cpp)
 void icpk_esdf_drop(icpk_ctx* ctx);     // the distance map no longer describes the volume: its getters answer ICPK_E_NOT_SET
+void icpk_brief_free(icpk_ctx* ctx);    // called by icpk_destroy (icpk_brief.cpp)
 int icpk_comm_allreduce_device(icpk_ctx* ctx, double* dev, int n);  // in-stream sum over the ranks (icpk_comm.cpp)
 // ICPK_NN_MAP: one K9 sweep of the working source against the map into ctx->best (icpk_map.cpp); the target must be
 // the map's current lookup target
@@ -547,10 +555,11 @@ inline int fail(icpk_ctx* ctx, int code, const char* msg) {
 }
 
 // the cloud `which` (0 the uploaded source, 1 the target) or its normals have changed: K16's descriptors and matches
-// speak of what was there before
+// speak of what was there before, and so does K32's map from slot `which`'s key points into the cloud
 inline void fpfh_dropped(icpk_ctx* ctx, int which) {
   ctx->fpfh[which].have = false;
   ctx->have_matches = false;
+  ctx->brief_map[which] = false;
 }
 
 inline int hip_failure(icpk_ctx* ctx, const char* what, hipError_t e) {
@@ -647,6 +656,20 @@ int device_loop_begin(icpk_ctx* ctx, const icpk_params* p, bool throttled = fals
 void device_loop_disarm(icpk_ctx* ctx);
 int device_loop_finish(icpk_ctx* ctx, const icpk_params* p, float T_out[16], icpk_stats* stats,
                        const LoopState* h = nullptr);
+
+// ---- icpk_fast.cpp: a key-point list into a cloud (K8's icpk_detected_to_cloud, K32's icpk_described_to_cloud) ----
+// n key points kp (device, x and y floats) back-projected from the host depth image, posed and made cloud `which`, as
+// icpk_detected_to_cloud documents; map (device, n ints, or null): every key point's index in the cloud, -1 if dropped
+int keypoints_to_cloud(icpk_ctx* ctx, const float* kp, int n, const uint16_t* depth, int32_t d_rows, int32_t d_cols, float fx,
+                       float cx, const float R[9], const float t[3], int32_t which, int* map, int32_t* n_out);
+// the image and the list the last icpk_detect_fast left on the device (n < 0: none); the pointers are views
+struct FastResident {
+  const uint8_t* img;
+  int rows, cols, channels;
+  const float* kp;
+  int n;
+};
+FastResident fast_resident(const icpk_ctx* ctx);
 
 // ---- icpk_tsdf.cpp: the last ray cast as K25 reads it ----
 // the eight planes where they lie, their shape, and the camera and pose icpk_tsdf_raycast was given

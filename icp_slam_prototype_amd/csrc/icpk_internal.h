@@ -644,7 +644,7 @@ void launch_bgr_to_gray(const uint8_t* bgr, int n, uint8_t* out, hipStream_t s);
 // `pad` up to the next multiple of NN_TILE; the count to *n_dev and the mapped word *n_host (or null)
 void launch_fast_cloud(const float* kp, int n, const uint16_t* depth, int rows, int cols, float fx, float cx, const Rt& rt,
                        float* x, float* y, float* z, float* x2, float* y2, float* z2, float pad, int* n_dev, int* n_host,
-                       hipStream_t s);
+                       int* map, hipStream_t s);
 
 // kernels_map.hip -- the voxel certainty map (map.hpp, map.cpp)
 constexpr int MAP_DIM = 300;                              // map.hpp:9 MAP_HEIGHT
@@ -1154,5 +1154,36 @@ void launch_esdf_box(const EsdfBoxArgs& a, int32_t* sq_out, uint8_t* cls_out, fl
 // THE QUERY RULE for n points: xyz three planes of n floats in, out five planes of n words: dist, gx, gy, gz and the
 // status widened to an int
 void launch_esdf_query(const EsdfMap& m, const float* xyz, int n, float* out, hipStream_t s);
+
+// kernels_brief.hip -- K32, oriented BRIEF descriptors of key points and their Hamming matches (the rule is brief_rule.h)
+constexpr int BRIEF_MATCH_CHUNK = 512;  // descriptors of the scanned side per run (grid.y of the match launch)
+inline int brief_match_runs(int n_scanned) { return n_scanned < 1 ? 1 : (n_scanned + BRIEF_MATCH_CHUNK - 1) / BRIEF_MATCH_CHUNK; }
+// words [n][8], bin [n], valid [n] of the n key points kp (x, y floats) against the device image; table: BRIEF_TABLE
+void launch_brief_describe(const uint8_t* img, int rows, int cols, int channels, const float* kp, int n, int upright,
+                           const int8_t* table, uint32_t* words, uint8_t* bin, uint8_t* valid, hipStream_t s);
+struct BriefSide {
+  const uint32_t* words;
+  const uint8_t* valid;
+  int n;
+};
+// for every descriptor i of a and every run c of b: key[c a.n + i] = H << 32 | j, h2[c a.n + i] = H2 over the valid
+// descriptors of the run (j all ones: none)
+void launch_brief_match(const BriefSide& a, const BriefSide& b, unsigned long long* key, unsigned* h2, hipStream_t s);
+struct BriefFinishArgs {
+  const unsigned long long* key[2];  // [0] sources against targets, [1] targets against sources (mutual only)
+  const unsigned* h2[2];
+  int runs[2];
+  int ns, nt;
+  const uint8_t* valid_s;
+  int max_hamming, ratio_num, ratio_den, mutual;
+  const int* map_s;  // key point -> cloud index of either side, or both null
+  const int* map_t;
+  int *out_src, *out_tgt, *out_H, *out_H2;  // [ns] the kept pairs, source order
+  int *cl_src, *cl_tgt;                     // [ns] K16's list (with the maps)
+  float* cl_D;
+  int* counts;  // kept pairs, pairs in K16's list
+  int* cl_n;    // K16's count word, or null
+};
+void launch_brief_finish(const BriefFinishArgs& a, hipStream_t s);
 
 }  // namespace icpk

@@ -180,11 +180,13 @@ __global__ __launch_bounds__(256) void bgr_gray_kernel(const uint8_t* __restrict
 // icpk_backproject_keypoints (pointcloud.cpp:60-98) on the detected list, then p <- fl32(fl32(R p) + t) with K3's
 // arithmetic, compacted in list order by ONE workgroup (a frame has a few thousand key points): x / y / z and the
 // working copy x2 / y2 / z2 (or null), padded with `pad` up to the next multiple of NN_TILE.  The count goes to *n_dev
-// and, after every store, to the mapped word *n_host (or null).
+// and, after every store, to the mapped word *n_host (or null).  map (or null, K32): per key point its rank in the cloud,
+// -1 where it was dropped.
 __global__ __launch_bounds__(FT_CLOUD_THREADS) void fast_cloud_kernel(
     const float* __restrict__ kp, int n, const uint16_t* __restrict__ depth, int rows, int cols, float fx, float cx,
     const Rt rt, float* __restrict__ x, float* __restrict__ y, float* __restrict__ z, float* __restrict__ x2,
-    float* __restrict__ y2, float* __restrict__ z2, float pad, int* __restrict__ n_dev, int* __restrict__ n_host) {
+    float* __restrict__ y2, float* __restrict__ z2, float pad, int* __restrict__ n_dev, int* __restrict__ n_host,
+    int* __restrict__ map) {
   __shared__ int wcnt[FT_CLOUD_THREADS / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int off = 0;
@@ -230,6 +232,9 @@ __global__ __launch_bounds__(FT_CLOUD_THREADS) void fast_cloud_kernel(
         y2[r] = vy;
         z2[r] = vz;
       }
+      if (map) map[i] = r;
+    } else if (map && i < n) {
+      map[i] = -1;
     }
     off += total;
     __syncthreads();  // (wcnt is rewritten by the next chunk)
@@ -276,9 +281,9 @@ void launch_bgr_to_gray(const uint8_t* bgr, int n, uint8_t* out, hipStream_t s) 
 
 void launch_fast_cloud(const float* kp, int n, const uint16_t* depth, int rows, int cols, float fx, float cx, const Rt& rt,
                        float* x, float* y, float* z, float* x2, float* y2, float* z2, float pad, int* n_dev, int* n_host,
-                       hipStream_t s) {
+                       int* map, hipStream_t s) {
   hipLaunchKernelGGL(fast_cloud_kernel, dim3(1), dim3(FT_CLOUD_THREADS), 0, s, kp, n, depth, rows, cols, fx, cx, rt, x, y, z,
-                     x2, y2, z2, pad, n_dev, n_host);
+                     x2, y2, z2, pad, n_dev, n_host, map);
 }
 
 }  // namespace icpk

@@ -58,6 +58,12 @@ struct FeatureMatch {
   float distance;
 };
 
+// one pair of Engine::matchDescriptors: the key points' indices in their slots, the Hamming distance, and the least
+// distance to any other target descriptor (257: none)
+struct DescriptorMatch {
+  int32_t source, target, hamming, second;
+};
+
 // one candidate pose as icpk_score_poses judges it: the inliers within maxDist, the metrics of icpk_score_metrics, the
 // 6x6 information matrix of the pair (row-major; rotation vector, then translation) and the sums they are made of
 struct PoseScore {
@@ -287,6 +293,34 @@ class Engine {
   }
   int registerGlobal(const icpk_global_params& params, icpk_global_result* out) {
     return icpk_register_global(ctx_, &params, out);
+  }
+  // appearance matching of key points (include/icpk.h, K32): oriented BRIEF descriptors of the list icpk_detect_fast
+  // left on the device (describeKeypoints) or of a caller's image and key points (describePoints) into slot `which` (0
+  // the source side, 1 the target side); the slot's key points back-projected into cloud `which` (describedToCloud,
+  // returns the number of points or a negative status); and the Hamming matches of the two slots, brought to the host if
+  // asked for.  With ICPK_BRIEF_TO_CLOUDS in params.flags the pairs are also K16's match list: registerGlobal runs on them.
+  int describeKeypoints(int which, int flags = 0) { return icpk_describe_keypoints(ctx_, which, flags); }
+  int describePoints(int which, const uint8_t* image, int rows, int cols, int channels, const float* kp_xy, int n,
+                     int flags = 0) {
+    return icpk_describe_points(ctx_, which, image, rows, cols, channels, kp_xy, n, flags);
+  }
+  int describedToCloud(int which, const uint16_t* depth, int rows, int cols, float fx, float cx, const float R[9],
+                       const float t[3]) {
+    int32_t n = 0;
+    const int rc = icpk_described_to_cloud(ctx_, which, depth, rows, cols, fx, cx, R, t, &n);
+    return rc < 0 ? rc : n;
+  }
+  int matchDescriptors(const icpk_brief_match_params& params, std::vector<DescriptorMatch>* out = nullptr) {
+    int32_t m = 0;
+    int rc = icpk_match_descriptors(ctx_, &params, out ? &m : nullptr);
+    if (rc != ICPK_OK || !out) return rc;
+    const size_t cap = (size_t)m + 1;
+    std::vector<int32_t> si(cap), ti(cap), H(cap), H2(cap);
+    rc = icpk_get_descriptor_matches(ctx_, si.data(), ti.data(), H.data(), H2.data(), &m);
+    if (rc != ICPK_OK) return rc;
+    out->resize((size_t)m);
+    for (int32_t k = 0; k < m; ++k) (*out)[(size_t)k] = DescriptorMatch{si[(size_t)k], ti[(size_t)k], H[(size_t)k], H2[(size_t)k]};
+    return ICPK_OK;
   }
 
  private:

@@ -154,12 +154,9 @@ def lattice_wall(rows=60, cols=80, z=2.0, shift_px=0.5):
     return dict(source=src.astype(np.float32), target=tgt.astype(np.float32))
 
 
-def render_room_color(rows, cols, R_wc, c_w, fx=FX, cx=CX, noise_sigma=0.0, rng=None, cell=0.3):
-    """BGR colour frame of the room render_room_depth draws, registered to it pixel for pixel (same rays, same
-    surfaces; the depth camera's pinhole).  Texture for FAST: on every plane, a lattice of `cell`-metre squares, most
-    of which hold one bright rectangle on the darker plane -- isolated rectangles give L-corners (an ideal
-    checkerboard's X-junctions are no FAST corners).  The sphere is plain, the background (no surface within the depth
-    range) dark.  noise_sigma: Gaussian noise per channel, in grey levels.  Returns (rows, cols, 3) uint8."""
+def _room_surface_coords(rows, cols, R_wc, c_w, fx, cx):
+    """What render_room_depth's rays hit: (surf, su, sv) per pixel -- the surface (0 floor, 1 back wall, 2 left wall,
+    3 sphere, -1 where render_room_depth has no depth) and the surface coordinates in metres on the three planes."""
     v, u = np.mgrid[0:rows, 0:cols].astype(np.float64)
     d_cam = np.stack([(u - float(cx)) / float(fx), (v - float(cx)) / float(fx), np.ones_like(u)], -1)
     w = d_cam @ np.asarray(R_wc, np.float64).T
@@ -198,6 +195,16 @@ def render_room_color(rows, cols, R_wc, c_w, fx=FX, cx=CX, noise_sigma=0.0, rng=
     # surface coordinates (metres) of the three planes: floor (x, z), back wall (x, y), left wall (z, y)
     su = np.select([surf == 0, surf == 1, surf == 2], [p[..., 0], p[..., 0], p[..., 2]], 0.0)
     sv = np.select([surf == 0, surf == 1, surf == 2], [p[..., 2], p[..., 1], p[..., 1]], 0.0)
+    return surf, su, sv
+
+
+def render_room_color(rows, cols, R_wc, c_w, fx=FX, cx=CX, noise_sigma=0.0, rng=None, cell=0.3):
+    """BGR colour frame of the room render_room_depth draws, registered to it pixel for pixel (same rays, same
+    surfaces; the depth camera's pinhole).  Texture for FAST: on every plane, a lattice of `cell`-metre squares, most
+    of which hold one bright rectangle on the darker plane -- isolated rectangles give L-corners (an ideal
+    checkerboard's X-junctions are no FAST corners).  The sphere is plain, the background (no surface within the depth
+    range) dark.  noise_sigma: Gaussian noise per channel, in grey levels.  Returns (rows, cols, 3) uint8."""
+    surf, su, sv = _room_surface_coords(rows, cols, R_wc, c_w, fx, cx)
     iu = np.floor(su / cell).astype(np.int64)
     iv = np.floor(sv / cell).astype(np.int64)
     fu = su / cell - iu
@@ -215,6 +222,39 @@ def render_room_color(rows, cols, R_wc, c_w, fx=FX, cx=CX, noise_sigma=0.0, rng=
         img[surf == k] = base[k]
     tint = np.stack([(hsh & 0x3f), ((hsh >> 6) & 0x3f), ((hsh >> 10) & 0x3f)], -1).astype(np.float64)
     img = np.where(rect[..., None], 170.0 + tint, img)
+    if noise_sigma > 0:
+        rng = rng if rng is not None else np.random.default_rng(0)
+        img = img + rng.normal(0.0, noise_sigma, img.shape)
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+def _hash8(iu, iv, surf, octave):
+    """an 8-bit integer hash of the cell (iu, iv) of surface `surf` at octave `octave`"""
+    h = (iu * 73856093) ^ (iv * 19349663) ^ (surf.astype(np.int64) * 83492791) ^ (octave * 2654435761)
+    h = (h ^ (h >> 13)) * 1274126177
+    h = h ^ (h >> 16)
+    return (h & 0xff).astype(np.float64)
+
+
+def render_room_textured(rows, cols, R_wc, c_w, fx=FX, cx=CX, noise_sigma=0.0, rng=None):
+    """BGR colour frame of render_room_color's room under a richer texture, registered to render_room_depth in the same
+    way.  On the three planes the grey value is 20 + 0.85 (0.35 h(0.32 m) + 0.35 h(0.12 m) + 0.30 h(0.045 m)), h an
+    8-bit hash of the cell indices at that cell size, of the surface and of the octave: three octaves of piecewise
+    constant noise, so that no two corners look alike and no large area is flat (descriptors need both; the isolated
+    rectangles of render_room_color give neither).  The three channels are equal on the planes.  The sphere and the
+    background are as in render_room_color.  noise_sigma: Gaussian noise per channel, in grey levels.  Returns
+    (rows, cols, 3) uint8."""
+    surf, su, sv = _room_surface_coords(rows, cols, R_wc, c_w, fx, cx)
+    grey = np.zeros((rows, cols))
+    for octave, (cell, weight) in enumerate(((0.32, 0.35), (0.12, 0.35), (0.045, 0.30))):
+        iu = np.floor(su / cell).astype(np.int64)
+        iv = np.floor(sv / cell).astype(np.int64)
+        grey += weight * _hash8(iu, iv, surf, octave)
+    grey = 20.0 + 0.85 * grey
+    img = np.full((rows, cols, 3), 25.0)
+    img[surf == 3] = [120, 130, 140]
+    plane = (surf >= 0) & (surf <= 2)
+    img[plane] = grey[plane][:, None]
     if noise_sigma > 0:
         rng = rng if rng is not None else np.random.default_rng(0)
         img = img + rng.normal(0.0, noise_sigma, img.shape)

@@ -2260,6 +2260,94 @@ int icpk_esdf_query_host(const icpk_tsdf_params *params, const icpk_esdf_params 
                          const uint8_t *cls, const float *x, const float *y, const float *z, int32_t n, float *dist,
                          float *gx, float *gy, float *gz, uint8_t *status);
 
+/* ---- K32: oriented BRIEF descriptors of key points, Hamming matches ------------------------------------------------
+ * A key point of icpk_detect_fast has a position and a response.  These calls give it a 256-bit appearance descriptor,
+ * pair the descriptors of two frames by Hamming distance, and hand the pairs, as cloud indices, to icpk_register_global:
+ * a pose between two frames without a prior.  A context holds two descriptor SLOTS, 0 the source side, 1 the target side.
+ *
+ * THE BRIEF RULE.  Integers only (committed tables: csrc/brief_table.h, handed out by icpk_brief_pattern and
+ * icpk_brief_boundaries; stated once in csrc/brief_rule.h for the kernel and the host-only functions).
+ *   Grey       three channels: K8's (1868 b + 9617 g + 4899 r + 8192) >> 14; one channel: the byte itself.
+ *   Described  a key point (x, y) -- K8's are whole numbers; any other coordinate is rounded to nearest, ties to even,
+ *              NaN and infinities describing nothing -- is described iff B <= x < cols - B and B <= y < rows - B, B = 15.
+ *              Otherwise valid = 0, bin 0, words 0.  Entries are never dropped: descriptor k belongs to key point k.
+ *   Bin        m10 = sum x I, m01 = sum y I over the disc x^2 + y^2 <= 225 around the key point (int32).  The bin k in
+ *              0 .. 31 is the multiple of 11.25 degrees nearest to the direction (m10, m01) (x right, y down): bin k is
+ *              the arc (b_{k-1}, b_k] between the boundaries b_j = (j + 1/2) 11.25 degrees, which ARE the eight committed
+ *              integer directions and their quarter turns.  A direction exactly on b_j is in bin j, the lower one.  The
+ *              direction is turned by quarter turns into x > 0, y >= 0; there the bin is the number of boundaries (bx, by)
+ *              with (int64)bx * y - (int64)by * x > 0, plus 8 per quarter turn, mod 32.  m10 = m01 = 0: bin 0.
+ *              ICPK_BRIEF_UPRIGHT: bin 0 everywhere.
+ *   Pattern    256 tests, each a pair of offsets (a, b), a != b, every offset with x^2 + y^2 <= 169; table[k][t] =
+ *              (ax, ay, bx, by) of test t in bin k, int8, 32 x 256 x 4 bytes.  Bin 0 was drawn with icpk_set_subsample's
+ *              finaliser from a fixed seed, bin k is bin 0 turned by k 11.25 degrees and rounded into the disc
+ *              (tools/make_brief_table.py).  The table is the rule, not the tool.
+ *   Bits       S(q) = the sum of grey over the 5 x 5 box centred on q.  Bit t = S(p + a) < S(p + b) with the offsets of
+ *              the key point's bin, stored as bit t & 31 of word t >> 5.  A descriptor is ICPK_BRIEF_WORDS uint32.
+ *
+ * THE MATCH RULE.  For every valid source descriptor i: j = the valid target descriptor minimising (H, j)
+ * lexicographically, H the Hamming distance; H2 = the least distance to any OTHER valid target (257 if none).  The pair
+ * is kept iff  1. H <= max_hamming;  2. if ratio_num > 0: H * ratio_den < H2 * ratio_num (integers);  3. with
+ * ICPK_BRIEF_MUTUAL: i is, among the valid source descriptors, the one minimising (H, i) for target j.  Kept pairs come
+ * out in source order; the list is the same bytes on every run.
+ *
+ * icpk_describe_keypoints   the detected list of the last icpk_detect_fast against its image, both where they lie on the
+ *     device, into slot `which`.  Stream-ordered, no host wait.  ICPK_E_NOT_SET before a detection, or once
+ *     icpk_bgr_to_gray has overwritten the image.
+ * icpk_describe_points      the same for a caller's image (rows x cols x channels, channels 1 or 3) and n key points of
+ *     any detector (x, y floats); n = 0 is legal.
+ * icpk_get_descriptors / icpk_set_descriptors   a slot to the host (any array may be NULL; *n its size) and a stored one
+ *     back (kp_xy or bin NULL: zeros): what a keyframe store needs.  Filling a slot, by either route, drops its cloud map
+ *     and the descriptor matches.
+ * icpk_described_to_cloud   icpk_detected_to_cloud's rule applied to the slot's key points: cloud `which` becomes, bit
+ *     for bit, what icpk_detected_to_cloud would make of that list.  The map key point -> cloud index (-1 where the key
+ *     point was dropped) stays on the device (icpk_get_descriptor_cloud_map reads it).  Whatever replaces cloud `which`
+ *     afterwards drops the map, as it drops K16's descriptors.
+ * icpk_match_descriptors    THE MATCH RULE over the two slots (params NULL: the defaults); *n_out (or NULL: no host
+ *     wait) = the number of kept pairs.  With ICPK_BRIEF_TO_CLOUDS the kept pairs whose two key points both have cloud
+ *     points are also written, as cloud indices with D = (float)H, into K16's match list, so that icpk_register_global
+ *     and icpk_get_feature_matches run unchanged; without both maps ICPK_E_NOT_SET.
+ * icpk_get_descriptor_matches   (src_kp, tgt_kp, H, H2) of the kept pairs, arrays of slot 0's size; any may be NULL.
+ * icpk_brief_describe_host, icpk_brief_match_host   host only, no context: the two rules over host arrays (words, bin,
+ *     valid of n entries; the match's outputs of ns entries, any may be NULL but n_out).  icpk_brief_bin: the bin of a
+ *     pair of moments.
+ * ICPK_E_ARG: another `which`, an unknown flag, a NULL image or key-point array with n > 0, rows or cols < 1, more than
+ *     2^27 pixels, channels other than 1 or 3, n outside 0 .. ICPK_BRIEF_MAX_KEYPOINTS, max_hamming outside 0 .. 256,
+ *     ratio_num outside 0 .. 65536, ratio_den outside 1 .. 65536, a stored valid byte above 1 or bin above 31.  Outputs
+ *     are always initialised (counts to 0).  ICPK_E_NOT_SET: an empty slot. */
+#define ICPK_BRIEF_WORDS 8
+#define ICPK_BRIEF_MAX_KEYPOINTS 65536
+#define ICPK_BRIEF_UPRIGHT 1   /* flags of the describe calls */
+#define ICPK_BRIEF_MUTUAL 1    /* flags of icpk_brief_match_params */
+#define ICPK_BRIEF_TO_CLOUDS 2
+typedef struct icpk_brief_match_params {
+  int32_t max_hamming; /* 0 .. 256 (48) */
+  int32_t ratio_num;   /* 0: no ratio test (0) */
+  int32_t ratio_den;   /* >= 1 (1) */
+  int32_t flags;       /* ICPK_BRIEF_MUTUAL | ICPK_BRIEF_TO_CLOUDS (ICPK_BRIEF_MUTUAL) */
+} icpk_brief_match_params;
+void icpk_default_brief_match_params(icpk_brief_match_params *p);
+int icpk_describe_keypoints(icpk_ctx *ctx, int32_t which, int32_t flags);
+int icpk_describe_points(icpk_ctx *ctx, int32_t which, const uint8_t *image, int32_t rows, int32_t cols, int32_t channels,
+                         const float *kp_xy, int32_t n, int32_t flags);
+int icpk_get_descriptors(icpk_ctx *ctx, int32_t which, float *kp_xy, uint32_t *words, uint8_t *bin, uint8_t *valid,
+                         int32_t *n);
+int icpk_set_descriptors(icpk_ctx *ctx, int32_t which, const float *kp_xy, const uint32_t *words, const uint8_t *bin,
+                         const uint8_t *valid, int32_t n);
+int icpk_described_to_cloud(icpk_ctx *ctx, int32_t which, const uint16_t *depth, int32_t d_rows, int32_t d_cols, float fx,
+                            float cx, const float R[9], const float t[3], int32_t *n_out);
+int icpk_get_descriptor_cloud_map(icpk_ctx *ctx, int32_t which, int32_t *map, int32_t *n);
+int icpk_match_descriptors(icpk_ctx *ctx, const icpk_brief_match_params *params, int32_t *n_out);
+int icpk_get_descriptor_matches(icpk_ctx *ctx, int32_t *src_kp, int32_t *tgt_kp, int32_t *H, int32_t *H2, int32_t *n);
+void icpk_brief_pattern(int8_t *out);      /* 32 x 256 x 4 bytes */
+void icpk_brief_boundaries(int32_t *out);  /* 8 x (x, y) */
+int icpk_brief_bin(int32_t m10, int32_t m01);
+int icpk_brief_describe_host(const uint8_t *image, int32_t rows, int32_t cols, int32_t channels, const float *kp_xy,
+                             int32_t n, int32_t flags, uint32_t *words, uint8_t *bin, uint8_t *valid);
+int icpk_brief_match_host(const uint32_t *words_s, const uint8_t *valid_s, int32_t ns, const uint32_t *words_t,
+                          const uint8_t *valid_t, int32_t nt, const icpk_brief_match_params *params, int32_t *src_kp,
+                          int32_t *tgt_kp, int32_t *H, int32_t *H2, int32_t *n_out);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
