@@ -52,6 +52,7 @@ BRIEF_WORDS = 8  # K32: uint32 words per descriptor
 BRIEF_MAX_KEYPOINTS = 65536
 BRIEF_UPRIGHT = 1  # the describe calls: bin 0 everywhere
 BRIEF_MUTUAL, BRIEF_TO_CLOUDS = 1, 2  # BriefMatchParams.flags
+CLUSTER_LABELS_ONLY = 1  # icpk_cluster_dbscan (K33): compute and keep the record, leave the cloud as it is
 
 # every symbol include/icpk.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -118,6 +119,7 @@ SYMBOLS = [
     "icpk_set_descriptors", "icpk_described_to_cloud", "icpk_get_descriptor_cloud_map", "icpk_match_descriptors",
     "icpk_get_descriptor_matches", "icpk_brief_pattern", "icpk_brief_boundaries", "icpk_brief_bin",
     "icpk_brief_describe_host", "icpk_brief_match_host",
+    "icpk_cluster_dbscan", "icpk_get_clusters", "icpk_cluster_host",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -346,6 +348,12 @@ class IcpkError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"icpk status {code}: {msg}")
         self.code = code
+
+
+class ClusterParams(C.Structure):
+    """icpk_cluster_params (K33): eps and min_points of THE CLUSTER RULE, min_size / max_size / largest_only of its selection"""
+    _fields_ = [("eps", C.c_float), ("min_points", C.c_int32), ("min_size", C.c_int32), ("max_size", C.c_int32),
+                ("largest_only", C.c_int32)]
 
 
 class BriefMatchParams(C.Structure):
@@ -656,6 +664,10 @@ def load():
     lib.icpk_brief_bin.argtypes = [C.c_int32, C.c_int32]
     lib.icpk_brief_describe_host.argtypes = [u8, C.c_int32, C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32, u32, u8, u8]
     lib.icpk_brief_match_host.argtypes = [u32, u8, C.c_int32, u32, u8, C.c_int32, bp, ip, ip, ip, ip, ip]
+    cp = C.POINTER(ClusterParams)
+    lib.icpk_cluster_dbscan.argtypes = [C.c_void_p, C.c_int32, cp, C.c_int32, ip, ip, ip]
+    lib.icpk_get_clusters.argtypes = [C.c_void_p, ip, ip, ip, u8, ip, ip, ip, ip, ip]
+    lib.icpk_cluster_host.argtypes = [fp, C.c_int32, cp, ip, ip, ip, ip, u8, ip, ip, ip, ip, ip]
     _lib = lib
     return lib
 

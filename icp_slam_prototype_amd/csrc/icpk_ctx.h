@@ -4,7 +4,7 @@
 // entry; icpk_frontend.cpp: depth images;
 // icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp, icpk_gicp.cpp,
 // icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp, icpk_posegraph.cpp, icpk_tsdf.cpp, icpk_projective.cpp, icpk_fern.cpp,
-// icpk_brief.cpp).  Not
+// icpk_brief.cpp, icpk_cluster.cpp).  Not
 // part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -522,6 +522,24 @@ struct icpk_ctx {
   // fpfh_dropped clears it with everything else that speaks of a cloud that is being replaced
   struct icpk_brief_state* brief = nullptr;
   bool brief_map[2] = {false, false};
+  // K33 (icpk_cluster.cpp), behind everything older for the same reason: the record of the last icpk_cluster_dbscan
+  // (icpk_get_clusters), kept on the device until asked for, the union-find forest and the compaction's scratch, and the
+  // selected planes on their way into the cloud (the index it walks is the target's, or aux_grid for the working source)
+  icpk::DevBuf<int> cl_labels;       // [n_in]
+  icpk::DevBuf<uint8_t> cl_core;     // [n_in]
+  icpk::DevBuf<int> cl_count;        // [n_in]
+  icpk::DevBuf<int> cl_nearest;      // [n_in]
+  icpk::DevBuf<int> cl_oidx;         // [n_in]
+  icpk::DevBuf<int> cl_sizes;        // [n_clusters <= n_in]
+  icpk::DevBuf<int> cl_first;        // [n_clusters <= n_in]
+  icpk::DevBuf<int> cl_parent;       // [n_in] scratch: the forest over the core points
+  icpk::DevBuf<int> cl_cid;          // [n_in] scratch: a representative's cluster id
+  icpk::DevBuf<int> cl_bsum;         // [ceil(n_in / 1024)]
+  icpk::DevBuf<int> cl_counts;       // CL_COUNTS words: clusters, noise, kept, dropped, the error word, the largest ...
+  icpk::PinnedBuf<int> cl_counts_host;  // ... and where the host reads them
+  icpk::DevBuf<float> cl_out;        // 3 planes of n_in floats (6 with normals)
+  bool have_cl = false;              // a clustering has run: the record describes it
+  int cl_n_in = 0, cl_n_clusters = 0;
 };
 
 #define ICPK_HIP(ctx, call)                                                                      \

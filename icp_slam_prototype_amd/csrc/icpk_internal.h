@@ -1186,4 +1186,35 @@ struct BriefFinishArgs {
 };
 void launch_brief_finish(const BriefFinishArgs& a, hipStream_t s);
 
+// kernels_cluster.hip -- K33, DBSCAN clustering of an indexed cloud (icpk_cluster_dbscan; the shared parts of the rule
+// are cluster_rule.h)
+constexpr int CL_COUNTS = 8;  // words of ClusterArgs::counts (a multiple of 16 bytes, zeroed before every call)
+enum { CL_N_CLUSTERS = 0, CL_N_NOISE = 1, CL_N_OUT = 2, CL_N_DROPPED = 3, CL_ERROR = 4, CL_LARGEST = 5 };
+struct ClusterArgs {
+  GridView index;             // K1d's index of the cloud
+  const float *x, *y, *z;     // the cloud in the caller's order, n points
+  const float *nx, *ny, *nz;  // its normals, or nullptr
+  int n;
+  float eps;
+  int min_points, min_size, max_size, largest_only;
+  // the record, by original index
+  int* labels;                // [n] (the root between the flatten and the label launches)
+  uint8_t* core;              // [n]
+  int* count;                 // [n] m_i
+  int* nearest;               // [n] nearest_core
+  int* out_index;             // [n]
+  int* sizes;                 // [n_clusters <= n]
+  int* first;                 // [n_clusters <= n]
+  // scratch
+  int* parent;                // [n] the union-find forest over the core points
+  int* cid;                   // [n] a representative's cluster id
+  int* bsum;                  // [ceil(n / 1024)]
+  int* counts;                // [CL_COUNTS]: CL_*, zero before the launches
+  float *ox, *oy, *oz;        // [n_out <= n] each
+  float *onx, *ony, *onz;     // (with normals)
+};
+// every launch of one call: count, link, flatten / scan / rank / label, the largest cluster if asked for, and the
+// selection's flag / scan / emit.  n <= 0: nothing
+void launch_cluster_dbscan(const ClusterArgs& a, hipStream_t s);
+
 }  // namespace icpk

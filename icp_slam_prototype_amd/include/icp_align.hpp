@@ -322,6 +322,35 @@ class Engine {
     for (int32_t k = 0; k < m; ++k) (*out)[(size_t)k] = DescriptorMatch{si[(size_t)k], ti[(size_t)k], H[(size_t)k], H2[(size_t)k]};
     return ICPK_OK;
   }
+  // DBSCAN clustering of the working source (which = 0) or the target (1) (include/icpk.h, K33, THE CLUSTER RULE):
+  // labels every point and, unless labelsOnly, keeps the points of the clusters params selects; labelsOnly: the cloud
+  // stays as it is and only clusters() changes
+  int clusterDbscan(int which, const icpk_cluster_params& params, bool labelsOnly = false, int* n_clusters = nullptr,
+                    int* n_noise = nullptr, int* n_out = nullptr) {
+    int32_t c = 0, z = 0, o = 0;
+    const int rc = icpk_cluster_dbscan(ctx_, which, &params, labelsOnly ? ICPK_CLUSTER_LABELS_ONLY : 0, &c, &z, &o);
+    if (rc != ICPK_OK) return rc;
+    if (n_clusters) *n_clusters = c;
+    if (n_noise) *n_noise = z;
+    if (n_out) *n_out = o;
+    return rc;
+  }
+  // what the last clusterDbscan found (icpk_get_clusters)
+  struct Clusters {
+    std::vector<int32_t> labels, count, nearestCore, outIndex;  // per point
+    std::vector<uint8_t> core;
+    std::vector<int32_t> sizes, first;  // per cluster
+  };
+  int clusters(Clusters* out) {
+    int32_t n = 0, nc = 0;
+    int rc = icpk_get_clusters(ctx_, &n, &nc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc != ICPK_OK || !out) return rc;
+    out->labels.assign((size_t)n, -1), out->count.assign((size_t)n, 0), out->nearestCore.assign((size_t)n, -1);
+    out->outIndex.assign((size_t)n, -1), out->core.assign((size_t)n, 0);
+    out->sizes.assign((size_t)nc, 0), out->first.assign((size_t)nc, 0);
+    return icpk_get_clusters(ctx_, nullptr, nullptr, out->labels.data(), out->core.data(), out->count.data(),
+                             out->nearestCore.data(), out->outIndex.data(), out->sizes.data(), out->first.data());
+  }
 
  private:
   icpk_ctx* ctx_ = nullptr;

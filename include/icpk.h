@@ -2348,6 +2348,72 @@ int icpk_brief_match_host(const uint32_t *words_s, const uint8_t *valid_s, int32
                           const uint8_t *valid_t, int32_t nt, const icpk_brief_match_params *params, int32_t *src_kp,
                           int32_t *tgt_kp, int32_t *H, int32_t *H2, int32_t *n_out);
 
+/* ---- DBSCAN clustering of one of the context's clouds (K33; extension: what pcl::EuclideanClusterExtraction and
+ * Open3D's cluster_dbscan offer) ----
+ * Says which points belong together: labels every point of the working source or the target with its cluster, and --
+ * unless ICPK_CLUSTER_LABELS_ONLY -- keeps the points of the selected clusters.  A clump of stray points has neighbours,
+ * so K13's filters keep it; a cluster too small to be a surface is what this call removes.
+ *
+ * THE CLUSTER RULE.  Input: the n points of the cloud in index order; eps > 0 (float) and min_points >= 1.
+ *   distance   d(i, j) is the pair distance of icp.cpp:606-620 exactly as every NN search here evaluates it (K13's).  It
+ *              is symmetric: the float differences only change sign.  `<=` is a float compare.  A point with a non-finite
+ *              coordinate is nobody's neighbour and has none.
+ *   count      m_i = #{ finite j : d(i, j) <= eps }, i itself and duplicates included: K12's and K13's count.  A
+ *              non-finite point has m_i = 0 (and only such a point has).
+ *   core       point i is a core point iff m_i >= min_points -- the point counts itself, as in Open3D and scikit-learn.
+ *              min_points = 1 makes every finite point a core point: PCL's Euclidean clustering.
+ *   clusters   a cluster is a connected component of the core points under d <= eps.  Its representative is the smallest
+ *              index among its core points; clusters are numbered 0, 1, ... by ascending representative.
+ *   border     a finite point that is not a core point but has at least one core neighbour joins the cluster of the core
+ *              neighbour j that minimises (d(i, j), j) lexicographically -- the key (float bits << 32) | j.  A border
+ *              point never joins two clusters together.  Libraries that give a border point to whichever cluster reaches
+ *              it first depend on the order of their traversal; this rule does not, so BORDER labels may differ from
+ *              Open3D's or scikit-learn's.  The partition of the core points cannot.
+ *   noise      every other point, the non-finite ones included: label -1.  n_noise counts them all; the non-finite ones
+ *              are exactly the points with count 0.
+ *   selection  a point is kept iff its label is >= 0 and min_size <= size[label] <= max_size (max_size = 0: no upper
+ *              bound; a cluster's size counts its core and border members) and, with largest_only, its cluster is the one
+ *              of greatest size among all clusters, ties to the lower label.  Kept points keep their order and their
+ *              floats and, on the target, their normals, exactly as K13's compaction does.
+ * Everything in the record is a function of the cloud alone: the same bytes on every run, and the bytes of the numpy model
+ * (tests/cluster_model.py) and of icpk_cluster_host.  The labels of the core points of a permuted cloud are the permuted
+ * partition.
+ *
+ * icpk_cluster_dbscan   which: 0 = the working source (indexed in buffers of the call's own: the target's index is not
+ *     disturbed), 1 = the target (its own index, built if it has none and then valid for the alignment that follows).
+ *     Without ICPK_CLUSTER_LABELS_ONLY the kept points become the context's cloud exactly as after icpk_remove_outliers:
+ *     everything derived from the old cloud is dropped, the target's normals are carried.  With it nothing of the cloud,
+ *     its normals or its index changes; the record (out_index and n_out included, which then say what a replacing call
+ *     would keep) is replaced either way.  n_clusters / n_noise / n_out: any may be NULL.  One host wait, for the counts.
+ *     An empty cloud is ICPK_OK with no cluster.
+ *     ICPK_E_ARG: another `which`, an unknown flag, NULL params, a non-finite or non-positive eps, min_points < 1, a
+ *     negative min_size or max_size, max_size below min_size when not 0, largest_only other than 0 or 1 (nothing
+ *     changes); ICPK_E_NOT_SET if that cloud has not been set.
+ * icpk_get_clusters   the record of the last call (it stays on the device until asked for; this call waits).  Per point
+ *     (n_in entries): labels; core (1 / 0); count (m_i); nearest_core (i for a core point, the chosen j for a border
+ *     point, -1 for noise); out_index (the position in the selected cloud, -1 where the point was not kept).  Per cluster
+ *     (n_clusters entries): sizes; first (the representative).  Any pointer may be NULL: a first call with all arrays NULL
+ *     returns the two sizes.  ICPK_E_NOT_SET before the first icpk_cluster_dbscan.
+ * icpk_cluster_host   host only, no context: the rule as a literal O(n^2) program over points[3][n] (x, y and z planes),
+ *     with the same outputs (labels_only has no meaning here: nothing is replaced).  The per-point arrays take n entries,
+ *     sizes and first n_clusters (<= n; a call with both NULL returns it).  Any output may be NULL.  ICPK_E_ARG as above,
+ *     and for n < 0 or NULL points with n > 0. */
+#define ICPK_CLUSTER_LABELS_ONLY 1 /* flags: compute and keep the record, leave the cloud as it is */
+typedef struct icpk_cluster_params {
+  float eps;            /* finite, > 0                                            */
+  int32_t min_points;   /* >= 1: neighbours (itself included) that make a core    */
+  int32_t min_size;     /* selection: >= 0                                        */
+  int32_t max_size;     /* selection: 0 = no upper bound, else >= min_size        */
+  int32_t largest_only; /* selection: 1 = only the cluster of greatest size       */
+} icpk_cluster_params;
+int icpk_cluster_dbscan(icpk_ctx *ctx, int32_t which, const icpk_cluster_params *params, int32_t flags,
+                        int32_t *n_clusters, int32_t *n_noise, int32_t *n_out);
+int icpk_get_clusters(icpk_ctx *ctx, int32_t *n_in, int32_t *n_clusters, int32_t *labels, uint8_t *core, int32_t *count,
+                      int32_t *nearest_core, int32_t *out_index, int32_t *sizes, int32_t *first);
+int icpk_cluster_host(const float *points, int32_t n, const icpk_cluster_params *params, int32_t *n_clusters,
+                      int32_t *n_noise, int32_t *n_out, int32_t *labels, uint8_t *core, int32_t *count,
+                      int32_t *nearest_core, int32_t *out_index, int32_t *sizes, int32_t *first);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
