@@ -53,6 +53,8 @@ BRIEF_MAX_KEYPOINTS = 65536
 BRIEF_UPRIGHT = 1  # the describe calls: bin 0 everywhere
 BRIEF_MUTUAL, BRIEF_TO_CLOUDS = 1, 2  # BriefMatchParams.flags
 CLUSTER_LABELS_ONLY = 1  # icpk_cluster_dbscan (K33): compute and keep the record, leave the cloud as it is
+PLANE_LABELS_ONLY, PLANE_KEEP_INLIERS = 1, 2  # icpk_segment_planes (K34): leave the cloud as it is / select the plane points
+PLANE_MAX_HYPOTHESES, PLANE_MAX_PLANES = 65536, 16
 
 # every symbol include/icpk.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
@@ -120,6 +122,7 @@ SYMBOLS = [
     "icpk_get_descriptor_matches", "icpk_brief_pattern", "icpk_brief_boundaries", "icpk_brief_bin",
     "icpk_brief_describe_host", "icpk_brief_match_host",
     "icpk_cluster_dbscan", "icpk_get_clusters", "icpk_cluster_host",
+    "icpk_default_plane_params", "icpk_segment_planes", "icpk_get_planes", "icpk_segment_planes_host", "icpk_plane_fit_host",
 ]
 MAX_FRAME_STREAMS = 256
 
@@ -348,6 +351,13 @@ class IcpkError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"icpk status {code}: {msg}")
         self.code = code
+
+
+class PlaneParams(C.Structure):
+    """icpk_plane_params (K34): seed, t, hypotheses per round, rounds and min_inliers of THE PLANE RULE, select_plane of its
+    selection"""
+    _fields_ = [("seed", C.c_uint64), ("distance_threshold", C.c_float), ("n_hypotheses", C.c_int32), ("max_planes", C.c_int32),
+                ("min_inliers", C.c_int32), ("select_plane", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ClusterParams(C.Structure):
@@ -668,6 +678,13 @@ def load():
     lib.icpk_cluster_dbscan.argtypes = [C.c_void_p, C.c_int32, cp, C.c_int32, ip, ip, ip]
     lib.icpk_get_clusters.argtypes = [C.c_void_p, ip, ip, ip, u8, ip, ip, ip, ip, ip]
     lib.icpk_cluster_host.argtypes = [fp, C.c_int32, cp, ip, ip, ip, ip, u8, ip, ip, ip, ip, ip]
+    pp, dp = C.POINTER(PlaneParams), C.POINTER(C.c_double)
+    lib.icpk_default_plane_params.argtypes = [pp]
+    lib.icpk_default_plane_params.restype = None
+    lib.icpk_segment_planes.argtypes = [C.c_void_p, C.c_int32, pp, C.c_int32, ip, ip, ip]
+    lib.icpk_get_planes.argtypes = [C.c_void_p, ip, ip, ip, ip, dp, ip, dp]
+    lib.icpk_segment_planes_host.argtypes = [fp, C.c_int32, pp, C.c_int32, ip, ip, ip, ip, ip, dp, ip, dp]
+    lib.icpk_plane_fit_host.argtypes = [dp, C.c_int32, fp, dp, dp]
     _lib = lib
     return lib
 

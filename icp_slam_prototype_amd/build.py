@@ -26,7 +26,7 @@ SOURCES = ["icpk_api.cpp", "icpk_sweep.cpp", "icpk_align.cpp", "icpk_batch.cpp",
            "icpk_fern.cpp", "kernels_fern.hip", "icpk_frame_view.cpp", "kernels_frame_view.hip",
            "icpk_sdf_track.cpp", "kernels_sdf_track.hip", "icpk_tsdf_apply.cpp", "kernels_tsdf_apply.hip",
            "icpk_esdf.cpp", "kernels_esdf.hip", "icpk_brief.cpp", "kernels_brief.hip",
-           "icpk_cluster.cpp", "kernels_cluster.hip"]
+           "icpk_cluster.cpp", "kernels_cluster.hip", "icpk_plane.cpp", "kernels_plane.hip"]
 
 # -ffp-contract=off: the exact kernels spell out every fma they want; nothing may
 # be fused behind their back (host solve included).  No -ffast-math anywhere.
@@ -167,6 +167,10 @@ LATER_PROGRAMS = {
     "cluster_host_sanitized": _sanitized(["icpk_cluster.cpp"], "icpk_cluster.cpp and so csrc/cluster_rule.h; the context's "
                                          "plumbing and the launchers come from the library; the program calls the host-only "
                                          "entry point alone, every array allocated at exactly its size"),
+    "test_plane": _mirror("icp::Engine::segmentPlanes / planes (icp_align.hpp, K34)"),
+    "plane_host_sanitized": _sanitized(["icpk_plane.cpp"], "icpk_plane.cpp and so csrc/plane_rule.h; the context's plumbing "
+                                       "and the launchers come from the library; the program calls the host-only entry "
+                                       "points alone, every array allocated at exactly its size"),
 }
 
 # What __graft_entry__.build() builds after DEFAULT: the later rows but the sanitized diagnostics.

@@ -4,7 +4,7 @@
 // entry; icpk_frontend.cpp: depth images;
 // icpk_comm.cpp, icpk_map.cpp, icpk_fast.cpp, icpk_voxel.cpp, icpk_normals.cpp, icpk_filter.cpp, icpk_gicp.cpp,
 // icpk_score.cpp, icpk_fpfh.cpp, icpk_global.cpp, icpk_posegraph.cpp, icpk_tsdf.cpp, icpk_projective.cpp, icpk_fern.cpp,
-// icpk_brief.cpp, icpk_cluster.cpp).  Not
+// icpk_brief.cpp, icpk_cluster.cpp, icpk_plane.cpp).  Not
 // part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -540,6 +540,26 @@ struct icpk_ctx {
   icpk::DevBuf<float> cl_out;        // 3 planes of n_in floats (6 with normals)
   bool have_cl = false;              // a clustering has run: the record describes it
   int cl_n_in = 0, cl_n_clusters = 0;
+  // K34 (icpk_plane.cpp), behind everything older for the same reason: the record of the last icpk_segment_planes
+  // (icpk_get_planes), kept on the device until asked for, the rounds' scratch, and the selected planes on their way into
+  // the cloud.  No index is built or read
+  icpk::DevBuf<int> pl_labels;       // [n_in]
+  icpk::DevBuf<int> pl_oidx;         // [n_in]
+  icpk::DevBuf<float4> pl_E;         // [n_in] scratch: a round's list of open points
+  icpk::DevBuf<int> pl_bsum;         // [ceil(n_in / 1024)]
+  icpk::DevBuf<int> pl_counts;       // (PL_MAX_PLANES + 1) x PL_COUNTS words: one block per round, one for the selection ...
+  icpk::PinnedBuf<int> pl_counts_host;  // ... and where the host reads a round's
+  icpk::DevBuf<double> pl_hyp;       // [8 n_hypotheses]: a PlaneHyp is 64 bytes
+  icpk::DevBuf<int> pl_hidx;         // [3 n_hypotheses]
+  icpk::DevBuf<int> pl_hcount;       // [n_hypotheses]
+  icpk::DevBuf<double> pl_partial;   // [9][RED_MAX_BLOCKS]
+  icpk::DevBuf<int> pl_pcount;       // [RED_MAX_BLOCKS]
+  icpk::DevBuf<double> pl_model;     // [PL_MAX_PLANES][8]
+  icpk::DevBuf<int> pl_info;         // [PL_MAX_PLANES][6]
+  icpk::DevBuf<double> pl_sums;      // [PL_MAX_PLANES][9]
+  icpk::DevBuf<float> pl_out;        // 3 planes of n_in floats (6 with normals)
+  bool have_pl = false;              // a segmentation has run: the record describes it
+  int pl_n_in = 0, pl_n_planes = 0;
 };
 
 #define ICPK_HIP(ctx, call)                                                                      \

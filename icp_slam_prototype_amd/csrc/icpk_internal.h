@@ -1217,4 +1217,41 @@ struct ClusterArgs {
 // selection's flag / scan / emit.  n <= 0: nothing
 void launch_cluster_dbscan(const ClusterArgs& a, hipStream_t s);
 
+// kernels_plane.hip -- K34, RANSAC plane segmentation of a cloud (icpk_segment_planes; the rule is plane_rule.h)
+struct PlaneHyp;                 // plane_rule.h: one hypothesis, 64 bytes
+constexpr int PL_COUNTS = 8;     // words of one round's count block (PlaneArgs::counts; all blocks zeroed before a call)
+constexpr int PL_MAX_PLANES = 16;  // ICPK_PLANE_MAX_PLANES: rounds, and so count blocks but the selection's
+enum { PL_M = 0, PL_WINNER = 1, PL_RANSAC = 2, PL_FINAL = 3, PL_ACCEPTED = 4, PL_FIT = 5, PL_N_OUT = 6 };
+struct PlaneArgs {
+  const float *x, *y, *z;     // the cloud in the caller's order, n points
+  const float *nx, *ny, *nz;  // its normals, or nullptr (the selection carries them)
+  int n;
+  unsigned long long seed;
+  float t;                    // distance_threshold
+  int H, min_inliers;
+  int round;                  // r: the label this round gives, the record's slot
+  int m_bound;                // an upper bound on |E| of this round that the host knows: it sizes the launches over E
+  int keep_inliers, select_plane;  // the selection
+  int* labels;                // [n] -1, or the plane
+  int* out_index;             // [n]
+  float4* E;                  // [n] scratch: the round's list, (x, y, z, index bits)
+  int* bsum;                  // [ceil(n / 1024)]
+  int* counts;                // [PL_COUNTS] THIS round's (or the selection's) block: PL_*
+  PlaneHyp* hyp;              // [H]
+  int* hyp_idx;               // [3 H] the samples' indices in the cloud
+  int* hcount;                // [H] c_h
+  double* partial;            // [9][RED_MAX_BLOCKS] scratch of the canonical tree
+  int* pcount;                // [RED_MAX_BLOCKS]
+  double* model;              // [8] per plane
+  int* info;                  // [6] per plane: h, the three samples, the RANSAC count, the final count
+  double* sums;               // [9] per plane
+  float *ox, *oy, *oz;        // [n_out <= n] each
+  float *onx, *ony, *onz;     // (with normals)
+};
+// every launch of round a.round: E, the hypotheses, the count, the pick, the refit, the final inliers and their labels.
+// The host reads a.counts afterwards.  n <= 0: nothing
+void launch_plane_round(const PlaneArgs& a, hipStream_t s);
+// the selection's flag / scan / emit: out_index, the selected cloud, counts[PL_N_OUT].  n <= 0: nothing
+void launch_plane_select(const PlaneArgs& a, hipStream_t s);
+
 }  // namespace icpk

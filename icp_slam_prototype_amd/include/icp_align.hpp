@@ -351,6 +351,38 @@ class Engine {
     return icpk_get_clusters(ctx_, nullptr, nullptr, out->labels.data(), out->core.data(), out->count.data(),
                              out->nearestCore.data(), out->outIndex.data(), out->sizes.data(), out->first.data());
   }
+  // RANSAC plane segmentation of the working source (which = 0) or the target (1) (include/icpk.h, K34, THE PLANE
+  // RULE): labels every point with its plane and, unless labelsOnly, keeps what is left when the planes are taken out --
+  // or, with keepInliers, the points of the planes (of params.select_plane alone if >= 0); labelsOnly: the cloud stays
+  // as it is and only planes() changes
+  int segmentPlanes(int which, const icpk_plane_params& params, bool labelsOnly = false, bool keepInliers = false,
+                    int* n_planes = nullptr, int* n_unassigned = nullptr, int* n_out = nullptr) {
+    int32_t p = 0, u = 0, o = 0;
+    const int32_t flags = (labelsOnly ? ICPK_PLANE_LABELS_ONLY : 0) | (keepInliers ? ICPK_PLANE_KEEP_INLIERS : 0);
+    const int rc = icpk_segment_planes(ctx_, which, &params, flags, &p, &u, &o);
+    if (rc != ICPK_OK) return rc;
+    if (n_planes) *n_planes = p;
+    if (n_unassigned) *n_unassigned = u;
+    if (n_out) *n_out = o;
+    return rc;
+  }
+  // what the last segmentPlanes found (icpk_get_planes)
+  struct Planes {
+    std::vector<int32_t> labels, outIndex;  // per point
+    std::vector<double> model;              // per plane 8: normal, d, centre, curvature
+    std::vector<int32_t> info;              // per plane 6: hypothesis, its three samples, RANSAC count, final count
+    std::vector<double> sums;               // per plane 9
+    int count() const { return (int)(info.size() / 6); }
+  };
+  int planes(Planes* out) {
+    int32_t n = 0, np = 0;
+    int rc = icpk_get_planes(ctx_, &n, &np, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc != ICPK_OK || !out) return rc;
+    out->labels.assign((size_t)n, -1), out->outIndex.assign((size_t)n, -1);
+    out->model.assign((size_t)np * 8, 0.0), out->info.assign((size_t)np * 6, 0), out->sums.assign((size_t)np * 9, 0.0);
+    return icpk_get_planes(ctx_, nullptr, nullptr, out->labels.data(), out->outIndex.data(), out->model.data(),
+                           out->info.data(), out->sums.data());
+  }
 
  private:
   icpk_ctx* ctx_ = nullptr;

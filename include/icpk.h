@@ -2414,6 +2414,104 @@ int icpk_cluster_host(const float *points, int32_t n, const icpk_cluster_params 
                       int32_t *n_noise, int32_t *n_out, int32_t *labels, uint8_t *core, int32_t *count,
                       int32_t *nearest_core, int32_t *out_index, int32_t *sizes, int32_t *first);
 
+/* ---- RANSAC plane segmentation of one of the context's clouds (K34; extension: what Open3D's segment_plane and PCL's
+ * SACSegmentation<SACMODEL_PLANE> offer, repeated until no plane is left) ----
+ * Says which points are the floor, the wall, the table top: labels every point of the working source or the target with
+ * the plane it lies on and -- unless ICPK_PLANE_LABELS_ONLY -- keeps either what is left when the planes are taken out
+ * (the default: "remove the planes, cluster the rest", icpk_cluster_dbscan) or the points of the planes.
+ *
+ * THE PLANE RULE.  Input: the n points of the cloud in index order, as floats; distance_threshold t (float, finite,
+ * > 0); n_hypotheses H (1 .. ICPK_PLANE_MAX_HYPOTHESES); seed (uint64); max_planes P (1 .. ICPK_PLANE_MAX_PLANES);
+ * min_inliers >= 3.  Everything below is float64 unless it says otherwise; every product, sum and difference is one
+ * rounded operation in the written association, none is fused, and of libm only sqrt is used.
+ *   labels     every point starts with label -1.  A point with a non-finite coordinate is never sampled and never an
+ *              inlier: it keeps -1 and counts as dropped (it is in neither n_unassigned nor any plane).
+ *   rounds     r = 0, 1, ... while r < P.  E is the list of the finite points with label -1 in ascending index, m = |E|.
+ *              The round ends the call if m < 3 or m < min_inliers.
+ *   draws      hypothesis h = 0 .. H-1 has g = r * H + h (uint64) and draws d = 0 .. 15:
+ *              z = seed + (g + 1) * 0x9E3779B97F4A7C15 + d * 0xD1B54A32D192ED03 mod 2^64, then icpk_set_subsample's
+ *              finaliser (z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31)
+ *              and c = (uint32)(z >> 32) % m -- K16's draw.  The first three distinct c in draw order give the samples
+ *              a = E[c0], b = E[c1], c = E[c2]; fewer than three distinct values make the hypothesis invalid.
+ *   plane      u = b - a, v = c - a (differences of the widened floats); N0 = u1 v2 - u2 v1, N1 = u2 v0 - u0 v2,
+ *              N2 = u0 v1 - u1 v0; L2 = (N0 N0 + N1 N1) + N2 N2; G = ((double)t * (double)t) * L2.  The hypothesis is valid
+ *              iff L2 > 0 and G is finite.
+ *   count      for every point p of E: e_k = (double)p_k - (double)a_k, s = (N0 e0 + N1 e1) + N2 e2; p is an inlier iff
+ *              s * s <= G.  c_h is the number of inliers.  The winner is the valid h of greatest c_h, ties to the lowest
+ *              h.  No valid hypothesis, or a winning count below 3, ends the call.
+ *   refit      over the winner's inliers the nine terms e0, e1, e2, e0 e0, e0 e1, e0 e2, e1 e1, e1 e2, e2 e2 (e relative
+ *              to the winner's a) are summed through the canonical tree (ICPK_RED_THREADS / ICPK_RED_MAX_BLOCKS, the tree
+ *              of icpk_reduce) over all n points in index order; a point that is not an inlier adds nothing.  With
+ *              k = (double)count: mu_a = S_a / k and C_ab = S_ab - (S_a * S_b) / k.  The symmetric 3 x 3 C goes through a
+ *              cyclic Jacobi eigen-solve: sweeps over (p, q) = (0,1), (0,2), (1,2), at most 32 of them, ended when every
+ *              off-diagonal entry is exactly 0; a rotation skips an entry that is exactly 0 and otherwise takes
+ *              theta = (C_qq - C_pp) / (2 C_pq), root = sqrt(theta theta + 1), tan = theta < 0 ? -1 / (root - theta)
+ *              : 1 / (root + theta), cos = 1 / sqrt(tan tan + 1), sin = tan cos; C_pp -= tan C_pq, C_qq += tan C_pq,
+ *              C_pq = 0, C_rp = cos C_rp - sin C_rq and C_rq = sin C_rp + cos C_rq (old values on the right), and the same
+ *              two-column update on the rows of V, which starts as the identity.  Eigenvalues l0 <= l1 <= l2: the least
+ *              diagonal entry (the lowest axis on a tie) is l0, and the column of V at its axis, divided by its length
+ *              sqrt((v0 v0 + v1 v1) + v2 v2), is the normal.  Sign: the component of largest magnitude is made positive,
+ *              the lowest axis on a tie.  centre = (double)a + mu.  If any of these is not finite, or
+ *              l1 <= 2^-20 * l2 (the inliers lie on a line), the plane falls back to the hypothesis: normal N / sqrt(L2)
+ *              with the same sign convention, centre a, curvature 0.
+ *   final      a point of E is a final inlier iff |(n0 (p0 - c0) + n1 (p1 - c1)) + n2 (p2 - c2)| <= (double)t (p widened,
+ *              c the centre).  If there are fewer than min_inliers of them the round writes nothing and ends the call;
+ *              otherwise they get label r and the next round starts.
+ *   record     per plane eight doubles -- normal (3), d = -((n0 c0 + n1 c1) + n2 c2), centre (3), the curvature
+ *              l0 / ((l0 + l1) + l2) -- six integers -- the winning h, the three samples' indices in the cloud, the RANSAC
+ *              count, the final count -- and the nine sums.
+ *   selection  default: the finite points with label -1.  ICPK_PLANE_KEEP_INLIERS: the points with label >= 0, or with
+ *              select_plane = k >= 0 those with label k.  Kept points keep their order, their floats and, on the target,
+ *              their normals, exactly as K13's compaction does.
+ * The draws, every count, the winner, the sums' bits and -- given a plane's eight doubles -- the final mask are exact for
+ * a given order of the cloud; the fit carries the rounding of the Jacobi, which is the same function on the host and on
+ * the device (csrc/plane_rule.h).  So the record is a function of the cloud and the seed alone: the same bytes on every
+ * run, and the bytes of the numpy model (tests/plane_model.py) and of icpk_segment_planes_host.
+ *
+ * icpk_default_plane_params   seed 0, t 0.01, 256 hypotheses, 4 planes, min_inliers 1000, select_plane -1.
+ * icpk_segment_planes   which: 0 = the working source, 1 = the target; no index is built or read.  Without
+ *     ICPK_PLANE_LABELS_ONLY the selected points become the context's cloud exactly as after icpk_remove_outliers:
+ *     everything derived from the old cloud is dropped, the target's normals are carried.  With it nothing of the cloud,
+ *     its normals or its index changes; the record (out_index and n_out included, which then say what a replacing call
+ *     would keep) is replaced either way.  n_planes; n_unassigned: the finite points left with label -1; n_out: the
+ *     selected points.  Any may be NULL.  One host wait per round that runs (at most max_planes), for the round's count
+ *     block; a round the rule would end at once is not started.  An empty cloud, and a cloud with no plane, are ICPK_OK
+ *     with n_planes = 0.
+ *     ICPK_E_ARG (nothing changes): another `which`, an unknown flag, NULL params, t not finite or <= 0, n_hypotheses,
+ *     max_planes, min_inliers or select_plane (-1 .. ICPK_PLANE_MAX_PLANES - 1) out of range, select_plane >= 0 without
+ *     ICPK_PLANE_KEEP_INLIERS; ICPK_E_NOT_SET if that cloud has not been set.
+ * icpk_get_planes   the record of the last call (it stays on the device until asked for; this call waits).  Per point
+ *     (n_in entries): labels, out_index (the position in the selected cloud, -1 where the point was not selected).  Per
+ *     plane (n_planes entries): model (8 doubles), info (6 integers), sums (9 doubles).  Any pointer may be NULL: a first
+ *     call with all arrays NULL returns the two sizes.  ICPK_E_NOT_SET before the first icpk_segment_planes.
+ * icpk_segment_planes_host   host only, no context: the rule as a literal O(P H n) program over points[3][n] (x, y and
+ *     z planes) with the same outputs; of the flags only ICPK_PLANE_KEEP_INLIERS means anything here.  Any output may be
+ *     NULL.  ICPK_E_ARG as above, and for n < 0 or NULL points with n > 0.
+ * icpk_plane_fit_host   host only: the refit alone -- the nine sums, their count (>= 1), the sample a and the
+ *     hypothesis' normal N (not normalised) to the plane's eight doubles. */
+#define ICPK_PLANE_MAX_HYPOTHESES 65536
+#define ICPK_PLANE_MAX_PLANES 16
+#define ICPK_PLANE_LABELS_ONLY 1  /* flags: compute and keep the record, leave the cloud as it is */
+#define ICPK_PLANE_KEEP_INLIERS 2 /* flags: the selection keeps the plane points; default keeps the rest (planes removed) */
+typedef struct icpk_plane_params {
+  uint64_t seed;
+  float distance_threshold; /* t: finite, > 0                                        */
+  int32_t n_hypotheses;     /* H: 1 .. ICPK_PLANE_MAX_HYPOTHESES, per round          */
+  int32_t max_planes;       /* P: 1 .. ICPK_PLANE_MAX_PLANES                         */
+  int32_t min_inliers;      /* >= 3: final inliers a plane needs                     */
+  int32_t select_plane;     /* -1: all planes; k: plane k only (with KEEP_INLIERS)   */
+  int32_t reserved;         /* 0                                                     */
+} icpk_plane_params;
+void icpk_default_plane_params(icpk_plane_params *params);
+int icpk_segment_planes(icpk_ctx *ctx, int32_t which, const icpk_plane_params *params, int32_t flags, int32_t *n_planes,
+                        int32_t *n_unassigned, int32_t *n_out);
+int icpk_get_planes(icpk_ctx *ctx, int32_t *n_in, int32_t *n_planes, int32_t *labels, int32_t *out_index, double *model,
+                    int32_t *info, double *sums);
+int icpk_segment_planes_host(const float *points, int32_t n, const icpk_plane_params *params, int32_t flags,
+                             int32_t *n_planes, int32_t *n_unassigned, int32_t *n_out, int32_t *labels, int32_t *out_index,
+                             double *model, int32_t *info, double *sums);
+int icpk_plane_fit_host(const double sums[9], int32_t count, const float a[3], const double hyp_normal[3], double model[8]);
+
 /* ---- test hook ------------------------------------------------------------ */
 /* icp.cpp:606-620 distance(color_point_t, color_point_t) evaluated on the
  * device for n pairs; a and b are host xyz-SoA arrays [3][n].  Lets the parity
